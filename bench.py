@@ -26,6 +26,14 @@ One process per GPU, weak scaling (32 images per GPU), one RCCL all_gather of th
 result records per step.  Rank 0 prints ONE JSON line; `ranks_seen` in it is the size of
 the process group the timed region really ran in, and a WORLD_SIZE that is not --gpus is an
 error, never a one-GPU measurement labelled N.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the
+headline does not need: every timed step's records checked bit for bit against the serial
+one-stream flow, the per-launch roofline leg (HIP events), the conv numerics of the plan, the
+gather on its own (N > 1), the rocprofv3 traffic passes (--no-traffic drops them) and the CPU
+baseline (--no-cpu-baseline drops it).
+--dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs);
+the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -256,6 +264,26 @@ def measure_traffic(timeout_s=150, dtype="fp32"):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(path, block, dec, cfg, maps):
+    """--dump-outputs: what the last timed step handed out, as float32 / float64 .npy files in ``path``.
+      records_peaks.npy   float32 [P, 6]  image index + the joint_list row of decode.parse_image (x, y, score, id, part)
+      records_humans.npy  float64 [H, 20] image index, the 18 part assignments (-1 = none), the human score
+      records_counts.npy  float64 [N, 3]  peaks, humans and overflow flags of each image
+      paf.npy, heatmap.npy float32 NCHW   the maps the decoder read (scene + 1e-3 * net output) of this rank's images
+    ``block``: the int32 record block [N, words] the step returned (every rank's images under a collective)."""
+    os.makedirs(path, exist_ok=True)
+    recs = [dec.parse_image(r, cfg) for r in np.asarray(block)]
+    peaks = [np.column_stack([np.full(len(r["peaks"]), i, np.float32), r["peaks"]]) for i, r in enumerate(recs)]
+    humans = [np.column_stack([np.full(len(r["score"]), i, np.float64), r["parts"].astype(np.float64),
+                               r["score"].astype(np.float64)]) for i, r in enumerate(recs)]
+    counts = [(r["n_peaks"], len(r["score"]), r["flags"]) for r in recs]
+    np.save(os.path.join(path, "records_peaks.npy"), np.concatenate(peaks, 0).astype(np.float32))
+    np.save(os.path.join(path, "records_humans.npy"), np.concatenate(humans, 0).astype(np.float64))
+    np.save(os.path.join(path, "records_counts.npy"), np.asarray(counts, dtype=np.float64).reshape(-1, 3))
+    for name, t in maps.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float32))
+
+
 def stub_main(args, par):
     """TEST INFRASTRUCTURE: the contract's skeleton - one process per rank, barrier + timing of exactly --steps steps,
     max over ranks, one all_gather of the result records per step, rank 0 prints ONE line - on CPU ranks over gloo with a
@@ -302,8 +330,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and secondary figures a plain run skips: records of every timed step against the "
+                         "serial flow, roofline leg, conv numerics, gather timing, rocprofv3 traffic, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the two rocprofv3 PMC passes")
     ap.add_argument("--dtype", choices=("fp32", "bf16", "bf16x3"), default="fp32",
                     help="fp32 = BASELINE.json configs[1] (the contract, default); bf16 = the configs[2] "
                          "arithmetic (bf16 operands, fp32 accumulate); bf16x3 = split bf16 operands, 3 MFMAs per "
@@ -396,11 +429,12 @@ def main():
     recs0 = est(x, scene)
     humans_per_batch = sum(r["parts"].shape[0] for r in recs0)
     peaks_per_batch = sum(r["n_peaks"] for r in recs0)
-    # what every step has to return: the records of the SERIAL flow (one stream, forward -> blend -> decode -> D2H, nothing
-    # beside the decoder) over the same batch, taken before the timed region
-    ref_bufs = est.enqueue(x, scene)
-    ref_block = dec.fetch(ref_bufs).copy()
-    ref_mask = dec.result_mask(ref_block)
+    if args.full:
+        # what every step has to return: the records of the SERIAL flow (one stream, forward -> blend -> decode -> D2H,
+        # nothing beside the decoder) over the same batch, taken before the timed region
+        ref_bufs = est.enqueue(x, scene)
+        ref_block = dec.fetch(ref_bufs).copy()
+        ref_mask = dec.result_mask(ref_block)
     run_steps(max(args.warmup, 1))              # >= 1 untimed step: also warms the RCCL gather
 
     plan = model.plan_for(x)
@@ -408,7 +442,7 @@ def main():
     # arithmetic of the plan as rtpose_net_conv_numerics reports it (fp32: the guarded per-layer AUTO choice is the
     # library default; the estimates are those of the filters loaded above)
     numerics = None
-    if not bf16:
+    if args.full and not bf16:
         names = {0: "direct", 3: "F(2x2,3x3)", 43: "F(4x4,3x3)", 4: "F(4,7)", 6: "F(6,7)"}
         forms, worst = {}, {}
         for _, form, amp in model.conv_numerics(plan):
@@ -423,23 +457,31 @@ def main():
     torch.cuda.synchronize()
     par.barrier(dev)
     t0 = time.perf_counter()
-    kept = []
+    kept = [] if args.full else None
     bufs, host = run_steps(args.steps, kept)
     torch.cuda.synchronize()
     par.barrier(dev)
     elapsed_local = time.perf_counter() - t0
-    # every block the timed steps handed out (copied inside the region, compared here, outside it) against the serial
-    # flow's: all result words bit for bit - peak coordinates, scores, ids, part assignments, human scores
-    differing = [i for i, blk in enumerate(kept)
-                 if blk.shape != ref_block.shape or not np.array_equal(blk[ref_mask], ref_block[ref_mask])]
-    if len(kept) != args.steps or differing:
-        raise SystemExit("bench.py: rank %d: the records of %d of %d timed steps differ from the serial flow's "
-                         "(steps %s) - the measurement is void" % (rank, len(differing), len(kept), differing[:8]))
+    if args.full:
+        # every block the timed steps handed out (copied inside the region, compared here, outside it) against the
+        # serial flow's: all result words bit for bit - peak coordinates, scores, ids, part assignments, human scores
+        differing = [i for i, blk in enumerate(kept)
+                     if blk.shape != ref_block.shape or not np.array_equal(blk[ref_mask], ref_block[ref_mask])]
+        if len(kept) != args.steps or differing:
+            raise SystemExit("bench.py: rank %d: the records of %d of %d timed steps differ from the serial flow's "
+                             "(steps %s) - the measurement is void" % (rank, len(differing), len(kept), differing[:8]))
+    flags = int(np.bitwise_or.reduce(np.asarray(host).reshape(-1, bufs.words)[:, dec.RES_HEADER + 2]))
+    if flags:
+        raise SystemExit("decode tables overflowed inside the timed region (flags=%d)" % flags)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's records and the maps its decoder read (no step has run on this plan since)
+        dump_outputs(args.dump_outputs, np.asarray(host).reshape(-1, bufs.words), dec, bufs.cfg,
+                     {"paf": model.read_output(plan, 10), "heatmap": model.read_output(plan, 11)})
     elapsed = par.max_over_ranks(elapsed_local, dev)
     per_rank_s = par.all_gather_floats(elapsed_local, dev)
     ranks_seen = torch.distributed.get_world_size() if collective else 1
     gather_us = None
-    if collective:      # the exchange step on its own, after the timed region: all_gather of one step's record block
+    if args.full and collective:    # the exchange step on its own, after the timed region: all_gather of one step's block
         blk = bufs.result.view(bufs.n, bufs.words)
         torch.cuda.synchronize()
         par.barrier(dev)
@@ -454,38 +496,35 @@ def main():
     k7_ms, k7_flops, k7_exec, k7_n, k7_wino, net_ms, k7_form = 0.0, 0.0, 0.0, 0, 0, 0.0, 0
     k3_ms, k3_flops, k3_exec, k3_n, k3_form = 0.0, 0.0, 0.0, 0, 0   # the second kernel family: the 3x3 convs
     prof_steps = max(3, min(args.steps, 8))
-    lib.rtpose_net_set_profiling(plan.handle, 1)
-    step()                                      # (the first profiled forward creates the events)
-    for _ in range(prof_steps):
-        step()
-        ms, k, fl, fx, wf = C.c_float(), C.c_int(), C.c_double(), C.c_double(), C.c_int()
-        for i in range(nl):
-            lib.rtpose_net_launch_info(plan.handle, i, C.byref(ms), C.byref(k), C.byref(fl), None, 0)
-            if ms.value > 0:
-                net_ms += ms.value
-                if k.value == 7:
-                    lib.rtpose_net_launch_executed_flops(plan.handle, i, C.byref(fx), C.byref(wf))
-                    k7_ms += ms.value
-                    k7_flops += fl.value
-                    k7_exec += fx.value
-                    k7_wino += 1 if wf.value else 0
-                    k7_form = wf.value
-                    k7_n += 1
-                elif k.value == 3:
-                    lib.rtpose_net_launch_executed_flops(plan.handle, i, C.byref(fx), C.byref(wf))
-                    k3_ms += ms.value
-                    k3_flops += fl.value
-                    k3_exec += fx.value
-                    k3_form = max(k3_form, wf.value)
-                    k3_n += 1
-    lib.rtpose_net_set_profiling(plan.handle, 0)
+    if args.full:
+        lib.rtpose_net_set_profiling(plan.handle, 1)
+        step()                                      # (the first profiled forward creates the events)
+        for _ in range(prof_steps):
+            step()
+            ms, k, fl, fx, wf = C.c_float(), C.c_int(), C.c_double(), C.c_double(), C.c_int()
+            for i in range(nl):
+                lib.rtpose_net_launch_info(plan.handle, i, C.byref(ms), C.byref(k), C.byref(fl), None, 0)
+                if ms.value > 0:
+                    net_ms += ms.value
+                    if k.value == 7:
+                        lib.rtpose_net_launch_executed_flops(plan.handle, i, C.byref(fx), C.byref(wf))
+                        k7_ms += ms.value
+                        k7_flops += fl.value
+                        k7_exec += fx.value
+                        k7_wino += 1 if wf.value else 0
+                        k7_form = wf.value
+                        k7_n += 1
+                    elif k.value == 3:
+                        lib.rtpose_net_launch_executed_flops(plan.handle, i, C.byref(fx), C.byref(wf))
+                        k3_ms += ms.value
+                        k3_flops += fl.value
+                        k3_exec += fx.value
+                        k3_form = max(k3_form, wf.value)
+                        k3_n += 1
+        lib.rtpose_net_set_profiling(plan.handle, 0)
     status = model.device_status(plan) if not bf16 else 0
     if status:
         raise SystemExit("device error word %d after the run (split-tile hand-over timed out)" % status)
-
-    flags = int(np.bitwise_or.reduce(np.asarray(host).reshape(-1, bufs.words)[:, dec.RES_HEADER + 2]))
-    if flags:
-        raise SystemExit("decode tables overflowed inside the timed region (flags=%d)" % flags)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -498,10 +537,6 @@ def main():
             "value": round(fps, 2), "unit": "images/s", "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "records_verified": len(kept),
-            "records_verified_note": "every timed step's record block (this rank's %d images: peaks, scores, ids, part "
-                                     "assignments, human scores) equals the serial one-stream flow's bit for bit; blocks "
-                                     "copied inside the timed region, compared after it; a difference exits non-zero" % BATCH,
             "config": {"workload": ("rtpose VGG19 368x368 batch=32 synthetic images, single MI355X, %s "
                                     "(NOT the contract config: BASELINE.json configs[1] is fp32)" % (
                                         "split bf16 operands hi+lo, 3 bf16 MFMAs per product, fp32 accumulate"
@@ -525,31 +560,38 @@ def main():
                                        "single GPU, RCCL all_gather of a world of one" if collective else "single GPU")},
             "per_rank_images_per_s": {"min": round(BATCH * args.steps / max(per_rank_s), 2),
                                       "max": round(BATCH * args.steps / min(per_rank_s), 2)},
-            "gather_us_per_step": None if gather_us is None else round(gather_us, 1),
             "multi_gpu_note": ("N > 1 has never run on hardware from this code (1-GPU leases only): unmeasured"
                                if world == 1 else "measured on %d ranks" % ranks_seen),
             "net_tflops_end_to_end": round(fps / world * GFLOP_PER_IMAGE / 1e3, 2),
-            "net_ms_per_step_events": round(net_ms / prof_steps, 3),
-            "roofline": {"bound": "mfma",
-                         "kernel": ("conv_mfma_bf16<7,16,0,..,SP=2>" if x3 else
-                                    "conv_mfma_bf16<7,32,0>" if bf16 else
-                                    "wino7_f32 (F(%d,7) Winograd along x)" % k7_form if wino7 else "conv_mfma_f32<7,16,0>") +
-                                   " (7x7 stage convs, 68% of the network's direct-convolution FLOPs)",
-                         "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": None,
-                         # `achieved` counts the ALGORITHMIC flops of the direct 7x7 sum.  In
-                         # Winograd form the kernel issues 84/294 of them (F(6,7); + group / channel padding), so
-                         # frac may exceed 1; executed_frac = issued MFMA flops / time / peak is the
-                         # matrix-pipe utilisation and cannot.
-                         "executed": round(executed, 2), "executed_frac": round(executed / peak, 4),
-                         "note": "achieved = SURVEY 8(d) direct-convolution flops / event time (the contract's "
-                                 "definition; > peak in Winograd form). executed = MFMA flops the launch issues "
-                                 "(= SQ_INSTS_MFMA x 4096, profiles/) / event time: the matrix-pipe roofline fraction. "
-                                 "Events are taken in %d extra steps after the timed region." % prof_steps,
-                         "launches_timed": k7_n,
-                         "flops_per_launch": round(k7_flops / max(k7_n, 1)),
-                         "avg_launch_ms": round(k7_ms / max(k7_n, 1), 4)},
         }
+        if args.full:
+            out.update({
+                "records_verified": len(kept),
+                "records_verified_note": "every timed step's record block (this rank's %d images: peaks, scores, ids, part "
+                                         "assignments, human scores) equals the serial one-stream flow's bit for bit; blocks "
+                                         "copied inside the timed region, compared after it; a difference exits non-zero" % BATCH,
+                "gather_us_per_step": None if gather_us is None else round(gather_us, 1),
+                "net_ms_per_step_events": round(net_ms / prof_steps, 3),
+                "roofline": {"bound": "mfma",
+                             "kernel": ("conv_mfma_bf16<7,16,0,..,SP=2>" if x3 else
+                                        "conv_mfma_bf16<7,32,0>" if bf16 else
+                                        "wino7_f32 (F(%d,7) Winograd along x)" % k7_form if wino7 else "conv_mfma_f32<7,16,0>") +
+                                       " (7x7 stage convs, 68% of the network's direct-convolution FLOPs)",
+                             "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                             "frac": round(achieved / peak, 4), "traffic": None,
+                             # `achieved` counts the ALGORITHMIC flops of the direct 7x7 sum.  In
+                             # Winograd form the kernel issues 84/294 of them (F(6,7); + group / channel padding), so
+                             # frac may exceed 1; executed_frac = issued MFMA flops / time / peak is the
+                             # matrix-pipe utilisation and cannot.
+                             "executed": round(executed, 2), "executed_frac": round(executed / peak, 4),
+                             "note": "achieved = SURVEY 8(d) direct-convolution flops / event time (the contract's "
+                                     "definition; > peak in Winograd form). executed = MFMA flops the launch issues "
+                                     "(= SQ_INSTS_MFMA x 4096, profiles/) / event time: the matrix-pipe roofline fraction. "
+                                     "Events are taken in %d extra steps after the timed region." % prof_steps,
+                             "launches_timed": k7_n,
+                             "flops_per_launch": round(k7_flops / max(k7_n, 1)),
+                             "avg_launch_ms": round(k7_ms / max(k7_n, 1), 4)},
+            })
         if k3_ms > 0:
             # not part of the contract's roofline object: the same accounting for the 3x3 convs (conv1_1 .. conv4_4_CPM
             # and the stage-1 convs), the second-largest share of the step
@@ -562,17 +604,15 @@ def main():
                 "executed_frac": round(k3_exec / (k3_ms * 1e-3) / 1e12 / peak, 4), "peak": peak, "unit": "TFLOP/s",
                 "note": "achieved = direct-convolution flops / event time; executed = MFMA flops issued (whole tiles, "
                         "36 frequencies per 4 x 4 outputs in F(4x4,3x3)) / event time"}
-        if world == 1 and not args.no_traffic and "ROCPROF" not in "".join(os.environ.keys()).upper():
+        if args.full and world == 1 and not args.no_traffic and "ROCPROF" not in "".join(os.environ.keys()).upper():
             # free this process's GPU memory pressure is irrelevant (288 GB); the child runs its own plan
             tr = measure_traffic(dtype=args.dtype)
             if tr:
                 out["roofline"]["traffic"] = round(tr["fetch_bytes"] + tr["write_bytes"])
                 out["roofline"]["traffic_detail"] = tr
                 out["roofline"]["algorithmic_bytes_per_launch"] = algorithmic_bytes_7x7(bf16 and not x3)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline((heat_np, paf_np))
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            out["cpu_baseline"] = cpu_baseline((heat_np, paf_np)) if world == 1 and not args.no_cpu_baseline else None
         print(json.dumps(out), flush=True)
     if collective:
         torch.distributed.destroy_process_group()

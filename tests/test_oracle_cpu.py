@@ -1,8 +1,9 @@
 """CPU suite: the oracle is pinned to the reference before anything trusts it.
 
 * oracle_process_paf (plain C) == golden vectors produced by the reference's own
-  pafprocess.cpp compiled unmodified, and == that compiled reference directly on
-  many random scenes when oracle/_ref is present (it is git-ignored but travels).
+  pafprocess.cpp compiled unmodified, on the stored scenes and on many random ones
+  (tests/golden/post_ref_random.npz; the compiled reference itself must reproduce
+  those vectors when oracle/_ref is present - it is git-ignored but travels).
 * oracle_nms peak positions == scipy.ndimage.maximum_filter, the call the reference
   makes (lib/utils/paf_to_pose.py:34); its bicubic refine == torch CPU bicubic
   (same A=-0.75 / half-pixel / clamped-tap definition) to ~1e-6 with equal arg-max.
@@ -16,11 +17,13 @@ import pytest
 import torch
 
 from conftest import PKG_NAME
+from oracle import make_golden_ref_random as gref
 from oracle import net_oracle
 from oracle import post_oracle as po
 
 GOLD_POST = os.path.join(os.path.dirname(__file__), "golden", "post_scenes.npz")
 GOLD_NET = os.path.join(os.path.dirname(__file__), "golden", "net_small.npz")
+GOLD_REF = os.path.join(os.path.dirname(__file__), "golden", "post_ref_random.npz")
 
 
 @pytest.fixture(scope="module")
@@ -45,18 +48,26 @@ def test_nms_oracle_reproduces_golden_joint_lists():
         assert np.array_equal(jl.view(np.uint32), z["jl%d" % i].view(np.uint32))
 
 
-@pytest.mark.skipif(not po.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+def _compiled_reference(z, key, jl, heat, paf):
+    """The compiled reference's process_paf on one scene of oracle/make_golden_ref_random.py: its stored outputs, which the
+    reference binary itself must reproduce bit for bit when oracle/_ref is present."""
+    assert str(z[key + "_digest"]) == gref.digest(jl, heat, paf), \
+        "%s: not the scene tests/golden/post_ref_random.npz was made on" % key
+    ref = {k: z[key + "_" + k] for k in gref.FIELDS}
+    if po.have_ref():
+        live = gref.reference(jl, heat, paf)
+        for k in gref.FIELDS:
+            assert live[k].dtype == ref[k].dtype and live[k].shape == ref[k].shape, (key, k)
+            assert live[k].tobytes() == ref[k].tobytes(), (key, k)
+    return ref
+
+
 def test_process_paf_oracle_vs_compiled_reference_random(synth):
-    rng = np.random.default_rng(42)
-    hits = ties = tie_free = 0
-    for trial in range(40):
-        hh, ww = int(rng.integers(12, 47)) * 8, int(rng.integers(12, 50)) * 8
-        people = synth.random_people(rng, int(rng.integers(1, 12)), hh, ww, drop_prob=float(rng.uniform(0, 0.3)))
-        heat, paf = synth.render(people, hh, ww, noise=float(rng.uniform(0.005, 0.08)), rng=rng)
-        jl = po.nms(heat)
-        if len(jl) == 0:
-            continue
-        ref = po.ref_process_paf(jl, po.upsample_nearest(heat, 8), po.upsample_nearest(paf, 8))
+    z = np.load(GOLD_REF)
+    hits = ties = tie_free = scenes = 0
+    for trial, jl, heat, paf in gref.random_scenes(synth):
+        ref = _compiled_reference(z, "random%d" % trial, jl, heat, paf)
+        scenes += 1
         # Two peaks that refine to the same pixel give exactly equal candidate scores; the
         # reference's std::sort (not stable) then decides.  libstdcxx_sort=True replays that
         # sort, so the whole restatement is compared even on such scenes ...
@@ -73,25 +84,21 @@ def test_process_paf_oracle_vs_compiled_reference_random(synth):
             assert np.array_equal(ref["parts"], contract["parts"]), trial
             assert np.array_equal(ref["score"].view(np.uint32), contract["score"].view(np.uint32)), trial
             tie_free += 1
+    assert scenes == int(z["n_random"])
     assert hits > 150 and tie_free >= 3
 
 
-@pytest.mark.skipif(not po.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_process_paf_oracle_vs_compiled_reference_junk_maps():
     """Pure-noise maps: hundreds of peaks, long candidate lists, found==2 merges."""
-    rng = np.random.default_rng(7)
+    z = np.load(GOLD_REF)
     compared = 0
-    for trial in range(6):
-        h, w = 20 + trial, 26 - trial
-        heat = rng.uniform(0, 0.35, (h, w, 19)).astype(np.float32)
-        paf = rng.uniform(-0.2, 1.0, (h, w, 38)).astype(np.float32)
-        jl = po.nms(heat)
-        ref = po.ref_process_paf(jl, po.upsample_nearest(heat, 8), po.upsample_nearest(paf, 8))
+    for trial, jl, heat, paf in gref.junk_scenes():
+        ref = _compiled_reference(z, "junk%d" % trial, jl, heat, paf)
         mine = po.process_paf(jl, paf, 8, libstdcxx_sort=True)   # long lists: introsort path
         assert np.array_equal(ref["parts"], mine["parts"])
         assert np.array_equal(ref["score"].view(np.uint32), mine["score"].view(np.uint32))
         compared += 1
-    assert compared >= 4
+    assert compared == int(z["n_junk"]) and compared >= 4
 
 
 def test_nms_peaks_match_scipy_find_peaks(synth):
