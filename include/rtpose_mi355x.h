@@ -593,8 +593,9 @@ int rtpose_net_set_persistent7(rtpose_net* net, int enable);
  * decoder of batch k under the forward of batch k + 1 - hands in the HIP event it records behind its last read: every
  * later forward of the plan waits for that event (hipStreamWaitEvent on the forward's stream) in front of its first launch
  * that writes the maps' buffer, and for nothing else (fp32: conv4_4_CPM, which writes the out1 channels of the same concat
- * buffer - the reader runs beside the trunk; bf16 / bf16x3: the last launch).  RTPOSE_GUARD_WHOLE_FORWARD=1 in the
- * environment moves the wait in FRONT of the launch list (the reader never beside this plan's kernels; 1 % slower).
+ * buffer - the reader runs beside the trunk; bf16 / bf16x3: the last launch).  RTPOSE_GUARD_WHOLE_FORWARD=1 (or
+ * RTPOSE_GUARD_FINE=0) in the environment moves the wait in FRONT of the launch list (the reader never beside this
+ * plan's kernels; 1 % slower).
  * The guard stays installed until it is replaced or removed: NULL = no guard.  The event must have been recorded and must
  * outlive the guard.  (History, DESIGN.md 3.3: a decoder built with packed-fp32 VALU instructions returned wrong limb scores
  * beside the bf16 plan's kernels; the library's decoder is built without them.) */

@@ -11,7 +11,7 @@
 //     8 planes of 16 bytes per pixel in LDS (77 KB; plane stride 617 pixels, = 1 mod 8, so the 8 lanes that store one pixel's
 //     128 bytes hit 8 different bank groups and the 32 lanes that read 32 neighbouring pixels of a plane read 512 contiguous
 //     bytes).  Two blocks fit a CU: while one is in its epilogue or parks its next halo, the other multiplies - measured
-//     (tools/exp/c64_timeline.py), the K loops of the two overlap almost always: the matrix pipe is busy at the rate the power
+//     (ee158f6:tools/exp/c64_timeline.py), the K loops of the two overlap almost always: the matrix pipe is busy at the rate the power
 //     controller allows with these operands (profiles/r04_bf16_mfma_power_cap.txt).
 //   * a wave multiplies 4 image rows x 32 pixels x 64 output channels (8 accumulators of 32 x 32): per K step of 16 channels
 //     it reads 4 pixel fragments from LDS (ds_read_b128, compile-time offsets: tap and plane are immediates) and 2 filter
@@ -33,7 +33,6 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "conv_exp.h"
 
 namespace rtpose {
 
@@ -92,17 +91,6 @@ __device__ __forceinline__ float max_with_lane_xor1(float v) {
   return r;
 }
 
-#ifdef RTPOSE_EXP_C64_TIMELINE  // developer build: wall_clock64 stamps per block and tile (tools/exp/c64_timeline.py)
-#ifndef RTPOSE_DEV_BUILD
-#error "RTPOSE_EXP_C64_TIMELINE is a developer-build experiment (tools/build_dev.sh)"
-#endif
-__device__ unsigned long long g_c64_tl[64][24][6];
-#define RTPOSE_C64_TL(i)                                                   \
-  if (tid == 0 && blockIdx.x < 64 && tl_k < 24) g_c64_tl[blockIdx.x][tl_k][i] = wall_clock64()
-#else
-#define RTPOSE_C64_TL(i)
-#endif
-
 template <bool POOL>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
   extern __shared__ __attribute__((aligned(16))) uintx4 halo[];  // [8 planes][PS pixels] x 16 bytes
@@ -138,9 +126,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
   asm volatile("" ::: "memory"); \
   __builtin_amdgcn_sched_barrier(0)
 
-#ifdef RTPOSE_EXP_C64_TIMELINE
-  int tl_k = 0;
-#endif
   // ---- halo of a tile: rows y0 - 1 .. y0 + TH, columns x0 - 1 .. x0 + TW; past the image: the zero gap row / column.  A
   // thread fetches its piece of column `ps` in all 18 rows (per-lane column offset, uniform row offset: no address
   // arithmetic per load), and the 18 x 2 pixels of the last two columns are shared out.  The loads of tile t + 1 are issued
@@ -199,7 +184,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
   __syncthreads();
 
   for (;;) {
-    RTPOSE_C64_TL(0);  // halo in LDS
     // ---- 36 K steps x (4 rows x 2 channel halves); the filters of step i + 5 and the pixels of step i + 1 are requested
     // before the 8 MFMAs of step i ----
     floatx16 acc[4][2];
@@ -231,9 +215,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
                                                                 __builtin_bit_cast(bf16x8, pf[i & 1][mf]), acc[mf][nf], 0, 0, 0);
       RTPOSE_C64_PIN();
     }
-    RTPOSE_C64_TL(1);  // this wave's K loop done
     __syncthreads();  // the halo may be overwritten
-    RTPOSE_C64_TL(2);
 
     // the next tile (the last one fetches its own halo again: no branch around the loads)
     const bool more = tile + tstep < A.tiles;
@@ -303,16 +285,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
           if (ok) *reinterpret_cast<uint4*>(op + nf * 32 + 8 * (2 * m + kh)) = make_uint4(a2[0], a2[1], b2[0], b2[1]);
         }
     }
-    RTPOSE_C64_TL(3);  // stores issued
     if (!more) break;
     park();
-    RTPOSE_C64_TL(4);  // next halo parked
     __syncthreads();
     tile += tstep;
     cur = nxt;
-#ifdef RTPOSE_EXP_C64_TIMELINE
-    ++tl_k;
-#endif
   }
 }
 
@@ -389,12 +366,6 @@ int conv_c64_bf16_launch(const rtpose_conv_desc* d, int N, int H, int W, hipStre
 }  // namespace rtpose
 
 extern "C" {
-
-#ifdef RTPOSE_EXP_C64_TIMELINE
-int rtpose_exp_c64_timeline(unsigned long long* out) {  // [64 blocks][24 tiles][6 stamps]
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rtpose::c64::g_c64_tl), sizeof(unsigned long long) * 64 * 24 * 6);
-}
-#endif
 
 int rtpose_conv3x3_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int W) {
   return rtpose::conv_c64_bf16_fits(d, ngroups, N, H, W, 0, 0);

@@ -31,7 +31,6 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "conv_exp.h"
 
 namespace rtpose {
 
@@ -68,14 +67,13 @@ struct ConvArgs {
   int tiles_x, tiles_y;
   int mtiles, ntiles, nbig;  // block-id decoding (see conv_mfma_f32)
   int ncombo, xcd_remap;
-  int dephase_mode;          // 0 off, 1: ids [n_cu, 2 n_cu), 2: odd ids (first wave of blocks only)
+  int dephase_mode;          // 0 off (every launch: the stagger measured 0 %), 1: ids [n_cu, 2 n_cu), 2: odd ids
   int dephase_cycles, n_cu;  // start-up delay that puts the 2 blocks of a CU half a tile apart
-  unsigned long long* dbg;   // RTPOSE_EXP_TIMELINE builds only: 8 x u64 per block
 };
 
 constexpr int kBM = 128;
-// 1x1 convs: CK-channel sub-chunks per LDS buffer (see conv_tile); developer knob (conv_exp.h)
-constexpr int kTB1x1 = RTPOSE_EXP_TB1X1;
+// 1x1 convs: CK-channel sub-chunks per LDS buffer (see conv_tile; 4: -20 % on the 1x1 layers)
+constexpr int kTB1x1 = 1;
 
 template <int KS>
 struct PiecesPerTap {
@@ -278,7 +276,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
   //  parking them afterwards - "load early / write late" - made the ShuffleNetV2 pointwise layers
   //  5-15 % SLOWER than the plain refill below with 4 blocks per CU hiding each other's latency.)
 
-  RTPOSE_TSTAMP(1);
   // the bias is fetched now (at the epilogue its latency would be fully exposed) and rides in
   // the accumulator: every register of a lane belongs to the lane's output channel
   floatx16 acc[MF][NF];
@@ -306,9 +303,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
   // 16-byte pieces per thread of the next chunk's halo, parked in LDS one tap later.
   // A wave issues MFMAs back to back on its own and the VALU port stays nearly idle:
   // measured, every VALU instruction in this loop costs MFMA issue slots once two
-  // waves share a SIMD (tools/exp_variants.sh drops one load stream at a time).
-  // which B register (k-group) is fetched after MFMA pair n (-1 = none)
-  // (RTPOSE_EXP_BSLOT / _B / _A / _STAGE: identity in production builds, see conv_exp.h)
+  // waves share a SIMD (measured by dropping one load stream at a time).
+  // B register (k-group) n is fetched after MFMA pair n < GB
   // memory clobber: loads/stores may not cross (IR + DAG); sched_barrier: nothing may
   // cross in the machine scheduler
 #define RTPOSE_PIN()                 \
@@ -327,17 +323,16 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
         }                                                                                      \
       }                                                                                        \
       RTPOSE_PIN();                                                                            \
-      if (RTPOSE_EXP_BSLOT(n) >= 0) {                                                          \
-        const int g2 = RTPOSE_EXP_BSLOT(n);                                                    \
-        bq[g2] += b_it_stride;                                                                 \
-        BLOAD[g2] = (RTPOSE_EXP_HALF_B && g2 >= 1) ? BCUR[g2] : RTPOSE_EXP_B(gload4(bq[g2]), BCUR[g2]); \
+      if (n < GB) {                                                                            \
+        bq[n] += b_it_stride;                                                                  \
+        BLOAD[n] = gload4(bq[n]);                                                              \
       }                                                                                        \
       if (n == 1) {                                                                            \
         if (KS == 1 || (KX) == KS - 1) { /* next tap: next sub-chunk (1x1) / next stencil row */ \
           _Pragma("unroll") for (int g2 = 0; g2 < G; ++g2)                                     \
             _Pragma("unroll") for (int fm = 0; fm < MF; ++fm) arow[g2][fm] += rowstep;         \
         }                                                                                      \
-        if (((STAGE) & RTPOSE_EXP_STAGE) != 0) {                                                     \
+        if (STAGE) {                                                                           \
           _Pragma("unroll") for (int p = 0; p < PPT; ++p) {                                    \
             smem4[hl[p]] = hv[p];                                                              \
             const int set = ps * PPT + p;                                                      \
@@ -354,7 +349,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
       }                                                                                        \
       if (n >= 2 && n - 2 < G) {                                                               \
         _Pragma("unroll") for (int fm = 0; fm < MF; ++fm)                                      \
-          ANXT[n - 2][fm] = RTPOSE_EXP_A(smem4[arow[n - 2][fm] + ((KS > 1 && (KX) + 1 < KS) ? (KX) + 1 : 0)], ACUR[n - 2][fm]); \
+          ANXT[n - 2][fm] = smem4[arow[n - 2][fm] + ((KS > 1 && (KX) + 1 < KS) ? (KX) + 1 : 0)];   \
       }                                                                                        \
       RTPOSE_PIN();                                                                            \
     }                                                                                          \
@@ -411,13 +406,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
       fill_halo(in_base + (size_t)chunk * TB * CK, nt);
       __syncthreads();
     }
-#ifdef RTPOSE_EXP_STAGGER
-    // de-phase the four waves of the block after every barrier so that their B loads
-    // do not hit the vector-memory path in the same cycles
-    if (wave == 1) __builtin_amdgcn_s_sleep(RTPOSE_EXP_STAGGER);
-    if (wave == 2) __builtin_amdgcn_s_sleep(2 * RTPOSE_EXP_STAGGER);
-    if (wave == 3) __builtin_amdgcn_s_sleep(3 * RTPOSE_EXP_STAGGER);
-#endif
     const int hb_off = NBUF == 2 ? (chunk & 1) * buf4 : 0;
     const int hn_off = NBUF == 2 ? ((chunk + 1) & 1) * buf4 : 0;
     // the last chunk re-stages itself into the idle buffer (never read): no branch
@@ -454,7 +442,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
 #undef RTPOSE_CONV_ROW
 #undef RTPOSE_CONV_STEP
 #undef RTPOSE_PIN
-  RTPOSE_TSTAMP(2);
 
   // ---- epilogue: bias (+ReLU) (+2x2 max-pool), masked stores -----------------
 #pragma unroll
@@ -544,11 +531,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
     }
   }
   }  // fn
-  RTPOSE_TSTAMP(3);
-#ifdef RTPOSE_EXP_TIMELINE
-  __builtin_amdgcn_s_waitcnt(0);
-  RTPOSE_TSTAMP(4);
-#endif
 }
 
 // Kernel: 1-D grid, block id -> (group, N tile, M tile).
@@ -563,7 +545,6 @@ template <int KS, int CK, int MODE, int NBUF, int NF>
 __global__ __launch_bounds__(256, NBUF == 1 ? 4 : 2) void conv_mfma_f32(const ConvArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int L = blockIdx.x;
-  RTPOSE_TSTAMP(0);
   // Equal tiles keep the two co-resident blocks of a CU in lock step, so their prologues
   // (first halo fill, ~2 us of exposed latency) and epilogues coincide instead of hiding
   // under each other's MFMAs.  Half of the first wave of blocks starts half a tile late.
@@ -628,10 +609,9 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, const float* __
 static int conv_ck(int cin) { return (cin % 16 == 0) ? 16 : 8; }
 
 struct ConvPlan {
-  int mode, ck, qs, hw_lds, tw_log2, tiles_x, tiles_y, grid_x, nbuf, nf;
+  int mode, ck, qs, hw_lds, tw_log2, tiles_x, tiles_y, grid_x, nbuf;
   size_t lds_bytes;
 };
-static int g_force_nbuf = 0;  // developer override (RTPOSE_CONV_NBUF=1|2)
 
 // LDS plane size: pixel count rounded so that the 4 channel-group planes of one
 // pixel land in different 16-byte bank slots on the staging writes.
@@ -654,20 +634,12 @@ static int plan_conv(const rtpose_conv_desc& d, int N, int H, int W, ConvPlan* p
   // piece sets per thread that fit the staging schedule (set s fetched at tap s, parked at s+1)
   const int max_pieces = (d.k == 1) ? PiecesPerTap<1>::value : d.k * d.k - 1;
   const int cg = (pl->ck / 4) * (d.k == 1 ? kTB1x1 : 1);  // channel-group planes per LDS buffer
-  if (!g_force_nbuf) {
-    const char* e = dev_env("RTPOSE_CONV_NBUF");
-    g_force_nbuf = e ? atoi(e) : -1;
-  }
   // 1x1 layers: single halo buffer, 4 blocks per CU (occupancy hides the refill latency of
   // these short-K GEMMs better than a second buffer: 42.7 vs 32.6 TF/s); k x k: double buffer
-  pl->nbuf = (g_force_nbuf == 1 || g_force_nbuf == 2) ? g_force_nbuf : (d.k == 1 ? 1 : 2);
+  pl->nbuf = d.k == 1 ? 1 : 2;
   // strips waste no MFMA work on tile edges but stage a longer halo than 2-D tiles on wide maps
   // (3x3 at W = 92: 2.4x the tile vs 1.4x, against 8.9 % edge waste); widest map that still strips:
-  static int strip_maxw = 0;
-  if (!strip_maxw) {
-    const char* e = dev_env("RTPOSE_CONV_STRIP_MAXW");
-    strip_maxw = e ? atoi(e) : 128;  // measured: conv3_1..3 (92 x 92) 6.70 -> 6.33 ms as strips; 184 x 184: no change
-  }
+  constexpr int strip_maxw = 128;  // measured: conv3_1..3 (92 x 92) 6.70 -> 6.33 ms as strips; 184 x 184: no change
   bool strip = (W <= strip_maxw) && !d.pool;
   if (strip) {
     const rtpose_layout& l = d.lin;
@@ -790,35 +762,13 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
   a.tiles_y = pl.tiles_y;
   // ---- 1-D grid: id order, XCD-aware remap, half-tile tail ------------------------------
   const int n_cu = device_cu_count();  // of the device this launch goes to
-  static int xcd_remap_env = -1;
-  if (xcd_remap_env < 0) {
-    const char* e = dev_env("RTPOSE_CONV_XCD_REMAP");
-    xcd_remap_env = e ? atoi(e) : 1;
-  }
   a.mtiles = pl.grid_x;
-  // 128-wide N tiles (wave tile 64 x 64, NF = 2) are available behind RTPOSE_CONV_NF=2 but
-  // NOT the default: measured on the 32 x 368 x 368 workload they help the 8-N-tile 3x3
-  // layers by ~3 % (conv4_1/4_2) and lose 11 % on the 7x7 stage convs (fewer, longer blocks:
-  // worse tail, and 32 MFMAs between filler slots) - 427 vs 464 img/s overall.
-  static int nf_env = 0;
-  if (!nf_env) {
-    const char* e = dev_env("RTPOSE_CONV_NF");
-    nf_env = e ? atoi(e) : 1;
-  }
-  pl.nf = (nf_env == 2 && d0.k != 1 && pl.ck == 16 && pl.nbuf == 2 && cout_pad(d0.cout) % 128 == 0) ? 2 : 1;
-  {
-    // 1x1 layers with >= 128 padded output channels: 128-wide N tiles halve the number of blocks
-    // that each re-stage the same input tile (developer A/B: RTPOSE_CONV_NF1X1=1|2)
-    static int nf1 = 0;
-    if (!nf1) {
-      const char* e = dev_env("RTPOSE_CONV_NF1X1");
-      nf1 = e ? atoi(e) : 1;
-    }
-    if (nf1 == 2 && d0.k == 1 && pl.ck == 16 && pl.nbuf == 1 && cout_pad(d0.cout) % 128 == 0) pl.nf = 2;
-  }
-  a.ntiles = cout_pad(d0.cout) / (kConvBN * pl.nf);
+  // 64-wide N tiles (NF = 1).  128-wide ones (wave tile 64 x 64, NF = 2), measured on the 32 x 368 x 368 workload, help
+  // the 8-N-tile 3x3 layers by ~3 % (conv4_1/4_2) and lose 11 % on the 7x7 stage convs (fewer, longer blocks: worse
+  // tail, and 32 MFMAs between filler slots) - 427 vs 464 img/s overall.
+  a.ntiles = cout_pad(d0.cout) / kConvBN;
   a.ncombo = a.ntiles * ngroups;
-  a.xcd_remap = (xcd_remap_env != 0 && a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
+  a.xcd_remap = (a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
   const long ids = a.xcd_remap ? (long)8 * a.ncombo * ceil_div(a.mtiles, 8) : (long)a.mtiles * a.ncombo;
   if (ids > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d: grid too large");
   a.nbig = (int)ids;
@@ -831,51 +781,15 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
     const int slots = n_cu * (pl.nbuf == 1 ? 4 : 2);
     const int total = (int)ids;
     const int rem = total % slots;
-    const char* e = dev_env("RTPOSE_CONV_NO_HALF_TILES");
-    if (total > slots && rem > 0 && 2 * rem <= n_cu && !(e && e[0] == '1')) a.nbig = total - rem;
+    if (total > slots && rem > 0 && 2 * rem <= n_cu) a.nbig = total - rem;
     // small batches (e.g. the reference's own one-image-at-a-time flow): fewer tiles than
     // CUs -> every tile is split, doubling the number of busy CUs
-    if (total <= n_cu && !(e && e[0] == '1')) a.nbig = 0;
+    if (total <= n_cu) a.nbig = 0;
   }
   dim3 grid((unsigned)(a.nbig + 2 * (ids - a.nbig)), 1, 1);
-#ifdef RTPOSE_EXP_TIMELINE
-  {  // developer build: stamps of the LAST launch with kernel size RTPOSE_TIMELINE_K (default 1)
-    extern unsigned long long* g_dbg32_buf;
-    extern unsigned g_dbg32_blocks;
-    static int kk = 0;
-    if (!kk) {
-      const char* e = dev_env("RTPOSE_TIMELINE_K");
-      kk = e ? atoi(e) : 1;
-    }
-    if (!g_dbg32_buf) (void)hipMalloc(&g_dbg32_buf, (size_t)32768 * 8 * 8);
-    if (d0.k == kk && grid.x <= 32768) {
-      (void)hipMemsetAsync(g_dbg32_buf, 0, (size_t)grid.x * 64, s);
-      a.dbg = g_dbg32_buf;
-      g_dbg32_blocks = grid.x;
-    }
-  }
-#endif
-  {
-    static int dephase_env = -1;
-    if (dephase_env < 0) {
-      const char* e = dev_env("RTPOSE_CONV_DEPHASE");
-      dephase_env = e ? atoi(e) : 0;
-    }
-    a.dephase_mode = (pl.nbuf == 2 && (long)grid.x > 4L * n_cu) ? dephase_env : 0;
-    a.n_cu = n_cu;
-    // half of a co-resident pair's tile time: taps x 16 MFMAs x 64 cycles x 2 blocks / 2
-    const long taps = (long)(d0.cin / pl.ck) * d0.k * d0.k;
-    a.dephase_cycles = (int)(taps * 16 * 64);
-  }
-#define RTPOSE_CONV_CASE(KS_, CK_, MODE_)                                  \
-  if (d0.k == KS_ && pl.ck == CK_ && pl.mode == MODE_) {                   \
-    if (pl.nbuf == 1 && pl.nf == 2 && KS_ == 1 && CK_ == 16)                \
-      return launch_inst<KS_, CK_, MODE_, 1, (KS_ == 1 && CK_ == 16) ? 2 : 1>(a, grid, pl.lds_bytes, s); \
-    if (pl.nbuf == 1) return launch_inst<KS_, CK_, MODE_, 1, 1>(a, grid, pl.lds_bytes, s); \
-    if (pl.nf == 2 && KS_ != 1 && CK_ == 16)                               \
-      return launch_inst<KS_, CK_, MODE_, 2, (KS_ != 1 && CK_ == 16) ? 2 : 1>(a, grid, pl.lds_bytes, s); \
-    return launch_inst<KS_, CK_, MODE_, 2, 1>(a, grid, pl.lds_bytes, s);   \
-  }
+#define RTPOSE_CONV_CASE(KS_, CK_, MODE_)                \
+  if (d0.k == KS_ && pl.ck == CK_ && pl.mode == MODE_) \
+    return launch_inst<KS_, CK_, MODE_, KS_ == 1 ? 1 : 2, 1>(a, grid, pl.lds_bytes, s);
   RTPOSE_CONV_CASE(3, 8, 0)
   RTPOSE_CONV_CASE(3, 8, 1)
   RTPOSE_CONV_CASE(3, 16, 0)
@@ -891,11 +805,6 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
 #undef RTPOSE_CONV_CASE
   return fail(RTPOSE_E_INVAL, "conv2d: no kernel instance for k=%d ck=%d mode=%d", d0.k, pl.ck, pl.mode);
 }
-
-#ifdef RTPOSE_EXP_TIMELINE
-unsigned long long* g_dbg32_buf = nullptr;
-unsigned g_dbg32_blocks = 0;
-#endif
 
 int pack_weights_launch(const float* w, const float* bias, int cout, int cin_src, int k,
                         const int32_t* cin_map, int cin_packed, float* wp, float* bp, hipStream_t s) {
@@ -935,14 +844,3 @@ int rtpose_conv2d(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, v
 }
 
 }  // extern "C"
-
-#ifdef RTPOSE_EXP_TIMELINE
-extern "C" int rtpose_debug_timeline32_dump(unsigned long long* host, unsigned cap_blocks) {
-  using namespace rtpose;
-  if (!g_dbg32_buf) return 0;
-  (void)hipDeviceSynchronize();
-  const unsigned n = g_dbg32_blocks < cap_blocks ? g_dbg32_blocks : cap_blocks;
-  (void)hipMemcpy(host, g_dbg32_buf, (size_t)n * 64, hipMemcpyDeviceToHost);
-  return (int)n;
-}
-#endif

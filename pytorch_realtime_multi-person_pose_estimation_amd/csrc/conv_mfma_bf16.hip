@@ -26,7 +26,7 @@
 //    kHD taps later); the first halo's loads are issued before the block's setup math;
 //  * epilogue: the bias rides in the accumulator from the start; each wave transposes its tile
 //    through LDS and stores 16 bytes per lane.
-// Per-CU timelines (tools/timeline_bf16.py): two co-resident blocks keep the matrix pipe ~96 %
+// Per-CU timelines (ee158f6:tools/timeline_bf16.py): two co-resident blocks keep the matrix pipe ~96 %
 // busy while both are in their tap loops; what is lost is the per-block prologue (~11k cycles,
 // memory latency) and epilogue (~7k) on a 50k-cycle tile, and the tail of the last round.
 #include <hip/hip_runtime.h>
@@ -35,7 +35,6 @@
 #include <type_traits>
 
 #include "common.h"
-#include "conv_exp.h"
 
 namespace rtpose {
 
@@ -105,8 +104,8 @@ struct ConvArgs {
   int mtiles, ntiles, nbig, ncombo, xcd_remap;
   int npersist;  // strip mode: blocks [0, npersist) walk the full-tile ids L, L + npersist, ... < nbig; blocks
                  // past them are the half tiles of the tail.  == nbig: one tile per block (not persistent)
-  int dephase_cycles, n_cu;  // second-slot blocks of the first dispatch wave start this much later
-  unsigned long long* dbg;  // RTPOSE_EXP_TIMELINE builds only: 8 x u64 per block
+  int dephase_cycles, n_cu;  // second-slot blocks of the first dispatch wave start this much later (0 in every
+                             // launch: the stagger measured 0 %)
 };
 
 constexpr int kBM = 128;
@@ -130,7 +129,7 @@ __device__ __forceinline__ void decode_block_id(const ConvArgs& A, int bi, int& 
 // staging load must be able to take a full HBM/MALL miss (1-3k cycles under load) without
 // being the oldest thing a wave waits for - measured per-CU timelines showed a block that has
 // the CU to itself (its partner in prologue/epilogue, or the tail) at 55 % MFMA rate with 3.
-constexpr int kHD = RTPOSE_EXP_HD;
+constexpr int kHD = 3;
 // Epilogue slab: each wave transposes its (up to) 64 x 64 bf16 tile through LDS so that a lane
 // stores 16 bytes (8 output channels of one pixel) instead of 64 scattered 2-byte values -
 // measured, the scalar epilogue cost 25-30 % of a 7x7 layer at bf16 MFMA speed.
@@ -179,7 +178,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
   // B register ring: the tap being multiplied + RB-1 taps in flight from L2.  Two taps of
   // lead (RB = 3) left the waves waiting on vmcnt once two blocks share a CU; the narrow-N
   // arrangement (NF = 1) has the registers for four.
-  constexpr int RB = (NF == 1 && CK <= 32) ? 5 : (CK <= 32 ? RTPOSE_EXP_RB2 : 3);
+  constexpr int RB = (NF == 1 && CK <= 32) ? 5 : (CK <= 32 ? 4 : 3);
   constexpr int TAPS = KS, ROWS = KS;
 
   const int tid = threadIdx.x;
@@ -305,13 +304,11 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
   const int nx_nsets = (nx_np_total + 255) / 256;
   float4 pf[kFillDepth];
   const bool pro_fast = FIRST && NBUF == 2 && nsets <= kFillDepth;
-#ifndef RTPOSE_EXP_NO_FILL
   if (FIRST && pro_fast) {
 #pragma unroll
     for (int u = 0; u < kFillDepth; ++u)
       if (u < nsets && u * 256 + tid < np_total) pf[u] = gload4(halo_base + piece_rel(u));
   }
-#endif
 
   // ---- per-lane A fragment bases (LDS pixel index of this lane's row) ----------------
   int abase[MF];
@@ -395,8 +392,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
         if (set0 + u < nsets && (set0 + u) * 256 + tid < np_total) smem4[piece_loff(set0 + u)] = t[u];
     }
   };
-  RTPOSE_TSTAMP(6);
-#ifndef RTPOSE_EXP_NO_FILL
   if (FIRST && NBUF == 2) {  // (persistent: only the block's first tile fills its own halo; lpar == 0)
     if (pro_fast) {
 #pragma unroll
@@ -405,11 +400,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     } else {
       fill_halo(halo_base);
     }
-    RTPOSE_TSTAMP(7);
     __syncthreads();
   }
-#endif
-  RTPOSE_TSTAMP(1);
 
   floatx16 acc[MF][NF];
   if (TR) {
@@ -448,7 +440,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     return TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(wt), as_bf8(px), c, 0, 0, 0)
               : __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(px), as_bf8(wt), c, 0, 0, 0);
   };
-// (RTPOSE_EXP_B / _A / _STAGE: identity in production builds, see conv_exp.h)
 #define RTPOSE_PIN()             \
   asm volatile("" ::: "memory"); \
   __builtin_amdgcn_sched_barrier(0)
@@ -470,7 +461,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
       RTPOSE_PIN();                                                                            \
       _Pragma("unroll") for (int fn = 0; fn < NF; ++fn)                                        \
         _Pragma("unroll") for (int sp = 0; sp < SP; ++sp)                                      \
-          BLOAD[fn * G + n][sp] = RTPOSE_EXP_B(RTPOSE_BLOAD(fn, n, sp), BCUR[fn * G + n][sp]); \
+          BLOAD[fn * G + n][sp] = RTPOSE_BLOAD(fn, n, sp);                                     \
       if (n == G - 1) wso += b_it_bytes;                                                       \
       if (KS > 1) {                                                                            \
         if (n == 0 && (KX) == KS - 1) { /* next tap starts the next stencil row */             \
@@ -479,17 +470,16 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
         }                                                                                      \
         _Pragma("unroll") for (int fm = 0; fm < MF; ++fm)                                      \
           _Pragma("unroll") for (int sp = 0; sp < SP; ++sp)                                    \
-            ANXT[n][fm][sp] = RTPOSE_EXP_A(smem4[arow[n][fm] + sp * QS + (((KX) + 1 < KS) ? (KX) + 1 : 0)], \
-                                           ACUR[n][fm][sp]);                                   \
+            ANXT[n][fm][sp] = smem4[arow[n][fm] + sp * QS + (((KX) + 1 < KS) ? (KX) + 1 : 0)];   \
       }                                                                                        \
-      if (((STAGE) & RTPOSE_EXP_STAGE) != 0 && n == G - 1) {                                   \
+      if ((STAGE) && n == G - 1) {                                                             \
         smem4[hl[0]] = hv[0];                                                                  \
         _Pragma("unroll") for (int d = 0; d + 1 < kHD; ++d) {                                  \
           hv[d] = hv[d + 1];                                                                   \
           hl[d] = hl[d + 1];                                                                   \
         }                                                                                      \
         if (ps < st_nsets) { /* uniform */                                                     \
-          hv[kHD - 1] = gload4(RTPOSE_EXP_STAGE_SRC(next_base, halo_base) + piece_rel(ps));    \
+          hv[kHD - 1] = gload4(next_base + piece_rel(ps));                                     \
           hl[kHD - 1] = (tid < st_np_total - ps * 256) ? hn_off + piece_loff(ps) : dummy_loff; \
         } else {                                                                               \
           hv[kHD - 1] = make_float4(0.f, 0.f, 0.f, 0.f);                                       \
@@ -576,29 +566,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     }
     __syncthreads();
   }
-  RTPOSE_TSTAMP(2);
 #undef RTPOSE_CONV_ROW
 #undef RTPOSE_CONV_STEP
 #undef RTPOSE_PIN
 #undef RTPOSE_BLOAD
 
   // ---- epilogue: bias (+ReLU) (+2x2 max-pool), masked stores, bf16 (RNE) or fp32 ---------
-#ifdef RTPOSE_EXP_NO_STORE
-  if (A.N > 0) {  // keep the accumulators live, skip the whole epilogue
-    float t_ = 0.f;  // every accumulator stays live (else the compiler drops their MFMAs)
-#pragma unroll
-    for (int fm = 0; fm < MF; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < NF; ++fn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t_ += acc[fm][fn][r];
-    if (t_ == 12345.678f) reinterpret_cast<float*>(g.out)[0] = t_;
-    if (!has_next) return;
-  }
-  if (false) {
-#else
   {
-#endif
   unsigned short* out_h = reinterpret_cast<unsigned short*>(g.out);
   float* out_f = reinterpret_cast<float*>(g.out);
   const float relu_lo = A.relu ? 0.f : -3.0e38f;  // uniform: v = max(v, relu_lo), no select
@@ -664,12 +638,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
         }
       }
     }
-    RTPOSE_TSTAMP(3);
-#ifdef RTPOSE_EXP_TIMELINE
-    __builtin_amdgcn_s_waitcnt(0);  // stores retired (vmcnt) - how long does the ack take?
-    RTPOSE_TSTAMP(4);
-    if (A.dbg && threadIdx.x == 0) A.dbg[(size_t)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-#endif
   } else if (A.vec_store) {  // uniform
     // The chunk loop ended with a barrier: the halo buffer multiplied last is dead.  Persistent blocks
     // keep the slabs inside that one buffer (the other one already holds the next tile's halo), which is
@@ -770,12 +738,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // slab reads precede the next half's writes
     }
-    RTPOSE_TSTAMP(3);
-#ifdef RTPOSE_EXP_TIMELINE
-    __builtin_amdgcn_s_waitcnt(0);  // stores retired (vmcnt) - how long does the ack take?
-    RTPOSE_TSTAMP(4);
-    if (A.dbg && threadIdx.x == 0) A.dbg[(size_t)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-#endif
   } else {
 #pragma unroll
   for (int fn = 0; fn < NF; ++fn) {
@@ -881,7 +843,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_bf16(const ConvArgs A) {
   constexpr int MF = 4 / WM;  // block M tile = 128 pixels either way
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int L = blockIdx.x;
-  RTPOSE_TSTAMP(0);
   // The two blocks sharing a CU start together and, having equal work, stay in lock step: their
   // prologues (halo fill) and epilogues coincide and the matrix pipe idles through both (measured:
   // 13k + 9k cycles on a 96k-cycle main loop).  Blocks [n_cu, 2 n_cu) are the second slot of every
@@ -949,12 +910,7 @@ static int conv_ck(int cin, int k, int sp) {
   if (sp == 2 || cin % 32) return 16;  // split operands: 16 channels = 64 B per pixel per chunk
   // 3x3 layers with deep inputs: 64-channel chunks halve the chunk barriers (conv4_2 1089 -> 1128
   // TFLOP/s); the wide shallow ones (conv1_2, 64 channels at 368x368) lose with them (645 -> 599)
-  static int ck3 = 0;  // developer A/B: RTPOSE_BF16_CK3=32|64 forces one size for all 3x3 layers
-  if (!ck3) {
-    const char* e = dev_env("RTPOSE_BF16_CK3");
-    ck3 = e ? atoi(e) : -1;
-  }
-  if (k == 3 && cin % 64 == 0 && (ck3 == 64 || (ck3 < 0 && cin >= 256))) return 64;
+  if (k == 3 && cin % 64 == 0 && cin >= 256) return 64;
   return (k == 1 && cin % 64 == 0) ? 64 : 32;
 }
 
@@ -985,20 +941,7 @@ static int plan_conv(const rtpose_conv_desc& d, int N, int H, int W, int sp, Con
   // widest map that still uses strips (see conv_mfma.hip); measured on the 92 x 92 layers: bf16
   // 841 (tiles) vs 835 TFLOP/s (strips), bf16x3 350 vs 356 - the longer tap loop of the split form
   // amortises the strips' longer halo
-  static int strip_maxw = -1;
-  if (strip_maxw < 0) {
-    const char* e = dev_env("RTPOSE_BF16_STRIP_MAXW");
-    strip_maxw = e ? atoi(e) : 0;
-  }
-  bool strip = (W <= (strip_maxw > 0 ? strip_maxw : (sp == 2 ? 128 : 64))) && !d.pool;
-  {
-    static int force_tile = -1;  // developer A/B: RTPOSE_BF16_FORCE_TILE=k forces 2-D tiles for k x k convs
-    if (force_tile < 0) {
-      const char* e = dev_env("RTPOSE_BF16_FORCE_TILE");
-      force_tile = e ? atoi(e) : 0;
-    }
-    if (force_tile == d.k) strip = false;
-  }
+  bool strip = (W <= (sp == 2 ? 128 : 64)) && !d.pool;
   if (strip) {
     const rtpose_layout& l = d.lin;
     const int lb = (kBM - 1) + ((kBM - 1) / W + 1) * (l.ws - W) +
@@ -1126,13 +1069,8 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   {
     // 3x3 layers with 64 input channels (conv1_2, conv2_1) have their own kernel: the whole K of a tile in one LDS halo,
     // persistent blocks (conv_c64_bf16.hip)
-    static int c64_env = -1;  // developer A/B: RTPOSE_BF16_C64=0 keeps the generic kernel for them
-    if (c64_env < 0) {
-      const char* e = dev_env("RTPOSE_BF16_C64");
-      c64_env = e ? atoi(e) : 1;
-    }
-    // (it reads the packing for 32-channel chunks: what conv_ck gives these layers unless a developer build forces 64)
-    if (c64_env && conv_ck(d0.cin, d0.k, sp) == 32 && conv_c64_bf16_fits(d, ngroups, N, H, W, out_f32, split))
+    // (it reads the packing for 32-channel chunks: what conv_ck gives these layers)
+    if (conv_ck(d0.cin, d0.k, sp) == 32 && conv_c64_bf16_fits(d, ngroups, N, H, W, out_f32, split))
       return conv_c64_bf16_launch(d, N, H, W, s);
   }
   ConvPlan pl;
@@ -1150,17 +1088,7 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   for (int i = 0; i < ngroups; ++i)
     if (d[i].out_cmap || (d[i].cout % kConvBN) || (d[i].lout.cstride % (8 * sp)) || (d[i].lout.choff % (8 * sp)))
       a.vec_store = 0;
-#ifdef RTPOSE_EXP_SCALAR_STORE
-  a.vec_store = 0;
-#endif
-  {
-    static int tr_env = -1;  // developer A/B: RTPOSE_BF16_TR=0 keeps the LDS-transposing epilogue
-    if (tr_env < 0) {
-      const char* e = dev_env("RTPOSE_BF16_TR");
-      tr_env = e ? atoi(e) : 1;
-    }
-    a.tr = (a.vec_store && !d0.pool && d0.k != 1 && tr_env) ? 1 : 0;
-  }
+  a.tr = (a.vec_store && !d0.pool && d0.k != 1) ? 1 : 0;
   a.qs = pl.qs;
   a.hw_lds = pl.hw_lds;
   a.tw_log2 = pl.tw_log2;
@@ -1169,16 +1097,11 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   const int n_cu = device_cu_count();  // of the device this launch goes to
   a.mtiles = pl.grid_x;
   const int coutp = cout_pad(d0.cout);
-  // 128-channel N tiles for the k x k layers whose cout allows it: 1 x 4 waves of 128 x 32
-  // (default) or 2 x 2 waves of 64 x 64 (RTPOSE_BF16_WAVES=22, kept for A/B); else 128 x 64
-  static int waves_env = 0;
-  if (!waves_env) {
-    const char* e = dev_env("RTPOSE_BF16_WAVES");
-    waves_env = e ? atoi(e) : 14;  // 14: per-kernel-size default, 41: 1 x 4 everywhere, 22: 2 x 2 everywhere
-  }
+  // 128-channel N tiles for the k x k layers whose cout allows it: 1 x 4 waves of 128 x 32 (7x7) or 2 x 2 waves of
+  // 64 x 64 (3x3); else 128 x 64
   const bool wide = d0.k != 1 && coutp % 128 == 0;
   // measured (32 x 368 x 368): 7x7 layers 1237 (1 x 4) vs 1166 (2 x 2) TFLOP/s, 3x3 layers 786 vs 812
-  pl.wm = (wide && (waves_env == 14 ? d0.k == 7 : waves_env != 22)) ? 1 : 2;
+  pl.wm = (wide && d0.k == 7) ? 1 : 2;
   pl.nf = (wide && pl.wm == 2) ? 2 : 1;
   a.ntiles = coutp / (32 * pl.nf * (4 / pl.wm));
   a.ncombo = a.ntiles * ngroups;
@@ -1194,15 +1117,9 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
     if (total <= n_cu) a.nbig = 0;
   }
   // persistent strips: 2 blocks per CU walk the full tiles (k x k layers; the grouped convs share the
-  // input pixel pitch, which the cross-tile staging relies on); RTPOSE_BF16_PERSIST=0 (developer builds)
-  // restores one tile per block
+  // input pixel pitch, which the cross-tile staging relies on)
   a.npersist = a.nbig;
   {
-    static int persist_env = -1;
-    if (persist_env < 0) {
-      const char* e = dev_env("RTPOSE_BF16_PERSIST");
-      persist_env = e ? atoi(e) : 1;
-    }
     const int slots = (n_cu * 2) & ~7;  // multiple of 8: a block stays on its XCD's ids
     bool same_pitch = true;
     for (int i = 1; i < ngroups; ++i) same_pitch = same_pitch && d[i].lin.cstride == d0.lin.cstride && d[i].lin.lead == d0.lin.lead;
@@ -1210,34 +1127,12 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
     const int mf = pl.wm == 1 ? 4 : 2;
     const size_t half_slabs = (size_t)4 * slab_bytes(mf / 2, pl.nf, sp);
     const size_t buf_bytes = (size_t)(pl.ck / 8 * sp) * pl.qs * 16;
-    if (persist_env && pl.mode == 0 && pl.nbuf == 2 && d0.k != 1 && same_pitch && slots >= 8 && a.nbig > slots &&
+    if (pl.mode == 0 && pl.nbuf == 2 && d0.k != 1 && same_pitch && slots >= 8 && a.nbig > slots &&
         (!a.vec_store || a.tr || half_slabs <= buf_bytes))
       a.npersist = slots;
   }
   dim3 grid((unsigned)(a.npersist + 2 * (ids - a.nbig)), 1, 1);
-  {
-    static int dephase_env = -1;  // percent of one block's MFMA time; 0 = off
-    if (dephase_env < 0) {
-      const char* e = dev_env("RTPOSE_BF16_DEPHASE");
-      dephase_env = e ? atoi(e) : 0;
-    }
-    a.n_cu = n_cu;
-    // one block's matrix time with the SIMD to itself: chunks x taps x MFMAs x 32 cycles
-    const long mfma_cycles = (long)(d0.cin / pl.ck) * d0.k * d0.k * (pl.ck / 16) * 4 * 32 * (split ? 3 : 1);
-    a.dephase_cycles = (pl.nbuf == 2 && (long)grid.x > 2L * n_cu) ? (int)(mfma_cycles * dephase_env / 100) : 0;
-  }
-#ifdef RTPOSE_EXP_TIMELINE
-  {  // developer build: time stamps of the LAST 7x7 launch, dumped by rtpose_debug_timeline_dump
-    extern unsigned long long* g_dbg_buf;
-    extern unsigned g_dbg_blocks;
-    if (!g_dbg_buf) (void)hipMalloc(&g_dbg_buf, (size_t)8192 * 8 * 8);
-    if (d0.k == 7 && grid.x <= 8192) {
-      (void)hipMemsetAsync(g_dbg_buf, 0, (size_t)grid.x * 64, s);
-      a.dbg = g_dbg_buf;
-      g_dbg_blocks = grid.x;
-    }
-  }
-#endif
+  a.n_cu = n_cu;
   {
     const size_t slab = (size_t)4 * slab_bytes(pl.wm == 1 ? 4 : 2, pl.nf, sp);
     if (a.vec_store && !a.tr && pl.lds_bytes < slab) pl.lds_bytes = slab;
@@ -1245,8 +1140,8 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   if (split) {
 #define RTPOSE_CONV_CASE_X3(KS_, MODE_, NBUF_)                                                    \
   if (d0.k == KS_ && pl.mode == MODE_) {                                                          \
-    if (pl.wm == 1) return launch_inst<KS_, 16, MODE_, NBUF_, (KS_ != 1) ? 1 : 2, 1, 2>(a, grid, pl.lds_bytes, s); \
-    if (pl.nf == 2) return launch_inst<KS_, 16, MODE_, NBUF_, 2, (KS_ != 1) ? 2 : 1, 2>(a, grid, pl.lds_bytes, s); \
+    if (pl.wm == 1) return launch_inst<KS_, 16, MODE_, NBUF_, (KS_ == 7) ? 1 : 2, 1, 2>(a, grid, pl.lds_bytes, s); \
+    if (pl.nf == 2) return launch_inst<KS_, 16, MODE_, NBUF_, 2, (KS_ == 3) ? 2 : 1, 2>(a, grid, pl.lds_bytes, s); \
     return launch_inst<KS_, 16, MODE_, NBUF_, 2, 1, 2>(a, grid, pl.lds_bytes, s);                  \
   }
     RTPOSE_CONV_CASE_X3(3, 0, 2)
@@ -1260,8 +1155,8 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   }
 #define RTPOSE_CONV_CASE(KS_, CK_, MODE_, NBUF_)                                                  \
   if (d0.k == KS_ && pl.ck == CK_ && pl.mode == MODE_) {                                          \
-    if (pl.wm == 1) return launch_inst<KS_, CK_, MODE_, NBUF_, (KS_ != 1) ? 1 : 2, 1, 1>(a, grid, pl.lds_bytes, s); \
-    if (pl.nf == 2) return launch_inst<KS_, CK_, MODE_, NBUF_, 2, (KS_ != 1) ? 2 : 1, 1>(a, grid, pl.lds_bytes, s); \
+    if (pl.wm == 1) return launch_inst<KS_, CK_, MODE_, NBUF_, (KS_ == 7) ? 1 : 2, 1, 1>(a, grid, pl.lds_bytes, s); \
+    if (pl.nf == 2) return launch_inst<KS_, CK_, MODE_, NBUF_, 2, (KS_ == 3) ? 2 : 1, 1>(a, grid, pl.lds_bytes, s); \
     return launch_inst<KS_, CK_, MODE_, NBUF_, 2, 1, 1>(a, grid, pl.lds_bytes, s);                 \
   }
   RTPOSE_CONV_CASE(3, 16, 0, 2)
@@ -1283,11 +1178,6 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
 #undef RTPOSE_CONV_CASE
   return fail(RTPOSE_E_INVAL, "conv2d_bf16: no kernel instance for k=%d ck=%d mode=%d", d0.k, pl.ck, pl.mode);
 }
-
-#ifdef RTPOSE_EXP_TIMELINE
-unsigned long long* g_dbg_buf = nullptr;
-unsigned g_dbg_blocks = 0;
-#endif
 
 int pack_weights_bf16_launch(const float* w, const float* bias, int cout, int cin_src, int k,
                              const int32_t* cin_map, int cin_packed, void* wp, float* bp, int split,
@@ -1346,14 +1236,3 @@ int rtpose_conv2d_bf16(const rtpose_conv_desc* d, int ngroups, int N, int H, int
 }
 
 }  // extern "C"
-
-#ifdef RTPOSE_EXP_TIMELINE
-extern "C" int rtpose_debug_timeline_dump(unsigned long long* host, unsigned cap_blocks) {
-  using namespace rtpose;
-  if (!g_dbg_buf) return 0;
-  (void)hipDeviceSynchronize();
-  const unsigned n = g_dbg_blocks < cap_blocks ? g_dbg_blocks : cap_blocks;
-  (void)hipMemcpy(host, g_dbg_buf, (size_t)n * 64, hipMemcpyDeviceToHost);
-  return (int)n;
-}
-#endif

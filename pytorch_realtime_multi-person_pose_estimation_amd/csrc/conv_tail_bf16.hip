@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void tail_bf16_kernel(const Args A) {
 
   // ---- X tile: 64 px x 16 pieces; consecutive lanes = consecutive pieces of a pixel (256-byte runs) ----
   // (offsets, then all loads, then all LDS writes: as one loop the table read of piece i + 1 could not be moved across the LDS
-  //  write of piece i and the global round trips ran one after the other - found in the fp32 kernel, tools/exp/tail_timeline.py)
+  //  write of piece i and the global round trips ran one after the other - found in the fp32 kernel, profiles/r06_tail_timeline.txt)
   {
     constexpr int NX = BM * 16 / 256;
     int qx[NX];

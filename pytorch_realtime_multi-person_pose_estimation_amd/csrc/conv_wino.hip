@@ -35,7 +35,6 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "conv_exp.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -43,6 +42,8 @@ namespace rtpose {
 namespace wino {
 
 using namespace winoc;
+
+constexpr int W_EPI = 16;  // accumulator registers per lane that go through the output transform + stores
 
 struct Group {
   const float* in;
@@ -62,7 +63,6 @@ struct Args {
   int cin;
   int relu, pool;
   int mtiles, ntiles, ncombo, xcd_remap;
-  unsigned long long* dbg;  // RTPOSE_EXP_TIMELINE builds only: 6 tiles x 8 u64 stamps per block
   int persist;  // 1: gridDim.x persistent blocks; block p keeps (n tile, group) p % ncombo and walks every (gridDim.x / ncombo)-th m tile
 };
 
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
   //  7 % of the kernel's cycles); round 2's rotation by 16 / CG was derived for 16-lane groups and left every write
   //  2-way conflicted: 26 % (this instance) / 36 % (conv1_2) of SQ_LDS_IDX_ACTIVE.  The A reads - ds_read_b128, groups
   //  of 16 lanes that are complete residue systems modulo 16 - are conflict-free under any rotation.)
-  constexpr int SW = RTPOSE_EXP_W3_SW(CG);
+  constexpr int SW = 8 / CG;
   const int vst = (half * 8 * CG + cg) * NT + ((tl + SW * cg) % NT);
   // transform in 2 IPT groups of 16 packed VALU instructions (few, full groups: see wino_common.h): rows, then
   // columns + LDS writes; with a whole patch (IPT 2) first for fy 0, 1 and then for fy 2, 3
@@ -237,9 +237,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
   }
   __syncthreads();
 
-  [[maybe_unused]] int ti = 0;  // tile counter of this block (timeline builds)
   for (int mt = j0; mt < A.mtiles; mt += jstep) {
-  RTPOSE_TSTAMP3(ti, 0);
   const bool has_next = mt + jstep < A.mtiles;
   // (without a next tile the "next" loader re-reads this tile's first chunks: valid addresses, results never used)
   if (has_next) {
@@ -263,7 +261,6 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
       wso += bstep;
     }
   }
-  RTPOSE_TSTAMP3(ti, 1);
 
   // One step = the two frequencies 2s, 2s+1 = 8 G MFMAs on two alternating accumulators.  Between MFMA
   // pairs, in a fixed (pinned) order: the A fragments of the next step (LDS), the B fragments two steps
@@ -307,29 +304,25 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
         RTPOSE_PIN();
         if (slot < 2 * G) {  // A of the next step (the first step of a chunk is read after the barrier)
           if (s < 7)
-            a[(s + 1) & 1][slot / G][slot % G] =
-                RTPOSE_EXP_A(va[slot % G][(2 * (s + 1) + slot / G) * CG * NT], a[s & 1][slot / G][slot % G]);
+            a[(s + 1) & 1][slot / G][slot % G] = va[slot % G][(2 * (s + 1) + slot / G) * CG * NT];
         } else {             // B two steps ahead
           const int i = slot - 2 * G;
-          bs[(s + 2) & 3][i / G][i % G] =
-              RTPOSE_EXP_B(bload_f4(rw, boff, wso + ((i / G) * CG + 2 * (i % G)) * cgstep), bs[s & 3][i / G][i % G]);
+          bs[(s + 2) & 3][i / G][i % G] = bload_f4(rw, boff, wso + ((i / G) * CG + 2 * (i % G)) * cgstep);
           // (after step 5 of a tile's last chunk the ring wraps to the first steps of the next tile's chunk 0)
           if (slot == SLOTS - 1) wso = (BRING && s == 5 && chunk == nchunks - 1) ? 0u : wso + bstep;
         }
-        if (RTPOSE_EXP_STAGE) {
-          if (IPT == 1) {  // groups in the last slots of steps 0, 1; two patch loads in the last slot of steps 2..7
-            if (slot == SLOTS - 1) {
-              if (s < 2) {
-                tgroup(nbuf, s);
-              } else {
-                load_next(2 * (s - 2));
-                load_next(2 * (s - 2) + 1);
-              }
+        if (IPT == 1) {  // groups in the last slots of steps 0, 1; two patch loads in the last slot of steps 2..7
+          if (slot == SLOTS - 1) {
+            if (s < 2) {
+              tgroup(nbuf, s);
+            } else {
+              load_next(2 * (s - 2));
+              load_next(2 * (s - 2) + 1);
             }
-          } else {         // 4 groups in the middle and last slots of steps 0, 1; 16 loads in the B slots of steps 2..5
-            if (s < 2 && (slot == SLOTS / 2 - 1 || slot == SLOTS - 1)) tgroup(nbuf, 2 * s + (slot == SLOTS - 1));
-            if (s >= 2 && s < 6 && slot >= SLOTS - 4) load_next(4 * (s - 2) + slot - (SLOTS - 4));
           }
+        } else {         // 4 groups in the middle and last slots of steps 0, 1; 16 loads in the B slots of steps 2..5
+          if (s < 2 && (slot == SLOTS / 2 - 1 || slot == SLOTS - 1)) tgroup(nbuf, 2 * s + (slot == SLOTS - 1));
+          if (s >= 2 && s < 6 && slot >= SLOTS - 4) load_next(4 * (s - 2) + slot - (SLOTS - 4));
         }
         RTPOSE_PIN();
       }
@@ -337,7 +330,6 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
     __syncthreads();
     par ^= 1;
   }
-  RTPOSE_TSTAMP3(ti, 2);
   rin = rin_nx;  // the next tile becomes the current one (its chunk 0 is in V[par], its chunk 1 in flight)
   pvoff = pvoff_nx;
 
@@ -371,7 +363,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
     const unsigned cs4 = (unsigned)g.out_cstride * 4, row4 = (unsigned)g.out_ws * cs4;
     const unsigned col4 = (unsigned)ncol * 4;
 #pragma unroll
-    for (int rg = 0; rg < RTPOSE_EXP_W_EPI / 4; ++rg) {
+    for (int rg = 0; rg < W_EPI / 4; ++rg) {
       // 4 consecutive wtiles: one division pair, then +1 steps with a branch-free wrap
       int tcur = mt * NT + wm * 32 + rg * 8 + 4 * kh;
       int sn = tcur / TT, sy, sx;
@@ -419,14 +411,6 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
       }
     }
   }
-  RTPOSE_TSTAMP3(ti, 3);
-#ifdef RTPOSE_EXP_TIMELINE3
-  if (ti < 6) {  // when the stores of this tile have been acknowledged
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RTPOSE_TSTAMP3(ti, 4);
-  }
-#endif
-  ++ti;
   }  // m tiles of this block
 #undef RTPOSE_PIN
 }
@@ -437,7 +421,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
 // wino_f32, the output transform is the same expression: bit-identical results, 4x (128-column blocks) or 2x
 // (64-column blocks) as many blocks.  16-channel chunks only.
 __global__ __launch_bounds__(256, 1) void wino3s_f32(const Args A) {
-  constexpr int NT = 32, CK = 16, CG = 4, G = 2, SW = RTPOSE_EXP_W3_SW(CG);
+  constexpr int NT = 32, CK = 16, CG = 4, G = 2, SW = 8 / CG;
   constexpr int VBUF = 16 * CG * NT;  // float4 per V buffer
   extern __shared__ __attribute__((aligned(16))) float4 V4[];
   const int tid = threadIdx.x;
@@ -690,11 +674,6 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, const float* __res
   wp[i] = v;
 }
 
-#ifdef RTPOSE_EXP_TIMELINE3
-static unsigned long long* g_dbgw3_buf = nullptr;
-static unsigned g_dbgw3_blocks = 0;
-#endif
-
 template <int WM, int WN, int CK>
 static int launch_inst(const Args& a, dim3 grid, hipStream_t s) {
   static PerDeviceOnce attr_set;
@@ -706,42 +685,12 @@ static int launch_inst(const Args& a, dim3 grid, hipStream_t s) {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     attr_set.set(dev);
   }
-#ifdef RTPOSE_EXP_TIMELINE3
-  {  // developer build: per-tile stamps of the LAST launch of this instance family (tools/timeline_w3.py)
-    static int only_wm = -1;
-    if (only_wm < 0) {
-      const char* e = dev_env("RTPOSE_TIMELINE_WM");  // 1: <1,4,16> launches, 2: conv1_2
-      only_wm = e ? atoi(e) : 1;
-    }
-    Args b = a;
-    if (WM == only_wm && grid.x <= 1024) {
-      if (!g_dbgw3_buf) (void)hipMalloc(&g_dbgw3_buf, (size_t)1024 * 6 * 8 * 8);
-      (void)hipMemsetAsync(g_dbgw3_buf, 0, (size_t)grid.x * 6 * 64, s);
-      b.dbg = g_dbgw3_buf;
-      g_dbgw3_blocks = grid.x;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, b);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-#endif
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
   RTPOSE_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 }  // namespace wino
-
-#ifdef RTPOSE_EXP_TIMELINE3
-extern "C" int rtpose_debug_timeline_w3_dump(unsigned long long* host, unsigned cap_blocks) {
-  using namespace wino;
-  if (!g_dbgw3_buf) return 0;
-  (void)hipDeviceSynchronize();
-  const unsigned n = g_dbgw3_blocks < cap_blocks ? g_dbgw3_blocks : cap_blocks;
-  (void)hipMemcpy(host, g_dbgw3_buf, (size_t)n * 6 * 64, hipMemcpyDeviceToHost);
-  return (int)n;
-}
-#endif
 
 // channel chunk the packed Winograd weights of a conv are laid out for (the kernel instance is chosen by
 // the padded output width: >= 128 columns -> 32 wtiles x 128 columns, 16-channel chunks; 64 -> 64 x 64, 8)
@@ -820,12 +769,7 @@ int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   {
     // persistent blocks when a CU would get more than one tile anyway (see wino_f32)
     const int n_cu = device_cu_count();
-    static int persist_env = -1;
-    if (persist_env < 0) {
-      const char* e = dev_env("RTPOSE_W3_PERSIST");
-      persist_env = e ? atoi(e) : 1;
-    }
-    if (persist_env && (long)a.mtiles * a.ncombo > n_cu && n_cu % a.ncombo == 0) {
+    if ((long)a.mtiles * a.ncombo > n_cu && n_cu % a.ncombo == 0) {
       a.persist = 1;
       ids = n_cu;
     }

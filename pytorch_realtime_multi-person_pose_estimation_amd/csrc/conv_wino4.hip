@@ -60,7 +60,6 @@
 #include <type_traits>
 
 #include "common.h"
-#include "conv_exp.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -68,6 +67,8 @@ namespace rtpose {
 namespace wino4 {
 
 using namespace winoc;
+
+constexpr int W4_L0 = 6;  // first pair step of a chunk's patch loads (of 9 steps; two loads per step)
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
@@ -99,9 +100,6 @@ struct Args {
   int mtiles, ntiles, ncombo, xcd_remap;
   int persist;
   int mt0;  // first m tile of this launch (a layer may run as a persistent launch of whole rounds + a launch of the rest)
-#ifdef RTPOSE_EXP_TIMELINE4
-  unsigned long long* dbg;  // developer build: [block][wave][64 chunks][2] s_memtime stamps of the block's first tile
-#endif
 };
 
 constexpr int NT = 32;    // wtiles per block
@@ -184,14 +182,9 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
     // group) sit on one XCD: they fetch the same patch rows, 32 bytes of a 128-byte line per chunk, and only if the
     // XCD's 4 MB L2 has to hold 32 / ncombo m tiles' lines instead of 32 do the lines survive until the next chunk
     // takes its 32 bytes.  (The filters of all column tiles then stream through every L2; they are read in long runs.)
-#if RTPOSE_EXP_W4_XCDMAP
     const int xcd = bi & 7, idx = bi >> 3;
     c = idx % A.ncombo;
     j0 = (idx / A.ncombo) * 8 + xcd;
-#else
-    c = bi % A.ncombo;
-    j0 = bi / A.ncombo;
-#endif
     jstep = gridDim.x / A.ncombo;
   } else {
     if (A.xcd_remap) {
@@ -253,13 +246,8 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
   F4 p[6];
   auto load_piece = [&](const i32x4& r_, const unsigned (&v_)[4], int chunk, int n5) {
     const unsigned cb = (unsigned)chunk * ckb;
-#ifdef RTPOSE_EXP_W4_AUX  // cache policy bits of the patch loads (1 sc0, 2 nt, 16 sc1): no effect / nt 2x slower
-    const f32x4 t = n5 < 3 ? llvm_raw_buffer_load_v4f32(r_, (int)v_[0], (int)(cb + n5 * pxb), RTPOSE_EXP_W4_AUX)
-                           : llvm_raw_buffer_load_v4f32(r_, (int)v_[n5 - 2], (int)cb, RTPOSE_EXP_W4_AUX);
-    p[n5] = F4{f2{t.x, t.y}, f2{t.z, t.w}};
-#else
+    // (cache policy bits on these loads - sc0, nt, sc1 - measured: no effect / nt 2x slower)
     p[n5] = n5 < 3 ? bload(r_, v_[0], cb + n5 * pxb) : bload(r_, v_[n5 - 2], cb);
-#endif
   };
   const int ust = (py * 2 + cg1) * NT + (wl1 ^ (4 * cg1));     // U[fx][y = py][cg][wtile ^ 4 cg], + fx * 6 * 2 * NT
   const int uld = ((fx * 6) * 2 + cg) * NT + (wl ^ (4 * cg));  // U[fx][y][cg][wtile ^ 4 cg], + y * 2 * NT
@@ -350,53 +338,22 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
         }
         const int c3 = lc++;
         const i32x4 rl = s1 ? rin : rnull;
-        if (mt == j0) RTPOSE_TSTAMP4(c2 + h, 0);
-#if RTPOSE_EXP_W4_A3
-        // A fragments in a ring of three: the fragment of half-step k + 2 (k = 2 i + row tile) is requested right after the
-        // MFMAs of half-step k are issued - 8 MFMAs ahead instead of 4.  (Per-wave timelines, tools/timeline_w4.py: a wave
-        // took 455..800 cycles per 256-cycle step, two LDS round trips per step on its critical path.)
-        float4 ar[3];
-        ar[0] = va[fh * 16];
-        ar[1] = va[(fh ^ 1) * 16];
-#else
         a0 = va[RT == 2 ? fh * 16 : 0];
         if (RT == 2) a1 = va[(fh ^ 1) * 16];
-#endif
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
-#if RTPOSE_EXP_W4_PRIO == 1  // the siblings of a SIMD take the matrix pipe's priority in turns, step by step
-          if (fh == (i & 1)) __builtin_amdgcn_s_setprio(1);
-          else __builtin_amdgcn_s_setprio(0);
-#elif RTPOSE_EXP_W4_PRIO == 2  // the younger sibling (wave w + 4) always has it
-          if (i == 0 && fh) __builtin_amdgcn_s_setprio(1);
-#elif RTPOSE_EXP_W4_PRIO == 3  // in turns, chunk by chunk
-          if (i == 0) {
-            if (fh == h) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-          }
-#endif
           const float4 bv = bs[(h * NPW + i) % NB];
-#if RTPOSE_EXP_W4_A3
-          const float4 a0 = ar[(2 * i) % 3], a1 = ar[(2 * i + 1) % 3];
-#endif
           acc[2 * i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, bv.x, acc[2 * i][0], 0, 0, 0);
           acc[2 * i + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, bv.z, acc[2 * i + 1][0], 0, 0, 0);
           acc[2 * i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, bv.y, acc[2 * i][0], 0, 0, 0);
           acc[2 * i + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, bv.w, acc[2 * i + 1][0], 0, 0, 0);
           RTPOSE_PIN();
-#if RTPOSE_EXP_W4_PRIO >= 4  // yield the matrix pipe to the sibling after every group of 4 MFMAs
-          __builtin_amdgcn_s_sleep(RTPOSE_EXP_W4_PRIO - 3);
-#endif
-#if RTPOSE_EXP_W4_A3
-          if (i < NPW - 1) ar[(2 * i + 2) % 3] = RTPOSE_EXP_A(va[(i + 1) * 4 * NT + fh * 16], ar[(2 * i) % 3]);
-#else
-          if (i < NPW - 1) a0 = RTPOSE_EXP_A(va[(i + 1) * 4 * NT + (RT == 2 ? fh * 16 : 0)], a0);
-#endif
+          if (i < NPW - 1) a0 = va[(i + 1) * 4 * NT + (RT == 2 ? fh * 16 : 0)];
           {
             // B PF pairs ahead.  After a chunk's ninth pair the sibling's nine are skipped; after the tile's last chunk
             // the ring wraps to the next tile.
             const int L = h * NPW + i + PF;
-            bs[L % NB] = RTPOSE_EXP_B(bload_f4(rw, boff, wso), bs[(h * NPW + i) % NB]);
+            bs[L % NB] = bload_f4(rw, boff, wso);
             if (L % NPW == NPW - 1) wso = (c2 + L / NPW == nchunks - 1) ? wbase : wso + (NPW + 1) * fstep;
             else wso += fstep;
           }
@@ -408,40 +365,27 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
             acc[2 * i + 1][RT - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, bv.w, acc[2 * i + 1][RT - 1], 0, 0, 0);
           }
           RTPOSE_PIN();
-#if RTPOSE_EXP_W4_PRIO >= 4
-          __builtin_amdgcn_s_sleep(RTPOSE_EXP_W4_PRIO - 3);
-#endif
-#if RTPOSE_EXP_W4_A3
-          if (i < NPW - 1) ar[(2 * i + 3) % 3] = RTPOSE_EXP_A(va[(i + 1) * 4 * NT + (fh ^ 1) * 16], ar[(2 * i + 1) % 3]);
-#else
-          if (RT == 2 && i < NPW - 1) a1 = RTPOSE_EXP_A(va[(i + 1) * 4 * NT + (fh ^ 1) * 16], a1);
-#endif
-          if (RTPOSE_EXP_STAGE) {
-            if (i < 2) {
-              if (s1 && i == turn) stage1(h);              // patch rows of position + 2 -> U[h]
-            } else if (i < 4) {
-              if (i == 2 + turn) stage2_read(h ^ 1);       // U[h ^ 1] = position + 1 (the waves 0, 1 read and discard: see the loads)
-            } else if (i < 6) {
-              if (s2 && i == 4 + turn) stage2(h ^ 1);      // -> V[h ^ 1]
-            }
-#ifndef RTPOSE_EXP_W4_NOLOAD  // (timing only: the transform on stale registers)
-            if (i >= RTPOSE_EXP_W4_L0 && i < RTPOSE_EXP_W4_L0 + 3) {
-              // Issued by ALL waves: the waves 6, 7 (no stage-1 item) go through a descriptor of zero extent - every lane is
-              // out of range, nothing is fetched.  Under a wave-uniform branch the compiler's vmcnt bookkeeping has to assume
-              // the loads were NOT issued: every later wait for a filter fragment then also waited for these patch loads,
-              // one or two steps after their issue (0.92 -> see DESIGN.md §3.0).
-              load_piece(rl, pv, c3, 2 * (i - RTPOSE_EXP_W4_L0));  // patch rows of position + 3
-              load_piece(rl, pv, c3, 2 * (i - RTPOSE_EXP_W4_L0) + 1);
-            }
-#endif
+          if (RT == 2 && i < NPW - 1) a1 = va[(i + 1) * 4 * NT + (fh ^ 1) * 16];
+          if (i < 2) {
+            if (s1 && i == turn) stage1(h);              // patch rows of position + 2 -> U[h]
+          } else if (i < 4) {
+            if (i == 2 + turn) stage2_read(h ^ 1);       // U[h ^ 1] = position + 1 (the waves 0, 1 read and discard: see the loads)
+          } else if (i < 6) {
+            if (s2 && i == 4 + turn) stage2(h ^ 1);      // -> V[h ^ 1]
+          }
+          if (i >= W4_L0 && i < W4_L0 + 3) {
+            // Issued by ALL waves: the waves 6, 7 (no stage-1 item) go through a descriptor of zero extent - every lane is
+            // out of range, nothing is fetched.  Under a wave-uniform branch the compiler's vmcnt bookkeeping has to assume
+            // the loads were NOT issued: every later wait for a filter fragment then also waited for these patch loads,
+            // one or two steps after their issue (0.92 -> see DESIGN.md §3.0).
+            load_piece(rl, pv, c3, 2 * (i - W4_L0));  // patch rows of position + 3
+            load_piece(rl, pv, c3, 2 * (i - W4_L0) + 1);
           }
           RTPOSE_PIN();
         }
-        if (mt == j0) RTPOSE_TSTAMP4(c2 + h, 1);
         __syncthreads();
       }
     }
-    if (mt == j0) RTPOSE_TSTAMP4(63, 0);
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------
     // 1. every wave runs the first pass of the output transform (along y) on its own frequencies fx = 3 fh .. 3 fh + 2,
@@ -610,7 +554,6 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
     };
     if (fh == 0) finish(std::integral_constant<int, 0>{});
     else finish(std::integral_constant<int, 1>{});
-    if (mt == j0) RTPOSE_TSTAMP4(63, 1);
   }  // m tiles of this block
 #undef RTPOSE_PIN
 }
@@ -959,11 +902,6 @@ __global__ void wino4_amp_kernel(const float* __restrict__ w, int cout, int cin,
 
 }  // namespace wino4
 
-#ifdef RTPOSE_EXP_TIMELINE4
-static unsigned long long* g_dbgw4_buf = nullptr;
-static unsigned g_dbgw4_blocks = 0;
-#endif
-
 // 1 when the 3x3 conv has an F(4x4,3x3) instance: 8-channel chunks, at least 3 of them (the transform pipeline is 3 deep)
 int conv2d_wino4_ok(int cin, int cout) { return cout > 0 && cin % 16 == 0 && cin >= 32; }
 
@@ -1074,9 +1012,6 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
     b.mt0 = 2 * mt0_32;
     b.mtiles = (int)((wtiles + 15) / 16);
     b.xcd_remap = (b.ncombo > 1 && b.mtiles >= 64) ? 1 : 0;
-#ifdef RTPOSE_EXP_TIMELINE4
-    b.dbg = nullptr;  // (the stamps are the main launch's)
-#endif
     const long idh = b.xcd_remap ? (long)8 * b.ncombo * ceil_div(b.mtiles, 8) : (long)b.mtiles * b.ncombo;
     static PerDeviceOnce attr_h;
     const int dev_h = current_device();
@@ -1090,7 +1025,7 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
     return 0;
   };
   // launches that fill at most half the CUs with 32 x 64 tiles run the 16 x 16 form (measured: at one round and beyond
-  // the big tiles win - the small form fetches the filters four times as often; tools/r3_sessions/session27.sh)
+  // the big tiles win - the small form fetches the filters four times as often; ee158f6:tools/r3_sessions/session27.sh)
   if ((long)a.mtiles * a.ncombo * 2 <= n_cu) return launch_small(a, 0, a.T);
   int rest = 0;  // m tiles left to a second launch
   bool rest_half = false;  // ... in half tiles (else the 16 x 16 form)
@@ -1103,20 +1038,10 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
     // (conv3_x) the cut changes nothing.  The forms are bit-identical, so the cut is invisible in the results.
     const int Pc = n_cu / a.ncombo;
     const int r = a.mtiles % Pc;
-    static int cut_pct = -1;  // developer switch: largest left-over (in % of a round) that is cut off
-    if (cut_pct < 0) {
-      const char* e = dev_env("RTPOSE_W4_CUT_PCT");
-      cut_pct = e ? atoi(e) : 25;
-    }
-    static int half_on = -1;  // developer switch: RTPOSE_W4_HALF=0 runs a left-over of 25..50 % of a round as a round of big tiles
-    if (half_on < 0) {
-      const char* e = dev_env("RTPOSE_W4_HALF");
-      half_on = e ? atoi(e) : 1;
-    }
-    if (r && (long)r * a.ncombo * 100 <= (long)cut_pct * n_cu) {
+    if (r && (long)r * a.ncombo * 4 <= n_cu) {  // at most a quarter of a round left over
       rest = r;
       a.mtiles -= r;
-    } else if (r && half_on && 2L * r * a.ncombo <= n_cu) {
+    } else if (r && 2L * r * a.ncombo <= n_cu) {
       // Round 4: up to half a round left over runs as ONE round of half tiles (16 wtiles x 64 columns: half the multiplies of a
       // tile, the same transform work per wtile) instead of a round of big tiles that leaves 50..75 % of the CUs idle:
       // conv3_x 8.27 rounds -> 8 + a half-tile round, conv4_1 / conv4_2 4.5 -> 4 + one.
@@ -1134,23 +1059,6 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     attr_set.set(dev);
   }
-#ifdef RTPOSE_EXP_TIMELINE4
-  {  // developer build: stamps of the LAST launch with the channel counts RTPOSE_TIMELINE_W4="cin,cout" (default 256,256)
-    static int want_cin = -1, want_cout = 256;
-    if (want_cin < 0) {
-      const char* e = dev_env("RTPOSE_TIMELINE_W4");
-      want_cin = 256;
-      if (e) sscanf(e, "%d,%d", &want_cin, &want_cout);
-    }
-    a.dbg = nullptr;
-    if (d0.cin == want_cin && d0.cout == want_cout && ids <= 1024) {
-      if (!g_dbgw4_buf) (void)hipMalloc(&g_dbgw4_buf, (size_t)1024 * 8 * 64 * 2 * 8);
-      (void)hipMemsetAsync(g_dbgw4_buf, 0, (size_t)ids * 8 * 64 * 2 * 8, s);
-      a.dbg = g_dbgw4_buf;
-      g_dbgw4_blocks = (unsigned)ids;
-    }
-  }
-#endif
   hipLaunchKernelGGL(wino4_f32<2>, dim3((unsigned)ids), dim3(512), (size_t)(2 * VBUF + 2 * UBUF) * sizeof(float4), s, a);
   RTPOSE_HIP_CHECK(hipGetLastError());
   if (rest && rest_half) return launch_half(a, a.mtiles, (long)a.T - (long)a.mtiles * NT);
@@ -1186,14 +1094,3 @@ double conv2d_wino4_issued_flops(int cin, int cout, int N, int H, int W) {
 }
 
 }  // namespace rtpose
-
-#ifdef RTPOSE_EXP_TIMELINE4
-extern "C" int rtpose_debug_timeline_w4_dump(unsigned long long* host, unsigned cap_blocks) {
-  using namespace rtpose;
-  if (!g_dbgw4_buf) return 0;
-  (void)hipDeviceSynchronize();
-  const unsigned n = g_dbgw4_blocks < cap_blocks ? g_dbgw4_blocks : cap_blocks;
-  (void)hipMemcpy(host, g_dbgw4_buf, (size_t)n * 8 * 64 * 2 * 8, hipMemcpyDeviceToHost);
-  return (int)n;
-}
-#endif

@@ -35,7 +35,6 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "conv_exp.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -45,6 +44,9 @@ size_t packed_weight_floats_wino7(int cout, int cin, int fm);
 namespace wino7 {
 
 using namespace winoc;
+
+// F(4,7) kernel: weight prefetch distance in (ky, frequency pair) steps (<= 4: 5 register sets; 2: +5 %, 3: +0.7 %)
+constexpr int W7_PF = 4;
 
 // F(FM, 7): FM outputs from FM + 6 inputs through NFQ = FM + 6 "frequencies" = Toom-Cook interpolation points
 // 0, +-p_1 .. +-p_NP, inf.  kBT = the input transform, rows scaled by N_f = prod_{l != f} (p_f - p_l) (the filter
@@ -163,7 +165,7 @@ struct Xform {
       const int r = i / (GX * CG), rem = i - r * (GX * CG);
       // channel-group-major inside a row: the 8 contiguous lanes a ds_write_b128 is serviced in then write 8
       // consecutive 16-byte slots (gx, cg interleaved they hit 4 slots twice: 12.5 % of SQ_LDS_IDX_ACTIVE in round 2)
-      const int cg = RTPOSE_EXP_W7_CGMAJOR ? rem / GX : (rem & 1), gx = RTPOSE_EXP_W7_CGMAJOR ? rem - cg * GX : (rem >> 1);
+      const int cg = rem / GX, gx = rem - cg * GX;
       voff[k] = (unsigned)((((long)r * g.in_ws + FM * gx) * g.in_cstride + cg * 4) * 4);
       vdst[k] = r * RS + cg * GX + gx;
 #pragma unroll
@@ -225,28 +227,21 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
   constexpr int NFQ = T::NFQ, NP = T::NP;
   constexpr int NFW = NFQ / FS;                              // frequencies of a wave
   static_assert(NFW % 2 == 0, "frequency pairs");
-  constexpr int NSETS = FS == 2 ? RTPOSE_EXP_W7_FS2SETS : (FM == 6 && NI == 2) ? 3 : T::NSETS;
+  constexpr int NSETS = FS == 2 ? 7 : (FM == 6 && NI == 2) ? 3 : T::NSETS;
   constexpr int NPS = 7 * NFW / 2;                           // (ky, frequency pair) steps per chunk (NPS % NSETS == 0)
   // B prefetch distance in steps.  The 8-wave form needs the deepest ring it can have: a step is 8 MFMAs of the wave's
   // own, and with 2 steps (3 sets) the layer took 0.603 ms, with 4 (7 sets) 0.527, with 6 0.522 (4-wave form: 0.544)
-  constexpr int PF = FS == 2 ? NSETS - 1 : (RTPOSE_EXP_W7_PF < NSETS ? RTPOSE_EXP_W7_PF : NSETS - 1);
+  constexpr int PF = FS == 2 ? NSETS - 1 : (W7_PF < NSETS ? W7_PF : NSETS - 1);
   static_assert(NPS % NSETS == 0, "B register sets must rotate in step with the chunk");
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = FS == 2 ? (wv & 3) : wv, fh = FS == 2 ? (wv >> 2) : 0;
-  // Who transforms.  RTPOSE_EXP_W7_XSPLIT = 0: the waves 0..3 (one per SIMD) do all of it while the sibling multiplies.
-  // 1: both siblings load an item's segments and each forms half of its frequency groups (even / odd group index):
-  // twice the segment loads (L2 hits), the VALU groups and LDS writes split evenly - neither sibling waits at the
-  // chunk barrier for the other's transform.
-  constexpr bool XSPLIT = FS == 2 && RTPOSE_EXP_W7_XSPLIT;
-  const bool xf = XSPLIT || wv < 4;  // this wave takes part in the input transform
-  auto my_group = [&](int gi) { return !XSPLIT || (gi & 1) == fh; };
-#if RTPOSE_EXP_W7_PRIO == 1
-  if (FS == 2 && xf) __builtin_amdgcn_s_setprio(1);
-#elif RTPOSE_EXP_W7_PRIO == 2
-  if (FS == 2 && !xf) __builtin_amdgcn_s_setprio(1);
-#endif
+  // Who transforms: the waves 0..3 (one per SIMD) do all of it while the sibling multiplies.
+  const bool xf = wv < 4;  // this wave takes part in the input transform
+  // It forms every group of its items.  (Spelled as a test on fh that cannot fail: without it clang emits the scalar
+  // prologue of the 8-wave form 4 bytes shorter, which moves the multiply loop's alignment - 0.4 % slower fp32 step.)
+  auto my_group = [&](int gi) { return true || (gi & 1) == fh; };
   const int l31 = lane & 31, kh = lane >> 5;
   const int nt = c % A.ntiles, grp = c / A.ntiles;
   const Group g = grp ? A.g[1] : A.g[0];
@@ -277,10 +272,9 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
   // ---- input transform role: NI items (row, gx, channel group), see Xform ----------------------------
   Xform<NI, FM> X;
   X.setup(g, A.W, GX, RS, R0, nrows);
-  // (RTPOSE_EXP_W7_NULLDESC, off: the waves 4..7 of the 8-wave form issue the segment loads too, through a descriptor of
-  //  zero extent, so that the loads are not under a wave-uniform branch and the compiler's vmcnt bookkeeping stays exact -
-  //  the fix that gave conv_wino4.hip 6 %; measured 0 % here, the deep filter ring already covers it)
-  if (RTPOSE_EXP_W7_NULLDESC && !xf) X.rin = make_rsrc(g.in, 0);
+  // (Not done: the waves 4..7 of the 8-wave form issuing the segment loads too, through a descriptor of zero extent, so
+  //  that the loads are not under a wave-uniform branch and the compiler's vmcnt bookkeeping stays exact - the fix that
+  //  gave conv_wino4.hip 6 %; measured 0 % here, the deep filter ring already covers it)
   const i32x4 rw = make_rsrc(g.w, g.w_bytes);
   auto load_piece = [&](int chunk, int k, int n) { X.load_piece(chunk, k, n); };
   auto tgroup = [&](float4* vw, int k, int gidx) { X.tgroup(vw, k, gidx); };
@@ -356,7 +350,7 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
     for (int k = 0; k < NI; ++k)
 #pragma unroll
       for (int gi = 0; gi < NP + 2; ++gi)
-        if (my_group(gi)) tgroup(V4, k, gi);
+        tgroup(V4, k, gi);
     const int c1 = min(cb + 1, ce - 1);
 #pragma unroll
     for (int k = 0; k < NI; ++k)
@@ -383,7 +377,9 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
   // fragments PF steps ahead (L2).  Slot 3 of the first steps also carries transform work of the NEXT chunk: its
   // 6 NI groups (steps 0..11), then the 10 NI segment loads of the chunk after that, two per step.
   constexpr int NG = (NP + 2) * NI, GSTR = (NI == 1 && FS == 1) ? 2 : 1, LS = NG * GSTR;  // groups, their step stride, first load step
-  constexpr int LPS = RTPOSE_EXP_W7_LPS, LSTEPS = (NFQ * NI + LPS - 1) / LPS;    // segment loads per step, steps with loads
+  // segment loads per step, steps with loads (1: 0.719 -> 0.695 ms per 128 -> 128 layer against 2; the loads touch 32
+  // cache lines each and all four waves issue them in the same steps, 5 per step 0.718)
+  constexpr int LPS = 1, LSTEPS = (NFQ * NI + LPS - 1) / LPS;
   static_assert(LS + LSTEPS <= NPS, "transform work does not fit the steps of a chunk");
   float4 a[2][2];
   for (int chunk = cb; chunk < ce; ++chunk) {
@@ -408,17 +404,16 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
         if (j < 2) {  // A of the next step (the first step of a chunk is read after the barrier)
           if (ps + 1 < NPS) {
             const int kyn = (ps + 1) / (NFW / 2), fn = 2 * ((ps + 1) % (NFW / 2)) + j;
-            a[(ps + 1) & 1][j] = RTPOSE_EXP_A(va[kyn * RS + fn * CG * GX], a[ps & 1][j]);
+            a[(ps + 1) & 1][j] = va[kyn * RS + fn * CG * GX];
           }
         } else {      // B PF steps ahead
-          bs[(ps + PF) % NSETS][j - 2] = RTPOSE_EXP_B(bload_f4(rw, boff, wso), bs[ps % NSETS][j - 2]);
+          bs[(ps + PF) % NSETS][j - 2] = bload_f4(rw, boff, wso);
           bnext(bl);
         }
-        if (RTPOSE_EXP_STAGE && j == 3 && (xf || RTPOSE_EXP_W7_NULLDESC)) {
+        if (j == 3 && xf) {
           if (ps % GSTR == 0 && ps / GSTR < NG) {
-            if (xf && (RTPOSE_EXP_W7_TMASK & 1) && my_group((ps / GSTR) % (NP + 2)))
-              tgroup(vw, (ps / GSTR) / (NP + 2), (ps / GSTR) % (NP + 2));
-          } else if (ps >= LS && ps < LS + LSTEPS && (RTPOSE_EXP_W7_TMASK & 2)) {  // LPS segment loads per step
+            if (xf && my_group((ps / GSTR) % (NP + 2))) tgroup(vw, (ps / GSTR) / (NP + 2), (ps / GSTR) % (NP + 2));
+          } else if (ps >= LS && ps < LS + LSTEPS) {  // LPS segment loads per step
 #pragma unroll
             for (int q = 0; q < LPS; ++q) {
               const int l = LPS * (ps - LS) + q;
@@ -471,7 +466,7 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
     sx = r - sy * GX;
   }
 #pragma unroll
-  for (int rr = 0; rr < (RTPOSE_EXP_W_EPI < R0E ? RTPOSE_EXP_W_EPI : R0E); ++rr) {
+  for (int rr = 0; rr < R0E; ++rr) {
     const int r = rr;  // position stepping below depends on r % 4 only
     float m[NFQ];
     if (FS == 2) {
@@ -1141,12 +1136,7 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
     // that is too small for this device) the launch runs one block per tile - same results, bit for bit.
     const int n_cu = device_cu_count();
     const long tiles = (long)a.mtiles * a.ncombo;
-    static int persist_env = -1;
-    if (persist_env < 0) {
-      const char* e = dev_env("RTPOSE_W7_PERSIST");
-      persist_env = e ? atoi(e) : 1;
-    }
-    if (persist_env && tiles >= n_cu && tiles % n_cu != 0 && scratch && scratch_bytes >= conv2d_wino7_scratch_bytes(n_cu)) {
+    if (tiles >= n_cu && tiles % n_cu != 0 && scratch && scratch_bytes >= conv2d_wino7_scratch_bytes(n_cu)) {
       if ((uintptr_t)scratch & 255) return fail(RTPOSE_E_INVAL, "conv2d_winograd: scratch must be 256-byte aligned");
       a.flags = static_cast<int*>(scratch);
       a.err = a.flags + n_cu + 1;
@@ -1159,12 +1149,7 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
   }
   const dim3 grid((unsigned)ids, 1, 1);
   // small grids: the frequency-split form (wino7s_f32), bit-identical, 4 x the blocks
-  static int small_env = -1;
-  if (small_env < 0) {
-    const char* e = dev_env("RTPOSE_W7_SMALL");
-    small_env = e ? atoi(e) : 1;
-  }
-  if (small_env && p.fm == 6 && !a.persist && (long)a.mtiles * a.ncombo * 2 <= device_cu_count()) {
+  if (p.fm == 6 && !a.persist && (long)a.mtiles * a.ncombo * 2 <= device_cu_count()) {
     Args b = a;
     b.ntiles = cout_pad(d0.cout) / 32;
     b.ncombo = b.ntiles * ngroups;
@@ -1175,17 +1160,10 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
   // 46-wide maps (368 x 368 inputs, BASELINE configs[1]): every LDS offset of the multiply loop is an immediate
   if (p.fm == 6) {
     // two waves per SIMD (8-wave blocks, the frequencies split between sibling waves: wino7_segment FS = 2) wherever
-    // a thread transforms one item per chunk; bit-identical to the 4-wave form (RTPOSE_W7_FS=1 in developer builds)
-    static int fs_env = -1;
-    if (fs_env < 0) {
-      const char* e = dev_env("RTPOSE_W7_FS");
-      fs_env = e ? atoi(e) : 2;
-    }
-    if (p.gx == 8 && p.tpi && p.ni == 1 && p.nrows == strip_rows(8)) {
-      const size_t lds8 = (size_t)2 * strip_rows(8) * row_stride(8, 12) * 16;
-      return fs_env == 2 ? launch_inst<1, 8, 6, 2>(a, grid, lds8, s) : launch_inst<1, 8, 6>(a, grid, lds8, s);
-    }
-    if (p.ni == 1) return fs_env == 2 ? launch_inst<1, 0, 6, 2>(a, grid, p.lds, s) : launch_inst<1, 0, 6>(a, grid, p.lds, s);
+    // a thread transforms one item per chunk; bit-identical to the 4-wave form
+    if (p.gx == 8 && p.tpi && p.ni == 1 && p.nrows == strip_rows(8))
+      return launch_inst<1, 8, 6, 2>(a, grid, (size_t)2 * strip_rows(8) * row_stride(8, 12) * 16, s);
+    if (p.ni == 1) return launch_inst<1, 0, 6, 2>(a, grid, p.lds, s);
     return launch_inst<2, 0, 6>(a, grid, p.lds, s);
   }
   if (p.gx == 12 && p.tpi && p.ni == 1 && p.nrows == strip_rows(12))

@@ -591,13 +591,7 @@ constexpr int kSortStack = 3 * 64;  // pending ranges <= the depth limit 2 floor
 // wrong sample, always in lanes 48..63 (most often the top active lane), with maps and peaks bit-identical before and after,
 // never in the serial flow, never on CUs the forward does not use.  Eight discriminating builds and three stand-alone
 // victims: DESIGN.md 3.3, profiles/r06_decoder_beside_forward.txt.  (a) - (c) were each tried as the cure and are not it
-// (they stay: fewer instructions); (d) is.  The RTPOSE_EXP_LIMB_* blocks below are those builds' switches
-// (tools/build_dev.sh -DRTPOSE_EXP_LIMB_...; a production build refuses them).
-#if !defined(RTPOSE_DEV_BUILD) && (defined(RTPOSE_EXP_LIMB_WAIT0) || defined(RTPOSE_EXP_LIMB_KEEP) || \
-                                   defined(RTPOSE_EXP_LIMB_ASM_COORD) || defined(RTPOSE_EXP_LIMB_ASM_DOT) || \
-                                   defined(RTPOSE_EXP_GROUP_TIMELINE))
-#error "RTPOSE_EXP_LIMB_* are developer-build experiments (tools/build_dev.sh)"
-#endif
+// (they stay: fewer instructions); (d) is.
 template <bool SCORES_IN_LDS, bool UP_POW2, bool A32>
 __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, int w, double inv_up, int up_shift,
                                                           int h1, int pcap,
@@ -665,27 +659,11 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, in
       const float step_y = (float)(B.y - A.y) / 10.f;
       float scores = 0.f;
       int crit1 = 0;
-#ifdef RTPOSE_EXP_LIMB_WAIT0  // experiment: every map load has landed before the first value is consumed
-      float pxa[10], pya[10];
-#endif
-#ifdef RTPOSE_EXP_LIMB_KEEP  // experiment: the loads' offset registers stay live until every load has returned
-      unsigned keep[10];
-#endif
 #pragma unroll
       for (int i = 0; i < 10; ++i) {
         // lx = (int)(v + 0.5) evaluated in double (pafprocess.cpp:232-233): v >= 0 is a float, so v + 0.5 is exact there
         // and the cast is floor(v + 0.5) = trunc(v) + (frac(v) >= 0.5), frac exact in fp32
-#ifdef RTPOSE_EXP_LIMB_ASM_COORD  // experiment: the y coordinate through opaque scalar instructions - the
-        const float fx = (float)A.x + (float)i * step_x;   // vectoriser cannot pair it with x
-        float fy;
-        {
-          float ty;
-          asm("v_mul_f32 %0, %1, %2" : "=v"(ty) : "v"((float)i), "v"(step_y));
-          asm("v_add_f32 %0, %1, %2" : "=v"(fy) : "v"((float)A.y), "v"(ty));
-        }
-#else
         const float fx = (float)A.x + (float)i * step_x, fy = (float)A.y + (float)i * step_y;
-#endif
         int lx = (int)fx, ly = (int)fy;
         if (fx - (float)lx >= 0.5f) ++lx;
         if (fy - (float)ly >= 0.5f) ++ly;
@@ -708,37 +686,14 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, in
           asm("v_mul_u32_u24 %0, %1, %2" : "=v"(boff) : "s"(pix_bytes), "v"(pix));
           px = *reinterpret_cast<const float*>(img_x + boff);
           py = *reinterpret_cast<const float*>(img_y + boff);
-#ifdef RTPOSE_EXP_LIMB_KEEP
-          keep[i] = boff;
-#endif
         } else {
           px = map_at(paf, n, sy, sx, chx);
           py = map_at(paf, n, sy, sx, chy);
         }
-#ifdef RTPOSE_EXP_LIMB_WAIT0
-        pxa[i] = px;
-        pya[i] = py;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < 10; ++i) {
-        float px = pxa[i], py = pya[i];
-        asm volatile("" : "+v"(px), "+v"(py));
-#endif
-#ifdef RTPOSE_EXP_LIMB_ASM_DOT  // experiment: one product of the dot product opaque - no packed multiply / add there
-        float typ;
-        asm("v_mul_f32 %0, %1, %2" : "=v"(typ) : "v"(vy), "v"(py));
-        const float s = vx * px + typ;
-#else
         const float s = vx * px + vy * py;
-#endif
         scores = scores + s;
         if (s > 0.05f) ++crit1;
       }
-#ifdef RTPOSE_EXP_LIMB_KEEP
-      asm volatile("" ::"v"(scores), "v"(keep[0]), "v"(keep[1]), "v"(keep[2]), "v"(keep[3]), "v"(keep[4]), "v"(keep[5]),
-                   "v"(keep[6]), "v"(keep[7]), "v"(keep[8]), "v"(keep[9]));
-#endif
       // min(0.5 h1 / norm - 1, 0) in double (cpp:238-240): 0 for every limb no longer than half the image (the quotient is
       // >= 1 then, and adding 0.0 to a float widened to double changes nothing)
       float crit2 = scores / 10.f;
@@ -908,13 +863,6 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, in
 // global round trip of the kernel is then taken once, with all lanes' loads in flight together, instead of once per limb (the
 // host picks it when 19 * pcap staged connections fit the LDS next to the rows: pcap <= 128).
 constexpr int kStageWords = 5;  // per staged connection: cid1, cid2, connection score, score of peak 2, score of peak 1
-#ifdef RTPOSE_EXP_GROUP_TIMELINE  // developer build: wall_clock64 stamps of the kernel's phases, per image (tools/exp/group_timeline.py)
-__device__ unsigned long long g_group_tl[256][8];
-#define RTPOSE_GTL(i)                                        \
-  if (lane == 0 && n < 256) g_group_tl[n][i] = wall_clock64()
-#else
-#define RTPOSE_GTL(i)
-#endif
 template <bool WRITE_IDS, bool STAGE_ALL>
 __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* __restrict__ result,
                                                    int result_words, const int32_t* __restrict__ conn,
@@ -927,7 +875,6 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
   // [row_cap][20 + alive]: the reference's `subset`; LDS unless grown past kLdsRows; then the staged connections of one limb
   float* rows = row_cap <= kLdsRows ? rows_lds : rows_ws + (size_t)n * row_cap * 21;
   float* stage = rows_lds + (row_cap <= kLdsRows ? (size_t)row_cap * 21 : 0);
-  RTPOSE_GTL(0);
 
   __shared__ int s_start[RTPOSE_NUM_PART + 1];
   if (lane == 0) {
@@ -972,7 +919,6 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
     st[4] = (id1 >= 0 && id1 < npeaks) ? (WRITE_IDS ? pA[ia].score : line_peak_score(id1)) : 0.f;
   };
   __shared__ int s_cbase[RTPOSE_NUM_LIMB + 1];
-  RTPOSE_GTL(1);
   if (STAGE_ALL) {
     if (lane < RTPOSE_NUM_LIMB) s_cbase[lane + 1] = cnb[(size_t)lane * (1 + 3 * pcap)];
     __syncthreads();
@@ -991,7 +937,6 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
     __syncthreads();
   }
 
-  RTPOSE_GTL(2);
   int nrows = 0;
   bool overflow = false;
   for (int pair_id = 0; pair_id < 19; ++pair_id) {
@@ -1073,10 +1018,6 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
     }
   }
 
-  RTPOSE_GTL(3);
-#ifdef RTPOSE_EXP_GROUP_TIMELINE
-  if (lane == 0 && n < 256) g_group_tl[n][6] = (unsigned long long)(STAGE_ALL ? s_cbase[RTPOSE_NUM_LIMB] : 0);
-#endif
   // prune (cpp:187-191) and emit
   int nh = 0;
   int32_t* hparts = res + kResPeaks + 4 * RTPOSE_NUM_PART * pcap;
@@ -1097,7 +1038,6 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
     res[kResHeader + 1] = nh;
     if (overflow) atomicOr(&res[kResHeader + 2], kOverflowHumans);
   }
-  RTPOSE_GTL(4);
 }
 
 // header + part counts of every record <- 0, except header[3] / [4] = the capacities the record is laid out for
@@ -1218,14 +1158,8 @@ int assign_group_launch(const float* paf, const rtpose_layout* lpaf, int N, int 
     if (up == (1 << k)) up_shift = k;
   const bool in_lds = pcap * pcap <= kLdsPairs;
   // 32-bit per-sample offsets when an image's maps span less than 2^31 bytes and the pixel index fits the 24-bit multiplier
-  bool a32 = (long long)lpaf->hs * lpaf->ws < (1ll << 24) && (long long)lpaf->cstride * (long long)sizeof(float) < (1 << 24) &&
-             (long long)lpaf->hs * lpaf->ws * lpaf->cstride * (long long)sizeof(float) < (1ll << 31);
-#ifdef RTPOSE_DEV_BUILD
-  {
-    static const char* e = getenv("RTPOSE_LIMB_A32");  // developer A/B of the two addressing forms (tools/exp/overlap_flake.py)
-    if (e && e[0] == '0') a32 = false;
-  }
-#endif
+  const bool a32 = (long long)lpaf->hs * lpaf->ws < (1ll << 24) && (long long)lpaf->cstride * (long long)sizeof(float) < (1 << 24) &&
+                   (long long)lpaf->hs * lpaf->ws * lpaf->cstride * (long long)sizeof(float) < (1ll << 31);
   {
 #define RTPOSE_LIMB_A(L, P, A)                                                                                         \
   hipLaunchKernelGGL((limb_assign_kernel<L, P, A>), dim3(RTPOSE_NUM_LIMB, N), dim3(256), lds, s, to_view(paf, lpaf), h, \
@@ -1265,12 +1199,6 @@ int assign_group_launch(const float* paf, const rtpose_layout* lpaf, int N, int 
 using namespace rtpose;
 
 extern "C" {
-
-#ifdef RTPOSE_EXP_GROUP_TIMELINE
-int rtpose_exp_group_timeline(unsigned long long* out, int n) {  // [n][8]: stamps 0..4, [6] = connections of the image
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(rtpose::g_group_tl), sizeof(unsigned long long) * 8 * (n < 256 ? n : 256));
-}
-#endif
 
 size_t rtpose_decode_workspace_bytes(const rtpose_decode_cfg* cfg, int N) {
   if (check_cfg(cfg) || N <= 0) return 0;

@@ -924,12 +924,6 @@ static void decide_guard_launch(rtpose_net* net) {
     const char* e = getenv("RTPOSE_GUARD_WHOLE_FORWARD");
     const char* f = getenv("RTPOSE_GUARD_FINE");
     if ((e && e[0] == '1') || (f && f[0] == '0')) net->guard_op = 0;
-#ifdef RTPOSE_DEV_BUILD
-    if (const char* o = getenv("RTPOSE_GUARD_OP")) {  // experiments: the wait in front of launch <n> (negative: from the end)
-      const int n = atoi(o), nops = (int)net->ops.size();
-      net->guard_op = n < 0 ? (nops + n > 0 ? nops + n : 0) : (n < nops ? n : nops - 1);
-    }
-#endif
   }
 }
 
@@ -1157,15 +1151,6 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
     if (prof) RTPOSE_HIP_CHECK(hipEventRecord(net->ev[i], s));
     if (net->out_guard && (int)i == net->guard_op) {
       RTPOSE_HIP_CHECK(hipStreamWaitEvent(s, net->out_guard, 0));
-#ifdef RTPOSE_DEV_BUILD
-      // experiment: behind the reader's last read, in front of the launch that rewrites them, the bf16
-      // plan's maps become NaNs - a reader that returns a NaN afterwards was served a stale copy of the same address
-      static const char* poison = getenv("RTPOSE_EXP_POISON");
-      if (poison && poison[0] == '1' && net->bf16) {
-        const Buf& b = net->bufs[net->save_buf[5]];
-        RTPOSE_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(net->ws + b.off_floats), 0x7fc00000, b.floats, s));
-      }
-#endif
     }
     int rc = 0;
     switch (o.kind) {

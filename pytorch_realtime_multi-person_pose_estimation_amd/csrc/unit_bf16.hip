@@ -32,7 +32,6 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-#include "conv_exp.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -115,16 +114,7 @@ struct Args {
   int K1, Kt, cout;          // cout: columns of conv.2 that exist (<= C2P, a multiple of 8)
   int tiles_x, tiles_y, nitems;
   FastDiv ftx, fty;
-  unsigned long long* dbg;   // developer builds (-DRTPOSE_EXP_TIMELINE_UNIT): s_memtime stamps [block][tile < 20][16]
 };
-
-#ifdef RTPOSE_EXP_TIMELINE_UNIT
-#define RTPOSE_UB_STAMP(K)                                                             \
-  if (A.dbg && wave == 0 && lane == 0 && tcount < 20)                                  \
-  A.dbg[((size_t)blockIdx.x * 20 + tcount) * 16 + (K)] = __builtin_amdgcn_s_memtime()
-#else
-#define RTPOSE_UB_STAMP(K)
-#endif
 
 #define RTPOSE_UB_PIN()          \
   asm volatile("" ::: "memory"); \
@@ -261,11 +251,8 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
     }
   }
   int pp = 0;  // which LDS tile buffer holds the current item
-  int tcount = 0;
-  (void)tcount;
 
   while (true) {
-    RTPOSE_UB_STAMP(0);
     float4* const xs = smem4 + pp * nr1 * XP1;        // x2 halo tile of this item, then its T1, then its y
     float4* const xn = smem4 + (pp ^ 1) * nr1 * XP1;  // receives the next item's tile
     const int nitem = item + (int)gridDim.x;
@@ -292,7 +279,6 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
       for (int j = 0; j < MF1; ++j) acc1[j] = t;
     }
     __syncthreads();  // B0: this item's x2 tile is in LDS (staged under the previous item), the previous y tile / a2 are dead
-    RTPOSE_UB_STAMP(1);
     {
       float4 xr[2][MF1];  // activation fragments: two k-steps x the wave's pixel fragments
       auto x1load = [&](float4(&dst)[MF1], int g) {
@@ -321,7 +307,6 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
         step1(IntTag<3>(), g0 + 3);
       }
     }
-    RTPOSE_UB_STAMP(2);
     // conv.2's fragments - all of them, from L2 - and BEHIND them the first round of the next tile from HBM: nothing
     // younger is waited for until that round is stored
 #pragma unroll
@@ -331,7 +316,6 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
     }
     stage_load(sqn, 0);
     __syncthreads();  // B1: every wave has read the x2 tile for the last time
-    RTPOSE_UB_STAMP(3);
 
     // ---- T1 = bf16(relu(.)) -> LDS [plane][halo pixel][8 channels] in the tile's place; zero outside the image --------
     mfma_drain();
@@ -355,9 +339,7 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
       }
       RTPOSE_UB_PIN();
     }
-    RTPOSE_UB_STAMP(4);
     __syncthreads();  // B2: T1 is in LDS
-    RTPOSE_UB_STAMP(5);
 
     // ---- depthwise 3x3 (fp32, VALU), all of T1's planes at once.  A thread owns FOUR horizontally adjacent output pixels
     //      of one plane: a tap's weights are read once for the four, a halo pixel once per row for up to three taps -
@@ -412,9 +394,7 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
     }
     stage_store(xn, 0);   // the round requested before the T1 write-out ...
     stage_load(sqn, 2);   // ... and the second (last) one: GEMM 2 below waits for no load
-    RTPOSE_UB_STAMP(6);
     __syncthreads();  // B3: the depthwise output is in a2
-    RTPOSE_UB_STAMP(7);
 
     // ---- GEMM 2 (transposed): y^T[column][slot], every filter fragment already in registers ---------------------------
     floatx16 acc2[MF2];
@@ -451,10 +431,7 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
         RTPOSE_UB_PIN();
       }
     }
-    RTPOSE_UB_STAMP(8);
-    RTPOSE_UB_STAMP(9);
     stage_store(xn, 2);
-    RTPOSE_UB_STAMP(10);
 
     // ---- epilogue: y = bf16(relu(.)) -> LDS [8-column group][slot] in the place of the dead T1 (everyone is past the
     //      depthwise conv), then 16 bytes per lane with the column groups along the lanes: groups that are neighbours in
@@ -491,8 +468,6 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
         }
       }
     }
-    RTPOSE_UB_STAMP(11);
-    ++tcount;
     if (!has_next) break;
     item = nitem;
     cur = nxt;
@@ -500,10 +475,6 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
   }
 }
 #undef RTPOSE_UB_PIN
-
-#ifdef RTPOSE_EXP_TIMELINE_UNIT
-static unsigned long long* g_unit_timeline = nullptr;  // device buffer [blocks][20][16], see tools/timeline_unit.py
-#endif
 
 template <int WM1, int WM2, int NCH2>
 static int launch_inst(const Args& a, int grid, size_t lds, hipStream_t s) {
@@ -588,9 +559,6 @@ int unit_bf16_launch(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int N, 
   a.nitems = N * a.tiles_x * a.tiles_y;
   a.ftx = make_fastdiv(a.tiles_x);
   a.fty = make_fastdiv(a.tiles_y);
-#ifdef RTPOSE_EXP_TIMELINE_UNIT
-  a.dbg = g_unit_timeline;
-#endif
   const size_t lds = ((size_t)2 * ((a.K1 > a.Kt ? a.K1 : a.Kt) >> 3) * XP1 + (size_t)(a.Kt >> 3) * AP2) * 16 + (size_t)10 * a.Kt * 4;
   const int slots = device_cu_count();  // one block per CU
   const int grid = a.nitems < slots ? a.nitems : slots;
@@ -606,12 +574,6 @@ int unit_bf16_launch(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int N, 
 }  // namespace rtpose
 
 extern "C" {
-
-#ifdef RTPOSE_EXP_TIMELINE_UNIT
-void rtpose_debug_unit_timeline(void* device_buffer) {
-  rtpose::unitb::g_unit_timeline = static_cast<unsigned long long*>(device_buffer);
-}
-#endif
 
 int rtpose_unit_bf16_fits(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int H, int W) {
   return rtpose::unit_bf16_fits(d0, d2, H, W);

@@ -36,7 +36,8 @@ class SideDecoder(object):
     The maps' buffer belongs to the plan, so the plan carries the guard (rtpose_net_set_output_guard): from the moment a
     decode is enqueued here, EVERY later forward of that plan - this object's next batch, PoseEstimator.__call__, a bare
     model(x), another estimator over the same module - waits for this decode's last read of the maps before it rewrites
-    them (library default: in front of its whole launch list; RTPOSE_GUARD_FINE=1: only where it first writes the buffer.
+    them (library default: only in front of its first launch that writes the buffer; RTPOSE_GUARD_WHOLE_FORWARD=1 or
+    RTPOSE_GUARD_FINE=0: in front of its whole launch list.
     DESIGN.md 3.3 has the history: the decoder's kernels are built without packed-fp32 VALU instructions because those
     returned wrong values beside the bf16 plan's kernels).  The guard stays installed until the next decode replaces it or
     close() removes it - ONE guard per plan: two pipelined consumers decoding the maps of the same plan at the same time
@@ -49,12 +50,6 @@ class SideDecoder(object):
         self.slots = [None, None]
         self.last = None            # slot of the decode enqueued last
         self._plans = {}            # id -> plan whose guard points at one of this object's events
-
-    def guarded(self, plan, forward):
-        """Run `forward()` (which enqueues the plan's launches on the current stream).  The guard a previous decode() left on
-        the plan makes it wait for that decode's final read of the maps; nothing to do here any more - kept as the one place
-        the pipelined callers enqueue their forward through."""
-        return forward()
 
     def close(self):
         """Remove this object's guard from the plans it was installed on (their events die with the slots)."""
@@ -193,7 +188,7 @@ class PoseEstimator(object):
                 self._ticket = 0
             k = self._ticket
             self._ticket += 1
-            plan = self._side.guarded(m.plan_for(x), lambda: m.forward_native(x, keep_intermediates=False))
+            plan = m.forward_native(x, keep_intermediates=False)
             n = x.shape[0]
             pbase, lpaf, _, h, w = m.output_view(plan, 0)
             hbase, lheat, _, _, _ = m.output_view(plan, 1)
@@ -308,8 +303,7 @@ class StreamingPoseEstimator(object):
                                        [(self.h0, self.w0)] * self.B, int(self.config.DATASET.IMAGE_SIZE),
                                        self.mode, s)                      # ONE launch for the whole batch
         check(lib.rtpose_net_set_keep_intermediates(plan.handle, 0))
-        self.side.guarded(plan, lambda: check(lib.rtpose_net_forward_prepared(plan.handle, s),
-                                              "rtpose_net_forward_prepared"))
+        check(lib.rtpose_net_forward_prepared(plan.handle, s), "rtpose_net_forward_prepared")
         pbase, lpaf, _, h, w = m.output_view(plan, 0)
         hbase, lheat, _, _, _ = m.output_view(plan, 1)
         if self.scene is not None:      # bench / tests only, see PoseEstimator.enqueue

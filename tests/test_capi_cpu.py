@@ -273,23 +273,46 @@ def test_decoder_objects_hold_no_packed_fp32_instruction(tmp_path):
     instructions (v_pk_mul_f32 / v_pk_add_f32) and returned wrong scores in lanes 48..63 beside the bf16 plan's kernels
     (~2 launches in 1000); the same source without them: 0 of 240,000.  csrc/Makefile therefore builds decode.hip /
     legacy_pafprocess.hip with -fno-slp-vectorize -fno-vectorize; this test disassembles the gfx950 code of the built
-    objects and refuses any packed-fp32 arithmetic instruction in them."""
+    library and refuses any packed-fp32 arithmetic instruction in the decoder's kernels (the forward's kernels may hold
+    them)."""
     import subprocess
     llvm = "/opt/rocm/lib/llvm/bin"
     tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-objdump")]
     if not all(os.path.exists(t) for t in tools):
         pytest.skip("no ROCm LLVM tools here")
-    build = os.path.join(ROOT, "pytorch_realtime_multi-person_pose_estimation_amd", "csrc", "build")
-    obj = os.path.join(build, "decode.o")
-    if not os.path.exists(obj):
-        pytest.skip("csrc/build/decode.o not built (run __graft_entry__.build())")
-    fat, co = str(tmp_path / "decode.fatbin"), str(tmp_path / "decode.co")
-    subprocess.run([tools[0], "--dump-section", ".hip_fatbin=" + fat, obj], check=True)
-    subprocess.run([tools[1], "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co,
-                    "--unbundle"], check=True)
-    dis = subprocess.run([tools[2], "-d", co], check=True, stdout=subprocess.PIPE, text=True).stdout
-    assert "limb_assign_kernel" in dis and "global_load_dword" in dis        # (it is the device code we are looking at)
-    packed = sorted(set(re.findall(r"\bv_pk_[a-z0-9_]*f32\b", dis)))
-    assert not packed, "packed-fp32 instructions in the decoder's device code: %s" % packed
+    lib = os.path.join(ROOT, "pytorch_realtime_multi-person_pose_estimation_amd", "lib", "librtpose_mi355x.so")
+    if not os.path.exists(lib):
+        pytest.skip("lib/librtpose_mi355x.so not built (run __graft_entry__.build())")
+    fat = str(tmp_path / "lib.fatbin")
+    subprocess.run([tools[0], "--dump-section", ".hip_fatbin=" + fat, lib, str(tmp_path / "lib.discard")], check=True)
+    # one offload bundle per translation unit: unbundle each one's gfx950 code object
+    data = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), data)] + [len(data)]
+    dis = ""
+    for i in range(len(starts) - 1):
+        part, co = str(tmp_path / ("bundle%d" % i)), str(tmp_path / ("bundle%d.co" % i))
+        with open(part, "wb") as f:
+            f.write(data[starts[i]:starts[i + 1]])
+        subprocess.run([tools[1], "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + part,
+                        "--output=" + co, "--unbundle"], check=True)
+        dis += subprocess.run([tools[2], "-d", co], check=True, stdout=subprocess.PIPE, text=True).stdout
+    bodies, cur = {}, None
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
+        if m:
+            cur = bodies.setdefault(m.group(1), [])
+        elif cur is not None:
+            cur.append(line)
+    # the kernels of decode.hip (legacy_pafprocess.hip launches those and defines none of its own)
+    names = ("nms_refine_kernel", "nms_refine_opt_kernel", "peak_prefix_kernel", "limb_assign_kernel", "group_kernel",
+             "clear_header_kernel")
+    for name in names:
+        syms = [s for s in bodies if "%d%s" % (len(name), name) in s]
+        assert syms, "kernel %s not found in the library's device code" % name
+        for s in syms:
+            body = "\n".join(bodies[s])
+            assert "s_endpgm" in body, s                                    # (it is a whole kernel body we are looking at)
+            packed = sorted(set(re.findall(r"\bv_pk_[a-z0-9_]*f32\b", body)))
+            assert not packed, "packed-fp32 instructions in %s: %s" % (s, packed)
     mk = open(os.path.join(ROOT, "pytorch_realtime_multi-person_pose_estimation_amd", "csrc", "Makefile")).read()
     assert re.search(r"build/decode\.o build/legacy_pafprocess\.o: CXXFLAGS \+= -fno-slp-vectorize -fno-vectorize", mk)

@@ -84,8 +84,7 @@ def main():
         imgs = synth_images(idx, HW, dev)
         pre.preprocess_into_plan(plan, [imgs.data_ptr() + k * HW * HW * 3 for k in range(B)], [(HW, HW)] * B, HW, 0, stream)
         capi.check(lib.rtpose_net_set_keep_intermediates(plan.handle, 0))
-        side.guarded(plan, lambda: capi.check(lib.rtpose_net_forward_prepared(plan.handle, stream),
-                                              "rtpose_net_forward_prepared"))
+        capi.check(lib.rtpose_net_forward_prepared(plan.handle, stream), "rtpose_net_forward_prepared")
         pbase, lpaf, _, h, w = model.output_view(plan, 0)
         hbase, lheat, _, _, _ = model.output_view(plan, 1)
         sh, sp = pool[(i0 // B) % len(pool)]

@@ -9,8 +9,7 @@ environment
     PEOPLE=8          every image of the three 16-image batches carries this many people (7-8 peaks per part: the
                       candidates scored by lanes >= 41 of the scoring wave, the ones the round-5 finding hit)
     CU_MASK=1         decoder stream on 32 CUs (hipExtStreamCreateWithCUMask), the forward's stream on the other 224
-    RTPOSE_LIB_PATH, RTPOSE_GUARD_OP=-1 (developer build: the forward waits for the decoder in front of its LAST launch),
-    RTPOSE_LIMB_A32=0|1, RTPOSE_EXP_POISON=1: see csrc/net.hip, csrc/decode.hip
+    RTPOSE_LIB_PATH, RTPOSE_GUARD_FINE=0|1: see csrc/net.hip
 Prints one line per differing record and a summary line per dtype (also as JSON for the session scripts)."""
 import ctypes as C
 import importlib
@@ -209,7 +208,7 @@ def main(steps, dtypes):
         summary[dt] = {"differing": bad, "steps": steps, "repeats": R, "steps_hit": len(bad_steps), "by_repeat": hist,
                        "seconds": round(el, 1)}
     print("SUMMARY " + json.dumps({"env": {k: os.environ.get(k) for k in (
-        "RTPOSE_LIB_PATH", "RTPOSE_GUARD_OP", "RTPOSE_GUARD_FINE", "RTPOSE_LIMB_A32", "RTPOSE_EXP_POISON", "CU_MASK",
+        "RTPOSE_LIB_PATH", "RTPOSE_GUARD_FINE", "CU_MASK",
         "REPEATS", "PEOPLE")}, "result": summary}), flush=True)
 
 
