@@ -127,6 +127,10 @@ typedef struct rtpose_conv_desc {
   int32_t out_plane_pixels; /* the same for the output slice (cout and lout.choff multiples of 8): a chain of F(4x4,3x3)
                    convs keeps its intermediates in planes, its first launch reads and its last one writes pixel-major.
                    rtpose_conv_first_planes writes planes for conv1_1.                                               */
+  const float* prelu; /* device float[>= cout] or NULL: per-output-channel PReLU after the bias, y = x >= 0 ? x : prelu[n] * x
+                   (nn.PReLU(num_parameters = cout), lib/network/openpose.py:56-63); `relu` must then be 0 and `pool` 0.
+                   Taken by the fp32 rtpose_conv2d (k = 1, 3) and the fp32 k = 3 Winograd forms (F(2x2,3x3), F(4x4,3x3));
+                   every other launcher refuses a non-NULL value (RTPOSE_E_INVAL).                                   */
 } rtpose_conv_desc;
 
 /* Launch one conv, or `ngroups` (<= 2) convs of identical geometry in one
@@ -642,6 +646,39 @@ int rtpose_net_launch_info(rtpose_net* net, int i, float* ms, int* k,
  * algorithmic flops / time can exceed the MFMA peak, executed flops / time cannot. */
 int rtpose_net_launch_executed_flops(const rtpose_net* net, int i, double* flops,
                                      int* winograd);
+
+/* ------------------------------------------------------------------------
+ * 3a. The OpenPose_Model network (lib/network/openpose.py:114-210): the same VGG19 trunk with PReLU on
+ *     conv4_2, conv4_3_CPM and conv4_4_CPM, then `l2_stages` PAF stages and `l1_stages` heat-map stages of
+ *     five dense blocks (three 3x3 conv + PReLU, outputs concatenated) and a 1x1 PReLU + 1x1 linear head.
+ *
+ *   OpenPose_Model(l2, l1, paf, heat) -> rtpose_openpose_create + rtpose_net_load_conv x114
+ *                                        + rtpose_net_load_prelu x99
+ *   OpenPose_Model.forward            -> rtpose_net_forward   (openpose.py:160-177)
+ *
+ * The handle is an rtpose_net: bind, load_conv, finalize_weights, conv_numerics, profiling, launch_info,
+ * launch_executed_flops, device_status, output_view and the output guard work on it unchanged.  Conv index
+ * order == the reference module's state_dict order, names are its prefixes ("feature_extractor.21",
+ * "l2_stages.0.Mconv1_0.Mconv", "l1_stages.1.Mconv7").  fp32 only.
+ *   rtpose_net_read_output(which): saved_for_loss flattened - the l2_stages PAF maps, then the l1_stages
+ *     heat maps; only the last of each survive a forward unless keep_intermediates was set.
+ *   rtpose_net_output_view(0 / 1): the last PAF / heat map, where the last stage heads wrote them.
+ * ---------------------------------------------------------------------- */
+typedef struct rtpose_openpose_options {
+  uint32_t struct_bytes; /* sizeof(rtpose_openpose_options) of the caller          */
+  int32_t l2_stages;     /* PAF stages, >= 2                                       */
+  int32_t l1_stages;     /* heat-map stages, >= 2                                  */
+  int32_t paf_channels;  /* 1..64                                                  */
+  int32_t heat_channels; /* 1..64                                                  */
+  int32_t winograd3;     /* as rtpose_net_options.winograd3                        */
+  float amp_limit;       /* as rtpose_net_options.amp_limit                        */
+} rtpose_openpose_options;
+int rtpose_openpose_create(int N, int H, int W, const rtpose_openpose_options* opt, rtpose_net** out);
+/* Slopes (device float[cout]) of the nn.PReLU that follows conv `idx`; RTPOSE_E_INVAL for a conv without one. */
+int rtpose_net_load_prelu(rtpose_net* net, int idx, const float* slope, void* stream);
+/* Host-only: 1 if conv `idx` is followed by a PReLU (its state_dict prefix, e.g. "feature_extractor.22" or
+ * "l2_stages.0.Mconv1_0.MPrelu", goes to `name`), 0 if not, negative on a bad index. */
+int rtpose_net_prelu_info(const rtpose_net* net, int idx, char* name, int name_cap);
 
 /* ------------------------------------------------------------------------
  * 3b. The ShuffleNetV2 x1.0 pose network (lib/network/rtpose_shufflenetV2.py:80-148,

@@ -43,7 +43,7 @@ class ConvDesc(C.Structure):
                 ("out", C.c_void_p), ("lin", Layout), ("lout", Layout), ("cin", C.c_int32),
                 ("cout", C.c_int32), ("k", C.c_int32), ("relu", C.c_int32), ("pool", C.c_int32),
                 ("out_cmap", C.c_void_p), ("wino_m", C.c_int32), ("in_plane_pixels", C.c_int32),
-                ("out_plane_pixels", C.c_int32)]
+                ("out_plane_pixels", C.c_int32), ("prelu", C.c_void_p)]
 
 
 class NetOptions(C.Structure):
@@ -54,6 +54,17 @@ class NetOptions(C.Structure):
     @classmethod
     def make(cls, dtype=0, winograd3=-1, winograd7=-1, amp_limit=0.0):
         return cls(C.sizeof(cls), dtype, winograd3, winograd7, amp_limit)
+
+
+class OpenPoseOptions(C.Structure):
+    """rtpose_openpose_options: topology and fp32 3x3 arithmetic of an OpenPose_Model plan (header §3a)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("l2_stages", C.c_int32), ("l1_stages", C.c_int32),
+                ("paf_channels", C.c_int32), ("heat_channels", C.c_int32), ("winograd3", C.c_int32),
+                ("amp_limit", C.c_float)]
+
+    @classmethod
+    def make(cls, l2_stages, l1_stages, paf_channels, heat_channels, winograd3=-1, amp_limit=0.0):
+        return cls(C.sizeof(cls), l2_stages, l1_stages, paf_channels, heat_channels, winograd3, amp_limit)
 
 
 class PwDesc(C.Structure):
@@ -159,6 +170,9 @@ _SIGS = {
     "rtpose_net_create_ex": (_i, [_i, _i, _i, _i, C.POINTER(_vp)]),
     "rtpose_net_create_opts": (_i, [_i, _i, _i, C.POINTER(NetOptions), C.POINTER(_vp)]),
     "rtpose_net_finalize_weights": (_i, [_vp, _vp]),
+    "rtpose_openpose_create": (_i, [_i, _i, _i, C.POINTER(OpenPoseOptions), C.POINTER(_vp)]),
+    "rtpose_net_load_prelu": (_i, [_vp, _i, _vp, _vp]),
+    "rtpose_net_prelu_info": (_i, [_vp, _i, C.c_char_p, _i]),
     "rtpose_net_conv_numerics": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(C.c_float), _vp]),
     "rtpose_net_device_status": (_i, [_vp, C.POINTER(_i), _vp]),
     "rtpose_net_device_status_async": (_i, [_vp, _vp, _vp]),

@@ -11,9 +11,13 @@ native plans, packed-weight arenas and the keys that say what an arena was packe
   ``load_state_dict`` and ``_apply`` also bump an explicit epoch, ``invalidate_weights()`` is public
   for code that mutates ``.data``, and ``always_resync = True`` re-packs on every forward.
 """
+import ctypes as C
 import threading
 
 import torch
+
+from . import _capi
+from ._capi import lib, check, ptr, current_stream
 
 # Plans (one per input shape) keep their activation workspace alive: ~0.22 GB per 368 x 368 image for
 # rtpose_vgg in fp32.  An MI355X has 288 GB, and an evaluation run over mixed-size images wants one
@@ -105,3 +109,56 @@ class NativeStateMixin(object):
         while mine and (total > cap or len(mine) >= MAX_PLANS_PER_DEVICE):
             total -= size(self._plans.pop(mine.pop(0)))          # evict plans of THIS device only
         self._plans[key] = plan
+
+
+class NetPlanMixin(object):
+    """What the two fronts of the rtpose_net executor (network.RtposeVGG, openpose.OpenPose_Model) do alike with a plan:
+    enqueue a forward, hand out the final maps in place, report the per-conv arithmetic and the device error word.  The
+    class supplies ``plan_for(x)`` and ``_convs()`` (entries whose first element is the conv's state_dict prefix, in the
+    executor's index order)."""
+
+    def conv_numerics(self, plan):
+        """[(state_dict prefix, form, (amp F(2x2,3x3), amp F(4,7), amp F(6,7), amp F(4x4,3x3)))] of a plan: form 0 =
+        direct kernel, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 / 6 = F(m,7); amp = rtpose_winograd_amplification of the
+        loaded filters (0 = n/a)."""
+        out = []
+        form = C.c_int()
+        amp = (C.c_float * 4)()
+        for i, entry in enumerate(self._convs()):
+            check(lib.rtpose_net_conv_numerics(plan.handle, i, C.byref(form), amp, current_stream()))
+            out.append((entry[0], form.value, tuple(amp)))
+        return out
+
+    def device_status(self, plan):
+        """Device-side error word of a plan (0 = fine; synchronises the stream)."""
+        word = C.c_int()
+        check(lib.rtpose_net_device_status(plan.handle, C.byref(word), current_stream()))
+        return word.value
+
+    def device_status_async(self, plan, pinned_word):
+        """Queue the copy of the plan's device error word into `pinned_word` (a pinned int32 tensor of one element)
+        on the current stream, without waiting; read it after an event recorded later on that stream."""
+        check(lib.rtpose_net_device_status_async(plan.handle, pinned_word.data_ptr(), current_stream()))
+
+    def forward_native(self, x, keep_intermediates=False):
+        """Enqueue the forward; returns the plan (outputs stay in its workspace)."""
+        if not x.is_cuda:
+            self.plan_for(x)  # raises: no CPU fallback
+        with torch.cuda.device(x.device):
+            plan = self.plan_for(x)
+            xin = x.detach()
+            if xin.dtype != torch.float32 or not xin.is_contiguous():
+                xin = xin.float().contiguous()
+            check(lib.rtpose_net_set_keep_intermediates(plan.handle, 1 if keep_intermediates else 0))
+            check(lib.rtpose_net_forward(plan.handle, ptr(xin), current_stream()), "rtpose_net_forward")
+            self._last_input = xin  # keep alive until the stream has consumed it
+        return plan
+
+    def output_view(self, plan, which):
+        """(base pointer, Layout, C, H, W) of the final PAF (0) / heat-map (1), in place."""
+        base = C.c_void_p()
+        lay = _capi.Layout()
+        c, h, w = C.c_int(), C.c_int(), C.c_int()
+        check(lib.rtpose_net_output_view(plan.handle, which, C.byref(base), C.byref(lay), C.byref(c),
+                                         C.byref(h), C.byref(w)))
+        return base, lay, c.value, h.value, w.value

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
 
 // 1: the launch below takes the conv (else the generic kernel does)
 int conv_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int out_f32, int split) {
-  if (!d || ngroups != 1 || out_f32 || split) return 0;
+  if (!d || ngroups != 1 || out_f32 || split || d[0].prelu) return 0;
   const rtpose_conv_desc& c = d[0];
   if (c.k != 3 || c.cin != 64 || c.cout < 64 || (c.cout % 64) || c.out_cmap || c.in_plane_pixels || c.out_plane_pixels) return 0;
   if ((c.lin.cstride % 8) || (c.lin.choff % 8) || c.lin.choff + 64 > c.lin.cstride) return 0;
@@ -312,6 +312,7 @@ int conv_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int
 
 int conv_c64_bf16_launch(const rtpose_conv_desc* d, int N, int H, int W, hipStream_t s) {
   using namespace c64;
+  RTPOSE_REFUSE_PRELU(d, 1, "conv_c64_bf16");
   if (!conv_c64_bf16_fits(d, 1, N, H, W, 0, 0) || N <= 0 || H <= 0 || W <= 0)
     return fail(RTPOSE_E_INVAL, "conv_c64_bf16: needs a 3x3 conv of 64 bf16 input channels into 16-byte aligned slices");
   const rtpose_conv_desc& c = d[0];

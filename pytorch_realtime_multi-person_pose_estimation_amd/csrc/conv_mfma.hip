@@ -1,5 +1,6 @@
 // fp32 implicit-GEMM convolution for gfx950 (MI355X), stride 1, "same" padding,
-// k in {1,3,7}, fused bias (+ReLU) (+2x2 max-pool).
+// k in {1,3,7}, fused bias (+ReLU) (+2x2 max-pool), or bias + per-channel PReLU (k = 1, 3: the
+// nn.PReLU of lib/network/openpose.py:56-63; a separate instantiation, see ConvArgsP).
 //
 // Stands in for the nn.Conv2d / nn.ReLU / nn.MaxPool2d modules instantiated by
 // lib/network/rtpose_vgg.py:23-35 and :49-55 (ATen kernels on the reference).
@@ -29,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 
@@ -71,6 +73,14 @@ struct ConvArgs {
   int dephase_cycles, n_cu;  // start-up delay that puts the 2 blocks of a CU half a tile apart
 };
 
+// PReLU launches: the slopes of the two groups follow the arguments the other instantiations read, so those keep
+// their argument offsets and instruction streams
+struct ConvArgsP : ConvArgs {
+  const float* prelu[2];  // float[cout] per group
+};
+template <bool PR>
+using ConvArgsT = typename std::conditional<PR, ConvArgsP, ConvArgs>::type;
+
 constexpr int kBM = 128;
 // 1x1 convs: CK-channel sub-chunks per LDS buffer (see conv_tile; 4: -20 % on the 1x1 layers)
 constexpr int kTB1x1 = 1;
@@ -100,9 +110,9 @@ __device__ __forceinline__ void tile_local_yx(int ml, int tw_log2, int& ty, int&
 // NF = 32-column N fragments per wave: 1 -> block tile 128 x 64, 2 -> 128 x 128 (wave tile
 // 64 x 64).  NF = 2 halves the B (weight) and A (LDS) operand bytes per MFMA; measured, the B
 // loads cost ~4.6 % of the forward and half of them ~2 %.
-template <int KS, int CK, int MODE, int NBUF, int MF, int NF>
+template <int KS, int CK, int MODE, int NBUF, int MF, int NF, bool PR = false>
 __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g, const int m0_arg,
-                                          const int ntile, float* smem) {
+                                          const int ntile, float* smem, const float* prelu = nullptr) {
   constexpr int P = KS / 2;
   constexpr int BMT = 64 * MF;  // pixels per block tile
   constexpr int CG = CK / 4;  // 16-byte channel groups per chunk
@@ -286,6 +296,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
     for (int fm = 0; fm < MF; ++fm)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[fm][fn][r] = b0;
+  }
+  float slope[NF];  // PReLU: fetched with the bias, for the same reason
+#pragma unroll
+  for (int fn = 0; fn < NF; ++fn) {
+    slope[fn] = 0.f;
+    if constexpr (PR) slope[fn] = ncol + fn * 32 < g.cout ? prelu[ncol + fn * 32] : 0.f;
   }
 
   // LDS float4 offsets of this lane's A fragments inside a halo buffer: [k-group][m-frag]
@@ -501,6 +517,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
           }
           float v = acc[fm][fn][rg * 4 + rr];
           if (A.relu) v = fmaxf(v, 0.f);
+          if constexpr (PR) v = prelu1(v, slope[fn]);
           if (ok && col_ok) {
             const size_t q = (size_t)g.out_lead + (size_t)(n * g.out_hs + y) * g.out_ws + x;
             out_base[q * g.out_cstride] = v;
@@ -541,8 +558,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
 //    = 14 reads of every input pixel of conv4_2 before this).
 //  * MODE 0 (strip) tail: ids [0, nbig) are 128-pixel tiles; the rest are pairs of 64-pixel
 //    halves of the remaining tiles, dispatched last (see plan in conv2d_launch).
-template <int KS, int CK, int MODE, int NBUF, int NF>
-__global__ __launch_bounds__(256, NBUF == 1 ? 4 : 2) void conv_mfma_f32(const ConvArgs A) {
+template <int KS, int CK, int MODE, int NBUF, int NF, bool PR = false>
+__global__ __launch_bounds__(256, NBUF == 1 ? 4 : 2) void conv_mfma_f32(const ConvArgsT<PR> A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int L = blockIdx.x;
   // Equal tiles keep the two co-resident blocks of a CU in lock step, so their prologues
@@ -566,13 +583,15 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 4 : 2) void conv_mfma_f32(const Co
   }
   if (mt >= A.mtiles) return;  // padding ids of the remapped order
   const int nt = c % A.ntiles, grp = c / A.ntiles;
+  const float* prelu = nullptr;
+  if constexpr (PR) prelu = grp ? A.prelu[1] : A.prelu[0];
   if (MODE == 1) {
-    conv_tile<KS, CK, MODE, NBUF, 2, NF>(A, A.g[grp], mt, nt, smem);
+    conv_tile<KS, CK, MODE, NBUF, 2, NF, PR>(A, A.g[grp], mt, nt, smem, prelu);
   } else if (!small) {
-    conv_tile<KS, CK, MODE, NBUF, 2, NF>(A, A.g[grp], mt * kBM, nt, smem);
+    conv_tile<KS, CK, MODE, NBUF, 2, NF, PR>(A, A.g[grp], mt * kBM, nt, smem, prelu);
   } else {
     const int m0 = mt * kBM + ((L - A.nbig) & 1) * (kBM / 2);
-    if (m0 < A.M) conv_tile<KS, CK, MODE, NBUF, 1, NF>(A, A.g[grp], m0, nt, smem);
+    if (m0 < A.M) conv_tile<KS, CK, MODE, NBUF, 1, NF, PR>(A, A.g[grp], m0, nt, smem, prelu);
   }
 }
 
@@ -689,11 +708,11 @@ static int plan_conv(const rtpose_conv_desc& d, int N, int H, int W, ConvPlan* p
   return 0;
 }
 
-template <int KS, int CK, int MODE, int NBUF, int NF>
-static int launch_inst(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+template <int KS, int CK, int MODE, int NBUF, int NF, bool PR = false>
+static int launch_inst(const ConvArgsT<PR>& a, dim3 grid, size_t lds, hipStream_t s) {
   static PerDeviceOnce attr_set;  // zero-initialised; the attribute is per device
   const int dev = current_device();
-  auto kern = conv_mfma_f32<KS, CK, MODE, NBUF, NF>;
+  auto kern = conv_mfma_f32<KS, CK, MODE, NBUF, NF, PR>;
   if (!attr_set.is_set(dev)) {
     RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -707,8 +726,11 @@ static int launch_inst(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) 
 int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
   if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d: ngroups must be 1 or 2");
   RTPOSE_REFUSE_PLANES(d, ngroups, "conv2d");
+  RTPOSE_CHECK_PRELU(d, ngroups, "conv2d");
   const rtpose_conv_desc& d0 = d[0];
   if (d0.k != 1 && d0.k != 3 && d0.k != 7) return fail(RTPOSE_E_INVAL, "conv2d: k must be 1, 3 or 7");
+  if (d0.prelu && (d0.k == 7 || d[0].out_cmap || (ngroups > 1 && d[1].out_cmap)))
+    return fail(RTPOSE_E_INVAL, "conv2d: the PReLU epilogue exists for k = 1 and 3 without out_cmap");
   if (d0.cin % 8 != 0 || d0.cin <= 0) return fail(RTPOSE_E_INVAL, "conv2d: cin must be a multiple of 8");
   if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "conv2d: empty tensor");
   const int P = d0.k / 2;
@@ -787,6 +809,25 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
     if (total <= n_cu) a.nbig = 0;
   }
   dim3 grid((unsigned)(a.nbig + 2 * (ids - a.nbig)), 1, 1);
+  if (d0.prelu) {
+    ConvArgsP ap;
+    static_cast<ConvArgs&>(ap) = a;
+    ap.prelu[0] = d[0].prelu;
+    ap.prelu[1] = ngroups > 1 ? d[1].prelu : d[0].prelu;
+#define RTPOSE_CONV_CASE_P(KS_, CK_, MODE_)            \
+  if (d0.k == KS_ && pl.ck == CK_ && pl.mode == MODE_) \
+    return launch_inst<KS_, CK_, MODE_, KS_ == 1 ? 1 : 2, 1, true>(ap, grid, pl.lds_bytes, s);
+    RTPOSE_CONV_CASE_P(3, 8, 0)
+    RTPOSE_CONV_CASE_P(3, 8, 1)
+    RTPOSE_CONV_CASE_P(3, 16, 0)
+    RTPOSE_CONV_CASE_P(3, 16, 1)
+    RTPOSE_CONV_CASE_P(1, 16, 0)
+    RTPOSE_CONV_CASE_P(1, 16, 1)
+    RTPOSE_CONV_CASE_P(1, 8, 0)
+    RTPOSE_CONV_CASE_P(1, 8, 1)
+#undef RTPOSE_CONV_CASE_P
+    return fail(RTPOSE_E_INVAL, "conv2d: no PReLU kernel instance for k=%d ck=%d mode=%d", d0.k, pl.ck, pl.mode);
+  }
 #define RTPOSE_CONV_CASE(KS_, CK_, MODE_)                \
   if (d0.k == KS_ && pl.ck == CK_ && pl.mode == MODE_) \
     return launch_inst<KS_, CK_, MODE_, KS_ == 1 ? 1 : 2, 1>(a, grid, pl.lds_bytes, s);

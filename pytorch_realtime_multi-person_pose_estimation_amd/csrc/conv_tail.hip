@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void tail_kernel(const Args A
 // Two grouped 1x1 convs back to back: d1[g] = 128 -> 128 | 512 (+ReLU), d2[g] = that -> cout2 <= 64 (no ReLU) reading d1[g]'s
 // output, which is never written.  Descriptors as for rtpose_conv2d (k = 1, plain packing); d1[g].out / lout are ignored.
 int conv_tail_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups) {
-  if (!d1 || !d2 || ngroups < 1 || ngroups > 2) return 0;
+  if (!d1 || !d2 || ngroups < 1 || ngroups > 2 || desc_has_prelu(d1, ngroups) || desc_has_prelu(d2, ngroups)) return 0;
   for (int i = 0; i < ngroups; ++i) {
     if (d1[i].k != 1 || d2[i].k != 1 || d1[i].cin != tail::KC || (d1[i].cout != tail::N1 && d1[i].cout != 4 * tail::N1) ||
         d1[i].cout != d1[0].cout || d2[i].cin != d1[i].cout ||
@@ -196,6 +196,8 @@ int conv_tail_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int n
 int conv_tail_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N, int H, int W,
                      hipStream_t s) {
   using namespace tail;
+  RTPOSE_REFUSE_PRELU(d1, ngroups, "conv_tail");
+  RTPOSE_REFUSE_PRELU(d2, ngroups, "conv_tail");
   if (!conv_tail_fits(d1, d2, ngroups) || N <= 0 || H <= 0 || W <= 0)
     return fail(RTPOSE_E_INVAL, "conv_tail: needs 128 -> 128 | 512 (+ReLU) -> <= 64 pointwise convs");
   RTPOSE_REFUSE_PLANES(d1, ngroups, "conv_tail");

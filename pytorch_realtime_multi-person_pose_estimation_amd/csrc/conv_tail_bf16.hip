@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void tail_bf16_kernel(const Args A) {
 // d1[g] / d2[g]: the two convs of branch g (k = 1; d1: 128 -> 128 | 512 with ReLU, d2: -> cout <= 64).  d1[g].in / lin: bf16
 // input (16-byte aligned slices); d2[g].out / lout: bf16 elements, or fp32 when out_f32; d1[g].out is not touched.
 int conv_tail_bf16_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups) {
-  if (!d1 || !d2 || ngroups < 1 || ngroups > 2) return 0;
+  if (!d1 || !d2 || ngroups < 1 || ngroups > 2 || desc_has_prelu(d1, ngroups) || desc_has_prelu(d2, ngroups)) return 0;
   for (int g = 0; g < ngroups; ++g) {
     if (d1[g].k != 1 || d2[g].k != 1 || d1[g].cin != tailb::KC || !d1[g].relu || d1[g].pool || d2[g].pool) return 0;
     if (d1[g].cout != 128 && d1[g].cout != 512) return 0;
@@ -235,6 +235,8 @@ int conv_tail_bf16_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, 
 int conv_tail_bf16_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N, int H, int W,
                           int out_f32, hipStream_t s) {
   using namespace tailb;
+  RTPOSE_REFUSE_PRELU(d1, ngroups, "conv1x1_pair_bf16");
+  RTPOSE_REFUSE_PRELU(d2, ngroups, "conv1x1_pair_bf16");
   if (!conv_tail_bf16_fits(d1, d2, ngroups))
     return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: not a 128 -> 128 | 512 (ReLU) -> <= 64 pair of 1x1 convs on 16-byte aligned bf16 slices");
   if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: empty tensor");

@@ -33,6 +33,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "wino_common.h"
@@ -66,8 +67,21 @@ struct Args {
   int persist;  // 1: gridDim.x persistent blocks; block p keeps (n tile, group) p % ncombo and walks every (gridDim.x / ncombo)-th m tile
 };
 
-template <int WM, int WN, int CK>
-__global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
+// PReLU launches (rtpose_conv_desc.prelu): the slopes follow the arguments the other instantiations read, so those keep
+// their argument offsets and instruction streams
+struct ArgsP : Args {
+  const float* prelu[2];  // float[cout] per group
+};
+template <bool PR>
+using ArgsT = typename std::conditional<PR, ArgsP, Args>::type;
+template <bool PR>
+__device__ __forceinline__ float slope_of(const ArgsT<PR>& A, int grp, int ncol, int cout) {
+  if constexpr (PR) return ncol < cout ? (grp ? A.prelu[1] : A.prelu[0])[ncol] : 0.f;
+  return 0.f;
+}
+
+template <int WM, int WN, int CK, bool PR = false>
+__global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
   constexpr int NT = 32 * WM;  // wtiles per block
   constexpr int CG = CK / 4;   // 16-byte channel groups per chunk
   constexpr int G = CK / 8;    // 8-deep k groups per chunk (4 MFMAs each)
@@ -193,6 +207,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
   const int arow = wm * 32 + l31;
   floatx16 acc[16];
   const float bias0 = g.bias[ncol];  // padded to cout_pad
+  const float slope0 = slope_of<PR>(A, grp, ncol, g.cout);
   // B: lane offset (k half, column) in one register; (frequency of the pair, k group) and the step in the scalar offset
   const unsigned boff = (unsigned)((kh * g.cout_pad + ncol) * 16);
   const unsigned cgstep = (unsigned)(g.cout_pad * 16);     // bytes per channel group plane
@@ -391,6 +406,10 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) y[i >> 1][i & 1] = fmaxf(y[i >> 1][i & 1], 0.f);
         }
+        if constexpr (PR) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) y[i >> 1][i & 1] = prelu1(y[i >> 1][i & 1], slope0);
+        }
         const bool ok = col_ok && tcur < A.T;
         const unsigned off = (unsigned)(wt_q(sn, sy, sx) - q0) * cs4 + col4;
         if (A.pool) {  // H and W even: every wtile is one pooled pixel
@@ -420,7 +439,8 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const Args A) {
 // LDS before the output transform.  Every frequency sum runs over the chunks, k groups and k pairs in the order of
 // wino_f32, the output transform is the same expression: bit-identical results, 4x (128-column blocks) or 2x
 // (64-column blocks) as many blocks.  16-channel chunks only.
-__global__ __launch_bounds__(256, 1) void wino3s_f32(const Args A) {
+template <bool PR = false>
+__global__ __launch_bounds__(256, 1) void wino3s_f32(const ArgsT<PR> A) {
   constexpr int NT = 32, CK = 16, CG = 4, G = 2, SW = 8 / CG;
   constexpr int VBUF = 16 * CG * NT;  // float4 per V buffer
   extern __shared__ __attribute__((aligned(16))) float4 V4[];
@@ -486,6 +506,7 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const Args A) {
 
   // ---- MFMA role: frequencies 4 wv .. 4 wv + 3 of the 32 x 32 tile ---------------------------------------
   const int ncol = nt * 32 + l31;
+  const float slope0 = slope_of<PR>(A, grp, ncol, g.cout);
   floatx16 acc[4];
 #pragma unroll
   for (int f = 0; f < 4; ++f)
@@ -616,6 +637,10 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const Args A) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) y[i >> 1][i & 1] = fmaxf(y[i >> 1][i & 1], 0.f);
       }
+      if constexpr (PR) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[i >> 1][i & 1] = prelu1(y[i >> 1][i & 1], slope0);
+      }
       const bool ok = col_ok && tcur < A.T;
       const unsigned off = (unsigned)(wt_q(sn, sy, sx) - q0) * cs4 + col4;
       if (A.pool) {
@@ -674,11 +699,11 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, const float* __res
   wp[i] = v;
 }
 
-template <int WM, int WN, int CK>
-static int launch_inst(const Args& a, dim3 grid, hipStream_t s) {
+template <int WM, int WN, int CK, bool PR = false>
+static int launch_inst(const ArgsT<PR>& a, dim3 grid, hipStream_t s) {
   static PerDeviceOnce attr_set;
   const int dev = current_device();
-  auto kern = wino_f32<WM, WN, CK>;
+  auto kern = wino_f32<WM, WN, CK, PR>;
   constexpr size_t lds = (size_t)2 * 16 * (CK / 4) * (32 * WM) * 16;
   if (!attr_set.is_set(dev)) {
     RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -702,10 +727,42 @@ int conv2d_wino_ok(int cin, int cout, int k) {
   return k == 3 && cin > 0 && cin % wino_ck(cout, cin) == 0 && cin / wino_ck(cout, cin) >= 2;
 }
 
+namespace {
+// the launch of one F(2x2,3x3) layer (see conv2d_wino_launch); PR: the PReLU instantiations
+template <bool PR>
+int wino_run(wino::ArgsT<PR> a, long ids, int ngroups, int ck, int wm, int cout0, hipStream_t s) {
+  using namespace wino;
+  const dim3 grid((unsigned)ids, 1, 1);
+  if (ck == 16 && !a.persist && (long)a.mtiles * a.ncombo * 2 <= device_cu_count()) {
+    // small grids: the frequency-split form (wino3s_f32), bit-identical, 32 x 32 tiles
+    ArgsT<PR> b = a;
+    b.mtiles = ceil_div(a.T, 32);
+    b.ntiles = cout_pad(cout0) / 32;
+    b.ncombo = b.ntiles * ngroups;
+    static PerDeviceOnce attr_set;
+    const int dev = current_device();
+    if (!attr_set.is_set(dev)) {
+      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino3s_f32<PR>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+      attr_set.set(dev);
+    }
+    hipLaunchKernelGGL(wino3s_f32<PR>, dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(256),
+                       (size_t)2 * 16 * 4 * 32 * 16, s, b);
+    RTPOSE_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
+  if (wm == 1) return launch_inst<1, 4, 16, PR>(a, grid, s);
+  // 64 columns (conv1_2): 64 wtiles x 64 columns; 16-channel chunks with a whole patch per thread where cin allows
+  if (ck == 16) return launch_inst<2, 2, 16, PR>(a, grid, s);
+  return launch_inst<2, 2, 8, PR>(a, grid, s);
+}
+}  // namespace
+
 int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
   using namespace wino;
   if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d_winograd: ngroups must be 1 or 2");
   RTPOSE_REFUSE_PLANES(d, ngroups, "conv2d_winograd (2x2)");
+  RTPOSE_CHECK_PRELU(d, ngroups, "conv2d_winograd (2x2)");
   const rtpose_conv_desc& d0 = d[0];
   if (!conv2d_wino_ok(d0.cin, d0.cout, d0.k))
     return fail(RTPOSE_E_INVAL, "conv2d_winograd: k must be 3 and cin a multiple of %d", wino_ck(d0.cout, d0.cin));
@@ -774,29 +831,12 @@ int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
       ids = n_cu;
     }
   }
-  const dim3 grid((unsigned)ids, 1, 1);
-  if (ck == 16 && !a.persist && (long)a.mtiles * a.ncombo * 2 <= device_cu_count()) {
-    // small grids: the frequency-split form (wino3s_f32), bit-identical, 32 x 32 tiles
-    Args b = a;
-    b.mtiles = ceil_div(a.T, 32);
-    b.ntiles = cout_pad(d0.cout) / 32;
-    b.ncombo = b.ntiles * ngroups;
-    static PerDeviceOnce attr_set;
-    const int dev = current_device();
-    if (!attr_set.is_set(dev)) {
-      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino3s_f32),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      attr_set.set(dev);
-    }
-    hipLaunchKernelGGL(wino3s_f32, dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(256),
-                       (size_t)2 * 16 * 4 * 32 * 16, s, b);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (wm == 1) return launch_inst<1, 4, 16>(a, grid, s);
-  // 64 columns (conv1_2): 64 wtiles x 64 columns; 16-channel chunks with a whole patch per thread where cin allows
-  if (ck == 16) return launch_inst<2, 2, 16>(a, grid, s);
-  return launch_inst<2, 2, 8>(a, grid, s);
+  if (!d0.prelu) return wino_run<false>(a, ids, ngroups, ck, wm, d0.cout, s);
+  ArgsP ap;
+  static_cast<Args&>(ap) = a;
+  ap.prelu[0] = d[0].prelu;
+  ap.prelu[1] = ngroups > 1 ? d[1].prelu : d[0].prelu;
+  return wino_run<true>(ap, ids, ngroups, ck, wm, d0.cout, s);
 }
 
 int pack_weights_wino_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map,
@@ -859,6 +899,7 @@ static bool wino_m_valid(const rtpose_conv_desc* d) {
 
 int rtpose_conv2d_winograd_fits(const rtpose_conv_desc* d, int N, int H, int W) {
   if (!d || !wino_m_valid(d)) return 0;
+  if (d->prelu && (d->k != 3 || d->pool || d->relu)) return 0;  // the PReLU epilogue: k = 3 forms, no ReLU, no fused pool
   return rtpose::conv2d_winograd_fits(d->k, d->cin, d->cout, d->pool, N, H, W, d->lin.hs, d->wino_m == 2 ? 0 : d->wino_m);
 }
 

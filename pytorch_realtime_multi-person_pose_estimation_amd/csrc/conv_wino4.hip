@@ -102,6 +102,19 @@ struct Args {
   int mt0;  // first m tile of this launch (a layer may run as a persistent launch of whole rounds + a launch of the rest)
 };
 
+// PReLU launches (rtpose_conv_desc.prelu): the slopes follow the arguments the other instantiations read, so those keep
+// their argument offsets and instruction streams
+struct ArgsP : Args {
+  const float* prelu[2];  // float[cout] per group
+};
+template <bool PR>
+using ArgsT = typename std::conditional<PR, ArgsP, Args>::type;
+template <bool PR>
+__device__ __forceinline__ float slope_of(const ArgsT<PR>& A, int grp, int ncol, int cout) {
+  if constexpr (PR) return ncol < cout ? (grp ? A.prelu[1] : A.prelu[0])[ncol] : 0.f;
+  return 0.f;
+}
+
 constexpr int NT = 32;    // wtiles per block
 constexpr int NC = 64;    // output columns per block
 constexpr int CK = 8;     // channels per chunk
@@ -159,8 +172,8 @@ __device__ __forceinline__ void at4_hi(const f2 (&m)[6], f2& y2, f2& y3) {
 // items are spread as in wino4s_f32 (waves 0..2: two patch rows each, waves 3..5: two fx each), and before the output
 // transform the siblings split the row tile by wtile PAIRS: wave (fh, wn) finishes the wtiles 4 kq + 2 fh, + 1 and hands the
 // first-pass row sums of the other pair over.  One tile per block (never persistent).
-template <int RT>
-__global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
+template <int RT, bool PR = false>
+__global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
   constexpr int NT = 16 * RT;           // (shadow the 32-wtile constants of the namespace inside the kernel)
   constexpr int VBUF = NFP * 4 * NT;
   constexpr int UBUF = 36 * 2 * NT;
@@ -285,6 +298,7 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
   const int ncol = nt * NC + wn * 16 + r16;
   floatx4 acc[NFW][RT];
   const float bias0 = g.bias[ncol];
+  const float slope0 = slope_of<PR>(A, grp, ncol, g.cout);
   const unsigned boff = (unsigned)((kq * g.cout_pad + ncol) * 16);
   const unsigned fstep = (unsigned)(4 * g.cout_pad * 16);  // bytes per (chunk, frequency pair)
   const unsigned wbase = (unsigned)fh * (NPW * fstep);
@@ -542,6 +556,10 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const Args A) {
                 const int i = 2 * ih + il;
                 f2 o = yy[il][j] + splat(bias0);
                 if (A.relu) o = __builtin_elementwise_max(o, splat(0.f));
+                if constexpr (PR) {
+                  o[0] = prelu1(o[0], slope0);
+                  o[1] = prelu1(o[1], slope0);
+                }
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                   const bool ok = okv[e] && i < ylim[e] && j < xlim[e];
@@ -569,7 +587,8 @@ constexpr int NTS = 16;                   // wtiles per block
 constexpr int VBUFS = NFP * 4 * NTS;      // float4 per V buffer: [pair][kq][wtile]
 constexpr int UBUFS = 36 * 2 * NTS;       // float4 per U buffer: [fx][y][channel group][wtile ^ 4 cg]
 
-__global__ __launch_bounds__(384, 2) void wino4s_f32(const Args A) {
+template <bool PR = false>
+__global__ __launch_bounds__(384, 2) void wino4s_f32(const ArgsT<PR> A) {
   extern __shared__ __attribute__((aligned(16))) float4 L4[];
   auto Vb = [&](int i) -> float4* { return L4 + i * VBUFS; };
   auto Ub = [&](int i) -> float4* { return L4 + 2 * VBUFS + i * UBUFS; };
@@ -745,6 +764,8 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const Args A) {
       }
       const bool col_ok = ncol < g.cout;
       const float bias0 = g.bias[ncol];
+      float slope0 = 0.f;
+      if constexpr (PR) slope0 = slope_of<PR>(A, grp, ncol, g.cout);
       const int sc = A.pool ? 2 : 4;
       auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.out_hs + sc * ty) * g.out_ws + sc * tx; };
       int q0;
@@ -802,6 +823,10 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const Args A) {
             const int i = 2 * ih + il;
             f2 o = yy[il][j] + splat(bias0);
             if (A.relu) o = __builtin_elementwise_max(o, splat(0.f));
+            if constexpr (PR) {
+              o[0] = prelu1(o[0], slope0);
+              o[1] = prelu1(o[1], slope0);
+            }
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
               const bool ok = okv[e] && i < ylim[e] && j < xlim[e];
@@ -907,9 +932,98 @@ int conv2d_wino4_ok(int cin, int cout) { return cout > 0 && cin % 16 == 0 && cin
 
 size_t packed_weight_floats_wino4(int cout, int cin) { return (size_t)36 * cin * cout_pad(cout); }
 
+namespace {
+// the launches of one F(4x4,3x3) layer (see conv2d_wino4_launch); PR: the PReLU instantiations
+template <bool PR>
+int wino4_run(wino4::ArgsT<PR> a, long ids, int ngroups, int cout0, hipStream_t s) {
+  using namespace wino4;
+  const int n_cu = device_cu_count();
+  auto launch_small = [&](const ArgsT<PR>& a0, int mt0_32, long wtiles) -> int {
+    // the 16 x 16 form (wino4s_f32<PR>), bit-identical, 8x the blocks: `wtiles` wtiles from m tile mt0_32 (in 32-wtile units) on
+    ArgsT<PR> b = a0;
+    b.persist = 0;
+    b.mt0 = 2 * mt0_32;
+    b.mtiles = (int)((wtiles + NTS - 1) / NTS);
+    b.ntiles = cout_pad(cout0) / 16;
+    b.ncombo = b.ntiles * ngroups;
+    static PerDeviceOnce attr_s;
+    const int dev_s = current_device();
+    if (!attr_s.is_set(dev_s)) {
+      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4s_f32<PR>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+      attr_s.set(dev_s);
+    }
+    hipLaunchKernelGGL(wino4s_f32<PR>, dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(384),
+                       (size_t)(2 * VBUFS + 2 * UBUFS) * sizeof(float4), s, b);
+    RTPOSE_HIP_CHECK(hipGetLastError());
+    return 0;
+  };
+  auto launch_half = [&](const ArgsT<PR>& a0, int mt0_32, long wtiles) -> int {
+    // half tiles (wino4_f32<1, PR>: 16 wtiles x 64 columns, one per block), bit-identical: `wtiles` wtiles from m tile mt0_32 on
+    ArgsT<PR> b = a0;
+    b.persist = 0;
+    b.mt0 = 2 * mt0_32;
+    b.mtiles = (int)((wtiles + 15) / 16);
+    b.xcd_remap = (b.ncombo > 1 && b.mtiles >= 64) ? 1 : 0;
+    const long idh = b.xcd_remap ? (long)8 * b.ncombo * ceil_div(b.mtiles, 8) : (long)b.mtiles * b.ncombo;
+    static PerDeviceOnce attr_h;
+    const int dev_h = current_device();
+    if (!attr_h.is_set(dev_h)) {
+      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_f32<1, PR>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+      attr_h.set(dev_h);
+    }
+    hipLaunchKernelGGL((wino4_f32<1, PR>), dim3((unsigned)idh), dim3(512), (size_t)(VBUF + UBUF) * sizeof(float4), s, b);
+    RTPOSE_HIP_CHECK(hipGetLastError());
+    return 0;
+  };
+  // launches that fill at most half the CUs with 32 x 64 tiles run the 16 x 16 form (measured: at one round and beyond
+  // the big tiles win - the small form fetches the filters four times as often; ee158f6:tools/r3_sessions/session27.sh)
+  if ((long)a.mtiles * a.ncombo * 2 <= n_cu) return launch_small(a, 0, a.T);
+  int rest = 0;  // m tiles left to a second launch
+  bool rest_half = false;  // ... in half tiles (else the 16 x 16 form)
+  if ((long)a.mtiles * a.ncombo > n_cu && n_cu % (8 * a.ncombo) == 0) {
+    // Persistent blocks: block (column tile / group c, q) takes the m tiles q, q + Pc, ...  When the tiles do not come out
+    // as whole rounds and what is left over is at most a quarter of a round, the whole rounds run here and the rest as a
+    // second launch in the 16 x 16 form: 2 rounds + a short launch instead of 3 (conv4_3_CPM, the stage-1 convs: 0.60 ->
+    // 0.53 ms, 0.17 -> 0.155), 1 + a short one instead of 2 (conv4_4_CPM: 0.21 -> 0.15).  Half a round left over is
+    // cheaper as a half-empty round of big tiles (conv4_1 / conv4_2: 0.51 -> 0.54 ms with the cut), and at 8.27 rounds
+    // (conv3_x) the cut changes nothing.  The forms are bit-identical, so the cut is invisible in the results.
+    const int Pc = n_cu / a.ncombo;
+    const int r = a.mtiles % Pc;
+    if (r && (long)r * a.ncombo * 4 <= n_cu) {  // at most a quarter of a round left over
+      rest = r;
+      a.mtiles -= r;
+    } else if (r && 2L * r * a.ncombo <= n_cu) {
+      // Round 4: up to half a round left over runs as ONE round of half tiles (16 wtiles x 64 columns: half the multiplies of a
+      // tile, the same transform work per wtile) instead of a round of big tiles that leaves 50..75 % of the CUs idle:
+      // conv3_x 8.27 rounds -> 8 + a half-tile round, conv4_1 / conv4_2 4.5 -> 4 + one.
+      rest = r;
+      rest_half = true;
+      a.mtiles -= r;
+    }
+    a.persist = 1;
+    ids = n_cu;
+  }
+  static PerDeviceOnce attr_set;
+  const int dev = current_device();
+  if (!attr_set.is_set(dev)) {
+    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_f32<2, PR>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    attr_set.set(dev);
+  }
+  hipLaunchKernelGGL((wino4_f32<2, PR>), dim3((unsigned)ids), dim3(512), (size_t)(2 * VBUF + 2 * UBUF) * sizeof(float4), s, a);
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  if (rest && rest_half) return launch_half(a, a.mtiles, (long)a.T - (long)a.mtiles * NT);
+  if (rest) return launch_small(a, a.mtiles, (long)a.T - (long)a.mtiles * NT);
+  return 0;
+}
+}  // namespace
+
 int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
   using namespace wino4;
   if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d_winograd (4x4): ngroups must be 1 or 2");
+  RTPOSE_CHECK_PRELU(d, ngroups, "conv2d_winograd (4x4)");
   const rtpose_conv_desc& d0 = d[0];
   if (d0.k != 3 || !conv2d_wino4_ok(d0.cin, d0.cout))
     return fail(RTPOSE_E_INVAL, "conv2d_winograd (4x4): k must be 3 and cin a multiple of 16, >= 32");
@@ -984,86 +1098,12 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
   a.xcd_remap = (a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
   long ids = a.xcd_remap ? (long)8 * a.ncombo * ceil_div(a.mtiles, 8) : (long)a.mtiles * a.ncombo;
   if (ids > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d_winograd: grid too large");
-  const int n_cu = device_cu_count();
-  auto launch_small = [&](const Args& a0, int mt0_32, long wtiles) -> int {
-    // the 16 x 16 form (wino4s_f32), bit-identical, 8x the blocks: `wtiles` wtiles from m tile mt0_32 (in 32-wtile units) on
-    Args b = a0;
-    b.persist = 0;
-    b.mt0 = 2 * mt0_32;
-    b.mtiles = (int)((wtiles + NTS - 1) / NTS);
-    b.ntiles = cout_pad(d0.cout) / 16;
-    b.ncombo = b.ntiles * ngroups;
-    static PerDeviceOnce attr_s;
-    const int dev_s = current_device();
-    if (!attr_s.is_set(dev_s)) {
-      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4s_f32),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-      attr_s.set(dev_s);
-    }
-    hipLaunchKernelGGL(wino4s_f32, dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(384),
-                       (size_t)(2 * VBUFS + 2 * UBUFS) * sizeof(float4), s, b);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-    return 0;
-  };
-  auto launch_half = [&](const Args& a0, int mt0_32, long wtiles) -> int {
-    // half tiles (wino4_f32<1>: 16 wtiles x 64 columns, one per block), bit-identical: `wtiles` wtiles from m tile mt0_32 on
-    Args b = a0;
-    b.persist = 0;
-    b.mt0 = 2 * mt0_32;
-    b.mtiles = (int)((wtiles + 15) / 16);
-    b.xcd_remap = (b.ncombo > 1 && b.mtiles >= 64) ? 1 : 0;
-    const long idh = b.xcd_remap ? (long)8 * b.ncombo * ceil_div(b.mtiles, 8) : (long)b.mtiles * b.ncombo;
-    static PerDeviceOnce attr_h;
-    const int dev_h = current_device();
-    if (!attr_h.is_set(dev_h)) {
-      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_f32<1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      attr_h.set(dev_h);
-    }
-    hipLaunchKernelGGL(wino4_f32<1>, dim3((unsigned)idh), dim3(512), (size_t)(VBUF + UBUF) * sizeof(float4), s, b);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-    return 0;
-  };
-  // launches that fill at most half the CUs with 32 x 64 tiles run the 16 x 16 form (measured: at one round and beyond
-  // the big tiles win - the small form fetches the filters four times as often; ee158f6:tools/r3_sessions/session27.sh)
-  if ((long)a.mtiles * a.ncombo * 2 <= n_cu) return launch_small(a, 0, a.T);
-  int rest = 0;  // m tiles left to a second launch
-  bool rest_half = false;  // ... in half tiles (else the 16 x 16 form)
-  if ((long)a.mtiles * a.ncombo > n_cu && n_cu % (8 * a.ncombo) == 0) {
-    // Persistent blocks: block (column tile / group c, q) takes the m tiles q, q + Pc, ...  When the tiles do not come out
-    // as whole rounds and what is left over is at most a quarter of a round, the whole rounds run here and the rest as a
-    // second launch in the 16 x 16 form: 2 rounds + a short launch instead of 3 (conv4_3_CPM, the stage-1 convs: 0.60 ->
-    // 0.53 ms, 0.17 -> 0.155), 1 + a short one instead of 2 (conv4_4_CPM: 0.21 -> 0.15).  Half a round left over is
-    // cheaper as a half-empty round of big tiles (conv4_1 / conv4_2: 0.51 -> 0.54 ms with the cut), and at 8.27 rounds
-    // (conv3_x) the cut changes nothing.  The forms are bit-identical, so the cut is invisible in the results.
-    const int Pc = n_cu / a.ncombo;
-    const int r = a.mtiles % Pc;
-    if (r && (long)r * a.ncombo * 4 <= n_cu) {  // at most a quarter of a round left over
-      rest = r;
-      a.mtiles -= r;
-    } else if (r && 2L * r * a.ncombo <= n_cu) {
-      // Round 4: up to half a round left over runs as ONE round of half tiles (16 wtiles x 64 columns: half the multiplies of a
-      // tile, the same transform work per wtile) instead of a round of big tiles that leaves 50..75 % of the CUs idle:
-      // conv3_x 8.27 rounds -> 8 + a half-tile round, conv4_1 / conv4_2 4.5 -> 4 + one.
-      rest = r;
-      rest_half = true;
-      a.mtiles -= r;
-    }
-    a.persist = 1;
-    ids = n_cu;
-  }
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_f32<2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(wino4_f32<2>, dim3((unsigned)ids), dim3(512), (size_t)(2 * VBUF + 2 * UBUF) * sizeof(float4), s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  if (rest && rest_half) return launch_half(a, a.mtiles, (long)a.T - (long)a.mtiles * NT);
-  if (rest) return launch_small(a, a.mtiles, (long)a.T - (long)a.mtiles * NT);
-  return 0;
+  if (!d0.prelu) return wino4_run<false>(a, ids, ngroups, d0.cout, s);
+  ArgsP ap;
+  static_cast<Args&>(ap) = a;
+  ap.prelu[0] = d[0].prelu;
+  ap.prelu[1] = ngroups > 1 ? d[1].prelu : d[0].prelu;
+  return wino4_run<true>(ap, ids, ngroups, d0.cout, s);
 }
 
 int pack_weights_wino4_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map,

@@ -15,6 +15,12 @@
 //    one grouped grid per layer.
 //  * MaxPool2d is fused into the epilogue of the conv in front of it when the
 //    map has even height and width.
+//
+// A second topology, OpenPose_Model (lib/network/openpose.py:114-177), shares the
+// executor (rtpose_openpose_create, build_plan_openpose): the same trunk with PReLU
+// epilogues on its last three convs, dense-block stages whose three convs write
+// slices of one 3 x inner buffer, and stage heads that write the next stage's
+// input buffer in place.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -94,6 +100,10 @@ struct ConvW {
   int form = 0;            // what THIS plan runs the conv in: 0 direct, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 = F(4,7), 6 = F(6,7)
   int H = 0, W = 0;        // map size the conv runs at in this plan
   size_t w_off = 0, b_off = 0;  // float offsets in the weight arena
+  // OpenPose_Model: nn.PReLU after the conv (slopes at pr_off, cout_pad floats; state_dict prefix prelu_name)
+  bool has_prelu = false;
+  size_t pr_off = 0;
+  std::string prelu_name;
 };
 
 enum OpKind { OP_INPUT, OP_CONV, OP_POOL, OP_COPY, OP_TAIL };
@@ -149,6 +159,14 @@ struct rtpose_net {
   int keep = 0;
   int save_buf[6] = {-1, -1, -1, -1, -1, -1};
   int cat_buf[2] = {-1, -1};
+  // topology: 0 = rtpose_vgg, 1 = OpenPose_Model (rtpose_openpose_create).  OpenPose plans keep their stage outputs in
+  // cat_buf[0] = the stage input buffer [features 128 | PAF | pad to 16 | heat | pad to 16] (heat at op_heat_off) and
+  // copy each stage's output to op_save[stage] when keep_intermediates is set; the packed-input map of the l1 stages
+  // 1.. (cat([features, heat, paf]) order) is catmap_host, uploaded at bind.
+  int topo = 0;
+  int op_l2 = 0, op_l1 = 0, op_paf = 0, op_heat = 0, op_heat_off = 0;
+  std::vector<int> op_save;
+  std::vector<int32_t> catmap_host;
   int x0_buf = -1;
   // hipGraph replay of the launch list (ops after the input conversion have fixed arguments):
   // captured once per keep_intermediates setting on a private non-blocking stream that is
@@ -210,12 +228,13 @@ int add_buf(rtpose_net* n, int C, int P, int H, int W, bool f32 = false) {
   return (int)n->bufs.size() - 1;
 }
 
-int add_conv_w(rtpose_net* n, const std::string& name, int cout, int cin, int k, bool cat_perm, int H = 0, int W = 0) {
+int add_conv_w(rtpose_net* n, const std::string& name, int cout, int cin, int k, bool cat_perm, int H = 0, int W = 0,
+               int cin_packed = 0) {
   ConvW c;
   c.name = name;
   c.cout = cout;
   c.cin_src = cin;
-  c.cin_packed = cat_perm ? kCatC : (n->bf16 ? ceil_div(cin, 16) * 16 : ceil_div(cin, 8) * 8);
+  c.cin_packed = cin_packed > 0 ? cin_packed : cat_perm ? kCatC : (n->bf16 ? ceil_div(cin, 16) * 16 : ceil_div(cin, 8) * 8);
   c.k = k;
   c.cat_perm = cat_perm;
   c.H = H;
@@ -389,7 +408,8 @@ void plan_vgg_conv(rtpose_net* n, int conv, int H, int W, int in_buf, int out_bu
                    int out_buf_pooled) {
   const int zero = 0;
   if (out_buf_pooled < 0) {
-    add_conv_op(n, H, W, 1, &conv, &in_buf, &zero, &out_buf_same, &zero, 1, 0);
+    // (OpenPose_Model: conv4_2 and conv4_3_CPM end in a PReLU instead of the ReLU; never in front of a pool)
+    add_conv_op(n, H, W, 1, &conv, &in_buf, &zero, &out_buf_same, &zero, n->convs[conv].has_prelu ? 0 : 1, 0);
   } else if (!((H | W) & 1)) {
     add_conv_op(n, H, W, 1, &conv, &in_buf, &zero, &out_buf_pooled, &zero, 1, 1);
   } else {
@@ -596,6 +616,153 @@ void build_plan(rtpose_net* n) {
   }
 }
 
+// the nn.PReLU that follows conv `conv`: slopes in the arena, padded like the bias
+void add_prelu(rtpose_net* n, int conv, const std::string& name) {
+  ConvW& c = n->convs[conv];
+  c.has_prelu = true;
+  c.prelu_name = name;
+  c.pr_off = n->wt_floats;
+  n->wt_floats += round_up(rtpose_packed_bias_floats(c.cout), 64);
+}
+
+// OpenPose_Model (openpose.py:114-177).  Stage input buffer IN = [features 0..127 | PAF 128.. | pad | heat R.. | pad], R =
+// the PAF end rounded up to 16, S = the heat end rounded up to 16.  The l2 stages 1.. and the l1 stage 0 read IN[0:R]
+// (cat([features, paf]) is its natural order, the pad gets zero taps), the l1 stages 1.. read IN[0:S] through a channel map
+// (cat([features, heat, paf]), openpose.py:174).  Nothing a stage reads is left over from an earlier forward: the PAF and
+// heat slices are written before they are read in every forward and the pads are never written.  Every 3x3 stage conv is
+// a dense-block conv: Mconv{b}_0 reads the whole 3 x inner buffer of block b - 1 (or IN) and writes slice 0 of block b's,
+// Mconv{b}_1 / _2 read slice 0 / 1 and write slice 1 / 2 (the torch.cat of openpose.py:86-105 never runs); two buffers
+// per inner width ping-pong between blocks.  The head (Mconv6 1x1 + PReLU into HEAD, Mconv7 1x1 linear) writes the stage's
+// output into its IN slice, from where the next stage reads it.
+void build_plan_openpose(rtpose_net* n) {
+  const int H0 = n->H, W0 = n->W;
+  const int H1 = H0 / 2, W1 = W0 / 2, H2 = H1 / 2, W2 = W1 / 2, H3 = H2 / 2, W3 = W2 / 2;
+  n->H3 = H3;
+  n->W3 = W3;
+  const int P = n->op_paf, Hc = n->op_heat;
+  const int R = (128 + P + 15) / 16 * 16;
+  const int S = (R + Hc + 15) / 16 * 16;
+  n->op_heat_off = R;
+
+  // ---- weights, in the reference's state_dict order ----
+  const int vgg_idx[12] = {0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25};
+  const int vgg_cin[12] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 256};
+  const int vgg_cout[12] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 256, 128};
+  int cw0[12];
+  for (int i = 0; i < 12; ++i) {
+    cw0[i] = add_conv_w(n, "feature_extractor." + std::to_string(vgg_idx[i]), vgg_cout[i], vgg_cin[i], 3, false);
+    if (i >= 9) add_prelu(n, cw0[i], "feature_extractor." + std::to_string(vgg_idx[i] + 1));  // openpose.py:40-44
+  }
+  struct StageW {
+    int br, inner, cw[5][3], m6, m7;
+  };
+  std::vector<StageW> st;
+  for (int br = 0; br < 2; ++br)
+    for (int s = 0; s < (br == 0 ? n->op_l2 : n->op_l1); ++s) {
+      StageW w;
+      w.br = br;
+      w.inner = s == 0 ? 96 : 128;
+      const int n1 = s == 0 ? 256 : 512, cout = br == 0 ? P : Hc;
+      const int cin0 = br == 0 ? (s == 0 ? 128 : 128 + P) : (s == 0 ? 128 + P : 128 + P + Hc);
+      const int cinp0 = br == 0 ? (s == 0 ? 128 : R) : (s == 0 ? R : S);
+      const std::string pre = (br == 0 ? "l2_stages." : "l1_stages.") + std::to_string(s) + ".";
+      for (int b = 0; b < 5; ++b)
+        for (int j = 0; j < 3; ++j) {
+          const std::string blk = pre + "Mconv" + std::to_string(b + 1) + "_" + std::to_string(j);
+          const bool in0 = b == 0 && j == 0;
+          const int cin = j ? w.inner : (b ? 3 * w.inner : cin0);
+          w.cw[b][j] = add_conv_w(n, blk + ".Mconv", w.inner, cin, 3, in0 && br == 1 && s > 0, H3, W3, in0 ? cinp0 : 0);
+          add_prelu(n, w.cw[b][j], blk + ".MPrelu");
+        }
+      w.m6 = add_conv_w(n, pre + "Mconv6.Mconv", n1, 3 * w.inner, 1, false, H3, W3);
+      add_prelu(n, w.m6, pre + "Mconv6.MPrelu");
+      w.m7 = add_conv_w(n, pre + "Mconv7", cout, n1, 1, false, H3, W3);
+      st.push_back(w);
+    }
+  n->catmap_off = n->wt_floats;
+  n->wt_floats += 256;  // int32[S <= 256]
+  n->catmap_host.assign(S, -1);
+  for (int c = 0; c < S; ++c) {
+    if (c < 128) n->catmap_host[c] = c;
+    else if (c < 128 + P) n->catmap_host[c] = 128 + Hc + (c - 128);
+    else if (c >= R && c < R + Hc) n->catmap_host[c] = 128 + (c - R);
+  }
+
+  // ---- activation buffers: the trunk's as in build_plan, then IN, the dense-block pairs, HEAD and the stage records ----
+  const int X0 = add_buf(n, 8, 1, H0, W0);
+  n->x0_buf = X0;
+  const int A1 = add_buf(n, 64, 1, H0, W0);
+  const bool even0 = !((H0 | W0) & 1), even1 = !((H1 | W1) & 1), even2 = !((H2 | W2) & 1);
+  const int A2 = even0 ? -1 : add_buf(n, 64, 0, H0, W0);
+  const int B0 = add_buf(n, 64, 1, H1, W1);
+  const int B1 = add_buf(n, 128, 1, H1, W1);
+  const int B2 = even1 ? -1 : add_buf(n, 128, 0, H1, W1);
+  const int C0 = add_buf(n, 128, 1, H2, W2);
+  const int C1 = add_buf(n, 256, 1, H2, W2);
+  const int C2 = add_buf(n, 256, 1, H2, W2);
+  const int C3 = add_buf(n, 256, 1, H2, W2);
+  const int C4 = even2 ? -1 : add_buf(n, 256, 0, H2, W2);
+  const int D0 = add_buf(n, 256, 1, H3, W3);
+  const int D1 = add_buf(n, 512, 1, H3, W3);
+  const int D2 = add_buf(n, 512, 1, H3, W3);
+  const int D3 = add_buf(n, 256, 1, H3, W3);
+  const int IN = add_buf(n, S, 1, H3, W3);
+  n->cat_buf[0] = IN;
+  const int DB96[2] = {add_buf(n, 288, 1, H3, W3), add_buf(n, 288, 1, H3, W3)};
+  const int DB128[2] = {add_buf(n, 384, 1, H3, W3), add_buf(n, 384, 1, H3, W3)};
+  const int HEAD = add_buf(n, 512, 0, H3, W3);
+  for (const StageW& w : st) n->op_save.push_back(add_buf(n, w.br == 0 ? P : Hc, 0, H3, W3));
+
+  // ---- launches ----
+  add_simple_op(n, OP_INPUT, "nchw_to_nhwc8", H0, W0, -1, 0, X0, 0, 3);
+  plan_vgg_conv(n, cw0[0], H0, W0, X0, A1, -1);
+  plan_vgg_conv(n, cw0[1], H0, W0, A1, A2, B0);
+  plan_vgg_conv(n, cw0[2], H1, W1, B0, B1, -1);
+  plan_vgg_conv(n, cw0[3], H1, W1, B1, B2, C0);
+  plan_vgg_conv(n, cw0[4], H2, W2, C0, C1, -1);
+  plan_vgg_conv(n, cw0[5], H2, W2, C1, C2, -1);
+  plan_vgg_conv(n, cw0[6], H2, W2, C2, C3, -1);
+  plan_vgg_conv(n, cw0[7], H2, W2, C3, C4, D0);
+  plan_vgg_conv(n, cw0[8], H3, W3, D0, D1, -1);
+  plan_vgg_conv(n, cw0[9], H3, W3, D1, D2, -1);
+  plan_vgg_conv(n, cw0[10], H3, W3, D2, D3, -1);
+  const int zero = 0;
+  add_conv_op(n, H3, W3, 1, &cw0[11], &D3, &zero, &IN, &zero, 0, 0);  // conv4_4_CPM + PReLU -> features
+  for (size_t si = 0; si < st.size(); ++si) {
+    const StageW& w = st[si];
+    const int* db = w.inner == 96 ? DB96 : DB128;
+    for (int b = 0; b < 5; ++b) {
+      const int dst = db[b & 1];
+      const int src0 = b ? db[(b + 1) & 1] : IN;
+      const int off1 = w.inner, off2 = 2 * w.inner;
+      add_conv_op(n, H3, W3, 1, &w.cw[b][0], &src0, &zero, &dst, &zero, 0, 0);
+      add_conv_op(n, H3, W3, 1, &w.cw[b][1], &dst, &zero, &dst, &off1, 0, 0);
+      add_conv_op(n, H3, W3, 1, &w.cw[b][2], &dst, &off1, &dst, &off2, 0, 0);
+    }
+    const int last = db[0];  // block 5 (b = 4) wrote db[0]
+    const int out_off = w.br == 0 ? 128 : R;
+    add_conv_op(n, H3, W3, 1, &w.m6, &last, &zero, &HEAD, &zero, 0, 0);
+    add_conv_op(n, H3, W3, 1, &w.m7, &HEAD, &zero, &IN, &out_off, 0, 0);
+    add_simple_op(n, OP_COPY, "save" + std::to_string(si), H3, W3, IN, out_off, n->op_save[si], 0,
+                  w.br == 0 ? P : Hc);
+  }
+}
+
+// RTPOSE_WINOGRAD in the environment of the process: 1 (unset) = both kernel sizes in Winograd form, 0 = none,
+// 3 / 7 = only that kernel size
+int winograd_env() {
+  const char* e = getenv("RTPOSE_WINOGRAD");
+  return !e ? 1 : e[0] == '0' ? 0 : e[0] == '3' ? 3 : e[0] == '7' ? 7 : 1;
+}
+
+// the default form of the fp32 3x3 convs (RTPOSE_WINO_DEFAULT): AUTO, unless the environment says otherwise
+// (RTPOSE_WINOGRAD=0|7: direct; RTPOSE_WINOGRAD3_M=2: F(2x2,3x3), =4: F(4x4,3x3) forced)
+int default_winograd3() {
+  const int env = winograd_env();
+  const char* e3 = getenv("RTPOSE_WINOGRAD3_M");
+  return (env == 1 || env == 3) ? ((e3 && e3[0] == '2') ? 1 : (e3 && e3[0] == '4') ? 4 : RTPOSE_WINO3_AUTO) : 0;
+}
+
 rtpose_layout slice(const Buf& b, int choff) {
   rtpose_layout l = b.lay;
   l.choff = choff;
@@ -633,20 +800,13 @@ int rtpose_net_create_opts(int N, int H, int W, const rtpose_net_options* opt, r
   {
     // defaults of the two fields: on, unless the environment of the process says otherwise (RTPOSE_WINOGRAD =
     // 0: direct kernels everywhere, 3 / 7: only that kernel size in Winograd form; RTPOSE_WINOGRAD7_M=4: F(4,7))
-    const char* e = getenv("RTPOSE_WINOGRAD");
-    const int env = !e ? 1 : e[0] == '0' ? 0 : e[0] == '3' ? 3 : e[0] == '7' ? 7 : 1;
-    // (RTPOSE_WINOGRAD3_M=2: F(2x2,3x3) instead of F(4x4,3x3))
-    const char* e3 = getenv("RTPOSE_WINOGRAD3_M");
+    const int env = winograd_env();
     // Round 4: the default is the GUARDED choice - per layer, the fastest form whose amplification estimate for the
     // filters actually loaded stays under amp_limit (256): nobody here has seen pose_model.pth (README.md:19), and a
     // forced F(6,7) / F(4x4,3x3) would run whatever it holds.  He-init / N(0, 0.01) filters estimate 115-120 and
     // 42-43, so the bench plan keeps its forms bit for bit; RTPOSE_WINOGRAD3_M / RTPOSE_WINOGRAD7_M force a form.
     const char* e7 = getenv("RTPOSE_WINOGRAD7_M");
-    n->w3 = opt->winograd3 != RTPOSE_WINO_DEFAULT ? opt->winograd3
-            : (env == 1 || env == 3)              ? ((e3 && e3[0] == '2')   ? 1
-                                                     : (e3 && e3[0] == '4') ? 4
-                                                                            : RTPOSE_WINO3_AUTO)
-                                                  : 0;
+    n->w3 = opt->winograd3 != RTPOSE_WINO_DEFAULT ? opt->winograd3 : default_winograd3();
     n->w7 = opt->winograd7 != RTPOSE_WINO_DEFAULT ? opt->winograd7
             : (env == 1 || env == 7)              ? ((e7 && (e7[0] == '4' || e7[0] == '6')) ? wino7_default_fm()
                                                                                            : RTPOSE_WINO7_AUTO)
@@ -659,6 +819,43 @@ int rtpose_net_create_opts(int N, int H, int W, const rtpose_net_options* opt, r
   }
   build_plan(n);
   if (!forms_need_amps(n)) {  // AUTO waits for the filters (rtpose_net_finalize_weights)
+    pick_forms(n);
+    mark_plane_bufs(n);
+    n->forms_final = true;
+  }
+  *out = n;
+  return 0;
+}
+
+int rtpose_openpose_create(int N, int H, int W, const rtpose_openpose_options* opt, rtpose_net** out) {
+  if (!out) return fail(RTPOSE_E_INVAL, "openpose_create: out is NULL");
+  if (!opt || opt->struct_bytes < sizeof(rtpose_openpose_options))
+    return fail(RTPOSE_E_INVAL, "openpose_create: options missing or struct_bytes smaller than this library's "
+                                "rtpose_openpose_options");
+  if (N <= 0 || H < 8 || W < 8) return fail(RTPOSE_E_INVAL, "openpose_create: need N>=1 and H,W>=8");
+  if (opt->l2_stages < 2 || opt->l1_stages < 2 || opt->l2_stages > 64 || opt->l1_stages > 64)
+    return fail(RTPOSE_E_INVAL, "openpose_create: l2_stages and l1_stages must be 2..64 (the forward returns the last two "
+                                "stages of each, openpose.py:177)");
+  if (opt->paf_channels < 1 || opt->paf_channels > 64 || opt->heat_channels < 1 || opt->heat_channels > 64)
+    return fail(RTPOSE_E_INVAL, "openpose_create: paf_channels and heat_channels must be 1..64");
+  if (opt->winograd3 != RTPOSE_WINO_DEFAULT && opt->winograd3 != 0 && opt->winograd3 != 1 && opt->winograd3 != 4 &&
+      opt->winograd3 != RTPOSE_WINO3_AUTO)
+    return fail(RTPOSE_E_INVAL, "openpose_create: winograd3 must be RTPOSE_WINO_DEFAULT, 0, 1, 4 or RTPOSE_WINO3_AUTO");
+  rtpose_net* n = new rtpose_net();
+  n->N = N;
+  n->H = H;
+  n->W = W;
+  n->topo = 1;
+  n->op_l2 = opt->l2_stages;
+  n->op_l1 = opt->l1_stages;
+  n->op_paf = opt->paf_channels;
+  n->op_heat = opt->heat_channels;
+  n->n_cu = device_cu_count();
+  n->w3 = opt->winograd3 != RTPOSE_WINO_DEFAULT ? opt->winograd3 : default_winograd3();
+  n->w7 = 0;  // no 7x7 convs
+  n->amp_limit = opt->amp_limit > 0.f ? opt->amp_limit : 256.f;
+  build_plan_openpose(n);
+  if (!forms_need_amps(n)) {
     pick_forms(n);
     mark_plane_bufs(n);
     n->forms_final = true;
@@ -736,6 +933,13 @@ int rtpose_net_bind(rtpose_net* net, void* workspace, size_t workspace_bytes, vo
     RTPOSE_HIP_CHECK(hipMemsetAsync(net->ws + net->scratch_off, 0,
                                     (size_t)((char*)(conv2d_wino7_scratch_err(net->ws + net->scratch_off, net->n_cu) + 1) -
                                              (char*)(net->ws + net->scratch_off)), s));
+  if (net->topo == 1) {  // OpenPose_Model: packed c -> source channel of cat([features, heat, paf])
+    RTPOSE_HIP_CHECK(hipMemcpyAsync(net->wt + net->catmap_off, net->catmap_host.data(),
+                                    net->catmap_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    RTPOSE_HIP_CHECK(hipStreamSynchronize(s));
+    net->bound = true;
+    return 0;
+  }
   // channel map of the concat input: packed c -> source channel of cat([L1,L2,out1])
   int32_t map[kCatC];
   for (int c = 0; c < kCatC; ++c) {
@@ -764,6 +968,26 @@ int rtpose_net_conv_info(const rtpose_net* net, int idx, char* name, int name_ca
 }
 
 static int net_on_its_device(const rtpose_net* net, const char* who);
+
+int rtpose_net_prelu_info(const rtpose_net* net, int idx, char* name, int name_cap) {
+  if (!net || idx < 0 || idx >= (int)net->convs.size()) return fail(RTPOSE_E_INVAL, "prelu_info: bad index");
+  const ConvW& c = net->convs[idx];
+  if (name && name_cap > 0) snprintf(name, name_cap, "%s", c.prelu_name.c_str());
+  return c.has_prelu ? 1 : 0;
+}
+
+int rtpose_net_load_prelu(rtpose_net* net, int idx, const float* slope, void* stream) {
+  if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_load_prelu: net not bound");
+  if (idx < 0 || idx >= (int)net->convs.size()) return fail(RTPOSE_E_INVAL, "net_load_prelu: bad index");
+  const ConvW& c = net->convs[idx];
+  if (!c.has_prelu) return fail(RTPOSE_E_INVAL, "net_load_prelu: conv %d (%s) has no PReLU", idx, c.name.c_str());
+  int rc = net_on_its_device(net, "net_load_prelu");
+  if (!rc) rc = check_device_ptr(slope, net->device, "net_load_prelu", "the slope tensor");
+  if (rc) return rc;
+  RTPOSE_HIP_CHECK(hipMemcpyAsync(net->wt + c.pr_off, slope, (size_t)c.cout * sizeof(float), hipMemcpyDeviceToDevice,
+                                  as_stream(stream)));
+  return 0;
+}
 
 int rtpose_net_load_conv(rtpose_net* net, int idx, const float* w_oihw, const float* bias, void* stream) {
   if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_load_conv: net not bound");
@@ -1231,6 +1455,7 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
           d[g].relu = o.relu;
           d[g].pool = o.pool;
           d[g].out_cmap = nullptr;
+          d[g].prelu = c.has_prelu ? net->wt + c.pr_off : nullptr;
         }
         if (net->convs[o.conv_idx[0]].first) {
           const ConvW& c = net->convs[o.conv_idx[0]];
@@ -1326,10 +1551,25 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
 
 int rtpose_net_read_output(rtpose_net* net, int which, float* dst_nchw, void* stream) {
   if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_read_output: net not bound");
-  if (which < 0 || which > 11 || !dst_nchw) return fail(RTPOSE_E_INVAL, "net_read_output: bad argument");
+  if (which < 0 || which >= (net->topo == 1 ? net->op_l2 + net->op_l1 : 12) || !dst_nchw)
+    return fail(RTPOSE_E_INVAL, "net_read_output: bad argument");
   int rcd = net_on_its_device(net, "net_read_output");
   if (!rcd) rcd = check_device_ptr(dst_nchw, net->device, "net_read_output", "the destination tensor");
   if (rcd) return rcd;
+  if (net->topo == 1) {  // saved_for_loss flattened: the PAF stages, then the heat-map stages
+    const bool paf = which < net->op_l2;
+    const int C = paf ? net->op_paf : net->op_heat;
+    int buf = net->op_save[which], choff = 0;
+    if (!net->keep) {
+      if (which != net->op_l2 - 1 && which != net->op_l2 + net->op_l1 - 1)
+        return fail(RTPOSE_E_STATE, "net_read_output: stage output %d not kept (set keep_intermediates)", which);
+      buf = net->cat_buf[0];
+      choff = paf ? 128 : net->op_heat_off;
+    }
+    const Buf& b = net->bufs[buf];
+    const rtpose_layout l = slice(b, choff);
+    return rtpose_layout_to_nchw(net->ws + b.off_floats, &l, dst_nchw, C, net->N, net->H3, net->W3, stream);
+  }
   const int stage = which / 2 + 1, br = which % 2;
   const int C = br == 0 ? 38 : 19;
   int buf, choff;
@@ -1354,6 +1594,15 @@ int rtpose_net_read_output(rtpose_net* net, int which, float* dst_nchw, void* st
 int rtpose_net_output_view(const rtpose_net* net, int which, const float** base, rtpose_layout* layout,
                            int* C, int* H, int* W) {
   if (!net || !net->bound || which < 0 || which > 1) return fail(RTPOSE_E_INVAL, "output_view: bad argument");
+  if (net->topo == 1) {  // the last PAF / heat maps, in the stage input buffer
+    const Buf& b = net->bufs[net->cat_buf[0]];
+    if (base) *base = net->ws + b.off_floats;
+    if (layout) *layout = slice(b, which == 0 ? 128 : net->op_heat_off);
+    if (C) *C = which == 0 ? net->op_paf : net->op_heat;
+    if (H) *H = net->H3;
+    if (W) *W = net->W3;
+    return 0;
+  }
   // stage 6 writes CATa (fp32 plans) / the fp32 stage-6 record (bf16 plans)
   const Buf& b = net->bufs[net->bf16 ? net->save_buf[5] : net->cat_buf[0]];
   if (base) *base = net->ws + b.off_floats;

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import _capi
 from ._capi import lib, check, ptr, current_stream
-from ._native_state import NativeStateMixin
+from ._native_state import NativeStateMixin, NetPlanMixin
 
 # (cin, cout, k) tables; 'P' = MaxPool2d(2, 2, 0).  reference :69-83, :95-127
 _VGG = [(3, 64, 3), (64, 64, 3), 'P', (64, 128, 3), (128, 128, 3), 'P', (128, 256, 3),
@@ -86,7 +86,7 @@ class _ShapeOnly(object):
             self.device = torch.device('cuda', torch.cuda.current_device())
 
 
-class RtposeVGG(NativeStateMixin, nn.Module):
+class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
     """Drop-in for the module built by reference ``get_model('vgg19')``."""
 
     def __init__(self):
@@ -131,29 +131,6 @@ class RtposeVGG(NativeStateMixin, nn.Module):
             raise ValueError("winograd7 must be None, 0, 4, 6 or 'auto'")
         self._wino = (w3, w7, float(amp_limit or 0.0))
         return self
-
-    def conv_numerics(self, plan):
-        """[(state_dict prefix, form, (amp F(2x2,3x3), amp F(4,7), amp F(6,7), amp F(4x4,3x3)))] of a plan: form 0 =
-        direct kernel, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 / 6 = F(m,7); amp = rtpose_winograd_amplification of the
-        loaded filters (0 = n/a)."""
-        out = []
-        form = C.c_int()
-        amp = (C.c_float * 4)()
-        for i, (nm, _) in enumerate(self._convs()):
-            check(lib.rtpose_net_conv_numerics(plan.handle, i, C.byref(form), amp, current_stream()))
-            out.append((nm, form.value, tuple(amp)))
-        return out
-
-    def device_status(self, plan):
-        """Device-side error word of a plan (0 = fine; synchronises the stream)."""
-        word = C.c_int()
-        check(lib.rtpose_net_device_status(plan.handle, C.byref(word), current_stream()))
-        return word.value
-
-    def device_status_async(self, plan, pinned_word):
-        """Queue the copy of the plan's device error word into `pinned_word` (a pinned int32 tensor of one element)
-        on the current stream, without waiting; read it after an event recorded later on that stream."""
-        check(lib.rtpose_net_device_status_async(plan.handle, pinned_word.data_ptr(), current_stream()))
 
     def set_compute_dtype(self, dtype):
         """'fp32' (reference arithmetic, v_mfma_f32_32x32x2_f32), 'bf16' (BASELINE config 3:
@@ -249,35 +226,12 @@ class RtposeVGG(NativeStateMixin, nn.Module):
             self._finalize(plan)
         return plan
 
-    def forward_native(self, x, keep_intermediates=False):
-        """Enqueue the forward; returns the plan (outputs stay in its workspace)."""
-        if not x.is_cuda:
-            self.plan_for(x)  # raises: no CPU fallback
-        with torch.cuda.device(x.device):
-            plan = self.plan_for(x)
-            xin = x.detach()
-            if xin.dtype != torch.float32 or not xin.is_contiguous():
-                xin = xin.float().contiguous()
-            check(lib.rtpose_net_set_keep_intermediates(plan.handle, 1 if keep_intermediates else 0))
-            check(lib.rtpose_net_forward(plan.handle, ptr(xin), current_stream()), "rtpose_net_forward")
-            self._last_input = xin  # keep alive until the stream has consumed it
-        return plan
-
     def read_output(self, plan, which):
         n = plan.shape[0]
         c = 38 if which % 2 == 0 else 19
         out = torch.empty((n, c, plan.h3, plan.w3), dtype=torch.float32, device=plan.workspace.device)
         check(lib.rtpose_net_read_output(plan.handle, which, ptr(out), current_stream()), "rtpose_net_read_output")
         return out
-
-    def output_view(self, plan, which):
-        """(base pointer, Layout, C, H, W) of the final PAF (0) / heat-map (1), in place."""
-        base = C.c_void_p()
-        lay = _capi.Layout()
-        c, h, w = C.c_int(), C.c_int(), C.c_int()
-        check(lib.rtpose_net_output_view(plan.handle, which, C.byref(base), C.byref(lay), C.byref(c),
-                                         C.byref(h), C.byref(w)))
-        return base, lay, c.value, h.value, w.value
 
     def forward(self, x):
         """reference :158-198 — returns ((out6_1, out6_2), saved_for_loss[12]), NCHW fp32."""

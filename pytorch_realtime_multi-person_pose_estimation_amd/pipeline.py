@@ -134,6 +134,12 @@ class SideDecoder(object):
 
 class PoseEstimator(object):
     def __init__(self, model, config=None, max_peaks_per_part=32, max_humans=64):
+        # the decoder is COCO-18: 38 PAF and 19 heat-map channels (a model with other counts, e.g. OpenPose_Model's
+        # defaults of 14 / 9, is refused here rather than decoded wrongly)
+        chans = (getattr(model, 'paf_out_channels', 38), getattr(model, 'heat_out_channels', 19))
+        if chans != (38, 19):
+            raise ValueError("PoseEstimator decodes COCO-18 maps (38 PAF, 19 heat-map channels); the model has %d / %d"
+                             % chans)
         self.model = model
         self.config = config or dec.default_config()
         self.max_peaks_per_part = max_peaks_per_part
