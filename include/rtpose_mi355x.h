@@ -100,7 +100,10 @@ typedef struct rtpose_conv_desc {
   const float* bias_packed;
   float* out;            /* activation buffer base (layout `lout`)          */
   rtpose_layout lin;
-  rtpose_layout lout;
+  rtpose_layout lout; /* the output slice: lout.choff + cout <= lout.cstride, or the launch is refused
+                   (RTPOSE_E_INVAL) - rtpose_conv2d, rtpose_conv2d_bf16, rtpose_conv2d_bf16x3 with out_f32 and
+                   the Winograd launches with pixel-major outputs.  Not checked where out_cmap places the
+                   channels (absolute) or for the split hi / lo pieces of bf16x3 bf16 outputs.          */
   int32_t cin;  /* packed input channels (multiple of 8)                    */
   int32_t cout; /* real output channels                                     */
   int32_t k;    /* 1, 3 or 7                                                */
@@ -174,7 +177,8 @@ int rtpose_conv_first_bf16(const float* x_nchw, const float* x_layout, const rtp
  * (csrc/conv_tail.hip; `ngroups` <= 2 branches per grid).  d1[g] / d2[g] are rtpose_conv_desc of the two convs
  * with the plain k = 1 packing (rtpose_pack_conv_weights); d1[g].out / lout are ignored - the 128-channel
  * intermediate never leaves the CU - and d2[g] reads it.  Same sums, in the same order, as two rtpose_conv2d
- * launches.  rtpose_conv1x1_pair_fits: 1 if the pair has this shape. */
+ * launches.  rtpose_conv1x1_pair_fits: 1 if the pair has this shape, its input slice (128 channels of d1[g].lin) and
+ * output slice (d2[g].cout channels of d2[g].lout) lie inside their cstride and neither conv has an out_cmap. */
 int rtpose_conv1x1_pair_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups);
 int rtpose_conv1x1_pair(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N,
                         int H, int W, void* stream);
@@ -373,7 +377,8 @@ int rtpose_conv2d_bf16(const rtpose_conv_desc* d, int ngroups, int N, int H, int
  * intermediate is rounded to bf16 where the two-launch form rounded it and never leaves the CU.  d1[g] / d2[g] are the
  * descs of the two convs with the k = 1 packing of rtpose_pack_conv_weights_bf16; d1[g].in / lin: 16-byte aligned bf16
  * slice; d1[g].out is ignored; d2[g].out / lout: bf16 elements, or fp32 when out_f32 (any channel offset).  Same contract
- * as two rtpose_conv2d_bf16 launches; the fp32 sums run in another order, so not bit for bit the same. */
+ * as two rtpose_conv2d_bf16 launches; the fp32 sums run in another order, so not bit for bit the same.  `_fits` says 1
+ * only when, as for rtpose_conv1x1_pair_fits, both slices lie inside their cstride and neither conv has an out_cmap. */
 int rtpose_conv1x1_pair_bf16_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups);
 int rtpose_conv1x1_pair_bf16(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N,
                              int H, int W, int out_f32, void* stream);

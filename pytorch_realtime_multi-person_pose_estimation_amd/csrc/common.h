@@ -126,34 +126,6 @@ __device__ __forceinline__ int fast_div(int m, const FastDiv f) {
 }
 #endif
 
-// channel-plane slices (rtpose_conv_desc.in_plane_pixels / out_plane_pixels) exist for the F(4x4,3x3) kernel only
-inline bool desc_has_planes(const rtpose_conv_desc* d, int ngroups) {
-  for (int g = 0; d && g < ngroups && g < 2; ++g)
-    if (d[g].in_plane_pixels || d[g].out_plane_pixels) return true;
-  return false;
-}
-#define RTPOSE_REFUSE_PLANES(d, ngroups, who)                                                                        \
-  if (::rtpose::desc_has_planes(d, ngroups))                                                                         \
-  return ::rtpose::fail(RTPOSE_E_INVAL, who ": channel-plane slices (in_plane_pixels / out_plane_pixels) are read and " \
-                                            "written by F(4x4,3x3) launches only (zero-initialise descriptors)")
-
-inline bool desc_has_prelu(const rtpose_conv_desc* d, int ngroups) {
-  for (int g = 0; d && g < ngroups && g < 2; ++g)
-    if (d[g].prelu) return true;
-  return false;
-}
-#define RTPOSE_REFUSE_PRELU(d, ngroups, who)                                                                         \
-  if (::rtpose::desc_has_prelu(d, ngroups))                                                                          \
-  return ::rtpose::fail(RTPOSE_E_INVAL, who ": no PReLU epilogue (rtpose_conv_desc.prelu is taken by the fp32 "         \
-                                            "rtpose_conv2d and the fp32 k = 3 Winograd forms only)")
-// a PReLU launch: `relu` and the fused pool are off, every branch of a grouped launch has slopes
-#define RTPOSE_CHECK_PRELU(d, ngroups, who)                                                                          \
-  if (::rtpose::desc_has_prelu(d, ngroups)) {                                                                        \
-    for (int g__ = 0; g__ < (ngroups); ++g__)                                                                        \
-      if (!(d)[g__].prelu || (d)[g__].relu || (d)[g__].pool)                                                         \
-        return ::rtpose::fail(RTPOSE_E_INVAL, who ": a PReLU launch has slopes in every group, relu = 0 and no "        \
-                                                  "fused pool");                                                     \
-  }
 #ifdef __HIPCC__
 __device__ __forceinline__ float prelu1(float v, float a) { return v >= 0.f ? v : a * v; }
 #endif

@@ -32,7 +32,7 @@
 
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -300,9 +300,7 @@ int conv_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   if (!d || ngroups != 1 || out_f32 || split || d[0].prelu) return 0;
   const rtpose_conv_desc& c = d[0];
   if (c.k != 3 || c.cin != 64 || c.cout < 64 || (c.cout % 64) || c.out_cmap || c.in_plane_pixels || c.out_plane_pixels) return 0;
-  if ((c.lin.cstride % 8) || (c.lin.choff % 8) || c.lin.choff + 64 > c.lin.cstride) return 0;
-  if ((c.lout.cstride % 8) || (c.lout.choff % 8) || c.lout.choff + c.cout > c.lout.cstride) return 0;
-  if (c.lin.ws < W + 1 || c.lin.hs < H + 1 || c.lin.lead < c.lin.ws + 1) return 0;
+  if (!slice_ok(c.lin, 64, 8) || !slice_ok(c.lout, c.cout, 8) || !gap_covers(c.lin, H, W, 1)) return 0;
   if (c.pool && ((H | W) & 1)) return 0;
   // unsigned 32-bit byte offsets inside the kernel (the 2 x 368 scale of the multi-scale flow at batch 32 is 2.2 GB)
   if (rtpose_layout_pixels(&c.lin, N, H, W) * (size_t)c.lin.cstride * 2 > 0xffffffffULL) return 0;
@@ -312,9 +310,10 @@ int conv_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int
 
 int conv_c64_bf16_launch(const rtpose_conv_desc* d, int N, int H, int W, hipStream_t s) {
   using namespace c64;
-  RTPOSE_REFUSE_PRELU(d, 1, "conv_c64_bf16");
+  if (desc_has_prelu(d, 1)) return fail(RTPOSE_E_INVAL, "conv_c64_bf16: no PReLU epilogue (rtpose_conv_desc.prelu)");
   if (!conv_c64_bf16_fits(d, 1, N, H, W, 0, 0) || N <= 0 || H <= 0 || W <= 0)
-    return fail(RTPOSE_E_INVAL, "conv_c64_bf16: needs a 3x3 conv of 64 bf16 input channels into 16-byte aligned slices");
+    return fail(RTPOSE_E_INVAL, "conv_c64_bf16: needs a 3x3 conv of 64 bf16 input channels into 16-byte aligned "
+                                "slices (no out_cmap; a slice that exceeds cstride is refused)");
   const rtpose_conv_desc& c = d[0];
   Args a;
   memset(&a, 0, sizeof(a));
@@ -345,23 +344,12 @@ int conv_c64_bf16_launch(const rtpose_conv_desc* d, int N, int H, int W, hipStre
   a.ntn = c.cout / 64;
   a.f_tpi = make_fastdiv(a.tiles_x * a.tiles_y);
   a.f_tx = make_fastdiv(a.tiles_x);
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_bf16<false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_bf16<true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    attr_set.set(dev);
-  }
   const long items = (long)a.tiles * a.ntn;
   long blocks = 2L * device_cu_count();
   if (blocks > items) blocks = items;
   blocks -= blocks % a.ntn;
-  if (c.pool) hipLaunchKernelGGL(conv3x3_c64_bf16<true>, dim3((unsigned)blocks), dim3(256), kLdsBytes, s, a);
-  else hipLaunchKernelGGL(conv3x3_c64_bf16<false>, dim3((unsigned)blocks), dim3(256), kLdsBytes, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  if (!c.pool) return launch_kernel<conv3x3_c64_bf16<false>>(dim3((unsigned)blocks), dim3(256), kLdsBytes, kLdsBytes, s, a);
+  return launch_kernel<conv3x3_c64_bf16<true>>(dim3((unsigned)blocks), dim3(256), kLdsBytes, kLdsBytes, s, a);
 }
 
 }  // namespace rtpose

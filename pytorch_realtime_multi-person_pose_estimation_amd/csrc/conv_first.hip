@@ -31,7 +31,7 @@
 // lane stores 8 consecutive channels of its pixel: one 16-byte store.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -336,14 +336,14 @@ int conv_first_launch(const float* x_nchw, const float* x_lay, const rtpose_layo
                       const rtpose_layout* lo, int out_plane_pixels, int relu, int N, int H, int W, hipStream_t s,
                       int out_bf16) {
   using namespace first;
-  if (out_bf16 && (out_plane_pixels || (lo && ((lo->cstride % 8) || (lo->choff % 8)))))
+  if (out_bf16 && (out_plane_pixels || (lo && !slice_aligned(*lo, 8))))
     return fail(RTPOSE_E_INVAL, "conv_first: bf16 output is pixel-major with 16-byte aligned slices");
   if ((!x_nchw && (!x_lay || !lx)) || !wp || !out || !lo || N <= 0 || H <= 0 || W <= 0 || out_plane_pixels < 0)
     return fail(RTPOSE_E_INVAL, "conv_first: bad arguments");
   if (out_plane_pixels) {
     if ((lo->choff % 8) || (size_t)out_plane_pixels < rtpose_layout_pixels(lo, N, H, W))
       return fail(RTPOSE_E_INVAL, "conv_first: channel planes start at a multiple of 8 channels and hold the layout's pixels");
-  } else if (lo->choff + 64 > lo->cstride) {
+  } else if (!slice_inside(*lo, 64)) {
     return fail(RTPOSE_E_INVAL, "conv_first: output slice exceeds cstride");
   }
   Args a;
@@ -409,7 +409,7 @@ int rtpose_pack_conv_first_bf16(const float* w_oihw, const float* bias, float* w
 
 int rtpose_conv_first_bf16(const float* x_nchw, const float* x_layout, const rtpose_layout* lx, const float* w_packed,
                            void* out_bf16, const rtpose_layout* lout, int relu, int N, int H, int W, void* stream) {
-  if (lout && lout->choff + 64 > lout->cstride) return rtpose::fail(RTPOSE_E_INVAL, "conv_first_bf16: output slice exceeds cstride");
+  if (lout && !rtpose::slice_inside(*lout, 64)) return rtpose::fail(RTPOSE_E_INVAL, "conv_first_bf16: output slice exceeds cstride");
   return rtpose::conv_first_launch(x_nchw, x_layout, lx, w_packed, static_cast<float*>(out_bf16), lout, 0, relu, N, H, W,
                                    rtpose::as_stream(stream), 1);
 }

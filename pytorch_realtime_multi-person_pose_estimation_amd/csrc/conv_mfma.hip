@@ -32,7 +32,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -632,20 +632,6 @@ struct ConvPlan {
   size_t lds_bytes;
 };
 
-// LDS plane size: pixel count rounded so that the 4 channel-group planes of one
-// pixel land in different 16-byte bank slots on the staging writes.
-static int round_qs(int npix) {
-  int qs = npix;
-  while ((qs & 3) != 2) ++qs;
-  return qs;
-}
-
-static int halo_row_lds(int tw, int p) {
-  int w = tw + 2 * p;
-  while ((w & 15) != 8) ++w;  // consecutive tile rows half a bank-row apart
-  return w;
-}
-
 static int plan_conv(const rtpose_conv_desc& d, int N, int H, int W, ConvPlan* pl) {
   const int P = d.k / 2;
   pl->ck = conv_ck(d.cin);
@@ -710,63 +696,21 @@ static int plan_conv(const rtpose_conv_desc& d, int N, int H, int W, ConvPlan* p
 
 template <int KS, int CK, int MODE, int NBUF, int NF, bool PR = false>
 static int launch_inst(const ConvArgsT<PR>& a, dim3 grid, size_t lds, hipStream_t s) {
-  static PerDeviceOnce attr_set;  // zero-initialised; the attribute is per device
-  const int dev = current_device();
-  auto kern = conv_mfma_f32<KS, CK, MODE, NBUF, NF, PR>;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<conv_mfma_f32<KS, CK, MODE, NBUF, NF, PR>>(grid, dim3(256), lds, 150 * 1024, s, a);
 }
 
 int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
-  if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d: ngroups must be 1 or 2");
-  RTPOSE_REFUSE_PLANES(d, ngroups, "conv2d");
-  RTPOSE_CHECK_PRELU(d, ngroups, "conv2d");
+  const ConvSpec spec = {"conv2d", 4, 1, true, false, true, true};
+  if (int rc = check_conv_features(d, ngroups, spec)) return rc;
   const rtpose_conv_desc& d0 = d[0];
   if (d0.k != 1 && d0.k != 3 && d0.k != 7) return fail(RTPOSE_E_INVAL, "conv2d: k must be 1, 3 or 7");
   if (d0.prelu && (d0.k == 7 || d[0].out_cmap || (ngroups > 1 && d[1].out_cmap)))
     return fail(RTPOSE_E_INVAL, "conv2d: the PReLU epilogue exists for k = 1 and 3 without out_cmap");
   if (d0.cin % 8 != 0 || d0.cin <= 0) return fail(RTPOSE_E_INVAL, "conv2d: cin must be a multiple of 8");
-  if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "conv2d: empty tensor");
-  const int P = d0.k / 2;
+  if (int rc = check_conv_layouts(d, ngroups, N, H, W, spec)) return rc;
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  for (int i = 0; i < ngroups; ++i) {
-    const rtpose_conv_desc& di = d[i];
-    if (di.k != d0.k || di.cin != d0.cin || di.relu != d0.relu || di.pool != d0.pool ||
-        cout_pad(di.cout) != cout_pad(d0.cout) || di.lin.ws != d0.lin.ws || di.lin.hs != d0.lin.hs)
-      return fail(RTPOSE_E_INVAL, "conv2d: grouped convs must share geometry");
-    if (di.lin.ws < W + P || di.lin.hs < H + P || di.lin.lead < P * di.lin.ws + P)
-      return fail(RTPOSE_E_INVAL, "conv2d: input layout gap smaller than the conv padding");
-    if ((di.lin.cstride % 4) || (di.lin.choff % 4))
-      return fail(RTPOSE_E_INVAL, "conv2d: input slice must be 16-byte aligned");
-    if (di.lin.choff + di.cin > di.lin.cstride)
-      return fail(RTPOSE_E_INVAL, "conv2d: input slice exceeds cstride");
-    ConvGroup& g = a.g[i];
-    g.in = di.in;
-    g.w = di.w_packed;
-    g.bias = di.bias_packed;
-    g.out = di.out;
-    g.in_cstride = di.lin.cstride;
-    g.in_choff = di.lin.choff;
-    g.in_ws = di.lin.ws;
-    g.in_hs = di.lin.hs;
-    g.in_lead = di.lin.lead;
-    g.out_cstride = di.lout.cstride;
-    g.out_choff = di.lout.choff;
-    g.out_ws = di.lout.ws;
-    g.out_hs = di.lout.hs;
-    g.out_lead = di.lout.lead;
-    g.cout = di.cout;
-    g.cout_pad = cout_pad(di.cout);
-    g.out_cmap = di.out_cmap;
-  }
-  if (d0.pool && ((H | W) & 1)) return fail(RTPOSE_E_INVAL, "conv2d: fused pool needs even H and W");
+  for (int i = 0; i < ngroups; ++i) fill_group(a.g[i], d[i]);
   ConvPlan pl;
   int rc = plan_conv(d0, N, H, W, &pl);
   if (rc) return rc;
@@ -790,9 +734,8 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
   // tail, and 32 MFMAs between filler slots) - 427 vs 464 img/s overall.
   a.ntiles = cout_pad(d0.cout) / kConvBN;
   a.ncombo = a.ntiles * ngroups;
-  a.xcd_remap = (a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
-  const long ids = a.xcd_remap ? (long)8 * a.ncombo * ceil_div(a.mtiles, 8) : (long)a.mtiles * a.ncombo;
-  if (ids > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d: grid too large");
+  long ids;
+  if (int rc = grid_ids(a.mtiles, a.ncombo, a.xcd_remap, ids, "conv2d")) return rc;
   a.nbig = (int)ids;
   if (pl.mode == 0) {
     // Tail quantisation: equal tiles on `slots` co-resident block slots run in lock-step
@@ -812,8 +755,7 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
   if (d0.prelu) {
     ConvArgsP ap;
     static_cast<ConvArgs&>(ap) = a;
-    ap.prelu[0] = d[0].prelu;
-    ap.prelu[1] = ngroups > 1 ? d[1].prelu : d[0].prelu;
+    set_prelu(ap, d, ngroups);
 #define RTPOSE_CONV_CASE_P(KS_, CK_, MODE_)            \
   if (d0.k == KS_ && pl.ck == CK_ && pl.mode == MODE_) \
     return launch_inst<KS_, CK_, MODE_, KS_ == 1 ? 1 : 2, 1, true>(ap, grid, pl.lds_bytes, s);

@@ -34,7 +34,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -919,17 +919,6 @@ struct ConvPlan {
   size_t lds_bytes;
 };
 
-static int round_qs(int npix) {
-  int qs = npix;
-  while ((qs & 3) != 2) ++qs;
-  return qs;
-}
-static int halo_row_lds(int tw, int p) {
-  int w = tw + 2 * p;
-  while ((w & 15) != 8) ++w;
-  return w;
-}
-
 static int plan_conv(const rtpose_conv_desc& d, int N, int H, int W, int sp, ConvPlan* pl) {
   const int P = d.k / 2;
   pl->ck = conv_ck(d.cin, d.k, sp);
@@ -995,17 +984,7 @@ static int plan_conv(const rtpose_conv_desc& d, int N, int H, int W, int sp, Con
 
 template <int KS, int CK, int MODE, int NBUF, int WM, int NF, int SP, bool TR>
 static int launch_tr(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  static PerDeviceOnce attr_set;  // zero-initialised; the attribute is per device
-  const int dev = current_device();
-  auto kern = conv_mfma_bf16<KS, CK, MODE, NBUF, WM, NF, SP, TR>;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<conv_mfma_bf16<KS, CK, MODE, NBUF, WM, NF, SP, TR>>(grid, dim3(256), lds, 150 * 1024, s, a);
 }
 // the transposed form exists for the k x k kernels (a.tr is never set for k = 1)
 template <int KS, int CK, int MODE, int NBUF, int WM, int NF, int SP>
@@ -1025,48 +1004,16 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
                        hipStream_t s) {
   using namespace bf;
   const int sp = split ? 2 : 1;
-  if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d_bf16: ngroups must be 1 or 2");
-  RTPOSE_REFUSE_PLANES(d, ngroups, "conv2d_bf16");
-  RTPOSE_REFUSE_PRELU(d, ngroups, "conv2d_bf16");
+  // bf16x3 outputs in bf16 are split pieces whose element offset is not a channel count (see the scalar epilogue)
+  const ConvSpec spec = {split ? "conv2d_bf16x3" : "conv2d_bf16", 8 * sp, sp, !split, false, false, !split || out_f32};
+  if (int rc = check_conv_features(d, ngroups, spec)) return rc;
   const rtpose_conv_desc& d0 = d[0];
-  if (d0.k != 1 && d0.k != 3 && d0.k != 7) return fail(RTPOSE_E_INVAL, "conv2d_bf16: k must be 1, 3 or 7");
-  if (d0.cin % 16 != 0 || d0.cin <= 0) return fail(RTPOSE_E_INVAL, "conv2d_bf16: cin must be a multiple of 16");
-  if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "conv2d_bf16: empty tensor");
-  const int P = d0.k / 2;
+  if (d0.k != 1 && d0.k != 3 && d0.k != 7) return fail(RTPOSE_E_INVAL, "%s: k must be 1, 3 or 7", spec.who);
+  if (d0.cin % 16 != 0 || d0.cin <= 0) return fail(RTPOSE_E_INVAL, "%s: cin must be a multiple of 16", spec.who);
+  if (int rc = check_conv_layouts(d, ngroups, N, H, W, spec)) return rc;
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  for (int i = 0; i < ngroups; ++i) {
-    const rtpose_conv_desc& di = d[i];
-    if (di.k != d0.k || di.cin != d0.cin || di.relu != d0.relu || di.pool != d0.pool ||
-        cout_pad(di.cout) != cout_pad(d0.cout) || di.lin.ws != d0.lin.ws || di.lin.hs != d0.lin.hs)
-      return fail(RTPOSE_E_INVAL, "conv2d_bf16: grouped convs must share geometry");
-    if (di.lin.ws < W + P || di.lin.hs < H + P || di.lin.lead < P * di.lin.ws + P)
-      return fail(RTPOSE_E_INVAL, "conv2d_bf16: input layout gap smaller than the conv padding");
-    if ((di.lin.cstride % (8 * sp)) || (di.lin.choff % (8 * sp)))
-      return fail(RTPOSE_E_INVAL, "conv2d_bf16: input slice must be 16-byte aligned");
-    if (di.lin.choff + di.cin * sp > di.lin.cstride)
-      return fail(RTPOSE_E_INVAL, "conv2d_bf16: input slice exceeds cstride");
-    if (split && di.out_cmap) return fail(RTPOSE_E_INVAL, "conv2d_bf16x3: out_cmap is not supported");
-    ConvGroup& g = a.g[i];
-    g.in = reinterpret_cast<const unsigned short*>(di.in);
-    g.w = reinterpret_cast<const float4*>(di.w_packed);
-    g.bias = di.bias_packed;
-    g.out = di.out;
-    g.in_cstride = di.lin.cstride;
-    g.in_choff = di.lin.choff;
-    g.in_ws = di.lin.ws;
-    g.in_hs = di.lin.hs;
-    g.in_lead = di.lin.lead;
-    g.out_cstride = di.lout.cstride;
-    g.out_choff = di.lout.choff;
-    g.out_ws = di.lout.ws;
-    g.out_hs = di.lout.hs;
-    g.out_lead = di.lout.lead;
-    g.cout = di.cout;
-    g.cout_pad = cout_pad(di.cout);
-    g.out_cmap = di.out_cmap;
-  }
-  if (d0.pool && ((H | W) & 1)) return fail(RTPOSE_E_INVAL, "conv2d_bf16: fused pool needs even H and W");
+  for (int i = 0; i < ngroups; ++i) fill_group(a.g[i], d[i]);
   {
     // 3x3 layers with 64 input channels (conv1_2, conv2_1) have their own kernel: the whole K of a tile in one LDS halo,
     // persistent blocks (conv_c64_bf16.hip)
@@ -1106,9 +1053,8 @@ int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   pl.nf = (wide && pl.wm == 2) ? 2 : 1;
   a.ntiles = coutp / (32 * pl.nf * (4 / pl.wm));
   a.ncombo = a.ntiles * ngroups;
-  a.xcd_remap = (a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
-  const long ids = a.xcd_remap ? (long)8 * a.ncombo * ceil_div(a.mtiles, 8) : (long)a.mtiles * a.ncombo;
-  if (ids > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d_bf16: grid too large");
+  long ids;
+  if (int rc = grid_ids(a.mtiles, a.ncombo, a.xcd_remap, ids, spec.who)) return rc;
   a.nbig = (int)ids;
   if (pl.mode == 0) {  // tail quantisation, see conv_mfma.hip
     const int slots = n_cu * 2;

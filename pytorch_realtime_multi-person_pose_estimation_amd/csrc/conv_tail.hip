@@ -12,7 +12,7 @@
 // same bits as with the two separate launches.  Weights are the generic kernel's k = 1 packing [c / 4][cout_pad][4].
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -181,27 +181,19 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void tail_kernel(const Args A
 // Two grouped 1x1 convs back to back: d1[g] = 128 -> 128 | 512 (+ReLU), d2[g] = that -> cout2 <= 64 (no ReLU) reading d1[g]'s
 // output, which is never written.  Descriptors as for rtpose_conv2d (k = 1, plain packing); d1[g].out / lout are ignored.
 int conv_tail_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups) {
-  if (!d1 || !d2 || ngroups < 1 || ngroups > 2 || desc_has_prelu(d1, ngroups) || desc_has_prelu(d2, ngroups)) return 0;
-  for (int i = 0; i < ngroups; ++i) {
-    if (d1[i].k != 1 || d2[i].k != 1 || d1[i].cin != tail::KC || (d1[i].cout != tail::N1 && d1[i].cout != 4 * tail::N1) ||
-        d1[i].cout != d1[0].cout || d2[i].cin != d1[i].cout ||
-        d2[i].cout > tail::N2 || d2[i].cout < 1 || !d1[i].relu || d2[i].relu || d1[i].pool || d2[i].pool ||
-        d1[i].out_cmap || d2[i].out_cmap || (d1[i].lin.cstride % 4) || (d1[i].lin.choff % 4) ||
-        d1[i].lin.choff + tail::KC > d1[i].lin.cstride || d2[i].lout.choff + d2[i].cout > d2[i].lout.cstride)
-      return 0;
-  }
-  return 1;
+  static_assert(tail::KC == 128 && tail::N1 == 128 && tail::N2 == 64, "conv_pair_fits: the pair's shape");
+  return conv_pair_fits(d1, d2, ngroups, 4, false);
 }
 
 int conv_tail_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N, int H, int W,
                      hipStream_t s) {
   using namespace tail;
-  RTPOSE_REFUSE_PRELU(d1, ngroups, "conv_tail");
-  RTPOSE_REFUSE_PRELU(d2, ngroups, "conv_tail");
+  const ConvSpec spec = {"conv_tail", 4, 1, false, false, false, true};
+  if (int rc = check_conv_features(d1, ngroups, spec)) return rc;
+  if (int rc = check_conv_features(d2, ngroups, spec)) return rc;
   if (!conv_tail_fits(d1, d2, ngroups) || N <= 0 || H <= 0 || W <= 0)
-    return fail(RTPOSE_E_INVAL, "conv_tail: needs 128 -> 128 | 512 (+ReLU) -> <= 64 pointwise convs");
-  RTPOSE_REFUSE_PLANES(d1, ngroups, "conv_tail");
-  RTPOSE_REFUSE_PLANES(d2, ngroups, "conv_tail");
+    return fail(RTPOSE_E_INVAL, "conv_tail: needs 128 -> 128 | 512 (+ReLU) -> <= 64 pointwise convs on 16-byte aligned "
+                                "slices (no out_cmap; a slice that exceeds cstride is refused)");
   const long M = (long)N * H * W;
   if (M > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv_tail: tensor too large");
   Args a;
@@ -226,8 +218,7 @@ int conv_tail_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int
     g.out_lead = d2[i].lout.lead;
     g.cout2 = d2[i].cout;
     // 32-bit element offsets inside the kernel
-    if (rtpose_layout_pixels(&d1[i].lin, N, H, W) * (size_t)d1[i].lin.cstride > 0x7fffffffULL ||
-        rtpose_layout_pixels(&d2[i].lout, N, H, W) * (size_t)d2[i].lout.cstride > 0x7fffffffULL)
+    if (!below_2g_elems(d1[i].lin, N, H, W) || !below_2g_elems(d2[i].lout, N, H, W))
       return fail(RTPOSE_E_INVAL, "conv_tail: buffer too large for 32-bit offsets");
   }
   a.N = N;
@@ -240,18 +231,10 @@ int conv_tail_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int
   const size_t lds = (size_t)(np == 1 ? 1 : 2) * (KC / 4) * PS * sizeof(float4) + 2 * BM * sizeof(int);
   if (np == 1) {
     hipLaunchKernelGGL(tail_kernel<1>, dim3((unsigned)a.mtiles * ngroups), dim3(256), lds, s, a);
-  } else {
-    static PerDeviceOnce attr_set;
-    const int dev = current_device();
-    if (!attr_set.is_set(dev)) {
-      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_kernel<4>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-      attr_set.set(dev);
-    }
-    hipLaunchKernelGGL(tail_kernel<4>, dim3((unsigned)a.mtiles * ngroups), dim3(256), lds, s, a);
+    RTPOSE_HIP_CHECK(hipGetLastError());
+    return 0;
   }
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<tail_kernel<4>>(dim3((unsigned)a.mtiles * ngroups), dim3(256), lds, 80 * 1024, s, a);
 }
 
 }  // namespace rtpose

@@ -21,7 +21,7 @@
 // Weights are the generic kernel's k = 1 packing [cin / 8][cout_pad][8 bf16] (rtpose_pack_conv_weights_bf16).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -221,32 +221,25 @@ __global__ __launch_bounds__(256) void tail_bf16_kernel(const Args A) {
 // d1[g] / d2[g]: the two convs of branch g (k = 1; d1: 128 -> 128 | 512 with ReLU, d2: -> cout <= 64).  d1[g].in / lin: bf16
 // input (16-byte aligned slices); d2[g].out / lout: bf16 elements, or fp32 when out_f32; d1[g].out is not touched.
 int conv_tail_bf16_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups) {
-  if (!d1 || !d2 || ngroups < 1 || ngroups > 2 || desc_has_prelu(d1, ngroups) || desc_has_prelu(d2, ngroups)) return 0;
-  for (int g = 0; g < ngroups; ++g) {
-    if (d1[g].k != 1 || d2[g].k != 1 || d1[g].cin != tailb::KC || !d1[g].relu || d1[g].pool || d2[g].pool) return 0;
-    if (d1[g].cout != 128 && d1[g].cout != 512) return 0;
-    if (d1[g].cout != d1[0].cout || d2[g].cin != d1[g].cout || d2[g].cout < 1 || d2[g].cout > tailb::N2) return 0;
-    if ((d1[g].lin.cstride % 8) || (d1[g].lin.choff % 8)) return 0;
-    if (d2[g].relu != d2[0].relu) return 0;
-  }
-  return 1;
+  static_assert(tailb::KC == 128 && tailb::N2 == 64, "conv_pair_fits: the pair's shape");
+  return conv_pair_fits(d1, d2, ngroups, 8, true);
 }
 
 int conv_tail_bf16_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N, int H, int W,
                           int out_f32, hipStream_t s) {
   using namespace tailb;
-  RTPOSE_REFUSE_PRELU(d1, ngroups, "conv1x1_pair_bf16");
-  RTPOSE_REFUSE_PRELU(d2, ngroups, "conv1x1_pair_bf16");
+  if (desc_has_prelu(d1, ngroups) || desc_has_prelu(d2, ngroups))
+    return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: no PReLU epilogue (rtpose_conv_desc.prelu)");
   if (!conv_tail_bf16_fits(d1, d2, ngroups))
-    return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: not a 128 -> 128 | 512 (ReLU) -> <= 64 pair of 1x1 convs on 16-byte aligned bf16 slices");
+    return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: not a 128 -> 128 | 512 (ReLU) -> <= 64 pair of 1x1 convs on 16-byte "
+                                "aligned bf16 slices (no out_cmap; a slice that exceeds cstride is refused)");
   if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: empty tensor");
   Args a;
   memset(&a, 0, sizeof(a));
   for (int g = 0; g < ngroups; ++g) {
     if (!d1[g].in || !d1[g].w_packed || !d1[g].bias_packed || !d2[g].w_packed || !d2[g].bias_packed || !d2[g].out)
       return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: NULL argument");
-    if (rtpose_layout_pixels(&d1[g].lin, N, H, W) * (size_t)d1[g].lin.cstride >= ((size_t)1 << 31) ||
-        rtpose_layout_pixels(&d2[g].lout, N, H, W) * (size_t)d2[g].lout.cstride >= ((size_t)1 << 31))
+    if (!below_2g_elems(d1[g].lin, N, H, W) || !below_2g_elems(d2[g].lout, N, H, W))
       return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: tensors must be below 2^31 elements (32-bit offsets)");
     Group& q = a.g[g];
     q.in = reinterpret_cast<const unsigned short*>(d1[g].in);
@@ -268,7 +261,6 @@ int conv_tail_bf16_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2
     q.cout2 = d2[g].cout;
     q.coutp1 = cout_pad(d1[g].cout);
     q.coutp2 = cout_pad(d2[g].cout);
-    if (q.out_choff + q.cout2 > q.out_cstride) return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: output slice exceeds cstride");
   }
   a.N = N;
   a.H = H;
@@ -278,21 +270,9 @@ int conv_tail_bf16_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2
   a.out_f32 = out_f32 ? 1 : 0;
   a.relu2 = d2[0].relu ? 1 : 0;
   const int mtiles = ceil_div(a.M, BM);
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_bf16_kernel<1>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_bf16_kernel<4>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    attr_set.set(dev);
-  }
-  if (d1[0].cout == 128)
-    hipLaunchKernelGGL(tail_bf16_kernel<1>, dim3(mtiles * ngroups), dim3(256), lds_bytes(), s, a);
-  else
-    hipLaunchKernelGGL(tail_bf16_kernel<4>, dim3(mtiles * ngroups), dim3(256), lds_bytes(), s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  const dim3 grid(mtiles * ngroups);
+  if (d1[0].cout == 128) return launch_kernel<tail_bf16_kernel<1>>(grid, dim3(256), lds_bytes(), 64 * 1024, s, a);
+  return launch_kernel<tail_bf16_kernel<4>>(grid, dim3(256), lds_bytes(), 64 * 1024, s, a);
 }
 
 }  // namespace rtpose

@@ -35,7 +35,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_desc.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -701,18 +701,8 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, const float* __res
 
 template <int WM, int WN, int CK, bool PR = false>
 static int launch_inst(const ArgsT<PR>& a, dim3 grid, hipStream_t s) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  auto kern = wino_f32<WM, WN, CK, PR>;
   constexpr size_t lds = (size_t)2 * 16 * (CK / 4) * (32 * WM) * 16;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<wino_f32<WM, WN, CK, PR>>(grid, dim3(256), lds, 150 * 1024, s, a);
 }
 
 }  // namespace wino
@@ -739,17 +729,8 @@ int wino_run(wino::ArgsT<PR> a, long ids, int ngroups, int ck, int wm, int cout0
     b.mtiles = ceil_div(a.T, 32);
     b.ntiles = cout_pad(cout0) / 32;
     b.ncombo = b.ntiles * ngroups;
-    static PerDeviceOnce attr_set;
-    const int dev = current_device();
-    if (!attr_set.is_set(dev)) {
-      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino3s_f32<PR>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      attr_set.set(dev);
-    }
-    hipLaunchKernelGGL(wino3s_f32<PR>, dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(256),
-                       (size_t)2 * 16 * 4 * 32 * 16, s, b);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_kernel<wino3s_f32<PR>>(dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(256),
+                                         (size_t)2 * 16 * 4 * 32 * 16, 150 * 1024, s, b);
   }
   if (wm == 1) return launch_inst<1, 4, 16, PR>(a, grid, s);
   // 64 columns (conv1_2): 64 wtiles x 64 columns; 16-channel chunks with a whole patch per thread where cin allows
@@ -760,45 +741,18 @@ int wino_run(wino::ArgsT<PR> a, long ids, int ngroups, int ck, int wm, int cout0
 
 int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
   using namespace wino;
-  if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d_winograd: ngroups must be 1 or 2");
-  RTPOSE_REFUSE_PLANES(d, ngroups, "conv2d_winograd (2x2)");
-  RTPOSE_CHECK_PRELU(d, ngroups, "conv2d_winograd (2x2)");
+  const ConvSpec spec = {"conv2d_winograd (2x2)", 4, 1, false, false, true, true};
+  if (int rc = check_conv_features(d, ngroups, spec)) return rc;
   const rtpose_conv_desc& d0 = d[0];
   if (!conv2d_wino_ok(d0.cin, d0.cout, d0.k))
-    return fail(RTPOSE_E_INVAL, "conv2d_winograd: k must be 3 and cin a multiple of %d", wino_ck(d0.cout, d0.cin));
-  if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "conv2d_winograd: empty tensor");
-  if (d0.pool && ((H | W) & 1)) return fail(RTPOSE_E_INVAL, "conv2d_winograd: fused pool needs even H and W");
+    return fail(RTPOSE_E_INVAL, "%s: k must be 3 and cin a multiple of %d", spec.who, wino_ck(d0.cout, d0.cin));
+  if (int rc = check_conv_layouts(d, ngroups, N, H, W, spec)) return rc;
   Args a;
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < ngroups; ++i) {
     const rtpose_conv_desc& di = d[i];
-    if (di.k != 3 || di.cin != d0.cin || di.relu != d0.relu || di.pool != d0.pool ||
-        cout_pad(di.cout) != cout_pad(d0.cout) || di.lin.ws != d0.lin.ws || di.lin.hs != d0.lin.hs)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: grouped convs must share geometry");
-    if (di.lin.ws < W + 1 || di.lin.hs < H + 1 || di.lin.lead < di.lin.ws + 1)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input layout gap smaller than the conv padding");
-    if ((di.lin.cstride % 4) || (di.lin.choff % 4))
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input slice must be 16-byte aligned");
-    if (di.lin.choff + di.cin > di.lin.cstride)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input slice exceeds cstride");
-    if (di.out_cmap) return fail(RTPOSE_E_INVAL, "conv2d_winograd: out_cmap is not supported");
     Group& g = a.g[i];
-    g.in = di.in;
-    g.w = di.w_packed;
-    g.bias = di.bias_packed;
-    g.out = di.out;
-    g.in_cstride = di.lin.cstride;
-    g.in_choff = di.lin.choff;
-    g.in_ws = di.lin.ws;
-    g.in_hs = di.lin.hs;
-    g.in_lead = di.lin.lead;
-    g.out_cstride = di.lout.cstride;
-    g.out_choff = di.lout.choff;
-    g.out_ws = di.lout.ws;
-    g.out_hs = di.lout.hs;
-    g.out_lead = di.lout.lead;
-    g.cout = di.cout;
-    g.cout_pad = cout_pad(di.cout);
+    fill_group(g, di);
     g.in_bytes = rtpose_layout_pixels(&di.lin, N, H, W) * (size_t)di.lin.cstride * sizeof(float);
     g.w_bytes = rtpose_packed_weight_floats_winograd(di.cout, di.cin, 3) * sizeof(float);
     g.out_bytes = rtpose_layout_pixels(&di.lout, N, di.pool ? H / 2 : H, di.pool ? W / 2 : W) *
@@ -810,7 +764,7 @@ int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   a.TY = ceil_div(H, 2);
   a.TX = ceil_div(W, 2);
   const long T = (long)N * a.TY * a.TX;
-  if (T > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d_winograd: tensor too large");
+  if (T > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "%s: tensor too large", spec.who);
   a.T = (int)T;
   a.cin = d0.cin;
   a.relu = d0.relu;
@@ -820,9 +774,8 @@ int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   a.mtiles = ceil_div(a.T, 32 * wm);
   a.ntiles = cout_pad(d0.cout) / (32 * wn);
   a.ncombo = a.ntiles * ngroups;
-  a.xcd_remap = (a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
-  long ids = a.xcd_remap ? (long)8 * a.ncombo * ceil_div(a.mtiles, 8) : (long)a.mtiles * a.ncombo;
-  if (ids > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d_winograd: grid too large");
+  long ids;
+  if (int rc = grid_ids(a.mtiles, a.ncombo, a.xcd_remap, ids, spec.who)) return rc;
   {
     // persistent blocks when a CU would get more than one tile anyway (see wino_f32)
     const int n_cu = device_cu_count();
@@ -834,8 +787,7 @@ int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int
   if (!d0.prelu) return wino_run<false>(a, ids, ngroups, ck, wm, d0.cout, s);
   ArgsP ap;
   static_cast<Args&>(ap) = a;
-  ap.prelu[0] = d[0].prelu;
-  ap.prelu[1] = ngroups > 1 ? d[1].prelu : d[0].prelu;
+  set_prelu(ap, d, ngroups);
   return wino_run<true>(ap, ids, ngroups, ck, wm, d0.cout, s);
 }
 

@@ -59,7 +59,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_desc.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -946,17 +946,8 @@ int wino4_run(wino4::ArgsT<PR> a, long ids, int ngroups, int cout0, hipStream_t 
     b.mtiles = (int)((wtiles + NTS - 1) / NTS);
     b.ntiles = cout_pad(cout0) / 16;
     b.ncombo = b.ntiles * ngroups;
-    static PerDeviceOnce attr_s;
-    const int dev_s = current_device();
-    if (!attr_s.is_set(dev_s)) {
-      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4s_f32<PR>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-      attr_s.set(dev_s);
-    }
-    hipLaunchKernelGGL(wino4s_f32<PR>, dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(384),
-                       (size_t)(2 * VBUFS + 2 * UBUFS) * sizeof(float4), s, b);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_kernel<wino4s_f32<PR>>(dim3((unsigned)((long)b.mtiles * b.ncombo)), dim3(384),
+                                         (size_t)(2 * VBUFS + 2 * UBUFS) * sizeof(float4), 80 * 1024, s, b);
   };
   auto launch_half = [&](const ArgsT<PR>& a0, int mt0_32, long wtiles) -> int {
     // half tiles (wino4_f32<1, PR>: 16 wtiles x 64 columns, one per block), bit-identical: `wtiles` wtiles from m tile mt0_32 on
@@ -964,18 +955,10 @@ int wino4_run(wino4::ArgsT<PR> a, long ids, int ngroups, int cout0, hipStream_t 
     b.persist = 0;
     b.mt0 = 2 * mt0_32;
     b.mtiles = (int)((wtiles + 15) / 16);
-    b.xcd_remap = (b.ncombo > 1 && b.mtiles >= 64) ? 1 : 0;
-    const long idh = b.xcd_remap ? (long)8 * b.ncombo * ceil_div(b.mtiles, 8) : (long)b.mtiles * b.ncombo;
-    static PerDeviceOnce attr_h;
-    const int dev_h = current_device();
-    if (!attr_h.is_set(dev_h)) {
-      RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_f32<1, PR>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      attr_h.set(dev_h);
-    }
-    hipLaunchKernelGGL((wino4_f32<1, PR>), dim3((unsigned)idh), dim3(512), (size_t)(VBUF + UBUF) * sizeof(float4), s, b);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-    return 0;
+    long idh;
+    if (int rc = grid_ids(b.mtiles, b.ncombo, b.xcd_remap, idh, "conv2d_winograd (4x4)")) return rc;
+    return launch_kernel<wino4_f32<1, PR>>(dim3((unsigned)idh), dim3(512), (size_t)(VBUF + UBUF) * sizeof(float4), 150 * 1024,
+                                           s, b);
   };
   // launches that fill at most half the CUs with 32 x 64 tiles run the 16 x 16 form (measured: at one round and beyond
   // the big tiles win - the small form fetches the filters four times as often; ee158f6:tools/r3_sessions/session27.sh)
@@ -1005,15 +988,9 @@ int wino4_run(wino4::ArgsT<PR> a, long ids, int ngroups, int cout0, hipStream_t 
     a.persist = 1;
     ids = n_cu;
   }
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_f32<2, PR>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL((wino4_f32<2, PR>), dim3((unsigned)ids), dim3(512), (size_t)(2 * VBUF + 2 * UBUF) * sizeof(float4), s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
+  if (int rc = launch_kernel<wino4_f32<2, PR>>(dim3((unsigned)ids), dim3(512), (size_t)(2 * VBUF + 2 * UBUF) * sizeof(float4),
+                                               150 * 1024, s, a))
+    return rc;
   if (rest && rest_half) return launch_half(a, a.mtiles, (long)a.T - (long)a.mtiles * NT);
   if (rest) return launch_small(a, a.mtiles, (long)a.T - (long)a.mtiles * NT);
   return 0;
@@ -1022,55 +999,29 @@ int wino4_run(wino4::ArgsT<PR> a, long ids, int ngroups, int cout0, hipStream_t 
 
 int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
   using namespace wino4;
-  if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d_winograd (4x4): ngroups must be 1 or 2");
-  RTPOSE_CHECK_PRELU(d, ngroups, "conv2d_winograd (4x4)");
+  const ConvSpec spec = {"conv2d_winograd (4x4)", 4, 1, false, true, true, true};
+  if (int rc = check_conv_features(d, ngroups, spec)) return rc;
   const rtpose_conv_desc& d0 = d[0];
   if (d0.k != 3 || !conv2d_wino4_ok(d0.cin, d0.cout))
-    return fail(RTPOSE_E_INVAL, "conv2d_winograd (4x4): k must be 3 and cin a multiple of 16, >= 32");
-  if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "conv2d_winograd: empty tensor");
-  if (d0.pool && ((H | W) & 1)) return fail(RTPOSE_E_INVAL, "conv2d_winograd: fused pool needs even H and W");
+    return fail(RTPOSE_E_INVAL, "%s: k must be 3 and cin a multiple of 16, >= 32", spec.who);
+  if (int rc = check_conv_layouts(d, ngroups, N, H, W, spec)) return rc;
   Args a;
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < ngroups; ++i) {
     const rtpose_conv_desc& di = d[i];
-    if (di.k != 3 || di.cin != d0.cin || di.relu != d0.relu || di.pool != d0.pool ||
-        cout_pad(di.cout) != cout_pad(d0.cout) || di.lin.ws != d0.lin.ws || di.lin.hs != d0.lin.hs)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: grouped convs must share geometry");
-    if (di.lin.ws < W + 1 || di.lin.hs < H + 1 || di.lin.lead < di.lin.ws + 1)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input layout gap smaller than the conv padding");
-    if ((di.lin.cstride % 4) || (di.lin.choff % 4))
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input slice must be 16-byte aligned");
-    if (di.lin.choff + di.cin > di.lin.cstride)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input slice exceeds cstride");
-    if (di.out_cmap) return fail(RTPOSE_E_INVAL, "conv2d_winograd: out_cmap is not supported");
     if (di.in_plane_pixels < 0 || di.out_plane_pixels < 0 ||
         (di.in_plane_pixels && ((di.lin.choff % 8) || (size_t)di.in_plane_pixels < rtpose_layout_pixels(&di.lin, N, H, W))) ||
         (di.out_plane_pixels &&
          ((di.lout.choff % 8) || (di.cout % 8) ||
           (size_t)di.out_plane_pixels < rtpose_layout_pixels(&di.lout, N, di.pool ? H / 2 : H, di.pool ? W / 2 : W))))
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd (4x4): channel-plane slices start at a multiple of 8 channels (the output "
-                                  "has a multiple of 8 of them) and a plane holds at least the layout's pixels");
+      return fail(RTPOSE_E_INVAL, "%s: channel-plane slices start at a multiple of 8 channels (the output "
+                                  "has a multiple of 8 of them) and a plane holds at least the layout's pixels", spec.who);
     // per-lane offsets are 32 bits and the descriptors clamp at 2 GiB: a plane slice spans (channels / 8) planes
     if ((di.in_plane_pixels && (size_t)(di.lin.choff + di.cin) / 8 * di.in_plane_pixels * 32 > (size_t)winoc::kMaxRange) ||
         (di.out_plane_pixels && (size_t)(di.lout.choff + cout_pad(di.cout)) / 8 * di.out_plane_pixels * 32 > (size_t)winoc::kMaxRange))
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd (4x4): channel-plane slice beyond 2 GiB");
+      return fail(RTPOSE_E_INVAL, "%s: channel-plane slice beyond 2 GiB", spec.who);
     Group& g = a.g[i];
-    g.in = di.in;
-    g.w = di.w_packed;
-    g.bias = di.bias_packed;
-    g.out = di.out;
-    g.in_cstride = di.lin.cstride;
-    g.in_choff = di.lin.choff;
-    g.in_ws = di.lin.ws;
-    g.in_hs = di.lin.hs;
-    g.in_lead = di.lin.lead;
-    g.out_cstride = di.lout.cstride;
-    g.out_choff = di.lout.choff;
-    g.out_ws = di.lout.ws;
-    g.out_hs = di.lout.hs;
-    g.out_lead = di.lout.lead;
-    g.cout = di.cout;
-    g.cout_pad = cout_pad(di.cout);
+    fill_group(g, di);
     g.in_pq = di.in_plane_pixels;
     g.out_pq = di.out_plane_pixels;
     // bytes addressable from the buffer base: the whole pixel-major tensor, or the planes up to the slice's last one
@@ -1087,7 +1038,7 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
   a.TY = ceil_div(H, 4);
   a.TX = ceil_div(W, 4);
   const long T = (long)N * a.TY * a.TX;
-  if (T > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d_winograd: tensor too large");
+  if (T > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "%s: tensor too large", spec.who);
   a.T = (int)T;
   a.cin = d0.cin;
   a.relu = d0.relu;
@@ -1095,14 +1046,12 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
   a.mtiles = ceil_div(a.T, NT);
   a.ntiles = cout_pad(d0.cout) / NC;
   a.ncombo = a.ntiles * ngroups;
-  a.xcd_remap = (a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
-  long ids = a.xcd_remap ? (long)8 * a.ncombo * ceil_div(a.mtiles, 8) : (long)a.mtiles * a.ncombo;
-  if (ids > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d_winograd: grid too large");
+  long ids;
+  if (int rc = grid_ids(a.mtiles, a.ncombo, a.xcd_remap, ids, spec.who)) return rc;
   if (!d0.prelu) return wino4_run<false>(a, ids, ngroups, d0.cout, s);
   ArgsP ap;
   static_cast<Args&>(ap) = a;
-  ap.prelu[0] = d[0].prelu;
-  ap.prelu[1] = ngroups > 1 ? d[1].prelu : d[0].prelu;
+  set_prelu(ap, d, ngroups);
   return wino4_run<true>(ap, ids, ngroups, d0.cout, s);
 }
 

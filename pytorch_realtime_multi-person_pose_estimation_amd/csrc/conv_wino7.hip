@@ -34,7 +34,7 @@
 
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_desc.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -893,35 +893,15 @@ static int make_plan(int N, int H, int W, int hs, int fm, Plan* p) {
 
 template <int NI, int GXT, int FM, int FS = 1>
 static int launch_inst(const Args& a, dim3 grid, size_t lds, hipStream_t s) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  auto kern = wino7_f32<NI, GXT, FM, FS>;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set.set(dev);
-  }
   // FS = 2: the accumulator exchange of the epilogue (4 wave tiles x 2 halves x 6 frequencies x 8 registers x 64
   // lanes) lives where the V buffers were
   const size_t ex = FS == 2 ? (size_t)4 * 2 * (FM + 6) / 2 * 8 * 64 * sizeof(float) : 0;
-  hipLaunchKernelGGL(kern, grid, dim3(256 * FS), lds > ex ? lds : ex, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<wino7_f32<NI, GXT, FM, FS>>(grid, dim3(256 * FS), lds > ex ? lds : ex, 160 * 1024, s, a);
 }
 
 template <int NI>
 static int launch_small(const Args& a, dim3 grid, size_t lds, hipStream_t s) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  auto kern = wino7s_f32<NI>;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<wino7s_f32<NI>>(grid, dim3(256), lds, 160 * 1024, s, a);
 }
 
 // ---- amplification estimate of a filter bank in a Winograd form ("numerics") ----------------
@@ -1071,44 +1051,19 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
                         size_t scratch_bytes, hipStream_t s) {
   using namespace wino7;
   fm = resolve_fm(fm);
-  if (!d || ngroups < 1 || ngroups > 2) return fail(RTPOSE_E_INVAL, "conv2d_winograd: ngroups must be 1 or 2");
-  RTPOSE_REFUSE_PLANES(d, ngroups, "conv2d_winograd (7x7)");
-  RTPOSE_REFUSE_PRELU(d, ngroups, "conv2d_winograd (7x7)");
+  const ConvSpec spec = {"conv2d_winograd (7x7)", 4, 1, false, false, false, true};
+  if (int rc = check_conv_features(d, ngroups, spec)) return rc;
   const rtpose_conv_desc& d0 = d[0];
   if (d0.k != 7 || d0.pool || !conv2d_wino7_fits(d0.cin, d0.cout, N, H, W, d0.lin.hs, fm))
-    return fail(RTPOSE_E_INVAL, "conv2d_winograd: no F(%d,7) instance for cin %d cout %d at %d x %d x %d", fm, d0.cin,
+    return fail(RTPOSE_E_INVAL, "%s: no F(%d,7) instance for cin %d cout %d at %d x %d x %d", spec.who, fm, d0.cin,
                 d0.cout, N, H, W);
+  if (int rc = check_conv_layouts(d, ngroups, N, H, W, spec)) return rc;
   Args a;
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < ngroups; ++i) {
     const rtpose_conv_desc& di = d[i];
-    if (di.k != 7 || di.cin != d0.cin || di.relu != d0.relu || di.pool ||
-        cout_pad(di.cout) != cout_pad(d0.cout) || di.lin.ws != d0.lin.ws || di.lin.hs != d0.lin.hs)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: grouped convs must share geometry");
-    if (di.lin.ws < W + 3 || di.lin.hs < H + 3 || di.lin.lead < 3 * di.lin.ws + 3)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input layout gap smaller than the conv padding");
-    if ((di.lin.cstride % 4) || (di.lin.choff % 4))
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input slice must be 16-byte aligned");
-    if (di.lin.choff + di.cin > di.lin.cstride)
-      return fail(RTPOSE_E_INVAL, "conv2d_winograd: input slice exceeds cstride");
-    if (di.out_cmap) return fail(RTPOSE_E_INVAL, "conv2d_winograd: out_cmap is not supported");
     Group& g = a.g[i];
-    g.in = di.in;
-    g.w = di.w_packed;
-    g.bias = di.bias_packed;
-    g.out = di.out;
-    g.in_cstride = di.lin.cstride;
-    g.in_choff = di.lin.choff;
-    g.in_ws = di.lin.ws;
-    g.in_hs = di.lin.hs;
-    g.in_lead = di.lin.lead;
-    g.out_cstride = di.lout.cstride;
-    g.out_choff = di.lout.choff;
-    g.out_ws = di.lout.ws;
-    g.out_hs = di.lout.hs;
-    g.out_lead = di.lout.lead;
-    g.cout = di.cout;
-    g.cout_pad = cout_pad(di.cout);
+    fill_group(g, di);
     g.in_bytes = rtpose_layout_pixels(&di.lin, N, H, W) * (size_t)di.lin.cstride * sizeof(float);
     g.w_bytes = packed_weight_floats_wino7(di.cout, di.cin, fm) * sizeof(float);
   }
@@ -1127,9 +1082,8 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
   a.mtiles = p.mtiles;
   a.ntiles = cout_pad(d0.cout) / 128;
   a.ncombo = a.ntiles * ngroups;
-  a.xcd_remap = (a.ncombo > 1 && a.mtiles >= 64) ? 1 : 0;
-  long ids = a.xcd_remap ? (long)8 * a.ncombo * ceil_div(a.mtiles, 8) : (long)a.mtiles * a.ncombo;
-  if (ids > 0x7fffffffL) return fail(RTPOSE_E_INVAL, "conv2d_winograd: grid too large");
+  long ids;
+  if (int rc = grid_ids(a.mtiles, a.ncombo, a.xcd_remap, ids, spec.who)) return rc;
   {
     // persistent form: as many blocks as CUs share the (tile, chunk) units evenly; worth it (and valid: a tile
     // may be split between at most two blocks) when there are at least as many tiles as CUs and the tiles do

@@ -27,7 +27,7 @@
 //     run under the other's MFMAs.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -594,17 +594,7 @@ int pw_halo_stride(const rtpose_layout& l, int H, int W) {
 
 template <int WM, int MF, int NFW, bool DW>
 static int pw_launch_inst(const PwArgs& a, int grid, size_t lds, hipStream_t s) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  auto kern = pw_gemm_f32<WM, MF, NFW, DW>;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<pw_gemm_f32<WM, MF, NFW, DW>>(dim3(grid), dim3(256), lds, 96 * 1024, s, a);
 }
 
 int pw_fused_launch(const rtpose_pw_desc* d, int N, int H, int W, hipStream_t s) {
@@ -613,19 +603,18 @@ int pw_fused_launch(const rtpose_pw_desc* d, int N, int H, int W, hipStream_t s)
   if (d->cin <= 0 || (d->cin % 8)) return fail(RTPOSE_E_INVAL, "pw_fused: cin must be a multiple of 8");
   if (d->coutp != 64 && d->coutp != 128 && (d->coutp % 256)) return fail(RTPOSE_E_INVAL, "pw_fused: coutp must be 64, 128 or a multiple of 256");
   if (d->cout <= 0 || d->cout > d->coutp) return fail(RTPOSE_E_INVAL, "pw_fused: cout exceeds coutp");
-  if ((d->lin.cstride % 4) || (d->lin.choff % 4) || (!d->in_planes && d->lin.choff + d->cin > d->lin.cstride))
+  if (!slice_aligned(d->lin, 4) || (!d->in_planes && !slice_inside(d->lin, d->cin)))
     return fail(RTPOSE_E_INVAL, "pw_fused: input slice must be 16-byte aligned and inside the pixel");
   const bool dw = d->dw_w != nullptr;
-  if (dw && (!d->dw_b || d->lin.ws < W + 1 || d->lin.hs < H + 1 || d->lin.lead < d->lin.ws + 1))
+  if (dw && (!d->dw_b || !gap_covers(d->lin, H, W, 1)))
     return fail(RTPOSE_E_INVAL, "pw_fused: the depthwise input needs a layout gap of 1 and a bias");
-  if (d->pt_src && d->pt_pairs == 0 && (!d->pt_cmap || d->pt_c <= 0 || (d->lpt.cstride % 4) || (d->lpt.choff % 4)))
+  if (d->pt_src && d->pt_pairs == 0 && (!d->pt_cmap || d->pt_c <= 0 || !slice_aligned(d->lpt, 4)))
     return fail(RTPOSE_E_INVAL, "pw_fused: bad pass-through description");
   if (d->pt_src && d->pt_pairs > 0 &&
       ((d->lpt.cstride % 4) || ((d->lpt.choff + d->pt_a) % 4) || ((d->lpt.choff + d->pt_b) % 4) || d->pt_pairs < 0))
     return fail(RTPOSE_E_INVAL, "pw_fused: interleave pass-through runs must be 16-byte aligned");
   if (d->cin > kPwMaxK) return fail(RTPOSE_E_INVAL, "pw_fused: cin > 1024");
-  if (rtpose_layout_pixels(&d->lin, N, H, W) * (size_t)d->lin.cstride >= ((size_t)1 << 31) ||
-      rtpose_layout_pixels(&d->lout, N, H, W) * (size_t)d->lout.cstride >= ((size_t)1 << 31))
+  if (!below_2g_elems(d->lin, N, H, W) || !below_2g_elems(d->lout, N, H, W))
     return fail(RTPOSE_E_INVAL, "pw_fused: tensors must be below 2^31 floats (32-bit element offsets)");
   PwArgs a;
   memset(&a, 0, sizeof(a));

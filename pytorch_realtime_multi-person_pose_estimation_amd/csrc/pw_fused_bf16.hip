@@ -15,7 +15,7 @@
 //    host packs the weights with a column map (a run of the four-run layout per 8-aligned group).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -493,17 +493,7 @@ int halo_stride(const rtpose_layout& l, int H, int W) {
 
 template <int WM, int MF, int NFW, bool DW>
 static int launch_inst(const Args& a, int grid, size_t lds, hipStream_t s) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  auto kern = pw_gemm_bf16<WM, MF, NFW, DW>;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024));
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_kernel<pw_gemm_bf16<WM, MF, NFW, DW>>(dim3(grid), dim3(256), lds, 112 * 1024, s, a);
 }
 
 }  // namespace pwb
@@ -530,17 +520,16 @@ int pw_fused_bf16_launch(const rtpose_pw_desc* d, int out_f32, int N, int H, int
   if (d->cin <= 0 || (d->cin % 16) || d->cin > kMaxK) return fail(RTPOSE_E_INVAL, "pw_fused_bf16: cin must be a multiple of 16, <= 1024");
   if (d->coutp != 64 && d->coutp != 128 && (d->coutp % 256)) return fail(RTPOSE_E_INVAL, "pw_fused_bf16: coutp must be 64, 128 or a multiple of 256");
   if (d->cout <= 0 || d->cout > d->coutp) return fail(RTPOSE_E_INVAL, "pw_fused_bf16: cout exceeds coutp");
-  if ((d->lin.cstride % 8) || (d->lin.choff % 8) || (!d->in_planes && d->lin.choff + d->cin > d->lin.cstride))
+  if (!slice_aligned(d->lin, 8) || (!d->in_planes && !slice_inside(d->lin, d->cin)))
     return fail(RTPOSE_E_INVAL, "pw_fused_bf16: input slice must be 16-byte aligned and inside the pixel");
-  if (!out_f32 && ((d->lout.cstride % 8) || (d->lout.choff % 8) || (d->cout % 8) || d->lout.choff + d->cout > d->lout.cstride))
+  if (!out_f32 && (!slice_ok(d->lout, d->cout, 8) || (d->cout % 8)))
     return fail(RTPOSE_E_INVAL, "pw_fused_bf16: bf16 output = whole 8-channel groups inside the pixel");
   const bool dw = d->dw_w != nullptr;
-  if (dw && (!d->dw_b || d->lin.ws < W + 1 || d->lin.hs < H + 1 || d->lin.lead < d->lin.ws + 1))
+  if (dw && (!d->dw_b || !gap_covers(d->lin, H, W, 1)))
     return fail(RTPOSE_E_INVAL, "pw_fused_bf16: the depthwise input needs a layout gap of 1 and a bias");
   if (d->pt_src && (d->pt_pairs <= 0 || (d->lpt.cstride % 8) || ((d->lpt.choff + d->pt_a) % 8) || ((d->lpt.choff + d->pt_b) % 8)))
     return fail(RTPOSE_E_INVAL, "pw_fused_bf16: pass-through runs must be 16-byte aligned (interleave form only)");
-  if (rtpose_layout_pixels(&d->lin, N, H, W) * (size_t)d->lin.cstride >= ((size_t)1 << 31) ||
-      rtpose_layout_pixels(&d->lout, N, H, W) * (size_t)d->lout.cstride >= ((size_t)1 << 31))
+  if (!below_2g_elems(d->lin, N, H, W) || !below_2g_elems(d->lout, N, H, W))
     return fail(RTPOSE_E_INVAL, "pw_fused_bf16: tensors must be below 2^31 elements");
   Args a;
   memset(&a, 0, sizeof(a));

@@ -30,7 +30,7 @@
 // fixed, independent of the batch (an image's maps do not depend on its batch neighbours).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 
 namespace rtpose {
 
@@ -337,8 +337,8 @@ int pw_head_fits(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2) {
     return 0;
   if (!d1->relu || d2->relu || d1->dw_w || d2->dw_w || d1->pt_src || d2->pt_src || d1->out_cmap || d2->out_cmap) return 0;
   if (d2->cin != d1->coutp || d2->coutp != head::N2 || d2->cout < 1 || d2->cout > head::N2 || d1->coutp > 1024) return 0;
-  if ((d1->lin.cstride % 4) || (d1->lin.choff % 4) || (!d1->in_planes && d1->lin.choff + d1->cin > d1->lin.cstride)) return 0;
-  if ((d2->lout.cstride % 4) || (d2->lout.choff % 4) || d2->lout.choff + head::N2 > d2->lout.cstride) return 0;
+  if (!slice_aligned(d1->lin, 4) || (!d1->in_planes && !slice_inside(d1->lin, d1->cin))) return 0;
+  if (!slice_ok(d2->lout, head::N2, 4)) return 0;
   return 1;
 }
 
@@ -350,8 +350,7 @@ int pw_head_launch(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2, int N, in
     return fail(RTPOSE_E_INVAL, "pw_head: NULL argument");
   if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "pw_head: empty tensor");
   const long M = (long)N * H * W;
-  if (M > 0x7fffffffL || rtpose_layout_pixels(&d1->lin, N, H, W) * (size_t)d1->lin.cstride >= ((size_t)1 << 31) ||
-      rtpose_layout_pixels(&d2->lout, N, H, W) * (size_t)d2->lout.cstride >= ((size_t)1 << 31))
+  if (M > 0x7fffffffL || !below_2g_elems(d1->lin, N, H, W) || !below_2g_elems(d2->lout, N, H, W))
     return fail(RTPOSE_E_INVAL, "pw_head: tensors must be below 2^31 floats (32-bit element offsets)");
   Args a;
   memset(&a, 0, sizeof(a));

@@ -30,7 +30,7 @@
 // 16-channel group) in MFMA order.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -411,8 +411,8 @@ int pw_head_bf16_fits(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2) {
     return 0;
   if (!d1->relu || d2->relu || d1->dw_w || d2->dw_w || d1->pt_src || d2->pt_src || d1->out_cmap || d2->out_cmap) return 0;
   if (d2->cin != d1->coutp || d2->coutp != headb::N2 || d2->cout < 1 || d2->cout > headb::N2) return 0;
-  if ((d1->lin.cstride % 8) || (d1->lin.choff % 8) || (!d1->in_planes && d1->lin.choff + d1->cin > d1->lin.cstride)) return 0;
-  if ((d2->lout.cstride % 4) || (d2->lout.choff % 4) || d2->lout.choff + headb::N2 > d2->lout.cstride) return 0;
+  if (!slice_aligned(d1->lin, 8) || (!d1->in_planes && !slice_inside(d1->lin, d1->cin))) return 0;
+  if (!slice_ok(d2->lout, headb::N2, 4)) return 0;
   return 1;
 }
 
@@ -425,8 +425,7 @@ int pw_head_bf16_launch(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2, int 
   if (N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "pw_head_bf16: empty tensor");
   const long M = (long)N * H * W;
   const size_t in_bytes = rtpose_layout_pixels(&d1->lin, N, H, W) * (size_t)d1->lin.cstride * 2;
-  if (M > 0x7fffffffL || in_bytes >= ((size_t)1 << 31) ||
-      rtpose_layout_pixels(&d2->lout, N, H, W) * (size_t)d2->lout.cstride >= ((size_t)1 << 31))
+  if (M > 0x7fffffffL || in_bytes >= ((size_t)1 << 31) || !below_2g_elems(d2->lout, N, H, W))
     return fail(RTPOSE_E_INVAL, "pw_head_bf16: tensors must be below 2^31 bytes / floats (32-bit offsets)");
   Args a;
   memset(&a, 0, sizeof(a));
@@ -459,16 +458,8 @@ int pw_head_bf16_launch(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2, int 
   a.fW = make_fastdiv(W);
   const int grid = a.nitems < device_cu_count() ? a.nitems : device_cu_count();  // one block per CU
   const size_t lds = ((size_t)(a.K1 >> 3) * XP + kRed4) * 16;
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_head_bf16_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4608));  // (4592 bytes are static)
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(pw_head_bf16_kernel, dim3(grid), dim3(256), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  // (4592 bytes of the kernel's LDS are static)
+  return launch_kernel<pw_head_bf16_kernel>(dim3(grid), dim3(256), lds, 160 * 1024 - 4608, s, a);
 }
 
 }  // namespace rtpose

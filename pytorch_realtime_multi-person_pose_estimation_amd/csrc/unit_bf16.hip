@@ -31,7 +31,7 @@
 // (the order of pw_fused_bf16.hip) - fixed, independent of the batch.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_desc.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -478,17 +478,8 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
 
 template <int WM1, int WM2, int NCH2>
 static int launch_inst(const Args& a, int grid, size_t lds, hipStream_t s) {
-  static PerDeviceOnce attr_set;
-  const int dev = current_device();
-  auto kern = unit_bf16_kernel<WM1, WM2, NCH2>;
-  if (!attr_set.is_set(dev)) {
-    RTPOSE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024 - 2560));  // (2.2 KB are static)
-    attr_set.set(dev);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  // (2.2 KB of the kernel's LDS are static)
+  return launch_kernel<unit_bf16_kernel<WM1, WM2, NCH2>>(dim3(grid), dim3(512), lds, 160 * 1024 - 2560, s, a);
 }
 
 }  // namespace unitb
@@ -506,8 +497,7 @@ int unit_bf16_fits(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int H, in
   if (d2->coutp != 128 && d2->coutp != 256) return 0;
   if (d2->cout < 8 || (d2->cout % 8) || d2->cout > d2->coutp || !d2->out_cmap) return 0;
   if (!d0->relu || !d2->relu || !d0->dw_w || !d0->dw_b || d0->pt_src || d2->pt_src || d2->dw_w) return 0;
-  if ((d0->lin.cstride % 8) || (d0->lin.choff % 8) || (d2->lout.cstride % 8)) return 0;
-  if (d0->lin.ws < W + 1 || d0->lin.hs < H + 1 || d0->lin.lead < d0->lin.ws + 1) return 0;
+  if (!slice_aligned(d0->lin, 8) || (d2->lout.cstride % 8) || !gap_covers(d0->lin, H, W, 1)) return 0;
   // the next tile's x2 is staged in two rounds of two 64-channel chunks (under the write-out + depthwise conv, under GEMM 2)
   if (d0->cin > 256) return 0;
   const size_t lds = ((size_t)2 * ((d0->cin > d2->cin ? d0->cin : d2->cin) >> 3) * unitb::XP1 + (size_t)(d2->cin >> 3) * unitb::AP2) * 16 +
