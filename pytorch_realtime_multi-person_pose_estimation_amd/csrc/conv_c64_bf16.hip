@@ -33,6 +33,7 @@
 #include <cstdlib>
 
 #include "conv_desc.h"
+#include "launchers.h"
 
 namespace rtpose {
 

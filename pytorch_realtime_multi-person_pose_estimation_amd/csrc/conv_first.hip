@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv_desc.h"
+#include "launchers.h"
 
 namespace rtpose {
 

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "conv_desc.h"
+#include "launchers.h"
 
 namespace rtpose {
 

@@ -35,11 +35,9 @@
 #include <type_traits>
 
 #include "conv_desc.h"
+#include "launchers.h"
 
 namespace rtpose {
-
-int conv_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int out_f32, int split);
-int conv_c64_bf16_launch(const rtpose_conv_desc* d, int N, int H, int W, hipStream_t s);
 
 namespace bf {
 

@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "conv_desc.h"
+#include "launchers.h"
 #include "wino_common.h"
 
 namespace rtpose {
@@ -813,24 +814,7 @@ double conv2d_wino_issued_flops(int cin, int cout, int N, int H, int W) {
   return 2.0 * tiles * 32.0 * wm * 16.0 * (double)cin * cout_pad(cout);
 }
 
-// k = 7: csrc/conv_wino7.hip
-int conv2d_wino7_fits(int cin, int cout, int N, int H, int W, int hs, int fm);
-int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int fm, void* scratch,
-                        size_t scratch_bytes, hipStream_t s);
-int pack_weights_wino7_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map,
-                              int cin_packed, int fm, float* wp, float* bp, hipStream_t s);
-size_t packed_weight_floats_wino7(int cout, int cin, int fm);
-size_t conv2d_wino7_scratch_bytes(int blocks);
-int* conv2d_wino7_scratch_err(void* scratch, int blocks);
-int wino_amplification_launch(const float* w, int cout, int cin, int k, int fm, float* amp, hipStream_t s);
-// k = 3, F(4x4,3x3): csrc/conv_wino4.hip
-int conv2d_wino4_ok(int cin, int cout);
-size_t packed_weight_floats_wino4(int cout, int cin);
-int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s);
-int pack_weights_wino4_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map,
-                              int cin_packed, float* wp, float* bp, hipStream_t s);
-int wino4_amplification_launch(const float* w, int cout, int cin, float* amp, hipStream_t s);
-
+// (k = 7: csrc/conv_wino7.hip; k = 3, F(4x4,3x3): csrc/conv_wino4.hip)
 int conv2d_winograd_fits(int k, int cin, int cout, int pool, int N, int H, int W, int hs, int fm) {
   if (k == 3) return fm == 4 ? conv2d_wino4_ok(cin, cout) : conv2d_wino_ok(cin, cout, 3);
   if (k == 7) return !pool && conv2d_wino7_fits(cin, cout, N, H, W, hs, fm);

@@ -60,6 +60,7 @@
 #include <type_traits>
 
 #include "conv_desc.h"
+#include "launchers.h"
 #include "wino_common.h"
 
 namespace rtpose {

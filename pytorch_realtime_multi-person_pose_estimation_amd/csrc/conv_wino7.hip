@@ -35,11 +35,10 @@
 #include <cstdlib>
 
 #include "conv_desc.h"
+#include "launchers.h"
 #include "wino_common.h"
 
 namespace rtpose {
-
-size_t packed_weight_floats_wino7(int cout, int cin, int fm);
 
 namespace wino7 {
 

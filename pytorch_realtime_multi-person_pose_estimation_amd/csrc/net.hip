@@ -29,44 +29,7 @@
 #include <vector>
 
 #include "common.h"
-
-namespace rtpose {
-int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s);
-int conv2d_winograd_fits(int k, int cin, int cout, int pool, int N, int H, int W, int hs, int fm);
-int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s);
-int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int fm, void* scratch,
-                        size_t scratch_bytes, hipStream_t s);
-double conv2d_wino_issued_flops(int cin, int cout, int N, int H, int W);
-double conv2d_wino7_issued_flops(int cin, int cout, int N, int H, int W, int hs, int fm);
-size_t conv2d_wino7_scratch_bytes(int blocks);
-int* conv2d_wino7_scratch_err(void* scratch, int blocks);
-size_t packed_weight_floats_wino7(int cout, int cin, int fm);
-int pack_weights_wino7_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map,
-                              int cin_packed, int fm, float* wp, float* bp, hipStream_t s);
-int wino_amplification_launch(const float* w, int cout, int cin, int k, int fm, float* amp, hipStream_t s);
-int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s);
-double conv2d_wino4_issued_flops(int cin, int cout, int N, int H, int W);
-int wino7_default_fm();
-// Mconv6 + Mconv7 of a stage as one launch (conv_tail.hip)
-int conv_tail_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N, int H, int W,
-                     hipStream_t s);
-// conv1_1 (conv_first.hip)
-size_t conv_first_packed_floats();
-int conv_tail_bf16_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int N, int H, int W,
-                          int out_f32, hipStream_t s);
-int conv_first_pack_launch(const float* w_oihw, const float* bias, float* wp, hipStream_t s, int to_bf16);
-int conv_first_launch(const float* x_nchw, const float* x_lay, const rtpose_layout* lx, const float* wp, float* out,
-                      const rtpose_layout* lo, int out_plane_pixels, int relu, int N, int H, int W, hipStream_t s,
-                      int out_bf16);
-int pack_weights_launch(const float* w, const float* bias, int cout, int cin_src, int k,
-                        const int32_t* cin_map, int cin_packed, float* wp, float* bp, hipStream_t s);
-// bf16 path (conv_mfma_bf16.hip)
-int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int out_f32, int split,
-                       hipStream_t s);
-int pack_weights_bf16_launch(const float* w, const float* bias, int cout, int cin_src, int k,
-                             const int32_t* cin_map, int cin_packed, void* wp, float* bp, int split,
-                             hipStream_t s);
-}  // namespace rtpose
+#include "launchers.h"
 
 using namespace rtpose;
 
@@ -84,29 +47,49 @@ struct Buf {
   bool stale = false;
 };
 
+// The forms a conv can run in, in the order their packings follow each other in the weight arena.  Everything that
+// depends on the form is read from kForm: the code the ABI reports (rtpose_net_conv_numerics,
+// rtpose_net_launch_executed_flops), the kernel size the form applies to, the m of F(m x m,3x3) / F(m,7) as the
+// descriptor's wino_m and the launchers' fm take it, the slot of its amplification estimate in the arena's amp[4]
+// (ABI too: rtpose_net_conv_numerics hands the four out in that order) and its rank among the forms of its kernel
+// size - direct, which sums in the reference's order, is the most conservative.
+enum Form { F_DIRECT, F_W3_2X2, F_W3_4X4, F_W7_4, F_W7_6, kForms };
+struct FormInfo {
+  int code, k, fm, amp_slot, rank;
+};
+constexpr FormInfo kForm[kForms] = {
+    {0, 0, 0, -1, 0},  // direct (any kernel size)
+    {3, 3, 0, 0, 1},   // F(2x2,3x3)
+    {43, 3, 4, 3, 2},  // F(4x4,3x3)
+    {4, 7, 4, 1, 1},   // F(4,7)
+    {6, 7, 6, 2, 2},   // F(6,7)
+};
+constexpr size_t kNotPacked = ~(size_t)0;
+
 struct ConvW {
   std::string name;
   int cout = 0, cin_src = 0, cin_packed = 0, k = 0;
   bool cat_perm = false;   // input channels follow the cat([L1,L2,out1]) order
-  // fp32 plans.  The arena holds EVERY packing a plan may run the conv in (it is shared by all plans of a module,
-  // whatever their geometry and options): the direct one at w_off, and - where the form has a kernel for these
-  // channel counts - F(2x2,3x3) at w_off_w3, F(4x4,3x3) at w_off_w43, F(4,7) / F(6,7) at w_off_w4 / w_off_w6.
+  // Float offsets in the weight arena.  An fp32 arena holds EVERY packing a plan may run the conv in (it is shared by
+  // all plans of a module, whatever their geometry and options): the direct one, and every Winograd form that has a
+  // kernel for these channel counts; kNotPacked where it has none.  bf16 arenas hold the direct packing only.
+  size_t w_off[kForms] = {kNotPacked, kNotPacked, kNotPacked, kNotPacked, kNotPacked};
+  size_t b_off = 0;
   bool first = false;      // conv1_1 (3 -> 64, 3x3): its own kernel, packing at w_off_first (csrc/conv_first.hip)
   size_t w_off_first = 0;
-  bool has_w3 = false, has_w43 = false, has_w7 = false;
-  size_t w_off_w3 = 0, w_off_w43 = 0, w_off_w4 = 0, w_off_w6 = 0;
-  size_t amp_off = 0;      // 4 floats in the arena: amplification estimates in F(2x2,3x3) / F(4,7) / F(6,7) / F(4x4,3x3) (0 = n/a)
+  size_t amp_off = 0;      // 4 floats in the arena: the amplification estimate of each Winograd form at its amp_slot (0 = n/a)
   float amp[4] = {0.f, 0.f, 0.f, 0.f};  // host copy (rtpose_net_finalize_weights)
-  int form = 0;            // what THIS plan runs the conv in: 0 direct, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 = F(4,7), 6 = F(6,7)
+  Form form = F_DIRECT;    // what THIS plan runs the conv in
   int H = 0, W = 0;        // map size the conv runs at in this plan
-  size_t w_off = 0, b_off = 0;  // float offsets in the weight arena
   // OpenPose_Model: nn.PReLU after the conv (slopes at pr_off, cout_pad floats; state_dict prefix prelu_name)
   bool has_prelu = false;
   size_t pr_off = 0;
   std::string prelu_name;
+  bool packed(Form f) const { return w_off[f] != kNotPacked; }
 };
 
-enum OpKind { OP_INPUT, OP_CONV, OP_POOL, OP_COPY, OP_TAIL };
+// OP_SAVE: the copy of a stage's maps into its record, run only under keep_intermediates
+enum OpKind { OP_INPUT, OP_CONV, OP_POOL, OP_COPY, OP_SAVE, OP_TAIL };
 
 struct Op {
   OpKind kind;
@@ -161,13 +144,15 @@ struct rtpose_net {
   int cat_buf[2] = {-1, -1};
   // topology: 0 = rtpose_vgg, 1 = OpenPose_Model (rtpose_openpose_create).  OpenPose plans keep their stage outputs in
   // cat_buf[0] = the stage input buffer [features 128 | PAF | pad to 16 | heat | pad to 16] (heat at op_heat_off) and
-  // copy each stage's output to op_save[stage] when keep_intermediates is set; the packed-input map of the l1 stages
-  // 1.. (cat([features, heat, paf]) order) is catmap_host, uploaded at bind.
+  // copy each stage's output to op_save[stage] when keep_intermediates is set.  catmap_host, uploaded at bind: packed
+  // input channel -> source channel of the filters that read a concat buffer (rtpose_vgg: cat([L1, L2, out1]);
+  // OpenPose_Model: cat([features, heat, paf]) of the l1 stages 1..), -1 = zero taps.
   int topo = 0;
   int op_l2 = 0, op_l1 = 0, op_paf = 0, op_heat = 0, op_heat_off = 0;
   std::vector<int> op_save;
   std::vector<int32_t> catmap_host;
   int x0_buf = -1;
+  int conv1_op = -1;             // the launch that runs conv1_1 in its own kernel (-1: the split plan has none)
   // hipGraph replay of the launch list (ops after the input conversion have fixed arguments):
   // captured once per keep_intermediates setting on a private non-blocking stream that is
   // joined to the caller's stream by events, so it also works under the legacy NULL stream
@@ -244,32 +229,29 @@ int add_conv_w(rtpose_net* n, const std::string& name, int cout, int cin, int k,
     n->wt_floats += round_up(floats, 64);
     return off;
   };
+  // conv1_1 has its own kernel in fp32 and bf16 plans (conv_first.hip; bf16: MODE 2 reads the fp32 image, rounds it and the
+  // filters to bf16, writes bf16; not the split plans) - the generic packing stays in the arena for rtpose_net_conv introspection
+  c.first = !n->split && k == 3 && cin == 3 && cout == 64;
   if (n->bf16) {
-    c.w_off = take(n->split ? rtpose_packed_weight_bytes_bf16x3(cout, c.cin_packed, k) / 4
-                            : rtpose_packed_weight_bytes_bf16(cout, c.cin_packed, k) / 4);
-    // bf16 plans (not the split ones): conv1_1 has its own kernel too (conv_first.hip MODE 2: reads the fp32 image, rounds it
-    // and the filters to bf16, writes bf16) - the generic packing above stays in the arena for rtpose_net_conv introspection
-    c.first = !n->split && k == 3 && cin == 3 && cout == 64;
-    if (c.first) c.w_off_first = take(conv_first_packed_floats());
+    c.w_off[F_DIRECT] = take(n->split ? rtpose_packed_weight_bytes_bf16x3(cout, c.cin_packed, k) / 4
+                                      : rtpose_packed_weight_bytes_bf16(cout, c.cin_packed, k) / 4);
   } else {
     // The weight arena is shared by every plan of a module (any N x H x W, any rtpose_net_options), so its layout
     // depends on the channel counts only: the direct packing, plus every Winograd packing that has a kernel.
     // (3x3 with < 32 input channels stays direct: nothing to amortise the transforms over - conv1_1, 3 -> 64 on 8
     //  padded channels, takes 0.71 ms in Winograd form and 0.50 ms in the direct kernel)
-    c.w_off = take(rtpose_packed_weight_floats(cout, c.cin_packed, k));
-    c.has_w3 = k == 3 && c.cin_packed >= 32 && conv2d_winograd_fits(3, c.cin_packed, cout, 0, 1, 8, 8, 9, 0);
-    c.has_w7 = k == 7 && c.cin_packed % 8 == 0 && cout_pad(cout) % 128 == 0;
-    c.has_w43 = c.has_w3 && conv2d_winograd_fits(3, c.cin_packed, cout, 0, 1, 8, 8, 9, 4);
-    if (c.has_w3) c.w_off_w3 = take(rtpose_packed_weight_floats_winograd(cout, c.cin_packed, 3));
-    if (c.has_w43) c.w_off_w43 = take(rtpose_packed_weight_floats_winograd3(cout, c.cin_packed, 4));
-    if (c.has_w7) {
-      c.w_off_w4 = take(packed_weight_floats_wino7(cout, c.cin_packed, 4));
-      c.w_off_w6 = take(packed_weight_floats_wino7(cout, c.cin_packed, 6));
+    c.w_off[F_DIRECT] = take(rtpose_packed_weight_floats(cout, c.cin_packed, k));
+    const bool w3 = k == 3 && c.cin_packed >= 32 && conv2d_winograd_fits(3, c.cin_packed, cout, 0, 1, 8, 8, 9, 0);
+    const bool w7 = k == 7 && c.cin_packed % 8 == 0 && cout_pad(cout) % 128 == 0;
+    for (int f = F_DIRECT + 1; f < kForms; ++f) {
+      const int fm = kForm[f].fm;
+      if (kForm[f].k == 3 && w3 && (f == F_W3_2X2 || conv2d_winograd_fits(3, c.cin_packed, cout, 0, 1, 8, 8, 9, fm)))
+        c.w_off[f] = take(rtpose_packed_weight_floats_winograd3(cout, c.cin_packed, fm));
+      if (kForm[f].k == 7 && w7) c.w_off[f] = take(packed_weight_floats_wino7(cout, c.cin_packed, fm));
     }
     c.amp_off = take(4);
-    c.first = k == 3 && cin == 3 && cout == 64;
-    if (c.first) c.w_off_first = take(conv_first_packed_floats());
   }
+  if (c.first) c.w_off_first = take(conv_first_packed_floats());
   c.b_off = take(rtpose_packed_bias_floats(cout));
   n->convs.push_back(c);
   return (int)n->convs.size() - 1;
@@ -279,24 +261,25 @@ int add_conv_w(rtpose_net* n, const std::string& name, int cout, int cin, int k,
 // an image's maps would depend on the batch it is evaluated in.  Small grids get the frequency-split launch of the
 // same arithmetic instead, conv_wino7.hip: wino7s_f32.)  A form without a kernel instance at the plan's geometry -
 // F(m,7) on maps so wide that the transformed rows of a block do not fit the LDS - falls back to the next one.
-int pick_form(const rtpose_net* n, const ConvW& c) {
-  if (n->bf16) return 0;
+Form pick_form(const rtpose_net* n, const ConvW& c) {
+  if (n->bf16) return F_DIRECT;
+  auto tame = [&](Form f) { return c.amp[kForm[f].amp_slot] <= n->amp_limit; };
   if (c.k == 3) {
-    if (!c.has_w3 || !n->w3) return 0;
-    if (c.has_w43 && (n->w3 == 4 || (n->w3 == RTPOSE_WINO3_AUTO && c.amp[3] <= n->amp_limit))) return 43;
-    return 3;
+    if (!c.packed(F_W3_2X2) || !n->w3) return F_DIRECT;
+    if (c.packed(F_W3_4X4) && (n->w3 == 4 || (n->w3 == RTPOSE_WINO3_AUTO && tame(F_W3_4X4)))) return F_W3_4X4;
+    return F_W3_2X2;
   }
-  if (c.k != 7 || !c.has_w7 || !n->w7) return 0;
-  auto fits = [&](int fm) {
-    return conv2d_winograd_fits(7, c.cin_packed, c.cout, 0, n->N, c.H, c.W, c.H + 3, fm) != 0;
+  if (c.k != 7 || !c.packed(F_W7_4) || !n->w7) return F_DIRECT;
+  auto fits = [&](Form f) {
+    return conv2d_winograd_fits(7, c.cin_packed, c.cout, 0, n->N, c.H, c.W, c.H + 3, kForm[f].fm) != 0;
   };
   if (n->w7 == RTPOSE_WINO7_AUTO) {
-    if (c.amp[2] <= n->amp_limit && fits(6)) return 6;
-    if (c.amp[1] <= n->amp_limit && fits(4)) return 4;
-    return 0;
+    if (tame(F_W7_6) && fits(F_W7_6)) return F_W7_6;
+    if (tame(F_W7_4) && fits(F_W7_4)) return F_W7_4;
+    return F_DIRECT;
   }
-  if (n->w7 == 6 && fits(6)) return 6;
-  return fits(4) ? 4 : 0;
+  if (n->w7 == 6 && fits(F_W7_6)) return F_W7_6;
+  return fits(F_W7_4) ? F_W7_4 : F_DIRECT;
 }
 
 bool forms_need_amps(const rtpose_net* n) {
@@ -320,15 +303,14 @@ void pick_forms(rtpose_net* n) {
   for (Op& o : n->ops) {
     if (o.kind != OP_CONV || o.ngroups < 2) continue;
     ConvW &a = n->convs[o.conv_idx[0]], &b = n->convs[o.conv_idx[1]];
-    const int f = a.form < b.form ? a.form : b.form;  // 3x3: 0 < 3 < 43, 7x7: 0 < 4 < 6: direct is the lowest
-    a.form = b.form = f;
+    a.form = b.form = kForm[a.form].rank < kForm[b.form].rank ? a.form : b.form;
   }
 }
 
 // Channel-plane storage (conv_wino4.hip) for every buffer that only F(4x4,3x3) launches - and conv1_1 - touch: written by
-// ONE conv (conv1_1's own kernel or a conv in form 43; a branch of a grouped launch counts) as a whole, read only by convs in
-// form 43 as a whole.  Depends on the
-// forms, so it is re-derived whenever they are; a buffer that changes storage is cleared before the next forward.
+// ONE conv (conv1_1's own kernel or a conv in that form; a branch of a grouped launch counts) as a whole, read only by convs
+// in that form as a whole.  Depends on the forms, so it is re-derived whenever they are; a buffer that changes storage is
+// cleared before the next forward.
 void mark_plane_bufs(rtpose_net* n) {
   const int nb = (int)n->bufs.size();
   std::vector<int> writers(nb, 0), readers(nb, 0);
@@ -340,11 +322,11 @@ void mark_plane_bufs(rtpose_net* n) {
       const ConvW* c = conv ? &n->convs[o.conv_idx[g]] : nullptr;
       if (bi >= 0) {
         ++readers[bi];
-        if (!(conv && c->form == 43 && o.in_choff[g] == 0 && c->cin_packed == n->bufs[bi].C)) ok[bi] = 0;
+        if (!(conv && c->form == F_W3_4X4 && o.in_choff[g] == 0 && c->cin_packed == n->bufs[bi].C)) ok[bi] = 0;
       }
       if (bo >= 0) {
         ++writers[bo];
-        if (!(conv && (c->form == 43 || c->first) && o.out_choff[g] == 0 && c->cout == n->bufs[bo].C))
+        if (!(conv && (c->form == F_W3_4X4 || c->first) && o.out_choff[g] == 0 && c->cout == n->bufs[bo].C))
           ok[bo] = 0;
       }
     }
@@ -385,6 +367,31 @@ void add_conv_op(rtpose_net* n, int H, int W, int ngroups, const int* conv_idx, 
   }
   o.flops = fl;
   o.ks = n->convs[conv_idx[0]].k;
+  if (n->convs[conv_idx[0]].first) n->conv1_op = (int)n->ops.size();
+  n->ops.push_back(o);
+}
+
+// The trailing 1x1 pair of a stage, c1 (ReLU) -> c2 (linear), of both branches as ONE back-to-back launch (conv_tail.hip /
+// conv_tail_bf16.hip): the intermediate never leaves the CU
+void add_tail_op(rtpose_net* n, int H, int W, const int* c1, const int* c2, const int* in_buf, const int* out_buf,
+                 const int* out_choff, int out_f32) {
+  Op o;
+  o.kind = OP_TAIL;
+  o.H = H;
+  o.W = W;
+  o.ngroups = 2;
+  o.out_f32 = out_f32;
+  o.ks = 1;
+  for (int b = 0; b < 2; ++b) {
+    o.conv_idx[b] = c1[b];
+    o.conv2_idx[b] = c2[b];
+    o.in_buf[b] = in_buf[b];
+    o.out_buf[b] = out_buf[b];
+    o.out_choff[b] = out_choff[b];
+    const ConvW &w1 = n->convs[c1[b]], &w2 = n->convs[c2[b]];
+    o.flops += 2.0 * n->N * H * W * ((double)w1.cout * w1.cin_src + (double)w2.cout * w2.cin_src);
+    o.name += (b ? "|" : "") + w1.name + "+" + w2.name;
+  }
   n->ops.push_back(o);
 }
 
@@ -408,7 +415,7 @@ void plan_vgg_conv(rtpose_net* n, int conv, int H, int W, int in_buf, int out_bu
                    int out_buf_pooled) {
   const int zero = 0;
   if (out_buf_pooled < 0) {
-    // (OpenPose_Model: conv4_2 and conv4_3_CPM end in a PReLU instead of the ReLU; never in front of a pool)
+    // (OpenPose_Model: conv4_2 .. conv4_4_CPM end in a PReLU instead of the ReLU; never in front of a pool)
     add_conv_op(n, H, W, 1, &conv, &in_buf, &zero, &out_buf_same, &zero, n->convs[conv].has_prelu ? 0 : 1, 0);
   } else if (!((H | W) & 1)) {
     add_conv_op(n, H, W, 1, &conv, &in_buf, &zero, &out_buf_pooled, &zero, 1, 1);
@@ -419,52 +426,43 @@ void plan_vgg_conv(rtpose_net* n, int conv, int H, int W, int in_buf, int out_bu
   }
 }
 
-void build_plan(rtpose_net* n) {
-  const int N = n->N;
-  (void)N;
+// the nn.PReLU that follows conv `conv`: slopes in the arena, padded like the bias
+void add_prelu(rtpose_net* n, int conv, const std::string& name) {
+  ConvW& c = n->convs[conv];
+  c.has_prelu = true;
+  c.prelu_name = name;
+  c.pr_off = n->wt_floats;
+  n->wt_floats += round_up(rtpose_packed_bias_floats(c.cout), 64);
+}
+
+// The trunk both topologies start with: VGG19's first 10 convs + 2 CPM convs (rtpose_vgg.py:69-83, openpose.py:28-44) as
+// convs `prefix`0 .. `prefix`25 in state_dict order, the input and trunk buffers, the input conversion and the launches of
+// convs 0..10.  Sets H3 / W3.  The last conv, cw[11] (conv4_4_CPM), reads D3; what it writes is the caller's.
+// `prelu_tail` (openpose.py:40-44): the last three convs end in an nn.PReLU, named by the index after the conv's.
+struct Trunk {
+  int cw[12];
+  int D3;
+};
+
+Trunk add_trunk(rtpose_net* n, const std::string& prefix, bool prelu_tail) {
   const int H0 = n->H, W0 = n->W;
   const int H1 = H0 / 2, W1 = W0 / 2, H2 = H1 / 2, W2 = W1 / 2, H3 = H2 / 2, W3 = W2 / 2;
   n->H3 = H3;
   n->W3 = W3;
-
-  // ---- weights, in the reference's state_dict order (rtpose_vgg.py:141-155) ----
-  // model0: VGG19 first 10 convs + 2 CPM convs (rtpose_vgg.py:69-83)
   const int vgg_idx[12] = {0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25};
   const int vgg_cin[12] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 256};
   const int vgg_cout[12] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 256, 128};
-  int cw0[12];
-  for (int i = 0; i < 12; ++i)
-    cw0[i] = add_conv_w(n, "model0." + std::to_string(vgg_idx[i]), vgg_cout[i], vgg_cin[i], 3, false);
-  // stages: branch 1 (PAF, 38) for stages 1..6, then branch 2 (heat, 19)
-  int cw1[2][5], cws[2][5][7];
-  for (int b = 0; b < 2; ++b) {
-    const int last = b == 0 ? 38 : 19;
-    const std::string sfx = "_" + std::to_string(b + 1) + ".";
-    // stage 1 (rtpose_vgg.py:95-105)
-    for (int i = 0; i < 5; ++i) {
-      const int cin = i < 4 ? 128 : 512;
-      const int cout = i < 3 ? 128 : (i == 3 ? 512 : last);
-      const int k = i < 3 ? 3 : 1;
-      cw1[b][i] = add_conv_w(n, "model1" + sfx + std::to_string(2 * i), cout, cin, k, false);
-    }
-    // stages 2..6 (rtpose_vgg.py:108-127)
-    for (int s = 2; s <= 6; ++s)
-      for (int i = 0; i < 7; ++i) {
-        const int cin = i == 0 ? 185 : 128;
-        const int cout = i < 6 ? 128 : last;
-        const int k = i < 5 ? 7 : 1;
-        cws[b][s - 2][i] = add_conv_w(n, "model" + std::to_string(s) + sfx + std::to_string(2 * i),
-                                      cout, cin, k, i == 0, H3, W3);
-      }
+  Trunk t;
+  for (int i = 0; i < 12; ++i) {
+    t.cw[i] = add_conv_w(n, prefix + std::to_string(vgg_idx[i]), vgg_cout[i], vgg_cin[i], 3, false);
+    if (prelu_tail && i >= 9) add_prelu(n, t.cw[i], prefix + std::to_string(vgg_idx[i] + 1));
   }
-  n->catmap_off = n->wt_floats;
-  n->wt_floats += 256;  // int32[192]
 
-  // ---- activation buffers ------------------------------------------------------
   const int X0 = add_buf(n, n->bf16 ? 16 : 8, 1, H0, W0);
   n->x0_buf = X0;
   if (n->bf16) n->x0f_buf = add_buf(n, 8, 1, H0, W0, true);
   const int A1 = add_buf(n, 64, 1, H0, W0);
+  // (A2 / B2 / C4: the un-pooled map of a conv whose pool cannot be fused, odd height or width)
   const bool even0 = !((H0 | W0) & 1), even1 = !((H1 | W1) & 1), even2 = !((H2 | W2) & 1);
   const int A2 = even0 ? -1 : add_buf(n, 64, 0, H0, W0);
   const int B0 = add_buf(n, 64, 1, H1, W1);
@@ -478,12 +476,63 @@ void build_plan(rtpose_net* n) {
   const int D0 = add_buf(n, 256, 1, H3, W3);
   const int D1 = add_buf(n, 512, 1, H3, W3);
   const int D2 = add_buf(n, 512, 1, H3, W3);
-  const int D3 = add_buf(n, 256, 1, H3, W3);
+  t.D3 = add_buf(n, 256, 1, H3, W3);
+
+  add_simple_op(n, OP_INPUT, "nchw_to_nhwc8", H0, W0, -1, 0, X0, 0, 3);
+  plan_vgg_conv(n, t.cw[0], H0, W0, X0, A1, -1);
+  plan_vgg_conv(n, t.cw[1], H0, W0, A1, A2, B0);
+  plan_vgg_conv(n, t.cw[2], H1, W1, B0, B1, -1);
+  plan_vgg_conv(n, t.cw[3], H1, W1, B1, B2, C0);
+  plan_vgg_conv(n, t.cw[4], H2, W2, C0, C1, -1);
+  plan_vgg_conv(n, t.cw[5], H2, W2, C1, C2, -1);
+  plan_vgg_conv(n, t.cw[6], H2, W2, C2, C3, -1);
+  plan_vgg_conv(n, t.cw[7], H2, W2, C3, C4, D0);
+  plan_vgg_conv(n, t.cw[8], H3, W3, D0, D1, -1);
+  plan_vgg_conv(n, t.cw[9], H3, W3, D1, D2, -1);
+  plan_vgg_conv(n, t.cw[10], H3, W3, D2, t.D3, -1);
+  return t;
+}
+
+// rtpose_vgg.  Weights in the reference's state_dict order (rtpose_vgg.py:141-155); the order of the add_conv_w / add_buf /
+// add_*_op calls IS the layout of the weight arena and of the workspace and the launch list.
+void build_plan(rtpose_net* n) {
+  const Trunk tr = add_trunk(n, "model0.", false);
+  const int H3 = n->H3, W3 = n->W3;
+
+  // ---- stage weights: branch 1 (PAF, 38) for stages 1..6, then branch 2 (heat, 19); [layer][branch] ----
+  int cw1[5][2], cws[5][7][2];
+  for (int b = 0; b < 2; ++b) {
+    const int last = b == 0 ? 38 : 19;
+    const std::string sfx = "_" + std::to_string(b + 1) + ".";
+    // stage 1 (rtpose_vgg.py:95-105)
+    for (int i = 0; i < 5; ++i) {
+      const int cin = i < 4 ? 128 : 512;
+      const int cout = i < 3 ? 128 : (i == 3 ? 512 : last);
+      const int k = i < 3 ? 3 : 1;
+      cw1[i][b] = add_conv_w(n, "model1" + sfx + std::to_string(2 * i), cout, cin, k, false);
+    }
+    // stages 2..6 (rtpose_vgg.py:108-127)
+    for (int s = 2; s <= 6; ++s)
+      for (int i = 0; i < 7; ++i) {
+        const int cin = i == 0 ? 185 : 128;
+        const int cout = i < 6 ? 128 : last;
+        const int k = i < 5 ? 7 : 1;
+        cws[s - 2][i][b] = add_conv_w(n, "model" + std::to_string(s) + sfx + std::to_string(2 * i),
+                                      cout, cin, k, i == 0, H3, W3);
+      }
+  }
+  n->catmap_off = n->wt_floats;
+  n->wt_floats += 256;  // int32[192]
+  n->catmap_host.assign(kCatC, -1);  // channel map of the concat input: packed c -> source channel of cat([L1,L2,out1])
+  for (int c = 0; c < 185; ++c)
+    n->catmap_host[c] = c < 128 ? 57 + c : c < kCatHeat ? c - kCatPaf : 38 + (c - kCatHeat);
+
+  // ---- activation buffers ------------------------------------------------------
   const int CATa = add_buf(n, kCatC, 3, H3, W3);
   const int CATb = add_buf(n, kCatC, 3, H3, W3);
   n->cat_buf[0] = CATa;
   n->cat_buf[1] = CATb;
-  int T1[2], T2[2], T3[2], T4[2], U[2][6];
+  int T1[2], T2[2], T3[2], T4[2], U[6][2];
   for (int b = 0; b < 2; ++b) {
     T1[b] = add_buf(n, 128, 1, H3, W3);
     T2[b] = add_buf(n, 128, 1, H3, W3);
@@ -491,9 +540,9 @@ void build_plan(rtpose_net* n) {
     // (fp32 and bf16 plans run the trailing 1x1 pairs back to back, conv_tail.hip / conv_tail_bf16.hip: their intermediates
     //  never reach HBM; the split plan keeps them)
     T4[b] = n->split ? add_buf(n, 512, 0, H3, W3) : -1;
-    for (int i = 0; i < 4; ++i) U[b][i] = add_buf(n, 128, 3, H3, W3);
-    U[b][4] = add_buf(n, 128, 0, H3, W3);
-    U[b][5] = n->split ? add_buf(n, 128, 0, H3, W3) : -1;
+    for (int i = 0; i < 4; ++i) U[i][b] = add_buf(n, 128, 3, H3, W3);
+    U[4][b] = add_buf(n, 128, 0, H3, W3);
+    U[5][b] = n->split ? add_buf(n, 128, 0, H3, W3) : -1;
   }
   for (int s = 0; s < 6; ++s) n->save_buf[s] = add_buf(n, 57, 0, H3, W3, true);  // always fp32
   if (!n->bf16) {
@@ -506,123 +555,50 @@ void build_plan(rtpose_net* n) {
   }
 
   // ---- launches ------------------------------------------------------------------
-  add_simple_op(n, OP_INPUT, "nchw_to_nhwc8", H0, W0, -1, 0, X0, 0, 3);
-  plan_vgg_conv(n, cw0[0], H0, W0, X0, A1, -1);
-  plan_vgg_conv(n, cw0[1], H0, W0, A1, A2, B0);
-  plan_vgg_conv(n, cw0[2], H1, W1, B0, B1, -1);
-  plan_vgg_conv(n, cw0[3], H1, W1, B1, B2, C0);
-  plan_vgg_conv(n, cw0[4], H2, W2, C0, C1, -1);
-  plan_vgg_conv(n, cw0[5], H2, W2, C1, C2, -1);
-  plan_vgg_conv(n, cw0[6], H2, W2, C2, C3, -1);
-  plan_vgg_conv(n, cw0[7], H2, W2, C3, C4, D0);
-  plan_vgg_conv(n, cw0[8], H3, W3, D0, D1, -1);
-  plan_vgg_conv(n, cw0[9], H3, W3, D1, D2, -1);
-  plan_vgg_conv(n, cw0[10], H3, W3, D2, D3, -1);
-  {  // conv4_4_CPM -> out1, written once into each concat buffer
-    const int zero = 0;
-    add_conv_op(n, H3, W3, 1, &cw0[11], &D3, &zero, &CATa, &zero, 1, 0);
-    add_simple_op(n, OP_COPY, "out1->cat_b", H3, W3, CATa, 0, CATb, 0, 128);
-  }
+  // conv4_4_CPM -> out1, written once into each concat buffer
+  plan_vgg_conv(n, tr.cw[11], H3, W3, tr.D3, CATa, -1);
+  add_simple_op(n, OP_COPY, "out1->cat_b", H3, W3, CATa, 0, CATb, 0, 128);
   const int zz[2] = {0, 0};
   const int head_off[2] = {kCatPaf, kCatHeat};
   {  // stage 1: reads out1 = CATa[0:128]; heads write CATb
-    const int in0[2] = {CATa, CATa};
-    int ci[2];
-    ci[0] = cw1[0][0]; ci[1] = cw1[1][0];
-    add_conv_op(n, H3, W3, 2, ci, in0, zz, T1, zz, 1, 0);
-    ci[0] = cw1[0][1]; ci[1] = cw1[1][1];
-    add_conv_op(n, H3, W3, 2, ci, T1, zz, T2, zz, 1, 0);
-    ci[0] = cw1[0][2]; ci[1] = cw1[1][2];
-    add_conv_op(n, H3, W3, 2, ci, T2, zz, T3, zz, 1, 0);
-    const int outb[2] = {CATb, CATb};
+    const int in0[2] = {CATa, CATa}, outb[2] = {CATb, CATb};
+    add_conv_op(n, H3, W3, 2, cw1[0], in0, zz, T1, zz, 1, 0);
+    add_conv_op(n, H3, W3, 2, cw1[1], T1, zz, T2, zz, 1, 0);
+    add_conv_op(n, H3, W3, 2, cw1[2], T2, zz, T3, zz, 1, 0);
     if (!n->split) {
-      // fp32 and bf16: conv5_4_CPM (128 -> 512, ReLU) + conv5_5_CPM (512 -> 38 | 19) as one back-to-back launch
-      // (conv_tail.hip / conv_tail_bf16.hip); the split (bf16x3) plan keeps two launches of its generic kernel
-      ci[0] = cw1[0][4]; ci[1] = cw1[1][4];
-      add_conv_op(n, H3, W3, 2, ci, T3, zz, outb, head_off, 0, 0);
-      Op& t = n->ops.back();
-      t.kind = OP_TAIL;
-      t.ks = 1;
-      for (int b = 0; b < 2; ++b) {
-        t.conv2_idx[b] = t.conv_idx[b];
-        t.conv_idx[b] = cw1[b][3];
-        const ConvW& c1 = n->convs[t.conv_idx[b]];
-        t.flops += 2.0 * n->N * H3 * W3 * (double)c1.cout * c1.cin_src;
-      }
-      t.name = n->convs[t.conv_idx[0]].name + "+" + n->convs[t.conv2_idx[0]].name + "|" +
-               n->convs[t.conv_idx[1]].name + "+" + n->convs[t.conv2_idx[1]].name;
+      // fp32 and bf16: conv5_4_CPM (128 -> 512, ReLU) + conv5_5_CPM (512 -> 38 | 19) as one back-to-back launch;
+      // the split (bf16x3) plan keeps two launches of its generic kernel
+      add_tail_op(n, H3, W3, cw1[3], cw1[4], T3, outb, head_off, 0);
     } else {
-      ci[0] = cw1[0][3]; ci[1] = cw1[1][3];
-      add_conv_op(n, H3, W3, 2, ci, T3, zz, T4, zz, 1, 0);
-      ci[0] = cw1[0][4]; ci[1] = cw1[1][4];
-      add_conv_op(n, H3, W3, 2, ci, T4, zz, outb, head_off, 0, 0);
+      add_conv_op(n, H3, W3, 2, cw1[3], T3, zz, T4, zz, 1, 0);
+      add_conv_op(n, H3, W3, 2, cw1[4], T4, zz, outb, head_off, 0, 0);
     }
-    add_simple_op(n, OP_COPY, "save1", H3, W3, CATb, kCatPaf, n->save_buf[0], 0, 57);
+    add_simple_op(n, OP_SAVE, "save1", H3, W3, CATb, kCatPaf, n->save_buf[0], 0, 57);
   }
   for (int s = 2; s <= 6; ++s) {
+    const int(*cw)[2] = cws[s - 2];
     const int cin_buf = (s % 2 == 0) ? CATb : CATa;
     const int cout_buf = (s % 2 == 0) ? CATa : CATb;
     const int in0[2] = {cin_buf, cin_buf};
-    int ci[2];
-    int u0[2] = {U[0][0], U[1][0]};
-    ci[0] = cws[0][s - 2][0]; ci[1] = cws[1][s - 2][0];
-    add_conv_op(n, H3, W3, 2, ci, in0, zz, u0, zz, 1, 0);
-    for (int i = 1; i < (n->split ? 6 : 5); ++i) {
-      const int ui[2] = {U[0][i - 1], U[1][i - 1]};
-      const int uo[2] = {U[0][i], U[1][i]};
-      ci[0] = cws[0][s - 2][i]; ci[1] = cws[1][s - 2][i];
-      add_conv_op(n, H3, W3, 2, ci, ui, zz, uo, zz, 1, 0);
-    }
+    add_conv_op(n, H3, W3, 2, cw[0], in0, zz, U[0], zz, 1, 0);
+    for (int i = 1; i < (n->split ? 6 : 5); ++i) add_conv_op(n, H3, W3, 2, cw[i], U[i - 1], zz, U[i], zz, 1, 0);
+    // The decoder and the TTA merge read fp32: the last heads of a bf16 plan write the fp32 stage-6 record (no bf16
+    // concat slice, no save copy).
+    const bool last_bf16 = n->bf16 && s == 6;
+    const int dst = last_bf16 ? n->save_buf[5] : cout_buf;
+    const int outb[2] = {dst, dst};
+    const int off57[2] = {0, 38};
+    const int* out_off = last_bf16 ? off57 : head_off;
     if (!n->split) {
       // fp32 and bf16: Mconv6 (128 -> 128, ReLU) + Mconv7 (128 -> 38 | 19) of both branches as ONE back-to-back launch
-      // (conv_tail.hip / conv_tail_bf16.hip): the 128-channel intermediate never leaves the CU.  The bf16 plan's last
-      // stage writes the fp32 record the decoder and the TTA merge read (no bf16 concat slice, no save copy).
-      const bool last_bf16 = n->bf16 && s == 6;
-      const int ui4[2] = {U[0][4], U[1][4]};
-      const int outb[2] = {last_bf16 ? n->save_buf[5] : cout_buf, last_bf16 ? n->save_buf[5] : cout_buf};
-      const int off57[2] = {0, 38};
-      ci[0] = cws[0][s - 2][6]; ci[1] = cws[1][s - 2][6];
-      add_conv_op(n, H3, W3, 2, ci, ui4, zz, outb, last_bf16 ? off57 : head_off, 0, 0);
-      Op& t = n->ops.back();
-      t.out_f32 = last_bf16 ? 1 : 0;
-      t.kind = OP_TAIL;
-      t.ks = 1;
-      for (int b = 0; b < 2; ++b) {
-        t.conv2_idx[b] = t.conv_idx[b];
-        t.conv_idx[b] = cws[b][s - 2][5];
-        const ConvW& c1 = n->convs[t.conv_idx[b]];
-        t.flops += 2.0 * n->N * H3 * W3 * (double)c1.cout * c1.cin_src;
-      }
-      t.name = n->convs[t.conv_idx[0]].name + "+" + n->convs[t.conv2_idx[0]].name + "|" +
-               n->convs[t.conv_idx[1]].name + "+" + n->convs[t.conv2_idx[1]].name;
-      if (!last_bf16)
-        add_simple_op(n, OP_COPY, "save" + std::to_string(s), H3, W3, cout_buf, kCatPaf, n->save_buf[s - 1], 0, 57);
-      continue;
+      add_tail_op(n, H3, W3, cw[5], cw[6], U[4], outb, out_off, last_bf16);
+    } else {
+      add_conv_op(n, H3, W3, 2, cw[6], U[5], zz, outb, out_off, 0, 0);
+      n->ops.back().out_f32 = last_bf16;
     }
-    const int ui[2] = {U[0][5], U[1][5]};
-    ci[0] = cws[0][s - 2][6]; ci[1] = cws[1][s - 2][6];
-    if (n->bf16 && s == 6) {
-      // the decoder and the TTA merge read fp32: the last heads skip the bf16 concat buffer
-      const int outb[2] = {n->save_buf[5], n->save_buf[5]};
-      const int off57[2] = {0, 38};
-      add_conv_op(n, H3, W3, 2, ci, ui, zz, outb, off57, 0, 0);
-      n->ops.back().out_f32 = 1;
-      continue;
-    }
-    const int outb[2] = {cout_buf, cout_buf};
-    add_conv_op(n, H3, W3, 2, ci, ui, zz, outb, head_off, 0, 0);
-    add_simple_op(n, OP_COPY, "save" + std::to_string(s), H3, W3, cout_buf, kCatPaf,
-                  n->save_buf[s - 1], 0, 57);
+    if (!last_bf16)
+      add_simple_op(n, OP_SAVE, "save" + std::to_string(s), H3, W3, cout_buf, kCatPaf, n->save_buf[s - 1], 0, 57);
   }
-}
-
-// the nn.PReLU that follows conv `conv`: slopes in the arena, padded like the bias
-void add_prelu(rtpose_net* n, int conv, const std::string& name) {
-  ConvW& c = n->convs[conv];
-  c.has_prelu = true;
-  c.prelu_name = name;
-  c.pr_off = n->wt_floats;
-  n->wt_floats += round_up(rtpose_packed_bias_floats(c.cout), 64);
 }
 
 // OpenPose_Model (openpose.py:114-177).  Stage input buffer IN = [features 0..127 | PAF 128.. | pad | heat R.. | pad], R =
@@ -635,24 +611,14 @@ void add_prelu(rtpose_net* n, int conv, const std::string& name) {
 // per inner width ping-pong between blocks.  The head (Mconv6 1x1 + PReLU into HEAD, Mconv7 1x1 linear) writes the stage's
 // output into its IN slice, from where the next stage reads it.
 void build_plan_openpose(rtpose_net* n) {
-  const int H0 = n->H, W0 = n->W;
-  const int H1 = H0 / 2, W1 = W0 / 2, H2 = H1 / 2, W2 = W1 / 2, H3 = H2 / 2, W3 = W2 / 2;
-  n->H3 = H3;
-  n->W3 = W3;
   const int P = n->op_paf, Hc = n->op_heat;
   const int R = (128 + P + 15) / 16 * 16;
   const int S = (R + Hc + 15) / 16 * 16;
   n->op_heat_off = R;
 
   // ---- weights, in the reference's state_dict order ----
-  const int vgg_idx[12] = {0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25};
-  const int vgg_cin[12] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 256};
-  const int vgg_cout[12] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 256, 128};
-  int cw0[12];
-  for (int i = 0; i < 12; ++i) {
-    cw0[i] = add_conv_w(n, "feature_extractor." + std::to_string(vgg_idx[i]), vgg_cout[i], vgg_cin[i], 3, false);
-    if (i >= 9) add_prelu(n, cw0[i], "feature_extractor." + std::to_string(vgg_idx[i] + 1));  // openpose.py:40-44
-  }
+  const Trunk tr = add_trunk(n, "feature_extractor.", true);
+  const int H3 = n->H3, W3 = n->W3;
   struct StageW {
     int br, inner, cw[5][3], m6, m7;
   };
@@ -688,24 +654,7 @@ void build_plan_openpose(rtpose_net* n) {
     else if (c >= R && c < R + Hc) n->catmap_host[c] = 128 + (c - R);
   }
 
-  // ---- activation buffers: the trunk's as in build_plan, then IN, the dense-block pairs, HEAD and the stage records ----
-  const int X0 = add_buf(n, 8, 1, H0, W0);
-  n->x0_buf = X0;
-  const int A1 = add_buf(n, 64, 1, H0, W0);
-  const bool even0 = !((H0 | W0) & 1), even1 = !((H1 | W1) & 1), even2 = !((H2 | W2) & 1);
-  const int A2 = even0 ? -1 : add_buf(n, 64, 0, H0, W0);
-  const int B0 = add_buf(n, 64, 1, H1, W1);
-  const int B1 = add_buf(n, 128, 1, H1, W1);
-  const int B2 = even1 ? -1 : add_buf(n, 128, 0, H1, W1);
-  const int C0 = add_buf(n, 128, 1, H2, W2);
-  const int C1 = add_buf(n, 256, 1, H2, W2);
-  const int C2 = add_buf(n, 256, 1, H2, W2);
-  const int C3 = add_buf(n, 256, 1, H2, W2);
-  const int C4 = even2 ? -1 : add_buf(n, 256, 0, H2, W2);
-  const int D0 = add_buf(n, 256, 1, H3, W3);
-  const int D1 = add_buf(n, 512, 1, H3, W3);
-  const int D2 = add_buf(n, 512, 1, H3, W3);
-  const int D3 = add_buf(n, 256, 1, H3, W3);
+  // ---- activation buffers: after the trunk's, IN, the dense-block pairs, HEAD and the stage records ----
   const int IN = add_buf(n, S, 1, H3, W3);
   n->cat_buf[0] = IN;
   const int DB96[2] = {add_buf(n, 288, 1, H3, W3), add_buf(n, 288, 1, H3, W3)};
@@ -714,20 +663,8 @@ void build_plan_openpose(rtpose_net* n) {
   for (const StageW& w : st) n->op_save.push_back(add_buf(n, w.br == 0 ? P : Hc, 0, H3, W3));
 
   // ---- launches ----
-  add_simple_op(n, OP_INPUT, "nchw_to_nhwc8", H0, W0, -1, 0, X0, 0, 3);
-  plan_vgg_conv(n, cw0[0], H0, W0, X0, A1, -1);
-  plan_vgg_conv(n, cw0[1], H0, W0, A1, A2, B0);
-  plan_vgg_conv(n, cw0[2], H1, W1, B0, B1, -1);
-  plan_vgg_conv(n, cw0[3], H1, W1, B1, B2, C0);
-  plan_vgg_conv(n, cw0[4], H2, W2, C0, C1, -1);
-  plan_vgg_conv(n, cw0[5], H2, W2, C1, C2, -1);
-  plan_vgg_conv(n, cw0[6], H2, W2, C2, C3, -1);
-  plan_vgg_conv(n, cw0[7], H2, W2, C3, C4, D0);
-  plan_vgg_conv(n, cw0[8], H3, W3, D0, D1, -1);
-  plan_vgg_conv(n, cw0[9], H3, W3, D1, D2, -1);
-  plan_vgg_conv(n, cw0[10], H3, W3, D2, D3, -1);
+  plan_vgg_conv(n, tr.cw[11], H3, W3, tr.D3, IN, -1);  // conv4_4_CPM + PReLU -> features
   const int zero = 0;
-  add_conv_op(n, H3, W3, 1, &cw0[11], &D3, &zero, &IN, &zero, 0, 0);  // conv4_4_CPM + PReLU -> features
   for (size_t si = 0; si < st.size(); ++si) {
     const StageW& w = st[si];
     const int* db = w.inner == 96 ? DB96 : DB128;
@@ -743,7 +680,7 @@ void build_plan_openpose(rtpose_net* n) {
     const int out_off = w.br == 0 ? 128 : R;
     add_conv_op(n, H3, W3, 1, &w.m6, &last, &zero, &HEAD, &zero, 0, 0);
     add_conv_op(n, H3, W3, 1, &w.m7, &HEAD, &zero, &IN, &out_off, 0, 0);
-    add_simple_op(n, OP_COPY, "save" + std::to_string(si), H3, W3, IN, out_off, n->op_save[si], 0,
+    add_simple_op(n, OP_SAVE, "save" + std::to_string(si), H3, W3, IN, out_off, n->op_save[si], 0,
                   w.br == 0 ? P : Hc);
   }
 }
@@ -763,10 +700,53 @@ int default_winograd3() {
   return (env == 1 || env == 3) ? ((e3 && e3[0] == '2') ? 1 : (e3 && e3[0] == '4') ? 4 : RTPOSE_WINO3_AUTO) : 0;
 }
 
-rtpose_layout slice(const Buf& b, int choff) {
+// channels choff.. of buffer b.  `per_channel` = 2: the split plan's buffers, whose layouts count elements, 2 per channel
+rtpose_layout slice(const Buf& b, int choff, int per_channel = 1) {
   rtpose_layout l = b.lay;
-  l.choff = choff;
+  l.cstride *= per_channel;
+  l.choff = choff * per_channel;
   return l;
+}
+
+// the fp32 NHWC8 buffer rtpose_net_input_view hands out and conv1_1 reads (bf16 plans: a staging buffer, converted by
+// forward_prepared's input launch in the split plan)
+const Buf& fp32_input_buf(const rtpose_net* net) { return net->bufs[net->bf16 ? net->x0f_buf : net->x0_buf]; }
+
+// ---- what the two create calls share ----
+int check_winograd3(const char* who, int w3) {
+  if (w3 == RTPOSE_WINO_DEFAULT || w3 == 0 || w3 == 1 || w3 == 4 || w3 == RTPOSE_WINO3_AUTO) return 0;
+  return fail(RTPOSE_E_INVAL, "%s: winograd3 must be RTPOSE_WINO_DEFAULT, 0, 1, 4 or RTPOSE_WINO3_AUTO", who);
+}
+
+rtpose_net* new_plan(int N, int H, int W, int winograd3, float amp_limit) {
+  rtpose_net* n = new rtpose_net();
+  n->N = N;
+  n->H = H;
+  n->W = W;
+  n->n_cu = device_cu_count();
+  n->w3 = winograd3 != RTPOSE_WINO_DEFAULT ? winograd3 : default_winograd3();
+  n->amp_limit = amp_limit > 0.f ? amp_limit : 256.f;
+  return n;
+}
+
+void decide_forms(rtpose_net* n) {
+  pick_forms(n);
+  mark_plane_bufs(n);
+  n->forms_final = true;
+}
+
+int finish_plan(rtpose_net* n, rtpose_net** out) {
+  if (!forms_need_amps(n)) decide_forms(n);  // AUTO waits for the filters (rtpose_net_finalize_weights)
+  *out = n;
+  return 0;
+}
+
+// a captured launch list holds the arenas' pointers, the forms and the 7x7 grids: dropped when one of them may change
+void drop_graphs(rtpose_net* net) {
+  for (hipGraphExec_t& g : net->gexec) {
+    if (g) (void)hipGraphExecDestroy(g);
+    g = nullptr;
+  }
 }
 
 }  // namespace
@@ -784,47 +764,33 @@ int rtpose_net_create_opts(int N, int H, int W, const rtpose_net_options* opt, r
   if (dtype != RTPOSE_DTYPE_F32 && ((H | W) & 7))
     return fail(RTPOSE_E_INVAL, "net_create: the bf16 plan needs H and W to be multiples of 8 "
                                 "(crop_with_factor pads to that, im_transform.py:128-132)");
-  if (opt->winograd3 != RTPOSE_WINO_DEFAULT && opt->winograd3 != 0 && opt->winograd3 != 1 && opt->winograd3 != 4 &&
-      opt->winograd3 != RTPOSE_WINO3_AUTO)
-    return fail(RTPOSE_E_INVAL, "net_create: winograd3 must be RTPOSE_WINO_DEFAULT, 0, 1, 4 or RTPOSE_WINO3_AUTO");
+  if (int rc = check_winograd3("net_create", opt->winograd3)) return rc;
   if (opt->winograd7 != RTPOSE_WINO_DEFAULT && opt->winograd7 != 0 && opt->winograd7 != 4 && opt->winograd7 != 6 &&
       opt->winograd7 != RTPOSE_WINO7_AUTO)
     return fail(RTPOSE_E_INVAL, "net_create: winograd7 must be RTPOSE_WINO_DEFAULT, 0, 4, 6 or RTPOSE_WINO7_AUTO");
-  rtpose_net* n = new rtpose_net();
-  n->N = N;
-  n->H = H;
-  n->W = W;
+  rtpose_net* n = new_plan(N, H, W, opt->winograd3, opt->amp_limit);
   n->bf16 = dtype != RTPOSE_DTYPE_F32;
   n->split = dtype == RTPOSE_DTYPE_BF16X3;
-  n->n_cu = device_cu_count();
   {
-    // defaults of the two fields: on, unless the environment of the process says otherwise (RTPOSE_WINOGRAD =
-    // 0: direct kernels everywhere, 3 / 7: only that kernel size in Winograd form; RTPOSE_WINOGRAD7_M=4: F(4,7))
+    // defaults of winograd3 (default_winograd3) and winograd7: on, unless the environment of the process says otherwise
+    // (RTPOSE_WINOGRAD = 0: direct kernels everywhere, 3 / 7: only that kernel size in Winograd form; RTPOSE_WINOGRAD7_M=4: F(4,7))
     const int env = winograd_env();
     // Round 4: the default is the GUARDED choice - per layer, the fastest form whose amplification estimate for the
     // filters actually loaded stays under amp_limit (256): nobody here has seen pose_model.pth (README.md:19), and a
     // forced F(6,7) / F(4x4,3x3) would run whatever it holds.  He-init / N(0, 0.01) filters estimate 115-120 and
     // 42-43, so the bench plan keeps its forms bit for bit; RTPOSE_WINOGRAD3_M / RTPOSE_WINOGRAD7_M force a form.
     const char* e7 = getenv("RTPOSE_WINOGRAD7_M");
-    n->w3 = opt->winograd3 != RTPOSE_WINO_DEFAULT ? opt->winograd3 : default_winograd3();
     n->w7 = opt->winograd7 != RTPOSE_WINO_DEFAULT ? opt->winograd7
             : (env == 1 || env == 7)              ? ((e7 && (e7[0] == '4' || e7[0] == '6')) ? wino7_default_fm()
                                                                                            : RTPOSE_WINO7_AUTO)
                                                   : 0;
-    n->amp_limit = opt->amp_limit > 0.f ? opt->amp_limit : 256.f;
     // RTPOSE_W7_PERSIST=0 in the environment of the process: plans start with the split-tile launches off
     // (rtpose_net_set_persistent7 changes it per plan)
     const char* ep = getenv("RTPOSE_W7_PERSIST");
     n->persist7 = (ep && ep[0] == '0') ? 0 : 1;
   }
   build_plan(n);
-  if (!forms_need_amps(n)) {  // AUTO waits for the filters (rtpose_net_finalize_weights)
-    pick_forms(n);
-    mark_plane_bufs(n);
-    n->forms_final = true;
-  }
-  *out = n;
-  return 0;
+  return finish_plan(n, out);
 }
 
 int rtpose_openpose_create(int N, int H, int W, const rtpose_openpose_options* opt, rtpose_net** out) {
@@ -838,30 +804,16 @@ int rtpose_openpose_create(int N, int H, int W, const rtpose_openpose_options* o
                                 "stages of each, openpose.py:177)");
   if (opt->paf_channels < 1 || opt->paf_channels > 64 || opt->heat_channels < 1 || opt->heat_channels > 64)
     return fail(RTPOSE_E_INVAL, "openpose_create: paf_channels and heat_channels must be 1..64");
-  if (opt->winograd3 != RTPOSE_WINO_DEFAULT && opt->winograd3 != 0 && opt->winograd3 != 1 && opt->winograd3 != 4 &&
-      opt->winograd3 != RTPOSE_WINO3_AUTO)
-    return fail(RTPOSE_E_INVAL, "openpose_create: winograd3 must be RTPOSE_WINO_DEFAULT, 0, 1, 4 or RTPOSE_WINO3_AUTO");
-  rtpose_net* n = new rtpose_net();
-  n->N = N;
-  n->H = H;
-  n->W = W;
+  if (int rc = check_winograd3("openpose_create", opt->winograd3)) return rc;
+  rtpose_net* n = new_plan(N, H, W, opt->winograd3, opt->amp_limit);
   n->topo = 1;
   n->op_l2 = opt->l2_stages;
   n->op_l1 = opt->l1_stages;
   n->op_paf = opt->paf_channels;
   n->op_heat = opt->heat_channels;
-  n->n_cu = device_cu_count();
-  n->w3 = opt->winograd3 != RTPOSE_WINO_DEFAULT ? opt->winograd3 : default_winograd3();
   n->w7 = 0;  // no 7x7 convs
-  n->amp_limit = opt->amp_limit > 0.f ? opt->amp_limit : 256.f;
   build_plan_openpose(n);
-  if (!forms_need_amps(n)) {
-    pick_forms(n);
-    mark_plane_bufs(n);
-    n->forms_final = true;
-  }
-  *out = n;
-  return 0;
+  return finish_plan(n, out);
 }
 
 int rtpose_net_create_ex(int N, int H, int W, int dtype, rtpose_net** out) {
@@ -885,8 +837,7 @@ int rtpose_net_dtype(const rtpose_net* net) {
 void rtpose_net_destroy(rtpose_net* net) {
   if (!net) return;
   for (hipEvent_t e : net->ev) (void)hipEventDestroy(e);
-  for (hipGraphExec_t g : net->gexec)
-    if (g) (void)hipGraphExecDestroy(g);
+  drop_graphs(net);
   if (net->gev_in) (void)hipEventDestroy(net->gev_in);
   if (net->gev_out) (void)hipEventDestroy(net->gev_out);
   if (net->gstream) (void)hipStreamDestroy(net->gstream);
@@ -912,10 +863,7 @@ int rtpose_net_bind(rtpose_net* net, void* workspace, size_t workspace_bytes, vo
                                 "(create the plan with that device current)", net->n_cu, dev, device_cu_count());
   net->device = dev;
   net->in_checked = CheckedPtr();
-  for (hipGraphExec_t& g : net->gexec) {  // captured pointers are about to change
-    if (g) (void)hipGraphExecDestroy(g);
-    g = nullptr;
-  }
+  drop_graphs(net);  // captured pointers are about to change
   net->forwards = 0;
   // a zeroed workspace suits either storage of a buffer; a caller-kept one is taken to hold pixel-major data with clean gaps
   net->zeroed_at_bind = zero_workspace != 0;
@@ -933,23 +881,10 @@ int rtpose_net_bind(rtpose_net* net, void* workspace, size_t workspace_bytes, vo
     RTPOSE_HIP_CHECK(hipMemsetAsync(net->ws + net->scratch_off, 0,
                                     (size_t)((char*)(conv2d_wino7_scratch_err(net->ws + net->scratch_off, net->n_cu) + 1) -
                                              (char*)(net->ws + net->scratch_off)), s));
-  if (net->topo == 1) {  // OpenPose_Model: packed c -> source channel of cat([features, heat, paf])
-    RTPOSE_HIP_CHECK(hipMemcpyAsync(net->wt + net->catmap_off, net->catmap_host.data(),
-                                    net->catmap_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    RTPOSE_HIP_CHECK(hipStreamSynchronize(s));
-    net->bound = true;
-    return 0;
-  }
-  // channel map of the concat input: packed c -> source channel of cat([L1,L2,out1])
-  int32_t map[kCatC];
-  for (int c = 0; c < kCatC; ++c) {
-    if (c < 128) map[c] = 57 + c;
-    else if (c < kCatHeat) map[c] = c - kCatPaf;
-    else if (c < 185) map[c] = 38 + (c - kCatHeat);
-    else map[c] = -1;
-  }
-  RTPOSE_HIP_CHECK(hipMemcpyAsync(net->wt + net->catmap_off, map, sizeof(map), hipMemcpyHostToDevice, s));
-  RTPOSE_HIP_CHECK(hipStreamSynchronize(s));  // `map` is a stack buffer
+  // channel map of the filters that read a concat buffer
+  RTPOSE_HIP_CHECK(hipMemcpyAsync(net->wt + net->catmap_off, net->catmap_host.data(),
+                                  net->catmap_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  RTPOSE_HIP_CHECK(hipStreamSynchronize(s));
   net->bound = true;
   return 0;
 }
@@ -1005,14 +940,14 @@ int rtpose_net_load_conv(rtpose_net* net, int idx, const float* w_oihw, const fl
       if (rcf) return rcf;
     }
     return pack_weights_bf16_launch(w_oihw, bias, c.cout, c.cin_src, c.k, map, c.cin_packed,
-                                    net->wt + c.w_off, net->wt + c.b_off, net->split, s);
+                                    net->wt + c.w_off[F_DIRECT], net->wt + c.b_off, net->split, s);
   }
   // every packing the arena holds for this conv (the plans that share the arena choose among them), and the
   // amplification estimate of each Winograd form; every plan on this arena re-reads them (sync_arena_generation)
   arena_bump(net->wt);
   net->amps_read = false;
   if (forms_need_amps(net)) net->forms_final = false;
-  int rc = pack_weights_launch(w_oihw, bias, c.cout, c.cin_src, c.k, map, c.cin_packed, net->wt + c.w_off,
+  int rc = pack_weights_launch(w_oihw, bias, c.cout, c.cin_src, c.k, map, c.cin_packed, net->wt + c.w_off[F_DIRECT],
                                net->wt + c.b_off, s);
   if (rc) return rc;
   if (c.first) {
@@ -1021,26 +956,15 @@ int rtpose_net_load_conv(rtpose_net* net, int idx, const float* w_oihw, const fl
   }
   float* amp = net->wt + c.amp_off;
   RTPOSE_HIP_CHECK(hipMemsetAsync(amp, 0, 4 * sizeof(float), s));
-  if (c.has_w3) {
-    rc = rtpose_pack_conv_weights_winograd(w_oihw, bias, c.cout, c.cin_src, 3, map, c.cin_packed,
-                                           net->wt + c.w_off_w3, net->wt + c.b_off, stream);
-    if (!rc) rc = wino_amplification_launch(w_oihw, c.cout, c.cin_src, 3, 0, amp + 0, s);
-    if (rc) return rc;
-  }
-  if (c.has_w43) {
-    rc = rtpose_pack_conv_weights_winograd3(w_oihw, bias, c.cout, c.cin_src, 4, map, c.cin_packed,
-                                            net->wt + c.w_off_w43, net->wt + c.b_off, stream);
-    if (!rc) rc = rtpose_winograd_amplification(w_oihw, c.cout, c.cin_src, 3, 4, amp + 3, stream);
-    if (rc) return rc;
-  }
-  if (c.has_w7) {
-    rc = pack_weights_wino7_launch(w_oihw, bias, c.cout, c.cin_src, map, c.cin_packed, 4, net->wt + c.w_off_w4,
-                                   net->wt + c.b_off, s);
-    if (!rc)
-      rc = pack_weights_wino7_launch(w_oihw, bias, c.cout, c.cin_src, map, c.cin_packed, 6, net->wt + c.w_off_w6,
-                                     net->wt + c.b_off, s);
-    if (!rc) rc = wino_amplification_launch(w_oihw, c.cout, c.cin_src, 7, 4, amp + 1, s);
-    if (!rc) rc = wino_amplification_launch(w_oihw, c.cout, c.cin_src, 7, 6, amp + 2, s);
+  for (int f = F_DIRECT + 1; f < kForms; ++f) {
+    if (!c.packed((Form)f)) continue;
+    const FormInfo& fi = kForm[f];
+    float* wp = net->wt + c.w_off[f];
+    rc = fi.k == 3 ? rtpose_pack_conv_weights_winograd3(w_oihw, bias, c.cout, c.cin_src, fi.fm, map, c.cin_packed, wp,
+                                                        net->wt + c.b_off, stream)
+                   : pack_weights_wino7_launch(w_oihw, bias, c.cout, c.cin_src, map, c.cin_packed, fi.fm, wp,
+                                               net->wt + c.b_off, s);
+    if (!rc) rc = rtpose_winograd_amplification(w_oihw, c.cout, c.cin_src, fi.k, fi.fm, amp + fi.amp_slot, stream);
     if (rc) return rc;
   }
   return 0;
@@ -1067,13 +991,8 @@ int rtpose_net_finalize_weights(rtpose_net* net, void* stream) {
   if (net->forms_final) return 0;
   const int rc = read_amps(net, as_stream(stream));
   if (rc) return rc;
-  pick_forms(net);
-  mark_plane_bufs(net);
-  net->forms_final = true;
-  for (hipGraphExec_t& g : net->gexec) {  // a captured launch list may hold other forms
-    if (g) (void)hipGraphExecDestroy(g);
-    g = nullptr;
-  }
+  decide_forms(net);
+  drop_graphs(net);  // a captured launch list may hold other forms
   return 0;
 }
 
@@ -1084,7 +1003,7 @@ int rtpose_net_conv_numerics(rtpose_net* net, int idx, int* form, float* amp, vo
   if (!rc && amp) rc = read_amps(net, as_stream(stream));
   if (rc) return rc;
   const ConvW& c = net->convs[idx];
-  if (form) *form = c.form;
+  if (form) *form = kForm[c.form].code;
   if (amp)
     for (int i = 0; i < 4; ++i) amp[i] = c.amp[i];
   return 0;
@@ -1154,10 +1073,7 @@ static void decide_guard_launch(rtpose_net* net) {
 int rtpose_net_set_persistent7(rtpose_net* net, int enable) {
   if (!net) return fail(RTPOSE_E_INVAL, "net_set_persistent7: NULL net");
   net->persist7 = enable ? 1 : 0;
-  for (hipGraphExec_t& g : net->gexec) {  // a captured launch list holds the other grids
-    if (g) (void)hipGraphExecDestroy(g);
-    g = nullptr;
-  }
+  drop_graphs(net);  // a captured launch list holds the other grids
   return 0;
 }
 
@@ -1210,20 +1126,17 @@ int rtpose_net_launch_executed_flops(const rtpose_net* net, int i, double* flops
     for (int g = 0; g < o.ngroups; ++g) {
       // what the matrix pipe is issued (SQ_INSTS_MFMA x 4096 of a launch): whole tiles, padded channels and columns
       const ConvW& c = net->convs[o.conv_idx[g]];
-      if (c.first) {  // conv_first_kernel (fp32 and bf16 plans: the fp32 matrix instruction either way): 8 x 32 pixel tiles, K = 28 (27 taps + a zero row), 64 columns
+      wino = kForm[c.form].code;
+      if (c.first)  // conv_first_kernel (fp32 and bf16 plans: the fp32 matrix instruction either way): 8 x 32 pixel tiles, K = 28 (27 taps + a zero row), 64 columns
         fl += 2.0 * net->N * ceil_div(o.H, 8) * ceil_div(o.W, 32) * 256.0 * 28.0 * 64.0;
-      } else if (c.form == 3) {         // 16 frequencies per 2 x 2 wtile
+      else if (c.form == F_W3_2X2)  // 16 frequencies per 2 x 2 wtile
         fl += conv2d_wino_issued_flops(c.cin_packed, c.cout, net->N, o.H, o.W);
-        wino = 3;
-      } else if (c.form == 43) {  // 36 frequencies per 4 x 4 wtile
+      else if (c.form == F_W3_4X4)  // 36 frequencies per 4 x 4 wtile
         fl += conv2d_wino4_issued_flops(c.cin_packed, c.cout, net->N, o.H, o.W);
-        wino = 43;
-      } else if (c.form) {       // FM + 6 frequencies x 7 rows per group of FM pixels, 32-position strips per image
-        fl += conv2d_wino7_issued_flops(c.cin_packed, c.cout, net->N, o.H, o.W, o.H + 3, c.form);
-        wino = c.form;
-      } else {
+      else if (c.form != F_DIRECT)  // FM + 6 frequencies x 7 rows per group of FM pixels, 32-position strips per image
+        fl += conv2d_wino7_issued_flops(c.cin_packed, c.cout, net->N, o.H, o.W, o.H + 3, kForm[c.form].fm);
+      else
         fl += 2.0 * net->N * o.H * o.W * (double)c.k * c.k * (double)c.cin_packed * cout_pad(c.cout);
-      }
     }
   if (flops) *flops = fl;
   if (winograd) *winograd = wino;
@@ -1259,8 +1172,7 @@ int rtpose_net_forward_prepared(rtpose_net* net, void* stream) { return net_forw
 
 int rtpose_net_input_view(const rtpose_net* net, float** base, rtpose_layout* layout) {
   if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_input_view: net not bound");
-  // bf16 plans expose an fp32 staging buffer; forward_prepared converts it
-  const Buf& b = net->bufs[net->bf16 ? net->x0f_buf : net->x0_buf];
+  const Buf& b = fp32_input_buf(net);
   if (base) *base = net->ws + b.off_floats;
   if (layout) *layout = b.lay;
   return 0;
@@ -1367,9 +1279,49 @@ static int net_forward_impl(rtpose_net* net, const float* x_nchw, void* stream) 
   return 0;
 }
 
+// Descriptor of group g of launch `o`.  OP_CONV: the whole conv.  OP_TAIL: what conv_tail_launch / conv_tail_bf16_launch
+// take for the first and the `second` conv of the pair - the input side / the output side only, ReLU by position and
+// nothing else (the launchers check what they are given, csrc/conv_desc.h).
+static rtpose_conv_desc conv_desc(const rtpose_net* net, const Op& o, int g, bool second = false) {
+  const bool pair = o.kind == OP_TAIL;
+  const ConvW& c = net->convs[second ? o.conv2_idx[g] : o.conv_idx[g]];
+  rtpose_conv_desc d;
+  memset(&d, 0, sizeof(d));
+  d.w_packed = net->wt + c.w_off[c.form];
+  d.bias_packed = net->wt + c.b_off;
+  d.cin = c.cin_packed;
+  d.cout = c.cout;
+  d.k = c.k;
+  if (!pair || !second) {
+    const Buf& bi = net->bufs[o.in_buf[g]];
+    d.in = net->ws + bi.off_floats;
+    d.lin = slice(bi, o.in_choff[g], net->split ? 2 : 1);
+    if (!pair) d.in_plane_pixels = bi.plane_px;
+  }
+  if (!pair || second) {
+    const Buf& bo = net->bufs[o.out_buf[g]];
+    d.out = net->ws + bo.off_floats;
+    d.lout = slice(bo, o.out_choff[g], net->split && !o.out_f32 ? 2 : 1);
+    if (!pair) d.out_plane_pixels = bo.plane_px;
+  }
+  if (pair) {
+    d.relu = !second;
+    return d;
+  }
+  d.wino_m = kForm[c.form].fm;
+  d.relu = o.relu;
+  d.pool = o.pool;
+  d.prelu = c.has_prelu ? net->wt + c.pr_off : nullptr;
+  return d;
+}
+
 static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* x_nchw, void* stream, bool prof) {
   hipStream_t s = as_stream(stream);
   const int N = net->N;
+  // conv1_1 of the fp32 and bf16 plans reads fp32 itself (conv_first.hip): the NCHW image where the caller left it when
+  // the image and the launch belong to the same call, else the plan's fp32 NHWC8 input buffer - filled by the caller
+  // (forward_prepared) or by OP_INPUT (graph replay: the captured launch list reads the plan's own buffer)
+  const bool conv1_reads_image = x_nchw && first == 0 && net->conv1_op >= 0 && (size_t)net->conv1_op < last;
   for (size_t i = first; i < last; ++i) {
     const Op& o = net->ops[i];
     if (prof) RTPOSE_HIP_CHECK(hipEventRecord(net->ev[i], s));
@@ -1379,130 +1331,43 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
     int rc = 0;
     switch (o.kind) {
       case OP_INPUT: {
-        const Buf& b = net->bufs[o.out_buf[0]];
-        if (net->bf16 && !net->split) {
-          // conv1_1 of the bf16 plan reads fp32 itself (conv_first.hip MODE 2): the image where the caller left it when it
-          // runs in the same call, else the plan's fp32 NHWC8 staging buffer (forward_prepared: filled by the caller; graph
-          // replay: filled here) - the NCHW -> bf16 NHWC16 conversion launch is gone
-          if (!x_nchw) break;
-          bool first_reads_image = false;
-          for (size_t j = first + 1; j < last && !first_reads_image; ++j)
-            first_reads_image = net->ops[j].kind == OP_CONV && net->convs[net->ops[j].conv_idx[0]].first;
-          if (first_reads_image) break;
-          const Buf& bs = net->bufs[net->x0f_buf];
+        const Buf& bs = fp32_input_buf(net);
+        if (net->split) {  // no conv1_1 kernel: the image, or what the caller left in the fp32 buffer, becomes hi + lo bf16
+          const Buf& b = net->bufs[o.out_buf[0]];
+          const rtpose_layout lb = slice(b, 0, 2);
+          rc = x_nchw ? rtpose_nchw_to_layout_split(x_nchw, net->ws + b.off_floats, &lb, 3, 16, N, o.H, o.W, stream)
+                      : rtpose_layout_f32_to_split(net->ws + bs.off_floats, &bs.lay, net->ws + b.off_floats, &lb, 3, 16,
+                                                   N, o.H, o.W, stream);
+        } else if (x_nchw && !conv1_reads_image) {
           rc = rtpose_nchw_to_layout(x_nchw, net->ws + bs.off_floats, &bs.lay, 3, 8, N, o.H, o.W, stream);
-          break;
         }
-        if (net->bf16) {
-          rtpose_layout lb = b.lay;
-          if (net->split) lb.cstride *= 2;  // elements
-          const Buf& bs = net->bufs[net->x0f_buf];
-          if (x_nchw && net->split)
-            rc = rtpose_nchw_to_layout_split(x_nchw, net->ws + b.off_floats, &lb, 3, 16, N, o.H, o.W, stream);
-          else if (x_nchw)
-            rc = rtpose_nchw_to_layout_bf16(x_nchw, net->ws + b.off_floats, &lb, 3, 16, N, o.H, o.W, stream);
-          else if (net->split)
-            rc = rtpose_layout_f32_to_split(net->ws + bs.off_floats, &bs.lay, net->ws + b.off_floats, &lb, 3, 16,
-                                            N, o.H, o.W, stream);
-          else
-            rc = rtpose_layout_f32_to_bf16(net->ws + bs.off_floats, &bs.lay, net->ws + b.off_floats, &lb, 3, 16,
-                                           N, o.H, o.W, stream);
-          break;
-        }
-        if (!x_nchw) break;  // forward_prepared: the input buffer was written by the caller
-        // fp32 plans: conv1_1 reads the NCHW image itself (conv_first.hip) when it runs in the same call; the
-        // conversion remains for graph replay, whose captured launch list reads the plan's own input buffer
-        {
-          bool first_reads_image = false;  // is conv1_1 (looked up by its flag, not by position) part of this call?
-          for (size_t j = first + 1; j < last && !first_reads_image; ++j)
-            first_reads_image = net->ops[j].kind == OP_CONV && net->convs[net->ops[j].conv_idx[0]].first;
-          if (first_reads_image) break;
-        }
-        rc = rtpose_nchw_to_layout(x_nchw, net->ws + b.off_floats, &b.lay, 3, 8, N, o.H, o.W, stream);
         break;
       }
       case OP_CONV: {
-        rtpose_conv_desc d[2];
-        memset(d, 0, sizeof(d));
-        for (int g = 0; g < o.ngroups; ++g) {
-          const ConvW& c = net->convs[o.conv_idx[g]];
-          const Buf& bi = net->bufs[o.in_buf[g]];
-          const Buf& bo = net->bufs[o.out_buf[g]];
-          d[g].in_plane_pixels = bi.plane_px;
-          d[g].out_plane_pixels = bo.plane_px;
-          d[g].in = net->ws + bi.off_floats;
-          d[g].out = net->ws + bo.off_floats;
-          d[g].w_packed = net->wt + (c.form == 3    ? c.w_off_w3
-                                     : c.form == 43 ? c.w_off_w43
-                                     : c.form == 4  ? c.w_off_w4
-                                     : c.form == 6  ? c.w_off_w6
-                                                    : c.w_off);
-          d[g].wino_m = c.form == 4 || c.form == 6 ? c.form : c.form == 43 ? 4 : 0;
-          d[g].bias_packed = net->wt + c.b_off;
-          d[g].lin = slice(bi, o.in_choff[g]);
-          d[g].lout = slice(bo, o.out_choff[g]);
-          if (net->split) {  // split buffers: layouts count elements, 2 per channel
-            d[g].lin.cstride *= 2;
-            d[g].lin.choff *= 2;
-            if (!o.out_f32) {
-              d[g].lout.cstride *= 2;
-              d[g].lout.choff *= 2;
-            }
-          }
-          d[g].cin = c.cin_packed;
-          d[g].cout = c.cout;
-          d[g].k = c.k;
-          d[g].relu = o.relu;
-          d[g].pool = o.pool;
-          d[g].out_cmap = nullptr;
-          d[g].prelu = c.has_prelu ? net->wt + c.pr_off : nullptr;
-        }
-        if (net->convs[o.conv_idx[0]].first) {
-          const ConvW& c = net->convs[o.conv_idx[0]];
-          const bool direct_src = x_nchw && first == 0;  // the image itself; else the plan's NHWC8 input buffer
-          if (net->bf16) {  // (fp32 source: the staging buffer, not this conv's bf16 input buffer)
-            const Buf& bs = net->bufs[net->x0f_buf];
-            rc = conv_first_launch(direct_src ? x_nchw : nullptr, net->ws + bs.off_floats, &bs.lay, net->wt + c.w_off_first,
-                                   d[0].out, &d[0].lout, 0, o.relu, N, o.H, o.W, s, 1);
-            break;
-          }
-          rc = conv_first_launch(direct_src ? x_nchw : nullptr, d[0].in, &d[0].lin, net->wt + c.w_off_first, d[0].out,
-                                 &d[0].lout, d[0].out_plane_pixels, o.relu, N, o.H, o.W, s, 0);
+        rtpose_conv_desc d[2] = {};
+        for (int g = 0; g < o.ngroups; ++g) d[g] = conv_desc(net, o, g);
+        const ConvW& c = net->convs[o.conv_idx[0]];  // grouped convs run one form (pick_forms)
+        if (c.first) {
+          const Buf& bs = fp32_input_buf(net);
+          rc = conv_first_launch(conv1_reads_image ? x_nchw : nullptr, net->ws + bs.off_floats, &bs.lay,
+                                 net->wt + c.w_off_first, d[0].out, &d[0].lout, d[0].out_plane_pixels, o.relu, N, o.H, o.W,
+                                 s, net->bf16);
           break;
         }
-        const int form = net->convs[o.conv_idx[0]].form;  // grouped convs run one form (pick_forms)
-        rc = net->bf16   ? conv2d_bf16_launch(d, o.ngroups, N, o.H, o.W, o.out_f32, net->split, s)
-             : form == 3  ? conv2d_wino_launch(d, o.ngroups, N, o.H, o.W, s)
-             : form == 43 ? conv2d_wino4_launch(d, o.ngroups, N, o.H, o.W, s)
-             : form      ? conv2d_wino7_launch(d, o.ngroups, N, o.H, o.W, form,
-                                               net->persist7 ? net->ws + net->scratch_off : nullptr,  // (no scratch:
-                                               net->persist7 ? net->scratch_bytes : 0, s)             //  one block per tile)
-                         : conv2d_launch(d, o.ngroups, N, o.H, o.W, s);
+        rc = net->bf16           ? conv2d_bf16_launch(d, o.ngroups, N, o.H, o.W, o.out_f32, net->split, s)
+             : c.form == F_W3_2X2 ? conv2d_wino_launch(d, o.ngroups, N, o.H, o.W, s)
+             : c.form == F_W3_4X4 ? conv2d_wino4_launch(d, o.ngroups, N, o.H, o.W, s)
+             : c.form != F_DIRECT ? conv2d_wino7_launch(d, o.ngroups, N, o.H, o.W, kForm[c.form].fm,
+                                                        net->persist7 ? net->ws + net->scratch_off : nullptr,  // (no scratch:
+                                                        net->persist7 ? net->scratch_bytes : 0, s)             //  one block per tile)
+                                  : conv2d_launch(d, o.ngroups, N, o.H, o.W, s);
         break;
       }
       case OP_TAIL: {
         rtpose_conv_desc d1[2], d2[2];
         for (int g = 0; g < o.ngroups; ++g) {
-          const ConvW &c1 = net->convs[o.conv_idx[g]], &c2 = net->convs[o.conv2_idx[g]];
-          const Buf& bi = net->bufs[o.in_buf[g]];
-          const Buf& bo = net->bufs[o.out_buf[g]];
-          memset(&d1[g], 0, sizeof(d1[g]));
-          memset(&d2[g], 0, sizeof(d2[g]));
-          d1[g].in = net->ws + bi.off_floats;
-          d1[g].lin = slice(bi, o.in_choff[g]);
-          d1[g].w_packed = net->wt + c1.w_off;
-          d1[g].bias_packed = net->wt + c1.b_off;
-          d1[g].cin = c1.cin_packed;
-          d1[g].cout = c1.cout;
-          d1[g].k = 1;
-          d1[g].relu = 1;
-          d2[g].w_packed = net->wt + c2.w_off;
-          d2[g].bias_packed = net->wt + c2.b_off;
-          d2[g].cin = c2.cin_packed;
-          d2[g].cout = c2.cout;
-          d2[g].k = 1;
-          d2[g].out = net->ws + bo.off_floats;
-          d2[g].lout = slice(bo, o.out_choff[g]);
+          d1[g] = conv_desc(net, o, g, false);
+          d2[g] = conv_desc(net, o, g, true);
         }
         rc = net->bf16 ? conv_tail_bf16_launch(d1, d2, o.ngroups, N, o.H, o.W, o.out_f32, s)
                        : conv_tail_launch(d1, d2, o.ngroups, N, o.H, o.W, s);
@@ -1515,37 +1380,73 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
                                N, o.H, o.W, stream);
         break;
       }
+      case OP_SAVE:  // a concat slice -> the fp32 record of the stage outputs
       case OP_COPY: {
-        const bool is_save = o.name.rfind("save", 0) == 0;
-        if (is_save && !net->keep) break;
+        const bool save = o.kind == OP_SAVE;
+        if (save && !net->keep) break;
         const Buf& bi = net->bufs[o.in_buf[0]];
         const Buf& bo = net->bufs[o.out_buf[0]];
-        rtpose_layout li = slice(bi, o.in_choff[0]), lo = slice(bo, o.out_choff[0]);
-        if (net->split && is_save) {
-          li.cstride *= 2;
-          li.choff *= 2;
+        rtpose_layout li = slice(bi, o.in_choff[0], save && net->split ? 2 : 1), lo = slice(bo, o.out_choff[0]);
+        if (save && net->split) {
           rc = rtpose_layout_split_to_f32(net->ws + bi.off_floats, &li, net->ws + bo.off_floats, &lo, o.C, N,
                                           o.H, o.W, stream);
           break;
         }
-        if (net->bf16 && is_save) {  // bf16 concat slice -> fp32 record of the stage outputs
+        if (save && net->bf16) {
           rc = rtpose_layout_bf16_to_f32(net->ws + bi.off_floats, &li, net->ws + bo.off_floats, &lo, o.C, N,
                                          o.H, o.W, stream);
           break;
         }
+        int words = o.C;
         if (net->bf16 && !net->split) {  // bf16 -> bf16: move channel pairs as 4-byte words
           li.cstride /= 2; li.choff /= 2; lo.cstride /= 2; lo.choff /= 2;
-          rc = rtpose_layout_copy(net->ws + bi.off_floats, &li, net->ws + bo.off_floats, &lo, o.C / 2, N, o.H,
-                                  o.W, stream);
-          break;
+          words /= 2;
         }
-        rc = rtpose_layout_copy(net->ws + bi.off_floats, &li, net->ws + bo.off_floats, &lo, o.C, N, o.H,
+        rc = rtpose_layout_copy(net->ws + bi.off_floats, &li, net->ws + bo.off_floats, &lo, words, N, o.H,
                                 o.W, stream);
         break;
       }
     }
     if (rc) return rc;
   }
+  return 0;
+}
+
+// Where the maps of stage output `which` (numbered as rtpose_net_read_output numbers them) are: in the stage records
+// when `records` (keep_intermediates; a bf16 plan's last stage always), else where the stage's last launch left them -
+// which only the last stages' are still there.
+static int stage_output_slice(const rtpose_net* net, int which, bool records, const float** base, rtpose_layout* lay,
+                              int* C) {
+  int buf, choff;
+  if (net->topo == 1) {  // saved_for_loss flattened: the PAF stages, then the heat-map stages
+    const bool paf = which < net->op_l2;
+    *C = paf ? net->op_paf : net->op_heat;
+    if (records) {
+      buf = net->op_save[which];
+      choff = 0;
+    } else {
+      if (which != net->op_l2 - 1 && which != net->op_l2 + net->op_l1 - 1)
+        return fail(RTPOSE_E_STATE, "net_read_output: stage output %d not kept (set keep_intermediates)", which);
+      buf = net->cat_buf[0];  // the stage input buffer
+      choff = paf ? 128 : net->op_heat_off;
+    }
+  } else {
+    const int stage = which / 2 + 1, br = which % 2;
+    *C = br == 0 ? 38 : 19;
+    if (records || (net->bf16 && stage == 6)) {
+      buf = net->save_buf[stage - 1];
+      choff = br == 0 ? 0 : 38;
+    } else {
+      if (net->bf16)
+        return fail(RTPOSE_E_STATE, "net_read_output: bf16 plan keeps only stage 6 (set keep_intermediates)");
+      if (stage < 5) return fail(RTPOSE_E_STATE, "net_read_output: stage %d not kept (set keep_intermediates)", stage);
+      buf = (stage % 2 == 0) ? net->cat_buf[0] : net->cat_buf[1];  // (stage 6 writes CATa)
+      choff = br == 0 ? kCatPaf : kCatHeat;
+    }
+  }
+  const Buf& b = net->bufs[buf];
+  *base = net->ws + b.off_floats;
+  *lay = slice(b, choff);
   return 0;
 }
 
@@ -1556,58 +1457,25 @@ int rtpose_net_read_output(rtpose_net* net, int which, float* dst_nchw, void* st
   int rcd = net_on_its_device(net, "net_read_output");
   if (!rcd) rcd = check_device_ptr(dst_nchw, net->device, "net_read_output", "the destination tensor");
   if (rcd) return rcd;
-  if (net->topo == 1) {  // saved_for_loss flattened: the PAF stages, then the heat-map stages
-    const bool paf = which < net->op_l2;
-    const int C = paf ? net->op_paf : net->op_heat;
-    int buf = net->op_save[which], choff = 0;
-    if (!net->keep) {
-      if (which != net->op_l2 - 1 && which != net->op_l2 + net->op_l1 - 1)
-        return fail(RTPOSE_E_STATE, "net_read_output: stage output %d not kept (set keep_intermediates)", which);
-      buf = net->cat_buf[0];
-      choff = paf ? 128 : net->op_heat_off;
-    }
-    const Buf& b = net->bufs[buf];
-    const rtpose_layout l = slice(b, choff);
-    return rtpose_layout_to_nchw(net->ws + b.off_floats, &l, dst_nchw, C, net->N, net->H3, net->W3, stream);
-  }
-  const int stage = which / 2 + 1, br = which % 2;
-  const int C = br == 0 ? 38 : 19;
-  int buf, choff;
-  if (net->bf16 && (net->keep || stage == 6)) {
-    buf = net->save_buf[stage - 1];
-    choff = br == 0 ? 0 : 38;
-  } else if (net->bf16) {
-    return fail(RTPOSE_E_STATE, "net_read_output: bf16 plan keeps only stage 6 (set keep_intermediates)");
-  } else if (net->keep) {
-    buf = net->save_buf[stage - 1];
-    choff = br == 0 ? 0 : 38;
-  } else {
-    if (stage < 5) return fail(RTPOSE_E_STATE, "net_read_output: stage %d not kept (set keep_intermediates)", stage);
-    buf = (stage % 2 == 0) ? net->cat_buf[0] : net->cat_buf[1];
-    choff = br == 0 ? kCatPaf : kCatHeat;
-  }
-  const Buf& b = net->bufs[buf];
-  const rtpose_layout l = slice(b, choff);
-  return rtpose_layout_to_nchw(net->ws + b.off_floats, &l, dst_nchw, C, net->N, net->H3, net->W3, stream);
+  const float* src;
+  rtpose_layout l;
+  int C;
+  if (int rc = stage_output_slice(net, which, net->keep != 0, &src, &l, &C)) return rc;
+  return rtpose_layout_to_nchw(src, &l, dst_nchw, C, net->N, net->H3, net->W3, stream);
 }
 
 int rtpose_net_output_view(const rtpose_net* net, int which, const float** base, rtpose_layout* layout,
                            int* C, int* H, int* W) {
   if (!net || !net->bound || which < 0 || which > 1) return fail(RTPOSE_E_INVAL, "output_view: bad argument");
-  if (net->topo == 1) {  // the last PAF / heat maps, in the stage input buffer
-    const Buf& b = net->bufs[net->cat_buf[0]];
-    if (base) *base = net->ws + b.off_floats;
-    if (layout) *layout = slice(b, which == 0 ? 128 : net->op_heat_off);
-    if (C) *C = which == 0 ? net->op_paf : net->op_heat;
-    if (H) *H = net->H3;
-    if (W) *W = net->W3;
-    return 0;
-  }
-  // stage 6 writes CATa (fp32 plans) / the fp32 stage-6 record (bf16 plans)
-  const Buf& b = net->bufs[net->bf16 ? net->save_buf[5] : net->cat_buf[0]];
-  if (base) *base = net->ws + b.off_floats;
-  if (layout) *layout = net->bf16 ? slice(b, which == 0 ? 0 : 38) : slice(b, which == 0 ? kCatPaf : kCatHeat);
-  if (C) *C = which == 0 ? 38 : 19;
+  // the last PAF / heat maps, where the last stage's launch writes them whether records are kept or not
+  const int last = net->topo == 1 ? (which == 0 ? net->op_l2 : net->op_l2 + net->op_l1) - 1 : 10 + which;
+  const float* b;
+  rtpose_layout l;
+  int c;
+  if (int rc = stage_output_slice(net, last, false, &b, &l, &c)) return rc;
+  if (base) *base = b;
+  if (layout) *layout = l;
+  if (C) *C = c;
   if (H) *H = net->H3;
   if (W) *W = net->W3;
   return 0;

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv_desc.h"
+#include "launchers.h"
 #include "wino_common.h"
 
 namespace rtpose {

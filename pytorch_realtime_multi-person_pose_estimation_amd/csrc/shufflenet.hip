@@ -24,43 +24,9 @@
 #include <vector>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace rtpose {
-int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s);
-int pack_weights_launch(const float* w, const float* bias, int cout, int cin_src, int k,
-                        const int32_t* cin_map, int cin_packed, float* wp, float* bp, hipStream_t s);
-// bf16 plans (conv_mfma_bf16.hip)
-int conv2d_bf16_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int out_f32, int split,
-                       hipStream_t s);
-int pack_weights_bf16_launch(const float* w, const float* bias, int cout, int cin_src, int k,
-                             const int32_t* cin_map, int cin_packed, void* wp, float* bp, int split,
-                             hipStream_t s);
-
-// fused pointwise chains of the fp32 plan (pw_fused.hip)
-int pw_fused_launch(const rtpose_pw_desc* d, int N, int H, int W, hipStream_t s);
-int pack_pw_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map, int K,
-                   int coutp, int col_off, float* wp, float* bp, hipStream_t s);
-int pw_halo_stride(const rtpose_layout& l, int H, int W);
-// conv5 + the two heads as one back-to-back launch (pw_head.hip)
-int pw_head_launch(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2, int N, int H, int W, hipStream_t s);
-int pw_zero_columns_launch(float* wp, float* bp, int K, int coutp, int c0, int c1, hipStream_t s);
-// ... and of the bf16 plan (pw_head_bf16.hip)
-int pw_head_bf16_launch(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2, int N, int H, int W, hipStream_t s);
-int pack_head_w2_bf16_launch(const float* w, const float* bias, int cout, int K, int col_off, void* wp, float* bp,
-                             hipStream_t s);
-int zero_head_columns_bf16_launch(void* wp, float* bp, int K, int c0, int c1, hipStream_t s);
-// conv.0 -> depthwise -> conv.2 of a stride-1 unit as one launch (unit_bf16.hip)
-int unit_bf16_fits(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int H, int W);
-int unit_bf16_launch(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int N, int H, int W, hipStream_t s);
-// column-mapped fp32 packing (pw_fused.hip): a layer's columns in the memory order of the runs it writes
-int pack_pw_cols_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map, int K,
-                        int ncols, const int32_t* col_map, int coutp, int col_off, float* wp, float* bp,
-                        hipStream_t s);
-// ... and of the bf16 plan (pw_fused_bf16.hip)
-int pw_fused_bf16_launch(const rtpose_pw_desc* d, int out_f32, int N, int H, int W, hipStream_t s);
-int pack_pw_bf16_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map, int K,
-                        int ncols, const int32_t* col_map, int coutp, int col_off, void* wp, float* bp,
-                        hipStream_t s);
 
 // w[C][1][3][3] (+bias[C]) -> wp[9][cphys], bp[cphys]; phys channel p reads logical pmap[p] (-1: zero)
 __global__ void pack_dw_kernel(const float* __restrict__ w, const float* __restrict__ b, int C,
