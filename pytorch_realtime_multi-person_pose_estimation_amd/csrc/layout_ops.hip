@@ -1234,6 +1234,7 @@ int rtpose_maxpool3x3s2_ceil(const float* in, const rtpose_layout* lin, float* o
     return fail(RTPOSE_E_INVAL, "maxpool3x3s2: channel slices must be 16-byte aligned, H,W >= 3");
   const int Ho = (H - 3 + 1) / 2 + 1, Wo = (W - 3 + 1) / 2 + 1;  // ceil((H-3)/2)+1
   const size_t total = (size_t)N * Ho * Wo * (C / 4);
+  if (!total) return 0;
   hipLaunchKernelGGL(maxpool3x3s2_ceil_kernel, dim3(nblocks(total, 256)), dim3(256), 0, as_stream(stream), in,
                      to_lay(lin), out, to_lay(lout), C, N, H, W, Ho, Wo);
   RTPOSE_HIP_CHECK(hipGetLastError());
@@ -1460,6 +1461,7 @@ int rtpose_maxpool3x3s2_ceil_bf16(const void* in, const rtpose_layout* lin, void
     return fail(RTPOSE_E_INVAL, "maxpool3x3s2_bf16: channel slices must be 16-byte aligned, H,W >= 3");
   const int Ho = (H - 3 + 1) / 2 + 1, Wo = (W - 3 + 1) / 2 + 1;
   const size_t total = (size_t)N * Ho * Wo * (C / 8);
+  if (!total) return 0;
   hipLaunchKernelGGL(maxpool3x3s2_ceil_bf16_kernel, dim3(nblocks(total, 256)), dim3(256), 0, as_stream(stream),
                      static_cast<const unsigned short*>(in), to_lay(lin), static_cast<unsigned short*>(out),
                      to_lay(lout), C, N, H, W, Ho, Wo);

@@ -3,9 +3,12 @@ CPU conv2d (the ATen arithmetic the reference's nn.Conv2d runs,
 lib/network/rtpose_vgg.py:23-35), called through the C ABI."""
 import ctypes as C
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import layout_restate as lr
 
 pytestmark = pytest.mark.gpu
 
@@ -93,6 +96,9 @@ def _run_conv(capi, dev, n, h, w, cin, cout, k, relu, pool, pad_in, pad_out, see
     total = obuf.abs().sum().item()
     inner = sum(o.abs().sum().item() for o in outs)
     assert abs(total - inner) <= 1e-3 * max(1.0, inner), "conv wrote outside its slice / into the gaps"
+    # the exact form: every word outside the written slices (lead, gaps, tail slack, the other channels) is still 0, bit for bit
+    written = [lr.index(lr.padded(cstride_out, ho, wo, pad_out, gi * cout + 1), n, ho, wo, cout) for gi in range(groups)]
+    assert lr.untouched(obuf.cpu().numpy().view(np.uint32), written, 0), "conv wrote outside its slice / into the gaps"
     return outs, refs
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import layout_restate as lr
 from conftest import PKG_NAME
 
 pytestmark = pytest.mark.gpu
@@ -220,6 +221,18 @@ def test_stem_and_pool_in_one_launch(capi, cuda, shape):
         capi.check(capi.lib.rtpose_stem_pool_nchw(capi.ptr(d[0]), capi.ptr(d[1]), capi.ptr(d[2]), capi.ptr(d[3]),
                                                   capi.ptr(d[4]), capi.ptr(out), C_.byref(lay), 24, n, H, W, bf16,
                                                   capi.current_stream()), "rtpose_stem_pool_nchw")
+        raw = out.cpu().numpy().view(np.uint16 if bf16 else np.uint32)
+        idx = lr.index(lr.padded(C, H2, W2, 1), n, H2, W2, 24)
+        if bf16:
+            # bracket test, every element: the conv sum lies within E = 30 * 2^-24 * S of the float64 value (27 products,
+            # the bias, the affine's roundings; S = |b| + sum |w| (|x s| + |t|)), ReLU, max-pool and the bf16 rounding are
+            # monotone, and the pool's maxima start from 0
+            v64, s64 = lr.stem_conv3x3_s2(x, scale, shift, w, b, True)
+            e64 = 30 * 2.0 ** -24 * s64
+            lo = torch.clamp(lr.maxpool3x3s2_ceil(v64 - e64), min=0.0).permute(0, 2, 3, 1).numpy().astype(np.float32)
+            hi = lr.maxpool3x3s2_ceil(v64 + e64).permute(0, 2, 3, 1).numpy().astype(np.float32)
+            k = lr.bf16_key(raw[idx])
+            assert np.all((lr.bf16_key(lr.bf16_rne(lo)) <= k) & (k <= lr.bf16_key(lr.bf16_rne(hi)))), (bf16, shape)
         if bf16:
             f = torch.zeros(npix * C, device=cuda)
             capi.check(capi.lib.rtpose_layout_bf16_to_f32(capi.ptr(out), C_.byref(lay), capi.ptr(f), C_.byref(lay), C, n,
@@ -233,3 +246,4 @@ def test_stem_and_pool_in_one_launch(capi, cuda, shape):
         tol = 1e-2 if bf16 else 1e-5
         assert (got[:, :24] - ref).abs().max().item() <= tol * max(1.0, ref.abs().max().item()), (bf16, shape)
         assert abs(out.abs().sum().item() - got.abs().sum().item()) <= 1e-3 * got.abs().sum().item()   # gaps untouched
+        assert lr.untouched(raw, idx, 0)      # the exact form: every word outside the 24 written channels is still 0, bit for bit
