@@ -134,6 +134,24 @@ typedef struct rtpose_conv_desc {
                    (nn.PReLU(num_parameters = cout), lib/network/openpose.py:56-63); `relu` must then be 0 and `pool` 0.
                    Taken by the fp32 rtpose_conv2d (k = 1, 3) and the fp32 k = 3 Winograd forms (F(2x2,3x3), F(4x4,3x3));
                    every other launcher refuses a non-NULL value (RTPOSE_E_INVAL).                                   */
+  /* ---- residual epilogue and input pre-activation: the pre-activation Bottleneck of the stacked hourglass
+   * (lib/network/rtpose_hourglass.py:9-46).  Taken by the fp32 rtpose_conv2d for k = 1, one group, no fused pool, no
+   * out_cmap and no PReLU; every other launcher (and rtpose_conv2d for k != 1) refuses a non-zero value of any of these
+   * fields (RTPOSE_E_INVAL).                                                                                          */
+  const float* residual; /* device base or NULL: out = conv + bias + residual, read through `lres` at the output pixel and
+                   at channel lres.choff + n for output channel n (`out += residual` of the Bottleneck, and the
+                   x + fc_(y) + ... hand-over between stacks); `relu` must be 0 - nothing follows the sum.  Every output
+                   element reads only its own residual element, so residual / lres may name the very slice out / lout
+                   name: the conv then adds into the buffer.                                                        */
+  const float* in_scale; /* device float[cin] or NULL (16-byte aligned), with in_shift: the conv reads                  */
+  const float* in_shift; /* relu(in_scale[c] * x + in_shift[c]) where it would read input channel c - an inference
+                   BatchNorm2d + ReLU in FRONT of the conv (`bn1` + `relu` of the Bottleneck), applied while the input
+                   tile is staged: no pass of its own over the map.  Both or neither.  The ReLU / bias of the epilogue
+                   are independent of it.                                                                           */
+  rtpose_layout lres;    /* layout of `residual`: lres.choff + cout <= lres.cstride                                    */
+  int32_t preact_cin;    /* real input channels of a pre-activated conv whose slice is padded to `cin`: channels
+                   preact_cin .. cin - 1 are staged as 0 whatever the buffer, in_scale and in_shift hold there (their
+                   taps stay zero taps).  0 = all `cin` channels are real.                                           */
 } rtpose_conv_desc;
 
 /* Launch one conv, or `ngroups` (<= 2) convs of identical geometry in one
@@ -171,6 +189,18 @@ int rtpose_pack_conv_first_bf16(const float* w_oihw, const float* bias, float* w
 int rtpose_conv_first_bf16(const float* x_nchw, const float* x_layout, const rtpose_layout* lx,
                            const float* w_packed, void* out_bf16, const rtpose_layout* lout, int relu, int N,
                            int H, int W, void* stream);
+
+/* ---- the stem of the stacked hourglass: nn.Conv2d(3, 64, 7, stride 2, padding 3) with `bn1` folded into filters and bias
+ * by the caller (+ nn.ReLU), lib/network/rtpose_hourglass.py:162-164 (csrc/hourglass_ops.hip).  The only strided conv of
+ * the library: H x W in, ceil(H / 2) x ceil(W / 2) out.  Reads the image like rtpose_conv_first (dense NCHW fp32, or with
+ * x_nchw = NULL a layout buffer with >= 3 channels per pixel; the zero padding is masked loads, no gap is needed) and writes
+ * 64 channels of `out` / `lout` (cstride and choff multiples of 4).  `w_packed` (rtpose_conv7x7_s2_packed_floats() floats)
+ * from rtpose_pack_conv7x7_s2(w [64,3,7,7], bias [64] or NULL).  H and W are the INPUT size. */
+size_t rtpose_conv7x7_s2_packed_floats(void);
+int rtpose_pack_conv7x7_s2(const float* w_oihw, const float* bias, float* w_packed, void* stream);
+int rtpose_conv7x7_s2(const float* x_nchw, const float* x_layout, const rtpose_layout* lx,
+                      const float* w_packed, float* out, const rtpose_layout* lout, int relu, int N,
+                      int H, int W, void* stream);
 
 /* ---- two pointwise convs back to back: nn.Conv2d(128, 128, 1) + nn.ReLU -> nn.Conv2d(128, cout2 <= 64, 1), the
  * Mconv6 / Mconv7 pair that ends every stage-2..6 branch (lib/network/rtpose_vgg.py:120-127), as ONE launch
@@ -431,6 +461,15 @@ int rtpose_maxpool2x2(const float* in, const rtpose_layout* lin, float* out,
                       const rtpose_layout* lout, int C, int N, int H, int W,
                       void* stream);
 
+/* out = up + Upsample(scale_factor 2, nearest)(low) as one pass: `up1 + self.upsample(low3)` of the stacked hourglass
+ * (lib/network/rtpose_hourglass.py:84-85; csrc/hourglass_ops.hip).  `up` and `out` are H x W maps, `low` is H/2 x W/2 (H and W
+ * even); C channels (a multiple of 4, as are every cstride and choff: 16-byte pieces) of each slice.  Each output element
+ * reads only its own `up` element, so out / lout may name the slice up / lup names.  The sum is up + low, bit for bit what
+ * the reference adds. */
+int rtpose_upsample2_add(const float* up, const rtpose_layout* lup, const float* low,
+                         const rtpose_layout* llow, float* out, const rtpose_layout* lout, int C,
+                         int N, int H, int W, void* stream);
+
 /* NCHW dense fp32 -> layout (channels [0,C) of the slice; extra channels of
  * the slice up to cpad are written as zero). */
 int rtpose_nchw_to_layout(const float* src_nchw, float* dst,
@@ -684,6 +723,45 @@ int rtpose_net_load_prelu(rtpose_net* net, int idx, const float* slope, void* st
 /* Host-only: 1 if conv `idx` is followed by a PReLU (its state_dict prefix, e.g. "feature_extractor.22" or
  * "l2_stages.0.Mconv1_0.MPrelu", goes to `name`), 0 if not, negative on a bad index. */
 int rtpose_net_prelu_info(const rtpose_net* net, int idx, char* name, int name_cap);
+
+/* ------------------------------------------------------------------------
+ * 3a'. The stacked hourglass (lib/network/rtpose_hourglass.py), a third topology of the same executor:
+ *   hg(num_stacks, num_blocks, paf_classes, ht_classes) -> rtpose_hourglass_create + rtpose_net_load_conv per conv
+ *                                                          + rtpose_net_load_preact per Bottleneck
+ *   HourglassNet.forward (eval)                         -> rtpose_net_forward   (rtpose_hourglass.py:162-189)
+ *
+ * The handle is an rtpose_net, as above.  fp32 only, inference only.  H and W must be multiples of 64: the sizes the
+ * reference itself accepts (`out = up1 + up2`, rtpose_hourglass.py:85, fails for any other).  Conv index order == the
+ * order of the nn.Conv2d in the reference's state_dict: "conv1", "layer1.0.conv1", "layer1.0.conv2", "layer1.0.conv3",
+ * "layer1.0.downsample.0", ..., "hg.3.hg.2.1.0.conv3", ..., "res.0.0.conv1", "fc.0.0", "score_ht.0", "score_paf.0",
+ * "fc_.0", "paf_score_.0", "ht_score_.0" (393 for hg(8, 1, 38, 19)).
+ * BatchNorm2d (running statistics; scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale) enters
+ * through the host in two ways:
+ *   - a BatchNorm that FOLLOWS a conv (bn2 after conv1, bn3 after conv2, fc.i.1 after fc.i.0, bn1 after the stem) is
+ *     folded into that conv: rtpose_net_load_conv gets w * scale[cout] and b * scale + shift, and the conv runs with a ReLU;
+ *   - `bn1` of a Bottleneck precedes its conv1 and follows a residual sum several modules read: its (scale, shift) go to
+ *     rtpose_net_load_preact of that conv1 and are applied where the conv stages its input (rtpose_conv_desc.in_scale).
+ *   rtpose_net_preact_info names that BatchNorm ("layer1.0.bn1"), as rtpose_net_prelu_info names a PReLU.
+ * rtpose_net_read_output(which): 0 = score_paf, 1 = score_ht of the LAST stack (what forward returns), at stride 4;
+ *   2 + 2 s / 3 + 2 s = score_paf / score_ht of stack s, kept only under keep_intermediates.
+ * rtpose_net_output_view(0 / 1): the last stack's maps in place.
+ * ---------------------------------------------------------------------- */
+typedef struct rtpose_hourglass_options {
+  uint32_t struct_bytes; /* sizeof(rtpose_hourglass_options) of the caller         */
+  int32_t num_stacks;    /* 1..64                                                  */
+  int32_t num_blocks;    /* Bottlenecks per residual module, 1..16                 */
+  int32_t paf_classes;   /* 1..64                                                  */
+  int32_t ht_classes;    /* 1..64                                                  */
+  int32_t winograd3;     /* as rtpose_net_options.winograd3 (the 3x3 conv2 of every Bottleneck) */
+  float amp_limit;       /* as rtpose_net_options.amp_limit                        */
+} rtpose_hourglass_options;
+int rtpose_hourglass_create(int N, int H, int W, const rtpose_hourglass_options* opt, rtpose_net** out);
+/* (scale, shift) (device float[cin] each) of the BatchNorm2d + ReLU in front of conv `idx`; RTPOSE_E_INVAL for a conv
+ * without one. */
+int rtpose_net_load_preact(rtpose_net* net, int idx, const float* scale, const float* shift, void* stream);
+/* Host-only: 1 if conv `idx` reads its input through a BatchNorm2d + ReLU (the BatchNorm's state_dict prefix goes to
+ * `name`), 0 if not, negative on a bad index. */
+int rtpose_net_preact_info(const rtpose_net* net, int idx, char* name, int name_cap);
 
 /* ------------------------------------------------------------------------
  * 3b. The ShuffleNetV2 x1.0 pose network (lib/network/rtpose_shufflenetV2.py:80-148,

@@ -43,7 +43,8 @@ class ConvDesc(C.Structure):
                 ("out", C.c_void_p), ("lin", Layout), ("lout", Layout), ("cin", C.c_int32),
                 ("cout", C.c_int32), ("k", C.c_int32), ("relu", C.c_int32), ("pool", C.c_int32),
                 ("out_cmap", C.c_void_p), ("wino_m", C.c_int32), ("in_plane_pixels", C.c_int32),
-                ("out_plane_pixels", C.c_int32), ("prelu", C.c_void_p)]
+                ("out_plane_pixels", C.c_int32), ("prelu", C.c_void_p), ("residual", C.c_void_p),
+                ("in_scale", C.c_void_p), ("in_shift", C.c_void_p), ("lres", Layout), ("preact_cin", C.c_int32)]
 
 
 class NetOptions(C.Structure):
@@ -65,6 +66,17 @@ class OpenPoseOptions(C.Structure):
     @classmethod
     def make(cls, l2_stages, l1_stages, paf_channels, heat_channels, winograd3=-1, amp_limit=0.0):
         return cls(C.sizeof(cls), l2_stages, l1_stages, paf_channels, heat_channels, winograd3, amp_limit)
+
+
+class HourglassOptions(C.Structure):
+    """rtpose_hourglass_options: topology and fp32 3x3 arithmetic of a stacked-hourglass plan (header §3a')."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("num_stacks", C.c_int32), ("num_blocks", C.c_int32),
+                ("paf_classes", C.c_int32), ("ht_classes", C.c_int32), ("winograd3", C.c_int32),
+                ("amp_limit", C.c_float)]
+
+    @classmethod
+    def make(cls, num_stacks, num_blocks, paf_classes, ht_classes, winograd3=-1, amp_limit=0.0):
+        return cls(C.sizeof(cls), num_stacks, num_blocks, paf_classes, ht_classes, winograd3, amp_limit)
 
 
 class PwDesc(C.Structure):
@@ -121,6 +133,10 @@ _SIGS = {
     "rtpose_pack_conv_first": (_i, [_vp, _vp, _vp, _vp]),
     "rtpose_conv_first": (_i, [_vp, _vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_conv_first_planes": (_i, [_vp, _vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
+    "rtpose_conv7x7_s2_packed_floats": (_sz, []),
+    "rtpose_pack_conv7x7_s2": (_i, [_vp, _vp, _vp, _vp]),
+    "rtpose_conv7x7_s2": (_i, [_vp, _vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _vp]),
+    "rtpose_upsample2_add": (_i, [_vp, _LP, _vp, _LP, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_pack_conv_first_bf16": (_i, [_vp, _vp, _vp, _vp]),
     "rtpose_conv_first_bf16": (_i, [_vp, _vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_conv2d_winograd_fits": (_i, [C.POINTER(ConvDesc), _i, _i, _i]),
@@ -173,6 +189,9 @@ _SIGS = {
     "rtpose_openpose_create": (_i, [_i, _i, _i, C.POINTER(OpenPoseOptions), C.POINTER(_vp)]),
     "rtpose_net_load_prelu": (_i, [_vp, _i, _vp, _vp]),
     "rtpose_net_prelu_info": (_i, [_vp, _i, C.c_char_p, _i]),
+    "rtpose_hourglass_create": (_i, [_i, _i, _i, C.POINTER(HourglassOptions), C.POINTER(_vp)]),
+    "rtpose_net_load_preact": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "rtpose_net_preact_info": (_i, [_vp, _i, C.c_char_p, _i]),
     "rtpose_net_conv_numerics": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(C.c_float), _vp]),
     "rtpose_net_device_status": (_i, [_vp, C.POINTER(_i), _vp]),
     "rtpose_net_device_status_async": (_i, [_vp, _vp, _vp]),

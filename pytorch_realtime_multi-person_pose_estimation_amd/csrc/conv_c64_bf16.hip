@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
 
 // 1: the launch below takes the conv (else the generic kernel does)
 int conv_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int out_f32, int split) {
-  if (!d || ngroups != 1 || out_f32 || split || d[0].prelu) return 0;
+  if (!d || ngroups != 1 || out_f32 || split || d[0].prelu || desc_has_residual(d, 1) || desc_has_preact(d, 1)) return 0;
   const rtpose_conv_desc& c = d[0];
   if (c.k != 3 || c.cin != 64 || c.cout < 64 || (c.cout % 64) || c.out_cmap || c.in_plane_pixels || c.out_plane_pixels) return 0;
   if (!slice_ok(c.lin, 64, 8) || !slice_ok(c.lout, c.cout, 8) || !gap_covers(c.lin, H, W, 1)) return 0;
@@ -312,6 +312,9 @@ int conv_c64_bf16_fits(const rtpose_conv_desc* d, int ngroups, int N, int H, int
 int conv_c64_bf16_launch(const rtpose_conv_desc* d, int N, int H, int W, hipStream_t s) {
   using namespace c64;
   if (desc_has_prelu(d, 1)) return fail(RTPOSE_E_INVAL, "conv_c64_bf16: no PReLU epilogue (rtpose_conv_desc.prelu)");
+  if (desc_has_residual(d, 1)) return fail(RTPOSE_E_INVAL, "conv_c64_bf16: no residual epilogue (rtpose_conv_desc.residual)");
+  if (desc_has_preact(d, 1))
+    return fail(RTPOSE_E_INVAL, "conv_c64_bf16: no input pre-activation (rtpose_conv_desc.in_scale / in_shift / preact_cin)");
   if (!conv_c64_bf16_fits(d, 1, N, H, W, 0, 0) || N <= 0 || H <= 0 || W <= 0)
     return fail(RTPOSE_E_INVAL, "conv_c64_bf16: needs a 3x3 conv of 64 bf16 input channels into 16-byte aligned "
                                 "slices (no out_cmap; a slice that exceeds cstride is refused)");

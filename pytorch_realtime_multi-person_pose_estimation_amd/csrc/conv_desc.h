@@ -32,6 +32,8 @@ struct ConvSpec {
   bool planes;      // channel-plane slices taken (the form checks their rules itself)
   bool prelu;       // PReLU epilogue taken
   bool out_extent;  // the output slice counts channels: lout.choff + cout <= lout.cstride (pixel-major, no out_cmap)
+  bool residual;    // residual epilogue taken (the form checks its rules itself)
+  bool preact;      // input pre-activation taken (likewise)
 };
 
 inline bool desc_has_prelu(const rtpose_conv_desc* d, int ngroups) {
@@ -42,6 +44,17 @@ inline bool desc_has_prelu(const rtpose_conv_desc* d, int ngroups) {
 inline bool desc_has_planes(const rtpose_conv_desc* d, int ngroups) {
   for (int g = 0; d && g < ngroups && g < 2; ++g)
     if (d[g].in_plane_pixels || d[g].out_plane_pixels) return true;
+  return false;
+}
+
+inline bool desc_has_residual(const rtpose_conv_desc* d, int ngroups) {
+  for (int g = 0; d && g < ngroups && g < 2; ++g)
+    if (d[g].residual) return true;
+  return false;
+}
+inline bool desc_has_preact(const rtpose_conv_desc* d, int ngroups) {
+  for (int g = 0; d && g < ngroups && g < 2; ++g)
+    if (d[g].in_scale || d[g].in_shift || d[g].preact_cin) return true;
   return false;
 }
 
@@ -60,6 +73,12 @@ inline int check_conv_features(const rtpose_conv_desc* d, int ngroups, const Con
       if (!d[i].prelu || d[i].relu || d[i].pool)
         return fail(RTPOSE_E_INVAL, "%s: a PReLU launch has slopes in every group, relu = 0 and no fused pool", sp.who);
   }
+  if (!sp.residual && desc_has_residual(d, ngroups))
+    return fail(RTPOSE_E_INVAL, "%s: no residual epilogue (rtpose_conv_desc.residual is taken by the fp32 rtpose_conv2d "
+                                "for k = 1 only; zero-initialise descriptors)", sp.who);
+  if (!sp.preact && desc_has_preact(d, ngroups))
+    return fail(RTPOSE_E_INVAL, "%s: no input pre-activation (rtpose_conv_desc.in_scale / in_shift / preact_cin are taken "
+                                "by the fp32 rtpose_conv2d for k = 1 only; zero-initialise descriptors)", sp.who);
   return 0;
 }
 
@@ -90,6 +109,9 @@ inline int check_conv_layouts(const rtpose_conv_desc* d, int ngroups, int N, int
 // slices inside their cstride.  relu2: d2 may have a ReLU (the same in every branch), else it has none.
 inline bool conv_pair_fits(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int ngroups, int align, bool relu2) {
   if (!d1 || !d2 || ngroups < 1 || ngroups > 2 || desc_has_prelu(d1, ngroups) || desc_has_prelu(d2, ngroups)) return false;
+  if (desc_has_residual(d1, ngroups) || desc_has_residual(d2, ngroups) || desc_has_preact(d1, ngroups) ||
+      desc_has_preact(d2, ngroups))
+    return false;
   for (int g = 0; g < ngroups; ++g) {
     const rtpose_conv_desc &a = d1[g], &b = d2[g];
     if (a.k != 1 || b.k != 1 || a.cin != 128 || (a.cout != 128 && a.cout != 512) || a.cout != d1[0].cout ||

@@ -82,6 +82,29 @@ struct ConvArgsP : ConvArgs {
 template <bool PR>
 using ConvArgsT = typename std::conditional<PR, ConvArgsP, ConvArgs>::type;
 
+// Residual epilogue and input pre-activation (rtpose_conv_desc.residual / in_scale / in_shift; k = 1, one group): the
+// pre-activation Bottleneck of the stacked hourglass.  A kernel of its own (conv_mfma_f32_x) with the operands behind the
+// arguments the other instantiations read, for the same reason as ConvArgsP.
+struct ConvX {
+  const float* res;       // NULL: no residual
+  int res_cstride, res_choff, res_ws, res_hs, res_lead;
+  const float* in_scale;  // NULL: no pre-activation; float[cin], 16-byte aligned
+  const float* in_shift;
+  int pre_cin;            // input channels >= pre_cin are staged as 0
+};
+struct ConvArgsX : ConvArgs {
+  ConvX x;
+};
+// relu(scale * x + shift) of one 16-byte piece with `left` real channels from its first one: the others are staged as 0
+// whatever the buffer and the vectors hold there (their filter taps are zero, and 0 * x has to be 0)
+__device__ __forceinline__ float4 preact4(float4 v, const float4 sc, const float4 sh, const int left) {
+  v.x = left > 0 ? fmaxf(sc.x * v.x + sh.x, 0.f) : 0.f;
+  v.y = left > 1 ? fmaxf(sc.y * v.y + sh.y, 0.f) : 0.f;
+  v.z = left > 2 ? fmaxf(sc.z * v.z + sh.z, 0.f) : 0.f;
+  v.w = left > 3 ? fmaxf(sc.w * v.w + sh.w, 0.f) : 0.f;
+  return v;
+}
+
 constexpr int kBM = 128;
 // 1x1 convs: CK-channel sub-chunks per LDS buffer (see conv_tile; 4: -20 % on the 1x1 layers)
 constexpr int kTB1x1 = 1;
@@ -111,9 +134,12 @@ __device__ __forceinline__ void tile_local_yx(int ml, int tw_log2, int& ty, int&
 // NF = 32-column N fragments per wave: 1 -> block tile 128 x 64, 2 -> 128 x 128 (wave tile
 // 64 x 64).  NF = 2 halves the B (weight) and A (LDS) operand bytes per MFMA; measured, the B
 // loads cost ~4.6 % of the forward and half of them ~2 %.
-template <int KS, int CK, int MODE, int NBUF, int MF, int NF, bool PR = false>
+// XT: the residual / pre-activation instantiation (KS = 1, NBUF = 1; X != nullptr)
+template <int KS, int CK, int MODE, int NBUF, int MF, int NF, bool PR = false, bool XT = false>
 __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g, const int m0_arg,
-                                          const int ntile, float* smem, const float* prelu = nullptr) {
+                                          const int ntile, float* smem, const float* prelu = nullptr,
+                                          const ConvX* X = nullptr) {
+  static_assert(!XT || (KS == 1 && NBUF == 1 && !PR), "residual / pre-activation: the single-buffered 1x1 kernel");
   constexpr int P = KS / 2;
   constexpr int BMT = 64 * MF;  // pixels per block tile
   constexpr int CG = CK / 4;  // 16-byte channel groups per chunk
@@ -268,6 +294,22 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
   auto fill_halo = [&](const float* src, int ntaps) {  // ntaps: sub-chunks that exist in this buffer
     const bool ch_ok = pj < ntaps * CG;
     constexpr int FD = (KS == 1 && kTB1x1 > 1) ? 8 : 4;  // loads in flight per thread
+    // pre-activation: this thread's pieces are 4 fixed channels of the chunk, so their scale / shift are fetched once per
+    // chunk and applied between the load and the LDS write.  Gap pixels of a strip become relu(shift) in LDS: no A fragment
+    // of a 1x1 conv reads them (a row of the product is one real pixel).
+    float4 psc = make_float4(0.f, 0.f, 0.f, 0.f), psh = psc;
+    int pc0 = 0;
+    bool pre = false;
+    if constexpr (XT) {
+      pre = X->in_scale != nullptr;
+      if (pre && ch_ok) {
+        pc0 = (int)(src - in_base) + pj * 4;
+        psc = gload4(X->in_scale + pc0);
+        psh = gload4(X->in_shift + pc0);
+        pc0 = X->pre_cin - pc0;  // real channels left from this piece's first one
+      }
+    }
+    (void)pre;
     for (int set0 = 0; set0 < nsets; set0 += FD) {
       float4 t[FD];
 #pragma unroll
@@ -275,7 +317,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
         if (ch_ok && set0 + u < nsets && (set0 + u) * 256 + tid < np_total) t[u] = gload4(src + piece_goff(set0 + u));
 #pragma unroll
       for (int u = 0; u < FD; ++u)
-        if (ch_ok && set0 + u < nsets && (set0 + u) * 256 + tid < np_total) smem4[piece_loff(set0 + u)] = t[u];
+        if (ch_ok && set0 + u < nsets && (set0 + u) * 256 + tid < np_total) {
+          if constexpr (XT) {
+            if (pre) t[u] = preact4(t[u], psc, psh, pc0);
+          }
+          smem4[piece_loff(set0 + u)] = t[u];
+        }
     }
   };
   const int nbig = (nchunks + TB - 1) / TB;  // LDS buffer fills per block
@@ -520,6 +567,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
           if (A.relu) v = fmaxf(v, 0.f);
           if constexpr (PR) v = prelu1(v, slope[fn]);
           if (ok && col_ok) {
+            if constexpr (XT) {
+              // the residual element of this output element alone (it may be the element about to be overwritten)
+              if (X->res)
+                v += X->res[((size_t)X->res_lead + (size_t)(n * X->res_hs + y) * X->res_ws + x) * X->res_cstride +
+                            X->res_choff + ncolf];
+            }
             const size_t q = (size_t)g.out_lead + (size_t)(n * g.out_hs + y) * g.out_ws + x;
             out_base[q * g.out_cstride] = v;
           }
@@ -593,6 +646,33 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 4 : 2) void conv_mfma_f32(const Co
   } else {
     const int m0 = mt * kBM + ((L - A.nbig) & 1) * (kBM / 2);
     if (m0 < A.M) conv_tile<KS, CK, MODE, NBUF, 1, NF, PR>(A, A.g[grp], m0, nt, smem, prelu);
+  }
+}
+
+// The residual / pre-activation 1x1 kernel: one group, no dephasing, the same id order as conv_mfma_f32.
+template <int CK, int MODE>
+__global__ __launch_bounds__(256, 4) void conv_mfma_f32_x(const ConvArgsX A) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int L = blockIdx.x;
+  const bool small = MODE == 0 && L >= A.nbig;
+  const int bi = small ? A.nbig + ((L - A.nbig) >> 1) : L;
+  int mt, nt;
+  if (A.xcd_remap) {
+    const int xcd = bi & 7, j = bi >> 3;
+    nt = j % A.ncombo;
+    mt = (j / A.ncombo) * 8 + xcd;
+  } else {
+    mt = bi % A.mtiles;
+    nt = bi / A.mtiles;
+  }
+  if (mt >= A.mtiles) return;  // padding ids of the remapped order
+  if (MODE == 1) {
+    conv_tile<1, CK, MODE, 1, 2, 1, false, true>(A, A.g[0], mt, nt, smem, nullptr, &A.x);
+  } else if (!small) {
+    conv_tile<1, CK, MODE, 1, 2, 1, false, true>(A, A.g[0], mt * kBM, nt, smem, nullptr, &A.x);
+  } else {
+    const int m0 = mt * kBM + ((L - A.nbig) & 1) * (kBM / 2);
+    if (m0 < A.M) conv_tile<1, CK, MODE, 1, 1, 1, false, true>(A, A.g[0], m0, nt, smem, nullptr, &A.x);
   }
 }
 
@@ -701,12 +781,35 @@ static int launch_inst(const ConvArgsT<PR>& a, dim3 grid, size_t lds, hipStream_
 }
 
 int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
-  const ConvSpec spec = {"conv2d", 4, 1, true, false, true, true};
+  const ConvSpec spec = {"conv2d", 4, 1, true, false, true, true, true, true};
   if (int rc = check_conv_features(d, ngroups, spec)) return rc;
   const rtpose_conv_desc& d0 = d[0];
   if (d0.k != 1 && d0.k != 3 && d0.k != 7) return fail(RTPOSE_E_INVAL, "conv2d: k must be 1, 3 or 7");
   if (d0.prelu && (d0.k == 7 || d[0].out_cmap || (ngroups > 1 && d[1].out_cmap)))
     return fail(RTPOSE_E_INVAL, "conv2d: the PReLU epilogue exists for k = 1 and 3 without out_cmap");
+  const bool has_res = desc_has_residual(d, ngroups), has_pre = desc_has_preact(d, ngroups);
+  if (has_res || has_pre) {
+    const char* what = has_res ? "residual epilogue (rtpose_conv_desc.residual)"
+                               : "input pre-activation (rtpose_conv_desc.in_scale / in_shift)";
+    if (d0.k != 1)
+      return fail(RTPOSE_E_INVAL, "conv2d: the %s exists for k = 1 only (a halo's zero padding would become relu(shift); "
+                                  "a k x k residual has no kernel)", what);
+    if (ngroups != 1 || d0.pool || d0.out_cmap || d0.prelu)
+      return fail(RTPOSE_E_INVAL, "conv2d: the %s takes one group without fused pool, out_cmap or PReLU", what);
+    if (has_res) {
+      if (d0.relu) return fail(RTPOSE_E_INVAL, "conv2d: the residual epilogue has no activation after the sum (relu must be 0)");
+      if (!slice_inside(d0.lres, d0.cout) || d0.lres.cstride <= 0 || d0.lres.choff < 0 || H > d0.lres.hs || W > d0.lres.ws)
+        return fail(RTPOSE_E_INVAL, "conv2d: residual slice (lres) exceeds cstride or is smaller than the map");
+    }
+    if (has_pre) {
+      if (!d0.in_scale || !d0.in_shift)
+        return fail(RTPOSE_E_INVAL, "conv2d: the input pre-activation needs both in_scale and in_shift");
+      if ((reinterpret_cast<uintptr_t>(d0.in_scale) | reinterpret_cast<uintptr_t>(d0.in_shift)) % 16)
+        return fail(RTPOSE_E_INVAL, "conv2d: in_scale and in_shift (input pre-activation) must be 16-byte aligned");
+      if (d0.preact_cin < 0 || d0.preact_cin > d0.cin)
+        return fail(RTPOSE_E_INVAL, "conv2d: preact_cin (input pre-activation) must lie in 0 .. cin");
+    }
+  }
   if (d0.cin % 8 != 0 || d0.cin <= 0) return fail(RTPOSE_E_INVAL, "conv2d: cin must be a multiple of 8");
   if (int rc = check_conv_layouts(d, ngroups, N, H, W, spec)) return rc;
   ConvArgs a;
@@ -753,6 +856,33 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
     if (total <= n_cu) a.nbig = 0;
   }
   dim3 grid((unsigned)(a.nbig + 2 * (ids - a.nbig)), 1, 1);
+  if (has_res || has_pre) {
+    ConvArgsX ax;
+    static_cast<ConvArgs&>(ax) = a;
+    memset(&ax.x, 0, sizeof(ax.x));
+    if (has_res) {
+      ax.x.res = d0.residual;
+      ax.x.res_cstride = d0.lres.cstride;
+      ax.x.res_choff = d0.lres.choff;
+      ax.x.res_ws = d0.lres.ws;
+      ax.x.res_hs = d0.lres.hs;
+      ax.x.res_lead = d0.lres.lead;
+    }
+    if (has_pre) {
+      ax.x.in_scale = d0.in_scale;
+      ax.x.in_shift = d0.in_shift;
+      ax.x.pre_cin = d0.preact_cin ? d0.preact_cin : d0.cin;
+    }
+#define RTPOSE_CONV_CASE_X(CK_, MODE_)    \
+  if (pl.ck == CK_ && pl.mode == MODE_) \
+    return launch_kernel<conv_mfma_f32_x<CK_, MODE_>>(grid, dim3(256), pl.lds_bytes, 150 * 1024, s, ax);
+    RTPOSE_CONV_CASE_X(16, 0)
+    RTPOSE_CONV_CASE_X(16, 1)
+    RTPOSE_CONV_CASE_X(8, 0)
+    RTPOSE_CONV_CASE_X(8, 1)
+#undef RTPOSE_CONV_CASE_X
+    return fail(RTPOSE_E_INVAL, "conv2d: no residual / pre-activation kernel instance for ck=%d mode=%d", pl.ck, pl.mode);
+  }
   if (d0.prelu) {
     ConvArgsP ap;
     static_cast<ConvArgs&>(ap) = a;

@@ -231,6 +231,10 @@ int conv_tail_bf16_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2
   using namespace tailb;
   if (desc_has_prelu(d1, ngroups) || desc_has_prelu(d2, ngroups))
     return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: no PReLU epilogue (rtpose_conv_desc.prelu)");
+  if (desc_has_residual(d1, ngroups) || desc_has_residual(d2, ngroups))
+    return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: no residual epilogue (rtpose_conv_desc.residual)");
+  if (desc_has_preact(d1, ngroups) || desc_has_preact(d2, ngroups))
+    return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: no input pre-activation (rtpose_conv_desc.in_scale / in_shift / preact_cin)");
   if (!conv_tail_bf16_fits(d1, d2, ngroups))
     return fail(RTPOSE_E_INVAL, "conv1x1_pair_bf16: not a 128 -> 128 | 512 (ReLU) -> <= 64 pair of 1x1 convs on 16-byte "
                                 "aligned bf16 slices (no out_cmap; a slice that exceeds cstride is refused)");

@@ -836,6 +836,7 @@ static bool wino_m_valid(const rtpose_conv_desc* d) {
 int rtpose_conv2d_winograd_fits(const rtpose_conv_desc* d, int N, int H, int W) {
   if (!d || !wino_m_valid(d)) return 0;
   if (d->prelu && (d->k != 3 || d->pool || d->relu)) return 0;  // the PReLU epilogue: k = 3 forms, no ReLU, no fused pool
+  if (rtpose::desc_has_residual(d, 1) || rtpose::desc_has_preact(d, 1)) return 0;  // taken by the direct k = 1 kernel only
   return rtpose::conv2d_winograd_fits(d->k, d->cin, d->cout, d->pool, N, H, W, d->lin.hs, d->wino_m == 2 ? 0 : d->wino_m);
 }
 

@@ -20,6 +20,14 @@ int conv_first_launch(const float* x_nchw, const float* x_lay, const rtpose_layo
                       const rtpose_layout* lo, int out_plane_pixels, int relu, int N, int H, int W, hipStream_t s,
                       int out_bf16);
 
+// ---- stacked hourglass: the 7x7 stride-2 stem and up1 + upsample2(low3) (hourglass_ops.hip) ----
+size_t conv7x7_s2_packed_floats();
+int conv7x7_s2_pack_launch(const float* w_oihw, const float* bias, float* wp, hipStream_t s);
+int conv7x7_s2_launch(const float* x_nchw, const float* x_lay, const rtpose_layout* lx, const float* wp, float* out,
+                      const rtpose_layout* lo, int relu, int N, int H, int W, hipStream_t s);
+int upsample2_add_launch(const float* up, const rtpose_layout* lup, const float* low, const rtpose_layout* llow, float* out,
+                         const rtpose_layout* lout, int C, int N, int H, int W, hipStream_t s);
+
 // ---- Winograd forms: F(2x2,3x3) and the form dispatch (conv_wino.hip) ----
 int conv2d_winograd_fits(int k, int cin, int cout, int pool, int N, int H, int W, int hs, int fm);
 int conv2d_wino_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s);

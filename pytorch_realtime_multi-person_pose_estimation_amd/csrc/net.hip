@@ -21,6 +21,12 @@
 // epilogues on its last three convs, dense-block stages whose three convs write
 // slices of one 3 x inner buffer, and stage heads that write the next stage's
 // input buffer in place.
+//
+// A third topology, the stacked hourglass (lib/network/rtpose_hourglass.py; rtpose_hourglass_create,
+// build_plan_hourglass): a 7x7 stride-2 stem, pre-activation Bottlenecks whose `bn1` + ReLU is applied while the 1x1
+// conv1 stages its input and whose `out += residual` is the epilogue of the 1x1 conv3 (csrc/conv_mfma.hip), 2x2 max-pools
+// and `up1 + upsample(low3)` launches (csrc/hourglass_ops.hip).  Every other BatchNorm follows a conv and reaches the
+// plan folded into that conv's filters and bias by the host.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -85,11 +91,19 @@ struct ConvW {
   bool has_prelu = false;
   size_t pr_off = 0;
   std::string prelu_name;
+  // stacked hourglass: the 7x7 stride-2 stem (its own kernel, packing at w_off_first, csrc/hourglass_ops.hip), and the
+  // BatchNorm2d + ReLU in FRONT of a 1x1 conv (scale at pa_off, shift round_up(cin_packed, 64) floats behind it;
+  // state_dict prefix of the BatchNorm preact_name)
+  bool stem = false;
+  bool has_preact = false;
+  size_t pa_off = 0;
+  std::string preact_name;
   bool packed(Form f) const { return w_off[f] != kNotPacked; }
 };
 
 // OP_SAVE: the copy of a stage's maps into its record, run only under keep_intermediates
-enum OpKind { OP_INPUT, OP_CONV, OP_POOL, OP_COPY, OP_SAVE, OP_TAIL };
+// OP_UPADD: out_buf[0] = in_buf[0] + upsample2(in_buf[1]) (stacked hourglass)
+enum OpKind { OP_INPUT, OP_CONV, OP_POOL, OP_COPY, OP_SAVE, OP_TAIL, OP_UPADD };
 
 struct Op {
   OpKind kind;
@@ -102,6 +116,7 @@ struct Op {
   int in_buf[2] = {-1, -1}, out_buf[2] = {-1, -1};
   int in_choff[2] = {0, 0}, out_choff[2] = {0, 0};
   int relu = 0, pool = 0;
+  int res_buf = -1, res_choff = 0;  // conv: the residual its epilogue adds (rtpose_conv_desc.residual)
   int out_f32 = 0;          // bf16 plans: this conv writes fp32 (the final stage heads)
   // pool / copy
   int C = 0;
@@ -147,7 +162,11 @@ struct rtpose_net {
   // copy each stage's output to op_save[stage] when keep_intermediates is set.  catmap_host, uploaded at bind: packed
   // input channel -> source channel of the filters that read a concat buffer (rtpose_vgg: cat([L1, L2, out1]);
   // OpenPose_Model: cat([features, heat, paf]) of the l1 stages 1..), -1 = zero taps.
+  // 2 = stacked hourglass (rtpose_hourglass_create): the score maps of the stack that ran last live in cat_buf[0] = [PAF |
+  // pad to 8 | heat at hg_heat_off | pad to 8] (the pads are never written: the 1x1 convs that read the maps back read them
+  // as zero taps), every stack's are copied to op_save[stack] under keep_intermediates.  H3 x W3 is the stride-4 map.
   int topo = 0;
+  int hg_stacks = 0, hg_blocks = 0, hg_paf = 0, hg_heat = 0, hg_heat_off = 0;
   int op_l2 = 0, op_l1 = 0, op_paf = 0, op_heat = 0, op_heat_off = 0;
   std::vector<int> op_save;
   std::vector<int32_t> catmap_host;
@@ -367,7 +386,7 @@ void add_conv_op(rtpose_net* n, int H, int W, int ngroups, const int* conv_idx, 
   }
   o.flops = fl;
   o.ks = n->convs[conv_idx[0]].k;
-  if (n->convs[conv_idx[0]].first) n->conv1_op = (int)n->ops.size();
+  if (n->convs[conv_idx[0]].first || n->convs[conv_idx[0]].stem) n->conv1_op = (int)n->ops.size();
   n->ops.push_back(o);
 }
 
@@ -685,6 +704,186 @@ void build_plan_openpose(rtpose_net* n) {
   }
 }
 
+// The stacked hourglass, hg(num_stacks, num_blocks, paf_classes, ht_classes) of rtpose_hourglass.py:201.  Weights in the
+// reference's state_dict order: conv1, layer1..3, hg (every stack), res, fc, score_ht, score_paf, fc_, paf_score_,
+// ht_score_ (the order HourglassNet.__init__ registers them in, :126-133); inside a Bottleneck conv1, conv2, conv3,
+// downsample.0.
+//
+// Buffers.  X (256 channels, stride 4) is the running `x` of the stacks: layer2 writes it, layer3 and every hand-over add
+// into it in place.  Depth level n of an hourglass (4 at stride 4 .. 1 at stride 32) owns UP[n], where hg[n-1][0] writes
+// up1 and the upsample-add leaves the level's result in place, and L[n-1], where the pooled input becomes low1 in place;
+// a level's input (X, or L[n] of the level above) is last read by its pool, so up1 survives until its add and nothing
+// else has to.  A Bottleneck without downsample whose input nobody else needs runs in place (conv3 adds into the buffer
+// its input lives in); one with downsample runs it first and conv3 on top.  T1[r] / T2[r] hold conv1's and conv2's
+// output per resolution.  Nothing is read through taps an earlier forward may have left non-finite: every channel count
+// but the score maps' is a multiple of 8, the score buffer's pad channels are never written, and the gap of T1 (the only
+// buffer a 3x3 conv reads) is never written either.
+//
+// The hand-over x + fc_(y) + paf_score_(score_paf) + ht_score_(score_ht) is three residual-accumulating 1x1 launches into
+// X: each conv keeps its own index, filters and bias as the state_dict has them (one K = 320 conv would need a packing
+// over three state_dict entries), and the two small ones are 4 % of fc_'s work.
+struct Bneck {
+  int c1, c2, c3, ds;
+};
+
+void add_preact(rtpose_net* n, int conv, const std::string& name) {
+  ConvW& c = n->convs[conv];
+  c.has_preact = true;
+  c.preact_name = name;
+  c.pa_off = n->wt_floats;
+  n->wt_floats += 2 * round_up((size_t)c.cin_packed, 64);
+}
+
+Bneck add_bneck_w(rtpose_net* n, const std::string& pre, int cin, int planes, bool ds) {
+  Bneck b;
+  b.c1 = add_conv_w(n, pre + ".conv1", planes, cin, 1, false);
+  add_preact(n, b.c1, pre + ".bn1");
+  b.c2 = add_conv_w(n, pre + ".conv2", planes, planes, 3, false);
+  b.c3 = add_conv_w(n, pre + ".conv3", 2 * planes, planes, 1, false);
+  b.ds = ds ? add_conv_w(n, pre + ".downsample.0", 2 * planes, cin, 1, false) : -1;
+  return b;
+}
+
+// the num_blocks Bottlenecks of one nn.Sequential (_make_residual): 2 * planes -> 2 * planes
+std::vector<Bneck> add_seq_w(rtpose_net* n, const std::string& pre, int blocks) {
+  std::vector<Bneck> v;
+  for (int b = 0; b < blocks; ++b) v.push_back(add_bneck_w(n, pre + "." + std::to_string(b), 256, 128, false));
+  return v;
+}
+
+void add_conv1(rtpose_net* n, int H, int W, int conv, int in_buf, int in_choff, int out_buf, int out_choff, int relu,
+               int res_buf = -1) {
+  add_conv_op(n, H, W, 1, &conv, &in_buf, &in_choff, &out_buf, &out_choff, relu, 0);
+  n->ops.back().res_buf = res_buf;
+}
+
+// one Bottleneck at H x W: in -> out (out == in: in place)
+void plan_bneck(rtpose_net* n, const Bneck& b, int H, int W, int in, int out, int t1, int t2) {
+  add_conv1(n, H, W, b.c1, in, 0, t1, 0, 1);  // relu(bn2(conv1(relu(bn1(x)))))
+  add_conv1(n, H, W, b.c2, t1, 0, t2, 0, 1);  // relu(bn3(conv2(.)))
+  if (b.ds >= 0) {
+    add_conv1(n, H, W, b.ds, in, 0, out, 0, 0);
+    add_conv1(n, H, W, b.c3, t2, 0, out, 0, 0, out);
+  } else {
+    add_conv1(n, H, W, b.c3, t2, 0, out, 0, 0, in);
+  }
+}
+
+void plan_seq(rtpose_net* n, const std::vector<Bneck>& v, int H, int W, int in, int out, int t1, int t2) {
+  for (size_t i = 0; i < v.size(); ++i) plan_bneck(n, v[i], H, W, i ? out : in, out, t1, t2);
+}
+
+void build_plan_hourglass(rtpose_net* n) {
+  const int S = n->hg_stacks, NB = n->hg_blocks, P = n->hg_paf, Hc = n->hg_heat;
+  const int hoff = ceil_div(P, 8) * 8, sc_c = hoff + ceil_div(Hc, 8) * 8;
+  n->hg_heat_off = hoff;
+  const int H0 = n->H, W0 = n->W, H1 = H0 / 2, W1 = W0 / 2;
+  int RH[5], RW[5];  // depth level 4 (stride 4) .. 0 (stride 64)
+  for (int l = 4; l >= 0; --l) {
+    RH[l] = H0 >> (6 - l);
+    RW[l] = W0 >> (6 - l);
+  }
+  n->H3 = RH[4];
+  n->W3 = RW[4];
+
+  // ---- weights, in the reference's state_dict order ----
+  const int stem = add_conv_w(n, "conv1", 64, 3, 7, false);
+  // (as for conv1_1: the generic 7x7 packing of add_conv_w stays in the arena - packed on every load, read by no launch -
+  //  so that the conv is an ordinary entry of the conv table; the launch reads the packing below)
+  n->convs[stem].stem = true;
+  n->convs[stem].w_off_first = n->wt_floats;
+  n->wt_floats += round_up(conv7x7_s2_packed_floats(), 64);
+  const Bneck l1 = add_bneck_w(n, "layer1.0", 64, 64, true);
+  const Bneck l2 = add_bneck_w(n, "layer2.0", 128, 128, true);
+  const Bneck l3 = add_bneck_w(n, "layer3.0", 256, 128, false);
+  std::vector<std::vector<std::vector<std::vector<Bneck>>>> hgw(S);  // [stack][level index 0..3][j]
+  for (int s = 0; s < S; ++s) {
+    hgw[s].resize(4);
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < (i == 0 ? 4 : 3); ++j)
+        hgw[s][i].push_back(add_seq_w(n, "hg." + std::to_string(s) + ".hg." + std::to_string(i) + "." + std::to_string(j), NB));
+  }
+  std::vector<std::vector<Bneck>> resw;
+  for (int s = 0; s < S; ++s) resw.push_back(add_seq_w(n, "res." + std::to_string(s), NB));
+  std::vector<int> fc(S), sht(S), spaf(S), fc_(S, -1), pafb(S, -1), htb(S, -1);
+  for (int s = 0; s < S; ++s) fc[s] = add_conv_w(n, "fc." + std::to_string(s) + ".0", 256, 256, 1, false);
+  for (int s = 0; s < S; ++s) sht[s] = add_conv_w(n, "score_ht." + std::to_string(s), Hc, 256, 1, false);
+  for (int s = 0; s < S; ++s) spaf[s] = add_conv_w(n, "score_paf." + std::to_string(s), P, 256, 1, false);
+  for (int s = 0; s + 1 < S; ++s) fc_[s] = add_conv_w(n, "fc_." + std::to_string(s), 256, 256, 1, false);
+  for (int s = 0; s + 1 < S; ++s) pafb[s] = add_conv_w(n, "paf_score_." + std::to_string(s), 256, P, 1, false);
+  for (int s = 0; s + 1 < S; ++s) htb[s] = add_conv_w(n, "ht_score_." + std::to_string(s), 256, Hc, 1, false);
+
+  // ---- activation buffers ----
+  const int X0 = add_buf(n, 8, 1, H0, W0);
+  n->x0_buf = X0;
+  const int S1 = add_buf(n, 64, 0, H1, W1);
+  const int T1a = add_buf(n, 64, 1, H1, W1), T2a = add_buf(n, 64, 0, H1, W1);
+  const int A = add_buf(n, 128, 0, H1, W1);
+  const int B0 = add_buf(n, 128, 0, RH[4], RW[4]);
+  const int X = add_buf(n, 256, 0, RH[4], RW[4]);
+  int T1[5], T2[5], UP[5], L[5];
+  for (int l = 4; l >= 0; --l) {
+    T1[l] = add_buf(n, 128, 1, RH[l], RW[l]);
+    T2[l] = add_buf(n, 128, 0, RH[l], RW[l]);
+    UP[l] = l ? add_buf(n, 256, 0, RH[l], RW[l]) : -1;
+    L[l] = l < 4 ? add_buf(n, 256, 0, RH[l], RW[l]) : -1;
+  }
+  const int Y = add_buf(n, 256, 0, RH[4], RW[4]);
+  const int SC = add_buf(n, sc_c, 0, RH[4], RW[4]);
+  n->cat_buf[0] = SC;
+  for (int s = 0; s < S; ++s) n->op_save.push_back(add_buf(n, hoff + Hc, 0, RH[4], RW[4]));
+
+  // ---- launches ----
+  add_simple_op(n, OP_INPUT, "nchw_to_nhwc8", H0, W0, -1, 0, X0, 0, 3);
+  add_conv1(n, H0, W0, stem, X0, 0, S1, 0, 1);  // (H0 x W0 is the INPUT size of the strided conv)
+  n->ops.back().flops /= 4.0;
+  plan_bneck(n, l1, H1, W1, S1, A, T1a, T2a);
+  add_simple_op(n, OP_POOL, "maxpool", H1, W1, A, 0, B0, 0, 128);
+  plan_bneck(n, l2, RH[4], RW[4], B0, X, T1[4], T2[4]);
+  plan_bneck(n, l3, RH[4], RW[4], X, X, T1[4], T2[4]);
+  for (int s = 0; s < S; ++s) {
+    const std::string tag = "hg." + std::to_string(s);
+    // _hour_glass_forward(lv, in), rtpose_hourglass.py:74-86; the level's result is left in UP[lv]
+    struct Rec {
+      rtpose_net* n;
+      const std::vector<std::vector<std::vector<Bneck>>>& w;
+      const int *RH, *RW, *T1, *T2, *UP, *L;
+      const std::string& tag;
+      void run(int lv, int in) const {
+        const int H = RH[lv], W = RW[lv], Hl = RH[lv - 1], Wl = RW[lv - 1];
+        plan_seq(n, w[lv - 1][0], H, W, in, UP[lv], T1[lv], T2[lv]);                                     // up1
+        add_simple_op(n, OP_POOL, tag + ".pool" + std::to_string(lv), H, W, in, 0, L[lv - 1], 0, 256);
+        plan_seq(n, w[lv - 1][1], Hl, Wl, L[lv - 1], L[lv - 1], T1[lv - 1], T2[lv - 1]);                 // low1
+        int low = L[lv - 1];
+        if (lv > 1) {
+          run(lv - 1, L[lv - 1]);
+          low = UP[lv - 1];
+        } else {
+          plan_seq(n, w[0][3], Hl, Wl, low, low, T1[0], T2[0]);                                          // low2
+        }
+        plan_seq(n, w[lv - 1][2], Hl, Wl, low, low, T1[lv - 1], T2[lv - 1]);                             // low3
+        add_simple_op(n, OP_UPADD, tag + ".up" + std::to_string(lv), H, W, UP[lv], 0, UP[lv], 0, 256);   // up1 + up2
+        n->ops.back().in_buf[1] = low;
+      }
+    };
+    const Rec rec = {n, hgw[s], RH, RW, T1, T2, UP, L, tag};
+    rec.run(4, X);
+    const int H = RH[4], W = RW[4];
+    plan_seq(n, resw[s], H, W, UP[4], UP[4], T1[4], T2[4]);
+    add_conv1(n, H, W, fc[s], UP[4], 0, Y, 0, 1);  // fc: conv + folded bn + relu
+    {
+      const int cw[2] = {spaf[s], sht[s]}, in2[2] = {Y, Y}, zz[2] = {0, 0}, out2[2] = {SC, SC}, off2[2] = {0, hoff};
+      add_conv_op(n, H, W, 2, cw, in2, zz, out2, off2, 0, 0);
+    }
+    add_simple_op(n, OP_SAVE, "save" + std::to_string(s), H, W, SC, 0, n->op_save[s], 0, hoff + Hc);
+    if (s + 1 < S) {
+      add_conv1(n, H, W, fc_[s], Y, 0, X, 0, 0, X);
+      add_conv1(n, H, W, pafb[s], SC, 0, X, 0, 0, X);
+      add_conv1(n, H, W, htb[s], SC, hoff, X, 0, 0, X);
+    }
+  }
+}
+
 // RTPOSE_WINOGRAD in the environment of the process: 1 (unset) = both kernel sizes in Winograd form, 0 = none,
 // 3 / 7 = only that kernel size
 int winograd_env() {
@@ -816,6 +1015,34 @@ int rtpose_openpose_create(int N, int H, int W, const rtpose_openpose_options* o
   return finish_plan(n, out);
 }
 
+int rtpose_hourglass_create(int N, int H, int W, const rtpose_hourglass_options* opt, rtpose_net** out) {
+  if (!out) return fail(RTPOSE_E_INVAL, "hourglass_create: out is NULL");
+  if (!opt || opt->struct_bytes < sizeof(rtpose_hourglass_options))
+    return fail(RTPOSE_E_INVAL, "hourglass_create: options missing or struct_bytes smaller than this library's "
+                                "rtpose_hourglass_options");
+  if (N <= 0) return fail(RTPOSE_E_INVAL, "hourglass_create: need N>=1");
+  if (H < 64 || W < 64 || (H % 64) || (W % 64))
+    return fail(RTPOSE_E_INVAL, "hourglass_create: H and W must be a multiple of 64 (got %d x %d): the depth-4 hourglass "
+                                "halves the stride-4 map four times and adds the upsampled maps back, `out = up1 + up2` "
+                                "(rtpose_hourglass.py:85), which fails in the reference too for any other size", H, W);
+  if (opt->num_stacks < 1 || opt->num_stacks > 64)
+    return fail(RTPOSE_E_INVAL, "hourglass_create: num_stacks must be 1..64 (forward returns the last stack's maps)");
+  if (opt->num_blocks < 1 || opt->num_blocks > 16)
+    return fail(RTPOSE_E_INVAL, "hourglass_create: num_blocks must be 1..16 (Bottlenecks per residual module)");
+  if (opt->paf_classes < 1 || opt->paf_classes > 64 || opt->ht_classes < 1 || opt->ht_classes > 64)
+    return fail(RTPOSE_E_INVAL, "hourglass_create: paf_classes and ht_classes must be 1..64");
+  if (int rc = check_winograd3("hourglass_create", opt->winograd3)) return rc;
+  rtpose_net* n = new_plan(N, H, W, opt->winograd3, opt->amp_limit);
+  n->topo = 2;
+  n->hg_stacks = opt->num_stacks;
+  n->hg_blocks = opt->num_blocks;
+  n->hg_paf = opt->paf_classes;
+  n->hg_heat = opt->ht_classes;
+  n->w7 = 0;  // the 7x7 stem has its own kernel
+  build_plan_hourglass(n);
+  return finish_plan(n, out);
+}
+
 int rtpose_net_create_ex(int N, int H, int W, int dtype, rtpose_net** out) {
   rtpose_net_options o;
   o.struct_bytes = sizeof(o);
@@ -882,8 +1109,9 @@ int rtpose_net_bind(rtpose_net* net, void* workspace, size_t workspace_bytes, vo
                                     (size_t)((char*)(conv2d_wino7_scratch_err(net->ws + net->scratch_off, net->n_cu) + 1) -
                                              (char*)(net->ws + net->scratch_off)), s));
   // channel map of the filters that read a concat buffer
-  RTPOSE_HIP_CHECK(hipMemcpyAsync(net->wt + net->catmap_off, net->catmap_host.data(),
-                                  net->catmap_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (!net->catmap_host.empty())
+    RTPOSE_HIP_CHECK(hipMemcpyAsync(net->wt + net->catmap_off, net->catmap_host.data(),
+                                    net->catmap_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
   RTPOSE_HIP_CHECK(hipStreamSynchronize(s));
   net->bound = true;
   return 0;
@@ -924,6 +1152,31 @@ int rtpose_net_load_prelu(rtpose_net* net, int idx, const float* slope, void* st
   return 0;
 }
 
+int rtpose_net_preact_info(const rtpose_net* net, int idx, char* name, int name_cap) {
+  if (!net || idx < 0 || idx >= (int)net->convs.size()) return fail(RTPOSE_E_INVAL, "preact_info: bad index");
+  const ConvW& c = net->convs[idx];
+  if (name && name_cap > 0) snprintf(name, name_cap, "%s", c.preact_name.c_str());
+  return c.has_preact ? 1 : 0;
+}
+
+int rtpose_net_load_preact(rtpose_net* net, int idx, const float* scale, const float* shift, void* stream) {
+  if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_load_preact: net not bound");
+  if (idx < 0 || idx >= (int)net->convs.size()) return fail(RTPOSE_E_INVAL, "net_load_preact: bad index");
+  const ConvW& c = net->convs[idx];
+  if (!c.has_preact)
+    return fail(RTPOSE_E_INVAL, "net_load_preact: conv %d (%s) has no pre-activation", idx, c.name.c_str());
+  int rc = net_on_its_device(net, "net_load_preact");
+  if (!rc) rc = check_device_ptr(scale, net->device, "net_load_preact", "the scale tensor");
+  if (!rc) rc = check_device_ptr(shift, net->device, "net_load_preact", "the shift tensor");
+  if (rc) return rc;
+  hipStream_t s = as_stream(stream);
+  float* dst = net->wt + c.pa_off;
+  RTPOSE_HIP_CHECK(hipMemcpyAsync(dst, scale, (size_t)c.cin_src * sizeof(float), hipMemcpyDeviceToDevice, s));
+  RTPOSE_HIP_CHECK(hipMemcpyAsync(dst + round_up((size_t)c.cin_packed, 64), shift, (size_t)c.cin_src * sizeof(float),
+                                  hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
 int rtpose_net_load_conv(rtpose_net* net, int idx, const float* w_oihw, const float* bias, void* stream) {
   if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_load_conv: net not bound");
   if (idx < 0 || idx >= (int)net->convs.size()) return fail(RTPOSE_E_INVAL, "net_load_conv: bad index");
@@ -952,6 +1205,10 @@ int rtpose_net_load_conv(rtpose_net* net, int idx, const float* w_oihw, const fl
   if (rc) return rc;
   if (c.first) {
     rc = conv_first_pack_launch(w_oihw, bias, net->wt + c.w_off_first, s, 0);
+    if (rc) return rc;
+  }
+  if (c.stem) {
+    rc = conv7x7_s2_pack_launch(w_oihw, bias, net->wt + c.w_off_first, s);
     if (rc) return rc;
   }
   float* amp = net->wt + c.amp_off;
@@ -1127,6 +1384,7 @@ int rtpose_net_launch_executed_flops(const rtpose_net* net, int i, double* flops
       // what the matrix pipe is issued (SQ_INSTS_MFMA x 4096 of a launch): whole tiles, padded channels and columns
       const ConvW& c = net->convs[o.conv_idx[g]];
       wino = kForm[c.form].code;
+      if (c.stem) continue;  // conv7x7_s2_kernel issues no matrix instruction (v_fma_f32 only)
       if (c.first)  // conv_first_kernel (fp32 and bf16 plans: the fp32 matrix instruction either way): 8 x 32 pixel tiles, K = 28 (27 taps + a zero row), 64 columns
         fl += 2.0 * net->N * ceil_div(o.H, 8) * ceil_div(o.W, 32) * 256.0 * 28.0 * 64.0;
       else if (c.form == F_W3_2X2)  // 16 frequencies per 2 x 2 wtile
@@ -1312,6 +1570,16 @@ static rtpose_conv_desc conv_desc(const rtpose_net* net, const Op& o, int g, boo
   d.relu = o.relu;
   d.pool = o.pool;
   d.prelu = c.has_prelu ? net->wt + c.pr_off : nullptr;
+  if (c.has_preact) {
+    d.in_scale = net->wt + c.pa_off;
+    d.in_shift = net->wt + c.pa_off + round_up((size_t)c.cin_packed, 64);
+    d.preact_cin = c.cin_src;
+  }
+  if (o.res_buf >= 0) {
+    const Buf& br = net->bufs[o.res_buf];
+    d.residual = net->ws + br.off_floats;
+    d.lres = slice(br, o.res_choff);
+  }
   return d;
 }
 
@@ -1347,6 +1615,12 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
         rtpose_conv_desc d[2] = {};
         for (int g = 0; g < o.ngroups; ++g) d[g] = conv_desc(net, o, g);
         const ConvW& c = net->convs[o.conv_idx[0]];  // grouped convs run one form (pick_forms)
+        if (c.stem) {
+          const Buf& bs = fp32_input_buf(net);
+          rc = conv7x7_s2_launch(conv1_reads_image ? x_nchw : nullptr, net->ws + bs.off_floats, &bs.lay,
+                                 net->wt + c.w_off_first, d[0].out, &d[0].lout, o.relu, N, o.H, o.W, s);
+          break;
+        }
         if (c.first) {
           const Buf& bs = fp32_input_buf(net);
           rc = conv_first_launch(conv1_reads_image ? x_nchw : nullptr, net->ws + bs.off_floats, &bs.lay,
@@ -1378,6 +1652,12 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
         const Buf& bo = net->bufs[o.out_buf[0]];
         rc = rtpose_maxpool2x2(net->ws + bi.off_floats, &bi.lay, net->ws + bo.off_floats, &bo.lay, o.C,
                                N, o.H, o.W, stream);
+        break;
+      }
+      case OP_UPADD: {
+        const Buf &bu = net->bufs[o.in_buf[0]], &bl = net->bufs[o.in_buf[1]], &bo = net->bufs[o.out_buf[0]];
+        rc = upsample2_add_launch(net->ws + bu.off_floats, &bu.lay, net->ws + bl.off_floats, &bl.lay,
+                                  net->ws + bo.off_floats, &bo.lay, o.C, N, o.H, o.W, s);
         break;
       }
       case OP_SAVE:  // a concat slice -> the fp32 record of the stage outputs
@@ -1418,7 +1698,17 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
 static int stage_output_slice(const rtpose_net* net, int which, bool records, const float** base, rtpose_layout* lay,
                               int* C) {
   int buf, choff;
-  if (net->topo == 1) {  // saved_for_loss flattened: the PAF stages, then the heat-map stages
+  if (net->topo == 2) {  // 0 / 1: PAF / heat of the last stack; 2 + 2 s / 3 + 2 s: of stack s (records)
+    const bool paf = which % 2 == 0;
+    *C = paf ? net->hg_paf : net->hg_heat;
+    choff = paf ? 0 : net->hg_heat_off;
+    if (which < 2) {
+      buf = net->cat_buf[0];  // the score buffer: the last stack wrote it last
+    } else {
+      if (!records) return fail(RTPOSE_E_STATE, "net_read_output: the maps of stack %d are not kept (set keep_intermediates)", which / 2 - 1);
+      buf = net->op_save[which / 2 - 1];
+    }
+  } else if (net->topo == 1) {  // saved_for_loss flattened: the PAF stages, then the heat-map stages
     const bool paf = which < net->op_l2;
     *C = paf ? net->op_paf : net->op_heat;
     if (records) {
@@ -1452,7 +1742,8 @@ static int stage_output_slice(const rtpose_net* net, int which, bool records, co
 
 int rtpose_net_read_output(rtpose_net* net, int which, float* dst_nchw, void* stream) {
   if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_read_output: net not bound");
-  if (which < 0 || which >= (net->topo == 1 ? net->op_l2 + net->op_l1 : 12) || !dst_nchw)
+  if (which < 0 || which >= (net->topo == 2 ? 2 + 2 * net->hg_stacks : net->topo == 1 ? net->op_l2 + net->op_l1 : 12) ||
+      !dst_nchw)
     return fail(RTPOSE_E_INVAL, "net_read_output: bad argument");
   int rcd = net_on_its_device(net, "net_read_output");
   if (!rcd) rcd = check_device_ptr(dst_nchw, net->device, "net_read_output", "the destination tensor");
@@ -1468,7 +1759,9 @@ int rtpose_net_output_view(const rtpose_net* net, int which, const float** base,
                            int* C, int* H, int* W) {
   if (!net || !net->bound || which < 0 || which > 1) return fail(RTPOSE_E_INVAL, "output_view: bad argument");
   // the last PAF / heat maps, where the last stage's launch writes them whether records are kept or not
-  const int last = net->topo == 1 ? (which == 0 ? net->op_l2 : net->op_l2 + net->op_l1) - 1 : 10 + which;
+  const int last = net->topo == 2   ? which
+                   : net->topo == 1 ? (which == 0 ? net->op_l2 : net->op_l2 + net->op_l1) - 1
+                                    : 10 + which;
   const float* b;
   rtpose_layout l;
   int c;

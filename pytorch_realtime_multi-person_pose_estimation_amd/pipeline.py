@@ -142,6 +142,12 @@ class PoseEstimator(object):
                              % chans)
         self.model = model
         self.config = config or dec.default_config()
+        # a model may say at which stride its maps are (hourglass.HourglassNet: 4); models that do not are at stride 8
+        self.stride = getattr(model, 'output_stride', None)
+        if self.stride is not None and int(self.config.MODEL.DOWNSAMPLE) != int(self.stride):
+            raise ValueError("PoseEstimator: the model's maps are at stride %d but config.MODEL.DOWNSAMPLE is %d (the "
+                             "decoder upsamples the maps by DOWNSAMPLE; set it to the model's stride)"
+                             % (int(self.stride), int(self.config.MODEL.DOWNSAMPLE)))
         self.max_peaks_per_part = max_peaks_per_part
         self.max_humans = max_humans
         self._bufs = {}
@@ -236,7 +242,8 @@ class PoseEstimator(object):
         out = []
         up = int(self.config.MODEL.DOWNSAMPLE)
         recs = self(x, **kw)
-        h, w = x.shape[2] // 8, x.shape[3] // 8
+        stride = int(self.stride) if self.stride is not None else 8
+        h, w = x.shape[2] // stride, x.shape[3] // stride
         for r in recs:
             out.append(dec.humans_from_record(r, w * up, h * up, int(self.config.MODEL.NUM_KEYPOINTS)))
         return out
