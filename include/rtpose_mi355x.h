@@ -115,8 +115,8 @@ typedef struct rtpose_conv_desc {
                    ignored) - folds channel_shuffle / concat of the ShuffleNetV2
                    blocks (rtpose_shufflenetV2.py:56-62) into the store        */
   int32_t wino_m; /* rtpose_conv2d_winograd* only (rtpose_conv2d ignores it): the form of THIS launch.
-                   k = 3: 0 or 2 = F(2x2,3x3), 4 = F(4x4,3x3);  k = 7: 6 = F(6,7), 4 = F(4,7), 0 = the
-                   library default (6; 4 with RTPOSE_WINOGRAD7_M=4 in the environment).  `w_packed` must
+                   k = 3: 0 or 2 = F(2x2,3x3), 4 = F(4x4,3x3);  k = 7: 6 = F(6,7), 4 = F(4,7), 8 = F(8,7), 0 = the
+                   library default (6; 4 with RTPOSE_WINOGRAD7_M=4 in the environment; never 8).  `w_packed` must
                    come from the packing of the same form.  Any other value is refused
                    (RTPOSE_E_INVAL): ZERO-INITIALISE descriptors (memset / `= {0}`) - the struct has
                    grown by trailing fields and may again.                                  */
@@ -219,7 +219,10 @@ int rtpose_conv1x1_pair(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, 
  *   k = 3: F(2x2, 3x3), 16 instead of 36 multiplies per 2 x 2 outputs and input channel (2.25x);
  *   k = 7: F(6, 7) along x, direct along y: 84 instead of 294 per 6 outputs (3.5x), no fused pool;
  *          or F(4, 7), 70 instead of 196 per 4 outputs (2.8x), selected per launch with
- *          rtpose_conv_desc.wino_m = 4 and the matching packing (rtpose_pack_conv_weights_winograd7).
+ *          rtpose_conv_desc.wino_m = 4 and the matching packing (rtpose_pack_conv_weights_winograd7);
+ *          or F(8, 7), 98 instead of 392 per 8 outputs (4x; points of F(6,7) and +-5/4), wino_m = 8 and
+ *          its packing: 12.5 % fewer matrix multiplies than F(6,7) for an error bound ~8x F(6,7)'s -
+ *          opt-in only, no default selects it (DESIGN.md §3.0 has the measured error and times).
  * fp32 MFMA throughout; results differ from the direct sum by rounding only (k = 3: a few ulp,
  * k = 7: ~3e-5 at magnitude 4; whole network < 4e-5 on the stage outputs; contract 1e-3).
  * The descriptor is rtpose_conv_desc with `w_packed` from rtpose_pack_conv_weights_winograd
@@ -246,7 +249,8 @@ int rtpose_pack_conv_weights_winograd3(const float* w_oihw, const float* bias, i
                                        int cin_src, int m, const int32_t* cin_map,
                                        int cin_packed, float* w_packed, float* bias_packed,
                                        void* stream);
-/* k = 7 with an explicit form m (4 or 6; 0 = default), see rtpose_conv_desc.wino_m */
+/* k = 7 with an explicit form m (4, 6 or 8; 0 = default), see rtpose_conv_desc.wino_m;
+ * (7 (m + 6) cin + 96) * cout_pad floats */
 size_t rtpose_packed_weight_floats_winograd7(int cout, int cin, int m);
 int rtpose_pack_conv_weights_winograd7(const float* w_oihw, const float* bias, int cout,
                                        int cin_src, int m, const int32_t* cin_map,
@@ -255,7 +259,8 @@ int rtpose_pack_conv_weights_winograd7(const float* w_oihw, const float* bias, i
 /* The 7x7 kernel balances launches whose tiles do not come out as whole rounds over the CUs by
  * running persistent blocks that split tiles (results bit-identical either way).  A split tile is
  * handed from one block to the next through `scratch`: device memory OWNED BY THE CALLER
- * (256-byte aligned, rtpose_conv2d_winograd_scratch_bytes() of it, for the current device),
+ * (256-byte aligned, rtpose_conv2d_winograd_scratch_bytes() of it, for the current device: sized for
+ * the widest form, F(8,7)),
  * because the library allocates nothing on the forward path.  One scratch serves all launches that
  * are serialised on one stream.  With scratch = NULL (and through rtpose_conv2d_winograd) every
  * launch runs one block per tile.  The last int of the flag area is a device error word: bit 0 is
@@ -266,11 +271,11 @@ int rtpose_conv2d_winograd_ex(const rtpose_conv_desc* d, int ngroups, int N, int
                               void* scratch, size_t scratch_bytes, void* stream);
 int rtpose_conv2d_winograd_scratch_error(const void* scratch, int* error_word, void* stream);
 /* Amplification estimate of a filter bank w[cout][cin][k][k] (device, OIHW fp32) in Winograd form:
- * k = 3 -> F(2x2,3x3); k = 7 -> F(m,7), m = 4 or 6 (0 = default).  Writes ONE float to the device
+ * k = 3 -> F(2x2,3x3); k = 7 -> F(m,7), m = 4, 6 or 8 (0 = default).  Writes ONE float to the device
  * address `amp_device`: the worst ratio over the output channels of the element-wise rounding-error
  * BOUND of the form to the direct sum's for inputs of uniform magnitude,
  *   max_i sum_f |AT[i][f]| (sum_n |BT[f][n]|) sum_{c,ky} |U[ky][f][c][o]|  /  sum_{c,ky,kx} |w[o][c][ky][kx]|
- * (i.i.d. Gaussian filters: 3.3, 62, 115; k = 3, m = 4 - F(4x4,3x3): see DESIGN.md §3.0).  The rtpose_vgg executor uses it to choose the form of a
+ * (i.i.d. Gaussian filters: 3.3, 62, 115, F(8,7) ~900; k = 3, m = 4 - F(4x4,3x3): see DESIGN.md §3.0).  The rtpose_vgg executor uses it to choose the form of a
  * layer (rtpose_net_options.winograd7 = RTPOSE_WINO7_AUTO). */
 int rtpose_winograd_amplification(const float* w_oihw, int cout, int cin, int k, int m,
                                   float* amp_device, void* stream);
@@ -568,15 +573,19 @@ int rtpose_net_create_ex(int N, int H, int W, int dtype, rtpose_net** out);
 /* Per-plan choice of the arithmetic of the fp32 convs (the Winograd forms sum fewer, transformed
  * products: results differ from the direct sum by rounding, bounds in DESIGN.md §3.0).  The weight
  * arena of fp32 plans holds every packing a plan may choose (direct, F(2x2,3x3), F(4,7), F(6,7)), so
- * plans with different options share one arena and the choice costs nothing at run time.
+ * plans with different options share one arena and the choice costs nothing at run time.  The one
+ * exception is winograd7 = 8: such a plan's arena is the standard layout FOLLOWED BY the F(8,7) packings
+ * of the 7x7 convs (rtpose_net_weight_bytes reports the larger size, rtpose_net_load_conv through it
+ * writes them too); an arena of that size also serves every other plan, not the other way round.
  *   winograd3: RTPOSE_WINO_DEFAULT (= RTPOSE_WINO3_AUTO since round 4; the environment's RTPOSE_WINOGRAD=0|7 ->
  *              direct, RTPOSE_WINOGRAD3_M=2|4 -> F(2x2,3x3) | F(4x4,3x3) forced), 0 = direct 3x3 kernels,
  *              1 = F(2x2,3x3), 4 = F(4x4,3x3) forced (layers without an F(4x4,3x3) instance: F(2x2,3x3)),
  *              RTPOSE_WINO3_AUTO = per layer F(4x4,3x3) if its amplification estimate is <= amp_limit, else
  *              F(2x2,3x3); decided by rtpose_net_finalize_weights
  *   winograd7: RTPOSE_WINO_DEFAULT (= RTPOSE_WINO7_AUTO since round 4; the environment's RTPOSE_WINOGRAD=0|3 ->
- *              direct, RTPOSE_WINOGRAD7_M=4|6 -> F(4,7) | F(6,7) forced), 0 = direct, 4 = F(4,7), 6 = F(6,7)
- *              forced, RTPOSE_WINO7_AUTO = per layer the fastest form whose amplification estimate
+ *              direct, RTPOSE_WINOGRAD7_M=4|6|8 -> F(4,7) | F(6,7) | F(8,7) forced), 0 = direct, 4 = F(4,7),
+ *              6 = F(6,7), 8 = F(8,7) forced (opt-in: ~8x the error bound of F(6,7), inside the 1e-3 contract for
+ *              He / N(0, 0.01) filters; never chosen by AUTO), RTPOSE_WINO7_AUTO = per layer the fastest form whose amplification estimate
  *              (rtpose_winograd_amplification of the loaded filters) is <= amp_limit: F(6,7), else F(4,7),
  *              else direct; decided by rtpose_net_finalize_weights
  *   The default is the guarded one because the forms' error bounds scale with the estimate and nobody can
@@ -585,7 +594,7 @@ int rtpose_net_create_ex(int N, int H, int W, int dtype, rtpose_net** out);
  *   amp_limit: the AUTO modes only; <= 0 = the library default (256: twice what i.i.d. Gaussian
  *              filters give in F(6,7))
  * Fields are ignored by bf16 / bf16x3 plans.  A form that has no kernel instance at the plan's
- * geometry falls back to the next one (F(6,7) -> F(4,7) -> direct) whatever the options say. */
+ * geometry falls back to the next one (F(8,7) -> F(6,7) -> F(4,7) -> direct) whatever the options say. */
 #define RTPOSE_WINO_DEFAULT (-1)
 #define RTPOSE_WINO7_AUTO 1
 #define RTPOSE_WINO3_AUTO 3
@@ -621,9 +630,9 @@ int rtpose_net_load_conv(rtpose_net* net, int idx, const float* w_oihw,
  * generation, and each plan re-reads the estimates and re-decides its forms (here, in rtpose_net_forward* and
  * in rtpose_net_conv_numerics) when the generation it decided at is no longer the arena's. */
 int rtpose_net_finalize_weights(rtpose_net* net, void* stream);
-/* Arithmetic of conv idx in this plan: *form = 0 direct, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 = F(4,7), 6 = F(6,7);
- * amp[4] = amplification estimates of the loaded filters in F(2x2,3x3) / F(4,7) / F(6,7) / F(4x4,3x3) (0 where
- * the form does not apply; synchronises `stream` if they have not been read back yet).  Either may be NULL. */
+/* Arithmetic of conv idx in this plan: *form = 0 direct, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 = F(4,7), 6 = F(6,7),
+ * 8 = F(8,7); amp[4] = amplification estimates of the loaded filters in F(2x2,3x3) / F(4,7) / F(6,7) / F(4x4,3x3) (0 where
+ * the form does not apply; F(8,7) has no entry - rtpose_winograd_amplification(w, cout, cin, 7, 8, ..) computes its estimate; synchronises `stream` if they have not been read back yet).  Either may be NULL. */
 int rtpose_net_conv_numerics(rtpose_net* net, int idx, int* form, float* amp, void* stream);
 /* Device-side error word of the plan (synchronises `stream`): bit 0 = a split-tile hand-over of a
  * persistent 7x7 launch timed out (see rtpose_conv2d_winograd_ex); 0 = none.  The word is cleared. */

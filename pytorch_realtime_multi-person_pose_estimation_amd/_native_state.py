@@ -35,7 +35,8 @@ _NATIVE_ATTRS = ('_plans', '_weights', '_weights_key', '_weights_epoch', '_nativ
 class NativeStateMixin(object):
     def _init_native_state(self):
         self._plans = {}         # (n, h, w, device index, dtype) -> plan
-        self._weights = {}       # (device index, dtype) -> packed weight arena (torch tensor)
+        self._weights = {}       # (device index, dtype) -> packed weight arena (torch tensor); rtpose_vgg plans that force
+                                 # F(8,7) keep theirs under (device index, dtype, 'f87') (network._arena_key)
         self._weights_key = {}   # (device index, dtype) -> what the arena was packed from
         self._weights_epoch = [0]   # boxed: shared with DataParallel replicas like the dicts above
         self._native_lock = threading.RLock()
@@ -119,7 +120,7 @@ class NetPlanMixin(object):
 
     def conv_numerics(self, plan):
         """[(state_dict prefix, form, (amp F(2x2,3x3), amp F(4,7), amp F(6,7), amp F(4x4,3x3)))] of a plan: form 0 =
-        direct kernel, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 / 6 = F(m,7); amp = rtpose_winograd_amplification of the
+        direct kernel, 3 = F(2x2,3x3), 43 = F(4x4,3x3), 4 / 6 / 8 = F(m,7); amp = rtpose_winograd_amplification of the
         loaded filters (0 = n/a)."""
         out = []
         form = C.c_int()

@@ -1,17 +1,21 @@
-// fp32 7x7 convolution in 1-D Winograd form F(FM, 7) along x (FM = 6; 4 behind RTPOSE_WINOGRAD7_M=4), direct along y,
+// fp32 7x7 convolution in 1-D Winograd form F(FM, 7) along x (FM = 6; 4 behind RTPOSE_WINOGRAD7_M=4; 8 on request only),
+// direct along y,
 // for gfx950 (MI355X): stride 1, "same" padding, fused bias (+ReLU).
 //
 // Stands in for the 7x7 nn.Conv2d + nn.ReLU modules of the refinement stages 2..6
 // (lib/network/rtpose_vgg.py:108-127: Mconv1..5_stageN_L1/L2, cin 185 or 128 -> 128), which are 65 % of
 // the network's flops.  Along x every group of FM consecutive outputs is computed from NFQ = FM + 6 "frequencies"
-// (Toom-Cook interpolation points 0, +-1, +-2, +-1/2, +-3/2 [, +-2/3], inf; struct WT below):
+// (Toom-Cook interpolation points 0, +-1, +-2, +-1/2, +-3/2 [, +-2/3 [, +-5/4]], inf; struct WT below):
 //
 //   out[y][FM gx + i][o] = sum_f AT[i][f] * sum_ky sum_c  V[y + ky - 3][gx][f][c] * U[ky][f][c][o]
 //   V[r][gx][f][c] = sum_n BT[f][n] * in[r][FM gx - 3 + n][c]        U[ky][f][c][o] = sum_kx G[f][kx] * w[o][c][ky][kx]
 //
 // i.e. 7 NFQ multiplies per FM outputs and input channel instead of 49 FM: 3.5x fewer matrix-core flops for F(6,7)
-// (84 per 6 outputs), 2.8x for F(4,7).  Through the whole network the stage outputs move by 1.5e-5 (F(6,7)) resp.
-// 1e-5 (F(4,7)) against the direct sum (contract: 1e-3); F(8,7) would be 1e-4 and is not offered.
+// (84 per 6 outputs), 2.8x for F(4,7), 4x for F(8,7) (98 per 8 outputs).  Through the whole network the stage outputs
+// move by 1.5e-5 (F(6,7)) resp. 1e-5 (F(4,7)) against the direct sum (contract: 1e-3).  F(8,7) - 12.5 % fewer matrix
+// multiplies than F(6,7), an element-wise error bound ~8x F(6,7)'s - is opt-in (rtpose_conv_desc.wino_m = 8,
+// rtpose_net_options.winograd7 = 8, RTPOSE_WINOGRAD7_M=8): no default and no 'auto' choice selects it; error bound,
+// register figures and measurements in DESIGN.md §3.0 / profiles/r09_wino7_f8.txt.
 //
 // MI355X shape:
 //  * "position" = one group of FM output pixels.  A wave owns all NFQ frequencies of 32 consecutive positions x 32
@@ -55,6 +59,9 @@ constexpr int W7_PF = 4;
 //           4 outputs instead of 196 (2.8x); whole-network stage outputs move by < 1e-5
 //   FM = 6: + the points +-2/3 - 84 per 6 outputs instead of 294 (3.5x); entries in 18ths / 144ths (rounded to fp32),
 //           whole network 1.5e-5 (points +-3 instead: 6.4e-5, +-1/4: 2.8e-5; contract 1e-3)
+//   FM = 8: + the points +-5/4 - 98 per 8 outputs instead of 392 (4x); 14 accumulators = 224 AGPRs, the 4-wave form only
+//           (7 frequencies per wave do not pair up for the two-waves-per-SIMD form).  Of +-5/4, +-3, +-1/4, +-1/3, +-3/4
+//           the pair with the smallest emulated element-wise error (worst gamma 475 against 541 .. 823; F(6,7): 111)
 template <int FM>
 struct WT;
 template <>
@@ -94,6 +101,31 @@ struct WT<6> {
   };
 };
 
+template <>
+struct WT<8> {
+  static constexpr int NFQ = 14, NP = 6, NSETS = 7;
+  __device__ static constexpr float kPts[6] = {1.f, 2.f, 0.5f, 1.5f, 0.666666667f, 1.25f};
+  __device__ static constexpr float kBT[14][14] = {
+      {1.5625f, 0.f, -13.4131944f, 0.f, 39.812934f, 0.f, -52.2643229f, 0.f, 32.8090278f, 0.f, -9.50694444f, 0.f, 1.f, 0.f},
+      {0.f, -1.5625f, -1.5625f, 11.8506944f, 11.8506944f, -27.9622396f, -27.9622396f, 24.3020833f, 24.3020833f, -8.50694444f, -8.50694444f, 1.f, 1.f, 0.f},
+      {0.f, 1.5625f, -1.5625f, -11.8506944f, 11.8506944f, 27.9622396f, -27.9622396f, -24.3020833f, 24.3020833f, 8.50694444f, -8.50694444f, -1.f, 1.f, 0.f},
+      {0.f, -0.78125f, -0.390625f, 6.51128472f, 3.25564236f, -18.2786458f, -9.13932292f, 21.5625f, 10.78125f, -11.0138889f, -5.50694444f, 2.f, 1.f, 0.f},
+      {0.f, 0.78125f, -0.390625f, -6.51128472f, 3.25564236f, 18.2786458f, -9.13932292f, -21.5625f, 10.78125f, 11.0138889f, -5.50694444f, -2.f, 1.f, 0.f},
+      {0.f, -3.125f, -6.25f, 14.3263889f, 28.6527778f, -22.3203125f, -44.640625f, 15.2473958f, 30.4947917f, -4.62847222f, -9.25694444f, 0.5f, 1.f, 0.f},
+      {0.f, 3.125f, -6.25f, -14.3263889f, 28.6527778f, 22.3203125f, -44.640625f, -15.2473958f, 30.4947917f, 4.62847222f, -9.25694444f, -0.5f, 1.f, 0.f},
+      {0.f, -1.04166667f, -0.694444444f, 8.47916667f, 5.65277778f, -22.7734375f, -15.1822917f, 24.7213542f, 16.4809028f, -10.8854167f, -7.25694444f, 1.5f, 1.f, 0.f},
+      {0.f, 1.04166667f, -0.694444444f, -8.47916667f, 5.65277778f, 22.7734375f, -15.1822917f, -24.7213542f, 16.4809028f, 10.8854167f, -7.25694444f, -1.5f, 1.f, 0.f},
+      {0.f, -2.34375f, -3.515625f, 14.8463542f, 22.2695312f, -26.3151042f, -39.4726562f, 19.1875f, 28.78125f, -6.04166667f, -9.0625f, 0.666666667f, 1.f, 0.f},
+      {0.f, 2.34375f, -3.515625f, -14.8463542f, 22.2695312f, 26.3151042f, -39.4726562f, -19.1875f, 28.78125f, 6.04166667f, -9.0625f, -0.666666667f, 1.f, 0.f},
+      {0.f, -1.25f, -1.f, 9.93055556f, 7.94444444f, -25.4947917f, -20.3958333f, 25.4947917f, 20.3958333f, -9.93055556f, -7.94444444f, 1.25f, 1.f, 0.f},
+      {0.f, 1.25f, -1.f, -9.93055556f, 7.94444444f, 25.4947917f, -20.3958333f, -25.4947917f, 20.3958333f, 9.93055556f, -7.94444444f, -1.25f, 1.f, 0.f},
+      {0.f, 1.5625f, 0.f, -13.4131944f, 0.f, 39.812934f, 0.f, -52.2643229f, 0.f, 32.8090278f, 0.f, -9.50694444f, 0.f, 1.f},
+  };
+};
+
+// the finite interpolation points in frequency order (frequency NFQ - 1 is the point at infinity)
+#define RTPOSE_W7_POINTS {0.0, 1.0, -1.0, 2.0, -2.0, 0.5, -0.5, 1.5, -1.5, 2.0 / 3.0, -2.0 / 3.0, 1.25, -1.25}
+
 struct Group {
   const float* in;
   const float* w;
@@ -115,10 +147,14 @@ struct Args {
   int VB;       // float4 per V buffer
   int mtiles, ntiles, ncombo, xcd_remap;
   int persist;      // 1: gridDim.x blocks share the (tile, chunk) units evenly (see wino7_f32)
-  float* scratch;   // persist: one accumulator tile per block (4 waves x 12 x 16 registers x 64 lanes)
+  float* scratch;   // persist: one accumulator tile per block (4 waves x NFQ x 16 registers x 64 lanes)
   int* flags;       // persist: flags[p] = 1 while the sums block p saved wait for block p + 1 (cleared at launch)
   int* err;         // persist: device error word (bit 0: a hand-over wait ran out, the tile's results are invalid)
 };
+
+// one dword per lane, clamped like the 16-byte loads of wino_common.h
+__device__ float llvm_raw_buffer_load_f32(i32x4 rsrc, int voffset, int soffset, int aux) __asm(
+    "llvm.amdgcn.raw.buffer.load.f32");
 
 constexpr int CK = 8, CG = 2;   // channels per chunk, 16-byte channel groups per chunk
 
@@ -290,7 +326,39 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
   floatx16 acc[NFW];
   // this wave's rows of the scratch slot (frequency-major: the slot looks the same whichever form wrote it)
   float* sp = A.scratch + ((size_t)(slot * 4 + wn) * (NFQ * 16) + (size_t)fh * NFW * 16) * 64 + lane;
-  if (cb == 0) {
+  if (FM == 8) {
+    // F(8,7), 14 accumulators: with the two starts below (constants / saved sums) merging in front of the multiply loop
+    // the compiler keeps part of the 224 registers outside the AGPRs and spills.  One start instead: every accumulator
+    // is LOADED, through a descriptor of the saved slot whose extent is zero for a tile's first segment - the hardware
+    // answers an out-of-range buffer load with 0.0 and touches no memory (~1000 cycles of a tile's > 400,000).
+    if (cb > 0) {  // (the hand-over wait: see below)
+      if (tid == 0) {
+        unsigned spins = 0;
+        while (__hip_atomic_load(A.flags + slot, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 1) {
+          __builtin_amdgcn_s_sleep(8);
+          if (++spins > (1u << 22)) {
+            __hip_atomic_fetch_or(A.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+          }
+        }
+      }
+      __syncthreads();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    }
+    const i32x4 rs = make_rsrc(sp - lane, cb > 0 ? (size_t)NFW * 16 * 64 * sizeof(float) : 0);
+    const float b0 = g.bias[ncol];  // padded to cout_pad
+#pragma unroll
+    for (int f = 0; f < NFW; ++f)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = llvm_raw_buffer_load_f32(rs, lane * 4, (f * 16 + r) * 256, 0);
+        acc[f][r] = (f == 1 && cb == 0) ? b0 : v;
+      }
+    if (cb > 0) {
+      __syncthreads();  // all reads done before the slot is handed back
+      if (tid == 0) __hip_atomic_store(A.flags + slot, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  } else if (cb == 0) {
 #pragma unroll
     for (int f = 0; f < NFW; ++f)
 #pragma unroll
@@ -824,7 +892,7 @@ __global__ void pack_wino7_kernel(const float* __restrict__ w, const float* __re
       v = gw[6];
     } else {
       // G[f][kx] = p_f^kx / N_f, N_f = prod_{l != f} (p_f - p_l) over the nfq - 1 finite points (in double)
-      const double pts[11] = {0.0, 1.0, -1.0, 2.0, -2.0, 0.5, -0.5, 1.5, -1.5, 2.0 / 3.0, -2.0 / 3.0};
+      const double pts[13] = RTPOSE_W7_POINTS;
       double nf = 1.0;
       for (int l = 0; l < nfq - 1; ++l)
         if (l != f) nf *= pts[f] - pts[l];
@@ -841,7 +909,8 @@ __global__ void pack_wino7_kernel(const float* __restrict__ w, const float* __re
 
 // Which F(FM, 7) a conv runs in is a property of the launch (rtpose_conv_desc.wino_m; the rtpose_vgg executor
 // chooses per plan and per layer, csrc/net.hip).  0 = the default: 6, or 4 with RTPOSE_WINOGRAD7_M=4 in the
-// environment of the process (read once).
+// environment of the process (read once).  (RTPOSE_WINOGRAD7_M=8 acts on the executor's default-option plans only: a
+// single launch runs F(8,7) when its descriptor says so.)
 int wino7_default_fm() {
   static int fm = 0;
   if (!fm) {
@@ -909,9 +978,16 @@ static int launch_small(const Args& a, dim3 grid, size_t lds, hipStream_t s) {
 //   Winograd:  X * max_i sum_f |AT[i][f]| * (sum_n |BT[f][n]|) * sum_{c,ky} |U[ky][f][c][o]|
 // and the rounding error of either sum is bounded by (a depth factor) x 2^-24 x that quantity.  amp = the worst
 // ratio of the two over the output channels: how much larger the element-wise error BOUND of the form is than the
-// direct sum's for these filters (i.i.d. Gaussian filters: F(2x2,3x3) 3.3, F(4,7) 62, F(6,7) 115; measured errors stay
+// direct sum's for these filters (i.i.d. Gaussian filters: F(2x2,3x3) 3.3, F(4,7) 62, F(6,7) 115, F(8,7) ~900; measured errors stay
 // below the bound, tests/test_wino_numerics_gpu.py).  One block per output channel, result by atomicMax on the bit
 // pattern of a non-negative float.
+template <int FM>
+__device__ float bt_abs_row_sum(int f) {
+  float b = 0.f;
+  for (int n = 0; n < WT<FM>::NFQ; ++n) b += fabsf(WT<FM>::kBT[f][n]);
+  return b;
+}
+
 __global__ void wino_amp_kernel(const float* __restrict__ w, int cout, int cin, int k, int fm, float* __restrict__ amp) {
   __shared__ float red[17][256];
   const int o = blockIdx.x, tid = threadIdx.x;
@@ -919,10 +995,10 @@ __global__ void wino_amp_kernel(const float* __restrict__ w, int cout, int cin, 
 #pragma unroll
   for (int f = 0; f < 16; ++f) sf[f] = 0.f;
   const int nfq = fm + 6;
-  const double pts[11] = {0.0, 1.0, -1.0, 2.0, -2.0, 0.5, -0.5, 1.5, -1.5, 2.0 / 3.0, -2.0 / 3.0};
+  const double pts[13] = RTPOSE_W7_POINTS;
   // N_f = prod_{l != f} (p_f - p_l): once per block (round 6; every thread used to rebuild it for every filter row - the
   // 117 launches of a weight load took 8.3 ms), by the same multiplications in the same order
-  __shared__ double s_nf[12];
+  __shared__ double s_nf[14];
   if (k == 7 && tid < nfq - 1) {
     double nf = 1.0;
     for (int l = 0; l < nfq - 1; ++l)
@@ -991,12 +1067,12 @@ __global__ void wino_amp_kernel(const float* __restrict__ w, int cout, int cin, 
           num = fmaxf(num, v);
         }
     } else {
-      const float pabs[12] = {0.f, 1.f, 1.f, 2.f, 2.f, 0.5f, 0.5f, 1.5f, 1.5f, 0.666666667f, 0.666666667f, 0.f};
+      const float pabs[14] = {0.f, 1.f, 1.f, 2.f, 2.f, 0.5f, 0.5f, 1.5f, 1.5f, 0.666666667f, 0.666666667f, 1.25f, 1.25f, 0.f};
       for (int i = 0; i < fm; ++i) {
         float v = 0.f;
         for (int f = 0; f < nfq; ++f) {
-          float b = 0.f;  // sum_n |BT[f][n]| of the kernel's (row-scaled) table
-          for (int n = 0; n < nfq; ++n) b += fabsf(fm == 4 ? WT<4>::kBT[f < 10 ? f : 0][n < 10 ? n : 0] : WT<6>::kBT[f][n]);
+          // sum_n |BT[f][n]| of the kernel's (row-scaled) table
+          const float b = fm == 4 ? bt_abs_row_sum<4>(f) : fm == 6 ? bt_abs_row_sum<6>(f) : bt_abs_row_sum<8>(f);
           float ai;  // |AT[i][f]| = |p_f|^i; the point 0 only reaches output 0, infinity only output fm - 1
           if (f == 0) ai = i == 0 ? 1.f : 0.f;
           else if (f == nfq - 1) ai = i == fm - 1 ? 1.f : 0.f;
@@ -1024,15 +1100,16 @@ int wino7_default_fm() { return wino7::wino7_default_fm(); }
 // serves launches that are serialised on one stream; concurrent launches need one each.
 static size_t wino7_scratch_flag_bytes(int blocks) { return round_up((size_t)(blocks + 2) * sizeof(int), 256); }
 int* conv2d_wino7_scratch_err(void* scratch, int blocks) { return static_cast<int*>(scratch) + blocks + 1; }
-size_t conv2d_wino7_scratch_bytes(int blocks) {
-  return wino7_scratch_flag_bytes(blocks) + (size_t)blocks * (4 * 12 * 16 * 64) * sizeof(float);
+size_t conv2d_wino7_scratch_bytes(int blocks, int fm) {
+  const int nfq = (fm == 8 ? 8 : 6) + 6;  // F(4,7) launches fit the F(6,7) size
+  return wino7_scratch_flag_bytes(blocks) + (size_t)blocks * (4 * nfq * 16 * 64) * sizeof(float);
 }
 
 // 1 when the 7x7 conv can run in F(fm, 7) form at this geometry (a kernel instance exists and the
 // transformed rows of a block fit the LDS), else 0: callers then use the direct kernel
 int conv2d_wino7_fits(int cin, int cout, int N, int H, int W, int hs, int fm) {
   fm = wino7::resolve_fm(fm);
-  if ((fm != 4 && fm != 6) || cin <= 0 || cin % wino7::CK || cout_pad(cout) % 128 || N <= 0 || H <= 0 || W <= 0) return 0;
+  if ((fm != 4 && fm != 6 && fm != 8) || cin <= 0 || cin % wino7::CK || cout_pad(cout) % 128 || N <= 0 || H <= 0 || W <= 0) return 0;
   wino7::Plan p;
   if (wino7::make_plan(N, H, W, hs, fm, &p)) return 0;
   return p.ni <= 2 && p.lds <= 156 * 1024;
@@ -1090,7 +1167,7 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
     // that is too small for this device) the launch runs one block per tile - same results, bit for bit.
     const int n_cu = device_cu_count();
     const long tiles = (long)a.mtiles * a.ncombo;
-    if (tiles >= n_cu && tiles % n_cu != 0 && scratch && scratch_bytes >= conv2d_wino7_scratch_bytes(n_cu)) {
+    if (tiles >= n_cu && tiles % n_cu != 0 && scratch && scratch_bytes >= conv2d_wino7_scratch_bytes(n_cu, fm)) {
       if ((uintptr_t)scratch & 255) return fail(RTPOSE_E_INVAL, "conv2d_winograd: scratch must be 256-byte aligned");
       a.flags = static_cast<int*>(scratch);
       a.err = a.flags + n_cu + 1;
@@ -1120,6 +1197,14 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
     if (p.ni == 1) return launch_inst<1, 0, 6, 2>(a, grid, p.lds, s);
     return launch_inst<2, 0, 6>(a, grid, p.lds, s);
   }
+  // F(8,7): the 4-wave form at every grid size (14 accumulators leave no room for a sibling wave, and 7 frequencies per
+  // wave do not pair up); 46-wide maps are 6 position groups per row
+  if (p.fm == 8) {
+    if (p.gx == 6 && p.tpi && p.ni == 1 && p.nrows == strip_rows(6))
+      return launch_inst<1, 6, 8>(a, grid, (size_t)2 * strip_rows(6) * row_stride(6, 14) * 16, s);
+    if (p.ni == 1) return launch_inst<1, 0, 8>(a, grid, p.lds, s);
+    return launch_inst<2, 0, 8>(a, grid, p.lds, s);
+  }
   if (p.gx == 12 && p.tpi && p.ni == 1 && p.nrows == strip_rows(12))
     return launch_inst<1, 12, 4>(a, grid, (size_t)2 * strip_rows(12) * row_stride(12, 10) * 16, s);
   if (p.ni == 1) return launch_inst<1, 0, 4>(a, grid, p.lds, s);
@@ -1129,7 +1214,7 @@ int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
 int pack_weights_wino7_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map,
                               int cin_packed, int fm, float* wp, float* bp, hipStream_t s) {
   fm = wino7::resolve_fm(fm);
-  if (fm != 4 && fm != 6) return fail(RTPOSE_E_INVAL, "pack_winograd: F(m,7) exists for m = 4 and m = 6");
+  if (fm != 4 && fm != 6 && fm != 8) return fail(RTPOSE_E_INVAL, "pack_winograd: F(m,7) exists for m = 4, 6 and 8");
   if (cin_packed % wino7::CK || cin_packed <= 0 || (cin_packed < cin_src && !cin_map))
     return fail(RTPOSE_E_INVAL, "pack_winograd: cin_packed must be a multiple of 8 and >= cin_src");
   const int coutp = cout_pad(cout);
@@ -1144,15 +1229,15 @@ int pack_weights_wino7_launch(const float* w, const float* bias, int cout, int c
 }
 
 size_t packed_weight_floats_wino7(int cout, int cin, int fm) {
-  // + 5 steps (10 frequency blocks of 8 x cout_pad floats): the B prefetch runs up to five steps ahead
+  // + 5 steps (10 frequency blocks of 8 x cout_pad floats): the B prefetch runs up to five steps ahead (F(8,7): four)
   return (size_t)(7 * (wino7::resolve_fm(fm) + 6) * cin + 96) * cout_pad(cout);
 }
 
 // amp (device, one float) <- amplification estimate of w[cout][cin][k][k] in F(2x2,3x3) (k = 3) or F(fm,7) (k = 7)
 int wino_amplification_launch(const float* w, int cout, int cin, int k, int fm, float* amp, hipStream_t s) {
   if (k == 7) fm = wino7::resolve_fm(fm);
-  if (!w || !amp || cout <= 0 || cin <= 0 || !(k == 3 || (k == 7 && (fm == 4 || fm == 6))))
-    return fail(RTPOSE_E_INVAL, "winograd_amplification: k must be 3, or 7 with m = 4 or 6");
+  if (!w || !amp || cout <= 0 || cin <= 0 || !(k == 3 || (k == 7 && (fm == 4 || fm == 6 || fm == 8))))
+    return fail(RTPOSE_E_INVAL, "winograd_amplification: k must be 3, or 7 with m = 4, 6 or 8");
   RTPOSE_HIP_CHECK(hipMemsetAsync(amp, 0, sizeof(float), s));
   hipLaunchKernelGGL(wino7::wino_amp_kernel, dim3((unsigned)cout), dim3(256), 0, s, w, cout, cin, k, k == 7 ? fm : 0, amp);
   RTPOSE_HIP_CHECK(hipGetLastError());

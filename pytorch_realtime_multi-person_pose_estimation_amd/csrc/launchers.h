@@ -40,13 +40,14 @@ int pack_weights_wino4_launch(const float* w, const float* bias, int cout, int c
                               int cin_packed, float* wp, float* bp, hipStream_t s);
 int wino4_amplification_launch(const float* w, int cout, int cin, float* amp, hipStream_t s);
 double conv2d_wino4_issued_flops(int cin, int cout, int N, int H, int W);
-// F(4,7) / F(6,7) (conv_wino7.hip)
+// F(4,7) / F(6,7) / F(8,7) (conv_wino7.hip)
 int wino7_default_fm();
 int conv2d_wino7_fits(int cin, int cout, int N, int H, int W, int hs, int fm);
 int conv2d_wino7_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, int fm, void* scratch,
                         size_t scratch_bytes, hipStream_t s);
 double conv2d_wino7_issued_flops(int cin, int cout, int N, int H, int W, int hs, int fm);
-size_t conv2d_wino7_scratch_bytes(int blocks);
+// hand-over scratch of a persistent launch in F(fm,7): fm = 8 needs 14 accumulators per wave, 4 / 6 twelve
+size_t conv2d_wino7_scratch_bytes(int blocks, int fm = 6);
 int* conv2d_wino7_scratch_err(void* scratch, int blocks);
 size_t packed_weight_floats_wino7(int cout, int cin, int fm);
 int pack_weights_wino7_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map,

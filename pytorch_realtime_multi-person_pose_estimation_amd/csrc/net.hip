@@ -59,7 +59,11 @@ struct Buf {
 // descriptor's wino_m and the launchers' fm take it, the slot of its amplification estimate in the arena's amp[4]
 // (ABI too: rtpose_net_conv_numerics hands the four out in that order) and its rank among the forms of its kernel
 // size - direct, which sums in the reference's order, is the most conservative.
-enum Form { F_DIRECT, F_W3_2X2, F_W3_4X4, F_W7_4, F_W7_6, kForms };
+// F(8,7) is the exception to "every arena holds every packing": only a plan created with winograd7 = 8 has it, BEHIND
+// the standard layout (add_f87_packings), so every other plan keeps its arena byte for byte.  It has no slot in amp[4]
+// (which is ABI) - nothing chooses it by its estimate; rtpose_winograd_amplification(.., 7, 8, ..) computes one on demand.
+enum Form { F_DIRECT, F_W3_2X2, F_W3_4X4, F_W7_4, F_W7_6, F_W7_8, kForms };
+constexpr int kStdForms = F_W7_8;  // the forms of the standard arena layout
 struct FormInfo {
   int code, k, fm, amp_slot, rank;
 };
@@ -69,6 +73,7 @@ constexpr FormInfo kForm[kForms] = {
     {43, 3, 4, 3, 2},  // F(4x4,3x3)
     {4, 7, 4, 1, 1},   // F(4,7)
     {6, 7, 6, 2, 2},   // F(6,7)
+    {8, 7, 8, -1, 3},  // F(8,7): opt-in only
 };
 constexpr size_t kNotPacked = ~(size_t)0;
 
@@ -79,7 +84,7 @@ struct ConvW {
   // Float offsets in the weight arena.  An fp32 arena holds EVERY packing a plan may run the conv in (it is shared by
   // all plans of a module, whatever their geometry and options): the direct one, and every Winograd form that has a
   // kernel for these channel counts; kNotPacked where it has none.  bf16 arenas hold the direct packing only.
-  size_t w_off[kForms] = {kNotPacked, kNotPacked, kNotPacked, kNotPacked, kNotPacked};
+  size_t w_off[kForms] = {kNotPacked, kNotPacked, kNotPacked, kNotPacked, kNotPacked, kNotPacked};
   size_t b_off = 0;
   bool first = false;      // conv1_1 (3 -> 64, 3x3): its own kernel, packing at w_off_first (csrc/conv_first.hip)
   size_t w_off_first = 0;
@@ -131,7 +136,7 @@ struct rtpose_net {
   int bf16 = 0;                  // 1: bf16 activations/weights, fp32 accumulate (BASELINE config 3)
   int split = 0;                 // bf16 plans only: 1 = "bf16x3" split operands (hi + lo bf16 per value)
   int w3 = RTPOSE_WINO3_AUTO;    // fp32 plans, 3x3 convs: 0 direct, 1 = F(2x2,3x3), 4 = F(4x4,3x3), RTPOSE_WINO3_AUTO = per layer by amp_limit (the default)
-  int w7 = RTPOSE_WINO7_AUTO;    // fp32 plans: 0 direct, 4 / 6 = F(4,7) / F(6,7), RTPOSE_WINO7_AUTO = per layer by amp_limit (the default)
+  int w7 = RTPOSE_WINO7_AUTO;    // fp32 plans: 0 direct, 4 / 6 / 8 = F(4,7) / F(6,7) / F(8,7), RTPOSE_WINO7_AUTO = per layer by amp_limit (the default)
   float amp_limit = 256.f;
   bool forms_final = false;      // forms chosen (AUTO: after the amplification estimates were read back)
   bool amps_read = false;
@@ -262,7 +267,7 @@ int add_conv_w(rtpose_net* n, const std::string& name, int cout, int cin, int k,
     c.w_off[F_DIRECT] = take(rtpose_packed_weight_floats(cout, c.cin_packed, k));
     const bool w3 = k == 3 && c.cin_packed >= 32 && conv2d_winograd_fits(3, c.cin_packed, cout, 0, 1, 8, 8, 9, 0);
     const bool w7 = k == 7 && c.cin_packed % 8 == 0 && cout_pad(cout) % 128 == 0;
-    for (int f = F_DIRECT + 1; f < kForms; ++f) {
+    for (int f = F_DIRECT + 1; f < kStdForms; ++f) {
       const int fm = kForm[f].fm;
       if (kForm[f].k == 3 && w3 && (f == F_W3_2X2 || conv2d_winograd_fits(3, c.cin_packed, cout, 0, 1, 8, 8, 9, fm)))
         c.w_off[f] = take(rtpose_packed_weight_floats_winograd3(cout, c.cin_packed, fm));
@@ -274,6 +279,17 @@ int add_conv_w(rtpose_net* n, const std::string& name, int cout, int cin, int k,
   c.b_off = take(rtpose_packed_bias_floats(cout));
   n->convs.push_back(c);
   return (int)n->convs.size() - 1;
+}
+
+// A plan created with winograd7 = 8: the F(8,7) packing of every 7x7 conv that has Winograd packings, behind everything
+// the standard layout holds (called last by build_plan).
+void add_f87_packings(rtpose_net* n) {
+  if (n->bf16 || n->w7 != 8) return;
+  for (ConvW& c : n->convs) {
+    if (!c.packed(F_W7_6)) continue;
+    c.w_off[F_W7_8] = n->wt_floats;
+    n->wt_floats += round_up(packed_weight_floats_wino7(c.cout, c.cin_packed, 8), 64);
+  }
 }
 
 // The form plan `n` runs conv `c` in.  (It is NOT chosen by batch size: the direct kernel sums in another order, and
@@ -297,7 +313,8 @@ Form pick_form(const rtpose_net* n, const ConvW& c) {
     if (tame(F_W7_4) && fits(F_W7_4)) return F_W7_4;
     return F_DIRECT;
   }
-  if (n->w7 == 6 && fits(F_W7_6)) return F_W7_6;
+  if (n->w7 == 8 && c.packed(F_W7_8) && fits(F_W7_8)) return F_W7_8;
+  if (n->w7 >= 6 && fits(F_W7_6)) return F_W7_6;
   return fits(F_W7_4) ? F_W7_4 : F_DIRECT;
 }
 
@@ -542,6 +559,7 @@ void build_plan(rtpose_net* n) {
   }
   n->catmap_off = n->wt_floats;
   n->wt_floats += 256;  // int32[192]
+  add_f87_packings(n);
   n->catmap_host.assign(kCatC, -1);  // channel map of the concat input: packed c -> source channel of cat([L1,L2,out1])
   for (int c = 0; c < 185; ++c)
     n->catmap_host[c] = c < 128 ? 57 + c : c < kCatHeat ? c - kCatPaf : 38 + (c - kCatHeat);
@@ -569,7 +587,7 @@ void build_plan(rtpose_net* n) {
     // forward allocates nothing, rtpose_net_workspace_bytes tells the whole truth and the launch list can be
     // stream-captured.  One scratch: the launches of a plan are serialised on one stream.
     n->scratch_off = round_up(n->ws_floats, 64);
-    n->scratch_bytes = conv2d_wino7_scratch_bytes(n->n_cu);
+    n->scratch_bytes = conv2d_wino7_scratch_bytes(n->n_cu, n->w7 == 8 ? 8 : 6);
     n->ws_floats = n->scratch_off + round_up(n->scratch_bytes / 4, 64);
   }
 
@@ -965,14 +983,14 @@ int rtpose_net_create_opts(int N, int H, int W, const rtpose_net_options* opt, r
                                 "(crop_with_factor pads to that, im_transform.py:128-132)");
   if (int rc = check_winograd3("net_create", opt->winograd3)) return rc;
   if (opt->winograd7 != RTPOSE_WINO_DEFAULT && opt->winograd7 != 0 && opt->winograd7 != 4 && opt->winograd7 != 6 &&
-      opt->winograd7 != RTPOSE_WINO7_AUTO)
-    return fail(RTPOSE_E_INVAL, "net_create: winograd7 must be RTPOSE_WINO_DEFAULT, 0, 4, 6 or RTPOSE_WINO7_AUTO");
+      opt->winograd7 != 8 && opt->winograd7 != RTPOSE_WINO7_AUTO)
+    return fail(RTPOSE_E_INVAL, "net_create: winograd7 must be RTPOSE_WINO_DEFAULT, 0, 4, 6, 8 or RTPOSE_WINO7_AUTO");
   rtpose_net* n = new_plan(N, H, W, opt->winograd3, opt->amp_limit);
   n->bf16 = dtype != RTPOSE_DTYPE_F32;
   n->split = dtype == RTPOSE_DTYPE_BF16X3;
   {
     // defaults of winograd3 (default_winograd3) and winograd7: on, unless the environment of the process says otherwise
-    // (RTPOSE_WINOGRAD = 0: direct kernels everywhere, 3 / 7: only that kernel size in Winograd form; RTPOSE_WINOGRAD7_M=4: F(4,7))
+    // (RTPOSE_WINOGRAD = 0: direct kernels everywhere, 3 / 7: only that kernel size in Winograd form; RTPOSE_WINOGRAD7_M=4: F(4,7), =8: F(8,7))
     const int env = winograd_env();
     // Round 4: the default is the GUARDED choice - per layer, the fastest form whose amplification estimate for the
     // filters actually loaded stays under amp_limit (256): nobody here has seen pose_model.pth (README.md:19), and a
@@ -980,8 +998,9 @@ int rtpose_net_create_opts(int N, int H, int W, const rtpose_net_options* opt, r
     // 42-43, so the bench plan keeps its forms bit for bit; RTPOSE_WINOGRAD3_M / RTPOSE_WINOGRAD7_M force a form.
     const char* e7 = getenv("RTPOSE_WINOGRAD7_M");
     n->w7 = opt->winograd7 != RTPOSE_WINO_DEFAULT ? opt->winograd7
-            : (env == 1 || env == 7)              ? ((e7 && (e7[0] == '4' || e7[0] == '6')) ? wino7_default_fm()
-                                                                                           : RTPOSE_WINO7_AUTO)
+            : (env == 1 || env == 7)              ? ((e7 && e7[0] == '8')                     ? 8
+                                                     : (e7 && (e7[0] == '4' || e7[0] == '6')) ? wino7_default_fm()
+                                                                                              : RTPOSE_WINO7_AUTO)
                                                   : 0;
     // RTPOSE_W7_PERSIST=0 in the environment of the process: plans start with the split-tile launches off
     // (rtpose_net_set_persistent7 changes it per plan)
@@ -1221,7 +1240,8 @@ int rtpose_net_load_conv(rtpose_net* net, int idx, const float* w_oihw, const fl
                                                         net->wt + c.b_off, stream)
                    : pack_weights_wino7_launch(w_oihw, bias, c.cout, c.cin_src, map, c.cin_packed, fi.fm, wp,
                                                net->wt + c.b_off, s);
-    if (!rc) rc = rtpose_winograd_amplification(w_oihw, c.cout, c.cin_src, fi.k, fi.fm, amp + fi.amp_slot, stream);
+    if (!rc && fi.amp_slot >= 0)
+      rc = rtpose_winograd_amplification(w_oihw, c.cout, c.cin_src, fi.k, fi.fm, amp + fi.amp_slot, stream);
     if (rc) return rc;
   }
   return 0;

@@ -60,6 +60,7 @@ class _Plan(object):
         self.shape = (n, h, w)
         self.dtype = dtype
         self.wino = wino
+        self.wkey = _arena_key(torch.device(device).index, dtype, wino)   # the arena it is bound to
         ws_bytes = lib.rtpose_net_workspace_bytes(handle)
         self.workspace = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=device)
         check(lib.rtpose_net_bind(handle, ptr(self.workspace), ws_bytes, ptr(weights),
@@ -72,6 +73,12 @@ class _Plan(object):
             lib.rtpose_net_destroy(self.handle)
         except Exception:
             pass
+
+
+def _arena_key(index, dtype, wino):
+    """Plans of a module share the weight arena of their (device, dtype) - except the fp32 plans that force F(8,7): their
+    arena is the standard layout followed by the F(8,7) packings of the 7x7 convs, and it is kept apart."""
+    return (index, dtype, 'f87') if dtype == _capi.DTYPE_F32 and wino[1] == 8 else (index, dtype)
 
 
 _DTYPES = {'fp32': _capi.DTYPE_F32, 'bf16': _capi.DTYPE_BF16, 'bf16x3': _capi.DTYPE_BF16X3}
@@ -109,8 +116,10 @@ class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
         F(2x2,3x3), 4 = F(4x4,3x3) forced, 'auto' = per layer F(4x4,3x3) if its amplification estimate is <=
         ``amp_limit``, else F(2x2,3x3);
         ``winograd7``: None = library default ('auto'), 0 = direct, 4 / 6 = F(4,7) / F(6,7) forced, 'auto' = per layer
-        the fastest form whose amplification estimate for the loaded filters is <= ``amp_limit`` (default 256).
-        All forms read one weight arena; results of different forms differ by rounding only."""
+        the fastest form whose amplification estimate for the loaded filters is <= ``amp_limit`` (default 256);
+        8 = F(8,7) forced: opt-in only ('auto' never chooses it), 12.5 % fewer matrix multiplies than F(6,7) for ~8x
+        its error bound; such plans keep a weight arena of their own (the standard one followed by the F(8,7) packings).
+        All other forms read one weight arena; results of different forms differ by rounding only."""
         if winograd3 is None:
             w3 = _capi.WINO_DEFAULT
         elif winograd3 == 'auto':
@@ -125,10 +134,10 @@ class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
             w7 = _capi.WINO_DEFAULT
         elif winograd7 == 'auto':
             w7 = _capi.WINO7_AUTO
-        elif winograd7 in (0, 4, 6):
+        elif winograd7 in (0, 4, 6, 8):
             w7 = int(winograd7)
         else:
-            raise ValueError("winograd7 must be None, 0, 4, 6 or 'auto'")
+            raise ValueError("winograd7 must be None, 0, 4, 6, 8 or 'auto'")
         self._wino = (w3, w7, float(amp_limit or 0.0))
         return self
 
@@ -163,7 +172,7 @@ class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
 
     def _sync_weights(self, plan, device):
         convs = self._convs()
-        wkey = (device.index, plan.dtype)
+        wkey = plan.wkey
         key = self._params_key([t for _, m in convs for t in (m.weight, m.bias)])
         if key == self._weights_key.get(wkey) and not self.always_resync:
             return
@@ -211,11 +220,15 @@ class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
         with self._native_lock, torch.cuda.device(x.device):
             plan = self._plans.get(key)
             if plan is None:
-                wkey = (x.device.index, dtype)
+                wkey = _arena_key(x.device.index, dtype, wino)
                 weights = self._weights.get(wkey)
                 if weights is None:
                     probe = C.c_void_p()
-                    check(lib.rtpose_net_create_ex(1, 8, 8, dtype, C.byref(probe)))
+                    if len(wkey) == 3:      # sized by a probe plan with the same option
+                        popts = _capi.NetOptions.make(dtype, _capi.WINO_DEFAULT, 8, 0.0)
+                        check(lib.rtpose_net_create_opts(1, 8, 8, C.byref(popts), C.byref(probe)))
+                    else:
+                        check(lib.rtpose_net_create_ex(1, 8, 8, dtype, C.byref(probe)))
                     wb = lib.rtpose_net_weight_bytes(probe)
                     lib.rtpose_net_destroy(probe)
                     weights = torch.zeros(wb // 4 + 64, dtype=torch.float32, device=x.device)
