@@ -927,6 +927,77 @@ int rtpose_decode_batch_ex(const float* heat, const rtpose_layout* lheat,
  * (scipy _gaussian_kernel1d(sigma=3, radius=12)); returns 25, or < 0. */
 int rtpose_gaussian_kernel1d(double* weights, int cap);
 
+/* ---- 4a. The same decoder with the skeleton as data ---------------------------------
+ * The entry points above decode COCO-18 maps (18 parts, 19 limbs over 38 PAF channels;
+ * their tables are compiled into the kernels).  The `_skel` entry points below run the
+ * same algorithm - NMS and the bicubic patch refine, the ten-sample PAF score with its two
+ * thresholds, the score-sorted greedy assignment (std::sort replayed on an exact tie),
+ * subset-row grouping and merging (cid 0 reads as absent; a person needs at least 4 parts
+ * and a score ratio of at least 0.3) - over a table the caller passes:
+ *   limb l joins part limb_part[l][0] (A) to limb_part[l][1] (B); its field is PAF
+ *   channel limb_paf[l][0] (x) and limb_paf[l][1] (y); the limbs are walked in table
+ *   order; bit l of seed_mask: a connection of limb l that matches no person starts one
+ *   (the reference's `pair_id < 18` is 0x3FFFF for COCO-18).
+ * The struct travels by value into the kernels as a launch argument: nothing is uploaded,
+ * two streams may decode different skeletons at the same time.
+ *
+ * Record of the _skel entry points, per image (P = num_parts, L = num_limbs):
+ *   int32 header[8]: n_peaks, n_humans, overflow_flags, max_peaks_per_part, max_humans,
+ *                    P, L, 0   (the entry points above leave words 5 and 6 zero: a
+ *                    record with 0 there is a COCO-18 record, 18 / 19)
+ *   int32 part_count[P]                          at word 8
+ *   rtpose_peak peaks[P * max_peaks_per_part]    at word max(32, round_up(8 + P, 4)):
+ *                                                any P up to 24 lays out as above
+ *   int32 human_parts[max_humans][P]             (cid, -1 = absent)
+ *   float human_score[max_humans]
+ * and the whole rounded up to 4 words.  A block describes itself: P, L and both capacities
+ * are in its header.  With rtpose_skeleton_coco18 the record equals the one of
+ * rtpose_decode_batch_ex word for word except header words 5 and 6.
+ *
+ * Not covered by a skeleton (COCO-18 only): rtpose_flip_merge / rtpose_tta_accumulate (they
+ * carry COCO-18's left / right permutations) and the legacy process_paf API of section 6. */
+#define RTPOSE_SKEL_MAX_PARTS 32
+#define RTPOSE_SKEL_MAX_LIMBS 32 /* 64 PAF channels: the limit of the native models */
+
+typedef struct rtpose_skeleton {
+  uint32_t struct_bytes;      /* sizeof(rtpose_skeleton)                            */
+  int32_t num_parts;          /* P, 1..32 (the heat map has at least P channels)    */
+  int32_t num_limbs;          /* L, 1..32                                           */
+  int32_t limb_part[RTPOSE_SKEL_MAX_LIMBS][2]; /* (part A, part B)                  */
+  int32_t limb_paf[RTPOSE_SKEL_MAX_LIMBS][2];  /* (PAF x channel, PAF y channel)    */
+  uint32_t seed_mask;         /* bit l: limb l may start a person                   */
+} rtpose_skeleton;
+
+/* Presets.  COCO-18: the tables of lib/pafprocess/pafprocess.h:16-24.
+ * BODY_25: 25 parts (heat-map channel 25 is background), 26 limbs over 52 PAF channels,
+ * every limb may seed; the tables were written from memory of upstream OpenPose's
+ * poseParameters.cpp and are NOT VERIFIED against CMU's weights.  The grouping run over
+ * them is this library's (the tf-pose pafprocess algorithm), not OpenPose's own. */
+int rtpose_skeleton_coco18(rtpose_skeleton* skel);
+int rtpose_skeleton_body25(rtpose_skeleton* skel);
+
+/* Host only.  0, or an error whose message names the limb: a part index outside
+ * [0, num_parts) or a PAF channel outside [0, paf_channels); a limb with A == B; the same
+ * (A, B) limb twice; x channel == y channel; num_parts / num_limbs outside 1..32 or more
+ * parts than heat_channels; seed bits at or above num_limbs; a wrong struct_bytes. */
+int rtpose_skeleton_check(const rtpose_skeleton* skel, int heat_channels, int paf_channels);
+
+/* Sizes for N images; 0 on a bad cfg / skeleton.  cfg->num_keypoints must be in
+ * 1..num_parts (parts at or above it keep empty peak lists). */
+size_t rtpose_decode_workspace_bytes_skel(const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel, int N);
+size_t rtpose_decode_result_bytes_skel(const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel, int N);
+
+int rtpose_nms_batch_skel(const float* heat, const rtpose_layout* lheat, int N, int h, int w,
+                          const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel,
+                          int nms_flags, void* result, void* stream);
+/* The skeleton is checked against the channels the two views can address
+ * (cstride - choff) before anything is launched. */
+int rtpose_decode_batch_skel(const float* heat, const rtpose_layout* lheat, const float* paf,
+                             const rtpose_layout* lpaf, int N, int h, int w,
+                             const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel,
+                             int nms_flags, void* workspace, size_t workspace_bytes,
+                             void* result, void* stream);
+
 /* ------------------------------------------------------------------------
  * 5. Flip test-time-augmentation merge
  *    stands in for evaluate/coco_eval.py:197-242 (handle_paf_and_heat).

@@ -101,6 +101,16 @@ class DecodeCfg(C.Structure):
                 ("max_humans", C.c_int32)]
 
 
+SKEL_MAX_PARTS, SKEL_MAX_LIMBS = 32, 32
+
+
+class SkeletonStruct(C.Structure):
+    """rtpose_skeleton: the tables of a `_skel` decode (header section 4a); skeleton.Skeleton.native() fills one."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("num_parts", C.c_int32), ("num_limbs", C.c_int32),
+                ("limb_part", (C.c_int32 * 2) * SKEL_MAX_LIMBS), ("limb_paf", (C.c_int32 * 2) * SKEL_MAX_LIMBS),
+                ("seed_mask", C.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -249,6 +259,14 @@ _SIGS = {
     "rtpose_nms_batch_ex": (_i, [_vp, _LP, _i, _i, _i, C.POINTER(DecodeCfg), _i, _vp, _vp]),
     "rtpose_decode_batch_ex": (_i, [_vp, _LP, _vp, _LP, _i, _i, _i, C.POINTER(DecodeCfg), _i, _vp, _sz, _vp, _vp]),
     "rtpose_gaussian_kernel1d": (_i, [C.POINTER(C.c_double), _i]),
+    "rtpose_skeleton_coco18": (_i, [C.POINTER(SkeletonStruct)]),
+    "rtpose_skeleton_body25": (_i, [C.POINTER(SkeletonStruct)]),
+    "rtpose_skeleton_check": (_i, [C.POINTER(SkeletonStruct), _i, _i]),
+    "rtpose_decode_workspace_bytes_skel": (_sz, [C.POINTER(DecodeCfg), C.POINTER(SkeletonStruct), _i]),
+    "rtpose_decode_result_bytes_skel": (_sz, [C.POINTER(DecodeCfg), C.POINTER(SkeletonStruct), _i]),
+    "rtpose_nms_batch_skel": (_i, [_vp, _LP, _i, _i, _i, C.POINTER(DecodeCfg), C.POINTER(SkeletonStruct), _i, _vp, _vp]),
+    "rtpose_decode_batch_skel": (_i, [_vp, _LP, _vp, _LP, _i, _i, _i, C.POINTER(DecodeCfg), C.POINTER(SkeletonStruct), _i,
+                                      _vp, _sz, _vp, _vp]),
     "rtpose_preprocess_u8_batch": (_i, [C.POINTER(PrepImage), _i, _i, _vp, _LP, _i, _i, _vp]),
     "rtpose_preprocess_u8": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_preprocess_u8_flip": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _i, _vp]),

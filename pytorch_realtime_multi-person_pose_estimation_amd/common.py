@@ -31,16 +31,18 @@ class CocoPart(Enum):
 
 class BodyPart(object):
     """part_idx: part index (0 = nose); x, y: normalised coordinates; score: peak score."""
-    __slots__ = ('uidx', 'part_idx', 'x', 'y', 'score')
+    __slots__ = ('uidx', 'part_idx', 'x', 'y', 'score', 'name')
 
-    def __init__(self, uidx, part_idx, x, y, score):
+    def __init__(self, uidx, part_idx, x, y, score, name=None):
         self.uidx = uidx
         self.part_idx = part_idx
         self.x, self.y = x, y
         self.score = score
+        self.name = name        # a skeleton's own part name (decode.humans_from_record); None: COCO-18
 
     def get_part_name(self):
-        return CocoPart(self.part_idx)
+        """CocoPart for COCO-18; the part's name (a string) for a part decoded with another skeleton."""
+        return CocoPart(self.part_idx) if self.name is None else self.name
 
     def __str__(self):
         return 'BodyPart:%d-(%.2f, %.2f) score=%.2f' % (self.part_idx, self.x, self.y, self.score)
@@ -99,10 +101,13 @@ CocoPairs = [(1, 2), (1, 5), (2, 3), (3, 4), (5, 6), (6, 7), (1, 8), (8, 9), (9,
 CocoPairsRender = CocoPairs[:-2]
 
 
-def draw_humans(npimg, humans, imgcopy=False):
+def draw_humans(npimg, humans, imgcopy=False, skeleton=None):
     """lib/utils/common.py:227-251 without cv2: filled 3-px discs at the joints and
-    3-px lines along CocoPairsRender, drawn with numpy (visualisation only)."""
+    3-px lines along CocoPairsRender, drawn with numpy (visualisation only).
+    skeleton: a skeleton.Skeleton - its parts and all its limbs are drawn instead (the colours repeat)."""
     import numpy as np
+    nparts = CocoPart.Background.value if skeleton is None else skeleton.num_parts
+    pairs = CocoPairsRender if skeleton is None else skeleton.pairs
     if imgcopy:
         npimg = np.copy(npimg)
     h, w = npimg.shape[:2]
@@ -117,17 +122,17 @@ def draw_humans(npimg, humans, imgcopy=False):
 
     for human in humans:
         centers = {}
-        for i in range(CocoPart.Background.value):
+        for i in range(nparts):
             if i not in human.body_parts:
                 continue
             bp = human.body_parts[i]
             centers[i] = (int(bp.x * w + 0.5), int(bp.y * h + 0.5))
-            disc(centers[i][0], centers[i][1], 4, CocoColors[i])
-        for order, (a, b) in enumerate(CocoPairsRender):
+            disc(centers[i][0], centers[i][1], 4, CocoColors[i % len(CocoColors)])
+        for order, (a, b) in enumerate(pairs):
             if a not in centers or b not in centers:
                 continue
             (xa, ya), (xb, yb) = centers[a], centers[b]
             n = max(abs(xb - xa), abs(yb - ya), 1)
             for t in range(n + 1):
-                disc(xa + (xb - xa) * t // n, ya + (yb - ya) * t // n, 1, CocoColors[order])
+                disc(xa + (xb - xa) * t // n, ya + (yb - ya) * t // n, 1, CocoColors[order % len(CocoColors)])
     return npimg

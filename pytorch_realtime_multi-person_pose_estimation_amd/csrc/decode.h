@@ -58,6 +58,50 @@ inline size_t decode_workspace_bytes(const rtpose_decode_cfg* c, int N) {
          decode_ws_tie_bytes(c, N);
 }
 
+// ---- the same sizes for a skeleton of P parts and L limbs (decode_skel.hip): every one a function of P and L, and every
+// ---- fit decision taken on bytes.  With P = 18, L = 19 each equals its COCO-18 counterpart above.
+constexpr int kLdsRowBytes = kLdsRows * 21 * (int)sizeof(float);  // the LDS share of the subset rows (720 rows of 21 floats)
+
+// peaks start behind the part counts, at a multiple of 4 words and never below kResPeaks: any P up to 24 lays out as today
+__host__ __device__ inline int skel_peaks_word(int P) {
+  const int w = (kResPartCount + P + 3) & ~3;
+  return w < kResPeaks ? kResPeaks : w;
+}
+inline int skel_result_words(const rtpose_decode_cfg* c, int P) {
+  const int w = skel_peaks_word(P) + 4 * P * c->max_peaks_per_part + (P + 1) * c->max_humans;
+  return (w + 3) & ~3;
+}
+// per image: L x { count, (a, b, score) x pcap }
+inline int skel_conn_words(const rtpose_decode_cfg* c, int L) { return L * (1 + 3 * c->max_peaks_per_part); }
+// a subset row: P cids, the score sum, the part count, alive
+inline size_t skel_rows_bytes(const rtpose_decode_cfg* c, int P) {
+  return (size_t)decode_row_cap(c) * (P + 3) * sizeof(float);
+}
+inline bool skel_rows_in_lds(const rtpose_decode_cfg* c, int P) { return skel_rows_bytes(c, P) <= (size_t)kLdsRowBytes; }
+inline bool skel_scores_in_lds(const rtpose_decode_cfg* c) {
+  const size_t p = (size_t)c->max_peaks_per_part;
+  return p * p * sizeof(float) <= (size_t)kLdsPairs * sizeof(float);
+}
+inline size_t skel_ws_conn_bytes(const rtpose_decode_cfg* c, int L, int N) {
+  return round_up((size_t)N * skel_conn_words(c, L) * sizeof(int32_t), 256);
+}
+inline size_t skel_ws_score_bytes(const rtpose_decode_cfg* c, int L, int N) {
+  const size_t p = (size_t)c->max_peaks_per_part;
+  return skel_scores_in_lds(c) ? 0 : round_up((size_t)N * L * p * p * sizeof(float), 256);
+}
+inline size_t skel_ws_rows_bytes(const rtpose_decode_cfg* c, int P, int N) {
+  return skel_rows_in_lds(c, P) ? 0 : round_up((size_t)N * skel_rows_bytes(c, P), 256);
+}
+inline size_t skel_ws_tie_bytes(const rtpose_decode_cfg* c, int L, int N) {
+  const size_t p = (size_t)c->max_peaks_per_part;
+  if (p * p * sizeof(unsigned long long) <= (size_t)kTieLdsCands * sizeof(unsigned long long)) return 0;
+  return round_up((size_t)N * L * p * p * sizeof(unsigned long long), 256);
+}
+inline size_t skel_workspace_bytes(const rtpose_decode_cfg* c, int P, int L, int N) {
+  return skel_ws_conn_bytes(c, L, N) + skel_ws_score_bytes(c, L, N) + skel_ws_rows_bytes(c, P, N) +
+         skel_ws_tie_bytes(c, L, N);
+}
+
 // with_ids: also run peak_prefix_kernel (the running peak ids + the peak total); a full decode leaves that to
 // assign_group_launch(write_ids = true), which writes them in its grouping kernel
 int nms_launch(const float* heat, const rtpose_layout* lheat, int N, int h, int w,

@@ -17,17 +17,31 @@ from ._capi import lib, check, ptr, current_stream, Layout, DecodeCfg, NUM_PART
 from .common import Human, BodyPart
 
 RES_HEADER, RES_PART_COUNT, RES_PEAKS = 0, 8, 32
+RES_NUM_PARTS, RES_NUM_LIMBS = 5, 6     # header words of a `_skel` record; 0 in a record of the COCO-18 entry points
 OVERFLOW_PEAKS, OVERFLOW_HUMANS = 1, 2
 MAX_PEAKS_LIMIT = 1024
 MAX_HUMANS_LIMIT = 16384
 
 
-def default_config():
-    """The four cfg keys the decoder reads (lib/config/default.py:40,41,69,126)."""
+def default_config(skeleton=None):
+    """The four cfg keys the decoder reads (lib/config/default.py:40,41,69,126); NUM_KEYPOINTS = the skeleton's parts."""
     return types.SimpleNamespace(
-        MODEL=types.SimpleNamespace(NUM_KEYPOINTS=18, DOWNSAMPLE=8),
+        MODEL=types.SimpleNamespace(NUM_KEYPOINTS=18 if skeleton is None else skeleton.num_parts, DOWNSAMPLE=8),
         DATASET=types.SimpleNamespace(IMAGE_SIZE=368),
         TEST=types.SimpleNamespace(THRESH_HEATMAP=0.1))
+
+
+def record_parts(rec):
+    """Part count P of a record: header word 5, where 0 (a record of the COCO-18 entry points) means 18.  Those entry
+    points define header words 0..4 only, so anything in words 5 / 6 that is not a (P, L) pair of a `_skel` record - both
+    in 1..32 - reads as COCO-18 as well."""
+    p, l = int(rec[RES_HEADER + RES_NUM_PARTS]), int(rec[RES_HEADER + RES_NUM_LIMBS])
+    return p if 1 <= p <= _capi.SKEL_MAX_PARTS and 1 <= l <= _capi.SKEL_MAX_LIMBS else NUM_PART
+
+
+def peaks_word(num_parts):
+    """Word at which a record's peaks start: behind the part counts, a multiple of 4, never below 32 (header 4a)."""
+    return max(RES_PEAKS, (RES_PART_COUNT + num_parts + 3) & ~3)
 
 
 def make_cfg(config=None, max_peaks_per_part=32, max_humans=64):
@@ -39,11 +53,17 @@ def make_cfg(config=None, max_peaks_per_part=32, max_humans=64):
 class DecodeBuffers(object):
     """Device scratch + result block for N images at a given capacity."""
 
-    def __init__(self, cfg, n, device):
+    def __init__(self, cfg, n, device, skeleton=None):
         self.cfg = cfg
         self.n = n
-        ws = lib.rtpose_decode_workspace_bytes(C.byref(cfg), n)
-        rb = lib.rtpose_decode_result_bytes(C.byref(cfg), n)
+        self.skeleton = skeleton
+        self.skel = skeleton.native() if skeleton is not None else None   # None: the COCO-18 entry points
+        if self.skel is None:
+            ws = lib.rtpose_decode_workspace_bytes(C.byref(cfg), n)
+            rb = lib.rtpose_decode_result_bytes(C.byref(cfg), n)
+        else:
+            ws = lib.rtpose_decode_workspace_bytes_skel(C.byref(cfg), C.byref(self.skel), n)
+            rb = lib.rtpose_decode_result_bytes_skel(C.byref(cfg), C.byref(self.skel), n)
         if ws == 0 or rb == 0:
             raise _capi.RtposeError("bad decode config: " + _capi.last_error())
         self.workspace = torch.empty(ws // 4, dtype=torch.int32, device=device)
@@ -54,9 +74,18 @@ class DecodeBuffers(object):
 
 def decode_enqueue(heat_ptr, lheat, paf_ptr, lpaf, n, h, w, bufs, nms_only=False, nms_flags=0):
     """Enqueue the decode kernels on the current stream (device pointers + layouts).
-    nms_flags: _capi.NMS_NO_REFINE | _capi.NMS_GAUSSIAN (the optional branches of NMS, paf_to_pose.py:67)."""
+    nms_flags: _capi.NMS_NO_REFINE | _capi.NMS_GAUSSIAN (the optional branches of NMS, paf_to_pose.py:67).
+    Buffers made with a skeleton go through the `_skel` entry points, all others through the COCO-18 ones."""
     cfg = bufs.cfg
-    if nms_only:
+    skel = getattr(bufs, "skel", None)
+    if skel is not None and nms_only:
+        check(lib.rtpose_nms_batch_skel(heat_ptr, C.byref(lheat), n, h, w, C.byref(cfg), C.byref(skel), nms_flags,
+                                        ptr(bufs.result), current_stream()), "rtpose_nms_batch_skel")
+    elif skel is not None:
+        check(lib.rtpose_decode_batch_skel(heat_ptr, C.byref(lheat), paf_ptr, C.byref(lpaf), n, h, w, C.byref(cfg),
+                                           C.byref(skel), nms_flags, ptr(bufs.workspace), bufs.workspace.numel() * 4,
+                                           ptr(bufs.result), current_stream()), "rtpose_decode_batch_skel")
+    elif nms_only:
         check(lib.rtpose_nms_batch_ex(heat_ptr, C.byref(lheat), n, h, w, C.byref(cfg), nms_flags, ptr(bufs.result),
                                       current_stream()), "rtpose_nms_batch_ex")
     else:
@@ -74,18 +103,20 @@ def fetch(bufs):
 
 
 def parse_image(rec, cfg=None):
-    """One image's record -> dict(peaks=[P,5] float32 joint_list, parts=[H,18], score=[H], flags).
+    """One image's record -> dict(peaks=[P,5] float32 joint_list, parts=[H,num_parts], score=[H], flags).
     The capacities the record was written with are read from its own header (words 3, 4); ``cfg`` is only
-    consulted for records without them."""
+    consulted for records without them.  The part count is header word 5 (0 = 18)."""
     pcap, hcap = int(rec[RES_HEADER + 3]), int(rec[RES_HEADER + 4])
     if pcap <= 0 or hcap <= 0:
         if cfg is None:
             raise _capi.RtposeError("record carries no capacities and no cfg was given")
         pcap, hcap = cfg.max_peaks_per_part, cfg.max_humans
-    counts = rec[RES_PART_COUNT:RES_PART_COUNT + NUM_PART]
-    pk = rec[RES_PEAKS:RES_PEAKS + 4 * NUM_PART * pcap].reshape(NUM_PART, pcap, 4)
+    npart = record_parts(rec)
+    pk0 = peaks_word(npart)
+    counts = rec[RES_PART_COUNT:RES_PART_COUNT + npart]
+    pk = rec[pk0:pk0 + 4 * npart * pcap].reshape(npart, pcap, 4)
     rows = []
-    for p in range(NUM_PART):
+    for p in range(npart):
         c = int(counts[p])
         if c:
             blk = pk[p, :c]
@@ -94,11 +125,11 @@ def parse_image(rec, cfg=None):
                                   np.full(c, p, np.float32)], axis=1))
     peaks = np.concatenate(rows, 0) if rows else np.zeros((0, 5), np.float32)
     nh = int(rec[RES_HEADER + 1])
-    off = RES_PEAKS + 4 * NUM_PART * pcap
-    parts = rec[off:off + NUM_PART * hcap].reshape(hcap, NUM_PART)[:nh].copy()
-    score = rec[off + NUM_PART * hcap:off + NUM_PART * hcap + hcap].copy().view(np.float32)[:nh].copy()
+    off = pk0 + 4 * npart * pcap
+    parts = rec[off:off + npart * hcap].reshape(hcap, npart)[:nh].copy()
+    score = rec[off + npart * hcap:off + npart * hcap + hcap].copy().view(np.float32)[:nh].copy()
     return {"peaks": peaks, "parts": parts, "score": score, "flags": int(rec[RES_HEADER + 2]),
-            "n_peaks": int(rec[RES_HEADER])}
+            "n_peaks": int(rec[RES_HEADER]), "num_parts": npart}
 
 
 def result_mask(block):
@@ -108,24 +139,28 @@ def result_mask(block):
     (``np.array_equal(a[m], b[m])`` with ``m = result_mask(b)``; a differing count differs inside the mask)."""
     block = np.asarray(block)
     pcap, hcap = int(block[0, RES_HEADER + 3]), int(block[0, RES_HEADER + 4])
+    npart = record_parts(block[0])
+    pk0 = peaks_word(npart)
     mask = np.zeros(block.shape, dtype=bool)
     mask[:, RES_HEADER:RES_HEADER + 5] = True
-    mask[:, RES_PART_COUNT:RES_PART_COUNT + NUM_PART] = True
-    hoff = RES_PEAKS + 4 * NUM_PART * pcap
+    mask[:, RES_PART_COUNT:RES_PART_COUNT + npart] = True
+    hoff = pk0 + 4 * npart * pcap
     for b in range(block.shape[0]):
-        for p in range(NUM_PART):
+        for p in range(npart):
             c = min(int(block[b, RES_PART_COUNT + p]), pcap)
-            o = RES_PEAKS + 4 * p * pcap
+            o = pk0 + 4 * p * pcap
             mask[b, o:o + 4 * c] = True
         nh = min(int(block[b, RES_HEADER + 1]), hcap)
-        mask[b, hoff:hoff + NUM_PART * nh] = True
-        mask[b, hoff + NUM_PART * hcap:hoff + NUM_PART * hcap + nh] = True
+        mask[b, hoff:hoff + npart * nh] = True
+        mask[b, hoff + npart * hcap:hoff + npart * hcap + nh] = True
     return mask
 
 
-def decode_maps(heat, paf, config=None, max_peaks_per_part=32, max_humans=64, nms_only=False, nms_flags=0):
+def decode_maps(heat, paf, config=None, max_peaks_per_part=32, max_humans=64, nms_only=False, nms_flags=0, skeleton=None):
     """heat [N,h,w,C>=num_keypoints], paf [N,h,w,38]: dense NHWC float32 CUDA tensors.
-    Returns a list of per-image dicts (see parse_image).  Grows capacities on overflow."""
+    Returns a list of per-image dicts (see parse_image).  Grows capacities on overflow.
+    skeleton: a skeleton.Skeleton - the maps are then its heat_channels / paf_channels wide and the decode runs through
+    the `_skel` entry points; None: COCO-18 through the original ones."""
     if not heat.is_cuda:
         raise _capi.RtposeError("decode runs on the GPU only (no CPU fallback); got a CPU tensor")
     n, h, w, ch = heat.shape
@@ -133,10 +168,11 @@ def decode_maps(heat, paf, config=None, max_peaks_per_part=32, max_humans=64, nm
     paf = paf.contiguous().float()
     lheat = Layout.dense(ch, h, w)
     lpaf = Layout.dense(paf.shape[3], h, w)
+    config = config or default_config(skeleton)
     while True:
         cfg = make_cfg(config, max_peaks_per_part, max_humans)
         with torch.cuda.device(heat.device):      # kernels + stream of the maps' device, whatever is current
-            bufs = DecodeBuffers(cfg, n, heat.device)
+            bufs = DecodeBuffers(cfg, n, heat.device, skeleton)
             decode_enqueue(ptr(heat), lheat, ptr(paf), lpaf, n, h, w, bufs, nms_only=nms_only, nms_flags=nms_flags)
             recs = fetch(bufs)
         flags = int(np.bitwise_or.reduce(recs[:, RES_HEADER + 2]))
@@ -153,9 +189,13 @@ def decode_maps(heat, paf, config=None, max_peaks_per_part=32, max_humans=64, nm
         return [parse_image(recs[i], cfg) for i in range(n)]
 
 
-def humans_from_record(rec, up_w, up_h, num_keypoints=18):
-    """paf_to_pose.py:387-404: result dict -> list[Human] with normalised coordinates."""
+def humans_from_record(rec, up_w, up_h, num_keypoints=18, skeleton=None):
+    """paf_to_pose.py:387-404: result dict -> list[Human] with normalised coordinates.
+    skeleton: every part of the skeleton is read (num_keypoints is ignored) and the BodyParts carry its part names."""
     humans = []
+    names = None
+    if skeleton is not None:
+        num_keypoints, names = skeleton.num_parts, skeleton.part_names
     peaks = rec["peaks"]
     for hid in range(rec["parts"].shape[0]):
         human = Human([])
@@ -167,7 +207,8 @@ def humans_from_record(rec, up_w, up_h, num_keypoints=18):
             added = True
             human.body_parts[part_idx] = BodyPart('%d-%d' % (hid, part_idx), part_idx,
                                                   float(int(peaks[cid, 0])) / up_w,
-                                                  float(int(peaks[cid, 1])) / up_h, float(peaks[cid, 2]))
+                                                  float(int(peaks[cid, 1])) / up_h, float(peaks[cid, 2]),
+                                                  names[part_idx] if names else None)
         if added:
             human.score = float(rec["score"][hid])
             humans.append(human)

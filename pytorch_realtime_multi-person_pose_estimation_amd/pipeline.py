@@ -44,8 +44,9 @@ class SideDecoder(object):
     are not supported (the later decode's event replaces the earlier one's).  The plan's device error word (persistent 7x7 hand-over, fp32 plans) rides in front of every decode and
     is checked in wait().  Two slots (record block, pinned copy, events, error word)."""
 
-    def __init__(self, config):
+    def __init__(self, config, skeleton=None):
         self.config = config
+        self.skeleton = skeleton    # skeleton.Skeleton: the `_skel` entry points; None: the COCO-18 ones
         self.stream = None
         self.slots = [None, None]
         self.last = None            # slot of the decode enqueued last
@@ -87,7 +88,7 @@ class SideDecoder(object):
                     self.close()        # a guard must not outlive its event
                     self.last = None
             cfg = dec.make_cfg(self.config, max_peaks_per_part, max_humans)
-            slot = {"key": key, "bufs": dec.DecodeBuffers(cfg, n, device), "maps": torch.cuda.Event(),
+            slot = {"key": key, "bufs": dec.DecodeBuffers(cfg, n, device, self.skeleton), "maps": torch.cuda.Event(),
                     "dec_done": torch.cuda.Event(), "done": torch.cuda.Event(), "host": None,
                     "err": torch.zeros(1, dtype=torch.int32).pin_memory(), "plan": None}
             self.slots[i] = slot
@@ -132,16 +133,31 @@ class SideDecoder(object):
         return slot["bufs"], slot["host"].numpy()
 
 
-class PoseEstimator(object):
-    def __init__(self, model, config=None, max_peaks_per_part=32, max_humans=64):
-        # the decoder is COCO-18: 38 PAF and 19 heat-map channels (a model with other counts, e.g. OpenPose_Model's
-        # defaults of 14 / 9, is refused here rather than decoded wrongly)
-        chans = (getattr(model, 'paf_out_channels', 38), getattr(model, 'heat_out_channels', 19))
+def _check_model_channels(model, skeleton):
+    """-> (PAF channels, heat-map channels) the decoder reads.  Without a skeleton the decoder is COCO-18: 38 PAF and 19
+    heat-map channels (a model with other counts, e.g. OpenPose_Model's defaults of 14 / 9, is refused rather than
+    decoded wrongly).  With one, the model must write exactly the skeleton's channel counts."""
+    chans = (getattr(model, 'paf_out_channels', 38), getattr(model, 'heat_out_channels', 19))
+    if skeleton is None:
         if chans != (38, 19):
             raise ValueError("PoseEstimator decodes COCO-18 maps (38 PAF, 19 heat-map channels); the model has %d / %d"
                              % chans)
+        return 38, 19
+    want = (skeleton.paf_channels, skeleton.heat_channels)
+    if chans != want:
+        raise ValueError("PoseEstimator: skeleton %s reads %d PAF / %d heat-map channels; the model has %d / %d"
+                         % ((skeleton.name,) + want + chans))
+    return want
+
+
+class PoseEstimator(object):
+    """skeleton: a skeleton.Skeleton (e.g. skeleton.BODY_25) whose tables the decoder runs over; None: COCO-18."""
+
+    def __init__(self, model, config=None, max_peaks_per_part=32, max_humans=64, skeleton=None):
+        self.paf_channels, self.heat_channels = _check_model_channels(model, skeleton)
+        self.skeleton = skeleton
         self.model = model
-        self.config = config or dec.default_config()
+        self.config = config or dec.default_config(skeleton)
         # a model may say at which stride its maps are (hourglass.HourglassNet: 4); models that do not are at stride 8
         self.stride = getattr(model, 'output_stride', None)
         if self.stride is not None and int(self.config.MODEL.DOWNSAMPLE) != int(self.stride):
@@ -157,14 +173,14 @@ class PoseEstimator(object):
         b = self._bufs.get(key)
         if b is None:
             cfg = dec.make_cfg(self.config, self.max_peaks_per_part, self.max_humans)
-            b = dec.DecodeBuffers(cfg, n, device)
+            b = dec.DecodeBuffers(cfg, n, device, self.skeleton)
             self._bufs = {key: b}
         return b
 
     def enqueue(self, x, scene=None, scene_alpha=1e-3):
         """Enqueue forward + decode for a device batch x [N,3,H,W]; returns the buffers.
 
-        scene = (heat [N,h,w,19], paf [N,h,w,38]) device tensors: if given, the maps the
+        scene = (heat [N,h,w,19], paf [N,h,w,38]) device tensors (the skeleton's channel counts, with one): if given, the maps the
         decoder sees are  scene + scene_alpha * net_output  (bench / tests only: there
         are no trained weights offline, so realistic peaks are superimposed on what
         the randomly initialised network wrote; see include/rtpose_mi355x.h)."""
@@ -178,8 +194,8 @@ class PoseEstimator(object):
             if scene is not None:
                 sh, sp = scene
                 s = current_stream()
-                check(lib.rtpose_layout_axpby(hbase, C.byref(lheat), ptr(sh), 19, n, h, w, scene_alpha, 1.0, s))
-                check(lib.rtpose_layout_axpby(pbase, C.byref(lpaf), ptr(sp), 38, n, h, w, scene_alpha, 1.0, s))
+                check(lib.rtpose_layout_axpby(hbase, C.byref(lheat), ptr(sh), self.heat_channels, n, h, w, scene_alpha, 1.0, s))
+                check(lib.rtpose_layout_axpby(pbase, C.byref(lpaf), ptr(sp), self.paf_channels, n, h, w, scene_alpha, 1.0, s))
             bufs = self._buffers(n, x.device)
             dec.decode_enqueue(hbase, lheat, pbase, lpaf, n, h, w, bufs)
         bufs.map_hw = (h, w)
@@ -196,7 +212,7 @@ class PoseEstimator(object):
         m = self.model
         with torch.cuda.device(x.device):
             if not hasattr(self, '_side'):
-                self._side = SideDecoder(self.config)
+                self._side = SideDecoder(self.config, self.skeleton)
                 self._ticket = 0
             k = self._ticket
             self._ticket += 1
@@ -207,8 +223,8 @@ class PoseEstimator(object):
             if scene is not None:
                 sh, sp = scene
                 s = current_stream()
-                check(lib.rtpose_layout_axpby(hbase, C.byref(lheat), ptr(sh), 19, n, h, w, scene_alpha, 1.0, s))
-                check(lib.rtpose_layout_axpby(pbase, C.byref(lpaf), ptr(sp), 38, n, h, w, scene_alpha, 1.0, s))
+                check(lib.rtpose_layout_axpby(hbase, C.byref(lheat), ptr(sh), self.heat_channels, n, h, w, scene_alpha, 1.0, s))
+                check(lib.rtpose_layout_axpby(pbase, C.byref(lpaf), ptr(sp), self.paf_channels, n, h, w, scene_alpha, 1.0, s))
             bufs = self._side.decode(k & 1, (hbase, lheat, pbase, lpaf, h, w), n, x.device, self.max_peaks_per_part,
                                      self.max_humans, post, plan=plan, model=m)
             bufs.plan = plan
@@ -245,7 +261,7 @@ class PoseEstimator(object):
         stride = int(self.stride) if self.stride is not None else 8
         h, w = x.shape[2] // stride, x.shape[3] // stride
         for r in recs:
-            out.append(dec.humans_from_record(r, w * up, h * up, int(self.config.MODEL.NUM_KEYPOINTS)))
+            out.append(dec.humans_from_record(r, w * up, h * up, int(self.config.MODEL.NUM_KEYPOINTS), self.skeleton))
         return out
 
 
@@ -265,13 +281,17 @@ class StreamingPoseEstimator(object):
     """
 
     def __init__(self, model, batch, h0, w0, preprocess='rtpose', config=None, max_peaks_per_part=32,
-                 max_humans=64, scene=None, scene_alpha=1e-3):
+                 max_humans=64, scene=None, scene_alpha=1e-3, skeleton=None):
         """scene = (heat [B,h,w,19], paf [B,h,w,38]) device tensors, bench / tests only: the decoder then sees
-        scene + scene_alpha * maps, bench.py's decoder-input definition for a network without trained weights."""
+        scene + scene_alpha * maps, bench.py's decoder-input definition for a network without trained weights.
+        skeleton: a skeleton.Skeleton the records are decoded with (the model and the scene then have its channel
+        counts); None: COCO-18."""
         import torch
         from . import preprocess as pre
+        self.paf_channels, self.heat_channels = _check_model_channels(model, skeleton) if skeleton is not None else (38, 19)
+        self.skeleton = skeleton
         self.model = model
-        self.config = config or dec.default_config()
+        self.config = config or dec.default_config(skeleton)
         self.B, self.h0, self.w0 = batch, h0, w0
         self.mode = {'rtpose': 0, 'vgg': 1}[preprocess]
         size, factor = int(self.config.DATASET.IMAGE_SIZE), int(self.config.MODEL.DOWNSAMPLE)
@@ -283,7 +303,7 @@ class StreamingPoseEstimator(object):
         self.devbuf = [torch.empty((batch, h0, w0, 3), dtype=torch.uint8, device=self.dev) for _ in range(2)]
         self.max_peaks_per_part, self.max_humans = max_peaks_per_part, max_humans
         self.scene, self.scene_alpha = scene, scene_alpha
-        self.side = SideDecoder(self.config)
+        self.side = SideDecoder(self.config, skeleton)
         self.bufs = None                    # the decode buffers of the batch enqueued last (tests read .cfg)
         self._torch = torch
         self._pre = pre
@@ -321,8 +341,8 @@ class StreamingPoseEstimator(object):
         hbase, lheat, _, _, _ = m.output_view(plan, 1)
         if self.scene is not None:      # bench / tests only, see PoseEstimator.enqueue
             sh, sp = self.scene
-            check(lib.rtpose_layout_axpby(hbase, C.byref(lheat), ptr(sh), 19, self.B, h, w, self.scene_alpha, 1.0, s))
-            check(lib.rtpose_layout_axpby(pbase, C.byref(lpaf), ptr(sp), 38, self.B, h, w, self.scene_alpha, 1.0, s))
+            check(lib.rtpose_layout_axpby(hbase, C.byref(lheat), ptr(sh), self.heat_channels, self.B, h, w, self.scene_alpha, 1.0, s))
+            check(lib.rtpose_layout_axpby(pbase, C.byref(lpaf), ptr(sp), self.paf_channels, self.B, h, w, self.scene_alpha, 1.0, s))
         # (the plan's device error word rides in front of the decode and is checked by side.wait(): the host never calls a
         #  stream-synchronising API while the next batch is queued - round-4 advisor finding)
         self.bufs = self.side.decode(slot, (hbase, lheat, pbase, lpaf, h, w), self.B, self.dev,

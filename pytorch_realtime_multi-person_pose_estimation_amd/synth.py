@@ -119,6 +119,81 @@ def make_batch(n_images, height=368, width=368, seed=1, max_people=8, noise=0.02
     return np.stack(heats), np.stack(pafs), gt
 
 
+# ---- scenes for any skeleton (skeleton.Skeleton): new beside random_people / render / make_batch, whose outputs bench.py reads -----
+def spaced_people(rng, template, n_people, height, width, drop_prob=0.1):
+    """People standing side by side, one per slot of the width in a shuffled order (two peaks of one part never come close
+    enough to refine to the same pixel, which would tie their candidates' scores exactly): list of (P, 2) float arrays in
+    input pixels, NaN = part absent (dropped with drop_prob, or outside the image)."""
+    people = []
+    P = template.shape[0]
+    slot = width / float(n_people)
+    for k in rng.permutation(n_people):
+        scale = rng.uniform(0.28, 0.42) * height
+        cx = (k + 0.5) * slot + rng.uniform(-0.1, 0.1) * slot
+        cy = rng.uniform(0.47, 0.58) * height
+        ang = rng.uniform(-0.25, 0.25)
+        rot = np.array([[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]])
+        pts = ((template + rng.normal(0, 0.015, template.shape)) @ rot.T * scale + [cx, cy]).astype(np.float64)
+        drop = rng.uniform(size=P) < drop_prob
+        outside = (pts[:, 0] < 2) | (pts[:, 0] > width - 3) | (pts[:, 1] < 2) | (pts[:, 1] > height - 3)
+        pts[drop | outside] = np.nan
+        people.append(pts)
+    return people
+
+
+def render_skeleton(table, people, height, width, stride=8, noise=0.02, rng=None):
+    """render() for any skeleton - `table` has num_parts, limbs [(part A, part B, PAF x, PAF y)], heat_channels and
+    paf_channels (a skeleton.Skeleton has) -: Gaussians (sigma 7 px at stride 8, scaled with the stride) in the parts' heat-map channels,
+    unit-vector fields one cell wide in the limbs' PAF channels (overlaps averaged), background channel, + U(0, noise) on the
+    heat map and U(-noise, noise) on the PAF: the noise is what keeps candidate scores from tying exactly.
+    -> heat [h, w, heat_channels], paf [h, w, paf_channels] float32."""
+    h, w = height // stride, width // stride
+    sigma = 7.0 * stride / 8.0
+    start = stride / 2.0 - 0.5
+    ys, xs = np.mgrid[0:h, 0:w]
+    gx, gy = xs * stride + start, ys * stride + start
+    heat = np.zeros((h, w, table.heat_channels), np.float64)
+    for pts in people:
+        for j in range(table.num_parts):
+            if np.isnan(pts[j, 0]):
+                continue
+            e = ((gx - pts[j, 0]) ** 2 + (gy - pts[j, 1]) ** 2) / 2.0 / sigma / sigma
+            heat[:, :, j] += np.where(e <= 4.6052, np.exp(-e), 0.0)
+    heat = np.minimum(heat, 1.0)
+    if table.heat_channels > table.num_parts:
+        heat[:, :, table.num_parts] = np.maximum(1.0 - heat[:, :, :table.num_parts].max(axis=2), 0.0)
+    paf = np.zeros((h, w, table.paf_channels), np.float64)
+    for a, b, chx, chy in table.limbs:
+        acc = np.zeros((h, w, 2))
+        cnt = np.zeros((h, w))
+        for pts in people:
+            if np.isnan(pts[a, 0]) or np.isnan(pts[b, 0]):
+                continue
+            ca, cb = pts[a] / stride, pts[b] / stride
+            v = cb - ca
+            nrm = np.linalg.norm(v)
+            if nrm == 0:
+                continue
+            u = v / nrm
+            x0, x1 = max(int(round(min(ca[0], cb[0]) - 1)), 0), min(int(round(max(ca[0], cb[0]) + 1)), w)
+            y0, y1 = max(int(round(min(ca[1], cb[1]) - 1)), 0), min(int(round(max(ca[1], cb[1]) + 1)), h)
+            if x1 <= x0 or y1 <= y0:
+                continue
+            yy, xx = np.mgrid[y0:y1, x0:x1]
+            m = np.abs((xx - ca[0]) * u[1] - (yy - ca[1]) * u[0]) < 1
+            acc[y0:y1, x0:x1, 0] += m * u[0]
+            acc[y0:y1, x0:x1, 1] += m * u[1]
+            cnt[y0:y1, x0:x1] += m
+        cnt = np.maximum(cnt, 1)
+        paf[:, :, chx] = acc[:, :, 0] / cnt
+        paf[:, :, chy] = acc[:, :, 1] / cnt
+    if noise > 0:
+        rng = rng or np.random.default_rng(0)
+        heat += rng.uniform(0, noise, heat.shape)
+        paf += rng.uniform(-noise, noise, paf.shape)
+    return heat.astype(np.float32), paf.astype(np.float32)
+
+
 def he_init_state_dict(model, seed=0):
     """Seeded stand-in weights for `pose_model.pth` (not available offline): Kaiming-normal conv
     weights + N(0, 0.05) biases, drawn key by key in state_dict order from one torch generator.

@@ -1,0 +1,218 @@
+"""The table-driven decoder (csrc/decode_skel.hip) on the MI355X.  Everything a record holds is integers and float bit
+patterns: every comparison here is bit for bit, inside decode.result_mask (the words a record defines).
+
+  * the COCO-18 preset through rtpose_decode_batch_skel against rtpose_decode_batch_ex, word for word (this inherits the
+    compiled-reference parity of the old entry point, std::sort replay on ties included);
+  * BODY_25, a 2-part / 1-limb table, a 32-part / 32-limb table with scattered PAF channels and COCO-18 walked backwards
+    under seed mask 0x15555 against the host restatement (tests/skeleton_restate.py), at capacities on both sides of every
+    switch of the launcher, into sentinel-filled buffers of exactly the queried sizes with a guard region behind them;
+  * rtpose_nms_batch_skel against the oracle's NMS with num_keypoints below P;
+  * PoseEstimator(skeleton=BODY_25) over OpenPose_Model(4, 2, 52, 26) and a stride-4 hourglass, serial and pipelined.
+
+tests/test_skeleton_cpu.py checks on the CPU that the scene sets used here hold people, merges, refused seeds and
+overflows (and says which of the issue's conditions two of the tables cannot meet, and why).
+"""
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import skeleton_restate as sr  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(__file__), "golden", "post_scenes.npz")
+SENTINEL = 0x5A5A5A5A
+GUARD = 4096        # words behind each buffer that must stay untouched
+
+
+@pytest.fixture(scope="module")
+def dec(pkg):
+    return importlib.import_module(pkg.__name__ + ".decode")
+
+
+@pytest.fixture(scope="module")
+def skm(pkg):
+    return importlib.import_module(pkg.__name__ + ".skeleton")
+
+
+def _run(capi, cuda, heat, paf, cfg, skel=None, flags=0, nms_only=False):
+    """One decode of dense NHWC maps (device tensors) into sentinel-filled buffers of exactly the queried sizes + a guard
+    region; skel None = the COCO-18 entry points.  -> int32 [N, words]."""
+    lib = capi.lib
+    n, h, w, ch = heat.shape
+    if skel is None:
+        rb, wb = lib.rtpose_decode_result_bytes(C.byref(cfg), n), lib.rtpose_decode_workspace_bytes(C.byref(cfg), n)
+    else:
+        rb = lib.rtpose_decode_result_bytes_skel(C.byref(cfg), C.byref(skel), n)
+        wb = lib.rtpose_decode_workspace_bytes_skel(C.byref(cfg), C.byref(skel), n)
+    assert rb > 0 and wb > 0 and rb % 4 == 0 and wb % 4 == 0, capi.last_error()
+    res = torch.full((rb // 4 + GUARD,), SENTINEL, dtype=torch.int32, device=cuda)
+    ws = torch.full((wb // 4 + GUARD,), SENTINEL, dtype=torch.int32, device=cuda)
+    lheat, lpaf = capi.Layout.dense(ch, h, w), capi.Layout.dense(paf.shape[3], h, w)
+    s = capi.current_stream()
+    if skel is None and nms_only:
+        rc = lib.rtpose_nms_batch_ex(capi.ptr(heat), C.byref(lheat), n, h, w, C.byref(cfg), flags, capi.ptr(res), s)
+    elif skel is None:
+        rc = lib.rtpose_decode_batch_ex(capi.ptr(heat), C.byref(lheat), capi.ptr(paf), C.byref(lpaf), n, h, w, C.byref(cfg),
+                                        flags, capi.ptr(ws), wb, capi.ptr(res), s)
+    elif nms_only:
+        rc = lib.rtpose_nms_batch_skel(capi.ptr(heat), C.byref(lheat), n, h, w, C.byref(cfg), C.byref(skel), flags,
+                                       capi.ptr(res), s)
+    else:
+        rc = lib.rtpose_decode_batch_skel(capi.ptr(heat), C.byref(lheat), capi.ptr(paf), C.byref(lpaf), n, h, w,
+                                          C.byref(cfg), C.byref(skel), flags, capi.ptr(ws), wb, capi.ptr(res), s)
+    capi.check(rc, "decode")
+    torch.cuda.synchronize()
+    assert bool((res[rb // 4:] == SENTINEL).all()), "the result block's guard region was written"
+    assert bool((ws[wb // 4:] == SENTINEL).all()), "the workspace's guard region was written"
+    return res[:rb // 4].cpu().numpy().reshape(n, -1)
+
+
+# ---- 5. the same records through both doors ---------------------------------------------------------------------------
+def _door_scenes(synth):
+    z = np.load(GOLD)
+    scenes = [("golden%d" % i, z["heat%d" % i][None], z["paf%d" % i][None]) for i in range(int(z["n"]))]
+    heat, paf, _ = synth.make_batch(4, 368, 368, seed=5)            # crowded figures: exact score ties among them
+    scenes.append(("synth368", heat, paf))
+    heat, paf, _ = synth.make_batch(3, 184, 248, seed=9)
+    scenes.append(("synth23x31", heat, paf))
+    rng = np.random.default_rng(0)                                  # junk: many peaks, no structure
+    scenes.append(("noise", rng.uniform(0, 0.3, (2, 13, 29, 19)).astype(np.float32),
+                   rng.uniform(-1, 1, (2, 13, 29, 38)).astype(np.float32)))
+    return scenes
+
+
+@pytest.mark.parametrize("pcap", [32, 111])
+@pytest.mark.parametrize("flags", [0, 1, 2], ids=["refine", "no_refine", "gaussian"])
+def test_coco18_preset_writes_the_records_of_the_old_entry_point(capi, dec, skm, pkg, cuda, flags, pcap):
+    synth = importlib.import_module(pkg.__name__ + ".synth")
+    coco = skm.COCO18.native()
+    humans = 0
+    for name, heat, paf in _door_scenes(synth):
+        heat_d, paf_d = torch.from_numpy(heat).to(cuda), torch.from_numpy(paf).to(cuda)
+        cfg = capi.DecodeCfg(18, 8, 0.1, pcap, 64)
+        old = _run(capi, cuda, heat_d, paf_d, cfg, None, flags)
+        new = _run(capi, cuda, heat_d, paf_d, cfg, coco, flags)
+        assert old.shape == new.shape, name
+        m = dec.result_mask(old)
+        assert np.array_equal(m, dec.result_mask(new)), name
+        assert np.array_equal(new[m], old[m]), "%s: the two entry points' records differ" % name
+        assert (old[:, 5:7] == 0).all() and (new[:, 5] == 18).all() and (new[:, 6] == 19).all(), name
+        humans += int(old[:, 1].sum())
+    assert humans > 12
+
+
+# ---- 6. other skeletons against the restatement -----------------------------------------------------------------------
+CAPS = [(4, 4), (32, 64), (65, 64), (111, 64), (128, 64), (32, 400)]
+CASES = [(n, c) for n in sorted(sr.SCENE_SETS) for c in CAPS] + [("coco18rev", (4, 1))]
+
+
+@pytest.mark.parametrize("name,caps", CASES, ids=["%s-%dx%d" % (n, c[0], c[1]) for n, c in CASES])
+def test_other_skeletons_match_the_restatement(capi, dec, skm, cuda, name, caps):
+    table, heat, paf, up = sr.scene_set(name)
+    want, _ = sr.expected_block(name, *caps)
+    skel = table.skeleton(skm).native()
+    cfg = capi.DecodeCfg(table.P, up, 0.1, caps[0], caps[1])
+    got = _run(capi, cuda, torch.tensor(heat, device=cuda), torch.tensor(paf, device=cuda), cfg, skel)
+    assert got.shape == want.shape
+    assert np.array_equal(got[:, :8], want[:, :8]), (got[:, :8], want[:, :8])       # counts, flags, capacities, P, L
+    m = dec.result_mask(want)
+    assert np.array_equal(got[m], want[m])
+    for i in range(len(got)):                                                      # and as the consumer reads it
+        d = dec.parse_image(got[i])
+        assert d["num_parts"] == table.P and d["parts"].shape == (want[i, 1], table.P)
+
+
+# ---- 7. NMS only -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,nk", [("body25", 20), ("full32", 29)])
+def test_nms_only_with_fewer_keypoints_than_parts(capi, dec, skm, cuda, name, nk):
+    table, heat, paf, up = sr.scene_set(name)
+    want, _ = sr.expected_block(name, 32, 64, nms_only=True, num_keypoints=nk)
+    assert (want[:, 8 + nk:8 + table.P] == 0).all() and int(want[:, 8:8 + nk].sum()) > nk * len(want)
+    cfg = capi.DecodeCfg(nk, up, 0.1, 32, 64)
+    got = _run(capi, cuda, torch.tensor(heat, device=cuda), torch.tensor(paf, device=cuda), cfg,
+               table.skeleton(skm).native(), nms_only=True)
+    assert np.array_equal(got[:, :8], want[:, :8])
+    m = dec.result_mask(want)
+    assert np.array_equal(got[m], want[m])
+
+
+# ---- 8. pipeline -----------------------------------------------------------------------------------------------------
+def _openpose_body25(pkg):
+    import openpose_restate as R
+    op = importlib.import_module(pkg.__name__ + ".openpose")
+    m = op.OpenPose_Model(4, 2, 52, 26)
+    m.load_state_dict(R.seeded_state_dict(R.state_dict_spec(4, 2, 52, 26), 3))
+    return m.cuda().eval(), 4, 368, 8, 2e-2, (3, 5)
+
+
+def _hourglass_body25(pkg):
+    import hourglass_restate as R
+    hgm = importlib.import_module(pkg.__name__ + ".hourglass")
+    m = hgm.hg(num_stacks=1, num_blocks=1, paf_classes=52, ht_classes=26)
+    m.load_state_dict(R.seeded_state_dict(R.state_dict_spec(1, 1, 52, 26), 3, R.BRANCH_GAIN))
+    return m.cuda().eval(), 2, 384, 4, 2e-3, (0, 1)
+
+
+@pytest.mark.parametrize("make", [_openpose_body25, _hourglass_body25], ids=["openpose_4x368", "hourglass_2x384_stride4"])
+def test_pose_estimator_with_body25(pkg, dec, skm, cuda, make):
+    from oracle import post_oracle
+    pipeline = importlib.import_module(pkg.__name__ + ".pipeline")
+    m, B, S, stride, alpha, outs = make(pkg)
+    table = sr.TABLES["body25"]
+    cfg = dec.default_config(skm.BODY_25)
+    cfg.MODEL.DOWNSAMPLE = stride
+
+    def batch(r):
+        g = torch.Generator().manual_seed(500 + r)
+        h, p = sr.make_scenes(table, [3 + (r + i) % 3 for i in range(B)], S // stride, S // stride, stride, 600 + r)
+        return (torch.rand(B, 3, S, S, generator=g) - 0.5).to(cuda), (torch.from_numpy(h).to(cuda), torch.from_numpy(p).to(cuda))
+
+    data = [batch(r) for r in range(2)]
+    est = pipeline.PoseEstimator(m, cfg, skeleton=skm.BODY_25)
+    want = []
+    for x, scene in data:
+        est(x, scene, scene_alpha=alpha)                      # capacities settle
+        bufs = est.enqueue(x, scene, scene_alpha=alpha)
+        recs = dec.fetch(bufs).copy()
+        assert bufs.map_hw == (S // stride, S // stride) and (recs[:, 5] == 25).all() and (recs[:, 6] == 26).all()
+        # the maps the decoder read: the blended last PAF / heat maps, where the plan keeps them
+        paf = m.read_output(bufs.plan, outs[0]).permute(0, 2, 3, 1).contiguous().cpu().numpy()
+        heat = m.read_output(bufs.plan, outs[1]).permute(0, 2, 3, 1).contiguous().cpu().numpy()
+        assert paf.shape[3] == 52 and heat.shape[3] == 26
+        pcap, hcap = bufs.cfg.max_peaks_per_part, bufs.cfg.max_humans
+        exp = []
+        for i in range(B):
+            jl, over = sr.truncate_peaks(post_oracle.nms(heat[i], num_keypoints=25, thr=0.1, up=stride), 25, pcap)
+            exp.append(sr.pack_record(jl, sr.process(jl, paf[i], table, stride, hcap), table, pcap, hcap, over))
+        exp = np.stack(exp)
+        mask = dec.result_mask(exp)
+        assert np.array_equal(recs[:, :8], exp[:, :8]) and np.array_equal(recs[mask], exp[mask])
+        assert int(exp[:, 1].sum()) > B and not exp[:, 2].any()
+        want.append(recs[mask].tobytes())
+    order = [0, 1, 1, 0]
+    prev, got = None, []
+
+    def content(block):
+        block = block.reshape(B, -1)
+        return block[dec.result_mask(block)].tobytes()
+    for r in order:
+        t = est.submit(*data[r], scene_alpha=alpha)
+        if prev is not None:
+            got.append(content(est.collect(prev)[1]))
+        prev = t
+    got.append(content(est.collect(prev)[1]))
+    torch.cuda.synchronize()
+    for k, r in enumerate(order):
+        assert got[k] == want[r], "step %d: the pipelined records differ from the serial path's" % k
+    # Human objects with BODY_25 part ids and names
+    humans = est.humans(data[0][0], scene=data[0][1], scene_alpha=alpha)
+    ids = set(k for img in humans for h in img for k in h.body_parts)
+    assert max(ids) > 18 and max(ids) <= 24 and sum(len(img) for img in humans) > B
+    assert all(bp.get_part_name() == skm.BODY_25.part_names[k] for img in humans for h in img for k, bp in h.body_parts.items())
