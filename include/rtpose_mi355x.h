@@ -954,8 +954,9 @@ int rtpose_gaussian_kernel1d(double* weights, int cap);
  * are in its header.  With rtpose_skeleton_coco18 the record equals the one of
  * rtpose_decode_batch_ex word for word except header words 5 and 6.
  *
- * Not covered by a skeleton (COCO-18 only): rtpose_flip_merge / rtpose_tta_accumulate (they
- * carry COCO-18's left / right permutations) and the legacy process_paf API of section 6. */
+ * Flip merge and multi-scale TTA take the skeleton's left / right permutation as a
+ * rtpose_flip_table (section 5: rtpose_flip_merge_skel / rtpose_tta_accumulate_skel).
+ * Not covered by a skeleton (COCO-18 only): the legacy process_paf API of section 6. */
 #define RTPOSE_SKEL_MAX_PARTS 32
 #define RTPOSE_SKEL_MAX_LIMBS 32 /* 64 PAF channels: the limit of the native models */
 
@@ -1006,6 +1007,67 @@ int rtpose_decode_batch_skel(const float* heat, const rtpose_layout* lheat, cons
 int rtpose_flip_merge(const float* heat, const float* heat_flipped,
                       const float* paf, const float* paf_flipped, int N, int h,
                       int w, float* heat_avg, float* paf_avg, void* stream);
+
+/* ---- 5a. The same merge with the left / right permutation as data --------------------
+ * rtpose_flip_merge and rtpose_tta_accumulate (section 4) carry COCO-18's permutations
+ * in their kernels.  The `_skel` entry points below take them as a flip table: output
+ * heat-map channel c averages with channel heat_src[c] of the x-mirrored pass, PAF
+ * channel c with channel paf_src[c], negated iff bit c of paf_neg_mask is set.  The
+ * arithmetic is that of the entry points above, expression for expression: with the
+ * COCO-18 table the results are theirs bit for bit.  The struct travels by value into the
+ * kernels as a launch argument (nothing is uploaded; two streams may merge different
+ * skeletons at the same time). */
+#define RTPOSE_FLIP_MAX_HEAT 33 /* 32 parts + background */
+#define RTPOSE_FLIP_MAX_PAF 64
+
+typedef struct rtpose_flip_table {
+  uint32_t struct_bytes;   /* sizeof(rtpose_flip_table)                              */
+  int32_t heat_channels;   /* 1..33: channels of the heat maps                        */
+  int32_t paf_channels;    /* 1..64: channels of the PAF maps                         */
+  uint32_t reserved;       /* 0                                                       */
+  uint64_t paf_neg_mask;   /* bit c: PAF channel c takes its source negated           */
+  uint8_t heat_src[RTPOSE_FLIP_MAX_HEAT];
+  uint8_t paf_src[RTPOSE_FLIP_MAX_PAF];
+} rtpose_flip_table;
+
+/* Host only.  The table of a skeleton whose part i becomes part part_mirror[i] in the
+ * mirrored image (num_parts entries); background != 0: the heat map carries one more
+ * channel behind the parts, which reads itself.  Limb (A, B, cx, cy) looks up the limb
+ * that joins part_mirror[A] and part_mirror[B]: found in that direction as (sx, sy), cx
+ * reads -sx and cy reads +sy; found only as part_mirror[B] -> part_mirror[A], the vector
+ * changes direction too: cx reads +sx and cy reads -sy.  A PAF channel no limb reads maps
+ * to itself.  Errors: a skeleton that fails rtpose_skeleton_check for these channel counts;
+ * a part_mirror that is not an involution over [0, num_parts); a limb whose mirror is in
+ * the table neither way (the message names the limb); a channel that two limbs would give
+ * different (source, sign) pairs. */
+int rtpose_flip_table_from_skeleton(const rtpose_skeleton* skel, const int32_t* part_mirror,
+                                    int background, int paf_channels, rtpose_flip_table* out);
+
+/* Host only; for a table filled in by hand.  0, or an error: a wrong struct_bytes or a
+ * channel count out of range; a source index outside the map; mask bits at or above
+ * paf_channels; a table that applied twice is not the identity (src[src[c]] != c, or PAF
+ * channels c and src[c] carrying different signs). */
+int rtpose_flip_table_check(const rtpose_flip_table* table);
+
+/* rtpose_flip_merge over a table: all maps dense NHWC fp32 on the device, the heat maps
+ * with table->heat_channels and the PAF maps with table->paf_channels channels.  N == 0
+ * is a no-op; NULL maps, a table that fails the check, N or h above 65535 are refused. */
+int rtpose_flip_merge_skel(const float* heat, const float* heat_flipped, const float* paf,
+                           const float* paf_flipped, int N, int h, int w, float* heat_avg,
+                           float* paf_avg, const rtpose_flip_table* table, void* stream);
+
+/* rtpose_tta_accumulate over a table: heat / paf are the network's own output views of a
+ * batch of 2B images ([0,B) normal, [B,2B) mirrored; B images if flip == 0), the
+ * accumulators dense [B,hd,wd,heat_channels] / [B,hd,wd,paf_channels].  Accumulates exactly
+ * as rtpose_flip_merge_skel followed by rtpose_resize_bilinear_accum would.  B == 0 is a
+ * no-op; refused before any launch: NULL pointers, w_valid outside 1..ws or hs above the
+ * views' hs, a table with more channels than a view addresses (cstride - choff) or that
+ * fails the check, B or hd above 65535. */
+int rtpose_tta_accumulate_skel(const float* heat, const rtpose_layout* lheat, const float* paf,
+                               const rtpose_layout* lpaf, int B, int hs, int w_valid,
+                               float* acc_heat, float* acc_paf, int hd, int wd,
+                               float src_h_valid, float src_w_valid, float alpha, float beta,
+                               int flip, const rtpose_flip_table* table, void* stream);
 
 /* ------------------------------------------------------------------------
  * 6. Legacy single-image API — same seven names and argument meaning as the

@@ -111,6 +111,17 @@ class SkeletonStruct(C.Structure):
                 ("seed_mask", C.c_uint32)]
 
 
+FLIP_MAX_HEAT, FLIP_MAX_PAF = 33, 64
+
+
+class FlipTable(C.Structure):
+    """rtpose_flip_table: the left / right permutation of a `_skel` flip merge (header section 5a);
+    skeleton.Skeleton.native_flip_table() fills one."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("heat_channels", C.c_int32), ("paf_channels", C.c_int32),
+                ("reserved", C.c_uint32), ("paf_neg_mask", C.c_uint64), ("heat_src", C.c_uint8 * FLIP_MAX_HEAT),
+                ("paf_src", C.c_uint8 * FLIP_MAX_PAF)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -276,6 +287,11 @@ _SIGS = {
     "rtpose_net_forward_prepared": (_i, [_vp, _vp]),
     "rtpose_resize_bilinear_accum": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
     "rtpose_flip_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "rtpose_flip_table_from_skeleton": (_i, [C.POINTER(SkeletonStruct), C.POINTER(C.c_int32), _i, _i, C.POINTER(FlipTable)]),
+    "rtpose_flip_table_check": (_i, [C.POINTER(FlipTable)]),
+    "rtpose_flip_merge_skel": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(FlipTable), _vp]),
+    "rtpose_tta_accumulate_skel": (_i, [_vp, _LP, _vp, _LP, _i, _i, _i, _vp, _vp, _i, _i, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, _i, C.POINTER(FlipTable), _vp]),
     # legacy SWIG-module names (lib/pafprocess/pafprocess.h:53-59)
     "process_paf": (_i, [_i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "get_num_humans": (_i, []),

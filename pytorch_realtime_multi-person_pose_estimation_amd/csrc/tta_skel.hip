@@ -1,0 +1,244 @@
+// Flip merge and fused multi-scale TTA for any skeleton: the kernels of layout_ops.hip
+// (flip_merge_kernel, tta_accumulate_kernel) with the left / right permutation as data.  The
+// rtpose_flip_table travels by value as a launch argument, like rtpose_skeleton in
+// decode_skel.hip: nothing is uploaded, two streams may merge different skeletons at once.
+// Same expressions, in the same order, as the COCO-18 kernels: with the COCO-18 table the
+// results are theirs bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "common.h"
+
+namespace rtpose {
+namespace {
+
+struct View {
+  int cstride, choff, ws, hs, lead;
+};
+View to_view(const rtpose_layout* l) { return View{l->cstride, l->choff, l->ws, l->hs, l->lead}; }
+
+__device__ __forceinline__ size_t view_off(const View& l, int n, int y, int x) {
+  return ((size_t)l.lead + (size_t)(n * l.hs + y) * l.ws + x) * l.cstride + l.choff;
+}
+
+constexpr int kThreads = 256;
+
+// grid (pieces of one output row, rows, images): a thread owns one (x, channel) of the row, channels fastest over the
+// heat map's and then the PAF's, so a wave's stores are two contiguous runs per pixel.  The only division left is
+// x = t / (heat + PAF channels), by a launch-time constant (FastDiv: one mul-hi and a shift).
+__global__ __launch_bounds__(kThreads) void flip_merge_skel_kernel(
+    const float* __restrict__ heat, const float* __restrict__ heat_f, const float* __restrict__ paf,
+    const float* __restrict__ paf_f, int h, int w, float* __restrict__ heat_avg, float* __restrict__ paf_avg,
+    const rtpose_flip_table tab, const FastDiv dc) {
+  const int CH = tab.heat_channels, CP = tab.paf_channels;
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  if (t >= w * (CH + CP)) return;
+  const int x = fast_div(t, dc);
+  const int c = t - x * (CH + CP);
+  const size_t row = (size_t)blockIdx.z * h + blockIdx.y;  // n*h + y
+  const size_t p = row * w + x;
+  const size_t pf = row * w + (w - 1 - x);
+  if (c < CH) {
+    heat_avg[p * CH + c] = (heat[p * CH + c] + heat_f[pf * CH + tab.heat_src[c]]) / 2.f;
+  } else {
+    const int k = c - CH;
+    float v = paf_f[pf * CP + tab.paf_src[k]];
+    if ((tab.paf_neg_mask >> k) & 1) v = -v;
+    paf_avg[p * CP + k] = (paf[p * CP + k] + v) / 2.f;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void tta_accumulate_skel_kernel(
+    const float* __restrict__ heat, View lh, const float* __restrict__ paf, View lp, int B, int hs, int wv,
+    float* __restrict__ acc_heat, float* __restrict__ acc_paf, int hd, int wd, float sy, float sx, float alpha,
+    float beta, int flip, const rtpose_flip_table tab, const FastDiv dc) {
+  const int CH = tab.heat_channels, CP = tab.paf_channels;
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  if (t >= wd * (CH + CP)) return;
+  const int x = fast_div(t, dc);
+  const int cc = t - x * (CH + CP);
+  const int y = blockIdx.y, b = blockIdx.z;
+  const size_t p = ((size_t)b * hd + y) * wd + x;
+  float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
+  fy = fmaxf(fy, 0.f);
+  fx = fmaxf(fx, 0.f);
+  int y0 = (int)fy, x0 = (int)fx;
+  y0 = min(y0, hs - 1);
+  x0 = min(x0, wv - 1);
+  const int y1 = min(y0 + 1, hs - 1), x1 = min(x0 + 1, wv - 1);
+  const float ly = fminf(fy - (float)y0, 1.f), lx = fminf(fx - (float)x0, 1.f);
+  const bool is_heat = cc < CH;
+  const int c = is_heat ? cc : cc - CH;
+  const float* src = is_heat ? heat : paf;
+  const View& l = is_heat ? lh : lp;
+  const int sc = is_heat ? tab.heat_src[c] : tab.paf_src[c];
+  const bool neg = !is_heat && ((tab.paf_neg_mask >> c) & 1);
+  auto tap = [&](int yy, int xx) -> float {
+    const float a = src[view_off(l, b, yy, xx) + c];
+    if (!flip) return a;
+    float v = src[view_off(l, B + b, yy, wv - 1 - xx) + sc];
+    if (neg) v = -v;
+    return (a + v) / 2.f;
+  };
+  const float top = tap(y0, x0) * (1.f - lx) + tap(y0, x1) * lx;
+  const float bot = tap(y1, x0) * (1.f - lx) + tap(y1, x1) * lx;
+  const float v = top * (1.f - ly) + bot * ly;
+  float* d = is_heat ? acc_heat + p * CH + c : acc_paf + p * CP + c;
+  *d = (beta == 0.f ? 0.f : beta * *d) + alpha * v;
+}
+
+int check_table(const rtpose_flip_table* t) {
+  if (!t) return fail(RTPOSE_E_INVAL, "flip table: NULL argument");
+  if (t->struct_bytes != sizeof(rtpose_flip_table))
+    return fail(RTPOSE_E_INVAL, "flip table: struct_bytes is %u, this library's rtpose_flip_table has %zu",
+                t->struct_bytes, sizeof(rtpose_flip_table));
+  const int CH = t->heat_channels, CP = t->paf_channels;
+  if (CH < 1 || CH > RTPOSE_FLIP_MAX_HEAT)
+    return fail(RTPOSE_E_INVAL, "flip table: heat_channels %d outside [1,%d]", CH, RTPOSE_FLIP_MAX_HEAT);
+  if (CP < 1 || CP > RTPOSE_FLIP_MAX_PAF)
+    return fail(RTPOSE_E_INVAL, "flip table: paf_channels %d outside [1,%d]", CP, RTPOSE_FLIP_MAX_PAF);
+  if (CP < 64 && (t->paf_neg_mask >> CP))
+    return fail(RTPOSE_E_INVAL, "flip table: paf_neg_mask has bits at or above paf_channels %d", CP);
+  for (int c = 0; c < CH; ++c) {
+    const int s = t->heat_src[c];
+    if (s >= CH) return fail(RTPOSE_E_INVAL, "flip table: heat channel %d reads channel %d, outside [0,%d)", c, s, CH);
+    if (t->heat_src[s] != c)
+      return fail(RTPOSE_E_INVAL, "flip table: heat channel %d reads %d but %d reads %d: flipping twice is not the identity",
+                  c, s, s, (int)t->heat_src[s]);
+  }
+  for (int c = 0; c < CP; ++c) {
+    const int s = t->paf_src[c];
+    if (s >= CP) return fail(RTPOSE_E_INVAL, "flip table: PAF channel %d reads channel %d, outside [0,%d)", c, s, CP);
+    if (t->paf_src[s] != c)
+      return fail(RTPOSE_E_INVAL, "flip table: PAF channel %d reads %d but %d reads %d: flipping twice is not the identity",
+                  c, s, s, (int)t->paf_src[s]);
+    if (((t->paf_neg_mask >> c) & 1) != ((t->paf_neg_mask >> s) & 1))
+      return fail(RTPOSE_E_INVAL, "flip table: PAF channels %d and %d read each other with different signs", c, s);
+  }
+  return 0;
+}
+
+// one PAF channel's (source, sign); the same channel named by two limbs must receive the same pair
+int assign(rtpose_flip_table* t, bool* set, int limb, int c, int s, bool neg) {
+  if (set[c] && (t->paf_src[c] != s || (bool)((t->paf_neg_mask >> c) & 1) != neg))
+    return fail(RTPOSE_E_INVAL, "flip table: limb %d gives PAF channel %d the source %s%d, another limb gave it %s%d", limb,
+                c, neg ? "-" : "+", s, ((t->paf_neg_mask >> c) & 1) ? "-" : "+", (int)t->paf_src[c]);
+  set[c] = true;
+  t->paf_src[c] = (uint8_t)s;
+  if (neg) t->paf_neg_mask |= 1ull << c;
+  return 0;
+}
+
+}  // namespace
+}  // namespace rtpose
+
+using namespace rtpose;
+
+extern "C" {
+
+int rtpose_flip_table_check(const rtpose_flip_table* table) { return check_table(table); }
+
+int rtpose_flip_table_from_skeleton(const rtpose_skeleton* skel, const int32_t* part_mirror, int background,
+                                    int paf_channels, rtpose_flip_table* out) {
+  if (!skel || !part_mirror || !out) return fail(RTPOSE_E_INVAL, "flip table: NULL argument");
+  if (paf_channels < 1 || paf_channels > RTPOSE_FLIP_MAX_PAF)
+    return fail(RTPOSE_E_INVAL, "flip table: paf_channels %d outside [1,%d]", paf_channels, RTPOSE_FLIP_MAX_PAF);
+  const int bg = background ? 1 : 0;
+  int rc = rtpose_skeleton_check(skel, skel->num_parts + bg, paf_channels);
+  if (rc) return rc;
+  const int P = skel->num_parts, L = skel->num_limbs;
+  for (int i = 0; i < P; ++i) {
+    const int m = part_mirror[i];
+    if (m < 0 || m >= P) return fail(RTPOSE_E_INVAL, "flip table: part %d mirrors to %d, outside [0,%d)", i, m, P);
+    if (part_mirror[m] != i)
+      return fail(RTPOSE_E_INVAL, "flip table: part %d mirrors to %d but %d mirrors to %d: the mirror is not an involution",
+                  i, m, m, part_mirror[m]);
+  }
+  rtpose_flip_table t;
+  memset(&t, 0, sizeof(t));
+  t.struct_bytes = (uint32_t)sizeof(t);
+  t.heat_channels = P + bg;
+  t.paf_channels = paf_channels;
+  for (int i = 0; i < P; ++i) t.heat_src[i] = (uint8_t)part_mirror[i];
+  if (bg) t.heat_src[P] = (uint8_t)P;
+  bool set[RTPOSE_FLIP_MAX_PAF] = {false};
+  for (int l = 0; l < L; ++l) {
+    const int ma = part_mirror[skel->limb_part[l][0]], mb = part_mirror[skel->limb_part[l][1]];
+    const int cx = skel->limb_paf[l][0], cy = skel->limb_paf[l][1];
+    int same = -1, rev = -1;
+    for (int k = 0; k < L; ++k) {
+      if (skel->limb_part[k][0] == ma && skel->limb_part[k][1] == mb) same = k;
+      if (skel->limb_part[k][0] == mb && skel->limb_part[k][1] == ma) rev = k;
+    }
+    // the mirrored field is (-x, y); read along a limb walked the other way it is (x, -y)
+    const int k = same >= 0 ? same : rev;
+    if (k < 0)
+      return fail(RTPOSE_E_INVAL, "flip table: limb %d (parts %d -> %d) has no mirror: no limb joins parts %d and %d", l,
+                  skel->limb_part[l][0], skel->limb_part[l][1], ma, mb);
+    const bool reversed = same < 0;
+    rc = assign(&t, set, l, cx, skel->limb_paf[k][0], !reversed);
+    if (!rc) rc = assign(&t, set, l, cy, skel->limb_paf[k][1], reversed);
+    if (rc) return rc;
+  }
+  for (int c = 0; c < paf_channels; ++c)
+    if (!set[c]) t.paf_src[c] = (uint8_t)c;  // a channel no limb reads: itself, sign +
+  rc = check_table(&t);
+  if (rc) return rc;
+  *out = t;
+  return 0;
+}
+
+int rtpose_flip_merge_skel(const float* heat, const float* heat_flipped, const float* paf, const float* paf_flipped,
+                           int N, int h, int w, float* heat_avg, float* paf_avg, const rtpose_flip_table* table,
+                           void* stream) {
+  if (!heat || !heat_flipped || !paf || !paf_flipped || !heat_avg || !paf_avg)
+    return fail(RTPOSE_E_INVAL, "flip_merge_skel: NULL map");
+  const int rc = check_table(table);
+  if (rc) return rc;
+  if (N == 0) return 0;
+  if (N < 0 || N > 65535 || h <= 0 || h > 65535 || w <= 0)
+    return fail(RTPOSE_E_INVAL, "flip_merge_skel: bad sizes (N %d, h %d, w %d; N and h at most 65535)", N, h, w);
+  const int ctot = table->heat_channels + table->paf_channels;
+  if ((long long)w * ctot > 0x7fffff00ll) return fail(RTPOSE_E_INVAL, "flip_merge_skel: row of %d pixels too long", w);
+  hipLaunchKernelGGL(flip_merge_skel_kernel, dim3(ceil_div(w * ctot, kThreads), h, N), dim3(kThreads), 0,
+                     as_stream(stream), heat, heat_flipped, paf, paf_flipped, h, w, heat_avg, paf_avg, *table,
+                     make_fastdiv(ctot));
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int rtpose_tta_accumulate_skel(const float* heat, const rtpose_layout* lheat, const float* paf,
+                               const rtpose_layout* lpaf, int B, int hs, int w_valid, float* acc_heat, float* acc_paf,
+                               int hd, int wd, float src_h_valid, float src_w_valid, float alpha, float beta, int flip,
+                               const rtpose_flip_table* table, void* stream) {
+  if (!heat || !lheat || !paf || !lpaf || !acc_heat || !acc_paf)
+    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: NULL argument");
+  const int rc = check_table(table);
+  if (rc) return rc;
+  if (table->heat_channels > lheat->cstride - lheat->choff)
+    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: the table has %d heat-map channels, the view addresses %d",
+                table->heat_channels, lheat->cstride - lheat->choff);
+  if (table->paf_channels > lpaf->cstride - lpaf->choff)
+    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: the table has %d PAF channels, the view addresses %d",
+                table->paf_channels, lpaf->cstride - lpaf->choff);
+  if (B == 0) return 0;
+  if (B < 0 || B > 65535 || hs <= 0 || hs > lheat->hs || hs > lpaf->hs || hd <= 0 || hd > 65535 || wd <= 0 ||
+      !(src_h_valid > 0) || !(src_w_valid > 0))
+    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: bad sizes (B %d, hs %d, hd %d, wd %d; B and hd at most 65535)", B,
+                hs, hd, wd);
+  if (w_valid < 1 || w_valid > lheat->ws || w_valid > lpaf->ws)
+    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: w_valid %d outside [1,%d]", w_valid,
+                lheat->ws < lpaf->ws ? lheat->ws : lpaf->ws);
+  const int ctot = table->heat_channels + table->paf_channels;
+  if ((long long)wd * ctot > 0x7fffff00ll)
+    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: row of %d pixels too long", wd);
+  hipLaunchKernelGGL(tta_accumulate_skel_kernel, dim3(ceil_div(wd * ctot, kThreads), hd, B), dim3(kThreads), 0,
+                     as_stream(stream), heat, to_view(lheat), paf, to_view(lpaf), B, hs, w_valid, acc_heat, acc_paf, hd,
+                     wd, src_h_valid / (float)hd, src_w_valid / (float)wd, alpha, beta, flip ? 1 : 0, *table,
+                     make_fastdiv(ctot));
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

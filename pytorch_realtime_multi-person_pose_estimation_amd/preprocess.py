@@ -185,13 +185,38 @@ def get_outputs_gpu(img, model, preprocess, config=None):
     return paf, heatmap, im_scale
 
 
-def handle_paf_and_heat(normal_heat, flipped_heat, normal_paf, flipped_paf):
-    """coco_eval.py:197-242 on the GPU (csrc/layout_ops.hip:flip_merge_kernel)."""
+def _skeleton_channels(model, skeleton):
+    """(PAF, heat-map) channels of the TTA accumulators: COCO-18's without a skeleton; with one, the skeleton's - and the
+    model must write exactly those (the check PoseEstimator makes)."""
+    if skeleton is None:
+        return 38, 19
+    from .pipeline import _check_model_channels
+    return _check_model_channels(_unwrap(model), skeleton)
+
+
+def _final_maps(model, x):
+    """(paf, heat) of the last stage, NCHW: rtpose_vgg returns them as the first result, OpenPose_Model as the last pair
+    of a list of (paf, heat) pairs."""
+    out, _ = model(x)
+    return out[-1] if isinstance(out, list) else out
+
+
+def handle_paf_and_heat(normal_heat, flipped_heat, normal_paf, flipped_paf, skeleton=None):
+    """coco_eval.py:197-242 on the GPU (csrc/layout_ops.hip:flip_merge_kernel); with a skeleton.Skeleton the same merge
+    over its left / right tables (csrc/tta_skel.hip), the maps carrying the skeleton's channel counts."""
     dev = torch.device('cuda', torch.cuda.current_device())
     t = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)[None]
          for a in (normal_heat, flipped_heat, normal_paf, flipped_paf)]
     h, w = t[0].shape[1], t[0].shape[2]
     oh, op = torch.empty_like(t[0]), torch.empty_like(t[2])
+    if skeleton is not None:
+        if (t[0].shape[3], t[2].shape[3]) != (skeleton.heat_channels, skeleton.paf_channels):
+            raise ValueError("handle_paf_and_heat: skeleton %s has %d heat-map / %d PAF channels, the maps have %d / %d"
+                             % (skeleton.name, skeleton.heat_channels, skeleton.paf_channels, t[0].shape[3], t[2].shape[3]))
+        table = skeleton.native_flip_table()
+        check(lib.rtpose_flip_merge_skel(ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), 1, h, w, ptr(oh), ptr(op),
+                                         C_byref(table), current_stream()), "rtpose_flip_merge_skel")
+        return op[0].cpu().numpy(), oh[0].cpu().numpy()
     check(lib.rtpose_flip_merge(ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), 1, h, w, ptr(oh), ptr(op),
                                 current_stream()), "rtpose_flip_merge")
     return op[0].cpu().numpy(), oh[0].cpu().numpy()
@@ -209,7 +234,8 @@ def append_result(image_id, humans, upsample_keypoints, outputs, num_keypoints=1
                         "keypoints": list(keypoints[ORDER_COCO, :].reshape(51))})
 
 
-def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.5, 2.0), flip=True, config=None):
+def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.5, 2.0), flip=True, config=None,
+                           skeleton=None):
     """Multi-scale (+ horizontal flip) test-time augmentation — BASELINE config 3 / README.md:26.
 
     The surveyed reference commit only keeps remnants of this path (handle_paf_and_heat is
@@ -219,7 +245,13 @@ def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.
     run through the net; every scale's PAF/heat-map (valid, un-padded region only) is bilinearly
     resized to the scale-1.0 map size and averaged; the flipped pass is merged per scale with the
     reference's handle_paf_and_heat semantics.  All arithmetic after the image prep is on the GPU.
-    Returns (paf [h,w,38], heatmap [h,w,19], im_scale of the 1.0 pass)."""
+    Returns (paf [h,w,38], heatmap [h,w,19], im_scale of the 1.0 pass).
+
+    skeleton: a skeleton.Skeleton (e.g. skeleton.BODY_25) - the model must write its channel counts, the flipped pass is
+    merged over skeleton.flip_tables() (rtpose_flip_merge_skel) and the maps returned carry its channels.  None: COCO-18.
+    Not for hourglass models: their input size is bound to multiples of 64, not of the stride this function pads to."""
+    paf_c, heat_c = _skeleton_channels(model, skeleton)
+    table = skeleton.native_flip_table() if skeleton is not None and flip else None
     config = config or dec.default_config()
     base = int(config.DATASET.IMAGE_SIZE)
     stride = int(config.MODEL.DOWNSAMPLE)
@@ -228,8 +260,8 @@ def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.
     h0, w0 = img.shape[:2]
     s1 = float(base) / min(h0, w0)
     hd, wd = -(-_cv_round(h0 * s1) // stride), -(-_cv_round(w0 * s1) // stride)
-    acc_heat = torch.zeros(1, hd, wd, 19, device=dev)
-    acc_paf = torch.zeros(1, hd, wd, 38, device=dev)
+    acc_heat = torch.zeros(1, hd, wd, heat_c, device=dev)
+    acc_paf = torch.zeros(1, hd, wd, paf_c, device=dev)
     stream = current_stream()
     m = _unwrap(model)
     for si, s in enumerate(scales):
@@ -242,18 +274,22 @@ def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.
             vw = real_shape[1]
             xb = torch.cat([x, x], 0)
             xb[1, :, :, :vw] = torch.flip(x[0, :, :, :vw], dims=[2])
-            (paf2, heat2), _ = model(xb)
+            paf2, heat2 = _final_maps(model, xb)
             heat2 = heat2.permute(0, 2, 3, 1)
             paf2 = paf2.permute(0, 2, 3, 1)
             vwm = -(-vw // stride)
             hv, pv = heat2[0:1, :, :vwm].contiguous(), paf2[0:1, :, :vwm].contiguous()
             hfv, pfv = heat2[1:2, :, :vwm].contiguous(), paf2[1:2, :, :vwm].contiguous()
             mh, mp = torch.empty_like(hv), torch.empty_like(pv)
-            check(lib.rtpose_flip_merge(ptr(hv), ptr(hfv), ptr(pv), ptr(pfv), 1, hv.shape[1], vwm, ptr(mh), ptr(mp),
-                                        stream), "rtpose_flip_merge")
+            if table is not None:
+                check(lib.rtpose_flip_merge_skel(ptr(hv), ptr(hfv), ptr(pv), ptr(pfv), 1, hv.shape[1], vwm, ptr(mh), ptr(mp),
+                                                 C_byref(table), stream), "rtpose_flip_merge_skel")
+            else:
+                check(lib.rtpose_flip_merge(ptr(hv), ptr(hfv), ptr(pv), ptr(pfv), 1, hv.shape[1], vwm, ptr(mh), ptr(mp),
+                                            stream), "rtpose_flip_merge")
             heat, paf = mh, mp
         else:
-            (paf, heat), _ = model(x)
+            paf, heat = _final_maps(model, x)
             heat = heat.permute(0, 2, 3, 1).contiguous()
             paf = paf.permute(0, 2, 3, 1).contiguous()
         hs, ws = heat.shape[1], heat.shape[2]
@@ -262,15 +298,15 @@ def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.
         ratio = im_scale / s1
         a = 1.0 / len(scales)
         beta = 0.0 if si == 0 else 1.0
-        check(lib.rtpose_resize_bilinear_accum(ptr(heat), hs, ws, ptr(acc_heat), hd, wd, 19, 1, hd * ratio, wd * ratio,
+        check(lib.rtpose_resize_bilinear_accum(ptr(heat), hs, ws, ptr(acc_heat), hd, wd, heat_c, 1, hd * ratio, wd * ratio,
                                                a, beta, stream), "rtpose_resize_bilinear_accum")
-        check(lib.rtpose_resize_bilinear_accum(ptr(paf), hs, ws, ptr(acc_paf), hd, wd, 38, 1, hd * ratio, wd * ratio,
+        check(lib.rtpose_resize_bilinear_accum(ptr(paf), hs, ws, ptr(acc_paf), hd, wd, paf_c, 1, hd * ratio, wd * ratio,
                                                a, beta, stream), "rtpose_resize_bilinear_accum")
     return acc_paf[0].cpu().numpy(), acc_heat[0].cpu().numpy(), s1
 
 
 def get_multiscale_outputs_batch(imgs, model, preprocess='rtpose', scales=(0.5, 1.0, 1.5, 2.0), flip=True,
-                                 config=None):
+                                 config=None, skeleton=None):
     """Batched, GPU-resident form of get_multiscale_outputs (BASELINE config 3): B uint8 BGR images
     of one size are uploaded once (3 B/pixel); per scale ONE kernel per image resizes + pads +
     normalises it (and its mirror image) straight into the input buffer of a 2B-image plan, one
@@ -278,8 +314,15 @@ def get_multiscale_outputs_batch(imgs, model, preprocess='rtpose', scales=(0.5, 
     the resize to the scale-1 map and the running average where the net wrote its outputs.
     Same arithmetic as get_multiscale_outputs, image by image.
     Returns DEVICE tensors (paf [B,h,w,38], heat [B,h,w,19]) and the scale-1 im_scale - feed them
-    to decode.decode_maps."""
+    to decode.decode_maps.
+
+    skeleton: a skeleton.Skeleton - the model must write its channel counts, the fused kernel is
+    rtpose_tta_accumulate_skel over skeleton.flip_tables() (packed once per call) and the tensors returned carry the
+    skeleton's channels: feed them to decode.decode_maps(..., skeleton=skeleton).  None: COCO-18, rtpose_tta_accumulate.
+    Not for hourglass models (see get_multiscale_outputs)."""
     import ctypes as C
+    paf_c, heat_c = _skeleton_channels(model, skeleton)
+    table = skeleton.native_flip_table() if skeleton is not None else None
     config = config or dec.default_config()
     base = int(config.DATASET.IMAGE_SIZE)
     stride = int(config.MODEL.DOWNSAMPLE)
@@ -290,8 +333,8 @@ def get_multiscale_outputs_batch(imgs, model, preprocess='rtpose', scales=(0.5, 
     img_d = torch.from_numpy(imgs).to(dev)
     s1 = float(base) / min(h0, w0)
     hd, wd = -(-_cv_round(h0 * s1) // stride), -(-_cv_round(w0 * s1) // stride)
-    acc_heat = torch.empty(B, hd, wd, 19, device=dev)
-    acc_paf = torch.empty(B, hd, wd, 38, device=dev)
+    acc_heat = torch.empty(B, hd, wd, heat_c, device=dev)
+    acc_paf = torch.empty(B, hd, wd, paf_c, device=dev)
     stream = current_stream()
     mode = {'rtpose': 0, 'vgg': 1}[preprocess]
     nb = 2 * B if flip else B
@@ -312,6 +355,12 @@ def get_multiscale_outputs_batch(imgs, model, preprocess='rtpose', scales=(0.5, 
         hbase, lheat, _, _, _ = m.output_view(plan, 1)
         wv = -(-wr // stride) if flip else ws
         ratio = im_scale / s1
+        if table is not None:
+            check(lib.rtpose_tta_accumulate_skel(hbase, C.byref(lheat), pbase, C.byref(lpaf), B, hs, wv, ptr(acc_heat),
+                                                 ptr(acc_paf), hd, wd, hd * ratio, wd * ratio, 1.0 / len(scales),
+                                                 0.0 if si == 0 else 1.0, 1 if flip else 0, C.byref(table), stream),
+                  "rtpose_tta_accumulate_skel")
+            continue
         check(lib.rtpose_tta_accumulate(hbase, C.byref(lheat), pbase, C.byref(lpaf), B, hs, wv, ptr(acc_heat),
                                         ptr(acc_paf), hd, wd, hd * ratio, wd * ratio, 1.0 / len(scales),
                                         0.0 if si == 0 else 1.0, 1 if flip else 0, stream), "rtpose_tta_accumulate")

@@ -5,10 +5,16 @@ A ``Skeleton`` is the data the `_skel` decode entry points take: the parts, the 
 limbs may start a new person.  ``decode.decode_maps(..., skeleton=s)``,
 ``pipeline.PoseEstimator(model, skeleton=s)`` and ``common.draw_humans(..., skeleton=s)`` take one.
 
-What a skeleton does NOT reach (COCO-18 only): flip merge and multi-scale TTA
-(``rtpose_flip_merge`` / ``rtpose_tta_accumulate`` carry COCO-18's left / right permutations), the
-legacy ``pafprocess.process_paf`` API and its getters, ``append_result`` / the OKS evaluation
-(COCO-18 -> COCO-17 mapping), and any reduced-precision plan.
+Flip merge and multi-scale TTA take one too: ``preprocess.handle_paf_and_heat``, ``get_multiscale_outputs`` and
+``get_multiscale_outputs_batch`` with ``skeleton=s`` run ``rtpose_flip_merge_skel`` / ``rtpose_tta_accumulate_skel``
+(csrc/tta_skel.hip, header section 5a) over ``s.flip_tables()``: which channel of the mirrored pass every output channel
+reads, and with which sign.  The tables follow from the part names (a leading ``L`` / ``R``) or an explicit ``mirror``
+and from the limbs.  The TTA paths resize with ``crop_with_factor(factor=stride)``; hourglass models, whose input size
+must be a multiple of 64, are out of their scope.
+
+What a skeleton does NOT reach (COCO-18 only): the legacy ``pafprocess.process_paf`` API and its getters,
+``append_result`` / the OKS evaluation (COCO-18 -> COCO-17 mapping), ``run_eval_batched``'s TTA mode, and any
+reduced-precision plan.
 """
 import ctypes as C
 
@@ -18,12 +24,14 @@ MAX_PARTS, MAX_LIMBS = 32, 32
 class Skeleton(object):
     """name; part_names: one string per part; limbs: sequence of (part A, part B, PAF x channel, PAF y channel);
     seed: the limbs (indices into ``limbs``) whose unmatched connections may start a person - None = every limb;
-    background: the heat map carries one more channel behind the parts.
+    background: the heat map carries one more channel behind the parts; mirror: for every part the part it becomes in
+    the x-mirrored image (a permutation that is its own inverse) - None derives it from the names: a leading ``L`` / ``R``
+    followed by an upper-case letter is swapped, any other name mirrors to itself.
 
     Validates like ``rtpose_skeleton_check``: 1..32 parts and limbs, part indices inside the parts, no limb from a
     part to itself, no (A, B) pair twice, x channel != y channel, channels >= 0, seed limbs inside the table."""
 
-    def __init__(self, name, part_names, limbs, seed=None, background=True):
+    def __init__(self, name, part_names, limbs, seed=None, background=True, mirror=None):
         self.name = str(name)
         self.part_names = tuple(str(p) for p in part_names)
         self.limbs = tuple(tuple(int(v) for v in l) for l in limbs)
@@ -56,14 +64,50 @@ class Skeleton(object):
                 raise ValueError("Skeleton %s: seed limb %d outside [0,%d)" % (self.name, s, L))
             mask |= 1 << s
         self.seed_mask = mask
+        # an explicit mirror is checked here; the one the names give is derived on first use, so that a skeleton whose
+        # names do not follow the L / R convention still decodes (it only cannot be flipped)
+        self._mirror = None if mirror is None else self._checked_mirror(tuple(int(m) for m in mirror))
+
+    @property
+    def mirror(self):
+        """For every part the part it becomes in the x-mirrored image."""
+        if self._mirror is None:
+            self._mirror = self._checked_mirror(self._mirror_from_names())
+        return self._mirror
+
+    def _checked_mirror(self, mirror):
+        P = len(self.part_names)
+        if len(mirror) != P:
+            raise ValueError("Skeleton %s: mirror has %d entries for %d parts" % (self.name, len(mirror), P))
+        for i, m in enumerate(mirror):
+            if not 0 <= m < P:
+                raise ValueError("Skeleton %s: part %d mirrors to %d, outside [0,%d)" % (self.name, i, m, P))
+            if mirror[m] != i:
+                raise ValueError("Skeleton %s: part %d mirrors to %d but %d mirrors to %d: the mirror is not an involution"
+                                 % (self.name, i, m, m, mirror[m]))
+        return mirror
+
+    def _mirror_from_names(self):
+        index = {n: i for i, n in enumerate(self.part_names)}
+        out = []
+        for n in self.part_names:
+            if len(n) > 1 and n[0] in "LR" and n[1].isupper():
+                other = ("R" if n[0] == "L" else "L") + n[1:]
+                if other not in index:
+                    raise ValueError("Skeleton %s: part %s has no counterpart %s (pass mirror= for names that do not "
+                                     "follow the L / R convention)" % (self.name, n, other))
+                out.append(index[other])
+            else:
+                out.append(index[n])
+        return tuple(out)
 
     @classmethod
-    def from_mask(cls, name, part_names, limbs, seed_mask, background=True):
+    def from_mask(cls, name, part_names, limbs, seed_mask, background=True, mirror=None):
         """The same with the seed limbs as a bit mask (bit l = limb l); bits at or above the limb count are refused."""
         n = len(tuple(limbs))
         if int(seed_mask) >> n:
             raise ValueError("Skeleton %s: seed mask 0x%x has bits at or above the %d limbs" % (name, int(seed_mask), n))
-        return cls(name, part_names, limbs, [l for l in range(n) if (int(seed_mask) >> l) & 1], background)
+        return cls(name, part_names, limbs, [l for l in range(n) if (int(seed_mask) >> l) & 1], background, mirror)
 
     num_parts = property(lambda self: len(self.part_names))
     num_limbs = property(lambda self: len(self.limbs))
@@ -82,6 +126,57 @@ class Skeleton(object):
     def pairs(self):
         """[(part A, part B)] in limb order (what draw_humans connects)."""
         return [(l[0], l[1]) for l in self.limbs]
+
+    def flip_tables(self):
+        """(heat_src, paf_src, paf_sign) of the flip merge: output heat-map channel c averages with channel heat_src[c] of
+        the x-mirrored pass, PAF channel c with paf_sign[c] * channel paf_src[c].  A limb A -> B reads the limb
+        mirror[A] -> mirror[B] as (-x, +y); where the table holds that limb only as mirror[B] -> mirror[A], as (+x, -y).
+        Raises if a limb has no mirror in the table, or if limbs that share a channel disagree about it."""
+        m, P, CP = self.mirror, self.num_parts, self.paf_channels
+        heat_src = list(m) + ([P] if self.background else [])
+        by_parts = {(l[0], l[1]): l for l in self.limbs}
+        got = {}
+        for i, (a, b, cx, cy) in enumerate(self.limbs):
+            same, rev = by_parts.get((m[a], m[b])), by_parts.get((m[b], m[a]))
+            if same is not None:
+                pairs = ((cx, same[2], -1), (cy, same[3], 1))
+            elif rev is not None:
+                pairs = ((cx, rev[2], 1), (cy, rev[3], -1))
+            else:
+                raise ValueError("Skeleton %s: limb %d (%s -> %s) has no mirror: no limb joins %s and %s"
+                                 % (self.name, i, self.part_names[a], self.part_names[b], self.part_names[m[a]],
+                                    self.part_names[m[b]]))
+            for c, s, sign in pairs:
+                if got.setdefault(c, (s, sign)) != (s, sign):
+                    raise ValueError("Skeleton %s: limb %d gives PAF channel %d the source %+d * channel %d, another limb gave "
+                                     "it %+d * channel %d" % (self.name, i, c, sign, s, got[c][1], got[c][0]))
+        paf_src = [got.get(c, (c, 1))[0] for c in range(CP)]
+        paf_sign = [got.get(c, (c, 1))[1] for c in range(CP)]
+        for c in range(CP):
+            if paf_src[paf_src[c]] != c or paf_sign[c] != paf_sign[paf_src[c]]:
+                raise ValueError("Skeleton %s: PAF channels %d and %d do not read each other: flipping twice is not the "
+                                 "identity" % (self.name, c, paf_src[c]))
+        return heat_src, paf_src, paf_sign
+
+    def native_flip_table(self):
+        """The ctypes mirror of rtpose_flip_table holding flip_tables(), checked by the library."""
+        from . import _capi
+        heat_src, paf_src, paf_sign = self.flip_tables()
+        if len(heat_src) > _capi.FLIP_MAX_HEAT or len(paf_src) > _capi.FLIP_MAX_PAF:
+            raise ValueError("Skeleton %s: %d heat-map / %d PAF channels, a flip table holds at most %d / %d"
+                             % (self.name, len(heat_src), len(paf_src), _capi.FLIP_MAX_HEAT, _capi.FLIP_MAX_PAF))
+        t = _capi.FlipTable()
+        t.struct_bytes = C.sizeof(_capi.FlipTable)
+        t.heat_channels, t.paf_channels = len(heat_src), len(paf_src)
+        for c, s in enumerate(heat_src):
+            t.heat_src[c] = s
+        mask = 0
+        for c, (s, sign) in enumerate(zip(paf_src, paf_sign)):
+            t.paf_src[c] = s
+            mask |= (sign < 0) << c
+        t.paf_neg_mask = mask
+        _capi.check(_capi.lib.rtpose_flip_table_check(C.byref(t)), "rtpose_flip_table_check")
+        return t
 
     def native(self):
         """The ctypes mirror of rtpose_skeleton, checked by the library against this skeleton's channel counts."""
