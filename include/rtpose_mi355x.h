@@ -928,9 +928,9 @@ int rtpose_decode_batch_ex(const float* heat, const rtpose_layout* lheat,
 int rtpose_gaussian_kernel1d(double* weights, int cap);
 
 /* ---- 4a. The same decoder with the skeleton as data ---------------------------------
- * The entry points above decode COCO-18 maps (18 parts, 19 limbs over 38 PAF channels;
- * their tables are compiled into the kernels).  The `_skel` entry points below run the
- * same algorithm - NMS and the bicubic patch refine, the ten-sample PAF score with its two
+ * The entry points above decode COCO-18 maps (18 parts, 19 limbs over 38 PAF channels:
+ * the library's own COCO-18 table).  The `_skel` entry points below run the same kernels
+ * and so the same algorithm - NMS and the bicubic patch refine, the ten-sample PAF score with its two
  * thresholds, the score-sorted greedy assignment (std::sort replayed on an exact tie),
  * subset-row grouping and merging (cid 0 reads as absent; a person needs at least 4 parts
  * and a score ratio of at least 0.3) - over a table the caller passes:

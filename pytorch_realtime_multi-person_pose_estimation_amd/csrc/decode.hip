@@ -3,9 +3,9 @@
 // C++ of lib/pafprocess/pafprocess.cpp (process_paf :22-194) with three
 // wavefront-level kernels, one launch each for a whole batch of images:
 //
-//   nms_refine_kernel      grid (18 parts, N)   peak test + ordered compaction +
+//   nms_refine_kernel      grid (P parts, N)    peak test + ordered compaction +
 //                                               8x bicubic patch refine/arg-max
-//   limb_assign_kernel     grid (19 limbs, N)   10-sample PAF line integral for
+//   limb_assign_kernel     grid (L limbs, N)    10-sample PAF line integral for
 //                                               every (a,b) pair + greedy 1:1
 //   group_kernel           grid (N)             subset merge + prune (one wave)
 //
@@ -15,7 +15,23 @@
 // divide/sqrt is relied upon).  All HBM reads are of the low-resolution maps:
 // the x8 nearest-neighbour up-sampling of paf_to_pose.py:382-385 is an index
 // computation (floor(x * 1/8)), never materialised.
+//
+// The skeleton is DATA - the part count P, the limbs as (part A, part B, PAF x channel, PAF y channel) and the limbs that
+// may start a person (rtpose_skeleton, header section 4a) - and there is one set of kernels for every skeleton:
+//
+//   * the skeleton travels BY VALUE as a kernel argument (528 bytes of the kernarg segment, read with scalar loads at an
+//     index that is uniform per block).  It is not uploaded to a __constant__ symbol: that would make a launch depend on
+//     what another stream uploaded last, and the decoder runs on a side stream beside the next forward;
+//   * the record is laid out by decode.h's size functions (peaks at word max(32, round_up(8 + P, 4)), subset rows of
+//     P + 3 floats, conn lists and the score / tie sections of L limbs), and every fit decision of the launcher is taken on
+//     those byte counts.
+//
+// rtpose_decode_batch[_ex] / rtpose_nms_batch[_ex] and the legacy process_paf are doors onto the same kernels with the
+// COCO-18 tables of pafprocess.h:16-24 (coco18_skeleton()); the `_skel` entry points take the caller's.  The line
+// references in the comments below are into the reference's COCO-18 code: what they say of "18 parts" holds for P.
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "common.h"
 #include "decode.h"
@@ -23,21 +39,12 @@
 
 namespace rtpose {
 
-// pafprocess.h:16-24
-__constant__ int kPairNet[19][2] = {{12, 13}, {20, 21}, {14, 15}, {16, 17}, {22, 23}, {24, 25}, {0, 1},
-                                    {2, 3},   {4, 5},   {6, 7},   {8, 9},   {10, 11}, {28, 29}, {30, 31},
-                                    {34, 35}, {32, 33}, {36, 37}, {18, 19}, {26, 27}};
-__constant__ int kPairs[19][2] = {{1, 2}, {1, 5},   {2, 3},   {3, 4},   {5, 6},   {6, 7},   {1, 8},
-                                  {8, 9}, {9, 10},  {1, 11},  {11, 12}, {12, 13}, {1, 0},   {0, 14},
-                                  {14, 16}, {0, 15}, {15, 17}, {2, 16},  {5, 17}};
-
 // ------------------------------------------------------------------------------
 // 1. NMS + refine
 // ------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void nms_refine_kernel(MapView heat, int h, int w, int up,
-                                                         double inv_up, float thr, int pcap,
-                                                         int32_t* __restrict__ result,
-                                                         int result_words) {
+__global__ __launch_bounds__(256) void nms_refine_kernel(MapView heat, int h, int w, int up, double inv_up, float thr,
+                                                         int pcap, int32_t* __restrict__ result, int result_words,
+                                                         int peaks_word) {
   const int part = blockIdx.x, n = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int32_t* res = result + (size_t)n * result_words;
@@ -70,7 +77,7 @@ __global__ __launch_bounds__(256) void nms_refine_kernel(MapView heat, int h, in
   const int count = find_peaks_block(heat, n, part, h, w, thr, pcap, s_wcount, s_px, s_py, res);
 
   // ---- refine (paf_to_pose.py:106-142): one wave per peak
-  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + kResPeaks) + (size_t)part * pcap;
+  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + peaks_word) + (size_t)part * pcap;
   for (int i = wave; i < count; i += 4) {
     const int px = s_px[i], py = s_py[i];
     const int x_min = max(0, px - 2), y_min = max(0, py - 2);
@@ -130,7 +137,7 @@ __global__ __launch_bounds__(256) void nms_refine_kernel(MapView heat, int h, in
       p.x = x_min * up + dx;  // paf_to_pose.py:129-141 collapses to this
       p.y = y_min * up + dy;
       p.score = best;
-      p.id = i;  // rebased to the running counter by the prefix kernel
+      p.id = i;  // rebased to the running counter by the prefix / grouping kernel
       peaks[i] = p;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -145,9 +152,9 @@ __global__ __launch_bounds__(256) void nms_refine_kernel(MapView heat, int h, in
 // gaussian_filter = correlate1d along axis 0 (rows), then axis 1, mode 'reflect', each pass
 // accumulated in double in scipy's symmetric-kernel order and stored as float32
 // (ndimage/src/ni_filters.c NI_Correlate1D).
-__global__ __launch_bounds__(256) void nms_refine_opt_kernel(MapView heat, int h, int w, int up, double inv_up,
-                                                             float thr, int pcap, int32_t* __restrict__ result,
-                                                             int result_words, int flags, GaussW gw) {
+__global__ __launch_bounds__(256) void nms_refine_opt_kernel(MapView heat, int h, int w, int up, double inv_up, float thr,
+                                                             int pcap, int32_t* __restrict__ result, int result_words,
+                                                             int flags, GaussW gw, int peaks_word) {
   const int part = blockIdx.x, n = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int32_t* res = result + (size_t)n * result_words;
@@ -179,7 +186,7 @@ __global__ __launch_bounds__(256) void nms_refine_opt_kernel(MapView heat, int h
     s_alpha[tid][3] = c[3];
   }
   const int count = find_peaks_block(heat, n, part, h, w, thr, pcap, s_wcount, s_px, s_py, res);
-  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + kResPeaks) + (size_t)part * pcap;
+  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + peaks_word) + (size_t)part * pcap;
 
   if (flags & RTPOSE_NMS_NO_REFINE) {
     // :135-139 + compute_resized_coords (:41-64): the peak's cell centre (c + 0.5) * up - 0.5 in
@@ -293,32 +300,32 @@ __global__ __launch_bounds__(256) void nms_refine_opt_kernel(MapView heat, int h
 }
 
 // ids = running counter over parts then peaks (paf_to_pose.py:141-142); also
-// totals in the header.  One wave per image.
-__global__ void peak_prefix_kernel(int pcap, int32_t* __restrict__ result, int result_words,
-                                   int nparts) {
+// totals in the header.  One wave per image.  (NMS only: a full decode leaves both to group_kernel<true, ...>.)
+__global__ void peak_prefix_kernel(int pcap, int32_t* __restrict__ result, int result_words, int nparts, int P,
+                                   int peaks_word) {
   const int n = blockIdx.x, lane = threadIdx.x;
   int32_t* res = result + (size_t)n * result_words;
-  __shared__ int s_start[RTPOSE_NUM_PART + 1];
+  __shared__ int s_start[RTPOSE_SKEL_MAX_PARTS + 1];
   if (lane == 0) {
     int acc = 0;
-    for (int p = 0; p < RTPOSE_NUM_PART; ++p) {
+    for (int p = 0; p < P; ++p) {
       s_start[p] = acc;
       acc += (p < nparts) ? res[kResPartCount + p] : 0;
     }
-    s_start[RTPOSE_NUM_PART] = acc;
+    s_start[P] = acc;
     res[kResHeader + 0] = acc;
   }
   __syncthreads();
-  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + kResPeaks);
+  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + peaks_word);
   for (int p = 0; p < nparts; ++p) {
     const int cnt = res[kResPartCount + p];
     for (int i = lane; i < cnt; i += 64) peaks[(size_t)p * pcap + i].id = s_start[p] + i;
   }
 }
 
-
 // ------------------------------------------------------------------------------
-// 2. PAF scoring + greedy assignment (pafprocess.cpp:46-124, :220-246)
+// 2. PAF scoring + greedy assignment (pafprocess.cpp:46-124, :220-246): grid (L limbs, N);
+//    the limb's parts and PAF channels come from `sk`
 // ------------------------------------------------------------------------------
 
 // Round 5: (a) SCORES_IN_LDS is a template parameter - the score matrix is addressed with LDS instructions (or global
@@ -336,11 +343,11 @@ __global__ void peak_prefix_kernel(int pcap, int32_t* __restrict__ result, int r
 // victims: DESIGN.md 3.3, profiles/r06_decoder_beside_forward.txt.  (a) - (c) were each tried as the cure and are not it
 // (they stay: fewer instructions); (d) is.
 template <bool SCORES_IN_LDS, bool UP_POW2, bool A32>
-__global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, int w, double inv_up, int up_shift,
-                                                          int h1, int pcap,
-                                                          const int32_t* __restrict__ result,
-                                                          int result_words, int32_t* __restrict__ conn,
-                                                          int conn_words, float* __restrict__ score_ws,
+__global__ __launch_bounds__(256) void limb_assign_kernel(rtpose_skeleton sk, int peaks_word, MapView paf, int h, int w,
+                                                          double inv_up, int up_shift, int h1, int pcap,
+                                                          const int32_t* __restrict__ result, int result_words,
+                                                          int32_t* __restrict__ conn, int conn_words,
+                                                          float* __restrict__ score_ws,
                                                           unsigned long long* __restrict__ tie_ws) {
   const int pair_id = blockIdx.x, n = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -358,16 +365,16 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, in
   // barrier let the next step start - a global round trip per connection)
   __shared__ int s_conn[3 * kDecodeMaxPeaks];
 
-  const int partA = kPairs[pair_id][0], partB = kPairs[pair_id][1];
-  const int chx = kPairNet[pair_id][0], chy = kPairNet[pair_id][1];
+  const int partA = sk.limb_part[pair_id][0], partB = sk.limb_part[pair_id][1];
+  const int chx = sk.limb_paf[pair_id][0], chy = sk.limb_paf[pair_id][1];
   const int nA = res[kResPartCount + partA], nB = res[kResPartCount + partB];
   if (tid == 0) s_nconn = 0;
   if (nA == 0 || nB == 0) {
     if (tid == 0) cn[0] = 0;
     return;
   }
-  const rtpose_peak* pA = reinterpret_cast<const rtpose_peak*>(res + kResPeaks) + (size_t)partA * pcap;
-  const rtpose_peak* pB = reinterpret_cast<const rtpose_peak*>(res + kResPeaks) + (size_t)partB * pcap;
+  const rtpose_peak* pA = reinterpret_cast<const rtpose_peak*>(res + peaks_word) + (size_t)partA * pcap;
+  const rtpose_peak* pB = reinterpret_cast<const rtpose_peak*>(res + peaks_word) + (size_t)partB * pcap;
   for (int i = tid; i < kDecodeMaxPeaks; i += 256) {
     s_usedA[i] = 0;
     s_usedB[i] = 0;
@@ -375,14 +382,15 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, in
 
   const int npairs = nA * nB;
   // A32: the image's two PAF channel planes as wave-uniform bases (SGPR pairs) + ONE 32-bit byte offset per sample
-  // (global_load_dword v, v_off, s[base:base+1]); the host picks it when every offset of an image fits 31 bits
+  // (global_load_dword v, v_off, s[base:base+1]); the host picks it when every offset of an image fits 31 bits.  The y
+  // plane may lie below the x plane (a skeleton names its channels freely): the difference is signed
   const char* const img_x =
       reinterpret_cast<const char*>(paf.base + ((size_t)paf.lead + (size_t)n * paf.hs * paf.ws) * paf.cstride + paf.choff + chx);
   const char* const img_y = img_x + (ptrdiff_t)(chy - chx) * (ptrdiff_t)sizeof(float);
   const unsigned pix_bytes = (unsigned)paf.cstride * (unsigned)sizeof(float);
   // the score matrix lives in LDS unless the tables were grown past what LDS holds
   // (junk maps with hundreds of peaks per part): then in the global workspace
-  float* const score_g = score_ws + ((size_t)n * RTPOSE_NUM_LIMB + pair_id) * pcap * pcap;
+  float* const score_g = score_ws + ((size_t)n * sk.num_limbs + pair_id) * pcap * pcap;
   auto s_score = [&](int p) -> float& {
     if constexpr (SCORES_IN_LDS)
       return s_score_lds[p];
@@ -541,7 +549,7 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, in
     // candidates in push order: ordered compaction by ballot / popcount, like the peak ids
     unsigned long long* lds_list =
         reinterpret_cast<unsigned long long*>(s_score_lds + (SCORES_IN_LDS ? ((pcap * pcap + 1) & ~1) : 0));
-    unsigned long long* ws_list = tie_ws + ((size_t)n * RTPOSE_NUM_LIMB + pair_id) * pcap * pcap;
+    unsigned long long* ws_list = tie_ws + ((size_t)n * sk.num_limbs + pair_id) * pcap * pcap;
     for (int pass = 0; pass < 2; ++pass) {  // pass 0 counts (LDS or workspace?), pass 1 writes
       unsigned long long* list = (s_nconn <= kTieLdsCands) ? lds_list : ws_list;  // (s_nconn = the count after pass 0)
       int base = 0;
@@ -596,58 +604,71 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(MapView paf, int h, in
 // ------------------------------------------------------------------------------
 // 3. Person grouping + prune (pafprocess.cpp:126-191), one wave per image
 // ------------------------------------------------------------------------------
+// A subset row (the reference's `subset` entry, 18 + 2 floats there) is P + 3 floats: [0, P) the parts' cids, [P] the score
+// sum, [P + 1] the part count, [P + 2] alive; lanes below P (P <= 32) work on a row.  A limb may start a person when its bit
+// of sk.seed_mask is set (COCO-18: the first 18 of the 19 limbs, the `pair_id < 18` of cpp:173).
 // The walk over the connections is the reference's serial loop (every connection sees the rows the previous one left), so
 // what it costs is the latency of one step.  Round 6: a limb's connections are STAGED first - the 64 lanes fetch the
 // (a, b, score) triples, the two peak ids and the two peak scores of up to 64 connections at a time into LDS, in parallel - and
 // the serial walk then touches LDS only (round 5: three dependent global loads per connection, ~1.6 us each step: 164 us per
 // batch whatever its size; now ~20).  WRITE_IDS: the running peak ids of paf_to_pose.py:141-142 (the former peak_prefix_kernel
-// launch) are written here - and taken arithmetically, id = s_start[part] + index, instead of read back.
-// STAGE_ALL: the connections of ALL 19 limbs are staged in one sweep over the flattened (limb, connection) list - every
+// launch) are written here - and taken arithmetically, id = s_start[part] + index, instead of read back; false for the legacy
+// process_paf, whose peak tables carry the ids of the caller's joint list.
+// STAGE_ALL: the connections of ALL L limbs are staged in one sweep over the flattened (limb, connection) list - every
 // global round trip of the kernel is then taken once, with all lanes' loads in flight together, instead of once per limb (the
-// host picks it when 19 * pcap staged connections fit the LDS next to the rows: pcap <= 128).
-template <bool WRITE_IDS, bool STAGE_ALL>
-__global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* __restrict__ result,
-                                                   int result_words, const int32_t* __restrict__ conn,
-                                                   int conn_words, int row_cap,
+// host picks it when L * pcap staged connections fit the LDS next to the rows: pcap <= 128 for COCO-18).
+// ROWS_IN_LDS: the rows are addressed with LDS instructions or global ones, decided by the host on their byte count
+// (decode_rows_in_lds) - a template parameter for the reason SCORES_IN_LDS is one.
+template <bool WRITE_IDS, bool STAGE_ALL, bool ROWS_IN_LDS>
+__global__ __launch_bounds__(64) void group_kernel(rtpose_skeleton sk, int peaks_word, int pcap, int hcap,
+                                                   int32_t* __restrict__ result, int result_words,
+                                                   const int32_t* __restrict__ conn, int conn_words, int row_cap,
                                                    float* __restrict__ rows_ws) {
   const int n = blockIdx.x, lane = threadIdx.x;
+  const int P = sk.num_parts, L = sk.num_limbs;
+  const int RW = P + 3, kSum = P, kCnt = P + 1, kAlive = P + 2;
   int32_t* res = result + (size_t)n * result_words;
   const int32_t* cnb = conn + (size_t)n * conn_words;
   extern __shared__ float rows_lds[];
-  // [row_cap][20 + alive]: the reference's `subset`; LDS unless grown past kLdsRows; then the staged connections of one limb
-  float* rows = row_cap <= kLdsRows ? rows_lds : rows_ws + (size_t)n * row_cap * 21;
-  float* stage = rows_lds + (row_cap <= kLdsRows ? (size_t)row_cap * 21 : 0);
+  // [row_cap][P + 2 + alive]: the reference's `subset`; LDS unless grown past kLdsRowBytes; then the staged connections (of
+  // one limb, or of all)
+  float* rows = ROWS_IN_LDS ? rows_lds : rows_ws + (size_t)n * row_cap * RW;
+  float* stage = rows_lds + (ROWS_IN_LDS ? (size_t)row_cap * RW : 0);
 
-  __shared__ int s_start[RTPOSE_NUM_PART + 1];
+  __shared__ int s_start[RTPOSE_SKEL_MAX_PARTS + 1];
   if (lane == 0) {
     int acc = 0;
-    for (int p = 0; p < RTPOSE_NUM_PART; ++p) {
+    for (int p = 0; p < P; ++p) {
       s_start[p] = acc;
       acc += res[kResPartCount + p];
     }
-    s_start[RTPOSE_NUM_PART] = acc;
+    s_start[P] = acc;
     if (WRITE_IDS) res[kResHeader + 0] = acc;
   }
   __syncthreads();
-  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + kResPeaks);
+  rtpose_peak* peaks = reinterpret_cast<rtpose_peak*>(res + peaks_word);
   if (WRITE_IDS) {
     // ids = running counter over parts then peaks (paf_to_pose.py:141-142)
-    for (int p = 0; p < RTPOSE_NUM_PART; ++p) {
+    for (int p = 0; p < P; ++p) {
       const int cnt = s_start[p + 1] - s_start[p];
       for (int i = lane; i < cnt; i += 64) peaks[(size_t)p * pcap + i].id = s_start[p] + i;
     }
   }
-  // peak_infos_line[pos] (cpp:38-43): part-major position -> peak
+  // peak_infos_line[pos] (cpp:38-43): part-major position -> peak (WRITE_IDS = false only).  The part is the number of
+  // starts at or below pos - s_start ascends - counted eight at a time, so that the LDS reads are independent and
+  // in flight together: walking the starts one dependent read after the other cost the legacy process_paf 1.4 us per call
+  // (profiles/r12_one_decoder.txt)
   auto line_peak_score = [&](int pos) -> float {
     int p = 0;
-    while (p + 1 < RTPOSE_NUM_PART && pos >= s_start[p + 1]) ++p;
+#pragma unroll 8
+    for (int q = 1; q < P; ++q) p += pos >= s_start[q] ? 1 : 0;
     return peaks[(size_t)p * pcap + (pos - s_start[p])].score;
   };
-  const int npeaks = s_start[RTPOSE_NUM_PART];
+  const int npeaks = s_start[P];
 
   // everything the walk needs from global memory about connection c of limb `limb`, into st[0 .. kStageWords)
   auto stage_conn = [&](int limb, int c, float* st) {
-    const int part1 = kPairs[limb][0], part2 = kPairs[limb][1];
+    const int part1 = sk.limb_part[limb][0], part2 = sk.limb_part[limb][1];
     const int32_t* cn = cnb + (size_t)limb * (1 + 3 * pcap);
     const rtpose_peak* pA = peaks + (size_t)part1 * pcap;
     const rtpose_peak* pB = peaks + (size_t)part2 * pcap;
@@ -660,16 +681,16 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
     st[3] = (id2 >= 0 && id2 < npeaks) ? (WRITE_IDS ? pB[ib].score : line_peak_score(id2)) : 0.f;
     st[4] = (id1 >= 0 && id1 < npeaks) ? (WRITE_IDS ? pA[ia].score : line_peak_score(id1)) : 0.f;
   };
-  __shared__ int s_cbase[RTPOSE_NUM_LIMB + 1];
+  __shared__ int s_cbase[RTPOSE_SKEL_MAX_LIMBS + 1];
   if (STAGE_ALL) {
-    if (lane < RTPOSE_NUM_LIMB) s_cbase[lane + 1] = cnb[(size_t)lane * (1 + 3 * pcap)];
+    if (lane < L) s_cbase[lane + 1] = cnb[(size_t)lane * (1 + 3 * pcap)];
     __syncthreads();
     if (lane == 0) {
       s_cbase[0] = 0;
-      for (int l = 0; l < RTPOSE_NUM_LIMB; ++l) s_cbase[l + 1] += s_cbase[l];
+      for (int l = 0; l < L; ++l) s_cbase[l + 1] += s_cbase[l];
     }
     __syncthreads();
-    const int total = s_cbase[RTPOSE_NUM_LIMB];
+    const int total = s_cbase[L];
     for (int i = lane; i < total; i += 64) {
       int limb = 0;
       while (i >= s_cbase[limb + 1]) ++limb;
@@ -681,8 +702,9 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
 
   int nrows = 0;
   bool overflow = false;
-  for (int pair_id = 0; pair_id < 19; ++pair_id) {
-    const int part1 = kPairs[pair_id][0], part2 = kPairs[pair_id][1];
+  for (int pair_id = 0; pair_id < L; ++pair_id) {
+    const int part1 = sk.limb_part[pair_id][0], part2 = sk.limb_part[pair_id][1];
+    const bool may_seed = (sk.seed_mask >> pair_id) & 1u;
     int nconn;
     const float* lst = stage;
     if (STAGE_ALL) {
@@ -703,8 +725,8 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
       for (int r0 = 0; r0 < nrows; r0 += 64) {
         const int r = r0 + lane;
         bool hit = false;
-        if (r < nrows && rows[(size_t)r * 21 + 20] != 0.f)
-          hit = rows[(size_t)r * 21 + part1] == cid1 || rows[(size_t)r * 21 + part2] == cid2;
+        if (r < nrows && rows[(size_t)r * RW + kAlive] != 0.f)
+          hit = rows[(size_t)r * RW + part1] == cid1 || rows[(size_t)r * RW + part2] == cid2;
         unsigned long long m = __ballot(hit);
         while (m) {
           const int b = __ffsll((long long)m) - 1;
@@ -715,40 +737,40 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
         }
       }
       if (found == 1) {
-        float* row = rows + (size_t)idx1 * 21;
+        float* row = rows + (size_t)idx1 * RW;
         if (lane == 0 && row[part2] != cid2) {
           row[part2] = cid2;
-          row[19] = row[19] + 1.f;
-          row[18] = row[18] + (s2 + cscore);
+          row[kCnt] = row[kCnt] + 1.f;
+          row[kSum] = row[kSum] + (s2 + cscore);
         }
       } else if (found == 2) {
-        float* r1 = rows + (size_t)idx1 * 21;
-        float* r2 = rows + (size_t)idx2 * 21;
+        float* r1 = rows + (size_t)idx1 * RW;
+        float* r2 = rows + (size_t)idx2 * RW;
         bool both = false;
-        if (lane < 18) both = r1[lane] > 0.f && r2[lane] > 0.f;  // cid 0 reads as absent (cpp:155)
+        if (lane < P) both = r1[lane] > 0.f && r2[lane] > 0.f;  // cid 0 reads as absent (cpp:155)
         const bool membership = __any(both);
         if (!membership) {
-          if (lane < 18) r1[lane] = r1[lane] + (r2[lane] + 1.f);
+          if (lane < P) r1[lane] = r1[lane] + (r2[lane] + 1.f);
           if (lane == 0) {
-            r1[19] = r1[19] + r2[19];
-            r1[18] = r1[18] + r2[18];
-            r1[18] = r1[18] + cscore;
-            r2[20] = 0.f;  // erase(subset_idx2): order of the survivors is kept
+            r1[kCnt] = r1[kCnt] + r2[kCnt];
+            r1[kSum] = r1[kSum] + r2[kSum];
+            r1[kSum] = r1[kSum] + cscore;
+            r2[kAlive] = 0.f;  // erase(subset_idx2): order of the survivors is kept
           }
         } else if (lane == 0) {
           r1[part2] = cid2;
-          r1[19] = r1[19] + 1.f;
-          r1[18] = r1[18] + (s2 + cscore);
+          r1[kCnt] = r1[kCnt] + 1.f;
+          r1[kSum] = r1[kSum] + (s2 + cscore);
         }
-      } else if (found == 0 && pair_id < 18) {
+      } else if (found == 0 && may_seed) {
         if (nrows < row_cap) {
-          float* row = rows + (size_t)nrows * 21;
+          float* row = rows + (size_t)nrows * RW;
           const float s1 = st[4];
-          if (lane < 18) row[lane] = (lane == part1) ? cid1 : ((lane == part2) ? cid2 : -1.f);
+          if (lane < P) row[lane] = (lane == part1) ? cid1 : ((lane == part2) ? cid2 : -1.f);
           if (lane == 0) {
-            row[19] = 2.f;
-            row[18] = (s1 + s2) + cscore;
-            row[20] = 1.f;
+            row[kCnt] = 2.f;
+            row[kSum] = (s1 + s2) + cscore;
+            row[kAlive] = 1.f;
           }
           ++nrows;
         } else {
@@ -762,15 +784,15 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
 
   // prune (cpp:187-191) and emit
   int nh = 0;
-  int32_t* hparts = res + kResPeaks + 4 * RTPOSE_NUM_PART * pcap;
-  float* hscore = reinterpret_cast<float*>(hparts + (size_t)RTPOSE_NUM_PART * hcap);
+  int32_t* hparts = res + peaks_word + 4 * P * pcap;
+  float* hscore = reinterpret_cast<float*>(hparts + (size_t)P * hcap);
   for (int r = 0; r < nrows; ++r) {
-    const float* row = rows + (size_t)r * 21;
-    if (row[20] == 0.f) continue;
-    if (row[19] < 4.f || row[18] / row[19] < 0.3f) continue;
+    const float* row = rows + (size_t)r * RW;
+    if (row[kAlive] == 0.f) continue;
+    if (row[kCnt] < 4.f || row[kSum] / row[kCnt] < 0.3f) continue;
     if (nh < hcap) {
-      if (lane < 18) hparts[(size_t)nh * RTPOSE_NUM_PART + lane] = (int)row[lane];
-      if (lane == 0) hscore[nh] = row[18] / row[19];
+      if (lane < P) hparts[(size_t)nh * P + lane] = (int)row[lane];
+      if (lane == 0) hscore[nh] = row[kSum] / row[kCnt];
       ++nh;
     } else {
       overflow = true;
@@ -782,21 +804,103 @@ __global__ __launch_bounds__(64) void group_kernel(int pcap, int hcap, int32_t* 
   }
 }
 
-// header + part counts of every record <- 0, except header[3] / [4] = the capacities the record is laid out for
-// (max_peaks_per_part, max_humans): a record block describes itself, a consumer that parses it later - after the
-// producer has grown its tables - does not need the producer's cfg of that moment.
-__global__ void clear_header_kernel(int32_t* __restrict__ result, int result_words, int N, int pcap, int hcap) {
+// header + part counts of every record <- 0, except the words that describe the record: [3] / [4] = the capacities the
+// record is laid out for (max_peaks_per_part, max_humans) - a record block describes itself, a consumer that parses it
+// later, after the producer has grown its tables, does not need the producer's cfg of that moment - and [5] / [6] = the two
+// values the caller passes: the skeleton's part and limb counts from the `_skel` entry points, 0 / 0 from the COCO-18
+// ones, whose records define words 0..4 only (0 / 0 reads as 18 / 19).
+__global__ void clear_header_kernel(int32_t* __restrict__ result, int result_words, int N, int pcap, int hcap, int P,
+                                    int L, int peaks_word) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N * kResPeaks) {
-    const int wd = i % kResPeaks;
-    result[(size_t)(i / kResPeaks) * result_words + wd] = wd == kResHeader + 3 ? pcap : wd == kResHeader + 4 ? hcap : 0;
+  if (i < N * peaks_word) {
+    const int wd = i % peaks_word;
+    result[(size_t)(i / peaks_word) * result_words + wd] = wd == kResHeader + 3   ? pcap
+                                                           : wd == kResHeader + 4 ? hcap
+                                                           : wd == kResHeader + 5 ? P
+                                                           : wd == kResHeader + 6 ? L
+                                                                                  : 0;
   }
 }
 
-static int check_cfg(const rtpose_decode_cfg* cfg) {
+// ------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------
+static const int kCoco18Limbs[19][4] = {  // (part A, part B, PAF x, PAF y): pafprocess.h:16-24's CocoPairs / CocoPairsNetwork
+    {1, 2, 12, 13},  {1, 5, 20, 21},   {2, 3, 14, 15},   {3, 4, 16, 17},   {5, 6, 22, 23},  {6, 7, 24, 25},  {1, 8, 0, 1},
+    {8, 9, 2, 3},    {9, 10, 4, 5},    {1, 11, 6, 7},    {11, 12, 8, 9},   {12, 13, 10, 11}, {1, 0, 28, 29}, {0, 14, 30, 31},
+    {14, 16, 34, 35}, {0, 15, 32, 33}, {15, 17, 36, 37}, {2, 16, 18, 19},  {5, 17, 26, 27}};
+
+// BODY_25 (25 parts, heat-map channel 25 = background; 26 limbs over 52 PAF channels), written from memory of upstream
+// OpenPose's poseParameters.cpp: NOT VERIFIED against CMU's weights - no copy of that file or of the weights was at hand.
+// The grouping run over these tables is this project's (the tf-pose pafprocess algorithm this file implements), not
+// OpenPose's own bodyPartConnector.
+static const int kBody25Limbs[26][4] = {
+    {1, 8, 0, 1},     {1, 2, 14, 15},   {1, 5, 22, 23},   {2, 3, 16, 17},   {3, 4, 18, 19},   {5, 6, 24, 25},  {6, 7, 26, 27},
+    {8, 9, 6, 7},     {9, 10, 2, 3},    {10, 11, 4, 5},   {8, 12, 8, 9},    {12, 13, 10, 11}, {13, 14, 12, 13}, {1, 0, 30, 31},
+    {0, 15, 32, 33},  {15, 17, 36, 37}, {0, 16, 34, 35},  {16, 18, 38, 39}, {2, 17, 20, 21},  {5, 18, 28, 29}, {14, 19, 40, 41},
+    {19, 20, 42, 43}, {14, 21, 44, 45}, {11, 22, 46, 47}, {22, 23, 48, 49}, {11, 24, 50, 51}};
+
+static int fill_skeleton(rtpose_skeleton* s, int P, int L, const int (*limbs)[4], uint32_t seed_mask) {
+  if (!s) return fail(RTPOSE_E_INVAL, "skeleton: NULL argument");
+  memset(s, 0, sizeof(*s));
+  s->struct_bytes = (uint32_t)sizeof(*s);
+  s->num_parts = P;
+  s->num_limbs = L;
+  for (int l = 0; l < L; ++l) {
+    s->limb_part[l][0] = limbs[l][0];
+    s->limb_part[l][1] = limbs[l][1];
+    s->limb_paf[l][0] = limbs[l][2];
+    s->limb_paf[l][1] = limbs[l][3];
+  }
+  s->seed_mask = seed_mask;
+  return 0;
+}
+
+// everything about the tables themselves; the channel counts of the maps are checked on top when they are known
+static int check_skeleton(const rtpose_skeleton* s, bool with_channels, int heat_channels, int paf_channels) {
+  if (!s) return fail(RTPOSE_E_INVAL, "skeleton: NULL argument");
+  if (s->struct_bytes != sizeof(rtpose_skeleton))
+    return fail(RTPOSE_E_INVAL, "skeleton: struct_bytes is %u, this library's rtpose_skeleton has %zu", s->struct_bytes,
+                sizeof(rtpose_skeleton));
+  const int P = s->num_parts, L = s->num_limbs;
+  if (P < 1 || P > RTPOSE_SKEL_MAX_PARTS)
+    return fail(RTPOSE_E_INVAL, "skeleton: num_parts %d outside [1,%d]", P, RTPOSE_SKEL_MAX_PARTS);
+  if (L < 1 || L > RTPOSE_SKEL_MAX_LIMBS)
+    return fail(RTPOSE_E_INVAL, "skeleton: num_limbs %d outside [1,%d]", L, RTPOSE_SKEL_MAX_LIMBS);
+  if (L < 32 && (s->seed_mask >> L) != 0)
+    return fail(RTPOSE_E_INVAL, "skeleton: seed_mask 0x%x has bits at or above num_limbs %d", s->seed_mask, L);
+  if (with_channels && heat_channels < P)
+    return fail(RTPOSE_E_INVAL, "skeleton: %d parts need at least %d heat-map channels, the map has %d", P, P, heat_channels);
+  for (int l = 0; l < L; ++l) {
+    const int a = s->limb_part[l][0], b = s->limb_part[l][1], cx = s->limb_paf[l][0], cy = s->limb_paf[l][1];
+    if (a < 0 || a >= P || b < 0 || b >= P)
+      return fail(RTPOSE_E_INVAL, "skeleton: limb %d joins parts %d and %d, outside [0,%d)", l, a, b, P);
+    if (a == b) return fail(RTPOSE_E_INVAL, "skeleton: limb %d joins part %d with itself", l, a);
+    if (cx < 0 || cy < 0) return fail(RTPOSE_E_INVAL, "skeleton: limb %d reads PAF channels %d and %d", l, cx, cy);
+    if (with_channels && (cx >= paf_channels || cy >= paf_channels))
+      return fail(RTPOSE_E_INVAL, "skeleton: limb %d reads PAF channels %d and %d, the map has %d", l, cx, cy, paf_channels);
+    if (cx == cy) return fail(RTPOSE_E_INVAL, "skeleton: limb %d has the same PAF channel %d for x and y", l, cx);
+    for (int k = 0; k < l; ++k)
+      if (s->limb_part[k][0] == a && s->limb_part[k][1] == b)
+        return fail(RTPOSE_E_INVAL, "skeleton: limb %d repeats limb %d (parts %d -> %d)", l, k, a, b);
+  }
+  return 0;
+}
+
+const rtpose_skeleton* coco18_skeleton() {
+  static const rtpose_skeleton coco = [] {
+    rtpose_skeleton s;
+    fill_skeleton(&s, RTPOSE_NUM_PART, RTPOSE_NUM_LIMB, kCoco18Limbs, 0x3FFFFu);
+    return s;
+  }();
+  return &coco;
+}
+
+// max_parts: the skeleton's part count (18 behind the entry points that take no skeleton)
+static int check_cfg(const rtpose_decode_cfg* cfg, int max_parts) {
   if (!cfg) return fail(RTPOSE_E_INVAL, "decode: cfg is NULL");
-  if (cfg->num_keypoints < 1 || cfg->num_keypoints > RTPOSE_NUM_PART)
-    return fail(RTPOSE_E_INVAL, "decode: num_keypoints must be in [1,18]");
+  if (cfg->num_keypoints < 1 || cfg->num_keypoints > max_parts)
+    return fail(RTPOSE_E_INVAL, "decode: num_keypoints must be in [1,%d]", max_parts);
   if (cfg->upsample < 1 || cfg->upsample > kMaxUp)
     return fail(RTPOSE_E_INVAL, "decode: upsample must be in [1,%d]", kMaxUp);
   if (cfg->max_peaks_per_part < 1 || cfg->max_peaks_per_part > kDecodeMaxPeaks)
@@ -805,51 +909,55 @@ static int check_cfg(const rtpose_decode_cfg* cfg) {
   return 0;
 }
 
-int nms_launch(const float* heat, const rtpose_layout* lheat, int N, int h, int w,
-               const rtpose_decode_cfg* cfg, void* result, hipStream_t s, int flags, bool with_ids) {
-  int rc = check_cfg(cfg);
-  if (rc) return rc;
+// cfg and sk have been checked by the caller.  header_P / header_L: what the records' header words 5 / 6 say.
+// with_ids: also run peak_prefix_kernel (the running peak ids + the peak total); a full decode leaves that to
+// assign_group_launch(write_ids = true), which writes them in its grouping kernel: one launch less
+static int nms_launch(const float* heat, const rtpose_layout* lheat, int N, int h, int w, const rtpose_decode_cfg* cfg,
+                      const rtpose_skeleton* sk, int header_P, int header_L, void* result, hipStream_t s, int flags,
+                      bool with_ids) {
   if (N <= 0 || h <= 0 || w <= 0) return fail(RTPOSE_E_INVAL, "decode: empty batch");
-  const int words = decode_result_words(cfg);
-  int32_t* res = static_cast<int32_t*>(result);
-  hipLaunchKernelGGL(clear_header_kernel, dim3(ceil_div(N * kResPeaks, 256)), dim3(256), 0, s, res, words, N,
-                     cfg->max_peaks_per_part, cfg->max_humans);
   if (flags & ~(RTPOSE_NMS_NO_REFINE | RTPOSE_NMS_GAUSSIAN)) return fail(RTPOSE_E_INVAL, "nms: unknown flag");
+  const int P = sk->num_parts;
+  const int words = decode_result_words(cfg, P), peaks_word = decode_peaks_word(P);
+  const int pcap = cfg->max_peaks_per_part, up = cfg->upsample;
+  int32_t* res = static_cast<int32_t*>(result);
+  hipLaunchKernelGGL(clear_header_kernel, dim3(ceil_div(N * peaks_word, 256)), dim3(256), 0, s, res, words, N, pcap,
+                     cfg->max_humans, header_P, header_L, peaks_word);
   if (flags) {
-    const size_t dyn = (size_t)2 * 25 * cfg->upsample * cfg->upsample * sizeof(float);
-    hipLaunchKernelGGL(nms_refine_opt_kernel, dim3(cfg->num_keypoints, N), dim3(256), dyn, s,
-                       to_view(heat, lheat), h, w, cfg->upsample, 1.0 / (double)cfg->upsample,
-                       cfg->thresh_heatmap, cfg->max_peaks_per_part, res, words, flags, gauss_weights());
+    const size_t dyn = (size_t)2 * 25 * up * up * sizeof(float);
+    hipLaunchKernelGGL(nms_refine_opt_kernel, dim3(cfg->num_keypoints, N), dim3(256), dyn, s, to_view(heat, lheat), h, w, up,
+                       1.0 / (double)up, cfg->thresh_heatmap, pcap, res, words, flags, gauss_weights(), peaks_word);
   } else {
-    hipLaunchKernelGGL(nms_refine_kernel, dim3(cfg->num_keypoints, N), dim3(256), 0, s, to_view(heat, lheat),
-                       h, w, cfg->upsample, 1.0 / (double)cfg->upsample, cfg->thresh_heatmap,
-                       cfg->max_peaks_per_part, res, words);
+    hipLaunchKernelGGL(nms_refine_kernel, dim3(cfg->num_keypoints, N), dim3(256), 0, s, to_view(heat, lheat), h, w, up,
+                       1.0 / (double)up, cfg->thresh_heatmap, pcap, res, words, peaks_word);
   }
-  if (with_ids)  // (a full decode writes the ids and the peak total in group_kernel<true> instead: one launch less)
-    hipLaunchKernelGGL(peak_prefix_kernel, dim3(N), dim3(64), 0, s, cfg->max_peaks_per_part, res, words,
-                       cfg->num_keypoints);
+  if (with_ids)
+    hipLaunchKernelGGL(peak_prefix_kernel, dim3(N), dim3(64), 0, s, pcap, res, words, cfg->num_keypoints, P, peaks_word);
   RTPOSE_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-// assignment + grouping on peak tables already in `result`
-int assign_group_launch(const float* paf, const rtpose_layout* lpaf, int N, int h, int w, double inv_up,
-                        int h1, const rtpose_decode_cfg* cfg, void* workspace, size_t workspace_bytes,
+// assignment + grouping on the peak tables in `result`; every switch below is taken on byte counts computed from P and L
+int assign_group_launch(const float* paf, const rtpose_layout* lpaf, int N, int h, int w, double inv_up, int h1,
+                        const rtpose_decode_cfg* cfg, const rtpose_skeleton* sk, void* workspace, size_t workspace_bytes,
                         void* result, hipStream_t s, bool write_ids) {
-  if (workspace_bytes < decode_workspace_bytes(cfg, N))
-    return fail(RTPOSE_E_INVAL, "decode: workspace too small");
+  const int P = sk->num_parts, L = sk->num_limbs;
+  if (workspace_bytes < decode_workspace_bytes(cfg, P, L, N)) return fail(RTPOSE_E_INVAL, "decode: workspace too small");
   const int pcap = cfg->max_peaks_per_part;
-  const int words = decode_result_words(cfg);
-  const int conn_words = decode_conn_words(cfg);
+  const int words = decode_result_words(cfg, P), peaks_word = decode_peaks_word(P);
+  const int conn_words = decode_conn_words(cfg, L);
   int32_t* res = static_cast<int32_t*>(result);
   int32_t* conn = static_cast<int32_t*>(workspace);
   char* wsb = static_cast<char*>(workspace);
-  float* score_ws = reinterpret_cast<float*>(wsb + decode_ws_conn_bytes(cfg, N));
-  float* rows_ws = reinterpret_cast<float*>(wsb + decode_ws_conn_bytes(cfg, N) + decode_ws_score_bytes(cfg, N));
-  unsigned long long* tie_ws = reinterpret_cast<unsigned long long*>(wsb + decode_ws_conn_bytes(cfg, N) + decode_ws_score_bytes(cfg, N) +
-                                               decode_ws_rows_bytes(cfg, N));
+  size_t off = decode_ws_conn_bytes(cfg, L, N);
+  float* score_ws = reinterpret_cast<float*>(wsb + off);
+  off += decode_ws_score_bytes(cfg, L, N);
+  float* rows_ws = reinterpret_cast<float*>(wsb + off);
+  off += decode_ws_rows_bytes(cfg, P, N);
+  unsigned long long* tie_ws = reinterpret_cast<unsigned long long*>(wsb + off);
   // scores (when they fit) + the LDS-resident candidate list of a limb that replays std::sort
-  const size_t lds = (pcap * pcap <= kLdsPairs ? (size_t)((pcap * pcap + 1) & ~1) * sizeof(float) : 0) +
+  const bool in_lds = decode_scores_in_lds(cfg);
+  const size_t lds = (in_lds ? (size_t)((pcap * pcap + 1) & ~1) * sizeof(float) : 0) +
                      (size_t)kTieLdsCands * sizeof(unsigned long long);
   static PerDeviceOnce attr_set;  // zero-initialised; the attribute is per device
   const int dev = current_device();
@@ -864,10 +972,14 @@ int assign_group_launch(const float* paf, const rtpose_layout* lpaf, int N, int 
                                    reinterpret_cast<const void*>(limb_assign_kernel<false, false, false>)};
     for (const void* k : limb_kernels)
       RTPOSE_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    const void* group_kernels[4] = {reinterpret_cast<const void*>(group_kernel<true, true>),
-                                    reinterpret_cast<const void*>(group_kernel<true, false>),
-                                    reinterpret_cast<const void*>(group_kernel<false, true>),
-                                    reinterpret_cast<const void*>(group_kernel<false, false>)};
+    const void* group_kernels[8] = {reinterpret_cast<const void*>(group_kernel<true, true, true>),
+                                    reinterpret_cast<const void*>(group_kernel<true, false, true>),
+                                    reinterpret_cast<const void*>(group_kernel<true, true, false>),
+                                    reinterpret_cast<const void*>(group_kernel<true, false, false>),
+                                    reinterpret_cast<const void*>(group_kernel<false, true, true>),
+                                    reinterpret_cast<const void*>(group_kernel<false, false, true>),
+                                    reinterpret_cast<const void*>(group_kernel<false, true, false>),
+                                    reinterpret_cast<const void*>(group_kernel<false, false, false>)};
     for (const void* k : group_kernels)
       RTPOSE_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     attr_set.set(dev);
@@ -876,18 +988,17 @@ int assign_group_launch(const float* paf, const rtpose_layout* lpaf, int N, int 
   int up_shift = -1;  // log2(up) when it is a power of two
   for (int k = 0; k < 8; ++k)
     if (up == (1 << k)) up_shift = k;
-  const bool in_lds = pcap * pcap <= kLdsPairs;
   // 32-bit per-sample offsets when an image's maps span less than 2^31 bytes and the pixel index fits the 24-bit multiplier
   const bool a32 = (long long)lpaf->hs * lpaf->ws < (1ll << 24) && (long long)lpaf->cstride * (long long)sizeof(float) < (1 << 24) &&
                    (long long)lpaf->hs * lpaf->ws * lpaf->cstride * (long long)sizeof(float) < (1ll << 31);
   {
-#define RTPOSE_LIMB_A(L, P, A)                                                                                         \
-  hipLaunchKernelGGL((limb_assign_kernel<L, P, A>), dim3(RTPOSE_NUM_LIMB, N), dim3(256), lds, s, to_view(paf, lpaf), h, \
-                     w, inv_up, up_shift, h1, pcap, res, words, conn, conn_words, score_ws, tie_ws)
-#define RTPOSE_LIMB(L, P)              \
-  do {                                 \
-    if (a32) RTPOSE_LIMB_A(L, P, true); \
-    else RTPOSE_LIMB_A(L, P, false);   \
+#define RTPOSE_LIMB_A(LD, PW, A)                                                                                       \
+  hipLaunchKernelGGL((limb_assign_kernel<LD, PW, A>), dim3(L, N), dim3(256), lds, s, *sk, peaks_word, to_view(paf, lpaf), \
+                     h, w, inv_up, up_shift, h1, pcap, res, words, conn, conn_words, score_ws, tie_ws)
+#define RTPOSE_LIMB(LD, PW)              \
+  do {                                   \
+    if (a32) RTPOSE_LIMB_A(LD, PW, true); \
+    else RTPOSE_LIMB_A(LD, PW, false);   \
   } while (0)
     if (in_lds && up_shift >= 0) RTPOSE_LIMB(true, true);
     else if (in_lds) RTPOSE_LIMB(true, false);
@@ -897,18 +1008,25 @@ int assign_group_launch(const float* paf, const rtpose_layout* lpaf, int N, int 
 #undef RTPOSE_LIMB
   }
   const int row_cap = decode_row_cap(cfg);
-  // subset rows (when they fit) + the staged connections: of all 19 limbs when that fits beside the rows, else of one limb
-  const size_t rows_bytes = row_cap <= kLdsRows ? (size_t)row_cap * 21 * sizeof(float) : 0;
-  const size_t all_bytes = (size_t)RTPOSE_NUM_LIMB * pcap * kStageWords * sizeof(float);
+  // subset rows (when they fit) + the staged connections: of all L limbs when that fits beside the rows, else of one limb
+  const bool rows_in_lds = decode_rows_in_lds(cfg, P);
+  const size_t rows_bytes = rows_in_lds ? decode_rows_bytes(cfg, P) : 0;
+  const size_t all_bytes = (size_t)L * pcap * kStageWords * sizeof(float);
   const bool stage_all = rows_bytes + all_bytes <= 96 * 1024;
   const size_t rows_lds = rows_bytes + (stage_all ? all_bytes : (size_t)pcap * kStageWords * sizeof(float));
-#define RTPOSE_GROUP(W, S)                                                                                               \
-  hipLaunchKernelGGL((group_kernel<W, S>), dim3(N), dim3(64), rows_lds, s, pcap, cfg->max_humans, res, words, conn, \
-                     conn_words, row_cap, rows_ws)
-  if (write_ids && stage_all) RTPOSE_GROUP(true, true);
-  else if (write_ids) RTPOSE_GROUP(true, false);
-  else if (stage_all) RTPOSE_GROUP(false, true);
+#define RTPOSE_GROUP_W(W, S, R)                                                                                      \
+  hipLaunchKernelGGL((group_kernel<W, S, R>), dim3(N), dim3(64), rows_lds, s, *sk, peaks_word, pcap, cfg->max_humans, \
+                     res, words, conn, conn_words, row_cap, rows_ws)
+#define RTPOSE_GROUP(S, R)                    \
+  do {                                        \
+    if (write_ids) RTPOSE_GROUP_W(true, S, R); \
+    else RTPOSE_GROUP_W(false, S, R);         \
+  } while (0)
+  if (stage_all && rows_in_lds) RTPOSE_GROUP(true, true);
+  else if (stage_all) RTPOSE_GROUP(true, false);
+  else if (rows_in_lds) RTPOSE_GROUP(false, true);
   else RTPOSE_GROUP(false, false);
+#undef RTPOSE_GROUP_W
 #undef RTPOSE_GROUP
   RTPOSE_HIP_CHECK(hipGetLastError());
   return 0;
@@ -920,14 +1038,15 @@ using namespace rtpose;
 
 extern "C" {
 
+// ---- the COCO-18 entry points: the tables of coco18_skeleton(), header words 5 / 6 left 0 --------------------------------
 size_t rtpose_decode_workspace_bytes(const rtpose_decode_cfg* cfg, int N) {
-  if (check_cfg(cfg) || N <= 0) return 0;
-  return decode_workspace_bytes(cfg, N);
+  if (check_cfg(cfg, RTPOSE_NUM_PART) || N <= 0) return 0;
+  return decode_workspace_bytes(cfg, RTPOSE_NUM_PART, RTPOSE_NUM_LIMB, N);
 }
 
 size_t rtpose_decode_result_bytes(const rtpose_decode_cfg* cfg, int N) {
-  if (check_cfg(cfg) || N <= 0) return 0;
-  return (size_t)N * decode_result_words(cfg) * sizeof(int32_t);
+  if (check_cfg(cfg, RTPOSE_NUM_PART) || N <= 0) return 0;
+  return (size_t)N * decode_result_words(cfg, RTPOSE_NUM_PART) * sizeof(int32_t);
 }
 
 int rtpose_nms_batch_ex(const float* heat, const rtpose_layout* lheat, int N, int h, int w,
@@ -938,7 +1057,9 @@ int rtpose_nms_batch_ex(const float* heat, const rtpose_layout* lheat, int N, in
   int rcd = c_heat.check(heat, dev, "nms", "the heat-map tensor");
   if (!rcd) rcd = c_res.check(result, dev, "nms", "the result block");
   if (rcd) return rcd;
-  return nms_launch(heat, lheat, N, h, w, cfg, result, as_stream(stream), nms_flags, /*with_ids=*/true);
+  if (int rc = check_cfg(cfg, RTPOSE_NUM_PART)) return rc;
+  return nms_launch(heat, lheat, N, h, w, cfg, coco18_skeleton(), 0, 0, result, as_stream(stream), nms_flags,
+                    /*with_ids=*/true);
 }
 
 int rtpose_nms_batch(const float* heat, const rtpose_layout* lheat, int N, int h, int w,
@@ -972,10 +1093,71 @@ int rtpose_decode_batch_ex(const float* heat, const rtpose_layout* lheat, const 
   if (!rcd) rcd = c_ws.check(workspace, dev, "decode", "the workspace");
   if (!rcd) rcd = c_res.check(result, dev, "decode", "the result block");
   if (rcd) return rcd;
-  int rc = nms_launch(heat, lheat, N, h, w, cfg, result, as_stream(stream), nms_flags, /*with_ids=*/false);
+  int rc = check_cfg(cfg, RTPOSE_NUM_PART);
+  if (!rc) rc = nms_launch(heat, lheat, N, h, w, cfg, coco18_skeleton(), 0, 0, result, as_stream(stream), nms_flags,
+                           /*with_ids=*/false);
   if (rc) return rc;
-  return assign_group_launch(paf, lpaf, N, h, w, 1.0 / (double)cfg->upsample, h * cfg->upsample, cfg,
+  return assign_group_launch(paf, lpaf, N, h, w, 1.0 / (double)cfg->upsample, h * cfg->upsample, cfg, coco18_skeleton(),
                              workspace, workspace_bytes, result, as_stream(stream), /*write_ids=*/true);
+}
+
+// ---- the `_skel` entry points: the caller's tables, header words 5 / 6 = P / L ------------------------------------------
+int rtpose_skeleton_coco18(rtpose_skeleton* skel) { return fill_skeleton(skel, 18, 19, kCoco18Limbs, 0x3FFFFu); }
+
+int rtpose_skeleton_body25(rtpose_skeleton* skel) { return fill_skeleton(skel, 25, 26, kBody25Limbs, 0x3FFFFFFu); }
+
+int rtpose_skeleton_check(const rtpose_skeleton* skel, int heat_channels, int paf_channels) {
+  return check_skeleton(skel, true, heat_channels, paf_channels);
+}
+
+size_t rtpose_decode_workspace_bytes_skel(const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel, int N) {
+  if (check_skeleton(skel, false, 0, 0) || check_cfg(cfg, skel->num_parts) || N <= 0) return 0;
+  return decode_workspace_bytes(cfg, skel->num_parts, skel->num_limbs, N);
+}
+
+size_t rtpose_decode_result_bytes_skel(const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel, int N) {
+  if (check_skeleton(skel, false, 0, 0) || check_cfg(cfg, skel->num_parts) || N <= 0) return 0;
+  return (size_t)N * decode_result_words(cfg, skel->num_parts) * sizeof(int32_t);
+}
+
+int rtpose_nms_batch_skel(const float* heat, const rtpose_layout* lheat, int N, int h, int w, const rtpose_decode_cfg* cfg,
+                          const rtpose_skeleton* skel, int nms_flags, void* result, void* stream) {
+  if (!heat || !lheat || !result) return fail(RTPOSE_E_INVAL, "nms: NULL argument");
+  int rc = check_skeleton(skel, false, 0, 0);
+  if (!rc) rc = check_cfg(cfg, skel->num_parts);
+  if (!rc && lheat->cstride - lheat->choff < cfg->num_keypoints)
+    rc = fail(RTPOSE_E_INVAL, "nms: num_keypoints %d but the heat-map view has %d channels", cfg->num_keypoints,
+              lheat->cstride - lheat->choff);
+  if (rc) return rc;
+  static thread_local CheckedPtr c_heat, c_res;
+  const int dev = current_device();
+  int rcd = c_heat.check(heat, dev, "nms", "the heat-map tensor");
+  if (!rcd) rcd = c_res.check(result, dev, "nms", "the result block");
+  if (rcd) return rcd;
+  return nms_launch(heat, lheat, N, h, w, cfg, skel, skel->num_parts, skel->num_limbs, result, as_stream(stream), nms_flags,
+                    /*with_ids=*/true);
+}
+
+int rtpose_decode_batch_skel(const float* heat, const rtpose_layout* lheat, const float* paf, const rtpose_layout* lpaf,
+                             int N, int h, int w, const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel, int nms_flags,
+                             void* workspace, size_t workspace_bytes, void* result, void* stream) {
+  if (!heat || !lheat || !paf || !lpaf || !workspace || !result) return fail(RTPOSE_E_INVAL, "decode: NULL argument");
+  // the channels a view can address: the kernels index the maps with the skeleton's numbers
+  int rc = check_skeleton(skel, true, lheat->cstride - lheat->choff, lpaf->cstride - lpaf->choff);
+  if (!rc) rc = check_cfg(cfg, skel->num_parts);
+  if (rc) return rc;
+  static thread_local CheckedPtr c_heat, c_paf, c_ws, c_res;
+  const int dev = current_device();
+  int rcd = c_heat.check(heat, dev, "decode", "the heat-map tensor");
+  if (!rcd) rcd = c_paf.check(paf, dev, "decode", "the PAF tensor");
+  if (!rcd) rcd = c_ws.check(workspace, dev, "decode", "the workspace");
+  if (!rcd) rcd = c_res.check(result, dev, "decode", "the result block");
+  if (rcd) return rcd;
+  rc = nms_launch(heat, lheat, N, h, w, cfg, skel, skel->num_parts, skel->num_limbs, result, as_stream(stream), nms_flags,
+                  /*with_ids=*/false);
+  if (rc) return rc;
+  return assign_group_launch(paf, lpaf, N, h, w, 1.0 / (double)cfg->upsample, h * cfg->upsample, cfg, skel, workspace,
+                             workspace_bytes, result, as_stream(stream), /*write_ids=*/true);
 }
 
 }  // extern "C"

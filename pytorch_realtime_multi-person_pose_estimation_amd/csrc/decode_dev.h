@@ -1,6 +1,6 @@
-// Device and host helpers shared by the decoder's two translation units: decode.hip (the COCO-18 kernels behind
-// rtpose_decode_batch[_ex] and the legacy process_paf) and decode_skel.hip (the same kernels with the skeleton as an
-// argument).  Nothing here declares LDS or a kernel: the helpers are inlined into the kernels that call them.
+// Device and host helpers of the decoder's kernels (decode.hip): map addressing, the peak sweep, the cubic and Gaussian
+// weights, the std::sort replay.  Nothing here declares LDS or a kernel: the helpers are inlined into the kernels that
+// call them.
 #pragma once
 #include <hip/hip_runtime.h>
 

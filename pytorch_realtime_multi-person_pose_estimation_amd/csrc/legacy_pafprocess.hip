@@ -2,7 +2,7 @@
 // argument meaning (lib/pafprocess/pafprocess.h:53-59, pafprocess.i:14-15),
 // with the arithmetic on the GPU: process_paf uploads the peak list and the
 // (already up-sampled, HWC) PAF it is handed, runs the same limb_assign /
-// group kernels the batched path uses (inv_up = 1: the map is indexed at full
+// group kernels the batched path uses, with the COCO-18 tables (inv_up = 1: the map is indexed at full
 // resolution exactly as PAF(y,x,c) at pafprocess.cpp:8) and keeps the result
 // in process-global state for the getters (pafprocess.cpp:12-13), behind a
 // mutex.  There is no CPU fallback: without a device process_paf returns
@@ -109,7 +109,7 @@ int process_paf(int p1, int p2, int p3, float* peaks, int h1, int h2, int h3, fl
   cfg.max_peaks_per_part = pcap;
   cfg.max_humans = 64;
   for (;;) {
-    const int words = decode_result_words(&cfg);
+    const int words = decode_result_words(&cfg, RTPOSE_NUM_PART);
     std::vector<int32_t> host((size_t)words, 0);
     int total = 0;
     for (int p = 0; p < RTPOSE_NUM_PART; ++p) {
@@ -124,7 +124,7 @@ int process_paf(int p1, int p2, int p3, float* peaks, int h1, int h2, int h3, fl
     int rc;
     if ((rc = grow(&S.d_paf, &S.paf_bytes, paf_bytes))) return rc;
     if ((rc = grow(&S.d_res, &S.res_bytes, (size_t)words * 4))) return rc;
-    if ((rc = grow(&S.d_ws, &S.ws_bytes, decode_workspace_bytes(&cfg, 1)))) return rc;
+    if ((rc = grow(&S.d_ws, &S.ws_bytes, decode_workspace_bytes(&cfg, RTPOSE_NUM_PART, RTPOSE_NUM_LIMB, 1)))) return rc;
     RTPOSE_HIP_CHECK(hipMemcpy(S.d_paf, pafmap, paf_bytes, hipMemcpyHostToDevice));
     RTPOSE_HIP_CHECK(hipMemcpy(S.d_res, host.data(), (size_t)words * 4, hipMemcpyHostToDevice));
     rtpose_layout lp;
@@ -133,7 +133,7 @@ int process_paf(int p1, int p2, int p3, float* peaks, int h1, int h2, int h3, fl
     lp.ws = f2;
     lp.hs = f1;
     lp.lead = 0;
-    rc = assign_group_launch(static_cast<const float*>(S.d_paf), &lp, 1, f1, f2, 1.0, h1, &cfg, S.d_ws,
+    rc = assign_group_launch(static_cast<const float*>(S.d_paf), &lp, 1, f1, f2, 1.0, h1, &cfg, coco18_skeleton(), S.d_ws,
                              S.ws_bytes, S.d_res, nullptr, /*write_ids=*/false);
     if (rc) return rc;
     RTPOSE_HIP_CHECK(hipMemcpy(host.data(), S.d_res, (size_t)words * 4, hipMemcpyDeviceToHost));

@@ -1,7 +1,7 @@
 // Flip merge and fused multi-scale TTA for any skeleton: the kernels of layout_ops.hip
 // (flip_merge_kernel, tta_accumulate_kernel) with the left / right permutation as data.  The
 // rtpose_flip_table travels by value as a launch argument, like rtpose_skeleton in
-// decode_skel.hip: nothing is uploaded, two streams may merge different skeletons at once.
+// decode.hip: nothing is uploaded, two streams may merge different skeletons at once.
 // Same expressions, in the same order, as the COCO-18 kernels: with the COCO-18 table the
 // results are theirs bit for bit.
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-"""Skeletons for the table-driven decoder (csrc/decode_skel.hip, header section 4a).
+"""Skeletons for the table-driven decoder (csrc/decode.hip, header section 4a).
 
 A ``Skeleton`` is the data the `_skel` decode entry points take: the parts, the limbs as
 (part A, part B, PAF x channel, PAF y channel) in the order the grouping walks them, and which

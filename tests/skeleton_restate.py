@@ -1,4 +1,4 @@
-"""Host restatement of the table-driven decoder (csrc/decode_skel.hip): PAF scoring, greedy assignment and grouping in
+"""Host restatement of the table-driven decoder (csrc/decode.hip): PAF scoring, greedy assignment and grouping in
 plain numpy / np.float32 with the skeleton's tables as arguments - what oracle/post_oracle.c states for COCO-18, generalised
 to P parts and a limb list - plus the scene sets the skeleton tests share (rendered by the package's
 synth.render_skeleton: Gaussians and limb fields the way synth.render draws them, + U(0, noise) noise).

@@ -1,8 +1,10 @@
-"""The table-driven decoder (csrc/decode_skel.hip) on the MI355X.  Everything a record holds is integers and float bit
+"""The table-driven decoder (csrc/decode.hip) on the MI355X.  Everything a record holds is integers and float bit
 patterns: every comparison here is bit for bit, inside decode.result_mask (the words a record defines).
 
-  * the COCO-18 preset through rtpose_decode_batch_skel against rtpose_decode_batch_ex, word for word (this inherits the
-    compiled-reference parity of the old entry point, std::sort replay on ties included);
+  * the COCO-18 preset through rtpose_decode_batch_skel against rtpose_decode_batch_ex, word for word, and both against
+    tests/golden/decode_coco18_records.npz: what the fixed COCO-18 kernels wrote before the two doors came to share one
+    kernel set (tools/make_golden_decode_records.py) - also at the capacities on both sides of every launcher switch and
+    for rtpose_nms_batch_ex;
   * BODY_25, a 2-part / 1-limb table, a 32-part / 32-limb table with scattered PAF channels and COCO-18 walked backwards
     under seed mask 0x15555 against the host restatement (tests/skeleton_restate.py), at capacities on both sides of every
     switch of the launcher, into sentinel-filled buffers of exactly the queried sizes with a guard region behind them;
@@ -13,6 +15,7 @@ tests/test_skeleton_cpu.py checks on the CPU that the scene sets used here hold 
 overflows (and says which of the issue's conditions two of the tables cannot meet, and why).
 """
 import ctypes as C
+import hashlib
 import importlib
 import os
 import sys
@@ -74,7 +77,13 @@ def _run(capi, cuda, heat, paf, cfg, skel=None, flags=0, nms_only=False):
     return res[:rb // 4].cpu().numpy().reshape(n, -1)
 
 
-# ---- 5. the same records through both doors ---------------------------------------------------------------------------
+# ---- 5. the same records through both doors, and the records of the fixed COCO-18 kernels they replaced ----------------
+GOLD_RECORDS = os.path.join(os.path.dirname(__file__), "golden", "decode_coco18_records.npz")
+DOOR_FLAGS = [0, 1, 2]                                  # refine, RTPOSE_NMS_NO_REFINE, RTPOSE_NMS_GAUSSIAN
+DOOR_CAPS = [(32, 64), (111, 64)]                       # (max_peaks_per_part, max_humans), at every flag
+SWITCH_CAPS = [(4, 4), (65, 64), (128, 64), (32, 400)]  # both sides of every launcher switch, at flags 0 (CAPS below)
+
+
 def _door_scenes(synth):
     z = np.load(GOLD)
     scenes = [("golden%d" % i, z["heat%d" % i][None], z["paf%d" % i][None]) for i in range(int(z["n"]))]
@@ -88,9 +97,42 @@ def _door_scenes(synth):
     return scenes
 
 
-@pytest.mark.parametrize("pcap", [32, 111])
-@pytest.mark.parametrize("flags", [0, 1, 2], ids=["refine", "no_refine", "gaussian"])
-def test_coco18_preset_writes_the_records_of_the_old_entry_point(capi, dec, skm, pkg, cuda, flags, pcap):
+def _gold_key(kind, flags, pcap, hcap, scene):
+    """Name of one (case, scene batch) entry of decode_coco18_records.npz; kind 'decode' or 'nms'."""
+    return "%s_f%d_p%d_h%d_%s" % (kind, flags, pcap, hcap, scene)
+
+
+def _maps_digest(heat, paf):
+    return hashlib.sha256(np.ascontiguousarray(heat).tobytes() + np.ascontiguousarray(paf).tobytes()).hexdigest()
+
+
+def _record_digest(block, mask):
+    """SHA-256 of the int32 words of a record block inside `mask`, in record order."""
+    return hashlib.sha256(np.ascontiguousarray(block[mask], dtype="<i4").tobytes()).hexdigest()
+
+
+@pytest.fixture(scope="module")
+def gold_records():
+    return np.load(GOLD_RECORDS)
+
+
+def _assert_parent_records(dec, gold, key, name, heat, paf, got, header_words):
+    """`got` against what the fixed COCO-18 kernels wrote for this case (tools/make_golden_decode_records.py): the header
+    words, the digest of the words inside the parent's result mask, and - to name the word on a failure - the records."""
+    assert str(gold["maps_" + name]) == _maps_digest(heat, paf), "%s: not the maps the fixture was recorded on" % name
+    want = gold[key + "_records"]
+    assert got.shape == want.shape, key
+    assert np.array_equal(got[:, header_words], gold[key + "_header"][:, header_words]), key
+    m = dec.result_mask(want)
+    diff = np.argwhere(got[m] != want[m])
+    assert diff.size == 0, "%s: %d words differ from the parent's record, the first at masked index %d" % (
+        key, len(diff), int(diff[0, 0]))
+    assert _record_digest(got, m) == str(gold[key + "_sha256"]), key
+
+
+@pytest.mark.parametrize("pcap", [c[0] for c in DOOR_CAPS])
+@pytest.mark.parametrize("flags", DOOR_FLAGS, ids=["refine", "no_refine", "gaussian"])
+def test_coco18_preset_writes_the_records_of_the_old_entry_point(capi, dec, skm, pkg, cuda, gold_records, flags, pcap):
     synth = importlib.import_module(pkg.__name__ + ".synth")
     coco = skm.COCO18.native()
     humans = 0
@@ -104,8 +146,32 @@ def test_coco18_preset_writes_the_records_of_the_old_entry_point(capi, dec, skm,
         assert np.array_equal(m, dec.result_mask(new)), name
         assert np.array_equal(new[m], old[m]), "%s: the two entry points' records differ" % name
         assert (old[:, 5:7] == 0).all() and (new[:, 5] == 18).all() and (new[:, 6] == 19).all(), name
+        # both doors run one kernel set now: what pins it is the record of the fixed kernels
+        key = _gold_key("decode", flags, pcap, 64, name)
+        _assert_parent_records(dec, gold_records, key, name, heat, paf, old, slice(0, 8))
+        _assert_parent_records(dec, gold_records, key, name, heat, paf, new, [0, 1, 2, 3, 4, 7])
         humans += int(old[:, 1].sum())
     assert humans > 12
+
+
+@pytest.mark.parametrize("caps", SWITCH_CAPS, ids=["%dx%d" % c for c in SWITCH_CAPS])
+def test_old_entry_point_at_the_launcher_switches_writes_the_parent_records(capi, dec, pkg, cuda, gold_records, caps):
+    synth = importlib.import_module(pkg.__name__ + ".synth")
+    for name, heat, paf in _door_scenes(synth):
+        cfg = capi.DecodeCfg(18, 8, 0.1, caps[0], caps[1])
+        got = _run(capi, cuda, torch.from_numpy(heat).to(cuda), torch.from_numpy(paf).to(cuda), cfg, None, 0)
+        _assert_parent_records(dec, gold_records, _gold_key("decode", 0, caps[0], caps[1], name), name, heat, paf, got,
+                               slice(0, 8))
+
+
+@pytest.mark.parametrize("flags", DOOR_FLAGS, ids=["refine", "no_refine", "gaussian"])
+def test_old_nms_entry_point_writes_the_parent_records(capi, dec, pkg, cuda, gold_records, flags):
+    synth = importlib.import_module(pkg.__name__ + ".synth")
+    for name, heat, paf in _door_scenes(synth):
+        cfg = capi.DecodeCfg(18, 8, 0.1, 32, 64)
+        got = _run(capi, cuda, torch.from_numpy(heat).to(cuda), torch.from_numpy(paf).to(cuda), cfg, None, flags,
+                   nms_only=True)
+        _assert_parent_records(dec, gold_records, _gold_key("nms", flags, 32, 64, name), name, heat, paf, got, slice(0, 8))
 
 
 # ---- 6. other skeletons against the restatement -----------------------------------------------------------------------

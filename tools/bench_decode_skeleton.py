@@ -10,6 +10,10 @@ after `warmup` untimed ones, host clock:
   b  rtpose_decode_batch_skel, COCO-18 preset    the same scenes
   c  rtpose_decode_batch_skel, BODY_25           BODY_25 scenes (synth.render_skeleton; 26 / 52 channels)
 
+a and b time the SAME kernels through two doors (since the fixed COCO-18 copy was dropped, profiles/r12_one_decoder.txt):
+a passes the library's built-in COCO-18 table and leaves header words 5 / 6 zero, b passes the caller's.  A difference
+between them is run-to-run noise plus b's skeleton check on the host.
+
 --forward: ms per OpenPose_Model(4, 2, 52, 26) forward of the same batch (32 x 3 x 368 x 368): the shortest forward a
 BODY_25 decode has to hide under in the pipelined flow.  --bench: runs `python bench.py` (defaults) as a child process and
 repeats its JSON line.  Variant a alone also runs on a tree that has no table-driven decoder (--variants a), which is how
