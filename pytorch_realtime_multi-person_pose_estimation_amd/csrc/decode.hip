@@ -616,7 +616,8 @@ __global__ __launch_bounds__(256) void limb_assign_kernel(rtpose_skeleton sk, in
 // process_paf, whose peak tables carry the ids of the caller's joint list.
 // STAGE_ALL: the connections of ALL L limbs are staged in one sweep over the flattened (limb, connection) list - every
 // global round trip of the kernel is then taken once, with all lanes' loads in flight together, instead of once per limb (the
-// host picks it when L * pcap staged connections fit the LDS next to the rows: pcap <= 128 for COCO-18).
+// host picks it when the L * pcap staged connections and the LDS-resident rows fit 96 KiB together: for COCO-18 up to pcap 230
+// with 128 rows in LDS, up to 258 with the rows in the workspace).
 // ROWS_IN_LDS: the rows are addressed with LDS instructions or global ones, decided by the host on their byte count
 // (decode_rows_in_lds) - a template parameter for the reason SCORES_IN_LDS is one.
 template <bool WRITE_IDS, bool STAGE_ALL, bool ROWS_IN_LDS>

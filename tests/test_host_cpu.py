@@ -119,6 +119,21 @@ def test_no_silent_cpu_fallback(pkg, dec, capi):
         pafprocess.process_paf(np.array([[[1, 1, .5, 0, 0]]], np.float32), np.zeros((8, 8, 19)), np.zeros((8, 8, 38)))
 
 
+def test_process_paf_refuses_more_peaks_of_a_part_than_the_device_table_holds(pkg, capi):
+    """1025 peaks of one part: RTPOSE_E_CAPACITY, decided on the host before any device call (so it is the same refusal
+    with and without a GPU), and the getters report an empty result afterwards."""
+    pafprocess = importlib.import_module(PKG_NAME + ".pafprocess")
+    jl = np.zeros((1, 1025, 5), np.float32)
+    jl[0, :, 0] = np.arange(1025) % 32
+    jl[0, :, 1] = np.arange(1025) // 32
+    jl[0, :, 2] = 0.5
+    jl[0, :, 3] = np.arange(1025)
+    jl[0, :, 4] = 7
+    with pytest.raises(capi.RtposeError, match="RTPOSE_E_CAPACITY"):
+        pafprocess.process_paf(jl, np.zeros((40, 40, 19), np.float32), np.zeros((40, 40, 38), np.float32))
+    assert pafprocess.get_num_humans() == 0 and pafprocess.get_part_cid(0, 7) == -1
+
+
 def test_shard_range_partitions(pkg):
     par = importlib.import_module(PKG_NAME + ".parallel")
     for n in (0, 1, 7, 32, 5000):

@@ -26,12 +26,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import skeleton_restate as sr  # noqa: E402
+from decode_run import GUARD, SENTINEL, run_decode as _run  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "post_scenes.npz")
-SENTINEL = 0x5A5A5A5A
-GUARD = 4096        # words behind each buffer that must stay untouched
 
 
 @pytest.fixture(scope="module")
@@ -42,39 +41,6 @@ def dec(pkg):
 @pytest.fixture(scope="module")
 def skm(pkg):
     return importlib.import_module(pkg.__name__ + ".skeleton")
-
-
-def _run(capi, cuda, heat, paf, cfg, skel=None, flags=0, nms_only=False):
-    """One decode of dense NHWC maps (device tensors) into sentinel-filled buffers of exactly the queried sizes + a guard
-    region; skel None = the COCO-18 entry points.  -> int32 [N, words]."""
-    lib = capi.lib
-    n, h, w, ch = heat.shape
-    if skel is None:
-        rb, wb = lib.rtpose_decode_result_bytes(C.byref(cfg), n), lib.rtpose_decode_workspace_bytes(C.byref(cfg), n)
-    else:
-        rb = lib.rtpose_decode_result_bytes_skel(C.byref(cfg), C.byref(skel), n)
-        wb = lib.rtpose_decode_workspace_bytes_skel(C.byref(cfg), C.byref(skel), n)
-    assert rb > 0 and wb > 0 and rb % 4 == 0 and wb % 4 == 0, capi.last_error()
-    res = torch.full((rb // 4 + GUARD,), SENTINEL, dtype=torch.int32, device=cuda)
-    ws = torch.full((wb // 4 + GUARD,), SENTINEL, dtype=torch.int32, device=cuda)
-    lheat, lpaf = capi.Layout.dense(ch, h, w), capi.Layout.dense(paf.shape[3], h, w)
-    s = capi.current_stream()
-    if skel is None and nms_only:
-        rc = lib.rtpose_nms_batch_ex(capi.ptr(heat), C.byref(lheat), n, h, w, C.byref(cfg), flags, capi.ptr(res), s)
-    elif skel is None:
-        rc = lib.rtpose_decode_batch_ex(capi.ptr(heat), C.byref(lheat), capi.ptr(paf), C.byref(lpaf), n, h, w, C.byref(cfg),
-                                        flags, capi.ptr(ws), wb, capi.ptr(res), s)
-    elif nms_only:
-        rc = lib.rtpose_nms_batch_skel(capi.ptr(heat), C.byref(lheat), n, h, w, C.byref(cfg), C.byref(skel), flags,
-                                       capi.ptr(res), s)
-    else:
-        rc = lib.rtpose_decode_batch_skel(capi.ptr(heat), C.byref(lheat), capi.ptr(paf), C.byref(lpaf), n, h, w,
-                                          C.byref(cfg), C.byref(skel), flags, capi.ptr(ws), wb, capi.ptr(res), s)
-    capi.check(rc, "decode")
-    torch.cuda.synchronize()
-    assert bool((res[rb // 4:] == SENTINEL).all()), "the result block's guard region was written"
-    assert bool((ws[wb // 4:] == SENTINEL).all()), "the workspace's guard region was written"
-    return res[:rb // 4].cpu().numpy().reshape(n, -1)
 
 
 # ---- 5. the same records through both doors, and the records of the fixed COCO-18 kernels they replaced ----------------
