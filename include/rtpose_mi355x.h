@@ -854,7 +854,13 @@ int rtpose_resize_bilinear_accum(const float* src, int hs, int ws, float* dst, i
  * (B images if flip == 0).  Forms the handle_paf_and_heat average (coco_eval.py:197-242;
  * mirror inside the first w_valid columns) and accumulates
  *   acc = beta * acc + alpha * bilinear_resize(average)   (dense [B,hd,wd,19] / [B,hd,wd,38])
- * exactly as rtpose_flip_merge followed by rtpose_resize_bilinear_accum would. */
+ * exactly as rtpose_flip_merge followed by rtpose_resize_bilinear_accum would.  This is
+ * rtpose_tta_accumulate_skel (section 5a) over COCO-18's table, with that entry's argument
+ * check: NULL pointers or layouts, w_valid outside 1..ws or hs above the views' hs, a view
+ * that addresses fewer than 19 / 38 channels (cstride - choff) are refused before any
+ * launch.  Unlike it, B == 0 is refused too.  The kernel's grid is (row pieces, hd, B):
+ * B or hd above 65535, or wd above 0x7fffff00 / 57 pixels, are refused (a 65536-row map
+ * is a 524288-pixel-tall image at stride 8). */
 int rtpose_tta_accumulate(const float* heat, const rtpose_layout* lheat, const float* paf,
                           const rtpose_layout* lpaf, int B, int hs, int w_valid, float* acc_heat,
                           float* acc_paf, int hd, int wd, float src_h_valid, float src_w_valid,
@@ -1003,20 +1009,24 @@ int rtpose_decode_batch_skel(const float* heat, const rtpose_layout* lheat, cons
  * 5. Flip test-time-augmentation merge
  *    stands in for evaluate/coco_eval.py:197-242 (handle_paf_and_heat).
  *    All four inputs dense HWC fp32 on the device, outputs likewise.
+ *    This is rtpose_flip_merge_skel (5a) over COCO-18's table: NULL maps are
+ *    refused; a call without pixels (N, h or w == 0) is a no-op.  The kernel's
+ *    grid is (row pieces, h, N): N or h above 65535, or w above
+ *    0x7fffff00 / 57 pixels, are refused.
  * ---------------------------------------------------------------------- */
 int rtpose_flip_merge(const float* heat, const float* heat_flipped,
                       const float* paf, const float* paf_flipped, int N, int h,
                       int w, float* heat_avg, float* paf_avg, void* stream);
 
 /* ---- 5a. The same merge with the left / right permutation as data --------------------
- * rtpose_flip_merge and rtpose_tta_accumulate (section 4) carry COCO-18's permutations
- * in their kernels.  The `_skel` entry points below take them as a flip table: output
- * heat-map channel c averages with channel heat_src[c] of the x-mirrored pass, PAF
- * channel c with channel paf_src[c], negated iff bit c of paf_neg_mask is set.  The
- * arithmetic is that of the entry points above, expression for expression: with the
- * COCO-18 table the results are theirs bit for bit.  The struct travels by value into the
- * kernels as a launch argument (nothing is uploaded; two streams may merge different
- * skeletons at the same time). */
+ * One kernel pair serves every skeleton.  The `_skel` entry points below take the
+ * permutation as a flip table: output heat-map channel c averages with channel
+ * heat_src[c] of the x-mirrored pass, PAF channel c with channel paf_src[c], negated iff
+ * bit c of paf_neg_mask is set.  rtpose_flip_merge and rtpose_tta_accumulate (section 4)
+ * are these entry points over COCO-18's table, which the library derives once from
+ * rtpose_skeleton_coco18 and the part mirror: same kernels, same argument check, same
+ * bits.  The struct travels by value into the kernels as a launch argument (nothing is
+ * uploaded; two streams may merge different skeletons at the same time). */
 #define RTPOSE_FLIP_MAX_HEAT 33 /* 32 parts + background */
 #define RTPOSE_FLIP_MAX_PAF 64
 

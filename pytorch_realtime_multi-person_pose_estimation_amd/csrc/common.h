@@ -126,6 +126,18 @@ __device__ __forceinline__ int fast_div(int m, const FastDiv f) {
 }
 #endif
 
+// A rtpose_layout as a kernel argument: the five fields the addressing formula of the header (section 1) reads.
+struct Lay {
+  int cstride, choff, ws, hs, lead;
+};
+inline Lay to_lay(const rtpose_layout* l) { return Lay{l->cstride, l->choff, l->ws, l->hs, l->lead}; }
+#ifdef __HIPCC__
+// element offset of channel 0 of the view at pixel (y, x) of image n
+__device__ __forceinline__ size_t lay_off(const Lay& l, int n, int y, int x) {
+  return ((size_t)l.lead + (size_t)(n * l.hs + y) * l.ws + x) * l.cstride + l.choff;
+}
+#endif
+
 #ifdef __HIPCC__
 __device__ __forceinline__ float prelu1(float v, float a) { return v >= 0.f ? v : a * v; }
 #endif

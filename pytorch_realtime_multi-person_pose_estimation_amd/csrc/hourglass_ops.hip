@@ -171,13 +171,6 @@ int conv7x7_s2_launch(const float* x_nchw, const float* x_lay, const rtpose_layo
 // ---- out = up + upsample2(low) -------------------------------------------------------------------------------------------
 namespace {
 
-struct Lay {
-  int cstride, choff, ws, hs, lead;
-};
-Lay to_lay(const rtpose_layout* l) { return Lay{l->cstride, l->choff, l->ws, l->hs, l->lead}; }
-__device__ __forceinline__ size_t lay_off(const Lay& l, int n, int y, int x) {
-  return ((size_t)l.lead + (size_t)(n * l.hs + y) * l.ws + x) * l.cstride + l.choff;
-}
 __device__ __forceinline__ float4 add4(const float4 a, const float4 b) {
   return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
 }

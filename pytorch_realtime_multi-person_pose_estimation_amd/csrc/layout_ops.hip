@@ -1,14 +1,15 @@
 // HBM-bound data-movement kernels around the conv path: NCHW <-> shared-gap
 // padded NHWC, slice copies, 2x2 max-pool (nn.MaxPool2d(2,2,0),
-// lib/network/rtpose_vgg.py:49-50) and the flip-TTA merge
-// (evaluate/coco_eval.py:197-242).  All are one coalesced pass, float4 on the
-// NHWC side where the slice is 16-byte aligned.
+// lib/network/rtpose_vgg.py:49-50) and the multi-scale TTA resize (the flip
+// merge and the fused TTA kernel are in tta.hip; their COCO-18 doors are here).  All are one coalesced pass,
+// float4 on the NHWC side where the slice is 16-byte aligned.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <type_traits>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace rtpose {
 
@@ -23,15 +24,6 @@ int fail(int code, const char* fmt, ...) {
   vsnprintf(err_buf(), 512, fmt, ap);
   va_end(ap);
   return code;
-}
-
-struct Lay {
-  int cstride, choff, ws, hs, lead;
-};
-static Lay to_lay(const rtpose_layout* l) { return Lay{l->cstride, l->choff, l->ws, l->hs, l->lead}; }
-
-__device__ __forceinline__ size_t lay_off(const Lay& l, int n, int y, int x) {
-  return ((size_t)l.lead + (size_t)(n * l.hs + y) * l.ws + x) * l.cstride + l.choff;
 }
 
 __device__ __forceinline__ unsigned short f32_to_bf16_rne(float v) {
@@ -129,41 +121,6 @@ __global__ void maxpool2x2_kernel(const float* __restrict__ src, Lay ls, float* 
   r.z = fmaxf(fmaxf(a.z, b.z), fmaxf(d.z, e.z));
   r.w = fmaxf(fmaxf(a.w, b.w), fmaxf(d.w, e.w));
   *reinterpret_cast<float4*>(dst + lay_off(ld, n, y, x) + c) = r;
-}
-
-// handle_paf_and_heat (evaluate/coco_eval.py:197-242): average a map with the
-// x-mirrored, left/right-channel-swapped map of the flipped image; the PAF
-// x components (even channels AFTER the swap gather, :237) change sign.
-__constant__ int kSwapHeat[19] = {0, 1, 5, 6, 7, 2, 3, 4, 11, 12, 13, 8, 9, 10, 15, 14, 17, 16, 18};
-__constant__ int kSwapPaf[38] = {6,  7,  8,  9,  10, 11, 0,  1,  2,  3,  4,  5,  20,
-                                 21, 22, 23, 24, 25, 26, 27, 12, 13, 14, 15, 16, 17,
-                                 18, 19, 28, 29, 32, 33, 30, 31, 36, 37, 34, 35};
-
-__global__ void flip_merge_kernel(const float* __restrict__ heat, const float* __restrict__ heat_f,
-                                  const float* __restrict__ paf, const float* __restrict__ paf_f,
-                                  int N, int h, int w, float* __restrict__ heat_avg,
-                                  float* __restrict__ paf_avg) {
-  const size_t npix = (size_t)N * h * w;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * 57) return;
-  const int c = i % 57;
-  const size_t p = i / 57;
-  const int x = p % w;
-  const size_t row = p / w;  // n*h + y
-  const size_t pf = row * w + (w - 1 - x);
-  if (c < 19) {
-    heat_avg[p * 19 + c] = (heat[p * 19 + c] + heat_f[pf * 19 + kSwapHeat[c]]) / 2.f;
-  } else {
-    const int k = c - 19;
-    // coco_eval.py:237 negates the channels listed in swap_paf[::2] in place
-    // (:236 is a no-op), then :238 gathers with swap_paf: output channel k
-    // reads flipped channel swap_paf[k], negated iff swap_paf[k] is one of the
-    // swap_paf[::2] entries, i.e. iff it is an even channel index.
-    const int sc = kSwapPaf[k];
-    float v = paf_f[pf * 38 + sc];
-    if ((sc & 1) == 0) v = -v;
-    paf_avg[p * 38 + k] = (paf[p * 38 + k] + v) / 2.f;
-  }
 }
 
 // Fused caller-side image prep: crop_with_factor + rtpose/vgg_preprocess
@@ -277,53 +234,6 @@ __global__ void resize_bilinear_accum_kernel(const float* __restrict__ src, int 
   const float bot = s1[(size_t)x0 * C] * (1.f - lx) + s1[(size_t)x1 * C] * lx;
   const float v = top * (1.f - ly) + bot * ly;
   dst[i] = (beta == 0.f ? 0.f : beta * dst[i]) + alpha * v;
-}
-
-// Fused test-time-augmentation merge for one scale (BASELINE config 3): reads the stage-6 maps
-// of B normal passes (images [0,B)) and, if flip, B x-mirrored passes (images [B,2B)) where the
-// net wrote them, forms handle_paf_and_heat's average (evaluate/coco_eval.py:197-242; mirror
-// inside the first wv columns only, left/right channel swap, PAF x sign) at the four
-// bilinear taps and accumulates alpha * resize(...) into the dense scale-1 maps.  Same
-// expressions as flip_merge_kernel followed by resize_bilinear_accum_kernel.
-__global__ void tta_accumulate_kernel(const float* __restrict__ heat, Lay lh, const float* __restrict__ paf,
-                                      Lay lp, int B, int hs, int wv, float* __restrict__ acc_heat,
-                                      float* __restrict__ acc_paf, int hd, int wd, float sy, float sx,
-                                      float alpha, float beta, int flip) {
-  const size_t total = (size_t)B * hd * wd * 57;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int c57 = i % 57;
-  size_t p = i / 57;
-  const int x = p % wd;
-  size_t r = p / wd;
-  const int y = r % hd;
-  const int b = (int)(r / hd);
-  float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
-  fy = fmaxf(fy, 0.f);
-  fx = fmaxf(fx, 0.f);
-  int y0 = (int)fy, x0 = (int)fx;
-  y0 = min(y0, hs - 1);
-  x0 = min(x0, wv - 1);
-  const int y1 = min(y0 + 1, hs - 1), x1 = min(x0 + 1, wv - 1);
-  const float ly = fminf(fy - (float)y0, 1.f), lx = fminf(fx - (float)x0, 1.f);
-  const bool is_heat = c57 < 19;
-  const int c = is_heat ? c57 : c57 - 19;
-  const float* src = is_heat ? heat : paf;
-  const Lay& l = is_heat ? lh : lp;
-  const int sc = is_heat ? kSwapHeat[c] : kSwapPaf[c];
-  const bool neg = !is_heat && (sc & 1) == 0;
-  auto tap = [&](int yy, int xx) -> float {
-    const float a = src[lay_off(l, b, yy, xx) + c];
-    if (!flip) return a;
-    float v = src[lay_off(l, B + b, yy, wv - 1 - xx) + sc];
-    if (neg) v = -v;
-    return (a + v) / 2.f;
-  };
-  const float top = tap(y0, x0) * (1.f - lx) + tap(y0, x1) * lx;
-  const float bot = tap(y1, x0) * (1.f - lx) + tap(y1, x1) * lx;
-  const float v = top * (1.f - ly) + bot * ly;
-  float* d = is_heat ? acc_heat + p * 19 + c : acc_paf + p * 38 + c;
-  *d = (beta == 0.f ? 0.f : beta * *d) + alpha * v;
 }
 
 // dst(n,y,x,c) = alpha * dst(n,y,x,c) + beta * src_dense[n][y][x][c]
@@ -1357,32 +1267,26 @@ int rtpose_resize_bilinear_accum(const float* src, int hs, int ws, float* dst, i
   return 0;
 }
 
-int rtpose_tta_accumulate(const float* heat, const rtpose_layout* lheat, const float* paf,
-                          const rtpose_layout* lpaf, int B, int hs, int w_valid, float* acc_heat, float* acc_paf,
-                          int hd, int wd, float src_h_valid, float src_w_valid, float alpha, float beta, int flip,
-                          void* stream) {
-  if (!heat || !paf || !acc_heat || !acc_paf || B <= 0 || hs <= 0 || w_valid <= 0 || hd <= 0 || wd <= 0 ||
-      src_h_valid <= 0 || src_w_valid <= 0)
-    return fail(RTPOSE_E_INVAL, "tta_accumulate: bad arguments");
-  const size_t total = (size_t)B * hd * wd * 57;
-  hipLaunchKernelGGL(tta_accumulate_kernel, dim3(nblocks(total, 256)), dim3(256), 0, as_stream(stream), heat,
-                     to_lay(lheat), paf, to_lay(lpaf), B, hs, w_valid, acc_heat, acc_paf, hd, wd,
-                     src_h_valid / (float)hd, src_w_valid / (float)wd, alpha, beta, flip ? 1 : 0);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+// COCO-18's flip merge and fused TTA merge: the table-driven kernels and argument check of tta.hip over the table the
+// library derives for itself.  As before, a flip merge without pixels (h or w 0 as well as N 0) is a no-op ...
+int rtpose_flip_merge(const float* heat, const float* heat_flipped, const float* paf, const float* paf_flipped, int N,
+                      int h, int w, float* heat_avg, float* paf_avg, void* stream) {
+  if (N == 0 || h == 0 || w == 0) return 0;
+  const rtpose_flip_table* t = coco18_flip_table();
+  return !t ? RTPOSE_E_INVAL
+            : flip_merge_launch("flip_merge", heat, heat_flipped, paf, paf_flipped, N, h, w, heat_avg, paf_avg, t, stream);
 }
 
-int rtpose_flip_merge(const float* heat, const float* heat_flipped, const float* paf,
-                      const float* paf_flipped, int N, int h, int w, float* heat_avg, float* paf_avg,
-                      void* stream) {
-  const size_t total = (size_t)N * h * w * 57;
-  if (!total) return 0;
-  hipLaunchKernelGGL(flip_merge_kernel, dim3(nblocks(total, 256)), dim3(256), 0, as_stream(stream),
-                     heat, heat_flipped, paf, paf_flipped, N, h, w, heat_avg, paf_avg);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+// ... and unlike rtpose_tta_accumulate_skel, this door refuses the empty batch
+int rtpose_tta_accumulate(const float* heat, const rtpose_layout* lheat, const float* paf, const rtpose_layout* lpaf,
+                          int B, int hs, int w_valid, float* acc_heat, float* acc_paf, int hd, int wd, float src_h_valid,
+                          float src_w_valid, float alpha, float beta, int flip, void* stream) {
+  if (B == 0) return fail(RTPOSE_E_INVAL, "tta_accumulate: B is 0");
+  const rtpose_flip_table* t = coco18_flip_table();
+  return !t ? RTPOSE_E_INVAL
+            : tta_accumulate_launch("tta_accumulate", heat, lheat, paf, lpaf, B, hs, w_valid, acc_heat, acc_paf, hd, wd,
+                                    src_h_valid, src_w_valid, alpha, beta, flip, t, stream);
 }
-
 
 int rtpose_nchw_to_layout_bf16(const float* src_nchw, void* dst, const rtpose_layout* ldst, int C, int cpad,
                                int N, int H, int W, void* stream) {

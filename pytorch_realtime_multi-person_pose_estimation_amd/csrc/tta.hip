@@ -1,33 +1,27 @@
-// Flip merge and fused multi-scale TTA for any skeleton: the kernels of layout_ops.hip
-// (flip_merge_kernel, tta_accumulate_kernel) with the left / right permutation as data.  The
-// rtpose_flip_table travels by value as a launch argument, like rtpose_skeleton in
-// decode.hip: nothing is uploaded, two streams may merge different skeletons at once.
-// Same expressions, in the same order, as the COCO-18 kernels: with the COCO-18 table the
-// results are theirs bit for bit.
+// Flip merge (handle_paf_and_heat, evaluate/coco_eval.py:197-242) and the fused multi-scale TTA kernel, with the
+// left / right permutation as data: one kernel pair for every skeleton.  The rtpose_flip_table travels by value as a
+// launch argument, like rtpose_skeleton in decode.hip: nothing is uploaded, two streams may merge different skeletons
+// at once.  The entry points without a table argument (rtpose_flip_merge, rtpose_tta_accumulate in layout_ops.hip) call
+// the launchers below with coco18_flip_table(): derived once on the host from coco18_skeleton() and the part mirror.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "common.h"
+#include "decode.h"
+#include "launchers.h"
 
 namespace rtpose {
 namespace {
 
-struct View {
-  int cstride, choff, ws, hs, lead;
-};
-View to_view(const rtpose_layout* l) { return View{l->cstride, l->choff, l->ws, l->hs, l->lead}; }
-
-__device__ __forceinline__ size_t view_off(const View& l, int n, int y, int x) {
-  return ((size_t)l.lead + (size_t)(n * l.hs + y) * l.ws + x) * l.cstride + l.choff;
-}
-
 constexpr int kThreads = 256;
 
+// handle_paf_and_heat (evaluate/coco_eval.py:197-242): average a map with the x-mirrored, left/right-channel-swapped map
+// of the flipped image; the PAF x components change sign.
 // grid (pieces of one output row, rows, images): a thread owns one (x, channel) of the row, channels fastest over the
 // heat map's and then the PAF's, so a wave's stores are two contiguous runs per pixel.  The only division left is
 // x = t / (heat + PAF channels), by a launch-time constant (FastDiv: one mul-hi and a shift).
-__global__ __launch_bounds__(kThreads) void flip_merge_skel_kernel(
+__global__ __launch_bounds__(kThreads) void flip_merge_kernel(
     const float* __restrict__ heat, const float* __restrict__ heat_f, const float* __restrict__ paf,
     const float* __restrict__ paf_f, int h, int w, float* __restrict__ heat_avg, float* __restrict__ paf_avg,
     const rtpose_flip_table tab, const FastDiv dc) {
@@ -43,14 +37,24 @@ __global__ __launch_bounds__(kThreads) void flip_merge_skel_kernel(
     heat_avg[p * CH + c] = (heat[p * CH + c] + heat_f[pf * CH + tab.heat_src[c]]) / 2.f;
   } else {
     const int k = c - CH;
+    // coco_eval.py:237 negates the channels listed in swap_paf[::2] in place (:236 is a no-op), then :238 gathers with
+    // swap_paf: output channel k reads flipped channel swap_paf[k], negated iff swap_paf[k] is one of the swap_paf[::2]
+    // entries, i.e. iff it is an even channel index.  The sign therefore belongs to the OUTPUT channel and is applied
+    // after the gather: bit k of paf_neg_mask (for COCO-18 exactly the k with swap_paf[k] even).
     float v = paf_f[pf * CP + tab.paf_src[k]];
     if ((tab.paf_neg_mask >> k) & 1) v = -v;
     paf_avg[p * CP + k] = (paf[p * CP + k] + v) / 2.f;
   }
 }
 
-__global__ __launch_bounds__(kThreads) void tta_accumulate_skel_kernel(
-    const float* __restrict__ heat, View lh, const float* __restrict__ paf, View lp, int B, int hs, int wv,
+// Fused test-time-augmentation merge for one scale (BASELINE config 3): reads the stage-6 maps of B normal passes (images
+// [0,B)) and, if flip, B x-mirrored passes (images [B,2B)) where the net wrote them, forms handle_paf_and_heat's average
+// (evaluate/coco_eval.py:197-242; mirror inside the first wv columns only, left/right channel swap, PAF x sign) at the
+// four bilinear taps and accumulates alpha * resize(...) into the dense scale-1 maps.  Same expressions as
+// flip_merge_kernel followed by layout_ops.hip's resize_bilinear_accum_kernel; the grid is flip_merge_kernel's over the
+// destination.
+__global__ __launch_bounds__(kThreads) void tta_accumulate_kernel(
+    const float* __restrict__ heat, Lay lh, const float* __restrict__ paf, Lay lp, int B, int hs, int wv,
     float* __restrict__ acc_heat, float* __restrict__ acc_paf, int hd, int wd, float sy, float sx, float alpha,
     float beta, int flip, const rtpose_flip_table tab, const FastDiv dc) {
   const int CH = tab.heat_channels, CP = tab.paf_channels;
@@ -71,13 +75,13 @@ __global__ __launch_bounds__(kThreads) void tta_accumulate_skel_kernel(
   const bool is_heat = cc < CH;
   const int c = is_heat ? cc : cc - CH;
   const float* src = is_heat ? heat : paf;
-  const View& l = is_heat ? lh : lp;
+  const Lay& l = is_heat ? lh : lp;
   const int sc = is_heat ? tab.heat_src[c] : tab.paf_src[c];
   const bool neg = !is_heat && ((tab.paf_neg_mask >> c) & 1);
   auto tap = [&](int yy, int xx) -> float {
-    const float a = src[view_off(l, b, yy, xx) + c];
+    const float a = src[lay_off(l, b, yy, xx) + c];
     if (!flip) return a;
-    float v = src[view_off(l, B + b, yy, wv - 1 - xx) + sc];
+    float v = src[lay_off(l, B + b, yy, wv - 1 - xx) + sc];
     if (neg) v = -v;
     return (a + v) / 2.f;
   };
@@ -131,6 +135,75 @@ int assign(rtpose_flip_table* t, bool* set, int limb, int c, int s, bool neg) {
 }
 
 }  // namespace
+
+// COCO-18's table for the entry points without a table argument: derived once from the decoder's coco18_skeleton() and the
+// part mirror (lib/utils/common.py:5-24: R / L shoulder, elbow, wrist, hip, knee, ankle, eye, ear change places), which
+// gives coco_eval.py's swap_heat / swap_paf lists and their signs.  A derivation that failed (it cannot, short of an edit
+// to one of the two tables: tests/test_skeleton_flip_cpu.py derives the same table) returns NULL with the error text
+// set, and those entry points fail with it.
+const rtpose_flip_table* coco18_flip_table() {
+  static const rtpose_flip_table coco = [] {
+    static const int32_t mirror18[RTPOSE_NUM_PART] = {0, 1, 5, 6, 7, 2, 3, 4, 11, 12, 13, 8, 9, 10, 15, 14, 17, 16};
+    rtpose_flip_table t;
+    if (rtpose_flip_table_from_skeleton(coco18_skeleton(), mirror18, 1, 38, &t)) memset(&t, 0, sizeof(t));
+    return t;
+  }();
+  if (coco.struct_bytes) return &coco;
+  fail(RTPOSE_E_INVAL, "the library's own COCO-18 flip table could not be derived from its skeleton and part mirror");
+  return nullptr;
+}
+
+// The one argument check and launch of each kernel; `who` is the entry point's name in the messages.  The 3-D grid bounds
+// N / B and the rows at 65535 and a row at 0x7fffff00 threads.
+int flip_merge_launch(const char* who, const float* heat, const float* heat_flipped, const float* paf,
+                      const float* paf_flipped, int N, int h, int w, float* heat_avg, float* paf_avg,
+                      const rtpose_flip_table* table, void* stream) {
+  if (!heat || !heat_flipped || !paf || !paf_flipped || !heat_avg || !paf_avg)
+    return fail(RTPOSE_E_INVAL, "%s: NULL map", who);
+  const int rc = check_table(table);
+  if (rc) return rc;
+  if (N == 0) return 0;
+  if (N < 0 || N > 65535 || h <= 0 || h > 65535 || w <= 0)
+    return fail(RTPOSE_E_INVAL, "%s: bad sizes (N %d, h %d, w %d; N and h at most 65535)", who, N, h, w);
+  const int ctot = table->heat_channels + table->paf_channels;
+  if ((long long)w * ctot > 0x7fffff00ll)
+    return fail(RTPOSE_E_INVAL, "%s: row of %d pixels too long (at most %d)", who, w, 0x7fffff00 / ctot);
+  hipLaunchKernelGGL(flip_merge_kernel, dim3(ceil_div(w * ctot, kThreads), h, N), dim3(kThreads), 0, as_stream(stream),
+                     heat, heat_flipped, paf, paf_flipped, h, w, heat_avg, paf_avg, *table, make_fastdiv(ctot));
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int tta_accumulate_launch(const char* who, const float* heat, const rtpose_layout* lheat, const float* paf,
+                          const rtpose_layout* lpaf, int B, int hs, int w_valid, float* acc_heat, float* acc_paf, int hd,
+                          int wd, float src_h_valid, float src_w_valid, float alpha, float beta, int flip,
+                          const rtpose_flip_table* table, void* stream) {
+  if (!heat || !lheat || !paf || !lpaf || !acc_heat || !acc_paf) return fail(RTPOSE_E_INVAL, "%s: NULL argument", who);
+  const int rc = check_table(table);
+  if (rc) return rc;
+  if (table->heat_channels > lheat->cstride - lheat->choff)
+    return fail(RTPOSE_E_INVAL, "%s: the table has %d heat-map channels, the view addresses %d", who, table->heat_channels,
+                lheat->cstride - lheat->choff);
+  if (table->paf_channels > lpaf->cstride - lpaf->choff)
+    return fail(RTPOSE_E_INVAL, "%s: the table has %d PAF channels, the view addresses %d", who, table->paf_channels,
+                lpaf->cstride - lpaf->choff);
+  if (B == 0) return 0;
+  if (B < 0 || B > 65535 || hs <= 0 || hs > lheat->hs || hs > lpaf->hs || hd <= 0 || hd > 65535 || wd <= 0 ||
+      !(src_h_valid > 0) || !(src_w_valid > 0))
+    return fail(RTPOSE_E_INVAL, "%s: bad sizes (B %d, hs %d, hd %d, wd %d; B and hd at most 65535)", who, B, hs, hd, wd);
+  if (w_valid < 1 || w_valid > lheat->ws || w_valid > lpaf->ws)
+    return fail(RTPOSE_E_INVAL, "%s: w_valid %d outside [1,%d]", who, w_valid, lheat->ws < lpaf->ws ? lheat->ws : lpaf->ws);
+  const int ctot = table->heat_channels + table->paf_channels;
+  if ((long long)wd * ctot > 0x7fffff00ll)
+    return fail(RTPOSE_E_INVAL, "%s: row of %d pixels too long (at most %d)", who, wd, 0x7fffff00 / ctot);
+  hipLaunchKernelGGL(tta_accumulate_kernel, dim3(ceil_div(wd * ctot, kThreads), hd, B), dim3(kThreads), 0,
+                     as_stream(stream), heat, to_lay(lheat), paf, to_lay(lpaf), B, hs, w_valid, acc_heat, acc_paf, hd, wd,
+                     src_h_valid / (float)hd, src_w_valid / (float)wd, alpha, beta, flip ? 1 : 0, *table,
+                     make_fastdiv(ctot));
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace rtpose
 
 using namespace rtpose;
@@ -192,53 +265,16 @@ int rtpose_flip_table_from_skeleton(const rtpose_skeleton* skel, const int32_t* 
 int rtpose_flip_merge_skel(const float* heat, const float* heat_flipped, const float* paf, const float* paf_flipped,
                            int N, int h, int w, float* heat_avg, float* paf_avg, const rtpose_flip_table* table,
                            void* stream) {
-  if (!heat || !heat_flipped || !paf || !paf_flipped || !heat_avg || !paf_avg)
-    return fail(RTPOSE_E_INVAL, "flip_merge_skel: NULL map");
-  const int rc = check_table(table);
-  if (rc) return rc;
-  if (N == 0) return 0;
-  if (N < 0 || N > 65535 || h <= 0 || h > 65535 || w <= 0)
-    return fail(RTPOSE_E_INVAL, "flip_merge_skel: bad sizes (N %d, h %d, w %d; N and h at most 65535)", N, h, w);
-  const int ctot = table->heat_channels + table->paf_channels;
-  if ((long long)w * ctot > 0x7fffff00ll) return fail(RTPOSE_E_INVAL, "flip_merge_skel: row of %d pixels too long", w);
-  hipLaunchKernelGGL(flip_merge_skel_kernel, dim3(ceil_div(w * ctot, kThreads), h, N), dim3(kThreads), 0,
-                     as_stream(stream), heat, heat_flipped, paf, paf_flipped, h, w, heat_avg, paf_avg, *table,
-                     make_fastdiv(ctot));
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return flip_merge_launch("flip_merge_skel", heat, heat_flipped, paf, paf_flipped, N, h, w, heat_avg, paf_avg, table,
+                           stream);
 }
 
 int rtpose_tta_accumulate_skel(const float* heat, const rtpose_layout* lheat, const float* paf,
                                const rtpose_layout* lpaf, int B, int hs, int w_valid, float* acc_heat, float* acc_paf,
                                int hd, int wd, float src_h_valid, float src_w_valid, float alpha, float beta, int flip,
                                const rtpose_flip_table* table, void* stream) {
-  if (!heat || !lheat || !paf || !lpaf || !acc_heat || !acc_paf)
-    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: NULL argument");
-  const int rc = check_table(table);
-  if (rc) return rc;
-  if (table->heat_channels > lheat->cstride - lheat->choff)
-    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: the table has %d heat-map channels, the view addresses %d",
-                table->heat_channels, lheat->cstride - lheat->choff);
-  if (table->paf_channels > lpaf->cstride - lpaf->choff)
-    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: the table has %d PAF channels, the view addresses %d",
-                table->paf_channels, lpaf->cstride - lpaf->choff);
-  if (B == 0) return 0;
-  if (B < 0 || B > 65535 || hs <= 0 || hs > lheat->hs || hs > lpaf->hs || hd <= 0 || hd > 65535 || wd <= 0 ||
-      !(src_h_valid > 0) || !(src_w_valid > 0))
-    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: bad sizes (B %d, hs %d, hd %d, wd %d; B and hd at most 65535)", B,
-                hs, hd, wd);
-  if (w_valid < 1 || w_valid > lheat->ws || w_valid > lpaf->ws)
-    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: w_valid %d outside [1,%d]", w_valid,
-                lheat->ws < lpaf->ws ? lheat->ws : lpaf->ws);
-  const int ctot = table->heat_channels + table->paf_channels;
-  if ((long long)wd * ctot > 0x7fffff00ll)
-    return fail(RTPOSE_E_INVAL, "tta_accumulate_skel: row of %d pixels too long", wd);
-  hipLaunchKernelGGL(tta_accumulate_skel_kernel, dim3(ceil_div(wd * ctot, kThreads), hd, B), dim3(kThreads), 0,
-                     as_stream(stream), heat, to_view(lheat), paf, to_view(lpaf), B, hs, w_valid, acc_heat, acc_paf, hd,
-                     wd, src_h_valid / (float)hd, src_w_valid / (float)wd, alpha, beta, flip ? 1 : 0, *table,
-                     make_fastdiv(ctot));
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return tta_accumulate_launch("tta_accumulate_skel", heat, lheat, paf, lpaf, B, hs, w_valid, acc_heat, acc_paf, hd, wd,
+                               src_h_valid, src_w_valid, alpha, beta, flip, table, stream);
 }
 
 }  // extern "C"

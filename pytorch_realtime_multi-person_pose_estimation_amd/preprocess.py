@@ -9,11 +9,14 @@ HResizeLinear -> VResizeLinear with the (x>>4, >>16, +2, >>2) rounding).  Parity
 that restatement against a real OpenCV build is UNPINNED here; when cv2 is importable
 it is used instead.  The network + decoder that follow run on the GPU.
 """
+import functools
+
 import numpy as np
 import torch
 
 from . import _capi, decode as dec
 from ._capi import lib, check, ptr, current_stream
+from .skeleton import COCO18
 
 
 def C_byref(x):
@@ -194,6 +197,12 @@ def _skeleton_channels(model, skeleton):
     return _check_model_channels(_unwrap(model), skeleton)
 
 
+@functools.lru_cache(maxsize=None)
+def _coco18_flip_table():
+    """COCO-18's packed rtpose_flip_table, what skeleton=None means to the merges: packed once per process."""
+    return COCO18.native_flip_table()
+
+
 def _final_maps(model, x):
     """(paf, heat) of the last stage, NCHW: rtpose_vgg returns them as the first result, OpenPose_Model as the last pair
     of a list of (paf, heat) pairs."""
@@ -202,23 +211,20 @@ def _final_maps(model, x):
 
 
 def handle_paf_and_heat(normal_heat, flipped_heat, normal_paf, flipped_paf, skeleton=None):
-    """coco_eval.py:197-242 on the GPU (csrc/layout_ops.hip:flip_merge_kernel); with a skeleton.Skeleton the same merge
-    over its left / right tables (csrc/tta_skel.hip), the maps carrying the skeleton's channel counts."""
+    """coco_eval.py:197-242 on the GPU (csrc/tta.hip:flip_merge_kernel) over the left / right tables of a
+    skeleton.Skeleton, the maps carrying its channel counts; None: COCO-18, 19 / 38 channels."""
     dev = torch.device('cuda', torch.cuda.current_device())
     t = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)[None]
          for a in (normal_heat, flipped_heat, normal_paf, flipped_paf)]
     h, w = t[0].shape[1], t[0].shape[2]
     oh, op = torch.empty_like(t[0]), torch.empty_like(t[2])
-    if skeleton is not None:
-        if (t[0].shape[3], t[2].shape[3]) != (skeleton.heat_channels, skeleton.paf_channels):
-            raise ValueError("handle_paf_and_heat: skeleton %s has %d heat-map / %d PAF channels, the maps have %d / %d"
-                             % (skeleton.name, skeleton.heat_channels, skeleton.paf_channels, t[0].shape[3], t[2].shape[3]))
-        table = skeleton.native_flip_table()
-        check(lib.rtpose_flip_merge_skel(ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), 1, h, w, ptr(oh), ptr(op),
-                                         C_byref(table), current_stream()), "rtpose_flip_merge_skel")
-        return op[0].cpu().numpy(), oh[0].cpu().numpy()
-    check(lib.rtpose_flip_merge(ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), 1, h, w, ptr(oh), ptr(op),
-                                current_stream()), "rtpose_flip_merge")
+    sk = skeleton or COCO18
+    if (t[0].shape[3], t[2].shape[3]) != (sk.heat_channels, sk.paf_channels):
+        raise ValueError("handle_paf_and_heat: skeleton %s has %d heat-map / %d PAF channels, the maps have %d / %d"
+                         % (sk.name, sk.heat_channels, sk.paf_channels, t[0].shape[3], t[2].shape[3]))
+    table = skeleton.native_flip_table() if skeleton is not None else _coco18_flip_table()
+    check(lib.rtpose_flip_merge_skel(ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), 1, h, w, ptr(oh), ptr(op),
+                                     C_byref(table), current_stream()), "rtpose_flip_merge_skel")
     return op[0].cpu().numpy(), oh[0].cpu().numpy()
 
 
@@ -248,10 +254,11 @@ def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.
     Returns (paf [h,w,38], heatmap [h,w,19], im_scale of the 1.0 pass).
 
     skeleton: a skeleton.Skeleton (e.g. skeleton.BODY_25) - the model must write its channel counts, the flipped pass is
-    merged over skeleton.flip_tables() (rtpose_flip_merge_skel) and the maps returned carry its channels.  None: COCO-18.
+    merged over skeleton.flip_tables() (rtpose_flip_merge_skel) and the maps returned carry its channels.  None: COCO-18's
+    tables and 38 / 19 channels.
     Not for hourglass models: their input size is bound to multiples of 64, not of the stride this function pads to."""
     paf_c, heat_c = _skeleton_channels(model, skeleton)
-    table = skeleton.native_flip_table() if skeleton is not None and flip else None
+    table = (skeleton.native_flip_table() if skeleton is not None else _coco18_flip_table()) if flip else None
     config = config or dec.default_config()
     base = int(config.DATASET.IMAGE_SIZE)
     stride = int(config.MODEL.DOWNSAMPLE)
@@ -281,12 +288,8 @@ def get_multiscale_outputs(img, model, preprocess='rtpose', scales=(0.5, 1.0, 1.
             hv, pv = heat2[0:1, :, :vwm].contiguous(), paf2[0:1, :, :vwm].contiguous()
             hfv, pfv = heat2[1:2, :, :vwm].contiguous(), paf2[1:2, :, :vwm].contiguous()
             mh, mp = torch.empty_like(hv), torch.empty_like(pv)
-            if table is not None:
-                check(lib.rtpose_flip_merge_skel(ptr(hv), ptr(hfv), ptr(pv), ptr(pfv), 1, hv.shape[1], vwm, ptr(mh), ptr(mp),
-                                                 C_byref(table), stream), "rtpose_flip_merge_skel")
-            else:
-                check(lib.rtpose_flip_merge(ptr(hv), ptr(hfv), ptr(pv), ptr(pfv), 1, hv.shape[1], vwm, ptr(mh), ptr(mp),
-                                            stream), "rtpose_flip_merge")
+            check(lib.rtpose_flip_merge_skel(ptr(hv), ptr(hfv), ptr(pv), ptr(pfv), 1, hv.shape[1], vwm, ptr(mh), ptr(mp),
+                                             C_byref(table), stream), "rtpose_flip_merge_skel")
             heat, paf = mh, mp
         else:
             paf, heat = _final_maps(model, x)
@@ -310,19 +313,19 @@ def get_multiscale_outputs_batch(imgs, model, preprocess='rtpose', scales=(0.5, 
     """Batched, GPU-resident form of get_multiscale_outputs (BASELINE config 3): B uint8 BGR images
     of one size are uploaded once (3 B/pixel); per scale ONE kernel per image resizes + pads +
     normalises it (and its mirror image) straight into the input buffer of a 2B-image plan, one
-    forward runs all of them, and one fused kernel (rtpose_tta_accumulate) does the flip merge,
+    forward runs all of them, and one fused kernel (rtpose_tta_accumulate_skel) does the flip merge,
     the resize to the scale-1 map and the running average where the net wrote its outputs.
     Same arithmetic as get_multiscale_outputs, image by image.
     Returns DEVICE tensors (paf [B,h,w,38], heat [B,h,w,19]) and the scale-1 im_scale - feed them
     to decode.decode_maps.
 
-    skeleton: a skeleton.Skeleton - the model must write its channel counts, the fused kernel is
-    rtpose_tta_accumulate_skel over skeleton.flip_tables() (packed once per call) and the tensors returned carry the
-    skeleton's channels: feed them to decode.decode_maps(..., skeleton=skeleton).  None: COCO-18, rtpose_tta_accumulate.
+    skeleton: a skeleton.Skeleton - the model must write its channel counts, the fused kernel runs over
+    skeleton.flip_tables() (packed once per call) and the tensors returned carry the skeleton's channels: feed them to
+    decode.decode_maps(..., skeleton=skeleton).  None: COCO-18's tables and 38 / 19 channels.
     Not for hourglass models (see get_multiscale_outputs)."""
     import ctypes as C
     paf_c, heat_c = _skeleton_channels(model, skeleton)
-    table = skeleton.native_flip_table() if skeleton is not None else None
+    table = skeleton.native_flip_table() if skeleton is not None else _coco18_flip_table()
     config = config or dec.default_config()
     base = int(config.DATASET.IMAGE_SIZE)
     stride = int(config.MODEL.DOWNSAMPLE)
@@ -355,15 +358,10 @@ def get_multiscale_outputs_batch(imgs, model, preprocess='rtpose', scales=(0.5, 
         hbase, lheat, _, _, _ = m.output_view(plan, 1)
         wv = -(-wr // stride) if flip else ws
         ratio = im_scale / s1
-        if table is not None:
-            check(lib.rtpose_tta_accumulate_skel(hbase, C.byref(lheat), pbase, C.byref(lpaf), B, hs, wv, ptr(acc_heat),
-                                                 ptr(acc_paf), hd, wd, hd * ratio, wd * ratio, 1.0 / len(scales),
-                                                 0.0 if si == 0 else 1.0, 1 if flip else 0, C.byref(table), stream),
-                  "rtpose_tta_accumulate_skel")
-            continue
-        check(lib.rtpose_tta_accumulate(hbase, C.byref(lheat), pbase, C.byref(lpaf), B, hs, wv, ptr(acc_heat),
-                                        ptr(acc_paf), hd, wd, hd * ratio, wd * ratio, 1.0 / len(scales),
-                                        0.0 if si == 0 else 1.0, 1 if flip else 0, stream), "rtpose_tta_accumulate")
+        check(lib.rtpose_tta_accumulate_skel(hbase, C.byref(lheat), pbase, C.byref(lpaf), B, hs, wv, ptr(acc_heat),
+                                             ptr(acc_paf), hd, wd, hd * ratio, wd * ratio, 1.0 / len(scales),
+                                             0.0 if si == 0 else 1.0, 1 if flip else 0, C.byref(table), stream),
+              "rtpose_tta_accumulate_skel")
     return acc_paf, acc_heat, s1
 
 

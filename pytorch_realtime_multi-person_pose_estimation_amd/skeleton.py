@@ -7,7 +7,7 @@ limbs may start a new person.  ``decode.decode_maps(..., skeleton=s)``,
 
 Flip merge and multi-scale TTA take one too: ``preprocess.handle_paf_and_heat``, ``get_multiscale_outputs`` and
 ``get_multiscale_outputs_batch`` with ``skeleton=s`` run ``rtpose_flip_merge_skel`` / ``rtpose_tta_accumulate_skel``
-(csrc/tta_skel.hip, header section 5a) over ``s.flip_tables()``: which channel of the mirrored pass every output channel
+(csrc/tta.hip, header section 5a) over ``s.flip_tables()``: which channel of the mirrored pass every output channel
 reads, and with which sign.  The tables follow from the part names (a leading ``L`` / ``R``) or an explicit ``mirror``
 and from the limbs.  The TTA paths resize with ``crop_with_factor(factor=stride)``; hourglass models, whose input size
 must be a multiple of 64, are out of their scope.

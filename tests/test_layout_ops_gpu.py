@@ -926,6 +926,16 @@ def test_argument_checks_refuse_and_write_nothing(K):
         "resize valid 0": lambda: lib.rtpose_resize_bilinear_accum(src, 8, 8, d32, 8, 8, 4, 1, 0.0, 8.0, 1.0, 0.0, s),
         "tta NULL": lambda: lib.rtpose_tta_accumulate(None, L(sc.ls16), src, L(sc.ls16), 1, 8, 8, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
         "tta w_valid 0": lambda: lib.rtpose_tta_accumulate(src, L(sc.ls16), src, L(sc.ls16), 1, 8, 0, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
+        # the COCO-18 doors share the table-driven doors' argument check (csrc/tta.hip): each of these used to read or
+        # write outside the caller's buffers, or dereference NULL
+        "tta NULL layout": lambda: lib.rtpose_tta_accumulate(src, None, src, L(sc.ls16), 1, 8, 8, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
+        "tta w_valid above ws": lambda: lib.rtpose_tta_accumulate(src, L(sc.ls16), src, L(sc.ls16), 1, 8, sc.ls16.ws + 1, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
+        "tta hs above the view's": lambda: lib.rtpose_tta_accumulate(src, L(sc.ls16), src, L(sc.ls16), 1, sc.ls16.hs + 1, 8, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
+        "tta heat view of 18 channels": lambda: lib.rtpose_tta_accumulate(src, L(sc.ls16._replace(choff=64 - 18)), src, L(sc.ls16), 1, 8, 8, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
+        "tta paf view of 37 channels": lambda: lib.rtpose_tta_accumulate(src, L(sc.ls16), src, L(sc.ls16._replace(choff=64 - 37)), 1, 8, 8, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
+        "tta B 65536": lambda: lib.rtpose_tta_accumulate(src, L(sc.ls16), src, L(sc.ls16), 65536, 8, 8, d32, d32, 8, 8, 8.0, 8.0, 1.0, 0.0, 0, s),
+        "flip_merge NULL output": lambda: lib.rtpose_flip_merge(src, src, src, src, 1, h, w, None, d32, s),
+        "flip_merge NULL map": lambda: lib.rtpose_flip_merge(src, None, src, src, 1, h, w, d32, d32, s),
         "to_bf16 cpad % 8": lambda: lib.rtpose_nchw_to_layout_bf16(src, d16, L(ld), 4, 4, n, h, w, s),
         "to_bf16 cpad < C": lambda: lib.rtpose_nchw_to_layout_bf16(src, d16, L(ld), 16, 8, n, h, w, s),
         "f32_to_bf16 choff % 8": lambda: lib.rtpose_layout_f32_to_bf16(src, L(ls), d16, L(off4), 8, 8, n, h, w, s),

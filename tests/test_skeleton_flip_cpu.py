@@ -119,6 +119,22 @@ def test_library_derivation_agrees_with_python(capi, skm, name):
     assert capi.lib.rtpose_flip_table_check(C.byref(out)) == 0
 
 
+def test_library_coco18_table_is_the_reference_lists_and_the_even_source_rule(capi, skm):
+    """What the COCO-18 doors (rtpose_flip_merge, rtpose_tta_accumulate) derive their table from - the library's own
+    rtpose_skeleton_coco18 and COCO-18's part mirror - gives the reference's swap lists, and negates exactly the PAF
+    channels k whose source SWAP_PAF[k] is even: the rule the fixed COCO-18 kernels applied, as data."""
+    from oracle.host_oracle import SWAP_HEAT, SWAP_PAF
+    sk, out = capi.SkeletonStruct(), capi.FlipTable()
+    capi.check(capi.lib.rtpose_skeleton_coco18(C.byref(sk)), "rtpose_skeleton_coco18")
+    mirror = (C.c_int32 * 18)(*skm.COCO18.mirror)
+    capi.check(capi.lib.rtpose_flip_table_from_skeleton(C.byref(sk), mirror, 1, 38, C.byref(out)),
+               "rtpose_flip_table_from_skeleton")
+    assert (out.heat_channels, out.paf_channels) == (19, 38)
+    assert list(out.heat_src[:19]) == list(SWAP_HEAT) and list(mirror) == list(SWAP_HEAT[:18])
+    assert list(out.paf_src[:38]) == list(SWAP_PAF)
+    assert int(out.paf_neg_mask) == sum(1 << k for k in range(38) if SWAP_PAF[k] % 2 == 0)
+
+
 def test_library_refuses_what_python_refuses(capi, skm):
     lib = capi.lib
     out = capi.FlipTable()

@@ -1,4 +1,4 @@
-"""Host restatement of the flip merge with the left / right permutation as data (csrc/tta_skel.hip), and the tables
+"""Host restatement of the flip merge with the left / right permutation as data (csrc/tta.hip), and the tables
 tests/test_skeleton_flip_cpu.py and tests/test_tta_skel_gpu.py share.  numpy + torch CPU float64, no GPU, no library call;
 extends tests/layout_restate.py (which stays as it is) and follows its convention: an arithmetic reference returns
 (value, S), the float64 result and the float64 sum of the absolute values of the terms that were added.

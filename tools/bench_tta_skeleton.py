@@ -1,4 +1,5 @@
-"""The fused TTA merge alone on one MI355X, through the COCO-18 entry point and through the table-driven one: JSON lines.
+"""The fused TTA merge and the flip merge alone on one MI355X, through the COCO-18 entry points and through the table-driven
+ones: JSON lines.
 
     timeout -k 10 300 python tools/bench_tta_skeleton.py [--iters 200] [--warmup 20] [--rounds 3] [--out FILE]
 
@@ -10,9 +11,11 @@ images at 23 x 23, 46 x 46, 69 x 69 and 92 x 92, read in place from a padded buf
   a  rtpose_tta_accumulate                       COCO-18 (38 / 19 channels at 2 / 41 of a 64-channel pixel)
   b  rtpose_tta_accumulate_skel, COCO-18 table   the same buffer and views
   c  rtpose_tta_accumulate_skel, BODY_25 table   52 / 26 channels at 2 / 60 of a 96-channel pixel
+  d  rtpose_flip_merge                           the unfused merge: dense 32 x hs x ws x 19 / 38 maps of the scale and
+  e  rtpose_flip_merge_skel, COCO-18 table       their mirrored passes into dense maps of the same size
 
-are timed one by one with device events, a and b alternating launch by launch (c after each pair), after `warmup` untimed
-rounds; the medians are reported, and the whole measurement is repeated `rounds` times so that the spread of the medians
+are timed one by one with device events, a and b alternating launch by launch (c, d, e after each pair), after `warmup`
+untimed rounds; the medians are reported, and the whole measurement is repeated `rounds` times so that the spread of the medians
 from one round to the next can be read beside the b / a ratio.  Values are random; the kernels' time does not depend on
 them.  --out appends the lines to a file as well.
 """
@@ -67,7 +70,7 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     acc = {c: torch.zeros(B, HD, WD, c, device=dev) for c in (19, 38, 26, 52)}
     for rnd in range(a.rounds):
-        total = {"a": 0.0, "b": 0.0, "c": 0.0}
+        total = {k: 0.0 for k in "abcde"}
         for si, (scale, hs) in enumerate(SCALES):
             ws = hs
             beta = 0.0 if si == 0 else 1.0
@@ -92,9 +95,18 @@ def main():
             def new25():
                 capi.check(lib.rtpose_tta_accumulate_skel(ptr(buf25), C.byref(lh25), ptr(buf25), C.byref(lp25), *common,
                                                           ptr(acc[26]), ptr(acc[52]), *tail, C.byref(body), stream))
-            us = {"a": [], "b": [], "c": []}
+            dense = [torch.randn(B, hs, ws, c, device=dev, generator=g) for c in (19, 19, 38, 38)]
+            merged = [torch.empty_like(dense[0]), torch.empty_like(dense[2])]
+            margs = tuple(ptr(t) for t in dense) + (B, hs, ws, ptr(merged[0]), ptr(merged[1]))
+
+            def merge_old():
+                capi.check(lib.rtpose_flip_merge(*margs, stream))
+
+            def merge_new():
+                capi.check(lib.rtpose_flip_merge_skel(*margs, C.byref(coco), stream))
+            us = {k: [] for k in "abcde"}
             for i in range(a.warmup + a.iters):
-                for key, fn in (("a", old), ("b", new18), ("c", new25)):
+                for key, fn in (("a", old), ("b", new18), ("c", new25), ("d", merge_old), ("e", merge_new)):
                     t = timed(fn)
                     if i >= a.warmup:
                         us[key].append(t)
@@ -106,10 +118,13 @@ def main():
                   "a_old_coco18_us": {"median": round(med["a"], 2), "min": round(min(us["a"]), 2), "max": round(max(us["a"]), 2)},
                   "b_skel_coco18_us": {"median": round(med["b"], 2), "min": round(min(us["b"]), 2), "max": round(max(us["b"]), 2)},
                   "c_skel_body25_us": {"median": round(med["c"], 2), "min": round(min(us["c"]), 2), "max": round(max(us["c"]), 2)},
-                  "b_over_a": round(med["b"] / med["a"], 3)})
-            del buf18, buf25
+                  "d_old_flip_merge_us": {"median": round(med["d"], 2), "min": round(min(us["d"]), 2), "max": round(max(us["d"]), 2)},
+                  "e_skel_flip_merge_us": {"median": round(med["e"], 2), "min": round(min(us["e"]), 2), "max": round(max(us["e"]), 2)},
+                  "b_over_a": round(med["b"] / med["a"], 3), "e_over_d": round(med["e"] / med["d"], 3)})
+            del buf18, buf25, dense, merged
         emit({"round": rnd, "four_scales_sum_of_medians_us": {k: round(v, 2) for k, v in total.items()},
-              "b_over_a": round(total["b"] / total["a"], 3), "c_over_a": round(total["c"] / total["a"], 3)})
+              "b_over_a": round(total["b"] / total["a"], 3), "c_over_a": round(total["c"] / total["a"], 3),
+              "e_over_d": round(total["e"] / total["d"], 3)})
     if a.out:
         with open(a.out, "a") as f:
             f.write("\n".join(lines) + "\n")
