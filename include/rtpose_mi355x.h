@@ -687,6 +687,12 @@ int rtpose_net_read_output(rtpose_net* net, int which, float* dst_nchw,
  * so the post-processing reads them where the last conv wrote them. */
 int rtpose_net_output_view(const rtpose_net* net, int which, const float** base,
                            rtpose_layout* layout, int* C, int* H, int* W);
+/* The same for any stage output, numbered as rtpose_net_read_output numbers them (rtpose_vgg: 0..11 =
+ * saved_for_loss order): where the maps are right now - in the stage records under keep_intermediates,
+ * else where the stage's last launch left them, which only the last stages' still are (RTPOSE_E_STATE for
+ * the others).  rtpose_stage_mse (section 4b) reads the loss terms off these views. */
+int rtpose_net_stage_view(const rtpose_net* net, int which, const float** base,
+                          rtpose_layout* layout, int* C, int* H, int* W);
 /* Per-layer HIP-event timing of the next forwards (bench.py roofline leg). */
 int rtpose_net_set_profiling(rtpose_net* net, int enable);
 int rtpose_net_num_launches(const rtpose_net* net);
@@ -1004,6 +1010,74 @@ int rtpose_decode_batch_skel(const float* heat, const rtpose_layout* lheat, cons
                              const rtpose_decode_cfg* cfg, const rtpose_skeleton* skel,
                              int nms_flags, void* workspace, size_t workspace_bytes,
                              void* result, void* stream);
+
+/* ---- 4b. The way back: people -> heat-map / PAF targets, and the stage loss terms ------
+ * stands in for lib/datasets/datasets.py:259-308 (CocoKeypoints.get_ground_truth) with
+ * lib/datasets/heatmap.py:20-36 (putGaussianMaps) and lib/datasets/paf.py:18-68 (putVecMaps), for any
+ * skeleton and a batch of images, and for one term of train/train_VGG19.py:143-174 (get_loss).
+ *
+ * h = input_h / stride, w = input_w / stride (integer division, datasets.py:261-262).  A part is
+ * present iff v > 0.5 and 0 <= x < input_w and 0 <= y < input_h (remove_illegal_joint, :216-225).
+ * Heat channel j at cell (y, x): cell centre gx = x * stride + (stride / 2.0 - 0.5), gy likewise; for
+ * each person in order e = ((gx - cx)^2 + (gy - cy)^2) / 2.0 / sigma / sigma (three divisions in that
+ * order); exp(-e) is added iff e <= 4.6052 and the running sum clipped to 1.  background != 0: heat
+ * channel num_parts = max(1 - max over the parts, 0).  Heat channels behind those are written as 0.
+ * Limb l = (A, B, chx, chy), for each person in order with both parts present: a = A / stride,
+ * b = B / stride, v = b - a, n = sqrt(vx vx + vy vy); n == 0 skips the person; u = v / n; the box is
+ * x0 = max(int(rint(min(ax, bx) - 1)), 0), x1 = min(int(rint(max(ax, bx) + 1)), w) (rint: half to
+ * even, Python's round), y likewise; a cell is in the mask iff it lies in [x0, x1) x [y0, y1) and
+ * |(x - ax) uy - (y - ay) ux| < 1; then for EVERY cell of the map acc = acc * count, acc += mask ? u : 0,
+ * count += mask, acc = acc / max(count, 1) - the reference's running average, which re-rounds a cell
+ * outside the box by * count / count (paf.py:56-66).  acc_x goes to channel chx, acc_y to chy; PAF
+ * channels no limb names are written as 0; a channel two limbs name belongs to the first of them.
+ * All of it in fp64, operation for operation in the reference's order, rounded to fp32 at the store:
+ * every decision (e <= 4.6052, |cross| < 1, the half-even box) is the reference's, the PAF values are
+ * its bits, the heat values are within 1 fp32 ulp (exp).  Not the reference's: np.linalg.norm may use a
+ * fused multiply-add inside BLAS's dot; n here is the unfused sqrt(vx vx + vy vy).
+ *
+ * The skeleton travels by value into the kernels as a launch argument; nothing is uploaded.  People are
+ * summed in people order whatever the launch geometry (no atomics): an image encodes to the same bits
+ * alone and inside a batch.  The raster kernel walks an image's people through LDS in chunks of
+ * RTPOSE_ENCODE_CHUNK records; max_people has no cap but the grid limit below. */
+#define RTPOSE_ENCODE_CHUNK 16
+
+typedef struct rtpose_encode_cfg {
+  uint32_t struct_bytes;     /* sizeof(rtpose_encode_cfg)                                        */
+  int32_t input_h, input_w;  /* network input size in pixels (reference: input_y, input_x)       */
+  int32_t stride;            /* 8 for rtpose_vgg / OpenPose_Model, 4 for the hourglass           */
+  double sigma;              /* reference: 7.0 (input pixels)                                    */
+  int32_t background;        /* != 0: heat channel num_parts = max(1 - max over parts, 0)        */
+  int32_t reserved;          /* 0                                                                */
+} rtpose_encode_cfg;
+
+/* Bytes of the caller-provided device workspace (the per-person records); 0 on a bad cfg, skeleton or count. */
+size_t rtpose_encode_workspace_bytes(const rtpose_encode_cfg* cfg, const rtpose_skeleton* skel, int N,
+                                     int max_people);
+/* keypoints: device fp64 [N][max_people][num_parts][3] = (x, y, v) in input pixels; n_people: device
+ * int32 [N] (clamped to 0..max_people) or NULL = max_people everywhere; heat / paf: dense
+ * [N][h][w][heat_channels] / [N][h][w][paf_channels], EVERY element is written.  N == 0 is a no-op.
+ * Refused before any launch, the message naming the argument: NULL pointers; a wrong struct_bytes; a
+ * skeleton that fails rtpose_skeleton_check for these channel counts; more than 33 heat-map or 64 PAF
+ * channels; background != 0 with heat_channels <= num_parts; stride < 1; sigma not greater than 0; an empty
+ * grid; N or h above 65535, or N * max_people * (num_parts + num_limbs) above 0x7fffff00 (grid limits);
+ * a workspace smaller than the query reports. */
+int rtpose_encode_targets_skel(const double* keypoints, const int32_t* n_people, int N, int max_people,
+                               const rtpose_encode_cfg* cfg, const rtpose_skeleton* skel,
+                               int heat_channels, int paf_channels, float* heat, float* paf,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* nn.MSELoss(reduction='mean') of one stage output against a target (train_VGG19.py:147, :156-157):
+ * `pred` is read in place through its padded-NHWC view (rtpose_net_stage_view / rtpose_net_output_view),
+ * `target` is dense NHWC [N][h][w][channels].  Both operands are widened to fp64 before the subtraction,
+ * squares and sums are fp64: per-block partials, then one block adds them in a fixed order and writes
+ * fp32(sum / (N h w channels)) to *loss_out (device).  No atomics: the same bits on every run.
+ * `partials`: device fp64 workspace of at least rtpose_stage_mse_partials(N, h, w, channels) elements
+ * (0 = sizes out of range: any below 1, or more than 0x7fffff00 elements).  Refused before any launch:
+ * NULL pointers, channels > cstride - choff, a map larger than the view, partial_count too small. */
+size_t rtpose_stage_mse_partials(int N, int h, int w, int channels);
+int rtpose_stage_mse(const float* pred, const rtpose_layout* lpred, const float* target, int N, int h,
+                     int w, int channels, double* partials, size_t partial_count, float* loss_out,
+                     void* stream);
 
 /* ------------------------------------------------------------------------
  * 5. Flip test-time-augmentation merge

@@ -122,6 +122,19 @@ class FlipTable(C.Structure):
                 ("paf_src", C.c_uint8 * FLIP_MAX_PAF)]
 
 
+ENCODE_CHUNK = 16   # RTPOSE_ENCODE_CHUNK: person records per LDS chunk of the raster kernel
+
+
+class EncodeCfg(C.Structure):
+    """rtpose_encode_cfg: geometry of the target encoder (header section 4b)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("input_h", C.c_int32), ("input_w", C.c_int32), ("stride", C.c_int32),
+                ("sigma", C.c_double), ("background", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, input_h, input_w, stride=8, sigma=7.0, background=1):
+        return cls(C.sizeof(cls), input_h, input_w, stride, sigma, 1 if background else 0, 0)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -278,6 +291,12 @@ _SIGS = {
     "rtpose_nms_batch_skel": (_i, [_vp, _LP, _i, _i, _i, C.POINTER(DecodeCfg), C.POINTER(SkeletonStruct), _i, _vp, _vp]),
     "rtpose_decode_batch_skel": (_i, [_vp, _LP, _vp, _LP, _i, _i, _i, C.POINTER(DecodeCfg), C.POINTER(SkeletonStruct), _i,
                                       _vp, _sz, _vp, _vp]),
+    "rtpose_net_stage_view": (_i, [_vp, _i, C.POINTER(_vp), _LP, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "rtpose_encode_workspace_bytes": (_sz, [C.POINTER(EncodeCfg), C.POINTER(SkeletonStruct), _i, _i]),
+    "rtpose_encode_targets_skel": (_i, [_vp, _vp, _i, _i, C.POINTER(EncodeCfg), C.POINTER(SkeletonStruct), _i, _i, _vp, _vp,
+                                        _vp, _sz, _vp]),
+    "rtpose_stage_mse_partials": (_sz, [_i, _i, _i, _i]),
+    "rtpose_stage_mse": (_i, [_vp, _LP, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "rtpose_preprocess_u8_batch": (_i, [C.POINTER(PrepImage), _i, _i, _vp, _LP, _i, _i, _vp]),
     "rtpose_preprocess_u8": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_preprocess_u8_flip": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1794,4 +1794,21 @@ int rtpose_net_output_view(const rtpose_net* net, int which, const float** base,
   return 0;
 }
 
+int rtpose_net_stage_view(const rtpose_net* net, int which, const float** base, rtpose_layout* layout, int* C, int* H,
+                          int* W) {
+  if (!net || !net->bound) return fail(RTPOSE_E_STATE, "net_stage_view: net not bound");
+  if (which < 0 || which >= (net->topo == 2 ? 2 + 2 * net->hg_stacks : net->topo == 1 ? net->op_l2 + net->op_l1 : 12))
+    return fail(RTPOSE_E_INVAL, "net_stage_view: bad argument");
+  const float* b;
+  rtpose_layout l;
+  int c;
+  if (int rc = stage_output_slice(net, which, net->keep != 0, &b, &l, &c)) return rc;
+  if (base) *base = b;
+  if (layout) *layout = l;
+  if (C) *C = c;
+  if (H) *H = net->H3;
+  if (W) *W = net->W3;
+  return 0;
+}
+
 }  // extern "C"

@@ -12,6 +12,11 @@ reads, and with which sign.  The tables follow from the part names (a leading ``
 and from the limbs.  The TTA paths resize with ``crop_with_factor(factor=stride)``; hourglass models, whose input size
 must be a multiple of 64, are out of their scope.
 
+The way back takes one as well: ``encode.encode_targets(people, skeleton=s)`` renders people into the heat-map / PAF
+targets of ``s`` on the device (csrc/encode.hip, header section 4b: the reference's get_ground_truth, fp64 operation for
+operation).  ``encode.COCO18_TRAIN`` is the reference's training table, which joins shoulder to eye where ``COCO18`` below
+(the decoder's, pafprocess.h) joins shoulder to ear on the same PAF channels; encode with the table the maps are for.
+
 What a skeleton does NOT reach (COCO-18 only): the legacy ``pafprocess.process_paf`` API and its getters,
 ``append_result`` / the OKS evaluation (COCO-18 -> COCO-17 mapping), ``run_eval_batched``'s TTA mode, and any
 reduced-precision plan.
