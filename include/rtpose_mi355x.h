@@ -1079,6 +1079,80 @@ int rtpose_stage_mse(const float* pred, const rtpose_layout* lpred, const float*
                      int w, int channels, double* partials, size_t partial_count, float* loss_out,
                      void* stream);
 
+/* ---- 4c. Training-batch augmentation: flip, rescale, crop, pad, normalise, mask -----------
+ * stands in for the image side of the preprocess chain of train/train_VGG19.py:124-130
+ * (RandomApply(HFlip), RescaleRelative, Crop, CenterPad of lib/datasets/transforms.py), for
+ * image_transform (ToTensor + ImageNet Normalize) and for utils.mask_valid_area
+ * (lib/datasets/utils.py:36-54): uint8 RGB sources in, the network's 3-channel fp32 input out, the
+ * reference's bits.  The random draws and the annotation side are host work (augment.py); the
+ * caller passes their results per image.
+ *
+ * RescaleRelative is Pillow's Image.resize((wr, hr), BICUBIC) on 8-bit RGB (ImagingResample).  Per axis
+ * with `in` pixels in and `out` pixels out, in float64 with every operation unfused:
+ *   scale = in / out, filterscale = max(scale, 1.0), support = 2.0 * filterscale,
+ *   ksize = int(ceil(support)) * 2 + 1; for output xx: center = (xx + 0.5) * scale, ss = 1.0 / filterscale,
+ *   xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), in) - xmin
+ *   (int() truncates), w[x] = bicubic((x + xmin - center + 0.5) * ss) for x < xmax with a = -0.5:
+ *   |t| < 1: ((a + 2) t - (a + 3)) t t + 1, |t| < 2: (((t - 5) t + 8) t - 4) a, else 0; ww = the sum of
+ *   w[x] in index order, w[x] /= ww if ww != 0; k[x] = int(0.5 + w[x] * 2^22), int(-0.5 + w[x] * 2^22)
+ *   for w[x] < 0.
+ * The horizontal pass runs first and only if wr != w0, the vertical pass on its uint8 result and only
+ * if hr != h0; each output is clip(((1 << 21) + sum pixel * k) >> 22, 0, 255) per channel (arithmetic
+ * shift); an axis whose size does not change is copied, not filtered.  hflip mirrors the SOURCE before
+ * the resize (a mirrored resize is not a resized mirror: xmin truncates).
+ * Crop takes the window [crop_x, crop_x + min(out_w, wr - crop_x)) of the resized image, CenterPad puts
+ * it at left = (out_w - width) / 2 (integer division) of the canvas and fills the rest with `fill`;
+ * y likewise.  norm == 1: (float(u) / 255.0f - mean) / std per channel, mean (0.485, 0.456, 0.406),
+ * std (0.229, 0.224, 0.225) as fp32, every fp32 operation correctly rounded and unfused; the fill is
+ * normalised like a pixel.  Last, canvas pixels outside mask = [x0, x1) x [y0, y1) are exactly 0.0f.
+ *
+ * Every element of the three channels of every named slot is written; nothing else of dst is touched
+ * (not the other channels, the gaps of a padded layout, or unnamed slots).  No atomics: an image gives
+ * the same bits alone and inside a batch.  `images` is a HOST array whose entries travel as kernel
+ * arguments in chunks, as in rtpose_preprocess_u8_batch: the library allocates and copies nothing.  Per
+ * chunk: one launch tabulates both axes of every image's crop window into the workspace (at most
+ * out_w + out_h entries per image), one fused launch does the rest; the horizontal pass's result
+ * lives in LDS only. */
+#define RTPOSE_AUG_MAX_TAPS 17 /* ksize at factor 0.25; smaller factors are refused */
+
+typedef struct rtpose_augment_image {
+  const void* img_rgb;    /* device uint8 [h0][w0][3], RGB                                   */
+  int32_t h0, w0;         /* source size                                                      */
+  int32_t hr, wr;         /* size after RescaleRelative: int(h0 * f), int(w0 * f)             */
+  int32_t hflip;          /* != 0: source mirrored before the resize                          */
+  int32_t crop_x, crop_y; /* Crop's offsets in the resized image                              */
+  int32_t mask[4];        /* x0, y0, x1, y1: canvas pixels outside [x0,x1) x [y0,y1) are 0    */
+  int32_t n_index;        /* destination slot                                                 */
+} rtpose_augment_image;
+
+typedef struct rtpose_augment_cfg {
+  uint32_t struct_bytes; /* sizeof(rtpose_augment_cfg)                                        */
+  int32_t out_h, out_w;  /* the canvas (Crop's long_edge == CenterPad's target)               */
+  int32_t norm;          /* 0: float(u) in 0..255; 1: ToTensor + ImageNet mean/std            */
+  int32_t nchw;          /* 0: dst through the rtpose_layout (3 channels from choff);
+                            1: dense [N][3][out_h][out_w] (ldst is not read)                  */
+  uint8_t fill[4];       /* CenterPad's fill, (124, 116, 104, 0)                              */
+} rtpose_augment_cfg;
+
+/* Bytes of the caller-provided device workspace (the tables) for `count` images; 0 on a bad cfg or a
+ * negative count. */
+size_t rtpose_augment_workspace_bytes(const rtpose_augment_cfg* cfg, int count);
+/* The table above for outputs [first, first + count) of one axis, made on the device in fp64 by the
+ * device function the batch call uses: bounds[i] = (xmin, xmax), coeffs[i][x] = k[x], 0 for x >= xmax
+ * (both device int32).  Refused: NULL pointers, sizes below 1, a ksize above RTPOSE_AUG_MAX_TAPS, a
+ * range outside [0, out_size].  count == 0 is a no-op. */
+int rtpose_resample_table(int in_size, int out_size, int first, int count, int32_t* bounds,
+                          int32_t* coeffs, void* stream);
+/* Refused before any launch, the message naming the argument and for an image its index: NULL pointers
+ * (ldst only when nchw == 0); a wrong struct_bytes; norm or nchw outside {0, 1}; a canvas side outside
+ * [1, 65535]; h0, w0, hr or wr below 1; a ksize above RTPOSE_AUG_MAX_TAPS on either axis; crop_x
+ * outside [0, max(wr - out_w, 0)], crop_y likewise; a mask outside the canvas or with x0 > x1, y
+ * likewise; n_index outside [0, 65535]; with nchw == 0 a ldst with fewer than 3 channels from choff or
+ * a view smaller than the canvas; a workspace smaller than the query reports.  count == 0 is a no-op. */
+int rtpose_augment_batch(const rtpose_augment_image* images, int count, const rtpose_augment_cfg* cfg,
+                         float* dst, const rtpose_layout* ldst, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ------------------------------------------------------------------------
  * 5. Flip test-time-augmentation merge
  *    stands in for evaluate/coco_eval.py:197-242 (handle_paf_and_heat).

@@ -135,6 +135,26 @@ class EncodeCfg(C.Structure):
         return cls(C.sizeof(cls), input_h, input_w, stride, sigma, 1 if background else 0, 0)
 
 
+AUG_MAX_TAPS = 17   # RTPOSE_AUG_MAX_TAPS: taps per output of the bicubic table (ksize at factor 0.25)
+
+
+class AugmentImage(C.Structure):
+    """rtpose_augment_image: one image of a rtpose_augment_batch call (header section 4c)."""
+    _fields_ = [("img_rgb", C.c_void_p), ("h0", C.c_int32), ("w0", C.c_int32), ("hr", C.c_int32), ("wr", C.c_int32),
+                ("hflip", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("mask", C.c_int32 * 4),
+                ("n_index", C.c_int32)]
+
+
+class AugmentCfg(C.Structure):
+    """rtpose_augment_cfg: canvas, arithmetic and destination form of rtpose_augment_batch (header section 4c)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("norm", C.c_int32),
+                ("nchw", C.c_int32), ("fill", C.c_uint8 * 4)]
+
+    @classmethod
+    def make(cls, out_h, out_w, norm=1, nchw=1, fill=(124, 116, 104)):
+        return cls(C.sizeof(cls), out_h, out_w, norm, nchw, (C.c_uint8 * 4)(fill[0], fill[1], fill[2], 0))
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -297,6 +317,9 @@ _SIGS = {
                                         _vp, _sz, _vp]),
     "rtpose_stage_mse_partials": (_sz, [_i, _i, _i, _i]),
     "rtpose_stage_mse": (_i, [_vp, _LP, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "rtpose_augment_workspace_bytes": (_sz, [C.POINTER(AugmentCfg), _i]),
+    "rtpose_resample_table": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "rtpose_augment_batch": (_i, [C.POINTER(AugmentImage), _i, C.POINTER(AugmentCfg), _vp, _LP, _vp, _sz, _vp]),
     "rtpose_preprocess_u8_batch": (_i, [C.POINTER(PrepImage), _i, _i, _vp, _LP, _i, _i, _vp]),
     "rtpose_preprocess_u8": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_preprocess_u8_flip": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _i, _vp]),

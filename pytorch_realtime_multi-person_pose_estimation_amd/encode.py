@@ -45,12 +45,15 @@ _FROM_COCO17 = {0: 0, 2: 6, 3: 8, 4: 10, 5: 5, 6: 7, 7: 9, 8: 12, 9: 14, 10: 16,
 _COCO17_LSHOULDER, _COCO17_RSHOULDER = 5, 6
 
 
-def add_neck(keypoints17):
+def add_neck(keypoints17, dtype=np.float64):
     """lib/datasets/datasets.py:227-257: (17, 3) COCO keypoints (x, y, v) -> (18, 3) float64 in this work's order, with
     the neck midway between the shoulders: v = 2 if both shoulders have v == 2, else the product of their v; the neck
-    row alone goes through np.round (half to even)."""
-    coco = np.asarray(keypoints17, dtype=np.float64).reshape(17, 3)
-    out = np.empty((18, 3), np.float64)
+    row alone goes through np.round (half to even).  ``dtype=None`` keeps a floating-point input's own dtype, as the
+    reference does: the float32 keypoints of its loader get a neck computed in float32 (augment.train_batch)."""
+    coco = np.asarray(keypoints17, dtype=dtype).reshape(17, 3)
+    if not np.issubdtype(coco.dtype, np.floating):
+        coco = coco.astype(np.float64)
+    out = np.empty((18, 3), coco.dtype)
     for part, row in _FROM_COCO17.items():
         out[part] = coco[row]
     ls, rs = coco[_COCO17_LSHOULDER], coco[_COCO17_RSHOULDER]
