@@ -17,32 +17,11 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._capi import lib, check, ptr, current_stream
-from ._native_state import NativeStateMixin, NetPlanMixin
-from .network import _ShapeOnly
+from ._capi import lib, check
+from ._native_state import ConvRecord, NativeStateMixin, NetPlanMixin, bn_scale_shift, fold_bn  # noqa: F401 (re-exported)
 
 NUM_JOINTS = 18
 NUM_LIMBS = 38
-
-
-def _bn_affine64(bn):
-    """Inference BatchNorm2d as y = scale * x + shift, float64, with the module's own eps."""
-    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-    return scale, bn.bias.detach().double() - bn.running_mean.detach().double() * scale
-
-
-def bn_scale_shift(bn):
-    """(scale, shift) of an inference BatchNorm2d as fp32 vectors (float64 arithmetic)."""
-    scale, shift = _bn_affine64(bn)
-    return scale.float(), shift.float()
-
-
-def fold_bn(weight, bias, bn):
-    """Filters and bias of ``bn(conv(x))`` as one conv: w * scale[cout], b * scale + shift."""
-    scale, shift = _bn_affine64(bn)
-    w = weight.detach().double() * scale.view(-1, 1, 1, 1)
-    b = (bias.detach().double() if bias is not None else torch.zeros_like(scale)) * scale + shift
-    return w.float(), b.float()
 
 
 # ---- the topology, as the plan builder (csrc/net.hip, build_plan_hourglass) and tests/hourglass_restate.py state it ----
@@ -95,36 +74,15 @@ class Hourglass(nn.Module):
         self.hg = nn.ModuleList(nn.ModuleList(_chain(num_blocks) for _ in range(3 if i else 4)) for i in range(depth))
 
 
-class _Plan(object):
-    """One native stacked-hourglass executor instance (fixed N, H, W) + its workspace."""
-
-    def __init__(self, n, h, w, weights, device, topo, wino):
-        handle = C.c_void_p()
-        opts = _capi.HourglassOptions.make(*(topo + wino))
-        check(lib.rtpose_hourglass_create(n, h, w, C.byref(opts), C.byref(handle)), "rtpose_hourglass_create")
-        self.handle = handle
-        self.shape = (n, h, w)
-        self.dtype = _capi.DTYPE_F32
-        self.wino = wino
-        ws_bytes = lib.rtpose_net_workspace_bytes(handle)
-        self.workspace = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=device)
-        check(lib.rtpose_net_bind(handle, ptr(self.workspace), ws_bytes, ptr(weights),
-                                  weights.numel() * 4, 1, current_stream()), "rtpose_net_bind")
-        self.h3 = h // 4
-        self.w3 = w // 4
-
-    def __del__(self):
-        try:
-            lib.rtpose_net_destroy(self.handle)
-        except Exception:
-            pass
-
-
 class HourglassNet(NativeStateMixin, NetPlanMixin, nn.Module):
     """Drop-in for reference ``HourglassNet`` (lib/network/rtpose_hourglass.py:92).  fp32, inference (``.eval()``) only;
     runs on an MI355X.  Its maps are at stride 4 (``output_stride``); H and W must be multiples of 64."""
 
     output_stride = 4
+    _front_name = 'HourglassNet'
+    _plan_stride = output_stride
+    _probe_hw = 64
+    _WINO_DEFAULT = (_capi.WINO_DEFAULT, 0.0)   # (winograd3, amp_limit)
 
     def __init__(self, block=Bottleneck, num_stacks=2, num_blocks=4, paf_classes=2 * NUM_LIMBS, ht_classes=NUM_JOINTS + 1):
         super(HourglassNet, self).__init__()
@@ -156,7 +114,7 @@ class HourglassNet(NativeStateMixin, NetPlanMixin, nn.Module):
         self._initialize_weights_norm()
         self._init_native_state()
         self.compute_dtype = 'fp32'
-        self._wino = (_capi.WINO_DEFAULT, 0.0)
+        self._wino = self._WINO_DEFAULT
 
     def _initialize_weights_norm(self):
         """The reference's initial values (:191-199): filters N(0, 0.01), biases 0, BatchNorm weight 1 and bias 0."""
@@ -174,16 +132,7 @@ class HourglassNet(NativeStateMixin, NetPlanMixin, nn.Module):
         ``OpenPose_Model.set_winograd``: None = library default ('auto'), False / 0 = direct, True / 1 / 2 = F(2x2,3x3),
         4 = F(4x4,3x3) forced, 'auto' = per layer F(4x4,3x3) if its amplification estimate is <= ``amp_limit`` (default
         256), else F(2x2,3x3)."""
-        if winograd3 is None:
-            w3 = _capi.WINO_DEFAULT
-        elif winograd3 == 'auto':
-            w3 = _capi.WINO3_AUTO
-        elif winograd3 in (1, 2):
-            w3 = 1
-        elif winograd3 in (0, 4):
-            w3 = int(winograd3)
-        else:
-            raise ValueError("winograd3 must be None, False / 0, True / 1 / 2, 4 or 'auto'")
+        w3 = self._parse_winograd3(winograd3)
         self._wino = (w3, float(amp_limit or 0.0))
         return self
 
@@ -217,103 +166,30 @@ class HourglassNet(NativeStateMixin, NetPlanMixin, nn.Module):
                 out.append(('%s.%d' % (nm, s), m, None, None, None))
         return out
 
-    def _sync_weights(self, plan, device):
-        convs = self._convs()
-        wkey = (device.index, plan.dtype)
-        tensors = []
-        for _, m, bn, _, pbn in convs:
-            tensors += [m.weight, m.bias]
-            for b in (bn, pbn):
-                if b is not None:
-                    tensors += [b.weight, b.bias, b.running_mean, b.running_var]
-        key = self._params_key(tensors)
-        if key == self._weights_key.get(wkey) and not self.always_resync:
-            return
-        n = lib.rtpose_net_num_convs(plan.handle)
-        if n != len(convs):
-            raise _capi.RtposeError("native plan has %d convs, module has %d" % (n, len(convs)))
-        name = C.create_string_buffer(96)
-        co, ci, k = C.c_int(), C.c_int(), C.c_int()
-        stream = current_stream()
-        keep = []  # temporaries stay alive until the stream has consumed them
+    def _conv_record(self, entry):
+        nm, m, bn, pnm, pbn = entry
+        return ConvRecord(nm, m, bn, None, (pnm, pbn) if pbn is not None else None)
 
-        def dev(t):
-            t = t.detach()
-            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
-                t = t.to(device=device, dtype=torch.float32).contiguous()
-            keep.append(t)
-            return t
-        for i, (nm, m, bn, pnm, pbn) in enumerate(convs):
-            check(lib.rtpose_net_conv_info(plan.handle, i, name, 96, C.byref(co), C.byref(ci), C.byref(k)))
-            if name.value.decode() != nm or tuple(m.weight.shape) != (co.value, ci.value, k.value, k.value):
-                raise _capi.RtposeError("conv %d mismatch: native %s vs module %s" % (i, name.value, nm))
-            w, b = (m.weight, m.bias) if bn is None else fold_bn(m.weight, m.bias, bn)
-            check(lib.rtpose_net_load_conv(plan.handle, i, ptr(dev(w)), ptr(dev(b)), stream), "rtpose_net_load_conv")
-            has = lib.rtpose_net_preact_info(plan.handle, i, name, 96)
-            if has < 0 or bool(has) != (pbn is not None) or (pbn is not None and name.value.decode() != pnm):
-                raise _capi.RtposeError("pre-activation of conv %d mismatch: native %s vs module %s" % (i, name.value, pnm))
-            if pbn is not None:
-                sc, sh = bn_scale_shift(pbn)
-                if sc.numel() != ci.value:
-                    raise _capi.RtposeError("%s has %d channels, the conv reads %d" % (pnm, sc.numel(), ci.value))
-                check(lib.rtpose_net_load_preact(plan.handle, i, ptr(dev(sc)), ptr(dev(sh)), stream),
-                      "rtpose_net_load_preact")
-        torch.cuda.current_stream().synchronize()  # temporaries above may be freed
-        del keep
-        self._weights_key[wkey] = key
+    def _create(self, n, h, w, dtype, wino):
+        handle = C.c_void_p()
+        opts = _capi.HourglassOptions.make(*(self._topo + wino))
+        check(lib.rtpose_hourglass_create(n, h, w, C.byref(opts), C.byref(handle)), "rtpose_hourglass_create")
+        return handle
 
-    def _require_eval(self):
+    def _check_ready(self):
         if self.training:
             raise _capi.RtposeError(
                 "HourglassNet runs its BatchNorm layers on their running statistics only: call .eval() first (a fresh "
                 "nn.Module is in training mode; there is no training-mode forward and no CPU fallback)")
 
-    def plan_for(self, x):
-        if not x.is_cuda:
-            raise _capi.RtposeError(
-                "HourglassNet forward runs only on an MI355X (HIP) device tensor; got a %s tensor - "
-                "there is deliberately no CPU fallback" % x.device)
-        n, c, h, w = x.shape
-        if c != 3:
-            raise _capi.RtposeError("expected NCHW input with 3 channels")
-        return self.plan_for_shape(n, h, w, x.device)
-
-    def plan_for_shape(self, n, h, w, device):
-        """The executor instance for N x 3 x H x W inputs on `device` (created on first use)."""
-        self._require_eval()
-        x = _ShapeOnly(device)
-        key = (n, h, w, x.device.index, _capi.DTYPE_F32, self._wino)
-        with self._native_lock, torch.cuda.device(x.device):
-            plan = self._plans.get(key)
-            if plan is None:
-                wkey = (x.device.index, _capi.DTYPE_F32)
-                weights = self._weights.get(wkey)
-                if weights is None:
-                    probe = C.c_void_p()
-                    opts = _capi.HourglassOptions.make(*self._topo)
-                    check(lib.rtpose_hourglass_create(1, 64, 64, C.byref(opts), C.byref(probe)))
-                    wb = lib.rtpose_net_weight_bytes(probe)
-                    lib.rtpose_net_destroy(probe)
-                    weights = torch.zeros(wb // 4 + 64, dtype=torch.float32, device=x.device)
-                    self._weights[wkey] = weights
-                    self._weights_key.pop(wkey, None)
-                plan = self._build_plan(key, lambda: _Plan(n, h, w, weights, x.device, self._topo, self._wino))
-            self._sync_weights(plan, x.device)
-            check(lib.rtpose_net_finalize_weights(plan.handle, current_stream()), "rtpose_net_finalize_weights")
-        return plan
-
-    def read_output(self, plan, which):
+    def _out_channels(self, which):
         """0 / 1: score_paf / score_ht of the last stack; 2 + 2 s / 3 + 2 s: of stack s (kept only by a forward with
-        keep_intermediates).  NCHW fp32."""
-        _, _, p, h = self._topo
-        out = torch.empty((plan.shape[0], p if which % 2 == 0 else h, plan.h3, plan.w3), dtype=torch.float32,
-                          device=plan.workspace.device)
-        check(lib.rtpose_net_read_output(plan.handle, which, ptr(out), current_stream()), "rtpose_net_read_output")
-        return out
+        keep_intermediates)"""
+        return self._topo[2] if which % 2 == 0 else self._topo[3]
 
     def forward(self, x):
         """reference :162-189 - ``(score_paf, score_ht), [score_paf, score_ht]`` of the last stack, NCHW fp32."""
-        self._require_eval()
+        self._check_ready()
         if not x.is_cuda:
             self.plan_for(x)  # raises: no CPU fallback
         with torch.cuda.device(x.device):

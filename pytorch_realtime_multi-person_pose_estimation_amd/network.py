@@ -19,8 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._capi import lib, check, ptr, current_stream
-from ._native_state import NativeStateMixin, NetPlanMixin
+from ._capi import lib, check
+from ._native_state import ConvRecord, NativeStateMixin, NetPlanMixin
 
 # (cin, cout, k) tables; 'P' = MaxPool2d(2, 2, 0).  reference :69-83, :95-127
 _VGG = [(3, 64, 3), (64, 64, 3), 'P', (64, 128, 3), (128, 128, 3), 'P', (128, 256, 3),
@@ -49,52 +49,16 @@ def _sequential(table, relu_after_last):
     return nn.Sequential(*mods)
 
 
-class _Plan(object):
-    """One native executor instance (fixed N, H, W) + its workspace."""
-
-    def __init__(self, n, h, w, weights, device, dtype=_capi.DTYPE_F32, wino=(-1, -1, 0.0)):
-        handle = C.c_void_p()
-        opts = _capi.NetOptions.make(dtype, *wino)
-        check(lib.rtpose_net_create_opts(n, h, w, C.byref(opts), C.byref(handle)), "rtpose_net_create_opts")
-        self.handle = handle
-        self.shape = (n, h, w)
-        self.dtype = dtype
-        self.wino = wino
-        self.wkey = _arena_key(torch.device(device).index, dtype, wino)   # the arena it is bound to
-        ws_bytes = lib.rtpose_net_workspace_bytes(handle)
-        self.workspace = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=device)
-        check(lib.rtpose_net_bind(handle, ptr(self.workspace), ws_bytes, ptr(weights),
-                                  weights.numel() * 4, 1, current_stream()), "rtpose_net_bind")
-        self.h3 = h // 2 // 2 // 2
-        self.w3 = w // 2 // 2 // 2
-
-    def __del__(self):
-        try:
-            lib.rtpose_net_destroy(self.handle)
-        except Exception:
-            pass
-
-
-def _arena_key(index, dtype, wino):
-    """Plans of a module share the weight arena of their (device, dtype) - except the fp32 plans that force F(8,7): their
-    arena is the standard layout followed by the F(8,7) packings of the 7x7 convs, and it is kept apart."""
-    return (index, dtype, 'f87') if dtype == _capi.DTYPE_F32 and wino[1] == 8 else (index, dtype)
-
-
 _DTYPES = {'fp32': _capi.DTYPE_F32, 'bf16': _capi.DTYPE_BF16, 'bf16x3': _capi.DTYPE_BF16X3}
-
-
-class _ShapeOnly(object):
-    def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise _capi.RtposeError("rtpose_vgg plans exist only on an MI355X (HIP) device; got %s" % device)
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
 
 
 class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
     """Drop-in for the module built by reference ``get_model('vgg19')``."""
+
+    _front_name = 'rtpose_vgg'
+    _plan_stride = 8
+    _probe_hw = 8
+    _WINO_DEFAULT = (_capi.WINO_DEFAULT, _capi.WINO_DEFAULT, 0.0)   # (winograd3, winograd7, amp_limit)
 
     def __init__(self):
         super(RtposeVGG, self).__init__()
@@ -108,7 +72,7 @@ class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
         self._init_native_state()   # plans / weight arenas per (device, dtype), see _native_state.py
         self.keep_intermediates = True   # reference forward returns all 12 stage outputs
         self.compute_dtype = 'fp32'
-        self._wino = (_capi.WINO_DEFAULT, _capi.WINO_DEFAULT, 0.0)
+        self._wino = self._WINO_DEFAULT
 
     def set_winograd(self, winograd3=None, winograd7=None, amp_limit=None):
         """Arithmetic of the fp32 convs of plans created from now on (``rtpose_net_options``):
@@ -120,16 +84,7 @@ class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
         8 = F(8,7) forced: opt-in only ('auto' never chooses it), 12.5 % fewer matrix multiplies than F(6,7) for ~8x
         its error bound; such plans keep a weight arena of their own (the standard one followed by the F(8,7) packings).
         All other forms read one weight arena; results of different forms differ by rounding only."""
-        if winograd3 is None:
-            w3 = _capi.WINO_DEFAULT
-        elif winograd3 == 'auto':
-            w3 = _capi.WINO3_AUTO
-        elif winograd3 in (1, 2):        # (True == 1)
-            w3 = 1
-        elif winograd3 in (0, 4):        # (False == 0)
-            w3 = int(winograd3)
-        else:
-            raise ValueError("winograd3 must be None, False / 0, True / 1 / 2, 4 or 'auto'")
+        w3 = self._parse_winograd3(winograd3)
         if winograd7 is None:
             w7 = _capi.WINO_DEFAULT
         elif winograd7 == 'auto':
@@ -170,81 +125,27 @@ class RtposeVGG(NativeStateMixin, NetPlanMixin, nn.Module):
                     out.append(('%s.%d' % (nm, idx), m))
         return out
 
-    def _sync_weights(self, plan, device):
-        convs = self._convs()
-        wkey = plan.wkey
-        key = self._params_key([t for _, m in convs for t in (m.weight, m.bias)])
-        if key == self._weights_key.get(wkey) and not self.always_resync:
-            return
-        n = lib.rtpose_net_num_convs(plan.handle)
-        if n != len(convs):
-            raise _capi.RtposeError("native plan has %d convs, module has %d" % (n, len(convs)))
-        name = C.create_string_buffer(64)
-        co, ci, k = C.c_int(), C.c_int(), C.c_int()
-        stream = current_stream()
-        for i, (nm, m) in enumerate(convs):
-            check(lib.rtpose_net_conv_info(plan.handle, i, name, 64, C.byref(co), C.byref(ci), C.byref(k)))
-            if name.value.decode() != nm or tuple(m.weight.shape) != (co.value, ci.value, k.value, k.value):
-                raise _capi.RtposeError("conv %d mismatch: native %s vs module %s" % (i, name.value, nm))
-            w = m.weight.detach()
-            b = m.bias.detach()
-            if w.device != device or w.dtype != torch.float32 or not w.is_contiguous():
-                w = w.to(device=device, dtype=torch.float32).contiguous()
-            if b.device != device or b.dtype != torch.float32 or not b.is_contiguous():
-                b = b.to(device=device, dtype=torch.float32).contiguous()
-            check(lib.rtpose_net_load_conv(plan.handle, i, ptr(w), ptr(b), stream), "rtpose_net_load_conv")
-        torch.cuda.current_stream().synchronize()  # temporaries above may be freed
-        self._weights_key[wkey] = key
+    def _conv_record(self, entry):
+        return ConvRecord(entry[0], entry[1], None, None, None)
 
-    def _finalize(self, plan):
-        # fixes the per-layer forms of an 'auto' plan from the filters in the arena (no-op otherwise)
-        check(lib.rtpose_net_finalize_weights(plan.handle, current_stream()), "rtpose_net_finalize_weights")
+    def _create(self, n, h, w, dtype, wino):
+        handle = C.c_void_p()
+        opts = _capi.NetOptions.make(dtype, *wino)
+        check(lib.rtpose_net_create_opts(n, h, w, C.byref(opts), C.byref(handle)), "rtpose_net_create_opts")
+        return handle
 
-    def plan_for(self, x):
-        if not x.is_cuda:
-            raise _capi.RtposeError(
-                "rtpose_vgg forward runs only on an MI355X (HIP) device tensor; got a %s tensor — "
-                "there is deliberately no CPU fallback" % x.device)
-        n, c, h, w = x.shape
-        if c != 3:
-            raise _capi.RtposeError("expected NCHW input with 3 channels")
-        return self.plan_for_shape(n, h, w, x.device)
+    def _plan_options(self):
+        return _DTYPES[self.compute_dtype], getattr(self, '_wino', self._WINO_DEFAULT)   # (unpickled from before _wino)
 
-    def plan_for_shape(self, n, h, w, device):
-        """The executor instance for N x 3 x H x W inputs on `device` (created on first use);
-        for callers that fill the plan's input buffer themselves (rtpose_preprocess_u8)."""
-        x = _ShapeOnly(device)
-        dtype = _DTYPES[self.compute_dtype]
-        wino = getattr(self, '_wino', (_capi.WINO_DEFAULT, _capi.WINO_DEFAULT, 0.0))
-        key = (n, h, w, x.device.index, dtype, wino)
-        with self._native_lock, torch.cuda.device(x.device):
-            plan = self._plans.get(key)
-            if plan is None:
-                wkey = _arena_key(x.device.index, dtype, wino)
-                weights = self._weights.get(wkey)
-                if weights is None:
-                    probe = C.c_void_p()
-                    if len(wkey) == 3:      # sized by a probe plan with the same option
-                        popts = _capi.NetOptions.make(dtype, _capi.WINO_DEFAULT, 8, 0.0)
-                        check(lib.rtpose_net_create_opts(1, 8, 8, C.byref(popts), C.byref(probe)))
-                    else:
-                        check(lib.rtpose_net_create_ex(1, 8, 8, dtype, C.byref(probe)))
-                    wb = lib.rtpose_net_weight_bytes(probe)
-                    lib.rtpose_net_destroy(probe)
-                    weights = torch.zeros(wb // 4 + 64, dtype=torch.float32, device=x.device)
-                    self._weights[wkey] = weights
-                    self._weights_key.pop(wkey, None)
-                plan = self._build_plan(key, lambda: _Plan(n, h, w, weights, x.device, dtype, wino))
-            self._sync_weights(plan, x.device)
-            self._finalize(plan)
-        return plan
+    def _arena(self, index, dtype, wino):
+        """As every front - except the fp32 plans that force F(8,7): their arena is the standard layout followed by the
+        F(8,7) packings of the 7x7 convs, it is kept apart and sized by a probe plan with the same option."""
+        if dtype == _capi.DTYPE_F32 and wino[1] == 8:
+            return (index, dtype, 'f87'), (_capi.WINO_DEFAULT, 8, 0.0)
+        return (index, dtype), self._WINO_DEFAULT
 
-    def read_output(self, plan, which):
-        n = plan.shape[0]
-        c = 38 if which % 2 == 0 else 19
-        out = torch.empty((n, c, plan.h3, plan.w3), dtype=torch.float32, device=plan.workspace.device)
-        check(lib.rtpose_net_read_output(plan.handle, which, ptr(out), current_stream()), "rtpose_net_read_output")
-        return out
+    def _out_channels(self, which):
+        return 38 if which % 2 == 0 else 19
 
     def forward(self, x):
         """reference :158-198 — returns ((out6_1, out6_2), saved_for_loss[12]), NCHW fp32."""

@@ -13,9 +13,8 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._capi import lib, check, ptr, current_stream
-from ._native_state import NativeStateMixin, NetPlanMixin
-from .network import _ShapeOnly
+from ._capi import lib, check
+from ._native_state import ConvRecord, NativeStateMixin, NetPlanMixin
 
 # reference :13-49: (name, cin, cout) or 'P' = MaxPool2d(2, 2, 0); conv4_2, conv4_3_CPM, conv4_4_CPM end in a PReLU
 _VGG = [('conv1_1', 3, 64), ('conv1_2', 64, 64), 'P', ('conv2_1', 64, 128), ('conv2_2', 128, 128), 'P',
@@ -66,33 +65,13 @@ class StageBlock(nn.Module):
             + [('Mconv6', self.Mconv6)]
 
 
-class _Plan(object):
-    """One native OpenPose_Model executor instance (fixed N, H, W) + its workspace."""
-
-    def __init__(self, n, h, w, weights, device, topo, wino):
-        handle = C.c_void_p()
-        opts = _capi.OpenPoseOptions.make(*(topo + wino))
-        check(lib.rtpose_openpose_create(n, h, w, C.byref(opts), C.byref(handle)), "rtpose_openpose_create")
-        self.handle = handle
-        self.shape = (n, h, w)
-        self.dtype = _capi.DTYPE_F32
-        self.wino = wino
-        ws_bytes = lib.rtpose_net_workspace_bytes(handle)
-        self.workspace = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=device)
-        check(lib.rtpose_net_bind(handle, ptr(self.workspace), ws_bytes, ptr(weights),
-                                  weights.numel() * 4, 1, current_stream()), "rtpose_net_bind")
-        self.h3 = h // 2 // 2 // 2
-        self.w3 = w // 2 // 2 // 2
-
-    def __del__(self):
-        try:
-            lib.rtpose_net_destroy(self.handle)
-        except Exception:
-            pass
-
-
 class OpenPose_Model(NativeStateMixin, NetPlanMixin, nn.Module):
     """Drop-in for reference ``OpenPose_Model`` (lib/network/openpose.py:114).  fp32 only; runs on an MI355X."""
+
+    _front_name = 'OpenPose_Model'
+    _plan_stride = 8
+    _probe_hw = 8
+    _WINO_DEFAULT = (_capi.WINO_DEFAULT, 0.0)   # (winograd3, amp_limit)
 
     def __init__(self, l2_stages=4, l1_stages=2, paf_out_channels=14, heat_out_channels=9):
         super(OpenPose_Model, self).__init__()
@@ -116,7 +95,7 @@ class OpenPose_Model(NativeStateMixin, NetPlanMixin, nn.Module):
         self._initialize_weights_norm()
         self._init_native_state()
         self.compute_dtype = 'fp32'
-        self._wino = (_capi.WINO_DEFAULT, 0.0)
+        self._wino = self._WINO_DEFAULT
 
     def _initialize_weights_norm(self):
         # reference :179-187: N(0, 0.01) weights and slopes, bias 0.001
@@ -150,16 +129,7 @@ class OpenPose_Model(NativeStateMixin, NetPlanMixin, nn.Module):
         """Arithmetic of the 3x3 convs of plans created from now on, as ``RtposeVGG.set_winograd``: None = library
         default ('auto'), False / 0 = direct, True / 1 / 2 = F(2x2,3x3), 4 = F(4x4,3x3) forced, 'auto' = per layer
         F(4x4,3x3) if its amplification estimate is <= ``amp_limit`` (default 256), else F(2x2,3x3)."""
-        if winograd3 is None:
-            w3 = _capi.WINO_DEFAULT
-        elif winograd3 == 'auto':
-            w3 = _capi.WINO3_AUTO
-        elif winograd3 in (1, 2):
-            w3 = 1
-        elif winograd3 in (0, 4):
-            w3 = int(winograd3)
-        else:
-            raise ValueError("winograd3 must be None, False / 0, True / 1 / 2, 4 or 'auto'")
+        w3 = self._parse_winograd3(winograd3)
         self._wino = (w3, float(amp_limit or 0.0))
         return self
 
@@ -188,80 +158,20 @@ class OpenPose_Model(NativeStateMixin, NetPlanMixin, nn.Module):
                 out.append((pre + 'Mconv7', stage.Mconv7, None, None))
         return out
 
-    def _sync_weights(self, plan, device):
-        convs = self._convs()
-        wkey = (device.index, plan.dtype)
-        key = self._params_key([t for _, m, _, pm in convs for t in (m.weight, m.bias) + ((pm.weight,) if pm else ())])
-        if key == self._weights_key.get(wkey) and not self.always_resync:
-            return
-        n = lib.rtpose_net_num_convs(plan.handle)
-        if n != len(convs):
-            raise _capi.RtposeError("native plan has %d convs, module has %d" % (n, len(convs)))
-        name = C.create_string_buffer(96)
-        co, ci, k = C.c_int(), C.c_int(), C.c_int()
-        stream = current_stream()
+    def _conv_record(self, entry):
+        nm, m, pnm, pm = entry
+        return ConvRecord(nm, m, None, (pnm, pm) if pm is not None else None, None)
 
-        def dev(t):
-            t = t.detach()
-            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
-                t = t.to(device=device, dtype=torch.float32).contiguous()
-            return t
-        for i, (nm, m, pnm, pm) in enumerate(convs):
-            check(lib.rtpose_net_conv_info(plan.handle, i, name, 96, C.byref(co), C.byref(ci), C.byref(k)))
-            if name.value.decode() != nm or tuple(m.weight.shape) != (co.value, ci.value, k.value, k.value):
-                raise _capi.RtposeError("conv %d mismatch: native %s vs module %s" % (i, name.value, nm))
-            check(lib.rtpose_net_load_conv(plan.handle, i, ptr(dev(m.weight)), ptr(dev(m.bias)), stream),
-                  "rtpose_net_load_conv")
-            has = lib.rtpose_net_prelu_info(plan.handle, i, name, 96)
-            if has < 0 or bool(has) != (pm is not None) or (pm is not None and name.value.decode() != pnm):
-                raise _capi.RtposeError("PReLU of conv %d mismatch: native %s vs module %s" % (i, name.value, pnm))
-            if pm is not None:
-                if pm.weight.numel() != co.value:
-                    raise _capi.RtposeError("%s has %d slopes, the conv %d channels" % (pnm, pm.weight.numel(), co.value))
-                check(lib.rtpose_net_load_prelu(plan.handle, i, ptr(dev(pm.weight)), stream), "rtpose_net_load_prelu")
-        torch.cuda.current_stream().synchronize()  # temporaries above may be freed
-        self._weights_key[wkey] = key
+    def _create(self, n, h, w, dtype, wino):
+        handle = C.c_void_p()
+        opts = _capi.OpenPoseOptions.make(*(self._topo + wino))
+        check(lib.rtpose_openpose_create(n, h, w, C.byref(opts), C.byref(handle)), "rtpose_openpose_create")
+        return handle
 
-    def plan_for(self, x):
-        if not x.is_cuda:
-            raise _capi.RtposeError(
-                "OpenPose_Model forward runs only on an MI355X (HIP) device tensor; got a %s tensor - "
-                "there is deliberately no CPU fallback" % x.device)
-        n, c, h, w = x.shape
-        if c != 3:
-            raise _capi.RtposeError("expected NCHW input with 3 channels")
-        return self.plan_for_shape(n, h, w, x.device)
-
-    def plan_for_shape(self, n, h, w, device):
-        """The executor instance for N x 3 x H x W inputs on `device` (created on first use)."""
-        x = _ShapeOnly(device)
-        key = (n, h, w, x.device.index, _capi.DTYPE_F32, self._wino)
-        with self._native_lock, torch.cuda.device(x.device):
-            plan = self._plans.get(key)
-            if plan is None:
-                wkey = (x.device.index, _capi.DTYPE_F32)
-                weights = self._weights.get(wkey)
-                if weights is None:
-                    probe = C.c_void_p()
-                    opts = _capi.OpenPoseOptions.make(*self._topo)
-                    check(lib.rtpose_openpose_create(1, 8, 8, C.byref(opts), C.byref(probe)))
-                    wb = lib.rtpose_net_weight_bytes(probe)
-                    lib.rtpose_net_destroy(probe)
-                    weights = torch.zeros(wb // 4 + 64, dtype=torch.float32, device=x.device)
-                    self._weights[wkey] = weights
-                    self._weights_key.pop(wkey, None)
-                plan = self._build_plan(key, lambda: _Plan(n, h, w, weights, x.device, self._topo, self._wino))
-            self._sync_weights(plan, x.device)
-            check(lib.rtpose_net_finalize_weights(plan.handle, current_stream()), "rtpose_net_finalize_weights")
-        return plan
-
-    def read_output(self, plan, which):
-        """saved_for_loss flattened: 0 .. l2_stages - 1 the PAF maps, then the heat maps (NCHW fp32)."""
+    def _out_channels(self, which):
+        """saved_for_loss flattened: 0 .. l2_stages - 1 the PAF maps, then the heat maps"""
         l2, _, p, h = self._topo
-        out = torch.empty((plan.shape[0], p if which < l2 else h, plan.h3, plan.w3), dtype=torch.float32,
-                          device=plan.workspace.device)
-        check(lib.rtpose_net_read_output(plan.handle, which, ptr(out), current_stream()), "rtpose_net_read_output")
-        return out
+        return p if which < l2 else h
 
     def forward(self, x):
         """reference :160-177 - ``[(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]``, NCHW fp32."""

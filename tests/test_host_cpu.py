@@ -368,7 +368,7 @@ def test_native_state_is_per_device_and_invalidates(pkg, monkeypatch):
     packs = []
 
     class FakePlan(object):
-        def __init__(self, n, h, w, weights, device, dtype=0, wino=None):
+        def __init__(self, handle, n, h, w, weights, device, dtype, wino, wkey, stride):
             self.shape, self.dtype, self.weights = (n, h, w), dtype, weights
             self.workspace = torch.empty(1 << 20, dtype=torch.float32)
             self.handle = None
@@ -382,10 +382,10 @@ def test_native_state_is_per_device_and_invalidates(pkg, monkeypatch):
 
         def __hash__(self):
             return self.index
-    monkeypatch.setattr(net, "_Plan", FakePlan)
-    monkeypatch.setattr(net, "_ShapeOnly", lambda d: type("S", (), {"device": d})())
+    monkeypatch.setattr(ns, "NetPlan", FakePlan)
+    monkeypatch.setattr(ns.NetPlanMixin, "_resolve_device", lambda self, d: d)
     monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
-    monkeypatch.setattr(net.lib, "rtpose_net_create_ex", lambda *a: 0)
+    monkeypatch.setattr(net.lib, "rtpose_net_create_opts", lambda *a: 0)
     monkeypatch.setattr(net.lib, "rtpose_net_weight_bytes", lambda p: 1024)
     monkeypatch.setattr(net.lib, "rtpose_net_destroy", lambda p: None)
     monkeypatch.setattr(type(net.get_model('vgg19')), "_finalize", lambda self, plan: None)
@@ -559,3 +559,167 @@ def test_oks_known_answer_ignore_rules_and_max_dets(pkg):
     many = [_det(g1, 0.5 + 0.01 * i, dx=3000.0 + 50 * i) for i in range(20)] + [_det(g1, 0.4)]
     assert oe.evaluate([g1], many)["AP"] == 0.0
     assert abs(oe.evaluate([g1], many[1:])["AP"] - 1.0 / 20.0) < 1e-9   # now 20th of 20: precision 1/20 at recall 1
+
+
+def _plan_topology_of(sd):
+    """What a native plan would report for a module with this state_dict, from its keys and shapes alone:
+    [[conv prefix, filter shape, BatchNorm prefix folded behind it, PReLU prefix, pre-activation BatchNorm prefix]] in
+    state_dict order (None where there is none).  A PReLU belongs to the conv listed just before it; `bn1` of a block
+    is the pre-activation of the block's conv1, `bnK` (and the stem's bn1, and `fc.S.1`) is folded behind the conv
+    that precedes it."""
+    prefixes = list(dict.fromkeys(k.rsplit('.', 1)[0] for k in sd))
+    convs = [[p, tuple(sd[p + '.weight'].shape), None, None, None] for p in prefixes if sd[p + '.weight'].dim() == 4]
+    by_name = {c[0]: c for c in convs}
+    last = None
+    for p in prefixes:
+        parent, _, leaf = p.rpartition('.')
+        if p in by_name:
+            last = by_name[p]
+        elif p + '.running_mean' not in sd:
+            last[3] = p                                                   # a PReLU
+        elif parent and leaf == 'bn1':
+            by_name[parent + '.conv1'][4] = p
+        elif leaf.startswith('bn'):
+            by_name[(parent + '.' if parent else '') + 'conv%d' % (int(leaf[2:]) - (1 if parent else 0))][2] = p
+        else:
+            by_name[parent + '.%d' % (int(leaf) - 1)][2] = p
+    return convs
+
+
+class _RecordingNetLib(object):
+    """The part of the C ABI that NetPlanMixin._sync_weights drives, answering from `topo` (_plan_topology_of) and
+    keeping what every call got: the floats behind the pointers of the load_* calls included."""
+
+    def __init__(self, topo):
+        self.topo, self.calls = topo, []
+
+    @staticmethod
+    def _floats(p, n):
+        import ctypes as C
+        import numpy as np
+        return np.ctypeslib.as_array((C.c_float * n).from_address(p.value)).copy()
+
+    def rtpose_net_num_convs(self, handle):
+        self.calls.append(('num_convs',))
+        return len(self.topo)
+
+    def rtpose_net_conv_info(self, handle, i, name, cap, co, ci, k):
+        self.calls.append(('conv_info', i))
+        name.value = self.topo[i][0].encode()
+        co._obj.value, ci._obj.value, k._obj.value = self.topo[i][1][:3]
+        return 0
+
+    def _extra_info(self, what, col, i, name):
+        self.calls.append((what, i))
+        name.value = (self.topo[i][col] or '').encode()
+        return 1 if self.topo[i][col] else 0
+
+    def rtpose_net_prelu_info(self, handle, i, name, cap):
+        return self._extra_info('prelu_info', 3, i, name)
+
+    def rtpose_net_preact_info(self, handle, i, name, cap):
+        return self._extra_info('preact_info', 4, i, name)
+
+    def rtpose_net_load_conv(self, handle, i, w, b, stream):
+        co, ci, k, _ = self.topo[i][1]
+        self.calls.append(('load_conv', i, self._floats(w, co * ci * k * k), self._floats(b, co)))
+        return 0
+
+    def rtpose_net_load_prelu(self, handle, i, slope, stream):
+        self.calls.append(('load_prelu', i, self._floats(slope, self.topo[i][1][0])))
+        return 0
+
+    def rtpose_net_load_preact(self, handle, i, scale, shift, stream):
+        ci = self.topo[i][1][1]
+        self.calls.append(('load_preact', i, self._floats(scale, ci), self._floats(shift, ci)))
+        return 0
+
+
+@pytest.mark.parametrize("front", ("rtpose_vgg", "openpose", "hourglass"))
+def test_shared_sync_weights_loads_what_the_state_dict_says(pkg, monkeypatch, front):
+    """NetPlanMixin._sync_weights of each front against a recording C ABI that knows the module by its state_dict only:
+    one load_conv per conv index, in order, with the state_dict's floats - or the float64 fold of the BatchNorm behind
+    the conv, computed here; each PReLU / pre-activation loaded once, after its conv; nothing freed before the stream
+    synchronise; the parameter key stored (a second call touches nothing); the three disagreements refused; and the refusals of a
+    host device, which name the front."""
+    import types
+    import weakref
+    import numpy as np
+    import torch
+    ns = importlib.import_module(PKG_NAME + "._native_state")
+    capi = importlib.import_module(PKG_NAME + "._capi")
+    if front == "rtpose_vgg":
+        m = pkg.get_model('vgg19')
+    elif front == "openpose":
+        m = importlib.import_module(PKG_NAME + ".openpose").OpenPose_Model(2, 2, 3, 2)
+    else:
+        m = importlib.import_module(PKG_NAME + ".hourglass").hg(num_stacks=1, num_blocks=1, paf_classes=4, ht_classes=3)
+    # the shared refusals name the front they speak for; the hourglass refuses training mode before it looks at the device
+    name = {"rtpose_vgg": "rtpose_vgg", "openpose": "OpenPose_Model", "hourglass": "HourglassNet"}[front]
+    if front == "hourglass":
+        with pytest.raises(capi.RtposeError, match=r"\.eval\(\)"):
+            m.plan_for_shape(1, 64, 64, 'cpu')
+        m.eval()
+    with pytest.raises(capi.RtposeError, match="^%s plans exist only on .* got cpu .*no CPU fallback" % name):
+        m.plan_for_shape(1, 64, 64, 'cpu')
+    with pytest.raises(capi.RtposeError, match="^%s forward runs only on .*no CPU fallback" % name):
+        m.plan_for(torch.zeros(1, 3, 64, 64))
+    g = torch.Generator().manual_seed(5)
+    m.load_state_dict({k: (torch.rand(v.shape, generator=g) + 0.5 if k.endswith(('running_var', '.weight')) and v.dim() == 1
+                           else torch.randn(v.shape, generator=g) if v.is_floating_point() else v)
+                       for k, v in m.state_dict().items()})
+    sd = {k: v.clone() for k, v in m.state_dict().items()}
+    topo = _plan_topology_of(sd)
+    assert len(topo) == len(m._convs()) and (front != "openpose" or sum(1 for t in topo if t[3]) == 3 + 4 * 16)
+    assert front != "hourglass" or (sum(1 for t in topo if t[4]), sum(1 for t in topo if t[2])) == (17, 36)
+    syncs, handed = [], []
+    real_ptr = ns.ptr
+    monkeypatch.setattr(ns, "ptr", lambda t: (handed.append(weakref.ref(t)), real_ptr(t))[1])
+    monkeypatch.setattr(ns, "current_stream", lambda: None)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: types.SimpleNamespace(
+        synchronize=lambda: syncs.append((len(fake.calls), all(r() is not None for r in handed)))))
+    fake = _RecordingNetLib(topo)
+    monkeypatch.setattr(ns, "lib", fake)
+    plan = types.SimpleNamespace(handle=None, wkey=('cpu', 0), dtype=0)
+    cpu = torch.device('cpu')
+    m._sync_weights(plan, cpu)
+
+    def affine64(p):
+        bn = m.get_submodule(p)
+        scale = sd[p + '.weight'].numpy().astype(np.float64) / np.sqrt(sd[p + '.running_var'].numpy().astype(np.float64) + bn.eps)
+        return scale, sd[p + '.bias'].numpy().astype(np.float64) - sd[p + '.running_mean'].numpy().astype(np.float64) * scale
+    loads = [c for c in fake.calls if c[0].startswith('load_')]
+    want = []
+    for i, (nm, shape, bn, prelu, preact) in enumerate(topo):
+        w, b = sd[nm + '.weight'].numpy(), sd[nm + '.bias'].numpy()
+        if bn:
+            scale, shift = affine64(bn)
+            w = (w.astype(np.float64) * scale[:, None, None, None]).astype(np.float32)
+            b = (b.astype(np.float64) * scale + shift).astype(np.float32)
+        want.append(('load_conv', i, w.ravel(), b))
+        if prelu:
+            want.append(('load_prelu', i, sd[prelu + '.weight'].numpy()))
+        if preact:
+            want.append(('load_preact', i) + tuple(v.astype(np.float32) for v in affine64(preact)))
+    assert [c[:2] for c in loads] == [c[:2] for c in want]
+    for got, exp in zip(loads, want):
+        for a, e in zip(got[2:], exp[2:]):
+            assert a.dtype == np.float32 and np.array_equal(a.view(np.uint32), e.view(np.uint32)), got[:2]
+    # one synchronise, after the last call, with every tensor whose address a load_* got still referenced
+    assert syncs == [(len(fake.calls), True)] and len(handed) == sum(len(c) - 2 for c in want)
+    stored = m._weights_key[plan.wkey]
+    assert list(m._weights_key) == [('cpu', 0)] and stored[0] == m._weights_epoch[0]
+    n_calls = len(fake.calls)
+    m._sync_weights(plan, cpu)
+    assert len(fake.calls) == n_calls and len(syncs) == 1   # packed from just these parameters: no C call at all
+    # the plan and the module disagree: a conv's name, a conv's shape, a PReLU the module does not have
+    plain = next(i for i, t in enumerate(topo) if not t[3])
+    co, ci, k, _ = topo[1][1]
+    for i, col, value in ((1, 0, topo[1][0] + 'x'), (1, 1, (co, ci + 1, k, k)), (plain, 3, topo[plain][0] + '.prelu')):
+        bad = [list(t) for t in topo]
+        bad[i][col] = value
+        monkeypatch.setattr(ns, "lib", _RecordingNetLib(bad))
+        m.invalidate_weights()
+        with pytest.raises(capi.RtposeError, match="mismatch"):
+            m._sync_weights(plan, cpu)
+        assert m._weights_key[plan.wkey] is stored          # still says what the arena was last packed from

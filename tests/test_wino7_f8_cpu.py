@@ -82,9 +82,10 @@ def _plan_sizes(capi, w7):
         lib.rtpose_net_destroy(h)
 
 
-def test_host_only_plan_with_the_form_forced(capi, monkeypatch):
+def test_host_only_plan_with_the_form_forced(pkg, capi, monkeypatch):
     """Same 92 convs and launch list; the arena of a winograd7 = 8 plan is the standard one plus the F(8,7) packings of
-    the fifty 7x7 convs; the default plan's byte count is what it is without the option in the same process."""
+    the fifty 7x7 convs; the default plan's byte count is what it is without the option in the same process; the module
+    sizes the arena of a key alike for every option set that maps to the key."""
     monkeypatch.delenv("RTPOSE_WINOGRAD7_M", raising=False)
     before = _plan_sizes(capi, capi.WINO_DEFAULT)
     forced = _plan_sizes(capi, 8)
@@ -97,6 +98,22 @@ def test_host_only_plan_with_the_form_forced(capi, monkeypatch):
     assert forced[2] == before[2] + 4 * extra
     # F(6,7) and F(4,7) plans read the standard arena
     assert _plan_sizes(capi, 6)[2] == before[2] and _plan_sizes(capi, 4)[2] == before[2]
+    # RtposeVGG allocates an arena at the size its probe plan reports: one size per arena key over every set_winograd
+    # that maps to the key, which is what a real plan with those options asks rtpose_net_bind for; F(8,7)'s is larger
+    m = pkg.get_model('vgg19')
+    sizes = {}
+    for w3 in (None, 0, 1, 4, 'auto'):
+        for w7 in (None, 0, 4, 6, 'auto', 8):
+            dtype, wino = m.set_winograd(winograd3=w3, winograd7=w7)._plan_options()
+            key, probe_wino = m._arena(0, dtype, wino)
+            assert key == ((0, capi.DTYPE_F32, 'f87') if w7 == 8 else (0, capi.DTYPE_F32))
+            sizes.setdefault(key, set()).add(m._arena_bytes(dtype, probe_wino))
+            h = m._create(2, 64, 72, dtype, wino)
+            try:
+                assert capi.lib.rtpose_net_weight_bytes(h) == m._arena_bytes(dtype, probe_wino), (w3, w7)
+            finally:
+                capi.lib.rtpose_net_destroy(h)
+    assert sizes == {(0, capi.DTYPE_F32): {before[2]}, (0, capi.DTYPE_F32, 'f87'): {forced[2]}}
     # the environment's switch forces the form for default-option plans (what lets bench.py run it unchanged)
     monkeypatch.setenv("RTPOSE_WINOGRAD7_M", "8")
     assert _plan_sizes(capi, capi.WINO_DEFAULT) == forced
