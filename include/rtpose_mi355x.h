@@ -164,6 +164,8 @@ int rtpose_conv2d(const rtpose_conv_desc* d, int ngroups, int N, int H, int W,
  * dense NCHW fp32 (`x_nchw`), or, with x_nchw = NULL, a layout buffer with >= 3 channels per pixel
  * (`x_layout` / `lx`: the plan's NHWC8 input written by rtpose_preprocess_u8) - and writes 64 channels
  * into `out` / `lout`: no NCHW -> NHWC conversion pass, no padding of the 3 input channels to 8.
+ * The three channels are a slice of the pixel like any other: lx->choff + 3 > lx->cstride is refused
+ * (RTPOSE_E_INVAL) by this launcher, by rtpose_conv_first_planes and by rtpose_conv_first_bf16.
  * `w_packed` (rtpose_conv_first_packed_floats() floats) from rtpose_pack_conv_first(w [64,3,3,3], bias [64]). */
 size_t rtpose_conv_first_packed_floats(void);
 int rtpose_pack_conv_first(const float* w_oihw, const float* bias, float* w_packed, void* stream);

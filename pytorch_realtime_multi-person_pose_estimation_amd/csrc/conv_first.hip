@@ -341,6 +341,7 @@ int conv_first_launch(const float* x_nchw, const float* x_lay, const rtpose_layo
     return fail(RTPOSE_E_INVAL, "conv_first: bf16 output is pixel-major with 16-byte aligned slices");
   if ((!x_nchw && (!x_lay || !lx)) || !wp || !out || !lo || N <= 0 || H <= 0 || W <= 0 || out_plane_pixels < 0)
     return fail(RTPOSE_E_INVAL, "conv_first: bad arguments");
+  if (!x_nchw && !slice_inside(*lx, 3)) return fail(RTPOSE_E_INVAL, "conv_first: input slice exceeds cstride");
   if (out_plane_pixels) {
     if ((lo->choff % 8) || (size_t)out_plane_pixels < rtpose_layout_pixels(lo, N, H, W))
       return fail(RTPOSE_E_INVAL, "conv_first: channel planes start at a multiple of 8 channels and hold the layout's pixels");
