@@ -17,98 +17,20 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_driver as cd
+
 pytestmark = pytest.mark.gpu
-
-
-def _rb(t):
-    return t.to(torch.bfloat16).to(torch.float32)
 
 
 def _run_conv_bf16(capi, dev, n, h, w, cin, cout, k, relu, pool, pad_in, pad_out, seed, groups=1,
                    cin_pad=None, out_f32=False, aligned=False, lead_extra=0):
-    lib, Layout = capi.lib, capi.Layout
-    g = torch.Generator().manual_seed(seed)
-    x = _rb(torch.randn(n, cin, h, w, generator=g))
-    cin_p = cin_pad or ((cin + 15) // 16 * 16)
-    ws, bs, refs = [], [], []
-    for gi in range(groups):
-        wt = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
-        b = torch.randn(cout, generator=g) * 0.1
-        y = F.conv2d(x.double(), _rb(wt).double(), b.double(), padding=k // 2).float()
-        if relu:
-            y = F.relu(y)
-        if pool:
-            y = F.max_pool2d(y, 2, 2, 0)
-        ws.append(wt.to(dev))
-        bs.append(b.to(dev))
-        refs.append(y)
-    stream = capi.current_stream()
-    lin = Layout.padded(cin_p, h, w, pad_in)
-    lin.lead += lead_extra  # (a slice far into a large buffer: byte offsets past 2^31)
-    npx = lib.rtpose_layout_pixels(C.byref(lin), n, h, w)
-    xin = torch.zeros(npx * cin_p, device=dev, dtype=torch.bfloat16)
-    xd = x.to(dev)
-    capi.check(lib.rtpose_nchw_to_layout_bf16(capi.ptr(xd), capi.ptr(xin), C.byref(lin), cin, cin_p, n, h, w,
-                                              stream))
-    ho, wo = (h // 2, w // 2) if pool else (h, w)
-    # odd stride + channel offsets: exercises slices (scalar stores); aligned: 16-byte aligned slices, the layout the
-    # network uses - full N tiles then take the 16-byte-store epilogues (transposed product / LDS slabs with a fused pool)
-    cstride_out = cout * groups + (16 if aligned else 3)
-    ch0 = 8 if aligned else 1
-    descs = (capi.ConvDesc * groups)()
-    outs, keep = [], []
-    lout_full = Layout.padded(cstride_out, ho, wo, pad_out)
-    odt = torch.float32 if out_f32 else torch.bfloat16
-    obuf = torch.zeros(lib.rtpose_layout_pixels(C.byref(lout_full), n, ho, wo) * cstride_out, device=dev,
-                       dtype=odt)
-    for gi in range(groups):
-        wp = torch.zeros(lib.rtpose_packed_weight_bytes_bf16(cout, cin_p, k) // 2, device=dev,
-                         dtype=torch.bfloat16)
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=dev)
-        capi.check(lib.rtpose_pack_conv_weights_bf16(capi.ptr(ws[gi]), capi.ptr(bs[gi]), cout, cin, k, None,
-                                                     cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        keep += [wp, bp]
-        d = descs[gi]
-        d.inp, d.w_packed, d.bias_packed, d.out = xin.data_ptr(), wp.data_ptr(), bp.data_ptr(), obuf.data_ptr()
-        d.lin = lin
-        d.lout = Layout.padded(cstride_out, ho, wo, pad_out, choff=gi * cout + ch0)
-        d.cin, d.cout, d.k, d.relu, d.pool = cin_p, cout, k, int(relu), int(pool)
-    capi.check(lib.rtpose_conv2d_bf16(descs, groups, n, h, w, int(out_f32), stream), "rtpose_conv2d_bf16")
-    for gi in range(groups):
-        o = torch.empty(n, cout, ho, wo, device=dev)
-        lo = Layout.padded(cstride_out, ho, wo, pad_out, choff=gi * cout + ch0)
-        if out_f32:
-            capi.check(lib.rtpose_layout_to_nchw(capi.ptr(obuf), C.byref(lo), capi.ptr(o), cout, n, ho, wo, stream))
-        else:
-            dense = torch.empty(n, ho, wo, cout, device=dev)
-            ld = Layout.dense(cout, ho, wo)
-            capi.check(lib.rtpose_layout_bf16_to_f32(capi.ptr(obuf), C.byref(lo), capi.ptr(dense), C.byref(ld),
-                                                     cout, n, ho, wo, stream))
-            o = dense.permute(0, 3, 1, 2).contiguous()
-        outs.append(o.cpu())
-    torch.cuda.synchronize()
-    total = obuf.float().abs().sum().item()
-    inner = sum(o.abs().sum().item() for o in outs)
-    assert abs(total - inner) <= 1e-3 * max(1.0, inner), "conv wrote outside its slice / into the gaps"
-    return outs, refs
-
-
-def _check(out, ref, out_f32):
-    scale = max(1.0, ref.abs().max().item())
-    if out_f32:
-        err = (out - ref).abs().max().item()
-        assert err <= 2e-5 * scale, "fp32-out max abs err %g (scale %g)" % (err, scale)
-    else:
-        # within one bf16 ulp of the rounded reference (an fp32 sum that differs in the last
-        # bits may round the other way); 2^-7 relative + a denormal-free floor
-        rr = _rb(ref)
-        err = (out - rr).abs()
-        bound = rr.abs() * 2.0 ** -7 + 1e-6 * scale
-        bad = (err > bound).sum().item()
-        assert bad == 0, "%d outputs further than 1 bf16 ulp from the reference (max err %g)" % (
-            bad, err.max().item())
-        exact = (out == rr).float().mean().item()
-        assert exact > 0.98, "only %.3f of the outputs equal the RNE-rounded reference" % exact
+    """(outputs, references: conv2d of the rounded operands in double) per branch.  The output slices sit at an odd stride +
+    channel offsets (scalar stores), or `aligned`: 16-byte aligned slices, the layout the network uses - full N tiles then take
+    the 16-byte-store epilogues (transposed product / LDS slabs with a fused pool).  lead_extra: a slice far into a large
+    buffer (byte offsets past 2^31)."""
+    P = cd.problem(cd.Form("bf16", k, None, out_f32), n, h, w, cin, cout, relu, pool, 0, groups, seed, cin_pad=cin_pad)
+    outs = cd.run(capi, dev, P, cd.ALIGNED if aligned else cd.ODD, pad_in, pad_out, lead_extra=lead_extra)
+    return outs, [r.float() for r in P.refs]
 
 
 CASES = [
@@ -135,7 +57,7 @@ def test_conv_bf16_matches_emulation(capi, cuda, case):
     src_cin = 3 if (cin == 16 and h == 72) else (185 if cin == 192 else cin)
     outs, refs = _run_conv_bf16(capi, cuda, n, h, w, src_cin, cout, k, relu, pool, pin, pout,
                                 seed=hash(case) % 1000, cin_pad=cin)
-    _check(outs[0], refs[0], False)
+    cd.check_bf16(outs[0], refs[0], False)
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[3], CASES[6]])
@@ -143,14 +65,14 @@ def test_conv_bf16_fp32_output(capi, cuda, case):
     n, h, w, cin, cout, k, relu, pool, pin, pout = case
     outs, refs = _run_conv_bf16(capi, cuda, n, h, w, cin, cout, k, relu, pool, pin, pout, seed=11, cin_pad=cin,
                                 out_f32=True)
-    _check(outs[0], refs[0], True)
+    cd.check_bf16(outs[0], refs[0], True)
 
 
 def test_conv_bf16_grouped_and_tail(capi, cuda):
     # two branches in one grid; 5*46*46 pixels = 83 strips: exercises the half-tile tail path
     outs, refs = _run_conv_bf16(capi, cuda, 5, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=7, groups=2)
     for o, r in zip(outs, refs):
-        _check(o, r, False)
+        cd.check_bf16(o, r, False)
 
 
 ALIGNED_CASES = [
@@ -175,7 +97,7 @@ def test_conv_bf16_aligned_slices_take_the_16_byte_store_epilogues(capi, cuda, c
     outs, refs = _run_conv_bf16(capi, cuda, n, h, w, cin, cout, k, relu, pool, pin, pout, seed=31 + k, groups=groups,
                                 aligned=True)
     for o, r in zip(outs, refs):
-        _check(o, r, False)
+        cd.check_bf16(o, r, False)
 
 
 @pytest.mark.parametrize("shape,src", [((2, 64, 72), "nchw"), ((1, 37, 45), "nchw"), ((1, 37, 45), "layout"),
@@ -191,7 +113,7 @@ def test_first_layer_bf16_kernel_matches_the_emulation(capi, cuda, shape, src):
     x = torch.rand(n, 3, h, w, generator=g) - 0.5                      # NOT pre-rounded: the kernel rounds
     wd = torch.randn(64, 3, 3, 3, generator=g) * (2.0 / 27) ** 0.5
     bd = torch.randn(64, generator=g) * 0.1
-    ref = F.relu(F.conv2d(_rb(x).double(), _rb(wd).double(), bd.double(), padding=1).float())
+    ref = F.relu(F.conv2d(cd.rb(x).double(), cd.rb(wd).double(), bd.double(), padding=1).float())
     stream = capi.current_stream()
     xd, wdd, bdd = x.to(cuda), wd.to(cuda), bd.to(cuda)
     wp = torch.zeros(lib.rtpose_conv_first_packed_floats(), device=cuda)
@@ -213,7 +135,7 @@ def test_first_layer_bf16_kernel_matches_the_emulation(capi, cuda, shape, src):
     capi.check(lib.rtpose_layout_bf16_to_f32(capi.ptr(obuf), C.byref(lo), capi.ptr(dense), C.byref(ld), 64, n, h, w, stream))
     torch.cuda.synchronize()
     out = dense.permute(0, 3, 1, 2).contiguous().cpu()
-    _check(out, ref, False)
+    cd.check_bf16(out, ref, False)
     total, inner = obuf.float().abs().sum().item(), out.abs().sum().item()
     assert abs(total - inner) <= 1e-3 * max(1.0, inner), "wrote outside its slice / into the gaps"
     if (n, h, w) == (2, 64, 72):                                       # the launch it replaces in the plan
@@ -236,7 +158,7 @@ def test_conv1x1_pair_bf16_matches_the_two_launch_contract(capi, cuda, case):
     n, h, w, mid, cout2, out_f32 = case
     g = torch.Generator().manual_seed(mid + cout2)
     stream = capi.current_stream()
-    x = _rb(torch.randn(n, 128, h, w, generator=g))
+    x = cd.rb(torch.randn(n, 128, h, w, generator=g))
     lin = Layout.padded(128 + 8, h, w, 0, choff=8)
     npx = lib.rtpose_layout_pixels(C.byref(lin), n, h, w)
     xin = torch.zeros(npx * (128 + 8), device=cuda, dtype=torch.bfloat16)
@@ -255,18 +177,10 @@ def test_conv1x1_pair_bf16_matches_the_two_launch_contract(capi, cuda, case):
         b1 = torch.randn(mid, generator=g) * 0.1
         w2 = torch.randn(cout2, mid, 1, 1, generator=g) * (1.0 / mid) ** 0.5
         b2 = torch.randn(cout2, generator=g) * 0.1
-        t = _rb(F.relu(F.conv2d(x.double(), _rb(w1).double(), b1.double()).float()))
-        refs.append(F.conv2d(t.double(), _rb(w2).double(), b2.double()).float())
+        t = cd.rb(F.relu(F.conv2d(x.double(), cd.rb(w1).double(), b1.double()).float()))
+        refs.append(F.conv2d(t.double(), cd.rb(w2).double(), b2.double()).float())
         tb = torch.zeros(lib.rtpose_layout_pixels(C.byref(tbuf_l), n, h, w) * mid, device=cuda, dtype=torch.bfloat16)
-        packs = []
-        for (wt, bs, co, ci) in ((w1, b1, mid, 128), (w2, b2, cout2, mid)):
-            wp = torch.zeros(lib.rtpose_packed_weight_bytes_bf16(co, ci, 1) // 2, device=cuda, dtype=torch.bfloat16)
-            bp = torch.zeros(lib.rtpose_packed_bias_floats(co), device=cuda)
-            wd, bdev = wt.to(cuda), bs.to(cuda)      # (kept alive: a temporary's block is re-used before the pack kernel runs)
-            capi.check(lib.rtpose_pack_conv_weights_bf16(capi.ptr(wd), capi.ptr(bdev), co, ci, 1, None, ci,
-                                                         capi.ptr(wp), capi.ptr(bp), stream))
-            packs.append((wp, bp))
-            keep += [wd, bdev]
+        packs = [cd.pack(capi, cuda, cd.Form("bf16", 1), wt, bs, ci) for (wt, bs, ci) in ((w1, b1, 128), (w2, b2, mid))]
         keep += packs + [tb]
         a, b = d1[gi], d2[gi]
         a.inp, a.w_packed, a.bias_packed, a.out = xin.data_ptr(), packs[0][0].data_ptr(), packs[0][1].data_ptr(), tb.data_ptr()
@@ -304,7 +218,7 @@ def test_conv1x1_pair_bf16_matches_the_two_launch_contract(capi, cuda, case):
         if out_f32:
             assert (o - r).abs().max().item() <= 2e-3 * scale and (o - p_).abs().max().item() <= 2e-3 * scale
         else:
-            rr = _rb(r)
+            rr = cd.rb(r)
             for other in (rr, p_):
                 assert ((o - other).abs() <= other.abs() * 2.0 ** -6 + 2e-3 * scale).all()
             assert (o == rr).float().mean().item() > 0.97
@@ -340,7 +254,7 @@ def test_conv3x3_of_64_input_channels_takes_its_own_kernel_and_keeps_the_contrac
     d[0].cin, d[0].cout, d[0].k, d[0].relu, d[0].pool = 64, cout, 3, relu, pool
     assert lib.rtpose_conv3x3_c64_bf16_fits(d, 1, n, h, w) == 1
     outs, refs = _run_conv_bf16(capi, cuda, n, h, w, 64, cout, 3, relu, pool, pin, pout, seed=64 + cout + h, aligned=True)
-    _check(outs[0], refs[0], False)
+    cd.check_bf16(outs[0], refs[0], False)
     # what it does not take: other channel counts, unaligned slices, grouped launches
     d[0].cin = 128
     assert lib.rtpose_conv3x3_c64_bf16_fits(d, 1, n, h, w) == 0
@@ -366,7 +280,7 @@ def test_conv3x3_of_64_input_channels_with_byte_offsets_past_2_to_31(capi, cuda)
     assert lib.rtpose_layout_pixels(C.byref(d[0].lin), n, h, w) * 128 > 2 ** 31
     assert lib.rtpose_conv3x3_c64_bf16_fits(d, 1, n, h, w) == 1
     outs, refs = _run_conv_bf16(capi, cuda, n, h, w, 64, cout, 3, 1, 1, 1, 1, seed=5, aligned=True, lead_extra=extra)
-    _check(outs[0], refs[0], False)
+    cd.check_bf16(outs[0], refs[0], False)
     d[0].lin.lead += extra
     assert lib.rtpose_conv3x3_c64_bf16_fits(d, 1, n, h, w) == 0
 

@@ -9,74 +9,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_driver as cd
+
 pytestmark = pytest.mark.gpu
 
 
 def _run_conv_x3(capi, dev, n, h, w, cin, cout, k, relu, pool, pad_in, pad_out, seed, groups=1, out_f32=False):
-    lib, Layout = capi.lib, capi.Layout
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, cin, h, w, generator=g)
-    cin_p = (cin + 15) // 16 * 16
-    ws, bs, refs = [], [], []
-    for gi in range(groups):
-        wt = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
-        b = torch.randn(cout, generator=g) * 0.1
-        y = F.conv2d(x.double(), wt.double(), b.double(), padding=k // 2).float()   # exact fp32-operand conv
-        if relu:
-            y = F.relu(y)
-        if pool:
-            y = F.max_pool2d(y, 2, 2, 0)
-        ws.append(wt.to(dev))
-        bs.append(b.to(dev))
-        refs.append(y)
-    stream = capi.current_stream()
-    lin = Layout.padded(2 * cin_p, h, w, pad_in)          # elements: 2 per channel
-    npx = lib.rtpose_layout_pixels(C.byref(lin), n, h, w)
-    xin = torch.zeros(npx * 2 * cin_p, device=dev, dtype=torch.bfloat16)
-    xd = x.to(dev)
-    capi.check(lib.rtpose_nchw_to_layout_split(capi.ptr(xd), capi.ptr(xin), C.byref(lin), cin, cin_p, n, h, w, stream))
-    ho, wo = (h // 2, w // 2) if pool else (h, w)
-    cpo = (cout + 7) // 8 * 8
-    ctot = cpo * groups + 8                               # channels per pixel of the output buffer
-    descs = (capi.ConvDesc * groups)()
-    outs, keep = [], []
-    if out_f32:
-        lfull = Layout.padded(ctot, ho, wo, pad_out)
-        obuf = torch.zeros(lib.rtpose_layout_pixels(C.byref(lfull), n, ho, wo) * ctot, device=dev)
-    else:
-        lfull = Layout.padded(2 * ctot, ho, wo, pad_out)
-        obuf = torch.zeros(lib.rtpose_layout_pixels(C.byref(lfull), n, ho, wo) * 2 * ctot, device=dev,
-                           dtype=torch.bfloat16)
-    for gi in range(groups):
-        wp = torch.zeros(lib.rtpose_packed_weight_bytes_bf16x3(cout, cin_p, k) // 2, device=dev, dtype=torch.bfloat16)
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=dev)
-        capi.check(lib.rtpose_pack_conv_weights_bf16x3(capi.ptr(ws[gi]), capi.ptr(bs[gi]), cout, cin, k, None, cin_p,
-                                                       capi.ptr(wp), capi.ptr(bp), stream))
-        keep += [wp, bp]
-        d = descs[gi]
-        d.inp, d.w_packed, d.bias_packed, d.out = xin.data_ptr(), wp.data_ptr(), bp.data_ptr(), obuf.data_ptr()
-        d.lin = lin
-        choff = gi * cpo + 8
-        d.lout = Layout.padded(ctot, ho, wo, pad_out, choff=choff) if out_f32 else \
-            Layout.padded(2 * ctot, ho, wo, pad_out, choff=2 * choff)
-        d.cin, d.cout, d.k, d.relu, d.pool = cin_p, cout, k, int(relu), int(pool)
-    capi.check(lib.rtpose_conv2d_bf16x3(descs, groups, n, h, w, int(out_f32), stream), "rtpose_conv2d_bf16x3")
-    for gi in range(groups):
-        choff = gi * cpo + 8
-        if out_f32:
-            o = torch.empty(n, cout, ho, wo, device=dev)
-            lo = Layout.padded(ctot, ho, wo, pad_out, choff=choff)
-            capi.check(lib.rtpose_layout_to_nchw(capi.ptr(obuf), C.byref(lo), capi.ptr(o), cout, n, ho, wo, stream))
-        else:
-            dense = torch.empty(n, ho, wo, cout, device=dev)
-            lo = Layout.padded(2 * ctot, ho, wo, pad_out, choff=2 * choff)
-            ld = Layout.dense(cout, ho, wo)
-            capi.check(lib.rtpose_layout_split_to_f32(capi.ptr(obuf), C.byref(lo), capi.ptr(dense), C.byref(ld), cout,
-                                                      n, ho, wo, stream))
-            o = dense.permute(0, 3, 1, 2).contiguous()
-        outs.append(o.cpu())
-    torch.cuda.synchronize()
-    return outs, refs
+    """(outputs, references: the exact fp32-operand conv in double) per branch; the output slices are 8-channel pieces of a
+    wider pixel, split into hi / lo unless out_f32."""
+    P = cd.problem(cd.Form("x3", k, None, out_f32), n, h, w, cin, cout, relu, pool, 0, groups, seed)
+    outs = cd.run(capi, dev, P, cd.PIECES, pad_in, pad_out)
+    return outs, [r.float() for r in P.refs]
 
 
 CASES = [
@@ -101,13 +44,13 @@ def test_conv_bf16x3_is_fp32_grade(capi, cuda, case):
     outs, refs = _run_conv_x3(capi, cuda, n, h, w, cin, cout, k, relu, pool, pin, pout, seed=hash(case) % 1000)
     scale = max(1.0, refs[0].abs().max().item())
     err = (outs[0] - refs[0]).abs().max().item()
-    assert err <= 3e-5 * scale, "max abs err %g (scale %g)" % (err, scale)
+    assert err <= cd.X3_TOL * scale, "max abs err %g (scale %g)" % (err, scale)
 
 
 def test_conv_bf16x3_grouped_fp32_out(capi, cuda):
     outs, refs = _run_conv_x3(capi, cuda, 5, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=7, groups=2, out_f32=True)
     for o, r in zip(outs, refs):
-        assert (o - r).abs().max().item() <= 3e-5 * max(1.0, r.abs().max().item())
+        assert (o - r).abs().max().item() <= cd.X3_TOL * max(1.0, r.abs().max().item())
 
 
 @pytest.fixture(scope="module")
@@ -206,12 +149,9 @@ def test_conv_bf16x3_error_bound_wide_dynamic_range(capi, cuda):
     stream = capi.current_stream()
     lin = Layout.padded(2 * cin, h, w, 1)
     xin = torch.zeros(lib.rtpose_layout_pixels(C.byref(lin), n, h, w) * 2 * cin, device=cuda, dtype=torch.bfloat16)
-    xd, wd, bd = x.to(cuda), wt.to(cuda), torch.zeros(cout, device=cuda)
+    xd = x.to(cuda)
     capi.check(lib.rtpose_nchw_to_layout_split(capi.ptr(xd), capi.ptr(xin), C.byref(lin), cin, cin, n, h, w, stream))
-    wp = torch.zeros(lib.rtpose_packed_weight_bytes_bf16x3(cout, cin, k) // 2, device=cuda, dtype=torch.bfloat16)
-    bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=cuda)
-    capi.check(lib.rtpose_pack_conv_weights_bf16x3(capi.ptr(wd), capi.ptr(bd), cout, cin, k, None, cin, capi.ptr(wp),
-                                                   capi.ptr(bp), stream))
+    wp, bp = cd.pack(capi, cuda, cd.Form("x3", k), wt, torch.zeros(cout), cin)
     lo = Layout.dense(cout, h, w)
     out = torch.zeros(n * h * w * cout, device=cuda)
     d = (capi.ConvDesc * 1)()

@@ -8,98 +8,22 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_driver as cd
 import layout_restate as lr
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-4  # relative to max|ref|; fp32 fma-chain vs ATen summation order
+TOL = cd.TOL
 
 
 def _run_conv(capi, dev, n, h, w, cin, cout, k, relu, pool, pad_in, pad_out, seed, groups=1, cin_pad=None,
               winograd=False, only_images=None, skip_ref=False, wino_m=0, scratch=True, first_image=0):
-    lib, Layout = capi.lib, capi.Layout
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, cin, h, w, generator=g)
-    if only_images:   # the same random stream, but only some images go through the kernel
-        x = x[first_image:first_image + only_images]
-        n = only_images
-    cin_p = cin_pad or ((cin + 7) // 8 * 8)
-    ws, bs, refs = [], [], []
-    for gi in range(groups):
-        wt = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
-        b = torch.randn(cout, generator=g) * 0.1
-        y = None
-        if not skip_ref:   # (the CPU reference is the slow part of a case)
-            y = F.conv2d(x[:n], wt, b, padding=k // 2)
-            if relu:
-                y = F.relu(y)
-            if pool:
-                y = F.max_pool2d(y, 2, 2, 0)
-        ws.append(wt.to(dev))
-        bs.append(b.to(dev))
-        refs.append(y)
-    stream = capi.current_stream()
-    lin = Layout.padded(cin_p, h, w, pad_in)
-    xin = torch.zeros(lib.rtpose_layout_pixels(C.byref(lin), n, h, w) * cin_p, device=dev)
-    xd = x[:n].contiguous().to(dev)
-    capi.check(lib.rtpose_nchw_to_layout(capi.ptr(xd), capi.ptr(xin), C.byref(lin), cin, cin_p, n, h, w, stream))
-    ho, wo = (h // 2, w // 2) if pool else (h, w)
-    cstride_out = cout * groups + 3  # odd stride + channel offsets: exercises slices
-    descs = (capi.ConvDesc * groups)()
-    outs, keep = [], []
-    lout_full = Layout.padded(cstride_out, ho, wo, pad_out)
-    obuf = torch.zeros(lib.rtpose_layout_pixels(C.byref(lout_full), n, ho, wo) * cstride_out, device=dev)
-    for gi in range(groups):
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=dev)
-        if winograd and k == 7 and wino_m:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd7(cout, cin_p, wino_m), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights_winograd7(capi.ptr(ws[gi]), capi.ptr(bs[gi]), cout, cin, wino_m,
-                                                              None, cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        elif winograd and k == 3 and wino_m:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd3(cout, cin_p, wino_m), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights_winograd3(capi.ptr(ws[gi]), capi.ptr(bs[gi]), cout, cin, wino_m,
-                                                              None, cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        elif winograd:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd(cout, cin_p, k), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights_winograd(capi.ptr(ws[gi]), capi.ptr(bs[gi]), cout, cin, k, None,
-                                                             cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        else:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin_p, k), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights(capi.ptr(ws[gi]), capi.ptr(bs[gi]), cout, cin, k, None, cin_p,
-                                                    capi.ptr(wp), capi.ptr(bp), stream))
-        keep += [wp, bp]
-        d = descs[gi]
-        d.inp, d.w_packed, d.bias_packed, d.out = xin.data_ptr(), wp.data_ptr(), bp.data_ptr(), obuf.data_ptr()
-        d.lin = lin
-        d.lout = Layout.padded(cstride_out, ho, wo, pad_out, choff=gi * cout + 1)
-        d.cin, d.cout, d.k, d.relu, d.pool = cin_p, cout, k, int(relu), int(pool)
-        d.wino_m = wino_m if winograd else 0
-    if winograd:
-        assert lib.rtpose_conv2d_winograd_fits(descs, n, h, w) == 1
-        # the hand-over scratch of the persistent 7x7 launches is the caller's (the library allocates nothing)
-        sc = torch.zeros(lib.rtpose_conv2d_winograd_scratch_bytes() // 4, dtype=torch.int32, device=dev) if scratch else None
-        capi.check(lib.rtpose_conv2d_winograd_ex(descs, groups, n, h, w, capi.ptr(sc) if scratch else None,
-                                                 sc.numel() * 4 if scratch else 0, stream), "rtpose_conv2d_winograd_ex")
-        if scratch:
-            word = C.c_int(-1)
-            capi.check(lib.rtpose_conv2d_winograd_scratch_error(capi.ptr(sc), C.byref(word), stream))
-            assert word.value == 0, "device error word %d" % word.value
-    else:
-        capi.check(lib.rtpose_conv2d(descs, groups, n, h, w, stream), "rtpose_conv2d")
-    for gi in range(groups):
-        o = torch.empty(n, cout, ho, wo, device=dev)
-        lo = Layout.padded(cstride_out, ho, wo, pad_out, choff=gi * cout + 1)
-        capi.check(lib.rtpose_layout_to_nchw(capi.ptr(obuf), C.byref(lo), capi.ptr(o), cout, n, ho, wo, stream))
-        outs.append(o.cpu())
-    torch.cuda.synchronize()
-    # gaps of the output buffer must still be zero (only real pixels are written)
-    total = obuf.abs().sum().item()
-    inner = sum(o.abs().sum().item() for o in outs)
-    assert abs(total - inner) <= 1e-3 * max(1.0, inner), "conv wrote outside its slice / into the gaps"
-    # the exact form: every word outside the written slices (lead, gaps, tail slack, the other channels) is still 0, bit for bit
-    written = [lr.index(lr.padded(cstride_out, ho, wo, pad_out, gi * cout + 1), n, ho, wo, cout) for gi in range(groups)]
-    assert lr.untouched(obuf.cpu().numpy().view(np.uint32), written, 0), "conv wrote outside its slice / into the gaps"
-    return outs, refs
+    """(outputs, torch fp32 conv2d references) per branch, the output slices at odd stride + channel offsets; winograd with
+    wino_m = 0: the library's default form of that k."""
+    form = cd.Form("f32", k, wino_m if winograd else None)
+    P = cd.problem(form, n, h, w, cin, cout, relu, pool, 0, groups, seed, only_images=only_images, first_image=first_image,
+                   cin_pad=cin_pad, ref=None if skip_ref else torch.float32)   # (the CPU reference is the slow part of a case)
+    return cd.run(capi, dev, P, cd.ODD, pad_in, pad_out, scratch), P.refs
 
 
 CASES = [
@@ -347,60 +271,44 @@ def _from_planes(buf, q_slots):
     return buf.view(-1, q_slots, 8).permute(1, 0, 2).reshape(q_slots, -1).contiguous()
 
 
-def _run_conv4_planes(capi, dev, n, h, w, cin, cout, relu, pool, pad_in, pad_out, seed, groups, in_planes, out_planes):
+def _run_conv4_planes(capi, dev, P, pad_in, pad_out, in_planes, out_planes):
     """F(4x4,3x3) through the C ABI with the input and / or the output stored as channel planes
-    (rtpose_conv_desc.in_plane_pixels / out_plane_pixels); same random stream as _run_conv."""
-    lib, Layout = capi.lib, capi.Layout
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, cin, h, w, generator=g)
-    ws, bs = [], []
-    for gi in range(groups):
-        ws.append((torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (cin * 9)) ** 0.5).to(dev))
-        bs.append((torch.randn(cout, generator=g) * 0.1).to(dev))
-    stream = capi.current_stream()
-    lin = Layout.padded(cin, h, w, pad_in)
-    q_in = lib.rtpose_layout_pixels(C.byref(lin), n, h, w)
-    xin = torch.zeros(q_in * cin, device=dev)
-    xd = x.contiguous().to(dev)
-    capi.check(lib.rtpose_nchw_to_layout(capi.ptr(xd), capi.ptr(xin), C.byref(lin), cin, cin, n, h, w, stream))
-    torch.cuda.synchronize()
+    (rtpose_conv_desc.in_plane_pixels / out_plane_pixels).  Problem, packed filters and the pixel-major input are the
+    driver's; the plane buffers are this file's."""
+    n, h, w, cin, cout, groups = P.n, P.h, P.w, P.cin, P.cout, P.groups
+    xin, lin = cd.to_layout(capi, dev, P, P.xs[0], pad_in)
+    q_in = xin.numel() // cin
     qs_in = q_in + 5                               # more slots per plane than the layout has pixels
     if in_planes:                                  # one plane of junk in front: the slice starts at channel 8
         xin = _to_planes(xin.view(q_in, cin), qs_in, lead_planes=1, fill=7.0)
         xin[:qs_in * 8] = 7.0
-    ho, wo = (h // 2, w // 2) if pool else (h, w)
+        lin = lr.padded(cin + 8, h, w, pad_in, 8)
+    ho, wo = (h // 2, w // 2) if P.pool else (h, w)
     ctot = cout * groups + 8
-    lout = Layout.padded(ctot, ho, wo, pad_out)
-    q_out = lib.rtpose_layout_pixels(C.byref(lout), n, ho, wo)
+    louts = [lr.padded(ctot, ho, wo, pad_out, 8 + gi * cout) for gi in range(groups)]
+    q_out = cd.npx(capi, louts[0], n, ho, wo)
     qs_out = q_out + 3
     obuf = torch.zeros((qs_out if out_planes else q_out) * ctot, device=dev)
     descs = (capi.ConvDesc * groups)()
-    keep = []
     for gi in range(groups):
-        wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd3(cout, cin, 4), device=dev)
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=dev)
-        capi.check(lib.rtpose_pack_conv_weights_winograd3(capi.ptr(ws[gi]), capi.ptr(bs[gi]), cout, cin, 4, None, cin,
-                                                          capi.ptr(wp), capi.ptr(bp), stream))
-        keep += [wp, bp]
         d = descs[gi]
-        d.inp, d.w_packed, d.bias_packed, d.out = xin.data_ptr(), wp.data_ptr(), bp.data_ptr(), obuf.data_ptr()
-        d.lin = Layout.padded(cin + 8, h, w, pad_in, choff=8) if in_planes else lin
-        d.lout = Layout.padded(ctot, ho, wo, pad_out, choff=8 + gi * cout)
-        d.cin, d.cout, d.k, d.relu, d.pool, d.wino_m = cin, cout, 3, int(relu), int(pool), 4
+        d.inp, d.w_packed, d.bias_packed, d.out = xin.data_ptr(), P.wp[gi].data_ptr(), P.bp[gi].data_ptr(), obuf.data_ptr()
+        d.lin, d.lout = cd.L(capi, lin), cd.L(capi, louts[gi])
+        d.cin, d.cout, d.k, d.relu, d.pool, d.wino_m = cin, cout, 3, P.relu, P.pool, 4
         d.in_plane_pixels = qs_in if in_planes else 0
         d.out_plane_pixels = qs_out if out_planes else 0
-    capi.check(lib.rtpose_conv2d_winograd_ex(descs, groups, n, h, w, None, 0, stream), "rtpose_conv2d_winograd_ex (planes)")
-    torch.cuda.synchronize()
-    pm = _from_planes(obuf, qs_out)[:q_out].contiguous() if out_planes else obuf
-    outs = []
-    for gi in range(groups):
-        o = torch.empty(n, cout, ho, wo, device=dev)
-        lo = Layout.padded(ctot, ho, wo, pad_out, choff=8 + gi * cout)
-        capi.check(lib.rtpose_layout_to_nchw(capi.ptr(pm), C.byref(lo), capi.ptr(o), cout, n, ho, wo, stream))
-        outs.append(o.cpu())
-    torch.cuda.synchronize()
-    total, inner = obuf.abs().sum().item(), sum(o.abs().sum().item() for o in outs)
-    assert abs(total - inner) <= 1e-3 * max(1.0, inner), "conv wrote outside its slice / into the gaps / into the slack slots"
+    cd.call(capi, dev, P.form, descs, groups, n, h, w, scratch=False)
+    bits = cd.np_bits(obuf)
+    outs, written = [], []
+    for lo in louts:
+        q = lr.offsets(lr.Lay(1, 0, lo.ws, lo.hs, lo.lead), n, ho, wo)[..., None]      # the pixels' indices [n, ho, wo, 1]
+        c = lo.choff + np.arange(cout, dtype=np.int64)                                  # the slice's channels of the buffer
+        # planes: plane c / 8, slot q < qs_out, lane c % 8; pixel-major: word q * ctot + c (lr.index)
+        idx = ((c >> 3) * qs_out + q) * 8 + (c & 7) if out_planes else q * ctot + c
+        written.append(idx)
+        outs.append(torch.from_numpy(np.ascontiguousarray(np.transpose(bits[idx].view(np.float32), (0, 3, 1, 2)))))
+    # every other word - gaps, the other channels, the slack slots of a plane, the junk plane in front - is still 0, bit for bit
+    assert lr.untouched(bits, written, 0), "conv wrote outside its slice / into the gaps / into the slack slots"
     return outs
 
 
@@ -422,21 +330,17 @@ def test_winograd4_channel_planes_are_bit_identical_to_pixel_major(capi, cuda, c
     end) - only addresses change: every combination gives the bits of the pixel-major launch, nothing lands in the gaps, the
     slack slots of a plane or a neighbouring plane, and a junk plane in front of the slice is not read."""
     n, h, w, cin, cout, relu, pool, pin, pout, groups = case
-    ref = _run_conv4_planes(capi, cuda, n, h, w, cin, cout, relu, pool, pin, pout, 77, groups, False, False)
+    # (the pixel-major launch is the one the other tests pin to torch's CPU conv2d; here too on the small batches)
+    P = cd.pack_all(capi, cuda, cd.problem(cd.Form("f32", 3, 4), n, h, w, cin, cout, relu, pool, groups=groups, seed=77,
+                                           cin_pad=cin, ref=torch.float32 if n <= 5 else None))
+    ref = _run_conv4_planes(capi, cuda, P, pin, pout, False, False)
     for inp, outp in ((True, False), (False, True), (True, True)):
-        got = _run_conv4_planes(capi, cuda, n, h, w, cin, cout, relu, pool, pin, pout, 77, groups, inp, outp)
+        got = _run_conv4_planes(capi, cuda, P, pin, pout, inp, outp)
         for a, b in zip(got, ref):
             assert torch.equal(a, b), (inp, outp)
-    if n <= 5:   # and the pixel-major launch is the one the other tests pin to torch's CPU conv2d
-        g = torch.Generator().manual_seed(77)
-        x = torch.randn(n, cin, h, w, generator=g)
-        for gi in range(groups):
-            wt = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (cin * 9)) ** 0.5
-            b = torch.randn(cout, generator=g) * 0.1
-            y = F.conv2d(x, wt, b, padding=1)
-            y = F.relu(y) if relu else y
-            y = F.max_pool2d(y, 2, 2, 0) if pool else y
-            assert (ref[gi] - y).abs().max().item() <= TOL * max(1.0, y.abs().max().item())
+    if n <= 5:
+        for o, y in zip(ref, P.refs):
+            assert (o - y).abs().max().item() <= TOL * max(1.0, y.abs().max().item())
 
 
 def test_channel_planes_are_refused_where_no_kernel_reads_them(capi, cuda):
@@ -632,13 +536,9 @@ def test_pointwise_pair_is_bit_identical_to_two_launches(capi, cuda, shape):
         return t
 
     def pack(wt, b, cout):
-        cin = wt.shape[1]
-        wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin, 1), device=cuda)
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=cuda)
-        capi.check(lib.rtpose_pack_conv_weights(capi.ptr(dev(wt)), capi.ptr(dev(b)), cout, cin, 1, None, cin, capi.ptr(wp),
-                                                capi.ptr(bp), stream))
-        keep.extend([wp, bp])
-        return wp, bp
+        packed = cd.pack(capi, cuda, cd.Form("f32", 1), wt, b, wt.shape[1])
+        keep.extend(packed)
+        return packed
 
     xin, p1, p2 = [], [], []
     for gi in range(2):

@@ -3,17 +3,17 @@ grouped launch - a cstride / choff / lead / base per branch), through the C ABI.
 
 One runner performs the same launch twice: on a COMPACT input (cstride == cin elements, choff == 0 - what every other
 launcher test feeds) and on the same data as a slice of a wider pixel whose other channels hold finite decoys of magnitude
-2^10 .. 2^11 (tests/conv_slices.py).  Weights, output layout (the odd-stride sliced one of the existing helpers), ws / hs /
-lead, stream and scratch are the same.  It asserts
+2^10 .. 2^11 (tests/conv_slices.py).  Problem, packing, launch and read-back are the shared driver's (tests/conv_driver.py);
+weights, output layout (the driver's preset for the form), ws / hs / lead, stream and scratch are the same.  It asserts
 
   (a) the wide run's output buffer holds the bits of the compact run's: lin.cstride / lin.choff change addresses only,
-  (b) on the tiny shapes, the wide run against a float64 conv2d of the slice data within the tolerance the launcher's own
-      test file states (restated or imported below: TOL of test_conv_gpu.py, `_check` of test_bf16_gpu.py, 3e-5 of
-      test_conv_bf16x3_is_fp32_grade, the gamma bound of test_f87_matches_direct_kernel_and_float64, 2e-4 of the hourglass
-      stem's test),
+  (b) on the tiny shapes, the wide run against a float64 conv2d of the slice data within the tolerance of the form
+      (conv_driver.check: TOL, check_bf16, X3_TOL, the gamma bound of F(8,7); STEM7_TOL for the hourglass stem),
   (c) the wide input buffer is bit-identical after the launch,
-  (d) every output word outside the written slices is untouched (layout_restate.untouched),
-  (e) the device error word of a Winograd launch with a scratch is 0.
+  (d) every output word outside the written slices is untouched (layout_restate.untouched, in conv_driver.outputs),
+  (e) the device error word of a Winograd launch with a scratch is 0 (conv_driver.call),
+  (f) the compact fp32 / bf16 input, which the library's conversion kernel fills, is bit-equal to conv_slices.scatter_nchw:
+      the input side of this file does not rest on the library.
 
 No launcher was found to pick another ARITHMETIC from the input cstride / choff, so (a) holds everywhere.  One launcher reads
 them for a scheduling choice: rtpose_conv2d_bf16 runs its persistent strips only when the branches of a grouped launch share
@@ -23,42 +23,27 @@ lead in its compact run as well, so both runs take the same path, and the sums d
 The large shapes are the smallest of the existing case tables known to select a launcher's main / persistent form; they
 run with bit identity only (the CPU reference is the slow part of a case)."""
 import ctypes as C
-from collections import namedtuple
-from types import SimpleNamespace
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_driver as cd
 import conv_slices as cs
 import layout_restate as lr
-import test_bf16_gpu as tb
-import test_conv_gpu as tc
-import test_wino7_f8_gpu as t87
-import test_wino_numerics_gpu as wn
+from conv_driver import STEM7_TOL, TOL, Form
 
 pytestmark = pytest.mark.gpu
-
-TOL = tc.TOL          # fp32 direct and every Winograd form but F(8,7): relative to max(1, max|ref|)
-X3_TOL = 3e-5         # test_conv_bf16x3_is_fp32_grade
-STEM7_TOL = 2e-4      # test_hourglass_gpu.py, rtpose_conv7x7_s2 against conv2d
-U = 2.0 ** -24
-
-# kind: 'f32' | 'bf16' | 'x3';  m: None = the direct kernel, else the Winograd form;  entry: 'c64' = rtpose_conv3x3_c64_bf16
-Form = namedtuple("Form", "kind k m out_f32 entry", defaults=(None, False, None))
 
 
 def _unit(form):
     return {"f32": cs.UNIT_F32, "bf16": cs.UNIT_BF16, "x3": cs.UNIT_X3}[form.kind]
 
 
-def _L(capi, lay):
-    return capi.Layout(lay.cstride, lay.choff, lay.ws, lay.hs, lay.lead)
-
-
-def _npx(capi, lay, n, h, w):
-    return capi.lib.rtpose_layout_pixels(C.byref(_L(capi, lay)), n, h, w)
+def _out(form):
+    """the output buffer of the form's own test file: 8-channel pieces for bf16x3, 16-byte aligned slices for the 64-channel
+    kernel, odd stride + channel offsets for the rest"""
+    return cd.PIECES if form.kind == "x3" else cd.ALIGNED if form.entry == "c64" else cd.ODD
 
 
 def _bits(t):
@@ -69,201 +54,28 @@ def _same_bits(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
-def _np_bits(t):
-    t = t.cpu()
-    return t.view(torch.int32).numpy().view(np.uint32) if t.dtype == torch.float32 else t.view(torch.int16).numpy().view(np.uint16)
-
-
-# ---- one conv problem: inputs, filters of every branch, packed on the device, float64 references -----------------------------
-def _reference(form, x, wt, b, relu, pool, slopes):
-    wq = tb._rb(wt) if form.kind == "bf16" else wt          # (bf16: x is rounded already; bf16x3: the exact fp32-operand conv)
-    y = F.conv2d(x.double(), wq.double(), b.double(), padding=form.k // 2)
-    if relu:
-        y = F.relu(y)
-    if slopes is not None:
-        y = torch.where(y >= 0, y, slopes.double().view(1, -1, 1, 1) * y)
-    if pool:
-        y = F.max_pool2d(y, 2, 2, 0)
-    return y
-
-
-def _problem(capi, dev, form, n, h, w, cin, cout, relu=1, pool=0, prelu=0, groups=1, seed=0, ninputs=1, ref=True):
-    lib, k = capi.lib, form.k
-    g = torch.Generator().manual_seed(seed)
-    xs = [torch.randn(n, cin, h, w, generator=g) for _ in range(ninputs)]
-    if form.kind == "bf16":
-        xs = [tb._rb(x) for x in xs]
-    cin_p = (cin + 7) // 8 * 8 if form.kind == "f32" else (cin + 15) // 16 * 16
-    P = SimpleNamespace(form=form, n=n, h=h, w=w, cin=cin, cin_p=cin_p, cout=cout, relu=relu, pool=pool, groups=groups,
-                        xs=xs, wts=[], biases=[], slopes=[], wp=[], bp=[], refs=[], keep=[])
-    stream = capi.current_stream()
-    for gi in range(groups):
-        wt = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
-        b = torch.randn(cout, generator=g) * 0.1
-        sl = (torch.rand(cout, generator=g) * 0.5 - 0.1) if prelu else None
-        wd, bd = wt.to(dev), b.to(dev)
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=dev)
-        args = (capi.ptr(wd), capi.ptr(bd), cout, cin)
-        if form.kind == "bf16":
-            wp = torch.zeros(lib.rtpose_packed_weight_bytes_bf16(cout, cin_p, k) // 2, device=dev, dtype=torch.bfloat16)
-            capi.check(lib.rtpose_pack_conv_weights_bf16(*args, k, None, cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        elif form.kind == "x3":
-            wp = torch.zeros(lib.rtpose_packed_weight_bytes_bf16x3(cout, cin_p, k) // 2, device=dev, dtype=torch.bfloat16)
-            capi.check(lib.rtpose_pack_conv_weights_bf16x3(*args, k, None, cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        elif form.m is None:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin_p, k), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights(*args, k, None, cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        elif k == 3:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd3(cout, cin_p, form.m), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights_winograd3(*args, form.m, None, cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        else:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd7(cout, cin_p, form.m), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights_winograd7(*args, form.m, None, cin_p, capi.ptr(wp), capi.ptr(bp), stream))
-        torch.cuda.synchronize()            # (wd / bd may go once the pack kernel has run)
-        P.wts.append(wt)
-        P.biases.append(b)
-        P.slopes.append(sl.to(dev) if prelu else None)
-        P.wp.append(wp)
-        P.bp.append(bp)
-        P.refs.append(_reference(form, xs[gi % ninputs], wt, b, relu, pool, sl) if ref else None)
-    return P
-
-
-def _compact(capi, dev, P, x, pad):
-    """x -> (compact input buffer on the device, its lr.Lay): cstride = the slice's elements, choff = 0"""
-    lib, form = capi.lib, P.form
-    e = 2 if form.kind == "x3" else 1
-    lay = lr.padded(e * P.cin_p, P.h, P.w, pad)
-    npx = _npx(capi, lay, P.n, P.h, P.w)
-    if form.kind == "x3":      # the split hi / lo pieces: the library's own conversion, as tests/test_bf16x3_gpu.py
-        buf = torch.zeros(npx * lay.cstride, device=dev, dtype=torch.bfloat16)
-        xd = x.contiguous().to(dev)
-        capi.check(lib.rtpose_nchw_to_layout_split(capi.ptr(xd), capi.ptr(buf), C.byref(_L(capi, lay)), P.cin, P.cin_p,
-                                                   P.n, P.h, P.w, capi.current_stream()))
-        torch.cuda.synchronize()
-        return buf, lay
-    dt = torch.float32 if form.kind == "f32" else torch.bfloat16
-    return cs.scatter_nchw(x, lay, npx, dt).to(dev), lay
-
-
-def _call(capi, dev, form, descs, groups, n, h, w, scratch):
-    """the launch of `descs` by the form's entry point; (e) where a scratch is passed"""
-    lib, stream = capi.lib, capi.current_stream()
-    if form.entry == "c64":
-        assert groups == 1 and lib.rtpose_conv3x3_c64_bf16_fits(descs, 1, n, h, w) == 1
-        capi.check(lib.rtpose_conv3x3_c64_bf16(descs, n, h, w, stream), "rtpose_conv3x3_c64_bf16")
-    elif form.kind == "bf16":
-        capi.check(lib.rtpose_conv2d_bf16(descs, groups, n, h, w, int(form.out_f32), stream), "rtpose_conv2d_bf16")
-    elif form.kind == "x3":
-        capi.check(lib.rtpose_conv2d_bf16x3(descs, groups, n, h, w, int(form.out_f32), stream), "rtpose_conv2d_bf16x3")
-    elif form.m is None:
-        capi.check(lib.rtpose_conv2d(descs, groups, n, h, w, stream), "rtpose_conv2d")
-    else:
-        assert lib.rtpose_conv2d_winograd_fits(descs, n, h, w) == 1
-        sc = torch.zeros(lib.rtpose_conv2d_winograd_scratch_bytes() // 4, dtype=torch.int32, device=dev) if scratch else None
-        capi.check(lib.rtpose_conv2d_winograd_ex(descs, groups, n, h, w, capi.ptr(sc) if scratch else None,
-                                                 sc.numel() * 4 if scratch else 0, stream), "rtpose_conv2d_winograd_ex")
-        if scratch:
-            word = C.c_int(-1)
-            capi.check(lib.rtpose_conv2d_winograd_scratch_error(capi.ptr(sc), C.byref(word), stream))
-            assert word.value == 0, "device error word %d" % word.value
-    torch.cuda.synchronize()
-
-
-def _out_layouts(P, pad_out):
-    """The output buffer of the existing helpers, restated: odd stride + channel offsets for fp32 and bf16 (_run_conv,
-    _run_conv_bf16), 8-channel pieces for bf16x3 (_run_conv_x3), 16-byte aligned slices for the 64-channel kernel
-    (_run_conv_bf16(aligned=True)).  Returns (elements per pixel, [lr.Lay per branch], element type, split)."""
-    form, cout, groups = P.form, P.cout, P.groups
-    ho, wo = (P.h // 2, P.w // 2) if P.pool else (P.h, P.w)
-    split = form.kind == "x3" and not form.out_f32
-    if form.kind == "x3":
-        cpo = (cout + 7) // 8 * 8
-        e = 2 if split else 1
-        cso, choffs = e * (cpo * groups + 8), [e * (gi * cpo + 8) for gi in range(groups)]
-    elif form.entry == "c64":
-        cso, choffs = cout * groups + 16, [gi * cout + 8 for gi in range(groups)]
-    else:
-        cso, choffs = cout * groups + 3, [gi * cout + 1 for gi in range(groups)]
-    dt = torch.float32 if (form.kind == "f32" or form.out_f32) else torch.bfloat16
-    return cso, [lr.padded(cso, ho, wo, pad_out, ch) for ch in choffs], dt, split
-
-
-def _launch(capi, dev, P, inputs, pad_out, scratch=True):
-    """inputs: one (buffer, lr.Lay) per branch.  Returns the output buffer (device) and its per-branch layouts."""
-    form = P.form
-    ho, wo = (P.h // 2, P.w // 2) if P.pool else (P.h, P.w)
-    cso, louts, dt, _ = _out_layouts(P, pad_out)
-    obuf = torch.zeros(_npx(capi, louts[0], P.n, ho, wo) * cso, device=dev, dtype=dt)
-    descs = (capi.ConvDesc * P.groups)()
-    for gi, (buf, lay) in enumerate(inputs):
-        d = descs[gi]
-        d.inp, d.w_packed, d.bias_packed, d.out = buf.data_ptr(), P.wp[gi].data_ptr(), P.bp[gi].data_ptr(), obuf.data_ptr()
-        d.lin, d.lout = _L(capi, lay), _L(capi, louts[gi])
-        d.cin, d.cout, d.k, d.relu, d.pool = P.cin_p, P.cout, form.k, int(P.relu), int(P.pool)
-        d.wino_m = form.m or 0
-        if P.slopes[gi] is not None:
-            d.prelu = P.slopes[gi].data_ptr()
-    _call(capi, dev, form, descs, P.groups, P.n, P.h, P.w, scratch)
-    return obuf, louts
-
-
-def _outputs(P, obuf, louts, pad_out, values=True):
-    """The branches' outputs [n, cout, ho, wo] (CPU fp32) read through lr.index (values = False: none), after (d): every
-    word of the output buffer outside the written slices still holds 0, bit for bit."""
-    ho, wo = (P.h // 2, P.w // 2) if P.pool else (P.h, P.w)
-    split = _out_layouts(P, pad_out)[3]
-    host = obuf.cpu()
-    bits = _np_bits(host)
-    outs, written = [], []
-    for lo in louts:
-        if split:
-            ih, il = lr.split_index(lo, P.n, ho, wo, P.cout)
-            written += [ih, il]
-            v = lr.bf16_to_f32(bits[ih]) + lr.bf16_to_f32(bits[il])
-            outs.append(None if not values else torch.from_numpy(np.ascontiguousarray(np.transpose(v, (0, 3, 1, 2)))))
-        else:
-            written.append(lr.index(lo, P.n, ho, wo, P.cout))
-            outs.append(cs.slice_of(host, lo, P.n, ho, wo, P.cout).float() if values else None)
-    assert lr.untouched(bits, written, 0), "the conv wrote outside its slice / into the gaps"
-    return outs
-
-
-def _check_reference(P, gi, out, x):
-    form, ref = P.form, P.refs[gi]
-    if form.kind == "bf16":
-        tb._check(out, ref.float(), form.out_f32)
-    elif form.kind == "x3":
-        err = (out.double() - ref).abs().max().item()
-        assert err <= X3_TOL * max(1.0, ref.abs().max().item()), "bf16x3 max abs err %g" % err
-    elif form.k == 7 and form.m == 8:        # the element-wise bound of test_f87_matches_direct_kernel_and_float64
-        y64, s = wn._ref64(x, P.wts[gi], P.biases[gi], 7, None)
-        y64 = F.relu(y64) if P.relu else y64
-        gamma = ((out.double() - y64).abs() / (U * s)).max().item()
-        assert gamma <= t87.gamma_limit_f87(P.wts[gi]), ("F(8,7) gamma", gamma)
-    else:
-        err = (out.double() - ref).abs().max().item()
-        assert err <= TOL * max(1.0, ref.abs().max().item()), "max abs err %g" % err
-
-
 def _compare(capi, dev, form, n, h, w, cin, cout, relu=1, pool=0, prelu=0, groups=1, pad_out=1, seed=0, ref=True,
              geoms=None, scratch=True):
-    """The generic runner: one compact launch, then the same launch per input geometry; (a) - (e)."""
-    P = _problem(capi, dev, form, n, h, w, cin, cout, relu, pool, prelu, groups, seed, 1, ref)
-    buf, lay = _compact(capi, dev, P, P.xs[0], form.k // 2)
-    ob_c, louts = _launch(capi, dev, P, [(buf, lay)] * groups, pad_out, scratch)
+    """The generic runner: one compact launch, then the same launch per input geometry; (a) - (f)."""
+    P = cd.problem(form, n, h, w, cin, cout, relu, pool, prelu, groups, seed, ref=torch.float64 if ref else None)
+    out = _out(form)
+    buf, lay = cd.to_layout(capi, dev, P, P.xs[0], form.k // 2)
+    if form.kind != "x3":
+        host = cs.scatter_nchw(P.xs[0], lay, cd.npx(capi, lay, n, h, w), buf.dtype)
+        assert _same_bits(buf.cpu(), host), "the conversion kernel's buffer is not the host scatter's"     # (f)
+    ob_c, louts = cd.launch(capi, dev, P, [(buf, lay)] * groups, out, pad_out, scratch)
     assert _bits(ob_c).ne(0).any()
     geoms = geoms or cs.geometries(lay.cstride, _unit(form))
     for name, extra, choff in geoms:
         wide, wlay = cs.widen(buf, lay, n, h, w, extra, choff, seed)
         before = wide.clone()
-        ob_w, _ = _launch(capi, dev, P, [(wide, wlay)] * groups, pad_out, scratch)
+        ob_w, _ = cd.launch(capi, dev, P, [(wide, wlay)] * groups, out, pad_out, scratch)
         assert _same_bits(wide, before), (name, "the launch changed its input buffer")                        # (c)
         assert _same_bits(ob_w, ob_c), (name, "lin.cstride / lin.choff changed the result")                   # (a)
-        outs = _outputs(P, ob_w, louts, pad_out, ref)                                                           # (d)
+        outs = cd.outputs(P, ob_w, louts, out, ref)                                                             # (d)
         if ref:
             for gi in range(groups):
-                _check_reference(P, gi, outs[gi], P.xs[0])                                                    # (b)
+                cd.check(P, gi, outs[gi], P.xs[0])                                                            # (b)
 
 
 def _mid(form, cin_e):
@@ -348,7 +160,7 @@ def _fits(capi, form, n, h, w, cin, cout):
         return True
     d = (capi.ConvDesc * 1)()
     d[0].k, d[0].cin, d[0].cout, d[0].wino_m = form.k, cin, cout, form.m
-    d[0].lin = _L(capi, lr.padded(cin, h, w, form.k // 2))
+    d[0].lin = cd.L(capi, lr.padded(cin, h, w, form.k // 2))
     return capi.lib.rtpose_conv2d_winograd_fits(d, n, h, w) == 1
 
 
@@ -366,24 +178,25 @@ def test_branches_that_read_different_buffers(capi, cuda, form, shape):
         assert form.k == 7 and form.m and cout == 16
         cout = 128
     ref = h < 20
-    P = _problem(capi, cuda, form, n, h, w, cin, cout, 1, 0, 0, groups=2, seed=500 + form.k, ninputs=2, ref=ref)
+    P = cd.problem(form, n, h, w, cin, cout, 1, 0, 0, groups=2, seed=500 + form.k, ninputs=2,
+                   ref=torch.float64 if ref else None)
     pad, u = form.k // 2, _unit(form)
-    a, lay = _compact(capi, cuda, P, P.xs[0], pad)
-    b0, _ = _compact(capi, cuda, P, P.xs[1], pad)
+    a, lay = cd.to_layout(capi, cuda, P, P.xs[0], pad)
+    b0, _ = cd.to_layout(capi, cuda, P, P.xs[1], pad)
     by = lay.ws + 3
     b, lay_b = cs.relead(b0, lay, by)
     a, b = _side_by_side([a, b])
-    ob_c, louts = _launch(capi, cuda, P, [(a, lay), (b, lay_b)], 3)
+    ob_c, louts = cd.launch(capi, cuda, P, [(a, lay), (b, lay_b)], _out(form), 3)
     wa, wlay_a = cs.widen(a, lay, n, h, w, 2 * u, u, 1)                 # middle: cstride cin + 2 u, choff u
     wb0, wl = cs.widen(b0, lay, n, h, w, 3 * u, 3 * u, 2)               # end: cstride cin + 3 u, choff 3 u
     wb, wlay_b = cs.relead(wb0, wl, by)
     wa, wb = _side_by_side([wa, wb])
     assert wlay_a.cstride != wlay_b.cstride and wlay_a.choff != wlay_b.choff and wlay_b.lead == wlay_a.lead + by
     keep = (wa.clone(), wb.clone())
-    ob_w, _ = _launch(capi, cuda, P, [(wa, wlay_a), (wb, wlay_b)], 3)
+    ob_w, _ = cd.launch(capi, cuda, P, [(wa, wlay_a), (wb, wlay_b)], _out(form), 3)
     assert _same_bits(wa, keep[0]) and _same_bits(wb, keep[1]), "the launch changed an input buffer"
-    outs_c = _outputs(P, ob_c, louts, 3)
-    outs_w = _outputs(P, ob_w, louts, 3)
+    outs_c = cd.outputs(P, ob_c, louts, _out(form))
+    outs_w = cd.outputs(P, ob_w, louts, _out(form))
     for gi in range(2):
         assert torch.equal(outs_w[gi], outs_c[gi]), "branch %d reads its buffer through the other's view" % gi
         assert outs_w[gi].abs().max().item() > 0
@@ -391,7 +204,7 @@ def test_branches_that_read_different_buffers(capi, cuda, form, shape):
     assert not torch.equal(outs_w[0], outs_w[1])
     if ref:
         for gi in range(2):
-            _check_reference(P, gi, outs_w[gi], P.xs[gi])
+            cd.check(P, gi, outs_w[gi], P.xs[gi])
 
 
 # ---- read and write one buffer: the OpenPose dense block --------------------------------------------------------------------------
@@ -407,16 +220,16 @@ def test_dense_block_reads_and_writes_one_buffer(capi, cuda, form, shape):
         assert form.m and c == 16
         c = 32
     lib = capi.lib
-    P = _problem(capi, cuda, form, n, h, w, c, c, 1, 0, 0, groups=2, seed=600 + c, ref=False)   # two filter banks: conv 1, conv 2
-    x0, lay = _compact(capi, cuda, P, P.xs[0], 1)
-    npx = _npx(capi, lay, n, h, w)
+    P = cd.pack_all(capi, cuda, cd.problem(form, n, h, w, c, c, 1, 0, 0, groups=2, seed=600 + c, ref=None))   # two filter banks: conv 1, conv 2
+    x0, lay = cd.to_layout(capi, cuda, P, P.xs[0], 1)
+    npx = cd.npx(capi, lay, n, h, w)
 
     def conv(gi, src, lsrc, dst, ldst):
         d = (capi.ConvDesc * 1)()
         d[0].inp, d[0].w_packed, d[0].bias_packed, d[0].out = src.data_ptr(), P.wp[gi].data_ptr(), P.bp[gi].data_ptr(), dst.data_ptr()
-        d[0].lin, d[0].lout = _L(capi, lsrc), _L(capi, ldst)
+        d[0].lin, d[0].lout = cd.L(capi, lsrc), cd.L(capi, ldst)
         d[0].cin, d[0].cout, d[0].k, d[0].relu, d[0].wino_m = c, c, 3, 1, form.m or 0
-        _call(capi, cuda, form, d, 1, n, h, w, True)
+        cd.call(capi, cuda, form, d, 1, n, h, w, True)
 
     # separate compact buffers
     t1, t2 = torch.zeros(npx * c, device=cuda), torch.zeros(npx * c, device=cuda)
@@ -436,7 +249,7 @@ def test_dense_block_reads_and_writes_one_buffer(capi, cuda, form, shape):
     assert t1.abs().max().item() > 0 and t2.abs().max().item() > 0
     # (slice equality over EVERY pixel covers the gaps; stated once more in the suite's exact form for slices 1 and 2)
     written = [lr.index(v, n, h, w, c) for v in views]
-    assert lr.untouched(_np_bits(blk), written, 0), "a conv wrote into the gaps of the shared buffer"
+    assert lr.untouched(cd.np_bits(blk), written, 0), "a conv wrote into the gaps of the shared buffer"
 
 
 # ---- rtpose_conv1x1_pair (fp32) ------------------------------------------------------------------------------------------------
@@ -455,19 +268,13 @@ def test_pointwise_pair_on_input_slices(capi, cuda, shape):
     w2 = [torch.randn(c, mid, 1, 1, generator=g) * (2.0 / mid) ** 0.5 for c in couts]
     b2 = [torch.randn(c, generator=g) * 0.1 for c in couts]
     lay = lr.padded(128, h, w, 0)
-    npx = _npx(capi, lay, n, h, w)
+    npx = cd.npx(capi, lay, n, h, w)
     keep = []
 
     def pack(wt, b, cout):
-        cin = wt.shape[1]
-        wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin, 1), device=cuda)
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=cuda)
-        wd, bd = wt.contiguous().to(cuda), b.to(cuda)
-        capi.check(lib.rtpose_pack_conv_weights(capi.ptr(wd), capi.ptr(bd), cout, cin, 1, None, cin, capi.ptr(wp), capi.ptr(bp),
-                                                stream))
-        torch.cuda.synchronize()
-        keep.extend([wp, bp])
-        return wp, bp
+        packed = cd.pack(capi, cuda, cd.Form("f32", 1), wt, b, wt.shape[1])
+        keep.extend(packed)
+        return packed
 
     p1 = [pack(w1[gi], b1[gi], mid) for gi in range(2)]
     p2 = [pack(w2[gi], b2[gi], couts[gi]) for gi in range(2)]
@@ -476,17 +283,17 @@ def test_pointwise_pair_on_input_slices(capi, cuda, shape):
     lmid = lr.padded(mid, h, w, 0)
 
     def run(inputs):
-        cat = torch.zeros(_npx(capi, lcat[0], n, h, w) * 192, device=cuda)
-        mids = [torch.zeros(_npx(capi, lmid, n, h, w) * mid, device=cuda) for _ in range(2)]
+        cat = torch.zeros(cd.npx(capi, lcat[0], n, h, w) * 192, device=cuda)
+        mids = [torch.zeros(cd.npx(capi, lmid, n, h, w) * mid, device=cuda) for _ in range(2)]
         d1, d2 = (capi.ConvDesc * 2)(), (capi.ConvDesc * 2)()
         for gi, (buf, l) in enumerate(inputs):
             d1[gi].inp, d1[gi].w_packed, d1[gi].bias_packed, d1[gi].out = (buf.data_ptr(), p1[gi][0].data_ptr(),
                                                                          p1[gi][1].data_ptr(), mids[gi].data_ptr())
-            d1[gi].lin, d1[gi].lout = _L(capi, l), _L(capi, lmid)
+            d1[gi].lin, d1[gi].lout = cd.L(capi, l), cd.L(capi, lmid)
             d1[gi].cin, d1[gi].cout, d1[gi].k, d1[gi].relu, d1[gi].pool = 128, mid, 1, 1, 0
             d2[gi].inp, d2[gi].w_packed, d2[gi].bias_packed, d2[gi].out = (mids[gi].data_ptr(), p2[gi][0].data_ptr(),
                                                                          p2[gi][1].data_ptr(), cat.data_ptr())
-            d2[gi].lin, d2[gi].lout = _L(capi, lmid), _L(capi, lcat[gi])
+            d2[gi].lin, d2[gi].lout = cd.L(capi, lmid), cd.L(capi, lcat[gi])
             d2[gi].cin, d2[gi].cout, d2[gi].k, d2[gi].relu, d2[gi].pool = mid, couts[gi], 1, 0, 0
         assert lib.rtpose_conv1x1_pair_fits(d1, d2, 2) == 1
         capi.check(lib.rtpose_conv1x1_pair(d1, d2, 2, n, h, w, stream), "rtpose_conv1x1_pair")
@@ -503,7 +310,7 @@ def test_pointwise_pair_on_input_slices(capi, cuda, shape):
         assert all(_same_bits(t, b) for (t, _), b in zip(wide, before)), "the launch changed an input buffer"
         assert _same_bits(cat_w, cat_c), "lin.cstride / lin.choff changed the result"
         host = cat_w.cpu()
-        assert lr.untouched(_np_bits(host), [lr.index(l, n, h, w, c) for l, c in zip(lcat, couts)], 0)
+        assert lr.untouched(cd.np_bits(host), [lr.index(l, n, h, w, c) for l, c in zip(lcat, couts)], 0)
         for gi in range(2):
             o = cs.slice_of(host, lcat[gi], n, h, w, couts[gi]).double()
             assert (o - refs[gi]).abs().max().item() <= TOL * max(1.0, refs[gi].abs().max().item())
@@ -516,7 +323,7 @@ LX = [(4, 0), (8, 4), (16, 8)]      # (cstride, choff) of the three image channe
 def _image_views(capi, dev, x, n, h, w):
     """the image as a compact 3-channel layout buffer and as the three LX slices of wider pixels"""
     lay = lr.padded(3, h, w, 1)
-    compact = cs.scatter_nchw(x, lay, _npx(capi, lay, n, h, w)).to(dev)
+    compact = cs.scatter_nchw(x, lay, cd.npx(capi, lay, n, h, w)).to(dev)
     return (compact, lay), [cs.widen(compact, lay, n, h, w, cstride - 3, choff, cstride) for cstride, choff in LX]
 
 
@@ -538,8 +345,8 @@ def test_first_layer_kernels_read_an_image_slice(capi, cuda, shape, bf16):
     entry = lib.rtpose_conv_first_bf16 if bf16 else lib.rtpose_conv_first
 
     def run(buf, lay):
-        obuf = torch.zeros(_npx(capi, lo, n, h, w) * lo.cstride, device=cuda, dtype=torch.bfloat16 if bf16 else torch.float32)
-        capi.check(entry(None, capi.ptr(buf), C.byref(_L(capi, lay)), capi.ptr(wp), capi.ptr(obuf), C.byref(_L(capi, lo)), 1,
+        obuf = torch.zeros(cd.npx(capi, lo, n, h, w) * lo.cstride, device=cuda, dtype=torch.bfloat16 if bf16 else torch.float32)
+        capi.check(entry(None, capi.ptr(buf), C.byref(cd.L(capi, lay)), capi.ptr(wp), capi.ptr(obuf), C.byref(cd.L(capi, lo)), 1,
                          n, h, w, stream), "rtpose_conv_first")
         torch.cuda.synchronize()
         return obuf
@@ -547,7 +354,7 @@ def test_first_layer_kernels_read_an_image_slice(capi, cuda, shape, bf16):
     (compact, lay), wides = _image_views(capi, cuda, x, n, h, w)
     ob_c = run(compact, lay)
     if bf16:
-        ref = F.relu(F.conv2d(tb._rb(x).double(), tb._rb(wt).double(), b.double(), padding=1)).float()
+        ref = F.relu(F.conv2d(cd.rb(x).double(), cd.rb(wt).double(), b.double(), padding=1)).float()
     else:
         ref = F.relu(F.conv2d(x.double(), wt.double(), b.double(), padding=1))
     for wide, wlay in wides:
@@ -555,10 +362,10 @@ def test_first_layer_kernels_read_an_image_slice(capi, cuda, shape, bf16):
         ob_w = run(wide, wlay)
         assert _same_bits(wide, before) and _same_bits(ob_w, ob_c), (wlay.cstride, wlay.choff)
         host = ob_w.cpu()
-        assert lr.untouched(_np_bits(host), lr.index(lo, n, h, w, 64), 0)
+        assert lr.untouched(cd.np_bits(host), lr.index(lo, n, h, w, 64), 0)
         out = cs.slice_of(host, lo, n, h, w, 64).float()
         if bf16:
-            tb._check(out, ref, False)
+            cd.check_bf16(out, ref, False)
         else:
             assert (out.double() - ref).abs().max().item() <= TOL * max(1.0, ref.abs().max().item())
 
@@ -578,9 +385,9 @@ def test_hourglass_stem_reads_an_image_slice(capi, cuda):
     lo = lr.padded(64 + 12, ho, wo, 1, 8)
 
     def run(buf, lay):
-        obuf = torch.zeros(_npx(capi, lo, n, ho, wo) * lo.cstride, device=cuda)
-        capi.check(lib.rtpose_conv7x7_s2(None, capi.ptr(buf), C.byref(_L(capi, lay)), capi.ptr(wp), capi.ptr(obuf),
-                                         C.byref(_L(capi, lo)), 1, n, h, w, capi.current_stream()), "rtpose_conv7x7_s2")
+        obuf = torch.zeros(cd.npx(capi, lo, n, ho, wo) * lo.cstride, device=cuda)
+        capi.check(lib.rtpose_conv7x7_s2(None, capi.ptr(buf), C.byref(cd.L(capi, lay)), capi.ptr(wp), capi.ptr(obuf),
+                                         C.byref(cd.L(capi, lo)), 1, n, h, w, capi.current_stream()), "rtpose_conv7x7_s2")
         torch.cuda.synchronize()
         return obuf
 
@@ -591,6 +398,6 @@ def test_hourglass_stem_reads_an_image_slice(capi, cuda):
         ob_w = run(wide, wlay)
         assert _same_bits(wide, before) and _same_bits(ob_w, ob_c), (wlay.cstride, wlay.choff)
         host = ob_w.cpu()
-        assert lr.untouched(_np_bits(host), lr.index(lo, n, ho, wo, 64), 0)
+        assert lr.untouched(cd.np_bits(host), lr.index(lo, n, ho, wo, 64), 0)
         out = cs.slice_of(host, lo, n, ho, wo, 64).double()
         assert (out - ref).abs().max().item() <= STEM7_TOL * max(1.0, ref.abs().max().item())

@@ -9,14 +9,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_driver as cd
 import conv_slices as cs
 import layout_restate as lr
-import test_conv_gpu as tc
-import test_wino7_f8_gpu as t87
-import test_wino_numerics_gpu as wn
-
-U = 2.0 ** -24
-STEM7_TOL = 2e-4          # tests/test_hourglass_gpu.py, restated as in tests/test_conv_input_slices_gpu.py
 
 
 def _bits(t):
@@ -115,8 +110,8 @@ def test_tiny_fp32_cases_discriminate(case):
 
     def tol_of(ref):
         if k == 7 and m == 8:      # F(8,7): the element-wise bound gamma * 2^-24 * sum |x| |w|
-            return t87.gamma_limit_f87(wt) * U * wn._ref64(x, wt, b, 7, None)[1]
-        return tc.TOL * max(1.0, ref.abs().max().item())
+            return cd.gamma_limit_f87(wt) * cd.U * cd.ref64(x, wt, b, 7, None)[1]
+        return cd.TOL * max(1.0, ref.abs().max().item())
 
     cin_e = (cin + 7) // 8 * 8
     _assert_discriminates(x, cin_e, k // 2, cs.UNIT_F32, cs.geometries(cin_e, cs.UNIT_F32), conv, tol_of)
@@ -131,7 +126,7 @@ def test_pointwise_pair_cases_discriminate(shape):
     w2 = torch.randn(38, mid, 1, 1, generator=g).double() * (2.0 / mid) ** 0.5
     conv = lambda v: F.conv2d(F.relu(F.conv2d(v.double(), w1)), w2)      # noqa: E731
     _assert_discriminates(x, 128, 0, cs.UNIT_F32, [("mid", 16, 8), ("end", 8, 8)], conv,
-                          lambda ref: tc.TOL * max(1.0, ref.abs().max().item()))
+                          lambda ref: cd.TOL * max(1.0, ref.abs().max().item()))
 
 
 @pytest.mark.parametrize("shape,k", [((3, 8, 8), 3), ((1, 37, 45), 3), ((1, 43, 33), 7)])
@@ -143,7 +138,7 @@ def test_first_layer_cases_discriminate(shape, k):
     x = torch.rand(n, 3, h, w, generator=g) - 0.5
     wt = torch.randn(64, 3, k, k, generator=g).double() * (2.0 / (3 * k * k)) ** 0.5
     conv = lambda v: F.relu(F.conv2d(v.double(), wt, None, stride=1 if k == 3 else 2, padding=k // 2))      # noqa: E731
-    tol = tc.TOL if k == 3 else STEM7_TOL
+    tol = cd.TOL if k == 3 else cd.STEM7_TOL
     geoms = [("lx", cstride - 3, choff) for cstride, choff in ((4, 0), (8, 4), (16, 8))]
     _assert_discriminates(x, 3, 1, 1, geoms, conv, lambda ref: tol * max(1.0, ref.abs().max().item()))
 

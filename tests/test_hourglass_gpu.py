@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import conv_driver as cd  # noqa: E402
 import hourglass_restate as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -204,15 +205,7 @@ def _from_layout(capi, cuda, buf, lay, c, n, h, w):
 
 
 def _packed(capi, cuda, wt, b, cin_packed):
-    lib = capi.lib
-    cout, cin = wt.shape[:2]
-    wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin_packed, 1), device=cuda)
-    bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=cuda)
-    wd, bd = wt.to(cuda).contiguous(), b.to(cuda)
-    capi.check(lib.rtpose_pack_conv_weights(capi.ptr(wd), capi.ptr(bd), cout, cin, 1, None, cin_packed, capi.ptr(wp),
-                                            capi.ptr(bp), None))
-    torch.cuda.synchronize()
-    return wp, bp
+    return cd.pack(capi, cuda, cd.Form("f32", 1), wt, b, cin_packed)
 
 
 def _sum(t):
@@ -343,7 +336,7 @@ def test_stem_7x7_stride_2(capi, cuda, n, h, w, src):
     assert abs(_sum(out) - _sum(got)) <= 1e-6 * max(1.0, _sum(got)), "wrote outside its slice"
     assert (ref == 0).any() and (ref > 0).any()
     err = (got - ref).abs().max().item()
-    assert err <= 2e-4 * max(1.0, ref.abs().max().item()), err
+    assert err <= cd.STEM7_TOL * max(1.0, ref.abs().max().item()), err
 
 
 @pytest.mark.parametrize("n,hl,wl,c", [(1, 3, 5, 256), (4, 24, 20, 256), (2, 48, 48, 64)])

@@ -11,16 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import test_wino_numerics_gpu as wn          # the suite's input / filter statistics and its float64 reference
+import conv_driver as cd          # the suite's input / filter statistics, its float64 reference and the F(8,7) limit
 import wino7_f8_restate as f87
-
-GAMMA_LIMIT_F67 = wn.GAMMA_LIMIT["F(6,7)"]   # 1000: the committed limit of F(6,7)
-
-
-def gamma_limit_f87(wts):
-    """F(6,7)'s limit scaled by the ratio of the two forms' amplification for THIS filter bank, from the exact rational
-    tables (not from the code under test): the element-wise error bound of a form is proportional to it."""
-    return GAMMA_LIMIT_F67 * f87.amp_exact(wts.numpy(), 8) / f87.amp_exact(wts.numpy(), 6)
 
 
 def test_toom_cook_identity_of_the_point_set():
@@ -143,16 +135,16 @@ def test_fp32_restatement_stays_under_the_gamma_limit(kw):
     Keeps that limit honest: the arithmetic of the form alone is inside it."""
     g = torch.Generator().manual_seed(8700 + len(kw))
     c, h, w, cout = 64, 12, 46, 16
-    wts = wn._weights(kw, cout, c, 7, g)
+    wts = cd.weights(kw, cout, c, 7, g)
     bias = torch.randn(cout, generator=g) * 0.1
-    limit = gamma_limit_f87(wts)
+    limit = cd.gamma_limit_f87(wts)
     assert 6000.0 < limit < 10000.0, limit
     worst = {}
-    for kx in wn.INPUT_KINDS:
-        x = wn._inputs(kx, 1, c, h, w, g)
+    for kx in cd.INPUT_KINDS:
+        x = cd.inputs(kx, 1, c, h, w, g)
         y = torch.from_numpy(f87.conv_rows_f87(x[0].numpy(), wts.numpy(), bias.numpy()))[None]
-        y64, s = wn._ref64(x, wts, bias, 7, (0, 13) if kx in wn.HETEROGENEOUS else None)
-        worst[kx] = ((y.double() - y64).abs() / (wn.U * s)).max().item()
+        y64, s = cd.ref64(x, wts, bias, 7, (0, 13) if kx in cd.HETEROGENEOUS else None)
+        worst[kx] = ((y.double() - y64).abs() / (cd.U * s)).max().item()
     print("F(8,7) restatement, %s filters: limit %.0f, gamma %s" % (kw, limit, {k: round(v, 1) for k, v in worst.items()}))
     assert all(v <= limit for v in worst.values()), (limit, worst)
     assert max(worst.values()) > 10.0           # (it IS the minimal-filtering form, not a direct sum in disguise)

@@ -12,26 +12,14 @@ the ratio taken from the exact rational tables (tests/wino7_f8_restate.py), not 
 with the direct kernel use the same bound plus the direct kernel's own (256)."""
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-import layout_restate as lr
-import test_wino_numerics_gpu as wn
+import conv_driver as cd
 import wino7_f8_restate as f87
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-SENTINEL = 0x7FC12345          # a quiet NaN with a recognisable payload
-
-
-def gamma_limit_f87(wts):
-    return wn.GAMMA_LIMIT["F(6,7)"] * f87.amp_exact(wts.numpy(), 8) / f87.amp_exact(wts.numpy(), 6)
-
-
-_note = wn._note       # measured figures of a passing test go where that suite's go (wino_gamma_f87.json, network_f87.json)
 
 
 def _conv7(capi, dev, x, wts, biases, form, relu=0, scratch=False, choff=1, extra_c=3, cin_pad=None):
@@ -39,63 +27,8 @@ def _conv7(capi, dev, x, wts, biases, form, relu=0, scratch=False, choff=1, extr
     m of F(m,7).  The branches write neighbouring channel slices (first at `choff`) of ONE buffer with `extra_c` more channels
     per pixel, filled with SENTINEL before the launch; every word outside the slices must still hold it.  Returns the
     outputs [n,cout,h,w] per branch (CPU)."""
-    lib, Layout = capi.lib, capi.Layout
-    n, cin, h, w = x.shape
-    groups, cout = len(wts), wts[0].shape[0]
-    cin_p = cin_pad or (cin + 7) // 8 * 8
-    stream = capi.current_stream()
-    lin = Layout.padded(cin_p, h, w, 3)
-    xin = torch.zeros(lib.rtpose_layout_pixels(C.byref(lin), n, h, w) * cin_p, device=dev)
-    xd = x.contiguous().to(dev)
-    capi.check(lib.rtpose_nchw_to_layout(capi.ptr(xd), capi.ptr(xin), C.byref(lin), cin, cin_p, n, h, w, stream))
-    cs = cout * groups + extra_c
-    lfull = Layout.padded(cs, h, w, 3)
-    nwords = lib.rtpose_layout_pixels(C.byref(lfull), n, h, w) * cs
-    obuf = torch.full((nwords,), SENTINEL, dtype=torch.int32, device=dev).view(torch.float32)
-    descs = (capi.ConvDesc * groups)()
-    keep = []
-    for gi in range(groups):
-        wd, bd = wts[gi].contiguous().to(dev), biases[gi].contiguous().to(dev)
-        bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=dev)
-        if form == "direct":
-            wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin_p, 7), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights(capi.ptr(wd), capi.ptr(bd), cout, cin, 7, None, cin_p, capi.ptr(wp),
-                                                    capi.ptr(bp), stream))
-        else:
-            wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd7(cout, cin_p, form), device=dev)
-            capi.check(lib.rtpose_pack_conv_weights_winograd7(capi.ptr(wd), capi.ptr(bd), cout, cin, form, None, cin_p,
-                                                              capi.ptr(wp), capi.ptr(bp), stream))
-        keep += [wd, bd, wp, bp]
-        d = descs[gi]
-        d.inp, d.w_packed, d.bias_packed, d.out = xin.data_ptr(), wp.data_ptr(), bp.data_ptr(), obuf.data_ptr()
-        d.lin = lin
-        d.lout = Layout.padded(cs, h, w, 3, choff=choff + gi * cout)
-        d.cin, d.cout, d.k, d.relu, d.pool = cin_p, cout, 7, int(relu), 0
-        d.wino_m = 0 if form == "direct" else form
-    if form == "direct":
-        capi.check(lib.rtpose_conv2d(descs, groups, n, h, w, stream), "rtpose_conv2d")
-    else:
-        assert lib.rtpose_conv2d_winograd_fits(descs, n, h, w) == 1
-        sc = torch.zeros(lib.rtpose_conv2d_winograd_scratch_bytes() // 4, dtype=torch.int32, device=dev) if scratch else None
-        capi.check(lib.rtpose_conv2d_winograd_ex(descs, groups, n, h, w, capi.ptr(sc) if scratch else None,
-                                                 sc.numel() * 4 if scratch else 0, stream), "rtpose_conv2d_winograd_ex")
-        if scratch:
-            word = C.c_int(-1)
-            capi.check(lib.rtpose_conv2d_winograd_scratch_error(capi.ptr(sc), C.byref(word), stream))
-            assert word.value == 0, "device error word %d" % word.value
-    outs = []
-    for gi in range(groups):
-        o = torch.empty(n, cout, h, w, device=dev)
-        lo = Layout.padded(cs, h, w, 3, choff=choff + gi * cout)
-        capi.check(lib.rtpose_layout_to_nchw(capi.ptr(obuf), C.byref(lo), capi.ptr(o), cout, n, h, w, stream))
-        outs.append(o.cpu())
-    torch.cuda.synchronize()
-    written = [lr.index(lr.padded(cs, h, w, 3, choff + gi * cout), n, h, w, cout) for gi in range(groups)]
-    assert lr.untouched(obuf.view(torch.int32).cpu().numpy().view(np.uint32), written, SENTINEL), \
-        "the launch wrote outside its channel slice"
-    for o in outs:
-        assert torch.isfinite(o).all(), "a pixel of the slice was not written"
-    return outs
+    P = cd.given(cd.Form("f32", 7, None if form == "direct" else form), [x], wts, biases, relu, cin_pad=cin_pad)
+    return cd.run(capi, dev, P, cd.sentinel(choff, extra_c), 3, 3, scratch)
 
 
 # ---- element-wise bound -------------------------------------------------------------------------------------------
@@ -111,19 +44,19 @@ def test_f87_elementwise_error_bound(capi, cuda, kw):
     profiles/r09_wino7_f8.txt yet - the emulation of the form stays at <= 624, F(6,7) measures 439 at worst.)"""
     g = torch.Generator().manual_seed(1000 + len(kw))
     n, c, h, w, cout = 2, 128, 46, 46, 128
-    wts = wn._weights(kw, cout, c, 7, g)
+    wts = cd.weights(kw, cout, c, 7, g)
     bias = torch.randn(cout, generator=g) * 0.1
-    limit = gamma_limit_f87(wts)
+    limit = cd.gamma_limit_f87(wts)
     assert 6000.0 < limit < 10000.0, limit
     failures = []
-    for kx in wn.INPUT_KINDS:
-        x = wn._inputs(kx, n, c, h, w, g)
+    for kx in cd.INPUT_KINDS:
+        x = cd.inputs(kx, n, c, h, w, g)
         y = _conv7(capi, cuda, x, [wts], [bias], 8, choff=0, extra_c=0)[0]
-        y64, s = wn._ref64(x, wts, bias, 7, (0, 13) if kx in wn.HETEROGENEOUS else None)
-        gamma = ((y.double() - y64).abs() / (U * s)).max().item()
+        y64, s = cd.ref64(x, wts, bias, 7, (0, 13) if kx in cd.HETEROGENEOUS else None)
+        gamma = ((y.double() - y64).abs() / (cd.U * s)).max().item()
         print("F(8,7) %s/%s gamma %.1f (limit %.0f)" % (kx, kw, gamma, limit))
         _GAMMAS["%s/%s" % (kx, kw)] = round(gamma, 2)
-        _note("wino_gamma_f87.json", {"unit": "|err| / (2^-24 * sum|x||w|), worst element", "gamma": _GAMMAS,
+        cd.note("wino_gamma_f87.json", {"unit": "|err| / (2^-24 * sum|x||w|), worst element", "gamma": _GAMMAS,
                                       "worst": max(_GAMMAS.values()), "limit/%s" % kw: limit})
         if not gamma <= limit:
             failures.append((kx, kw, gamma, limit))
@@ -136,15 +69,15 @@ def _check_against_direct_and_f64(capi, cuda, x, wts, biases, relu, scratch=Fals
     f8 = _conv7(capi, cuda, x, wts, biases, 8, relu=relu, scratch=scratch)
     dr = _conv7(capi, cuda, x, wts, biases, "direct", relu=relu)
     for gi in range(len(wts)):
-        lim8 = gamma_limit_f87(wts[gi])
+        lim8 = cd.gamma_limit_f87(wts[gi])
         sel = slice(None) if f64_images is None else f64_images     # (the float64 sums are the slow part of a case)
-        y64, s = wn._ref64(x[sel], wts[gi], biases[gi], 7, None)
+        y64, s = cd.ref64(x[sel], wts[gi], biases[gi], 7, None)
         if relu:
             y64 = F.relu(y64)          # (ReLU is 1-Lipschitz: the bound of the pre-activation holds for the output)
-        e64 = ((f8[gi][sel].double() - y64).abs() / (U * s)).max().item()
+        e64 = ((f8[gi][sel].double() - y64).abs() / (cd.U * s)).max().item()
         assert e64 <= lim8, ("float64", gi, e64, lim8)
-        ed = ((f8[gi][sel].double() - dr[gi][sel].double()).abs() / (U * s)).max().item()
-        assert ed <= lim8 + wn.GAMMA_LIMIT["direct7"], ("direct", gi, ed)
+        ed = ((f8[gi][sel].double() - dr[gi][sel].double()).abs() / (cd.U * s)).max().item()
+        assert ed <= lim8 + cd.GAMMA_LIMIT["direct7"], ("direct", gi, ed)
     return f8
 
 
@@ -261,7 +194,7 @@ def test_network_with_the_form_forced_stays_in_contract(model_f87, cuda):
                   % (name, ws, wf))
     finally:
         m.set_winograd()
-    _note("network_f87.json", worst)
+    cd.note("network_f87.json", worst)
     # the F(8,7) plans have an arena of their own, everything else still shares the original one
     keys = sorted(m._weights, key=repr)
     assert [k for k in keys if len(k) == 2] == [(cuda.index or 0, 0)] and [k for k in keys if len(k) == 3] == [(cuda.index or 0, 0, 'f87')]
@@ -310,7 +243,7 @@ def test_f87_amplification_estimate_matches_its_definition(capi, cuda):
     g = torch.Generator().manual_seed(5)
     amp = torch.zeros(1, device=cuda)
     for kind in ("he", "pos", "smooth"):
-        wts = wn._weights(kind, 24, 40, 7, g)
+        wts = cd.weights(kind, 24, 40, 7, g)
         wd = wts.to(cuda)
         got = {}
         for m in (6, 8):

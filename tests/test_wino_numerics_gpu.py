@@ -20,151 +20,33 @@ activations and positive biases, the fp32 tier-B end-to-end check (GPU net -> GP
 on the 32 bench images, evaluate/coco_eval.py:270-272) and the runtime hardening (caller-owned scratch, graph replay
 with persistent launches, hardware bounds clamp)."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_driver as cd
+from conv_driver import GAMMA_LIMIT, HETEROGENEOUS, INPUT_KINDS, U
+
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# gamma limits (own receptive field; dilated S for the spatially heterogeneous inputs).  Measured on MI355X (see
-# profiles/r03_wino_gamma.json / DESIGN.md §3.0): the limits are ~2x the worst measured value of each form.
-# Worst measured (28 input x filter statistics each): direct3 30, F(2x2,3x3) 18, direct7 120, F(4,7) 277, F(6,7) 439;
-# zero-mean Gaussian inputs and filters: 4.3, 2.1, 5.3, 51, 108.
-GAMMA_LIMIT = {"direct3": 64.0, "F(2x2,3x3)": 48.0, "F(4x4,3x3)": 100.0, "direct7": 256.0, "F(4,7)": 600.0,
-               "F(6,7)": 1000.0}
-HETEROGENEOUS = ("logu_px", "heavy")
-
-
-def _inputs(kind, n, c, h, w, g):
-    r = lambda *s: torch.randn(*s, generator=g)   # noqa: E731
-    if kind == "randn":
-        return r(n, c, h, w)
-    if kind == "relu":                     # non-negative, mean ~ std
-        return F.relu(r(n, c, h, w))
-    if kind == "relu_mean":                # non-negative, mean >> std (100x)
-        return F.relu(r(n, c, h, w)) * 0.05 + 5.0
-    if kind == "logu_ch":                  # channel magnitudes log-uniform over six decades
-        return r(n, c, h, w) * 10.0 ** (torch.rand(1, c, 1, 1, generator=g) * 6 - 3)
-    if kind == "logu_px":                  # every element its own magnitude, six decades
-        return r(n, c, h, w) * 10.0 ** (torch.rand(n, c, h, w, generator=g) * 6 - 3)
-    if kind == "ramp":                     # smooth ramps on a large offset
-        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
-        return 100.0 + 0.7 * xx + 0.3 * yy + 0.01 * r(n, c, h, w)
-    if kind == "heavy":                    # heavy-tailed, non-negative
-        return r(n, c, h, w).abs() ** 4
-    raise KeyError(kind)
-
-
-def _weights(kind, cout, cin, k, g):
-    r = lambda *s: torch.randn(*s, generator=g)   # noqa: E731
-    he = (2.0 / (cin * k * k)) ** 0.5
-    if kind == "he":
-        return r(cout, cin, k, k) * he
-    if kind == "pos":                      # all-positive filters: nothing cancels in the direct sum
-        return r(cout, cin, k, k).abs() * he
-    if kind == "smooth":                   # separable Gaussian bumps (what trained 7x7 filters tend to)
-        t = torch.arange(k, dtype=torch.float32) - k // 2
-        gk = torch.exp(-t * t / (2 * (k / 4.0) ** 2))
-        return (gk[:, None] * gk[None, :])[None, None] * r(cout, cin, 1, 1) * he
-    if kind == "ref_init_x30":             # the reference's own init N(0, 0.01) (rtpose_vgg.py:200-222), scaled up
-        return r(cout, cin, k, k) * 0.3
-    raise KeyError(kind)
 
 
 def _gpu_conv(capi, dev, x, wts, bias, k, form, relu=0, pool=0):
-    """x [n,cin,h,w], wts [cout,cin,k,k] (CPU fp32) through the C ABI; form: 'direct', 3 (F(2x2,3x3)), 43 (F(4x4,3x3)),
-    4 or 6 (F(m,7))."""
-    lib, Layout = capi.lib, capi.Layout
-    n, cin, h, w = x.shape
-    cout = wts.shape[0]
-    pad = k // 2
-    stream = capi.current_stream()
-    lin = Layout.padded(cin, h, w, pad)
-    xin = torch.zeros(lib.rtpose_layout_pixels(C.byref(lin), n, h, w) * cin, device=dev)
-    xd = x.contiguous().to(dev)
-    capi.check(lib.rtpose_nchw_to_layout(capi.ptr(xd), capi.ptr(xin), C.byref(lin), cin, cin, n, h, w, stream))
-    ho, wo = (h // 2, w // 2) if pool else (h, w)
-    lout = Layout.padded(cout, ho, wo, 1)
-    obuf = torch.zeros(lib.rtpose_layout_pixels(C.byref(lout), n, ho, wo) * cout, device=dev)
-    wd, bd = wts.contiguous().to(dev), bias.contiguous().to(dev)
-    bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=dev)
-    if form == "direct":
-        wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin, k), device=dev)
-        capi.check(lib.rtpose_pack_conv_weights(capi.ptr(wd), capi.ptr(bd), cout, cin, k, None, cin, capi.ptr(wp),
-                                                capi.ptr(bp), stream))
-    elif form == 3:
-        wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd(cout, cin, 3), device=dev)
-        capi.check(lib.rtpose_pack_conv_weights_winograd(capi.ptr(wd), capi.ptr(bd), cout, cin, 3, None, cin,
-                                                         capi.ptr(wp), capi.ptr(bp), stream))
-    elif form == 43:
-        wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd3(cout, cin, 4), device=dev)
-        capi.check(lib.rtpose_pack_conv_weights_winograd3(capi.ptr(wd), capi.ptr(bd), cout, cin, 4, None, cin,
-                                                          capi.ptr(wp), capi.ptr(bp), stream))
-    else:
-        wp = torch.zeros(lib.rtpose_packed_weight_floats_winograd7(cout, cin, form), device=dev)
-        capi.check(lib.rtpose_pack_conv_weights_winograd7(capi.ptr(wd), capi.ptr(bd), cout, cin, form, None, cin,
-                                                          capi.ptr(wp), capi.ptr(bp), stream))
-    d = (capi.ConvDesc * 1)()
-    d[0].inp, d[0].w_packed, d[0].bias_packed, d[0].out = xin.data_ptr(), wp.data_ptr(), bp.data_ptr(), obuf.data_ptr()
-    d[0].lin, d[0].lout = lin, lout
-    d[0].cin, d[0].cout, d[0].k, d[0].relu, d[0].pool = cin, cout, k, relu, pool
-    d[0].wino_m = form if form in (4, 6) else 4 if form == 43 else 0
-    if form == "direct":
-        capi.check(lib.rtpose_conv2d(d, 1, n, h, w, stream), "rtpose_conv2d")
-    else:
-        assert lib.rtpose_conv2d_winograd_fits(d, n, h, w) == 1
-        capi.check(lib.rtpose_conv2d_winograd(d, 1, n, h, w, stream), "rtpose_conv2d_winograd")
-    o = torch.empty(n, cout, ho, wo, device=dev)
-    capi.check(lib.rtpose_layout_to_nchw(capi.ptr(obuf), C.byref(lout), capi.ptr(o), cout, n, ho, wo, stream))
-    torch.cuda.synchronize()
-    return o.cpu()
-
-
-def _ref64(x, wts, bias, k, dil):
-    """float64 direct sum and the bound quantity S (with |x| dilated by `dil` = (ry, rx) pixels if given)."""
-    y = F.conv2d(x.double(), wts.double(), bias.double(), padding=k // 2)
-    ax = x.abs().double()
-    if dil is not None:
-        ry, rx = dil
-        ax = F.max_pool2d(ax, (2 * ry + 1, 2 * rx + 1), stride=1, padding=(ry, rx))
-    s = F.conv2d(ax, wts.abs().double(), bias.abs().double(), padding=k // 2)
-    return y, s
+    """x [n,cin,h,w], wts [cout,cin,k,k] (CPU fp32) through the C ABI; form: 'direct', 3 (F(2x2,3x3): the library's default
+    form, wino_m = 0), 43 (F(4x4,3x3)), 4 or 6 (F(m,7)).  The Winograd forms go through rtpose_conv2d_winograd."""
+    fm = cd.Form("f32", k, {"direct": None, 3: 0, 43: 4}.get(form, form), entry="noex")
+    P = cd.given(fm, [x], [wts], [bias], relu, pool, cin_pad=x.shape[1])
+    return cd.run(capi, dev, P, cd.PLAIN, k // 2, 1)[0]
 
 
 _GAMMAS = {}
 
 
-def _note(name, obj):
-    """Measured figures of a passing test, for DESIGN.md / profiles/ (gpurun_out/ travels back from the GPU box)."""
-    out = os.path.join(ROOT, "gpurun_out")
-    try:
-        os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, name), "w") as f:
-            json.dump(obj, f, indent=1, sort_keys=True)
-    except OSError:
-        pass
-
-
 def _record(form, kx, kw, g):
     _GAMMAS.setdefault(form, {})["%s/%s" % (kx, kw)] = round(float(g), 2)
-    out = os.path.join(ROOT, "gpurun_out")
-    try:
-        os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, "wino_gamma.json"), "w") as f:
-            json.dump({"unit": "|err| / (2^-24 * sum|x||w|), worst element", "gamma": _GAMMAS,
-                       "worst": {k: max(v.values()) for k, v in _GAMMAS.items()}}, f, indent=1, sort_keys=True)
-    except OSError:
-        pass
-
-
-INPUT_KINDS = ("randn", "relu", "relu_mean", "logu_ch", "logu_px", "ramp", "heavy")
+    cd.note("wino_gamma.json", {"unit": "|err| / (2^-24 * sum|x||w|), worst element", "gamma": _GAMMAS,
+                                "worst": {k: max(v.values()) for k, v in _GAMMAS.items()}})
 
 
 @pytest.mark.parametrize("kw", ("he", "pos", "smooth", "ref_init_x30"))
@@ -172,15 +54,15 @@ def test_7x7_forms_elementwise_error_bound(capi, cuda, kw):
     """128 -> 128 at 2 x 46 x 46 (the Mconv2..5_stageN geometry: the <1,8,6> instance of the headline kernel)."""
     g = torch.Generator().manual_seed(1000 + len(kw))
     n, c, h, w, cout = 2, 128, 46, 46, 128
-    wts = _weights(kw, cout, c, 7, g)
+    wts = cd.weights(kw, cout, c, 7, g)
     bias = torch.randn(cout, generator=g) * 0.1
     failures = []
     for kx in INPUT_KINDS:
-        x = _inputs(kx, n, c, h, w, g)
+        x = cd.inputs(kx, n, c, h, w, g)
         outs = {f: _gpu_conv(capi, cuda, x, wts, bias, 7, f) for f in ("direct", 4, 6)}
         for f, name, reach in (("direct", "direct7", 0), (4, "F(4,7)", 9), (6, "F(6,7)", 11)):
             het = kx in HETEROGENEOUS and reach
-            y64, s = _ref64(x, wts, bias, 7, (0, reach) if het else None)
+            y64, s = cd.ref64(x, wts, bias, 7, (0, reach) if het else None)
             gamma = ((outs[f].double() - y64).abs() / (U * s)).max().item()
             _record(name, kx, kw, gamma)
             if not gamma <= GAMMA_LIMIT[name]:
@@ -195,14 +77,14 @@ def test_3x3_form_elementwise_error_bound(capi, cuda, kw):
     g = torch.Generator().manual_seed(2000 + len(kw))
     failures = []
     for (n, c, h, w, cout) in ((2, 128, 46, 46, 128), (1, 64, 48, 40, 64)):
-        wts = _weights(kw, cout, c, 3, g)
+        wts = cd.weights(kw, cout, c, 3, g)
         bias = torch.randn(cout, generator=g) * 0.1
         for kx in INPUT_KINDS:
-            x = _inputs(kx, n, c, h, w, g)
+            x = cd.inputs(kx, n, c, h, w, g)
             outs = {f: _gpu_conv(capi, cuda, x, wts, bias, 3, f) for f in ("direct", 3, 43)}
             for f, name in (("direct", "direct3"), (3, "F(2x2,3x3)"), (43, "F(4x4,3x3)")):
                 het = kx in HETEROGENEOUS and f != "direct"
-                y64, s = _ref64(x, wts, bias, 3, ((5, 5) if f == 43 else (3, 3)) if het else None)
+                y64, s = cd.ref64(x, wts, bias, 3, ((5, 5) if f == 43 else (3, 3)) if het else None)
                 gamma = ((outs[f].double() - y64).abs() / (U * s)).max().item()
                 _record(name, kx, kw, gamma)
                 if not gamma <= GAMMA_LIMIT[name]:
@@ -223,7 +105,7 @@ def test_f43_kernel_against_its_cpu_restatement(capi, cuda):
         bias = torch.randn(cout, generator=g) * 0.1
         y_gpu = _gpu_conv(capi, cuda, x, wts, bias, 3, 43)
         y_cpu = torch.from_numpy(np.stack([conv3x3_f43(x[i].numpy(), wts.numpy(), bias.numpy()) for i in range(n)]))
-        _, s = _ref64(x, wts, bias, 3, None)
+        _, s = cd.ref64(x, wts, bias, 3, None)
         d = (y_gpu.double() - y_cpu.double()).abs()
         assert (d / (U * s)).max().item() <= 2 * GAMMA_LIMIT["F(4x4,3x3)"]
         assert d.max().item() <= 2e-5 * max(1.0, y_cpu.abs().max().item())
@@ -258,7 +140,7 @@ def test_amplification_estimate_matches_its_definition(capi, cuda):
     seen = {}
     for kind in ("he", "pos", "smooth"):
         for k, m in ((3, 0), (3, 4), (7, 4), (7, 6)):
-            wts = _weights(kind, 24, 40, k, g)
+            wts = cd.weights(kind, 24, 40, k, g)
             wd = wts.to(cuda)
             capi.check(lib.rtpose_winograd_amplification(capi.ptr(wd), 24, 40, k, m, capi.ptr(amp),
                                                          capi.current_stream()))
@@ -539,7 +421,7 @@ def test_network_on_unnormalised_inputs_large_activations_and_positive_biases(pk
     m.load_state_dict(sd_c)
     w2, mx2 = _check_stages(m, sd_c, x - 0.5, cuda, "all biases +0.25")
     assert m.device_status(plan) == 0
-    _note("hostile_network_%dx%dx%d.json" % shape,
+    cd.note("hostile_network_%dx%dx%d.json" % shape,
           {"unit": "worst |err| / max(1, max|ref|) over the 12 stage outputs", "x = rand * 255": [w0, mx0],
            "first layer x 1000": [w1, mx1], "all biases +0.25": [w2, mx2]})
 
@@ -581,7 +463,7 @@ def test_tier_b_fp32_end_to_end_keypoints_on_the_32_bench_images(pkg, model_and_
             same += int((d.max(axis=1) == 0).sum())
             people += len(r["parts"])
     assert people >= 32 and tot >= 500
-    _note("tier_b.json", {"images": n, "people": people, "keypoints": tot, "identical": same})
+    cd.note("tier_b.json", {"images": n, "people": people, "keypoints": tot, "identical": same})
     assert same >= 0.998 * tot
 
 
@@ -640,26 +522,16 @@ def test_reads_past_the_tensor_are_clamped_by_the_buffer_descriptor(capi, cuda):
         lin = Layout.padded(cin, h, w, pad)
         lout = Layout.padded(cout, h, w, 1)
         nin = lib.rtpose_layout_pixels(C.byref(lin), n, h, w) * cin
-        nw = (lib.rtpose_packed_weight_floats_winograd3(cout, cin, 4) if form == 43
-              else lib.rtpose_packed_weight_floats_winograd(cout, cin, 3) if k == 3
-              else lib.rtpose_packed_weight_floats_winograd7(cout, cin, form))
+        fm = cd.Form("f32", k, {3: 0, 43: 4}.get(form, form))
+        nw = cd.packed_numel(capi, fm, cout, cin)
         res = []
         for fill in (0.0, float("nan")):
             arena = torch.full((nin + nw + (1 << 20),), fill, device=cuda)
             xin, wp = arena[:nin], arena[nin:nin + nw]
             xin.zero_()
             wp.zero_()
-            bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), device=cuda)
             capi.check(lib.rtpose_nchw_to_layout(capi.ptr(x), capi.ptr(xin), C.byref(lin), cin, cin, n, h, w, stream))
-            if form == 43:
-                capi.check(lib.rtpose_pack_conv_weights_winograd3(capi.ptr(wts), capi.ptr(b), cout, cin, 4, None, cin,
-                                                                  capi.ptr(wp), capi.ptr(bp), stream))
-            elif k == 3:
-                capi.check(lib.rtpose_pack_conv_weights_winograd(capi.ptr(wts), capi.ptr(b), cout, cin, 3, None, cin,
-                                                                 capi.ptr(wp), capi.ptr(bp), stream))
-            else:
-                capi.check(lib.rtpose_pack_conv_weights_winograd7(capi.ptr(wts), capi.ptr(b), cout, cin, form, None,
-                                                                  cin, capi.ptr(wp), capi.ptr(bp), stream))
+            _, bp = cd.pack(capi, cuda, fm, wts, b, cin, into=wp)
             obuf = torch.zeros(lib.rtpose_layout_pixels(C.byref(lout), n, h, w) * cout, device=cuda)
             d = (capi.ConvDesc * 1)()
             d[0].inp, d[0].w_packed, d[0].bias_packed, d[0].out = xin.data_ptr(), wp.data_ptr(), bp.data_ptr(), obuf.data_ptr()
