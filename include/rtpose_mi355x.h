@@ -159,6 +159,47 @@ typedef struct rtpose_conv_desc {
 int rtpose_conv2d(const rtpose_conv_desc* d, int ngroups, int N, int H, int W,
                   void* stream);
 
+/* ---- 2b. Backward pass of these convs: what `total_loss.backward()` of train/train_VGG19.py:216 runs through
+ * nn.Conv2d + nn.ReLU (ATen convolution_backward and threshold_backward on the reference).  csrc/conv_backward.hip.
+ *
+ * Weight gradient (+ bias gradient) of a stride-1 "same" conv, k in {1, 3, 7}:
+ *     dw[o][c][dy][dx] = sum over (n, y, x) of gy[n, y, x, o] * x[n, y + dy - k/2, x + dx - k/2, c]
+ *     dbias[o]         = sum over (n, y, x) of gy[n, y, x, o]                         (dbias != NULL)
+ * `x` / `lx` is the conv's input slice: `cin` real channels from lx.choff, zero gaps of at least k/2 (the tap is the
+ * constant pixel offset of §1, no bounds test); `gy` / `lgy` the gradient with respect to the conv's output: `cout`
+ * channels from lgy.choff, read at the valid pixels only.  cin and cout are any value >= 1 and need no alignment:
+ * channels outside the two slices are never read.  `dw` is dense OIHW fp32 (the shape of nn.Conv2d.weight), `dbias`
+ * cout floats; both are OVERWRITTEN.  fp32 operands, fp32 accumulate (v_mfma_f32_32x32x2_f32).  The valid pixels are
+ * cut, in (n, y, x) order, into rtpose_conv2d_wgrad_slabs() slabs that depend on the shape only - equal multiples of
+ * 32 pixels but for the last one, across image boundaries; every slab's partial sums go to
+ * `workspace` (device memory of the caller, rtpose_conv2d_wgrad_workspace_floats() floats, 16-byte aligned as `dw`)
+ * and a second launch adds them in slab order: no atomics, the same inputs give the same bits on every run.
+ * ZERO-INITIALISE the descriptor. */
+typedef struct rtpose_wgrad_desc {
+  const float* x;
+  const float* gy;
+  float* dw;
+  float* dbias;     /* or NULL */
+  float* workspace;
+  size_t workspace_floats;
+  rtpose_layout lx;
+  rtpose_layout lgy;
+  int32_t cin;
+  int32_t cout;
+  int32_t k;
+} rtpose_wgrad_desc;
+size_t rtpose_conv2d_wgrad_workspace_floats(int cin, int cout, int k, int N, int H, int W);
+int rtpose_conv2d_wgrad_slabs(int cin, int cout, int k, int N, int H, int W);
+int rtpose_conv2d_wgrad(const rtpose_wgrad_desc* d, int N, int H, int W, void* stream);
+/* out = y > 0 ? gy : 0 over `channels` channels of the valid pixels (the gradient through a conv's fused ReLU, from the
+ * conv's OUTPUT y): gaps are neither read nor written, so a zero-initialised `out` keeps its zero gaps and stays
+ * convolvable.  Every element reads only its own gy element: out / lout may name the slice gy / lgy name.
+ *
+ * Data gradient: no entry point of its own.  The gradient with respect to a conv's input is rtpose_conv2d (relu = 0,
+ * zero bias) of gy with the filter w.flip(2, 3).transpose(0, 1), packed by rtpose_pack_conv_weights. */
+int rtpose_relu_grad(const float* y, const rtpose_layout* ly, const float* gy, const rtpose_layout* lgy,
+                     float* out, const rtpose_layout* lout, int channels, int N, int H, int W, void* stream);
+
 /* ---- the first layer: nn.Conv2d(3, 64, 3, 1, 1) (+ nn.ReLU), conv1_1 of the VGG-19 front end
  * (lib/network/rtpose_vgg.py:23-35, `model0.0`; csrc/conv_first.hip).  Reads the image where it is -
  * dense NCHW fp32 (`x_nchw`), or, with x_nchw = NULL, a layout buffer with >= 3 channels per pixel

@@ -47,6 +47,13 @@ class ConvDesc(C.Structure):
                 ("in_scale", C.c_void_p), ("in_shift", C.c_void_p), ("lres", Layout), ("preact_cin", C.c_int32)]
 
 
+class WgradDesc(C.Structure):
+    """rtpose_wgrad_desc: one weight-gradient launch (header section 2b)."""
+    _fields_ = [("x", C.c_void_p), ("gy", C.c_void_p), ("dw", C.c_void_p), ("dbias", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_floats", C.c_size_t), ("lx", Layout), ("lgy", Layout),
+                ("cin", C.c_int32), ("cout", C.c_int32), ("k", C.c_int32)]
+
+
 class NetOptions(C.Structure):
     """rtpose_net_options: per-plan arithmetic of the fp32 convs (header §3)."""
     _fields_ = [("struct_bytes", C.c_uint32), ("dtype", C.c_int32), ("winograd3", C.c_int32),
@@ -177,6 +184,10 @@ _SIGS = {
     "rtpose_packed_bias_floats": (_sz, [_i]),
     "rtpose_pack_conv_weights": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "rtpose_conv2d": (_i, [C.POINTER(ConvDesc), _i, _i, _i, _i, _vp]),
+    "rtpose_conv2d_wgrad_workspace_floats": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "rtpose_conv2d_wgrad_slabs": (_i, [_i, _i, _i, _i, _i, _i]),
+    "rtpose_conv2d_wgrad": (_i, [C.POINTER(WgradDesc), _i, _i, _i, _vp]),
+    "rtpose_relu_grad": (_i, [_vp, _LP, _vp, _LP, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),
     "rtpose_conv1x1_pair": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_bf16_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),

@@ -1,0 +1,242 @@
+"""Training through the library's kernels: ``loss.backward()`` and ``optimizer.step()`` of the reference's loop
+(train/train_VGG19.py:194-217) on an ``RtposeVGG``.
+
+PyTorch keeps the graph and the optimizer; every convolution of it, forward and backward, is hand-written HIP:
+
+* ``conv2d(x, weight, bias, relu)`` is a ``torch.autograd.Function`` on NCHW fp32 device tensors.  Forward: the library's
+  NCHW -> layout conversion, ``rtpose_conv2d`` (fp32 direct kernel, bias and ReLU fused as in inference), layout -> NCHW.
+  Backward: ``rtpose_relu_grad`` through the fused ReLU, the data gradient as ``rtpose_conv2d`` on the flipped, transposed
+  filter (``dgrad_weights``), the weight and bias gradients by ``rtpose_conv2d_wgrad``.  A conv whose parameters are
+  frozen launches no weight gradient, a conv whose input needs no gradient (the first trainable conv behind a frozen trunk
+  or behind the image) no data gradient.  All launches go on the current stream; every buffer comes from torch's caching
+  allocator.  The Winograd forms are not used here: their error contracts were set for the forward statistics.
+* ``forward_train(model, x)`` is the reference's forward order (lib/network/rtpose_vgg.py:158-198) over the module tree of
+  an ``RtposeVGG`` with graph-carrying tensors; ``model.forward`` (the inference plan) is untouched.
+* ``train_step`` is one iteration of the reference's loop, ``freeze_trunk`` its ``requires_grad = False`` preamble (:305-307).
+
+The NCHW <-> layout conversion around every conv is known overhead; activations do not stay in layouts across layers yet.
+"""
+import ctypes as C
+import weakref
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _capi, encode
+from ._capi import lib, check, ptr, current_stream
+
+
+def dgrad_weights(weight):
+    """The filter whose stride-1 "same" conv of gy is the gradient with respect to the input of conv(x, weight):
+    taps flipped, in / out axes swapped.  [cout, cin, k, k] -> [cin, cout, k, k]."""
+    return weight.flip(2, 3).transpose(0, 1).contiguous()
+
+
+def _up8(c):
+    return (c + 7) // 8 * 8
+
+
+# ---- packed filters, per parameter (_version, data_ptr), as _native_state.py keys the forward arenas ------------------------
+_packed = {}   # id(weight) -> {'fwd': (key, w_packed, b_packed), 'bwd': (key, w_packed, b_packed)}
+
+
+def _pack(weight, bias, cin_p):
+    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+    wp = torch.zeros(lib.rtpose_packed_weight_floats(cout, cin_p, k), dtype=torch.float32, device=weight.device)
+    bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), dtype=torch.float32, device=weight.device)
+    check(lib.rtpose_pack_conv_weights(ptr(weight), ptr(bias), cout, cin, k, None, cin_p, ptr(wp), ptr(bp), current_stream()),
+          "rtpose_pack_conv_weights")
+    return wp, bp
+
+
+def _packed_for(weight, bias, which):
+    """The packing of `weight` (+ `bias`) for the forward ('fwd') or of its flipped, transposed form for the data gradient
+    ('bwd', zero bias), re-packed when the parameter's (_version, data_ptr) changed."""
+    entry = _packed.get(id(weight))
+    if entry is None or entry['ref']() is not weight:
+        entry = _packed[id(weight)] = {'ref': weakref.ref(weight)}
+        weakref.finalize(weight, _packed.pop, id(weight), None)
+    key = (weight._version, weight.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    if which == 'fwd' and bias is not None:
+        key += (bias._version, bias.data_ptr())
+    hit = entry.get(which)
+    if hit is not None and hit[0] == key:
+        return hit[1], hit[2]
+    w = weight.detach()
+    if which == 'fwd':
+        b = bias.detach() if bias is not None else torch.zeros(w.shape[0], dtype=torch.float32, device=w.device)
+        wp, bp = _pack(w.contiguous(), b.contiguous(), _up8(w.shape[1]))
+    else:
+        wt = dgrad_weights(w)
+        wp, bp = _pack(wt, torch.zeros(wt.shape[0], dtype=torch.float32, device=w.device), _up8(wt.shape[1]))
+    entry[which] = (key, wp, bp)
+    return wp, bp
+
+
+# ---- layout buffers ---------------------------------------------------------------------------------------------------------
+def _buffer(lay, n, h, w, device, zero):
+    numel = lib.rtpose_layout_pixels(C.byref(lay), n, h, w) * lay.cstride
+    return (torch.zeros if zero else torch.empty)(numel, dtype=torch.float32, device=device)
+
+
+def _to_layout(t, pad):
+    """NCHW -> a zero-gapped layout buffer with the channels rounded up to 8 (the extra ones zero)."""
+    n, c, h, w = t.shape
+    lay = _capi.Layout.padded(_up8(c), h, w, pad)
+    buf = _buffer(lay, n, h, w, t.device, True)
+    check(lib.rtpose_nchw_to_layout(ptr(t), ptr(buf), C.byref(lay), c, lay.cstride, n, h, w, current_stream()),
+          "rtpose_nchw_to_layout")
+    return buf, lay
+
+
+def _from_layout(buf, lay, n, c, h, w):
+    out = torch.empty((n, c, h, w), dtype=torch.float32, device=buf.device)
+    check(lib.rtpose_layout_to_nchw(ptr(buf), C.byref(lay), ptr(out), c, n, h, w, current_stream()), "rtpose_layout_to_nchw")
+    return out
+
+
+def _launch_conv(inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
+    """rtpose_conv2d of a layout buffer into a new dense one: (buffer, layout)"""
+    lout = _capi.Layout.dense(_up8(cout), h, w)
+    out = _buffer(lout, n, h, w, inp.device, False)
+    d = _capi.ConvDesc()
+    d.inp, d.w_packed, d.bias_packed, d.out = inp.data_ptr(), wp.data_ptr(), bp.data_ptr(), out.data_ptr()
+    d.lin, d.lout = lin, lout
+    d.cin, d.cout, d.k, d.relu = cin_p, cout, k, 1 if relu else 0
+    check(lib.rtpose_conv2d(C.byref(d), 1, n, h, w, current_stream()), "rtpose_conv2d")
+    return out, lout
+
+
+def _check_input(x, weight):
+    if not (x.is_cuda and weight.is_cuda):
+        raise _capi.RtposeError("train.conv2d runs only on an MI355X (HIP) device; got x on %s, weight on %s - there is "
+                                "deliberately no CPU fallback" % (x.device, weight.device))
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or weight.dim() != 4:
+        raise _capi.RtposeError("train.conv2d takes NCHW fp32 inputs and OIHW fp32 filters")
+    k = weight.shape[2]
+    if weight.shape[3] != k or k not in (1, 3, 7) or weight.shape[1] != x.shape[1]:
+        raise _capi.RtposeError("train.conv2d: stride-1 'same' convs with k in {1, 3, 7}; got filters %s for input %s"
+                                % (tuple(weight.shape), tuple(x.shape)))
+
+
+class _Conv2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        _check_input(x, weight)
+        with torch.cuda.device(x.device):
+            n, cin, h, w = x.shape
+            cout, k = weight.shape[0], weight.shape[2]
+            xbuf, lx = _to_layout(x.detach().contiguous(), k // 2)
+            wp, bp = _packed_for(weight, bias, 'fwd')
+            ybuf, ly = _launch_conv(xbuf, lx, wp, bp, lx.cstride, cout, k, relu, n, h, w)
+            y = _from_layout(ybuf, ly, n, cout, h, w)
+        ctx.geom = (n, cin, cout, k, h, w)
+        ctx.relu = bool(relu)
+        ctx.has_bias = bias is not None
+        ctx.weight = weight
+        ctx.save_for_backward(weight)    # (for autograd's check that the filters were not modified in place since)
+        wants_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
+        ctx.xbuf, ctx.lx = (xbuf, lx) if wants_w else (None, None)
+        ctx.ybuf, ctx.ly = (ybuf, ly) if relu and any(ctx.needs_input_grad) else (None, None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        ctx.saved_tensors
+        n, cin, cout, k, h, w = ctx.geom
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        dx = dw = db = None
+        with torch.cuda.device(gy.device):
+            stream = current_stream()
+            gbuf, lg = _to_layout(gy.detach().float().contiguous(), k // 2)
+            if ctx.relu:
+                check(lib.rtpose_relu_grad(ptr(ctx.ybuf), C.byref(ctx.ly), ptr(gbuf), C.byref(lg), ptr(gbuf), C.byref(lg), cout,
+                                           n, h, w, stream), "rtpose_relu_grad")
+            if need_x:
+                wp, bp = _packed_for(ctx.weight, None, 'bwd')
+                dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
+                dx = _from_layout(dbuf, ld, n, cin, h, w)
+            if need_w or need_b:
+                dw = torch.empty_like(ctx.weight, memory_format=torch.contiguous_format)
+                db = torch.empty(cout, dtype=torch.float32, device=gy.device) if need_b else None
+                floats = lib.rtpose_conv2d_wgrad_workspace_floats(cin, cout, k, n, h, w)
+                ws = torch.empty(floats, dtype=torch.float32, device=gy.device)
+                d = _capi.WgradDesc()
+                d.x, d.gy, d.dw, d.dbias = ctx.xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
+                d.workspace, d.workspace_floats = ws.data_ptr(), floats
+                d.lx, d.lgy = ctx.lx, lg
+                d.cin, d.cout, d.k = cin, cout, k
+                check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, stream), "rtpose_conv2d_wgrad")
+                if not need_w:
+                    dw = None
+        return dx, dw, db, None
+
+
+def conv2d(x, weight, bias=None, relu=False):
+    """``relu(conv2d(x, weight, bias, padding=k // 2))`` (ReLU only if `relu`) with the library's kernels in both directions;
+    NCHW fp32 device tensors, k in {1, 3, 7}."""
+    return _Conv2d.apply(x, weight, bias, bool(relu))
+
+
+def run_sequential(seq, x):
+    """An nn.Sequential of the RtposeVGG tree (nn.Conv2d [+ nn.ReLU] and nn.MaxPool2d(2, 2, 0)): the convs through
+    ``conv2d`` with their ReLU fused, the pools through torch."""
+    mods = list(seq)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.Conv2d):
+            k = m.kernel_size[0]
+            if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
+                raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
+            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            x = conv2d(x, m.weight, m.bias, relu)
+            i += 2 if relu else 1
+        elif isinstance(m, nn.MaxPool2d):
+            x = F.max_pool2d(x, m.kernel_size, m.stride, m.padding)
+            i += 1
+        elif isinstance(m, nn.ReLU):
+            x = F.relu(x)
+            i += 1
+        else:
+            raise _capi.RtposeError("train: no backward for %r" % (m,))
+    return x
+
+
+def forward_train(model, x):
+    """lib/network/rtpose_vgg.py:158-198 over the module tree of `model` (an RtposeVGG), with an autograd graph behind the
+    outputs: ((out6_1, out6_2), saved_for_loss[12])."""
+    if not x.is_cuda:
+        raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
+                                "deliberately no CPU fallback" % (x.device,))
+    saved_for_loss = []
+    out1 = run_sequential(model.model0, x)
+    feed = out1
+    for s in range(1, 7):
+        o1 = run_sequential(getattr(model, 'model%d_1' % s), feed)
+        o2 = run_sequential(getattr(model, 'model%d_2' % s), feed)
+        saved_for_loss += [o1, o2]
+        if s < 6:
+            feed = torch.cat([o1, o2, out1], 1)
+    return (saved_for_loss[10], saved_for_loss[11]), saved_for_loss
+
+
+def freeze_trunk(model, n=20):
+    """train/train_VGG19.py:305-307: the parameters of the first `n` modules of model0 (conv1_1 .. conv4_1) stop training."""
+    for i in range(n):
+        for p in model.model0[i].parameters():
+            p.requires_grad = False
+    return model
+
+
+def train_step(model, optimizer, image, heat, paf):
+    """One iteration of train/train_VGG19.py:206-217: (total_loss, saved_for_log)."""
+    _, saved_for_loss = forward_train(model, image)
+    total_loss, saved_for_log = encode.get_loss(saved_for_loss, heat, paf)
+    optimizer.zero_grad()
+    total_loss.backward()
+    optimizer.step()
+    return total_loss, saved_for_log

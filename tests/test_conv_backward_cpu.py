@@ -1,0 +1,191 @@
+"""CPU suite of the conv backward pass (header section 2b, csrc/conv_backward.hip, train.py): the flipped, transposed filter
+of the data gradient and the float64 restatements of tests/conv_backward_restate.py against torch's CPU autograd, the host
+side of rtpose_conv2d_wgrad / rtpose_relu_grad (geometry queries, every refusal with its text, before any HIP call), and
+what train.freeze_trunk / train.forward_train do to a CPU-constructed model without a launch."""
+import ctypes as C
+import importlib
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import conv_backward_restate as cb
+from conftest import PKG_NAME
+
+FAKE = 1 << 20          # a 16-byte aligned "device pointer" no refused launch touches
+N, H, W = 2, 9, 7
+
+
+@pytest.fixture(scope="module")
+def train(pkg):
+    return importlib.import_module(PKG_NAME + ".train")
+
+
+# ---- the data gradient's filter and the restatements -------------------------------------------------------------------------
+@pytest.mark.parametrize("k,cin,cout", [(1, 5, 3), (3, 3, 7), (7, 6, 2)])
+def test_dgrad_weights_give_the_input_gradient(train, k, cin, cout):
+    g = torch.Generator().manual_seed(k)
+    x = torch.randn(2, cin, 6, 9, generator=g, dtype=torch.float64, requires_grad=True)
+    w = torch.randn(cout, cin, k, k, generator=g, dtype=torch.float64)
+    gy = torch.randn(2, cout, 6, 9, generator=g, dtype=torch.float64)
+    F.conv2d(x, w, None, padding=k // 2).backward(gy)
+    wt = train.dgrad_weights(w)
+    assert tuple(wt.shape) == (cin, cout, k, k) and wt.is_contiguous()
+    got = F.conv2d(gy, wt, None, padding=k // 2)
+    assert (got - x.grad).abs().max().item() <= 1e-12 * x.grad.abs().max().item()
+    dx, s = cb.dgrad64(gy, w)
+    assert torch.equal(dx, x.grad) and (s >= dx.abs() * (1 - 1e-12)).all()
+
+
+@pytest.mark.parametrize("k", [1, 3, 7])
+def test_wgrad_restatement_is_the_defining_sum(k):
+    """wgrad64 (autograd of F.conv2d) against the formula of the header, tap by tap, on a zero-padded input"""
+    g = torch.Generator().manual_seed(10 + k)
+    n, cin, cout, h, w = 2, 3, 4, 5, 6
+    x = torch.randn(n, cin, h, w, generator=g)
+    gy = torch.randn(n, cout, h, w, generator=g)
+    dw, s = cb.wgrad64(x, gy, k)
+    p = k // 2
+    xp = F.pad(x.double(), (p, p, p, p))
+    for dy in range(k):
+        for dx in range(k):
+            ref = torch.einsum("nohw,nchw->oc", gy.double(), xp[:, :, dy:dy + h, dx:dx + w])
+            sref = torch.einsum("nohw,nchw->oc", gy.double().abs(), xp[:, :, dy:dy + h, dx:dx + w].abs())
+            assert (dw[:, :, dy, dx] - ref).abs().max().item() <= 1e-12
+            assert (s[:, :, dy, dx] - sref).abs().max().item() <= 1e-12
+    db, sb = cb.dbias64(gy)
+    assert torch.allclose(db, gy.double().sum((0, 2, 3))) and (sb >= db.abs()).all()
+    assert cb.gamma(1) > cb.U and cb.gamma(1 << 20) < 0.07
+
+
+def test_relu_grad_restatement_on_bits():
+    import numpy as np
+    y = np.array([1.0, 0.0, -0.0, -2.0, np.nan, 3.0], dtype=np.float32)
+    g = np.array([0x3F800000, 0x3F800000, 0x3F800000, 0x3F800000, 0x3F800000, 0x7FC12345], dtype=np.uint32)
+    assert cb.relu_grad_bits(y, g).tolist() == [0x3F800000, 0, 0, 0, 0, 0x7FC12345]
+
+
+# ---- geometry queries ---------------------------------------------------------------------------------------------------------
+def test_slabs_and_workspace_depend_on_the_shape_only(capi):
+    lib = capi.lib
+    for c in cb.CASES:
+        slabs = lib.rtpose_conv2d_wgrad_slabs(c.cin, c.cout, c.k, c.n, c.h, c.w)
+        floats = lib.rtpose_conv2d_wgrad_workspace_floats(c.cin, c.cout, c.k, c.n, c.h, c.w)
+        assert slabs >= 1
+        # every slab holds a [tap][cout][cin] partial tile and a [cout] bias partial
+        assert floats >= slabs * (c.k * c.k * c.cin * c.cout + c.cout) and floats % 4 == 0
+        assert slabs == lib.rtpose_conv2d_wgrad_slabs(c.cin, c.cout, c.k, c.n, c.h, c.w)
+    big = cb.CASES[-1]
+    assert lib.rtpose_conv2d_wgrad_slabs(big.cin, big.cout, big.k, big.n, big.h, big.w) >= 3
+    # unsupported shapes have no geometry
+    assert lib.rtpose_conv2d_wgrad_slabs(8, 8, 5, 1, 4, 4) == 0
+    assert lib.rtpose_conv2d_wgrad_workspace_floats(0, 8, 3, 1, 4, 4) == 0
+
+
+# ---- refusals -----------------------------------------------------------------------------------------------------------------
+def base(capi, k=3, cin=24, cout=38):
+    d = capi.WgradDesc()
+    d.x = d.gy = d.dw = d.dbias = d.workspace = FAKE
+    d.workspace_floats = capi.lib.rtpose_conv2d_wgrad_workspace_floats(cin, cout, k, N, H, W)
+    d.lx = capi.Layout.padded(40, H, W, k // 2, 8)
+    d.lgy = capi.Layout.padded(48, H, W, 0, 4)
+    d.cin, d.cout, d.k = cin, cout, k
+    return d
+
+
+def _set(field, value):
+    def f(d):
+        setattr(d, field, value)
+    return f
+
+
+def _lay(which, field, value):
+    def f(d):
+        setattr(getattr(d, which), field, value)
+    return f
+
+
+def _small_ws(d):
+    d.workspace_floats -= 1
+
+
+WGRAD_FAULTS = [
+    ("null x", _set("x", None), "NULL x"),
+    ("null gy", _set("gy", None), "NULL gy"),
+    ("null dw", _set("dw", None), "NULL dw"),
+    ("null workspace", _set("workspace", None), "NULL workspace"),
+    ("k = 5", _set("k", 5), "k must be 1, 3 or 7"),
+    ("k = 0", _set("k", 0), "k must be 1, 3 or 7"),
+    ("cin = 0", _set("cin", 0), "cin and cout must be >= 1"),
+    ("x slice past cstride", _set("cin", 33), "input slice exceeds cstride"),
+    ("gy slice past cstride", _set("cout", 45), "output-gradient slice exceeds cstride"),
+    ("row gap below k/2", _lay("lx", "ws", W), "gap smaller than the conv padding"),
+    ("image gap below k/2", _lay("lx", "hs", H), "gap smaller than the conv padding"),
+    ("lead below k/2", _lay("lx", "lead", W + 1), "gap smaller than the conv padding"),
+    ("gy rows shorter than the map", _lay("lgy", "ws", W - 1), "output-gradient layout smaller than the map"),
+    ("workspace too small", _small_ws, "workspace of"),
+    ("dw not 16-byte aligned", _set("dw", FAKE + 4), "16-byte aligned"),
+    ("workspace not 16-byte aligned", _set("workspace", FAKE + 8), "16-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("name,fault,text", WGRAD_FAULTS, ids=[f[0] for f in WGRAD_FAULTS])
+def test_wgrad_refuses_on_the_host(capi, name, fault, text):
+    d = base(capi)
+    fault(d)
+    rc = capi.lib.rtpose_conv2d_wgrad(C.byref(d), N, H, W, None)
+    assert rc == -1, (name, rc, capi.last_error())            # RTPOSE_E_INVAL, not a HIP error
+    assert text in capi.last_error(), (name, capi.last_error())
+    assert "device memory" not in capi.last_error()           # returned before the pointers were looked at
+
+
+def test_wgrad_refuses_null_descriptor_and_empty_tensor(capi):
+    assert capi.lib.rtpose_conv2d_wgrad(None, N, H, W, None) == -1 and "NULL descriptor" in capi.last_error()
+    d = base(capi)
+    assert capi.lib.rtpose_conv2d_wgrad(C.byref(d), 0, H, W, None) == -1 and "empty tensor" in capi.last_error()
+
+
+def test_wgrad_takes_a_gap_of_exactly_half_the_filter(capi):
+    """k = 7 with a gap of 3 passes every host check: the refusal is then the pointer's (fake: no device owns it)"""
+    d = base(capi, k=7)
+    rc = capi.lib.rtpose_conv2d_wgrad(C.byref(d), N, H, W, None)
+    assert rc != 0 and "gap" not in capi.last_error() and "x" in capi.last_error()
+
+
+def test_relu_grad_refuses_on_the_host(capi):
+    lib = capi.lib
+    lay = capi.Layout.padded(24, H, W, 1, 4)
+    ok = [FAKE, C.byref(lay), FAKE, C.byref(lay), FAKE, C.byref(lay), 19, N, H, W, None]
+
+    def call(**kw):
+        a = list(ok)
+        for i, v in kw.items():
+            a[int(i[1:])] = v
+        return lib.rtpose_relu_grad(*a)
+    assert call(a0=None) == -1 and "NULL buffer" in capi.last_error()
+    assert call(a2=None) == -1 and "NULL buffer" in capi.last_error()
+    assert call(a4=None) == -1 and "NULL buffer" in capi.last_error()
+    assert call(a3=None) == -1 and "NULL layout" in capi.last_error()
+    assert call(a6=21) == -1 and "slice exceeds cstride" in capi.last_error()
+    assert call(a6=0) == -1 and "empty tensor" in capi.last_error()
+    assert call(a9=W + 2) == -1 and "smaller than the map" in capi.last_error()
+
+
+# ---- train.py on a CPU-constructed model ---------------------------------------------------------------------------------------
+def test_freeze_trunk_and_forward_train_leave_the_module_tree_alone(pkg, capi, train):
+    model = pkg.get_model('vgg19')
+    keys = list(model.state_dict().keys())
+    tree = [n for n, _ in model.named_modules()]
+    assert train.freeze_trunk(model) is model
+    frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
+    # train/train_VGG19.py:305-307: modules 0 .. 19 of model0 hold conv1_1 .. conv4_1, nine convs
+    assert frozen == ["model0.%d.%s" % (i, s) for i in (0, 2, 5, 7, 10, 12, 14, 16, 19) for s in ("weight", "bias")]
+    assert sum(1 for p in model.parameters() if p.requires_grad) == 184 - len(frozen)
+    # no CPU fallback, and the refusal comes before anything is changed
+    with pytest.raises(capi.RtposeError, match="no CPU fallback"):
+        train.forward_train(model, torch.zeros(1, 3, 16, 16))
+    with pytest.raises(capi.RtposeError, match="no CPU fallback"):
+        train.conv2d(torch.zeros(1, 3, 8, 8), model.model0[0].weight, model.model0[0].bias, relu=True)
+    assert list(model.state_dict().keys()) == keys and [n for n, _ in model.named_modules()] == tree
+    assert len(keys) == 184 and model.training
+    assert all(isinstance(m, torch.nn.Conv2d) for _, m in model._convs())
