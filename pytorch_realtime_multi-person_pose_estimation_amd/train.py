@@ -13,6 +13,13 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
 * ``forward_train(model, x)`` is the reference's forward order (lib/network/rtpose_vgg.py:158-198) over the module tree of
   an ``RtposeVGG`` with graph-carrying tensors; ``model.forward`` (the inference plan) is untouched.
 * ``train_step`` is one iteration of the reference's loop, ``freeze_trunk`` its ``requires_grad = False`` preamble (:305-307).
+* Packed filters are cached per parameter, one packing for the forward and one of the flipped, transposed filter for the
+  data gradient, and re-packed under the contract ``_native_state.py`` states for the inference arenas: when the
+  parameter's ``_version`` / ``data_ptr()`` changed (optimiser steps, ``copy_``, ``load_state_dict``, ``.to()``), when the
+  model's weight epoch moved (``model.invalidate_weights()``, the way to announce edits through ``.data``, which bump no
+  ``_version``), and on every forward and backward while ``model.always_resync`` is set.  ``forward_train`` and
+  ``run_sequential`` hand both to ``conv2d`` (``epoch=``, ``resync=``); a bare ``conv2d`` caller that edits ``.data`` calls
+  ``drop_packed_filters()``.
 
 The NCHW <-> layout conversion around every conv is known overhead; activations do not stay in layouts across layers yet.
 """
@@ -37,8 +44,18 @@ def _up8(c):
     return (c + 7) // 8 * 8
 
 
-# ---- packed filters, per parameter (_version, data_ptr), as _native_state.py keys the forward arenas ------------------------
+# ---- packed filters, per parameter (epoch, _version, data_ptr), as _native_state.py keys the forward arenas -----------------
 _packed = {}   # id(weight) -> {'fwd': (key, w_packed, b_packed), 'bwd': (key, w_packed, b_packed)}
+
+
+def drop_packed_filters(weight=None):
+    """Forget the cached packings of `weight` (None: of every parameter): the next ``conv2d`` forward and backward pack
+    from the values the parameters hold then.  For callers of ``conv2d`` that edit a parameter through ``.data``; a model
+    run by ``forward_train`` announces such edits with ``model.invalidate_weights()`` instead."""
+    if weight is None:
+        _packed.clear()
+    else:
+        _packed.pop(id(weight), None)
 
 
 def _pack(weight, bias, cin_p):
@@ -50,18 +67,19 @@ def _pack(weight, bias, cin_p):
     return wp, bp
 
 
-def _packed_for(weight, bias, which):
+def _packed_for(weight, bias, which, epoch=0, resync=False):
     """The packing of `weight` (+ `bias`) for the forward ('fwd') or of its flipped, transposed form for the data gradient
-    ('bwd', zero bias), re-packed when the parameter's (_version, data_ptr) changed."""
+    ('bwd', zero bias), re-packed when `epoch` (the owning model's weight epoch) or the parameter's (_version, data_ptr)
+    changed, and always if `resync`."""
     entry = _packed.get(id(weight))
     if entry is None or entry['ref']() is not weight:
         entry = _packed[id(weight)] = {'ref': weakref.ref(weight)}
         weakref.finalize(weight, _packed.pop, id(weight), None)
-    key = (weight._version, weight.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    key = (epoch, weight._version, weight.data_ptr(), torch.cuda.current_stream().cuda_stream)
     if which == 'fwd' and bias is not None:
         key += (bias._version, bias.data_ptr())
     hit = entry.get(which)
-    if hit is not None and hit[0] == key:
+    if hit is not None and hit[0] == key and not resync:
         return hit[1], hit[2]
     w = weight.detach()
     if which == 'fwd':
@@ -122,19 +140,20 @@ def _check_input(x, weight):
 
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
+    def forward(ctx, x, weight, bias, relu, epoch, resync):
         _check_input(x, weight)
         with torch.cuda.device(x.device):
             n, cin, h, w = x.shape
             cout, k = weight.shape[0], weight.shape[2]
             xbuf, lx = _to_layout(x.detach().contiguous(), k // 2)
-            wp, bp = _packed_for(weight, bias, 'fwd')
+            wp, bp = _packed_for(weight, bias, 'fwd', epoch, resync)
             ybuf, ly = _launch_conv(xbuf, lx, wp, bp, lx.cstride, cout, k, relu, n, h, w)
             y = _from_layout(ybuf, ly, n, cout, h, w)
         ctx.geom = (n, cin, cout, k, h, w)
         ctx.relu = bool(relu)
         ctx.has_bias = bias is not None
         ctx.weight = weight
+        ctx.epoch, ctx.resync = epoch, resync
         ctx.save_for_backward(weight)    # (for autograd's check that the filters were not modified in place since)
         wants_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
         ctx.xbuf, ctx.lx = (xbuf, lx) if wants_w else (None, None)
@@ -156,7 +175,7 @@ class _Conv2d(torch.autograd.Function):
                 check(lib.rtpose_relu_grad(ptr(ctx.ybuf), C.byref(ctx.ly), ptr(gbuf), C.byref(lg), ptr(gbuf), C.byref(lg), cout,
                                            n, h, w, stream), "rtpose_relu_grad")
             if need_x:
-                wp, bp = _packed_for(ctx.weight, None, 'bwd')
+                wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
                 dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
                 dx = _from_layout(dbuf, ld, n, cin, h, w)
             if need_w or need_b:
@@ -172,18 +191,19 @@ class _Conv2d(torch.autograd.Function):
                 check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, stream), "rtpose_conv2d_wgrad")
                 if not need_w:
                     dw = None
-        return dx, dw, db, None
+        return dx, dw, db, None, None, None
 
 
-def conv2d(x, weight, bias=None, relu=False):
+def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False):
     """``relu(conv2d(x, weight, bias, padding=k // 2))`` (ReLU only if `relu`) with the library's kernels in both directions;
-    NCHW fp32 device tensors, k in {1, 3, 7}."""
-    return _Conv2d.apply(x, weight, bias, bool(relu))
+    NCHW fp32 device tensors, k in {1, 3, 7}.  `epoch` (an int) is part of what the cached packings of `weight` are keyed
+    by, `resync` packs anew in this forward and its backward: the owning model's weight epoch and ``always_resync``."""
+    return _Conv2d.apply(x, weight, bias, bool(relu), int(epoch), bool(resync))
 
 
-def run_sequential(seq, x):
+def run_sequential(seq, x, epoch=0, resync=False):
     """An nn.Sequential of the RtposeVGG tree (nn.Conv2d [+ nn.ReLU] and nn.MaxPool2d(2, 2, 0)): the convs through
-    ``conv2d`` with their ReLU fused, the pools through torch."""
+    ``conv2d`` with their ReLU fused, the pools through torch.  `epoch` / `resync`: see ``conv2d``."""
     mods = list(seq)
     i = 0
     while i < len(mods):
@@ -193,7 +213,7 @@ def run_sequential(seq, x):
             if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
                 raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
             relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-            x = conv2d(x, m.weight, m.bias, relu)
+            x = conv2d(x, m.weight, m.bias, relu, epoch, resync)
             i += 2 if relu else 1
         elif isinstance(m, nn.MaxPool2d):
             x = F.max_pool2d(x, m.kernel_size, m.stride, m.padding)
@@ -212,12 +232,14 @@ def forward_train(model, x):
     if not x.is_cuda:
         raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
                                 "deliberately no CPU fallback" % (x.device,))
+    # the contract of _native_state.py: invalidate_weights() (the epoch) and always_resync decide a re-pack here as well
+    epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
     saved_for_loss = []
-    out1 = run_sequential(model.model0, x)
+    out1 = run_sequential(model.model0, x, epoch, resync)
     feed = out1
     for s in range(1, 7):
-        o1 = run_sequential(getattr(model, 'model%d_1' % s), feed)
-        o2 = run_sequential(getattr(model, 'model%d_2' % s), feed)
+        o1 = run_sequential(getattr(model, 'model%d_1' % s), feed, epoch, resync)
+        o2 = run_sequential(getattr(model, 'model%d_2' % s), feed, epoch, resync)
         saved_for_loss += [o1, o2]
         if s < 6:
             feed = torch.cat([o1, o2, out1], 1)

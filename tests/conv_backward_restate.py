@@ -1,7 +1,12 @@
 """Host restatement of the backward pass of the stride-1 "same" convs (include/rtpose_mi355x.h section 2b,
 csrc/conv_backward.hip, train.py): float64 gradients taken from F.conv2d's own autograd on the CPU - never from the code
 under test - with the quantity S a rounding-error bound is taken of, the bound itself, the ReLU gradient bit for bit, and
-the cases the GPU tests run.  torch CPU + numpy only: no GPU, no library call."""
+the cases the GPU tests run.  torch CPU + numpy only: no GPU, no library call.
+
+The exact cases (EXACT_CASES, exact_tensors): operands that are small integers held in float32.  Every kernel of the backward
+pass is fp32 in, fp32 accumulate, so while every sum of absolute terms S stays below 2^24 each product and each partial sum is
+an integer fp32 holds exactly - whatever the summation order, slab split or fma chain - and the float64 reference is compared
+with ==.  exact_margin(c) is that S; the largest over EXACT_CASES is 8 783 (k7_8to72_1x23x45), of 16 777 216."""
 from collections import namedtuple
 
 import numpy as np
@@ -78,3 +83,61 @@ def case_tensors(c, seed=0):
     gy = torch.randn(c.n, c.cout, c.h, c.w, generator=g)
     wt = torch.randn(c.cout, c.cin, c.k, c.k, generator=g) * (2.0 / (c.cin * c.k * c.k)) ** 0.5
     return x, gy, wt
+
+
+# ---- exact integer operands ---------------------------------------------------------------------------------------------------
+# x_cs / x_off as above; gap: pixels of gap of the x buffer on top of k // 2.  tags, checked against the library's host-side
+# geometry by tests/test_conv_backward_cpu.py: "several slabs" (slabs >= 2), "partial last chunk" (N H W % 32 != 0), "full"
+# (N H W % 32 == 0); the rest of the string says what the case is there for.
+ExactCase = namedtuple("ExactCase", "k cin cout n h w x_cs x_off gap tags")
+EXACT_CASES = [
+    ExactCase(1, 1, 1, 1, 1, 1, 1, 0, 0, "partial last chunk; one pixel, one channel"),
+    ExactCase(3, 1, 1, 1, 1, 1, 3, 2, 0, "partial last chunk; only the centre tap sees data; slice ends at cstride"),
+    ExactCase(7, 1, 1, 1, 1, 1, 4, 0, 2, "partial last chunk; the same with 49 taps; wide gap"),
+    ExactCase(3, 2, 2, 1, 2, 2, 5, 3, 0, "partial last chunk; map smaller than a chunk; odd choff, odd cstride, ends at cstride"),
+    ExactCase(7, 3, 5, 2, 1, 9, 8, 4, 2, "partial last chunk; H = 1: rows of taps read only the gap; wide gap"),
+    ExactCase(7, 5, 3, 2, 9, 1, 11, 3, 0, "partial last chunk; W = 1; odd choff, odd cstride"),
+    ExactCase(1, 64, 64, 1, 4, 8, 64, 0, 0, "full; exactly one chunk, a full <1,1> tile"),
+    ExactCase(1, 63, 65, 1, 3, 11, 67, 4, 2, "partial last chunk; <2,1>, one pixel in chunk 2; ends at cstride; wide gap"),
+    ExactCase(1, 65, 63, 1, 3, 11, 72, 3, 0, "partial last chunk; <1,2>; odd choff"),
+    ExactCase(1, 129, 130, 1, 5, 7, 136, 4, 0, "partial last chunk; <2,2>, second M and N tiles with 2 and 1 live channels"),
+    ExactCase(1, 257, 129, 1, 3, 3, 257, 0, 0, "partial last chunk; three N tiles"),
+    ExactCase(3, 65, 129, 2, 5, 7, 77, 11, 2, "partial last chunk; <2,2>, 3x3, a chunk across the image boundary; odd choff, "
+                                              "odd cstride; wide gap"),
+    ExactCase(1, 8, 8, 1, 31, 33, 11, 3, 0, "several slabs; partial last chunk; P = 1023; odd choff, odd cstride"),
+    ExactCase(1, 8, 8, 1, 32, 32, 8, 0, 0, "several slabs; full; P = 1024"),
+    ExactCase(1, 8, 8, 1, 25, 41, 16, 8, 0, "several slabs; partial last chunk; P = 1025, one pixel in the last chunk"),
+    ExactCase(1, 8, 8, 3, 19, 18, 12, 4, 0, "several slabs; partial last chunk; P = 1026, slabs across image boundaries; ends at "
+                                            "cstride"),
+    ExactCase(1, 8, 8, 1, 1, 1537, 9, 1, 0, "several slabs; partial last chunk; a single row; odd choff, odd cstride, ends at "
+                                            "cstride"),
+    ExactCase(3, 8, 8, 5, 15, 14, 16, 4, 2, "several slabs; partial last chunk; five images; wide gap"),
+    ExactCase(3, 72, 8, 2, 23, 23, 72, 0, 0, "several slabs; partial last chunk; <1,2>"),
+    ExactCase(7, 8, 72, 1, 23, 45, 13, 5, 0, "several slabs; partial last chunk; <2,1>, 7x7; odd choff, odd cstride, ends at "
+                                             "cstride"),
+    ExactCase(1, 40, 24, 7, 13, 17, 48, 8, 0, "several slabs; partial last chunk; seven images; ends at cstride"),
+]
+
+
+def exact_tensors(c, seed=0):
+    """(x, gy, wt, bias) of a case (any tuple with k cin cout n h w), float32 holding integers: x in {0, 1, 2, 3} with zeros as
+    a ReLU leaves them but channel 0 in {1, 2, 3} everywhere, gy in {+-1, +-2, +-3} and never zero, wt in {-2 .. 2}, bias in
+    {-3 .. 3}.  With gy never zero and channel 0 of x positive, a single missing (pixel, tap) term changes dbias[o] and
+    dW[o, 0, tap]."""
+    g = torch.Generator().manual_seed(2000 + seed)
+    ri = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).float()   # noqa: E731
+    x = ri(0, 3, c.n, c.cin, c.h, c.w)
+    x[:, 0] = ri(1, 3, c.n, c.h, c.w)
+    gy = ri(1, 3, c.n, c.cout, c.h, c.w) * (2 * ri(0, 1, c.n, c.cout, c.h, c.w) - 1)
+    wt = ri(-2, 2, c.cout, c.cin, c.k, c.k)
+    bias = ri(-3, 3, c.cout)
+    return x, gy, wt, bias
+
+
+def exact_margin(c, seed=0):
+    """The largest sum of absolute terms S over dW, dbias, dx and the forward y of the case's exact tensors.  S < 2^24 is the
+    condition under which fp32 arithmetic in any order gives the exact integer."""
+    x, gy, wt, bias = exact_tensors(c, seed)
+    s_y = F.conv2d(x.double().abs(), wt.double().abs(), bias.double().abs(), padding=c.k // 2)
+    return max(wgrad64(x, gy, c.k)[1].max().item(), dbias64(gy)[1].max().item(), dgrad64(gy, wt)[1].max().item(),
+               s_y.max().item())

@@ -82,6 +82,71 @@ def test_slabs_and_workspace_depend_on_the_shape_only(capi):
     assert lib.rtpose_conv2d_wgrad_workspace_floats(0, 8, 3, 1, 4, 4) == 0
 
 
+# ---- the exact cases do what they claim ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", cb.EXACT_CASES, ids=cb.case_id)
+def test_exact_case_is_exact_in_fp32_and_detects_a_missing_term(c):
+    """S < 2^24 (the condition, not a measurement), torch's own fp32 CPU autograd of F.conv2d on the integer tensors equals the
+    float64 one bit for bit - the reference meets the condition by itself - and no operand hides a dropped term."""
+    assert cb.exact_margin(c) < 2 ** 24
+    x, gy, wt, bias = cb.exact_tensors(c)
+    for t, lo, hi in ((x, 0, 3), (gy, -3, 3), (wt, -2, 2), (bias, -3, 3)):
+        assert t.dtype == torch.float32 and torch.equal(t, t.round()) and lo <= t.min().item() and t.max().item() <= hi
+    assert (gy != 0).all() and (x[:, 0] >= 1).all()
+    assert (c.cin - 1) * c.n * c.h * c.w < 32 or (x == 0).any()          # zeros as a ReLU leaves them
+    got = {}
+    for dt in (torch.float32, torch.float64):
+        xx, ww, bb = (t.to(dt).requires_grad_(True) for t in (x, wt, bias))
+        y = F.conv2d(xx, ww, bb, padding=c.k // 2)
+        got[dt] = (y.detach(),) + torch.autograd.grad(y, (xx, ww, bb), gy.to(dt))
+    for a, b, name in zip(got[torch.float32], got[torch.float64], ("y", "dx", "dw", "db")):
+        assert torch.equal(a.double(), b), name
+    # the restatements the GPU tests compare with are those gradients
+    assert torch.equal(cb.wgrad64(x, gy, c.k)[0], got[torch.float64][2])
+    assert torch.equal(cb.dbias64(gy)[0], got[torch.float64][3])
+    assert torch.equal(cb.dgrad64(gy, wt)[0], got[torch.float64][1])
+
+
+@pytest.mark.parametrize("c", [cb.EXACT_CASES[i] for i in (4, 11, 17)], ids=cb.case_id)
+def test_a_single_missing_pixel_changes_the_exact_gradients(c):
+    """zeroing one pixel of gy changes dbias of every channel, and dW[:, 0] at every tap whose shifted pixel lies in the map"""
+    x, gy, _, _ = cb.exact_tensors(c)
+    dw, db = cb.wgrad64(x, gy, c.k)[0], cb.dbias64(gy)[0]
+    half = c.k // 2
+    for n, yy, xx in ((0, 0, 0), (c.n - 1, c.h - 1, c.w - 1), (c.n // 2, c.h // 2, c.w // 2)):
+        g2 = gy.clone()
+        g2[n, :, yy, xx] = 0
+        assert (cb.dbias64(g2)[0] != db).all()
+        changed = cb.wgrad64(x, g2, c.k)[0][:, 0] != dw[:, 0]
+        for dy in range(c.k):
+            for dx in range(c.k):
+                inside = 0 <= yy + dy - half < c.h and 0 <= xx + dx - half < c.w
+                assert bool(changed[:, dy, dx].all()) == inside and bool(changed[:, dy, dx].any()) == inside, (dy, dx)
+
+
+def test_exact_case_tags_hold_in_the_library_geometry(capi):
+    """A tag that no longer holds fails here: a later change of the slab rule cannot quietly empty the sweep."""
+    lib = capi.lib
+    several = 0
+    for c in cb.EXACT_CASES:
+        p = c.n * c.h * c.w
+        slabs = lib.rtpose_conv2d_wgrad_slabs(c.cin, c.cout, c.k, c.n, c.h, c.w)
+        floats = lib.rtpose_conv2d_wgrad_workspace_floats(c.cin, c.cout, c.k, c.n, c.h, c.w)
+        assert slabs >= 1 and floats >= slabs * (c.k * c.k * c.cin * c.cout + c.cout) and floats % 4 == 0, c
+        assert ("several slabs" in c.tags) == (slabs >= 2), (c, slabs)
+        assert ("partial last chunk" in c.tags) == (p % 32 != 0) and ("full" in c.tags) == (p % 32 == 0), c
+        assert c.gap in (0, 2) and ("wide gap" in c.tags) == (c.gap == 2), c        # the gap is k // 2 + c.gap
+        assert "ends at cstride" not in c.tags or (c.x_off > 0 and c.x_off + c.cin == c.x_cs), c
+        assert ("odd choff, odd cstride" in c.tags) == (c.x_off % 2 == 1 and c.x_cs % 2 == 1), c
+        assert c.x_off + c.cin <= c.x_cs
+        several += slabs >= 2
+    assert several >= 9
+    # the layouts the issue of the exact tests asks for are all there
+    assert any(c.x_off == 0 for c in cb.EXACT_CASES) and any(c.x_off and c.x_off % 4 == 0 for c in cb.EXACT_CASES)
+    assert sum("wide gap" in c.tags for c in cb.EXACT_CASES) >= 4
+    assert {1, 3, 7} == {c.k for c in cb.EXACT_CASES if "several slabs" in c.tags}
+    assert len({cb.case_id(c) for c in cb.EXACT_CASES}) == len(cb.EXACT_CASES)
+
+
 # ---- refusals -----------------------------------------------------------------------------------------------------------------
 def base(capi, k=3, cin=24, cout=38):
     d = capi.WgradDesc()
