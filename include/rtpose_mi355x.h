@@ -381,7 +381,8 @@ int rtpose_pack_pw_weights_cols(const float* w_oi, const float* bias, int cout, 
 /* ---- conv5 + both heads of the ShuffleNetV2 pose network as ONE back-to-back GEMM launch (csrc/pw_head.hip):
  *   slim.conv_bn_relu('conv5', 464, 1024, 1) -> { self.paf = nn.Conv2d(1024, 38, 1), self.heatmap = nn.Conv2d(1024, 19, 1) }
  * (lib/network/rtpose_shufflenetV2.py:104, :107-108, :143-147).  d1 = the wide conv (+ReLU): `in` / `lin` a contiguous
- * slice of cin channels (a multiple of 16, <= 1024) or, with d1->in_planes, a gather of cin / 4 16-byte planes of
+ * slice of cin channels (a multiple of 16, 32 <= cin <= 1024: below one 32-channel chunk the launcher refuses the
+ * shape before any launch) or, with d1->in_planes, a gather of cin / 4 16-byte planes of
  * the pixel; w_packed [cin / 4][coutp][4] with cout = coutp a multiple of 256; d1->out is
  * ignored - the intermediate never leaves the registers.  d2 = the heads: ONE shared matrix [coutp1 / 4][64][4] whose
  * columns sit at their output channels (rtpose_pack_pw_weights with col_off; columns nobody owns must be zero), bias

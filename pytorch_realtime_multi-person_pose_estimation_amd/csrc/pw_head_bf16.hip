@@ -356,6 +356,12 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
     }
     if (!has_next) break;
     item = nitem;
+    // The last step of the last pass requested the next item's first activation fragments from LDS.  With K1 <= 128
+    // (kst == 8: one staging granule) that step runs BEFORE the granule's stage_store - the fragments were the old
+    // item's, and the first 16 channels of every item of a block but its first were multiplied with the previous
+    // item's pixels (tests/test_pw_exact_gpu.py, head-bf16-walk).  Read them again behind the barrier above: with
+    // wider K1 these are the same bytes (chunk 0 was replaced after the first granule of the last pass).
+    xload(xr[0], 0);
   }
 }
 #undef RTPOSE_HB_PIN

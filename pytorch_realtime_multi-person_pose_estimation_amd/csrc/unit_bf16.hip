@@ -153,7 +153,12 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
   const int kst1 = (k1real + 3) & ~3;         // ... that the loop walks (whole turns of the four-slot filter ring)
   const int nplt = A.Kt >> 3;                 // planes of T1
   const int k2real = A.Kt >> 4;               // k-steps of GEMM 2 (<= 4 NCH2)
-  const int nr1 = max(npl1, nplt);
+  // planes of a halo-tile buffer: x2, then T1, then the y tile - ALL C2P / 8 column groups of it, zero columns included
+  // (the epilogue writes whole fragments).  With fewer planes than C2P / 8 (K1 and Kt both below conv.2's packed width)
+  // the y tile of an item ran over the end of its buffer: into the other buffer, where the block's NEXT tile was staged
+  // already, or into the depthwise output and the taps - every item of a block but its first was computed from
+  // overwritten operands (tests/test_pw_exact_gpu.py, unit-bf16-walk).  unit_lds_bytes() sizes the buffers alike.
+  const int nr1 = max(max(npl1, nplt), C2P / 8);
   // LDS: [2][nr1][XP1] x2 halo tiles, ping-pong (the tile being worked on becomes T1, then y, in place; the other one
   // receives the block's next tile) | [nplt][AP2] depthwise output | [10][Kt] depthwise taps + bias
   float4* const a2 = smem4 + 2 * nr1 * XP1;
@@ -490,6 +495,13 @@ static int launch_inst(const Args& a, int grid, size_t lds, hipStream_t s) {
 // dw_w / dw_b in d0: conv.1's fp32 taps [9][Kt] and bias [Kt] (Kt = d2->cin).
 // d2: conv.2 (+ReLU): w_packed [Kt / 8][coutp][8 bf16], coutp = 128 or 256, `cout` columns exist (a multiple of 8),
 //     out_cmap[column] = absolute channel, groups of 8 columns contiguous; d2->out / lout = the stage buffer.
+// dynamic LDS of a launch: two halo-tile buffers of max(K1, Kt, conv.2's packed columns) / 8 planes, the depthwise output,
+// the taps and their bias
+static size_t unit_lds_bytes(int K1, int Kt, int c2p) {
+  const int nr1 = (K1 > Kt ? (K1 > c2p ? K1 : c2p) : (Kt > c2p ? Kt : c2p)) >> 3;
+  return ((size_t)2 * nr1 * unitb::XP1 + (size_t)(Kt >> 3) * unitb::AP2) * 16 + (size_t)10 * Kt * 4;
+}
+
 int unit_bf16_fits(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int H, int W) {
   if (!d0 || !d2 || H < 1 || W < 1) return 0;
   if (d0->cin < 16 || (d0->cin % 16) || d0->cin > unitb::kMaxK1) return 0;
@@ -501,9 +513,7 @@ int unit_bf16_fits(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int H, in
   if (!slice_aligned(d0->lin, 8) || (d2->lout.cstride % 8) || !gap_covers(d0->lin, H, W, 1)) return 0;
   // the next tile's x2 is staged in two rounds of two 64-channel chunks (under the write-out + depthwise conv, under GEMM 2)
   if (d0->cin > 256) return 0;
-  const size_t lds = ((size_t)2 * ((d0->cin > d2->cin ? d0->cin : d2->cin) >> 3) * unitb::XP1 + (size_t)(d2->cin >> 3) * unitb::AP2) * 16 +
-                     (size_t)10 * d2->cin * 4;
-  return lds <= 160 * 1024 - 2560 ? 1 : 0;
+  return unit_lds_bytes(d0->cin, d2->cin, d2->coutp) <= 160 * 1024 - 2560 ? 1 : 0;
 }
 
 int unit_bf16_launch(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int N, int H, int W, hipStream_t s) {
@@ -550,7 +560,7 @@ int unit_bf16_launch(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int N, 
   a.nitems = N * a.tiles_x * a.tiles_y;
   a.ftx = make_fastdiv(a.tiles_x);
   a.fty = make_fastdiv(a.tiles_y);
-  const size_t lds = ((size_t)2 * ((a.K1 > a.Kt ? a.K1 : a.Kt) >> 3) * XP1 + (size_t)(a.Kt >> 3) * AP2) * 16 + (size_t)10 * a.Kt * 4;
+  const size_t lds = unit_lds_bytes(a.K1, a.Kt, d2->coutp);
   const int slots = device_cu_count();  // one block per CU
   const int grid = a.nitems < slots ? a.nitems : slots;
   // instances: T1 of 64 / 128 / 192-256 channels (1, 2, 4 chunks; conv.0 packed 128 / 128 / 256 columns wide) x conv.2

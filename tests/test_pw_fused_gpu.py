@@ -10,6 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import layout_restate as lr
+import pw_driver as pd
+
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-4   # fp32 MFMA vs ATen fp32: different summation order only
@@ -64,7 +67,7 @@ def _run(capi, cuda, n, h, w, cin, cout, coutp, dw, relu, pt_c=0, pad_in=1, seed
     ctot = (2 * cout if pt_c else cout)
     cs = (ctot + 7) // 8 * 8
     lout = capi.Layout.padded(cs, h, w, 1)
-    out = torch.zeros(capi.lib.rtpose_layout_pixels(C.byref(lout), n, h, w) * cs, device=cuda)
+    out = pd.sentinel_buffer(capi.lib.rtpose_layout_pixels(C.byref(lout), n, h, w) * cs, "f32", cuda)
     keep += [wpk, bpk, wt_d, b_d, out]
     d.inp, d.w_packed, d.bias_packed, d.out = xin.data_ptr(), wpk.data_ptr(), bpk.data_ptr(), out.data_ptr()
     d.lin, d.lout = lin, lout
@@ -81,11 +84,12 @@ def _run(capi, cuda, n, h, w, cin, cout, coutp, dw, relu, pt_c=0, pad_in=1, seed
         d.out_cmap, d.pt_src, d.lpt, d.pt_cmap, d.pt_c = odd_d.data_ptr(), ptb.data_ptr(), lpt, even_d.data_ptr(), pt_c
         ref = torch.stack([xpt, ref], 2).reshape(n, 2 * cout, h, w)      # cat + channel_shuffle(2)
     capi.check(capi.lib.rtpose_pw_fused(C.byref(d), n, h, w, capi.current_stream()), "rtpose_pw_fused")
-    got = _from_layout(capi, out, lout, ctot, n, h, w, cuda)
-    # the layout gaps must stay untouched (zero): everything outside the real pixels
-    total = out.abs().sum().item()
-    inside = got.abs().sum().item()
-    assert abs(total - inside) <= 1e-3 * max(1.0, inside), "kernel wrote outside the real pixels"
+    # read on the host: everything outside the real pixels' channels must still hold the sentinel, bit for bit
+    bits = pd.host_bits(out)
+    idx = lr.index(lr.padded(cs, h, w, 1), n, h, w, ctot)
+    assert lr.untouched(bits, idx, pd.SENTINEL["f32"]), "kernel wrote outside the real pixels"
+    got = pd.values(bits, idx)
+    assert torch.isfinite(got).all(), "a pixel of the output was not written"
     scale = max(1.0, ref.abs().max().item())
     err = (got - ref).abs().max().item()
     assert err <= TOL * scale, (err, scale)
@@ -144,7 +148,7 @@ def test_unit_in_the_four_run_layout(capi, cuda, h, w_map):
     xp[:, perm] = x
     lay = capi.Layout.padded(C4, H, w_map, 1)
     cur = _to_layout(capi, xp, lay, C4, cuda)
-    nxt = torch.zeros_like(cur)
+    nxt = pd.sentinel_buffer(cur.numel(), "f32", cuda)
     K = 2 * q
     lt1 = capi.Layout.padded(K, H, w_map, 1)
     t1 = torch.zeros(capi.lib.rtpose_layout_pixels(C.byref(lt1), n, H, w_map) * K, device=cuda)
@@ -189,12 +193,17 @@ def test_unit_in_the_four_run_layout(capi, cuda, h, w_map):
     d2.pt_src, d2.lpt = cur.data_ptr(), lay
     d2.pt_pairs, d2.pt_a, d2.pt_b, d2.pt_split, d2.pt_d0, d2.pt_d1 = hh_, 0, 2 * q, hh_, 0, q
     capi.check(capi.lib.rtpose_pw_fused(C.byref(d2), n, H, w_map, capi.current_stream()), "conv.1+conv.2+x1")
-    got = _from_layout(capi, nxt, lay, C4, n, H, w_map, cuda)[:, perm]
+    # written: conv.2's h columns at the odd slots, the next x1 at the even-low / odd-low runs; nothing else, bit for bit
+    bits = pd.host_bits(nxt)
+    hl = lr.padded(C4, H, w_map, 1)
+    wrote = sorted(set(odd.tolist()) | set(range(hh_)) | set(range(q, q + 2 * hh_ - hh_)))
+    assert lr.untouched(bits, lr.index_map(hl, n, H, w_map, wrote), pd.SENTINEL["f32"]), \
+        "kernel wrote outside the real channels / pixels"
+    got = pd.values(bits, lr.index_map(hl, n, H, w_map, perm.numpy()))
+    assert torch.isfinite(got).all()
     scale = max(1.0, ref.abs().max().item())
     assert (got[:, 0::2] - ref[:, 0::2]).abs().max().item() == 0.0          # the pass-through half is a copy
     assert (got - ref).abs().max().item() <= TOL * scale
-    total, inside = nxt.abs().sum().item(), got.abs().sum().item()
-    assert abs(total - inside) <= 1e-3 * max(1.0, inside), "kernel wrote outside the real channels / pixels"
 
 
 @pytest.mark.parametrize("h,w_map", [(58, 46), (116, 46), (232, 46), (116, 70)])
@@ -230,7 +239,7 @@ def test_unit_in_the_four_run_layout_with_column_mapped_packing(capi, cuda, h, w
     xp[:, perm] = x
     lay = capi.Layout.padded(C4, H, w_map, 1)
     cur = _to_layout(capi, xp, lay, C4, cuda)
-    nxt = torch.zeros_like(cur)
+    nxt = pd.sentinel_buffer(cur.numel(), "f32", cuda)
     lt1 = capi.Layout.padded(Kp, H, w_map, 1)
     t1 = torch.zeros(capi.lib.rtpose_layout_pixels(C.byref(lt1), n, H, w_map) * Kp, device=cuda)
     coutp = (hp + 63) // 64 * 64
@@ -280,12 +289,18 @@ def test_unit_in_the_four_run_layout_with_column_mapped_packing(capi, cuda, h, w
     d2.pt_src, d2.lpt = cur.data_ptr(), lay
     d2.pt_pairs, d2.pt_a, d2.pt_b, d2.pt_split, d2.pt_d0, d2.pt_d1 = hh_, 0, 2 * q, hh_, 0, q
     capi.check(capi.lib.rtpose_pw_fused(C.byref(d2), n, H, w_map, capi.current_stream()), "conv.1+conv.2+x1")
-    got = _from_layout(capi, nxt, lay, C4, n, H, w_map, cuda)[:, perm]
+    # written: conv.2's hp columns = the odd runs (their padding: relu(0) = 0), the next x1 at the even-low / odd-low
+    # runs; nothing else, bit for bit
+    bits = pd.host_bits(nxt)
+    hl = lr.padded(C4, H, w_map, 1)
+    wrote = sorted(set(range(hp, 2 * hp)) | set(range(hh_)) | set(range(q, q + 2 * hh_ - hh_)))
+    assert lr.untouched(bits, lr.index_map(hl, n, H, w_map, wrote), pd.SENTINEL["f32"]), \
+        "kernel wrote outside the real channels / pixels"
+    got = pd.values(bits, lr.index_map(hl, n, H, w_map, perm.numpy()))
+    assert torch.isfinite(got).all()
     scale = max(1.0, ref.abs().max().item())
     assert (got[:, 0::2] - ref[:, 0::2]).abs().max().item() == 0.0          # the pass-through half is a copy
     assert (got - ref).abs().max().item() <= TOL * scale
-    total, inside = nxt.abs().sum().item(), got.abs().sum().item()
-    assert abs(total - inside) <= 1e-3 * max(1.0, inside), "kernel wrote outside the real channels / pixels"
 
 
 def _rb(t):
@@ -325,7 +340,7 @@ def test_unit_bf16_four_run_layout(capi, cuda, h):
     lay = capi.Layout.padded(C4, H, W, 1)
     npix = capi.lib.rtpose_layout_pixels(C.byref(lay), n, H, W)
     cur = torch.zeros(npix * C4, dtype=torch.int16, device=cuda)
-    nxt = torch.zeros_like(cur)
+    nxt = pd.sentinel_buffer(cur.numel(), "bf16", cuda)
     xs = xp.to(cuda).contiguous()
     capi.check(capi.lib.rtpose_nchw_to_layout_bf16(capi.ptr(xs), capi.ptr(cur), C.byref(lay), C4, C4, n, H, W,
                                                    capi.current_stream()))
@@ -375,14 +390,18 @@ def test_unit_bf16_four_run_layout(capi, cuda, h):
     d2.pt_src, d2.lpt = cur.data_ptr(), lay
     d2.pt_pairs, d2.pt_a, d2.pt_b, d2.pt_split, d2.pt_d0, d2.pt_d1 = hh_, 0, 2 * q, hh_, 0, q
     capi.check(capi.lib.rtpose_pw_fused_bf16(C.byref(d2), 0, n, H, W, capi.current_stream()), "conv.1+conv.2+x1 bf16")
-    # read back: bf16 layout -> fp32 layout -> NCHW
-    f32buf = torch.zeros(npix * C4, device=cuda)
-    capi.check(capi.lib.rtpose_layout_bf16_to_f32(capi.ptr(nxt), C.byref(lay), capi.ptr(f32buf), C.byref(lay), C4, n, H, W,
-                                                  capi.current_stream()))
-    got = _from_layout(capi, f32buf, lay, C4, n, H, W, cuda)
-    pads = [c for c in range(C4) if c not in set(perm.tolist())]
-    assert got[:, pads].abs().max().item() == 0.0                      # the run padding stays zero
-    got = got[:, perm]
+    # read back on the host.  Written: conv.2's K columns = the odd runs, the next x1 at the even-low / odd-low runs;
+    # nothing else, bit for bit (the padding of the even runs is nobody's: it keeps the sentinel)
+    bits = pd.host_bits(nxt)
+    hl = lr.padded(C4, H, W, 1)
+    wrote = sorted(set(range(2 * q, 4 * q)) | set(range(hh_)) | set(range(q, q + 2 * hh_ - hh_)))
+    assert lr.untouched(bits, lr.index_map(hl, n, H, W, wrote), pd.SENTINEL["bf16"]), \
+        "kernel wrote outside the real channels / pixels"
+    pads = [c for c in wrote if c not in set(perm.tolist())]
+    if pads:
+        assert pd.values(bits, lr.index_map(hl, n, H, W, pads)).abs().max().item() == 0.0     # the written run padding is zero
+    got = pd.values(bits, lr.index_map(hl, n, H, W, perm.numpy()))
+    assert torch.isfinite(got).all()
     assert (got[:, 0::2] - ref[:, 0::2]).abs().max().item() == 0.0     # the pass-through half is a copy
     scale = max(1.0, ref.abs().max().item())
     # one bf16 ulp (2^-8 relative) where the fp32 dw accumulation order flips a rounding, two stages deep
