@@ -1,8 +1,8 @@
 """The one driver of the conv launcher tests: a conv problem (drawn from a seed or given), its input buffer filled by the
 library's conversion kernel, an output buffer laid out by a policy, one descriptor array, the launch through the form's
 entry point, and the slices read back on the host after an exact check that nothing else was written.  tests/test_conv_gpu.py,
-test_wino_numerics_gpu.py, test_wino7_f8_gpu.py, test_bf16_gpu.py, test_bf16x3_gpu.py and test_conv_input_slices_gpu.py run
-their launches through it; `pack` and `call` are the only places that map a form to a packer and a launcher.
+test_wino_numerics_gpu.py, test_wino7_f8_gpu.py, test_bf16_gpu.py, test_bf16x3_gpu.py, test_conv_input_slices_gpu.py and
+test_conv_forward_exact_gpu.py run their launches through it; `pack` and `call` are the only places that map a form to a packer and a launcher.
 
 The tolerances and references those files (and the CPU files beside them) share live here as well, one definition each.
 Importing this module touches neither the GPU nor the library: `capi` and the device are arguments."""
@@ -301,15 +301,18 @@ def out_layouts(P, out, pad_out):
 
 
 # ---- launch and read-back ---------------------------------------------------------------------------------------------------------
-def launch(capi, dev, P, inputs, out, pad_out, scratch=True):
-    """inputs: one (buffer, lr.Lay) per branch.  Returns the output buffer (device) and its per-branch layouts."""
+def launch(capi, dev, P, inputs, out, pad_out, scratch=True, hook=None, into=None):
+    """inputs: one (buffer, lr.Lay) per branch.  Returns the output buffer (device) and its per-branch layouts.
+    hook(gi, desc, obuf, lout): sets the fields of a branch's descriptor the driver has no argument for (out_cmap, residual,
+    in_scale ...) before the launch; into: an output buffer of an earlier launch of the same problem and policy, written again."""
     form = P.form
     if not P.wp:
         pack_all(capi, dev, P)
     ho, wo = (P.h // 2, P.w // 2) if P.pool else (P.h, P.w)
     cso, louts, dt, _ = out_layouts(P, out, pad_out)
     ibits = torch.int32 if dt == torch.float32 else torch.int16
-    obuf = torch.full((npx(capi, louts[0], P.n, ho, wo) * cso,), out.fill, dtype=ibits, device=dev).view(dt)
+    obuf = into if into is not None else torch.full((npx(capi, louts[0], P.n, ho, wo) * cso,), out.fill, dtype=ibits,
+                                                    device=dev).view(dt)
     descs = (capi.ConvDesc * P.groups)()            # zero-initialised: every field the form does not use stays 0
     for gi, (buf, lay) in enumerate(inputs):
         d = descs[gi]
@@ -319,6 +322,8 @@ def launch(capi, dev, P, inputs, out, pad_out, scratch=True):
         d.wino_m = form.m or 0
         if P.sl[gi] is not None:
             d.prelu = P.sl[gi].data_ptr()
+        if hook is not None:
+            hook(gi, d, obuf, louts[gi])
     call(capi, dev, form, descs, P.groups, P.n, P.h, P.w, scratch)
     return obuf, louts
 
@@ -328,21 +333,24 @@ def np_bits(t):
     return t.view(torch.int32).numpy().view(np.uint32) if t.dtype == torch.float32 else t.view(torch.int16).numpy().view(np.uint16)
 
 
-def outputs(P, obuf, louts, out, values=True):
+def outputs(P, obuf, louts, out, values=True, cmaps=None, pieces=None):
     """The branches' outputs [n, cout, ho, wo] (CPU fp32; values = False: none) read on the host through lr.index /
-    lr.split_index, after the exact check: every word of the output buffer outside the written slices still holds the
-    policy's fill word, bit for bit."""
+    lr.split_index (cmaps: per branch the absolute channels of an out_cmap launch, lr.index_map), after the exact check:
+    every word of the output buffer outside the written slices still holds the policy's fill word, bit for bit.
+    pieces: a list that receives, per branch of a split bf16x3 output, the (hi, lo) words as float32 [n, cout, ho, wo]."""
     ho, wo = (P.h // 2, P.w // 2) if P.pool else (P.h, P.w)
     split = P.form.kind == "x3" and not P.form.out_f32
     bits = np_bits(obuf)
     outs, written = [], []
-    for lo in louts:
+    for gi, lo in enumerate(louts):
         if split:
             ih, il = lr.split_index(lo, P.n, ho, wo, P.cout)
             written += [ih, il]
             v = (lr.bf16_to_f32(bits[ih]) + lr.bf16_to_f32(bits[il])) if values else None
+            if pieces is not None:
+                pieces.append(tuple(np.ascontiguousarray(np.transpose(lr.bf16_to_f32(bits[i]), (0, 3, 1, 2))) for i in (ih, il)))
         else:
-            idx = lr.index(lo, P.n, ho, wo, P.cout)
+            idx = lr.index(lo, P.n, ho, wo, P.cout) if cmaps is None else lr.index_map(lo, P.n, ho, wo, cmaps[gi])
             written.append(idx)
             v = (bits[idx].view(np.float32) if bits.dtype == np.uint32 else lr.bf16_to_f32(bits[idx])) if values else None
         outs.append(torch.from_numpy(np.ascontiguousarray(np.transpose(v, (0, 3, 1, 2)))) if values else None)
