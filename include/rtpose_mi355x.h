@@ -200,6 +200,44 @@ int rtpose_conv2d_wgrad(const rtpose_wgrad_desc* d, int N, int H, int W, void* s
 int rtpose_relu_grad(const float* y, const rtpose_layout* ly, const float* gy, const rtpose_layout* lgy,
                      float* out, const rtpose_layout* lout, int channels, int N, int H, int W, void* stream);
 
+/* ---- 2b, continued.  PReLU as a pass of its own, for training (csrc/prelu_backward.hip).  The conv launchers fuse
+ * nn.PReLU(num_parameters = cout) into their epilogue (rtpose_conv_desc.prelu) and keep only its output; slopes may have
+ * either sign (the reference draws them from N(0, 0.01)), so the sign of the output says nothing about the sign of the
+ * PRE-activation z and a backward pass needs z itself.  A training forward launches the conv with relu = 0 and
+ * prelu = NULL into z and then rtpose_prelu; the backward runs rtpose_prelu_grad on the same z.
+ *
+ * All three entry points check every argument on the host before any HIP call (RTPOSE_E_INVAL with a text), launch on
+ * `stream`, and read and write only `channels` channels from `choff` at the valid pixels of each layout: gaps and
+ * neighbouring channels are neither read nor written.  `slope` is device float[channels], read where it is: nothing is
+ * packed or cached.  16-byte loads and stores where every cstride and choff is a multiple of 4 floats and every base is
+ * 16-byte aligned, element by element otherwise: the same values either way.
+ *
+ * y = z >= 0 ? z : slope[c] * z : the bits of the fused epilogue (prelu1 in common.h), from a conv launched with
+ * relu = 0 and prelu = NULL.  It differs from torch's F.prelu only in the sign of a zero under a negative slope.
+ * y / ly may name the slice z / lz names. */
+int rtpose_prelu(const float* z, const rtpose_layout* lz, const float* slope, float* y, const rtpose_layout* ly,
+                 int channels, int N, int H, int W, void* stream);
+
+/* torch's prelu_backward from the PRE-activation z:
+ *     out[n,y,x,c] = z > 0 ? gy : slope[c] * gy              (out / lout may name gy / lgy)
+ *     dslope[c]    = sum over valid (n,y,x) of (z > 0 ? 0 : z * gy)     (dslope != NULL; OVERWRITTEN)
+ * z == 0 (either sign) and a NaN z take the slope path, as in torch: the forward's `>=` and the backward's `>` differ on
+ * purpose.  Where z > 0 `out` holds gy's bits, a NaN's payload included.  fp32, one rounding per product.
+ * z and gy are read once.  The valid pixels are cut, in (n, y, x) order, into rtpose_prelu_grad_slabs() slabs that
+ * depend on the shape only - equal multiples of 64 pixels but for the last one, across image boundaries; within a slab a
+ * thread owns fixed channels and adds its terms in a fixed pixel order, the threads of a channel are added in a fixed
+ * order through LDS, every slab's [channels] partial goes to `workspace` (device memory of the caller,
+ * rtpose_prelu_grad_workspace_floats() >= slabs * channels floats) and a second launch adds the partials in slab
+ * order: no atomics, the same inputs give the same bits on every run.
+ * dslope == NULL (frozen slopes): no reduction is launched and workspace may be NULL.
+ * Both queries return 0 for a shape the launcher refuses (channels < 1, an empty map, N * H * W above the launch limit
+ * of 2^31 - 256 pixels). */
+size_t rtpose_prelu_grad_workspace_floats(int channels, int N, int H, int W);
+int rtpose_prelu_grad_slabs(int channels, int N, int H, int W);
+int rtpose_prelu_grad(const float* z, const rtpose_layout* lz, const float* slope, const float* gy,
+                      const rtpose_layout* lgy, float* out, const rtpose_layout* lout, float* dslope,
+                      float* workspace, size_t workspace_floats, int channels, int N, int H, int W, void* stream);
+
 /* ---- the first layer: nn.Conv2d(3, 64, 3, 1, 1) (+ nn.ReLU), conv1_1 of the VGG-19 front end
  * (lib/network/rtpose_vgg.py:23-35, `model0.0`; csrc/conv_first.hip).  Reads the image where it is -
  * dense NCHW fp32 (`x_nchw`), or, with x_nchw = NULL, a layout buffer with >= 3 channels per pixel

@@ -188,6 +188,10 @@ _SIGS = {
     "rtpose_conv2d_wgrad_slabs": (_i, [_i, _i, _i, _i, _i, _i]),
     "rtpose_conv2d_wgrad": (_i, [C.POINTER(WgradDesc), _i, _i, _i, _vp]),
     "rtpose_relu_grad": (_i, [_vp, _LP, _vp, _LP, _vp, _LP, _i, _i, _i, _i, _vp]),
+    "rtpose_prelu": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _vp]),
+    "rtpose_prelu_grad_workspace_floats": (_sz, [_i, _i, _i, _i]),
+    "rtpose_prelu_grad_slabs": (_i, [_i, _i, _i, _i]),
+    "rtpose_prelu_grad": (_i, [_vp, _LP, _vp, _vp, _LP, _vp, _LP, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),
     "rtpose_conv1x1_pair": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_bf16_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),

@@ -11,7 +11,8 @@ bit for bit, the heat values within 1 fp32 ulp (``exp``).  Not the reference's: 
 multiply-add inside BLAS's ``dot``, the limb norm here is the unfused ``sqrt(vx * vx + vy * vy)``.
 
 ``stage_losses`` covers ``network.RtposeVGG`` only (OpenPose_Model and the hourglass return other numbers of stage
-outputs); ``encode_targets`` takes any skeleton and any stride, 4 included.
+outputs); ``get_loss_openpose`` is the loss of an ``openpose.OpenPose_Model`` in torch, as ``get_loss`` is for rtpose_vgg
+(train.train_step picks between them); ``encode_targets`` takes any skeleton and any stride, 4 included.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -141,6 +142,28 @@ def get_loss(saved_for_loss, heat_temp, vec_temp):
     for t in terms[1:]:
         total = total + t
     log.update(_extremes(saved_for_loss[11].detach(), saved_for_loss[10].detach()))
+    return total, log
+
+
+def get_loss_openpose(saved_for_loss, heat_temp, vec_temp):
+    """The loss of an ``openpose.OpenPose_Model`` from its ``saved_for_loss = [paf_ret, heat_ret]``.  The reference ships
+    no training script for this network, so this is the project's definition, after get_loss: one
+    nn.MSELoss(reduction='mean') per PAF stage against ``vec_temp`` and per heat stage against ``heat_temp``, added in the
+    order PAF stages then heat stages.  (total_loss, saved_for_log): the terms under ``loss_paf_stage%d`` /
+    ``loss_heat_stage%d`` (1-based), plus max_ht / min_ht / max_paf / min_paf of the last heat map and the last PAF."""
+    if (not isinstance(saved_for_loss, (list, tuple)) or len(saved_for_loss) != 2
+            or not all(isinstance(s, (list, tuple)) and len(s) >= 1 for s in saved_for_loss)):
+        raise ValueError("get_loss_openpose wants [paf_ret, heat_ret], two non-empty lists of stage outputs")
+    paf_ret, heat_ret = saved_for_loss
+    names = ['loss_paf_stage%d' % (i + 1) for i in range(len(paf_ret))] \
+        + ['loss_heat_stage%d' % (i + 1) for i in range(len(heat_ret))]
+    terms = [torch.nn.functional.mse_loss(out, vec_temp) for out in paf_ret] \
+        + [torch.nn.functional.mse_loss(out, heat_temp) for out in heat_ret]
+    log = OrderedDict(zip(names, (t.item() for t in terms)))
+    total = terms[0]
+    for t in terms[1:]:
+        total = total + t
+    log.update(_extremes(heat_ret[-1].detach(), paf_ret[-1].detach()))
     return total, log
 
 

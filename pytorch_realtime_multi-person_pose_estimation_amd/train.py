@@ -1,5 +1,5 @@
 """Training through the library's kernels: ``loss.backward()`` and ``optimizer.step()`` of the reference's loop
-(train/train_VGG19.py:194-217) on an ``RtposeVGG``.
+(train/train_VGG19.py:194-217) on an ``RtposeVGG`` or an ``openpose.OpenPose_Model``.
 
 PyTorch keeps the graph and the optimizer; every convolution of it, forward and backward, is hand-written HIP:
 
@@ -8,11 +8,16 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   Backward: ``rtpose_relu_grad`` through the fused ReLU, the data gradient as ``rtpose_conv2d`` on the flipped, transposed
   filter (``dgrad_weights``), the weight and bias gradients by ``rtpose_conv2d_wgrad``.  A conv whose parameters are
   frozen launches no weight gradient, a conv whose input needs no gradient (the first trainable conv behind a frozen trunk
-  or behind the image) no data gradient.  All launches go on the current stream; every buffer comes from torch's caching
+  or behind the image) no data gradient.  With ``prelu=`` (the ``weight`` of an ``nn.PReLU(num_parameters=cout)``) the conv
+  is launched without an activation into the pre-activation ``z``, ``rtpose_prelu`` makes ``y`` from it - the bits of the
+  inference kernels' fused epilogue - and the backward runs ``rtpose_prelu_grad`` on the saved ``z`` (the slope gradient
+  only if the slope requires one); ``y``'s layout buffer is not kept.  All launches go on the current stream; every buffer comes from torch's caching
   allocator.  The Winograd forms are not used here: their error contracts were set for the forward statistics.
-* ``forward_train(model, x)`` is the reference's forward order (lib/network/rtpose_vgg.py:158-198) over the module tree of
-  an ``RtposeVGG`` with graph-carrying tensors; ``model.forward`` (the inference plan) is untouched.
+* ``forward_train(model, x)`` is the reference's forward order over the module tree of an ``RtposeVGG``
+  (lib/network/rtpose_vgg.py:158-198) or of an ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177; the
+  dense-block ``torch.cat``s stay in torch) with graph-carrying tensors; ``model.forward`` (the inference plan) is untouched.
 * ``train_step`` is one iteration of the reference's loop, ``freeze_trunk`` its ``requires_grad = False`` preamble (:305-307).
+  For an ``OpenPose_Model``, for which the reference ships no training script, the loss is ``encode.get_loss_openpose``.
 * Packed filters are cached per parameter, one packing for the forward and one of the flipped, transposed filter for the
   data gradient, and re-packed under the contract ``_native_state.py`` states for the inference arenas: when the
   parameter's ``_version`` / ``data_ptr()`` changed (optimiser steps, ``copy_``, ``load_state_dict``, ``.to()``), when the
@@ -20,6 +25,9 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   ``_version``), and on every forward and backward while ``model.always_resync`` is set.  ``forward_train`` and
   ``run_sequential`` hand both to ``conv2d`` (``epoch=``, ``resync=``); a bare ``conv2d`` caller that edits ``.data`` calls
   ``drop_packed_filters()``.
+* PReLU slopes are neither packed nor cached: every ``rtpose_prelu`` / ``rtpose_prelu_grad`` launch reads the parameter's
+  own storage, so a slope edited through ``.data`` needs no ``invalidate_weights()`` and the packed-filter cache is as it
+  was.
 
 The NCHW <-> layout conversion around every conv is known overhead; activations do not stay in layouts across layers yet.
 """
@@ -32,6 +40,8 @@ import torch.nn.functional as F
 
 from . import _capi, encode
 from ._capi import lib, check, ptr, current_stream
+from .network import RtposeVGG
+from .openpose import OpenPose_Model
 
 
 def dgrad_weights(weight):
@@ -126,6 +136,17 @@ def _launch_conv(inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
     return out, lout
 
 
+def _check_prelu(prelu, weight, relu):
+    if relu:
+        raise _capi.RtposeError("train.conv2d: relu and prelu are exclusive")
+    if not torch.is_tensor(prelu) or prelu.dtype != torch.float32 or tuple(prelu.shape) != (weight.shape[0],):
+        raise _capi.RtposeError("train.conv2d: prelu is the fp32 [cout] weight of an nn.PReLU(num_parameters=cout), cout = %d; "
+                                "got %s" % (weight.shape[0], "%s %s" % (prelu.dtype, tuple(prelu.shape))
+                                            if torch.is_tensor(prelu) else type(prelu).__name__))
+    if prelu.device != weight.device:
+        raise _capi.RtposeError("train.conv2d: prelu on %s, the filters on %s" % (prelu.device, weight.device))
+
+
 def _check_input(x, weight):
     if not (x.is_cuda and weight.is_cuda):
         raise _capi.RtposeError("train.conv2d runs only on an MI355X (HIP) device; got x on %s, weight on %s - there is "
@@ -140,7 +161,9 @@ def _check_input(x, weight):
 
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, relu, epoch, resync):
+    def forward(ctx, x, weight, bias, relu, epoch, resync, prelu):
+        if prelu is not None:
+            _check_prelu(prelu, weight, relu)
         _check_input(x, weight)
         with torch.cuda.device(x.device):
             n, cin, h, w = x.shape
@@ -148,32 +171,48 @@ class _Conv2d(torch.autograd.Function):
             xbuf, lx = _to_layout(x.detach().contiguous(), k // 2)
             wp, bp = _packed_for(weight, bias, 'fwd', epoch, resync)
             ybuf, ly = _launch_conv(xbuf, lx, wp, bp, lx.cstride, cout, k, relu, n, h, w)
+            zbuf = None
+            if prelu is not None:        # ybuf so far holds the pre-activation: keep it as z, y goes to a buffer of its own
+                zbuf, ybuf = ybuf, _buffer(ly, n, h, w, x.device, False)
+                check(lib.rtpose_prelu(ptr(zbuf), C.byref(ly), ptr(prelu.detach().contiguous()), ptr(ybuf), C.byref(ly), cout,
+                                       n, h, w, current_stream()), "rtpose_prelu")
             y = _from_layout(ybuf, ly, n, cout, h, w)
         ctx.geom = (n, cin, cout, k, h, w)
         ctx.relu = bool(relu)
         ctx.has_bias = bias is not None
         ctx.weight = weight
         ctx.epoch, ctx.resync = epoch, resync
-        ctx.save_for_backward(weight)    # (for autograd's check that the filters were not modified in place since)
+        ctx.has_prelu = prelu is not None
+        # (for autograd's check that the filters and slopes were not modified in place since)
+        ctx.save_for_backward(*((weight, prelu) if ctx.has_prelu else (weight,)))
         wants_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
         ctx.xbuf, ctx.lx = (xbuf, lx) if wants_w else (None, None)
         ctx.ybuf, ctx.ly = (ybuf, ly) if relu and any(ctx.needs_input_grad) else (None, None)
+        ctx.zbuf, ctx.lz = (zbuf, ly) if ctx.has_prelu and any(ctx.needs_input_grad) else (None, None)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        ctx.saved_tensors
+        saved = ctx.saved_tensors
         n, cin, cout, k, h, w = ctx.geom
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        dx = dw = db = None
+        need_a = ctx.has_prelu and ctx.needs_input_grad[6]
+        dx = dw = db = da = None
         with torch.cuda.device(gy.device):
             stream = current_stream()
             gbuf, lg = _to_layout(gy.detach().float().contiguous(), k // 2)
             if ctx.relu:
                 check(lib.rtpose_relu_grad(ptr(ctx.ybuf), C.byref(ctx.ly), ptr(gbuf), C.byref(lg), ptr(gbuf), C.byref(lg), cout,
                                            n, h, w, stream), "rtpose_relu_grad")
+            if ctx.has_prelu:
+                floats = lib.rtpose_prelu_grad_workspace_floats(cout, n, h, w) if need_a else 0
+                ws = torch.empty(floats, dtype=torch.float32, device=gy.device) if need_a else None
+                da = torch.empty(cout, dtype=torch.float32, device=gy.device) if need_a else None
+                check(lib.rtpose_prelu_grad(ptr(ctx.zbuf), C.byref(ctx.lz), ptr(saved[1].detach().contiguous()), ptr(gbuf),
+                                            C.byref(lg), ptr(gbuf), C.byref(lg), ptr(da), ptr(ws), floats, cout, n, h, w, stream),
+                      "rtpose_prelu_grad")
             if need_x:
                 wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
                 dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
@@ -191,19 +230,22 @@ class _Conv2d(torch.autograd.Function):
                 check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, stream), "rtpose_conv2d_wgrad")
                 if not need_w:
                     dw = None
-        return dx, dw, db, None, None, None
+        return dx, dw, db, None, None, None, da
 
 
-def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False):
+def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None):
     """``relu(conv2d(x, weight, bias, padding=k // 2))`` (ReLU only if `relu`) with the library's kernels in both directions;
     NCHW fp32 device tensors, k in {1, 3, 7}.  `epoch` (an int) is part of what the cached packings of `weight` are keyed
-    by, `resync` packs anew in this forward and its backward: the owning model's weight epoch and ``always_resync``."""
-    return _Conv2d.apply(x, weight, bias, bool(relu), int(epoch), bool(resync))
+    by, `resync` packs anew in this forward and its backward: the owning model's weight epoch and ``always_resync``.
+    `prelu`: an fp32 [cout] device tensor, the ``weight`` of an ``nn.PReLU(num_parameters=cout)`` applied to the conv's
+    output (exclusive with `relu`); read from its storage by every launch, never packed or cached."""
+    return _Conv2d.apply(x, weight, bias, bool(relu), int(epoch), bool(resync), prelu)
 
 
 def run_sequential(seq, x, epoch=0, resync=False):
-    """An nn.Sequential of the RtposeVGG tree (nn.Conv2d [+ nn.ReLU] and nn.MaxPool2d(2, 2, 0)): the convs through
-    ``conv2d`` with their ReLU fused, the pools through torch.  `epoch` / `resync`: see ``conv2d``."""
+    """An nn.Sequential of the RtposeVGG / OpenPose_Model trees (nn.Conv2d [+ nn.ReLU | nn.PReLU] and
+    nn.MaxPool2d(2, 2, 0)): the convs through ``conv2d`` with their ReLU or PReLU fused, the pools through torch.
+    `epoch` / `resync`: see ``conv2d``."""
     mods = list(seq)
     i = 0
     while i < len(mods):
@@ -212,9 +254,13 @@ def run_sequential(seq, x, epoch=0, resync=False):
             k = m.kernel_size[0]
             if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
                 raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
-            relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-            x = conv2d(x, m.weight, m.bias, relu, epoch, resync)
-            i += 2 if relu else 1
+            nxt = mods[i + 1] if i + 1 < len(mods) else None
+            relu, prelu = isinstance(nxt, nn.ReLU), isinstance(nxt, nn.PReLU)
+            if prelu and nxt.num_parameters != m.out_channels:
+                raise _capi.RtposeError("train: a PReLU behind a conv has one slope per output channel (num_parameters = %d); "
+                                        "got %r behind %r" % (m.out_channels, nxt, m))
+            x = conv2d(x, m.weight, m.bias, relu, epoch, resync, nxt.weight if prelu else None)
+            i += 2 if relu or prelu else 1
         elif isinstance(m, nn.MaxPool2d):
             x = F.max_pool2d(x, m.kernel_size, m.stride, m.padding)
             i += 1
@@ -226,14 +272,23 @@ def run_sequential(seq, x, epoch=0, resync=False):
     return x
 
 
-def forward_train(model, x):
-    """lib/network/rtpose_vgg.py:158-198 over the module tree of `model` (an RtposeVGG), with an autograd graph behind the
-    outputs: ((out6_1, out6_2), saved_for_loss[12])."""
-    if not x.is_cuda:
-        raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
-                                "deliberately no CPU fallback" % (x.device,))
-    # the contract of _native_state.py: invalidate_weights() (the epoch) and always_resync decide a re-pack here as well
-    epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
+def _conv_block(blk, x, epoch, resync):
+    """openpose.ConvBlock (reference :59-62): Mconv + MPrelu as one fused conv2d"""
+    return run_sequential([blk.Mconv, blk.MPrelu], x, epoch, resync)
+
+
+def _stage_block(st, x, epoch, resync):
+    """openpose.StageBlock.forward of the reference (:86-109): five dense blocks of three ConvBlocks whose outputs are
+    concatenated (torch.cat), the 1x1 ConvBlock Mconv6 and the 1x1 conv Mconv7."""
+    for b in range(1, 6):
+        o1 = _conv_block(getattr(st, 'Mconv%d_0' % b), x, epoch, resync)
+        o2 = _conv_block(getattr(st, 'Mconv%d_1' % b), o1, epoch, resync)
+        o3 = _conv_block(getattr(st, 'Mconv%d_2' % b), o2, epoch, resync)
+        x = torch.cat([o1, o2, o3], 1)
+    return run_sequential([st.Mconv7], _conv_block(st.Mconv6, x, epoch, resync), epoch, resync)
+
+
+def _forward_train_vgg(model, x, epoch, resync):
     saved_for_loss = []
     out1 = run_sequential(model.model0, x, epoch, resync)
     feed = out1
@@ -246,18 +301,59 @@ def forward_train(model, x):
     return (saved_for_loss[10], saved_for_loss[11]), saved_for_loss
 
 
+def _forward_train_openpose(model, x, epoch, resync):
+    features = run_sequential(model.feature_extractor, x, epoch, resync)
+    paf_ret, heat_ret = [], []
+    x_in = features
+    for st in model.l2_stages:
+        paf_pred = _stage_block(st, x_in, epoch, resync)
+        x_in = torch.cat([features, paf_pred], 1)
+        paf_ret.append(paf_pred)
+    for st in model.l1_stages:
+        heat_pred = _stage_block(st, x_in, epoch, resync)
+        x_in = torch.cat([features, heat_pred, paf_pred], 1)
+        heat_ret.append(heat_pred)
+    return [(paf_ret[-2], heat_ret[-2]), (paf_ret[-1], heat_ret[-1])], [paf_ret, heat_ret]
+
+
+def _model_kind(model, who):
+    if isinstance(model, RtposeVGG):
+        return 'vgg'
+    if isinstance(model, OpenPose_Model):
+        return 'openpose'
+    raise TypeError("%s takes a network.RtposeVGG or an openpose.OpenPose_Model; got %s" % (who, type(model).__name__))
+
+
+def forward_train(model, x):
+    """The reference's forward over the module tree of `model`, with an autograd graph behind the outputs.
+    ``RtposeVGG`` (lib/network/rtpose_vgg.py:158-198): ((out6_1, out6_2), saved_for_loss[12]).
+    ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177):
+    ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret])."""
+    kind = _model_kind(model, "train.forward_train")
+    if not x.is_cuda:
+        raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
+                                "deliberately no CPU fallback" % (x.device,))
+    # the contract of _native_state.py: invalidate_weights() (the epoch) and always_resync decide a re-pack here as well
+    epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
+    return (_forward_train_vgg if kind == 'vgg' else _forward_train_openpose)(model, x, epoch, resync)
+
+
 def freeze_trunk(model, n=20):
-    """train/train_VGG19.py:305-307: the parameters of the first `n` modules of model0 (conv1_1 .. conv4_1) stop training."""
+    """train/train_VGG19.py:305-307: the parameters of the first `n` modules of model0 - of feature_extractor for an
+    OpenPose_Model - (conv1_1 .. conv4_1, nine convs) stop training."""
+    trunk = model.model0 if _model_kind(model, "train.freeze_trunk") == 'vgg' else model.feature_extractor
     for i in range(n):
-        for p in model.model0[i].parameters():
+        for p in trunk[i].parameters():
             p.requires_grad = False
     return model
 
 
 def train_step(model, optimizer, image, heat, paf):
-    """One iteration of train/train_VGG19.py:206-217: (total_loss, saved_for_log)."""
+    """One iteration of train/train_VGG19.py:206-217: (total_loss, saved_for_log).  The loss is ``encode.get_loss`` for an
+    RtposeVGG and ``encode.get_loss_openpose`` for an OpenPose_Model."""
+    get_loss = encode.get_loss if _model_kind(model, "train.train_step") == 'vgg' else encode.get_loss_openpose
     _, saved_for_loss = forward_train(model, image)
-    total_loss, saved_for_log = encode.get_loss(saved_for_loss, heat, paf)
+    total_loss, saved_for_log = get_loss(saved_for_loss, heat, paf)
     optimizer.zero_grad()
     total_loss.backward()
     optimizer.step()
