@@ -238,6 +238,65 @@ int rtpose_prelu_grad(const float* z, const rtpose_layout* lz, const float* slop
                       const rtpose_layout* lgy, float* out, const rtpose_layout* lout, float* dslope,
                       float* workspace, size_t workspace_floats, int channels, int N, int H, int W, void* stream);
 
+/* ---- 2b, continued.  Training-mode BatchNorm2d (+ ReLU) on layout slices (csrc/batchnorm.hip): what the stacked
+ * hourglass needs to train (train.batch_norm).  The inference plans know a BatchNorm only by its RUNNING statistics
+ * (folded into a conv, or a per-channel (scale, shift) a 1x1 conv applies while it stages its input); these three compute
+ * the statistics of the batch, normalise by them and differentiate through them.
+ *
+ * All three check every argument on the host before any HIP call (RTPOSE_E_INVAL with a text), launch on `stream`, and
+ * read and write only `channels` channels from `choff` at the valid pixels of each layout: gaps and neighbouring channels
+ * are neither read nor written, so a zero-initialised output keeps its zero gaps and stays convolvable.  16-byte loads and
+ * stores where every cstride and choff is a multiple of 4 floats and every base is 16-byte aligned, element by element
+ * otherwise: the same values either way.  No atomics and no scratch: the same inputs give the same bits on every run.
+ * P = N * H * W below; P = 1 is refused, as torch refuses it.
+ *
+ * Sums.  The valid pixels are cut, in (n, y, x) order, into rtpose_bn_slabs() slabs that depend on the shape only - equal
+ * multiples of 64 pixels but for the last one, across image boundaries; within a slab a thread owns fixed channels and
+ * adds its terms in a fixed pixel order IN FP64 (an fp32 value and the product of two are exact there; the passes are
+ * memory bound), the threads of a channel are added in a fixed order through LDS, every slab's two [channels] partials go
+ * to `workspace` (device memory of the caller, 8-byte aligned, rtpose_bn_workspace_doubles() = slabs * 2 * channels +
+ * 2 * channels doubles) and a second launch of one thread per channel adds them in slab order and finalises.
+ * Both queries return 0 for a shape the launchers refuse (channels < 1, an empty map, P = 1, P above 2^31 - 256).
+ *
+ * rtpose_bn_stats.  ONE pass over x with SHIFTED sums, K[c] = x[0, 0, 0, c] (the channel's first value), all in fp64:
+ *     S1 = sum (x - K)      S2 = sum (x - K) * (x - K)
+ *     md = S1 / P           mean = K + md           var = max(S2 / P - md * md, 0)        (the biased variance)
+ *     invstd = 1 / sqrt(var + eps)      scale = weight * invstd      shift = bias - mean * scale
+ * each rounded to fp32 once into save[RTPOSE_BN_SAVE_ROWS][channels]: rows mean, var, invstd, scale, shift, and mean_lo =
+ * fp32(mean - fp32(mean)), the part of the mean its fp32 value lost (the backward's sums use mean + mean_lo).  (scale,
+ * shift) is the pair _native_state.bn_scale_shift makes from the running statistics, here from the batch's.
+ * |md| is of the order of the channel's standard deviation whatever its mean, so S2 / P - md * md does not cancel for
+ * |mean| >> std.  Bounds against the float64 values m, v of the same fp32 inputs, u = 2^-53, D1 = sum |x - K| / P,
+ * D2 = sum (x - K)^2 / P:   |mean - m| <= 2^-24 |m| + (P + 8) u (D1 + |m|),   |var - v| <= 2^-24 v + (3 P + 8) u D2
+ * - one fp32 rounding plus fp64 dust; invstd, scale and shift are smooth functions of these in fp64, rounded once.
+ * running_mean / running_var (both or neither; device float[channels]) are updated in place by torch's rule, in fp64:
+ *     r = fp32((1 - momentum) * r + momentum * v),   v = mean, and var * P / (P - 1) for the variance. */
+#define RTPOSE_BN_SAVE_ROWS 6
+size_t rtpose_bn_workspace_doubles(int channels, int N, int H, int W);
+int rtpose_bn_slabs(int channels, int N, int H, int W);
+int rtpose_bn_stats(const float* x, const rtpose_layout* lx, const float* weight, const float* bias, float* running_mean,
+                    float* running_var, double momentum, double eps, float* save, double* workspace,
+                    size_t workspace_doubles, int channels, int N, int H, int W, void* stream);
+/* y = scale[c] * x + shift[c] with save's rows 3 and 4: one fp32 multiply and one fp32 add, never fused (the expression
+ * of the inference plan's pre-activation), then max(y, 0) if relu.  y / ly may name the slice x / lx names. */
+int rtpose_bn_apply(const float* x, const rtpose_layout* lx, const float* save, float* y, const rtpose_layout* ly, int relu,
+                    int channels, int N, int H, int W, void* stream);
+/* torch's native_batch_norm_backward (training) from x, gy, save and weight.
+ *     g = relu ? (scale[c] * x + shift[c] > 0 ? gy : 0) : gy
+ * - the mask is RECOMPUTED from x with apply's two fp32 operations, so it is the mask of the y apply wrote; no y is kept.
+ * First pass, fp64, the two-stage reduction above:   G1 = sum g      G2 = sum g * (x - K)
+ *     mdk = (mean + mean_lo) - K      dbias = G1      dweight = invstd * (G2 - mdk * G1)         (invstd: save's fp32 value)
+ *     A = weight * invstd             B = A * G1 / P  C = A * invstd * dweight / P   (dweight before its rounding)
+ * dbias, dweight, A, B, C rounded to fp32 once each; A, B, C go to the workspace's tail (float[3][channels] at double
+ * offset slabs * 2 * channels).  Second pass, element by element in fp32, each operation rounded on its own:
+ *     dx = (g * A - B) - (x - mean) * C
+ * x - mean is formed first, so nothing cancels for |mean| >> std.  dweight and dbias are OVERWRITTEN; either may be NULL
+ * (frozen) - the sums are still taken for dx.  dx may be NULL (the input needs no gradient): only the reduction runs.
+ * dx / ldx may name the slice gy / lgy names. */
+int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, const rtpose_layout* lgy, const float* save,
+                   const float* weight, int relu, float* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
+                   double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream);
+
 /* ---- the first layer: nn.Conv2d(3, 64, 3, 1, 1) (+ nn.ReLU), conv1_1 of the VGG-19 front end
  * (lib/network/rtpose_vgg.py:23-35, `model0.0`; csrc/conv_first.hip).  Reads the image where it is -
  * dense NCHW fp32 (`x_nchw`), or, with x_nchw = NULL, a layout buffer with >= 3 channels per pixel

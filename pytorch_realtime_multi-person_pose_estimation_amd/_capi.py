@@ -17,6 +17,7 @@ NUM_LIMB = 19
 DTYPE_F32, DTYPE_BF16, DTYPE_BF16X3 = 0, 1, 2
 WINO_DEFAULT, WINO7_AUTO, WINO3_AUTO = -1, 1, 3
 NMS_NO_REFINE, NMS_GAUSSIAN = 1, 2
+BN_SAVE_ROWS = 6   # RTPOSE_BN_SAVE_ROWS: mean, var, invstd, scale, shift, mean_lo
 
 
 class RtposeError(RuntimeError):
@@ -192,6 +193,11 @@ _SIGS = {
     "rtpose_prelu_grad_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "rtpose_prelu_grad_slabs": (_i, [_i, _i, _i, _i]),
     "rtpose_prelu_grad": (_i, [_vp, _LP, _vp, _vp, _LP, _vp, _LP, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "rtpose_bn_workspace_doubles": (_sz, [_i, _i, _i, _i]),
+    "rtpose_bn_slabs": (_i, [_i, _i, _i, _i]),
+    "rtpose_bn_stats": (_i, [_vp, _LP, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "rtpose_bn_apply": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
+    "rtpose_bn_grad": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _i, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),
     "rtpose_conv1x1_pair": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_bf16_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),

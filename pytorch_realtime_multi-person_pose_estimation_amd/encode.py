@@ -167,6 +167,28 @@ def get_loss_openpose(saved_for_loss, heat_temp, vec_temp):
     return total, log
 
 
+def get_loss_hourglass(saved_for_loss, heat_temp, heat_weight, vec_temp, vec_weight):
+    """train/train_SH.py:80-126 with the reference's signature: ``saved_for_loss = [score_paf, score_ht]`` of the last
+    stack, the masked sum of squares of each over ``2 * batch_size`` (nn.MSELoss(size_average=False) of pred * weight
+    against target * weight), PAF term then heat-map term.  (total_loss, saved_for_log) with the reference's keys 'paf',
+    'heatmap', max_ht / min_ht (without the background channel), max_paf / min_paf.  A weight of None means ones: the
+    multiplications are left out."""
+    if not isinstance(saved_for_loss, (list, tuple)) or len(saved_for_loss) != 2:
+        raise ValueError("get_loss_hourglass wants [score_paf, score_ht] of the last stack")
+    batch_size = heat_temp.size(0)
+    pred1 = saved_for_loss[0] if vec_weight is None else saved_for_loss[0] * vec_weight
+    gt1 = vec_temp if vec_weight is None else vec_temp * vec_weight
+    pred2 = saved_for_loss[1] if heat_weight is None else saved_for_loss[1] * heat_weight
+    gt2 = heat_temp if heat_weight is None else heat_weight * heat_temp
+    loss1 = torch.nn.functional.mse_loss(pred1, gt1, reduction='sum') / (2 * batch_size)
+    loss2 = torch.nn.functional.mse_loss(pred2, gt2, reduction='sum') / (2 * batch_size)
+    total = 0 + loss1
+    total = total + loss2
+    log = OrderedDict([('paf', loss1.item()), ('heatmap', loss2.item())])
+    log.update(_extremes(saved_for_loss[-1].detach(), saved_for_loss[-2].detach()))
+    return total, log
+
+
 def _extremes(last_heat, last_paf):
     """The four range entries of saved_for_log: the last heat map without its background channel, the last PAF."""
     parts = last_heat[:, :last_heat.shape[1] - 1]

@@ -1,5 +1,6 @@
-"""Training through the library's kernels: ``loss.backward()`` and ``optimizer.step()`` of the reference's loop
-(train/train_VGG19.py:194-217) on an ``RtposeVGG`` or an ``openpose.OpenPose_Model``.
+"""Training through the library's kernels: ``loss.backward()`` and ``optimizer.step()`` of the reference's loops
+(train/train_VGG19.py:194-217, train/train_SH.py:160-172) on an ``RtposeVGG``, an ``openpose.OpenPose_Model`` or an
+``hourglass.HourglassNet``.
 
 PyTorch keeps the graph and the optimizer; every convolution of it, forward and backward, is hand-written HIP:
 
@@ -29,7 +30,13 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   own storage, so a slope edited through ``.data`` needs no ``invalidate_weights()`` and the packed-filter cache is as it
   was.
 
-The NCHW <-> layout conversion around every conv is known overhead; activations do not stay in layouts across layers yet.
+* The stacked hourglass (training mode only): ``batch_norm(x, bn, relu)`` is training-mode ``nn.BatchNorm2d`` (+ ReLU) through
+  ``rtpose_bn_stats`` / ``rtpose_bn_apply`` / ``rtpose_bn_grad`` (batch statistics in fp64, running statistics updated by the
+  kernel); ``conv7x7_s2`` the 7x7 stride-2 stem, whose weight gradient is ``rtpose_conv2d_wgrad`` (k = 7) on the zero-stuffed
+  output gradient; ``hourglass_forward(model, x, conv, bn, stem)`` the reference's forward order written once over three
+  callables, which ``forward_train`` calls with the native operations (and the tests with torch's float64 ones).
+
+The NCHW <-> layout conversion around every operation is known overhead; activations do not stay in layouts across layers yet.
 """
 import ctypes as C
 import weakref
@@ -40,6 +47,7 @@ import torch.nn.functional as F
 
 from . import _capi, encode
 from ._capi import lib, check, ptr, current_stream
+from .hourglass import HourglassNet
 from .network import RtposeVGG
 from .openpose import OpenPose_Model
 
@@ -86,12 +94,18 @@ def _packed_for(weight, bias, which, epoch=0, resync=False):
         entry = _packed[id(weight)] = {'ref': weakref.ref(weight)}
         weakref.finalize(weight, _packed.pop, id(weight), None)
     key = (epoch, weight._version, weight.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    if which == 'fwd' and bias is not None:
+    if which in ('fwd', 'stem') and bias is not None:
         key += (bias._version, bias.data_ptr())
     hit = entry.get(which)
     if hit is not None and hit[0] == key and not resync:
         return hit[1], hit[2]
     w = weight.detach()
+    if which == 'stem':      # the 7x7 stride-2 stem's own packing, from the unfolded filter
+        wp = torch.zeros(lib.rtpose_conv7x7_s2_packed_floats(), dtype=torch.float32, device=w.device)
+        check(lib.rtpose_pack_conv7x7_s2(ptr(w.contiguous()), ptr(bias.detach().contiguous()) if bias is not None else None,
+                                         ptr(wp), current_stream()), "rtpose_pack_conv7x7_s2")
+        entry[which] = (key, wp, None)
+        return wp, None
     if which == 'fwd':
         b = bias.detach() if bias is not None else torch.zeros(w.shape[0], dtype=torch.float32, device=w.device)
         wp, bp = _pack(w.contiguous(), b.contiguous(), _up8(w.shape[1]))
@@ -242,6 +256,159 @@ def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None):
     return _Conv2d.apply(x, weight, bias, bool(relu), int(epoch), bool(resync), prelu)
 
 
+# ---- the stacked hourglass: its stem and training-mode BatchNorm -------------------------------------------------------------
+class _Conv7x7S2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, epoch, resync):
+        if not (x.is_cuda and weight.is_cuda):
+            raise _capi.RtposeError("train.conv7x7_s2 runs only on an MI355X (HIP) device; got x on %s, weight on %s - there "
+                                    "is deliberately no CPU fallback" % (x.device, weight.device))
+        if (x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3
+                or tuple(weight.shape) != (64, 3, 7, 7) or (bias is not None and tuple(bias.shape) != (64,))):
+            raise _capi.RtposeError("train.conv7x7_s2 is nn.Conv2d(3, 64, 7, stride 2, padding 3) on an NCHW fp32 image; got "
+                                    "filters %s for input %s" % (tuple(weight.shape), tuple(x.shape)))
+        if ctx.needs_input_grad[0]:
+            raise _capi.RtposeError("train.conv7x7_s2: the stem reads the image and has no data gradient; x must not require "
+                                    "a gradient")
+        with torch.cuda.device(x.device):
+            n, _, h, w = x.shape
+            ho, wo = (h + 1) // 2, (w + 1) // 2
+            xc = x.detach().contiguous()
+            wp, _ = _packed_for(weight, bias, 'stem', epoch, resync)
+            ly = _capi.Layout.dense(64, ho, wo)
+            ybuf = _buffer(ly, n, ho, wo, x.device, False)
+            check(lib.rtpose_conv7x7_s2(ptr(xc), None, None, ptr(wp), ptr(ybuf), C.byref(ly), 0, n, h, w, current_stream()),
+                  "rtpose_conv7x7_s2")
+            y = _from_layout(ybuf, ly, n, 64, ho, wo)
+        ctx.geom = (n, h, w, ho, wo)
+        ctx.has_bias = bias is not None
+        ctx.x = xc if (ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])) else None
+        ctx.save_for_backward(weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        """The weight gradient as the stride-1 k = 7 one on the zero-stuffed gradient: gyz[n, :, 2 y, 2 x] = gy[n, :, y, x]
+        and zero elsewhere, an H x W map; then dW[o][c][dy][dx] = sum gyz[n, Y, X, o] * x[n, Y + dy - 3, X + dx - 3, c]
+        exactly (the zeros add nothing), which is rtpose_conv2d_wgrad on the image layout with a gap of 3."""
+        (weight,) = ctx.saved_tensors
+        n, h, w, ho, wo = ctx.geom
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        dw = db = None
+        with torch.cuda.device(gy.device):
+            gyz = torch.zeros((n, 64, h, w), dtype=torch.float32, device=gy.device)
+            gyz[:, :, ::2, ::2] = gy.detach().float()
+            gbuf, lg = _to_layout(gyz, 3)
+            del gyz
+            xbuf, lx = _to_layout(ctx.x, 3)
+            dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            db = torch.empty(64, dtype=torch.float32, device=gy.device) if need_b else None
+            floats = lib.rtpose_conv2d_wgrad_workspace_floats(3, 64, 7, n, h, w)
+            ws = torch.empty(floats, dtype=torch.float32, device=gy.device)
+            d = _capi.WgradDesc()
+            d.x, d.gy, d.dw, d.dbias = xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
+            d.workspace, d.workspace_floats = ws.data_ptr(), floats
+            d.lx, d.lgy = lx, lg
+            d.cin, d.cout, d.k = 3, 64, 7
+            check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad")
+            if not need_w:
+                dw = None
+        return None, dw, db, None, None
+
+
+def conv7x7_s2(x, weight, bias=None, epoch=0, resync=False):
+    """``conv2d(x, weight, bias, stride=2, padding=3)`` of the hourglass stem (nn.Conv2d(3, 64, 7, 2, 3), no activation):
+    forward ``rtpose_conv7x7_s2`` on the packing of the unfolded filter, weight and bias gradients from
+    ``rtpose_conv2d_wgrad`` (k = 7) on the zero-stuffed output gradient - four times the necessary multiplies, on a
+    3 -> 64 layer.  `x` is the image: one that requires a gradient is refused.  `epoch` / `resync`: see ``conv2d``."""
+    return _Conv7x7S2.apply(x, weight, bias, int(epoch), bool(resync))
+
+
+def _check_bn(x, bn):
+    if not isinstance(bn, nn.BatchNorm2d):
+        raise _capi.RtposeError("train.batch_norm takes an nn.BatchNorm2d; got %s" % type(bn).__name__)
+    if not bn.training:
+        raise _capi.RtposeError("train.batch_norm computes batch statistics: the nn.BatchNorm2d must be in training mode "
+                                "(eval-mode fine-tuning on frozen statistics is out of scope)")
+    if not bn.affine or not bn.track_running_stats:
+        raise _capi.RtposeError("train.batch_norm: the nn.BatchNorm2d must have affine=True and track_running_stats=True")
+    if bn.momentum is None:
+        raise _capi.RtposeError("train.batch_norm: momentum=None (the cumulative moving average) is not supported; give the "
+                                "nn.BatchNorm2d a momentum")
+    if not (x.is_cuda and bn.weight.is_cuda):
+        raise _capi.RtposeError("train.batch_norm runs only on an MI355X (HIP) device; got x on %s, the BatchNorm on %s - "
+                                "there is deliberately no CPU fallback" % (x.device, bn.weight.device))
+    if x.dtype != torch.float32 or bn.weight.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != bn.num_features:
+        raise _capi.RtposeError("train.batch_norm takes an NCHW fp32 input with %d channels; got %s %s"
+                                % (bn.num_features, x.dtype, tuple(x.shape)))
+    if x.shape[0] * x.shape[2] * x.shape[3] < 2:
+        raise _capi.RtposeError("train.batch_norm: expected more than 1 value per channel when training; got input size %s"
+                                % (tuple(x.shape),))
+
+
+class _BatchNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, relu):
+        _check_bn(x, bn)
+        with torch.cuda.device(x.device):
+            stream = current_stream()
+            n, c, h, w = x.shape
+            xbuf, lx = _to_layout(x.detach().contiguous(), 0)
+            doubles = lib.rtpose_bn_workspace_doubles(c, n, h, w)
+            ws = torch.empty(doubles, dtype=torch.float64, device=x.device)
+            save = torch.empty(_capi.BN_SAVE_ROWS * c, dtype=torch.float32, device=x.device)
+            rm, rv = bn.running_mean, bn.running_var
+            if not (rm.is_contiguous() and rv.is_contiguous() and rm.dtype == rv.dtype == torch.float32):
+                raise _capi.RtposeError("train.batch_norm: running_mean / running_var must be contiguous fp32 tensors")
+            check(lib.rtpose_bn_stats(ptr(xbuf), C.byref(lx), ptr(weight.detach().contiguous()), ptr(bias.detach().contiguous()),
+                                      ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), ptr(save), ptr(ws), doubles,
+                                      c, n, h, w, stream), "rtpose_bn_stats")
+            bn.num_batches_tracked.add_(1)
+            ybuf = _buffer(lx, n, h, w, x.device, False)
+            check(lib.rtpose_bn_apply(ptr(xbuf), C.byref(lx), ptr(save), ptr(ybuf), C.byref(lx), 1 if relu else 0, c, n, h, w,
+                                      stream), "rtpose_bn_apply")
+            y = _from_layout(ybuf, lx, n, c, h, w)
+        ctx.geom = (n, c, h, w)
+        ctx.relu = bool(relu)
+        ctx.save_for_backward(weight)    # (for autograd's check that the weight was not modified in place since)
+        ctx.xbuf, ctx.lx, ctx.save = (xbuf, lx, save) if any(ctx.needs_input_grad[:3]) else (None, None, None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (weight,) = ctx.saved_tensors
+        n, c, h, w = ctx.geom
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        dx = dw = db = None
+        with torch.cuda.device(gy.device):
+            gbuf, lg = _to_layout(gy.detach().float().contiguous(), 0)
+            doubles = lib.rtpose_bn_workspace_doubles(c, n, h, w)
+            ws = torch.empty(doubles, dtype=torch.float64, device=gy.device)
+            dw = torch.empty(c, dtype=torch.float32, device=gy.device) if need_w else None
+            db = torch.empty(c, dtype=torch.float32, device=gy.device) if need_b else None
+            # dx onto gy's own buffer: every element reads only its own gy element
+            check(lib.rtpose_bn_grad(ptr(ctx.xbuf), C.byref(ctx.lx), ptr(gbuf), C.byref(lg), ptr(ctx.save),
+                                     ptr(weight.detach().contiguous()), 1 if ctx.relu else 0, ptr(gbuf) if need_x else None,
+                                     C.byref(lg) if need_x else None, ptr(dw), ptr(db), ptr(ws), doubles, c, n, h, w,
+                                     current_stream()), "rtpose_bn_grad")
+            if need_x:
+                dx = _from_layout(gbuf, lg, n, c, h, w)
+        return dx, dw, db, None, None
+
+
+def batch_norm(x, bn, relu=False):
+    """``bn(x)`` of an ``nn.BatchNorm2d`` in training mode (affine, track_running_stats, a momentum), then ReLU if `relu`,
+    with the library's kernels in both directions; NCHW fp32 device tensors.  Forward: ``rtpose_bn_stats`` (batch
+    statistics in fp64; ``running_mean`` / ``running_var`` updated in place by the kernel, ``num_batches_tracked`` + 1) and
+    ``rtpose_bn_apply``; backward: ``rtpose_bn_grad`` on the kept layout copy of x (the ReLU mask is recomputed from it; no y
+    is kept), for any ``requires_grad`` subset of (x, weight, bias).  The kernels write the running statistics through raw
+    pointers, which bumps no ``_version``: a model whose inference plan folds them calls ``invalidate_weights()``
+    (``forward_train`` does)."""
+    return _BatchNorm.apply(x, bn.weight, bn.bias, bn, bool(relu))
+
+
 def run_sequential(seq, x, epoch=0, resync=False):
     """An nn.Sequential of the RtposeVGG / OpenPose_Model trees (nn.Conv2d [+ nn.ReLU | nn.PReLU] and
     nn.MaxPool2d(2, 2, 0)): the convs through ``conv2d`` with their ReLU or PReLU fused, the pools through torch.
@@ -316,24 +483,111 @@ def _forward_train_openpose(model, x, epoch, resync):
     return [(paf_ret[-2], heat_ret[-2]), (paf_ret[-1], heat_ret[-1])], [paf_ret, heat_ret]
 
 
+# ---- the stacked hourglass (lib/network/rtpose_hourglass.py), written once over three callables ------------------------------
+def hourglass_bottleneck(blk, x, conv, bn):
+    """reference :26-46: bn -> relu -> conv three times, the skip (through `downsample` where the width changes) added last"""
+    out = conv(bn(x, blk.bn1), blk.conv1)
+    out = conv(bn(out, blk.bn2), blk.conv2)
+    out = conv(bn(out, blk.bn3), blk.conv3)
+    residual = conv(x, blk.downsample[0]) if blk.downsample is not None else x
+    return out + residual
+
+
+def _hg_chain(seq, x, conv, bn):
+    for blk in seq:
+        x = hourglass_bottleneck(blk, x, conv, bn)
+    return x
+
+
+def _hg_level(hg, n, x, conv, bn):
+    """reference :74-86"""
+    up1 = _hg_chain(hg[n - 1][0], x, conv, bn)
+    low1 = _hg_chain(hg[n - 1][1], F.max_pool2d(x, 2, stride=2), conv, bn)
+    low2 = _hg_level(hg, n - 1, low1, conv, bn) if n > 1 else _hg_chain(hg[n - 1][3], low1, conv, bn)
+    low3 = _hg_chain(hg[n - 1][2], low2, conv, bn)
+    return up1 + F.interpolate(low3, scale_factor=2)
+
+
+def hourglass_forward(model, x, conv, bn, stem):
+    """The reference's training-mode forward (lib/network/rtpose_hourglass.py:26-46, :74-89, :162-189) over the module
+    tree of a ``HourglassNet``, with the three operations as callables: ``conv(x, m)`` an ``nn.Conv2d`` m (stride 1,
+    "same"), ``bn(x, m)`` ReLU of an ``nn.BatchNorm2d`` m in training mode (every BatchNorm of this network is followed by
+    one), ``stem(x, m)`` the 7x7 stride-2 ``conv1``.  Max-pool, nearest upsampling, the residual sums and the hand-over
+    ``x + fc_ + paf_score_ + ht_score_`` are torch's, in the reference's order of additions.  Returns
+    ((score_paf, score_ht), [score_paf, score_ht]) of the last stack - the only one the reference supervises."""
+    if not isinstance(model, HourglassNet):
+        raise TypeError("train.hourglass_forward takes an hourglass.HourglassNet; got %s" % type(model).__name__)
+    if not model.training:
+        raise _capi.RtposeError("train.hourglass_forward is the training-mode forward (batch statistics): call .train() "
+                                "first; fine-tuning on frozen statistics (.eval()) is out of scope")
+    x = bn(stem(x, model.conv1), model.bn1)
+    x = _hg_chain(model.layer1, x, conv, bn)
+    x = F.max_pool2d(x, 2, stride=2)
+    x = _hg_chain(model.layer2, x, conv, bn)
+    x = _hg_chain(model.layer3, x, conv, bn)
+    score_paf = score_ht = None
+    for i in range(model.num_stacks):
+        y = _hg_level(model.hg[i].hg, model.hg[i].depth, x, conv, bn)
+        y = _hg_chain(model.res[i], y, conv, bn)
+        y = bn(conv(y, model.fc[i][0]), model.fc[i][1])
+        score_paf = conv(y, model.score_paf[i])
+        score_ht = conv(y, model.score_ht[i])
+        if i < model.num_stacks - 1:
+            fc_ = conv(y, model.fc_[i])
+            paf_score_ = conv(score_paf, model.paf_score_[i])
+            ht_score_ = conv(score_ht, model.ht_score_[i])
+            x = x + fc_ + paf_score_ + ht_score_
+    return (score_paf, score_ht), [score_paf, score_ht]
+
+
+def _forward_train_hourglass(model, x):
+    if not model.training:
+        raise _capi.RtposeError("train.forward_train of a HourglassNet is the training-mode forward (batch statistics): call "
+                                ".train() first; fine-tuning on frozen statistics (.eval()) is out of scope")
+    if x.requires_grad:
+        raise _capi.RtposeError("train.forward_train of a HourglassNet: the stem has no data gradient; the image must not "
+                                "require a gradient")
+    # the BatchNorm kernels write the running statistics through raw pointers (no _version bump): the inference plan,
+    # which folds them, re-packs after .eval() only if the weight epoch moves
+    model.invalidate_weights()
+    epoch, resync = model._weights_epoch[0], bool(getattr(model, 'always_resync', False))
+
+    def conv(t, m):
+        k = m.kernel_size[0]
+        if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
+            raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
+        return conv2d(t, m.weight, m.bias, False, epoch, resync)
+
+    return hourglass_forward(model, x, conv, lambda t, m: batch_norm(t, m, relu=True),
+                             lambda t, m: conv7x7_s2(t, m.weight, m.bias, epoch, resync))
+
+
 def _model_kind(model, who):
     if isinstance(model, RtposeVGG):
         return 'vgg'
     if isinstance(model, OpenPose_Model):
         return 'openpose'
-    raise TypeError("%s takes a network.RtposeVGG or an openpose.OpenPose_Model; got %s" % (who, type(model).__name__))
+    if isinstance(model, HourglassNet):
+        return 'hourglass'
+    raise TypeError("%s takes a network.RtposeVGG, an openpose.OpenPose_Model or an hourglass.HourglassNet; got %s"
+                    % (who, type(model).__name__))
 
 
 def forward_train(model, x):
     """The reference's forward over the module tree of `model`, with an autograd graph behind the outputs.
     ``RtposeVGG`` (lib/network/rtpose_vgg.py:158-198): ((out6_1, out6_2), saved_for_loss[12]).
     ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177):
-    ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret])."""
+    ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]).
+    ``HourglassNet`` in training mode (``hourglass_forward`` with ``conv2d``, ``batch_norm(relu=True)`` and ``conv7x7_s2``):
+    ((score_paf, score_ht), [score_paf, score_ht]) of the last stack; every BatchNorm's running statistics are updated and
+    ``model.invalidate_weights()`` is called once."""
     kind = _model_kind(model, "train.forward_train")
     if not x.is_cuda:
         raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
                                 "deliberately no CPU fallback" % (x.device,))
     # the contract of _native_state.py: invalidate_weights() (the epoch) and always_resync decide a re-pack here as well
+    if kind == 'hourglass':
+        return _forward_train_hourglass(model, x)
     epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
     return (_forward_train_vgg if kind == 'vgg' else _forward_train_openpose)(model, x, epoch, resync)
 
@@ -341,19 +595,30 @@ def forward_train(model, x):
 def freeze_trunk(model, n=20):
     """train/train_VGG19.py:305-307: the parameters of the first `n` modules of model0 - of feature_extractor for an
     OpenPose_Model - (conv1_1 .. conv4_1, nine convs) stop training."""
-    trunk = model.model0 if _model_kind(model, "train.freeze_trunk") == 'vgg' else model.feature_extractor
+    kind = _model_kind(model, "train.freeze_trunk")
+    if kind == 'hourglass':
+        raise TypeError("train.freeze_trunk: the reference freezes nothing of a HourglassNet (train/train_SH.py); it takes a "
+                        "network.RtposeVGG or an openpose.OpenPose_Model")
+    trunk = model.model0 if kind == 'vgg' else model.feature_extractor
     for i in range(n):
         for p in trunk[i].parameters():
             p.requires_grad = False
     return model
 
 
-def train_step(model, optimizer, image, heat, paf):
+def train_step(model, optimizer, image, heat, paf, heat_mask=None, paf_mask=None):
     """One iteration of train/train_VGG19.py:206-217: (total_loss, saved_for_log).  The loss is ``encode.get_loss`` for an
-    RtposeVGG and ``encode.get_loss_openpose`` for an OpenPose_Model."""
-    get_loss = encode.get_loss if _model_kind(model, "train.train_step") == 'vgg' else encode.get_loss_openpose
+    RtposeVGG, ``encode.get_loss_openpose`` for an OpenPose_Model and, for a HourglassNet (train/train_SH.py:160-172),
+    ``encode.get_loss_hourglass`` with the optional `heat_mask` / `paf_mask` (None: ones); the masks belong to that loss
+    only."""
+    kind = _model_kind(model, "train.train_step")
+    if kind != 'hourglass' and (heat_mask is not None or paf_mask is not None):
+        raise TypeError("train.train_step: heat_mask / paf_mask belong to the HourglassNet loss (encode.get_loss_hourglass)")
     _, saved_for_loss = forward_train(model, image)
-    total_loss, saved_for_log = get_loss(saved_for_loss, heat, paf)
+    if kind == 'hourglass':
+        total_loss, saved_for_log = encode.get_loss_hourglass(saved_for_loss, heat, heat_mask, paf, paf_mask)
+    else:
+        total_loss, saved_for_log = (encode.get_loss if kind == 'vgg' else encode.get_loss_openpose)(saved_for_loss, heat, paf)
     optimizer.zero_grad()
     total_loss.backward()
     optimizer.step()
