@@ -297,6 +297,49 @@ int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, con
                    const float* weight, int relu, float* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
                    double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream);
 
+/* ---- 2b, continued.  Backward pass of the depthwise 3x3 convolution, padding 1, stride 1 or 2 (csrc/dwconv_backward.hip):
+ * what nn.Conv2d(C, C, 3, stride, 1, groups = C, bias = False) of the ShuffleNetV2 blocks needs to train
+ * (train.dwconv3x3); the forward is rtpose_dwconv3x3.  H, W are the conv's INPUT size, stride is 1 or 2,
+ * Ho = (H - 1) / stride + 1 and Wo likewise: rtpose_dwconv3x3's rule.
+ *
+ * Both launchers check every argument on the host before any HIP call (RTPOSE_E_INVAL with a text), launch on `stream`,
+ * accept any C >= 1, and read and write only C channels from `choff`: neighbouring channels are neither read nor written,
+ * and nothing but the valid pixels of an output slice is written.  16-byte loads and stores where every cstride and choff
+ * is a multiple of 4 floats and every base is 16-byte aligned, element by element otherwise: the same values either way.
+ * No atomics and no scratch: the same inputs give the same bits on every run.
+ *
+ * Weight gradient.
+ *     dw[c][0][ky][kx] = sum over (n, yo, xo) of gy[n, yo, xo, c] * x[n, stride * yo + ky - 1, stride * xo + kx - 1, c]
+ *     dbias[c]         = sum over (n, yo, xo) of gy[n, yo, xo, c]                  (dbias may be NULL)
+ * Both are OVERWRITTEN; dw is dense [C][1][3][3] fp32, the shape of the nn.Conv2d.weight, dbias float[C].  `x` / lx is the
+ * conv's input, H x W with zero gaps of at least 1 (a tap is a constant pixel offset, no bounds test); `gy` / lgy is
+ * Ho x Wo and is read at its valid pixels only.  The sums follow rtpose_bn_grad's scheme: the valid OUTPUT pixels are cut,
+ * in (n, yo, xo) order, into rtpose_dwconv3x3_wgrad_slabs() slabs that depend on the shape only - equal multiples of 64
+ * pixels but for the last one, across image boundaries; within a slab a thread owns fixed channels and adds its 9 (+ 1)
+ * terms in a fixed pixel order IN FP64 (the product of two fp32 values is exact there; the pass is memory bound), the
+ * threads of a channel are added in a fixed order through LDS, every slab's [10][C] partials go to `workspace` (device
+ * memory of the caller, 8-byte aligned, rtpose_dwconv3x3_wgrad_workspace_doubles() = slabs * 10 * C doubles) and a second
+ * launch adds them in slab order and rounds once to fp32.  Against the float64 sum v of the same fp32 operands:
+ * |result - v| <= 2^-24 |v| + (P_out + 8) 2^-53 sum |terms|, P_out = N * Ho * Wo; with integer operands whose sums of
+ * absolute terms stay below 2^53 the result is fp32(v), bit for bit.
+ * Both queries return 0 for a shape the launcher refuses (C < 1, an empty map, a stride other than 1 or 2, N * H * W above
+ * the launch limit of 2^31 - 256 pixels). */
+size_t rtpose_dwconv3x3_wgrad_workspace_doubles(int C, int N, int H, int W, int stride);
+int rtpose_dwconv3x3_wgrad_slabs(int C, int N, int H, int W, int stride);
+int rtpose_dwconv3x3_wgrad(const float* x, const rtpose_layout* lx, const float* gy, const rtpose_layout* lgy, float* dw,
+                           float* dbias, double* workspace, size_t workspace_doubles, int C, int N, int H, int W, int stride,
+                           void* stream);
+/* Data gradient.  `w` is the forward's [9][C] tap-major packing (w[ky * 3 + kx][c]), UNFLIPPED: the kernel does the flip.
+ *     dx[n, y, x, c] = sum over the taps (ky, kx) with (y + 1 - ky) and (x + 1 - kx) divisible by stride of
+ *                      w[ky * 3 + kx][c] * gy[n, (y + 1 - ky) / stride, (x + 1 - kx) / stride, c]
+ * `gy` / lgy is Ho x Wo with zero gaps of at least 1: a tap that lands on yo = -1, yo = Ho, xo = -1 or xo = Wo reads a gap
+ * (an even H at stride 2 does reach yo = Ho).  fp32, one rounding per product and one per add, never fused, from +0, the
+ * contributing taps in order of ascending gy row, then ascending gy column (ky = 2, 1, 0, within a row kx = 2, 1, 0): a
+ * host restatement reproduces the bits.  At stride 1 this is what rtpose_dwconv3x3 computes with flipped taps and a zero
+ * bias.  All H x W valid pixels of `dx` / ldx are written; dx must not overlap gy. */
+int rtpose_dwconv3x3_dgrad(const float* gy, const rtpose_layout* lgy, const float* w, float* dx, const rtpose_layout* ldx, int C,
+                           int N, int H, int W, int stride, void* stream);
+
 /* ---- the first layer: nn.Conv2d(3, 64, 3, 1, 1) (+ nn.ReLU), conv1_1 of the VGG-19 front end
  * (lib/network/rtpose_vgg.py:23-35, `model0.0`; csrc/conv_first.hip).  Reads the image where it is -
  * dense NCHW fp32 (`x_nchw`), or, with x_nchw = NULL, a layout buffer with >= 3 channels per pixel

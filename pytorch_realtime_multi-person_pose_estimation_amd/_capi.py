@@ -198,6 +198,10 @@ _SIGS = {
     "rtpose_bn_stats": (_i, [_vp, _LP, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rtpose_bn_apply": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_bn_grad": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _i, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "rtpose_dwconv3x3_wgrad_workspace_doubles": (_sz, [_i, _i, _i, _i, _i]),
+    "rtpose_dwconv3x3_wgrad_slabs": (_i, [_i, _i, _i, _i, _i]),
+    "rtpose_dwconv3x3_wgrad": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "rtpose_dwconv3x3_dgrad": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),
     "rtpose_conv1x1_pair": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_bf16_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),

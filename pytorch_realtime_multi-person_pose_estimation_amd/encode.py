@@ -10,7 +10,8 @@ Reference-exact: every decision of the encoder (``e <= 4.6052``, ``|cross| < 1``
 bit for bit, the heat values within 1 fp32 ulp (``exp``).  Not the reference's: ``np.linalg.norm`` may use a fused
 multiply-add inside BLAS's ``dot``, the limb norm here is the unfused ``sqrt(vx * vx + vy * vy)``.
 
-``stage_losses`` covers ``network.RtposeVGG`` only (OpenPose_Model and the hourglass return other numbers of stage
+``get_loss_hourglass`` and ``get_loss_shufflenet`` are the masked losses of train/train_SH.py and
+train/train_ShuffleNetV2.py.  ``stage_losses`` covers ``network.RtposeVGG`` only (OpenPose_Model and the hourglass return other numbers of stage
 outputs); ``get_loss_openpose`` is the loss of an ``openpose.OpenPose_Model`` in torch, as ``get_loss`` is for rtpose_vgg
 (train.train_step picks between them); ``encode_targets`` takes any skeleton and any stride, 4 included.
 """
@@ -182,6 +183,26 @@ def get_loss_hourglass(saved_for_loss, heat_temp, heat_weight, vec_temp, vec_wei
     gt2 = heat_temp if heat_weight is None else heat_weight * heat_temp
     loss1 = torch.nn.functional.mse_loss(pred1, gt1, reduction='sum') / (2 * batch_size)
     loss2 = torch.nn.functional.mse_loss(pred2, gt2, reduction='sum') / (2 * batch_size)
+    total = 0 + loss1
+    total = total + loss2
+    log = OrderedDict([('paf', loss1.item()), ('heatmap', loss2.item())])
+    log.update(_extremes(saved_for_loss[-1].detach(), saved_for_loss[-2].detach()))
+    return total, log
+
+
+def get_loss_shufflenet(saved_for_loss, heat_temp, heat_weight, vec_temp, vec_weight):
+    """train/train_ShuffleNetV2.py:77-123 with the reference's signature: ``saved_for_loss = [PAF, HEAT]``, the MEAN of the
+    masked squares of each (nn.MSELoss(size_average=True) of pred * weight against target * weight), PAF term then
+    heat-map term.  (total_loss, saved_for_log) with the reference's keys 'paf', 'heatmap', max_ht / min_ht (without the
+    background channel), max_paf / min_paf.  A weight of None means ones: the multiplications are left out."""
+    if not isinstance(saved_for_loss, (list, tuple)) or len(saved_for_loss) != 2:
+        raise ValueError("get_loss_shufflenet wants [PAF, HEAT], the two outputs of the network")
+    pred1 = saved_for_loss[0] if vec_weight is None else saved_for_loss[0] * vec_weight
+    gt1 = vec_temp if vec_weight is None else vec_temp * vec_weight
+    pred2 = saved_for_loss[1] if heat_weight is None else saved_for_loss[1] * heat_weight
+    gt2 = heat_temp if heat_weight is None else heat_weight * heat_temp
+    loss1 = torch.nn.functional.mse_loss(pred1, gt1)
+    loss2 = torch.nn.functional.mse_loss(pred2, gt2)
     total = 0 + loss1
     total = total + loss2
     log = OrderedDict([('paf', loss1.item()), ('heatmap', loss2.item())])

@@ -7,7 +7,10 @@ missing ``network.slim`` helpers are given the semantics inferred from its call 
 ``network.0.*`` (data/bn), ``network.1.{0,1}.*`` (stem conv+bn), ``network.{3,4,5}.{b}.conv.{i}.{0,1}.*``,
 ``…conv0.{i}…``, ``network.6.{0,1}.*`` (conv5), ``paf.*``, ``heatmap.*``.  ``forward`` runs the native
 executor (csrc/shufflenet.hip); eval-mode BatchNorm is folded into the convs here, on the device,
-whenever a parameter/buffer version changes.  Training-mode BN is out of scope (inference path).
+whenever a parameter/buffer version or the weight epoch changes.  ``forward`` and ``plan_for`` are the
+inference path and refuse training mode; a model in training mode runs through ``train.forward_train`` /
+``train.train_step`` (batch statistics, ``train.shufflenet_forward``), which update the running statistics
+and call ``invalidate_weights()`` so that the next ``.eval()`` forward folds them anew.
 """
 import ctypes as C
 

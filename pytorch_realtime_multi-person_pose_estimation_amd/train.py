@@ -1,6 +1,6 @@
 """Training through the library's kernels: ``loss.backward()`` and ``optimizer.step()`` of the reference's loops
-(train/train_VGG19.py:194-217, train/train_SH.py:160-172) on an ``RtposeVGG``, an ``openpose.OpenPose_Model`` or an
-``hourglass.HourglassNet``.
+(train/train_VGG19.py:194-217, train/train_SH.py:160-172, train/train_ShuffleNetV2.py:126-172) on an ``RtposeVGG``, an
+``openpose.OpenPose_Model``, an ``hourglass.HourglassNet`` or a ``shufflenet.Network``.
 
 PyTorch keeps the graph and the optimizer; every convolution of it, forward and backward, is hand-written HIP:
 
@@ -36,6 +36,13 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   output gradient; ``hourglass_forward(model, x, conv, bn, stem)`` the reference's forward order written once over three
   callables, which ``forward_train`` calls with the native operations (and the tests with torch's float64 ones).
 
+* ShuffleNetV2 (training mode only): ``dwconv3x3(x, weight, stride)`` is the depthwise 3x3 conv of the blocks, forward
+  ``rtpose_dwconv3x3``, backward ``rtpose_dwconv3x3_wgrad`` / ``rtpose_dwconv3x3_dgrad``; ``conv3x3_s2`` the 3 -> 24 stride-2
+  stem, forward ``rtpose_stem_conv3x3_s2``, both gradients from the stride-1 kernels on the zero-stuffed output gradient;
+  ``shufflenet_forward(model, x, conv, bn, dw, stem)`` the reference's forward order written once over four callables (the
+  split, ``torch.cat``, the channel shuffle and the ceil-mode max-pool stay torch's); the pointwise convs and the heads are
+  ``conv2d``, every BatchNorm ``batch_norm``.
+
 The NCHW <-> layout conversion around every operation is known overhead; activations do not stay in layouts across layers yet.
 """
 import ctypes as C
@@ -50,6 +57,7 @@ from ._capi import lib, check, ptr, current_stream
 from .hourglass import HourglassNet
 from .network import RtposeVGG
 from .openpose import OpenPose_Model
+from .shufflenet import Network as ShuffleNetV2
 
 
 def dgrad_weights(weight):
@@ -325,6 +333,151 @@ def conv7x7_s2(x, weight, bias=None, epoch=0, resync=False):
     return _Conv7x7S2.apply(x, weight, bias, int(epoch), bool(resync))
 
 
+# ---- ShuffleNetV2: its depthwise 3x3 convs and its stem --------------------------------------------------------------------------
+def _dw_taps(weight, cp):
+    """[C, 1, 3, 3] -> the [9][cp] tap-major packing rtpose_dwconv3x3 reads (channels past C zero), and a zero bias"""
+    c = weight.shape[0]
+    taps = torch.zeros((9, cp), dtype=torch.float32, device=weight.device)
+    taps[:, :c] = weight.detach().reshape(c, 9).t()
+    return taps, torch.zeros(cp, dtype=torch.float32, device=weight.device)
+
+
+class _DwConv3x3(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        if not (torch.is_tensor(x) and torch.is_tensor(weight) and x.is_cuda and weight.is_cuda):
+            raise _capi.RtposeError("train.dwconv3x3 runs only on an MI355X (HIP) device; got x on %s, weight on %s - there is "
+                                    "deliberately no CPU fallback" % (getattr(x, 'device', None), getattr(weight, 'device', None)))
+        if stride not in (1, 2):
+            raise _capi.RtposeError("train.dwconv3x3: stride must be 1 or 2; got %r" % (stride,))
+        if (x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4
+                or tuple(weight.shape) != (x.shape[1], 1, 3, 3)):
+            raise _capi.RtposeError("train.dwconv3x3 is nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False) on an NCHW fp32 input: "
+                                    "filters [C, 1, 3, 3]; got filters %s %s for input %s %s"
+                                    % (weight.dtype, tuple(weight.shape), x.dtype, tuple(x.shape)))
+        with torch.cuda.device(x.device):
+            n, c, h, w = x.shape
+            ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+            xbuf, lx = _to_layout(x.detach().contiguous(), 1)
+            taps, zero = _dw_taps(weight, lx.cstride)
+            ly = _capi.Layout.dense(lx.cstride, ho, wo)
+            ybuf = _buffer(ly, n, ho, wo, x.device, False)
+            check(lib.rtpose_dwconv3x3(ptr(xbuf), C.byref(lx), ptr(taps), ptr(zero), ptr(ybuf), C.byref(ly), lx.cstride, n, h, w,
+                                       stride, current_stream()), "rtpose_dwconv3x3")
+            y = _from_layout(ybuf, ly, n, c, ho, wo)
+        ctx.geom = (n, c, h, w, ho, wo, stride)
+        ctx.save_for_backward(weight)    # (for autograd's check that the filters were not modified in place since)
+        ctx.xbuf, ctx.lx = (xbuf, lx) if ctx.needs_input_grad[1] else (None, None)
+        ctx.taps = taps if ctx.needs_input_grad[0] else None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        (weight,) = ctx.saved_tensors
+        n, c, h, w, ho, wo, stride = ctx.geom
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = dw = None
+        with torch.cuda.device(gy.device):
+            stream = current_stream()
+            gbuf, lg = _to_layout(gy.detach().float().contiguous(), 1)
+            if need_x:
+                ld = _capi.Layout.dense(lg.cstride, h, w)
+                dbuf = _buffer(ld, n, h, w, gy.device, False)
+                check(lib.rtpose_dwconv3x3_dgrad(ptr(gbuf), C.byref(lg), ptr(ctx.taps), ptr(dbuf), C.byref(ld), lg.cstride, n, h, w,
+                                                 stride, stream), "rtpose_dwconv3x3_dgrad")
+                dx = _from_layout(dbuf, ld, n, c, h, w)
+            if need_w:
+                dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+                doubles = lib.rtpose_dwconv3x3_wgrad_workspace_doubles(c, n, h, w, stride)
+                ws = torch.empty(doubles, dtype=torch.float64, device=gy.device)
+                check(lib.rtpose_dwconv3x3_wgrad(ptr(ctx.xbuf), C.byref(ctx.lx), ptr(gbuf), C.byref(lg), ptr(dw), None, ptr(ws),
+                                                 doubles, c, n, h, w, stride, stream), "rtpose_dwconv3x3_wgrad")
+        return dx, dw, None
+
+
+def dwconv3x3(x, weight, stride=1):
+    """``conv2d(x, weight, None, stride, 1, groups=C)`` of an ``nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False)``, stride 1
+    or 2, with the library's kernels in both directions; NCHW fp32 device tensors, `weight` [C, 1, 3, 3].  Forward:
+    ``rtpose_dwconv3x3`` on the channels rounded up to 8, with the taps permuted to its [9][C] packing by torch ops on the
+    device on every call (9 C floats: nothing is cached, so nothing needs invalidating) and a zero bias.  Backward:
+    ``rtpose_dwconv3x3_dgrad`` on the same taps and ``rtpose_dwconv3x3_wgrad`` on the kept layout copy of x, each only if its
+    gradient is needed."""
+    return _DwConv3x3.apply(x, weight, stride)
+
+
+class _Conv3x3S2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, epoch, resync):
+        if not (torch.is_tensor(x) and torch.is_tensor(weight) and x.is_cuda and weight.is_cuda):
+            raise _capi.RtposeError("train.conv3x3_s2 runs only on an MI355X (HIP) device; got x on %s, weight on %s - there "
+                                    "is deliberately no CPU fallback" % (getattr(x, 'device', None), getattr(weight, 'device', None)))
+        if (x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3
+                or tuple(weight.shape) != (24, 3, 3, 3)):
+            raise _capi.RtposeError("train.conv3x3_s2 is nn.Conv2d(3, 24, 3, stride 2, padding 1, bias=False) on an NCHW fp32 "
+                                    "image; got filters %s %s for input %s %s"
+                                    % (weight.dtype, tuple(weight.shape), x.dtype, tuple(x.shape)))
+        with torch.cuda.device(x.device):
+            n, _, h, w = x.shape
+            ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            xbuf, lx = _to_layout(x.detach().contiguous(), 1)
+            # the kernel's packing: [tap][input channel, padded to 8][output channel]
+            taps = torch.zeros((9, 8, 24), dtype=torch.float32, device=x.device)
+            taps[:, :3] = weight.detach().permute(2, 3, 1, 0).reshape(9, 3, 24)
+            zero = torch.zeros(24, dtype=torch.float32, device=x.device)
+            ly = _capi.Layout.dense(24, ho, wo)
+            ybuf = _buffer(ly, n, ho, wo, x.device, False)
+            check(lib.rtpose_stem_conv3x3_s2(ptr(xbuf), C.byref(lx), ptr(taps), ptr(zero), ptr(ybuf), C.byref(ly), 8, 24, n, h, w,
+                                             0, current_stream()), "rtpose_stem_conv3x3_s2")
+            y = _from_layout(ybuf, ly, n, 24, ho, wo)
+        ctx.geom = (n, h, w)
+        ctx.weight, ctx.epoch, ctx.resync = weight, epoch, resync
+        ctx.save_for_backward(weight)
+        ctx.xbuf, ctx.lx = (xbuf, lx) if ctx.needs_input_grad[1] else (None, None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        """Both gradients from the stride-1 k = 3 kernels on the zero-stuffed gradient: gyz[n, :, 2 y, 2 x] = gy[n, :, y, x] and
+        zero elsewhere, an H x W map.  dW[o][c][ky][kx] = sum gyz[n, Y, X, o] * x[n, Y + ky - 1, X + kx - 1, c] and
+        dx[n, Y, X, c] = sum w[o][c][ky][kx] * gyz[n, Y + 1 - ky, X + 1 - kx, o] exactly: the zeros add nothing."""
+        (weight,) = ctx.saved_tensors
+        n, h, w = ctx.geom
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = dw = None
+        with torch.cuda.device(gy.device):
+            gyz = torch.zeros((n, 24, h, w), dtype=torch.float32, device=gy.device)
+            gyz[:, :, ::2, ::2] = gy.detach().float()
+            gbuf, lg = _to_layout(gyz, 1)
+            del gyz
+            if need_x:
+                wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
+                dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, 3, 3, False, n, h, w)
+                dx = _from_layout(dbuf, ld, n, 3, h, w)
+            if need_w:
+                dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+                floats = lib.rtpose_conv2d_wgrad_workspace_floats(3, 24, 3, n, h, w)
+                ws = torch.empty(floats, dtype=torch.float32, device=gy.device)
+                d = _capi.WgradDesc()
+                d.x, d.gy, d.dw, d.dbias = ctx.xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), None
+                d.workspace, d.workspace_floats = ws.data_ptr(), floats
+                d.lx, d.lgy = ctx.lx, lg
+                d.cin, d.cout, d.k = 3, 24, 3
+                check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad")
+        return dx, dw, None, None
+
+
+def conv3x3_s2(x, weight, epoch=0, resync=False):
+    """``conv2d(x, weight, None, stride=2, padding=1)`` of the ShuffleNetV2 stem (nn.Conv2d(3, 24, 3, 2, 1, bias=False), no
+    activation): forward ``rtpose_stem_conv3x3_s2`` (relu = 0, a zero bias; the taps permuted to its packing on every call).
+    Unlike the hourglass stem this one has a data gradient - ``data/bn`` in front of it trains: the weight gradient is
+    ``rtpose_conv2d_wgrad`` (k = 3) and the data gradient ``rtpose_conv2d`` (k = 3, the cached ``dgrad_weights`` packing) of
+    the zero-stuffed H x W output gradient.  Both reuses spend four times the necessary multiplies, on a 3 -> 24 layer.
+    `epoch` / `resync`: see ``conv2d``."""
+    return _Conv3x3S2.apply(x, weight, int(epoch), bool(resync))
+
+
 def _check_bn(x, bn):
     if not isinstance(bn, nn.BatchNorm2d):
         raise _capi.RtposeError("train.batch_norm takes an nn.BatchNorm2d; got %s" % type(bn).__name__)
@@ -562,6 +715,85 @@ def _forward_train_hourglass(model, x):
                              lambda t, m: conv7x7_s2(t, m.weight, m.bias, epoch, resync))
 
 
+# ---- ShuffleNetV2 (lib/network/rtpose_shufflenetV2.py), written once over four callables -------------------------------------------
+def _channel_shuffle(x):
+    n, c, h, w = x.shape
+    return x.view(n, 2, c // 2, h, w).transpose(1, 2).reshape(n, c, h, w)
+
+
+def shufflenet_block(blk, x, conv, bn, dw):
+    """reference :31-63: conv_bn_relu 1x1, conv_bn depthwise 3x3, conv_bn_relu 1x1 on the second half of the channels (the
+    first half passes through), or on all of them beside conv0 (depthwise 3x3, 1x1) where the block has one; then the
+    concatenation and the shuffle of two groups"""
+    def unit(t, seq, op):
+        return bn(op(t, seq[0]), seq[1], len(seq) > 2)
+
+    def branch(t):
+        return unit(unit(unit(t, blk.conv[0], conv), blk.conv[1], dw), blk.conv[2], conv)
+
+    if hasattr(blk, 'conv0'):
+        x = torch.cat((unit(unit(x, blk.conv0[0], dw), blk.conv0[1], conv), branch(x)), 1)
+    else:
+        half = x.shape[1] // 2
+        x = torch.cat((x[:, :half], branch(x[:, half:])), 1)
+    return _channel_shuffle(x)
+
+
+def shufflenet_forward(model, x, conv, bn, dw, stem):
+    """The reference's training-mode forward (lib/network/rtpose_shufflenetV2.py:56-63, :96-104, :144-148) over the module
+    tree of a ``shufflenet.Network``, with the four operations as callables: ``conv(x, m)`` a pointwise ``nn.Conv2d`` m,
+    ``bn(x, m, relu)`` an ``nn.BatchNorm2d`` m in training mode followed by a ReLU if `relu`, ``dw(x, m)`` a depthwise 3x3
+    ``nn.Conv2d`` m of stride 1 or 2, ``stem(x, m)`` the 3x3 stride-2 ``stage1/conv``.  The split, ``torch.cat``, the channel
+    shuffle and ``MaxPool2d(3, 2, 0, ceil_mode=True)`` are torch's.  Returns ([PAF, HEAT], [PAF, HEAT])."""
+    if not isinstance(model, ShuffleNetV2):
+        raise TypeError("train.shufflenet_forward takes a shufflenet.Network; got %s" % type(model).__name__)
+    if not model.training:
+        raise _capi.RtposeError("train.shufflenet_forward is the training-mode forward (batch statistics): call .train() "
+                                "first; fine-tuning on frozen statistics (.eval()) is out of scope")
+    net = model.network
+    x = bn(x, net[0], False)
+    x = bn(stem(x, net[1][0]), net[1][1], True)
+    pool = net[2]
+    x = F.max_pool2d(x, pool.kernel_size, pool.stride, pool.padding, ceil_mode=pool.ceil_mode)
+    for stage in (net[3], net[4], net[5]):
+        for blk in stage:
+            x = shufflenet_block(blk, x, conv, bn, dw)
+    x = bn(conv(x, net[6][0]), net[6][1], True)
+    paf = conv(x, model.paf)
+    heat = conv(x, model.heatmap)
+    return [paf, heat], [paf, heat]
+
+
+def _forward_train_shufflenet(model, x):
+    if not model.training:
+        raise _capi.RtposeError("train.forward_train of a shufflenet.Network is the training-mode forward (batch statistics): "
+                                "call .train() first; fine-tuning on frozen statistics (.eval()) is out of scope")
+    # the BatchNorm kernels write the running statistics through raw pointers (no _version bump): the inference plan,
+    # which folds them, re-packs after .eval() only if the weight epoch moves
+    model.invalidate_weights()
+    epoch, resync = model._weights_epoch[0], bool(getattr(model, 'always_resync', False))
+
+    def conv(t, m):
+        if m.kernel_size != (1, 1) or m.stride != (1, 1) or m.padding != (0, 0) or m.dilation != (1, 1) or m.groups != 1:
+            raise _capi.RtposeError("train: a pointwise conv of the ShuffleNetV2 tree is 1x1, stride 1; got %r" % (m,))
+        return conv2d(t, m.weight, m.bias, False, epoch, resync)
+
+    def dw(t, m):
+        s = m.stride[0]
+        if (m.kernel_size != (3, 3) or m.stride != (s, s) or m.padding != (1, 1) or m.dilation != (1, 1)
+                or m.groups != m.in_channels or m.out_channels != m.in_channels or m.bias is not None):
+            raise _capi.RtposeError("train: a depthwise conv of the ShuffleNetV2 tree is 3x3, padding 1, groups = channels, "
+                                    "without a bias; got %r" % (m,))
+        return dwconv3x3(t, m.weight, s)
+
+    def stem(t, m):
+        if m.kernel_size != (3, 3) or m.stride != (2, 2) or m.padding != (1, 1) or m.dilation != (1, 1) or m.bias is not None:
+            raise _capi.RtposeError("train: the ShuffleNetV2 stem is nn.Conv2d(3, 24, 3, 2, 1, bias=False); got %r" % (m,))
+        return conv3x3_s2(t, m.weight, epoch, resync)
+
+    return shufflenet_forward(model, x, conv, lambda t, m, relu: batch_norm(t, m, relu=relu), dw, stem)
+
+
 def _model_kind(model, who):
     if isinstance(model, RtposeVGG):
         return 'vgg'
@@ -569,8 +801,10 @@ def _model_kind(model, who):
         return 'openpose'
     if isinstance(model, HourglassNet):
         return 'hourglass'
-    raise TypeError("%s takes a network.RtposeVGG, an openpose.OpenPose_Model or an hourglass.HourglassNet; got %s"
-                    % (who, type(model).__name__))
+    if isinstance(model, ShuffleNetV2):
+        return 'shufflenet'
+    raise TypeError("%s takes a network.RtposeVGG, an openpose.OpenPose_Model, an hourglass.HourglassNet or a "
+                    "shufflenet.Network; got %s" % (who, type(model).__name__))
 
 
 def forward_train(model, x):
@@ -580,7 +814,9 @@ def forward_train(model, x):
     ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]).
     ``HourglassNet`` in training mode (``hourglass_forward`` with ``conv2d``, ``batch_norm(relu=True)`` and ``conv7x7_s2``):
     ((score_paf, score_ht), [score_paf, score_ht]) of the last stack; every BatchNorm's running statistics are updated and
-    ``model.invalidate_weights()`` is called once."""
+    ``model.invalidate_weights()`` is called once.
+    ``shufflenet.Network`` in training mode (``shufflenet_forward`` with ``conv2d``, ``batch_norm``, ``dwconv3x3`` and
+    ``conv3x3_s2``): ([PAF, HEAT], [PAF, HEAT]); running statistics and ``invalidate_weights()`` as for the hourglass."""
     kind = _model_kind(model, "train.forward_train")
     if not x.is_cuda:
         raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
@@ -588,6 +824,8 @@ def forward_train(model, x):
     # the contract of _native_state.py: invalidate_weights() (the epoch) and always_resync decide a re-pack here as well
     if kind == 'hourglass':
         return _forward_train_hourglass(model, x)
+    if kind == 'shufflenet':
+        return _forward_train_shufflenet(model, x)
     epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
     return (_forward_train_vgg if kind == 'vgg' else _forward_train_openpose)(model, x, epoch, resync)
 
@@ -599,6 +837,9 @@ def freeze_trunk(model, n=20):
     if kind == 'hourglass':
         raise TypeError("train.freeze_trunk: the reference freezes nothing of a HourglassNet (train/train_SH.py); it takes a "
                         "network.RtposeVGG or an openpose.OpenPose_Model")
+    if kind == 'shufflenet':
+        raise TypeError("train.freeze_trunk: the reference freezes nothing of a shufflenet.Network "
+                        "(train/train_ShuffleNetV2.py); it takes a network.RtposeVGG or an openpose.OpenPose_Model")
     trunk = model.model0 if kind == 'vgg' else model.feature_extractor
     for i in range(n):
         for p in trunk[i].parameters():
@@ -609,14 +850,18 @@ def freeze_trunk(model, n=20):
 def train_step(model, optimizer, image, heat, paf, heat_mask=None, paf_mask=None):
     """One iteration of train/train_VGG19.py:206-217: (total_loss, saved_for_log).  The loss is ``encode.get_loss`` for an
     RtposeVGG, ``encode.get_loss_openpose`` for an OpenPose_Model and, for a HourglassNet (train/train_SH.py:160-172),
-    ``encode.get_loss_hourglass`` with the optional `heat_mask` / `paf_mask` (None: ones); the masks belong to that loss
-    only."""
+    ``encode.get_loss_hourglass`` with the optional `heat_mask` / `paf_mask` (None: ones), for a shufflenet.Network
+    (train/train_ShuffleNetV2.py:144-156) ``encode.get_loss_shufflenet`` with the same masks; the masks belong to those two
+    losses only."""
     kind = _model_kind(model, "train.train_step")
-    if kind != 'hourglass' and (heat_mask is not None or paf_mask is not None):
-        raise TypeError("train.train_step: heat_mask / paf_mask belong to the HourglassNet loss (encode.get_loss_hourglass)")
+    if kind not in ('hourglass', 'shufflenet') and (heat_mask is not None or paf_mask is not None):
+        raise TypeError("train.train_step: heat_mask / paf_mask belong to the HourglassNet and shufflenet.Network losses "
+                        "(encode.get_loss_hourglass, encode.get_loss_shufflenet)")
     _, saved_for_loss = forward_train(model, image)
     if kind == 'hourglass':
         total_loss, saved_for_log = encode.get_loss_hourglass(saved_for_loss, heat, heat_mask, paf, paf_mask)
+    elif kind == 'shufflenet':
+        total_loss, saved_for_log = encode.get_loss_shufflenet(saved_for_loss, heat, heat_mask, paf, paf_mask)
     else:
         total_loss, saved_for_log = (encode.get_loss if kind == 'vgg' else encode.get_loss_openpose)(saved_for_loss, heat, paf)
     optimizer.zero_grad()
