@@ -17,62 +17,26 @@
 //                      A = weight * invstd; B = A * G1 / P; C = A * invstd * dweight / P            (fp64 -> fp32 each)
 //                    dx = (g * A - B) - (x - mean) * C       (fp32: a multiply, a subtract, a subtract and a multiply, a subtract)
 //
-// Sums: the valid pixels p = (n * H + y) * W + x are cut into slabs whose size follows from the shape alone (bn_geometry:
-// equal multiples of 64 pixels but for the last one).  A workgroup of 256 threads is a tx x ty rectangle: a thread owns one
-// unit of V channels (V = 4: 16-byte loads and stores, where every cstride, choff and base allows it; V = 1 otherwise; a last
-// unit with fewer than 4 live channels goes element by element) and walks the pixels p0 + row, p0 + row + ty, ... of its slab,
-// adding its terms in that order in fp64; the rows of a unit are added in row order through LDS; the slab's two [channels]
-// partials go to the caller's workspace, [slab][2][channels] doubles, and a second launch of one thread per channel adds
-// them in slab order and finalises.  No atomics: the same inputs give the same bits on every run.  An fp32 value and the
-// product of two are exact in fp64, so with integer operands every sum is exact whatever its order.
-// The two element-wise passes (apply, dx) are the same kernel without sums; their values do not depend on how the pixels are
-// cut, so they run 64 pixels per workgroup whatever the slab of the sums.
-// Gaps and the channels beside the slices are neither read nor written; every element reads only its own x / gy element, so
-// y may name the slice x names and dx the slice gy names.
+// Sums and walks: chan_slab.h.  The two sum passes add their two terms per channel in fp64 (an fp32 value and the product
+// of two are exact there) and take both through LDS in one pass; the slab's partials are [slab][2][channels] doubles, and
+// the second launch of one thread per channel adds them in slab order and finalises.  apply and dx are the element-wise
+// passes.  Every element reads only its own x / gy element, so y may name the slice x names and dx the slice gy names.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
 
-#include "conv_desc.h"
+#include "chan_slab.h"
 
 namespace rtpose {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kFinalThreads = 64;
-constexpr int kSlabUnit = 64;    // pixels: every slab but the last is a multiple of it
-constexpr int kMaxSlabs = 1024;  // slabs grow beyond kSlabUnit pixels once there would be more than these
-constexpr int kMaxTX = 64;       // channel units a workgroup is wide: 1 KB of one pixel with V = 4
 static_assert(RTPOSE_BN_SAVE_ROWS == 6, "save rows: mean, var, invstd, scale, shift, mean_lo");
-
-struct BnGeom {
-  int slab;   // pixels per slab
-  int slabs;
-  size_t ws_doubles;  // slabs * 2 * channels partials + 2 * channels (the three fp32 dx coefficients of a channel)
-};
-
-// the valid pixels as a count the kernels index with an int, or -1
-long pixel_count(int N, int H, int W) {
-  if (N < 1 || H < 1 || W < 1) return -1;
-  const long nh = (long)N * H;
-  if (nh >= (1L << 31)) return -1;
-  const long P = nh * W;
-  return P < (1L << 31) - kThreads ? P : -1;
-}
 
 bool shape_ok(int channels, int N, int H, int W) { return channels >= 1 && pixel_count(N, H, W) > 1; }
 
-// shape only: nothing here looks at the device
-BnGeom bn_geometry(int channels, int N, int H, int W) {
-  BnGeom g;
-  const long P = pixel_count(N, H, W);
-  const long per = (long)kSlabUnit * kMaxSlabs;
-  g.slab = (int)(kSlabUnit * ((P + per - 1) / per));
-  g.slabs = (int)((P + g.slab - 1) / g.slab);
-  g.ws_doubles = (size_t)g.slabs * 2 * (size_t)channels + 2 * (size_t)channels;
-  return g;
-}
+// slabs * 2 * channels partials + 2 * channels (the three fp32 dx coefficients of a channel)
+size_t ws_doubles(int channels, const SlabGeom& g) { return (size_t)g.slabs * 2 * (size_t)channels + 2 * (size_t)channels; }
 
 struct BnArgs {
   const float* x;
@@ -85,38 +49,25 @@ struct BnArgs {
   int channels, H, W, P;
   int slab;
   int relu;
-  int tx, ty;  // the workgroup's rectangle: tx channel units x ty pixel rows, tx * ty <= kThreads
-  FastDiv d_tx, d_w, d_h;
+  Rect r;
+  FastDiv d_w, d_h;
 };
 
 enum { kStats = 0, kGradSums = 1, kApply = 2, kGradDx = 3 };
-
-template <int V>
-struct Unit {
-  float v[V];
-};
 
 template <int V, int MODE>
 __global__ __launch_bounds__(kThreads) void bn_kernel(const BnArgs a) {
   constexpr bool SUM = MODE == kStats || MODE == kGradSums;
   constexpr bool GRAD = MODE == kGradSums || MODE == kGradDx;
-  __shared__ double red[SUM ? kThreads * V * 2 : 1];
-  const int tid = threadIdx.x;
-  const int row = fast_div(tid, a.d_tx), col = tid - row * a.tx;
-  const int c0 = ((int)blockIdx.y * a.tx + col) * V;
-  const int nc = min(V, a.channels - c0);  // live channels of this thread's unit (<= 0: none)
-  const bool live = row < a.ty && nc > 0;
-  const bool whole = V > 1 && nc == V;
-  const int p0 = (int)blockIdx.x * a.slab;
-  const int p1 = min(p0 + a.slab, a.P);
+  const Place t = place<V>(a.r, a.channels, a.slab, a.P);
 
   // per channel: the shift K of the sums, the fp32 (scale, shift) of apply and of the mask, mean and the dx coefficients
-  double kk[V], acc0[V], acc1[V];
+  double kk[V], acc[2][V];
   float sc[V], sh[V], mean[V], cA[V], cB[V], cC[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) {
-    const bool on = live && v < nc;
-    const int c = c0 + v;
+    const bool on = t.live && v < t.nc;
+    const int c = t.c0 + v;
     kk[v] = (SUM && on) ? (double)a.x[lay_off(a.lx, 0, 0, 0) + c] : 0.0;
     sc[v] = (MODE != kStats && on) ? a.save[3 * a.channels + c] : 0.f;
     sh[v] = (MODE != kStats && on) ? a.save[4 * a.channels + c] : 0.f;
@@ -124,43 +75,17 @@ __global__ __launch_bounds__(kThreads) void bn_kernel(const BnArgs a) {
     cA[v] = (MODE == kGradDx && on) ? a.coef[c] : 0.f;
     cB[v] = (MODE == kGradDx && on) ? a.coef[a.channels + c] : 0.f;
     cC[v] = (MODE == kGradDx && on) ? a.coef[2 * a.channels + c] : 0.f;
-    acc0[v] = acc1[v] = 0.0;
+    acc[0][v] = acc[1][v] = 0.0;
   }
 
-  auto fetch = [&](const float* src, size_t o) {
-    Unit<V> u;
-    if constexpr (V == 4) {
-      if (whole) {
-        const float4 t = *reinterpret_cast<const float4*>(src + o);
-        u.v[0] = t.x, u.v[1] = t.y, u.v[2] = t.z, u.v[3] = t.w;
-        return u;
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < V; ++v) u.v[v] = v < nc ? src[o + v] : 0.f;
-    return u;
-  };
-  auto store = [&](size_t o, const Unit<V>& r) {
-    if constexpr (V == 4) {
-      if (whole) {
-        *reinterpret_cast<float4*>(a.out + o) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-        return;
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < V; ++v)
-      if (v < nc) a.out[o + v] = r.v[v];
-  };
-
-  if (live) {
+  if (t.live) {
     // (unrolled: the sum passes store nothing, so the loads of four pixels are in flight; the additions keep their order)
 #pragma unroll 4
-    for (int p = p0 + row; p < p1; p += a.ty) {
-      const int r = fast_div(p, a.d_w), xx = p - r * a.W;
-      const int n = fast_div(r, a.d_h), yy = r - n * a.H;
-      const Unit<V> xv = fetch(a.x, lay_off(a.lx, n, yy, xx) + c0);
+    for (int p = t.p0 + t.row; p < t.p1; p += a.r.ty) {
+      const Pixel q = pixel_of(p, a.H, a.W, a.d_h, a.d_w);
+      const Unit<V> xv = fetch<V>(a.x, lay_off(a.lx, q) + t.c0, t);
       Unit<V> gv = xv, res;
-      if (GRAD) gv = fetch(a.gy, lay_off(a.lgy, n, yy, xx) + c0);
+      if (GRAD) gv = fetch<V>(a.gy, lay_off(a.lgy, q) + t.c0, t);
 #pragma unroll
       for (int v = 0; v < V; ++v) {
         float y = 0.f;
@@ -172,51 +97,27 @@ __global__ __launch_bounds__(kThreads) void bn_kernel(const BnArgs a) {
         const float g = (GRAD && a.relu) ? (y > 0.f ? gv.v[v] : 0.f) : gv.v[v];
         if (MODE == kStats) {
           const double d = (double)xv.v[v] - kk[v];
-          acc0[v] += d;
-          acc1[v] += d * d;
+          acc[0][v] += d;
+          acc[1][v] += d * d;
         } else if (MODE == kGradSums) {
           const double d = (double)xv.v[v] - kk[v];
-          acc0[v] += (double)g;
-          acc1[v] += (double)g * d;
+          acc[0][v] += (double)g;
+          acc[1][v] += (double)g * d;
         } else if (MODE == kApply) {
           res.v[v] = a.relu ? (y > 0.f ? y : 0.f) : y;
         } else {
           const float xm = xv.v[v] - mean[v];
-          float t = g * cA[v];
-          t = t - cB[v];
+          float t0 = g * cA[v];
+          t0 = t0 - cB[v];
           const float u = xm * cC[v];
-          res.v[v] = t - u;
+          res.v[v] = t0 - u;
         }
       }
-      if (!SUM) store(lay_off(a.lout, n, yy, xx) + c0, res);
+      if (!SUM) store<V>(a.out, lay_off(a.lout, q) + t.c0, t, res);
     }
   }
 
-  if (SUM) {
-    if (live) {
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        red[((row * a.tx + col) * V + v) * 2] = acc0[v];
-        red[((row * a.tx + col) * V + v) * 2 + 1] = acc1[v];
-      }
-    }
-    __syncthreads();
-    if (live && row == 0) {
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        double s0 = red[(col * V + v) * 2], s1 = red[(col * V + v) * 2 + 1];
-        for (int r = 1; r < a.ty; ++r) {
-          s0 += red[((r * a.tx + col) * V + v) * 2];
-          s1 += red[((r * a.tx + col) * V + v) * 2 + 1];
-        }
-        if (v < nc) {
-          double* w = a.ws + (size_t)blockIdx.x * 2 * a.channels;
-          w[c0 + v] = s0;
-          w[a.channels + c0 + v] = s1;
-        }
-      }
-    }
-  }
+  if constexpr (SUM) sum_rows<V, 2, 2>(t, a.r, acc, a.ws, a.channels);
 }
 
 struct FinalArgs {
@@ -234,21 +135,13 @@ struct FinalArgs {
   int slabs, channels, P;
 };
 
-// thread c < channels: the slabs' partials of channel c, added in slab order
-__device__ __forceinline__ void add_slabs(const FinalArgs& a, int c, double& s0, double& s1) {
-  s0 = a.ws[c];
-  s1 = a.ws[a.channels + c];
-  for (int s = 1; s < a.slabs; ++s) {
-    s0 += a.ws[(size_t)s * 2 * a.channels + c];
-    s1 += a.ws[(size_t)s * 2 * a.channels + a.channels + c];
-  }
-}
-
+// thread c < channels
 __global__ __launch_bounds__(kFinalThreads) void bn_stats_final_kernel(const FinalArgs a) {
   const int c = (int)blockIdx.x * kFinalThreads + threadIdx.x;
   if (c >= a.channels) return;
-  double s1, s2;
-  add_slabs(a, c, s1, s2);
+  double s[2];
+  sum_slabs<2, 1>(a.ws, a.slabs, 2, a.channels, 0, c, s);
+  const double s1 = s[0], s2 = s[1];
   const double P = (double)a.P;
   const double md = s1 / P;
   const double mean = (double)a.x0[c] + md;
@@ -275,8 +168,9 @@ __global__ __launch_bounds__(kFinalThreads) void bn_stats_final_kernel(const Fin
 __global__ __launch_bounds__(kFinalThreads) void bn_grad_final_kernel(const FinalArgs a) {
   const int c = (int)blockIdx.x * kFinalThreads + threadIdx.x;
   if (c >= a.channels) return;
-  double g1, g2;
-  add_slabs(a, c, g1, g2);
+  double s[2];
+  sum_slabs<2, 1>(a.ws, a.slabs, 2, a.channels, 0, c, s);
+  const double g1 = s[0], g2 = s[1];
   const double P = (double)a.P;
   const double mean = (double)a.save[c] + (double)a.save[5 * a.channels + c];
   const double mdk = mean - (double)a.x0[c];
@@ -292,70 +186,31 @@ __global__ __launch_bounds__(kFinalThreads) void bn_grad_final_kernel(const Fina
   }
 }
 
-bool layout_sane(const rtpose_layout& l) { return l.cstride > 0 && l.choff >= 0 && l.ws > 0 && l.hs > 0 && l.lead >= 0; }
-
-bool aligned16(const rtpose_layout& l, const void* base) {
-  return slice_aligned(l, 4) && reinterpret_cast<uintptr_t>(base) % 16 == 0;
-}
-
-// the rectangle and the grid of a launch; 0 or fail(...)
-int set_rectangle(BnArgs& a, int V, int slabs, dim3& grid, const char* who) {
-  const int units = ceil_div(a.channels, V);
-  a.tx = units < kMaxTX ? units : kMaxTX;
-  a.ty = kThreads / a.tx;
-  a.d_tx = make_fastdiv(a.tx);
-  const int ctiles = ceil_div(units, a.tx);
-  if (ctiles > 65535) return fail(RTPOSE_E_INVAL, "%s: grid too large", who);
-  grid = dim3((unsigned)slabs, (unsigned)ctiles);
-  return 0;
-}
-
-// what every entry point asks of one of its slices; 0 or fail(...)
-int check_slice(const char* who, const char* what, const void* p, const rtpose_layout* l, int channels, int H, int W) {
-  if (!p) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (%s)", who, what);
-  if (!l) return fail(RTPOSE_E_INVAL, "%s: NULL layout (%s)", who, what);
-  if (!layout_sane(*l)) return fail(RTPOSE_E_INVAL, "%s: bad layout (%s)", who, what);
-  if (!slice_inside(*l, channels)) return fail(RTPOSE_E_INVAL, "%s: %s slice exceeds cstride", who, what);
-  if (!gap_covers(*l, H, W, 0)) return fail(RTPOSE_E_INVAL, "%s: layout smaller than the map (%s)", who, what);
-  return 0;
-}
-
-int check_shape(const char* who, int channels, int N, int H, int W) {
-  if (channels < 1 || N <= 0 || H <= 0 || W <= 0) return fail(RTPOSE_E_INVAL, "%s: empty tensor", who);
-  const long P = pixel_count(N, H, W);
-  if (P < 0) return fail(RTPOSE_E_INVAL, "%s: tensor above the launch limit", who);
+int check_shape_bn(const char* who, int channels, int N, int H, int W, long& P) {
+  if (int rc = check_shape(who, channels, N, H, W, P)) return rc;
   if (P == 1)
     return fail(RTPOSE_E_INVAL, "%s: N * H * W = 1: a channel of one value has no batch statistics (torch refuses it too)", who);
   return 0;
 }
 
-int check_workspace(const char* who, const double* ws, size_t given, const BnGeom& g) {
-  if (!ws) return fail(RTPOSE_E_INVAL, "%s: NULL workspace", who);
-  if (reinterpret_cast<uintptr_t>(ws) % 8) return fail(RTPOSE_E_INVAL, "%s: workspace must be 8-byte aligned", who);
-  if (given < g.ws_doubles)
-    return fail(RTPOSE_E_INVAL, "%s: workspace of %zu doubles below the %zu rtpose_bn_workspace_doubles reports", who, given,
-                g.ws_doubles);
-  return 0;
+int check_ws(const char* who, const double* ws, size_t given, int channels, const SlabGeom& g) {
+  return check_workspace(who, ws, given, ws_doubles(channels, g), "rtpose_bn_workspace_doubles");
 }
 
-// elementwise: apply and dx, whose values do not depend on how the pixels are cut - kSlabUnit pixels per workgroup whatever
-// the slab of the sums, for more workgroups in flight
-void fill_args(BnArgs& a, int channels, int N, int H, int W, const BnGeom& g, bool elementwise) {
+// slab: g.slab for the sums; kSlabUnit for apply and dx (element-wise, chan_slab.h), for more workgroups in flight
+void fill_args(BnArgs& a, int channels, int H, int W, long P, int slab) {
   a.channels = channels;
   a.H = H;
   a.W = W;
-  a.P = N * H * W;
-  a.slab = elementwise ? kSlabUnit : g.slab;
+  a.P = (int)P;
+  a.slab = slab;
   a.d_w = make_fastdiv(W);
   a.d_h = make_fastdiv(H);
 }
 
 template <int MODE>
 void launch_bn(bool vec, dim3 grid, hipStream_t s, const BnArgs& a) {
-  if (vec)
-    hipLaunchKernelGGL((bn_kernel<4, MODE>), grid, dim3(kThreads), 0, s, a);
-  else
-    hipLaunchKernelGGL((bn_kernel<1, MODE>), grid, dim3(kThreads), 0, s, a);
+  launch_units<bn_kernel<4, MODE>, bn_kernel<1, MODE>>(vec, grid, s, a);
 }
 
 }  // namespace
@@ -367,37 +222,38 @@ using namespace rtpose;
 
 size_t rtpose_bn_workspace_doubles(int channels, int N, int H, int W) {
   if (!shape_ok(channels, N, H, W)) return 0;
-  return bn_geometry(channels, N, H, W).ws_doubles;
+  return ws_doubles(channels, slab_geometry(pixel_count(N, H, W)));
 }
 
 int rtpose_bn_slabs(int channels, int N, int H, int W) {
   if (!shape_ok(channels, N, H, W)) return 0;
-  return bn_geometry(channels, N, H, W).slabs;
+  return slab_geometry(pixel_count(N, H, W)).slabs;
 }
 
 int rtpose_bn_stats(const float* x, const rtpose_layout* lx, const float* weight, const float* bias, float* running_mean,
                     float* running_var, double momentum, double eps, float* save, double* workspace,
                     size_t workspace_doubles, int channels, int N, int H, int W, void* stream) {
   const char* who = "bn_stats";
-  if (int rc = check_shape(who, channels, N, H, W)) return rc;
-  if (int rc = check_slice(who, "x", x, lx, channels, H, W)) return rc;
+  long P;
+  if (int rc = check_shape_bn(who, channels, N, H, W, P)) return rc;
+  if (int rc = check_slice(who, "x", x, lx, channels, H, W, 0)) return rc;
   if (!weight || !bias || !save) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (weight, bias or save)", who);
   if ((running_mean == nullptr) != (running_var == nullptr))
     return fail(RTPOSE_E_INVAL, "%s: running_mean and running_var are given together or not at all", who);
   if (!(eps > 0.0) || !std::isfinite(eps)) return fail(RTPOSE_E_INVAL, "%s: eps must be a positive finite number", who);
   if (running_mean && !(momentum >= 0.0 && momentum <= 1.0))
     return fail(RTPOSE_E_INVAL, "%s: momentum must lie in [0, 1]", who);
-  const BnGeom g = bn_geometry(channels, N, H, W);
-  if (int rc = check_workspace(who, workspace, workspace_doubles, g)) return rc;
+  const SlabGeom g = slab_geometry(P);
+  if (int rc = check_ws(who, workspace, workspace_doubles, channels, g)) return rc;
 
   BnArgs a{};
   a.x = x;
   a.ws = workspace;
   a.lx = a.lgy = a.lout = to_lay(lx);
-  fill_args(a, channels, N, H, W, g, false);
+  fill_args(a, channels, H, W, P, g.slab);
   const bool vec = aligned16(*lx, x);
   dim3 grid;
-  if (int rc = set_rectangle(a, vec ? 4 : 1, g.slabs, grid, who)) return rc;
+  if (int rc = set_rectangle(a.r, channels, vec ? 4 : 1, g.slabs, grid, who)) return rc;
 
   static thread_local CheckedPtr c_x, c_w, c_b, c_rm, c_rv, c_s, c_ws;
   const int dev = current_device();
@@ -434,11 +290,11 @@ int rtpose_bn_stats(const float* x, const rtpose_layout* lx, const float* weight
 int rtpose_bn_apply(const float* x, const rtpose_layout* lx, const float* save, float* y, const rtpose_layout* ly, int relu,
                     int channels, int N, int H, int W, void* stream) {
   const char* who = "bn_apply";
-  if (int rc = check_shape(who, channels, N, H, W)) return rc;
-  if (int rc = check_slice(who, "x", x, lx, channels, H, W)) return rc;
-  if (int rc = check_slice(who, "y", y, ly, channels, H, W)) return rc;
+  long P;
+  if (int rc = check_shape_bn(who, channels, N, H, W, P)) return rc;
+  if (int rc = check_slice(who, "x", x, lx, channels, H, W, 0)) return rc;
+  if (int rc = check_slice(who, "y", y, ly, channels, H, W, 0)) return rc;
   if (!save) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (save)", who);
-  const BnGeom g = bn_geometry(channels, N, H, W);
 
   BnArgs a{};
   a.x = x;
@@ -447,10 +303,10 @@ int rtpose_bn_apply(const float* x, const rtpose_layout* lx, const float* save, 
   a.lx = a.lgy = to_lay(lx);
   a.lout = to_lay(ly);
   a.relu = relu ? 1 : 0;
-  fill_args(a, channels, N, H, W, g, true);
+  fill_args(a, channels, H, W, P, kSlabUnit);
   const bool vec = aligned16(*lx, x) && aligned16(*ly, y);
   dim3 grid;
-  if (int rc = set_rectangle(a, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc;
+  if (int rc = set_rectangle(a.r, channels, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc;
 
   static thread_local CheckedPtr c_x, c_s, c_y;
   const int dev = current_device();
@@ -468,15 +324,16 @@ int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, con
                    const float* weight, int relu, float* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
                    double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream) {
   const char* who = "bn_grad";
-  if (int rc = check_shape(who, channels, N, H, W)) return rc;
-  if (int rc = check_slice(who, "x", x, lx, channels, H, W)) return rc;
-  if (int rc = check_slice(who, "gy", gy, lgy, channels, H, W)) return rc;
+  long P;
+  if (int rc = check_shape_bn(who, channels, N, H, W, P)) return rc;
+  if (int rc = check_slice(who, "x", x, lx, channels, H, W, 0)) return rc;
+  if (int rc = check_slice(who, "gy", gy, lgy, channels, H, W, 0)) return rc;
   if (dx)
-    if (int rc = check_slice(who, "dx", dx, ldx, channels, H, W)) return rc;
+    if (int rc = check_slice(who, "dx", dx, ldx, channels, H, W, 0)) return rc;
   if (!save || !weight) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (save or weight)", who);
   if (!dx && !dweight && !dbias) return fail(RTPOSE_E_INVAL, "%s: nothing to compute (dx, dweight and dbias are all NULL)", who);
-  const BnGeom g = bn_geometry(channels, N, H, W);
-  if (int rc = check_workspace(who, workspace, workspace_doubles, g)) return rc;
+  const SlabGeom g = slab_geometry(P);
+  if (int rc = check_ws(who, workspace, workspace_doubles, channels, g)) return rc;
 
   BnArgs a{};
   a.x = x;
@@ -487,12 +344,12 @@ int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, con
   a.lgy = to_lay(lgy);
   a.lout = to_lay(dx ? ldx : lgy);
   a.relu = relu ? 1 : 0;
-  fill_args(a, channels, N, H, W, g, false);
+  fill_args(a, channels, H, W, P, g.slab);
   float* coef = reinterpret_cast<float*>(workspace + (size_t)g.slabs * 2 * (size_t)channels);
   const bool vec_in = aligned16(*lx, x) && aligned16(*lgy, gy);
   const bool vec = vec_in && (!dx || aligned16(*ldx, dx));
   dim3 grid_in, grid;
-  if (int rc = set_rectangle(a, vec_in ? 4 : 1, g.slabs, grid_in, who)) return rc;
+  if (int rc = set_rectangle(a.r, channels, vec_in ? 4 : 1, g.slabs, grid_in, who)) return rc;
 
   static thread_local CheckedPtr c_x, c_gy, c_s, c_w, c_dx, c_dw, c_db, c_ws;
   const int dev = current_device();
@@ -526,7 +383,7 @@ int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, con
     a.out = dx;
     a.coef = coef;
     a.slab = kSlabUnit;
-    if (int rc2 = set_rectangle(a, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc2;
+    if (int rc2 = set_rectangle(a.r, channels, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc2;
     launch_bn<kGradDx>(vec, grid, s, a);
     RTPOSE_HIP_CHECK(hipGetLastError());
   }

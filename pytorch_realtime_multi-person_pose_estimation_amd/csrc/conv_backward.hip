@@ -233,8 +233,6 @@ __global__ __launch_bounds__(kThreads) void relu_grad_kernel(const ReluGradArgs 
   a.out[lay_off(a.lout, n, yy, xx) + c] = yv > 0.f ? g : 0u;
 }
 
-bool layout_sane(const rtpose_layout& l) { return l.cstride > 0 && l.choff >= 0 && l.ws > 0 && l.hs > 0 && l.lead >= 0; }
-
 bool shape_ok(int cin, int cout, int k, int N, int H, int W) {
   return cin >= 1 && cout >= 1 && (k == 1 || k == 3 || k == 7) && N >= 1 && H >= 1 && W >= 1 &&
          (long)N * H * W < (1L << 31) - kThreads && (long)k * k * cout * cin < (1L << 31) - kThreads;

@@ -22,7 +22,7 @@ inline bool gap_covers(const rtpose_layout& l, int H, int W, int p) {
 inline bool below_2g_elems(const rtpose_layout& l, int N, int H, int W) {
   return rtpose_layout_pixels(&l, N, H, W) * (size_t)l.cstride < ((size_t)1 << 31);
 }
-
+inline bool layout_sane(const rtpose_layout& l) { return l.cstride > 0 && l.choff >= 0 && l.ws > 0 && l.hs > 0 && l.lead >= 0; }
 // ---- one launcher's view of a group of 1 or 2 descriptors -----------------------------------------------------------------
 struct ConvSpec {
   const char* who;  // message prefix

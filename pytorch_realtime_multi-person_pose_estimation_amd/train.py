@@ -158,6 +158,37 @@ def _launch_conv(inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
     return out, lout
 
 
+def _wgrad(xbuf, lx, gbuf, lg, like_weight, cin, cout, k, n, h, w, need_b):
+    """rtpose_conv2d_wgrad of the layout buffers of x and of the output gradient (an h x w map, gaps of k // 2):
+    (dw shaped like `like_weight`, db or None)"""
+    dw = torch.empty_like(like_weight, memory_format=torch.contiguous_format)
+    db = torch.empty(cout, dtype=torch.float32, device=gbuf.device) if need_b else None
+    floats = lib.rtpose_conv2d_wgrad_workspace_floats(cin, cout, k, n, h, w)
+    ws = torch.empty(floats, dtype=torch.float32, device=gbuf.device)
+    d = _capi.WgradDesc()
+    d.x, d.gy, d.dw, d.dbias = xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
+    d.workspace, d.workspace_floats = ws.data_ptr(), floats
+    d.lx, d.lgy = lx, lg
+    d.cin, d.cout, d.k = cin, cout, k
+    check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad")
+    return dw, db
+
+
+def _zero_stuffed_layout(gy, h, w, pad):
+    """The output gradient of a stride-2 conv as the h x w map gyz[n, :, 2 y, 2 x] = gy[n, :, y, x], zero elsewhere, in a
+    layout with a gap of `pad`: the stride-1 kernels on it give the stride-2 gradients exactly (the zeros add nothing)."""
+    gyz = torch.zeros((gy.shape[0], gy.shape[1], h, w), dtype=torch.float32, device=gy.device)
+    gyz[:, :, ::2, ::2] = gy.detach().float()
+    return _to_layout(gyz, pad)
+
+
+def _require_device(who, *tensors, names=("x", "weight")):
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise _capi.RtposeError("%s runs only on an MI355X (HIP) device; got %s - there is deliberately no CPU fallback"
+                                % (who, ", ".join("%s on %s" % (nm, getattr(t, 'device', None))
+                                                  for nm, t in zip(names, tensors))))
+
+
 def _check_prelu(prelu, weight, relu):
     if relu:
         raise _capi.RtposeError("train.conv2d: relu and prelu are exclusive")
@@ -170,9 +201,7 @@ def _check_prelu(prelu, weight, relu):
 
 
 def _check_input(x, weight):
-    if not (x.is_cuda and weight.is_cuda):
-        raise _capi.RtposeError("train.conv2d runs only on an MI355X (HIP) device; got x on %s, weight on %s - there is "
-                                "deliberately no CPU fallback" % (x.device, weight.device))
+    _require_device("train.conv2d", x, weight)
     if x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or weight.dim() != 4:
         raise _capi.RtposeError("train.conv2d takes NCHW fp32 inputs and OIHW fp32 filters")
     k = weight.shape[2]
@@ -240,16 +269,7 @@ class _Conv2d(torch.autograd.Function):
                 dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
                 dx = _from_layout(dbuf, ld, n, cin, h, w)
             if need_w or need_b:
-                dw = torch.empty_like(ctx.weight, memory_format=torch.contiguous_format)
-                db = torch.empty(cout, dtype=torch.float32, device=gy.device) if need_b else None
-                floats = lib.rtpose_conv2d_wgrad_workspace_floats(cin, cout, k, n, h, w)
-                ws = torch.empty(floats, dtype=torch.float32, device=gy.device)
-                d = _capi.WgradDesc()
-                d.x, d.gy, d.dw, d.dbias = ctx.xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
-                d.workspace, d.workspace_floats = ws.data_ptr(), floats
-                d.lx, d.lgy = ctx.lx, lg
-                d.cin, d.cout, d.k = cin, cout, k
-                check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, stream), "rtpose_conv2d_wgrad")
+                dw, db = _wgrad(ctx.xbuf, ctx.lx, gbuf, lg, ctx.weight, cin, cout, k, n, h, w, need_b)
                 if not need_w:
                     dw = None
         return dx, dw, db, None, None, None, da
@@ -268,9 +288,7 @@ def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None):
 class _Conv7x7S2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, epoch, resync):
-        if not (x.is_cuda and weight.is_cuda):
-            raise _capi.RtposeError("train.conv7x7_s2 runs only on an MI355X (HIP) device; got x on %s, weight on %s - there "
-                                    "is deliberately no CPU fallback" % (x.device, weight.device))
+        _require_device("train.conv7x7_s2", x, weight)
         if (x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3
                 or tuple(weight.shape) != (64, 3, 7, 7) or (bias is not None and tuple(bias.shape) != (64,))):
             raise _capi.RtposeError("train.conv7x7_s2 is nn.Conv2d(3, 64, 7, stride 2, padding 3) on an NCHW fp32 image; got "
@@ -305,21 +323,9 @@ class _Conv7x7S2(torch.autograd.Function):
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         dw = db = None
         with torch.cuda.device(gy.device):
-            gyz = torch.zeros((n, 64, h, w), dtype=torch.float32, device=gy.device)
-            gyz[:, :, ::2, ::2] = gy.detach().float()
-            gbuf, lg = _to_layout(gyz, 3)
-            del gyz
+            gbuf, lg = _zero_stuffed_layout(gy, h, w, 3)
             xbuf, lx = _to_layout(ctx.x, 3)
-            dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-            db = torch.empty(64, dtype=torch.float32, device=gy.device) if need_b else None
-            floats = lib.rtpose_conv2d_wgrad_workspace_floats(3, 64, 7, n, h, w)
-            ws = torch.empty(floats, dtype=torch.float32, device=gy.device)
-            d = _capi.WgradDesc()
-            d.x, d.gy, d.dw, d.dbias = xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
-            d.workspace, d.workspace_floats = ws.data_ptr(), floats
-            d.lx, d.lgy = lx, lg
-            d.cin, d.cout, d.k = 3, 64, 7
-            check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad")
+            dw, db = _wgrad(xbuf, lx, gbuf, lg, weight, 3, 64, 7, n, h, w, need_b)
             if not need_w:
                 dw = None
         return None, dw, db, None, None
@@ -345,9 +351,7 @@ def _dw_taps(weight, cp):
 class _DwConv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, stride):
-        if not (torch.is_tensor(x) and torch.is_tensor(weight) and x.is_cuda and weight.is_cuda):
-            raise _capi.RtposeError("train.dwconv3x3 runs only on an MI355X (HIP) device; got x on %s, weight on %s - there is "
-                                    "deliberately no CPU fallback" % (getattr(x, 'device', None), getattr(weight, 'device', None)))
+        _require_device("train.dwconv3x3", x, weight)
         if stride not in (1, 2):
             raise _capi.RtposeError("train.dwconv3x3: stride must be 1 or 2; got %r" % (stride,))
         if (x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4
@@ -409,9 +413,7 @@ def dwconv3x3(x, weight, stride=1):
 class _Conv3x3S2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, epoch, resync):
-        if not (torch.is_tensor(x) and torch.is_tensor(weight) and x.is_cuda and weight.is_cuda):
-            raise _capi.RtposeError("train.conv3x3_s2 runs only on an MI355X (HIP) device; got x on %s, weight on %s - there "
-                                    "is deliberately no CPU fallback" % (getattr(x, 'device', None), getattr(weight, 'device', None)))
+        _require_device("train.conv3x3_s2", x, weight)
         if (x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3
                 or tuple(weight.shape) != (24, 3, 3, 3)):
             raise _capi.RtposeError("train.conv3x3_s2 is nn.Conv2d(3, 24, 3, stride 2, padding 1, bias=False) on an NCHW fp32 "
@@ -447,24 +449,13 @@ class _Conv3x3S2(torch.autograd.Function):
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = dw = None
         with torch.cuda.device(gy.device):
-            gyz = torch.zeros((n, 24, h, w), dtype=torch.float32, device=gy.device)
-            gyz[:, :, ::2, ::2] = gy.detach().float()
-            gbuf, lg = _to_layout(gyz, 1)
-            del gyz
+            gbuf, lg = _zero_stuffed_layout(gy, h, w, 1)
             if need_x:
                 wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
                 dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, 3, 3, False, n, h, w)
                 dx = _from_layout(dbuf, ld, n, 3, h, w)
             if need_w:
-                dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-                floats = lib.rtpose_conv2d_wgrad_workspace_floats(3, 24, 3, n, h, w)
-                ws = torch.empty(floats, dtype=torch.float32, device=gy.device)
-                d = _capi.WgradDesc()
-                d.x, d.gy, d.dw, d.dbias = ctx.xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), None
-                d.workspace, d.workspace_floats = ws.data_ptr(), floats
-                d.lx, d.lgy = ctx.lx, lg
-                d.cin, d.cout, d.k = 3, 24, 3
-                check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad")
+                dw, _ = _wgrad(ctx.xbuf, ctx.lx, gbuf, lg, weight, 3, 24, 3, n, h, w, False)
         return dx, dw, None, None
 
 
@@ -489,9 +480,7 @@ def _check_bn(x, bn):
     if bn.momentum is None:
         raise _capi.RtposeError("train.batch_norm: momentum=None (the cumulative moving average) is not supported; give the "
                                 "nn.BatchNorm2d a momentum")
-    if not (x.is_cuda and bn.weight.is_cuda):
-        raise _capi.RtposeError("train.batch_norm runs only on an MI355X (HIP) device; got x on %s, the BatchNorm on %s - "
-                                "there is deliberately no CPU fallback" % (x.device, bn.weight.device))
+    _require_device("train.batch_norm", x, bn.weight, names=("x", "the BatchNorm"))
     if x.dtype != torch.float32 or bn.weight.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != bn.num_features:
         raise _capi.RtposeError("train.batch_norm takes an NCHW fp32 input with %d channels; got %s %s"
                                 % (bn.num_features, x.dtype, tuple(x.shape)))
@@ -562,6 +551,12 @@ def batch_norm(x, bn, relu=False):
     return _BatchNorm.apply(x, bn.weight, bn.bias, bn, bool(relu))
 
 
+def _check_same_conv(m):
+    k = m.kernel_size[0]
+    if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
+        raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
+
+
 def run_sequential(seq, x, epoch=0, resync=False):
     """An nn.Sequential of the RtposeVGG / OpenPose_Model trees (nn.Conv2d [+ nn.ReLU | nn.PReLU] and
     nn.MaxPool2d(2, 2, 0)): the convs through ``conv2d`` with their ReLU or PReLU fused, the pools through torch.
@@ -571,9 +566,7 @@ def run_sequential(seq, x, epoch=0, resync=False):
     while i < len(mods):
         m = mods[i]
         if isinstance(m, nn.Conv2d):
-            k = m.kernel_size[0]
-            if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
-                raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
+            _check_same_conv(m)
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             relu, prelu = isinstance(nxt, nn.ReLU), isinstance(nxt, nn.PReLU)
             if prelu and nxt.num_parameters != m.out_channels:
@@ -693,22 +686,25 @@ def hourglass_forward(model, x, conv, bn, stem):
     return (score_paf, score_ht), [score_paf, score_ht]
 
 
-def _forward_train_hourglass(model, x):
+def _begin_bn_forward(model, what):
+    """What the forward of a network with BatchNorms does first: (epoch, resync) for its convs"""
     if not model.training:
-        raise _capi.RtposeError("train.forward_train of a HourglassNet is the training-mode forward (batch statistics): call "
-                                ".train() first; fine-tuning on frozen statistics (.eval()) is out of scope")
-    if x.requires_grad:
-        raise _capi.RtposeError("train.forward_train of a HourglassNet: the stem has no data gradient; the image must not "
-                                "require a gradient")
+        raise _capi.RtposeError("train.forward_train of a %s is the training-mode forward (batch statistics): call "
+                                ".train() first; fine-tuning on frozen statistics (.eval()) is out of scope" % what)
     # the BatchNorm kernels write the running statistics through raw pointers (no _version bump): the inference plan,
     # which folds them, re-packs after .eval() only if the weight epoch moves
     model.invalidate_weights()
-    epoch, resync = model._weights_epoch[0], bool(getattr(model, 'always_resync', False))
+    return model._weights_epoch[0], bool(getattr(model, 'always_resync', False))
+
+
+def _forward_train_hourglass(model, x):
+    if x.requires_grad:
+        raise _capi.RtposeError("train.forward_train of a HourglassNet: the stem has no data gradient; the image must not "
+                                "require a gradient")
+    epoch, resync = _begin_bn_forward(model, "HourglassNet")
 
     def conv(t, m):
-        k = m.kernel_size[0]
-        if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
-            raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
+        _check_same_conv(m)
         return conv2d(t, m.weight, m.bias, False, epoch, resync)
 
     return hourglass_forward(model, x, conv, lambda t, m: batch_norm(t, m, relu=True),
@@ -765,13 +761,7 @@ def shufflenet_forward(model, x, conv, bn, dw, stem):
 
 
 def _forward_train_shufflenet(model, x):
-    if not model.training:
-        raise _capi.RtposeError("train.forward_train of a shufflenet.Network is the training-mode forward (batch statistics): "
-                                "call .train() first; fine-tuning on frozen statistics (.eval()) is out of scope")
-    # the BatchNorm kernels write the running statistics through raw pointers (no _version bump): the inference plan,
-    # which folds them, re-packs after .eval() only if the weight epoch moves
-    model.invalidate_weights()
-    epoch, resync = model._weights_epoch[0], bool(getattr(model, 'always_resync', False))
+    epoch, resync = _begin_bn_forward(model, "shufflenet.Network")
 
     def conv(t, m):
         if m.kernel_size != (1, 1) or m.stride != (1, 1) or m.padding != (0, 0) or m.dilation != (1, 1) or m.groups != 1:
