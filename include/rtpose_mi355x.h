@@ -1337,6 +1337,84 @@ int rtpose_augment_batch(const rtpose_augment_image* images, int count, const rt
                          float* dst, const rtpose_layout* ldst, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- 4d. Colour jitter of the padded canvas: ColorJitter, RandomGrayscale, normalise, mask ----
+ * stands in for image_transform_train of lib/datasets/transforms.py:53-65 without its JPEG step:
+ * torchvision's ColorJitter and RandomGrayscale on the 8-bit RGB PIL image CenterPad left (the canvas,
+ * fill included), then ToTensor + ImageNet Normalize and utils.mask_valid_area.  On a PIL image every
+ * one of these operations is integer, fp32 or fp64 arithmetic inside Pillow (ImageEnhance, Image.blend,
+ * convert('L' / 'HSV' / 'RGB')); it is restated here operation for operation.  The random draws are
+ * host work (augment.py); the caller passes their results per image.  JPEG re-compression
+ * (RandomApply([jpeg], p=0.1)) is not built.
+ *
+ * `src` is dense fp32 [N][3][h][w] holding the integers 0..255 - what rtpose_augment_batch writes with
+ * norm == 0, nchw == 1 and a whole-canvas mask.  A value v is read as u = (int)v clamped to 0..255,
+ * NaN -> 0.  Per image, on the uint8 (r, g, b) of every canvas pixel, the operations of `order` in turn:
+ *   L(r, g, b) = (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16          (convert('L'))
+ *   blend(d, x, alpha): t = float(d) + alpha * (float(x) - float(d)), three fp32 operations, unfused and
+ *     correctly rounded; 0 <= alpha <= 1: (uint8)(int)t (truncating); otherwise 0 if t <= 0, 255 if
+ *     t >= 255, else (int)t                                                   (ImagingBlend)
+ *   0 brightness: blend(0, x, factor[0]) per channel
+ *   1 contrast:   blend(m, x, factor[1]) per channel, m = int(sum_L / (h * w) + 0.5) in fp64, sum_L the
+ *                 integer sum of L over the whole canvas (fill included, the mask ignored) as it stands
+ *                 when contrast's turn comes, i.e. after the operations before it in `order`
+ *   2 saturation: blend(L(r, g, b), x, factor[2]) per channel
+ *   3 hue:        convert('HSV'), H = (H + hue_shift) mod 256, convert('RGB') - always, a shift of 0
+ *                 still takes the lossy round trip:
+ *     RGB -> HSV: maxc, minc the largest and smallest channel; V = maxc; minc == maxc: H = S = 0; else in
+ *       fp32 cr = maxc - minc, s = cr / maxc, rc = (maxc - r) / cr, gc, bc likewise; r == maxc:
+ *       h = bc - gc in fp32; else g == maxc: h = 2.0 + rc - bc in fp64; else h = 4.0 + gc - rc in fp64;
+ *       h rounded to fp32; h = fmod(h / 6.0 + 1.0, 1.0) in fp64, rounded to fp32;
+ *       H = clip8((int)(h * 255.0)), S = clip8((int)(s * 255.0)), the products in fp64.
+ *     HSV -> RGB: S == 0: grey V; else in fp64 hf = float(H) * 6.0 / 255.0, i = floor(hf),
+ *       f = (float)(hf - i), fs = (float)(S / 255.0); p = round(V * (1.0 - fs)),
+ *       q = round(V * (1.0 - fs * f)) with the product fs * f in fp32,
+ *       t = round(V * (1.0 - fs * (1.0 - f))), round = C's half away from zero, each clipped to 0..255;
+ *       i % 6 = 0: (V, t, p), 1: (q, V, p), 2: (p, V, t), 3: (p, q, V), 4: (t, p, V), 5: (V, p, q).
+ * then, if `gray`, r = g = b = L(r, g, b) (RandomGrayscale), then norm and mask as in 4c: norm == 1:
+ * (float(u) / 255.0f - mean) / std, norm == 0: float(u); exactly 0.0f outside the mask.
+ *
+ * dst, ldst, norm and nchw mean what they mean in rtpose_augment_batch: every element of the three
+ * channels of every named destination slot is written and nothing else.  dst == src is allowed where
+ * nchw == 1 and every image has n_dst == n_src (in place; no two images may then name the same slot),
+ * and refused otherwise.
+ * Launches, per chunk of images (they travel by value as kernel arguments; the library allocates and
+ * copies nothing): the L-sum pass, over the images that have contrast only, applies the operations before
+ * contrast on the fly and writes one uint32 partial per slab of RTPOSE_JITTER_SLAB * ceil(h * w /
+ * (RTPOSE_JITTER_SLAB * 1024)) pixels into the workspace; the apply pass adds an image's partials in
+ * uint64 and applies the whole chain per pixel.  Integer sums, no atomics: an image gives the same bits
+ * alone and inside any batch. */
+#define RTPOSE_JITTER_SLAB 2048
+
+typedef struct rtpose_jitter_image {
+  int32_t order[4];     /* operations in the order applied: 0 brightness, 1 contrast, 2 saturation,
+                           3 hue; -1 = slot unused; an operation may appear at most once             */
+  float factor[3];      /* brightness, contrast, saturation: Pillow's alpha, (float)python_factor    */
+  int32_t hue_shift;    /* 0..255, added to H modulo 256                                              */
+  int32_t gray;         /* != 0: RandomGrayscale fired                                                */
+  int32_t mask[4];      /* as rtpose_augment_image.mask                                               */
+  int32_t n_src, n_dst; /* source and destination slots                                               */
+} rtpose_jitter_image;
+
+typedef struct rtpose_jitter_cfg {
+  uint32_t struct_bytes; /* sizeof(rtpose_jitter_cfg)                                                 */
+  int32_t h, w;          /* the canvas                                                                */
+  int32_t norm, nchw;    /* as in rtpose_augment_cfg                                                  */
+} rtpose_jitter_cfg;
+
+/* Bytes of the caller-provided device workspace (the slab partials) for `count` images; 0 on a bad cfg
+ * or a negative count. */
+size_t rtpose_jitter_workspace_bytes(const rtpose_jitter_cfg* cfg, int count);
+/* Refused before any launch, the message naming the argument and for an image its index: NULL pointers
+ * (ldst only when nchw == 0); a wrong struct_bytes; norm or nchw outside {0, 1}; h or w outside
+ * [1, 65535]; an order entry outside {-1, 0..3} or an operation twice; a factor that is not finite or
+ * is negative; hue_shift outside 0..255; a mask outside the canvas or with x0 > x1, y likewise; n_src
+ * or n_dst outside [0, 65535]; with nchw == 0 a ldst with fewer than 3 channels from choff or a view
+ * smaller than the canvas; dst == src unless in place as above; a workspace smaller than the query
+ * reports.  count == 0 is a no-op. */
+int rtpose_jitter_batch(const rtpose_jitter_image* images, int count, const rtpose_jitter_cfg* cfg,
+                        const float* src, float* dst, const rtpose_layout* ldst, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * 5. Flip test-time-augmentation merge
  *    stands in for evaluate/coco_eval.py:197-242 (handle_paf_and_heat).

@@ -163,6 +163,25 @@ class AugmentCfg(C.Structure):
         return cls(C.sizeof(cls), out_h, out_w, norm, nchw, (C.c_uint8 * 4)(fill[0], fill[1], fill[2], 0))
 
 
+JITTER_SLAB = 2048  # RTPOSE_JITTER_SLAB: the L-sum pass's slabs are equal multiples of it
+
+
+class JitterImage(C.Structure):
+    """rtpose_jitter_image: one image of a rtpose_jitter_batch call (header section 4d)."""
+    _fields_ = [("order", C.c_int32 * 4), ("factor", C.c_float * 3), ("hue_shift", C.c_int32), ("gray", C.c_int32),
+                ("mask", C.c_int32 * 4), ("n_src", C.c_int32), ("n_dst", C.c_int32)]
+
+
+class JitterCfg(C.Structure):
+    """rtpose_jitter_cfg: canvas, arithmetic and destination form of rtpose_jitter_batch (header section 4d)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("h", C.c_int32), ("w", C.c_int32), ("norm", C.c_int32),
+                ("nchw", C.c_int32)]
+
+    @classmethod
+    def make(cls, h, w, norm=1, nchw=1):
+        return cls(C.sizeof(cls), h, w, norm, nchw)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -345,6 +364,8 @@ _SIGS = {
     "rtpose_augment_workspace_bytes": (_sz, [C.POINTER(AugmentCfg), _i]),
     "rtpose_resample_table": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "rtpose_augment_batch": (_i, [C.POINTER(AugmentImage), _i, C.POINTER(AugmentCfg), _vp, _LP, _vp, _sz, _vp]),
+    "rtpose_jitter_workspace_bytes": (_sz, [C.POINTER(JitterCfg), _i]),
+    "rtpose_jitter_batch": (_i, [C.POINTER(JitterImage), _i, C.POINTER(JitterCfg), _vp, _vp, _LP, _vp, _sz, _vp]),
     "rtpose_preprocess_u8_batch": (_i, [C.POINTER(PrepImage), _i, _i, _vp, _LP, _i, _i, _vp]),
     "rtpose_preprocess_u8": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_preprocess_u8_flip": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _i, _vp]),

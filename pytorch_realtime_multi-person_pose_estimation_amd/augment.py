@@ -1,20 +1,31 @@
-"""Training batches augmented on the device: flip, rescale, crop, pad, normalise, mask (csrc/augment.hip, header 4c).
+"""Training batches augmented on the device: flip, rescale, crop, pad, colour jitter, normalise, mask
+(csrc/augment.hip, header 4c; csrc/colorjitter.hip, header 4d).
 
 What ``CocoKeypoints.__getitem__`` of the reference does before it yields ``(image, heatmaps, pafs)``
 (lib/datasets/datasets.py:156-214): the preprocess chain of train/train_VGG19.py:124-130 - ``Normalize``,
 ``RandomApply(HFlip, 0.5)``, ``RescaleRelative()``, ``Crop(368)``, ``CenterPad(368)`` of lib/datasets/transforms.py -,
-then ``image_transform`` (``ToTensor`` + ImageNet ``Normalize``), ``utils.mask_valid_area`` and ``get_ground_truth``.
+then the image transform, ``utils.mask_valid_area`` and ``get_ground_truth``.  The image transform is ``image_transform``
+(``ToTensor`` + ImageNet ``Normalize``) by default and, with ``color``, the one the training script passes
+(train_VGG19.py:55,70): ``image_transform_train`` (transforms.py:53-65) = ``ColorJitter(0.1, 0.1, 0.1, 0.1)``,
+``RandomApply([jpeg], p=0.1)``, ``RandomGrayscale(p=0.01)``, ``ToTensor``, ``Normalize``.
 
-The split: the random draws (``draw_params``, torch's global generator in the reference's order) and the annotation
-bookkeeping (``transform_annotations``, numpy in the reference's dtypes) are host work of a few microseconds per image;
-the pixels - a PIL bicubic resize per image in the reference - are one table launch and one fused launch per batch
-(``augment_images``), and the targets are ``encode.encode_targets``.  ``train_batch`` is the whole item pipeline for a
-batch.  The image is the reference's bits (Pillow's two integer passes restated on the device), the keypoints are its
-bits including their dtype (float32 until a flip makes them float64), the targets follow encode.py's contract.
+The split: the random draws (``draw_params``, ``draw_color_params``, ``draw_train_params``: torch's global generator in
+the reference's order) and the annotation bookkeeping (``transform_annotations``, numpy in the reference's dtypes) are
+host work of a few microseconds per image; the pixels - a PIL bicubic resize and four PIL enhancement passes per image
+in the reference - are launches per batch (``augment_images``, ``color_jitter``), and the targets are
+``encode.encode_targets``.  ``train_batch`` is the whole item pipeline for a batch.  The image is the reference's bits
+(Pillow's two integer resample passes, its ImageEnhance / blend / convert('L' / 'HSV' / 'RGB') arithmetic restated on the
+device), the keypoints are its bits including their dtype (float32 until a flip makes them float64), the targets follow
+encode.py's contract.
 
-Out of scope: ``image_transform_train``'s ``ColorJitter``, JPEG re-compression and ``RandomGrayscale`` (random and
-photometric, torchvision); ``RandomRotate`` (cv2 ``warpAffine``; not in the training script's chain);
-``RescaleAbsolute`` / ``MultiScale``; image decoding; the DataLoader.
+Not pinned: torchvision is not installed where this was written and the reference pins no version of it, so the order
+of ColorJitter's and RandomGrayscale's draws is restated from torchvision 0.9 and later (``draw_color_params``), as
+``ToTensor`` was.  Not built: the JPEG re-compression of ``RandomApply([jpeg], p=0.1)`` - its draw is consumed, so the
+generator stays in step with the reference, and recorded as ``jpeg``, but the device path does not apply it.
+
+Out of scope: JPEG re-compression; ``RandomRotate`` (cv2 ``warpAffine``; not in the training script's chain);
+``RescaleAbsolute`` / ``MultiScale``; image decoding; the DataLoader.  (``ColorJitter`` and ``RandomGrayscale`` were out
+of scope until the colour jitter of header section 4d.)
 """
 import copy
 import ctypes as C
@@ -59,6 +70,55 @@ def draw_params(sizes, square_edge=368, scale_range=(0.5, 1.0), hflip_p=0.5):
         out.append(dict(hflip=bool(hflip), factor=factor, hr=hr, wr=wr, crop_x=int(crop_x), crop_y=int(crop_y),
                         square_edge=edge))
     return out
+
+
+def hue_shift_of(hue_factor):
+    """What torchvision's adjust_hue adds to the uint8 H plane of a PIL image: ``np.uint8(hue_factor * 255)``, i.e.
+    int(hue_factor * 255) truncated toward zero, modulo 256 (-12.75 -> -12 -> 244)."""
+    return int(hue_factor * 255) % 256
+
+
+def _uniform(lo, hi):
+    return float(torch.empty(1).uniform_(lo, hi))
+
+
+def _draw_color_one(brightness, contrast, saturation, hue, jpeg_p, gray_p):
+    fn_idx = [int(v) for v in torch.randperm(4)]
+    b = _uniform(max(0.0, 1 - brightness), 1 + brightness) if brightness else None
+    c = _uniform(max(0.0, 1 - contrast), 1 + contrast) if contrast else None
+    s = _uniform(max(0.0, 1 - saturation), 1 + saturation) if saturation else None
+    h = _uniform(-hue, hue) if hue else None
+    jpeg = not jpeg_p < float(torch.rand(1))
+    gray = float(torch.rand(1)) < gray_p
+    present = (b is not None, c is not None, s is not None, h is not None)
+    order = [op if present[op] else -1 for op in fn_idx]
+    return dict(order=order, brightness=b, contrast=c, saturation=s, hue=h,
+                hue_shift=hue_shift_of(h) if h is not None else 0, jpeg=bool(jpeg), gray=bool(gray))
+
+
+def draw_color_params(n, brightness=0.1, contrast=0.1, saturation=0.1, hue=0.1, jpeg_p=0.1, gray_p=0.01):
+    """The draws of ``image_transform_train`` (transforms.py:53-65) for ``n`` images one after another, from torch's
+    global generator.  Per image, in the order of torchvision 0.9 and later (``ColorJitter.get_params``, then
+    ``RandomApply.forward``, then ``RandomGrayscale.forward``): ``torch.randperm(4)`` (the order of the four operations:
+    0 brightness, 1 contrast, 2 saturation, 3 hue); ``float(torch.empty(1).uniform_(lo, hi))`` for brightness, contrast
+    and saturation over (max(0, 1 - x), 1 + x) each and for hue over (-x, x), an operation whose x is 0 drawing nothing
+    and dropping out (order entry -1); ``torch.rand(1)`` for RandomApply - the JPEG step fires unless ``p < draw``;
+    ``torch.rand(1)`` for RandomGrayscale - fires if ``draw < p``.
+    torchvision is not installed where this was written and the reference pins no version of it: this order is restated
+    from its source, not checked against it.  The JPEG draw is consumed and recorded, the re-compression is not built.
+    -> a list of dicts: order, brightness, contrast, saturation, hue (python floats or None), hue_shift, jpeg, gray."""
+    return [_draw_color_one(brightness, contrast, saturation, hue, jpeg_p, gray_p) for _ in range(n)]
+
+
+def draw_train_params(sizes, square_edge=368, scale_range=(0.5, 1.0), hflip_p=0.5, **color):
+    """The draws of whole items as ``CocoKeypoints.__getitem__`` makes them (datasets.py:180, :198): for image k the
+    geometry (``draw_params``' draws), then its colour (``draw_color_params``' draws, ``color`` its keywords), then image
+    k + 1.  -> (params, cparams)."""
+    params, cparams = [], []
+    for size in sizes:
+        params += draw_params([size], square_edge, scale_range, hflip_p)
+        cparams += draw_color_params(1, **color)
+    return params, cparams
 
 
 def _horizontal_swap_coco(keypoints):
@@ -160,14 +220,95 @@ def augment_enqueue(descs, count, cfg, dst, layout, workspace):
           "rtpose_augment_batch")
 
 
-def augment_images(images, params, out=None, norm=1, mask_valid=True, device=None, slots=None):
+def jitter_enqueue(descs, count, cfg, src, dst, layout, workspace):
+    """Enqueue rtpose_jitter_batch on the current stream: descs a (_capi.JitterImage * count) array, src a dense device
+    tensor, dst a device address or tensor, layout a _capi.Layout or None (cfg.nchw == 1), workspace a device tensor of
+    rtpose_jitter_workspace_bytes."""
+    check(lib.rtpose_jitter_batch(descs, count, C.byref(cfg), ptr(src), dst if isinstance(dst, C.c_void_p) else ptr(dst),
+                                  C.byref(layout) if layout is not None else None, ptr(workspace),
+                                  workspace.numel() * workspace.element_size(), current_stream()),
+          "rtpose_jitter_batch")
+
+
+def color_jitter(canvas, cparams, masks=None, norm=1, out=None, slots=None):
+    """ColorJitter and RandomGrayscale on the device, then ToTensor + Normalize and the mask (header section 4d).
+    ``canvas``: a dense fp32 [N, 3, h, w] device tensor holding the integers 0..255 (what augment_images makes with
+    ``norm=0, mask_valid=False``); ``cparams``: what draw_color_params returned for its N images (order, brightness,
+    contrast, saturation, hue_shift, gray; ``jpeg`` is not applied: the JPEG re-compression is not built); ``masks``: per
+    image (x0, y0, x1, y1), None = the whole canvas.  ``out=None`` -> a new [N, 3, h, w] tensor; ``out=canvas`` works in
+    place; another dense [>= N, 3, h, w] tensor or a native plan of [>= N, h, w] takes image k in slot slots[k]
+    (default k).  ``norm=1`` normalises, 0 keeps float(u).  Bit for bit what Pillow computes for the same operations
+    (ImageEnhance.Brightness / Contrast / Color, convert('HSV') / convert('RGB') around the hue shift, convert('L')).
+    Two launches per 32 images - one if none of them has contrast -, on the current stream.  -> the result."""
+    if not hasattr(canvas, "data_ptr") or canvas.dim() != 4 or canvas.shape[1] != 3 or canvas.dtype != torch.float32 \
+            or not canvas.is_contiguous():
+        raise ValueError("canvas must be a contiguous fp32 [N, 3, h, w] tensor")
+    if canvas.device.type != 'cuda':
+        raise _capi.RtposeError("color_jitter runs on an MI355X (HIP) device only (no CPU fallback); got %s" % canvas.device)
+    n, _, h, w = (int(v) for v in canvas.shape)
+    if len(cparams) != n:
+        raise ValueError("%d canvases for %d colour params" % (n, len(cparams)))
+    if masks is not None and len(masks) != n:
+        raise ValueError("%d canvases for %d masks" % (n, len(masks)))
+    if slots is not None and len(slots) != n:
+        raise ValueError("%d canvases for %d slots" % (n, len(slots)))
+    with torch.cuda.device(canvas.device):
+        descs = (_capi.JitterImage * max(n, 1))()
+        for k, cp in enumerate(cparams):
+            d = descs[k]
+            for j in range(4):
+                d.order[j] = cp["order"][j]
+            for j, name in enumerate(("brightness", "contrast", "saturation")):
+                d.factor[j] = cp[name] if cp.get(name) is not None else 1.0
+            d.hue_shift, d.gray = int(cp.get("hue_shift", 0)), int(bool(cp.get("gray")))
+            mask = masks[k] if masks is not None else (0, 0, w, h)
+            for j in range(4):
+                d.mask[j] = mask[j]
+            d.n_src, d.n_dst = k, (slots[k] if slots is not None else k)
+        if out is None or hasattr(out, "data_ptr"):
+            cfg = _capi.JitterCfg.make(h, w, int(norm), 1)
+            if out is None:
+                out = torch.empty_like(canvas)
+            if out.dim() != 4 or tuple(out.shape[1:]) != (3, h, w) or out.dtype != torch.float32 or not out.is_contiguous() \
+                    or out.device != canvas.device:
+                raise ValueError("out must be a contiguous fp32 [>= N, 3, %d, %d] tensor on the canvas's device" % (h, w))
+            for k in range(n):
+                if not 0 <= descs[k].n_dst < out.shape[0]:
+                    raise _capi.RtposeError("image slot %d outside the %d-image result" % (descs[k].n_dst, out.shape[0]))
+            base, lay = ptr(out), None
+        else:
+            cfg = _capi.JitterCfg.make(h, w, int(norm), 0)
+            base, lay = C.c_void_p(), _capi.Layout()
+            check(lib.rtpose_net_input_view(out.handle, C.byref(base), C.byref(lay)), "rtpose_net_input_view")
+            pn, ph, pw = out.shape
+            if (ph, pw) != (h, w):
+                raise _capi.RtposeError("a %d x %d plan for a %d x %d canvas" % (ph, pw, h, w))
+            for k in range(n):
+                if not 0 <= descs[k].n_dst < pn:
+                    raise _capi.RtposeError("image slot %d outside the %d-image plan" % (descs[k].n_dst, pn))
+        if n == 0:
+            return out
+        wb = lib.rtpose_jitter_workspace_bytes(C.byref(cfg), n)
+        if wb == 0:
+            raise _capi.RtposeError("bad jitter arguments: " + _capi.last_error())
+        workspace = torch.empty(wb // 4, dtype=torch.int32, device=canvas.device)
+        jitter_enqueue(descs, n, cfg, canvas, base, lay, workspace)
+        del workspace     # as in augment_images: handed out again only to work queued behind the launches
+    return out
+
+
+def augment_images(images, params, out=None, norm=1, mask_valid=True, device=None, slots=None, color=None):
     """The image side for a batch: ``images`` a list of uint8 RGB [h0, w0, 3] numpy arrays or device tensors of any
     sizes, ``params`` what draw_params returned for their sizes.  -> an [N, 3, S, S] fp32 device tensor (S the
     square_edge of the params): flipped, resized (Pillow's bicubic, bit for bit), cropped, centre-padded with
     (124, 116, 104), ToTensor + ImageNet Normalize (``norm=1``; 0 keeps float(u) in 0..255) and, with ``mask_valid``,
     zero outside the valid area (utils.mask_valid_area).  With ``out=plan`` (a native plan of [>= N, S, S]) the images
     go into the plan's own input view instead, image k into slot slots[k] (default k), as preprocess_into_plan does,
-    and the plan is returned.  One table launch and one fused launch per 32 images, on the current stream."""
+    and the plan is returned.  One table launch and one fused launch per 32 images, on the current stream.
+    ``color``: what draw_color_params returned for the images; then the geometry launches write the uint8 canvas
+    (norm 0, no mask) into a tensor of their own and color_jitter's launches make the result from it with the real
+    ``norm`` and mask (ColorJitter and RandomGrayscale of image_transform_train; its JPEG step is not built).  The
+    default, None, gives the launches and the bits of a call without the keyword."""
     if len(images) != len(params):
         raise ValueError("%d images for %d params" % (len(images), len(params)))
     n = len(images)
@@ -182,6 +323,20 @@ def augment_images(images, params, out=None, norm=1, mask_valid=True, device=Non
     device = torch.device(device)
     if device.type != 'cuda':
         raise _capi.RtposeError("augment_images runs on an MI355X (HIP) device only (no CPU fallback); got %s" % device)
+    if color is not None:
+        if len(color) != n:
+            raise ValueError("%d images for %d colour params" % (n, len(color)))
+        masks = [transform_annotations([], _size_of(im), p)[3] if mask_valid else (0, 0, edge, edge)
+                 for im, p in zip(images, params)]
+        with torch.cuda.device(device):
+            canvas = augment_images(images, params, norm=0, mask_valid=False, device=device)
+            if out is None and slots is None:
+                return color_jitter(canvas, color, masks, norm, out=canvas)
+            if out is None:
+                if n and not all(0 <= s < n for s in slots):
+                    raise _capi.RtposeError("image slots %s outside the %d-image result" % (list(slots), n))
+                out = torch.empty_like(canvas)
+            return color_jitter(canvas, color, masks, norm, out=out, slots=slots)
     with torch.cuda.device(device):
         held = []
         descs = (_capi.AugmentImage * max(n, 1))()
@@ -229,17 +384,29 @@ def augment_images(images, params, out=None, norm=1, mask_valid=True, device=Non
     return result
 
 
-def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, stride=8, sigma=7.0, device=None):
+def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, stride=8, sigma=7.0, device=None,
+                color=False):
     """-> (image [N, 3, S, S], heat [N, C_h, S / stride, S / stride], paf [N, C_p, ...], metas): the tuple
     collate_images_targets_meta makes of CocoKeypoints items (datasets.py:86-92, :193-214), as fp32 device tensors,
     plus the per-image meta dicts (with 'keypoints': the augmented [K, 17, 3] annotations in the reference's dtype, and
     'bboxes').  ``images``: uint8 RGB arrays or device tensors; ``annotations``: per image a list of COCO annotation
     dicts ('keypoints', 'bbox'); ``params=None`` draws them (draw_params on torch's global generator).  The targets come
     from the augmented keypoints through add_neck in their own dtype, remove_illegal_joint and encode_targets, as
-    get_ground_truth does (datasets.py:259-274)."""
+    get_ground_truth does (datasets.py:259-274).
+    ``color``: False - the image is ``image_transform``'s, as before the keyword; True - ``image_transform_train``'s
+    ColorJitter and RandomGrayscale are applied to the canvas before normalisation (its JPEG step is not built), drawn
+    with the geometry in the reference's order where ``params`` is None (draw_train_params), else on their own
+    (draw_color_params); or a list of colour params.  The metas then carry 'color' (the params) and 'jpeg' (whether the
+    reference would have re-compressed this image)."""
     if len(images) != len(annotations):
         raise ValueError("%d images for %d annotation lists" % (len(images), len(annotations)))
     sizes = [_size_of(im) for im in images]
+    cparams = None if color is False or color is None else color
+    if cparams is True:
+        if params is None:
+            params, cparams = draw_train_params(sizes)
+        else:
+            cparams = draw_color_params(len(sizes))
     if params is None:
         params = draw_params(sizes)
     edge = params[0]["square_edge"] if params else 368
@@ -253,6 +420,11 @@ def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, 
         meta = copy.deepcopy(meta)
         meta["keypoints"], meta["bboxes"] = kps, boxes
         metas.append(meta)
-    image = augment_images(images, params, device=device)
+    if cparams is not None:
+        for meta, cp in zip(metas, cparams):
+            meta["color"], meta["jpeg"] = copy.deepcopy(cp), bool(cp.get("jpeg"))
+        image = augment_images(images, params, device=device, color=cparams)
+    else:
+        image = augment_images(images, params, device=device)
     heat, paf = encode.encode_targets(people, skeleton, (edge, edge), stride, sigma, device=image.device)
     return image, heat, paf, metas
