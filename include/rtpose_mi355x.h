@@ -1338,13 +1338,16 @@ int rtpose_augment_batch(const rtpose_augment_image* images, int count, const rt
                          void* stream);
 
 /* ---- 4d. Colour jitter of the padded canvas: ColorJitter, RandomGrayscale, normalise, mask ----
- * stands in for image_transform_train of lib/datasets/transforms.py:53-65 without its JPEG step:
+ * stands in for image_transform_train of lib/datasets/transforms.py:53-65 but for its JPEG step, which
+ * is section 4e:
  * torchvision's ColorJitter and RandomGrayscale on the 8-bit RGB PIL image CenterPad left (the canvas,
  * fill included), then ToTensor + ImageNet Normalize and utils.mask_valid_area.  On a PIL image every
  * one of these operations is integer, fp32 or fp64 arithmetic inside Pillow (ImageEnhance, Image.blend,
  * convert('L' / 'HSV' / 'RGB')); it is restated here operation for operation.  The random draws are
  * host work (augment.py); the caller passes their results per image.  JPEG re-compression
- * (RandomApply([jpeg], p=0.1)) is not built.
+ * (RandomApply([jpeg], p=0.1)) sits between ColorJitter and RandomGrayscale and is not pointwise: it is
+ * rtpose_jpeg_roundtrip_batch of section 4e, between one call here with gray = 0, norm = 0 and a
+ * whole-canvas mask and a second one with an empty order (augment.py: color_jitter(jpeg=True)).
  *
  * `src` is dense fp32 [N][3][h][w] holding the integers 0..255 - what rtpose_augment_batch writes with
  * norm == 0, nchw == 1 and a whole-canvas mask.  A value v is read as u = (int)v clamped to 0..255,
@@ -1414,6 +1417,76 @@ size_t rtpose_jitter_workspace_bytes(const rtpose_jitter_cfg* cfg, int count);
 int rtpose_jitter_batch(const rtpose_jitter_image* images, int count, const rtpose_jitter_cfg* cfg,
                         const float* src, float* dst, const rtpose_layout* ldst, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ---- 4e. JPEG re-compression of the padded canvas: save at a quality, re-open ----
+ * stands in for RandomApply([jpeg_compression_augmentation], p=0.1) of lib/datasets/transforms.py:28-31,
+ * 58-61: Image.save(f, 'jpeg', quality=q) and Image.open(f) on the 8-bit RGB canvas, the step of
+ * image_transform_train between ColorJitter and RandomGrayscale.  Huffman coding is lossless: the
+ * pixels that come back depend only on integer arithmetic, restated here from libjpeg-turbo (default
+ * 4:2:0 sampling, JDCT_ISLOW, fancy up-sampling) - a Pillow built on another libjpeg may give other
+ * bits.  `>>` is an arithmetic shift, D(x, n) = (x + (1 << (n - 1))) >> n.
+ *
+ * `src` and `dst` are dense fp32 [N][3][h][w] holding the integers 0..255 (a source value is read as in
+ * 4d); image i is read from slot n_src and written to slot n_dst.  Per image:
+ *   RGB -> YCbCr:  Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *                  Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *                  Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   edges: the last column of the full-resolution planes repeats out to the MCU width (a multiple of
+ *     16); the last row repeats once if h is odd; chroma is down-sampled; then each plane's own last
+ *     row repeats to the MCU height (for chroma that is not the average of Y's repeated rows).
+ *   chroma down-sampling: (a + b + c + d + bias) >> 2 over each 2 x 2 cell, bias 1 at even output
+ *     columns and 2 at odd ones.
+ *   quantiser tables: the luminance and chrominance tables of the JPEG specification's Annex K, scaled
+ *     by s = 5000 / quality (integer) below quality 50, else 200 - 2 * quality: an entry is
+ *     (base * s + 50) / 100 clamped to 1..255.
+ *   forward DCT (jfdctint) on sample - 128 per 8 x 8 block, rows then columns, constants at 13 bits
+ *     (2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172): row pass outputs 0 and 4
+ *     << 2, the others D(.., 11); column pass outputs 0 and 4 D(.., 2), the others D(.., 15).
+ *   quantise and de-quantise: a = (|c| + (Q * 8 >> 1)) / (Q * 8), the sign restored, times Q.
+ *   inverse DCT (jidctint): columns with D(.., 11), the even part from (in0 +- in4) << 13; rows with
+ *     D(.., 18); then the range-limit table as a function of that x: with i = x & 1023, i + 128 for
+ *     i < 128, 255 for i < 512, 0 for i < 896, else i - 896 (x + 128 clamped to 0..255 for x in
+ *     [-512, 511], a wrap beyond).
+ *   up-sampling, on the real chroma plane of ceil(h / 2) x ceil(w / 2) samples (h2v2_fancy_upsample):
+ *     vertically s = 3 * near + far, far the row above for even output rows and the row below for odd
+ *     ones; horizontally (3 s[x] + s[x - 1] + 8) >> 4 at even output columns and
+ *     (3 s[x] + s[x + 1] + 7) >> 4 at odd ones; a neighbour outside the real plane is the sample
+ *     itself.  Where that plane is at most 2 samples wide (w <= 4) libjpeg replicates each chroma sample
+ *     over its 2 x 2 cell instead (h2v2_upsample), and so does this: every w from 1 is served.
+ *   YCbCr -> RGB with cb = Cb - 128, cr = Cr - 128: R = Y + ((91881 cr + 32768) >> 16),
+ *     G = Y + ((-22554 cb + 32768 - 46802 cr) >> 16), B = Y + ((116130 cb + 32768) >> 16), each
+ *     clamped to 0..255 and stored as float(u).
+ *
+ * Launches, per chunk of 32 images (they and the two tables travel by value as kernel arguments; the
+ * library allocates and copies nothing): the codec pass, a block per run of 4 MCUs, stores the decoder's
+ * 8-bit Y (h rows of w rounded up to 8 bytes), Cb and Cr (ceil(h / 2) rows of ceil(w / 2) rounded up to
+ * 8 bytes) planes of image i at workspace + i * (those three sizes); the up-sample pass reads them - the
+ * chroma filter reaches across MCU borders - and writes dst.  Every codec launch of a call precedes its
+ * first up-sample launch on the stream, so all images are read before any is written: dst == src is
+ * allowed where every image has n_dst == n_src (in place).  No atomics, no order to keep: an image gives
+ * the same bits alone and inside any batch. */
+typedef struct rtpose_jpeg_image {
+  int32_t n_src, n_dst; /* source and destination slots                                               */
+} rtpose_jpeg_image;
+
+typedef struct rtpose_jpeg_cfg {
+  uint32_t struct_bytes; /* sizeof(rtpose_jpeg_cfg)                                                   */
+  int32_t h, w;          /* the canvas                                                                */
+  int32_t quality;       /* 1..100, libjpeg's scale; the reference saves at 50                        */
+} rtpose_jpeg_cfg;
+
+/* Bytes of the caller-provided device workspace (the decoded planes) for `count` images; 0 on a bad cfg
+ * or a negative count. */
+size_t rtpose_jpeg_workspace_bytes(const rtpose_jpeg_cfg* cfg, int count);
+/* Refused before any launch, the message naming the argument and for an image its index: NULL pointers;
+ * a wrong struct_bytes; quality outside [1, 100]; h or w outside [1, 65535]; a negative count; a
+ * workspace not aligned to 8 bytes; n_src or n_dst outside [0, 65535]; an n_dst that appears twice;
+ * dst == src with an image whose n_dst != n_src; dst != src with the span of images written
+ * overlapping the span of images read in memory (two views of one tensor: stricter than the launch
+ * order needs, and cheap to tell); a workspace smaller than the query reports.  count == 0 is a no-op. */
+int rtpose_jpeg_roundtrip_batch(const rtpose_jpeg_image* images, int count, const rtpose_jpeg_cfg* cfg,
+                                const float* src, float* dst, void* workspace, size_t workspace_bytes,
+                                void* stream);
 
 /* ------------------------------------------------------------------------
  * 5. Flip test-time-augmentation merge

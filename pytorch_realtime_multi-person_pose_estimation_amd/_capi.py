@@ -182,6 +182,20 @@ class JitterCfg(C.Structure):
         return cls(C.sizeof(cls), h, w, norm, nchw)
 
 
+class JpegImage(C.Structure):
+    """rtpose_jpeg_image: one image of a rtpose_jpeg_roundtrip_batch call (header section 4e)."""
+    _fields_ = [("n_src", C.c_int32), ("n_dst", C.c_int32)]
+
+
+class JpegCfg(C.Structure):
+    """rtpose_jpeg_cfg: canvas and quality of rtpose_jpeg_roundtrip_batch (header section 4e)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("h", C.c_int32), ("w", C.c_int32), ("quality", C.c_int32)]
+
+    @classmethod
+    def make(cls, h, w, quality=50):
+        return cls(C.sizeof(cls), h, w, quality)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -366,6 +380,8 @@ _SIGS = {
     "rtpose_augment_batch": (_i, [C.POINTER(AugmentImage), _i, C.POINTER(AugmentCfg), _vp, _LP, _vp, _sz, _vp]),
     "rtpose_jitter_workspace_bytes": (_sz, [C.POINTER(JitterCfg), _i]),
     "rtpose_jitter_batch": (_i, [C.POINTER(JitterImage), _i, C.POINTER(JitterCfg), _vp, _vp, _LP, _vp, _sz, _vp]),
+    "rtpose_jpeg_workspace_bytes": (_sz, [C.POINTER(JpegCfg), _i]),
+    "rtpose_jpeg_roundtrip_batch": (_i, [C.POINTER(JpegImage), _i, C.POINTER(JpegCfg), _vp, _vp, _vp, _sz, _vp]),
     "rtpose_preprocess_u8_batch": (_i, [C.POINTER(PrepImage), _i, _i, _vp, _LP, _i, _i, _vp]),
     "rtpose_preprocess_u8": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_preprocess_u8_flip": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _i, _vp]),

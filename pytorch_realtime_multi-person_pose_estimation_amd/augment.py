@@ -1,5 +1,5 @@
-"""Training batches augmented on the device: flip, rescale, crop, pad, colour jitter, normalise, mask
-(csrc/augment.hip, header 4c; csrc/colorjitter.hip, header 4d).
+"""Training batches augmented on the device: flip, rescale, crop, pad, colour jitter, JPEG re-compression, normalise,
+mask (csrc/augment.hip, header 4c; csrc/colorjitter.hip, header 4d; csrc/jpeg_roundtrip.hip, header 4e).
 
 What ``CocoKeypoints.__getitem__`` of the reference does before it yields ``(image, heatmaps, pafs)``
 (lib/datasets/datasets.py:156-214): the preprocess chain of train/train_VGG19.py:124-130 - ``Normalize``,
@@ -12,20 +12,25 @@ then the image transform, ``utils.mask_valid_area`` and ``get_ground_truth``.  T
 The split: the random draws (``draw_params``, ``draw_color_params``, ``draw_train_params``: torch's global generator in
 the reference's order) and the annotation bookkeeping (``transform_annotations``, numpy in the reference's dtypes) are
 host work of a few microseconds per image; the pixels - a PIL bicubic resize and four PIL enhancement passes per image
-in the reference - are launches per batch (``augment_images``, ``color_jitter``), and the targets are
-``encode.encode_targets``.  ``train_batch`` is the whole item pipeline for a batch.  The image is the reference's bits
-(Pillow's two integer resample passes, its ImageEnhance / blend / convert('L' / 'HSV' / 'RGB') arithmetic restated on the
-device), the keypoints are its bits including their dtype (float32 until a flip makes them float64), the targets follow
-encode.py's contract.
+in the reference - are launches per batch (``augment_images``, ``color_jitter``, ``jpeg_roundtrip``), and the targets
+are ``encode.encode_targets``.  ``train_batch`` is the whole item pipeline for a batch.  The image is the reference's bits
+(Pillow's two integer resample passes, its ImageEnhance / blend / convert('L' / 'HSV' / 'RGB') arithmetic and
+libjpeg-turbo's integer codec chain restated on the device), the keypoints are its bits including their dtype (float32
+until a flip makes them float64), the targets follow encode.py's contract.
 
 Not pinned: torchvision is not installed where this was written and the reference pins no version of it, so the order
 of ColorJitter's and RandomGrayscale's draws is restated from torchvision 0.9 and later (``draw_color_params``), as
-``ToTensor`` was.  Not built: the JPEG re-compression of ``RandomApply([jpeg], p=0.1)`` - its draw is consumed, so the
-generator stays in step with the reference, and recorded as ``jpeg``, but the device path does not apply it.
+``ToTensor`` was.
 
-Out of scope: JPEG re-compression; ``RandomRotate`` (cv2 ``warpAffine``; not in the training script's chain);
-``RescaleAbsolute`` / ``MultiScale``; image decoding; the DataLoader.  (``ColorJitter`` and ``RandomGrayscale`` were out
-of scope until the colour jitter of header section 4d.)
+Opt-in: the JPEG re-compression of ``RandomApply([jpeg], p=0.1)`` (save at quality 50, re-open).  Its draw is always
+consumed, so the generator stays in step with the reference, and recorded as ``jpeg``; the pixels take the round trip
+only with ``jpeg=True`` (``color_jitter``, ``augment_images``, ``train_batch``), through the kernels of header section
+4e, in libjpeg-turbo's bits.  Without the keyword the launches and the bits are those of the releases in which the step
+was not built.
+
+Out of scope: ``RandomRotate`` (cv2 ``warpAffine``; not in the training script's chain); ``RescaleAbsolute`` /
+``MultiScale``; image decoding; the DataLoader.  (``ColorJitter`` and ``RandomGrayscale`` were out of scope until the
+colour jitter of header section 4d, JPEG re-compression until section 4e.)
 """
 import copy
 import ctypes as C
@@ -105,7 +110,8 @@ def draw_color_params(n, brightness=0.1, contrast=0.1, saturation=0.1, hue=0.1, 
     and dropping out (order entry -1); ``torch.rand(1)`` for RandomApply - the JPEG step fires unless ``p < draw``;
     ``torch.rand(1)`` for RandomGrayscale - fires if ``draw < p``.
     torchvision is not installed where this was written and the reference pins no version of it: this order is restated
-    from its source, not checked against it.  The JPEG draw is consumed and recorded, the re-compression is not built.
+    from its source, not checked against it.  The JPEG draw is consumed and recorded here whatever happens to the pixels:
+    the re-compression itself, not built before header section 4e, is ``jpeg=True`` of color_jitter.
     -> a list of dicts: order, brightness, contrast, saturation, hue (python floats or None), hue_shift, jpeg, gray."""
     return [_draw_color_one(brightness, contrast, saturation, hue, jpeg_p, gray_p) for _ in range(n)]
 
@@ -230,22 +236,81 @@ def jitter_enqueue(descs, count, cfg, src, dst, layout, workspace):
           "rtpose_jitter_batch")
 
 
-def color_jitter(canvas, cparams, masks=None, norm=1, out=None, slots=None):
-    """ColorJitter and RandomGrayscale on the device, then ToTensor + Normalize and the mask (header section 4d).
-    ``canvas``: a dense fp32 [N, 3, h, w] device tensor holding the integers 0..255 (what augment_images makes with
-    ``norm=0, mask_valid=False``); ``cparams``: what draw_color_params returned for its N images (order, brightness,
-    contrast, saturation, hue_shift, gray; ``jpeg`` is not applied: the JPEG re-compression is not built); ``masks``: per
-    image (x0, y0, x1, y1), None = the whole canvas.  ``out=None`` -> a new [N, 3, h, w] tensor; ``out=canvas`` works in
-    place; another dense [>= N, 3, h, w] tensor or a native plan of [>= N, h, w] takes image k in slot slots[k]
-    (default k).  ``norm=1`` normalises, 0 keeps float(u).  Bit for bit what Pillow computes for the same operations
-    (ImageEnhance.Brightness / Contrast / Color, convert('HSV') / convert('RGB') around the hue shift, convert('L')).
-    Two launches per 32 images - one if none of them has contrast -, on the current stream.  -> the result."""
+def jpeg_enqueue(descs, count, cfg, src, dst, workspace):
+    """Enqueue rtpose_jpeg_roundtrip_batch on the current stream: descs a (_capi.JpegImage * count) array, src and dst
+    dense device tensors (or addresses; the same one for in place), workspace a device tensor of
+    rtpose_jpeg_workspace_bytes."""
+    check(lib.rtpose_jpeg_roundtrip_batch(descs, count, C.byref(cfg), src if isinstance(src, C.c_void_p) else ptr(src),
+                                          dst if isinstance(dst, C.c_void_p) else ptr(dst), ptr(workspace),
+                                          workspace.numel() * workspace.element_size(), current_stream()),
+          "rtpose_jpeg_roundtrip_batch")
+
+
+def _dense_canvas(canvas, who):
     if not hasattr(canvas, "data_ptr") or canvas.dim() != 4 or canvas.shape[1] != 3 or canvas.dtype != torch.float32 \
             or not canvas.is_contiguous():
         raise ValueError("canvas must be a contiguous fp32 [N, 3, h, w] tensor")
     if canvas.device.type != 'cuda':
-        raise _capi.RtposeError("color_jitter runs on an MI355X (HIP) device only (no CPU fallback); got %s" % canvas.device)
-    n, _, h, w = (int(v) for v in canvas.shape)
+        raise _capi.RtposeError("%s runs on an MI355X (HIP) device only (no CPU fallback); got %s" % (who, canvas.device))
+    return (int(v) for v in canvas.shape)
+
+
+def jpeg_roundtrip(canvas, which=None, quality=50, out=None, slots=None):
+    """Saving as a JPEG at ``quality`` and re-opening, on the device (header section 4e): what
+    ``jpeg_compression_augmentation`` of the reference (transforms.py:28-31) does to the pixels, in libjpeg-turbo's bits.
+    ``canvas``: a dense fp32 [N, 3, h, w] device tensor holding the integers 0..255; ``which``: the indices of the images
+    that take the round trip (default all; each at most once).  ``out=None`` -> a copy of the canvas with those images
+    replaced; ``out=canvas`` works in place; another dense [M, 3, h, w] tensor takes listed image which[j] in slot
+    slots[j] (default which[j]) and keeps its other slots as they are.  Two launches per 32 listed images, on the current
+    stream.  -> the result."""
+    n, _, h, w = _dense_canvas(canvas, "jpeg_roundtrip")
+    which = list(range(n)) if which is None else [int(k) for k in which]
+    if not all(0 <= k < n for k in which):
+        raise ValueError("which %s outside the %d canvases" % (which, n))
+    if slots is not None and len(slots) != len(which):
+        raise ValueError("%d listed images for %d slots" % (len(which), len(slots)))
+    if out is None:
+        out = canvas.clone()
+    if not hasattr(out, "data_ptr") or out.dim() != 4 or tuple(out.shape[1:]) != (3, h, w) or out.dtype != torch.float32 \
+            or not out.is_contiguous() or out.device != canvas.device:
+        raise ValueError("out must be a contiguous fp32 [M, 3, %d, %d] tensor on the canvas's device" % (h, w))
+    count = len(which)
+    descs = (_capi.JpegImage * max(count, 1))()
+    for j, k in enumerate(which):
+        descs[j].n_src, descs[j].n_dst = k, (int(slots[j]) if slots is not None else k)
+        if not 0 <= descs[j].n_dst < out.shape[0]:
+            raise _capi.RtposeError("image slot %d outside the %d-image result" % (descs[j].n_dst, out.shape[0]))
+    if count == 0:
+        return out
+    with torch.cuda.device(canvas.device):
+        cfg = _capi.JpegCfg.make(h, w, int(quality))
+        wb = lib.rtpose_jpeg_workspace_bytes(C.byref(cfg), count)
+        if wb == 0:
+            raise _capi.RtposeError("bad jpeg arguments: " + _capi.last_error())
+        workspace = torch.empty(wb // 8, dtype=torch.int64, device=canvas.device)
+        jpeg_enqueue(descs, count, cfg, canvas, out, workspace)
+        del workspace     # as in augment_images: handed out again only to work queued behind the launches
+    return out
+
+
+def color_jitter(canvas, cparams, masks=None, norm=1, out=None, slots=None, jpeg=False):
+    """ColorJitter and RandomGrayscale on the device, then ToTensor + Normalize and the mask (header section 4d).
+    ``canvas``: a dense fp32 [N, 3, h, w] device tensor holding the integers 0..255 (what augment_images makes with
+    ``norm=0, mask_valid=False``); ``cparams``: what draw_color_params returned for its N images (order, brightness,
+    contrast, saturation, hue_shift, gray, jpeg); ``masks``: per
+    image (x0, y0, x1, y1), None = the whole canvas.  ``out=None`` -> a new [N, 3, h, w] tensor; ``out=canvas`` works in
+    place; another dense [>= N, 3, h, w] tensor or a native plan of [>= N, h, w] takes image k in slot slots[k]
+    (default k).  ``norm=1`` normalises, 0 keeps float(u).  Bit for bit what Pillow computes for the same operations
+    (ImageEnhance.Brightness / Contrast / Color, convert('HSV') / convert('RGB') around the hue shift, convert('L')).
+    Two launches per 32 images - one if none of them has contrast -, on the current stream.
+    ``jpeg``: False, the default - an image's ``jpeg`` entry is not applied, the launches and the bits are those of the
+    releases where the JPEG re-compression was not built.  True - the images whose entry is true (the reference's
+    RandomApply fired) take image_transform_train's middle step where the reference takes it, between ColorJitter and
+    RandomGrayscale: their ColorJitter operations alone into an 8-bit canvas of their own (rtpose_jitter_batch with
+    gray 0, norm 0, the whole canvas), rtpose_jpeg_roundtrip_batch on it in place at quality 50 (header section 4e),
+    then rtpose_jitter_batch with an empty order and the real gray, norm, mask and destination; the other images go
+    through one rtpose_jitter_batch call exactly as without the keyword.  -> the result."""
+    n, _, h, w = _dense_canvas(canvas, "color_jitter")
     if len(cparams) != n:
         raise ValueError("%d canvases for %d colour params" % (n, len(cparams)))
     if masks is not None and len(masks) != n:
@@ -288,16 +353,44 @@ def color_jitter(canvas, cparams, masks=None, norm=1, out=None, slots=None):
                     raise _capi.RtposeError("image slot %d outside the %d-image plan" % (descs[k].n_dst, pn))
         if n == 0:
             return out
-        wb = lib.rtpose_jitter_workspace_bytes(C.byref(cfg), n)
-        if wb == 0:
-            raise _capi.RtposeError("bad jitter arguments: " + _capi.last_error())
-        workspace = torch.empty(wb // 4, dtype=torch.int32, device=canvas.device)
-        jitter_enqueue(descs, n, cfg, canvas, base, lay, workspace)
-        del workspace     # as in augment_images: handed out again only to work queued behind the launches
+        fire = [k for k, cp in enumerate(cparams) if cp.get("jpeg")] if jpeg else []
+
+        def jitter(some, count, jcfg, src, dst, dlay):
+            wb = lib.rtpose_jitter_workspace_bytes(C.byref(jcfg), count)
+            if wb == 0:
+                raise _capi.RtposeError("bad jitter arguments: " + _capi.last_error())
+            workspace = torch.empty(wb // 4, dtype=torch.int32, device=canvas.device)
+            jitter_enqueue(some, count, jcfg, src, dst, dlay, workspace)
+            del workspace     # as in augment_images: handed out again only to work queued behind the launches
+
+        if not fire:
+            jitter(descs, n, cfg, canvas, base, lay)
+            return out
+        rest = [k for k in range(n) if not cparams[k].get("jpeg")]
+        if rest:
+            plain = (_capi.JitterImage * len(rest))(*[descs[k] for k in rest])
+            jitter(plain, len(rest), cfg, canvas, base, lay)
+        # the firing images: ColorJitter alone -> the 8-bit canvas the reference saves; the round trip; the rest of the chain
+        nf = len(fire)
+        u8 = torch.empty((nf, 3, h, w), dtype=torch.float32, device=canvas.device)
+        before, after = (_capi.JitterImage * nf)(), (_capi.JitterImage * nf)()
+        for j, k in enumerate(fire):
+            a, b, d = before[j], after[j], descs[k]
+            for i in range(4):
+                a.order[i], b.order[i] = d.order[i], -1
+                a.mask[i], b.mask[i] = (0, 0, w, h)[i], d.mask[i]
+            for i in range(3):
+                a.factor[i], b.factor[i] = d.factor[i], 1.0
+            a.hue_shift, a.gray, a.n_src, a.n_dst = d.hue_shift, 0, d.n_src, j
+            b.hue_shift, b.gray, b.n_src, b.n_dst = 0, d.gray, j, d.n_dst
+        jitter(before, nf, _capi.JitterCfg.make(h, w, 0, 1), canvas, u8, None)
+        jpeg_roundtrip(u8, out=u8)
+        jitter(after, nf, cfg, u8, base, lay)
+        del u8
     return out
 
 
-def augment_images(images, params, out=None, norm=1, mask_valid=True, device=None, slots=None, color=None):
+def augment_images(images, params, out=None, norm=1, mask_valid=True, device=None, slots=None, color=None, jpeg=False):
     """The image side for a batch: ``images`` a list of uint8 RGB [h0, w0, 3] numpy arrays or device tensors of any
     sizes, ``params`` what draw_params returned for their sizes.  -> an [N, 3, S, S] fp32 device tensor (S the
     square_edge of the params): flipped, resized (Pillow's bicubic, bit for bit), cropped, centre-padded with
@@ -307,10 +400,15 @@ def augment_images(images, params, out=None, norm=1, mask_valid=True, device=Non
     and the plan is returned.  One table launch and one fused launch per 32 images, on the current stream.
     ``color``: what draw_color_params returned for the images; then the geometry launches write the uint8 canvas
     (norm 0, no mask) into a tensor of their own and color_jitter's launches make the result from it with the real
-    ``norm`` and mask (ColorJitter and RandomGrayscale of image_transform_train; its JPEG step is not built).  The
-    default, None, gives the launches and the bits of a call without the keyword."""
+    ``norm`` and mask (ColorJitter and RandomGrayscale of image_transform_train).  The default, None, gives the launches
+    and the bits of a call without the keyword.
+    ``jpeg``: with ``color``, color_jitter's keyword - True applies image_transform_train's JPEG step (header section
+    4e) to the images whose colour params say it fired; False, the default, leaves it out as the releases did in which
+    it was not built."""
     if len(images) != len(params):
         raise ValueError("%d images for %d params" % (len(images), len(params)))
+    if jpeg and color is None:
+        raise ValueError("jpeg=True needs the colour params that say which images fire (color=...)")
     n = len(images)
     edge = params[0]["square_edge"] if n else 368
     if any(p["square_edge"] != edge for p in params):
@@ -331,12 +429,12 @@ def augment_images(images, params, out=None, norm=1, mask_valid=True, device=Non
         with torch.cuda.device(device):
             canvas = augment_images(images, params, norm=0, mask_valid=False, device=device)
             if out is None and slots is None:
-                return color_jitter(canvas, color, masks, norm, out=canvas)
+                return color_jitter(canvas, color, masks, norm, out=canvas, jpeg=jpeg)
             if out is None:
                 if n and not all(0 <= s < n for s in slots):
                     raise _capi.RtposeError("image slots %s outside the %d-image result" % (list(slots), n))
                 out = torch.empty_like(canvas)
-            return color_jitter(canvas, color, masks, norm, out=out, slots=slots)
+            return color_jitter(canvas, color, masks, norm, out=out, slots=slots, jpeg=jpeg)
     with torch.cuda.device(device):
         held = []
         descs = (_capi.AugmentImage * max(n, 1))()
@@ -385,7 +483,7 @@ def augment_images(images, params, out=None, norm=1, mask_valid=True, device=Non
 
 
 def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, stride=8, sigma=7.0, device=None,
-                color=False):
+                color=False, jpeg=False):
     """-> (image [N, 3, S, S], heat [N, C_h, S / stride, S / stride], paf [N, C_p, ...], metas): the tuple
     collate_images_targets_meta makes of CocoKeypoints items (datasets.py:86-92, :193-214), as fp32 device tensors,
     plus the per-image meta dicts (with 'keypoints': the augmented [K, 17, 3] annotations in the reference's dtype, and
@@ -394,14 +492,19 @@ def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, 
     from the augmented keypoints through add_neck in their own dtype, remove_illegal_joint and encode_targets, as
     get_ground_truth does (datasets.py:259-274).
     ``color``: False - the image is ``image_transform``'s, as before the keyword; True - ``image_transform_train``'s
-    ColorJitter and RandomGrayscale are applied to the canvas before normalisation (its JPEG step is not built), drawn
+    ColorJitter and RandomGrayscale are applied to the canvas before normalisation, drawn
     with the geometry in the reference's order where ``params`` is None (draw_train_params), else on their own
-    (draw_color_params); or a list of colour params.  The metas then carry 'color' (the params) and 'jpeg' (whether the
-    reference would have re-compressed this image)."""
+    (draw_color_params); or a list of colour params.  The metas then carry 'color' (the params), 'jpeg' (whether the
+    reference would have re-compressed this image) and 'jpeg_applied' (whether this call did).
+    ``jpeg``: False, the default - the JPEG step is left out, as in the releases where it was not built; True - with
+    ``color``, the images whose draw fired are saved at quality 50 and re-opened on the device between ColorJitter and
+    RandomGrayscale (header section 4e), which completes image_transform_train."""
     if len(images) != len(annotations):
         raise ValueError("%d images for %d annotation lists" % (len(images), len(annotations)))
     sizes = [_size_of(im) for im in images]
     cparams = None if color is False or color is None else color
+    if jpeg and cparams is None:
+        raise ValueError("jpeg=True needs color (the JPEG step is part of image_transform_train)")
     if cparams is True:
         if params is None:
             params, cparams = draw_train_params(sizes)
@@ -423,7 +526,8 @@ def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, 
     if cparams is not None:
         for meta, cp in zip(metas, cparams):
             meta["color"], meta["jpeg"] = copy.deepcopy(cp), bool(cp.get("jpeg"))
-        image = augment_images(images, params, device=device, color=cparams)
+            meta["jpeg_applied"] = bool(jpeg) and meta["jpeg"]
+        image = augment_images(images, params, device=device, color=cparams, jpeg=jpeg)
     else:
         image = augment_images(images, params, device=device)
     heat, paf = encode.encode_targets(people, skeleton, (edge, edge), stride, sigma, device=image.device)

@@ -1,7 +1,7 @@
 // Colour jitter of the padded canvas on the device (header section 4d): torchvision's ColorJitter and RandomGrayscale on
 // the 8-bit RGB canvas, then ToTensor + Normalize and the valid-area mask - Pillow's bits.
 //
-//   lib/datasets/transforms.py:53-65 (image_transform_train; its JPEG step is not built), lib/datasets/datasets.py:193-204,
+//   lib/datasets/transforms.py:53-65 (image_transform_train; its JPEG step is jpeg_roundtrip.hip, header section 4e), lib/datasets/datasets.py:193-204,
 //   Pillow's ImageEnhance.Brightness / Contrast / Color over ImagingBlend, convert('L'), convert('HSV'), convert('RGB')
 //
 // Every operation is restated in the number format Pillow's C uses for it (-ffp-contract=off: the order written is the
