@@ -1488,6 +1488,133 @@ int rtpose_jpeg_roundtrip_batch(const rtpose_jpeg_image* images, int count, cons
                                 const float* src, float* dst, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
+/* ---- 4f. Decoding baseline JPEG files into training sources ----
+ * stands in for lib/datasets/datasets.py:171-172, Image.open(f).convert('RGB') of CocoKeypoints.__getitem__:
+ * the bytes of a file -> the dense uint8 [h][w][3] RGB image that section 4c takes as a source, in the bits
+ * of Pillow on libjpeg-turbo (JDCT_ISLOW, fancy up-sampling).  Two stages: the host reads the markers and
+ * the Huffman-coded scan into quantised coefficients (csrc/jpeg_entropy.cpp: plain C++, no device, no state,
+ * callable from any thread); the device de-quantises, runs the inverse DCT, up-samples and converts
+ * (csrc/jpeg_decode.hip).  D(x, n) and `>>` as in 4e.
+ *
+ * Served: SOF0 (baseline sequential Huffman) frames of 8-bit precision with 8-bit quantiser tables and one
+ * scan that interleaves all components; one component sampled 1 x 1 (gray), or three components - read as
+ * Y, Cb, Cr - with chroma sampled 1 x 1 and luma 1 x 1 (4:4:4), 2 x 1 (4:2:2), 2 x 2 (4:2:0) or 1 x 2
+ * (4:4:0, h x v); width and height 1..16384.  0xFF fill bytes, stuffed FF 00, APPn / COM and other
+ * segments with a length are skipped; several DQT / DHT segments and tables redefined before SOS are
+ * followed; with DRI, each RSTn resets the DC predictors and its number is checked.
+ *
+ * Refused, by a reason code (RTPOSE_JPEG_R_*, positive; rtpose_jpeg_reason_text gives its sentence), never
+ * by a crash and never with a partial result a caller may use: anything that is not a JPEG file or whose
+ * segments are malformed (SYNTAX: a length below 2, a table or frame segment of the wrong size, a Huffman
+ * table whose codes do not fit their lengths or whose DC symbols exceed 15, a quantiser entry of 0, ...);
+ * SOF1..SOF15, DAC and JPG markers (FRAME: extended, progressive, lossless, differential, arithmetic) and
+ * a scan whose spectral selection is not 0..63 or whose approximation is not 0; precision other than 8
+ * (PRECISION); 16-bit quantiser tables (QTABLE16); component counts other than 1 and 3 (COMPONENTS); an
+ * APP14 segment that begins "Adobe" (ADOBE) and the component ids 'R', 'G', 'B' (COLORSPACE) - either
+ * makes libjpeg choose another colour transform; any other sampling (SAMPLING); a scan that does not
+ * list the frame's components in the frame's order, or a second SOS behind the first scan (SCANS); a DNL
+ * marker or a height of 0 (DNL); a width or height of 0 or above 16384 (SIZE); a DC category above 11 or
+ * an AC size above 10 (CATEGORY); a zero run that passes coefficient 63 (RUN); a code in no table (CODE); a
+ * table selector never defined (TABLE); a missing, misplaced or wrongly numbered RSTn (RST); data that
+ * ends, or runs into a marker, before the last MCU, or that lacks the EOI marker (TRUNCATED); whole bytes
+ * other than fill bytes and EOI behind the last MCU (TRAILING); `capacity` below coef_count (CAPACITY);
+ * and any coefficient - the accumulated DC value included - whose product with its quantiser entry lies
+ * outside int16 (RANGE): libjpeg-turbo's SIMD inverse DCT multiplies in 16 bits and its C code does not,
+ * so outside that range "libjpeg's bits" is not one thing; inside it no int32 sum of the device's passes
+ * can overflow.  libjpeg pads a truncated scan with zeros and warns; this refuses.  Refusing too much is
+ * safe: the caller decodes a refused file elsewhere (augment.decode_jpegs: Pillow).
+ *
+ * Coefficients: int16, quantised as the file holds them (the device multiplies).  Component c occupies
+ * blocks_y[c] x blocks_x[c] blocks (the MCU grid times its sampling factors, so padded to whole MCUs) in
+ * raster order from coef + coef_offset[c], 64 words per block in natural order (row-major: word 8 r + k is
+ * row r, column k of the block; the file's zig-zag order is undone).  coef_count is their sum.  `qtab`
+ * receives each component's quantiser table in the same natural order (gray: all three rows the same).
+ *
+ * Up-sampling, on the real planes - component c has ceil(h * v_c / vmax) rows of ceil(w * h_c / hmax)
+ * samples, the rest of its blocks is padding - with a neighbour outside the real plane standing for the
+ * sample itself:
+ *   4:2:0  h2v2_fancy_upsample and, where the chroma plane is at most 2 samples wide, box replication,
+ *          exactly as in 4e.
+ *   4:2:2  h2v1_fancy_upsample: (3 c[x] + c[x - 1] + 1) >> 2 at even output columns, (3 c[x] + c[x + 1] +
+ *          2) >> 2 at odd ones (so the first and the last column of the up-sampled row are the sample
+ *          itself); box replication where the chroma plane is at most 2 samples wide.
+ *   4:4:0  h1v2_fancy_upsample: (3 c[y] + c[y - 1] + 1) >> 2 at even output rows, (3 c[y] + c[y + 1] + 2)
+ *          >> 2 at odd ones; no width condition.
+ *   4:4:4  none.   gray: Y into all three channels (convert('RGB') of an 'L' image).
+ * Then 4e's YCbCr -> RGB expression, clamped to 0..255, stored as bytes. */
+enum {
+  RTPOSE_JPEG_GRAY = 0, RTPOSE_JPEG_444 = 1, RTPOSE_JPEG_422 = 2, RTPOSE_JPEG_420 = 3, RTPOSE_JPEG_440 = 4
+};
+enum {
+  RTPOSE_JPEG_R_ARGUMENT = 1, RTPOSE_JPEG_R_NOT_JPEG = 2, RTPOSE_JPEG_R_SYNTAX = 3, RTPOSE_JPEG_R_TRUNCATED = 4,
+  RTPOSE_JPEG_R_FRAME = 5, RTPOSE_JPEG_R_PRECISION = 6, RTPOSE_JPEG_R_QTABLE16 = 7, RTPOSE_JPEG_R_COMPONENTS = 8,
+  RTPOSE_JPEG_R_ADOBE = 9, RTPOSE_JPEG_R_COLORSPACE = 10, RTPOSE_JPEG_R_SAMPLING = 11, RTPOSE_JPEG_R_SCANS = 12,
+  RTPOSE_JPEG_R_DNL = 13, RTPOSE_JPEG_R_SIZE = 14, RTPOSE_JPEG_R_CATEGORY = 15, RTPOSE_JPEG_R_RUN = 16,
+  RTPOSE_JPEG_R_CODE = 17, RTPOSE_JPEG_R_TABLE = 18, RTPOSE_JPEG_R_RST = 19, RTPOSE_JPEG_R_CAPACITY = 20,
+  RTPOSE_JPEG_R_RANGE = 21, RTPOSE_JPEG_R_TRAILING = 22
+};
+
+typedef struct rtpose_jpeg_info {
+  uint32_t struct_bytes;    /* sizeof(rtpose_jpeg_info), set by rtpose_jpeg_probe                        */
+  int32_t width, height;
+  int32_t components;       /* 1 or 3                                                                    */
+  int32_t mode;             /* RTPOSE_JPEG_GRAY .. RTPOSE_JPEG_440                                       */
+  int32_t hsamp[3], vsamp[3]; /* sampling factors                                                        */
+  int32_t mcus_x, mcus_y;   /* the MCU grid: ceil(width / (8 hmax)) x ceil(height / (8 vmax))            */
+  int32_t blocks_x[3], blocks_y[3]; /* per component: mcus_x * hsamp x mcus_y * vsamp                    */
+  int32_t restart_interval; /* MCUs between RSTn markers, 0 = none                                       */
+  int32_t reason;           /* 0 = served, else RTPOSE_JPEG_R_* (every other field is then 0)            */
+  uint64_t coef_offset[3];  /* int16 words from the image's first coefficient to component c's           */
+  uint64_t coef_count;      /* int16 words of the whole image: 64 * the sum of the block grids           */
+} rtpose_jpeg_info;
+
+/* Both walk host memory only, set no rtpose_last_error text and return 0 or the reason.  Probe reads the
+ * markers up to and including the SOS header; the refusals that only the scan can show (CATEGORY, RUN, CODE,
+ * RST, TRUNCATED, TRAILING, RANGE, a second scan) come from the decode.  The decode reads the file again
+ * by itself and requires `info` to agree (ARGUMENT otherwise); it zero-fills and writes coef[0 ..
+ * coef_count) - `capacity` is in words - and, on success only, qtab.  After a refusal coef holds no image. */
+int rtpose_jpeg_probe(const void* data, size_t len, rtpose_jpeg_info* info);
+int rtpose_jpeg_entropy_decode(const void* data, size_t len, const rtpose_jpeg_info* info, int16_t* coef,
+                               size_t capacity, uint16_t qtab[3][64]);
+const char* rtpose_jpeg_reason_text(int reason);
+
+/* The device stage.  `coef` is one device buffer of coef_words int16 words, 16-byte aligned, that holds for
+ * every image its coefficients (coef_count(width, height, mode) words from coef_offset, laid out as above)
+ * and its three quantiser tables (192 uint16 words from qtab_offset, natural order); both offsets are
+ * multiples of 8 words.  The tables travel in that buffer and not in the descriptor so that a chunk of 32
+ * images stays a kernel argument of 2.5 KB (with three 64-entry tables each it would be 13 KB); a host
+ * writes them in front of the image's coefficients and uploads both with one copy.  `dst` is the image: dense uint8 [height][width][3] device
+ * memory, 4-byte aligned.  The library derives every grid, count and plane size from width, height and
+ * mode; it allocates and copies nothing.
+ *
+ * Launches, per chunk of 32 images (descriptors by value): the IDCT pass - eight threads per block, 32
+ * blocks per 256-thread workgroup, all blocks of all components of an image flattened; a thread loads one
+ * 16-byte row of coefficients and of the table, multiplies, and the workgroup runs jidctint's column pass
+ * D(.., 11), row pass D(.., 18) and the range limit of 4e through an int32 LDS tile - stores 8-bit planes
+ * in the workspace, a component's rows padded to 8 bytes, blocks wholly outside the real plane left out;
+ * the up-sample pass, a thread per run of 4 pixels, reads Y and chroma by the rules above and stores 12
+ * bytes.  Every IDCT launch of a call precedes its first up-sample launch on the stream (the filters read
+ * across block borders).  Integer arithmetic only, no atomics: an image gives the same bits alone and in
+ * any batch. */
+typedef struct rtpose_jpeg_decode_image {
+  int32_t width, height;  /* 1..16384                                                                   */
+  int32_t mode;           /* RTPOSE_JPEG_GRAY .. RTPOSE_JPEG_440                                        */
+  int32_t reserved;       /* 0                                                                          */
+  uint64_t coef_offset;   /* words into coef                                                            */
+  uint64_t qtab_offset;   /* words into coef                                                            */
+  void* dst;
+} rtpose_jpeg_decode_image;
+
+/* Bytes of the caller-provided device workspace (the decoded planes of all images); 0 on a bad argument. */
+size_t rtpose_jpeg_decode_workspace_bytes(const rtpose_jpeg_decode_image* images, int count);
+/* Refused before any launch, the message naming the argument and for an image its index: NULL pointers; a
+ * negative count; width or height outside 1..16384; an unknown mode; a non-zero reserved; a coefficient or
+ * table offset that is no multiple of 8 or whose range ends beyond coef_words; a coef not aligned to 16
+ * bytes; a dst not aligned to 4 bytes; two destinations that overlap; a workspace that is not aligned to 8
+ * bytes or smaller than the query reports.  count == 0 is a no-op. */
+int rtpose_jpeg_decode_batch(const rtpose_jpeg_decode_image* images, int count, const int16_t* coef,
+                             size_t coef_words, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * 5. Flip test-time-augmentation merge
  *    stands in for evaluate/coco_eval.py:197-242 (handle_paf_and_heat).

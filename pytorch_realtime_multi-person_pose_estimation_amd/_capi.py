@@ -196,6 +196,25 @@ class JpegCfg(C.Structure):
         return cls(C.sizeof(cls), h, w, quality)
 
 
+class JpegInfo(C.Structure):
+    """rtpose_jpeg_info: what rtpose_jpeg_probe reads from a file's markers (header section 4f)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32),
+                ("mode", C.c_int32), ("hsamp", C.c_int32 * 3), ("vsamp", C.c_int32 * 3), ("mcus_x", C.c_int32),
+                ("mcus_y", C.c_int32), ("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3),
+                ("restart_interval", C.c_int32), ("reason", C.c_int32), ("coef_offset", C.c_uint64 * 3),
+                ("coef_count", C.c_uint64)]
+
+
+class JpegDecodeImage(C.Structure):
+    """rtpose_jpeg_decode_image: one image of a rtpose_jpeg_decode_batch call (header section 4f)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32),
+                ("coef_offset", C.c_uint64), ("qtab_offset", C.c_uint64), ("dst", C.c_void_p)]
+
+
+JPEG_MODES = ("gray", "4:4:4", "4:2:2", "4:2:0", "4:4:0")     # RTPOSE_JPEG_GRAY .. RTPOSE_JPEG_440
+JPEG_R_CAPACITY, JPEG_R_RANGE = 20, 21
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -382,6 +401,11 @@ _SIGS = {
     "rtpose_jitter_batch": (_i, [C.POINTER(JitterImage), _i, C.POINTER(JitterCfg), _vp, _vp, _LP, _vp, _sz, _vp]),
     "rtpose_jpeg_workspace_bytes": (_sz, [C.POINTER(JpegCfg), _i]),
     "rtpose_jpeg_roundtrip_batch": (_i, [C.POINTER(JpegImage), _i, C.POINTER(JpegCfg), _vp, _vp, _vp, _sz, _vp]),
+    "rtpose_jpeg_probe": (_i, [_vp, _sz, C.POINTER(JpegInfo)]),
+    "rtpose_jpeg_entropy_decode": (_i, [_vp, _sz, C.POINTER(JpegInfo), _vp, _sz, _vp]),
+    "rtpose_jpeg_reason_text": (C.c_char_p, [_i]),
+    "rtpose_jpeg_decode_workspace_bytes": (_sz, [C.POINTER(JpegDecodeImage), _i]),
+    "rtpose_jpeg_decode_batch": (_i, [C.POINTER(JpegDecodeImage), _i, _vp, _sz, _vp, _sz, _vp]),
     "rtpose_preprocess_u8_batch": (_i, [C.POINTER(PrepImage), _i, _i, _vp, _LP, _i, _i, _vp]),
     "rtpose_preprocess_u8": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_preprocess_u8_flip": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _LP, _i, _i, _i, _i, _i, _i, _vp]),

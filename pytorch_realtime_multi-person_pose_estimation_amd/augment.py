@@ -28,13 +28,23 @@ only with ``jpeg=True`` (``color_jitter``, ``augment_images``, ``train_batch``),
 4e, in libjpeg-turbo's bits.  Without the keyword the launches and the bits are those of the releases in which the step
 was not built.
 
+File entries: an image may be given as the ``bytes`` of a JPEG file or as a path (datasets.py:171-172,
+``Image.open(f).convert('RGB')``).  ``decode_jpegs`` turns baseline files into the uint8 device tensors the rest takes:
+Huffman decoding on host threads (csrc/jpeg_entropy.cpp), de-quantisation, inverse DCT, up-sampling and colour
+conversion on the device (csrc/jpeg_decode.hip, header section 4f), in the bits of Pillow on libjpeg-turbo.  A file
+outside the served subset (progressive, CMYK, ...) goes through Pillow itself.
+
 Out of scope: ``RandomRotate`` (cv2 ``warpAffine``; not in the training script's chain); ``RescaleAbsolute`` /
-``MultiScale``; image decoding; the DataLoader.  (``ColorJitter`` and ``RandomGrayscale`` were out of scope until the
-colour jitter of header section 4d, JPEG re-compression until section 4e.)
+``MultiScale``; EXIF orientation (``Image.open`` does not apply it either); PNG; the DataLoader.  (``ColorJitter`` and
+``RandomGrayscale`` were out of scope until the colour jitter of header section 4d, JPEG re-compression until section
+4e, image decoding until section 4f.)
 """
 import copy
 import ctypes as C
+import io
 import math
+import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -212,8 +222,152 @@ def transform_annotations(anns, size, params):
     return keypoints, bboxes, meta, valid_mask(meta["valid_area"], edge, edge)
 
 
+def _is_file(image):
+    """An entry of ``images`` that stands for a file: its bytes, or a path."""
+    return isinstance(image, (bytes, bytearray, memoryview, str, os.PathLike))
+
+
+def _file_bytes(f):
+    if isinstance(f, (str, os.PathLike)):
+        with open(f, 'rb') as fh:
+            return fh.read()
+    return f if isinstance(f, bytes) else bytes(f)
+
+
+def _probe(data):
+    info = _capi.JpegInfo()
+    lib.rtpose_jpeg_probe(data, len(data), C.byref(info))
+    return info
+
+
+def _reason(code):
+    return lib.rtpose_jpeg_reason_text(int(code)).decode()
+
+
+def jpeg_probe(data):
+    """What the markers of a JPEG file (its ``bytes``, or a path) say, without decoding it (rtpose_jpeg_probe, header
+    section 4f).  -> a dict: ``served`` - whether the native decoder takes the file as far as its headers tell; if so
+    ``width``, ``height``, ``components`` (1 or 3), ``mode`` ('gray', '4:4:4', '4:2:2', '4:2:0', '4:4:0'), ``sampling``
+    (per component (h, v)), ``restart_interval`` and ``coef_count``; if not, ``reason`` (a sentence) and ``reason_code``
+    (RTPOSE_JPEG_R_*), the other entries None."""
+    info = _probe(_file_bytes(data))
+    if info.reason:
+        return dict(served=False, reason=_reason(info.reason), reason_code=int(info.reason), width=None, height=None,
+                    components=None, mode=None, sampling=None, restart_interval=None, coef_count=None)
+    nc = int(info.components)
+    return dict(served=True, reason=None, reason_code=0, width=int(info.width), height=int(info.height), components=nc,
+                mode=_capi.JPEG_MODES[info.mode], sampling=[(int(info.hsamp[c]), int(info.vsamp[c])) for c in range(nc)],
+                restart_interval=int(info.restart_interval), coef_count=int(info.coef_count))
+
+
+def _pil_open(data):
+    from PIL import Image
+    return Image.open(io.BytesIO(data))
+
+
+def decode_jpegs(files, device=None, fallback='pil', workers=8, pinned=True):
+    """``Image.open(f).convert('RGB')`` for a batch of JPEG files.  ``files``: ``bytes``, or paths that are read with
+    ``open(..., 'rb')``.  -> (images, infos): images uint8 [h, w, 3] device tensors - what augment_images takes as
+    sources -, infos per image a dict with width, height, mode, ``native`` (which path it took) and ``reason`` (why
+    not, else None).
+    The native path (header section 4f): rtpose_jpeg_probe sizes one staging tensor (``pinned``: in page-locked memory)
+    that holds per image its three quantiser tables and its quantised coefficients; rtpose_jpeg_entropy_decode fills
+    it on a ThreadPoolExecutor of ``workers`` threads (ctypes releases the GIL; capped at 16, never derived from the
+    machine's CPU count); one host-to-device copy; then rtpose_jpeg_decode_batch's two launch kinds per 32 images, all on
+    the current stream.  Bit for bit what Pillow on libjpeg-turbo returns.
+    A file the native path refuses - progressive, CMYK, an Adobe segment, odd sampling, damaged data, a coefficient
+    beyond int16: the refusals of section 4f - goes through Pillow and an upload with ``fallback='pil'``; with
+    ``fallback=None`` it raises RtposeError with the reason."""
+    if fallback not in ('pil', None):
+        raise ValueError("fallback is 'pil' or None")
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != 'cuda':
+        raise _capi.RtposeError("decode_jpegs runs on an MI355X (HIP) device only (no CPU fallback); got %s" % device)
+    datas = [_file_bytes(f) for f in files]
+    n = len(datas)
+    probes = [_probe(d) for d in datas]
+    offsets, total = [], 0
+    for info in probes:                      # per served image: 192 words of tables, then its coefficients
+        offsets.append(total)
+        if not info.reason:
+            total += 192 + int(info.coef_count)
+    reasons = [int(info.reason) for info in probes]
+    jobs = [k for k in range(n) if not reasons[k]]
+    staging = torch.empty(max(total, 8), dtype=torch.int16, pin_memory=bool(pinned)) if jobs else None
+
+    def host_stage(k):
+        at = staging.data_ptr() + 2 * offsets[k]
+        return lib.rtpose_jpeg_entropy_decode(datas[k], len(datas[k]), C.byref(probes[k]), C.c_void_p(at + 2 * 192),
+                                              int(probes[k].coef_count), C.c_void_p(at))
+
+    threads = max(1, min(int(workers), 16, len(jobs)))
+    if threads > 1:
+        with ThreadPoolExecutor(max_workers=threads) as pool:
+            codes = list(pool.map(host_stage, jobs))
+    else:
+        codes = [host_stage(k) for k in jobs]
+    for k, rc in zip(jobs, codes):
+        reasons[k] = int(rc)
+    if fallback is None:
+        for k in range(n):
+            if reasons[k]:
+                raise _capi.RtposeError("decode_jpegs: file %d is not served by the native decoder: %s (reason %d)"
+                                        % (k, _reason(reasons[k]), reasons[k]))
+    native = [k for k in range(n) if not reasons[k]]
+    images, infos = [None] * n, [None] * n
+    with torch.cuda.device(device):
+        if native:
+            coef = torch.empty(staging.numel(), dtype=torch.int16, device=device)
+            coef.copy_(staging, non_blocking=True)
+            descs = (_capi.JpegDecodeImage * len(native))()
+            for j, k in enumerate(native):
+                info, d = probes[k], descs[j]
+                images[k] = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=device)
+                d.width, d.height, d.mode, d.reserved = info.width, info.height, info.mode, 0
+                d.qtab_offset, d.coef_offset, d.dst = offsets[k], offsets[k] + 192, images[k].data_ptr()
+                infos[k] = dict(width=int(info.width), height=int(info.height), mode=_capi.JPEG_MODES[info.mode],
+                                native=True, reason=None)
+            wb = lib.rtpose_jpeg_decode_workspace_bytes(descs, len(native))
+            if wb == 0:
+                raise _capi.RtposeError("bad jpeg decode arguments: " + _capi.last_error())
+            workspace = torch.empty(wb // 8, dtype=torch.int64, device=device)
+            check(lib.rtpose_jpeg_decode_batch(descs, len(native), ptr(coef), coef.numel(), ptr(workspace), wb,
+                                               current_stream()), "rtpose_jpeg_decode_batch")
+            # the copy reads the staging tensor and the launches read coef and the workspace after this function returns:
+            # torch's allocators hand their memory out again only to work queued behind them (as in augment_images)
+            del coef, workspace
+        for k in range(n):
+            if reasons[k]:
+                im = _pil_open(datas[k])
+                mode = im.mode           # Pillow's own name for what the file holds: 'L', 'RGB', 'CMYK'
+                arr = np.array(im.convert('RGB'))
+                images[k] = torch.from_numpy(arr).to(device, non_blocking=True)
+                infos[k] = dict(width=int(arr.shape[1]), height=int(arr.shape[0]), mode=mode, native=False,
+                                reason=_reason(reasons[k]))
+    return images, infos
+
+
 def _size_of(image):
+    if _is_file(image):                  # a file entry: its header says the size, nothing is decoded
+        data = _file_bytes(image)
+        info = _probe(data)
+        if not info.reason:
+            return int(info.height), int(info.width)
+        w, h = _pil_open(data).size
+        return int(h), int(w)
     return int(image.shape[0]), int(image.shape[1])
+
+
+def _decode_entries(images, device):
+    """The file entries of ``images`` decoded by decode_jpegs.  -> (images with tensors in their places, {index: info})."""
+    which = [k for k, im in enumerate(images) if _is_file(im)]
+    if not which:
+        return images, {}
+    decoded, infos = decode_jpegs([images[k] for k in which], device=device)
+    images = list(images)
+    for j, k in enumerate(which):
+        images[k] = decoded[j]
+    return images, {k: infos[j] for j, k in enumerate(which)}
 
 
 def augment_enqueue(descs, count, cfg, dst, layout, workspace):
@@ -392,7 +546,8 @@ def color_jitter(canvas, cparams, masks=None, norm=1, out=None, slots=None, jpeg
 
 def augment_images(images, params, out=None, norm=1, mask_valid=True, device=None, slots=None, color=None, jpeg=False):
     """The image side for a batch: ``images`` a list of uint8 RGB [h0, w0, 3] numpy arrays or device tensors of any
-    sizes, ``params`` what draw_params returned for their sizes.  -> an [N, 3, S, S] fp32 device tensor (S the
+    sizes - or JPEG files, as ``bytes`` or paths, which decode_jpegs decodes first (their sizes for draw_params come
+    from jpeg_probe) -, ``params`` what draw_params returned for their sizes.  -> an [N, 3, S, S] fp32 device tensor (S the
     square_edge of the params): flipped, resized (Pillow's bicubic, bit for bit), cropped, centre-padded with
     (124, 116, 104), ToTensor + ImageNet Normalize (``norm=1``; 0 keeps float(u) in 0..255) and, with ``mask_valid``,
     zero outside the valid area (utils.mask_valid_area).  With ``out=plan`` (a native plan of [>= N, S, S]) the images
@@ -421,6 +576,7 @@ def augment_images(images, params, out=None, norm=1, mask_valid=True, device=Non
     device = torch.device(device)
     if device.type != 'cuda':
         raise _capi.RtposeError("augment_images runs on an MI355X (HIP) device only (no CPU fallback); got %s" % device)
+    images, _ = _decode_entries(images, device)       # file entries (bytes, paths) become device tensors first
     if color is not None:
         if len(color) != n:
             raise ValueError("%d images for %d colour params" % (n, len(color)))
@@ -487,7 +643,9 @@ def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, 
     """-> (image [N, 3, S, S], heat [N, C_h, S / stride, S / stride], paf [N, C_p, ...], metas): the tuple
     collate_images_targets_meta makes of CocoKeypoints items (datasets.py:86-92, :193-214), as fp32 device tensors,
     plus the per-image meta dicts (with 'keypoints': the augmented [K, 17, 3] annotations in the reference's dtype, and
-    'bboxes').  ``images``: uint8 RGB arrays or device tensors; ``annotations``: per image a list of COCO annotation
+    'bboxes').  ``images``: uint8 RGB arrays or device tensors, or JPEG files as ``bytes`` or paths - those are sized by
+    jpeg_probe for the draws, decoded by decode_jpegs (header section 4f; Pillow for a file outside the served subset),
+    and their metas carry 'decoded_native'; ``annotations``: per image a list of COCO annotation
     dicts ('keypoints', 'bbox'); ``params=None`` draws them (draw_params on torch's global generator).  The targets come
     from the augmented keypoints through add_neck in their own dtype, remove_illegal_joint and encode_targets, as
     get_ground_truth does (datasets.py:259-274).
@@ -501,6 +659,7 @@ def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, 
     RandomGrayscale (header section 4e), which completes image_transform_train."""
     if len(images) != len(annotations):
         raise ValueError("%d images for %d annotation lists" % (len(images), len(annotations)))
+    images = [_file_bytes(im) if _is_file(im) else im for im in images]     # a path is read once
     sizes = [_size_of(im) for im in images]
     cparams = None if color is False or color is None else color
     if jpeg and cparams is None:
@@ -523,6 +682,13 @@ def train_batch(images, annotations, params=None, skeleton=encode.COCO18_TRAIN, 
         meta = copy.deepcopy(meta)
         meta["keypoints"], meta["bboxes"] = kps, boxes
         metas.append(meta)
+    if any(_is_file(im) for im in images):
+        if device is None:
+            on_device = [im for im in images if hasattr(im, "data_ptr")]
+            device = on_device[0].device if on_device else None
+        images, decoded = _decode_entries(images, device)
+        for k, info in decoded.items():
+            metas[k]["decoded_native"] = bool(info["native"])
     if cparams is not None:
         for meta, cp in zip(metas, cparams):
             meta["color"], meta["jpeg"] = copy.deepcopy(cp), bool(cp.get("jpeg"))
