@@ -340,6 +340,43 @@ int rtpose_dwconv3x3_wgrad(const float* x, const rtpose_layout* lx, const float*
 int rtpose_dwconv3x3_dgrad(const float* gy, const rtpose_layout* lgy, const float* w, float* dx, const rtpose_layout* ldx, int C,
                            int N, int H, int W, int stride, void* stream);
 
+/* ---- 2b, continued.  Mixed-precision training: the weight gradient (+ bias gradient) of a stride-1 "same" conv,
+ * k in {1, 3, 7}, from bf16 layout slices (csrc/conv_backward_bf16.hip; train.conv2d(compute_dtype='bf16')).  The forward
+ * and the data gradient of such a step are rtpose_conv2d_bf16 (out_f32 = 1); this is the third kernel.  The reference has
+ * no reduced-precision training: the contract is this project's.
+ *     dw[o][c][dy][dx] = sum over (n, y, x) of gy[n, y, x, o] * x[n, y + dy - k/2, x + dx - k/2, c]
+ *     dbias[o]         = sum over (n, y, x) of gy[n, y, x, o]                         (dbias != NULL)
+ * `x` and `gy` point at bf16 elements and their layouts count ELEMENTS per pixel.  Products of two bf16 values are exact
+ * in fp32; they are accumulated in fp32 (v_mfma_f32_32x32x16_bf16), dbias in fp32 pixel by pixel.  `dw` is dense OIHW
+ * fp32, `dbias` cout floats; both are OVERWRITTEN.
+ * The slices: both bases 16-byte aligned, choff and cstride multiples of 8 elements (the kernel loads 16 bytes = 8
+ * channels of a pixel at a time); the gaps of `x` at least k/2 wide and bf16 zero; `gy` is read at its valid pixels only.
+ * cin and cout are any value >= 1.  Channels outside [choff, choff + cin) of x and [choff, choff + cout) of gy never
+ * reach a sum; those that share a 16-byte group with the last channels of a slice are loaded and cleared.
+ * The sums follow rtpose_conv2d_wgrad's scheme: the valid pixels are cut, in (n, y, x) order, into
+ * rtpose_conv2d_wgrad_bf16_slabs() slabs that depend on the shape only - equal multiples of 64 pixels but for the last
+ * one, across image boundaries; every slab's partial sums go to `workspace` (device memory of the caller,
+ * rtpose_conv2d_wgrad_bf16_workspace_floats() = slabs * (k * k * cout * cin + cout) floats rounded up to 4, 16-byte
+ * aligned as `dw`) and a second launch adds them in slab order: no atomics, the same inputs give the same bits on every
+ * run.  Every argument is checked on the host before any launch (RTPOSE_E_INVAL with a text); both queries are host-only
+ * and return 0 for a shape the launcher refuses.  ZERO-INITIALISE the descriptor. */
+typedef struct rtpose_wgrad_bf16_desc {
+  const void* x;    /* bf16 layout slices */
+  const void* gy;
+  float* dw;
+  float* dbias;     /* or NULL */
+  float* workspace;
+  size_t workspace_floats;
+  rtpose_layout lx;   /* count ELEMENTS per pixel */
+  rtpose_layout lgy;
+  int32_t cin;
+  int32_t cout;
+  int32_t k;
+} rtpose_wgrad_bf16_desc;
+size_t rtpose_conv2d_wgrad_bf16_workspace_floats(int cin, int cout, int k, int N, int H, int W);
+int rtpose_conv2d_wgrad_bf16_slabs(int cin, int cout, int k, int N, int H, int W);
+int rtpose_conv2d_wgrad_bf16(const rtpose_wgrad_bf16_desc* d, int N, int H, int W, void* stream);
+
 /* ---- the first layer: nn.Conv2d(3, 64, 3, 1, 1) (+ nn.ReLU), conv1_1 of the VGG-19 front end
  * (lib/network/rtpose_vgg.py:23-35, `model0.0`; csrc/conv_first.hip).  Reads the image where it is -
  * dense NCHW fp32 (`x_nchw`), or, with x_nchw = NULL, a layout buffer with >= 3 channels per pixel

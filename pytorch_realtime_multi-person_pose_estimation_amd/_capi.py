@@ -55,6 +55,11 @@ class WgradDesc(C.Structure):
                 ("cin", C.c_int32), ("cout", C.c_int32), ("k", C.c_int32)]
 
 
+class WgradBf16Desc(C.Structure):
+    """rtpose_wgrad_bf16_desc: one weight-gradient launch on bf16 slices (header section 2b, continued); WgradDesc's fields."""
+    _fields_ = WgradDesc._fields_
+
+
 class NetOptions(C.Structure):
     """rtpose_net_options: per-plan arithmetic of the fp32 convs (header §3)."""
     _fields_ = [("struct_bytes", C.c_uint32), ("dtype", C.c_int32), ("winograd3", C.c_int32),
@@ -240,6 +245,9 @@ _SIGS = {
     "rtpose_conv2d_wgrad_workspace_floats": (_sz, [_i, _i, _i, _i, _i, _i]),
     "rtpose_conv2d_wgrad_slabs": (_i, [_i, _i, _i, _i, _i, _i]),
     "rtpose_conv2d_wgrad": (_i, [C.POINTER(WgradDesc), _i, _i, _i, _vp]),
+    "rtpose_conv2d_wgrad_bf16_workspace_floats": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "rtpose_conv2d_wgrad_bf16_slabs": (_i, [_i, _i, _i, _i, _i, _i]),
+    "rtpose_conv2d_wgrad_bf16": (_i, [C.POINTER(WgradBf16Desc), _i, _i, _i, _vp]),
     "rtpose_relu_grad": (_i, [_vp, _LP, _vp, _LP, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_prelu": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_prelu_grad_workspace_floats": (_sz, [_i, _i, _i, _i]),

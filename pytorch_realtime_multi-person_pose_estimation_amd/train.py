@@ -43,6 +43,17 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   split, ``torch.cat``, the channel shuffle and the ceil-mode max-pool stay torch's); the pointwise convs and the heads are
   ``conv2d``, every BatchNorm ``batch_norm``.
 
+* Mixed precision (``compute_dtype='bf16'`` of ``conv2d``, ``run_sequential``, ``forward_train`` and ``train_step``; RtposeVGG
+  and OpenPose_Model): bf16 operands, fp32 accumulation, fp32 master weights, no loss scaling (bf16 has fp32's exponent
+  range).  Tensors at the autograd boundary stay NCHW fp32 and parameters stay fp32.  Forward: ``rtpose_nchw_to_layout_bf16``
+  (round to nearest even, channels padded to 16), the filters packed by ``rtpose_pack_conv_weights_bf16`` (cached as
+  'fwd16' / 'bwd16' beside the fp32 packings), ``rtpose_conv2d_bf16(out_f32=1)`` with bias and ReLU fused; the bf16 input
+  buffer is what is kept for the weight gradient.  Backward: ``rtpose_relu_grad`` / ``rtpose_prelu_grad`` in fp32 as above,
+  ``rtpose_layout_f32_to_bf16`` of the masked gradient (its one rounding point), the data gradient as
+  ``rtpose_conv2d_bf16(out_f32=1)`` on the bf16 packing of ``dgrad_weights``, the weight and bias gradients by
+  ``rtpose_conv2d_wgrad_bf16``.  A shape ``rtpose_conv2d_bf16`` refuses (it refuses before launching) runs that direction of
+  that conv on the fp32 path and is counted in ``bf16_fallbacks``.  The default ``'fp32'`` is the path above, launch for launch.
+
 The NCHW <-> layout conversion around every operation is known overhead; activations do not stay in layouts across layers yet.
 """
 import ctypes as C
@@ -70,8 +81,26 @@ def _up8(c):
     return (c + 7) // 8 * 8
 
 
+def _up16(c):
+    return (c + 15) // 16 * 16
+
+
+COMPUTE_DTYPES = ('fp32', 'bf16')
+# convs of a compute_dtype='bf16' run whose forward / data gradient rtpose_conv2d_bf16 refused and the fp32 path ran instead
+bf16_fallbacks = {'fwd': 0, 'dgrad': 0}
+
+
+def reset_bf16_fallbacks():
+    bf16_fallbacks['fwd'] = bf16_fallbacks['dgrad'] = 0
+
+
+def _check_compute_dtype(who, compute_dtype):
+    if compute_dtype not in COMPUTE_DTYPES:
+        raise _capi.RtposeError("%s: compute_dtype is 'fp32' or 'bf16'; got %r" % (who, compute_dtype))
+
+
 # ---- packed filters, per parameter (epoch, _version, data_ptr), as _native_state.py keys the forward arenas -----------------
-_packed = {}   # id(weight) -> {'fwd': (key, w_packed, b_packed), 'bwd': (key, w_packed, b_packed)}
+_packed = {}   # id(weight) -> {'fwd': (key, w_packed, b_packed), 'bwd': (key, w_packed, b_packed)}; 'fwd16' / 'bwd16': in bf16
 
 
 def drop_packed_filters(weight=None):
@@ -93,16 +122,25 @@ def _pack(weight, bias, cin_p):
     return wp, bp
 
 
+def _pack_bf16(weight, bias, cin_p):
+    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+    wp = torch.zeros(lib.rtpose_packed_weight_bytes_bf16(cout, cin_p, k) // 2, dtype=torch.bfloat16, device=weight.device)
+    bp = torch.zeros(lib.rtpose_packed_bias_floats(cout), dtype=torch.float32, device=weight.device)
+    check(lib.rtpose_pack_conv_weights_bf16(ptr(weight), ptr(bias), cout, cin, k, None, cin_p, ptr(wp), ptr(bp),
+                                            current_stream()), "rtpose_pack_conv_weights_bf16")
+    return wp, bp
+
+
 def _packed_for(weight, bias, which, epoch=0, resync=False):
     """The packing of `weight` (+ `bias`) for the forward ('fwd') or of its flipped, transposed form for the data gradient
-    ('bwd', zero bias), re-packed when `epoch` (the owning model's weight epoch) or the parameter's (_version, data_ptr)
+    ('bwd', zero bias) - 'fwd16' / 'bwd16': the same two rounded to bf16, input channels padded to 16 -, re-packed when `epoch` (the owning model's weight epoch) or the parameter's (_version, data_ptr)
     changed, and always if `resync`."""
     entry = _packed.get(id(weight))
     if entry is None or entry['ref']() is not weight:
         entry = _packed[id(weight)] = {'ref': weakref.ref(weight)}
         weakref.finalize(weight, _packed.pop, id(weight), None)
     key = (epoch, weight._version, weight.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    if which in ('fwd', 'stem') and bias is not None:
+    if which in ('fwd', 'fwd16', 'stem') and bias is not None:
         key += (bias._version, bias.data_ptr())
     hit = entry.get(which)
     if hit is not None and hit[0] == key and not resync:
@@ -114,12 +152,13 @@ def _packed_for(weight, bias, which, epoch=0, resync=False):
                                          ptr(wp), current_stream()), "rtpose_pack_conv7x7_s2")
         entry[which] = (key, wp, None)
         return wp, None
-    if which == 'fwd':
+    pack, up = (_pack_bf16, _up16) if which in ('fwd16', 'bwd16') else (_pack, _up8)
+    if which in ('fwd', 'fwd16'):
         b = bias.detach() if bias is not None else torch.zeros(w.shape[0], dtype=torch.float32, device=w.device)
-        wp, bp = _pack(w.contiguous(), b.contiguous(), _up8(w.shape[1]))
+        wp, bp = pack(w.contiguous(), b.contiguous(), up(w.shape[1]))
     else:
         wt = dgrad_weights(w)
-        wp, bp = _pack(wt, torch.zeros(wt.shape[0], dtype=torch.float32, device=w.device), _up8(wt.shape[1]))
+        wp, bp = pack(wt, torch.zeros(wt.shape[0], dtype=torch.float32, device=w.device), up(wt.shape[1]))
     entry[which] = (key, wp, bp)
     return wp, bp
 
@@ -171,6 +210,54 @@ def _wgrad(xbuf, lx, gbuf, lg, like_weight, cin, cout, k, n, h, w, need_b):
     d.lx, d.lgy = lx, lg
     d.cin, d.cout, d.k = cin, cout, k
     check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad")
+    return dw, db
+
+
+def _buffer_bf16(lay, n, h, w, device):
+    numel = lib.rtpose_layout_pixels(C.byref(lay), n, h, w) * lay.cstride
+    return torch.zeros(numel, dtype=torch.bfloat16, device=device)
+
+
+def _to_layout_bf16(t, pad):
+    """NCHW fp32 -> a zero-gapped bf16 layout buffer (round to nearest even) with the channels rounded up to 16, the
+    extra ones zero"""
+    n, c, h, w = t.shape
+    lay = _capi.Layout.padded(_up16(c), h, w, pad)
+    buf = _buffer_bf16(lay, n, h, w, t.device)
+    check(lib.rtpose_nchw_to_layout_bf16(ptr(t), ptr(buf), C.byref(lay), c, lay.cstride, n, h, w, current_stream()),
+          "rtpose_nchw_to_layout_bf16")
+    return buf, lay
+
+
+def _launch_conv_bf16(inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
+    """rtpose_conv2d_bf16 (out_f32 = 1) of a bf16 layout buffer into a new dense fp32 one: (buffer, layout), or None if the
+    launcher refused the shape (RTPOSE_E_INVAL: returned before any launch)"""
+    lout = _capi.Layout.dense(_up8(cout), h, w)
+    out = _buffer(lout, n, h, w, inp.device, False)
+    d = _capi.ConvDesc()
+    d.inp, d.w_packed, d.bias_packed, d.out = inp.data_ptr(), wp.data_ptr(), bp.data_ptr(), out.data_ptr()
+    d.lin, d.lout = lin, lout
+    d.cin, d.cout, d.k, d.relu = cin_p, cout, k, 1 if relu else 0
+    rc = lib.rtpose_conv2d_bf16(C.byref(d), 1, n, h, w, 1, current_stream())
+    if rc == -1:        # RTPOSE_E_INVAL
+        return None
+    check(rc, "rtpose_conv2d_bf16")
+    return out, lout
+
+
+def _wgrad_bf16(xbuf, lx, gbuf, lg, like_weight, cin, cout, k, n, h, w, need_b):
+    """rtpose_conv2d_wgrad_bf16 of the bf16 layout buffers of x and of the output gradient: (dw shaped like `like_weight`,
+    db or None), both fp32"""
+    dw = torch.empty_like(like_weight, memory_format=torch.contiguous_format)
+    db = torch.empty(cout, dtype=torch.float32, device=gbuf.device) if need_b else None
+    floats = lib.rtpose_conv2d_wgrad_bf16_workspace_floats(cin, cout, k, n, h, w)
+    ws = torch.empty(floats, dtype=torch.float32, device=gbuf.device)
+    d = _capi.WgradBf16Desc()
+    d.x, d.gy, d.dw, d.dbias = xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
+    d.workspace, d.workspace_floats = ws.data_ptr(), floats
+    d.lx, d.lgy = lx, lg
+    d.cin, d.cout, d.k = cin, cout, k
+    check(lib.rtpose_conv2d_wgrad_bf16(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad_bf16")
     return dw, db
 
 
@@ -275,13 +362,100 @@ class _Conv2d(torch.autograd.Function):
         return dx, dw, db, None, None, None, da
 
 
-def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None):
+class _Conv2dBf16(torch.autograd.Function):
+    """_Conv2d with bf16 operands: what is rounded, and where, is in the module docstring.  Everything fp32 here - the
+    activation gradients, the buffers y / z they read, the outputs of all three convs - is as in _Conv2d."""
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu, epoch, resync, prelu):
+        if prelu is not None:
+            _check_prelu(prelu, weight, relu)
+        _check_input(x, weight)
+        with torch.cuda.device(x.device):
+            n, cin, h, w = x.shape
+            cout, k = weight.shape[0], weight.shape[2]
+            xc = x.detach().contiguous()
+            xbuf, lx = _to_layout_bf16(xc, k // 2)
+            wp, bp = _packed_for(weight, bias, 'fwd16', epoch, resync)
+            done = _launch_conv_bf16(xbuf, lx, wp, bp, lx.cstride, cout, k, relu, n, h, w)
+            if done is None:             # refused before any launch: this direction of this conv in fp32
+                bf16_fallbacks['fwd'] += 1
+                xbuf32, lx32 = _to_layout(xc, k // 2)
+                wp, bp = _packed_for(weight, bias, 'fwd', epoch, resync)
+                done = _launch_conv(xbuf32, lx32, wp, bp, lx32.cstride, cout, k, relu, n, h, w)
+            ybuf, ly = done
+            zbuf = None
+            if prelu is not None:        # as in _Conv2d: the conv wrote the pre-activation z
+                zbuf, ybuf = ybuf, _buffer(ly, n, h, w, x.device, False)
+                check(lib.rtpose_prelu(ptr(zbuf), C.byref(ly), ptr(prelu.detach().contiguous()), ptr(ybuf), C.byref(ly), cout,
+                                       n, h, w, current_stream()), "rtpose_prelu")
+            y = _from_layout(ybuf, ly, n, cout, h, w)
+        ctx.geom = (n, cin, cout, k, h, w)
+        ctx.relu = bool(relu)
+        ctx.has_bias = bias is not None
+        ctx.weight = weight
+        ctx.epoch, ctx.resync = epoch, resync
+        ctx.has_prelu = prelu is not None
+        ctx.save_for_backward(*((weight, prelu) if ctx.has_prelu else (weight,)))
+        wants_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
+        ctx.xbuf, ctx.lx = (xbuf, lx) if wants_w else (None, None)      # the bf16 buffer
+        ctx.ybuf, ctx.ly = (ybuf, ly) if relu and any(ctx.needs_input_grad) else (None, None)
+        ctx.zbuf, ctx.lz = (zbuf, ly) if ctx.has_prelu and any(ctx.needs_input_grad) else (None, None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        saved = ctx.saved_tensors
+        n, cin, cout, k, h, w = ctx.geom
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        need_a = ctx.has_prelu and ctx.needs_input_grad[6]
+        dx = dw = db = da = None
+        with torch.cuda.device(gy.device):
+            stream = current_stream()
+            gbuf, lg = _to_layout(gy.detach().float().contiguous(), k // 2)
+            if ctx.relu:
+                check(lib.rtpose_relu_grad(ptr(ctx.ybuf), C.byref(ctx.ly), ptr(gbuf), C.byref(lg), ptr(gbuf), C.byref(lg), cout,
+                                           n, h, w, stream), "rtpose_relu_grad")
+            if ctx.has_prelu:
+                floats = lib.rtpose_prelu_grad_workspace_floats(cout, n, h, w) if need_a else 0
+                ws = torch.empty(floats, dtype=torch.float32, device=gy.device) if need_a else None
+                da = torch.empty(cout, dtype=torch.float32, device=gy.device) if need_a else None
+                check(lib.rtpose_prelu_grad(ptr(ctx.zbuf), C.byref(ctx.lz), ptr(saved[1].detach().contiguous()), ptr(gbuf),
+                                            C.byref(lg), ptr(gbuf), C.byref(lg), ptr(da), ptr(ws), floats, cout, n, h, w, stream),
+                      "rtpose_prelu_grad")
+            if need_x or need_w or need_b:
+                # the one rounding point of the output gradient: both gradients below read these bf16 values
+                lg16 = _capi.Layout.padded(_up16(cout), h, w, k // 2)
+                g16 = _buffer_bf16(lg16, n, h, w, gy.device)
+                check(lib.rtpose_layout_f32_to_bf16(ptr(gbuf), C.byref(lg), ptr(g16), C.byref(lg16), cout, lg16.cstride,
+                                                    n, h, w, stream), "rtpose_layout_f32_to_bf16")
+            if need_x:
+                wp, bp = _packed_for(ctx.weight, None, 'bwd16', ctx.epoch, ctx.resync)
+                done = _launch_conv_bf16(g16, lg16, wp, bp, lg16.cstride, cin, k, False, n, h, w)
+                if done is None:
+                    bf16_fallbacks['dgrad'] += 1
+                    wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
+                    done = _launch_conv(gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
+                dx = _from_layout(done[0], done[1], n, cin, h, w)
+            if need_w or need_b:
+                dw, db = _wgrad_bf16(ctx.xbuf, ctx.lx, g16, lg16, ctx.weight, cin, cout, k, n, h, w, need_b)
+                if not need_w:
+                    dw = None
+        return dx, dw, db, None, None, None, da
+
+
+def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None, compute_dtype='fp32'):
     """``relu(conv2d(x, weight, bias, padding=k // 2))`` (ReLU only if `relu`) with the library's kernels in both directions;
     NCHW fp32 device tensors, k in {1, 3, 7}.  `epoch` (an int) is part of what the cached packings of `weight` are keyed
     by, `resync` packs anew in this forward and its backward: the owning model's weight epoch and ``always_resync``.
     `prelu`: an fp32 [cout] device tensor, the ``weight`` of an ``nn.PReLU(num_parameters=cout)`` applied to the conv's
-    output (exclusive with `relu`); read from its storage by every launch, never packed or cached."""
-    return _Conv2d.apply(x, weight, bias, bool(relu), int(epoch), bool(resync), prelu)
+    output (exclusive with `relu`); read from its storage by every launch, never packed or cached.
+    `compute_dtype`: 'fp32', or 'bf16' for bf16 operands of all three convs with fp32 accumulation (module docstring);
+    inputs, outputs, gradients and parameters are fp32 either way."""
+    _check_compute_dtype("train.conv2d", compute_dtype)
+    fn = _Conv2d if compute_dtype == 'fp32' else _Conv2dBf16
+    return fn.apply(x, weight, bias, bool(relu), int(epoch), bool(resync), prelu)
 
 
 # ---- the stacked hourglass: its stem and training-mode BatchNorm -------------------------------------------------------------
@@ -557,10 +731,11 @@ def _check_same_conv(m):
         raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
 
 
-def run_sequential(seq, x, epoch=0, resync=False):
+def run_sequential(seq, x, epoch=0, resync=False, compute_dtype='fp32'):
     """An nn.Sequential of the RtposeVGG / OpenPose_Model trees (nn.Conv2d [+ nn.ReLU | nn.PReLU] and
     nn.MaxPool2d(2, 2, 0)): the convs through ``conv2d`` with their ReLU or PReLU fused, the pools through torch.
-    `epoch` / `resync`: see ``conv2d``."""
+    `epoch` / `resync` / `compute_dtype`: see ``conv2d``."""
+    _check_compute_dtype("train.run_sequential", compute_dtype)
     mods = list(seq)
     i = 0
     while i < len(mods):
@@ -572,7 +747,7 @@ def run_sequential(seq, x, epoch=0, resync=False):
             if prelu and nxt.num_parameters != m.out_channels:
                 raise _capi.RtposeError("train: a PReLU behind a conv has one slope per output channel (num_parameters = %d); "
                                         "got %r behind %r" % (m.out_channels, nxt, m))
-            x = conv2d(x, m.weight, m.bias, relu, epoch, resync, nxt.weight if prelu else None)
+            x = conv2d(x, m.weight, m.bias, relu, epoch, resync, nxt.weight if prelu else None, compute_dtype)
             i += 2 if relu or prelu else 1
         elif isinstance(m, nn.MaxPool2d):
             x = F.max_pool2d(x, m.kernel_size, m.stride, m.padding)
@@ -585,45 +760,45 @@ def run_sequential(seq, x, epoch=0, resync=False):
     return x
 
 
-def _conv_block(blk, x, epoch, resync):
+def _conv_block(blk, x, epoch, resync, dt):
     """openpose.ConvBlock (reference :59-62): Mconv + MPrelu as one fused conv2d"""
-    return run_sequential([blk.Mconv, blk.MPrelu], x, epoch, resync)
+    return run_sequential([blk.Mconv, blk.MPrelu], x, epoch, resync, dt)
 
 
-def _stage_block(st, x, epoch, resync):
+def _stage_block(st, x, epoch, resync, dt):
     """openpose.StageBlock.forward of the reference (:86-109): five dense blocks of three ConvBlocks whose outputs are
     concatenated (torch.cat), the 1x1 ConvBlock Mconv6 and the 1x1 conv Mconv7."""
     for b in range(1, 6):
-        o1 = _conv_block(getattr(st, 'Mconv%d_0' % b), x, epoch, resync)
-        o2 = _conv_block(getattr(st, 'Mconv%d_1' % b), o1, epoch, resync)
-        o3 = _conv_block(getattr(st, 'Mconv%d_2' % b), o2, epoch, resync)
+        o1 = _conv_block(getattr(st, 'Mconv%d_0' % b), x, epoch, resync, dt)
+        o2 = _conv_block(getattr(st, 'Mconv%d_1' % b), o1, epoch, resync, dt)
+        o3 = _conv_block(getattr(st, 'Mconv%d_2' % b), o2, epoch, resync, dt)
         x = torch.cat([o1, o2, o3], 1)
-    return run_sequential([st.Mconv7], _conv_block(st.Mconv6, x, epoch, resync), epoch, resync)
+    return run_sequential([st.Mconv7], _conv_block(st.Mconv6, x, epoch, resync, dt), epoch, resync, dt)
 
 
-def _forward_train_vgg(model, x, epoch, resync):
+def _forward_train_vgg(model, x, epoch, resync, dt):
     saved_for_loss = []
-    out1 = run_sequential(model.model0, x, epoch, resync)
+    out1 = run_sequential(model.model0, x, epoch, resync, dt)
     feed = out1
     for s in range(1, 7):
-        o1 = run_sequential(getattr(model, 'model%d_1' % s), feed, epoch, resync)
-        o2 = run_sequential(getattr(model, 'model%d_2' % s), feed, epoch, resync)
+        o1 = run_sequential(getattr(model, 'model%d_1' % s), feed, epoch, resync, dt)
+        o2 = run_sequential(getattr(model, 'model%d_2' % s), feed, epoch, resync, dt)
         saved_for_loss += [o1, o2]
         if s < 6:
             feed = torch.cat([o1, o2, out1], 1)
     return (saved_for_loss[10], saved_for_loss[11]), saved_for_loss
 
 
-def _forward_train_openpose(model, x, epoch, resync):
-    features = run_sequential(model.feature_extractor, x, epoch, resync)
+def _forward_train_openpose(model, x, epoch, resync, dt):
+    features = run_sequential(model.feature_extractor, x, epoch, resync, dt)
     paf_ret, heat_ret = [], []
     x_in = features
     for st in model.l2_stages:
-        paf_pred = _stage_block(st, x_in, epoch, resync)
+        paf_pred = _stage_block(st, x_in, epoch, resync, dt)
         x_in = torch.cat([features, paf_pred], 1)
         paf_ret.append(paf_pred)
     for st in model.l1_stages:
-        heat_pred = _stage_block(st, x_in, epoch, resync)
+        heat_pred = _stage_block(st, x_in, epoch, resync, dt)
         x_in = torch.cat([features, heat_pred, paf_pred], 1)
         heat_ret.append(heat_pred)
     return [(paf_ret[-2], heat_ret[-2]), (paf_ret[-1], heat_ret[-1])], [paf_ret, heat_ret]
@@ -797,8 +972,10 @@ def _model_kind(model, who):
                     "shufflenet.Network; got %s" % (who, type(model).__name__))
 
 
-def forward_train(model, x):
+def forward_train(model, x, compute_dtype='fp32'):
     """The reference's forward over the module tree of `model`, with an autograd graph behind the outputs.
+    `compute_dtype`: 'fp32', or 'bf16' (``conv2d``) for an ``RtposeVGG`` or an ``OpenPose_Model``; refused for the other two,
+    whose BatchNorm and depthwise kernels are fp32.
     ``RtposeVGG`` (lib/network/rtpose_vgg.py:158-198): ((out6_1, out6_2), saved_for_loss[12]).
     ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177):
     ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]).
@@ -807,7 +984,12 @@ def forward_train(model, x):
     ``model.invalidate_weights()`` is called once.
     ``shufflenet.Network`` in training mode (``shufflenet_forward`` with ``conv2d``, ``batch_norm``, ``dwconv3x3`` and
     ``conv3x3_s2``): ([PAF, HEAT], [PAF, HEAT]); running statistics and ``invalidate_weights()`` as for the hourglass."""
+    _check_compute_dtype("train.forward_train", compute_dtype)
     kind = _model_kind(model, "train.forward_train")
+    if compute_dtype != 'fp32' and kind in ('hourglass', 'shufflenet'):
+        raise _capi.RtposeError("train.forward_train: compute_dtype=%r is for a network.RtposeVGG or an openpose.OpenPose_Model; "
+                                "the BatchNorm%s kernels a %s trains through are fp32 and take no compute dtype"
+                                % (compute_dtype, " and depthwise" if kind == 'shufflenet' else "", type(model).__name__))
     if not x.is_cuda:
         raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
                                 "deliberately no CPU fallback" % (x.device,))
@@ -817,7 +999,7 @@ def forward_train(model, x):
     if kind == 'shufflenet':
         return _forward_train_shufflenet(model, x)
     epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
-    return (_forward_train_vgg if kind == 'vgg' else _forward_train_openpose)(model, x, epoch, resync)
+    return (_forward_train_vgg if kind == 'vgg' else _forward_train_openpose)(model, x, epoch, resync, compute_dtype)
 
 
 def freeze_trunk(model, n=20):
@@ -837,17 +1019,18 @@ def freeze_trunk(model, n=20):
     return model
 
 
-def train_step(model, optimizer, image, heat, paf, heat_mask=None, paf_mask=None):
+def train_step(model, optimizer, image, heat, paf, heat_mask=None, paf_mask=None, compute_dtype='fp32'):
     """One iteration of train/train_VGG19.py:206-217: (total_loss, saved_for_log).  The loss is ``encode.get_loss`` for an
     RtposeVGG, ``encode.get_loss_openpose`` for an OpenPose_Model and, for a HourglassNet (train/train_SH.py:160-172),
     ``encode.get_loss_hourglass`` with the optional `heat_mask` / `paf_mask` (None: ones), for a shufflenet.Network
     (train/train_ShuffleNetV2.py:144-156) ``encode.get_loss_shufflenet`` with the same masks; the masks belong to those two
-    losses only."""
+    losses only.  `compute_dtype`: see ``forward_train``; the optimizer steps the fp32 parameters either way."""
+    _check_compute_dtype("train.train_step", compute_dtype)
     kind = _model_kind(model, "train.train_step")
     if kind not in ('hourglass', 'shufflenet') and (heat_mask is not None or paf_mask is not None):
         raise TypeError("train.train_step: heat_mask / paf_mask belong to the HourglassNet and shufflenet.Network losses "
                         "(encode.get_loss_hourglass, encode.get_loss_shufflenet)")
-    _, saved_for_loss = forward_train(model, image)
+    _, saved_for_loss = forward_train(model, image, compute_dtype)
     if kind == 'hourglass':
         total_loss, saved_for_log = encode.get_loss_hourglass(saved_for_loss, heat, heat_mask, paf, paf_mask)
     elif kind == 'shufflenet':
