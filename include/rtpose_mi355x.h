@@ -199,6 +199,21 @@ int rtpose_conv2d_wgrad(const rtpose_wgrad_desc* d, int N, int H, int W, void* s
  * zero bias) of gy with the filter w.flip(2, 3).transpose(0, 1), packed by rtpose_pack_conv_weights. */
 int rtpose_relu_grad(const float* y, const rtpose_layout* ly, const float* gy, const rtpose_layout* lgy,
                      float* out, const rtpose_layout* lout, int channels, int N, int H, int W, void* stream);
+/* The same gradient on bf16 slices (csrc/act_grad_bf16.hip), for a training run whose activations and gradients stay in
+ * the layouts between convs: y, gy and out are 2-byte bf16 slices and their layouts count ELEMENTS.  `y` is the conv's
+ * output as rtpose_conv2d_bf16(out_f32 = 0) stored it - the buffer the next conv read; no other copy of y is needed -,
+ * `ly` and `lgy` may differ in every field (gaps of 1 and 3, say).  Gaps and the channels beside the slices are neither
+ * read nor written; every element reads only its own y and gy element, so out / lout may name the slice gy / lgy name.
+ * The comparison is on the bf16 value: +0, -0, NaN and every negative y give +0; any other y - subnormals and +Inf
+ * included - passes gy's 16 bits through untouched, NaN and Inf included.  This is where the pass can differ from
+ * rtpose_relu_grad on the fp32 y the conv accumulated: 0 < y <= 2^-134 rounds to a bf16 +0 and masks the gradient here.
+ * 16-byte loads and stores (8 bf16) where every base is 16-byte aligned and every cstride and choff a multiple of 8,
+ * element by element otherwise: the same bits either way.  Every argument is checked on the host before any HIP call
+ * (RTPOSE_E_INVAL with a text): NULL pointers or layouts, channels / N / H / W < 1, choff + channels > cstride, a layout
+ * smaller than the map, N * H * W above the launch limit of 2^31 - 256 pixels, an odd base, and an `out` whose bytes
+ * overlap those of gy or y without being the same slice (disjoint channel slices of one buffer are fine). */
+int rtpose_relu_grad_bf16(const void* y, const rtpose_layout* ly, const void* gy, const rtpose_layout* lgy, void* out,
+                          const rtpose_layout* lout, int channels, int N, int H, int W, void* stream);
 
 /* ---- 2b, continued.  PReLU as a pass of its own, for training (csrc/prelu_backward.hip).  The conv launchers fuse
  * nn.PReLU(num_parameters = cout) into their epilogue (rtpose_conv_desc.prelu) and keep only its output; slopes may have

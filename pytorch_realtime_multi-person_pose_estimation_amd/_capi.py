@@ -249,6 +249,7 @@ _SIGS = {
     "rtpose_conv2d_wgrad_bf16_slabs": (_i, [_i, _i, _i, _i, _i, _i]),
     "rtpose_conv2d_wgrad_bf16": (_i, [C.POINTER(WgradBf16Desc), _i, _i, _i, _vp]),
     "rtpose_relu_grad": (_i, [_vp, _LP, _vp, _LP, _vp, _LP, _i, _i, _i, _i, _vp]),
+    "rtpose_relu_grad_bf16": (_i, [_vp, _LP, _vp, _LP, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_prelu": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _vp]),
     "rtpose_prelu_grad_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "rtpose_prelu_grad_slabs": (_i, [_i, _i, _i, _i]),

@@ -54,7 +54,13 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   ``rtpose_conv2d_wgrad_bf16``.  A shape ``rtpose_conv2d_bf16`` refuses (it refuses before launching) runs that direction of
   that conv on the fp32 path and is counted in ``bf16_fallbacks``.  The default ``'fp32'`` is the path above, launch for launch.
 
-The NCHW <-> layout conversion around every operation is known overhead; activations do not stay in layouts across layers yet.
+* Layout-resident runs (``conv_chain``; ``resident=True`` of ``run_sequential``, ``forward_train`` and ``train_step``, RtposeVGG
+  only): a run of convs with one consumer each is one autograd node; its inner activations and gradients stay in the gapped
+  layout buffers (bf16 ones for ``compute_dtype='bf16'``: ``rtpose_conv2d_bf16(out_f32=0)`` forward and data gradient,
+  ``rtpose_relu_grad_bf16`` in place), and NCHW fp32 exists only where the run begins and ends.  Opt-in; the default is the
+  per-conv path, launch for launch.
+
+On the default path the NCHW <-> layout conversion around every operation is known overhead.
 """
 import ctypes as C
 import weakref
@@ -458,6 +464,234 @@ def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None, 
     return fn.apply(x, weight, bias, bool(relu), int(epoch), bool(resync), prelu)
 
 
+# ---- a run of convs as one autograd node: the inner activations and gradients stay in the layouts ---------------------------------
+# chains of a compute_dtype='bf16' run that gave up residency because rtpose_conv2d_bf16 refused one of their forward convs
+chain_fallbacks = 0
+
+
+def reset_chain_fallbacks():
+    global chain_fallbacks
+    chain_fallbacks = 0
+
+
+class _ChainRefused(Exception):
+    """rtpose_conv2d_bf16 refused a forward conv of a chain (before any launch of that conv)"""
+
+
+def _conv_into(bf16, inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w, out, lout, out_f32=0):
+    """One conv of a layout buffer into the slice out / lout: rtpose_conv2d, or rtpose_conv2d_bf16 writing bf16 (out_f32 = 0)
+    or fp32.  True, or False if the bf16 launcher refused the shape (RTPOSE_E_INVAL: returned before any launch)."""
+    d = _capi.ConvDesc()
+    d.inp, d.w_packed, d.bias_packed, d.out = inp.data_ptr(), wp.data_ptr(), bp.data_ptr(), out.data_ptr()
+    d.lin, d.lout = lin, lout
+    d.cin, d.cout, d.k, d.relu = cin_p, cout, k, 1 if relu else 0
+    if not bf16:
+        check(lib.rtpose_conv2d(C.byref(d), 1, n, h, w, current_stream()), "rtpose_conv2d")
+        return True
+    rc = lib.rtpose_conv2d_bf16(C.byref(d), 1, n, h, w, 1 if out_f32 else 0, current_stream())
+    if rc == -1:
+        return False
+    check(rc, "rtpose_conv2d_bf16")
+    return True
+
+
+def _check_chain(x, layers):
+    if len(layers) < 1:
+        raise _capi.RtposeError("train.conv_chain: no layers")
+    c = x.shape[1] if torch.is_tensor(x) and x.dim() == 4 else None
+    for i, layer in enumerate(layers):
+        if not isinstance(layer, (tuple, list)) or len(layer) != 3 or not torch.is_tensor(layer[0]):
+            raise _capi.RtposeError("train.conv_chain: layers are (weight, bias_or_None, relu) triples; got %r at %d"
+                                    % (type(layer).__name__, i))
+        weight, bias, _ = layer
+        if i == 0:
+            _check_input(x, weight)
+        _require_device("train.conv_chain", weight, names=("a weight",))
+        k = weight.shape[2] if weight.dim() == 4 else 0
+        if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[3] != k or k not in (1, 3, 7) or weight.shape[1] != c:
+            raise _capi.RtposeError("train.conv_chain: layer %d: stride-1 'same' convs with fp32 OIHW filters, k in {1, 3, 7}, "
+                                    "whose input channels are the output channels of the layer before (%s); got filters %s %s"
+                                    % (i, c, weight.dtype, tuple(weight.shape)))
+        if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (weight.shape[0],)
+                                 or bias.device != weight.device):
+            raise _capi.RtposeError("train.conv_chain: layer %d: the bias is None or an fp32 [%d] tensor beside the filters"
+                                    % (i, weight.shape[0]))
+        c = weight.shape[0]
+
+
+class _ConvChain(torch.autograd.Function):
+    """conv_chain's node.  Inputs: x, (relus, epoch, resync, bf16), then weight and bias (or None) of every layer."""
+    @staticmethod
+    def forward(ctx, x, meta, *params):
+        relus, epoch, resync, bf16 = meta
+        weights, biases = params[0::2], params[1::2]
+        L = len(weights)
+        up = _up16 if bf16 else _up8
+        fwd = 'fwd16' if bf16 else 'fwd'
+        with torch.cuda.device(x.device):
+            n, _, h, w = x.shape
+            ks = [wt.shape[2] for wt in weights]
+            couts = [wt.shape[0] for wt in weights]
+            buf, lay = (_to_layout_bf16 if bf16 else _to_layout)(x.detach().contiguous(), ks[0] // 2)
+            bufs, lays = [buf], [lay]
+            for i in range(L):
+                wp, bp = _packed_for(weights[i], biases[i], fwd, epoch, resync)
+                if i + 1 < L:    # zero gaps for the next conv's padding; zero pad channels (the conv writes cout channels only)
+                    lout = _capi.Layout.padded(up(couts[i]), h, w, ks[i + 1] // 2)
+                    out = _buffer_bf16(lout, n, h, w, x.device) if bf16 else _buffer(lout, n, h, w, x.device, True)
+                else:
+                    lout = _capi.Layout.dense(_up8(couts[i]), h, w)
+                    out = _buffer(lout, n, h, w, x.device, False)
+                if not _conv_into(bf16, bufs[i], lays[i], wp, bp, lays[i].cstride, couts[i], ks[i], relus[i], n, h, w, out, lout,
+                                  out_f32=i + 1 == L):
+                    raise _ChainRefused()
+                bufs.append(out)
+                lays.append(lout)
+            y = _from_layout(bufs[L], lays[L], n, couts[L - 1], h, w)
+        need_x = ctx.needs_input_grad[0]
+        wants = [ctx.needs_input_grad[2 + 2 * i] or (biases[i] is not None and ctx.needs_input_grad[3 + 2 * i]) for i in range(L)]
+        # the lowest layer whose backward anything needs: the walk stops there
+        low = 0 if need_x else next((i for i in range(L) if wants[i]), L)
+        ctx.geom = (n, h, w)
+        ctx.meta = meta
+        ctx.weights = weights
+        ctx.has_bias = [b is not None for b in biases]
+        ctx.low, ctx.wants = low, wants
+        ctx.save_for_backward(*weights)   # (for autograd's check that the filters were not modified in place since)
+        # per layer only the input buffer, where the weight gradient or the mask of the layer below reads it; of the last
+        # layer's fp32 output only what a ReLU behind it needs
+        keep = [low < L and (wants[i] or (i > low and relus[i - 1])) for i in range(L)] + [low < L and relus[L - 1]]
+        ctx.bufs = [b if kp else None for b, kp in zip(bufs, keep)]
+        ctx.lays = lays
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        relus, epoch, resync, bf16 = ctx.meta
+        ctx.saved_tensors
+        weights, bufs, lays, low, wants = ctx.weights, ctx.bufs, ctx.lays, ctx.low, ctx.wants
+        L = len(weights)
+        n, h, w = ctx.geom
+        need_x = ctx.needs_input_grad[0]
+        up = _up16 if bf16 else _up8
+        bwd = 'bwd16' if bf16 else 'bwd'
+        grads = [None] * (2 * L)
+        dx = None
+        if low >= L:
+            return (None, None) + tuple(grads)
+        with torch.cuda.device(gy.device):
+            stream = current_stream()
+            dev = gy.device
+            gyc = gy.detach().float().contiguous()
+            k, cout = weights[L - 1].shape[2], weights[L - 1].shape[0]
+            if relus[L - 1] or not bf16:
+                g, lg = _to_layout(gyc, k // 2)
+                if relus[L - 1]:     # a ReLU behind the last conv: masked by the fp32 output, as conv2d does
+                    check(lib.rtpose_relu_grad(ptr(bufs[L]), C.byref(lays[L]), ptr(g), C.byref(lg), ptr(g), C.byref(lg), cout,
+                                               n, h, w, stream), "rtpose_relu_grad")
+                if bf16:
+                    lg16 = _capi.Layout.padded(_up16(cout), h, w, k // 2)
+                    g16 = _buffer_bf16(lg16, n, h, w, dev)
+                    check(lib.rtpose_layout_f32_to_bf16(ptr(g), C.byref(lg), ptr(g16), C.byref(lg16), cout, lg16.cstride,
+                                                        n, h, w, stream), "rtpose_layout_f32_to_bf16")
+                    g, lg = g16, lg16
+            else:
+                g, lg = _to_layout_bf16(gyc, k // 2)
+            for i in range(L - 1, low - 1, -1):
+                wt = weights[i]
+                cout, cin, k = wt.shape[0], wt.shape[1], wt.shape[2]
+                if wants[i]:
+                    need_b = ctx.has_bias[i] and ctx.needs_input_grad[3 + 2 * i]
+                    dw, db = (_wgrad_bf16 if bf16 else _wgrad)(bufs[i], lays[i], g, lg, wt, cin, cout, k, n, h, w, need_b)
+                    grads[2 * i] = dw if ctx.needs_input_grad[2 + 2 * i] else None
+                    grads[2 * i + 1] = db
+                if i == low and not (i == 0 and need_x):
+                    break
+                # the data gradient: the conv of g on the flipped, transposed filter, straight into the buffer the layer
+                # below reads its output gradient from (gapped for that layer), or into a dense fp32 one for dx
+                wp, bp = _packed_for(wt, None, bwd, epoch, resync)
+                if i > 0:
+                    ld = _capi.Layout.padded(up(cin), h, w, weights[i - 1].shape[2] // 2)
+                    d = _buffer_bf16(ld, n, h, w, dev) if bf16 else _buffer(ld, n, h, w, dev, True)
+                else:
+                    ld = _capi.Layout.dense(_up8(cin), h, w)
+                    d = _buffer(ld, n, h, w, dev, False)
+                if not _conv_into(bf16, g, lg, wp, bp, lg.cstride, cin, k, False, n, h, w, d, ld, out_f32=i == 0):
+                    # refused: this one conv in fp32 on the widened gradient, rounded again at its store inside the chain
+                    bf16_fallbacks['dgrad'] += 1
+                    l32 = _capi.Layout.padded(_up8(cout), h, w, k // 2)
+                    g32 = _buffer(l32, n, h, w, dev, True)
+                    check(lib.rtpose_layout_bf16_to_f32(ptr(g), C.byref(lg), ptr(g32), C.byref(l32), cout, n, h, w, stream),
+                          "rtpose_layout_bf16_to_f32")
+                    wp, bp = _packed_for(wt, None, 'bwd', epoch, resync)
+                    d32, ld32 = _launch_conv(g32, l32, wp, bp, l32.cstride, cin, k, False, n, h, w)
+                    if i > 0:
+                        check(lib.rtpose_layout_f32_to_bf16(ptr(d32), C.byref(ld32), ptr(d), C.byref(ld), cin, ld.cstride,
+                                                            n, h, w, stream), "rtpose_layout_f32_to_bf16")
+                    else:
+                        d, ld = d32, ld32
+                if i == 0:
+                    dx = _from_layout(d, ld, n, cin, h, w)
+                    break
+                if relus[i - 1]:     # in place, by the layer below's output as stored: this layer's kept input buffer
+                    if bf16:
+                        check(lib.rtpose_relu_grad_bf16(ptr(bufs[i]), C.byref(lays[i]), ptr(d), C.byref(ld), ptr(d), C.byref(ld),
+                                                        cin, n, h, w, stream), "rtpose_relu_grad_bf16")
+                    else:
+                        check(lib.rtpose_relu_grad(ptr(bufs[i]), C.byref(lays[i]), ptr(d), C.byref(ld), ptr(d), C.byref(ld),
+                                                   cin, n, h, w, stream), "rtpose_relu_grad")
+                g, lg = d, ld
+        return (dx, None) + tuple(grads)
+
+
+def conv_chain(x, layers, epoch=0, resync=False, compute_dtype='fp32'):
+    """A run of stride-1 "same" convs, each read by the next alone, as ONE autograd node whose inner activations and
+    gradients never leave the library's layouts.  `layers`: a sequence of (weight, bias_or_None, relu), k in {1, 3, 7},
+    every layer's input channels the output channels of the one before; `x` NCHW fp32 on the device; the result is the last
+    conv's output (after its ReLU, if it has one), NCHW fp32.  `epoch` / `resync` / `compute_dtype`: see ``conv2d``; the
+    packings are the same cached ones.
+
+    Forward: x is converted once into a buffer gapped for layer 0; every inner conv writes into a zero-initialised buffer
+    gapped by the next layer's k // 2 with the channels padded as that layer reads them (16 for bf16, 8 for fp32; the
+    conv writes its cout channels only, so the pad channels stay zero) - ``rtpose_conv2d_bf16(out_f32 = 0)`` or
+    ``rtpose_conv2d``; the last conv writes fp32 into a dense buffer, and one ``rtpose_layout_to_nchw`` leaves.
+    Backward: gy is converted once (``rtpose_nchw_to_layout_bf16`` / ``rtpose_nchw_to_layout``); then, from the last layer
+    down to the lowest one anything still needs: the weight and bias gradients from the kept input buffer and the current
+    gradient buffer (if that layer's parameters want them), the data gradient as the conv on the cached 'bwd16' / 'bwd'
+    packing straight into a buffer gapped for the layer below (``out_f32 = 0``), masked in place by that layer's ReLU with
+    ``rtpose_relu_grad_bf16`` / ``rtpose_relu_grad`` against the kept input buffer of the current layer - the layer below's
+    output as stored.  The first layer's data gradient leaves as fp32 NCHW, only if x needs one.  Per layer only the input
+    buffer is kept; no fp32 copy of an inner y and no NCHW intermediate exists.  A ReLU behind the LAST conv is masked as
+    ``conv2d`` masks it, by the kept fp32 output, before the gradient's one rounding.
+
+    The rounding points are ``conv2d(compute_dtype='bf16')``'s: an activation rounded at the conv's store is what the next
+    conv's input conversion produced, a data gradient rounded at the store and then masked is the masked fp32 gradient
+    rounded.  Two differences remain: the mask is taken from y rounded to bf16, so an activation 0 < y <= 2^-134 (which bf16
+    rounds to +0) masks its gradient here and not there; and ``out_f32 = 0`` may reach another kernel instance (the
+    64-input-channel 3x3 kernel takes only such launches) whose fp32 sums run in another order.  On exact integer operands
+    the two forms are equal bit for bit.
+
+    A forward conv ``rtpose_conv2d_bf16`` refuses (before launching) makes the chain give up residency: it runs layer by layer
+    through ``conv2d`` (whose own fallback counters apply) and ``chain_fallbacks`` counts it.  A refused data gradient runs
+    that one conv in fp32 on the widened gradient (``rtpose_layout_bf16_to_f32``) and is counted in
+    ``bf16_fallbacks['dgrad']``; inside the chain its result is rounded to bf16 at the store like every other, and its
+    operand is the gradient already rounded - so its bits differ from the per-conv fallback's, which convolves the fp32
+    masked gradient."""
+    global chain_fallbacks
+    _check_compute_dtype("train.conv_chain", compute_dtype)
+    layers = [tuple(layer) if isinstance(layer, (tuple, list)) else layer for layer in layers]
+    _check_chain(x, layers)
+    meta = (tuple(bool(r) for _, _, r in layers), int(epoch), bool(resync), compute_dtype == 'bf16')
+    try:
+        return _ConvChain.apply(x, meta, *[p for wt, b, _ in layers for p in (wt, b)])
+    except _ChainRefused:
+        chain_fallbacks += 1
+    for wt, b, relu in layers:
+        x = conv2d(x, wt, b, relu, epoch, resync, None, compute_dtype)
+    return x
+
+
 # ---- the stacked hourglass: its stem and training-mode BatchNorm -------------------------------------------------------------
 class _Conv7x7S2(torch.autograd.Function):
     @staticmethod
@@ -731,15 +965,32 @@ def _check_same_conv(m):
         raise _capi.RtposeError("train: only stride-1 'same' convs have a backward here; got %r" % (m,))
 
 
-def run_sequential(seq, x, epoch=0, resync=False, compute_dtype='fp32'):
+def run_sequential(seq, x, epoch=0, resync=False, compute_dtype='fp32', resident=False):
     """An nn.Sequential of the RtposeVGG / OpenPose_Model trees (nn.Conv2d [+ nn.ReLU | nn.PReLU] and
     nn.MaxPool2d(2, 2, 0)): the convs through ``conv2d`` with their ReLU or PReLU fused, the pools through torch.
-    `epoch` / `resync` / `compute_dtype`: see ``conv2d``."""
+    `epoch` / `resync` / `compute_dtype`: see ``conv2d``.  `resident`: every maximal run of nn.Conv2d (+ nn.ReLU) goes to
+    ``conv_chain`` as one node (a run of one conv to ``conv2d``); a conv with a PReLU ends a run and stays ``conv2d``'s."""
     _check_compute_dtype("train.run_sequential", compute_dtype)
     mods = list(seq)
     i = 0
     while i < len(mods):
         m = mods[i]
+        if resident and isinstance(m, nn.Conv2d):
+            run = []
+            while i < len(mods) and isinstance(mods[i], nn.Conv2d):
+                nxt = mods[i + 1] if i + 1 < len(mods) else None
+                if isinstance(nxt, nn.PReLU):
+                    break
+                _check_same_conv(mods[i])
+                run.append((mods[i].weight, mods[i].bias, isinstance(nxt, nn.ReLU)))
+                i += 2 if isinstance(nxt, nn.ReLU) else 1
+            if len(run) > 1:
+                x = conv_chain(x, run, epoch, resync, compute_dtype)
+                continue
+            if len(run) == 1:
+                x = conv2d(x, run[0][0], run[0][1], run[0][2], epoch, resync, None, compute_dtype)
+                continue
+            m = mods[i]     # a conv with a PReLU: below
         if isinstance(m, nn.Conv2d):
             _check_same_conv(m)
             nxt = mods[i + 1] if i + 1 < len(mods) else None
@@ -776,13 +1027,15 @@ def _stage_block(st, x, epoch, resync, dt):
     return run_sequential([st.Mconv7], _conv_block(st.Mconv6, x, epoch, resync, dt), epoch, resync, dt)
 
 
-def _forward_train_vgg(model, x, epoch, resync, dt):
+def _forward_train_vgg(model, x, epoch, resync, dt, resident=False):
+    """`resident`: model0 between the pools and each of the twelve stage branches as one ``conv_chain`` node; the pools and
+    the torch.cat between the stages stay torch's"""
     saved_for_loss = []
-    out1 = run_sequential(model.model0, x, epoch, resync, dt)
+    out1 = run_sequential(model.model0, x, epoch, resync, dt, resident)
     feed = out1
     for s in range(1, 7):
-        o1 = run_sequential(getattr(model, 'model%d_1' % s), feed, epoch, resync, dt)
-        o2 = run_sequential(getattr(model, 'model%d_2' % s), feed, epoch, resync, dt)
+        o1 = run_sequential(getattr(model, 'model%d_1' % s), feed, epoch, resync, dt, resident)
+        o2 = run_sequential(getattr(model, 'model%d_2' % s), feed, epoch, resync, dt, resident)
         saved_for_loss += [o1, o2]
         if s < 6:
             feed = torch.cat([o1, o2, out1], 1)
@@ -972,10 +1225,27 @@ def _model_kind(model, who):
                     "shufflenet.Network; got %s" % (who, type(model).__name__))
 
 
-def forward_train(model, x, compute_dtype='fp32'):
+# why forward_train(resident=True) refuses the networks that are not an RtposeVGG
+_NOT_RESIDENT = {
+    'openpose': "an openpose.OpenPose_Model's PReLU needs the fp32 pre-activation of every conv, and its dense blocks give an "
+                "activation two consumers, whose gradients would have to be summed in the layouts (conv_chain runs convs with "
+                "one consumer and a ReLU or no activation)",
+    'hourglass': "a HourglassNet trains through BatchNorm kernels between its convs and residual sums, which are fp32 passes "
+                 "on NCHW tensors at the autograd boundary (conv_chain runs convs with one consumer and a ReLU or no "
+                 "activation)",
+    'shufflenet': "a shufflenet.Network trains through BatchNorm and depthwise kernels between its convs, which are fp32 "
+                  "passes on NCHW tensors at the autograd boundary (conv_chain runs convs with one consumer and a ReLU or no "
+                  "activation)",
+}
+
+
+def forward_train(model, x, compute_dtype='fp32', resident=False):
     """The reference's forward over the module tree of `model`, with an autograd graph behind the outputs.
     `compute_dtype`: 'fp32', or 'bf16' (``conv2d``) for an ``RtposeVGG`` or an ``OpenPose_Model``; refused for the other two,
     whose BatchNorm and depthwise kernels are fp32.
+    `resident`: for an ``RtposeVGG`` only - every run of convs between two pools of model0 and each stage branch is one
+    ``conv_chain`` node whose inner activations and gradients stay in the layouts; refused for the other three (why: the
+    message).  The default False is the per-conv path, launch for launch.
     ``RtposeVGG`` (lib/network/rtpose_vgg.py:158-198): ((out6_1, out6_2), saved_for_loss[12]).
     ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177):
     ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]).
@@ -990,6 +1260,8 @@ def forward_train(model, x, compute_dtype='fp32'):
         raise _capi.RtposeError("train.forward_train: compute_dtype=%r is for a network.RtposeVGG or an openpose.OpenPose_Model; "
                                 "the BatchNorm%s kernels a %s trains through are fp32 and take no compute dtype"
                                 % (compute_dtype, " and depthwise" if kind == 'shufflenet' else "", type(model).__name__))
+    if resident and kind != 'vgg':
+        raise _capi.RtposeError("train.forward_train: resident=True is for a network.RtposeVGG only; " + _NOT_RESIDENT[kind])
     if not x.is_cuda:
         raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
                                 "deliberately no CPU fallback" % (x.device,))
@@ -999,7 +1271,9 @@ def forward_train(model, x, compute_dtype='fp32'):
     if kind == 'shufflenet':
         return _forward_train_shufflenet(model, x)
     epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
-    return (_forward_train_vgg if kind == 'vgg' else _forward_train_openpose)(model, x, epoch, resync, compute_dtype)
+    if kind == 'vgg':
+        return _forward_train_vgg(model, x, epoch, resync, compute_dtype, bool(resident))
+    return _forward_train_openpose(model, x, epoch, resync, compute_dtype)
 
 
 def freeze_trunk(model, n=20):
@@ -1019,18 +1293,18 @@ def freeze_trunk(model, n=20):
     return model
 
 
-def train_step(model, optimizer, image, heat, paf, heat_mask=None, paf_mask=None, compute_dtype='fp32'):
+def train_step(model, optimizer, image, heat, paf, heat_mask=None, paf_mask=None, compute_dtype='fp32', resident=False):
     """One iteration of train/train_VGG19.py:206-217: (total_loss, saved_for_log).  The loss is ``encode.get_loss`` for an
     RtposeVGG, ``encode.get_loss_openpose`` for an OpenPose_Model and, for a HourglassNet (train/train_SH.py:160-172),
     ``encode.get_loss_hourglass`` with the optional `heat_mask` / `paf_mask` (None: ones), for a shufflenet.Network
     (train/train_ShuffleNetV2.py:144-156) ``encode.get_loss_shufflenet`` with the same masks; the masks belong to those two
-    losses only.  `compute_dtype`: see ``forward_train``; the optimizer steps the fp32 parameters either way."""
+    losses only.  `compute_dtype` / `resident`: see ``forward_train``; the optimizer steps the fp32 parameters either way."""
     _check_compute_dtype("train.train_step", compute_dtype)
     kind = _model_kind(model, "train.train_step")
     if kind not in ('hourglass', 'shufflenet') and (heat_mask is not None or paf_mask is not None):
         raise TypeError("train.train_step: heat_mask / paf_mask belong to the HourglassNet and shufflenet.Network losses "
                         "(encode.get_loss_hourglass, encode.get_loss_shufflenet)")
-    _, saved_for_loss = forward_train(model, image, compute_dtype)
+    _, saved_for_loss = forward_train(model, image, compute_dtype, resident)
     if kind == 'hourglass':
         total_loss, saved_for_log = encode.get_loss_hourglass(saved_for_loss, heat, heat_mask, paf, paf_mask)
     elif kind == 'shufflenet':
