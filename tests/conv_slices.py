@@ -92,9 +92,11 @@ TINY_F32 = [
 
 # the smallest geometries of the existing case tables (tests/test_conv_gpu.py) that select a launcher's main / persistent
 # form: bit identity only, no CPU reference.  (k, wino_m, n, h, w, cin, cout, relu, pool, groups)
+# (what each Winograd row of the two tables launches on 256 CUs: tests/wino_cases.py, SLICES)
 LARGE_F32 = [
     (3, None, 1, 100, 92, 128, 256, 1, 0, 1),   # direct 3x3: 2-D tiles with ragged right / bottom edges
     (7, None, 1, 70, 66, 128, 128, 1, 0, 1),    # direct 7x7 in 2-D tile mode
     (3, 2, 9, 46, 46, 256, 512, 1, 0, 1),       # F(2x2,3x3): whole 32 x 128 tiles (wino_f32)
-    (3, 4, 40, 46, 46, 64, 128, 1, 0, 1),       # F(4x4,3x3): persistent blocks
-] + [(7, m, 12, 46, 46, 128, 128, 1, 0, 2) for m in (4, 6, 8)]   # F(m,7): two branches, persistent split tiles with a scratch
+    (3, 4, 40, 46, 46, 64, 128, 1, 0, 1),       # F(4x4,3x3): persistent blocks + a round of half tiles
+] + [(7, m, 12, 46, 46, 128, 128, 1, 0, 2) for m in (4, 6, 8)]   # F(m,7): two branches; persistent split tiles with a scratch for
+#                                                                  m = 4 (336 tiles) and 6 (288); m = 8 is 216 tiles: one block each

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 import conv_driver as cd
 import layout_restate as lr
+import wino_cases as wc
 
 pytestmark = pytest.mark.gpu
 
@@ -60,18 +61,9 @@ def test_grouped_branches(capi, cuda):
         assert (o - r).abs().max().item() <= TOL * max(1.0, r.abs().max().item())
 
 
-WINO7_CASES = [
-    # n, h, w, cin (packed), cout, relu, pad_in, pad_out      (k = 7; csrc/conv_wino7.hip, F(6,7): groups of 6 pixels)
-    (2, 46, 46, 128, 128, 1, 3, 3),      # Mconv2_stageN: 8 position groups per row (W % 6 == 4), strips per image
-    (1, 46, 49, 192, 128, 1, 3, 3),      # ski.jpg geometry (46x49), 185 -> 192 packed input, W % 6 == 1
-    (3, 23, 18, 64, 256, 0, 3, 0),       # W % 6 == 0, two N tiles, no ReLU, strips crossing images
-    (5, 6, 7, 16, 128, 1, 3, 3),         # tiny maps: a block spans several images (W % 6 == 1)
-    (2, 20, 27, 32, 128, 1, 3, 3),       # W % 6 == 3
-    (1, 17, 35, 8, 128, 0, 3, 1),        # W % 6 == 5, one chunk
-    (1, 30, 44, 24, 128, 1, 3, 0),       # W % 6 == 2
-    (1, 70, 66, 128, 128, 1, 3, 0),      # multi-scale map, wider rows
-    (1, 9, 80, 8, 128, 1, 4, 1),         # one chunk; 20 groups per row; gap wider than the padding
-]
+# The Winograd case tables live in tests/wino_cases.py, each row beside the launch it selects on 256 CUs (asserted on the CPU
+# by tests/test_wino_reach_cpu.py); the rows are run here as they always were.
+WINO7_CASES = [row for _, row in wc.WINO7_CASES]      # n, h, w, cin (packed), cout, relu, pad_in, pad_out; k = 7, F(6,7)
 
 
 @pytest.mark.parametrize("case", WINO7_CASES)
@@ -86,8 +78,8 @@ def test_winograd7_matches_torch_cpu(capi, cuda, case):
 
 
 def test_winograd7_grouped_branches_and_direct_agree(capi, cuda):
-    outs, refs = _run_conv(capi, cuda, 2, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=7, groups=2, winograd=True)
-    direct, _ = _run_conv(capi, cuda, 2, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=7, groups=2)
+    outs, refs = _run_conv(capi, cuda, *wc.W7_STAGE, 7, 1, 0, 3, 3, seed=7, groups=2, winograd=True)
+    direct, _ = _run_conv(capi, cuda, *wc.W7_STAGE, 7, 1, 0, 3, 3, seed=7, groups=2)
     for o, r, d in zip(outs, refs, direct):
         assert (o - r).abs().max().item() <= TOL * max(1.0, r.abs().max().item())
         assert (o - d).abs().max().item() <= 1e-4 * max(1.0, r.abs().max().item())
@@ -98,19 +90,19 @@ def test_winograd7_persistent_blocks_split_tiles(capi, cuda):
     (tile, chunk) units evenly, most tiles are split between two blocks (conv_wino7.hip: wino7_f32).  The second
     block continues the first one's sums, so the result is BIT-identical to the one-block-per-tile launch of a
     smaller batch of the same images; run twice: the hand-over flags are back to zero after a launch."""
-    outs, refs = _run_conv(capi, cuda, 12, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True)
-    again, _ = _run_conv(capi, cuda, 12, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True)
+    outs, refs = _run_conv(capi, cuda, *wc.W7_PERSIST, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True)
+    again, _ = _run_conv(capi, cuda, *wc.W7_PERSIST, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True)
     for o, r, o2 in zip(outs, refs, again):
         assert (o - r).abs().max().item() <= TOL * max(1.0, r.abs().max().item())
         assert torch.equal(o, o2)
     # same generator stream: the first 2 images / both filters of an n = 2 run are those of the n = 8 run? no -
     # the inputs are drawn as one (n, c, h, w) tensor, so re-run the FIRST image alone through a slice instead
-    small, _ = _run_conv(capi, cuda, 12, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True,
-                         only_images=3)
+    small, _ = _run_conv(capi, cuda, *wc.W7_PERSIST, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True,
+                         only_images=wc.W7_PERSIST_HEAD)
     for o, sm in zip(outs, small):
-        assert torch.equal(o[:3], sm)
+        assert torch.equal(o[:wc.W7_PERSIST_HEAD], sm)
     # without a scratch the same launch runs one block per tile: the same bits again
-    plain, _ = _run_conv(capi, cuda, 12, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True,
+    plain, _ = _run_conv(capi, cuda, *wc.W7_PERSIST, 7, 1, 0, 3, 3, seed=11, groups=2, winograd=True,
                          scratch=False, skip_ref=True)
     for o, pl in zip(outs, plain):
         assert torch.equal(o, pl)
@@ -119,16 +111,16 @@ def test_winograd7_persistent_blocks_split_tiles(capi, cuda):
 def test_winograd7_f47_form_selected_per_launch(capi, cuda):
     """rtpose_conv_desc.wino_m = 4 with the F(4,7) packing: the form is a property of the launch, not of the
     process (round 2 read it from the environment); persistent split tiles (14 x 46 x 46 x 2 = 504 tiles) included."""
-    f4, refs = _run_conv(capi, cuda, 2, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=4)
-    f6, _ = _run_conv(capi, cuda, 2, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=6,
+    f4, refs = _run_conv(capi, cuda, *wc.W7_STAGE, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=4)
+    f6, _ = _run_conv(capi, cuda, *wc.W7_STAGE, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=6,
                       skip_ref=True)
     for a, b, r in zip(f4, f6, refs):
         assert (a - r).abs().max().item() <= TOL * max(1.0, r.abs().max().item())
         assert (b - r).abs().max().item() <= TOL * max(1.0, r.abs().max().item())
         assert not torch.equal(a, b)      # two different arithmetic forms
-    big, _ = _run_conv(capi, cuda, 14, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=4,
+    big, _ = _run_conv(capi, cuda, *wc.W7_F47_BIG, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=4,
                        skip_ref=True)
-    plain, _ = _run_conv(capi, cuda, 14, 46, 46, 128, 128, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=4,
+    plain, _ = _run_conv(capi, cuda, *wc.W7_F47_BIG, 7, 1, 0, 3, 3, seed=13, groups=2, winograd=True, wino_m=4,
                          skip_ref=True, scratch=False)
     for a, b in zip(big, plain):
         assert torch.equal(a, b)
@@ -171,17 +163,7 @@ def test_winograd_matches_torch_cpu(capi, cuda, case):
     assert err <= TOL * max(1.0, ref.abs().max().item()), "max abs err %g" % err
 
 
-WINO4_CASES = [
-    # n, h, w, cin (packed), cout, relu, pool, pad_in, pad_out      (k = 3, F(4x4,3x3): csrc/conv_wino4.hip)
-    (2, 46, 46, 256, 512, 1, 0, 1, 1),     # conv4_1: 8 column tiles, H, W % 4 == 2 (clamped patch rows / columns)
-    (1, 46, 46, 128, 128, 1, 0, 3, 1),     # stage-1 conv reading the P = 3 concat layout
-    (3, 96, 80, 64, 64, 1, 1, 1, 1),       # conv1_2 shape: fused pool, one column tile
-    (1, 100, 92, 128, 256, 1, 0, 1, 1),    # H, W % 4 == 0
-    (2, 45, 47, 32, 64, 0, 0, 1, 0),       # odd sizes (W % 4 == 3, H % 4 == 1), no ReLU, 4 chunks
-    (5, 7, 9, 48, 24, 1, 0, 1, 3),         # tiny maps: a block spans several images; ragged cout; 6 chunks
-    (1, 30, 44, 80, 128, 1, 1, 2, 0),      # pool with H % 4 == 2; gap wider than the padding
-    (40, 46, 46, 64, 128, 1, 0, 1, 1),     # persistent blocks: 180 m tiles x 2 column tiles > 256
-]
+WINO4_CASES = [row for _, row in wc.WINO4_CASES]      # n, h, w, cin (packed), cout, relu, pool, pad_in, pad_out; F(4x4,3x3)
 
 
 @pytest.mark.parametrize("case", WINO4_CASES)
@@ -195,12 +177,12 @@ def test_winograd4_matches_torch_cpu(capi, cuda, case):
 
 
 def test_winograd4_grouped_branches_and_batch_invariance(capi, cuda):
-    outs, refs = _run_conv(capi, cuda, 2, 46, 46, 128, 128, 3, 1, 0, 3, 3, seed=9, groups=2, winograd=True, wino_m=4)
+    outs, refs = _run_conv(capi, cuda, *wc.W4_STAGE, 3, 1, 0, 3, 3, seed=9, groups=2, winograd=True, wino_m=4)
     for o, r in zip(outs, refs):
         assert (o - r).abs().max().item() <= TOL * max(1.0, r.abs().max().item())
     # an image's result does not depend on its neighbours in the batch (clamped patch rows / columns)
-    big, _ = _run_conv(capi, cuda, 3, 45, 47, 64, 64, 3, 1, 0, 1, 1, seed=31, winograd=True, wino_m=4, skip_ref=True)
-    one, _ = _run_conv(capi, cuda, 3, 45, 47, 64, 64, 3, 1, 0, 1, 1, seed=31, winograd=True, wino_m=4, skip_ref=True,
+    big, _ = _run_conv(capi, cuda, *wc.W4_ODD, 3, 1, 0, 1, 1, seed=31, winograd=True, wino_m=4, skip_ref=True)
+    one, _ = _run_conv(capi, cuda, *wc.W4_ODD, 3, 1, 0, 1, 1, seed=31, winograd=True, wino_m=4, skip_ref=True,
                        only_images=1)
     assert torch.equal(big[0][:1], one[0])
 
@@ -209,33 +191,33 @@ def test_winograd4_small_grid_form_is_bit_identical(capi, cuda):
     """Few tiles (batch 1): F(4x4,3x3) launches its 16 x 16 form (wino4s_f32: six waves split the frequencies) - the same
     sums in the same order as the 32 x 64 kernel with its persistent blocks: an image's result does not depend on the
     batch it is evaluated in."""
-    big, refs = _run_conv(capi, cuda, 9, 46, 46, 256, 512, 3, 1, 0, 1, 1, seed=21, winograd=True, wino_m=4)
-    one, _ = _run_conv(capi, cuda, 9, 46, 46, 256, 512, 3, 1, 0, 1, 1, seed=21, winograd=True, wino_m=4, only_images=1)
+    big, refs = _run_conv(capi, cuda, *wc.W4_CONV4_1, 3, 1, 0, 1, 1, seed=21, winograd=True, wino_m=4)
+    one, _ = _run_conv(capi, cuda, *wc.W4_CONV4_1, 3, 1, 0, 1, 1, seed=21, winograd=True, wino_m=4, only_images=1)
     assert (big[0] - refs[0]).abs().max().item() <= TOL * max(1.0, refs[0].abs().max().item())
     assert torch.equal(big[0][:1], one[0])
     # fused pool, one column tile of 64 (four of 16 in the small form), odd tile counts, two branches
-    big, _ = _run_conv(capi, cuda, 20, 96, 80, 64, 64, 3, 1, 1, 1, 1, seed=22, winograd=True, wino_m=4, skip_ref=True)
-    one, _ = _run_conv(capi, cuda, 20, 96, 80, 64, 64, 3, 1, 1, 1, 1, seed=22, winograd=True, wino_m=4, only_images=1,
+    big, _ = _run_conv(capi, cuda, *wc.W4_POOLED, 3, 1, 1, 1, 1, seed=22, winograd=True, wino_m=4, skip_ref=True)
+    one, _ = _run_conv(capi, cuda, *wc.W4_POOLED, 3, 1, 1, 1, 1, seed=22, winograd=True, wino_m=4, only_images=1,
                        skip_ref=True)
     assert torch.equal(big[0][:1], one[0])
-    big, _ = _run_conv(capi, cuda, 40, 45, 47, 128, 128, 3, 1, 0, 3, 3, seed=23, groups=2, winograd=True, wino_m=4,
+    big, _ = _run_conv(capi, cuda, *wc.W4_TWO_BRANCH, 3, 1, 0, 3, 3, seed=23, groups=2, winograd=True, wino_m=4,
                        skip_ref=True)
-    two, _ = _run_conv(capi, cuda, 40, 45, 47, 128, 128, 3, 1, 0, 3, 3, seed=23, groups=2, winograd=True, wino_m=4,
+    two, _ = _run_conv(capi, cuda, *wc.W4_TWO_BRANCH, 3, 1, 0, 3, 3, seed=23, groups=2, winograd=True, wino_m=4,
                        only_images=2, skip_ref=True)
     for a, b in zip(big, two):
         assert torch.equal(a[:2], b)
     # the stage-1 geometry of the bench: 144 m tiles x 4 (column tile, branch) on 256 CUs = 2.25 rounds -> two persistent
     # rounds + the last 16 m tiles as a second launch in the small form; the cut is invisible
-    big, _ = _run_conv(capi, cuda, 32, 46, 46, 128, 128, 3, 1, 0, 3, 3, seed=24, groups=2, winograd=True, wino_m=4,
+    big, _ = _run_conv(capi, cuda, *wc.W4_STAGE1_BENCH, 3, 1, 0, 3, 3, seed=24, groups=2, winograd=True, wino_m=4,
                        skip_ref=True)
     for first, count in ((0, 2), (30, 2)):
-        part, _ = _run_conv(capi, cuda, 32, 46, 46, 128, 128, 3, 1, 0, 3, 3, seed=24, groups=2, winograd=True, wino_m=4,
+        part, _ = _run_conv(capi, cuda, *wc.W4_STAGE1_BENCH, 3, 1, 0, 3, 3, seed=24, groups=2, winograd=True, wino_m=4,
                             skip_ref=True, only_images=count, first_image=first)
         for a, b in zip(big, part):
             assert torch.equal(a[first:first + count], b)
 
 
-@pytest.mark.parametrize("geom", [(32, 92, 92, 32, 256, 1), (32, 46, 46, 64, 512, 1), (32, 45, 47, 64, 256, 2)])
+@pytest.mark.parametrize("geom", [row for _, row in wc.HALF4])      # n, h, w, cin, cout, groups
 def test_winograd4_half_tiles_of_the_left_over_round_are_bit_identical(capi, cuda, geom):
     """Round 4: when the 32 x 64 tiles of a layer are not whole rounds of the CUs and 25..50 % of a round is left over (the
     92 x 92 layers of the 32-image batch: 8.27 rounds; 46 x 46 with 512 columns: 4.5), the left-over runs as one round of HALF
@@ -312,15 +294,7 @@ def _run_conv4_planes(capi, dev, P, pad_in, pad_out, in_planes, out_planes):
     return outs
 
 
-PLANE_CASES = [
-    # n, h, w, cin, cout, relu, pool, pad_in, pad_out, groups
-    (2, 46, 46, 64, 128, 1, 0, 1, 1, 1),      # small-grid form (wino4s_f32)
-    (40, 46, 46, 64, 128, 1, 0, 1, 1, 1),     # persistent blocks
-    (3, 96, 80, 64, 64, 1, 1, 1, 1, 1),       # fused pool
-    (5, 7, 9, 48, 24, 0, 0, 1, 3, 1),         # tiny maps, ragged cout (24 = 3 planes), no ReLU
-    (20, 45, 47, 128, 128, 1, 0, 3, 3, 2),    # two branches in one grid, odd sizes, one round + a left-over launch
-    (32, 92, 92, 32, 256, 1, 0, 1, 1, 1),     # 8.27 rounds: whole rounds + a round of half tiles (wino4_f32<1>)
-]
+PLANE_CASES = [row for _, row in wc.PLANE_CASES]      # n, h, w, cin, cout, relu, pool, pad_in, pad_out, groups
 
 
 @pytest.mark.parametrize("case", PLANE_CASES)

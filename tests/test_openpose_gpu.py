@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import openpose_restate as R  # noqa: E402
+import wino_cases as wc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -192,23 +193,9 @@ def _launch(capi, cuda, n, h, w, cin, cout, k, form, slopes, seed=0, out_planes=
     return out.cpu(), ref
 
 
-# The kernel a case reaches depends on the grid against the device's CUs; named here for the MI355X's 256.
-@pytest.mark.parametrize("n,h,w,cin,cout,k,form,planes", [
-    (2, 23, 19, 64, 96, 3, 0, False),      # direct 3x3 (conv_mfma_f32), padded columns
-    (1, 46, 46, 128, 128, 3, 0, False),
-    (2, 21, 17, 384, 512, 1, 0, False),    # direct 1x1 (Mconv6)
-    (2, 23, 19, 96, 96, 3, 2, False),      # F(2x2,3x3), small grid: wino3s_f32
-    (4, 46, 46, 128, 128, 3, 2, False),    # ... 67 m tiles: still wino3s_f32
-    (16, 46, 46, 128, 128, 3, 2, False),   # F(2x2,3x3), 265 m tiles: persistent wino_f32<1, 4, 16>
-    (16, 46, 46, 96, 96, 3, 2, False),     # ... 96 columns padded to 128
-    (1, 23, 19, 288, 96, 3, 4, False),     # F(4x4,3x3), small grid: wino4s_f32
-    (8, 46, 46, 128, 128, 3, 4, False),    # ... 36 m tiles x 2 column tiles: wino4s_f32
-    (8, 46, 46, 128, 128, 3, 4, True),     # ... writing channel planes
-    (16, 46, 46, 128, 128, 3, 4, False),   # F(4x4,3x3), 72 x 2 tiles: wino4_f32<2> (big tiles)
-    (16, 46, 46, 128, 128, 3, 4, True),    # ... writing channel planes
-    (37, 46, 46, 128, 128, 3, 4, False),   # 167 x 2 tiles: persistent wino4_f32<2> + a half-tile round wino4_f32<1>
-    (33, 46, 46, 128, 128, 3, 4, True),    # 149 x 2 tiles: persistent wino4_f32<2> + the rest in wino4s_f32, planes
-])
+# The kernel a case reaches depends on the grid against the device's CUs: tests/wino_cases.py has the rows, the F(4x4,3x3) ones
+# beside the launch shape each selects on the MI355X's 256 (asserted on the CPU by tests/test_wino_reach_cpu.py).
+@pytest.mark.parametrize("n,h,w,cin,cout,k,form,planes", [row for _, row in wc.PRELU_CASES])
 def test_prelu_epilogue_in_every_form(capi, cuda, n, h, w, cin, cout, k, form, planes):
     slopes = torch.linspace(-1.5, 2.0, cout)  # negative slopes and slopes above 1
     out, ref = _launch(capi, cuda, n, h, w, cin, cout, k, form, slopes, out_planes=planes)

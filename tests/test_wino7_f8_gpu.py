@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 import conv_driver as cd
 import wino7_f8_restate as f87
+import wino_cases as wc
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +44,7 @@ def test_f87_elementwise_error_bound(capi, cuda, kw):
     1000 x amp_exact(w,7,8) / amp_exact(w,7,6).  (Measured gammas: written to wino_gamma_f87.json by _note; none recorded in
     profiles/r09_wino7_f8.txt yet - the emulation of the form stays at <= 624, F(6,7) measures 439 at worst.)"""
     g = torch.Generator().manual_seed(1000 + len(kw))
-    n, c, h, w, cout = 2, 128, 46, 46, 128
+    n, h, w, c, cout = wc.NUMERICS7
     wts = cd.weights(kw, cout, c, 7, g)
     bias = torch.randn(cout, generator=g) * 0.1
     limit = cd.gamma_limit_f87(wts)
@@ -81,17 +82,8 @@ def _check_against_direct_and_f64(capi, cuda, x, wts, biases, relu, scratch=Fals
     return f8
 
 
-GEOMETRIES = [
-    # n, h, w, cin, cout, relu
-    (2, 46, 46, 128, 128, 1),     # the <1,6,8> instance: 6 position groups per row, strips per image
-    (1, 45, 45, 32, 128, 1),      # the same instance with W % 8 == 5: the last group's segments are clamped
-    (2, 30, 45, 64, 128, 0),      # run-time GX (< 256 positions per image: one flat strip space), no ReLU
-    (2, 40, 47, 32, 128, 1),      # run-time GX, W % 8 == 7
-    (5, 6, 7, 16, 128, 1),        # tiny maps, one group per row: a strip spans several images
-    (2, 20, 100, 32, 128, 1),     # 13 groups per row: two transform items per thread (<2,0,8>)
-    (3, 1, 46, 24, 128, 0),       # H = 1
-    (4, 5, 23, 40, 256, 1),       # H = 5, two column tiles
-]
+# n, h, w, cin, cout, relu: tests/wino_cases.py has the rows beside the instance each selects (asserted on the CPU)
+GEOMETRIES = [row for _, row in wc.F87_GEOMETRIES]
 
 
 @pytest.mark.parametrize("geom", GEOMETRIES)
@@ -110,9 +102,10 @@ def test_f87_matches_direct_kernel_and_float64(capi, cuda, geom):
 def test_f87_grouped_two_branch_launch(capi, cuda):
     """The stage-input geometry: 185 -> 128 (packed to 192) for both branches in one grid."""
     g = torch.Generator().manual_seed(871)
-    x = torch.randn(2, 185, 46, 46, generator=g)
-    wts = [torch.randn(128, 185, 7, 7, generator=g) * (2.0 / (185 * 49)) ** 0.5 for _ in range(2)]
-    biases = [torch.randn(128, generator=g) * 0.1 for _ in range(2)]
+    n, h, w, cin, cout = wc.F87_STAGE_IN
+    x = torch.randn(n, cin, h, w, generator=g)
+    wts = [torch.randn(cout, cin, 7, 7, generator=g) * (2.0 / (cin * 49)) ** 0.5 for _ in range(2)]
+    biases = [torch.randn(cout, generator=g) * 0.1 for _ in range(2)]
     f8 = _check_against_direct_and_f64(capi, cuda, x, wts, biases, 1)
     f6 = _conv7(capi, cuda, x, wts, biases, 6, relu=1)
     assert not torch.equal(f8[0], f6[0])          # two different arithmetic forms
@@ -124,16 +117,17 @@ def test_f87_persistent_split_tiles_are_bit_identical(capi, cuda):
     word stays zero, the result is the bits of the one-block-per-tile launch (no scratch) and of a small batch of the same
     images, and a second launch on a fresh scratch repeats it."""
     g = torch.Generator().manual_seed(872)
-    n = 15
-    x = torch.randn(n, 128, 46, 46, generator=g)
-    wts = [torch.randn(128, 128, 7, 7, generator=g) * (2.0 / (128 * 49)) ** 0.5 for _ in range(2)]
-    biases = [torch.randn(128, generator=g) * 0.1 for _ in range(2)]
+    n, h, w, cin, cout = wc.F87_PERSIST
+    x = torch.randn(n, cin, h, w, generator=g)
+    wts = [torch.randn(cout, cin, 7, 7, generator=g) * (2.0 / (cin * 49)) ** 0.5 for _ in range(2)]
+    biases = [torch.randn(cout, generator=g) * 0.1 for _ in range(2)]
     pers = _check_against_direct_and_f64(capi, cuda, x, wts, biases, 1, scratch=True, f64_images=slice(13, 15))
     plain = _conv7(capi, cuda, x, wts, biases, 8, relu=1, scratch=False)
     again = _conv7(capi, cuda, x, wts, biases, 8, relu=1, scratch=True)
-    small = _conv7(capi, cuda, x[6:8], wts, biases, 8, relu=1, scratch=True)     # 36 tiles: one block per tile
+    part = slice(*wc.F87_PERSIST_PART)
+    small = _conv7(capi, cuda, x[part], wts, biases, 8, relu=1, scratch=True)     # 36 tiles: one block per tile
     for a, b, c, d in zip(pers, plain, again, small):
-        assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(a[6:8], d)
+        assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(a[part], d)
 
 
 # ---- whole network ------------------------------------------------------------------------------------------------

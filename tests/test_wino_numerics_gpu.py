@@ -27,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_driver as cd
+import wino_cases as wc
 from conv_driver import GAMMA_LIMIT, HETEROGENEOUS, INPUT_KINDS, U
 
 pytestmark = pytest.mark.gpu
@@ -51,9 +52,12 @@ def _record(form, kx, kw, g):
 
 @pytest.mark.parametrize("kw", ("he", "pos", "smooth", "ref_init_x30"))
 def test_7x7_forms_elementwise_error_bound(capi, cuda, kw):
-    """128 -> 128 at 2 x 46 x 46 (the Mconv2..5_stageN geometry: the <1,8,6> instance of the headline kernel)."""
+    """128 -> 128 at 2 x 46 x 46 (the Mconv2..5_stageN map).  One branch of two images is 24 tiles of F(6,7): twice that stays
+    under the 256 CUs, so the launch runs the small-grid form wino7s_f32<1> - bit-identical to the headline instance
+    wino7_f32<1,8,6,2>, which larger batches of this map select (tests/wino_cases.py, NUMERICS7); F(4,7) runs
+    wino7_f32<1,12,4,1>."""
     g = torch.Generator().manual_seed(1000 + len(kw))
-    n, c, h, w, cout = 2, 128, 46, 46, 128
+    n, h, w, c, cout = wc.NUMERICS7
     wts = cd.weights(kw, cout, c, 7, g)
     bias = torch.randn(cout, generator=g) * 0.1
     failures = []
@@ -508,13 +512,12 @@ def test_reads_past_the_tensor_are_clamped_by_the_buffer_descriptor(capi, cuda):
     input and the filters are placed in front of a NaN-filled region; outputs stay finite and equal to the run
     with a zero-filled neighbourhood.  F(4x4,3x3) - the plan default of 17 convs - is covered in all three launch
     forms: the 16 x 16 small-grid kernel (wino4s_f32), one round of 32 x 64 tiles, and persistent blocks
-    (2 x 184 x 184 -> 133 m tiles x 2 column tiles = 266 tiles on 256 CUs)."""
+    (2 x 184 x 184 -> 133 m tiles x 2 column tiles = 266 tiles on 256 CUs: one round + 5 m tiles in the small form).
+    The geometries: tests/wino_cases.py, CLAMP_CASES."""
     lib, Layout = capi.lib, capi.Layout
     stream = capi.current_stream()
     g = torch.Generator().manual_seed(3)
-    for k, form, (n, cin, cout, h, w) in ((3, 3, (1, 32, 128, 10, 13)), (7, 6, (1, 32, 128, 10, 13)),
-                                          (7, 4, (1, 32, 128, 10, 13)), (3, 43, (1, 32, 128, 10, 13)),
-                                          (3, 43, (1, 32, 128, 200, 200)), (3, 43, (2, 32, 128, 184, 184))):
+    for k, form, (n, cin, cout, h, w) in [row for _, row in wc.CLAMP_CASES]:
         pad = k // 2
         x = torch.randn(n, cin, h, w, generator=g).to(cuda)
         wts = (torch.randn(cout, cin, k, k, generator=g) * 0.05).to(cuda)
