@@ -159,6 +159,27 @@ typedef struct rtpose_conv_desc {
 int rtpose_conv2d(const rtpose_conv_desc* d, int ngroups, int N, int H, int W,
                   void* stream);
 
+/* Non-finite values.  A training run that diverges must say so: the loss of the reference becomes NaN, and so must ours.
+ * PROMISED for the entry points a training step calls - rtpose_conv2d (bias and ReLU), rtpose_conv2d_bf16 (every instance it
+ * dispatches to, the 64-input-channel kernel of rtpose_conv3x3_c64_bf16 included; without a fused pool),
+ * rtpose_conv2d_wgrad, rtpose_conv2d_wgrad_bf16, rtpose_bn_stats / _apply / _grad, rtpose_dwconv3x3 with its _dgrad /
+ * _wgrad, rtpose_conv7x7_s2 with relu = 0 and the fp32 -> bf16 conversions rtpose_nchw_to_layout_bf16,
+ * rtpose_layout_f32_to_bf16, rtpose_nchw_to_layout_split: NaN and Inf travel through the sums as IEEE arithmetic has them
+ * (Inf + finite = Inf, Inf - Inf = NaN, anything + NaN = NaN; the class of a sum does not depend on its order), a fused
+ * ReLU is torch's relu - NaN stays NaN, +Inf stays +Inf, -Inf, every negative value and -0 give +0 -, relu = 0 stores the
+ * sum whatever it is (no clamp: -Inf and sums below -3.0e38 included), a conversion to bf16 keeps a NaN a NaN of its sign,
+ * and a per-channel kernel keeps a non-finite value inside its channel.  The gap pixels of a slice are zeros that ARE
+ * multiplied (no bounds test), so an Inf filter tap or an Inf of gy next to a border meets 0 and gives NaN where a sum over
+ * the map alone has no such term (F.conv2d's own backward forms the same products).  The exceptions of the BatchNorm
+ * passes stand next to rtpose_bn_stats and rtpose_bn_grad.  The backward masks - rtpose_relu_grad*, the recomputed mask of
+ * rtpose_bn_grad, rtpose_prelu_grad - keep their documented comparisons: a NaN y passes no gradient; its forward has
+ * stored that NaN already and the loss is NaN.
+ * NOT PROMISED: inference.  The network executors (rtpose_net_*, every topology) launch the fp32 direct kernel with the
+ * ReLU as max(v, 0), which stores a NaN sum as 0: what a plan computes is what it computed before this paragraph existed.
+ * The fused 2x2 max-pool of any conv launcher, the Winograd, pointwise-pair, pointwise-chain and rtpose_conv_first*
+ * kernels, the max-pools and the in_scale / in_shift pre-activation use max instructions as well.
+ * tests/test_nonfinite_gpu.py. */
+
 /* ---- 2b. Backward pass of these convs: what `total_loss.backward()` of train/train_VGG19.py:216 runs through
  * nn.Conv2d + nn.ReLU (ATen convolution_backward and threshold_backward on the reference).  csrc/conv_backward.hip.
  *
@@ -194,6 +215,8 @@ int rtpose_conv2d_wgrad(const rtpose_wgrad_desc* d, int N, int H, int W, void* s
 /* out = y > 0 ? gy : 0 over `channels` channels of the valid pixels (the gradient through a conv's fused ReLU, from the
  * conv's OUTPUT y): gaps are neither read nor written, so a zero-initialised `out` keeps its zero gaps and stays
  * convolvable.  Every element reads only its own gy element: out / lout may name the slice gy / lgy name.
+ * The comparison is IEEE's on the fp32 y: +0, -0, NaN, -Inf and every negative y give +0; any other y - subnormals and
+ * +Inf included - passes gy's 32 bits through untouched, NaN payloads and both Infs included.
  *
  * Data gradient: no entry point of its own.  The gradient with respect to a conv's input is rtpose_conv2d (relu = 0,
  * zero bias) of gy with the filter w.flip(2, 3).transpose(0, 1), packed by rtpose_pack_conv_weights. */
@@ -273,9 +296,11 @@ int rtpose_prelu_grad(const float* z, const rtpose_layout* lz, const float* slop
  * 2 * channels doubles) and a second launch of one thread per channel adds them in slab order and finalises.
  * Both queries return 0 for a shape the launchers refuse (channels < 1, an empty map, P = 1, P above 2^31 - 256).
  *
- * rtpose_bn_stats.  ONE pass over x with SHIFTED sums, K[c] = x[0, 0, 0, c] (the channel's first value), all in fp64:
+ * rtpose_bn_stats.  ONE pass over x with SHIFTED sums, K[c] = x[0, 0, 0, c] (the channel's first value), all in fp64
+ * (a NaN or Inf of x stays in its channel and gives the mean, variance and running statistics torch gives - but an Inf AT
+ * pixel (0, 0, 0) is K itself: every x - K is NaN or -Inf and the mean is NaN where torch's is Inf):
  *     S1 = sum (x - K)      S2 = sum (x - K) * (x - K)
- *     md = S1 / P           mean = K + md           var = max(S2 / P - md * md, 0)        (the biased variance)
+ *     md = S1 / P           mean = K + md           var = max(S2 / P - md * md, 0)        (the biased variance; NaN stays)
  *     invstd = 1 / sqrt(var + eps)      scale = weight * invstd      shift = bias - mean * scale
  * each rounded to fp32 once into save[RTPOSE_BN_SAVE_ROWS][channels]: rows mean, var, invstd, scale, shift, and mean_lo =
  * fp32(mean - fp32(mean)), the part of the mean its fp32 value lost (the backward's sums use mean + mean_lo).  (scale,
@@ -293,7 +318,7 @@ int rtpose_bn_stats(const float* x, const rtpose_layout* lx, const float* weight
                     float* running_var, double momentum, double eps, float* save, double* workspace,
                     size_t workspace_doubles, int channels, int N, int H, int W, void* stream);
 /* y = scale[c] * x + shift[c] with save's rows 3 and 4: one fp32 multiply and one fp32 add, never fused (the expression
- * of the inference plan's pre-activation), then max(y, 0) if relu.  y / ly may name the slice x / lx names. */
+ * of the inference plan's pre-activation), then y <= 0 ? +0 : y if relu (a NaN y stays NaN).  y / ly may name the slice x / lx names. */
 int rtpose_bn_apply(const float* x, const rtpose_layout* lx, const float* save, float* y, const rtpose_layout* ly, int relu,
                     int channels, int N, int H, int W, void* stream);
 /* torch's native_batch_norm_backward (training) from x, gy, save and weight.
@@ -307,7 +332,12 @@ int rtpose_bn_apply(const float* x, const rtpose_layout* lx, const float* save, 
  *     dx = (g * A - B) - (x - mean) * C
  * x - mean is formed first, so nothing cancels for |mean| >> std.  dweight and dbias are OVERWRITTEN; either may be NULL
  * (frozen) - the sums are still taken for dx.  dx may be NULL (the input needs no gradient): only the reduction runs.
- * dx / ldx may name the slice gy / lgy names. */
+ * dx / ldx may name the slice gy / lgy names.
+ * Non-finite values stay in their channel.  The mask is IEEE's `> 0`: a NaN y passes no gradient (dbias of a channel whose
+ * y is NaN is +0, where torch's threshold_backward passes gy; apply has stored that NaN, so the loss is NaN).  A NaN of gy
+ * gives the NaN dbias, dweight and dx torch gives.  An Inf of gy gives torch's dbias; dweight is the difference of two
+ * shifted sums, G2 - mdk * G1, and is torch's signed Inf or, where the two agree in sign, Inf - Inf = NaN; dx meets
+ * Inf - Inf in another order than torch's and is not held to its class. */
 int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, const rtpose_layout* lgy, const float* save,
                    const float* weight, int relu, float* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
                    double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream);

@@ -4,13 +4,13 @@
 //
 //   rtpose_bn_stats  per channel c over the P = N H W valid pixels, K[c] = x[0, 0, 0, c]:
 //                      S1 = sum (x - K), S2 = sum (x - K)^2                         (fp64; the SHIFTED sums, one pass)
-//                      md = S1 / P; mean = K + md; var = max(S2 / P - md * md, 0)   (fp64)
+//                      md = S1 / P; mean = K + md; var = max(S2 / P - md * md, 0)   (fp64; NaN stays NaN)
 //                      invstd = 1 / sqrt(var + eps); scale = weight * invstd; shift = bias - mean * scale   (fp64)
 //                    save[0..5][c] = fp32(mean), fp32(var), fp32(invstd), fp32(scale), fp32(shift), fp32(mean - fp32(mean))
 //                    running_mean = fp32((1 - m) * running_mean + m * mean),
 //                    running_var  = fp32((1 - m) * running_var + m * (var * P / (P - 1)))           (fp64, if given)
 //   rtpose_bn_apply  y = scale[c] * x + shift[c] (one fp32 multiply, one fp32 add; the library is built with
-//                    -ffp-contract=off), then max(y, 0) if relu
+//                    -ffp-contract=off), then relu: y <= 0 ? +0 : y (a NaN y stays NaN, as torch's relu has it)
 //   rtpose_bn_grad   g = relu ? (scale[c] * x + shift[c] > 0 ? gy : 0) : gy      (the mask RECOMPUTED from x: apply's bits)
 //                      G1 = sum g, G2 = sum g * (x - K)                              (fp64)
 //                      mdk = (mean + mean_lo) - K; dbias = G1; dweight = invstd * (G2 - mdk * G1)   (fp64 -> fp32)
@@ -93,7 +93,8 @@ __global__ __launch_bounds__(kThreads) void bn_kernel(const BnArgs a) {
           y = sc[v] * xv.v[v];
           y = y + sh[v];
         }
-        // the gradient through the ReLU: gy's bits where apply's y > 0, +0 elsewhere (a NaN y: 0, as max(y, 0) gave 0)
+        // the gradient through the ReLU: gy's bits where apply's y > 0, +0 elsewhere (a NaN y: +0; apply stores that NaN, so the
+        // loss is NaN already)
         const float g = (GRAD && a.relu) ? (y > 0.f ? gv.v[v] : 0.f) : gv.v[v];
         if (MODE == kStats) {
           const double d = (double)xv.v[v] - kk[v];
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void bn_kernel(const BnArgs a) {
           acc[0][v] += (double)g;
           acc[1][v] += (double)g * d;
         } else if (MODE == kApply) {
-          res.v[v] = a.relu ? (y > 0.f ? y : 0.f) : y;
+          res.v[v] = a.relu ? (y <= 0.f ? 0.f : y) : y;  // torch's relu: a NaN y stays NaN
         } else {
           const float xm = xv.v[v] - mean[v];
           float t0 = g * cA[v];
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(kFinalThreads) void bn_stats_final_kernel(const Fin
   const double md = s1 / P;
   const double mean = (double)a.x0[c] + md;
   double var = s2 / P - md * md;
-  var = var > 0.0 ? var : 0.0;
+  var = var <= 0.0 ? 0.0 : var;  // (this way round a NaN variance stays NaN; `var > 0 ? var : 0` would store 0 and a finite scale)
   const double invstd = 1.0 / sqrt(var + a.eps);
   const double scale = (double)a.weight[c] * invstd;
   const double shift = (double)a.bias[c] - mean * scale;

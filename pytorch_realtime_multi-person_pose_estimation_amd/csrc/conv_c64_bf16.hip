@@ -79,11 +79,9 @@ __device__ __forceinline__ float vmax(float a, float b) {
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-__device__ __forceinline__ float vmax_lo(float lo, float a) {  // lo: wave-uniform lower bound (0 = ReLU, -inf = none)
-  float r;
-  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "s"(lo), "v"(a));
-  return r;
-}
+// ReLU as torch has it, or none: thr is wave-uniform, 0 with ReLU and NaN without.  `v <= NaN` is false for every v, so
+// relu = 0 stores the sum whatever it is; with ReLU a NaN sum stays NaN (a max would store the operand that is not NaN)
+__device__ __forceinline__ float relu_thr(float thr, float v) { return v <= thr ? 0.f : v; }
 // max(v, v of lane ^ 1): the DPP quad permute [1, 0, 3, 2] on the first operand.  (s_nop 1: a DPP operand written by the VALU
 // instruction in front needs two wait states, and the hazard pass does not look into inline assembly)
 __device__ __forceinline__ float max_with_lane_xor1(float v) {
@@ -227,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
 
     // ---- epilogue: lane = pixel x0 + l31 of a row; registers 4 j .. 4 j + 3 of a half = channels 8 j + 4 kh .. + 3 ----
     const float4* const b4 = reinterpret_cast<const float4*>(s_bias);
-    const float relu_lo = A.relu ? 0.f : -__builtin_inff();
+    const float thr = A.relu ? 0.f : __builtin_nanf("");
     constexpr int ROWS = POOL ? 2 : 4;
 #pragma unroll
     for (int ro = 0; ro < ROWS; ++ro) {
@@ -270,8 +268,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
               a = acc[ro][nf][8 * m + e];
               b = acc[ro][nf][8 * m + 4 + e];
             }
-            lo[e] = vmax_lo(relu_lo, a + blv[e]);
-            hi[e] = vmax_lo(relu_lo, b + bhv[e]);
+            lo[e] = relu_thr(thr, a + blv[e]);
+            hi[e] = relu_thr(thr, b + bhv[e]);
           }
           unsigned a2[2], b2[2];
 #pragma unroll

@@ -59,11 +59,19 @@ struct ConvGroup {
   const int32_t* out_cmap;  // optional output-channel scatter (see rtpose_conv_desc)
 };
 
+// The fused ReLU.  kReluKeepsNan (rtpose_conv2d): torch's relu by a compare and a select - NaN stays NaN, +Inf stays +Inf,
+// -Inf, negatives and -0 give +0.  kReluMax (the inference executor): max(v, 0), which returns the operand that is not NaN.
+// Finite sums get the same bits from both.  `form` is wave-uniform.
+constexpr int kReluMax = 1, kReluKeepsNan = 2;
+__device__ __forceinline__ float relu_of(float v, int form) {
+  return form == kReluKeepsNan ? (v <= 0.f ? 0.f : v) : fmaxf(v, 0.f);
+}
+
 struct ConvArgs {
   ConvGroup g[2];
   int N, H, W, M;     // output == input spatial size (before pooling)
   int cin;            // packed input channels
-  int relu, pool;
+  int relu, pool;     // relu: 0, kReluMax or kReluKeepsNan
   int qs;             // LDS pixels per channel-group plane
   int hw_lds;         // MODE 1: LDS row stride of the halo (pixels)
   int tw_log2;        // MODE 1: log2(tile width); tile height = 128 >> tw_log2
@@ -564,7 +572,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
             ok = (y < A.H) && (x < A.W);
           }
           float v = acc[fm][fn][rg * 4 + rr];
-          if (A.relu) v = fmaxf(v, 0.f);
+          if (A.relu) v = relu_of(v, A.relu);
           if constexpr (PR) v = prelu1(v, slope[fn]);
           if (ok && col_ok) {
             if constexpr (XT) {
@@ -593,7 +601,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
         const int px = (x0 >> 1) + (qi & ((1 << hw_log2) - 1));
         float v = fmaxf(fmaxf(acc[fm][fn][rg * 4 + 0], acc[fm][fn][rg * 4 + 1]),
                         fmaxf(acc[fm][fn][rg * 4 + 2], acc[fm][fn][rg * 4 + 3]));
-        if (A.relu) v = fmaxf(v, 0.f);
+        if (A.relu) v = relu_of(v, A.relu);
         if (py < Ho && px < Wo && col_ok) {
           const size_t q = (size_t)g.out_lead + (size_t)(n_img * g.out_hs + py) * g.out_ws + px;
           out_base[q * g.out_cstride] = v;
@@ -780,7 +788,7 @@ static int launch_inst(const ConvArgsT<PR>& a, dim3 grid, size_t lds, hipStream_
   return launch_kernel<conv_mfma_f32<KS, CK, MODE, NBUF, NF, PR>>(grid, dim3(256), lds, 150 * 1024, s, a);
 }
 
-int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s) {
+int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s, bool relu_max) {
   const ConvSpec spec = {"conv2d", 4, 1, true, false, true, true, true, true};
   if (int rc = check_conv_features(d, ngroups, spec)) return rc;
   const rtpose_conv_desc& d0 = d[0];
@@ -823,7 +831,7 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
   a.W = W;
   a.M = N * H * W;
   a.cin = d0.cin;
-  a.relu = d0.relu;
+  a.relu = d0.relu ? (relu_max ? kReluMax : kReluKeepsNan) : 0;
   a.pool = d0.pool;
   a.qs = pl.qs;
   a.hw_lds = pl.hw_lds;
@@ -954,7 +962,7 @@ int rtpose_pack_conv_weights(const float* w_oihw, const float* bias, int cout, i
 }
 
 int rtpose_conv2d(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, void* stream) {
-  return rtpose::conv2d_launch(d, ngroups, N, H, W, rtpose::as_stream(stream));
+  return rtpose::conv2d_launch(d, ngroups, N, H, W, rtpose::as_stream(stream), false);
 }
 
 }  // extern "C"

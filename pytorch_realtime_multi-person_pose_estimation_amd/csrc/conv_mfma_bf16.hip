@@ -573,7 +573,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
   {
   unsigned short* out_h = reinterpret_cast<unsigned short*>(g.out);
   float* out_f = reinterpret_cast<float*>(g.out);
-  const float relu_lo = A.relu ? 0.f : -3.0e38f;  // uniform: v = max(v, relu_lo), no select
+  // ReLU as torch has it: NaN stays NaN, +Inf stays +Inf, everything <= 0 (-0, -Inf) becomes +0.  The threshold is uniform:
+  // without ReLU it is NaN, `v <= NaN` is false for every v, and the sum is stored as it is (one compare, one select)
+  const float relu_thr = A.relu ? 0.f : __builtin_nanf("");
+  auto act = [relu_thr](float v) { return v <= relu_thr ? 0.f : v; };
   const bool pool = MODE == 1 && A.pool;          // (the fused 2x2 max-pool exists for 2-D tiles only)
   if (TR) {
     // lane = pixel l31 of fragment fm (column of the transposed product), registers = the channels 16 kh .. 16 kh + 15 of
@@ -615,7 +618,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
         unsigned hi[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          hi[i] = pack_bf2(fmaxf(acc[fm][fn][2 * i], relu_lo), fmaxf(acc[fm][fn][2 * i + 1], relu_lo));
+          hi[i] = pack_bf2(act(acc[fm][fn][2 * i]), act(acc[fm][fn][2 * i + 1]));
         if (SP == 1) {
           if (ok) {
             gstore4(op + fn * 32, as_f4(hi[0], hi[1], hi[2], hi[3]));
@@ -625,8 +628,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
           unsigned lo[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i)
-            lo[i] = pack_bf2(fmaxf(acc[fm][fn][2 * i], relu_lo) - __uint_as_float(hi[i] << 16),
-                             fmaxf(acc[fm][fn][2 * i + 1], relu_lo) - __uint_as_float(hi[i] & 0xffff0000u));
+            lo[i] = pack_bf2(act(acc[fm][fn][2 * i]) - __uint_as_float(hi[i] << 16),
+                             act(acc[fm][fn][2 * i + 1]) - __uint_as_float(hi[i] & 0xffff0000u));
           if (ok) {
             gstore4(op + fn * 64, as_f4(hi[0], hi[1], hi[2], hi[3]));
             gstore4(op + fn * 64 + 8, as_f4(lo[0], lo[1], lo[2], lo[3]));
@@ -648,7 +651,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     // element of output channel c inside a slab row: c, or (split) its 8-channel group's hi piece
     const int ce = SP == 1 ? l31 : ((l31 >> 3) * 16 + (l31 & 7));
     auto put = [&](int row, int fn, float v) {
-      v = fmaxf(v, relu_lo);
+      v = act(v);
       unsigned short* d = sl + row * PITCH2 + fn * 32 * SP + ce;
       const unsigned short hi = to_bf16(v);
       d[0] = hi;
@@ -774,7 +777,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
               x = x0 + tx;
               ok = (y < A.H) && (x < A.W);
             }
-            const float v = fmaxf(acc[fm][fn][rg * 4 + rr], relu_lo);
+            const float v = act(acc[fm][fn][rg * 4 + rr]);
             if (ok && col_ok) {
               const size_t q = (size_t)g.out_lead + (size_t)(n * g.out_hs + y) * g.out_ws + x;
               if (A.out_f32) {
@@ -801,8 +804,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
           const int qi = ml0 >> 2;
           const int py = (y0 >> 1) + (qi >> hw_log2);
           const int px = (x0 >> 1) + (qi & ((1 << hw_log2) - 1));
-          const float v = fmaxf(fmaxf(fmaxf(acc[fm][fn][rg * 4 + 0], acc[fm][fn][rg * 4 + 1]),
-                                      fmaxf(acc[fm][fn][rg * 4 + 2], acc[fm][fn][rg * 4 + 3])), relu_lo);
+          const float v = act(fmaxf(fmaxf(acc[fm][fn][rg * 4 + 0], acc[fm][fn][rg * 4 + 1]),
+                                    fmaxf(acc[fm][fn][rg * 4 + 2], acc[fm][fn][rg * 4 + 3])));
           if (py < Ho && px < Wo && col_ok) {
             const size_t q = (size_t)g.out_lead + (size_t)(n_img * g.out_hs + py) * g.out_ws + px;
             if (A.out_f32) {

@@ -9,7 +9,9 @@
 namespace rtpose {
 
 // ---- fp32 direct conv (conv_mfma.hip) ----
-int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s);
+// relu_max: the fused ReLU as max(v, 0), which stores a NaN sum as 0 - the form the inference executor launches (its outputs
+// stay what they were; header section 2, "Non-finite values").  false (rtpose_conv2d): torch's relu, a NaN stays NaN
+int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, hipStream_t s, bool relu_max);
 int pack_weights_launch(const float* w, const float* bias, int cout, int cin_src, int k,
                         const int32_t* cin_map, int cin_packed, float* wp, float* bp, hipStream_t s);
 

@@ -1654,7 +1654,7 @@ static int net_run_ops(rtpose_net* net, size_t first, size_t last, const float* 
              : c.form != F_DIRECT ? conv2d_wino7_launch(d, o.ngroups, N, o.H, o.W, kForm[c.form].fm,
                                                         net->persist7 ? net->ws + net->scratch_off : nullptr,  // (no scratch:
                                                         net->persist7 ? net->scratch_bytes : 0, s)             //  one block per tile)
-                                  : conv2d_launch(d, o.ngroups, N, o.H, o.W, s);
+                                  : conv2d_launch(d, o.ngroups, N, o.H, o.W, s, true);
         break;
       }
       case OP_TAIL: {

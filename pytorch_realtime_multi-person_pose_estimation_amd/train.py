@@ -61,6 +61,11 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   per-conv path, launch for launch.
 
 On the default path the NCHW <-> layout conversion around every operation is known overhead.
+
+A non-finite activation reaches the loss: the entry points called here carry NaN and Inf through their sums and their
+fused ReLU is torch's (NaN stays NaN), in every mode - fp32, bf16 and layout-resident -, so a run that diverges prints a NaN
+loss as the reference's loops do (header section 2, "Non-finite values"; tests/test_nonfinite_gpu.py).  ``model.forward``,
+the inference plan, promises nothing of the kind.
 """
 import ctypes as C
 import weakref

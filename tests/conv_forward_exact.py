@@ -685,9 +685,10 @@ def _direct_x():
     cs.append(_c(L, "pre-both-1x1", 1, 1, 1, 8, 8, x={"preact": "both"}, edges=("preact", "one pixel"), seed=112))
     # preact_cin < cin.  The header: channels >= preact_cin are staged as 0 whatever the buffer and the vectors hold there.
     # The -nan cases (NaN in the buffer's padded channels) meet that wording but cannot tell whether the kernel looks at
-    # preact_cin at all: relu is fmaxf(., 0), which turns NaN into 0, and the padded filter taps are zero.  The -inf cases
-    # can: the padded channels hold 1.0 and in_shift is +inf there, so a kernel that pre-activated them would stage +inf,
-    # and inf x the zero tap is NaN in every output.
+    # preact_cin at all: the pre-activation's ReLU is fmaxf(., 0), which promises nothing about NaN and turns it into 0 (header
+    # section 2, "Non-finite values"), and the padded filter taps are zero.
+    # The -inf cases can: the padded channels hold 1.0 and in_shift is +inf there, so a kernel that pre-activated them would
+    # stage +inf, and inf x the zero tap is NaN in every output.
     cs.append(_c(L, "pre-cin21of24-inf", 2, 5, 7, 21, 24, relu=1, pad_in=2, x={"preact": "both", "inf_pad": 1},
                  edges=("preact", "cin padded", "gap pixels", "ck8"), seed=117))
     cs.append(_c(L, "pre-cin41of48-inf-2d", 1, 2, 131, 41, 65, x={"preact": "both", "inf_pad": 1},
