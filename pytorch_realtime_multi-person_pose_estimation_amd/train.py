@@ -52,7 +52,8 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   ``rtpose_layout_f32_to_bf16`` of the masked gradient (its one rounding point), the data gradient as
   ``rtpose_conv2d_bf16(out_f32=1)`` on the bf16 packing of ``dgrad_weights``, the weight and bias gradients by
   ``rtpose_conv2d_wgrad_bf16``.  A shape ``rtpose_conv2d_bf16`` refuses (it refuses before launching) runs that direction of
-  that conv on the fp32 path and is counted in ``bf16_fallbacks``.  The default ``'fp32'`` is the path above, launch for launch.
+  that conv on the fp32 path and is counted in ``bf16_fallbacks``.  The default ``'fp32'`` is the path above, launch for launch:
+  one node, ``_Conv2d``, runs both, and tests/test_train_trace_gpu.py holds the launch sequence of either to a recorded one.
 
 * Layout-resident runs (``conv_chain``; ``resident=True`` of ``run_sequential``, ``forward_train`` and ``train_step``, RtposeVGG
   only): a run of convs with one consumer each is one autograd node; its inner activations and gradients stay in the gapped
@@ -175,18 +176,20 @@ def _packed_for(weight, bias, which, epoch=0, resync=False):
 
 
 # ---- layout buffers ---------------------------------------------------------------------------------------------------------
-def _buffer(lay, n, h, w, device, zero):
+def _buffer(lay, n, h, w, device, zero, bf16=False):
+    """A buffer for n maps of h x w in the layout `lay`: fp32, zero-filled if `zero`, or bf16, which is always zero-filled"""
     numel = lib.rtpose_layout_pixels(C.byref(lay), n, h, w) * lay.cstride
-    return (torch.zeros if zero else torch.empty)(numel, dtype=torch.float32, device=device)
+    return (torch.zeros if zero or bf16 else torch.empty)(numel, dtype=torch.bfloat16 if bf16 else torch.float32, device=device)
 
 
-def _to_layout(t, pad):
-    """NCHW -> a zero-gapped layout buffer with the channels rounded up to 8 (the extra ones zero)."""
+def _to_layout(t, pad, bf16=False):
+    """NCHW fp32 -> a zero-gapped layout buffer with the channels rounded up to 8 (the extra ones zero); `bf16`: a bf16
+    buffer (round to nearest even) with the channels rounded up to 16"""
     n, c, h, w = t.shape
-    lay = _capi.Layout.padded(_up8(c), h, w, pad)
-    buf = _buffer(lay, n, h, w, t.device, True)
-    check(lib.rtpose_nchw_to_layout(ptr(t), ptr(buf), C.byref(lay), c, lay.cstride, n, h, w, current_stream()),
-          "rtpose_nchw_to_layout")
+    lay = _capi.Layout.padded((_up16 if bf16 else _up8)(c), h, w, pad)
+    buf = _buffer(lay, n, h, w, t.device, True, bf16)
+    name = "rtpose_nchw_to_layout_bf16" if bf16 else "rtpose_nchw_to_layout"
+    check(getattr(lib, name)(ptr(t), ptr(buf), C.byref(lay), c, lay.cstride, n, h, w, current_stream()), name)
     return buf, lay
 
 
@@ -196,80 +199,88 @@ def _from_layout(buf, lay, n, c, h, w):
     return out
 
 
-def _launch_conv(inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
-    """rtpose_conv2d of a layout buffer into a new dense one: (buffer, layout)"""
-    lout = _capi.Layout.dense(_up8(cout), h, w)
-    out = _buffer(lout, n, h, w, inp.device, False)
+def _round_to_bf16(src, lsrc, c, n, h, w, pad=None, into=None):
+    """rtpose_layout_f32_to_bf16 of the c channels of an fp32 layout buffer, into a new bf16 buffer with a zero gap of `pad`
+    and the channels rounded up to 16, or into the slice `into` = (buffer, layout): (buffer, layout)"""
+    if into is None:
+        ldst = _capi.Layout.padded(_up16(c), h, w, pad)
+        into = _buffer(ldst, n, h, w, src.device, True, True), ldst
+    dst, ldst = into
+    check(lib.rtpose_layout_f32_to_bf16(ptr(src), C.byref(lsrc), ptr(dst), C.byref(ldst), c, ldst.cstride, n, h, w,
+                                        current_stream()), "rtpose_layout_f32_to_bf16")
+    return dst, ldst
+
+
+def _conv_launch(bf16, inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w, out, lout, out_f32=0):
+    """One conv of a layout buffer into the slice out / lout - the one place a ConvDesc is filled: rtpose_conv2d, or
+    rtpose_conv2d_bf16 writing bf16 (out_f32 = 0) or fp32.  True, or False if the bf16 launcher refused the shape
+    (RTPOSE_E_INVAL: returned before any launch)."""
     d = _capi.ConvDesc()
     d.inp, d.w_packed, d.bias_packed, d.out = inp.data_ptr(), wp.data_ptr(), bp.data_ptr(), out.data_ptr()
     d.lin, d.lout = lin, lout
     d.cin, d.cout, d.k, d.relu = cin_p, cout, k, 1 if relu else 0
-    check(lib.rtpose_conv2d(C.byref(d), 1, n, h, w, current_stream()), "rtpose_conv2d")
-    return out, lout
-
-
-def _wgrad(xbuf, lx, gbuf, lg, like_weight, cin, cout, k, n, h, w, need_b):
-    """rtpose_conv2d_wgrad of the layout buffers of x and of the output gradient (an h x w map, gaps of k // 2):
-    (dw shaped like `like_weight`, db or None)"""
-    dw = torch.empty_like(like_weight, memory_format=torch.contiguous_format)
-    db = torch.empty(cout, dtype=torch.float32, device=gbuf.device) if need_b else None
-    floats = lib.rtpose_conv2d_wgrad_workspace_floats(cin, cout, k, n, h, w)
-    ws = torch.empty(floats, dtype=torch.float32, device=gbuf.device)
-    d = _capi.WgradDesc()
-    d.x, d.gy, d.dw, d.dbias = xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
-    d.workspace, d.workspace_floats = ws.data_ptr(), floats
-    d.lx, d.lgy = lx, lg
-    d.cin, d.cout, d.k = cin, cout, k
-    check(lib.rtpose_conv2d_wgrad(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad")
-    return dw, db
-
-
-def _buffer_bf16(lay, n, h, w, device):
-    numel = lib.rtpose_layout_pixels(C.byref(lay), n, h, w) * lay.cstride
-    return torch.zeros(numel, dtype=torch.bfloat16, device=device)
-
-
-def _to_layout_bf16(t, pad):
-    """NCHW fp32 -> a zero-gapped bf16 layout buffer (round to nearest even) with the channels rounded up to 16, the
-    extra ones zero"""
-    n, c, h, w = t.shape
-    lay = _capi.Layout.padded(_up16(c), h, w, pad)
-    buf = _buffer_bf16(lay, n, h, w, t.device)
-    check(lib.rtpose_nchw_to_layout_bf16(ptr(t), ptr(buf), C.byref(lay), c, lay.cstride, n, h, w, current_stream()),
-          "rtpose_nchw_to_layout_bf16")
-    return buf, lay
-
-
-def _launch_conv_bf16(inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
-    """rtpose_conv2d_bf16 (out_f32 = 1) of a bf16 layout buffer into a new dense fp32 one: (buffer, layout), or None if the
-    launcher refused the shape (RTPOSE_E_INVAL: returned before any launch)"""
-    lout = _capi.Layout.dense(_up8(cout), h, w)
-    out = _buffer(lout, n, h, w, inp.device, False)
-    d = _capi.ConvDesc()
-    d.inp, d.w_packed, d.bias_packed, d.out = inp.data_ptr(), wp.data_ptr(), bp.data_ptr(), out.data_ptr()
-    d.lin, d.lout = lin, lout
-    d.cin, d.cout, d.k, d.relu = cin_p, cout, k, 1 if relu else 0
-    rc = lib.rtpose_conv2d_bf16(C.byref(d), 1, n, h, w, 1, current_stream())
-    if rc == -1:        # RTPOSE_E_INVAL
-        return None
+    if not bf16:
+        check(lib.rtpose_conv2d(C.byref(d), 1, n, h, w, current_stream()), "rtpose_conv2d")
+        return True
+    rc = lib.rtpose_conv2d_bf16(C.byref(d), 1, n, h, w, 1 if out_f32 else 0, current_stream())
+    if rc == -1:
+        return False
     check(rc, "rtpose_conv2d_bf16")
-    return out, lout
+    return True
 
 
-def _wgrad_bf16(xbuf, lx, gbuf, lg, like_weight, cin, cout, k, n, h, w, need_b):
-    """rtpose_conv2d_wgrad_bf16 of the bf16 layout buffers of x and of the output gradient: (dw shaped like `like_weight`,
-    db or None), both fp32"""
+# the name _ConvChain launches through, and nothing else does: replacing it plays a refusal of a chain's own launches and
+# leaves alone the conv2d nodes the chain falls back to (tests/test_train_resident_gpu.py)
+_conv_into = _conv_launch
+
+
+def _launch_conv(bf16, inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
+    """_conv_launch into a new dense fp32 buffer: (buffer, layout), or None if the bf16 launcher refused the shape"""
+    lout = _capi.Layout.dense(_up8(cout), h, w)
+    out = _buffer(lout, n, h, w, inp.device, False)
+    return (out, lout) if _conv_launch(bf16, inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w, out, lout, 1) else None
+
+
+def _wgrad(bf16, xbuf, lx, gbuf, lg, like_weight, cin, cout, k, n, h, w, need_b):
+    """rtpose_conv2d_wgrad - `bf16`: rtpose_conv2d_wgrad_bf16 - of the layout buffers of x and of the output gradient (an
+    h x w map, gaps of k // 2; both fp32 or both bf16): (dw shaped like `like_weight`, db or None), fp32"""
+    name = "rtpose_conv2d_wgrad_bf16" if bf16 else "rtpose_conv2d_wgrad"
     dw = torch.empty_like(like_weight, memory_format=torch.contiguous_format)
     db = torch.empty(cout, dtype=torch.float32, device=gbuf.device) if need_b else None
-    floats = lib.rtpose_conv2d_wgrad_bf16_workspace_floats(cin, cout, k, n, h, w)
+    floats = getattr(lib, name + "_workspace_floats")(cin, cout, k, n, h, w)
     ws = torch.empty(floats, dtype=torch.float32, device=gbuf.device)
-    d = _capi.WgradBf16Desc()
+    d = (_capi.WgradBf16Desc if bf16 else _capi.WgradDesc)()
     d.x, d.gy, d.dw, d.dbias = xbuf.data_ptr(), gbuf.data_ptr(), dw.data_ptr(), db.data_ptr() if need_b else None
     d.workspace, d.workspace_floats = ws.data_ptr(), floats
     d.lx, d.lgy = lx, lg
     d.cin, d.cout, d.k = cin, cout, k
-    check(lib.rtpose_conv2d_wgrad_bf16(C.byref(d), n, h, w, current_stream()), "rtpose_conv2d_wgrad_bf16")
+    check(getattr(lib, name)(C.byref(d), n, h, w, current_stream()), name)
     return dw, db
+
+
+def _relu_grad(bf16, ybuf, ly, gbuf, lg, c, n, h, w):
+    """g = y > 0 ? g : 0 in place on the gradient's layout buffer: rtpose_relu_grad, or rtpose_relu_grad_bf16 on bf16 buffers"""
+    name = "rtpose_relu_grad_bf16" if bf16 else "rtpose_relu_grad"
+    check(getattr(lib, name)(ptr(ybuf), C.byref(ly), ptr(gbuf), C.byref(lg), ptr(gbuf), C.byref(lg), c, n, h, w,
+                             current_stream()), name)
+
+
+def _prelu(zbuf, lz, slopes, c, n, h, w):
+    """rtpose_prelu of the pre-activation's layout buffer into a new one of the same layout"""
+    ybuf = _buffer(lz, n, h, w, zbuf.device, False)
+    check(lib.rtpose_prelu(ptr(zbuf), C.byref(lz), ptr(slopes.detach().contiguous()), ptr(ybuf), C.byref(lz), c, n, h, w,
+                           current_stream()), "rtpose_prelu")
+    return ybuf
+
+
+def _prelu_grad(zbuf, lz, slopes, gbuf, lg, c, n, h, w, need_a):
+    """rtpose_prelu_grad in place on the gradient's layout buffer; the slope gradient, or None unless `need_a`"""
+    floats = lib.rtpose_prelu_grad_workspace_floats(c, n, h, w) if need_a else 0
+    ws = torch.empty(floats, dtype=torch.float32, device=gbuf.device) if need_a else None
+    da = torch.empty(c, dtype=torch.float32, device=gbuf.device) if need_a else None
+    check(lib.rtpose_prelu_grad(ptr(zbuf), C.byref(lz), ptr(slopes.detach().contiguous()), ptr(gbuf), C.byref(lg), ptr(gbuf),
+                                C.byref(lg), ptr(da), ptr(ws), floats, c, n, h, w, current_stream()), "rtpose_prelu_grad")
+    return da
 
 
 def _zero_stuffed_layout(gy, h, w, pad):
@@ -298,86 +309,27 @@ def _check_prelu(prelu, weight, relu):
         raise _capi.RtposeError("train.conv2d: prelu on %s, the filters on %s" % (prelu.device, weight.device))
 
 
+def _is_same_conv_filter(weight, cin):
+    """an fp32 OIHW filter of a stride-1 "same" conv on `cin` channels that the kernels here run: square, k in {1, 3, 7}"""
+    return (weight.dtype == torch.float32 and weight.dim() == 4 and weight.shape[3] == weight.shape[2]
+            and weight.shape[2] in (1, 3, 7) and weight.shape[1] == cin)
+
+
 def _check_input(x, weight):
     _require_device("train.conv2d", x, weight)
     if x.dtype != torch.float32 or weight.dtype != torch.float32 or x.dim() != 4 or weight.dim() != 4:
         raise _capi.RtposeError("train.conv2d takes NCHW fp32 inputs and OIHW fp32 filters")
-    k = weight.shape[2]
-    if weight.shape[3] != k or k not in (1, 3, 7) or weight.shape[1] != x.shape[1]:
+    if not _is_same_conv_filter(weight, x.shape[1]):
         raise _capi.RtposeError("train.conv2d: stride-1 'same' convs with k in {1, 3, 7}; got filters %s for input %s"
                                 % (tuple(weight.shape), tuple(x.shape)))
 
 
 class _Conv2d(torch.autograd.Function):
+    """conv2d's node.  Inputs: x, weight, bias (or None), relu, epoch, resync, the PReLU slopes (or None), bf16.  With `bf16`
+    the operands of all three convs are bf16: what is rounded, and where, is in the module docstring.  Everything fp32 - the
+    activation gradients, the buffers y / z they read, the outputs of all three convs - is the same in both."""
     @staticmethod
-    def forward(ctx, x, weight, bias, relu, epoch, resync, prelu):
-        if prelu is not None:
-            _check_prelu(prelu, weight, relu)
-        _check_input(x, weight)
-        with torch.cuda.device(x.device):
-            n, cin, h, w = x.shape
-            cout, k = weight.shape[0], weight.shape[2]
-            xbuf, lx = _to_layout(x.detach().contiguous(), k // 2)
-            wp, bp = _packed_for(weight, bias, 'fwd', epoch, resync)
-            ybuf, ly = _launch_conv(xbuf, lx, wp, bp, lx.cstride, cout, k, relu, n, h, w)
-            zbuf = None
-            if prelu is not None:        # ybuf so far holds the pre-activation: keep it as z, y goes to a buffer of its own
-                zbuf, ybuf = ybuf, _buffer(ly, n, h, w, x.device, False)
-                check(lib.rtpose_prelu(ptr(zbuf), C.byref(ly), ptr(prelu.detach().contiguous()), ptr(ybuf), C.byref(ly), cout,
-                                       n, h, w, current_stream()), "rtpose_prelu")
-            y = _from_layout(ybuf, ly, n, cout, h, w)
-        ctx.geom = (n, cin, cout, k, h, w)
-        ctx.relu = bool(relu)
-        ctx.has_bias = bias is not None
-        ctx.weight = weight
-        ctx.epoch, ctx.resync = epoch, resync
-        ctx.has_prelu = prelu is not None
-        # (for autograd's check that the filters and slopes were not modified in place since)
-        ctx.save_for_backward(*((weight, prelu) if ctx.has_prelu else (weight,)))
-        wants_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
-        ctx.xbuf, ctx.lx = (xbuf, lx) if wants_w else (None, None)
-        ctx.ybuf, ctx.ly = (ybuf, ly) if relu and any(ctx.needs_input_grad) else (None, None)
-        ctx.zbuf, ctx.lz = (zbuf, ly) if ctx.has_prelu and any(ctx.needs_input_grad) else (None, None)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gy):
-        saved = ctx.saved_tensors
-        n, cin, cout, k, h, w = ctx.geom
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        need_a = ctx.has_prelu and ctx.needs_input_grad[6]
-        dx = dw = db = da = None
-        with torch.cuda.device(gy.device):
-            stream = current_stream()
-            gbuf, lg = _to_layout(gy.detach().float().contiguous(), k // 2)
-            if ctx.relu:
-                check(lib.rtpose_relu_grad(ptr(ctx.ybuf), C.byref(ctx.ly), ptr(gbuf), C.byref(lg), ptr(gbuf), C.byref(lg), cout,
-                                           n, h, w, stream), "rtpose_relu_grad")
-            if ctx.has_prelu:
-                floats = lib.rtpose_prelu_grad_workspace_floats(cout, n, h, w) if need_a else 0
-                ws = torch.empty(floats, dtype=torch.float32, device=gy.device) if need_a else None
-                da = torch.empty(cout, dtype=torch.float32, device=gy.device) if need_a else None
-                check(lib.rtpose_prelu_grad(ptr(ctx.zbuf), C.byref(ctx.lz), ptr(saved[1].detach().contiguous()), ptr(gbuf),
-                                            C.byref(lg), ptr(gbuf), C.byref(lg), ptr(da), ptr(ws), floats, cout, n, h, w, stream),
-                      "rtpose_prelu_grad")
-            if need_x:
-                wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
-                dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
-                dx = _from_layout(dbuf, ld, n, cin, h, w)
-            if need_w or need_b:
-                dw, db = _wgrad(ctx.xbuf, ctx.lx, gbuf, lg, ctx.weight, cin, cout, k, n, h, w, need_b)
-                if not need_w:
-                    dw = None
-        return dx, dw, db, None, None, None, da
-
-
-class _Conv2dBf16(torch.autograd.Function):
-    """_Conv2d with bf16 operands: what is rounded, and where, is in the module docstring.  Everything fp32 here - the
-    activation gradients, the buffers y / z they read, the outputs of all three convs - is as in _Conv2d."""
-    @staticmethod
-    def forward(ctx, x, weight, bias, relu, epoch, resync, prelu):
+    def forward(ctx, x, weight, bias, relu, epoch, resync, prelu, bf16):
         if prelu is not None:
             _check_prelu(prelu, weight, relu)
         _check_input(x, weight)
@@ -385,30 +337,29 @@ class _Conv2dBf16(torch.autograd.Function):
             n, cin, h, w = x.shape
             cout, k = weight.shape[0], weight.shape[2]
             xc = x.detach().contiguous()
-            xbuf, lx = _to_layout_bf16(xc, k // 2)
-            wp, bp = _packed_for(weight, bias, 'fwd16', epoch, resync)
-            done = _launch_conv_bf16(xbuf, lx, wp, bp, lx.cstride, cout, k, relu, n, h, w)
+            xbuf, lx = _to_layout(xc, k // 2, bf16)
+            wp, bp = _packed_for(weight, bias, 'fwd16' if bf16 else 'fwd', epoch, resync)
+            done = _launch_conv(bf16, xbuf, lx, wp, bp, lx.cstride, cout, k, relu, n, h, w)
             if done is None:             # refused before any launch: this direction of this conv in fp32
                 bf16_fallbacks['fwd'] += 1
                 xbuf32, lx32 = _to_layout(xc, k // 2)
                 wp, bp = _packed_for(weight, bias, 'fwd', epoch, resync)
-                done = _launch_conv(xbuf32, lx32, wp, bp, lx32.cstride, cout, k, relu, n, h, w)
+                done = _launch_conv(False, xbuf32, lx32, wp, bp, lx32.cstride, cout, k, relu, n, h, w)
             ybuf, ly = done
             zbuf = None
-            if prelu is not None:        # as in _Conv2d: the conv wrote the pre-activation z
-                zbuf, ybuf = ybuf, _buffer(ly, n, h, w, x.device, False)
-                check(lib.rtpose_prelu(ptr(zbuf), C.byref(ly), ptr(prelu.detach().contiguous()), ptr(ybuf), C.byref(ly), cout,
-                                       n, h, w, current_stream()), "rtpose_prelu")
+            if prelu is not None:        # ybuf so far holds the pre-activation: keep it as z, y goes to a buffer of its own
+                zbuf, ybuf = ybuf, _prelu(ybuf, ly, prelu, cout, n, h, w)
             y = _from_layout(ybuf, ly, n, cout, h, w)
         ctx.geom = (n, cin, cout, k, h, w)
-        ctx.relu = bool(relu)
+        ctx.relu, ctx.bf16 = bool(relu), bf16
         ctx.has_bias = bias is not None
         ctx.weight = weight
         ctx.epoch, ctx.resync = epoch, resync
         ctx.has_prelu = prelu is not None
+        # (for autograd's check that the filters and slopes were not modified in place since)
         ctx.save_for_backward(*((weight, prelu) if ctx.has_prelu else (weight,)))
         wants_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
-        ctx.xbuf, ctx.lx = (xbuf, lx) if wants_w else (None, None)      # the bf16 buffer
+        ctx.xbuf, ctx.lx = (xbuf, lx) if wants_w else (None, None)      # with bf16 the bf16 buffer, also after a fallback
         ctx.ybuf, ctx.ly = (ybuf, ly) if relu and any(ctx.needs_input_grad) else (None, None)
         ctx.zbuf, ctx.lz = (zbuf, ly) if ctx.has_prelu and any(ctx.needs_input_grad) else (None, None)
         return y
@@ -418,42 +369,34 @@ class _Conv2dBf16(torch.autograd.Function):
     def backward(ctx, gy):
         saved = ctx.saved_tensors
         n, cin, cout, k, h, w = ctx.geom
+        bf16 = ctx.bf16
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         need_a = ctx.has_prelu and ctx.needs_input_grad[6]
         dx = dw = db = da = None
         with torch.cuda.device(gy.device):
-            stream = current_stream()
             gbuf, lg = _to_layout(gy.detach().float().contiguous(), k // 2)
             if ctx.relu:
-                check(lib.rtpose_relu_grad(ptr(ctx.ybuf), C.byref(ctx.ly), ptr(gbuf), C.byref(lg), ptr(gbuf), C.byref(lg), cout,
-                                           n, h, w, stream), "rtpose_relu_grad")
+                _relu_grad(False, ctx.ybuf, ctx.ly, gbuf, lg, cout, n, h, w)
             if ctx.has_prelu:
-                floats = lib.rtpose_prelu_grad_workspace_floats(cout, n, h, w) if need_a else 0
-                ws = torch.empty(floats, dtype=torch.float32, device=gy.device) if need_a else None
-                da = torch.empty(cout, dtype=torch.float32, device=gy.device) if need_a else None
-                check(lib.rtpose_prelu_grad(ptr(ctx.zbuf), C.byref(ctx.lz), ptr(saved[1].detach().contiguous()), ptr(gbuf),
-                                            C.byref(lg), ptr(gbuf), C.byref(lg), ptr(da), ptr(ws), floats, cout, n, h, w, stream),
-                      "rtpose_prelu_grad")
-            if need_x or need_w or need_b:
+                da = _prelu_grad(ctx.zbuf, ctx.lz, saved[1], gbuf, lg, cout, n, h, w, need_a)
+            g, lgr = gbuf, lg            # what the two gradients below read
+            if bf16 and (need_x or need_w or need_b):
                 # the one rounding point of the output gradient: both gradients below read these bf16 values
-                lg16 = _capi.Layout.padded(_up16(cout), h, w, k // 2)
-                g16 = _buffer_bf16(lg16, n, h, w, gy.device)
-                check(lib.rtpose_layout_f32_to_bf16(ptr(gbuf), C.byref(lg), ptr(g16), C.byref(lg16), cout, lg16.cstride,
-                                                    n, h, w, stream), "rtpose_layout_f32_to_bf16")
+                g, lgr = _round_to_bf16(gbuf, lg, cout, n, h, w, k // 2)
             if need_x:
-                wp, bp = _packed_for(ctx.weight, None, 'bwd16', ctx.epoch, ctx.resync)
-                done = _launch_conv_bf16(g16, lg16, wp, bp, lg16.cstride, cin, k, False, n, h, w)
-                if done is None:
+                wp, bp = _packed_for(ctx.weight, None, 'bwd16' if bf16 else 'bwd', ctx.epoch, ctx.resync)
+                done = _launch_conv(bf16, g, lgr, wp, bp, lgr.cstride, cin, k, False, n, h, w)
+                if done is None:         # refused: on the fp32 masked gradient
                     bf16_fallbacks['dgrad'] += 1
                     wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
-                    done = _launch_conv(gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
+                    done = _launch_conv(False, gbuf, lg, wp, bp, lg.cstride, cin, k, False, n, h, w)
                 dx = _from_layout(done[0], done[1], n, cin, h, w)
             if need_w or need_b:
-                dw, db = _wgrad_bf16(ctx.xbuf, ctx.lx, g16, lg16, ctx.weight, cin, cout, k, n, h, w, need_b)
+                dw, db = _wgrad(bf16, ctx.xbuf, ctx.lx, g, lgr, ctx.weight, cin, cout, k, n, h, w, need_b)
                 if not need_w:
                     dw = None
-        return dx, dw, db, None, None, None, da
+        return dx, dw, db, None, None, None, da, None
 
 
 def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None, compute_dtype='fp32'):
@@ -465,8 +408,7 @@ def conv2d(x, weight, bias=None, relu=False, epoch=0, resync=False, prelu=None, 
     `compute_dtype`: 'fp32', or 'bf16' for bf16 operands of all three convs with fp32 accumulation (module docstring);
     inputs, outputs, gradients and parameters are fp32 either way."""
     _check_compute_dtype("train.conv2d", compute_dtype)
-    fn = _Conv2d if compute_dtype == 'fp32' else _Conv2dBf16
-    return fn.apply(x, weight, bias, bool(relu), int(epoch), bool(resync), prelu)
+    return _Conv2d.apply(x, weight, bias, bool(relu), int(epoch), bool(resync), prelu, compute_dtype == 'bf16')
 
 
 # ---- a run of convs as one autograd node: the inner activations and gradients stay in the layouts ---------------------------------
@@ -483,21 +425,15 @@ class _ChainRefused(Exception):
     """rtpose_conv2d_bf16 refused a forward conv of a chain (before any launch of that conv)"""
 
 
-def _conv_into(bf16, inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w, out, lout, out_f32=0):
-    """One conv of a layout buffer into the slice out / lout: rtpose_conv2d, or rtpose_conv2d_bf16 writing bf16 (out_f32 = 0)
-    or fp32.  True, or False if the bf16 launcher refused the shape (RTPOSE_E_INVAL: returned before any launch)."""
-    d = _capi.ConvDesc()
-    d.inp, d.w_packed, d.bias_packed, d.out = inp.data_ptr(), wp.data_ptr(), bp.data_ptr(), out.data_ptr()
-    d.lin, d.lout = lin, lout
-    d.cin, d.cout, d.k, d.relu = cin_p, cout, k, 1 if relu else 0
-    if not bf16:
-        check(lib.rtpose_conv2d(C.byref(d), 1, n, h, w, current_stream()), "rtpose_conv2d")
-        return True
-    rc = lib.rtpose_conv2d_bf16(C.byref(d), 1, n, h, w, 1 if out_f32 else 0, current_stream())
-    if rc == -1:
-        return False
-    check(rc, "rtpose_conv2d_bf16")
-    return True
+def _chain_buffer(bf16, c, k_next, n, h, w, device):
+    """Where a conv of a chain writes its c channels: a zero-initialised buffer gapped for the conv of size `k_next` that reads
+    it next, the channels padded as that conv reads them (16 for bf16, 8 for fp32; the conv writes c channels only, so the
+    pad channels stay zero) - or, for `k_next` None, where the chain ends: a dense fp32 one.  (buffer, layout)"""
+    if k_next is None:
+        lay = _capi.Layout.dense(_up8(c), h, w)
+        return _buffer(lay, n, h, w, device, False), lay
+    lay = _capi.Layout.padded((_up16 if bf16 else _up8)(c), h, w, k_next // 2)
+    return _buffer(lay, n, h, w, device, True, bf16), lay
 
 
 def _check_chain(x, layers):
@@ -512,8 +448,7 @@ def _check_chain(x, layers):
         if i == 0:
             _check_input(x, weight)
         _require_device("train.conv_chain", weight, names=("a weight",))
-        k = weight.shape[2] if weight.dim() == 4 else 0
-        if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[3] != k or k not in (1, 3, 7) or weight.shape[1] != c:
+        if not _is_same_conv_filter(weight, c):
             raise _capi.RtposeError("train.conv_chain: layer %d: stride-1 'same' convs with fp32 OIHW filters, k in {1, 3, 7}, "
                                     "whose input channels are the output channels of the layer before (%s); got filters %s %s"
                                     % (i, c, weight.dtype, tuple(weight.shape)))
@@ -531,22 +466,16 @@ class _ConvChain(torch.autograd.Function):
         relus, epoch, resync, bf16 = meta
         weights, biases = params[0::2], params[1::2]
         L = len(weights)
-        up = _up16 if bf16 else _up8
         fwd = 'fwd16' if bf16 else 'fwd'
         with torch.cuda.device(x.device):
             n, _, h, w = x.shape
             ks = [wt.shape[2] for wt in weights]
             couts = [wt.shape[0] for wt in weights]
-            buf, lay = (_to_layout_bf16 if bf16 else _to_layout)(x.detach().contiguous(), ks[0] // 2)
+            buf, lay = _to_layout(x.detach().contiguous(), ks[0] // 2, bf16)
             bufs, lays = [buf], [lay]
             for i in range(L):
                 wp, bp = _packed_for(weights[i], biases[i], fwd, epoch, resync)
-                if i + 1 < L:    # zero gaps for the next conv's padding; zero pad channels (the conv writes cout channels only)
-                    lout = _capi.Layout.padded(up(couts[i]), h, w, ks[i + 1] // 2)
-                    out = _buffer_bf16(lout, n, h, w, x.device) if bf16 else _buffer(lout, n, h, w, x.device, True)
-                else:
-                    lout = _capi.Layout.dense(_up8(couts[i]), h, w)
-                    out = _buffer(lout, n, h, w, x.device, False)
+                out, lout = _chain_buffer(bf16, couts[i], ks[i + 1] if i + 1 < L else None, n, h, w, x.device)
                 if not _conv_into(bf16, bufs[i], lays[i], wp, bp, lays[i].cstride, couts[i], ks[i], relus[i], n, h, w, out, lout,
                                   out_f32=i + 1 == L):
                     raise _ChainRefused()
@@ -579,36 +508,29 @@ class _ConvChain(torch.autograd.Function):
         L = len(weights)
         n, h, w = ctx.geom
         need_x = ctx.needs_input_grad[0]
-        up = _up16 if bf16 else _up8
         bwd = 'bwd16' if bf16 else 'bwd'
         grads = [None] * (2 * L)
         dx = None
         if low >= L:
             return (None, None) + tuple(grads)
         with torch.cuda.device(gy.device):
-            stream = current_stream()
             dev = gy.device
             gyc = gy.detach().float().contiguous()
             k, cout = weights[L - 1].shape[2], weights[L - 1].shape[0]
             if relus[L - 1] or not bf16:
                 g, lg = _to_layout(gyc, k // 2)
                 if relus[L - 1]:     # a ReLU behind the last conv: masked by the fp32 output, as conv2d does
-                    check(lib.rtpose_relu_grad(ptr(bufs[L]), C.byref(lays[L]), ptr(g), C.byref(lg), ptr(g), C.byref(lg), cout,
-                                               n, h, w, stream), "rtpose_relu_grad")
+                    _relu_grad(False, bufs[L], lays[L], g, lg, cout, n, h, w)
                 if bf16:
-                    lg16 = _capi.Layout.padded(_up16(cout), h, w, k // 2)
-                    g16 = _buffer_bf16(lg16, n, h, w, dev)
-                    check(lib.rtpose_layout_f32_to_bf16(ptr(g), C.byref(lg), ptr(g16), C.byref(lg16), cout, lg16.cstride,
-                                                        n, h, w, stream), "rtpose_layout_f32_to_bf16")
-                    g, lg = g16, lg16
+                    g, lg = _round_to_bf16(g, lg, cout, n, h, w, k // 2)
             else:
-                g, lg = _to_layout_bf16(gyc, k // 2)
+                g, lg = _to_layout(gyc, k // 2, True)
             for i in range(L - 1, low - 1, -1):
                 wt = weights[i]
                 cout, cin, k = wt.shape[0], wt.shape[1], wt.shape[2]
                 if wants[i]:
                     need_b = ctx.has_bias[i] and ctx.needs_input_grad[3 + 2 * i]
-                    dw, db = (_wgrad_bf16 if bf16 else _wgrad)(bufs[i], lays[i], g, lg, wt, cin, cout, k, n, h, w, need_b)
+                    dw, db = _wgrad(bf16, bufs[i], lays[i], g, lg, wt, cin, cout, k, n, h, w, need_b)
                     grads[2 * i] = dw if ctx.needs_input_grad[2 + 2 * i] else None
                     grads[2 * i + 1] = db
                 if i == low and not (i == 0 and need_x):
@@ -616,36 +538,22 @@ class _ConvChain(torch.autograd.Function):
                 # the data gradient: the conv of g on the flipped, transposed filter, straight into the buffer the layer
                 # below reads its output gradient from (gapped for that layer), or into a dense fp32 one for dx
                 wp, bp = _packed_for(wt, None, bwd, epoch, resync)
-                if i > 0:
-                    ld = _capi.Layout.padded(up(cin), h, w, weights[i - 1].shape[2] // 2)
-                    d = _buffer_bf16(ld, n, h, w, dev) if bf16 else _buffer(ld, n, h, w, dev, True)
-                else:
-                    ld = _capi.Layout.dense(_up8(cin), h, w)
-                    d = _buffer(ld, n, h, w, dev, False)
+                d, ld = _chain_buffer(bf16, cin, weights[i - 1].shape[2] if i > 0 else None, n, h, w, dev)
                 if not _conv_into(bf16, g, lg, wp, bp, lg.cstride, cin, k, False, n, h, w, d, ld, out_f32=i == 0):
                     # refused: this one conv in fp32 on the widened gradient, rounded again at its store inside the chain
                     bf16_fallbacks['dgrad'] += 1
                     l32 = _capi.Layout.padded(_up8(cout), h, w, k // 2)
                     g32 = _buffer(l32, n, h, w, dev, True)
-                    check(lib.rtpose_layout_bf16_to_f32(ptr(g), C.byref(lg), ptr(g32), C.byref(l32), cout, n, h, w, stream),
-                          "rtpose_layout_bf16_to_f32")
+                    check(lib.rtpose_layout_bf16_to_f32(ptr(g), C.byref(lg), ptr(g32), C.byref(l32), cout, n, h, w,
+                                                        current_stream()), "rtpose_layout_bf16_to_f32")
                     wp, bp = _packed_for(wt, None, 'bwd', epoch, resync)
-                    d32, ld32 = _launch_conv(g32, l32, wp, bp, l32.cstride, cin, k, False, n, h, w)
-                    if i > 0:
-                        check(lib.rtpose_layout_f32_to_bf16(ptr(d32), C.byref(ld32), ptr(d), C.byref(ld), cin, ld.cstride,
-                                                            n, h, w, stream), "rtpose_layout_f32_to_bf16")
-                    else:
-                        d, ld = d32, ld32
+                    d32, ld32 = _launch_conv(False, g32, l32, wp, bp, l32.cstride, cin, k, False, n, h, w)
+                    d, ld = _round_to_bf16(d32, ld32, cin, n, h, w, into=(d, ld)) if i > 0 else (d32, ld32)
                 if i == 0:
                     dx = _from_layout(d, ld, n, cin, h, w)
                     break
                 if relus[i - 1]:     # in place, by the layer below's output as stored: this layer's kept input buffer
-                    if bf16:
-                        check(lib.rtpose_relu_grad_bf16(ptr(bufs[i]), C.byref(lays[i]), ptr(d), C.byref(ld), ptr(d), C.byref(ld),
-                                                        cin, n, h, w, stream), "rtpose_relu_grad_bf16")
-                    else:
-                        check(lib.rtpose_relu_grad(ptr(bufs[i]), C.byref(lays[i]), ptr(d), C.byref(ld), ptr(d), C.byref(ld),
-                                                   cin, n, h, w, stream), "rtpose_relu_grad")
+                    _relu_grad(bf16, bufs[i], lays[i], d, ld, cin, n, h, w)
                 g, lg = d, ld
         return (dx, None) + tuple(grads)
 
@@ -738,7 +646,7 @@ class _Conv7x7S2(torch.autograd.Function):
         with torch.cuda.device(gy.device):
             gbuf, lg = _zero_stuffed_layout(gy, h, w, 3)
             xbuf, lx = _to_layout(ctx.x, 3)
-            dw, db = _wgrad(xbuf, lx, gbuf, lg, weight, 3, 64, 7, n, h, w, need_b)
+            dw, db = _wgrad(False, xbuf, lx, gbuf, lg, weight, 3, 64, 7, n, h, w, need_b)
             if not need_w:
                 dw = None
         return None, dw, db, None, None
@@ -865,10 +773,10 @@ class _Conv3x3S2(torch.autograd.Function):
             gbuf, lg = _zero_stuffed_layout(gy, h, w, 1)
             if need_x:
                 wp, bp = _packed_for(ctx.weight, None, 'bwd', ctx.epoch, ctx.resync)
-                dbuf, ld = _launch_conv(gbuf, lg, wp, bp, lg.cstride, 3, 3, False, n, h, w)
+                dbuf, ld = _launch_conv(False, gbuf, lg, wp, bp, lg.cstride, 3, 3, False, n, h, w)
                 dx = _from_layout(dbuf, ld, n, 3, h, w)
             if need_w:
-                dw, _ = _wgrad(ctx.xbuf, ctx.lx, gbuf, lg, weight, 3, 24, 3, n, h, w, False)
+                dw, _ = _wgrad(False, ctx.xbuf, ctx.lx, gbuf, lg, weight, 3, 24, 3, n, h, w, False)
         return dx, dw, None, None
 
 

@@ -80,8 +80,8 @@ def main():
         gy = torch.randn(N, cout, hw, hw, device=dev, generator=g).bfloat16().float()
         wt = torch.randn(cout, cin, k, k, device=dev, generator=g) * (2.0 / (cin * k * k)) ** 0.5
         stream = capi.current_stream()
-        x16, lx16 = train._to_layout_bf16(x, k // 2)
-        g16, lg16 = train._to_layout_bf16(gy, k // 2)
+        x16, lx16 = train._to_layout(x, k // 2, True)
+        g16, lg16 = train._to_layout(gy, k // 2, True)
         dw, db = torch.empty_like(wt), torch.empty(cout, device=dev)
         floats = lib.rtpose_conv2d_wgrad_bf16_workspace_floats(cin, cout, k, N, hw, hw)
         ws = torch.empty(floats, device=dev)
