@@ -163,8 +163,8 @@ int rtpose_conv2d(const rtpose_conv_desc* d, int ngroups, int N, int H, int W,
  * PROMISED for the entry points a training step calls - rtpose_conv2d (bias and ReLU), rtpose_conv2d_bf16 (every instance it
  * dispatches to, the 64-input-channel kernel of rtpose_conv3x3_c64_bf16 included; without a fused pool),
  * rtpose_conv2d_wgrad, rtpose_conv2d_wgrad_bf16, rtpose_bn_stats / _apply / _grad, rtpose_dwconv3x3 with its _dgrad /
- * _wgrad, rtpose_conv7x7_s2 with relu = 0 and the fp32 -> bf16 conversions rtpose_nchw_to_layout_bf16,
- * rtpose_layout_f32_to_bf16, rtpose_nchw_to_layout_split: NaN and Inf travel through the sums as IEEE arithmetic has them
+ * _wgrad, rtpose_conv7x7_s2 with relu = 0, rtpose_prelu_bf16, rtpose_prelu_grad_bf16 and the fp32 -> bf16 conversions
+ * rtpose_nchw_to_layout_bf16, rtpose_layout_f32_to_bf16, rtpose_nchw_to_layout_split: NaN and Inf travel through the sums as IEEE arithmetic has them
  * (Inf + finite = Inf, Inf - Inf = NaN, anything + NaN = NaN; the class of a sum does not depend on its order), a fused
  * ReLU is torch's relu - NaN stays NaN, +Inf stays +Inf, -Inf, every negative value and -0 give +0 -, relu = 0 stores the
  * sum whatever it is (no clamp: -Inf and sums below -3.0e38 included), a conversion to bf16 keeps a NaN a NaN of its sign,
@@ -275,6 +275,46 @@ int rtpose_prelu_grad_slabs(int channels, int N, int H, int W);
 int rtpose_prelu_grad(const float* z, const rtpose_layout* lz, const float* slope, const float* gy,
                       const rtpose_layout* lgy, float* out, const rtpose_layout* lout, float* dslope,
                       float* workspace, size_t workspace_floats, int channels, int N, int H, int W, void* stream);
+
+/* ---- 2b, continued.  PReLU between the bf16 convs of a layout-resident training run (csrc/prelu_bf16.hip;
+ * train.dense_stage): the two passes above with the rounding of rtpose_layout_f32_to_bf16 at their store, so that the
+ * fp32 y and the fp32 masked gradient never exist.  `z`, `ga`, `gb` are fp32 slices; `y` / `out` are 2-byte bf16 slices
+ * whose layouts count ELEMENTS.  Gaps and the channels beside the slices are neither read nor written, so a
+ * zero-initialised destination keeps its zero gaps and stays convolvable, and several launches may fill disjoint channel
+ * slices of one buffer (the concatenation of a dense block is that buffer).
+ *
+ *     y[n,y,x,c]   = bf16(z >= 0 ? z : slope[c] * z)                           (rtpose_prelu's fp32 value, rounded)
+ *     g            = gb ? ga + gb : ga                                          (one fp32 add; gb may be NULL)
+ *     out[n,y,x,c] = bf16(z > 0 ? g : slope[c] * g)                             (rtpose_prelu_grad's fp32 value on g, rounded)
+ *     dslope[c]    = sum over valid (n,y,x) of (z > 0 ? 0 : z * g)              (dslope != NULL; fp32; OVERWRITTEN)
+ *
+ * bf16() rounds to nearest even as rtpose_layout_f32_to_bf16 does: Inf stays Inf, a NaN stays a NaN of its sign.  So y
+ * has the bits of rtpose_prelu followed by rtpose_layout_f32_to_bf16 - what the next conv's input conversion makes of the
+ * fp32 y -, and out the bits of rtpose_prelu_grad on the fp32 sum ga + gb followed by rtpose_layout_f32_to_bf16.  `gb` is
+ * the gradient of a second consumer of the activation (a dense block's concatenation and the block's next conv both read
+ * it): the sum autograd forms for it, which does not depend on the order of its two operands.  gb == NULL adds nothing
+ * (ga's -0 stays -0, where ga + (+0) is +0).  z == 0 of either sign and a NaN z take the slope path; where z > 0, out is g
+ * rounded.  A NaN z stores a NaN y.
+ * The sums walk as rtpose_prelu_grad's do - the same slabs (rtpose_prelu_grad_bf16_slabs() == rtpose_prelu_grad_slabs()),
+ * rectangle, unit and order, no atomics: the same inputs give the same bits on every run, and dslope has the bits
+ * rtpose_prelu_grad gives on the summed gradient whenever both take their 4-channel units.  dslope == NULL (a frozen
+ * slope): no reduction is launched, workspace may be NULL and is not written.
+ * 16-byte loads and one 8-byte store of 4 bf16 where every fp32 slice has a 16-byte-aligned base and a cstride and choff
+ * that are multiples of 4, and the bf16 slice an 8-byte-aligned base and a cstride and choff that are multiples of 4
+ * elements; element by element otherwise: the same bits of y / out either way.
+ * Every argument is checked on the host before any HIP call (RTPOSE_E_INVAL with a text): NULL pointers or layouts (gb
+ * alone may be NULL, and lgb is then not looked at), channels / N / H / W < 1, choff + channels > cstride, a layout
+ * smaller than the map, N * H * W above the launch limit of 2^31 - 256 pixels, an odd base of the bf16 slice, a bf16
+ * slice whose bytes overlap those of z, ga, gb or slope, and a workspace below
+ * rtpose_prelu_grad_bf16_workspace_floats() floats.  Both queries return 0 for a shape the launcher refuses. */
+int rtpose_prelu_bf16(const float* z, const rtpose_layout* lz, const float* slope, void* y, const rtpose_layout* ly,
+                      int channels, int N, int H, int W, void* stream);
+size_t rtpose_prelu_grad_bf16_workspace_floats(int channels, int N, int H, int W);
+int rtpose_prelu_grad_bf16_slabs(int channels, int N, int H, int W);
+int rtpose_prelu_grad_bf16(const float* z, const rtpose_layout* lz, const float* slope, const float* ga,
+                           const rtpose_layout* lga, const float* gb, const rtpose_layout* lgb, void* out,
+                           const rtpose_layout* lout, float* dslope, float* workspace, size_t workspace_floats,
+                           int channels, int N, int H, int W, void* stream);
 
 /* ---- 2b, continued.  Training-mode BatchNorm2d (+ ReLU) on layout slices (csrc/batchnorm.hip): what the stacked
  * hourglass needs to train (train.batch_norm).  The inference plans know a BatchNorm only by its RUNNING statistics

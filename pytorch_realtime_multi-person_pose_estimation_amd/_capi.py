@@ -254,6 +254,10 @@ _SIGS = {
     "rtpose_prelu_grad_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "rtpose_prelu_grad_slabs": (_i, [_i, _i, _i, _i]),
     "rtpose_prelu_grad": (_i, [_vp, _LP, _vp, _vp, _LP, _vp, _LP, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "rtpose_prelu_bf16": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _vp]),
+    "rtpose_prelu_grad_bf16_workspace_floats": (_sz, [_i, _i, _i, _i]),
+    "rtpose_prelu_grad_bf16_slabs": (_i, [_i, _i, _i, _i]),
+    "rtpose_prelu_grad_bf16": (_i, [_vp, _LP, _vp, _vp, _LP, _vp, _LP, _vp, _LP, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rtpose_bn_workspace_doubles": (_sz, [_i, _i, _i, _i]),
     "rtpose_bn_slabs": (_i, [_i, _i, _i, _i]),
     "rtpose_bn_stats": (_i, [_vp, _LP, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),

@@ -55,6 +55,13 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   that conv on the fp32 path and is counted in ``bf16_fallbacks``.  The default ``'fp32'`` is the path above, launch for launch:
   one node, ``_Conv2d``, runs both, and tests/test_train_trace_gpu.py holds the launch sequence of either to a recorded one.
 
+* Layout-resident dense stages (``dense_stage``; ``resident='dense'`` of ``forward_train`` and ``train_step``, OpenPose_Model
+  with ``compute_dtype='bf16'`` only): a ``StageBlock`` is one autograd node.  Its conv launches are the per-conv bf16 path's
+  (``out_f32 = 1``); between them ``rtpose_prelu_bf16`` writes the PReLU output as bf16 straight into the slice of the
+  block's concat buffer the next convs read, and ``rtpose_prelu_grad_bf16`` makes a layer's bf16 output gradient from its
+  kept fp32 pre-activation and the fp32 data gradients of its one or two consumers.  No NCHW tensor, ``torch.cat`` or fp32
+  PReLU output exists inside a stage.  Opt-in.
+
 * Layout-resident runs (``conv_chain``; ``resident=True`` of ``run_sequential``, ``forward_train`` and ``train_step``, RtposeVGG
   only): a run of convs with one consumer each is one autograd node; its inner activations and gradients stay in the gapped
   layout buffers (bf16 ones for ``compute_dtype='bf16'``: ``rtpose_conv2d_bf16(out_f32=0)`` forward and data gradient,
@@ -605,6 +612,301 @@ def conv_chain(x, layers, epoch=0, resync=False, compute_dtype='fp32'):
     return x
 
 
+# ---- a StageBlock of an OpenPose_Model as one autograd node: dense blocks and PReLU inside the layouts (bf16) ---------------------
+# stages of a resident='dense' run that gave up residency: a width that is no multiple of 16, or a forward conv that
+# rtpose_conv2d_bf16 refused
+dense_fallbacks = 0
+
+
+def reset_dense_fallbacks():
+    global dense_fallbacks
+    dense_fallbacks = 0
+
+
+class _DenseRefused(Exception):
+    """rtpose_conv2d_bf16 refused a forward conv of a dense stage (before any launch of that conv)"""
+
+
+# the name _DenseStage launches its convs through, and nothing else does: replacing it plays a refusal of the node's own
+# launches and leaves alone the conv2d nodes the stage falls back to (tests/test_train_dense_gpu.py)
+_dense_conv_into = _conv_launch
+
+
+def _prelu_bf16(zbuf, lz, slope, ybuf, ly, c, n, h, w):
+    """rtpose_prelu_bf16 of the fp32 pre-activation into the bf16 slice ybuf / ly"""
+    check(lib.rtpose_prelu_bf16(ptr(zbuf), C.byref(lz), ptr(slope.detach().contiguous()), ptr(ybuf), C.byref(ly), c, n, h, w,
+                                current_stream()), "rtpose_prelu_bf16")
+
+
+def _prelu_grad_bf16(zbuf, lz, slope, ga, lga, gb, lgb, out, lout, c, n, h, w, need_a):
+    """rtpose_prelu_grad_bf16 of the fp32 gradient slice ga (+ gb, or None) into the bf16 slice out / lout; the slope
+    gradient, or None unless `need_a`"""
+    floats = lib.rtpose_prelu_grad_bf16_workspace_floats(c, n, h, w) if need_a else 0
+    ws = torch.empty(floats, dtype=torch.float32, device=out.device) if need_a else None
+    da = torch.empty(c, dtype=torch.float32, device=out.device) if need_a else None
+    check(lib.rtpose_prelu_grad_bf16(ptr(zbuf), C.byref(lz), ptr(slope.detach().contiguous()), ptr(ga), C.byref(lga), ptr(gb),
+                                     C.byref(lgb) if gb is not None else None, ptr(out), C.byref(lout), ptr(da), ptr(ws),
+                                     floats, c, n, h, w, current_stream()), "rtpose_prelu_grad_bf16")
+    return da
+
+
+def _check_dense(x, layers):
+    who = "train.dense_stage"
+    _require_device(who, x, names=("x",))
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise _capi.RtposeError("%s takes an NCHW fp32 input; got %s %s" % (who, x.dtype, tuple(x.shape)))
+    L = len(layers)
+    if L < 5 or (L - 2) % 3:
+        raise _capi.RtposeError("%s: layers are 3 B + 2 (weight, bias_or_None, slope_or_None) triples, B >= 1 dense blocks of "
+                                "three 3x3 convs, then the 1x1 convs Mconv6 and Mconv7; got %d" % (who, L))
+    for i, layer in enumerate(layers):
+        if not isinstance(layer, tuple) or len(layer) != 3 or not torch.is_tensor(layer[0]):
+            raise _capi.RtposeError("%s: layers are (weight, bias_or_None, slope_or_None) triples; got %r at %d"
+                                    % (who, type(layer).__name__, i))
+        _require_device(who, layer[0], names=("the filters of layer %d" % i,))
+    def rows(t):
+        return t.shape[0] if t.dim() else 0
+
+    width = rows(layers[0][0])
+    for i, (weight, bias, slope) in enumerate(layers):
+        block, j = divmod(i, 3)
+        k = 3 if i < L - 2 else 1
+        cin = (width if j else (x.shape[1] if block == 0 else 3 * width)) if i < L - 2 else \
+            (3 * width if i == L - 2 else rows(layers[L - 2][0]))
+        if (weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[1:]) != (cin, k, k)
+                or (i < L - 2 and weight.shape[0] != width)):
+            raise _capi.RtposeError("%s: layer %d: fp32 OIHW filters [%s, %d, %d, %d] (a dense block is three 3x3 convs of "
+                                    "layer 0's width %d, the first on the stage input or on the 3 x %d channels of the block "
+                                    "before; Mconv6 and Mconv7 are 1x1); got %s %s"
+                                    % (who, i, width if i < L - 2 else "cout", cin, k, k, width, width, weight.dtype,
+                                       tuple(weight.shape)))
+        cout = weight.shape[0]
+        if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (cout,)
+                                 or bias.device != weight.device):
+            raise _capi.RtposeError("%s: layer %d: the bias is None or an fp32 [%d] tensor beside the filters" % (who, i, cout))
+        if i == L - 1:
+            if slope is not None:
+                raise _capi.RtposeError("%s: layer %d (Mconv7) has no activation: its slope must be None" % (who, i))
+        elif slope is None:
+            raise _capi.RtposeError("%s: layer %d has a PReLU: its slope is missing" % (who, i))
+        elif (not torch.is_tensor(slope) or slope.dtype != torch.float32 or tuple(slope.shape) != (cout,)
+              or slope.device != weight.device):
+            raise _capi.RtposeError("%s: layer %d: the slope is the fp32 [%d] weight of an nn.PReLU(num_parameters=%d) on the "
+                                    "filters' device %s; got %s"
+                                    % (who, i, cout, cout, weight.device,
+                                       "%s %s on %s" % (slope.dtype, tuple(slope.shape), slope.device)
+                                       if torch.is_tensor(slope) else type(slope).__name__))
+
+
+class _DenseStage(torch.autograd.Function):
+    """dense_stage's node.  Inputs: x, (epoch, resync), then weight, bias (or None) and slope (None for the last) of every
+    layer.  Layer i < 3 B is conv (b, j) = divmod(i, 3) of the dense blocks, 3 B is Mconv6, 3 B + 1 is Mconv7."""
+    @staticmethod
+    def forward(ctx, x, meta, *params):
+        epoch, resync = meta
+        weights, biases, slopes = params[0::3], params[1::3], params[2::3]
+        L = len(weights)
+        B = (L - 2) // 3
+        width, c6, cout = weights[0].shape[0], weights[L - 2].shape[0], weights[L - 1].shape[0]
+        with torch.cuda.device(x.device):
+            n, cin, h, w = x.shape
+            dev = x.device
+            xbuf, lx = _to_layout(x.detach().contiguous(), 1, True)
+            lz = _capi.Layout.dense(width, h, w)
+            lcat = _capi.Layout.padded(3 * width, h, w, 1)              # a block's concat buffer, whole
+            lsl = [_capi.Layout.padded(3 * width, h, w, 1, j * width) for j in range(3)]     # and its three slices
+            ybufs, zbufs = [], []
+            src, lsrc, csrc = xbuf, lx, lx.cstride
+            for b in range(B):
+                ycat = _buffer(lcat, n, h, w, dev, True, True)
+                for j in range(3):
+                    i = 3 * b + j
+                    wp, bp = _packed_for(weights[i], biases[i], 'fwd16', epoch, resync)
+                    z = _buffer(lz, n, h, w, dev, False)
+                    inp, lin, cin_p = (src, lsrc, csrc) if j == 0 else (ycat, lsl[j - 1], width)
+                    if not _dense_conv_into(True, inp, lin, wp, bp, cin_p, width, 3, False, n, h, w, z, lz, out_f32=1):
+                        raise _DenseRefused()
+                    _prelu_bf16(z, lz, slopes[i], ycat, lsl[j], width, n, h, w)
+                    zbufs.append(z)
+                ybufs.append(ycat)
+                src, lsrc, csrc = ycat, lcat, 3 * width
+            wp, bp = _packed_for(weights[L - 2], biases[L - 2], 'fwd16', epoch, resync)
+            lz6 = _capi.Layout.dense(c6, h, w)
+            z6 = _buffer(lz6, n, h, w, dev, False)
+            if not _dense_conv_into(True, src, lsrc, wp, bp, csrc, c6, 1, False, n, h, w, z6, lz6, out_f32=1):
+                raise _DenseRefused()
+            y6 = _buffer(lz6, n, h, w, dev, True, True)
+            _prelu_bf16(z6, lz6, slopes[L - 2], y6, lz6, c6, n, h, w)
+            zbufs.append(z6)
+            wp, bp = _packed_for(weights[L - 1], biases[L - 1], 'fwd16', epoch, resync)
+            lo = _capi.Layout.dense(_up8(cout), h, w)
+            obuf = _buffer(lo, n, h, w, dev, False)
+            if not _dense_conv_into(True, y6, lz6, wp, bp, c6, cout, 1, False, n, h, w, obuf, lo, out_f32=1):
+                raise _DenseRefused()
+            y = _from_layout(obuf, lo, n, cout, h, w)
+        need = ctx.needs_input_grad
+        wants = [need[2 + 3 * i] or (biases[i] is not None and need[3 + 3 * i]) for i in range(L)]
+        need_a = [slopes[i] is not None and need[4 + 3 * i] for i in range(L)]
+        # the lowest layer whose backward anything needs: the walk stops there
+        low = 0 if need[0] else next((i for i in range(L) if wants[i] or need_a[i]), L)
+        ctx.geom = (n, cin, h, w)
+        ctx.meta = meta
+        ctx.weights, ctx.slopes = weights, slopes
+        ctx.has_bias = [b is not None for b in biases]
+        ctx.low, ctx.wants, ctx.need_a = low, wants, need_a
+        # (for autograd's check that the filters and slopes were not modified in place since)
+        ctx.save_for_backward(*(weights + tuple(s for s in slopes if s is not None)))
+        # the fp32 pre-activations from the lowest layer up, and a bf16 input buffer where a weight gradient reads it
+        ctx.zbufs = [z if i >= low else None for i, z in enumerate(zbufs)]
+        ctx.xbuf, ctx.lx = (xbuf, lx) if wants[0] else (None, None)
+        ctx.ybufs = [yc if any(wants[3 * b + 1:3 * b + 4]) else None for b, yc in enumerate(ybufs)]
+        ctx.y6 = y6 if wants[L - 1] else None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        epoch, resync = ctx.meta
+        ctx.saved_tensors
+        weights, slopes, low, wants, need_a = ctx.weights, ctx.slopes, ctx.low, ctx.wants, ctx.need_a
+        L = len(weights)
+        B = (L - 2) // 3
+        n, cin0, h, w = ctx.geom
+        need_x = ctx.needs_input_grad[0]
+        grads = [None] * (3 * L)
+        dx = None
+        if low >= L:
+            return (None, None) + tuple(grads)
+        width, c6 = weights[0].shape[0], weights[L - 2].shape[0]
+        with torch.cuda.device(gy.device):
+            dev = gy.device
+            lz, lz6 = _capi.Layout.dense(width, h, w), _capi.Layout.dense(c6, h, w)
+            lcat = _capi.Layout.padded(3 * width, h, w, 1)
+            lsl = [_capi.Layout.padded(3 * width, h, w, 1, j * width) for j in range(3)]
+            ldc = [_capi.Layout.dense(3 * width, h, w, j * width) for j in range(3)]    # the slices of a concat gradient
+
+            def weight_grads(i, inp, lin, g, lg):
+                if wants[i]:
+                    wt = weights[i]
+                    need_b = ctx.has_bias[i] and ctx.needs_input_grad[3 + 3 * i]
+                    dw, db = _wgrad(True, inp, lin, g, lg, wt, wt.shape[1], wt.shape[0], wt.shape[2], n, h, w, need_b)
+                    grads[3 * i] = dw if ctx.needs_input_grad[2 + 3 * i] else None
+                    grads[3 * i + 1] = db
+
+            def data_grad(i, g, lg):
+                """the conv of the bf16 gradient g on the flipped, transposed filter of layer i into a new dense fp32
+                buffer: (buffer, layout)"""
+                wt = weights[i]
+                cout, cin, k = wt.shape[0], wt.shape[1], wt.shape[2]
+                wp, bp = _packed_for(wt, None, 'bwd16', epoch, resync)
+                ld = _capi.Layout.dense(_up8(cin), h, w)
+                d = _buffer(ld, n, h, w, dev, False)
+                if _dense_conv_into(True, g, lg, wp, bp, lg.cstride, cin, k, False, n, h, w, d, ld, out_f32=1):
+                    return d, ld
+                # refused: this one conv in fp32 on the widened gradient
+                bf16_fallbacks['dgrad'] += 1
+                l32 = _capi.Layout.padded(_up8(cout), h, w, k // 2)
+                g32 = _buffer(l32, n, h, w, dev, True)
+                check(lib.rtpose_layout_bf16_to_f32(ptr(g), C.byref(lg), ptr(g32), C.byref(l32), cout, n, h, w,
+                                                    current_stream()), "rtpose_layout_bf16_to_f32")
+                wp, bp = _packed_for(wt, None, 'bwd', epoch, resync)
+                return _launch_conv(False, g32, l32, wp, bp, l32.cstride, cin, k, False, n, h, w)
+
+            # Mconv7: no activation behind it, gy is rounded as it enters
+            g, lg = _to_layout(gy.detach().float().contiguous(), 0, True)
+            weight_grads(L - 1, ctx.y6, lz6, g, lg)
+            if low < L - 1:
+                d, ld = data_grad(L - 1, g, lg)
+                # Mconv6
+                g = _buffer(lz6, n, h, w, dev, True, True)
+                grads[3 * (L - 2) + 2] = _prelu_grad_bf16(ctx.zbufs[L - 2], lz6, slopes[L - 2], d, ld, None, None, g, lz6, c6,
+                                                          n, h, w, need_a[L - 2])
+                weight_grads(L - 2, ctx.ybufs[B - 1], lcat, g, lz6)
+            if low < L - 2:
+                dc, _ = data_grad(L - 2, g, lz6)     # the gradient of the last block's concat: dense fp32, 3 x width
+                # every 3x3 conv's gradient goes through ONE bf16 buffer gapped by 1: a launch writes all its valid pixels
+                # and none of its gaps, which stay the zeros they were made
+                lg = _capi.Layout.padded(width, h, w, 1)
+                g = _buffer(lg, n, h, w, dev, True, True)
+                d = ld = None
+                for i in range(L - 3, low - 1, -1):
+                    b, j = divmod(i, 3)
+                    # the activation of conv (b, j) is read by the concat and, for j < 2, by conv (b, j + 1) as well
+                    grads[3 * i + 2] = _prelu_grad_bf16(ctx.zbufs[i], lz, slopes[i], dc, ldc[j], d if j < 2 else None,
+                                                        ld if j < 2 else None, g, lg, width, n, h, w, need_a[i])
+                    if j:
+                        weight_grads(i, ctx.ybufs[b], lsl[j - 1], g, lg)
+                    elif b:
+                        weight_grads(i, ctx.ybufs[b - 1], lcat, g, lg)
+                    else:
+                        weight_grads(i, ctx.xbuf, ctx.lx, g, lg)
+                    if i == low and not (i == 0 and need_x):
+                        break
+                    if j:
+                        d, ld = data_grad(i, g, lg)
+                    elif b:
+                        dc, _ = data_grad(i, g, lg)   # the gradient of the concat of the block below
+                    else:
+                        d, ld = data_grad(i, g, lg)
+                        dx = _from_layout(d, ld, n, cin0, h, w)
+        return (dx, None) + tuple(grads)
+
+
+def _dense_per_conv(x, layers, epoch, resync):
+    """the stage through conv2d(compute_dtype='bf16') and torch.cat: what dense_stage falls back to"""
+    L = len(layers)
+    for b in range((L - 2) // 3):
+        outs = []
+        for wt, bias, slope in layers[3 * b:3 * b + 3]:
+            x = conv2d(x, wt, bias, False, epoch, resync, slope, 'bf16')
+            outs.append(x)
+        x = torch.cat(outs, 1)
+    for wt, bias, slope in layers[L - 2:]:
+        x = conv2d(x, wt, bias, False, epoch, resync, slope, 'bf16')
+    return x
+
+
+def dense_stage(x, layers, epoch=0, resync=False):
+    """A ``StageBlock`` of an ``OpenPose_Model`` (lib/network/openpose.py:86-109) as ONE autograd node, bf16 operands: B
+    dense blocks of three 3x3 convs with PReLU whose outputs are concatenated, the 1x1 conv Mconv6 with PReLU, the 1x1
+    conv Mconv7.  `x`: NCHW fp32 on the device; `layers`: 3 B + 2 triples (weight, bias_or_None, slope_or_None) in that
+    order - the first conv of a block reads x or the 3 C channels of the block before, the other two C channels; every slope
+    the fp32 [cout] weight of an ``nn.PReLU``, None for Mconv7.  Returns Mconv7's output, NCHW fp32.  `epoch` / `resync`: see
+    ``conv2d``; the packings are the cached 'fwd16' / 'bwd16' ones.
+
+    Every conv launch is ``conv2d(compute_dtype='bf16')``'s: ``rtpose_conv2d_bf16(out_f32 = 1)`` forward and data gradient,
+    ``rtpose_conv2d_wgrad_bf16``.  What lies between them is two kernels.  Forward: x is converted once
+    (``rtpose_nchw_to_layout_bf16``, gap 1); a block has ONE zero-initialised bf16 buffer of 3 C channels (gap 1): conv
+    (b, j) reads x or the whole buffer of the block before (j = 0) or slice j - 1 of its own block's, writes its fp32
+    pre-activation z into a dense buffer - the only fp32 activation kept - and ``rtpose_prelu_bf16`` writes slice j.  The
+    concat is never made: it is the buffer.  Mconv6 reads the last one whole; Mconv7's fp32 output leaves through one
+    ``rtpose_layout_to_nchw``.  Backward: gy is converted once; a layer's bf16 output gradient is
+    ``rtpose_prelu_grad_bf16`` of its z and the fp32 data gradient(s) of its consumer(s) - the slice of the concat's
+    gradient and, for the first two convs of a block, the next conv's as well, summed in fp32 as autograd sums them -; its
+    weight gradient reads the kept bf16 slice, its data gradient is a dense fp32 buffer.  The walk stops at the lowest
+    layer anything needs, a slope gradient is computed only where that slope requires one, dx only if x does.
+
+    The rounding points are the per-conv path's: the fp32 PReLU output rounded at the store is what the next conv's input
+    conversion made of it, the fp32 PReLU gradient rounded at the store is ``rtpose_layout_f32_to_bf16`` of it.
+
+    The stage gives up residency - it runs conv by conv through ``conv2d`` and ``torch.cat``, and ``dense_fallbacks``
+    counts it - when C or Mconv6's width is no multiple of 16 (the bf16 conv reads 16-channel groups: a slice must own
+    its groups), decided before any launch, or when ``rtpose_conv2d_bf16`` refuses a forward conv (it refuses before
+    launching; the node's earlier launches are abandoned).  A refused data gradient runs that one conv in fp32 on the
+    widened gradient (``rtpose_layout_bf16_to_f32``) and is counted in ``bf16_fallbacks['dgrad']``."""
+    global dense_fallbacks
+    layers = [tuple(layer) if isinstance(layer, (tuple, list)) else layer for layer in layers]
+    _check_dense(x, layers)
+    epoch, resync = int(epoch), bool(resync)
+    if layers[0][0].shape[0] % 16 == 0 and layers[-2][0].shape[0] % 16 == 0:
+        try:
+            return _DenseStage.apply(x, (epoch, resync), *[p for layer in layers for p in layer])
+        except _DenseRefused:
+            pass
+    dense_fallbacks += 1
+    return _dense_per_conv(x, layers, epoch, resync)
+
+
 # ---- the stacked hourglass: its stem and training-mode BatchNorm -------------------------------------------------------------
 class _Conv7x7S2(torch.autograd.Function):
     @staticmethod
@@ -955,16 +1257,32 @@ def _forward_train_vgg(model, x, epoch, resync, dt, resident=False):
     return (saved_for_loss[10], saved_for_loss[11]), saved_for_loss
 
 
-def _forward_train_openpose(model, x, epoch, resync, dt):
-    features = run_sequential(model.feature_extractor, x, epoch, resync, dt)
+def _dense_stage_block(st, x, epoch, resync, dt):
+    """openpose.StageBlock.forward as one ``dense_stage`` node (bf16)"""
+    blocks = [blk for _, blk in st.conv_blocks()]
+    for blk in blocks:
+        _check_same_conv(blk.Mconv)
+        if blk.MPrelu.num_parameters != blk.Mconv.out_channels:
+            raise _capi.RtposeError("train: a PReLU behind a conv has one slope per output channel (num_parameters = %d); "
+                                    "got %r behind %r" % (blk.Mconv.out_channels, blk.MPrelu, blk.Mconv))
+    _check_same_conv(st.Mconv7)
+    layers = [(blk.Mconv.weight, blk.Mconv.bias, blk.MPrelu.weight) for blk in blocks]
+    return dense_stage(x, layers + [(st.Mconv7.weight, st.Mconv7.bias, None)], epoch, resync)
+
+
+def _forward_train_openpose(model, x, epoch, resync, dt, dense=False):
+    """`dense`: every StageBlock as one ``dense_stage`` node, the ReLU runs of feature_extractor as ``conv_chain`` nodes (its
+    three PReLU convs stay ``conv2d``'s); the torch.cat between the stages stays torch's"""
+    stage = _dense_stage_block if dense else _stage_block
+    features = run_sequential(model.feature_extractor, x, epoch, resync, dt, dense)
     paf_ret, heat_ret = [], []
     x_in = features
     for st in model.l2_stages:
-        paf_pred = _stage_block(st, x_in, epoch, resync, dt)
+        paf_pred = stage(st, x_in, epoch, resync, dt)
         x_in = torch.cat([features, paf_pred], 1)
         paf_ret.append(paf_pred)
     for st in model.l1_stages:
-        heat_pred = _stage_block(st, x_in, epoch, resync, dt)
+        heat_pred = stage(st, x_in, epoch, resync, dt)
         x_in = torch.cat([features, heat_pred, paf_pred], 1)
         heat_ret.append(heat_pred)
     return [(paf_ret[-2], heat_ret[-2]), (paf_ret[-1], heat_ret[-1])], [paf_ret, heat_ret]
@@ -1152,13 +1470,35 @@ _NOT_RESIDENT = {
 }
 
 
+# why forward_train(resident='dense') refuses the networks that are not an OpenPose_Model
+_NOT_DENSE = {
+    'vgg': "a network.RtposeVGG has no dense blocks and no PReLU: its runs of convs are conv_chain's (resident=True)",
+    'hourglass': _NOT_RESIDENT['hourglass'].replace("conv_chain runs convs with one consumer and a ReLU or no activation",
+                                                    "dense_stage runs the dense blocks of an openpose.StageBlock"),
+    'shufflenet': _NOT_RESIDENT['shufflenet'].replace("conv_chain runs convs with one consumer and a ReLU or no activation",
+                                                      "dense_stage runs the dense blocks of an openpose.StageBlock"),
+}
+
+
+def _check_resident(who, resident):
+    """`resident` is False, True or 'dense': whether it is 'dense'"""
+    if isinstance(resident, str):
+        if resident == 'dense':
+            return True
+    elif resident in (False, True):
+        return False
+    raise _capi.RtposeError("%s: resident is False, True or 'dense'; got %r" % (who, resident))
+
+
 def forward_train(model, x, compute_dtype='fp32', resident=False):
     """The reference's forward over the module tree of `model`, with an autograd graph behind the outputs.
     `compute_dtype`: 'fp32', or 'bf16' (``conv2d``) for an ``RtposeVGG`` or an ``OpenPose_Model``; refused for the other two,
     whose BatchNorm and depthwise kernels are fp32.
-    `resident`: for an ``RtposeVGG`` only - every run of convs between two pools of model0 and each stage branch is one
+    `resident`: True, for an ``RtposeVGG`` only - every run of convs between two pools of model0 and each stage branch is one
     ``conv_chain`` node whose inner activations and gradients stay in the layouts; refused for the other three (why: the
-    message).  The default False is the per-conv path, launch for launch.
+    message).  'dense', for an ``OpenPose_Model`` with ``compute_dtype='bf16'`` only - every ``StageBlock`` is one
+    ``dense_stage`` node, feature_extractor runs as under ``run_sequential(resident=True)``; refused for the other three
+    and for 'fp32'.  Any other value is refused.  The default False is the per-conv path, launch for launch.
     ``RtposeVGG`` (lib/network/rtpose_vgg.py:158-198): ((out6_1, out6_2), saved_for_loss[12]).
     ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177):
     ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]).
@@ -1173,7 +1513,16 @@ def forward_train(model, x, compute_dtype='fp32', resident=False):
         raise _capi.RtposeError("train.forward_train: compute_dtype=%r is for a network.RtposeVGG or an openpose.OpenPose_Model; "
                                 "the BatchNorm%s kernels a %s trains through are fp32 and take no compute dtype"
                                 % (compute_dtype, " and depthwise" if kind == 'shufflenet' else "", type(model).__name__))
-    if resident and kind != 'vgg':
+    dense = _check_resident("train.forward_train", resident)
+    if dense:
+        if kind != 'openpose':
+            raise _capi.RtposeError("train.forward_train: resident='dense' is for an openpose.OpenPose_Model only; "
+                                    + _NOT_DENSE[kind])
+        if compute_dtype != 'bf16':
+            raise _capi.RtposeError("train.forward_train: resident='dense' needs compute_dtype='bf16': dense_stage keeps bf16 "
+                                    "activations and gradients in the layouts, and an fp32 node is not built; got "
+                                    "compute_dtype=%r" % (compute_dtype,))
+    elif resident and kind != 'vgg':
         raise _capi.RtposeError("train.forward_train: resident=True is for a network.RtposeVGG only; " + _NOT_RESIDENT[kind])
     if not x.is_cuda:
         raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there is "
@@ -1186,7 +1535,7 @@ def forward_train(model, x, compute_dtype='fp32', resident=False):
     epoch, resync = getattr(model, '_weights_epoch', [0])[0], bool(getattr(model, 'always_resync', False))
     if kind == 'vgg':
         return _forward_train_vgg(model, x, epoch, resync, compute_dtype, bool(resident))
-    return _forward_train_openpose(model, x, epoch, resync, compute_dtype)
+    return _forward_train_openpose(model, x, epoch, resync, compute_dtype, dense)
 
 
 def freeze_trunk(model, n=20):
