@@ -276,7 +276,7 @@ int rtpose_prelu_grad(const float* z, const rtpose_layout* lz, const float* slop
                       const rtpose_layout* lgy, float* out, const rtpose_layout* lout, float* dslope,
                       float* workspace, size_t workspace_floats, int channels, int N, int H, int W, void* stream);
 
-/* ---- 2b, continued.  PReLU between the bf16 convs of a layout-resident training run (csrc/prelu_bf16.hip;
+/* ---- 2b, continued.  PReLU between the bf16 convs of a layout-resident training run (csrc/prelu_backward.hip;
  * train.dense_stage): the two passes above with the rounding of rtpose_layout_f32_to_bf16 at their store, so that the
  * fp32 y and the fp32 masked gradient never exist.  `z`, `ga`, `gb` are fp32 slices; `y` / `out` are 2-byte bf16 slices
  * whose layouts count ELEMENTS.  Gaps and the channels beside the slices are neither read nor written, so a
@@ -426,7 +426,7 @@ int rtpose_dwconv3x3_dgrad(const float* gy, const rtpose_layout* lgy, const floa
                            int N, int H, int W, int stride, void* stream);
 
 /* ---- 2b, continued.  Mixed-precision training: the weight gradient (+ bias gradient) of a stride-1 "same" conv,
- * k in {1, 3, 7}, from bf16 layout slices (csrc/conv_backward_bf16.hip; train.conv2d(compute_dtype='bf16')).  The forward
+ * k in {1, 3, 7}, from bf16 layout slices (csrc/conv_backward.hip; train.conv2d(compute_dtype='bf16')).  The forward
  * and the data gradient of such a step are rtpose_conv2d_bf16 (out_f32 = 1); this is the third kernel.  The reference has
  * no reduced-precision training: the contract is this project's.
  *     dw[o][c][dy][dx] = sum over (n, y, x) of gy[n, y, x, o] * x[n, y + dy - k/2, x + dx - k/2, c]

@@ -122,14 +122,6 @@ bool aligned16_bf16(const rtpose_layout& l, const void* base) {
   return slice_aligned(l, 8) && reinterpret_cast<uintptr_t>(base) % 16 == 0;
 }
 
-// the bytes [first, last) the valid pixels' slices of a layout span
-void span_bytes(const void* base, const rtpose_layout& l, int channels, int N, int H, int W, uintptr_t& first, uintptr_t& last) {
-  const size_t lo = (size_t)l.lead * l.cstride + l.choff;
-  const size_t hi = ((size_t)l.lead + ((size_t)(N - 1) * l.hs + (H - 1)) * l.ws + (W - 1)) * l.cstride + l.choff + channels;
-  first = reinterpret_cast<uintptr_t>(base) + 2 * lo;
-  last = reinterpret_cast<uintptr_t>(base) + 2 * hi;
-}
-
 bool same_slice(const void* a, const rtpose_layout& la, const void* b, const rtpose_layout& lb) {
   return a == b && la.cstride == lb.cstride && la.choff == lb.choff && la.ws == lb.ws && la.hs == lb.hs && la.lead == lb.lead;
 }
@@ -141,8 +133,8 @@ bool out_apart(const void* out, const rtpose_layout& lo, const void* in, const r
   if (out == in && lo.cstride == li.cstride && lo.ws == li.ws && lo.hs == li.hs && lo.lead == li.lead)
     return lo.choff + channels <= li.choff || li.choff + channels <= lo.choff;
   uintptr_t o0, o1, i0, i1;
-  span_bytes(out, lo, channels, N, H, W, o0, o1);
-  span_bytes(in, li, channels, N, H, W, i0, i1);
+  slice_span_bytes(out, lo, 2, channels, N, H, W, o0, o1);
+  slice_span_bytes(in, li, 2, channels, N, H, W, i0, i1);
   return o1 <= i0 || i1 <= o0;
 }
 

@@ -1,5 +1,5 @@
 // The deterministic per-channel sum of the training kernels (prelu_backward.hip, batchnorm.hip, dwconv_backward.hip), and
-// the element-wise passes that walk the same way.
+// the element-wise passes that walk the same way (prelu_backward.hip's forwards, act_grad_bf16.hip).
 //
 // The valid pixels p = (n * H + y) * W + x of a map are cut into slabs whose size follows from the shape alone
 // (slab_geometry: equal multiples of 64 pixels but for the last one, across image boundaries).  A workgroup of 256 threads
@@ -51,6 +51,15 @@ inline SlabGeom slab_geometry(long P) {
 
 inline bool aligned16(const rtpose_layout& l, const void* base) {
   return slice_aligned(l, 4) && reinterpret_cast<uintptr_t>(base) % 16 == 0;
+}
+
+// the bytes [first, last) the valid pixels' slices of a layout of `esize`-byte elements span
+inline void slice_span_bytes(const void* base, const rtpose_layout& l, int esize, int channels, int N, int H, int W,
+                             uintptr_t& first, uintptr_t& last) {
+  const size_t lo = (size_t)l.lead * l.cstride + l.choff;
+  const size_t hi = ((size_t)l.lead + ((size_t)(N - 1) * l.hs + (H - 1)) * l.ws + (W - 1)) * l.cstride + l.choff + channels;
+  first = reinterpret_cast<uintptr_t>(base) + (size_t)esize * lo;
+  last = reinterpret_cast<uintptr_t>(base) + (size_t)esize * hi;
 }
 
 // P = pixel_count of a non-empty tensor; 0 or fail(...)

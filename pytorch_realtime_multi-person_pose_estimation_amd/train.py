@@ -248,6 +248,20 @@ def _launch_conv(bf16, inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w):
     return (out, lout) if _conv_launch(bf16, inp, lin, wp, bp, cin_p, cout, k, relu, n, h, w, out, lout, 1) else None
 
 
+def _dgrad_fp32_fallback(g, lg, wt, n, h, w, epoch, resync):
+    """the data gradient of one conv whose bf16 launch was refused: the bf16 gradient g widened
+    (rtpose_layout_bf16_to_f32) and convolved in fp32 on the flipped, transposed filter of `wt` into a new dense fp32
+    buffer, (buffer, layout); counted in ``bf16_fallbacks['dgrad']``"""
+    cout, cin, k = wt.shape[0], wt.shape[1], wt.shape[2]
+    bf16_fallbacks['dgrad'] += 1
+    l32 = _capi.Layout.padded(_up8(cout), h, w, k // 2)
+    g32 = _buffer(l32, n, h, w, g.device, True)
+    check(lib.rtpose_layout_bf16_to_f32(ptr(g), C.byref(lg), ptr(g32), C.byref(l32), cout, n, h, w, current_stream()),
+          "rtpose_layout_bf16_to_f32")
+    wp, bp = _packed_for(wt, None, 'bwd', epoch, resync)
+    return _launch_conv(False, g32, l32, wp, bp, l32.cstride, cin, k, False, n, h, w)
+
+
 def _wgrad(bf16, xbuf, lx, gbuf, lg, like_weight, cin, cout, k, n, h, w, need_b):
     """rtpose_conv2d_wgrad - `bf16`: rtpose_conv2d_wgrad_bf16 - of the layout buffers of x and of the output gradient (an
     h x w map, gaps of k // 2; both fp32 or both bf16): (dw shaped like `like_weight`, db or None), fp32"""
@@ -548,13 +562,7 @@ class _ConvChain(torch.autograd.Function):
                 d, ld = _chain_buffer(bf16, cin, weights[i - 1].shape[2] if i > 0 else None, n, h, w, dev)
                 if not _conv_into(bf16, g, lg, wp, bp, lg.cstride, cin, k, False, n, h, w, d, ld, out_f32=i == 0):
                     # refused: this one conv in fp32 on the widened gradient, rounded again at its store inside the chain
-                    bf16_fallbacks['dgrad'] += 1
-                    l32 = _capi.Layout.padded(_up8(cout), h, w, k // 2)
-                    g32 = _buffer(l32, n, h, w, dev, True)
-                    check(lib.rtpose_layout_bf16_to_f32(ptr(g), C.byref(lg), ptr(g32), C.byref(l32), cout, n, h, w,
-                                                        current_stream()), "rtpose_layout_bf16_to_f32")
-                    wp, bp = _packed_for(wt, None, 'bwd', epoch, resync)
-                    d32, ld32 = _launch_conv(False, g32, l32, wp, bp, l32.cstride, cin, k, False, n, h, w)
+                    d32, ld32 = _dgrad_fp32_fallback(g, lg, wt, n, h, w, epoch, resync)
                     d, ld = _round_to_bf16(d32, ld32, cin, n, h, w, into=(d, ld)) if i > 0 else (d32, ld32)
                 if i == 0:
                     dx = _from_layout(d, ld, n, cin, h, w)
@@ -797,20 +805,14 @@ class _DenseStage(torch.autograd.Function):
                 """the conv of the bf16 gradient g on the flipped, transposed filter of layer i into a new dense fp32
                 buffer: (buffer, layout)"""
                 wt = weights[i]
-                cout, cin, k = wt.shape[0], wt.shape[1], wt.shape[2]
+                cin, k = wt.shape[1], wt.shape[2]
                 wp, bp = _packed_for(wt, None, 'bwd16', epoch, resync)
                 ld = _capi.Layout.dense(_up8(cin), h, w)
                 d = _buffer(ld, n, h, w, dev, False)
                 if _dense_conv_into(True, g, lg, wp, bp, lg.cstride, cin, k, False, n, h, w, d, ld, out_f32=1):
                     return d, ld
                 # refused: this one conv in fp32 on the widened gradient
-                bf16_fallbacks['dgrad'] += 1
-                l32 = _capi.Layout.padded(_up8(cout), h, w, k // 2)
-                g32 = _buffer(l32, n, h, w, dev, True)
-                check(lib.rtpose_layout_bf16_to_f32(ptr(g), C.byref(lg), ptr(g32), C.byref(l32), cout, n, h, w,
-                                                    current_stream()), "rtpose_layout_bf16_to_f32")
-                wp, bp = _packed_for(wt, None, 'bwd', epoch, resync)
-                return _launch_conv(False, g32, l32, wp, bp, l32.cstride, cin, k, False, n, h, w)
+                return _dgrad_fp32_fallback(g, lg, wt, n, h, w, epoch, resync)
 
             # Mconv7: no activation behind it, gy is rounded as it enters
             g, lg = _to_layout(gy.detach().float().contiguous(), 0, True)

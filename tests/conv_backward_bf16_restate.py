@@ -1,4 +1,4 @@
-"""Host restatement of mixed-precision training (header section 2b, continued; csrc/conv_backward_bf16.hip;
+"""Host restatement of mixed-precision training (header section 2b, continued; csrc/conv_backward.hip;
 train.conv2d(compute_dtype='bf16')): where a bf16 step rounds, stated in float64 on the CPU, the slab rule of the bf16 weight
 gradient, and the cases the GPU tests run.  torch CPU + numpy only: no GPU, no library call.  The float64 gradients, the
 bound factor gamma and the integer operands are those of tests/conv_backward_restate.py.
@@ -17,6 +17,8 @@ import torch
 import torch.nn.functional as F
 
 from conv_backward_restate import gamma, wgrad64, dbias64, dgrad64, exact_tensors  # noqa: F401  (re-exported)
+from conv_backward_restate import (FAKE, FAULT_H, FAULT_N, FAULT_W, WGRAD_FAULTS, set_field, set_layout,  # noqa: F401
+                                   wgrad_null_empty_and_launch_limits, wgrad_passes_the_host_checks, wgrad_refused)
 
 U = 2.0 ** -24
 
@@ -25,7 +27,7 @@ def rb(t):
     return t.to(torch.bfloat16).float()
 
 
-# ---- the slab rule of csrc/conv_backward_bf16.hip (wgrad_geometry), restated ------------------------------------------------------
+# ---- the slab rule of csrc/conv_backward.hip (wgrad_geometry), restated ------------------------------------------------------
 CHUNK = 64            # pixels per LDS chunk: 4 MFMA steps of K = 16
 MIN_SLAB = 512
 TARGET_BLOCKS = 1024

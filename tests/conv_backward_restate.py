@@ -141,3 +141,97 @@ def exact_margin(c, seed=0):
     s_y = F.conv2d(x.double().abs(), wt.double().abs(), bias.double().abs(), padding=c.k // 2)
     return max(wgrad64(x, gy, c.k)[1].max().item(), dbias64(gy)[1].max().item(), dgrad64(gy, wt)[1].max().item(),
                s_y.max().item())
+
+
+# ---- the host refusals rtpose_conv2d_wgrad and rtpose_conv2d_wgrad_bf16 share (csrc/conv_backward.hip: one host path) ----------
+# Each test file brings its own base(capi, k, cin, cout) descriptor - fake pointers, lx = padded(40, H, W, k // 2, 8), lgy =
+# padded(48, H, W, 0, choff) - and runs every row on its entry point.  (name, fault(d), text the message holds)
+def set_field(field, value):
+    def f(d):
+        setattr(d, field, value)
+    return f
+
+
+def set_layout(which, field, value):
+    def f(d):
+        setattr(getattr(d, which), field, value)
+    return f
+
+
+def _small_ws(d):
+    d.workspace_floats -= 1
+
+
+def _gy_past_cstride(d):
+    d.cout = d.lgy.cstride - d.lgy.choff + 1        # (45 on the fp32 base, 41 on the bf16 one)
+
+
+FAULT_N, FAULT_H, FAULT_W = 2, 9, 7
+FAKE = 1 << 20          # a 16-byte aligned "device pointer" no refused launch touches
+
+WGRAD_FAULTS = [
+    ("null x", set_field("x", None), "NULL x"),
+    ("null gy", set_field("gy", None), "NULL gy"),
+    ("null dw", set_field("dw", None), "NULL dw"),
+    ("null workspace", set_field("workspace", None), "NULL workspace"),
+    ("k = 5", set_field("k", 5), "k must be 1, 3 or 7"),
+    ("k = 0", set_field("k", 0), "k must be 1, 3 or 7"),
+    ("cin = 0", set_field("cin", 0), "cin and cout must be >= 1"),
+    ("cout = 0", set_field("cout", 0), "cin and cout must be >= 1"),
+    ("x slice past cstride", set_field("cin", 33), "input slice exceeds cstride"),
+    ("gy slice past cstride", _gy_past_cstride, "output-gradient slice exceeds cstride"),
+    ("row gap below k/2", set_layout("lx", "ws", FAULT_W), "gap smaller than the conv padding"),
+    ("image gap below k/2", set_layout("lx", "hs", FAULT_H), "gap smaller than the conv padding"),
+    ("lead below k/2", set_layout("lx", "lead", FAULT_W + 1), "gap smaller than the conv padding"),
+    ("gy rows shorter than the map", set_layout("lgy", "ws", FAULT_W - 1), "output-gradient layout smaller than the map"),
+    ("bad layout", set_layout("lgy", "cstride", 0), "bad layout"),
+    ("workspace too small", _small_ws, "workspace of"),
+    ("dw not 16-byte aligned", set_field("dw", FAKE + 4), "16-byte aligned"),
+    ("workspace not 16-byte aligned", set_field("workspace", FAKE + 8), "16-byte aligned"),
+]
+
+
+def wgrad_refused(capi, entry, who, d, shape, text):
+    """`entry` returns RTPOSE_E_INVAL with `text` in a message that names the entry point, before any pointer is looked at"""
+    import ctypes as C
+    rc = entry(C.byref(d) if d is not None else None, *shape, None)
+    err = capi.last_error()
+    assert rc == -1, (rc, err)                                # RTPOSE_E_INVAL, not a HIP error
+    assert text in err and err.startswith(who + ":"), err
+    assert "device memory" not in err                         # returned before the pointers were looked at
+
+
+def wgrad_null_empty_and_launch_limits(capi, entry, slabs, who, base):
+    """the NULL descriptor, each of the three empty shapes and the two shapes above the launch limit"""
+    n, h, w = FAULT_N, FAULT_H, FAULT_W
+    wgrad_refused(capi, entry, who, None, (n, h, w), "NULL descriptor")
+    d = base(capi)
+    for shape in ((0, h, w), (n, 0, w), (n, h, 0)):
+        wgrad_refused(capi, entry, who, d, shape, "empty tensor")
+    # a tensor whose pixels do not fit the kernels' int index: N * H * W >= 2^31 - 256
+    d = base(capi, k=1, cin=8, cout=8)
+    big = 1 << 16
+    d.lx = capi.Layout.padded(40, big, big, 0, 8)
+    d.lgy = capi.Layout.padded(48, big, big, 0, 8)
+    wgrad_refused(capi, entry, who, d, (1, big, big), "above the launch limit")
+    # a grid beyond the launch limits: the slab count is at most 1024 by the slab rule and taps at most 49, so the grid can only
+    # outgrow its limits along x, M tiles * N tiles - which needs taps * cout * cin >= 2^31 - 256, refused under the same text
+    c = 46344                                   # c * c > 2^31, a multiple of 8
+    assert slabs(8, 8, 1, 1, 1 << 15, 1 << 15) <= 1024
+    d = base(capi, k=1, cin=c, cout=c)
+    d.lx = capi.Layout.padded(c, h, w, 0, 0)
+    d.lgy = capi.Layout.padded(c, h, w, 0, 0)
+    d.workspace_floats = 1 << 62
+    wgrad_refused(capi, entry, who, d, (n, h, w), "above the launch limit")
+    assert slabs(c, c, 1, n, h, w) == 0
+
+
+def wgrad_passes_the_host_checks(capi, entry, base):
+    """k = 7 with a gap of exactly 3, with and without dbias, passes every host check: the refusal is then the pointer's
+    (fake: no device owns it)"""
+    import ctypes as C
+    for dbias in (FAKE, None):
+        d = base(capi, k=7)
+        d.dbias = dbias
+        rc = entry(C.byref(d), FAULT_N, FAULT_H, FAULT_W, None)
+        assert rc != 0 and "gap" not in capi.last_error() and "x" in capi.last_error()

@@ -1,5 +1,5 @@
 """Host restatement of the bf16 PReLU passes of a layout-resident training run (include/rtpose_mi355x.h section 2b continued,
-csrc/prelu_bf16.hip, train.dense_stage): rtpose_prelu_bf16 and rtpose_prelu_grad_bf16 as the restatements of
+csrc/prelu_backward.hip, train.dense_stage): rtpose_prelu_bf16 and rtpose_prelu_grad_bf16 as the restatements of
 tests/prelu_restate.py - a select or one numpy-float32 multiply, on the one numpy-float32 sum ga + gb - followed by
 layout_restate.bf16_rne, and the cases and operands tests/test_prelu_bf16_gpu.py runs.  torch CPU + numpy only: no GPU, no
 library call.

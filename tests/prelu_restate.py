@@ -194,3 +194,64 @@ def spec_margin(s):
     s_gz = m * G.abs()
     return max((m * s_z).max().item(), cb.dgrad64(s_gz, wt)[1].max().item(), cb.wgrad64(x, s_gz, s.k)[1].max().item(),
                cb.dbias64(s_gz)[1].max().item(), (s_z * G.abs()).sum((0, 2, 3)).max().item())
+
+
+# ---- the host refusals the four PReLU entry points share (csrc/prelu_backward.hip) ----------------------------------------------
+# rtpose_prelu, rtpose_prelu_grad, rtpose_prelu_bf16 and rtpose_prelu_grad_bf16 take the same kinds of argument at different
+# positions.  A test file describes its entry point's argument list - each slice as (name, index of the buffer, index of the
+# layout, index of the layout in `lays`, buffer may be NULL), the index of the slopes, of `channels` (N, H, W and the stream
+# follow it) and, for a gradient, of the workspace (workspace_floats follows it) - and shared_faults gives the rows that entry
+# point has: (name, fault(a, lays), text the message holds).
+FAULT_N, FAULT_H, FAULT_W, FAULT_CH = 2, 9, 7, 19
+
+
+def arg_fault(i, v):
+    def f(a, lays):
+        a[i] = v
+    return f
+
+
+def layout_fault(j, field, v):
+    def f(a, lays):
+        setattr(lays[j], field, v)
+    return f
+
+
+def _past_cstride(j):
+    def f(a, lays):
+        lays[j].choff = lays[j].cstride - FAULT_CH + 1
+    return f
+
+
+def above_launch_limit(a, lays):
+    """a map above the launch limit, in layouts that hold it"""
+    for lay in lays:
+        lay.ws, lay.hs, lay.lead = 1 << 15, 1 << 16, 0
+    a[-4:-1] = [1, 1 << 16, 1 << 15]
+
+
+def shared_faults(slices, slope, channels, workspace=None):
+    rows = []
+    for name, ib, il, j, optional in slices:
+        if not optional:
+            rows.append(("null " + name, arg_fault(ib, None), "NULL buffer (%s)" % name))
+        rows += [("null l" + name, arg_fault(il, None), "NULL layout (%s)" % name),
+                 (name + " bad layout", layout_fault(j, "cstride", 0), "bad layout (%s)" % name),
+                 (name + " slice past cstride", _past_cstride(j), "%s slice exceeds cstride" % name),
+                 (name + " rows shorter than the map", layout_fault(j, "ws", FAULT_W - 1), "layout smaller than the map (%s)" % name)]
+    rows += [("null slope", arg_fault(slope, None), "NULL buffer (slope)"),
+             ("no channels", arg_fault(channels, 0), "empty tensor"),
+             ("no images", arg_fault(channels + 1, 0), "empty tensor"),
+             ("above the launch limit", above_launch_limit, "above the launch limit")]
+    if workspace is not None:
+        rows += [("dslope without a workspace", arg_fault(workspace, None), "NULL workspace"),
+                 ("workspace too small", arg_fault(workspace + 1, 2 * FAULT_CH - 1), "workspace of")]
+    return rows
+
+
+def refused(capi, fn, who, a, text):
+    rc = fn(*a)
+    err = capi.last_error()
+    assert rc == -1, (rc, err)                                   # RTPOSE_E_INVAL, not a HIP error
+    assert text in err and err.startswith(who + ":"), err
+    assert "device memory" not in err                            # returned before the pointers were looked at

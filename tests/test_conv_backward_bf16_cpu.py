@@ -1,4 +1,4 @@
-"""CPU suite of mixed-precision training (header section 2b, continued; csrc/conv_backward_bf16.hip; train.py's
+"""CPU suite of mixed-precision training (header section 2b, continued; csrc/conv_backward.hip; train.py's
 compute_dtype): the host side of rtpose_conv2d_wgrad_bf16 - geometry queries, every refusal with its text, before any HIP
 call -, the exact cases' condition, the float64 emulation of tests/conv_backward_bf16_restate.py against torch's own autograd,
 and what train.py refuses without a launch."""
@@ -12,8 +12,8 @@ import torch.nn.functional as F
 import conv_backward_bf16_restate as cb
 from conftest import PKG_NAME
 
-FAKE = 1 << 20          # a 16-byte aligned "device pointer" no refused launch touches
-N, H, W = 2, 9, 7
+FAKE = cb.FAKE          # a 16-byte aligned "device pointer" no refused launch touches
+N, H, W = cb.FAULT_N, cb.FAULT_H, cb.FAULT_W
 
 
 @pytest.fixture(scope="module")
@@ -132,91 +132,36 @@ def base(capi, k=3, cin=24, cout=38):
     return d
 
 
-def _set(field, value):
-    def f(d):
-        setattr(d, field, value)
-    return f
-
-
-def _lay(which, field, value):
-    def f(d):
-        setattr(getattr(d, which), field, value)
-    return f
-
-
-def _small_ws(d):
-    d.workspace_floats -= 1
-
-
-WGRAD_FAULTS = [
-    ("null x", _set("x", None), "NULL x"),
-    ("null gy", _set("gy", None), "NULL gy"),
-    ("null dw", _set("dw", None), "NULL dw"),
-    ("null workspace", _set("workspace", None), "NULL workspace"),
-    ("k = 5", _set("k", 5), "k must be 1, 3 or 7"),
-    ("k = 0", _set("k", 0), "k must be 1, 3 or 7"),
-    ("cin = 0", _set("cin", 0), "cin and cout must be >= 1"),
-    ("cout = 0", _set("cout", 0), "cin and cout must be >= 1"),
-    ("x base not 16-byte aligned", _set("x", FAKE + 8), "input slice must be 16-byte aligned"),
-    ("gy base not 16-byte aligned", _set("gy", FAKE + 2), "output-gradient slice must be 16-byte aligned"),
-    ("x choff not a multiple of 8", _lay("lx", "choff", 4), "input slice must be 16-byte aligned"),
-    ("x cstride not a multiple of 8", _lay("lx", "cstride", 36), "input slice must be 16-byte aligned"),
-    ("gy choff not a multiple of 8", _lay("lgy", "choff", 4), "output-gradient slice must be 16-byte aligned"),
-    ("gy cstride not a multiple of 8", _lay("lgy", "cstride", 52), "output-gradient slice must be 16-byte aligned"),
-    ("x slice past cstride", _set("cin", 33), "input slice exceeds cstride"),
-    ("gy slice past cstride", _set("cout", 41), "output-gradient slice exceeds cstride"),
-    ("row gap below k/2", _lay("lx", "ws", W), "gap smaller than the conv padding"),
-    ("image gap below k/2", _lay("lx", "hs", H), "gap smaller than the conv padding"),
-    ("lead below k/2", _lay("lx", "lead", W + 1), "gap smaller than the conv padding"),
-    ("gy rows shorter than the map", _lay("lgy", "ws", W - 1), "output-gradient layout smaller than the map"),
-    ("bad layout", _lay("lgy", "cstride", 0), "bad layout"),
-    ("workspace too small", _small_ws, "workspace of"),
-    ("dw not 16-byte aligned", _set("dw", FAKE + 4), "16-byte aligned"),
-    ("workspace not 16-byte aligned", _set("workspace", FAKE + 8), "16-byte aligned"),
+# the rows both entry points share (tests/conv_backward_restate.py) and the alignment rows only the bf16 kernel's 16-byte
+# operand loads ask for
+BF16_FAULTS = [
+    ("x base not 16-byte aligned", cb.set_field("x", FAKE + 8), "input slice must be 16-byte aligned"),
+    ("gy base not 16-byte aligned", cb.set_field("gy", FAKE + 2), "output-gradient slice must be 16-byte aligned"),
+    ("x choff not a multiple of 8", cb.set_layout("lx", "choff", 4), "input slice must be 16-byte aligned"),
+    ("x cstride not a multiple of 8", cb.set_layout("lx", "cstride", 36), "input slice must be 16-byte aligned"),
+    ("gy choff not a multiple of 8", cb.set_layout("lgy", "choff", 4), "output-gradient slice must be 16-byte aligned"),
+    ("gy cstride not a multiple of 8", cb.set_layout("lgy", "cstride", 52), "output-gradient slice must be 16-byte aligned"),
 ]
+WGRAD_FAULTS = cb.WGRAD_FAULTS + BF16_FAULTS
 
 
 @pytest.mark.parametrize("name,fault,text", WGRAD_FAULTS, ids=[f[0] for f in WGRAD_FAULTS])
 def test_wgrad_bf16_refuses_on_the_host(capi, name, fault, text):
     d = base(capi)
     fault(d)
-    rc = capi.lib.rtpose_conv2d_wgrad_bf16(C.byref(d), N, H, W, None)
-    assert rc == -1, (name, rc, capi.last_error())            # RTPOSE_E_INVAL, not a HIP error
-    assert text in capi.last_error(), (name, capi.last_error())
-    assert "conv2d_wgrad_bf16" in capi.last_error()
-    assert "device memory" not in capi.last_error()           # returned before the pointers were looked at
+    cb.wgrad_refused(capi, capi.lib.rtpose_conv2d_wgrad_bf16, "conv2d_wgrad_bf16", d, (N, H, W), text)
 
 
 def test_wgrad_bf16_refuses_null_descriptor_empty_tensor_and_launch_limits(capi):
-    lib = capi.lib
-    assert lib.rtpose_conv2d_wgrad_bf16(None, N, H, W, None) == -1 and "NULL descriptor" in capi.last_error()
-    d = base(capi)
-    for shape in ((0, H, W), (N, 0, W), (N, H, 0)):
-        assert lib.rtpose_conv2d_wgrad_bf16(C.byref(d), *shape, None) == -1 and "empty tensor" in capi.last_error()
-    # a tensor whose pixels do not fit the kernels' int index: N * H * W >= 2^31 - 256
-    d = base(capi, k=1, cin=8, cout=8)
-    big = 1 << 16
-    d.lx = capi.Layout.padded(40, big, big, 0, 8)
-    d.lgy = capi.Layout.padded(48, big, big, 0, 8)
-    assert lib.rtpose_conv2d_wgrad_bf16(C.byref(d), 1, big, big, None) == -1 and "above the launch limit" in capi.last_error()
-    # a grid beyond the launch limits: the slab count is at most 1024 by the slab rule and taps at most 49, so the grid can only
-    # outgrow its limits along x, M tiles * N tiles - which needs taps * cout * cin >= 2^31 - 256, refused under the same text
-    c = 46344                                   # c * c > 2^31, a multiple of 8
-    assert cb.geometry(c, c, 1, N, H, W)[1] <= 1024 and cb.geometry(8, 8, 1, 1, 1 << 15, 1 << 15)[1] <= 1024
-    d = base(capi, k=1, cin=c, cout=c)
-    d.lx = capi.Layout.padded(c, H, W, 0, 0)
-    d.lgy = capi.Layout.padded(c, H, W, 0, 0)
-    d.workspace_floats = 1 << 62
-    assert lib.rtpose_conv2d_wgrad_bf16(C.byref(d), N, H, W, None) == -1 and "above the launch limit" in capi.last_error()
-    assert lib.rtpose_conv2d_wgrad_bf16_slabs(c, c, 1, N, H, W) == 0
+    # (the restated slab rule agrees that neither shape of the launch-limit cases could outgrow the grid along z)
+    assert cb.geometry(46344, 46344, 1, N, H, W)[1] <= 1024 and cb.geometry(8, 8, 1, 1, 1 << 15, 1 << 15)[1] <= 1024
+    cb.wgrad_null_empty_and_launch_limits(capi, capi.lib.rtpose_conv2d_wgrad_bf16, capi.lib.rtpose_conv2d_wgrad_bf16_slabs,
+                                          "conv2d_wgrad_bf16", base)
 
 
 def test_wgrad_bf16_takes_a_gap_of_exactly_half_the_filter_and_no_dbias(capi):
     """k = 7 with a gap of 3 and dbias = NULL pass every host check: the refusal is then the pointer's (fake: no device owns it)"""
-    d = base(capi, k=7)
-    d.dbias = None
-    rc = capi.lib.rtpose_conv2d_wgrad_bf16(C.byref(d), N, H, W, None)
-    assert rc != 0 and "gap" not in capi.last_error() and "x" in capi.last_error()
+    cb.wgrad_passes_the_host_checks(capi, capi.lib.rtpose_conv2d_wgrad_bf16, base)
 
 
 # ---- train.py's compute_dtype on CPU-constructed models ----------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""GPU suite of rtpose_conv2d_wgrad_bf16 (header section 2b, continued; csrc/conv_backward_bf16.hip): the weight and bias
+"""GPU suite of rtpose_conv2d_wgrad_bf16 (header section 2b, continued; csrc/conv_backward.hip): the weight and bias
 gradient of a stride-1 "same" conv from bf16 slices of wider buffers.
 
 Buffers: bf16 NaN (0x7FC0) in every channel beside a slice - the pad channels that share a 16-byte group with its last

@@ -12,8 +12,8 @@ import torch.nn.functional as F
 import conv_backward_restate as cb
 from conftest import PKG_NAME
 
-FAKE = 1 << 20          # a 16-byte aligned "device pointer" no refused launch touches
-N, H, W = 2, 9, 7
+FAKE = cb.FAKE          # a 16-byte aligned "device pointer" no refused launch touches
+N, H, W = cb.FAULT_N, cb.FAULT_H, cb.FAULT_W
 
 
 @pytest.fixture(scope="module")
@@ -158,63 +158,23 @@ def base(capi, k=3, cin=24, cout=38):
     return d
 
 
-def _set(field, value):
-    def f(d):
-        setattr(d, field, value)
-    return f
-
-
-def _lay(which, field, value):
-    def f(d):
-        setattr(getattr(d, which), field, value)
-    return f
-
-
-def _small_ws(d):
-    d.workspace_floats -= 1
-
-
-WGRAD_FAULTS = [
-    ("null x", _set("x", None), "NULL x"),
-    ("null gy", _set("gy", None), "NULL gy"),
-    ("null dw", _set("dw", None), "NULL dw"),
-    ("null workspace", _set("workspace", None), "NULL workspace"),
-    ("k = 5", _set("k", 5), "k must be 1, 3 or 7"),
-    ("k = 0", _set("k", 0), "k must be 1, 3 or 7"),
-    ("cin = 0", _set("cin", 0), "cin and cout must be >= 1"),
-    ("x slice past cstride", _set("cin", 33), "input slice exceeds cstride"),
-    ("gy slice past cstride", _set("cout", 45), "output-gradient slice exceeds cstride"),
-    ("row gap below k/2", _lay("lx", "ws", W), "gap smaller than the conv padding"),
-    ("image gap below k/2", _lay("lx", "hs", H), "gap smaller than the conv padding"),
-    ("lead below k/2", _lay("lx", "lead", W + 1), "gap smaller than the conv padding"),
-    ("gy rows shorter than the map", _lay("lgy", "ws", W - 1), "output-gradient layout smaller than the map"),
-    ("workspace too small", _small_ws, "workspace of"),
-    ("dw not 16-byte aligned", _set("dw", FAKE + 4), "16-byte aligned"),
-    ("workspace not 16-byte aligned", _set("workspace", FAKE + 8), "16-byte aligned"),
-]
-
-
-@pytest.mark.parametrize("name,fault,text", WGRAD_FAULTS, ids=[f[0] for f in WGRAD_FAULTS])
+@pytest.mark.parametrize("name,fault,text", cb.WGRAD_FAULTS, ids=[f[0] for f in cb.WGRAD_FAULTS])
 def test_wgrad_refuses_on_the_host(capi, name, fault, text):
+    """the table rtpose_conv2d_wgrad_bf16 runs too (tests/conv_backward_restate.py): one host path serves both"""
     d = base(capi)
     fault(d)
-    rc = capi.lib.rtpose_conv2d_wgrad(C.byref(d), N, H, W, None)
-    assert rc == -1, (name, rc, capi.last_error())            # RTPOSE_E_INVAL, not a HIP error
-    assert text in capi.last_error(), (name, capi.last_error())
-    assert "device memory" not in capi.last_error()           # returned before the pointers were looked at
+    cb.wgrad_refused(capi, capi.lib.rtpose_conv2d_wgrad, "conv2d_wgrad", d, (N, H, W), text)
 
 
 def test_wgrad_refuses_null_descriptor_and_empty_tensor(capi):
-    assert capi.lib.rtpose_conv2d_wgrad(None, N, H, W, None) == -1 and "NULL descriptor" in capi.last_error()
-    d = base(capi)
-    assert capi.lib.rtpose_conv2d_wgrad(C.byref(d), 0, H, W, None) == -1 and "empty tensor" in capi.last_error()
+    """and each of the three empty shapes and the two shapes above the launch limit, rtpose_conv2d_wgrad_slabs == 0 included"""
+    cb.wgrad_null_empty_and_launch_limits(capi, capi.lib.rtpose_conv2d_wgrad, capi.lib.rtpose_conv2d_wgrad_slabs,
+                                          "conv2d_wgrad", base)
 
 
 def test_wgrad_takes_a_gap_of_exactly_half_the_filter(capi):
-    """k = 7 with a gap of 3 passes every host check: the refusal is then the pointer's (fake: no device owns it)"""
-    d = base(capi, k=7)
-    rc = capi.lib.rtpose_conv2d_wgrad(C.byref(d), N, H, W, None)
-    assert rc != 0 and "gap" not in capi.last_error() and "x" in capi.last_error()
+    """k = 7 with a gap of 3 passes every host check, with dbias and with dbias = NULL: the refusal is then the pointer's"""
+    cb.wgrad_passes_the_host_checks(capi, capi.lib.rtpose_conv2d_wgrad, base)
 
 
 def test_relu_grad_refuses_on_the_host(capi):

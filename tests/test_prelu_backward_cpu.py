@@ -14,7 +14,7 @@ import prelu_restate as pr
 from conftest import PKG_NAME
 
 FAKE = 1 << 20          # a 16-byte aligned "device pointer" no refused launch touches
-N, H, W = 2, 9, 7
+N, H, W = pr.FAULT_N, pr.FAULT_H, pr.FAULT_W
 
 
 @pytest.fixture(scope="module")
@@ -143,7 +143,7 @@ def test_slabs_and_workspace_depend_on_the_shape_only(capi):
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------
-CH = 19
+CH = pr.FAULT_CH
 
 
 def grad_args(capi):
@@ -154,39 +154,14 @@ def grad_args(capi):
     return lays, [FAKE, C.byref(lays[0]), FAKE, FAKE, C.byref(lays[1]), FAKE, C.byref(lays[2]), FAKE, FAKE, floats, CH, N, H, W, None]
 
 
-def _arg(i, v):
-    def f(a, lays):
-        a[i] = v
-    return f
-
-
-def _lay(j, field, v):
-    def f(a, lays):
-        setattr(lays[j], field, v)
-    return f
-
-
-GRAD_FAULTS = [
-    ("null z", _arg(0, None), "NULL buffer"),
-    ("null slope", _arg(2, None), "NULL buffer"),
-    ("null gy", _arg(3, None), "NULL buffer"),
-    ("null out", _arg(5, None), "NULL buffer"),
-    ("null lz", _arg(1, None), "NULL layout"),
-    ("null lgy", _arg(4, None), "NULL layout"),
-    ("null lout", _arg(6, None), "NULL layout"),
-    ("cstride 0", _lay(0, "cstride", 0), "bad layout"),
-    ("negative choff", _lay(1, "choff", -1), "bad layout"),
-    ("negative lead", _lay(2, "lead", -1), "bad layout"),
-    ("z slice past cstride", _lay(0, "choff", 6), "z slice exceeds cstride"),
-    ("gy slice past cstride", _lay(1, "choff", 6), "gy slice exceeds cstride"),
-    ("out slice past cstride", _lay(2, "choff", 2), "out slice exceeds cstride"),
-    ("z rows shorter than the map", _lay(0, "ws", W - 1), "layout smaller than the map"),
-    ("gy images shorter than the map", _lay(1, "hs", H - 1), "layout smaller than the map"),
-    ("out rows shorter than the map", _lay(2, "ws", W - 1), "layout smaller than the map"),
-    ("dslope without a workspace", _arg(8, None), "NULL workspace"),
-    ("workspace too small", _arg(9, 2 * CH - 1), "workspace of"),
-    ("no channels", _arg(10, 0), "empty tensor"),
-    ("no images", _arg(11, 0), "empty tensor"),
+# the rows all four PReLU entry points share (tests/prelu_restate.py) on this entry point's arguments, and the rows that are
+# only here
+GRAD_FAULTS = pr.shared_faults([("z", 0, 1, 0, False), ("gy", 3, 4, 1, False), ("out", 5, 6, 2, False)], slope=2, channels=10,
+                               workspace=8) + [
+    ("cstride 0", pr.layout_fault(0, "cstride", 0), "bad layout"),
+    ("negative choff", pr.layout_fault(1, "choff", -1), "bad layout"),
+    ("negative lead", pr.layout_fault(2, "lead", -1), "bad layout"),
+    ("gy images shorter than the map", pr.layout_fault(1, "hs", H - 1), "layout smaller than the map"),
 ]
 
 
@@ -194,10 +169,7 @@ GRAD_FAULTS = [
 def test_prelu_grad_refuses_on_the_host(capi, name, fault, text):
     lays, a = grad_args(capi)
     fault(a, lays)
-    rc = capi.lib.rtpose_prelu_grad(*a)
-    assert rc == -1, (name, rc, capi.last_error())            # RTPOSE_E_INVAL, not a HIP error
-    assert text in capi.last_error() and capi.last_error().startswith("prelu_grad:"), (name, capi.last_error())
-    assert "device memory" not in capi.last_error()           # returned before the pointers were looked at
+    pr.refused(capi, capi.lib.rtpose_prelu_grad, "prelu_grad", a, text)
 
 
 def test_prelu_grad_host_checks_pass_valid_arguments_and_frozen_slopes(capi):
@@ -214,6 +186,22 @@ def test_prelu_grad_host_checks_pass_valid_arguments_and_frozen_slopes(capi):
         lay.ws, lay.hs, lay.lead = 1 << 15, 1 << 16, 0
     a[11:14] = [1, 1 << 16, 1 << 15]
     assert capi.lib.rtpose_prelu_grad(*a) == -1 and "above the launch limit" in capi.last_error()
+
+
+def fwd_args(capi):
+    """valid arguments of rtpose_prelu but for the pointers: [z, lz, slope, y, ly, channels, N, H, W, stream]"""
+    lays = [capi.Layout.padded(24, H, W, 1, 4), capi.Layout.padded(20, H, W, 0, 1)]
+    return lays, [FAKE, C.byref(lays[0]), FAKE, FAKE, C.byref(lays[1]), CH, N, H, W, None]
+
+
+FWD_FAULTS = pr.shared_faults([("z", 0, 1, 0, False), ("y", 3, 4, 1, False)], slope=2, channels=5)
+
+
+@pytest.mark.parametrize("name,fault,text", FWD_FAULTS, ids=[f[0] for f in FWD_FAULTS])
+def test_prelu_refuses_the_shared_rows(capi, name, fault, text):
+    lays, a = fwd_args(capi)
+    fault(a, lays)
+    pr.refused(capi, capi.lib.rtpose_prelu, "prelu", a, text)
 
 
 def test_prelu_refuses_on_the_host(capi):

@@ -1,4 +1,4 @@
-"""CPU suite of the bf16 PReLU passes (header section 2b continued, csrc/prelu_bf16.hip): the restatements of
+"""CPU suite of the bf16 PReLU passes (header section 2b continued, csrc/prelu_backward.hip): the restatements of
 tests/prelu_bf16_restate.py against torch's float64 F.prelu autograd, the exact operand sets held to their condition on torch
 alone, and the host side of rtpose_prelu_bf16 / rtpose_prelu_grad_bf16 - the symbols, the geometry queries against
 rtpose_prelu_grad's own, every refusal with its text, before any HIP call."""
@@ -11,8 +11,8 @@ import torch
 import prelu_bf16_restate as pb
 import prelu_restate as pr
 
-N, H, W = 2, 9, 7
-CH = 19
+N, H, W = pr.FAULT_N, pr.FAULT_H, pr.FAULT_W
+CH = pr.FAULT_CH
 # 16-byte aligned "device pointers" no refused launch touches, far enough apart that no two slices meet
 Z, SLOPE, GA, GB, OUT, DS, WS = ((i + 1) << 24 for i in range(7))
 
@@ -156,18 +156,6 @@ def fwd_args(capi, ptrs=(Z, SLOPE, OUT)):
     return lays, [z, C.byref(lays[0]), slope, y, C.byref(lays[1]), CH, N, H, W, None]
 
 
-def _arg(i, v):
-    def f(a, lays):
-        a[i] = v
-    return f
-
-
-def _lay(j, field, v):
-    def f(a, lays):
-        setattr(lays[j], field, v)
-    return f
-
-
 def _onto(i, j, delta=64):
     """argument i (the bf16 destination) moved to `delta` bytes past argument j: inside its bytes"""
     def f(a, lays):
@@ -175,77 +163,39 @@ def _onto(i, j, delta=64):
     return f
 
 
-def _big(a, lays):
-    """a map above the launch limit, in layouts that hold it"""
-    for lay in lays:
-        lay.ws, lay.hs, lay.lead = 1 << 15, 1 << 16, 0
-    a[-4:-1] = [1, 1 << 16, 1 << 15]
+_arg, _lay = pr.arg_fault, pr.layout_fault
 
-
+# The rows all four PReLU entry points share (tests/prelu_restate.py) on these entry points' arguments, and the rows that are
+# only the bf16 passes': the 2-byte alignment and every overlap of the destination.
 # (the destination's first valid element lies (9 * 24 + 3) * 2 = 438 bytes past its base: 430 bytes before the slopes puts
 # it 8 bytes into them)
-GRAD_FAULTS = [
-    ("null z", _arg(0, None), "NULL buffer (z)"),
-    ("null slope", _arg(2, None), "NULL buffer (slope)"),
-    ("null ga", _arg(3, None), "NULL buffer (ga)"),
-    ("null out", _arg(7, None), "NULL buffer (out)"),
-    ("null lz", _arg(1, None), "NULL layout (z)"),
-    ("null lga", _arg(4, None), "NULL layout (ga)"),
+GRAD_FAULTS = pr.shared_faults([("z", 0, 1, 0, False), ("ga", 3, 4, 1, False), ("gb", 5, 6, 2, True), ("out", 7, 8, 3, False)],
+                               slope=2, channels=12, workspace=10) + [
     ("gb without a layout", _arg(6, None), "NULL layout (gb)"),
-    ("null lout", _arg(8, None), "NULL layout (out)"),
     ("cstride 0", _lay(0, "cstride", 0), "bad layout"),
     ("negative choff", _lay(2, "choff", -1), "bad layout"),
     ("negative lead", _lay(3, "lead", -1), "bad layout"),
-    ("z slice past cstride", _lay(0, "choff", 6), "z slice exceeds cstride"),
-    ("ga slice past cstride", _lay(1, "choff", 6), "ga slice exceeds cstride"),
-    ("gb slice past cstride", _lay(2, "choff", 2), "gb slice exceeds cstride"),
-    ("out slice past cstride", _lay(3, "choff", 6), "out slice exceeds cstride"),
-    ("z rows shorter than the map", _lay(0, "ws", W - 1), "layout smaller than the map (z)"),
     ("ga images shorter than the map", _lay(1, "hs", H - 1), "layout smaller than the map (ga)"),
-    ("gb rows shorter than the map", _lay(2, "ws", W - 1), "layout smaller than the map (gb)"),
-    ("out rows shorter than the map", _lay(3, "ws", W - 1), "layout smaller than the map (out)"),
-    ("above the launch limit", _big, "above the launch limit"),
     ("an odd bf16 base", _arg(7, OUT + 1), "out must be 2-byte aligned"),
     ("out inside z", _onto(7, 0), "overlap those of z"),
     ("out inside ga", _onto(7, 3), "overlap those of ga"),
     ("out inside gb", _onto(7, 5), "overlap those of gb"),
     ("out inside slope", _onto(7, 2, -430), "overlap those of slope"),
-    ("dslope without a workspace", _arg(10, None), "NULL workspace"),
-    ("workspace too small", _arg(11, 2 * CH - 1), "workspace of"),
-    ("no channels", _arg(12, 0), "empty tensor"),
-    ("no images", _arg(13, 0), "empty tensor"),
     ("no rows", _arg(14, -1), "empty tensor"),
     ("no columns", _arg(15, 0), "empty tensor"),
 ]
 
-FWD_FAULTS = [
-    ("null z", _arg(0, None), "NULL buffer (z)"),
-    ("null slope", _arg(2, None), "NULL buffer (slope)"),
-    ("null y", _arg(3, None), "NULL buffer (y)"),
-    ("null lz", _arg(1, None), "NULL layout (z)"),
-    ("null ly", _arg(4, None), "NULL layout (y)"),
+FWD_FAULTS = pr.shared_faults([("z", 0, 1, 0, False), ("y", 3, 4, 1, False)], slope=2, channels=5) + [
     ("bad layout", _lay(1, "hs", 0), "bad layout"),
-    ("z slice past cstride", _lay(0, "choff", 6), "z slice exceeds cstride"),
-    ("y slice past cstride", _lay(1, "choff", 6), "y slice exceeds cstride"),
-    ("z rows shorter than the map", _lay(0, "ws", W - 1), "layout smaller than the map (z)"),
     ("y images shorter than the map", _lay(1, "hs", H - 1), "layout smaller than the map (y)"),
-    ("above the launch limit", _big, "above the launch limit"),
     ("an odd bf16 base", _arg(3, OUT + 1), "y must be 2-byte aligned"),
     ("y inside z", _onto(3, 0), "overlap those of z"),
     ("y inside slope", _onto(3, 2, -430), "overlap those of slope"),
-    ("no channels", _arg(5, 0), "empty tensor"),
-    ("no images", _arg(6, 0), "empty tensor"),
     ("no rows", _arg(7, 0), "empty tensor"),
     ("no columns", _arg(8, -3), "empty tensor"),
 ]
 
-
-def refused(capi, fn, who, a, text):
-    rc = fn(*a)
-    err = capi.last_error()
-    assert rc == -1, (rc, err)                                   # RTPOSE_E_INVAL, not a HIP error
-    assert text in err and err.startswith(who + ":"), err
-    assert "device memory" not in err                            # returned before the pointers were looked at
+refused = pr.refused
 
 
 @pytest.mark.parametrize("name,fault,text", GRAD_FAULTS, ids=[f[0] for f in GRAD_FAULTS])

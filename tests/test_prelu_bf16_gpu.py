@@ -1,4 +1,4 @@
-"""GPU suite of the bf16 PReLU passes (header section 2b continued, csrc/prelu_bf16.hip): rtpose_prelu_bf16 and
+"""GPU suite of the bf16 PReLU passes (header section 2b continued, csrc/prelu_backward.hip): rtpose_prelu_bf16 and
 rtpose_prelu_grad_bf16 on slices of wider buffers - four different layouts per case - whose other channels and gaps hold NaN
 sentinels (conv_driver.SENTINEL in the fp32 inputs, SENT16 in the bf16 destination); after every launch everything outside
 the destination's valid pixels is intact, bit for bit, and so is every input.
