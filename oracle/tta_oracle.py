@@ -21,7 +21,7 @@ import numpy as np
 
 def resize_bilinear(src, hd, wd, sy, sx):
     """src [hs, ws, C] float32 -> [hd, wd, C]; (sy, sx) = source pixels per destination pixel.
-    float32 arithmetic in the order of csrc/layout_ops.hip:resize_bilinear_accum_kernel
+    float32 arithmetic in the order of csrc/image_ops.hip:resize_bilinear_accum_kernel
     (== F.interpolate(bilinear, align_corners=False, scale given))."""
     hs, ws = src.shape[:2]
     f32 = np.float32

@@ -1,6 +1,6 @@
 // Backward pass of the depthwise 3x3 convolution, padding 1, stride 1 or 2 (header section 2b, continued): what
 // nn.Conv2d(C, C, 3, stride, 1, groups = C, bias = False) of the ShuffleNetV2 blocks needs to train (train.dwconv3x3).
-// The forward is rtpose_dwconv3x3 (layout_ops.hip).  H, W are the conv's INPUT size, Ho = (H - 1) / stride + 1, Wo likewise.
+// The forward is rtpose_dwconv3x3 (shufflenet_ops.hip).  H, W are the conv's INPUT size, Ho = (H - 1) / stride + 1, Wo likewise.
 //
 //   rtpose_dwconv3x3_wgrad   dw[c][0][ky][kx] = sum over (n, yo, xo) of gy[n, yo, xo, c] * x[n, stride yo + ky - 1, stride xo + kx - 1, c]
 //                            dbias[c]         = sum over (n, yo, xo) of gy[n, yo, xo, c]

@@ -22,18 +22,6 @@ int conv_first_launch(const float* x_nchw, const float* x_lay, const rtpose_layo
                       const rtpose_layout* lo, int out_plane_pixels, int relu, int N, int H, int W, hipStream_t s,
                       int out_bf16);
 
-// ---- flip merge and fused multi-scale TTA over a flip table (tta.hip): the argument check and the launch of each kernel;
-// ---- `who` is the entry point's name in the messages.  coco18_flip_table(): what rtpose_flip_merge / rtpose_tta_accumulate
-// ---- (layout_ops.hip) pass, derived once; NULL with the error text set if the derivation failed
-const rtpose_flip_table* coco18_flip_table();
-int flip_merge_launch(const char* who, const float* heat, const float* heat_flipped, const float* paf,
-                      const float* paf_flipped, int N, int h, int w, float* heat_avg, float* paf_avg,
-                      const rtpose_flip_table* table, void* stream);
-int tta_accumulate_launch(const char* who, const float* heat, const rtpose_layout* lheat, const float* paf,
-                          const rtpose_layout* lpaf, int B, int hs, int w_valid, float* acc_heat, float* acc_paf, int hd,
-                          int wd, float src_h_valid, float src_w_valid, float alpha, float beta, int flip,
-                          const rtpose_flip_table* table, void* stream);
-
 // ---- stacked hourglass: the 7x7 stride-2 stem and up1 + upsample2(low3) (hourglass_ops.hip) ----
 size_t conv7x7_s2_packed_floats();
 int conv7x7_s2_pack_launch(const float* w_oihw, const float* bias, float* wp, hipStream_t s);

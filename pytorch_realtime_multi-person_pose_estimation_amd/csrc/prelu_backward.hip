@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "chan_slab.h"
+#include "pixel_walk.h"
 
 namespace rtpose {
 namespace {
@@ -47,8 +48,6 @@ namespace {
 constexpr int kReduceThreads = 64;
 
 typedef uint32_t Word2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t f32_to_bf16_rne(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 
 bool shape_ok(int channels, int N, int H, int W) { return channels >= 1 && pixel_count(N, H, W) > 0; }
 
@@ -74,14 +73,14 @@ template <int V>
 __device__ __forceinline__ void store_bf16(uint16_t* dst, size_t o, const Place& t, const Unit<V>& u) {
   if constexpr (V == 4) {
     if (t.whole) {
-      *reinterpret_cast<Word2*>(dst + o) = Word2{f32_to_bf16_rne(u.v[0]) | (f32_to_bf16_rne(u.v[1]) << 16),
-                                                 f32_to_bf16_rne(u.v[2]) | (f32_to_bf16_rne(u.v[3]) << 16)};
+      *reinterpret_cast<Word2*>(dst + o) = Word2{f32_to_bf16_rne(u.v[0]) | ((uint32_t)f32_to_bf16_rne(u.v[1]) << 16),
+                                                 f32_to_bf16_rne(u.v[2]) | ((uint32_t)f32_to_bf16_rne(u.v[3]) << 16)};
       return;
     }
   }
 #pragma unroll
   for (int v = 0; v < V; ++v)
-    if (v < t.nc) dst[o + v] = (uint16_t)f32_to_bf16_rne(u.v[v]);
+    if (v < t.nc) dst[o + v] = f32_to_bf16_rne(u.v[v]);
 }
 
 // V: channels per unit.  OUT: float, or uint16_t for a bf16 destination.  GRAD: the backward (else y = prelu1(z, slope)).

@@ -1,7 +1,7 @@
 // Flip merge (handle_paf_and_heat, evaluate/coco_eval.py:197-242) and the fused multi-scale TTA kernel, with the
 // left / right permutation as data: one kernel pair for every skeleton.  The rtpose_flip_table travels by value as a
 // launch argument, like rtpose_skeleton in decode.hip: nothing is uploaded, two streams may merge different skeletons
-// at once.  The entry points without a table argument (rtpose_flip_merge, rtpose_tta_accumulate in layout_ops.hip) call
+// at once.  The entry points without a table argument (rtpose_flip_merge, rtpose_tta_accumulate, at the end) call
 // the launchers below with coco18_flip_table(): derived once on the host from coco18_skeleton() and the part mirror.
 #include <hip/hip_runtime.h>
 
@@ -9,7 +9,6 @@
 
 #include "common.h"
 #include "decode.h"
-#include "launchers.h"
 
 namespace rtpose {
 namespace {
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(kThreads) void flip_merge_kernel(
 // [0,B)) and, if flip, B x-mirrored passes (images [B,2B)) where the net wrote them, forms handle_paf_and_heat's average
 // (evaluate/coco_eval.py:197-242; mirror inside the first wv columns only, left/right channel swap, PAF x sign) at the
 // four bilinear taps and accumulates alpha * resize(...) into the dense scale-1 maps.  Same expressions as
-// flip_merge_kernel followed by layout_ops.hip's resize_bilinear_accum_kernel; the grid is flip_merge_kernel's over the
+// flip_merge_kernel followed by image_ops.hip's resize_bilinear_accum_kernel; the grid is flip_merge_kernel's over the
 // destination.
 __global__ __launch_bounds__(kThreads) void tta_accumulate_kernel(
     const float* __restrict__ heat, Lay lh, const float* __restrict__ paf, Lay lp, int B, int hs, int wv,
@@ -134,8 +133,6 @@ int assign(rtpose_flip_table* t, bool* set, int limb, int c, int s, bool neg) {
   return 0;
 }
 
-}  // namespace
-
 // COCO-18's table for the entry points without a table argument: derived once from the decoder's coco18_skeleton() and the
 // part mirror (lib/utils/common.py:5-24: R / L shoulder, elbow, wrist, hip, knee, ankle, eye, ear change places), which
 // gives coco_eval.py's swap_heat / swap_paf lists and their signs.  A derivation that failed (it cannot, short of an edit
@@ -204,6 +201,7 @@ int tta_accumulate_launch(const char* who, const float* heat, const rtpose_layou
   return 0;
 }
 
+}  // namespace
 }  // namespace rtpose
 
 using namespace rtpose;
@@ -275,6 +273,27 @@ int rtpose_tta_accumulate_skel(const float* heat, const rtpose_layout* lheat, co
                                const rtpose_flip_table* table, void* stream) {
   return tta_accumulate_launch("tta_accumulate_skel", heat, lheat, paf, lpaf, B, hs, w_valid, acc_heat, acc_paf, hd, wd,
                                src_h_valid, src_w_valid, alpha, beta, flip, table, stream);
+}
+
+// COCO-18's flip merge and fused TTA merge: the same kernels and argument check over the table the library derives for
+// itself.  As before, a flip merge without pixels (h or w 0 as well as N 0) is a no-op ...
+int rtpose_flip_merge(const float* heat, const float* heat_flipped, const float* paf, const float* paf_flipped, int N,
+                      int h, int w, float* heat_avg, float* paf_avg, void* stream) {
+  if (N == 0 || h == 0 || w == 0) return 0;
+  const rtpose_flip_table* t = coco18_flip_table();
+  return !t ? RTPOSE_E_INVAL
+            : flip_merge_launch("flip_merge", heat, heat_flipped, paf, paf_flipped, N, h, w, heat_avg, paf_avg, t, stream);
+}
+
+// ... and unlike rtpose_tta_accumulate_skel, this door refuses the empty batch
+int rtpose_tta_accumulate(const float* heat, const rtpose_layout* lheat, const float* paf, const rtpose_layout* lpaf,
+                          int B, int hs, int w_valid, float* acc_heat, float* acc_paf, int hd, int wd, float src_h_valid,
+                          float src_w_valid, float alpha, float beta, int flip, void* stream) {
+  if (B == 0) return fail(RTPOSE_E_INVAL, "tta_accumulate: B is 0");
+  const rtpose_flip_table* t = coco18_flip_table();
+  return !t ? RTPOSE_E_INVAL
+            : tta_accumulate_launch("tta_accumulate", heat, lheat, paf, lpaf, B, hs, w_valid, acc_heat, acc_paf, hd, wd,
+                                    src_h_valid, src_w_valid, alpha, beta, flip, t, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 """Host restatement of the activation layout (include/rtpose_mi355x.h §1), of the bf16 / split element
-formats and of the arithmetic of the kernels in csrc/layout_ops.hip.  numpy (+ torch CPU float64), no GPU,
-no library call: tests/test_layout_ops_gpu.py compares every entry point of that file with this, and
+formats and of the arithmetic of the kernels in csrc/layout_ops.hip, shufflenet_ops.hip and image_ops.hip.  numpy
+(+ torch CPU float64), no GPU, no library call: tests/test_layout_ops_gpu.py compares every entry point of those files with this, and
 tests/test_layout_restate_cpu.py checks this file against torch on the CPU.
 
 Tensors are NCHW unless a name says NHWC.  The arithmetic references return (value, S): the float64 result

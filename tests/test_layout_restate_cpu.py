@@ -1,5 +1,6 @@
 """The host reference of tests/test_layout_ops_gpu.py (tests/layout_restate.py) checked on the CPU, so that
-the reference is not itself the unknown; and the rule that every entry point of csrc/layout_ops.hip is named
+the reference is not itself the unknown; and the rule that every entry point of the data-movement files
+(csrc/layout_ops.hip, shufflenet_ops.hip, image_ops.hip, common.hip and the COCO-18 doors of tta.hip) is named
 by a GPU test."""
 import glob
 import os
@@ -197,11 +198,14 @@ def test_flip_merge_and_resize_references():
 
 
 def test_every_layout_ops_entry_point_is_named_by_a_gpu_test():
-    src = open(os.path.join(ROOT, "pytorch_realtime_multi-person_pose_estimation_amd", "csrc", "layout_ops.hip")).read()
+    csrc = os.path.join(ROOT, "pytorch_realtime_multi-person_pose_estimation_amd", "csrc")
+    # the files layout_ops.hip was split into; of tta.hip only the two COCO-18 doors that moved there
+    src = "".join(open(os.path.join(csrc, f)).read() for f in ("common.hip", "layout_ops.hip", "shufflenet_ops.hip", "image_ops.hip"))
     names = re.findall(r"^(?:int|size_t|const char\*) (rtpose_\w+)\(", src, flags=re.M)
+    names += re.findall(r"^int (rtpose_flip_merge|rtpose_tta_accumulate)\(", open(os.path.join(csrc, "tta.hip")).read(), flags=re.M)
     assert len(names) >= 31 and "rtpose_tta_accumulate" in names and "rtpose_layout_copy_cmap_bf16" in names
     tests = ""
     for p in glob.glob(os.path.join(ROOT, "tests", "test_*_gpu.py")):
         tests += open(p).read()
     missing = [n for n in names if not re.search(r"\b%s\b" % n, tests)]
-    assert not missing, "entry points of layout_ops.hip that no GPU test names: %s" % missing
+    assert not missing, "data-movement entry points that no GPU test names: %s" % missing

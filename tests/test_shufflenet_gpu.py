@@ -1,5 +1,5 @@
 """GPU parity of the ShuffleNetV2 x1.0 pose network (csrc/shufflenet.hip + the building-block
-kernels in csrc/layout_ops.hip) against the oracle restatement and the golden outputs of the
+kernels in csrc/shufflenet_ops.hip) against the oracle restatement and the golden outputs of the
 reference module (imported unmodified through the slim stub; parity unpinned w.r.t. the real slim)."""
 import ctypes as C
 import ctypes as C_
