@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "rtpose_mi355x.h"
 
@@ -130,11 +131,21 @@ __device__ __forceinline__ int fast_div(int m, const FastDiv f) {
 struct Lay {
   int cstride, choff, ws, hs, lead;
 };
+static_assert(sizeof(Lay) == 5 * sizeof(int) && std::is_standard_layout<Lay>::value,
+              "kernel-argument structs hold a Lay where they held five ints: their offsets must not move");
 inline Lay to_lay(const rtpose_layout* l) { return Lay{l->cstride, l->choff, l->ws, l->hs, l->lead}; }
+inline Lay to_lay(const rtpose_layout& l) { return to_lay(&l); }
 #ifdef __HIPCC__
 // element offset of channel 0 of the view at pixel (y, x) of image n
 __device__ __forceinline__ size_t lay_off(const Lay& l, int n, int y, int x) {
   return ((size_t)l.lead + (size_t)(n * l.hs + y) * l.ws + x) * l.cstride + l.choff;
+}
+// the 32-bit forms of the forward kernels, whose launchers refuse a tensor of 2^31 elements or more (below_2g_elems):
+// the pixel index of (y, x) of image n, and the element offset of channel 0 of the view there.  (Lay by value: through a
+// reference the kernels that copy their group struct, conv_tail*.hip, compile to other instructions.)
+__device__ __forceinline__ int lay_pix(const Lay l, int n, int y, int x) { return l.lead + (n * l.hs + y) * l.ws + x; }
+__device__ __forceinline__ int lay_elem(const Lay l, int n, int y, int x) {
+  return lay_pix(l, n, y, x) * l.cstride + l.choff;
 }
 #endif
 

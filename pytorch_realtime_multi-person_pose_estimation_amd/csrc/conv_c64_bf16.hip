@@ -34,14 +34,11 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace c64 {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 16, TW = 32;         // pixel tile of a block: 4 waves x 4 rows
 constexpr int HR = TH + 2, HC = TW + 2;  // halo
@@ -58,20 +55,13 @@ struct Args {
   const void* w;
   const float* bias;
   unsigned short* out;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;
   unsigned in_bytes, w_bytes;
   int N, H, W, cout_pad, relu;
   int tiles_x, tiles_y, tiles, ntn;  // ntn = passes of 64 output channels
   FastDiv f_tpi, f_tx;
 };
 
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {  // (bf16(a), bf16(b)), RNE, a in the low half
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  typedef float fl2 __attribute__((ext_vector_type(2)));
-  const fl2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf2));
-}
 // max as ONE instruction: fmaxf compiles to v_max_f32 behind a canonicalising v_max_f32 x, x per operand the compiler cannot
 // prove quiet (an accumulator) - 381 v_max in the pooling epilogue instead of 192
 __device__ __forceinline__ float vmax(float a, float b) {
@@ -121,10 +111,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
 
   const int plane = tid & 7, ps = tid >> 3;  // staging role: piece `plane` of halo column `ps` in every halo row
   const uintx4* const pl = halo + kh * PS + (4 * wave) * HC + l31;
-#define RTPOSE_C64_PIN()         \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
-
   // ---- halo of a tile: rows y0 - 1 .. y0 + TH, columns x0 - 1 .. x0 + TW; past the image: the zero gap row / column.  A
   // thread fetches its piece of column `ps` in all 18 rows (per-lane column offset, uniform row offset: no address
   // arithmetic per load), and the 18 x 2 pixels of the last two columns are shared out.  The loads of tile t + 1 are issued
@@ -151,12 +137,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
     return c;
   };
   auto issue_rows = [&](const Tile& c, int r0, int r1) {
-    const unsigned col_b = ((unsigned)min(c.x0 + ps, A.W + 1) * (unsigned)A.in_cstride + (unsigned)(A.in_choff + plane * 8)) * 2u;
+    const unsigned col_b = ((unsigned)min(c.x0 + ps, A.W + 1) * (unsigned)A.lin.cstride + (unsigned)(A.lin.choff + plane * 8)) * 2u;
 #pragma unroll
     for (int r = 0; r < HR; ++r) {
       if (r < r0 || r >= r1) continue;
       const int yy = min(c.y0 - 1 + r, A.H);
-      const unsigned row_b = (unsigned)(A.in_lead + (c.n * A.in_hs + yy) * A.in_ws - 1) * (unsigned)A.in_cstride * 2u;
+      const unsigned row_b = (unsigned)lay_pix(A.lin, c.n, yy, -1) * (unsigned)A.lin.cstride * 2u;
       v[r] = __builtin_amdgcn_raw_buffer_load_b128(irs, col_b, row_b, 0);
     }
   };
@@ -164,8 +150,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int yy = min(c.y0 - 1 + er[k], A.H);
-      const unsigned q = (unsigned)(A.in_lead + (c.n * A.in_hs + yy) * A.in_ws - 1 + min(c.x0 + ec[k], A.W + 1));
-      ex[k] = __builtin_amdgcn_raw_buffer_load_b128(irs, (q * (unsigned)A.in_cstride + (unsigned)(A.in_choff + plane * 8)) * 2u, 0, 0);
+      const unsigned q = (unsigned)lay_pix(A.lin, c.n, yy, min(c.x0 + ec[k], A.W + 1) - 1);
+      ex[k] = __builtin_amdgcn_raw_buffer_load_b128(irs, (q * (unsigned)A.lin.cstride + (unsigned)(A.lin.choff + plane * 8)) * 2u, 0, 0);
     }
   };
   auto park = [&]() {
@@ -205,14 +191,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
       wq[(i + AHEAD) % RING][0] = wload(i + AHEAD, 0);
       wq[(i + AHEAD) % RING][1] = wload(i + AHEAD, 1);
       if (i + 1 < NSTEP) pread(i + 1, pf[(i + 1) & 1]);
-      RTPOSE_C64_PIN();  // (else the scheduler sinks the reads to one MFMA in front of their use)
+      RTPOSE_PIN();  // (else the scheduler sinks the reads to one MFMA in front of their use)
 #pragma unroll
       for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
         for (int mf = 0; mf < 4; ++mf)
           acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wq[i % RING][nf]),
                                                                 __builtin_bit_cast(bf16x8, pf[i & 1][mf]), acc[mf][nf], 0, 0, 0);
-      RTPOSE_C64_PIN();
+      RTPOSE_PIN();
     }
     __syncthreads();  // the halo may be overwritten
 
@@ -221,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
     const Tile nxt = coords(more ? tile + tstep : tile);
     issue_rows(nxt, 0, HR / 2);
     issue_extra(nxt);
-    RTPOSE_C64_PIN();
+    RTPOSE_PIN();
 
     // ---- epilogue: lane = pixel x0 + l31 of a row; registers 4 j .. 4 j + 3 of a half = channels 8 j + 4 kh .. + 3 ----
     const float4* const b4 = reinterpret_cast<const float4*>(s_bias);
@@ -230,9 +216,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
 #pragma unroll
     for (int ro = 0; ro < ROWS; ++ro) {
       if (ro == ROWS / 2) {
-        RTPOSE_C64_PIN();
+        RTPOSE_PIN();
         issue_rows(nxt, HR / 2, HR);
-        RTPOSE_C64_PIN();
+        RTPOSE_PIN();
       }
       int oy, ox;
       bool ok;
@@ -249,8 +235,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16(const Args A) {
         oy = min(oy, A.H - 1);
         ox = min(ox, A.W - 1);
       }
-      const size_t q = (size_t)A.out_lead + (size_t)(cur.n * A.out_hs + oy) * A.out_ws + ox;
-      unsigned short* const op = A.out + q * A.out_cstride + A.out_choff + pass * 64;
+      const size_t q = (size_t)A.lout.lead + (size_t)(cur.n * A.lout.hs + oy) * A.lout.ws + ox;
+      unsigned short* const op = A.out + q * A.lout.cstride + A.lout.choff + pass * 64;
 #pragma unroll
       for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
@@ -323,16 +309,8 @@ int conv_c64_bf16_launch(const rtpose_conv_desc* d, int N, int H, int W, hipStre
   a.w = c.w_packed;
   a.bias = c.bias_packed;
   a.out = reinterpret_cast<unsigned short*>(c.out);
-  a.in_cstride = c.lin.cstride;
-  a.in_choff = c.lin.choff;
-  a.in_ws = c.lin.ws;
-  a.in_hs = c.lin.hs;
-  a.in_lead = c.lin.lead;
-  a.out_cstride = c.lout.cstride;
-  a.out_choff = c.lout.choff;
-  a.out_ws = c.lout.ws;
-  a.out_hs = c.lout.hs;
-  a.out_lead = c.lout.lead;
+  a.lin = to_lay(c.lin);
+  a.lout = to_lay(c.lout);
   a.in_bytes = (unsigned)(rtpose_layout_pixels(&c.lin, N, H, W) * (size_t)c.lin.cstride * 2);
   a.cout_pad = cout_pad(c.cout);
   a.w_bytes = (unsigned)((size_t)2 * 9 * 4 * a.cout_pad * 16);

@@ -1,5 +1,5 @@
 // Host-side helpers shared by the conv launchers: what a valid rtpose_conv_desc slice is, the fill of a kernel's group
-// struct from a descriptor, the grid-id count of the XCD-aware block order and the launch of one kernel instance.
+// struct from a descriptor (and of the fused pointwise kernels' arguments from theirs), the grid-id count of the XCD-aware block order and the launch of one kernel instance.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -135,16 +135,8 @@ inline void fill_group(G& g, const rtpose_conv_desc& d) {
   g.w = reinterpret_cast<decltype(g.w)>(d.w_packed);
   g.bias = d.bias_packed;
   g.out = d.out;
-  g.in_cstride = d.lin.cstride;
-  g.in_choff = d.lin.choff;
-  g.in_ws = d.lin.ws;
-  g.in_hs = d.lin.hs;
-  g.in_lead = d.lin.lead;
-  g.out_cstride = d.lout.cstride;
-  g.out_choff = d.lout.choff;
-  g.out_ws = d.lout.ws;
-  g.out_hs = d.lout.hs;
-  g.out_lead = d.lout.lead;
+  g.lin = to_lay(d.lin);
+  g.lout = to_lay(d.lout);
   g.cout = d.cout;
   g.cout_pad = cout_pad(d.cout);
   if constexpr (has_out_cmap<G>::value) g.out_cmap = d.out_cmap;
@@ -155,6 +147,51 @@ template <class A>
 inline void set_prelu(A& a, const rtpose_conv_desc* d, int ngroups) {
   a.prelu[0] = d[0].prelu;
   a.prelu[1] = ngroups > 1 ? d[1].prelu : d[0].prelu;
+}
+
+// What the arguments of the fp32 and the bf16 fused pointwise kernel (pw_fused.hip, pw_fused_bf16.hip) have in common, from
+// a descriptor the launcher has checked: pointers, layouts, the interleave pass-through, sizes and the FastDiv constants of
+// the work-item decode.  bm: pixels of a block, tile: edge of a depthwise block's pixel tile.  Returns the grid: one block
+// per work item, at most the 2 persistent blocks per CU.
+template <class A>
+inline int fill_pw_args(A& a, const rtpose_pw_desc* d, int N, int H, int W, int bm, int tile) {
+  memset(&a, 0, sizeof(a));
+  a.in = reinterpret_cast<decltype(a.in)>(d->in);
+  a.lin = to_lay(d->lin);
+  a.dw_w = d->dw_w;
+  a.dw_b = d->dw_b;
+  a.w = reinterpret_cast<decltype(a.w)>(d->w_packed);
+  a.bias = d->bias_packed;
+  a.out = d->out;
+  a.lout = to_lay(d->lout);
+  a.out_cmap = d->out_cmap;
+  if (d->pt_src) {
+    a.pt = reinterpret_cast<decltype(a.pt)>(d->pt_src);
+    a.lpt = to_lay(d->lpt);
+    a.pt_pairs = d->pt_pairs;
+    a.pt_a = d->pt_a;
+    a.pt_b = d->pt_b;
+    a.pt_split = d->pt_split;
+    a.pt_d0 = d->pt_d0;
+    a.pt_d1 = d->pt_d1;
+  }
+  a.in_planes = d->in_planes;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.M = N * H * W;
+  a.K = d->cin;
+  a.coutp = d->coutp;
+  a.cout = d->cout;
+  a.relu = d->relu;
+  const int npass = d->coutp <= 128 ? 1 : d->coutp / 256;
+  a.fHW = make_fastdiv(H * W);
+  a.fW = make_fastdiv(W);
+  a.fnp = make_fastdiv(npass);
+  a.ftx = make_fastdiv(ceil_div(W, tile));
+  a.fty = make_fastdiv(ceil_div(H, tile));
+  const int nwork = (d->dw_w ? N * ceil_div(H, tile) * ceil_div(W, tile) : ceil_div(a.M, bm)) * npass;
+  return nwork < 2 * device_cu_count() ? nwork : 2 * device_cu_count();
 }
 
 // Block ids of a 1-D grid over mtiles x ncombo tiles.  XCD-aware order (xcd_remap = 1, when there are several column tiles /

@@ -33,12 +33,11 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace first {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int TH = 8, TW = 32;        // pixel tile of a block (4 waves x 2 rows)
 constexpr int HH = TH + 2, WW = TW + 2;
@@ -47,23 +46,17 @@ constexpr int KS = 14;                // K = 28 in steps of 2
 struct Args {
   const float* x_nchw;    // dense [N, 3, H, W], or NULL: read `x_lay` below
   const float* x_lay;     // shared-gap NHWC buffer with >= 3 channels per pixel (the plan's NHWC8 input)
-  int xl_cstride, xl_choff, xl_ws, xl_hs, xl_lead;
+  Lay lxl;
   const float* wp;        // packed filters [2 k halves][32 lanes][2 column halves][14 steps] (pack_first_kernel)
   const float* bias;      // 64 floats
   float* out;
-  int o_cstride, o_choff, o_ws, o_hs, o_lead;
+  Lay lo;
   int o_pq;               // PLANES: pixel slots per plane
   int N, H, W, relu, tiles_x, tiles_y;
 };
 
 __device__ __forceinline__ float round_bf16(float v) {  // RNE to bf16, as a float (v_cvt_pk_bf16_f32)
   return __uint_as_float((unsigned)__builtin_bit_cast(unsigned short, (__bf16)v) << 16);
-}
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {  // (bf16(a), bf16(b)), a in the low half
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  typedef float fl2 __attribute__((ext_vector_type(2)));
-  const fl2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf2));
 }
 
 // k = c * 9 + dy * 3 + dx (k = 27: the zero row) -> offset of the tap in the LDS halo [3][HH][WW]
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const Args A) {
       float v = 0.f;
       if (yy >= 0 && yy < A.H && xx >= 0 && xx < A.W) {
         v = A.x_nchw ? A.x_nchw[((size_t)(n * 3 + c) * A.H + yy) * A.W + xx]
-                     : A.x_lay[((size_t)A.xl_lead + (size_t)(n * A.xl_hs + yy) * A.xl_ws + xx) * A.xl_cstride + A.xl_choff + c];
+                     : A.x_lay[lay_off(A.lxl, n, yy, xx) + c];
       }
       hv[j] = BF16 ? round_bf16(v) : v;
     }
@@ -123,8 +116,6 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const Args A) {
   }
   // ---- filters: 28 values per lane (k = 2 step + kh, column = half * 32 + l31), bias in the accumulators ----
   // (MODE 2: 4 x 8 bf16 per lane - channel half * 32 + l31, taps 16 s + 8 kh .. + 7)
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
   float wv[2][BF16 ? 1 : KS];
   uintx4 wq[2][2];
   if (BF16) {
@@ -218,8 +209,8 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const Args A) {
     for (int mt = 0; mt < 2; ++mt) {
       const int y = y0 + 2 * wave + mt;
       const bool ok = y < A.H && x0 + l31 < A.W;
-      const size_t q = (size_t)A.o_lead + (size_t)(n * A.o_hs + min(y, A.H - 1)) * A.o_ws + min(x0 + l31, A.W - 1);
-      unsigned short* op = out16 + q * A.o_cstride + A.o_choff;
+      const size_t q = (size_t)A.lo.lead + (size_t)(n * A.lo.hs + min(y, A.H - 1)) * A.lo.ws + min(x0 + l31, A.W - 1);
+      unsigned short* op = out16 + q * A.lo.cstride + A.lo.choff;
 #pragma unroll
       for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
@@ -253,8 +244,8 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const Args A) {
     for (int mt = 0; mt < 2; ++mt) {
       const int y = y0 + 2 * wave + mt;
       if (y >= A.H || x0 + l31 >= A.W) continue;
-      const size_t q = (size_t)A.o_lead + (size_t)(n * A.o_hs + y) * A.o_ws + x0 + l31;
-      float* op = A.out + ((size_t)(A.o_choff >> 3) * A.o_pq + q) * 8 + 4 * kh;
+      const size_t q = (size_t)A.lo.lead + (size_t)(n * A.lo.hs + y) * A.lo.ws + x0 + l31;
+      float* op = A.out + ((size_t)(A.lo.choff >> 3) * A.o_pq + q) * 8 + 4 * kh;
 #pragma unroll
       for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
@@ -270,7 +261,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const Args A) {
   for (int mt = 0; mt < 2; ++mt) {
     const int y = y0 + 2 * wave + mt;
     if (y >= A.H) continue;
-    float* orow = A.out + ((size_t)A.o_lead + (size_t)(n * A.o_hs + y) * A.o_ws + x0) * A.o_cstride + A.o_choff + l31;
+    float* orow = A.out + ((size_t)A.lo.lead + (size_t)(n * A.lo.hs + y) * A.lo.ws + x0) * A.lo.cstride + A.lo.choff + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int px = (r >> 2) * 8 + 4 * kh + (r & 3);
@@ -278,7 +269,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const Args A) {
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh) {
           const float v = acc[mt][nh][r];
-          orow[(size_t)px * A.o_cstride + nh * 32] = A.relu ? fmaxf(v, 0.f) : v;
+          orow[(size_t)px * A.lo.cstride + nh * 32] = A.relu ? fmaxf(v, 0.f) : v;
         }
       }
     }
@@ -353,20 +344,12 @@ int conv_first_launch(const float* x_nchw, const float* x_lay, const rtpose_layo
   a.x_nchw = x_nchw;
   a.x_lay = x_lay;
   if (lx) {
-    a.xl_cstride = lx->cstride;
-    a.xl_choff = lx->choff;
-    a.xl_ws = lx->ws;
-    a.xl_hs = lx->hs;
-    a.xl_lead = lx->lead;
+    a.lxl = to_lay(lx);
   }
   a.wp = wp;
   a.bias = wp + 2 * 32 * 2 * KS;
   a.out = out;
-  a.o_cstride = lo->cstride;
-  a.o_choff = lo->choff;
-  a.o_ws = lo->ws;
-  a.o_hs = lo->hs;
-  a.o_lead = lo->lead;
+  a.lo = to_lay(lo);
   a.o_pq = out_plane_pixels;
   a.N = N;
   a.H = H;

@@ -34,27 +34,16 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-// Explicit global address space: if clang loses track of a pointer's provenance it
-// falls back to FLAT loads, which also tick lgkmcnt and drag every LDS read behind a
-// full `s_waitcnt vmcnt(0) lgkmcnt(0)` (seen in the tap loop; cost several %).
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef const floatx4 __attribute__((address_space(1)))* gcf4_t;
-__device__ __forceinline__ float4 gload4(const void* p) {
-  const floatx4 v = *(gcf4_t)(unsigned long long)(p);
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
 
 struct ConvGroup {
   const float* in;
   const float* w;
   const float* bias;
   float* out;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;
   int cout, cout_pad;
   const int32_t* out_cmap;  // optional output-channel scatter (see rtpose_conv_desc)
 };
@@ -95,7 +84,7 @@ using ConvArgsT = typename std::conditional<PR, ConvArgsP, ConvArgs>::type;
 // arguments the other instantiations read, for the same reason as ConvArgsP.
 struct ConvX {
   const float* res;       // NULL: no residual
-  int res_cstride, res_choff, res_ws, res_hs, res_lead;
+  Lay lres;
   const float* in_scale;  // NULL: no pre-activation; float[cin], 16-byte aligned
   const float* in_shift;
   int pre_cin;            // input channels >= pre_cin are staged as 0
@@ -185,14 +174,14 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
     const int HW = A.H * A.W;
     const int n = m0 / HW, r = m0 - n * HW;
     const int y = r / A.W, x = r - y * A.W;
-    qc0 = g.in_lead + (n * g.in_hs + y) * g.in_ws + x;
+    qc0 = g.lin.lead + (n * g.lin.hs + y) * g.lin.ws + x;
     int ml = min(m0 + BMT, A.M) - 1;
     const int n2 = ml / HW, r2 = ml - n2 * HW;
     const int y2 = r2 / A.W, x2 = r2 - y2 * A.W;
-    const int qcl = g.in_lead + (n2 * g.in_hs + y2) * g.in_ws + x2;
-    q_origin = qc0 - P * g.in_ws - P;
-    np_pix = qcl + P * g.in_ws + P - q_origin + 1;
-    row_lds = g.in_ws;
+    const int qcl = g.lin.lead + (n2 * g.lin.hs + y2) * g.lin.ws + x2;
+    q_origin = qc0 - P * g.lin.ws - P;
+    np_pix = qcl + P * g.lin.ws + P - q_origin + 1;
+    row_lds = g.lin.ws;
   } else {
     int b = m0_arg;  // MODE 1: the tile index
     const int txi = b % A.tiles_x;
@@ -202,7 +191,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
     const int TW = 1 << A.tw_log2, TH = kBM >> A.tw_log2;
     y0 = tyi * TH;
     x0 = txi * TW;
-    q_origin = g.in_lead + (n_img * g.in_hs + y0 - P) * g.in_ws + x0 - P;
+    q_origin = g.lin.lead + (n_img * g.lin.hs + y0 - P) * g.lin.ws + x0 - P;
     np_pix = (TH + 2 * P) * A.hw_lds;
     row_lds = A.hw_lds;
   }
@@ -226,7 +215,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
       // rows past the end of the tensor (last strip) read the last real pixel's halo
       const bool past = m0 + ml > A.M - 1;
       const int n = past ? A.N - 1 : an, y = past ? A.H - 1 : ay, x = past ? A.W - 1 : ax;
-      abase[fm] = g.in_lead + (n * g.in_hs + y) * g.in_ws + x - qc0;
+      abase[fm] = g.lin.lead + (n * g.lin.hs + y) * g.lin.ws + x - qc0;
       ax += 32;
       while (ax >= A.W) {
         ax -= A.W;
@@ -245,8 +234,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
   // ---- halo staging helpers -------------------------------------------------
   // A halo is staged as 16-byte pieces: piece idx = (pixel idx/CG, channel group idx%CG);
   // thread `tid` owns pieces tid, tid+256, ... ("sets").  LDS image: [group][pixel][4].
-  const int in_cstride = g.in_cstride, in_ws = g.in_ws;
-  const float* in_base = g.in + g.in_choff;
+  const int in_cstride = g.lin.cstride, in_ws = g.lin.ws;
+  const float* in_base = g.in + g.lin.choff;
   constexpr int PIXSET = 256 / CGB;             // halo pixels covered by one piece set
   const int pj = tid % CGB, ppix0 = tid / CGB;  // this thread's group and first pixel
   const unsigned hw_inv = MODE == 1 ? (65536u + A.hw_lds - 1) / A.hw_lds : 0u;
@@ -379,9 +368,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
   // B register (k-group) n is fetched after MFMA pair n < GB
   // memory clobber: loads/stores may not cross (IR + DAG); sched_barrier: nothing may
   // cross in the machine scheduler
-#define RTPOSE_PIN()                 \
-  asm volatile("" ::: "memory");     \
-  __builtin_amdgcn_sched_barrier(0)
 #define RTPOSE_CONV_STEP(ACUR, ANXT, BCUR, BLOAD, KX, STAGE)                                   \
   {                                                                                            \
     _Pragma("unroll") for (int n = 0; n < 4 * G; ++n) {                                        \
@@ -513,14 +499,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
   }
 #undef RTPOSE_CONV_ROW
 #undef RTPOSE_CONV_STEP
-#undef RTPOSE_PIN
 
   // ---- epilogue: bias (+ReLU) (+2x2 max-pool), masked stores -----------------
 #pragma unroll
   for (int fn = 0; fn < NF; ++fn) {
   const int ncolf = ncol + fn * 32;
   const bool col_ok = ncolf < g.cout;
-  float* out_base = g.out + ((g.out_cmap && col_ok) ? g.out_cmap[ncolf] : g.out_choff + ncolf);
+  float* out_base = g.out + ((g.out_cmap && col_ok) ? g.out_cmap[ncolf] : g.lout.choff + ncolf);
   if (!A.pool) {
     // strip mode: the lane's rows are m0 + wm*32*MF + 4*kh + {0,1,2,3, 8,9,10,11, 16,...}: pixel
     // coordinates by ONE division pair, then stepped (+1,+1,+1,+5 repeating).  An integer division
@@ -578,11 +563,11 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
             if constexpr (XT) {
               // the residual element of this output element alone (it may be the element about to be overwritten)
               if (X->res)
-                v += X->res[((size_t)X->res_lead + (size_t)(n * X->res_hs + y) * X->res_ws + x) * X->res_cstride +
-                            X->res_choff + ncolf];
+                v += X->res[((size_t)X->lres.lead + (size_t)(n * X->lres.hs + y) * X->lres.ws + x) * X->lres.cstride +
+                            X->lres.choff + ncolf];
             }
-            const size_t q = (size_t)g.out_lead + (size_t)(n * g.out_hs + y) * g.out_ws + x;
-            out_base[q * g.out_cstride] = v;
+            const size_t q = (size_t)g.lout.lead + (size_t)(n * g.lout.hs + y) * g.lout.ws + x;
+            out_base[q * g.lout.cstride] = v;
           }
         }
       }
@@ -603,8 +588,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const ConvGroup& g,
                         fmaxf(acc[fm][fn][rg * 4 + 2], acc[fm][fn][rg * 4 + 3]));
         if (A.relu) v = relu_of(v, A.relu);
         if (py < Ho && px < Wo && col_ok) {
-          const size_t q = (size_t)g.out_lead + (size_t)(n_img * g.out_hs + py) * g.out_ws + px;
-          out_base[q * g.out_cstride] = v;
+          const size_t q = (size_t)g.lout.lead + (size_t)(n_img * g.lout.hs + py) * g.lout.ws + px;
+          out_base[q * g.lout.cstride] = v;
         }
       }
     }
@@ -870,11 +855,7 @@ int conv2d_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, int W, h
     memset(&ax.x, 0, sizeof(ax.x));
     if (has_res) {
       ax.x.res = d0.residual;
-      ax.x.res_cstride = d0.lres.cstride;
-      ax.x.res_choff = d0.lres.choff;
-      ax.x.res_ws = d0.lres.ws;
-      ax.x.res_hs = d0.lres.hs;
-      ax.x.res_lead = d0.lres.lead;
+      ax.x.lres = to_lay(d0.lres);
     }
     if (has_pre) {
       ax.x.in_scale = d0.in_scale;

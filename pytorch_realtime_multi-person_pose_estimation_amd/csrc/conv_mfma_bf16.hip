@@ -36,43 +36,12 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace bf {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef const floatx4 __attribute__((address_space(1)))* gcf4_t;
-// explicit global address space (see conv_mfma.hip: FLAT loads drag LDS reads behind vmcnt)
-__device__ __forceinline__ float4 gload4(const void* p) {
-  const floatx4 v = *(gcf4_t)(unsigned long long)(p);
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
-typedef floatx4 __attribute__((address_space(1)))* gf4_t;
-__device__ __forceinline__ void gstore4(void* p, const float4& v) {
-  const floatx4 t = {v.x, v.y, v.z, v.w};
-  *(gf4_t)(unsigned long long)(p) = t;
-}
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-  const floatx4 v = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ bf16x8 as_bf8(const float4& v) {
-  const floatx4 t = {v.x, v.y, v.z, v.w};
-  return __builtin_bit_cast(bf16x8, t);
-}
-__device__ __forceinline__ unsigned short to_bf16(float v) {
-  return __builtin_bit_cast(unsigned short, (__bf16)v);  // v_cvt_pk_bf16_f32: RNE
-}
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf2(float a, float b) {  // (bf16(a), bf16(b)) in one dword, a in the low half
-  const floatx2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 __device__ __forceinline__ float4 as_f4(unsigned a, unsigned b, unsigned c, unsigned d) {
   return make_float4(__uint_as_float(a), __uint_as_float(b), __uint_as_float(c), __uint_as_float(d));
 }
@@ -82,8 +51,7 @@ struct ConvGroup {
   const float4* w;           // packed bf16 weights, 16-byte pieces
   const float* bias;         // fp32, padded to cout_pad
   void* out;                 // bf16 or fp32 activations
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;  // channel counts in ELEMENTS
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;  // channel counts in ELEMENTS
   int cout, cout_pad;
   const int32_t* out_cmap;
 };
@@ -199,13 +167,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     const int HW = A.H * A.W;
     const int n = m0s / HW, r = m0s - n * HW;
     const int y = r / A.W, x = r - y * A.W;
-    const int qf = gg.in_lead + (n * gg.in_hs + y) * gg.in_ws + x;
+    const int qf = gg.lin.lead + (n * gg.lin.hs + y) * gg.lin.ws + x;
     const int ml = min(m0s + 32 * MF * WM, A.M) - 1;
     const int n2 = ml / HW, r2 = ml - n2 * HW;
     const int y2 = r2 / A.W, x2 = r2 - y2 * A.W;
-    const int ql = gg.in_lead + (n2 * gg.in_hs + y2) * gg.in_ws + x2;
-    q_org = qf - (KS / 2) * gg.in_ws - (KS / 2);
-    np_tot = (ql + (KS / 2) * gg.in_ws + (KS / 2) - q_org + 1) * (CK / 8 * SP);
+    const int ql = gg.lin.lead + (n2 * gg.lin.hs + y2) * gg.lin.ws + x2;
+    q_org = qf - (KS / 2) * gg.lin.ws - (KS / 2);
+    np_tot = (ql + (KS / 2) * gg.lin.ws + (KS / 2) - q_org + 1) * (CK / 8 * SP);
   };
   // One tile.  Instantiated twice: FIRST (the block's first tile fills its own halo - the prologue) and the
   // persistent continuation, whose chunk 0 was staged by the previous tile.  Keeping the prologue out of the
@@ -223,14 +191,14 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     const int HW = A.H * A.W;
     const int n = m0 / HW, r = m0 - n * HW;
     const int y = r / A.W, x = r - y * A.W;
-    qc0 = g.in_lead + (n * g.in_hs + y) * g.in_ws + x;
+    qc0 = g.lin.lead + (n * g.lin.hs + y) * g.lin.ws + x;
     const int ml = min(m0 + BMT, A.M) - 1;
     const int n2 = ml / HW, r2 = ml - n2 * HW;
     const int y2 = r2 / A.W, x2 = r2 - y2 * A.W;
-    const int qcl = g.in_lead + (n2 * g.in_hs + y2) * g.in_ws + x2;
-    q_origin = qc0 - P * g.in_ws - P;
-    np_pix = qcl + P * g.in_ws + P - q_origin + 1;
-    row_lds = g.in_ws;
+    const int qcl = g.lin.lead + (n2 * g.lin.hs + y2) * g.lin.ws + x2;
+    q_origin = qc0 - P * g.lin.ws - P;
+    np_pix = qcl + P * g.lin.ws + P - q_origin + 1;
+    row_lds = g.lin.ws;
   } else {
     int b = m0_arg;
     const int txi = b % A.tiles_x;
@@ -240,15 +208,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     const int TW = 1 << A.tw_log2, TH = kBM >> A.tw_log2;
     y0 = tyi * TH;
     x0 = txi * TW;
-    q_origin = g.in_lead + (n_img * g.in_hs + y0 - P) * g.in_ws + x0 - P;
+    q_origin = g.lin.lead + (n_img * g.lin.hs + y0 - P) * g.lin.ws + x0 - P;
     np_pix = (TH + 2 * P) * A.hw_lds;
     row_lds = A.hw_lds;
   }
   const int np_total = np_pix * CG;  // 16-byte pieces per LDS buffer
 
   // ---- halo staging helpers: piece idx = (pixel idx / CG, piece idx % CG) ------------
-  const int in_cs4 = g.in_cstride >> 3, in_ws = g.in_ws;  // 16-byte pieces per pixel
-  const float4* in_base = reinterpret_cast<const float4*>(g.in + g.in_choff);
+  const int in_cs4 = g.lin.cstride >> 3, in_ws = g.lin.ws;  // 16-byte pieces per pixel
+  const float4* in_base = reinterpret_cast<const float4*>(g.in + g.lin.choff);
   constexpr int PIXSET = 256 / CG;
   const int pj = tid % CG, ppix0 = tid / CG;
   const unsigned hw_inv = MODE == 1 ? (65536u + A.hw_lds - 1) / A.hw_lds : 0u;
@@ -298,7 +266,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     }
   }
   const float4* nx_in_base = reinterpret_cast<const float4*>(
-      nx_grp ? A.g[1].in + A.g[1].in_choff : A.g[0].in + A.g[0].in_choff);
+      nx_grp ? A.g[1].in + A.g[1].lin.choff : A.g[0].in + A.g[0].lin.choff);
   const int nx_nsets = (nx_np_total + 255) / 256;
   float4 pf[kFillDepth];
   const bool pro_fast = FIRST && NBUF == 2 && nsets <= kFillDepth;
@@ -326,7 +294,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
       // rows past the end of the tensor (last strip) read the last real pixel's halo
       const bool past = m0 + ml > A.M - 1;
       const int n = past ? A.N - 1 : an, y = past ? A.H - 1 : ay, x = past ? A.W - 1 : ax;
-      abase[fm] = g.in_lead + (n * g.in_hs + y) * g.in_ws + x - qc0;
+      abase[fm] = g.lin.lead + (n * g.lin.hs + y) * g.lin.ws + x - qc0;
       ax += 32;
       while (ax >= A.W) {
         ax -= A.W;
@@ -438,9 +406,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     return TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(wt), as_bf8(px), c, 0, 0, 0)
               : __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(px), as_bf8(wt), c, 0, 0, 0);
   };
-#define RTPOSE_PIN()             \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
   // One tap = G K-steps of MF*NF MFMAs; after K-step n: the B pieces of step n for the tap
   // two ahead, then the A pieces of step n for the next tap, then (last step, staged rows
   // only) one halo piece parked and one fetched.
@@ -566,7 +531,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
   }
 #undef RTPOSE_CONV_ROW
 #undef RTPOSE_CONV_STEP
-#undef RTPOSE_PIN
 #undef RTPOSE_BLOAD
 
   // ---- epilogue: bias (+ReLU) (+2x2 max-pool), masked stores, bf16 (RNE) or fp32 ---------
@@ -590,14 +554,14 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
       oy = r / A.W;
       ox = r - oy * A.W;
     }
-    unsigned short* const ob = out_h + g.out_choff + (ntile * BN + wn * (32 * NF) + 16 * kh) * SP;
+    unsigned short* const ob = out_h + g.lout.choff + (ntile * BN + wn * (32 * NF) + 16 * kh) * SP;
 #pragma unroll
     for (int fm = 0; fm < MF; ++fm) {
       bool ok;
       size_t q;
       if (MODE == 0) {
         ok = m0 + wm * (32 * MF) + fm * 32 + l31 < A.M;
-        q = (size_t)g.out_lead + (size_t)(on * g.out_hs + oy) * g.out_ws + ox;
+        q = (size_t)g.lout.lead + (size_t)(on * g.lout.hs + oy) * g.lout.ws + ox;
         ox += 32;
         while (ox >= A.W) {
           ox -= A.W;
@@ -610,15 +574,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
         int ty, tx;
         tile_local_yx(wm * (32 * MF) + fm * 32 + l31, A.tw_log2, ty, tx);
         ok = (y0 + ty < A.H) && (x0 + tx < A.W);
-        q = (size_t)g.out_lead + (size_t)(n_img * g.out_hs + y0 + ty) * g.out_ws + x0 + tx;
+        q = (size_t)g.lout.lead + (size_t)(n_img * g.lout.hs + y0 + ty) * g.lout.ws + x0 + tx;
       }
-      unsigned short* const op = ob + q * g.out_cstride;
+      unsigned short* const op = ob + q * g.lout.cstride;
 #pragma unroll
       for (int fn = 0; fn < NF; ++fn) {
         unsigned hi[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          hi[i] = pack_bf2(act(acc[fm][fn][2 * i]), act(acc[fm][fn][2 * i + 1]));
+          hi[i] = pack_bf16x2(act(acc[fm][fn][2 * i]), act(acc[fm][fn][2 * i + 1]));
         if (SP == 1) {
           if (ok) {
             gstore4(op + fn * 32, as_f4(hi[0], hi[1], hi[2], hi[3]));
@@ -628,7 +592,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
           unsigned lo[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i)
-            lo[i] = pack_bf2(act(acc[fm][fn][2 * i]) - __uint_as_float(hi[i] << 16),
+            lo[i] = pack_bf16x2(act(acc[fm][fn][2 * i]) - __uint_as_float(hi[i] << 16),
                              act(acc[fm][fn][2 * i + 1]) - __uint_as_float(hi[i] & 0xffff0000u));
           if (ok) {
             gstore4(op + fn * 64, as_f4(hi[0], hi[1], hi[2], hi[3]));
@@ -653,15 +617,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     auto put = [&](int row, int fn, float v) {
       v = act(v);
       unsigned short* d = sl + row * PITCH2 + fn * 32 * SP + ce;
-      const unsigned short hi = to_bf16(v);
+      const unsigned short hi = f32_to_bf16_rne(v);
       d[0] = hi;
-      if (SP == 2) d[8] = to_bf16(v - __uint_as_float((unsigned)hi << 16));
+      if (SP == 2) d[8] = f32_to_bf16_rne(v - __uint_as_float((unsigned)hi << 16));
     };
     constexpr int LPR = NF * 4 * SP;  // lanes (16 bytes each) per slab row
     constexpr int RPI = 64 / LPR;   // rows per wave-instruction
     const int rows_h = pool ? 8 * MFH : 32 * MFH;  // slab rows per half
     const int lrow = lane / LPR, c16 = lane % LPR;
-    unsigned short* ob = out_h + g.out_choff + (ntile * BN + wn * (32 * NF)) * SP + c16 * 8;
+    unsigned short* ob = out_h + g.lout.choff + (ntile * BN + wn * (32 * NF)) * SP + c16 * 8;
     const int Ho = A.H >> 1, Wo = A.W >> 1;
     // strip mode: (n, y, x) of this lane's first row by division once, then stepped by RPI pixels
     // (integer division is ~40 VALU instructions; 8 row steps of it were a third of the epilogue)
@@ -733,8 +697,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
           ok = (y < A.H) && (x < A.W);
         }
         if (ok && row < rows_h) {
-          const size_t q = (size_t)g.out_lead + (size_t)(n * g.out_hs + y) * g.out_ws + x;
-          gstore4(ob + q * g.out_cstride, v);
+          const size_t q = (size_t)g.lout.lead + (size_t)(n * g.lout.hs + y) * g.lout.ws + x;
+          gstore4(ob + q * g.lout.cstride, v);
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // slab reads precede the next half's writes
@@ -745,10 +709,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
     const int ncolf = ncol + fn * 32;
     const bool col_ok = ncolf < g.cout;
     // (split layouts: out_choff counts elements = 2 x channels; out_cmap is not combined with them)
-    const int och = (g.out_cmap && col_ok) ? g.out_cmap[ncolf] : (SP == 1 || A.out_f32 ? g.out_choff + ncolf : 0);
+    const int och = (g.out_cmap && col_ok) ? g.out_cmap[ncolf] : (SP == 1 || A.out_f32 ? g.lout.choff + ncolf : 0);
     // split: out_choff counts elements (2 per channel) and may sit inside an 8-channel group (the
     // heat-map slice of the concat buffer starts at channel 166): address by absolute channel
-    const int ca = (g.out_choff >> 1) + ncolf;
+    const int ca = (g.lout.choff >> 1) + ncolf;
     const int ochs = (ca >> 3) * 16 + (ca & 7);  // hi element, lo at +8
     if (!pool) {
 #pragma unroll
@@ -779,15 +743,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
             }
             const float v = act(acc[fm][fn][rg * 4 + rr]);
             if (ok && col_ok) {
-              const size_t q = (size_t)g.out_lead + (size_t)(n * g.out_hs + y) * g.out_ws + x;
+              const size_t q = (size_t)g.lout.lead + (size_t)(n * g.lout.hs + y) * g.lout.ws + x;
               if (A.out_f32) {
-                out_f[q * g.out_cstride + och] = v;
+                out_f[q * g.lout.cstride + och] = v;
               } else if (SP == 1) {
-                out_h[q * g.out_cstride + och] = to_bf16(v);
+                out_h[q * g.lout.cstride + och] = f32_to_bf16_rne(v);
               } else {
-                const unsigned short hi = to_bf16(v);
-                out_h[q * g.out_cstride + ochs] = hi;
-                out_h[q * g.out_cstride + ochs + 8] = to_bf16(v - __uint_as_float((unsigned)hi << 16));
+                const unsigned short hi = f32_to_bf16_rne(v);
+                out_h[q * g.lout.cstride + ochs] = hi;
+                out_h[q * g.lout.cstride + ochs + 8] = f32_to_bf16_rne(v - __uint_as_float((unsigned)hi << 16));
               }
             }
           }
@@ -807,15 +771,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& A, const int grp_first
           const float v = act(fmaxf(fmaxf(acc[fm][fn][rg * 4 + 0], acc[fm][fn][rg * 4 + 1]),
                                     fmaxf(acc[fm][fn][rg * 4 + 2], acc[fm][fn][rg * 4 + 3])));
           if (py < Ho && px < Wo && col_ok) {
-            const size_t q = (size_t)g.out_lead + (size_t)(n_img * g.out_hs + py) * g.out_ws + px;
+            const size_t q = (size_t)g.lout.lead + (size_t)(n_img * g.lout.hs + py) * g.lout.ws + px;
             if (A.out_f32) {
-              out_f[q * g.out_cstride + och] = v;
+              out_f[q * g.lout.cstride + och] = v;
             } else if (SP == 1) {
-              out_h[q * g.out_cstride + och] = to_bf16(v);
+              out_h[q * g.lout.cstride + och] = f32_to_bf16_rne(v);
             } else {
-              const unsigned short hi = to_bf16(v);
-              out_h[q * g.out_cstride + ochs] = hi;
-              out_h[q * g.out_cstride + ochs + 8] = to_bf16(v - __uint_as_float((unsigned)hi << 16));
+              const unsigned short hi = f32_to_bf16_rne(v);
+              out_h[q * g.lout.cstride + ochs] = hi;
+              out_h[q * g.lout.cstride + ochs + 8] = f32_to_bf16_rne(v - __uint_as_float((unsigned)hi << 16));
             }
           }
         }
@@ -901,8 +865,8 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, const floa
     const int ky = tap / k, kx = tap - ky * k;
     v = w[(((size_t)n * cin_src + src) * k + ky) * k + kx];
   }
-  const unsigned short hi = to_bf16(v);
-  wp[i] = lo ? to_bf16(v - __uint_as_float((unsigned)hi << 16)) : hi;
+  const unsigned short hi = f32_to_bf16_rne(v);
+  wp[i] = lo ? f32_to_bf16_rne(v - __uint_as_float((unsigned)hi << 16)) : hi;
 }
 
 // ---- host side ----------------------------------------------------------------------------

@@ -14,12 +14,12 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace tail {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 64;    // pixels per block
 constexpr int KC = 128;   // input channels of both GEMMs
@@ -34,8 +34,7 @@ struct Group {
   const float* w2;
   const float* b2;
   float* out;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;
   int cout2;
 };
 
@@ -68,8 +67,8 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void tail_kernel(const Args A
     const int HW = A.H * A.W;
     const int n = m / HW, r = m - n * HW;
     const int y = r / A.W, x = r - y * A.W;
-    qin[tid] = (g.in_lead + (n * g.in_hs + y) * g.in_ws + x) * g.in_cstride + g.in_choff;
-    qout[tid] = (g.out_lead + (n * g.out_hs + y) * g.out_ws + x) * g.out_cstride + g.out_choff;
+    qin[tid] = lay_elem(g.lin, n, y, x);
+    qout[tid] = lay_elem(g.lout, n, y, x);
   }
   // ---- B fragments of GEMM 1, pass 0 (this wave's 32 columns, all 16 k groups): issued before the wait ----
   float4 b1v[KC / 8];
@@ -207,16 +206,8 @@ int conv_tail_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2, int
     g.w2 = d2[i].w_packed;
     g.b2 = d2[i].bias_packed;
     g.out = d2[i].out;
-    g.in_cstride = d1[i].lin.cstride;
-    g.in_choff = d1[i].lin.choff;
-    g.in_ws = d1[i].lin.ws;
-    g.in_hs = d1[i].lin.hs;
-    g.in_lead = d1[i].lin.lead;
-    g.out_cstride = d2[i].lout.cstride;
-    g.out_choff = d2[i].lout.choff;
-    g.out_ws = d2[i].lout.ws;
-    g.out_hs = d2[i].lout.hs;
-    g.out_lead = d2[i].lout.lead;
+    g.lin = to_lay(d1[i].lin);
+    g.lout = to_lay(d2[i].lout);
     g.cout2 = d2[i].cout;
     // 32-bit element offsets inside the kernel
     if (!below_2g_elems(d1[i].lin, N, H, W) || !below_2g_elems(d2[i].lout, N, H, W))

@@ -23,14 +23,11 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace tailb {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 64;      // pixels per block
 constexpr int KC = 128;     // input channels, and intermediate channels per pass
@@ -45,8 +42,7 @@ struct Group {
   const uintx4* w2;
   const float* b2;
   void* out;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;
   int cout2, coutp1, coutp2;
 };
 
@@ -54,13 +50,6 @@ struct Args {
   Group g[2];
   int N, H, W, M, ngroups, out_f32, relu2;
 };
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {  // (bf16(a), bf16(b)) RNE, a in the low half
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  typedef float fl2 __attribute__((ext_vector_type(2)));
-  const fl2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf2));
-}
 
 constexpr size_t lds_bytes() { return (size_t)2 * 16 * PS * 16 + (size_t)BM * OS * 4 + 2 * BM * 4; }
 
@@ -85,8 +74,8 @@ __global__ __launch_bounds__(256) void tail_bf16_kernel(const Args A) {
     const int HW = A.H * A.W;
     const int n = mc / HW, r = mc - n * HW;
     const int y = r / A.W, x = r - y * A.W;
-    qin[tid] = (g.in_lead + (n * g.in_hs + y) * g.in_ws + x) * g.in_cstride + g.in_choff;
-    qout[tid] = m < A.M ? (g.out_lead + (n * g.out_hs + y) * g.out_ws + x) * g.out_cstride + g.out_choff : -1;
+    qin[tid] = lay_elem(g.lin, n, y, x);
+    qout[tid] = m < A.M ? lay_elem(g.lout, n, y, x) : -1;
   }
   // ---- A fragments of GEMM 1, pass 0 (this wave's 32 channels, all 8 k steps): requested before the first wait ----
   uintx4 w1v[KC / 16];
@@ -165,8 +154,8 @@ __global__ __launch_bounds__(256) void tail_bf16_kernel(const Args A) {
         unsigned a[2], b[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          a[e] = pack2(fmaxf(acc[nf][8 * m + 2 * e], 0.f), fmaxf(acc[nf][8 * m + 2 * e + 1], 0.f));
-          b[e] = pack2(fmaxf(acc[nf][8 * m + 4 + 2 * e], 0.f), fmaxf(acc[nf][8 * m + 4 + 2 * e + 1], 0.f));
+          a[e] = pack_bf16x2(fmaxf(acc[nf][8 * m + 2 * e], 0.f), fmaxf(acc[nf][8 * m + 2 * e + 1], 0.f));
+          b[e] = pack_bf16x2(fmaxf(acc[nf][8 * m + 4 + 2 * e], 0.f), fmaxf(acc[nf][8 * m + 4 + 2 * e + 1], 0.f));
           const auto sw = __builtin_amdgcn_permlane32_swap(a[e], b[e], false, false);  // lanes 32..63 of a <-> lanes 0..31 of b
           a[e] = sw[0];
           b[e] = sw[1];
@@ -253,16 +242,8 @@ int conv_tail_bf16_launch(const rtpose_conv_desc* d1, const rtpose_conv_desc* d2
     q.w2 = reinterpret_cast<const uintx4*>(d2[g].w_packed);
     q.b2 = d2[g].bias_packed;
     q.out = d2[g].out;
-    q.in_cstride = d1[g].lin.cstride;
-    q.in_choff = d1[g].lin.choff;
-    q.in_ws = d1[g].lin.ws;
-    q.in_hs = d1[g].lin.hs;
-    q.in_lead = d1[g].lin.lead;
-    q.out_cstride = d2[g].lout.cstride;
-    q.out_choff = d2[g].lout.choff;
-    q.out_ws = d2[g].lout.ws;
-    q.out_hs = d2[g].lout.hs;
-    q.out_lead = d2[g].lout.lead;
+    q.lin = to_lay(d1[g].lin);
+    q.lout = to_lay(d2[g].lout);
     q.cout2 = d2[g].cout;
     q.coutp1 = cout_pad(d1[g].cout);
     q.coutp2 = cout_pad(d2[g].cout);

@@ -52,8 +52,7 @@ struct Group {
   const float* w;
   const float* bias;
   float* out;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;
   int cout, cout_pad;
   size_t in_bytes, w_bytes, out_bytes;  // extents of the three allocations from in / w / out (hardware bounds clamp)
 };
@@ -145,13 +144,13 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
     auto patch_q = [&](int t) -> size_t {
       const int n = t / TT, r = t - n * TT;
       const int ty = r / A.TX, tx = r - ty * A.TX;
-      return (size_t)g.in_lead + (size_t)(n * g.in_hs + 2 * ty - 1) * g.in_ws + (2 * tx - 1);
+      return (size_t)g.lin.lead + (size_t)(n * g.lin.hs + 2 * ty - 1) * g.lin.ws + (2 * tx - 1);
     };
     const size_t q0 = patch_q(min(mt * NT, A.T - 1));                // uniform: lowest address of the tile
     const size_t q = patch_q(min(mt * NT + tl, A.T - 1));            // wtiles past the end re-read the last one
-    const size_t o0 = q0 * g.in_cstride + g.in_choff;
+    const size_t o0 = q0 * g.lin.cstride + g.lin.choff;
     r_ = make_rsrc(g.in + o0, g.in_bytes - o0 * 4);
-    v_ = (unsigned)(((q - q0) * g.in_cstride + cg * 4) * 4);
+    v_ = (unsigned)(((q - q0) * g.lin.cstride + cg * 4) * 4);
   };
   set_loader(j0, rin, pvoff);
   constexpr int NROW = IPT == 2 ? 4 : 3, NPC = 4 * NROW;  // patch rows / 16-byte pieces a thread loads per chunk
@@ -159,9 +158,9 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
 #pragma unroll
   for (int r = 0; r < NROW; ++r) {
     const int row = half ? (r == 0 ? 2 : r == 1 ? 3 : 1) : r;
-    psoff[r] = (unsigned)(row * g.in_ws * g.in_cstride * 4);
+    psoff[r] = (unsigned)(row * g.lin.ws * g.lin.cstride * 4);
   }
-  const unsigned pxb = (unsigned)g.in_cstride * 4;  // bytes per pixel
+  const unsigned pxb = (unsigned)g.lin.cstride * 4;  // bytes per pixel
   F4 p[NROW][4], ta[4], tb[4];
   auto load_piece_from = [&](const i32x4& r_, unsigned v_, int chunk, int i) {
     p[i >> 2][i & 3] = bload(r_, v_, (unsigned)chunk * (CK * 4) + psoff[i >> 2] + (i & 3) * pxb);
@@ -248,7 +247,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
 #pragma unroll
     for (int fs = 0; fs < 2; ++fs)
 #pragma unroll
-      for (int gi = 0; gi < G; ++gi) bs[s2][fs][gi] = bload_f4(rw, boff, wso + (fs * CG + 2 * gi) * cgstep);
+      for (int gi = 0; gi < G; ++gi) bs[s2][fs][gi] = bload4(rw, boff, wso + (fs * CG + 2 * gi) * cgstep);
     wso += bstep;
   }
   __syncthreads();
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
 #pragma unroll
       for (int fs = 0; fs < 2; ++fs)
 #pragma unroll
-        for (int gi = 0; gi < G; ++gi) bs[s2][fs][gi] = bload_f4(rw, boff, wso + (fs * CG + 2 * gi) * cgstep);
+        for (int gi = 0; gi < G; ++gi) bs[s2][fs][gi] = bload4(rw, boff, wso + (fs * CG + 2 * gi) * cgstep);
       wso += bstep;
     }
   }
@@ -282,9 +281,6 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
   // pairs, in a fixed (pinned) order: the A fragments of the next step (LDS), the B fragments two steps
   // ahead (L2); the last slot of step 0 / 1 also carries the two halves of the input transform of the NEXT
   // chunk, the last slots of steps 2..7 two patch loads each of the chunk after that.
-#define RTPOSE_PIN()             \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
   constexpr int SLOTS = 4 * G;  // MFMA pairs (= filler slots) per step
   float4 a[2][2][G];            // [step % 2][frequency of the pair][k group]
   for (int chunk = 0; chunk < nchunks; ++chunk) {
@@ -323,7 +319,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
             a[(s + 1) & 1][slot / G][slot % G] = va[slot % G][(2 * (s + 1) + slot / G) * CG * NT];
         } else {             // B two steps ahead
           const int i = slot - 2 * G;
-          bs[(s + 2) & 3][i / G][i % G] = bload_f4(rw, boff, wso + ((i / G) * CG + 2 * (i % G)) * cgstep);
+          bs[(s + 2) & 3][i / G][i % G] = bload4(rw, boff, wso + ((i / G) * CG + 2 * (i % G)) * cgstep);
           // (after step 5 of a tile's last chunk the ring wraps to the first steps of the next tile's chunk 0)
           if (slot == SLOTS - 1) wso = (BRING && s == 5 && chunk == nchunks - 1) ? 0u : wso + bstep;
         }
@@ -366,7 +362,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
   {
     const bool col_ok = ncol < g.cout;
     const int sc = A.pool ? 1 : 2;  // output pixels per wtile and direction
-    auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.out_hs + sc * ty) * g.out_ws + sc * tx; };
+    auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.lout.hs + sc * ty) * g.lout.ws + sc * tx; };
     int q0;                          // uniform: first wtile of the block's tile
     {
       const int t = min(mt * NT, A.T - 1);
@@ -374,9 +370,9 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
       const int ty = r / A.TX;
       q0 = wt_q(n, ty, r - ty * A.TX);
     }
-    const size_t oo0 = ((size_t)g.out_lead + (size_t)q0) * g.out_cstride + g.out_choff;
+    const size_t oo0 = ((size_t)g.lout.lead + (size_t)q0) * g.lout.cstride + g.lout.choff;
     const i32x4 rout = make_rsrc(g.out + oo0, g.out_bytes - oo0 * 4);
-    const unsigned cs4 = (unsigned)g.out_cstride * 4, row4 = (unsigned)g.out_ws * cs4;
+    const unsigned cs4 = (unsigned)g.lout.cstride * 4, row4 = (unsigned)g.lout.ws * cs4;
     const unsigned col4 = (unsigned)ncol * 4;
 #pragma unroll
     for (int rg = 0; rg < W_EPI / 4; ++rg) {
@@ -432,7 +428,6 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const ArgsT<PR> A) {
     }
   }
   }  // m tiles of this block
-#undef RTPOSE_PIN
 }
 
 // Small grids (few images): the same arithmetic on more blocks, as wino7s_f32 (conv_wino7.hip).  A block = 32 wtiles x
@@ -466,21 +461,21 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const ArgsT<PR> A) {
     auto patch_q = [&](int t) -> size_t {
       const int n = t / TT, r = t - n * TT;
       const int ty = r / A.TX, tx = r - ty * A.TX;
-      return (size_t)g.in_lead + (size_t)(n * g.in_hs + 2 * ty - 1) * g.in_ws + (2 * tx - 1);
+      return (size_t)g.lin.lead + (size_t)(n * g.lin.hs + 2 * ty - 1) * g.lin.ws + (2 * tx - 1);
     };
     const size_t q0 = patch_q(min(mt * NT, A.T - 1));
     const size_t q = patch_q(min(mt * NT + tl, A.T - 1));
-    const size_t o0 = q0 * g.in_cstride + g.in_choff;
+    const size_t o0 = q0 * g.lin.cstride + g.lin.choff;
     rin = make_rsrc(g.in + o0, g.in_bytes - o0 * 4);
-    pvoff = (unsigned)(((q - q0) * g.in_cstride + cg * 4) * 4);
+    pvoff = (unsigned)(((q - q0) * g.lin.cstride + cg * 4) * 4);
   }
   unsigned psoff[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     const int row = half ? (r == 0 ? 2 : r == 1 ? 3 : 1) : r;
-    psoff[r] = (unsigned)(row * g.in_ws * g.in_cstride * 4);
+    psoff[r] = (unsigned)(row * g.lin.ws * g.lin.cstride * 4);
   }
-  const unsigned pxb = (unsigned)g.in_cstride * 4;
+  const unsigned pxb = (unsigned)g.lin.cstride * 4;
   F4 p[3][4], ta[4], tb[4];
   auto load_piece = [&](int chunk, int i) {
     p[i >> 2][i & 3] = bload(rin, pvoff, (unsigned)chunk * (CK * 4) + psoff[i >> 2] + (i & 3) * pxb);
@@ -529,7 +524,7 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const ArgsT<PR> A) {
     for (int f = 0; f < 4; ++f)
 #pragma unroll
       for (int gi = 0; gi < G; ++gi)
-        dst[f][gi] = bload_f4(rw, boff, (unsigned)chunk * cstep + (unsigned)(4 * wv + f) * fstep + 2 * gi * cgstep);
+        dst[f][gi] = bload4(rw, boff, (unsigned)chunk * cstep + (unsigned)(4 * wv + f) * fstep + 2 * gi * cgstep);
   };
 #pragma unroll
   for (int i = 0; i < 12; ++i) load_piece(0, i);
@@ -543,9 +538,6 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const ArgsT<PR> A) {
   load_b(bcur, 0);
   __syncthreads();
 
-#define RTPOSE_PIN()             \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
   for (int chunk = 0; chunk < nchunks; ++chunk) {
     const float4* vab = V4 + (chunk & 1) * VBUF;
     const int nbuf = (chunk + 1) & 1;
@@ -584,7 +576,6 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const ArgsT<PR> A) {
       for (int gi = 0; gi < G; ++gi) bcur[f][gi] = bnxt[f][gi];
     __syncthreads();
   }
-#undef RTPOSE_PIN
 
   // ---- exchange through LDS (the V buffers are free), then output transform + stores as in wino_f32 ------
   float* E = reinterpret_cast<float*>(V4);  // E[f][r][lane]: 16 x 16 x 64 floats = the two V buffers
@@ -596,7 +587,7 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const ArgsT<PR> A) {
   {
     const bool col_ok = ncol < g.cout;
     const int sc = A.pool ? 1 : 2;
-    auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.out_hs + sc * ty) * g.out_ws + sc * tx; };
+    auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.lout.hs + sc * ty) * g.lout.ws + sc * tx; };
     int q0;
     {
       const int t = min(mt * NT, A.T - 1);
@@ -604,9 +595,9 @@ __global__ __launch_bounds__(256, 1) void wino3s_f32(const ArgsT<PR> A) {
       const int ty = r / A.TX;
       q0 = wt_q(n, ty, r - ty * A.TX);
     }
-    const size_t oo0 = ((size_t)g.out_lead + (size_t)q0) * g.out_cstride + g.out_choff;
+    const size_t oo0 = ((size_t)g.lout.lead + (size_t)q0) * g.lout.cstride + g.lout.choff;
     const i32x4 rout = make_rsrc(g.out + oo0, g.out_bytes - oo0 * 4);
-    const unsigned cs4 = (unsigned)g.out_cstride * 4, row4 = (unsigned)g.out_ws * cs4;
+    const unsigned cs4 = (unsigned)g.lout.cstride * 4, row4 = (unsigned)g.lout.ws * cs4;
     const unsigned col4 = (unsigned)ncol * 4;
     // wave wv stores accumulator registers 4 wv .. 4 wv + 3 = wtiles 8 wv + 4 kh + (0..3) of the tile
     int tcur = mt * NT + 8 * wv + 4 * kh;

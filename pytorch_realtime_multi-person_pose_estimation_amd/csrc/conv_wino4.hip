@@ -71,15 +71,13 @@ using namespace winoc;
 
 constexpr int W4_L0 = 6;  // first pair step of a chunk's patch loads (of 9 steps; two loads per step)
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct Group {
   const float* in;
   const float* w;
   const float* bias;
   float* out;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;
   int cout, cout_pad;
   int in_pq, out_pq;  // > 0: the slice is stored as planes of 8 channels, this many pixel slots per plane (0: pixel-major)
   size_t in_bytes, w_bytes, out_bytes;
@@ -234,23 +232,23 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
   i32x4 rin;
   unsigned pv[4];  // byte offsets of pixel 0 and of the pixels 3, 4, 5 (clamped to the gap column) of the row
   int lt = j0, lc = 3;
-  const int cs_ld = px_floats(g.in_cstride, g.in_pq);
+  const int cs_ld = px_floats(g.lin.cstride, g.in_pq);
   const unsigned pxb = (unsigned)cs_ld * 4;                                 // bytes per pixel step
   const unsigned ckb = g.in_pq ? (unsigned)g.in_pq * (CK * 4) : CK * 4;     // bytes per chunk step
-  const size_t in_ch0 = ch0_floats(g.in_choff, g.in_pq);
+  const size_t in_ch0 = ch0_floats(g.lin.choff, g.in_pq);
   auto set_loader = [&](int mt, i32x4& r_, unsigned (&v_)[4]) {
     size_t q0;
     {
       const int t = min((A.mt0 + mt) * NT, A.T - 1);
       const int n = t / TT, r = t - n * TT;
       const int ty = r / A.TX, tx = r - ty * A.TX;
-      q0 = (size_t)g.in_lead + (size_t)(n * g.in_hs + 4 * ty - 1) * g.in_ws + (4 * tx - 1);
+      q0 = (size_t)g.lin.lead + (size_t)(n * g.lin.hs + 4 * ty - 1) * g.lin.ws + (4 * tx - 1);
     }
     const int t = min((A.mt0 + mt) * NT + wl1, A.T - 1);
     const int n = t / TT, r = t - n * TT;
     const int ty = r / A.TX, tx = r - ty * A.TX;
     const int yy = min(4 * ty - 1 + py, A.H);  // rows past the image: the zero gap row
-    const size_t qq = (size_t)g.in_lead + (size_t)(n * g.in_hs + yy) * g.in_ws + (4 * tx - 1);
+    const size_t qq = (size_t)g.lin.lead + (size_t)(n * g.lin.hs + yy) * g.lin.ws + (4 * tx - 1);
     const size_t o0 = q0 * cs_ld + in_ch0;
     r_ = make_rsrc(g.in + o0, g.in_bytes - o0 * 4);
     v_[0] = (unsigned)(((qq - q0) * cs_ld + cg1 * 4) * 4);
@@ -317,7 +315,7 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
   for (int i = 0; i < 6; ++i) load_piece(rin, pv, 1, i);
 #pragma unroll
   for (int f = 0; f < PF; ++f) {
-    bs[f] = bload_f4(rw, boff, wso);
+    bs[f] = bload4(rw, boff, wso);
     wso += fstep;
   }
   __syncthreads();
@@ -328,9 +326,6 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
   for (int i = 0; i < 6; ++i) load_piece(rin, pv, 2, i);
   __syncthreads();
 
-#define RTPOSE_PIN()             \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
   for (int mt = j0; mt < A.mtiles; mt += jstep) {
 #pragma unroll
     for (int f = 0; f < NFW; ++f)
@@ -368,7 +363,7 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
             // B PF pairs ahead.  After a chunk's ninth pair the sibling's nine are skipped; after the tile's last chunk
             // the ring wraps to the next tile.
             const int L = h * NPW + i + PF;
-            bs[L % NB] = bload_f4(rw, boff, wso);
+            bs[L % NB] = bload4(rw, boff, wso);
             if (L % NPW == NPW - 1) wso = (c2 + L / NPW == nchunks - 1) ? wbase : wso + (NPW + 1) * fstep;
             else wso += fstep;
           }
@@ -486,7 +481,7 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
       auto S = [&](int x, int vp, int i) -> f2 { return (x / 3 == FH) ? sk[x % 3][vp][i] : sr[x % 3][vp][i]; };
       const bool col_ok = ncol < g.cout;
       const int sc = A.pool ? 2 : 4;
-      auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.out_hs + sc * ty) * g.out_ws + sc * tx; };
+      auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.lout.hs + sc * ty) * g.lout.ws + sc * tx; };
       int q0;
       {
         const int t = min((A.mt0 + mt) * NT, A.T - 1);
@@ -494,10 +489,10 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
         const int ty = r / A.TX;
         q0 = wt_q(n, ty, r - ty * A.TX);
       }
-      const int cs_st = px_floats(g.out_cstride, g.out_pq);
-      const size_t oo0 = ((size_t)g.out_lead + (size_t)q0) * cs_st + ch0_floats(g.out_choff, g.out_pq);
+      const int cs_st = px_floats(g.lout.cstride, g.out_pq);
+      const size_t oo0 = ((size_t)g.lout.lead + (size_t)q0) * cs_st + ch0_floats(g.lout.choff, g.out_pq);
       const i32x4 rout = make_rsrc(g.out + oo0, g.out_bytes - oo0 * 4);
-      const unsigned cs4 = (unsigned)cs_st * 4, row4 = (unsigned)g.out_ws * cs4;
+      const unsigned cs4 = (unsigned)cs_st * 4, row4 = (unsigned)g.lout.ws * cs4;
       const unsigned col4 = col_floats(ncol, g.out_pq) * 4;
       int tcur = (A.mt0 + mt) * NT + (RT == 2 ? FH * 16 + 4 * kq : 4 * kq + 2 * FH);
       int sn = tcur / TT, sy, sx;
@@ -574,7 +569,6 @@ __global__ __launch_bounds__(512, 1) void wino4_f32(const ArgsT<PR> A) {
     if (fh == 0) finish(std::integral_constant<int, 0>{});
     else finish(std::integral_constant<int, 1>{});
   }  // m tiles of this block
-#undef RTPOSE_PIN
 }
 
 // Small grids (few images): the same arithmetic on 8x as many blocks.  A block = 6 waves = 16 wtiles x 16 columns;
@@ -614,7 +608,7 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const ArgsT<PR> A) {
   const i32x4 rw = make_rsrc(g.w, g.w_bytes);
   i32x4 rin;
   unsigned pv0, pvx;  // byte offset of pixel 0 of the row; pixels of the row before the gap column (W + 1 - 4 tx)
-  const int cs_ld = px_floats(g.in_cstride, g.in_pq);
+  const int cs_ld = px_floats(g.lin.cstride, g.in_pq);
   const unsigned pxb = (unsigned)cs_ld * 4;
   const unsigned ckb = g.in_pq ? (unsigned)g.in_pq * (CK * 4) : CK * 4;
   {
@@ -623,14 +617,14 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const ArgsT<PR> A) {
       const int t = min(mt * NTS, A.T - 1);
       const int n = t / TT, r = t - n * TT;
       const int ty = r / A.TX, tx = r - ty * A.TX;
-      q0 = (size_t)g.in_lead + (size_t)(n * g.in_hs + 4 * ty - 1) * g.in_ws + (4 * tx - 1);
+      q0 = (size_t)g.lin.lead + (size_t)(n * g.lin.hs + 4 * ty - 1) * g.lin.ws + (4 * tx - 1);
     }
     const int t = min(mt * NTS + wl1, A.T - 1);
     const int n = t / TT, r = t - n * TT;
     const int ty = r / A.TX, tx = r - ty * A.TX;
     const int yy = min(4 * ty - 1 + py, A.H);  // rows past the image: the zero gap row
-    const size_t qq = (size_t)g.in_lead + (size_t)(n * g.in_hs + yy) * g.in_ws + (4 * tx - 1);
-    const size_t o0 = q0 * cs_ld + ch0_floats(g.in_choff, g.in_pq);
+    const size_t qq = (size_t)g.lin.lead + (size_t)(n * g.lin.hs + yy) * g.lin.ws + (4 * tx - 1);
+    const size_t o0 = q0 * cs_ld + ch0_floats(g.lin.choff, g.in_pq);
     rin = make_rsrc(g.in + o0, s1 ? g.in_bytes - o0 * 4 : 0);
     pv0 = (unsigned)(((qq - q0) * cs_ld + cg1 * 4) * 4);
     pvx = (unsigned)(A.W + 1 - 4 * tx);
@@ -692,7 +686,7 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const ArgsT<PR> A) {
   for (int i = 0; i < 6; ++i) load_piece(1, i);
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    bs[i] = bload_f4(rw, boff, wso);
+    bs[i] = bload4(rw, boff, wso);
     wso += fstep;
   }
   wso += (NFP - 3) * fstep;
@@ -714,7 +708,7 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const ArgsT<PR> A) {
       // the filter pairs of the next chunk (past the last one: clamped by the descriptor, unused)
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        bs[((h ^ 1) * 3) + i] = bload_f4(rw, boff, wso);
+        bs[((h ^ 1) * 3) + i] = bload4(rw, boff, wso);
         wso += fstep;
       }
       wso += (NFP - 3) * fstep;
@@ -768,7 +762,7 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const ArgsT<PR> A) {
       float slope0 = 0.f;
       if constexpr (PR) slope0 = slope_of<PR>(A, grp, ncol, g.cout);
       const int sc = A.pool ? 2 : 4;
-      auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.out_hs + sc * ty) * g.out_ws + sc * tx; };
+      auto wt_q = [&](int n, int ty, int tx) -> int { return (n * g.lout.hs + sc * ty) * g.lout.ws + sc * tx; };
       int q0;
       {
         const int t = min(mt * NTS, A.T - 1);
@@ -776,10 +770,10 @@ __global__ __launch_bounds__(384, 2) void wino4s_f32(const ArgsT<PR> A) {
         const int ty = r / A.TX;
         q0 = wt_q(n, ty, r - ty * A.TX);
       }
-      const int cs_st = px_floats(g.out_cstride, g.out_pq);
-      const size_t oo0 = ((size_t)g.out_lead + (size_t)q0) * cs_st + ch0_floats(g.out_choff, g.out_pq);
+      const int cs_st = px_floats(g.lout.cstride, g.out_pq);
+      const size_t oo0 = ((size_t)g.lout.lead + (size_t)q0) * cs_st + ch0_floats(g.lout.choff, g.out_pq);
       const i32x4 rout = make_rsrc(g.out + oo0, g.out_bytes - oo0 * 4);
-      const unsigned cs4 = (unsigned)cs_st * 4, row4 = (unsigned)g.out_ws * cs4;
+      const unsigned cs4 = (unsigned)cs_st * 4, row4 = (unsigned)g.lout.ws * cs4;
       const unsigned col4 = col_floats(ncol, g.out_pq) * 4;
       unsigned off[2];
       bool okv[2];
@@ -1018,8 +1012,8 @@ int conv2d_wino4_launch(const rtpose_conv_desc* d, int ngroups, int N, int H, in
       return fail(RTPOSE_E_INVAL, "%s: channel-plane slices start at a multiple of 8 channels (the output "
                                   "has a multiple of 8 of them) and a plane holds at least the layout's pixels", spec.who);
     // per-lane offsets are 32 bits and the descriptors clamp at 2 GiB: a plane slice spans (channels / 8) planes
-    if ((di.in_plane_pixels && (size_t)(di.lin.choff + di.cin) / 8 * di.in_plane_pixels * 32 > (size_t)winoc::kMaxRange) ||
-        (di.out_plane_pixels && (size_t)(di.lout.choff + cout_pad(di.cout)) / 8 * di.out_plane_pixels * 32 > (size_t)winoc::kMaxRange))
+    if ((di.in_plane_pixels && (size_t)(di.lin.choff + di.cin) / 8 * di.in_plane_pixels * 32 > (size_t)kMaxRange) ||
+        (di.out_plane_pixels && (size_t)(di.lout.choff + cout_pad(di.cout)) / 8 * di.out_plane_pixels * 32 > (size_t)kMaxRange))
       return fail(RTPOSE_E_INVAL, "%s: channel-plane slice beyond 2 GiB", spec.who);
     Group& g = a.g[i];
     fill_group(g, di);

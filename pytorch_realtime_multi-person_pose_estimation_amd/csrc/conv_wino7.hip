@@ -131,8 +131,7 @@ struct Group {
   const float* w;
   const float* bias;
   float* out;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lin, lout;
   int cout, cout_pad;
   size_t in_bytes, w_bytes;  // extents of the allocations from in / w (hardware bounds clamp of the buffer loads)
 };
@@ -190,8 +189,8 @@ struct Xform {
   __device__ __forceinline__ void setup(const Group& g, int W, int GX, int RS, int R0, int nrows) {
     const int tid = threadIdx.x;
     const int nitems = nrows * GX * CG;
-    const long qbase = (long)g.in_lead + (long)(R0 - 3) * g.in_ws - 3;
-    const size_t o0 = (size_t)qbase * g.in_cstride + g.in_choff;
+    const long qbase = (long)g.lin.lead + (long)(R0 - 3) * g.lin.ws - 3;
+    const size_t o0 = (size_t)qbase * g.lin.cstride + g.lin.choff;
     rin = make_rsrc(g.in + o0, g.in_bytes - o0 * 4);
 #pragma unroll
     for (int k = 0; k < NI; ++k) {
@@ -201,12 +200,12 @@ struct Xform {
       // channel-group-major inside a row: the 8 contiguous lanes a ds_write_b128 is serviced in then write 8
       // consecutive 16-byte slots (gx, cg interleaved they hit 4 slots twice: 12.5 % of SQ_LDS_IDX_ACTIVE in round 2)
       const int cg = rem / GX, gx = rem - cg * GX;
-      voff[k] = (unsigned)((((long)r * g.in_ws + FM * gx) * g.in_cstride + cg * 4) * 4);
+      voff[k] = (unsigned)((((long)r * g.lin.ws + FM * gx) * g.lin.cstride + cg * 4) * 4);
       vdst[k] = r * RS + cg * GX + gx;
 #pragma unroll
-      for (int n = 7; n < NFQ; ++n) vhi[k][n - 7] = voff[k] + (unsigned)(min(n, W + 5 - FM * gx) * g.in_cstride * 4);
+      for (int n = 7; n < NFQ; ++n) vhi[k][n - 7] = voff[k] + (unsigned)(min(n, W + 5 - FM * gx) * g.lin.cstride * 4);
     }
-    pxb = (unsigned)g.in_cstride * 4;  // bytes per pixel (uniform)
+    pxb = (unsigned)g.lin.cstride * 4;  // bytes per pixel (uniform)
     fstride = CG * GX;
   }
   __device__ __forceinline__ void load_piece(int chunk, int k, int n) {
@@ -301,8 +300,8 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
     const int n0 = t0 / PI, y0 = (t0 - n0 * PI) / GX;
     const int t1 = min(t0 + 31, tlim - 1);
     const int n1 = t1 / PI, y1 = (t1 - n1 * PI) / GX;
-    R0 = n0 * g.in_hs + y0;
-    nrows = n1 * g.in_hs + y1 - R0 + 7;
+    R0 = n0 * g.lin.hs + y0;
+    nrows = n1 * g.lin.hs + y1 - R0 + 7;
   }
   // ---- input transform role: NI items (row, gx, channel group), see Xform ----------------------------
   Xform<NI, FM> X;
@@ -320,7 +319,7 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
     const int t = min(t0 + l31, tlim - 1);  // positions past the end repeat the last one (not stored)
     const int n = t / PI, r = t - n * PI;
     const int y = r / GX, gx = r - y * GX;
-    abase = (n * g.in_hs + y - R0) * RS + kh * GX + gx + (fh * NFW) * CG * GX;  // this wave's first frequency
+    abase = (n * g.lin.hs + y - R0) * RS + kh * GX + gx + (fh * NFW) * CG * GX;  // this wave's first frequency
   }
   const int ncol = nt * 128 + wn * 32 + l31;
   floatx16 acc[NFW];
@@ -429,16 +428,13 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
   //  segment loads here it made every transform group wait for the B loads in flight - 5 % of the kernel)
 #pragma unroll
   for (int s = 0; s < PF; ++s) {
-    bs[s][0] = bload_f4(rw, boff, wso);
+    bs[s][0] = bload4(rw, boff, wso);
     bnext(bl);
-    bs[s][1] = bload_f4(rw, boff, wso);
+    bs[s][1] = bload4(rw, boff, wso);
     bnext(bl);
   }
   __syncthreads();
 
-#define RTPOSE_PIN()             \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
   // One step = the frequency pair (2 fp, 2 fp + 1) of one ky = 8 MFMAs on two alternating accumulators, with a
   // filler slot after every second one.  Slot 0 / 1: the A fragments of the next step (LDS); slot 2 / 3: the B
   // fragments PF steps ahead (L2).  Slot 3 of the first steps also carries transform work of the NEXT chunk: its
@@ -474,7 +470,7 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
             a[(ps + 1) & 1][j] = va[kyn * RS + fn * CG * GX];
           }
         } else {      // B PF steps ahead
-          bs[(ps + PF) % NSETS][j - 2] = bload_f4(rw, boff, wso);
+          bs[(ps + PF) % NSETS][j - 2] = bload4(rw, boff, wso);
           bnext(bl);
         }
         if (j == 3 && xf) {
@@ -493,7 +489,6 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
     }
     __syncthreads();
   }
-#undef RTPOSE_PIN
 
   // ---- first part of a split tile: hand the sums over ------------------------------------------------
   if (ce < nch) {
@@ -510,7 +505,7 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
   // ---- epilogue: output transform AT (points 0, +-1, +-2, +-1/2, +-3/2, inf), (+ReLU), masked stores ----
   // accumulator register r of a lane = position (r / 4) * 8 + 4 kh + r % 4 of the block, column l31
   const bool col_ok = ncol < g.cout;
-  float* out_base = g.out + g.out_choff + ncol;
+  float* out_base = g.out + g.lout.choff + ncol;
   // FS = 2: wave (wn, fh) finishes the accumulator registers [8 fh, 8 fh + 8) = positions 16 fh .. 16 fh + 15 of the
   // tile and gets the sibling's NFW frequencies of those registers through LDS (the V buffers are free now):
   // E[wn][writer's fh][f][r % 8][lane]
@@ -572,11 +567,11 @@ __device__ __forceinline__ void wino7_segment(const Args& A, float4* V4, const i
       y[i] = v;
     }
     if (col_ok && tcur < tlim) {
-      const size_t q = (size_t)g.out_lead + (size_t)(sn * g.out_hs + sy) * g.out_ws + FM * sx;
+      const size_t q = (size_t)g.lout.lead + (size_t)(sn * g.lout.hs + sy) * g.lout.ws + FM * sx;
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
         const float v = A.relu ? fmaxf(y[i], 0.f) : y[i];
-        if (FM * sx + i < A.W) out_base[(q + i) * g.out_cstride] = v;
+        if (FM * sx + i < A.W) out_base[(q + i) * g.lout.cstride] = v;
       }
     }
     const int dstep = (r & 3) == 3 ? 5 : 1;  // next register: +1, +1, +1, +5 positions
@@ -685,8 +680,8 @@ __global__ __launch_bounds__(256, 1) void wino7s_f32(const Args A) {
     const int n0 = t0 / PI, y0 = (t0 - n0 * PI) / GX;
     const int t1 = min(t0 + 31, tlim - 1);
     const int n1 = t1 / PI, y1 = (t1 - n1 * PI) / GX;
-    R0 = n0 * g.in_hs + y0;
-    nrows = n1 * g.in_hs + y1 - R0 + 7;
+    R0 = n0 * g.lin.hs + y0;
+    nrows = n1 * g.lin.hs + y1 - R0 + 7;
   }
   Xform<NI, FM> X;
   X.setup(g, A.W, GX, RS, R0, nrows);
@@ -697,7 +692,7 @@ __global__ __launch_bounds__(256, 1) void wino7s_f32(const Args A) {
     const int t = min(t0 + l31, tlim - 1);
     const int n = t / PI, r = t - n * PI;
     const int y = r / GX, gx = r - y * GX;
-    abase = (n * g.in_hs + y - R0) * RS + kh * GX + gx + (wv * FW) * CG * GX;  // this wave's first frequency
+    abase = (n * g.lin.hs + y - R0) * RS + kh * GX + gx + (wv * FW) * CG * GX;  // this wave's first frequency
   }
   const int ncol = nt * 32 + l31;
   floatx16 acc[FW];
@@ -738,14 +733,11 @@ __global__ __launch_bounds__(256, 1) void wino7s_f32(const Args A) {
 #pragma unroll
   for (int s = 0; s < PF; ++s) {
 #pragma unroll
-    for (int f = 0; f < FW; ++f) bs[s][f] = bload_f4(rw, boff, wso + f * fstep);
+    for (int f = 0; f < FW; ++f) bs[s][f] = bload4(rw, boff, wso + f * fstep);
     wso = min(wso + kstep, wso_max);
   }
   __syncthreads();
 
-#define RTPOSE_PIN()             \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
   // One step = one ky: the wave's FW frequencies x 4 MFMAs on FW alternating accumulators, a filler slot after each
   // round of FW: A fragments of the next step, B fragments PF steps ahead, transform groups / segment loads.
   constexpr int NG = (NP + 2) * NI;
@@ -775,7 +767,7 @@ __global__ __launch_bounds__(256, 1) void wino7s_f32(const Args A) {
           }
         } else if (j == 1) {
 #pragma unroll
-          for (int f = 0; f < FW; ++f) bs[(ky + PF) % NSETS][f] = bload_f4(rw, boff, wso + f * fstep);
+          for (int f = 0; f < FW; ++f) bs[(ky + PF) % NSETS][f] = bload4(rw, boff, wso + f * fstep);
           wso = min(wso + kstep, wso_max);
         } else {  // j = 2, 3: steps 0..3 the transform groups of the next chunk (they read the segment registers),
                   // steps 4..6 - only then - the segment loads of the chunk after that (they overwrite them)
@@ -799,7 +791,6 @@ __global__ __launch_bounds__(256, 1) void wino7s_f32(const Args A) {
     }
     __syncthreads();
   }
-#undef RTPOSE_PIN
 
   // ---- exchange: every wave needs all 12 frequencies of the accumulator registers it stores --------------
   // LDS (the V buffers are free now): E[f][r][lane]; wave w stores registers r = 4 w .. 4 w + 3, i.e. positions
@@ -811,7 +802,7 @@ __global__ __launch_bounds__(256, 1) void wino7s_f32(const Args A) {
     for (int r = 0; r < 16; ++r) E[((wv * FW + f) * 16 + r) * 64 + lane] = acc[f][r];
   __syncthreads();
   const bool col_ok = ncol < g.cout;
-  float* out_base = g.out + g.out_choff + ncol;
+  float* out_base = g.out + g.lout.choff + ncol;
   int tcur = t0 + 8 * wv + 4 * kh;
   int sn = tcur / PI, sy, sx;
   {
@@ -847,11 +838,11 @@ __global__ __launch_bounds__(256, 1) void wino7s_f32(const Args A) {
       y[i] = v;
     }
     if (col_ok && tcur < tlim) {
-      const size_t q = (size_t)g.out_lead + (size_t)(sn * g.out_hs + sy) * g.out_ws + FM * sx;
+      const size_t q = (size_t)g.lout.lead + (size_t)(sn * g.lout.hs + sy) * g.lout.ws + FM * sx;
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
         const float v = A.relu ? fmaxf(y[i], 0.f) : y[i];
-        if (FM * sx + i < A.W) out_base[(q + i) * g.out_cstride] = v;
+        if (FM * sx + i < A.W) out_base[(q + i) * g.lout.cstride] = v;
       }
     }
     ++tcur;

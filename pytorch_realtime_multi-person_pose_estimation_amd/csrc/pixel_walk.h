@@ -1,10 +1,11 @@
 // What the data-movement kernels (layout_ops.hip, shufflenet_ops.hip, image_ops.hip) share: the decode of the flat thread
-// index into a pixel and a channel group, the 16-byte channel vector of either element type, the bf16 bit helpers, and on
+// index into a pixel and a channel group, the 16-byte channel vector of either element type (bf16 bits by mfma_dev.h), and on
 // the host the one-dimensional launch and the alignment test of a layout slice.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
@@ -24,15 +25,6 @@ static int launch_flat(K kernel, size_t total, void* stream, A... args) {
 inline bool slice_aligned(const rtpose_layout* l, int k) { return !(l->cstride % k) && !(l->choff % k); }
 
 #ifdef __HIPCC__
-// ---- bf16 bits: round to nearest even (Inf stays Inf, a NaN stays a NaN of its sign), and back ----
-__device__ __forceinline__ unsigned short f32_to_bf16_rne(float v) {
-  return __builtin_bit_cast(unsigned short, (__bf16)v);
-}
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-
-// two bf16 as one 32-bit word, `a` in the low half
-__device__ __forceinline__ unsigned bf16_pair(unsigned short a, unsigned short b) { return a | ((unsigned)b << 16); }
-
 // ---- 16 bytes of consecutive channels of element type T: 4 float, or 8 bf16 (unsigned short bits); lanes held as float ----
 template <class T>
 struct ChanVec {

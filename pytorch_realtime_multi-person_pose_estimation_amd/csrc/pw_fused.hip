@@ -29,34 +29,22 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
-typedef float pw_f2 __attribute__((ext_vector_type(2)));
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef const floatx4 __attribute__((address_space(1)))* gcf4_t;
-__device__ __forceinline__ float4 pw_gload4(const void* p) {  // explicit global address space (no FLAT loads)
-  const floatx4 v = *(gcf4_t)(unsigned long long)(p);
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
-
-struct PwView {  // one activation tensor (shared-gap padded NHWC slice)
-  const float* base;
-  int cstride, choff, ws, hs, lead;
-};
-
 struct PwArgs {
-  PwView in;          // A source: the GEMM input (DW = 0) or the depthwise conv's input (DW = 1, gap >= 1)
+  const float* in;    // A source: the GEMM input (DW = 0) or the depthwise conv's input (DW = 1, gap >= 1),
+  Lay lin;            // a shared-gap padded NHWC slice like every tensor here
   const float* dw_w;  // DW: [9][K] taps (ky*3+kx major) and
   const float* dw_b;  //     [K] bias of the depthwise conv (BN folded)
   const float* w;     // packed pointwise weights [K/4][coutp][4]
   const float* bias;  // [coutp]
   float* out;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lout;
   const int32_t* out_cmap;  // optional [coutp]: column n -> absolute channel (< 0: not stored)
-  PwView pt;                // PT: source of the pass-through channels (same N, H, W)
+  const float* pt;          // PT: source of the pass-through channels (same N, H, W)
+  Lay lpt;
   const int32_t* pt_cmap;   // PT: [pt_c] source channel i -> absolute output channel
   int pt_c;
   // PT, interleave form (pt_pairs > 0, pt_cmap unused): output channel j < 2 pt_pairs takes source channel
@@ -79,23 +67,6 @@ constexpr int kPwMaxStage = 4;  // DW: staged 16-byte pieces per thread per chun
 constexpr int kPwTile = 8;      // DW: the block's 64 pixels are an 8 x 8 tile (halo 100 pixels = 1.56x; a 64-pixel strip of
                                 // a 46-wide map needed 209 = 3.3x)
 constexpr int kPwHalo = kPwTile + 2;
-
-#define RTPOSE_PW_PIN()          \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
-
-struct PwPix {  // pixel m of the batch as (image, row, column)
-  int n, y, x;
-};
-__device__ __forceinline__ PwPix pw_pix(int m, int HW, int W, const FastDiv fHW, const FastDiv fW) {
-  PwPix p;
-  p.n = fast_div(m, fHW);
-  const int r = m - p.n * HW;
-  p.y = fast_div(r, fW);
-  p.x = r - p.y * W;
-  return p;
-}
-__device__ __forceinline__ int pw_q(const PwPix& p, int lead, int hs, int ws) { return lead + (p.n * hs + p.y) * ws + p.x; }
 
 // WM x WN waves (WM * WN = 4), wave tile (32 MF) x (32 NFW), WM * MF = 2.
 // PERSISTENT: the grid is 2 blocks per CU; a block walks work items (64-pixel strip, BN-column pass)
@@ -140,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
   // Addresses are a uniform (scalar) base + a 32-bit per-lane element offset: the loads take the
   // SGPR-base form and no 64-bit address pairs are kept per piece (the host checks that every tensor
   // is below 2^31 floats).
-  const float* in_base = A.in.base + A.in.choff;
+  const float* in_base = A.in + A.lin.choff;
 
   // Per work item, per thread: where its staged pieces come from.
   //   DW = 0: piece u = (pixel px + 32 u, plane pl) of the strip, u < 2          -> q[u] = pixel index
@@ -163,12 +134,12 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
       const int ty = r - it.n * tiles_y;
       it.y0 = ty * kPwTile;
       it.x0 = tx * kPwTile;
-      it.q0 = A.in.lead + (it.n * A.in.hs + it.y0 - 1) * A.in.ws + it.x0 - 1;  // >= 0: lead = ws + 1
+      it.q0 = lay_pix(A.lin, it.n, it.y0 - 1, it.x0 - 1);  // >= 0: lead = ws + 1
       it.q1 = 0;
     } else {
       const int ma = min(it.m0 + px, A.M - 1), mb = min(it.m0 + px + 32, A.M - 1);  // rows past the end replay the last pixel
-      it.q0 = pw_q(pw_pix(ma, HW, A.W, A.fHW, A.fW), A.in.lead, A.in.hs, A.in.ws);
-      it.q1 = pw_q(pw_pix(mb, HW, A.W, A.fHW, A.fW), A.in.lead, A.in.hs, A.in.ws);
+      it.q0 = lay_pix(A.lin, pix_of(ma, HW, A.W, A.fHW, A.fW));
+      it.q1 = lay_pix(A.lin, pix_of(mb, HW, A.W, A.fHW, A.fW));
     }
     return it;
   };
@@ -177,14 +148,14 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
       const int y = it.y0 + (tid >> 3), x = it.x0 + (tid & 7);
       const bool ok = y < A.H && x < A.W;
       const int yc = min(y, A.H - 1), xc = min(x, A.W - 1);
-      s_qout[par][tid] = ok ? A.out_lead + (it.n * A.out_hs + yc) * A.out_ws + xc : -1;
-      s_qpt[par][tid] = A.pt.base ? A.pt.lead + (it.n * A.pt.hs + yc) * A.pt.ws + xc : 0;
+      s_qout[par][tid] = ok ? lay_pix(A.lout, it.n, yc, xc) : -1;
+      s_qpt[par][tid] = A.pt ? lay_pix(A.lpt, it.n, yc, xc) : 0;
     } else {
       const int m = it.m0 + tid;
       const int mc = min(m, A.M - 1);
-      const PwPix pp = pw_pix(mc, HW, A.W, A.fHW, A.fW);
-      s_qout[par][tid] = m < A.M ? pw_q(pp, A.out_lead, A.out_hs, A.out_ws) : -1;
-      s_qpt[par][tid] = A.pt.base ? pw_q(pp, A.pt.lead, A.pt.hs, A.pt.ws) : 0;
+      const Pix pp = pix_of(mc, HW, A.W, A.fHW, A.fW);
+      s_qout[par][tid] = m < A.M ? lay_pix(A.lout, pp) : -1;
+      s_qpt[par][tid] = A.pt ? lay_pix(A.lpt, pp) : 0;
     }
   };
   // DW: halo pixel (hy, hx) of the tile, hp = 10 hy + hx, sits hy * ws + hx pixels after the corner: the
@@ -194,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
 #pragma unroll
     for (int u = 0; u < kPwMaxStage; ++u) {
       const int hp = min(px + 32 * u, kPwHalo * kPwHalo - 1);
-      hoff[u] = (hp / kPwHalo) * A.in.ws + hp % kPwHalo;
+      hoff[u] = (hp / kPwHalo) * A.lin.ws + hp % kPwHalo;
     }
   }
   // the thread's two depthwise output pixels are tile rows px and px + 32: halo index of their tap (0, 0)
@@ -209,10 +180,10 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
     if (DW) {
 #pragma unroll
       for (int u = 0; u < kPwMaxStage; ++u)
-        sr[u] = pw_gload4(in_base + ((unsigned)(it.q0 + hoff[u]) * (unsigned)A.in.cstride + cofs));
+        sr[u] = gload4(in_base + ((unsigned)(it.q0 + hoff[u]) * (unsigned)A.lin.cstride + cofs));
     } else {
-      sr[0] = pw_gload4(in_base + ((unsigned)it.q0 * (unsigned)A.in.cstride + cofs));
-      sr[1] = pw_gload4(in_base + ((unsigned)it.q1 * (unsigned)A.in.cstride + cofs));
+      sr[0] = gload4(in_base + ((unsigned)it.q0 * (unsigned)A.lin.cstride + cofs));
+      sr[1] = gload4(in_base + ((unsigned)it.q1 * (unsigned)A.lin.cstride + cofs));
     }
   };
 
@@ -228,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
   if (DW) {  // (visible after the first chunk's barrier)
     const int k4 = A.K >> 2;
     for (int i = tid; i < 10 * k4; i += 256)
-      dwl[i] = i < 9 * k4 ? pw_gload4(A.dw_w + 4 * (size_t)i) : pw_gload4(A.dw_b + 4 * (size_t)(i - 9 * k4));
+      dwl[i] = i < 9 * k4 ? gload4(A.dw_w + 4 * (size_t)i) : gload4(A.dw_b + 4 * (size_t)(i - 9 * k4));
   }
   int par = 0;   // work-item parity (tables)
   int lbuf = 0;  // LDS chunk-buffer parity, runs on across work items
@@ -246,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
     for (int g = 0; g < 4; ++g)
 #pragma unroll
       for (int fn = 0; fn < NFW; ++fn) {
-        bw_cur[g][fn] = pw_gload4(w4 + (size_t)(2 * min(g, gtot - 1) * A.coutp) + (wl0 + fn * 32));
+        bw_cur[g][fn] = gload4(w4 + (size_t)(2 * min(g, gtot - 1) * A.coutp) + (wl0 + fn * 32));
         bw_nxt[g][fn] = bw_cur[g][fn];
       }
   }
@@ -263,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
     float4 bcur[NFW], bnxt[NFW];
 #pragma unroll
     for (int fn = 0; fn < NFW; ++fn) {
-      bcur[fn] = pw_gload4(w4 + (w_lane + fn * 32));
+      bcur[fn] = gload4(w4 + (w_lane + fn * 32));
       bnxt[fn] = bcur[fn];
     }
     floatx16 acc[MF][NFW];
@@ -290,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
         const int k4 = A.K >> 2;
         const float4* wl = dwl + min((c0 >> 2) + pl, k4 - 1);  // (groups past K: their A planes are not read)
         const float4 vb = wl[9 * k4];                          // bias
-        pw_f2 v0lo = {vb.x, vb.y}, v0hi = {vb.z, vb.w}, v1lo = v0lo, v1hi = v0hi;
+        floatx2 v0lo = {vb.x, vb.y}, v0hi = {vb.z, vb.w}, v1lo = v0lo, v1hi = v0hi;
         const float4* s0 = st + pl * nps + sp0;
         const float4* s1 = st + pl * nps + sp1;
 #pragma unroll
@@ -301,13 +272,13 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
             const float4 x0 = s0[ky * kPwHalo + kx], x1 = s1[ky * kPwHalo + kx];
             // packed fused multiply-adds (v_pk_fma_f32): fp32 VALU instructions take their cycles from the ALUs the
             // fp32 MFMAs run on - 4 instead of 16 per tap
-            const pw_f2 wlo = {ww.x, ww.y}, whi = {ww.z, ww.w};
-            v0lo = __builtin_elementwise_fma(pw_f2{x0.x, x0.y}, wlo, v0lo);
-            v0hi = __builtin_elementwise_fma(pw_f2{x0.z, x0.w}, whi, v0hi);
-            v1lo = __builtin_elementwise_fma(pw_f2{x1.x, x1.y}, wlo, v1lo);
-            v1hi = __builtin_elementwise_fma(pw_f2{x1.z, x1.w}, whi, v1hi);
+            const floatx2 wlo = {ww.x, ww.y}, whi = {ww.z, ww.w};
+            v0lo = __builtin_elementwise_fma(floatx2{x0.x, x0.y}, wlo, v0lo);
+            v0hi = __builtin_elementwise_fma(floatx2{x0.z, x0.w}, whi, v0hi);
+            v1lo = __builtin_elementwise_fma(floatx2{x1.x, x1.y}, wlo, v1lo);
+            v1hi = __builtin_elementwise_fma(floatx2{x1.z, x1.w}, whi, v1hi);
           }
-          RTPOSE_PW_PIN();  // one stencil row (9 LDS reads) at a time: all 27 at once cost 108 VGPRs
+          RTPOSE_PIN();  // one stencil row (9 LDS reads) at a time: all 27 at once cost 108 VGPRs
         }
         a_buf[pl * kPwQS + px] = make_float4(v0lo.x, v0lo.y, v0hi.x, v0hi.y);
         a_buf[pl * kPwQS + px + 32] = make_float4(v1lo.x, v1lo.y, v1hi.x, v1hi.y);
@@ -326,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
           for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int fn = 0; fn < NFW; ++fn)
-              bw_nxt[g][fn] = pw_gload4(w4 + (size_t)(2 * min(gnext + g, gtot - 1) * A.coutp) + (wl + fn * 32));
+              bw_nxt[g][fn] = gload4(w4 + (size_t)(2 * min(gnext + g, gtot - 1) * A.coutp) + (wl + fn * 32));
         }
         load_pieces(last ? nxt : cur, last ? 0 : c0 + 32);  // (no next item: nxt == cur, a harmless re-read)
         __syncthreads();  // A tile of chunk c visible (the other buffer was last read before the previous barrier)
@@ -344,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
       const float4* a_rd = a_buf + kh * kPwQS + wm * (32 * MF) + l31;
 #define RTPOSE_PW_BLOAD(DST, GG)                                                              \
   _Pragma("unroll") for (int fn = 0; fn < NFW; ++fn)                                          \
-      DST[fn] = pw_gload4(w4 + (size_t)(2 * (GG) * A.coutp) + (w_lane + fn * 32))
+      DST[fn] = gload4(w4 + (size_t)(2 * (GG) * A.coutp) + (w_lane + fn * 32))
 #define RTPOSE_PW_ALOAD(DST, GI) \
   _Pragma("unroll") for (int fm = 0; fm < MF; ++fm) DST[fm] = a_rd[2 * (GI) * kPwQS + fm * 32]
 #define RTPOSE_PW_MUL(AV, BV)                                                                           \
@@ -365,24 +336,24 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
       RTPOSE_PW_ALOAD(a0, 0);
       if (BAHEAD) {
         RTPOSE_PW_ALOAD(a1, 1);
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
         RTPOSE_PW_MUL(a0, bw_cur[0]);
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
         if (ng > 1) {
           RTPOSE_PW_ALOAD(a0, 2);
-          RTPOSE_PW_PIN();
+          RTPOSE_PIN();
           RTPOSE_PW_MUL(a1, bw_cur[1]);
-          RTPOSE_PW_PIN();
+          RTPOSE_PIN();
         }
         if (ng > 2) {
           RTPOSE_PW_ALOAD(a1, 3);
-          RTPOSE_PW_PIN();
+          RTPOSE_PIN();
           RTPOSE_PW_MUL(a0, bw_cur[2]);
-          RTPOSE_PW_PIN();
+          RTPOSE_PIN();
         }
         if (ng > 3) {
           RTPOSE_PW_MUL(a1, bw_cur[3]);
-          RTPOSE_PW_PIN();
+          RTPOSE_PIN();
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g)
@@ -391,28 +362,28 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
       } else {
       RTPOSE_PW_BLOAD(bnxt, min(gg + 1, gl));
       RTPOSE_PW_ALOAD(a1, 1);
-      RTPOSE_PW_PIN();
+      RTPOSE_PIN();
       RTPOSE_PW_MUL(a0, bcur);
-      RTPOSE_PW_PIN();
+      RTPOSE_PIN();
       if (ng > 1) {
         RTPOSE_PW_BLOAD(bcur, min(gg + 2, gl));
         RTPOSE_PW_ALOAD(a0, 2);
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
         RTPOSE_PW_MUL(a1, bnxt);
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
       }
       if (ng > 2) {
         RTPOSE_PW_BLOAD(bnxt, min(gg + 3, gl));
         RTPOSE_PW_ALOAD(a1, 3);
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
         RTPOSE_PW_MUL(a0, bcur);
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
       }
       if (ng > 3) {
         RTPOSE_PW_BLOAD(bcur, min(gg + 4, gl));  // first group of the next chunk
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
         RTPOSE_PW_MUL(a1, bnxt);
-        RTPOSE_PW_PIN();
+        RTPOSE_PIN();
       }
       }  // BAHEAD
 #undef RTPOSE_PW_MUL
@@ -427,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
     for (int fn = 0; fn < NFW; ++fn) {
       const int n = ncol + fn * 32;
       chn[fn] = -1;
-      if (n < A.cout) chn[fn] = A.out_cmap ? A.out_cmap[n] : A.out_choff + n;
+      if (n < A.cout) chn[fn] = A.out_cmap ? A.out_cmap[n] : A.lout.choff + n;
     }
 #pragma unroll
     for (int fm = 0; fm < MF; ++fm) {
@@ -442,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
         for (int r = 0; r < 16; ++r) {
           float v = acc[fm][fn][r];
           if (A.relu) v = fmaxf(v, 0.f);
-          if (qrow[r] >= 0 && chn[fn] >= 0) A.out[(unsigned)qrow[r] * (unsigned)A.out_cstride + (unsigned)chn[fn]] = v;
+          if (qrow[r] >= 0 && chn[fn] >= 0) A.out[(unsigned)qrow[r] * (unsigned)A.lout.cstride + (unsigned)chn[fn]] = v;
         }
       }
     }
@@ -450,7 +421,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
     // ---- pass-through half, interleave form: the next unit's x1 = this buffer's logical channels [0, h)
     //      = (even run, odd run) interleaved, written as contiguous runs: 16-byte loads, 8-byte stores,
     //      every line written once (the scatter form below wrote every line of the buffer twice) ------
-    if (A.pt.base && A.pt_pairs > 0 && cur.pass == 0) {
+    if (A.pt && A.pt_pairs > 0 && cur.pass == 0) {
       const int g4 = (A.pt_pairs + 3) >> 2;
       const int nit = kPwBM * g4;
       const bool vec2 = !(A.pt_split & 1) && !((A.pt_d1 - A.pt_split) & 1) && !(A.pt_d0 & 1);
@@ -463,15 +434,15 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
           const int p = it / g4;
           k0[u] = 4 * (it - p * g4);
           qo[u] = it0 + 256 * u < nit ? s_qout[par][p] : -1;
-          const unsigned so = (unsigned)s_qpt[par][p] * (unsigned)A.pt.cstride + (unsigned)(A.pt.choff + k0[u]);
-          va[u] = pw_gload4(A.pt.base + (so + (unsigned)A.pt_a));
-          vb[u] = pw_gload4(A.pt.base + (so + (unsigned)A.pt_b));
+          const unsigned so = (unsigned)s_qpt[par][p] * (unsigned)A.lpt.cstride + (unsigned)(A.lpt.choff + k0[u]);
+          va[u] = gload4(A.pt + (so + (unsigned)A.pt_a));
+          vb[u] = gload4(A.pt + (so + (unsigned)A.pt_b));
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           if (qo[u] < 0) continue;
           const float a4[4] = {va[u].x, va[u].y, va[u].z, va[u].w}, b4[4] = {vb[u].x, vb[u].y, vb[u].z, vb[u].w};
-          const unsigned o = (unsigned)qo[u] * (unsigned)A.out_cstride;
+          const unsigned o = (unsigned)qo[u] * (unsigned)A.lout.cstride;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int k = k0[u] + e;  // pair index: outputs j = 2k, 2k + 1
@@ -492,7 +463,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
     }
 
     // ---- pass-through half, scatter form: x1 -> pt_cmap slots (cat + channel_shuffle folded into the store) ------
-    if (A.pt.base && A.pt_pairs == 0 && cur.pass == 0) {
+    if (A.pt && A.pt_pairs == 0 && cur.pass == 0) {
       const int g4 = (A.pt_c + 3) >> 2;
       const int nit = kPwBM * g4;
       constexpr int PB = 4;  // loads in flight per thread (a load -> 4 stores chain per item exposed a full
@@ -506,13 +477,13 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
           const int p = min(it, nit - 1) / g4;
           gg[u] = min(it, nit - 1) - p * g4;
           qo[u] = it < nit ? s_qout[par][p] : -1;
-          v[u] = pw_gload4(A.pt.base + ((unsigned)s_qpt[par][p] * (unsigned)A.pt.cstride + (unsigned)(A.pt.choff + 4 * gg[u])));
+          v[u] = gload4(A.pt + ((unsigned)s_qpt[par][p] * (unsigned)A.lpt.cstride + (unsigned)(A.lpt.choff + 4 * gg[u])));
         }
 #pragma unroll
         for (int u = 0; u < PB; ++u) {
           if (qo[u] < 0) continue;
           const float vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-          const unsigned o = (unsigned)qo[u] * (unsigned)A.out_cstride;
+          const unsigned o = (unsigned)qo[u] * (unsigned)A.lout.cstride;
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (4 * gg[u] + e < A.pt_c) A.out[o + (unsigned)A.pt_cmap[4 * gg[u] + e]] = vv[e];
@@ -525,21 +496,6 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f32(const PwArgs A) {
     wi = wnext;
     par ^= 1;
   }
-}
-#undef RTPOSE_PW_PIN
-
-// packed[c/4][coutp][4] columns [col_off, col_off + cout)  <-  w[cout][cin_src] (1x1), bias likewise:
-// several layers may share one packed matrix (the PAF and heat-map heads are one 128-column GEMM)
-__global__ void pack_pw_kernel(const float* __restrict__ w, const float* __restrict__ bias, int cout,
-                               int cin_src, const int32_t* __restrict__ cin_map, int K, int coutp, int col_off,
-                               float* __restrict__ wp, float* __restrict__ bp) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < cout) bp[col_off + i] = bias ? bias[i] : 0.f;
-  if (i >= K * cout) return;
-  const int n = i % cout, c = i / cout;
-  const int src = cin_map ? cin_map[c] : (c < cin_src ? c : -1);
-  const float v = (src >= 0 && src < cin_src) ? w[(size_t)n * cin_src + src] : 0.f;
-  wp[((size_t)(c >> 2) * coutp + col_off + n) * 4 + (c & 3)] = v;
 }
 
 // packed[c / 4][coutp][4], columns [col_off, col_off + ncols): column col_off + i holds output channel col_map[i] of
@@ -561,7 +517,6 @@ __global__ void pack_pw_cols_kernel(const float* __restrict__ w, const float* __
   wp[((size_t)(c >> 2) * coutp + col_off + ci) * 4 + (c & 3)] = v;
 }
 
-
 int pack_pw_cols_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map, int K,
                         int ncols, const int32_t* col_map, int coutp, int col_off, float* wp, float* bp,
                         hipStream_t s) {
@@ -573,19 +528,19 @@ int pack_pw_cols_launch(const float* w, const float* bias, int cout, int cin_src
   return 0;
 }
 
+// columns [col_off, col_off + cout) <- w[cout][cin_src] in its own column order, bias likewise: several layers may share
+// one packed matrix (the PAF and heat-map heads are one 128-column GEMM)
 int pack_pw_launch(const float* w, const float* bias, int cout, int cin_src, const int32_t* cin_map, int K,
                    int coutp, int col_off, float* wp, float* bp, hipStream_t s) {
   if (!w || !wp || !bp || cout <= 0 || K <= 0 || (K % 8) || col_off < 0 || col_off + cout > coutp)
     return fail(RTPOSE_E_INVAL, "pack_pw: bad arguments");
-  hipLaunchKernelGGL(pack_pw_kernel, dim3(ceil_div(K * cout, 256)), dim3(256), 0, s, w, bias, cout, cin_src,
-                     cin_map, K, coutp, col_off, wp, bp);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+  return pack_pw_cols_launch(w, bias, cout, cin_src, cin_map, K, cout, nullptr, coutp, col_off, wp, bp, s);
 }
 
 // LDS plane stride of the staged halo of a 64-pixel strip: the strip, the row gaps it crosses, at most
 // one image gap, one row above and below (+1 pixel each side); rounded so that the 8 planes sit 8
-// banks apart like the A tile's
+// banks apart like the A tile's.  (For a strip-shaped depthwise block, of either element type; the 8 x 8 tiles of today's
+// launchers stage a fixed 32 * kPwMaxStage + 2.)
 int pw_halo_stride(const rtpose_layout& l, int H, int W) {
   int np = (kPwBM - 1) + ((kPwBM - 1) / W + 1) * (l.ws - W) + ((kPwBM - 1) / (H * W) + 1) * (l.hs - H) * l.ws +
            2 * l.ws + 3;
@@ -618,52 +573,16 @@ int pw_fused_launch(const rtpose_pw_desc* d, int N, int H, int W, hipStream_t s)
   if (!below_2g_elems(d->lin, N, H, W) || !below_2g_elems(d->lout, N, H, W))
     return fail(RTPOSE_E_INVAL, "pw_fused: tensors must be below 2^31 floats (32-bit element offsets)");
   PwArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = PwView{d->in, d->lin.cstride, d->lin.choff, d->lin.ws, d->lin.hs, d->lin.lead};
-  a.dw_w = d->dw_w;
-  a.dw_b = d->dw_b;
-  a.w = d->w_packed;
-  a.bias = d->bias_packed;
-  a.out = d->out;
-  a.out_cstride = d->lout.cstride;
-  a.out_choff = d->lout.choff;
-  a.out_ws = d->lout.ws;
-  a.out_hs = d->lout.hs;
-  a.out_lead = d->lout.lead;
-  a.out_cmap = d->out_cmap;
+  const int grid = fill_pw_args(a, d, N, H, W, kPwBM, kPwTile);
   if (d->pt_src) {
-    a.pt = PwView{d->pt_src, d->lpt.cstride, d->lpt.choff, d->lpt.ws, d->lpt.hs, d->lpt.lead};
     a.pt_cmap = d->pt_cmap;
     a.pt_c = d->pt_c;
-    a.pt_pairs = d->pt_pairs;
-    a.pt_a = d->pt_a;
-    a.pt_b = d->pt_b;
-    a.pt_split = d->pt_split;
-    a.pt_d0 = d->pt_d0;
-    a.pt_d1 = d->pt_d1;
   }
-  a.in_planes = d->in_planes;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.M = N * H * W;
-  a.K = d->cin;
-  a.coutp = d->coutp;
-  a.cout = d->cout;
-  a.relu = d->relu;
   size_t lds = (size_t)2 * kPwPL * kPwQS * 16;
   if (dw) {
     a.nps = 32 * kPwMaxStage + 2;  // every staged piece has a slot (unconditional parking); planes 8 banks apart
     lds += (size_t)kPwPL * a.nps * 16 + (size_t)10 * d->cin * 4;
   }
-  const int npass_h = d->coutp == 64 ? 1 : (d->coutp == 128 ? 1 : d->coutp / 256);
-  a.fHW = make_fastdiv(H * W);
-  a.fW = make_fastdiv(W);
-  a.fnp = make_fastdiv(npass_h);
-  a.ftx = make_fastdiv(ceil_div(W, kPwTile));
-  a.fty = make_fastdiv(ceil_div(H, kPwTile));
-  const int nwork = (dw ? N * ceil_div(H, kPwTile) * ceil_div(W, kPwTile) : ceil_div(a.M, kPwBM)) * npass_h;
-  const int grid = nwork < 2 * device_cu_count() ? nwork : 2 * device_cu_count();  // persistent: 2 blocks per CU
   if (d->coutp == 64) return dw ? pw_launch_inst<2, 1, 1, true>(a, grid, lds, s) : pw_launch_inst<2, 1, 1, false>(a, grid, lds, s);
   if (d->coutp == 128) return dw ? pw_launch_inst<1, 2, 1, true>(a, grid, lds, s) : pw_launch_inst<1, 2, 1, false>(a, grid, lds, s);
   return dw ? pw_launch_inst<1, 2, 2, true>(a, grid, lds, s) : pw_launch_inst<1, 2, 2, false>(a, grid, lds, s);

@@ -17,62 +17,26 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace pwb {
 
-typedef float pwb_f2 __attribute__((ext_vector_type(2)));
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef const floatx4 __attribute__((address_space(1)))* gcf4_t;
-typedef floatx4 __attribute__((address_space(1)))* gf4_t;
-__device__ __forceinline__ float4 gload4(const void* p) {  // explicit global address space (no FLAT loads)
-  const floatx4 v = *(gcf4_t)(unsigned long long)(p);
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ void gstore4(void* p, const float4& v) {
-  const floatx4 t = {v.x, v.y, v.z, v.w};
-  *(gf4_t)(unsigned long long)(p) = t;
-}
-__device__ __forceinline__ bf16x8 as_bf8(const float4& v) {
-  const floatx4 t = {v.x, v.y, v.z, v.w};
-  return __builtin_bit_cast(bf16x8, t);
-}
-__device__ __forceinline__ unsigned short to_bf16(float v) {
-  return __builtin_bit_cast(unsigned short, (__bf16)v);  // v_cvt_pk_bf16_f32: RNE
-}
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-  return (unsigned)to_bf16(lo) | ((unsigned)to_bf16(hi) << 16);
-}
-// 8 bf16 (one 16-byte piece) -> 8 floats
-__device__ __forceinline__ void unpack8(const float4& p, float* f) {
-  const unsigned u[4] = {__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), __float_as_uint(p.w)};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(u[i] << 16);
-    f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-  }
-}
-
-struct View {  // one activation tensor (shared-gap padded NHWC slice), channel counts in ELEMENTS
-  const unsigned short* base;
-  int cstride, choff, ws, hs, lead;
-};
-
 struct Args {
-  View in;            // A source: the GEMM input (DW = 0) or the depthwise conv's input (DW = 1, gap >= 1)
+  const unsigned short* in;  // A source: the GEMM input (DW = 0) or the depthwise conv's input (DW = 1, gap >= 1),
+  Lay lin;                   // a shared-gap padded NHWC slice, channel counts in ELEMENTS
   const float* dw_w;  // DW: fp32 [9][K] taps and
   const float* dw_b;  //     fp32 [K] bias of the depthwise conv (BN folded)
   const float4* w;    // packed bf16 pointwise weights [K/8][coutp][8]
   const float* bias;  // fp32 [coutp]
   void* out;          // bf16 (vec epilogue: columns [0, cout) -> channels out_choff ..) or fp32 (out_f32)
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lout;
   const int32_t* out_cmap;  // out_f32 only: column n -> absolute channel (< 0: not stored)
   int out_f32;
-  View pt;  // pass-through source (interleave form, see pw_fused.hip)
+  const unsigned short* pt;  // pass-through source (interleave form, see pw_fused.hip)
+  Lay lpt;
+  int pad_;  // (the tail padding of the view struct this was: the arguments behind it keep their offsets)
   int pt_pairs, pt_a, pt_b, pt_split, pt_d0, pt_d1;
   const int32_t* in_planes;  // optional [K/8]: element offset (inside the pixel) of every 8-channel plane of K
   int N, H, W, M;
@@ -88,23 +52,6 @@ constexpr int kMaxK = 1024;
 constexpr int kMaxStage = 4;   // DW: staged pieces per thread per chunk (10 x 10 halo of an 8 x 8 tile)
 constexpr int kTile = 8;       // DW: the block's 64 pixels are an 8 x 8 tile (see pw_fused.hip)
 constexpr int kHalo = kTile + 2;
-
-#define RTPOSE_PWB_PIN()         \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
-
-struct Pix {  // pixel m of the batch as (image, row, column)
-  int n, y, x;
-};
-__device__ __forceinline__ Pix pix_of(int m, int HW, int W, const FastDiv fHW, const FastDiv fW) {
-  Pix p;
-  p.n = fast_div(m, fHW);
-  const int r = m - p.n * HW;
-  p.y = fast_div(r, fW);
-  p.x = r - p.y * W;
-  return p;
-}
-__device__ __forceinline__ int pix_q(const Pix& p, int lead, int hs, int ws) { return lead + (p.n * hs + p.y) * ws + p.x; }
 
 template <int WM, int MF, int NFW, bool DW>
 __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
@@ -138,8 +85,8 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
   const int npass = A.coutp / BN;
   const int tiles_x = (A.W + kTile - 1) / kTile, tiles_y = (A.H + kTile - 1) / kTile;  // DW: 8 x 8 tiles of one image
   const int nwork = (DW ? A.N * tiles_y * tiles_x : (A.M + kBM - 1) / kBM) * npass;
-  const float4* in4 = reinterpret_cast<const float4*>(A.in.base);
-  const unsigned in_cs4 = (unsigned)A.in.cstride >> 3, in_co4 = (unsigned)A.in.choff >> 3;
+  const float4* in4 = reinterpret_cast<const float4*>(A.in);
+  const unsigned in_cs4 = (unsigned)A.lin.cstride >> 3, in_co4 = (unsigned)A.lin.choff >> 3;
 
   struct Item {
     int m0, pass;    // DW = 0: first pixel of the strip
@@ -158,12 +105,12 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
       const int ty = r - it.n * tiles_y;
       it.y0 = ty * kTile;
       it.x0 = tx * kTile;
-      it.q0 = A.in.lead + (it.n * A.in.hs + it.y0 - 1) * A.in.ws + it.x0 - 1;  // >= 0: lead = ws + 1
+      it.q0 = lay_pix(A.lin, it.n, it.y0 - 1, it.x0 - 1);  // >= 0: lead = ws + 1
       it.q1 = 0;
     } else {
       const int ma = min(it.m0 + px, A.M - 1), mb = min(it.m0 + px + 32, A.M - 1);  // rows past the end replay the last pixel
-      it.q0 = pix_q(pix_of(ma, HW, A.W, A.fHW, A.fW), A.in.lead, A.in.hs, A.in.ws);
-      it.q1 = pix_q(pix_of(mb, HW, A.W, A.fHW, A.fW), A.in.lead, A.in.hs, A.in.ws);
+      it.q0 = lay_pix(A.lin, pix_of(ma, HW, A.W, A.fHW, A.fW));
+      it.q1 = lay_pix(A.lin, pix_of(mb, HW, A.W, A.fHW, A.fW));
     }
     return it;
   };
@@ -172,14 +119,14 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
       const int y = it.y0 + (tid >> 3), x = it.x0 + (tid & 7);
       const bool ok = y < A.H && x < A.W;
       const int yc = min(y, A.H - 1), xc = min(x, A.W - 1);
-      s_qout[par][tid] = ok ? A.out_lead + (it.n * A.out_hs + yc) * A.out_ws + xc : -1;
-      s_qpt[par][tid] = A.pt.base ? A.pt.lead + (it.n * A.pt.hs + yc) * A.pt.ws + xc : 0;
+      s_qout[par][tid] = ok ? lay_pix(A.lout, it.n, yc, xc) : -1;
+      s_qpt[par][tid] = A.pt ? lay_pix(A.lpt, it.n, yc, xc) : 0;
     } else {
       const int m = it.m0 + tid;
       const int mc = min(m, A.M - 1);
       const Pix pp = pix_of(mc, HW, A.W, A.fHW, A.fW);
-      s_qout[par][tid] = m < A.M ? pix_q(pp, A.out_lead, A.out_hs, A.out_ws) : -1;
-      s_qpt[par][tid] = A.pt.base ? pix_q(pp, A.pt.lead, A.pt.hs, A.pt.ws) : 0;
+      s_qout[par][tid] = m < A.M ? lay_pix(A.lout, pp) : -1;
+      s_qpt[par][tid] = A.pt ? lay_pix(A.lpt, pp) : 0;
     }
   };
   // DW: halo pixel (hy, hx) of the tile, hp = 10 hy + hx, sits hy * ws + hx pixels after the corner: the
@@ -189,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
 #pragma unroll
     for (int u = 0; u < kMaxStage; ++u) {
       const int hp = min(px + 32 * u, kHalo * kHalo - 1);
-      hoff[u] = (hp / kHalo) * A.in.ws + hp % kHalo;
+      hoff[u] = (hp / kHalo) * A.lin.ws + hp % kHalo;
     }
   }
   // the thread's two depthwise output pixels are tile rows px and px + 32: halo index of their tap (0, 0)
@@ -262,11 +209,11 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
         //  more registers than the 256-column variant has)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-          pwb_f2 v[4];  // 8 channels as 4 packed pairs (v_pk_fma_f32: 4 instead of 16 VALU instructions per tap)
+          floatx2 v[4];  // 8 channels as 4 packed pairs (v_pk_fma_f32: 4 instead of 16 VALU instructions per tap)
           {
             const float4 b0 = *reinterpret_cast<const float4*>(dwl + 9 * A.K + ch);
             const float4 b1 = *reinterpret_cast<const float4*>(dwl + 9 * A.K + ch + 4);
-            v[0] = pwb_f2{b0.x, b0.y}, v[1] = pwb_f2{b0.z, b0.w}, v[2] = pwb_f2{b1.x, b1.y}, v[3] = pwb_f2{b1.z, b1.w};
+            v[0] = floatx2{b0.x, b0.y}, v[1] = floatx2{b0.z, b0.w}, v[2] = floatx2{b1.x, b1.y}, v[3] = floatx2{b1.z, b1.w};
           }
           const float4* s0 = st + pl * nps + (u ? sp1 : sp0);
 #pragma unroll
@@ -275,18 +222,18 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
             for (int kx = 0; kx < 3; ++kx) {
               const float4 w0 = *reinterpret_cast<const float4*>(dwl + (ky * 3 + kx) * A.K + ch);
               const float4 w1 = *reinterpret_cast<const float4*>(dwl + (ky * 3 + kx) * A.K + ch + 4);
-              const pwb_f2 ww[4] = {{w0.x, w0.y}, {w0.z, w0.w}, {w1.x, w1.y}, {w1.z, w1.w}};
+              const floatx2 ww[4] = {{w0.x, w0.y}, {w0.z, w0.w}, {w1.x, w1.y}, {w1.z, w1.w}};
               float x[8];
               unpack8(s0[ky * kHalo + kx], x);
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_fma(pwb_f2{x[2 * e], x[2 * e + 1]}, ww[e], v[e]);
+              for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_fma(floatx2{x[2 * e], x[2 * e + 1]}, ww[e], v[e]);
             }
-            RTPOSE_PWB_PIN();
+            RTPOSE_PIN();
           }
           a_buf[pl * kQS + px + 32 * u] =
-              make_float4(__uint_as_float(pack2(v[0].x, v[0].y)), __uint_as_float(pack2(v[1].x, v[1].y)),
-                          __uint_as_float(pack2(v[2].x, v[2].y)), __uint_as_float(pack2(v[3].x, v[3].y)));
-          RTPOSE_PWB_PIN();
+              make_float4(__uint_as_float(pack_bf16x2_bits(v[0].x, v[0].y)), __uint_as_float(pack_bf16x2_bits(v[1].x, v[1].y)),
+                          __uint_as_float(pack_bf16x2_bits(v[2].x, v[2].y)), __uint_as_float(pack_bf16x2_bits(v[3].x, v[3].y)));
+          RTPOSE_PIN();
         }
         // the next chunk's halo (of this item, or chunk 0 of the next) is requested only now: the depthwise
         // phase above is the register peak of the kernel, and the MFMAs below still cover the latency
@@ -320,28 +267,28 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
       RTPOSE_PWB_ALOAD(a0, 0);
       RTPOSE_PWB_BLOAD(bnxt, min(gg + 1, gl));
       RTPOSE_PWB_ALOAD(a1, 1);
-      RTPOSE_PWB_PIN();
+      RTPOSE_PIN();
       RTPOSE_PWB_MUL(a0, bcur);
-      RTPOSE_PWB_PIN();
+      RTPOSE_PIN();
       if (ng > 1) {
         RTPOSE_PWB_BLOAD(bcur, min(gg + 2, gl));
         RTPOSE_PWB_ALOAD(a0, 2);
-        RTPOSE_PWB_PIN();
+        RTPOSE_PIN();
         RTPOSE_PWB_MUL(a1, bnxt);
-        RTPOSE_PWB_PIN();
+        RTPOSE_PIN();
       }
       if (ng > 2) {
         RTPOSE_PWB_BLOAD(bnxt, min(gg + 3, gl));
         RTPOSE_PWB_ALOAD(a1, 3);
-        RTPOSE_PWB_PIN();
+        RTPOSE_PIN();
         RTPOSE_PWB_MUL(a0, bcur);
-        RTPOSE_PWB_PIN();
+        RTPOSE_PIN();
       }
       if (ng > 3) {
         RTPOSE_PWB_BLOAD(bcur, min(gg + 4, gl));  // first K-step of the next chunk
-        RTPOSE_PWB_PIN();
+        RTPOSE_PIN();
         RTPOSE_PWB_MUL(a1, bnxt);
-        RTPOSE_PWB_PIN();
+        RTPOSE_PIN();
       }
 #undef RTPOSE_PWB_MUL
 #undef RTPOSE_PWB_ALOAD
@@ -356,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
       for (int fn = 0; fn < NFW; ++fn) {
         const int n = ncol + fn * 32;
         int ch = -1;
-        if (n < A.cout) ch = A.out_cmap ? A.out_cmap[n] : A.out_choff + n;
+        if (n < A.cout) ch = A.out_cmap ? A.out_cmap[n] : A.lout.choff + n;
 #pragma unroll
         for (int fm = 0; fm < MF; ++fm)
 #pragma unroll
@@ -366,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
               const int qo = s_qout[par][wm * (32 * MF) + fm * 32 + rg * 8 + 4 * kh + rr];
               float v = acc[fm][fn][rg * 4 + rr];
               if (A.relu) v = fmaxf(v, 0.f);
-              if (qo >= 0 && ch >= 0) outf[(unsigned)qo * (unsigned)A.out_cstride + (unsigned)ch] = v;
+              if (qo >= 0 && ch >= 0) outf[(unsigned)qo * (unsigned)A.lout.cstride + (unsigned)ch] = v;
             }
       }
     } else {
@@ -384,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
             for (int rr = 0; rr < 4; ++rr) {
               float v = acc[fm][fn][rg * 4 + rr];
               if (A.relu) v = fmaxf(v, 0.f);
-              sl[(fm * 32 + rg * 8 + 4 * kh + rr) * PITCH2 + fn * 32 + l31] = to_bf16(v);
+              sl[(fm * 32 + rg * 8 + 4 * kh + rr) * PITCH2 + fn * 32 + l31] = f32_to_bf16_rne(v);
             }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // same-wave LDS traffic is in order
       constexpr int LPR = NFW * 4;    // 16-byte lanes per slab row
@@ -399,19 +346,19 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
         const int qo = s_qout[par][wm * (32 * MF) + row];
         // (out_cmap: the 8 columns from col0 go to the 8 channels from out_cmap[col0] - absolute, 8-aligned, the host
         //  keeps a group's channels contiguous; < 0: the group is not stored)
-        const int chb = A.out_cmap ? A.out_cmap[min(col0, A.cout - 8)] : A.out_choff + col0;
+        const int chb = A.out_cmap ? A.out_cmap[min(col0, A.cout - 8)] : A.lout.choff + col0;
         if (qo >= 0 && col0 < A.cout && chb >= 0)
-          gstore4(outh + ((unsigned)qo * (unsigned)A.out_cstride + (unsigned)chb), v);
+          gstore4(outh + ((unsigned)qo * (unsigned)A.lout.cstride + (unsigned)chb), v);
       }
     }
 
     // ---- pass-through half, interleave form (see pw_fused.hip): 16-byte loads of 8 channels from the two
     //      source runs, 4-byte stores of (even, odd) pairs ------------------------------------------------
-    if (A.pt.base && A.pt_pairs > 0 && cur.pass == 0) {
+    if (A.pt && A.pt_pairs > 0 && cur.pass == 0) {
       const int g8 = (A.pt_pairs + 7) >> 3;
       const int nit = kBM * g8;
-      const float4* pt4 = reinterpret_cast<const float4*>(A.pt.base);
-      const unsigned pt_cs4 = (unsigned)A.pt.cstride >> 3;
+      const float4* pt4 = reinterpret_cast<const float4*>(A.pt);
+      const unsigned pt_cs4 = (unsigned)A.lpt.cstride >> 3;
       unsigned short* outh = static_cast<unsigned short*>(A.out);
       const bool pair_ok = !(A.pt_split & 1) && !(A.pt_d0 & 1) && !((A.pt_d1 - A.pt_split) & 1);
       for (int it0 = tid; it0 < nit; it0 += 512) {
@@ -423,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
           const int p = it / g8;
           k0[u] = 8 * (it - p * g8);
           qo[u] = it0 + 256 * u < nit ? s_qout[par][p] : -1;
-          const unsigned so = (unsigned)s_qpt[par][p] * pt_cs4 + ((unsigned)(A.pt.choff + k0[u]) >> 3);
+          const unsigned so = (unsigned)s_qpt[par][p] * pt_cs4 + ((unsigned)(A.lpt.choff + k0[u]) >> 3);
           va[u] = gload4(pt4 + (so + ((unsigned)A.pt_a >> 3)));
           vb[u] = gload4(pt4 + (so + ((unsigned)A.pt_b >> 3)));
         }
@@ -434,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
                                   __float_as_uint(va[u].w)};
           const unsigned ub[4] = {__float_as_uint(vb[u].x), __float_as_uint(vb[u].y), __float_as_uint(vb[u].z),
                                   __float_as_uint(vb[u].w)};
-          const unsigned o = (unsigned)qo[u] * (unsigned)A.out_cstride;
+          const unsigned o = (unsigned)qo[u] * (unsigned)A.lout.cstride;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const int k = k0[u] + e;  // pair index: outputs j = 2k (from run a), 2k + 1 (from run b)
@@ -463,7 +410,6 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16(const Args A) {
     par ^= 1;
   }
 }
-#undef RTPOSE_PWB_PIN
 
 // packed[c/8][coutp][8 bf16], bias[coutp]  <-  w[cout][cin_src] (1x1, fp32), bias.  Packed input channel c reads
 // source channel cin_map[c] (NULL: c, < 0: zero); packed column n (col_off + i) is output channel col_map[i]
@@ -483,13 +429,7 @@ __global__ void pack_pw_bf16_kernel(const float* __restrict__ w, const float* __
   const int o = col_map ? col_map[n] : n;
   const int src = cin_map ? cin_map[c] : (c < cin_src ? c : -1);
   const float v = (o >= 0 && o < cout && src >= 0 && src < cin_src) ? w[(size_t)o * cin_src + src] : 0.f;
-  wp[((size_t)(c >> 3) * coutp + col_off + n) * 8 + (c & 7)] = to_bf16(v);
-}
-
-int halo_stride(const rtpose_layout& l, int H, int W) {
-  int np = (kBM - 1) + ((kBM - 1) / W + 1) * (l.ws - W) + ((kBM - 1) / (H * W) + 1) * (l.hs - H) * l.ws + 2 * l.ws + 3;
-  while ((np & 3) != 2) ++np;
-  return np;
+  wp[((size_t)(c >> 3) * coutp + col_off + n) * 8 + (c & 7)] = f32_to_bf16_rne(v);
 }
 
 template <int WM, int MF, int NFW, bool DW>
@@ -509,8 +449,6 @@ int pack_pw_bf16_launch(const float* w, const float* bias, int cout, int cin_src
   RTPOSE_HIP_CHECK(hipGetLastError());
   return 0;
 }
-
-int pw_halo_stride_bf16(const rtpose_layout& l, int H, int W) { return pwb::halo_stride(l, H, W); }
 
 // d->in / out / pt_src point at bf16 elements (out: fp32 when out_f32), layouts count ELEMENTS; d->w_packed from
 // pack_pw_bf16_launch; out_cmap is used by the fp32 (heads) epilogue only; pass-through = interleave form only.
@@ -533,38 +471,8 @@ int pw_fused_bf16_launch(const rtpose_pw_desc* d, int out_f32, int N, int H, int
   if (!below_2g_elems(d->lin, N, H, W) || !below_2g_elems(d->lout, N, H, W))
     return fail(RTPOSE_E_INVAL, "pw_fused_bf16: tensors must be below 2^31 elements");
   Args a;
-  memset(&a, 0, sizeof(a));
-  a.in = View{reinterpret_cast<const unsigned short*>(d->in), d->lin.cstride, d->lin.choff, d->lin.ws, d->lin.hs, d->lin.lead};
-  a.dw_w = d->dw_w;
-  a.dw_b = d->dw_b;
-  a.w = reinterpret_cast<const float4*>(d->w_packed);
-  a.bias = d->bias_packed;
-  a.out = d->out;
-  a.out_cstride = d->lout.cstride;
-  a.out_choff = d->lout.choff;
-  a.out_ws = d->lout.ws;
-  a.out_hs = d->lout.hs;
-  a.out_lead = d->lout.lead;
-  a.out_cmap = d->out_cmap;
+  const int grid = fill_pw_args(a, d, N, H, W, kBM, kTile);
   a.out_f32 = out_f32 ? 1 : 0;
-  if (d->pt_src) {
-    a.pt = View{reinterpret_cast<const unsigned short*>(d->pt_src), d->lpt.cstride, d->lpt.choff, d->lpt.ws, d->lpt.hs, d->lpt.lead};
-    a.pt_pairs = d->pt_pairs;
-    a.pt_a = d->pt_a;
-    a.pt_b = d->pt_b;
-    a.pt_split = d->pt_split;
-    a.pt_d0 = d->pt_d0;
-    a.pt_d1 = d->pt_d1;
-  }
-  a.in_planes = d->in_planes;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.M = N * H * W;
-  a.K = d->cin;
-  a.coutp = d->coutp;
-  a.cout = d->cout;
-  a.relu = d->relu;
   const int nfw = d->coutp >= 256 ? 2 : 1, mf = d->coutp == 64 ? 1 : 2;
   const size_t slab4 = (size_t)4 * 32 * mf * ((32 * nfw + 8) / 8);
   size_t st4 = slab4;
@@ -573,14 +481,6 @@ int pw_fused_bf16_launch(const rtpose_pw_desc* d, int out_f32, int N, int H, int
     if ((size_t)kPL * a.nps > st4) st4 = (size_t)kPL * a.nps;
   }
   const size_t lds = ((size_t)2 * kPL * kQS + st4) * 16 + (dw ? (size_t)10 * d->cin * 4 : 0);
-  const int npass_h = d->coutp <= 128 ? 1 : d->coutp / 256;
-  a.fHW = make_fastdiv(H * W);
-  a.fW = make_fastdiv(W);
-  a.fnp = make_fastdiv(npass_h);
-  a.ftx = make_fastdiv(ceil_div(W, kTile));
-  a.fty = make_fastdiv(ceil_div(H, kTile));
-  const int nwork = (dw ? N * ceil_div(H, kTile) * ceil_div(W, kTile) : ceil_div(a.M, kBM)) * npass_h;
-  const int grid = nwork < 2 * device_cu_count() ? nwork : 2 * device_cu_count();
   if (d->coutp == 64) return dw ? launch_inst<2, 1, 1, true>(a, grid, lds, s) : launch_inst<2, 1, 1, false>(a, grid, lds, s);
   if (d->coutp == 128) return dw ? launch_inst<1, 2, 1, true>(a, grid, lds, s) : launch_inst<1, 2, 1, false>(a, grid, lds, s);
   return dw ? launch_inst<1, 2, 2, true>(a, grid, lds, s) : launch_inst<1, 2, 2, false>(a, grid, lds, s);

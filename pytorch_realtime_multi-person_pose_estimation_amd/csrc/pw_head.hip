@@ -32,18 +32,11 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace head {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef const floatx4 __attribute__((address_space(1)))* gcf4_t;
-__device__ __forceinline__ float4 gload4(const void* p) {  // explicit global address space (no FLAT loads)
-  const floatx4 v = *(gcf4_t)(unsigned long long)(p);
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
 
 constexpr int PX = 32;   // pixels of a work item (one MFMA fragment)
 constexpr int PS = 33;   // LDS plane pitch in float4 (planes 4 banks apart for the 8-lane write groups)
@@ -52,22 +45,18 @@ constexpr int kMaxK1 = 1024;  // largest K of the wide conv (plane table in LDS)
 
 struct Args {
   const float* in;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
+  Lay lin;
   const int32_t* in_planes;  // optional [K1 / 4]: channel offset (inside the slice) of every 4-channel plane of K1
   const float* w1;  // [K1 / 4][N1][4]
   const float* b1;  // [N1]
   const float* w2;  // [N1 / 4][64][4]
   const float* b2;  // [64]
   float* out;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lout;
   int N, H, W, M;
   int K1, N1, nitems;
   FastDiv fHW, fW;  // divisions by launch constants (common.h)
 };
-
-#define RTPOSE_HEAD_PIN()        \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
 
 template <int NF>
 __global__ __launch_bounds__(256, 1) void pw_head_f32(const Args A) {
@@ -96,21 +85,17 @@ __global__ __launch_bounds__(256, 1) void pw_head_f32(const Args A) {
   const int NP = A.N1 / (32 * NF);
   const float4* const w1 = reinterpret_cast<const float4*>(A.w1);
   const float4* const w2 = reinterpret_cast<const float4*>(A.w2);
-  const float* const in_base = A.in + A.in_choff;
+  const float* const in_base = A.in + A.lin.choff;
 
   // staging role of a lane: 16-byte plane spl of the pixels spx + 8 u, u < 4 (a pixel's chunk = one 128-byte line)
   const int spl = lane & 7, spx = lane >> 3;
-  auto pixel_q = [&](int m, int lead, int hs, int ws) {
-    const int n = fast_div(m, A.fHW), r = m - n * HW;
-    const int y = fast_div(r, A.fW), x = r - y * A.W;
-    return lead + (n * hs + y) * ws + x;
-  };
+  auto pixel_q = [&](int m, const Lay& l) { return lay_pix(l, pix_of(m, HW, A.W, A.fHW, A.fW)); };
   unsigned sq[4], sqn[4];  // element offsets of the lane's four staged pixels: this item / the next one
   auto setup = [&](int it, unsigned* q) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int m = min(it * PX + spx + 8 * u, A.M - 1);  // pixels past the end replay the last one (never stored)
-      q[u] = (unsigned)pixel_q(m, A.in_lead, A.in_hs, A.in_ws) * (unsigned)A.in_cstride;
+      q[u] = (unsigned)pixel_q(m, A.lin) * (unsigned)A.lin.cstride;
     }
   };
   float4 sr[4];
@@ -173,7 +158,7 @@ __global__ __launch_bounds__(256, 1) void pw_head_f32(const Args A) {
   for (int f = 0; f < NF; ++f) init_acc(f, 0);
   init_out();
   stage_store(0);
-  RTPOSE_HEAD_PIN();  // (LDS serves a wave's requests in order: the write is seen by the read below)
+  RTPOSE_PIN();  // (LDS serves a wave's requests in order: the write is seen by the read below)
   RTPOSE_HEAD_XLOAD(xa, 0, 0);
   int lb = 0;  // LDS buffer of the current chunk
 
@@ -184,8 +169,8 @@ __global__ __launch_bounds__(256, 1) void pw_head_f32(const Args A) {
     // output pixel of this lane
     const int mo = item * PX + l31;
     const bool ovalid = mo < A.M;
-    const unsigned oq = (unsigned)pixel_q(min(mo, A.M - 1), A.out_lead, A.out_hs, A.out_ws) * (unsigned)A.out_cstride +
-                        (unsigned)A.out_choff;
+    const unsigned oq = (unsigned)pixel_q(min(mo, A.M - 1), A.lout) * (unsigned)A.lout.cstride +
+                        (unsigned)A.lout.choff;
 
     for (int p = 0; p < NP; ++p) {
       const bool lastp = p + 1 == NP;
@@ -204,34 +189,34 @@ __global__ __launch_bounds__(256, 1) void pw_head_f32(const Args A) {
         RTPOSE_HEAD_WLOAD(wb, g0 + 1, p);
         stage_load(qn, cn);  // AFTER the weight request: the next wait for weights does not wait for these
         RTPOSE_HEAD_XLOAD(xb, lb, 1);
-        RTPOSE_HEAD_PIN();
+        RTPOSE_PIN();
         RTPOSE_HEAD_MUL(wa, xa);
-        RTPOSE_HEAD_PIN();
+        RTPOSE_PIN();
         // ---- group 1 (set B); the last group of a two-group chunk: the next chunk goes to LDS and its first
         //      fragments are requested (selected operands instead of a second code path: one MFMA region) ----
         const bool short_chunk = lastc && ng_last == 2;
         if (short_chunk) stage_store(nb);
         RTPOSE_HEAD_WLOAD(wa, short_chunk ? 0 : g0 + 2, short_chunk ? pn : p);
-        RTPOSE_HEAD_PIN();
+        RTPOSE_PIN();
         RTPOSE_HEAD_XLOAD(xa, short_chunk ? nb : lb, short_chunk ? 0 : 2);
-        RTPOSE_HEAD_PIN();
+        RTPOSE_PIN();
         RTPOSE_HEAD_MUL(wb, xb);
-        RTPOSE_HEAD_PIN();
+        RTPOSE_PIN();
         if (!short_chunk) {
           // ---- group 2 (set A) ----
           RTPOSE_HEAD_WLOAD(wb, g0 + 3, p);
           RTPOSE_HEAD_XLOAD(xb, lb, 3);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           RTPOSE_HEAD_MUL(wa, xa);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           // ---- group 3 (set B): the next chunk goes to LDS, its first fragments are requested ----
           stage_store(nb);
           RTPOSE_HEAD_WLOAD(wa, lastc ? 0 : g0 + 4, pn);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           RTPOSE_HEAD_XLOAD(xa, nb, 0);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           RTPOSE_HEAD_MUL(wb, xb);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
         }
         lb = nb;
       }
@@ -270,15 +255,15 @@ __global__ __launch_bounds__(256, 1) void pw_head_f32(const Args A) {
         for (int f = 0; f < NF; f += 2) {
           RTPOSE_HEAD_W2LOAD(vb, f + 1);
           RTPOSE_HEAD_BLOAD(f);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           RTPOSE_HEAD_FOLD(va, f);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           RTPOSE_HEAD_BSET(f);
           if (f + 2 < NF) { RTPOSE_HEAD_W2LOAD(va, f + 2); }
           RTPOSE_HEAD_BLOAD(f + 1);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           RTPOSE_HEAD_FOLD(vb, f + 1);
-          RTPOSE_HEAD_PIN();
+          RTPOSE_PIN();
           RTPOSE_HEAD_BSET(f + 1);
         }
 #undef RTPOSE_HEAD_BSET
@@ -307,7 +292,6 @@ __global__ __launch_bounds__(256, 1) void pw_head_f32(const Args A) {
 #undef RTPOSE_HEAD_XLOAD
 #undef RTPOSE_HEAD_WLOAD
 }
-#undef RTPOSE_HEAD_PIN
 
 // zero the columns [c0, c1) of a packed pointwise matrix [K / 4][coutp][4] and of its bias
 __global__ void zero_columns_kernel(float* __restrict__ wp, float* __restrict__ bp, int K, int coutp, int c0, int c1) {
@@ -356,22 +340,14 @@ int pw_head_launch(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2, int N, in
   Args a;
   memset(&a, 0, sizeof(a));
   a.in = d1->in;
-  a.in_cstride = d1->lin.cstride;
-  a.in_choff = d1->lin.choff;
-  a.in_ws = d1->lin.ws;
-  a.in_hs = d1->lin.hs;
-  a.in_lead = d1->lin.lead;
+  a.lin = to_lay(d1->lin);
   a.in_planes = d1->in_planes;
   a.w1 = d1->w_packed;
   a.b1 = d1->bias_packed;
   a.w2 = d2->w_packed;
   a.b2 = d2->bias_packed;
   a.out = d2->out;
-  a.out_cstride = d2->lout.cstride;
-  a.out_choff = d2->lout.choff;
-  a.out_ws = d2->lout.ws;
-  a.out_hs = d2->lout.hs;
-  a.out_lead = d2->lout.lead;
+  a.lout = to_lay(d2->lout);
   a.N = N;
   a.H = H;
   a.W = W;

@@ -32,51 +32,15 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
-#include "wino_common.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace headb {
 
-using winoc::i32x4;
-using winoc::make_rsrc;
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float4 bload4(i32x4 r, unsigned voff, unsigned soff) {
-  const winoc::f32x4 v = winoc::llvm_raw_buffer_load_v4f32(r, (int)voff, (int)soff, 0);
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ bf16x8 as_bf8(const float4& v) {
-  const floatx4 t = {v.x, v.y, v.z, v.w};
-  return __builtin_bit_cast(bf16x8, t);
-}
-__device__ __forceinline__ unsigned short to_bf16(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
-// ReLU on the bit pattern: a negative float (and -0) is a negative int, a positive one orders like its bits - one
-// v_max_i32 where fmaxf costs a canonicalising v_max_f32 more (no NaN reaches here that the reference would keep)
-// The compiler's hazard recogniser does not know that the asm above reads an MFMA result: the wait states between the last
-// MFMA that wrote an accumulator and its first v_accvgpr_read (up to 18 for a 16-pass 32x32x16) are inserted by hand,
-// once, in front of every read-out section.  (Found the hard way: registers 0 and 1 of the first fragment read stale
-// values in one instance of unit_bf16_kernel whose epilogue followed the last MFMA directly.)
-__device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-__device__ __forceinline__ float relu_bits(float v) {
-  return __builtin_bit_cast(float, max(__builtin_bit_cast(int, v), 0));
-}
-// One accumulator register -> a VGPR, HERE.  The allocator otherwise moves the pass' whole C1^T tile (128 registers)
-// out of the accumulator file right behind the last MFMA of GEMM 1 - the VALU of the fold cannot read AGPRs - and
-// spills around it; read one at a time, a fragment's values are live for the length of its own conversion only.
-__device__ __forceinline__ float acc_read(float a) {
-  float v;
-  asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
-  return v;
-}
 // relu + RNE of two fp32 -> one dword of two bf16 (v_cvt_pk_bf16_f32)
 __device__ __forceinline__ float pack_relu2(float lo, float hi) {
-  const bf16x2 t = {(__bf16)relu_bits(lo), (__bf16)relu_bits(hi)};
-  return __builtin_bit_cast(float, t);
+  return __uint_as_float(pack_bf16x2(relu_bits(lo), relu_bits(hi)));
 }
 
 constexpr int PXB = 128;      // pixels of a block item (four MFMA fragments)
@@ -89,22 +53,18 @@ constexpr int kRed4 = 4 * 8 * 64;  // float4 slots of the cross-wave reduction b
 struct Args {
   const unsigned short* in;  // bf16 activations
   size_t in_bytes;           // addressable from `in` (buffer descriptor range)
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;   // in ELEMENTS / pixels
+  Lay lin;   // in ELEMENTS / pixels
   const int32_t* in_planes;  // optional [K1 / 8]: element offset (inside the slice) of every 8-channel plane of K1
   const void* w1;            // [K1 / 8][N1][8 bf16]   (pack_pw_bf16_launch, plain column order)
   const float* b1;           // [N1]
   const void* w2;            // [N1 / 8][64][8 bf16], k permuted (pack_head_w2_bf16)
   const float* b2;           // [64]
   float* out;
-  int out_cstride, out_choff, out_ws, out_hs, out_lead;
+  Lay lout;
   int N, H, W, M;
   int K1, N1, nitems;
   FastDiv fHW, fW;
 };
-
-#define RTPOSE_HB_PIN()          \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
 
 template <int V>
 struct IntTag {
@@ -146,11 +106,7 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
   const unsigned w2_lane = (unsigned)(kh * N2 + l31) * 16u;
   const unsigned x_lane = (unsigned)(kh * XP + l31);                        // float4 index in a k-step's two LDS planes
 
-  auto pixel_q = [&](int m, int lead, int hs, int ws) {
-    const int n = fast_div(m, A.fHW), r = m - n * HW;
-    const int y = fast_div(r, A.fW), x = r - y * A.W;
-    return lead + (n * hs + y) * ws + x;
-  };
+  auto pixel_q = [&](int m, const Lay& l) { return lay_pix(l, pix_of(m, HW, A.W, A.fHW, A.fW)); };
   // staging role of a thread: plane spl of a chunk, pixels spx + 32 u.  8 consecutive lanes = 4 planes x 2 pixels
   // (conflict-free ds_write_b128), a wave = 8 planes x 8 pixels = eight whole 128-byte lines per load instruction
   const int spl = (tid & 3) | (((tid >> 3) & 1) << 2);
@@ -160,7 +116,7 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int m = min(it * PXB + spx + 32 * u, A.M - 1);  // pixels past the end replay the last one (never stored)
-      q[u] = ((unsigned)pixel_q(m, A.in_lead, A.in_hs, A.in_ws) * (unsigned)A.in_cstride + (unsigned)A.in_choff) * 2u;
+      q[u] = ((unsigned)pixel_q(m, A.lin) * (unsigned)A.lin.cstride + (unsigned)A.lin.choff) * 2u;
     }
   };
   float4 sr[2][4];  // two chunks in flight: requested at the first step of a chunk pair, stored behind its eighth
@@ -257,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
       }
       wload(wr[(S + 7) & 7], p3, g3);
       xload(xr[XS ^ 1], g + 1 == kst ? 0 : g + 1);
-      RTPOSE_HB_PIN();
+      RTPOSE_PIN();
       if (g < kreal) {  // (uniform, no load inside; a step past K1 - the ring and the chunk pairs want whole turns - is skipped)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -265,7 +221,7 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
           for (int f = 0; f < 2; ++f)
             acc[f][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(wr[S][f]), as_bf8(xr[XS][j]), acc[f][j], 0, 0, 0);
       }
-      RTPOSE_HB_PIN();
+      RTPOSE_PIN();
     };
     auto run_pass = [&](int p) {
       const bool lastp = p + 1 == NP;
@@ -308,11 +264,11 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
                                         pack_relu2(acc_read(a[8 * h + 6]), acc_read(a[8 * h + 7])));
           o[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(w2r[ks & 1][0]), as_bf8(bv), o[0][j], 0, 0, 0);
           o[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(w2r[ks & 1][1]), as_bf8(bv), o[1][j], 0, 0, 0);
-          RTPOSE_HB_PIN();  // (one fragment's eight values at a time: hoisted together they would not fit the registers)
+          RTPOSE_PIN();  // (one fragment's eight values at a time: hoisted together they would not fit the registers)
         }
         if (ks < 2) w2load(w2r[ks & 1], p, ks + 2);
       }
-      RTPOSE_HB_PIN();
+      RTPOSE_PIN();
     };
 
     for (int p = 0; p < NP; ++p) run_pass(p);
@@ -324,14 +280,14 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
     for (int j = 0; j < 4; ++j) {
       const int mo = item * PXB + 32 * j + l31;
       const bool ov = mo < A.M;
-      const unsigned oq = (unsigned)pixel_q(min(mo, A.M - 1), A.out_lead, A.out_hs, A.out_ws) * (unsigned)A.out_cstride +
-                          (unsigned)A.out_choff;
+      const unsigned oq = (unsigned)pixel_q(min(mo, A.M - 1), A.lout) * (unsigned)A.lout.cstride +
+                          (unsigned)A.lout.choff;
 #pragma unroll
       for (int r4 = 0; r4 < 8; ++r4) {
         const floatx16& v = o[r4 >> 2][j];
         const int b = (r4 & 3) * 4;
         red[(wave * 8 + r4) * 64 + lane] = make_float4(acc_read(v[b]), acc_read(v[b + 1]), acc_read(v[b + 2]), acc_read(v[b + 3]));
-        if (r4 & 1) { RTPOSE_HB_PIN(); }
+        if (r4 & 1) { RTPOSE_PIN(); }
       }
       __syncthreads();
 #pragma unroll
@@ -364,7 +320,6 @@ __global__ __launch_bounds__(256, 1) void pw_head_bf16_kernel(const Args A) {
     xload(xr[0], 0);
   }
 }
-#undef RTPOSE_HB_PIN
 
 // w[cout][K] fp32 (+ bias) -> the heads' shared matrix [K / 8][64][8 bf16] at columns col_off .. col_off + cout - 1, with
 // the k order GEMM 2 reads its B operand in: inside a 16-channel group c16, lane half kh = (c16 / 4) % 2 holds the
@@ -378,7 +333,7 @@ __global__ void pack_head_w2_bf16_kernel(const float* __restrict__ w, const floa
   const int n = i % cout, c = i / cout;
   const int c16 = c & 15;
   const int q = 2 * (c >> 4) + ((c16 >> 2) & 1), e = ((c16 >> 3) << 2) | (c16 & 3);
-  wp[((size_t)q * N2 + col_off + n) * 8 + e] = to_bf16(w[(size_t)n * K + c]);
+  wp[((size_t)q * N2 + col_off + n) * 8 + e] = f32_to_bf16_rne(w[(size_t)n * K + c]);
 }
 __global__ void zero_head_columns_bf16_kernel(unsigned short* __restrict__ wp, float* __restrict__ bp, int K, int c0, int c1) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -438,22 +393,14 @@ int pw_head_bf16_launch(const rtpose_pw_desc* d1, const rtpose_pw_desc* d2, int 
   memset(&a, 0, sizeof(a));
   a.in = reinterpret_cast<const unsigned short*>(d1->in);
   a.in_bytes = in_bytes;
-  a.in_cstride = d1->lin.cstride;
-  a.in_choff = d1->lin.choff;
-  a.in_ws = d1->lin.ws;
-  a.in_hs = d1->lin.hs;
-  a.in_lead = d1->lin.lead;
+  a.lin = to_lay(d1->lin);
   a.in_planes = d1->in_planes;
   a.w1 = d1->w_packed;
   a.b1 = d1->bias_packed;
   a.w2 = d2->w_packed;
   a.b2 = d2->bias_packed;
   a.out = d2->out;
-  a.out_cstride = d2->lout.cstride;
-  a.out_choff = d2->lout.choff;
-  a.out_ws = d2->lout.ws;
-  a.out_hs = d2->lout.hs;
-  a.out_lead = d2->lout.lead;
+  a.lout = to_lay(d2->lout);
   a.N = N;
   a.H = H;
   a.W = W;

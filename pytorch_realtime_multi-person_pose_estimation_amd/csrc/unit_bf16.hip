@@ -33,60 +33,11 @@
 
 #include "conv_desc.h"
 #include "launchers.h"
-#include "wino_common.h"
+#include "mfma_dev.h"
 
 namespace rtpose {
 
 namespace unitb {
-
-using winoc::i32x4;
-using winoc::make_rsrc;
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float4 bload4(i32x4 r, unsigned voff, unsigned soff) {
-  const winoc::f32x4 v = winoc::llvm_raw_buffer_load_v4f32(r, (int)voff, (int)soff, 0);
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ void llvm_raw_buffer_store_v4f32(winoc::f32x4 v, i32x4 rsrc, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.raw.buffer.store.v4f32");
-__device__ __forceinline__ void bstore4(const float4& v, i32x4 r, unsigned voff) {
-  const winoc::f32x4 t = {v.x, v.y, v.z, v.w};
-  llvm_raw_buffer_store_v4f32(t, r, (int)voff, 0, 0);
-}
-__device__ __forceinline__ bf16x8 as_bf8(const float4& v) {
-  const floatx4 t = {v.x, v.y, v.z, v.w};
-  return __builtin_bit_cast(bf16x8, t);
-}
-__device__ __forceinline__ float acc_read(float a) {  // one accumulator register -> a VGPR, here (see pw_head_bf16.hip)
-  float v;
-  asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
-  return v;
-}
-// The compiler's hazard recogniser does not know that the asm above reads an MFMA result: the wait states between the last
-// MFMA that wrote an accumulator and its first v_accvgpr_read (up to 18 for a 16-pass 32x32x16) are inserted by hand,
-// once, in front of every read-out section.  (Found the hard way: registers 0 and 1 of the first fragment read stale
-// values in one instance of unit_bf16_kernel whose epilogue followed the last MFMA directly.)
-__device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-__device__ __forceinline__ float relu_bits(float v) {
-  return __builtin_bit_cast(float, max(__builtin_bit_cast(int, v), 0));
-}
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {  // RNE (v_cvt_pk_bf16_f32)
-  const bf16x2 t = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, t);
-}
-__device__ __forceinline__ void unpack8(const float4& p, float* f) {  // 8 bf16 -> 8 floats
-  const unsigned u[4] = {__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), __float_as_uint(p.w)};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(u[i] << 16);
-    f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-  }
-}
 
 constexpr int kTile = 8;               // output tile edge
 constexpr int kHalo = kTile + 2;       // halo edge
@@ -99,7 +50,7 @@ constexpr int kMaxKt = 256;            // widest T1
 struct Args {
   const unsigned short* in;  // the stage buffer (bf16), gap >= 1
   size_t in_bytes;
-  int in_cstride, in_choff, in_ws, in_hs, in_lead;
+  Lay lin;
   const int32_t* in_planes;  // [K1 / 8]: element offset (inside the pixel slice) of every 8-channel plane of x2
   const void* w0;            // conv.0: [K1 / 8][C1P][8 bf16], columns = T1 channels, zero columns past Kt
   const float* b0;           // [C1P]
@@ -116,10 +67,6 @@ struct Args {
   int tiles_x, tiles_y, nitems;
   FastDiv ftx, fty;
 };
-
-#define RTPOSE_UB_PIN()          \
-  asm volatile("" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0)
 
 template <int V>
 struct IntTag {
@@ -215,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
       const int hp = min(spx + 64 * u, kNHP - 1);
       const int hy = (hp * 205) >> 11, hx = hp - 10 * hy;  // hp / 10 for hp < 1024
       const int y = min(max(t.y0 - 1 + hy, -1), A.H), x = min(max(t.x0 - 1 + hx, -1), A.W);
-      q[u] = ((unsigned)(A.in_lead + (t.n * A.in_hs + y) * A.in_ws + x) * (unsigned)A.in_cstride + (unsigned)A.in_choff) * 2u;
+      q[u] = ((unsigned)lay_pix(A.lin, t.n, y, x) * (unsigned)A.lin.cstride + (unsigned)A.lin.choff) * 2u;
     }
   };
   // Chunks c0, c0 + 1 of a tile: requested, and later stored, as one round.  The next tile's rounds fly under the
@@ -298,13 +245,13 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
         constexpr int XS = decltype(i_tag)::value & 1;
         w0load(w0r[(S + 3) & 3], g + 3);  // (past K1: nothing fetched)
         x1load(xr[XS ^ 1], g + 1);
-        RTPOSE_UB_PIN();
+        RTPOSE_PIN();
         if (g < k1real) {  // (uniform; no load inside)
 #pragma unroll
           for (int j = 0; j < MF1; ++j)
             acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(w0r[S]), as_bf8(xr[XS][j]), acc1[j], 0, 0, 0);
         }
-        RTPOSE_UB_PIN();
+        RTPOSE_PIN();
       };
       for (int g0 = 0; g0 < kst1; g0 += 4) {
         step1(IntTag<0>(), g0);
@@ -337,13 +284,13 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
         const int pl = 4 * wc1 + rg;  // (uniform)
         const floatx16& a = acc1[j];
         uint2 v;
-        v.x = pack2(relu_bits(acc_read(a[rg * 4 + 0])), relu_bits(acc_read(a[rg * 4 + 1])));
-        v.y = pack2(relu_bits(acc_read(a[rg * 4 + 2])), relu_bits(acc_read(a[rg * 4 + 3])));
+        v.x = pack_bf16x2_scalar(relu_bits(acc_read(a[rg * 4 + 0])), relu_bits(acc_read(a[rg * 4 + 1])));
+        v.y = pack_bf16x2_scalar(relu_bits(acc_read(a[rg * 4 + 2])), relu_bits(acc_read(a[rg * 4 + 3])));
         if (!inside) v = make_uint2(0u, 0u);
         if (pl < nplt && hp < kNHP)
           *reinterpret_cast<uint2*>(reinterpret_cast<char*>(xs + pl * XP1 + hp) + 8 * kh) = v;
       }
-      RTPOSE_UB_PIN();
+      RTPOSE_PIN();
     }
     __syncthreads();  // B2: T1 is in LDS
 
@@ -359,13 +306,13 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
         const float4* s0 = xs + pl * XP1 + (qr >> 1) * kHalo + (qr & 1) * 4;  // halo pixel of tap (0, 0) of the first pixel
         const float4 bz0 = *reinterpret_cast<const float4*>(dwl + 9 * A.Kt + ch);
         const float4 bz1 = *reinterpret_cast<const float4*>(dwl + 9 * A.Kt + ch + 4);
-        f2 v[4][4];
+        floatx2 v[4][4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          v[q][0] = f2{bz0.x, bz0.y};
-          v[q][1] = f2{bz0.z, bz0.w};
-          v[q][2] = f2{bz1.x, bz1.y};
-          v[q][3] = f2{bz1.z, bz1.w};
+          v[q][0] = floatx2{bz0.x, bz0.y};
+          v[q][1] = floatx2{bz0.z, bz0.w};
+          v[q][2] = floatx2{bz1.x, bz1.y};
+          v[q][3] = floatx2{bz1.z, bz1.w};
         }
         float4 row[2][6];
 #pragma unroll
@@ -380,22 +327,22 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
           for (int kx = 0; kx < 3; ++kx) {
             const float4 w0 = *reinterpret_cast<const float4*>(dwl + (ky * 3 + kx) * A.Kt + ch);
             const float4 w1 = *reinterpret_cast<const float4*>(dwl + (ky * 3 + kx) * A.Kt + ch + 4);
-            const f2 ww[4] = {{w0.x, w0.y}, {w0.z, w0.w}, {w1.x, w1.y}, {w1.z, w1.w}};
+            const floatx2 ww[4] = {{w0.x, w0.y}, {w0.z, w0.w}, {w1.x, w1.y}, {w1.z, w1.w}};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               float x[8];
               unpack8(row[ky & 1][q + kx], x);
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[q][e] = __builtin_elementwise_fma(f2{x[2 * e], x[2 * e + 1]}, ww[e], v[q][e]);
+              for (int e = 0; e < 4; ++e) v[q][e] = __builtin_elementwise_fma(floatx2{x[2 * e], x[2 * e + 1]}, ww[e], v[q][e]);
             }
           }
-          RTPOSE_UB_PIN();
+          RTPOSE_PIN();
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           a2[pl * AP2 + 16 * q + qr] =
-              make_float4(__uint_as_float(pack2(v[q][0].x, v[q][0].y)), __uint_as_float(pack2(v[q][1].x, v[q][1].y)),
-                          __uint_as_float(pack2(v[q][2].x, v[q][2].y)), __uint_as_float(pack2(v[q][3].x, v[q][3].y)));
+              make_float4(__uint_as_float(pack_bf16x2_scalar(v[q][0].x, v[q][0].y)), __uint_as_float(pack_bf16x2_scalar(v[q][1].x, v[q][1].y)),
+                          __uint_as_float(pack_bf16x2_scalar(v[q][2].x, v[q][2].y)), __uint_as_float(pack_bf16x2_scalar(v[q][3].x, v[q][3].y)));
       }
     }
     stage_store(xn, 0);   // the round requested before the T1 write-out ...
@@ -428,13 +375,13 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
 #pragma unroll
       for (int g = 0; g < 4 * NCH2; ++g) {
         x2load(xq[(g & 1) ^ 1], g + 1);
-        RTPOSE_UB_PIN();
+        RTPOSE_PIN();
         if (g < k2real) {  // (uniform)
 #pragma unroll
           for (int j = 0; j < MF2; ++j)
             acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(w2r[g]), as_bf8(xq[g & 1][j]), acc2[j], 0, 0, 0);
         }
-        RTPOSE_UB_PIN();
+        RTPOSE_PIN();
       }
     }
     stage_store(xn, 2);
@@ -451,11 +398,11 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
         const int pl = 4 * wc2 + rg;  // (uniform)
         const floatx16& a = acc2[j];
         uint2 v;
-        v.x = pack2(relu_bits(acc_read(a[rg * 4 + 0])), relu_bits(acc_read(a[rg * 4 + 1])));
-        v.y = pack2(relu_bits(acc_read(a[rg * 4 + 2])), relu_bits(acc_read(a[rg * 4 + 3])));
+        v.x = pack_bf16x2_scalar(relu_bits(acc_read(a[rg * 4 + 0])), relu_bits(acc_read(a[rg * 4 + 1])));
+        v.y = pack_bf16x2_scalar(relu_bits(acc_read(a[rg * 4 + 2])), relu_bits(acc_read(a[rg * 4 + 3])));
         *reinterpret_cast<uint2*>(reinterpret_cast<char*>(xs + pl * XP1 + 32 * (MF2 * wm2 + j) + l31) + 8 * kh) = v;
       }
-      RTPOSE_UB_PIN();
+      RTPOSE_PIN();
     }
     __syncthreads();  // B5: the y tile is in LDS
     {
@@ -480,7 +427,6 @@ __global__ __launch_bounds__(512, 1) void unit_bf16_kernel(const Args A) {
     pp ^= 1;
   }
 }
-#undef RTPOSE_UB_PIN
 
 template <int WM1, int WM2, int NCH2>
 static int launch_inst(const Args& a, int grid, size_t lds, hipStream_t s) {
@@ -530,11 +476,7 @@ int unit_bf16_launch(const rtpose_pw_desc* d0, const rtpose_pw_desc* d2, int N, 
   memset(&a, 0, sizeof(a));
   a.in = reinterpret_cast<const unsigned short*>(d0->in);
   a.in_bytes = in_bytes;
-  a.in_cstride = d0->lin.cstride;
-  a.in_choff = d0->lin.choff;
-  a.in_ws = d0->lin.ws;
-  a.in_hs = d0->lin.hs;
-  a.in_lead = d0->lin.lead;
+  a.lin = to_lay(d0->lin);
   a.in_planes = d0->in_planes;
   a.w0 = d0->w_packed;
   a.b0 = d0->bias_packed;

@@ -126,6 +126,26 @@ def unit_bf16(x, w0, b0, dw, w2, b2, trace=None, drop=None):
 
 
 # ---- the channel bookkeeping, as index arithmetic ---------------------------------------------------------------------------------
+def pack_pw(w, b, K, coutp, col_off, cin_map=None, col_map=None, ncols=None, wp=None, bp=None):
+    """The fp32 pointwise packers (rtpose_pack_pw_weights; rtpose_pack_pw_weights_cols with col_map / ncols) restated: into
+    packed [K / 4][coutp][4] and bias [coutp] (given, or zeros), column col_off + i takes output channel col_map[i] (None: i;
+    outside [0, cout): a zero column, zero bias) of w [cout, cin_src] and b (None: zero bias), K row c reads input channel
+    cin_map[c] (None: c; outside [0, cin_src): a zero row).  Every other word keeps what it held.  Returns flat copies."""
+    cout, cin_src = w.shape
+    ncols = cout if ncols is None else ncols
+    wp = np.zeros(K * coutp, np.float32) if wp is None else np.array(wp, dtype=np.float32)
+    bp = np.zeros(coutp, np.float32) if bp is None else np.array(bp, dtype=np.float32)
+    w3 = wp.reshape(K // 4, coutp, 4)
+    for i in range(ncols):
+        n = i if col_map is None else int(col_map[i])
+        live = 0 <= n < cout
+        bp[col_off + i] = b[n] if live and b is not None else 0.0
+        for c in range(K):
+            src = (c if c < cin_src else -1) if cin_map is None else int(cin_map[c])
+            w3[c // 4, col_off + i, c % 4] = w[n, src] if live and 0 <= src < cin_src else 0.0
+    return wp, bp
+
+
 def plane_channels(planes, unit):
     """in_planes: K channel k is channel planes[k // unit] + k % unit of the pixel (relative to lin.choff); unit = 4 (fp32)
     or 8 (bf16) channels = 16 bytes"""

@@ -113,6 +113,24 @@ def test_bad_arguments_are_rejected_on_the_host(capi):
     assert lib.get_part_cid(3, 3) == -1 and lib.get_part_x(0) == -1
 
 
+def test_both_pointwise_packers_refuse_bad_arguments_in_their_own_words(capi):
+    """rtpose_pack_pw_weights forwards to the column-mapped packer of rtpose_pack_pw_weights_cols; each door checks its own
+    arguments first and names itself in the message.  Every call here returns before any HIP call (the pointers are never
+    read: 16 stands for a non-NULL address)."""
+    lib, p = capi.lib, C.c_void_p(16)
+    plain = lambda w=p, cout=3, K=8, coutp=64, col_off=5, wp=p, bp=p: lib.rtpose_pack_pw_weights(
+        w, None, cout, 8, None, K, coutp, col_off, wp, bp, None)
+    cols = lambda w=p, cout=3, K=8, ncols=3, coutp=64, col_off=5, wp=p, bp=p: lib.rtpose_pack_pw_weights_cols(
+        w, None, cout, 8, None, K, ncols, None, coutp, col_off, wp, bp, None)
+    bad = [dict(w=None), dict(wp=None), dict(bp=None), dict(cout=0), dict(K=0), dict(K=12), dict(col_off=-1)]
+    for kw in bad + [dict(col_off=62)]:                 # 62 + cout = 65 > coutp
+        assert plain(**kw) != 0, kw
+        assert capi.last_error() == "pack_pw: bad arguments", kw
+    for kw in bad + [dict(ncols=0), dict(col_off=62)]:  # 62 + ncols = 65 > coutp
+        assert cols(**kw) != 0, kw
+        assert capi.last_error() == "pack_pw_cols: bad arguments", kw
+
+
 def test_compute_dtype_plans_on_the_host(capi, pkg):
     """Plan construction is host-only: the reduced-precision plans exist, report their dtype, keep
     the same 92 convs / launch list, size their arenas sensibly and reject what they cannot run."""

@@ -86,3 +86,39 @@ def test_pw_head_refuses_a_16_channel_input(capi, cuda):
     assert capi.lib.rtpose_pw_head(C.byref(d1), C.byref(d2), case.n, case.h, case.w, capi.current_stream()) != 0
     torch.cuda.synchronize()
     assert np.all(pd.host_bits(out) == pd.SENTINEL["f32"])
+
+
+@pytest.mark.parametrize("K", [8, 16])
+@pytest.mark.parametrize("variant", ["bias", "no_bias", "cin_map"])
+def test_both_fp32_packer_doors_pack_the_same_bytes(capi, cuda, K, variant):
+    """rtpose_pack_pw_weights and rtpose_pack_pw_weights_cols(col_map = NULL, ncols = cout) are one packer behind two doors:
+    into sentinel-filled buffers both write byte-identical packed weights and biases, which are pr.pack_pw's - the three
+    columns from col_off and nothing else.  cin_map holds a negative entry (a zero K row) and an entry past cin_src."""
+    lib, stream = capi.lib, capi.current_stream()
+    cout, coutp, col_off, cin_src = 3, 64, 5, 6
+    rng = np.random.default_rng(K)
+    w = rng.standard_normal((cout, cin_src)).astype(np.float32)
+    b = rng.standard_normal(cout).astype(np.float32) if variant != "no_bias" else None
+    cmap = None
+    if variant == "cin_map":
+        cmap = rng.integers(0, cin_src, K).astype(np.int32)
+        cmap[1], cmap[K - 2] = -1, cin_src
+    assert lib.rtpose_packed_pw_floats(K, coutp) == K * coutp
+    wd, bd, md = pd.f32(cuda, w), None if b is None else pd.f32(cuda, b), None if cmap is None else pd.i32(cuda, cmap)
+    got = []
+    for door in ("plain", "cols"):
+        wp, bp = pd.sentinel_buffer(K * coutp, "f32", cuda), pd.sentinel_buffer(coutp, "f32", cuda)
+        if door == "plain":
+            capi.check(lib.rtpose_pack_pw_weights(capi.ptr(wd), capi.ptr(bd), cout, cin_src, capi.ptr(md), K, coutp, col_off,
+                                                  capi.ptr(wp), capi.ptr(bp), stream))
+        else:
+            capi.check(lib.rtpose_pack_pw_weights_cols(capi.ptr(wd), capi.ptr(bd), cout, cin_src, capi.ptr(md), K, cout, None,
+                                                       coutp, col_off, capi.ptr(wp), capi.ptr(bp), stream))
+        torch.cuda.synchronize()
+        got.append((pd.host_bits(wp), pd.host_bits(bp)))
+    sent_w = np.full(K * coutp, pd.SENTINEL["f32"], np.uint32).view(np.float32)
+    sent_b = np.full(coutp, pd.SENTINEL["f32"], np.uint32).view(np.float32)
+    want_w, want_b = pr.pack_pw(w, b, K, coutp, col_off, cin_map=cmap, wp=sent_w, bp=sent_b)
+    for gw, gb in got:
+        assert np.array_equal(gw, want_w.view(np.uint32)) and np.array_equal(gb, want_b.view(np.uint32))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])

@@ -508,7 +508,7 @@ def test_forward_allocates_nothing_and_graph_replay_covers_persistent_launches(p
 
 def test_reads_past_the_tensor_are_clamped_by_the_buffer_descriptor(capi, cuda):
     """The raw buffer descriptors of the Winograd kernels carry the real extent of the tensor they address
-    (wino_common.h: make_rsrc): memory past the end of the input / the packed filters is never interpreted.  The
+    (mfma_dev.h: make_rsrc): memory past the end of the input / the packed filters is never interpreted.  The
     input and the filters are placed in front of a NaN-filled region; outputs stay finite and equal to the run
     with a zero-filled neighbourhood.  F(4x4,3x3) - the plan default of 17 convs - is covered in all three launch
     forms: the 16 x 16 small-grid kernel (wino4s_f32), one round of 32 x 64 tiles, and persistent blocks
