@@ -382,6 +382,41 @@ int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, con
                    const float* weight, int relu, float* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
                    double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream);
 
+/* ---- 2b, continued.  The two element-wise BatchNorm passes between the bf16 convs of a layout-resident training run
+ * (csrc/batchnorm.hip; train.preact_chain): rtpose_bn_apply and the second pass of rtpose_bn_grad with the rounding of
+ * rtpose_layout_f32_to_bf16 at their store, so that the fp32 y and the fp32 dx of a BatchNorm that sits between two bf16
+ * convs never exist.  `x`, `gy` are fp32 slices; `y` / `dx` are 2-byte bf16 slices whose layouts count ELEMENTS, as in
+ * rtpose_prelu_bf16.  Gaps and the channels beside the slices are neither read nor written, so a zero-initialised
+ * destination keeps its zero gaps and stays convolvable.
+ *
+ *     y[n,y,x,c]  = bf16(rtpose_bn_apply's y)       v = scale[c] * x + shift[c], one fp32 multiply and one fp32 add, never
+ *                                                   fused; relu: v <= 0 ? +0 : v (a NaN v stays NaN); then the rounding
+ *     dx[n,y,x,c] = bf16(rtpose_bn_grad's dx)       (g * A - B) - (x - mean) * C, its five fp32 operations; then the rounding
+ *
+ * bf16() rounds to nearest even as rtpose_layout_f32_to_bf16 does: Inf stays Inf, a NaN stays a NaN of its sign.  So y has
+ * the bits of rtpose_bn_apply followed by rtpose_layout_f32_to_bf16 - what the next conv's input conversion makes of the
+ * fp32 y - and dx the bits of rtpose_bn_grad's fp32 dx followed by rtpose_layout_f32_to_bf16.
+ * rtpose_bn_grad_bf16's first pass and finalising launch ARE rtpose_bn_grad's - the same kernel instances on the same slabs
+ * (rtpose_bn_slabs()), the same fp64 sums in the same order, no atomics -, so dweight, dbias and the workspace tail A, B, C
+ * have the bits rtpose_bn_grad gives on the same inputs.  The workspace is rtpose_bn_workspace_doubles() doubles; there
+ * are no queries of their own.  dx == NULL, dweight == NULL and dbias == NULL behave as they do there (all three NULL is
+ * refused; dx == NULL launches the reduction only).
+ * Non-finite values: what rtpose_bn_apply / rtpose_bn_grad do with a NaN or an Inf of x or gy (above), then the rounding:
+ * a finite fp32 value above bf16's largest rounds to Inf of its sign.
+ * 16-byte loads and one 8-byte store of 4 bf16 where every fp32 slice has a 16-byte-aligned base and a cstride and choff
+ * that are multiples of 4, and the bf16 slice an 8-byte-aligned base and a cstride and choff that are multiples of 4
+ * elements (rtpose_prelu_bf16's rule); element by element otherwise: the same bits either way.  No scratch.
+ * Every argument is checked on the host before any HIP call (RTPOSE_E_INVAL with a text): NULL pointers or layouts,
+ * channels / N / H / W < 1, N * H * W = 1, choff + channels > cstride, a layout smaller than the map, N * H * W above the
+ * launch limit of 2^31 - 256 pixels, an odd base of the bf16 slice, a bf16 slice whose bytes overlap those of x, gy, save or
+ * weight (these passes never run in place), and a workspace below rtpose_bn_workspace_doubles() doubles. */
+int rtpose_bn_apply_bf16(const float* x, const rtpose_layout* lx, const float* save, void* y, const rtpose_layout* ly,
+                         int relu, int channels, int N, int H, int W, void* stream);
+int rtpose_bn_grad_bf16(const float* x, const rtpose_layout* lx, const float* gy, const rtpose_layout* lgy,
+                        const float* save, const float* weight, int relu, void* dx, const rtpose_layout* ldx, float* dweight,
+                        float* dbias, double* workspace, size_t workspace_doubles, int channels, int N, int H, int W,
+                        void* stream);
+
 /* ---- 2b, continued.  Backward pass of the depthwise 3x3 convolution, padding 1, stride 1 or 2 (csrc/dwconv_backward.hip):
  * what nn.Conv2d(C, C, 3, stride, 1, groups = C, bias = False) of the ShuffleNetV2 blocks needs to train
  * (train.dwconv3x3); the forward is rtpose_dwconv3x3.  H, W are the conv's INPUT size, stride is 1 or 2,

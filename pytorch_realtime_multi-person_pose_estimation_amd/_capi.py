@@ -263,6 +263,8 @@ _SIGS = {
     "rtpose_bn_stats": (_i, [_vp, _LP, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rtpose_bn_apply": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_bn_grad": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _i, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "rtpose_bn_apply_bf16": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
+    "rtpose_bn_grad_bf16": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _i, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "rtpose_dwconv3x3_wgrad_workspace_doubles": (_sz, [_i, _i, _i, _i, _i]),
     "rtpose_dwconv3x3_wgrad_slabs": (_i, [_i, _i, _i, _i, _i]),
     "rtpose_dwconv3x3_wgrad": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),

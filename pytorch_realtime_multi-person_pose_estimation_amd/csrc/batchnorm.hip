@@ -21,10 +21,22 @@
 // of two are exact there) and take both through LDS in one pass; the slab's partials are [slab][2][channels] doubles, and
 // the second launch of one thread per channel adds them in slab order and finalises.  apply and dx are the element-wise
 // passes.  Every element reads only its own x / gy element, so y may name the slice x names and dx the slice gy names.
+//
+// And the two element-wise passes between the bf16 convs of a layout-resident training run (train.preact_chain): the same
+// device code with the store rounded to bf16 (OUT = uint16_t; bf16_dest.h), straight into the slice the next conv reads.
+//
+//   rtpose_bn_apply_bf16  y  = bf16(rtpose_bn_apply's fp32 y)
+//   rtpose_bn_grad_bf16   dx = bf16(rtpose_bn_grad's fp32 dx); the sum pass and the finalising launch ARE rtpose_bn_grad's
+//
+// bf16(): round to nearest even as rtpose_layout_f32_to_bf16 rounds (Inf stays Inf, a NaN stays a NaN of its sign), so the
+// bits are those of the fp32 entry point followed by rtpose_layout_f32_to_bf16.  The bf16 destination lies bytes apart from
+// every input and is 2-byte aligned; its 4-channel units ask aligned8_bf16 of it where the fp32 ones ask aligned16.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
+#include "bf16_dest.h"
 #include "chan_slab.h"
 
 namespace rtpose {
@@ -43,7 +55,7 @@ struct BnArgs {
   const float* gy;     // grad only
   const float* save;   // [kSaveRows][channels]; NULL for the statistics
   const float* coef;   // [3][channels] A, B, C: the dx pass
-  float* out;          // y / dx
+  void* out;           // y / dx: float, or bf16 bits
   double* ws;          // [slab][2][channels] partials: the two sum passes
   Lay lx, lgy, lout;
   int channels, H, W, P;
@@ -55,7 +67,8 @@ struct BnArgs {
 
 enum { kStats = 0, kGradSums = 1, kApply = 2, kGradDx = 3 };
 
-template <int V, int MODE>
+// OUT: float, or uint16_t for a bf16 destination (the element-wise passes only)
+template <int V, int MODE, class OUT = float>
 __global__ __launch_bounds__(kThreads) void bn_kernel(const BnArgs a) {
   constexpr bool SUM = MODE == kStats || MODE == kGradSums;
   constexpr bool GRAD = MODE == kGradSums || MODE == kGradDx;
@@ -114,7 +127,12 @@ __global__ __launch_bounds__(kThreads) void bn_kernel(const BnArgs a) {
           res.v[v] = t0 - u;
         }
       }
-      if (!SUM) store<V>(a.out, lay_off(a.lout, q) + t.c0, t, res);
+      if constexpr (!SUM) {
+        if constexpr (std::is_same_v<OUT, float>)
+          store<V>(static_cast<float*>(a.out), lay_off(a.lout, q) + t.c0, t, res);
+        else
+          store_bf16<V>(static_cast<uint16_t*>(a.out), lay_off(a.lout, q) + t.c0, t, res);
+      }
     }
   }
 
@@ -209,9 +227,149 @@ void fill_args(BnArgs& a, int channels, int H, int W, long P, int slab) {
   a.d_h = make_fastdiv(H);
 }
 
-template <int MODE>
+template <int MODE, class OUT = float>
 void launch_bn(bool vec, dim3 grid, hipStream_t s, const BnArgs& a) {
-  launch_units<bn_kernel<4, MODE>, bn_kernel<1, MODE>>(vec, grid, s, a);
+  launch_units<bn_kernel<4, MODE, OUT>, bn_kernel<1, MODE, OUT>>(vec, grid, s, a);
+}
+
+// whether a destination slice takes the 4-channel units
+template <class OUT>
+bool dest_vec(const rtpose_layout& l, const void* p) {
+  if constexpr (std::is_same_v<OUT, float>)
+    return aligned16(l, p);
+  else
+    return aligned8_bf16(l, p);
+}
+
+// what the bf16 entry points ask of their destination beside check_slice: 2-byte aligned, and bytes apart from x, gy (or
+// NULL), save and weight (or NULL); 0 or fail(...)
+int check_dest(const char* who, const char* what, const void* out, const rtpose_layout& lout, const float* x,
+               const rtpose_layout& lx, const float* gy, const rtpose_layout* lgy, const float* save, const float* weight,
+               int channels, int N, int H, int W) {
+  if (reinterpret_cast<uintptr_t>(out) % 2) return fail(RTPOSE_E_INVAL, "%s: %s must be 2-byte aligned", who, what);
+  if (int rc = check_apart_slice(who, "x", out, lout, x, lx, channels, N, H, W)) return rc;
+  if (gy)
+    if (int rc = check_apart_slice(who, "gy", out, lout, gy, *lgy, channels, N, H, W)) return rc;
+  if (int rc = check_apart_vector(who, "save", out, lout, save, (size_t)RTPOSE_BN_SAVE_ROWS * channels, channels, N, H, W))
+    return rc;
+  if (weight)
+    if (int rc = check_apart_vector(who, "weight", out, lout, weight, (size_t)channels, channels, N, H, W)) return rc;
+  return 0;
+}
+
+// rtpose_bn_apply (OUT = float) and rtpose_bn_apply_bf16 (OUT = uint16_t)
+template <class OUT>
+int bn_apply(const char* who, const float* x, const rtpose_layout* lx, const float* save, void* y, const rtpose_layout* ly,
+             int relu, int channels, int N, int H, int W, void* stream) {
+  constexpr bool kBf16 = !std::is_same_v<OUT, float>;
+  long P;
+  if (int rc = check_shape_bn(who, channels, N, H, W, P)) return rc;
+  if (int rc = check_slice(who, "x", x, lx, channels, H, W, 0)) return rc;
+  if (int rc = check_slice(who, "y", y, ly, channels, H, W, 0)) return rc;
+  if (!save) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (save)", who);
+  if constexpr (kBf16)
+    if (int rc = check_dest(who, "y", y, *ly, x, *lx, nullptr, nullptr, save, nullptr, channels, N, H, W)) return rc;
+
+  BnArgs a{};
+  a.x = x;
+  a.save = save;
+  a.out = y;
+  a.lx = a.lgy = to_lay(lx);
+  a.lout = to_lay(ly);
+  a.relu = relu ? 1 : 0;
+  fill_args(a, channels, H, W, P, kSlabUnit);
+  const bool vec = aligned16(*lx, x) && dest_vec<OUT>(*ly, y);
+  dim3 grid;
+  if (int rc = set_rectangle(a.r, channels, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc;
+
+  // (statics of a function template: each entry point has its own set)
+  static thread_local CheckedPtr c_x, c_s, c_y;
+  const int dev = current_device();
+  int rc = c_x.check(x, dev, who, "x");
+  if (!rc) rc = c_s.check(save, dev, who, "save");
+  if (!rc) rc = c_y.check(y, dev, who, "y");
+  if (rc) return rc;
+
+  launch_bn<kApply, OUT>(vec, grid, as_stream(stream), a);
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// rtpose_bn_grad (OUT = float) and rtpose_bn_grad_bf16 (OUT = uint16_t): the sum pass and the finalising launch are the
+// same instances for both, the dx pass is OUT's
+template <class OUT>
+int bn_grad(const char* who, const float* x, const rtpose_layout* lx, const float* gy, const rtpose_layout* lgy,
+            const float* save, const float* weight, int relu, void* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
+            double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream) {
+  constexpr bool kBf16 = !std::is_same_v<OUT, float>;
+  long P;
+  if (int rc = check_shape_bn(who, channels, N, H, W, P)) return rc;
+  if (int rc = check_slice(who, "x", x, lx, channels, H, W, 0)) return rc;
+  if (int rc = check_slice(who, "gy", gy, lgy, channels, H, W, 0)) return rc;
+  if (dx)
+    if (int rc = check_slice(who, "dx", dx, ldx, channels, H, W, 0)) return rc;
+  if (!save || !weight) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (save or weight)", who);
+  if (!dx && !dweight && !dbias) return fail(RTPOSE_E_INVAL, "%s: nothing to compute (dx, dweight and dbias are all NULL)", who);
+  if constexpr (kBf16)
+    if (dx)
+      if (int rc = check_dest(who, "dx", dx, *ldx, x, *lx, gy, lgy, save, weight, channels, N, H, W)) return rc;
+  const SlabGeom g = slab_geometry(P);
+  if (int rc = check_ws(who, workspace, workspace_doubles, channels, g)) return rc;
+
+  BnArgs a{};
+  a.x = x;
+  a.gy = gy;
+  a.save = save;
+  a.ws = workspace;
+  a.lx = to_lay(lx);
+  a.lgy = to_lay(lgy);
+  a.lout = to_lay(dx ? ldx : lgy);
+  a.relu = relu ? 1 : 0;
+  fill_args(a, channels, H, W, P, g.slab);
+  float* coef = reinterpret_cast<float*>(workspace + (size_t)g.slabs * 2 * (size_t)channels);
+  const bool vec_in = aligned16(*lx, x) && aligned16(*lgy, gy);
+  const bool vec = vec_in && (!dx || dest_vec<OUT>(*ldx, dx));
+  dim3 grid_in, grid;
+  if (int rc = set_rectangle(a.r, channels, vec_in ? 4 : 1, g.slabs, grid_in, who)) return rc;
+
+  // (statics of a function template: each entry point has its own set)
+  static thread_local CheckedPtr c_x, c_gy, c_s, c_w, c_dx, c_dw, c_db, c_ws;
+  const int dev = current_device();
+  int rc = c_x.check(x, dev, who, "x");
+  if (!rc) rc = c_gy.check(gy, dev, who, "gy");
+  if (!rc) rc = c_s.check(save, dev, who, "save");
+  if (!rc) rc = c_w.check(weight, dev, who, "weight");
+  if (!rc && dx) rc = c_dx.check(dx, dev, who, "dx");
+  if (!rc && dweight) rc = c_dw.check(dweight, dev, who, "dweight");
+  if (!rc && dbias) rc = c_db.check(dbias, dev, who, "dbias");
+  if (!rc) rc = c_ws.check(workspace, dev, who, "workspace");
+  if (rc) return rc;
+
+  hipStream_t s = as_stream(stream);
+  launch_bn<kGradSums>(vec_in, grid_in, s, a);
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  FinalArgs f{};
+  f.ws = workspace;
+  f.x0 = x + ((size_t)lx->lead * lx->cstride + lx->choff);
+  f.weight = weight;
+  f.save = const_cast<float*>(save);
+  f.coef = dx ? coef : nullptr;
+  f.dweight = dweight;
+  f.dbias = dbias;
+  f.slabs = g.slabs;
+  f.channels = channels;
+  f.P = a.P;
+  hipLaunchKernelGGL(bn_grad_final_kernel, dim3((unsigned)ceil_div(channels, kFinalThreads)), dim3(kFinalThreads), 0, s, f);
+  RTPOSE_HIP_CHECK(hipGetLastError());
+  if (dx) {
+    a.out = dx;
+    a.coef = coef;
+    a.slab = kSlabUnit;
+    if (int rc2 = set_rectangle(a.r, channels, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc2;
+    launch_bn<kGradDx, OUT>(vec, grid, s, a);
+    RTPOSE_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
 }
 
 }  // namespace
@@ -290,105 +448,26 @@ int rtpose_bn_stats(const float* x, const rtpose_layout* lx, const float* weight
 
 int rtpose_bn_apply(const float* x, const rtpose_layout* lx, const float* save, float* y, const rtpose_layout* ly, int relu,
                     int channels, int N, int H, int W, void* stream) {
-  const char* who = "bn_apply";
-  long P;
-  if (int rc = check_shape_bn(who, channels, N, H, W, P)) return rc;
-  if (int rc = check_slice(who, "x", x, lx, channels, H, W, 0)) return rc;
-  if (int rc = check_slice(who, "y", y, ly, channels, H, W, 0)) return rc;
-  if (!save) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (save)", who);
+  return bn_apply<float>("bn_apply", x, lx, save, y, ly, relu, channels, N, H, W, stream);
+}
 
-  BnArgs a{};
-  a.x = x;
-  a.save = save;
-  a.out = y;
-  a.lx = a.lgy = to_lay(lx);
-  a.lout = to_lay(ly);
-  a.relu = relu ? 1 : 0;
-  fill_args(a, channels, H, W, P, kSlabUnit);
-  const bool vec = aligned16(*lx, x) && aligned16(*ly, y);
-  dim3 grid;
-  if (int rc = set_rectangle(a.r, channels, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc;
-
-  static thread_local CheckedPtr c_x, c_s, c_y;
-  const int dev = current_device();
-  int rc = c_x.check(x, dev, who, "x");
-  if (!rc) rc = c_s.check(save, dev, who, "save");
-  if (!rc) rc = c_y.check(y, dev, who, "y");
-  if (rc) return rc;
-
-  launch_bn<kApply>(vec, grid, as_stream(stream), a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  return 0;
+int rtpose_bn_apply_bf16(const float* x, const rtpose_layout* lx, const float* save, void* y, const rtpose_layout* ly, int relu,
+                         int channels, int N, int H, int W, void* stream) {
+  return bn_apply<uint16_t>("bn_apply_bf16", x, lx, save, y, ly, relu, channels, N, H, W, stream);
 }
 
 int rtpose_bn_grad(const float* x, const rtpose_layout* lx, const float* gy, const rtpose_layout* lgy, const float* save,
                    const float* weight, int relu, float* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
                    double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream) {
-  const char* who = "bn_grad";
-  long P;
-  if (int rc = check_shape_bn(who, channels, N, H, W, P)) return rc;
-  if (int rc = check_slice(who, "x", x, lx, channels, H, W, 0)) return rc;
-  if (int rc = check_slice(who, "gy", gy, lgy, channels, H, W, 0)) return rc;
-  if (dx)
-    if (int rc = check_slice(who, "dx", dx, ldx, channels, H, W, 0)) return rc;
-  if (!save || !weight) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (save or weight)", who);
-  if (!dx && !dweight && !dbias) return fail(RTPOSE_E_INVAL, "%s: nothing to compute (dx, dweight and dbias are all NULL)", who);
-  const SlabGeom g = slab_geometry(P);
-  if (int rc = check_ws(who, workspace, workspace_doubles, channels, g)) return rc;
+  return bn_grad<float>("bn_grad", x, lx, gy, lgy, save, weight, relu, dx, ldx, dweight, dbias, workspace, workspace_doubles,
+                        channels, N, H, W, stream);
+}
 
-  BnArgs a{};
-  a.x = x;
-  a.gy = gy;
-  a.save = save;
-  a.ws = workspace;
-  a.lx = to_lay(lx);
-  a.lgy = to_lay(lgy);
-  a.lout = to_lay(dx ? ldx : lgy);
-  a.relu = relu ? 1 : 0;
-  fill_args(a, channels, H, W, P, g.slab);
-  float* coef = reinterpret_cast<float*>(workspace + (size_t)g.slabs * 2 * (size_t)channels);
-  const bool vec_in = aligned16(*lx, x) && aligned16(*lgy, gy);
-  const bool vec = vec_in && (!dx || aligned16(*ldx, dx));
-  dim3 grid_in, grid;
-  if (int rc = set_rectangle(a.r, channels, vec_in ? 4 : 1, g.slabs, grid_in, who)) return rc;
-
-  static thread_local CheckedPtr c_x, c_gy, c_s, c_w, c_dx, c_dw, c_db, c_ws;
-  const int dev = current_device();
-  int rc = c_x.check(x, dev, who, "x");
-  if (!rc) rc = c_gy.check(gy, dev, who, "gy");
-  if (!rc) rc = c_s.check(save, dev, who, "save");
-  if (!rc) rc = c_w.check(weight, dev, who, "weight");
-  if (!rc && dx) rc = c_dx.check(dx, dev, who, "dx");
-  if (!rc && dweight) rc = c_dw.check(dweight, dev, who, "dweight");
-  if (!rc && dbias) rc = c_db.check(dbias, dev, who, "dbias");
-  if (!rc) rc = c_ws.check(workspace, dev, who, "workspace");
-  if (rc) return rc;
-
-  hipStream_t s = as_stream(stream);
-  launch_bn<kGradSums>(vec_in, grid_in, s, a);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  FinalArgs f{};
-  f.ws = workspace;
-  f.x0 = x + ((size_t)lx->lead * lx->cstride + lx->choff);
-  f.weight = weight;
-  f.save = const_cast<float*>(save);
-  f.coef = dx ? coef : nullptr;
-  f.dweight = dweight;
-  f.dbias = dbias;
-  f.slabs = g.slabs;
-  f.channels = channels;
-  f.P = a.P;
-  hipLaunchKernelGGL(bn_grad_final_kernel, dim3((unsigned)ceil_div(channels, kFinalThreads)), dim3(kFinalThreads), 0, s, f);
-  RTPOSE_HIP_CHECK(hipGetLastError());
-  if (dx) {
-    a.out = dx;
-    a.coef = coef;
-    a.slab = kSlabUnit;
-    if (int rc2 = set_rectangle(a.r, channels, vec ? 4 : 1, ceil_div(a.P, kSlabUnit), grid, who)) return rc2;
-    launch_bn<kGradDx>(vec, grid, s, a);
-    RTPOSE_HIP_CHECK(hipGetLastError());
-  }
-  return 0;
+int rtpose_bn_grad_bf16(const float* x, const rtpose_layout* lx, const float* gy, const rtpose_layout* lgy, const float* save,
+                        const float* weight, int relu, void* dx, const rtpose_layout* ldx, float* dweight, float* dbias,
+                        double* workspace, size_t workspace_doubles, int channels, int N, int H, int W, void* stream) {
+  return bn_grad<uint16_t>("bn_grad_bf16", x, lx, gy, lgy, save, weight, relu, dx, ldx, dweight, dbias, workspace,
+                           workspace_doubles, channels, N, H, W, stream);
 }
 
 }  // extern "C"

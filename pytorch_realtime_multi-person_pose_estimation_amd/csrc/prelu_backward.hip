@@ -31,7 +31,7 @@
 // Three things differ between the fp32 and the bf16 entry points on purpose.  They were decided when each was written, not by
 // the change that put them into one file, and none is this file's to unify:
 //   * aliasing: every element reads only its own gy element, so the fp32 out / lout may name the slice gy / lgy name.  The
-//     bf16 destination must lie bytes apart from every input (check_dest, check_apart*) and be 2-byte aligned;
+//     bf16 destination must lie bytes apart from every input (check_dest; bf16_dest.h) and be 2-byte aligned;
 //   * grid: the fp32 passes take slab_geometry's slab and slab count with or without sums, the bf16 element-wise passes (no
 //     sums) kSlabUnit pixels per workgroup.  The values do not depend on it;
 //   * the 4-channel units: aligned16 on every fp32 slice; aligned8_bf16 on the bf16 destination.
@@ -39,6 +39,7 @@
 
 #include <type_traits>
 
+#include "bf16_dest.h"
 #include "chan_slab.h"
 #include "pixel_walk.h"
 
@@ -46,8 +47,6 @@ namespace rtpose {
 namespace {
 
 constexpr int kReduceThreads = 64;
-
-typedef uint32_t Word2 __attribute__((ext_vector_type(2)));
 
 bool shape_ok(int channels, int N, int H, int W) { return channels >= 1 && pixel_count(N, H, W) > 0; }
 
@@ -67,21 +66,6 @@ struct PreluArgs {
   Rect r;
   FastDiv d_w, d_h;
 };
-
-// the V channels of a unit rounded to bf16 at element offset o: one 8-byte store of a whole unit, else its live channels
-template <int V>
-__device__ __forceinline__ void store_bf16(uint16_t* dst, size_t o, const Place& t, const Unit<V>& u) {
-  if constexpr (V == 4) {
-    if (t.whole) {
-      *reinterpret_cast<Word2*>(dst + o) = Word2{f32_to_bf16_rne(u.v[0]) | ((uint32_t)f32_to_bf16_rne(u.v[1]) << 16),
-                                                 f32_to_bf16_rne(u.v[2]) | ((uint32_t)f32_to_bf16_rne(u.v[3]) << 16)};
-      return;
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < V; ++v)
-    if (v < t.nc) dst[o + v] = f32_to_bf16_rne(u.v[v]);
-}
 
 // V: channels per unit.  OUT: float, or uint16_t for a bf16 destination.  GRAD: the backward (else y = prelu1(z, slope)).
 // TWO: g = ga + gb.  SUM: with the slope-gradient partials.
@@ -153,27 +137,6 @@ __global__ __launch_bounds__(kReduceThreads) void prelu_grad_reduce_kernel(const
   float v[1];
   sum_slabs<1, 8>(ws, slabs, 1, channels, 0, c, v);
   dslope[c] = v[0];
-}
-
-// 8-byte pieces of 4 bf16: every pixel's slice starts on one
-bool aligned8_bf16(const rtpose_layout& l, const void* base) {
-  return slice_aligned(l, 4) && reinterpret_cast<uintptr_t>(base) % 8 == 0;
-}
-
-// the bf16 slice out / lout against the bytes [i0, i1) of an input: apart, never in place; 0 or fail(...)
-int check_apart(const char* who, const char* what, const void* out, const rtpose_layout& lout, uintptr_t i0, uintptr_t i1,
-                int channels, int N, int H, int W) {
-  uintptr_t o0, o1;
-  slice_span_bytes(out, lout, 2, channels, N, H, W, o0, o1);
-  if (o1 <= i0 || i1 <= o0) return 0;
-  return fail(RTPOSE_E_INVAL, "%s: the bytes of the bf16 destination overlap those of %s", who, what);
-}
-
-int check_apart_slice(const char* who, const char* what, const void* out, const rtpose_layout& lout, const float* in,
-                      const rtpose_layout& lin, int channels, int N, int H, int W) {
-  uintptr_t i0, i1;
-  slice_span_bytes(in, lin, 4, channels, N, H, W, i0, i1);
-  return check_apart(who, what, out, lout, i0, i1, channels, N, H, W);
 }
 
 // what the bf16 entry points ask of their destination beside check_slice; 0 or fail(...)

@@ -68,6 +68,12 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   ``rtpose_relu_grad_bf16`` in place), and NCHW fp32 exists only where the run begins and ends.  Opt-in; the default is the
   per-conv path, launch for launch.
 
+* Layout-resident Bottlenecks (``preact_chain``; ``resident='bottleneck'`` of ``forward_train`` and ``train_step``, HourglassNet
+  with ``compute_dtype='bf16'`` only): the BatchNorm -> ReLU -> conv triples of a pre-activation Bottleneck's main branch are
+  one autograd node.  Its conv launches are the per-conv bf16 path's (``out_f32 = 1``); between them ``rtpose_bn_apply_bf16``
+  writes relu(bn(.)) as bf16 straight into the gapped buffer the next conv reads and ``rtpose_bn_grad_bf16`` the bf16
+  gradient the conv below reads.  No NCHW tensor and no fp32 BatchNorm output exists inside a run.  Opt-in.
+
 On the default path the NCHW <-> layout conversion around every operation is known overhead.
 
 A non-finite activation reaches the loss: the entry points called here carry NaN and Inf through their sums and their
@@ -1176,6 +1182,226 @@ def batch_norm(x, bn, relu=False):
     return _BatchNorm.apply(x, bn.weight, bn.bias, bn, bool(relu))
 
 
+# ---- a run of BatchNorm -> ReLU -> conv triples as one autograd node: a pre-activation Bottleneck's main branch (bf16) ---------
+# runs that gave up residency because rtpose_conv2d_bf16 refused one of their forward convs
+preact_fallbacks = 0
+
+
+def reset_preact_fallbacks():
+    global preact_fallbacks
+    preact_fallbacks = 0
+
+
+class _PreactRefused(Exception):
+    """rtpose_conv2d_bf16 refused a forward conv of a pre-activation run (before any launch of that conv)"""
+
+
+# the name _PreactChain launches its convs through, and nothing else does: replacing it plays a refusal of the node's own
+# launches and leaves alone the conv2d nodes the run falls back to (tests/test_train_bottleneck_gpu.py)
+_preact_conv_into = _conv_launch
+
+
+def _bn_workspace(c, n, h, w, device):
+    doubles = lib.rtpose_bn_workspace_doubles(c, n, h, w)
+    return torch.empty(doubles, dtype=torch.float64, device=device), doubles
+
+
+def _check_preact(x, layers):
+    who = "train.preact_chain"
+    if len(layers) < 1:
+        raise _capi.RtposeError("%s: no layers" % who)
+    for i, layer in enumerate(layers):
+        if not isinstance(layer, tuple) or len(layer) != 3 or not torch.is_tensor(layer[1]):
+            raise _capi.RtposeError("%s: layers are (nn.BatchNorm2d, weight, bias_or_None) triples; got %r at %d"
+                                    % (who, type(layer).__name__, i))
+    _require_device(who, x, names=("x",))
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise _capi.RtposeError("%s takes an NCHW fp32 input; got %s %s" % (who, x.dtype, tuple(x.shape)))
+    c = x.shape[1]
+    for i, (bn, weight, bias) in enumerate(layers):
+        # (the BatchNorm's input has the run's n, h, w and c channels: a view of that shape stands for it)
+        _check_bn(x[:, :1].expand(-1, c, -1, -1), bn)
+        rm, rv = bn.running_mean, bn.running_var
+        if not (rm.is_contiguous() and rv.is_contiguous() and rm.dtype == rv.dtype == torch.float32):
+            raise _capi.RtposeError("%s: running_mean / running_var must be contiguous fp32 tensors" % who)
+        _require_device(who, weight, names=("a weight",))
+        if not _is_same_conv_filter(weight, c):
+            raise _capi.RtposeError("%s: layer %d: stride-1 'same' convs with fp32 OIHW filters, k in {1, 3, 7}, whose input "
+                                    "channels are those of the BatchNorm in front (%s); got filters %s %s"
+                                    % (who, i, c, weight.dtype, tuple(weight.shape)))
+        if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (weight.shape[0],)
+                                 or bias.device != weight.device):
+            raise _capi.RtposeError("%s: layer %d: the bias is None or an fp32 [%d] tensor beside the filters"
+                                    % (who, i, weight.shape[0]))
+        c = weight.shape[0]
+
+
+class _PreactChain(torch.autograd.Function):
+    """preact_chain's node.  Inputs: x, (the BatchNorm modules, epoch, resync), then the BatchNorm's weight and bias and the
+    conv's weight and bias (or None) of every triple."""
+    @staticmethod
+    def forward(ctx, x, meta, *params):
+        bns, epoch, resync = meta
+        gammas, betas, weights, biases = params[0::4], params[1::4], params[2::4], params[3::4]
+        L = len(weights)
+        with torch.cuda.device(x.device):
+            stream = current_stream()
+            dev = x.device
+            n, _, h, w = x.shape
+            # what a refusal puts back: the kernels below update the running statistics, and the per-conv run the node
+            # falls back to updates them again
+            stats = torch.cat([t for bn in bns for t in (bn.running_mean, bn.running_var)])
+            cur, lcur = _to_layout(x.detach().contiguous(), 0)
+            xins, lxins, saves, abufs, lays = [], [], [], [], []
+            for i in range(L):
+                cout, c, k = weights[i].shape[0], weights[i].shape[1], weights[i].shape[2]
+                ws, doubles = _bn_workspace(c, n, h, w, dev)
+                save = torch.empty(_capi.BN_SAVE_ROWS * c, dtype=torch.float32, device=dev)
+                check(lib.rtpose_bn_stats(ptr(cur), C.byref(lcur), ptr(gammas[i].detach().contiguous()),
+                                          ptr(betas[i].detach().contiguous()), ptr(bns[i].running_mean),
+                                          ptr(bns[i].running_var), float(bns[i].momentum), float(bns[i].eps), ptr(save), ptr(ws),
+                                          doubles, c, n, h, w, stream), "rtpose_bn_stats")
+                # relu(bn(.)) rounded straight into the buffer the conv reads: gapped for it, its pad channels zero
+                la = _capi.Layout.padded(_up16(c), h, w, k // 2)
+                abuf = _buffer(la, n, h, w, dev, True, True)
+                check(lib.rtpose_bn_apply_bf16(ptr(cur), C.byref(lcur), ptr(save), ptr(abuf), C.byref(la), 1, c, n, h, w, stream),
+                      "rtpose_bn_apply_bf16")
+                wp, bp = _packed_for(weights[i], biases[i], 'fwd16', epoch, resync)
+                lz = _capi.Layout.dense(_up8(cout), h, w)
+                z = _buffer(lz, n, h, w, dev, False)
+                if not _preact_conv_into(True, abuf, la, wp, bp, la.cstride, cout, k, False, n, h, w, z, lz, out_f32=1):
+                    for j, bn in enumerate(bns):
+                        cj = bn.num_features
+                        off = 2 * sum(b.num_features for b in bns[:j])
+                        bn.running_mean.copy_(stats[off:off + cj])
+                        bn.running_var.copy_(stats[off + cj:off + 2 * cj])
+                    raise _PreactRefused()
+                xins.append(cur), lxins.append(lcur), saves.append(save), abufs.append(abuf), lays.append(la)
+                cur, lcur = z, lz
+            for bn in bns:
+                bn.num_batches_tracked.add_(1)
+            y = _from_layout(cur, lcur, n, weights[L - 1].shape[0], h, w)
+        need = ctx.needs_input_grad
+        wants = [need[4 + 4 * i] or (biases[i] is not None and need[5 + 4 * i]) for i in range(L)]
+        wants_bn = [need[2 + 4 * i] or need[3 + 4 * i] for i in range(L)]
+        # the lowest triple whose backward anything needs: the walk stops there
+        low = 0 if need[0] else next((i for i in range(L) if wants[i] or wants_bn[i]), L)
+        ctx.geom = (n, h, w)
+        ctx.meta = (epoch, resync)
+        ctx.gammas, ctx.weights = gammas, weights
+        ctx.has_bias = [b is not None for b in biases]
+        ctx.low, ctx.wants, ctx.wants_bn = low, wants, wants_bn
+        ctx.save_for_backward(*(gammas + weights))   # (for autograd's check that none was modified in place since)
+        # per triple: the fp32 input of its BatchNorm and its save rows where the BatchNorm's backward runs, the bf16
+        # activation where a weight gradient reads it; nothing else
+        bn_runs = [i > low or (i == low and (wants_bn[i] or (i == 0 and need[0]))) for i in range(L)]
+        ctx.bn_runs = bn_runs
+        ctx.xins = [(b, l) if run else None for b, l, run in zip(xins, lxins, bn_runs)]
+        ctx.saves = [s if run else None for s, run in zip(saves, bn_runs)]
+        ctx.abufs = [(b, l) if i >= low and wants[i] else None for i, (b, l) in enumerate(zip(abufs, lays))]
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        epoch, resync = ctx.meta
+        ctx.saved_tensors
+        gammas, weights, low, wants, wants_bn = ctx.gammas, ctx.weights, ctx.low, ctx.wants, ctx.wants_bn
+        L = len(weights)
+        n, h, w = ctx.geom
+        need = ctx.needs_input_grad
+        grads = [None] * (4 * L)
+        dx = None
+        if low >= L:
+            return (None, None) + tuple(grads)
+        with torch.cuda.device(gy.device):
+            dev = gy.device
+            stream = current_stream()
+            # no activation behind the last conv: gy is rounded as it enters
+            g, lg = _to_layout(gy.detach().float().contiguous(), weights[L - 1].shape[2] // 2, True)
+            for i in range(L - 1, low - 1, -1):
+                wt = weights[i]
+                cout, c, k = wt.shape[0], wt.shape[1], wt.shape[2]
+                if wants[i]:
+                    need_b = ctx.has_bias[i] and need[5 + 4 * i]
+                    dw, db = _wgrad(True, ctx.abufs[i][0], ctx.abufs[i][1], g, lg, wt, c, cout, k, n, h, w, need_b)
+                    grads[4 * i + 2] = dw if need[4 + 4 * i] else None
+                    grads[4 * i + 3] = db
+                if not ctx.bn_runs[i]:
+                    break
+                # the data gradient: the conv of g on the flipped, transposed filter into a dense fp32 buffer
+                wp, bp = _packed_for(wt, None, 'bwd16', epoch, resync)
+                ld = _capi.Layout.dense(_up8(c), h, w)
+                d = _buffer(ld, n, h, w, dev, False)
+                if not _preact_conv_into(True, g, lg, wp, bp, lg.cstride, c, k, False, n, h, w, d, ld, out_f32=1):
+                    d, ld = _dgrad_fp32_fallback(g, lg, wt, n, h, w, epoch, resync)   # refused: this one conv in fp32
+                xin, lxin = ctx.xins[i]
+                ws, doubles = _bn_workspace(c, n, h, w, dev)
+                dgam = torch.empty(c, dtype=torch.float32, device=dev) if need[2 + 4 * i] else None
+                dbet = torch.empty(c, dtype=torch.float32, device=dev) if need[3 + 4 * i] else None
+                gamma = ptr(gammas[i].detach().contiguous())
+                if i > 0:
+                    # through the ReLU and the BatchNorm straight into the bf16 gradient the conv below reads, gapped for it
+                    need_dx = i > low
+                    if need_dx:
+                        lg = _capi.Layout.padded(_up16(c), h, w, weights[i - 1].shape[2] // 2)
+                        g = _buffer(lg, n, h, w, dev, True, True)
+                    check(lib.rtpose_bn_grad_bf16(ptr(xin), C.byref(lxin), ptr(d), C.byref(ld), ptr(ctx.saves[i]), gamma, 1,
+                                                  ptr(g) if need_dx else None, C.byref(lg) if need_dx else None, ptr(dgam),
+                                                  ptr(dbet), ptr(ws), doubles, c, n, h, w, stream), "rtpose_bn_grad_bf16")
+                else:
+                    # the lowest BatchNorm: its dx leaves as NCHW fp32 (onto the data gradient's own buffer, as batch_norm does)
+                    check(lib.rtpose_bn_grad(ptr(xin), C.byref(lxin), ptr(d), C.byref(ld), ptr(ctx.saves[i]), gamma, 1,
+                                             ptr(d) if need[0] else None, C.byref(ld) if need[0] else None, ptr(dgam), ptr(dbet),
+                                             ptr(ws), doubles, c, n, h, w, stream), "rtpose_bn_grad")
+                    if need[0]:
+                        dx = _from_layout(d, ld, n, c, h, w)
+                grads[4 * i], grads[4 * i + 1] = dgam, dbet
+        return (dx, None) + tuple(grads)
+
+
+def preact_chain(x, layers, epoch=0, resync=False):
+    """A run of L >= 1 triples BatchNorm -> ReLU -> stride-1 "same" conv (k in {1, 3, 7}) - the main branch of a
+    pre-activation Bottleneck - as ONE autograd node, bf16 operands.  `layers`: (``nn.BatchNorm2d`` in training mode, conv
+    weight, conv bias or None) triples, every BatchNorm on the channels the conv before it writes; `x` NCHW fp32 on the
+    device.  Returns the last conv's output, NCHW fp32.  The BatchNorm checks are ``batch_norm``'s, the conv checks
+    ``conv_chain``'s; `epoch` / `resync`: see ``conv2d``; the packings are the cached 'fwd16' / 'bwd16' ones.
+
+    Forward: x enters through one ``rtpose_nchw_to_layout`` as fp32 and is kept for the first BatchNorm's backward.  Per
+    triple: ``rtpose_bn_stats`` on the fp32 buffer (the running statistics updated by the kernel, ``num_batches_tracked``
+    + 1, as ``batch_norm`` does), ``rtpose_bn_apply_bf16(relu = 1)`` into a zero-initialised bf16 buffer gapped for the
+    conv that reads it with the channels rounded up to 16, ``rtpose_conv2d_bf16(out_f32 = 1)`` on the 'fwd16' packing into
+    a dense fp32 pre-activation buffer - the next BatchNorm's input.  The last one leaves through one
+    ``rtpose_layout_to_nchw``.  Kept per triple: the fp32 input of its BatchNorm, its ``save`` rows, and the bf16 activation
+    where a weight gradient reads it.
+    Backward (``once_differentiable``; any ``requires_grad`` subset of x, the BatchNorm weights and biases, the filters and
+    biases): gy enters through one ``rtpose_nchw_to_layout_bf16``; per triple, top down, ``rtpose_conv2d_wgrad_bf16`` on the
+    kept bf16 activation, the data gradient as ``rtpose_conv2d_bf16(out_f32 = 1)`` on the 'bwd16' packing into a dense fp32
+    buffer, and ``rtpose_bn_grad_bf16(relu = 1)`` on the kept fp32 input, which writes the bf16 gradient the conv below
+    reads (gapped for it).  The lowest BatchNorm runs ``rtpose_bn_grad``: its dx leaves as NCHW fp32, only if x needs one.
+    The walk stops at the lowest triple anything needs; a parameter gradient is computed only where it is required.
+
+    No rounding point moves against ``conv2d(batch_norm(x, bn, relu=True), weight, bias, compute_dtype='bf16')`` repeated L
+    times: the output, every gradient and the running statistics are equal to that composition's bit for bit.
+
+    A forward conv ``rtpose_conv2d_bf16`` refuses (before launching) makes the run give up residency: the running statistics
+    the node has updated so far are put back, the run goes triple by triple through ``batch_norm`` and
+    ``conv2d(compute_dtype='bf16')`` - so every BatchNorm is updated once - and ``preact_fallbacks`` counts it.  A refused data
+    gradient runs that one conv in fp32 on the widened gradient and is counted in ``bf16_fallbacks['dgrad']``."""
+    global preact_fallbacks
+    layers = [tuple(layer) if isinstance(layer, (tuple, list)) else layer for layer in layers]
+    _check_preact(x, layers)
+    epoch, resync = int(epoch), bool(resync)
+    meta = (tuple(bn for bn, _, _ in layers), epoch, resync)
+    try:
+        return _PreactChain.apply(x, meta, *[p for bn, wt, b in layers for p in (bn.weight, bn.bias, wt, b)])
+    except _PreactRefused:
+        preact_fallbacks += 1
+    for bn, wt, b in layers:
+        x = conv2d(batch_norm(x, bn, relu=True), wt, b, False, epoch, resync, None, 'bf16')
+    return x
+
+
 def _check_same_conv(m):
     k = m.kernel_size[0]
     if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
@@ -1300,27 +1526,28 @@ def hourglass_bottleneck(blk, x, conv, bn):
     return out + residual
 
 
-def _hg_chain(seq, x, conv, bn):
+def _hg_chain(seq, x, conv, bn, block=None):
     for blk in seq:
-        x = hourglass_bottleneck(blk, x, conv, bn)
+        x = hourglass_bottleneck(blk, x, conv, bn) if block is None else block(blk, x)
     return x
 
 
-def _hg_level(hg, n, x, conv, bn):
+def _hg_level(hg, n, x, conv, bn, block=None):
     """reference :74-86"""
-    up1 = _hg_chain(hg[n - 1][0], x, conv, bn)
-    low1 = _hg_chain(hg[n - 1][1], F.max_pool2d(x, 2, stride=2), conv, bn)
-    low2 = _hg_level(hg, n - 1, low1, conv, bn) if n > 1 else _hg_chain(hg[n - 1][3], low1, conv, bn)
-    low3 = _hg_chain(hg[n - 1][2], low2, conv, bn)
+    up1 = _hg_chain(hg[n - 1][0], x, conv, bn, block)
+    low1 = _hg_chain(hg[n - 1][1], F.max_pool2d(x, 2, stride=2), conv, bn, block)
+    low2 = _hg_level(hg, n - 1, low1, conv, bn, block) if n > 1 else _hg_chain(hg[n - 1][3], low1, conv, bn, block)
+    low3 = _hg_chain(hg[n - 1][2], low2, conv, bn, block)
     return up1 + F.interpolate(low3, scale_factor=2)
 
 
-def hourglass_forward(model, x, conv, bn, stem):
+def hourglass_forward(model, x, conv, bn, stem, block=None):
     """The reference's training-mode forward (lib/network/rtpose_hourglass.py:26-46, :74-89, :162-189) over the module
     tree of a ``HourglassNet``, with the three operations as callables: ``conv(x, m)`` an ``nn.Conv2d`` m (stride 1,
     "same"), ``bn(x, m)`` ReLU of an ``nn.BatchNorm2d`` m in training mode (every BatchNorm of this network is followed by
     one), ``stem(x, m)`` the 7x7 stride-2 ``conv1``.  Max-pool, nearest upsampling, the residual sums and the hand-over
-    ``x + fc_ + paf_score_ + ht_score_`` are torch's, in the reference's order of additions.  Returns
+    ``x + fc_ + paf_score_ + ht_score_`` are torch's, in the reference's order of additions.  `block`: None, or a callable
+    ``block(blk, x)`` that stands for ``hourglass_bottleneck(blk, x, conv, bn)`` of every Bottleneck.  Returns
     ((score_paf, score_ht), [score_paf, score_ht]) of the last stack - the only one the reference supervises."""
     if not isinstance(model, HourglassNet):
         raise TypeError("train.hourglass_forward takes an hourglass.HourglassNet; got %s" % type(model).__name__)
@@ -1328,14 +1555,14 @@ def hourglass_forward(model, x, conv, bn, stem):
         raise _capi.RtposeError("train.hourglass_forward is the training-mode forward (batch statistics): call .train() "
                                 "first; fine-tuning on frozen statistics (.eval()) is out of scope")
     x = bn(stem(x, model.conv1), model.bn1)
-    x = _hg_chain(model.layer1, x, conv, bn)
+    x = _hg_chain(model.layer1, x, conv, bn, block)
     x = F.max_pool2d(x, 2, stride=2)
-    x = _hg_chain(model.layer2, x, conv, bn)
-    x = _hg_chain(model.layer3, x, conv, bn)
+    x = _hg_chain(model.layer2, x, conv, bn, block)
+    x = _hg_chain(model.layer3, x, conv, bn, block)
     score_paf = score_ht = None
     for i in range(model.num_stacks):
-        y = _hg_level(model.hg[i].hg, model.hg[i].depth, x, conv, bn)
-        y = _hg_chain(model.res[i], y, conv, bn)
+        y = _hg_level(model.hg[i].hg, model.hg[i].depth, x, conv, bn, block)
+        y = _hg_chain(model.res[i], y, conv, bn, block)
         y = bn(conv(y, model.fc[i][0]), model.fc[i][1])
         score_paf = conv(y, model.score_paf[i])
         score_ht = conv(y, model.score_ht[i])
@@ -1358,18 +1585,29 @@ def _begin_bn_forward(model, what):
     return model._weights_epoch[0], bool(getattr(model, 'always_resync', False))
 
 
-def _forward_train_hourglass(model, x):
+def _forward_train_hourglass(model, x, bottleneck=False):
+    """`bottleneck`: every Bottleneck's main branch as one ``preact_chain`` node and every other stride-1 conv through
+    ``conv2d(compute_dtype='bf16')``; the stem and the BatchNorms outside the Bottlenecks are the default's"""
     if x.requires_grad:
         raise _capi.RtposeError("train.forward_train of a HourglassNet: the stem has no data gradient; the image must not "
                                 "require a gradient")
     epoch, resync = _begin_bn_forward(model, "HourglassNet")
+    dt = 'bf16' if bottleneck else 'fp32'
 
     def conv(t, m):
         _check_same_conv(m)
-        return conv2d(t, m.weight, m.bias, False, epoch, resync)
+        return conv2d(t, m.weight, m.bias, False, epoch, resync, None, dt)
+
+    def block(blk, t):
+        convs = (blk.conv1, blk.conv2, blk.conv3)
+        for m in convs:
+            _check_same_conv(m)
+        out = preact_chain(t, [(b, m.weight, m.bias) for b, m in zip((blk.bn1, blk.bn2, blk.bn3), convs)], epoch, resync)
+        residual = conv(t, blk.downsample[0]) if blk.downsample is not None else t
+        return out + residual
 
     return hourglass_forward(model, x, conv, lambda t, m: batch_norm(t, m, relu=True),
-                             lambda t, m: conv7x7_s2(t, m.weight, m.bias, epoch, resync))
+                             lambda t, m: conv7x7_s2(t, m.weight, m.bias, epoch, resync), block if bottleneck else None)
 
 
 # ---- ShuffleNetV2 (lib/network/rtpose_shufflenetV2.py), written once over four callables -------------------------------------------
@@ -1489,7 +1727,8 @@ def _check_resident(who, resident):
             return True
     elif resident in (False, True):
         return False
-    raise _capi.RtposeError("%s: resident is False, True or 'dense'; got %r" % (who, resident))
+    raise _capi.RtposeError("%s: resident is False, True or 'dense'; got %r ('bottleneck' is forward_train's and train_step's "
+                            "fourth value, for an hourglass.HourglassNet)" % (who, resident))
 
 
 def forward_train(model, x, compute_dtype='fp32', resident=False):
@@ -1500,7 +1739,11 @@ def forward_train(model, x, compute_dtype='fp32', resident=False):
     ``conv_chain`` node whose inner activations and gradients stay in the layouts; refused for the other three (why: the
     message).  'dense', for an ``OpenPose_Model`` with ``compute_dtype='bf16'`` only - every ``StageBlock`` is one
     ``dense_stage`` node, feature_extractor runs as under ``run_sequential(resident=True)``; refused for the other three
-    and for 'fp32'.  Any other value is refused.  The default False is the per-conv path, launch for launch.
+    and for 'fp32'.  'bottleneck', for a ``HourglassNet`` in training mode with ``compute_dtype='bf16'`` only - the main
+    branch of every Bottleneck is one ``preact_chain`` node, ``downsample``, ``fc``, the score heads and the hand-over convs
+    run through ``conv2d(compute_dtype='bf16')``, ``bn1`` and the BatchNorm of ``fc`` through ``batch_norm``, the stem through
+    ``conv7x7_s2`` (fp32); refused for the other three and for 'fp32'.  Without it a ``HourglassNet`` takes no 'bf16'.  Any
+    other value is refused.  The default False is the per-conv path, launch for launch.
     ``RtposeVGG`` (lib/network/rtpose_vgg.py:158-198): ((out6_1, out6_2), saved_for_loss[12]).
     ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177):
     ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]).
@@ -1511,6 +1754,19 @@ def forward_train(model, x, compute_dtype='fp32', resident=False):
     ``conv3x3_s2``): ([PAF, HEAT], [PAF, HEAT]); running statistics and ``invalidate_weights()`` as for the hourglass."""
     _check_compute_dtype("train.forward_train", compute_dtype)
     kind = _model_kind(model, "train.forward_train")
+    if isinstance(resident, str) and resident == 'bottleneck':
+        if kind != 'hourglass':
+            raise _capi.RtposeError("train.forward_train: resident='bottleneck' is for an hourglass.HourglassNet only: "
+                                    "preact_chain runs the BatchNorm -> ReLU -> conv triples of its pre-activation Bottlenecks, "
+                                    "and a %s has none" % type(model).__name__)
+        if compute_dtype != 'bf16':
+            raise _capi.RtposeError("train.forward_train: resident='bottleneck' needs compute_dtype='bf16': preact_chain keeps "
+                                    "bf16 activations and gradients in the layouts, and an fp32 node is not built; got "
+                                    "compute_dtype=%r" % (compute_dtype,))
+        if not x.is_cuda:
+            raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there "
+                                    "is deliberately no CPU fallback" % (x.device,))
+        return _forward_train_hourglass(model, x, True)
     if compute_dtype != 'fp32' and kind in ('hourglass', 'shufflenet'):
         raise _capi.RtposeError("train.forward_train: compute_dtype=%r is for a network.RtposeVGG or an openpose.OpenPose_Model; "
                                 "the BatchNorm%s kernels a %s trains through are fp32 and take no compute dtype"
