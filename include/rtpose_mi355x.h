@@ -460,6 +460,50 @@ int rtpose_dwconv3x3_wgrad(const float* x, const rtpose_layout* lx, const float*
 int rtpose_dwconv3x3_dgrad(const float* gy, const rtpose_layout* lgy, const float* w, float* dx, const rtpose_layout* ldx, int C,
                            int N, int H, int W, int stride, void* stream);
 
+/* ---- 2b, continued.  The depthwise 3x3 conv of a layout-resident bf16 training run (train.unit_chain,
+ * train.dwconv3x3(compute_dtype='bf16')): the three kernels above with bf16 activations and gradients.  The taps, the
+ * bias, every accumulator and every OUTPUT stay fp32 - a BatchNorm in training mode reads the fp32 pre-activation on one
+ * side and writes an fp32-computed gradient on the other -, so each kernel differs from its fp32 form only in the element
+ * type it loads: a bf16 value is widened exactly, and the arithmetic, its order and its roundings are the fp32 kernel's.
+ * Each result therefore has the bits of the fp32 entry point run on the widened operands (rtpose_layout_bf16_to_f32).
+ * bf16 slices point at 2-byte elements and their layouts count ELEMENTS per pixel; their gaps are bf16 zeros.
+ *
+ * rtpose_dwconv3x3_bf16_f32 (csrc/shufflenet_ops.hip).  out = bias + sum over the taps of widen(in) * w, in fp32: from the
+ * bias, ky = 0, 1, 2 and within a row kx = 0, 1, 2, one rounding per product and one per add, never fused - the order of
+ * rtpose_dwconv3x3 at either stride, whose bits it gives on the widened input.  `in` / lin is H x W with a zero gap of at
+ * least 1, `out` / lout Ho x Wo fp32 (any gap; gaps are not written); `w` [9][C] and `bias` [C] fp32, neither NULL.  The
+ * doors of rtpose_dwconv3x3_bf16: C % 8 == 0, both bases 16-byte aligned, lin's cstride and choff multiples of 8 elements,
+ * lout's multiples of 4 floats, stride 1 or 2.  out must not overlap in.
+ *
+ * rtpose_dwconv3x3_wgrad_bf16 (csrc/dwconv_backward.hip).  rtpose_dwconv3x3_wgrad's scheme unchanged: the slabs of
+ * rtpose_dwconv3x3_wgrad_slabs(), fp64 terms, the fixed-order LDS sum, per-slab partials, the second launch in slab order;
+ * the workspace is rtpose_dwconv3x3_wgrad_workspace_doubles() doubles.  The product of two bf16 values is exact in fp64
+ * (16 significant bits).  `x` (zero gap >= 1) and `gy` (read at its valid pixels only) are bf16; dw, dbias fp32, OVERWRITTEN.
+ *
+ * rtpose_dwconv3x3_dgrad_bf16 (csrc/dwconv_backward.hip).  rtpose_dwconv3x3_dgrad's expression in its order, on a bf16
+ * `gy` (zero gap >= 1, of which only the ring of 1 is read), the fp32 [9][C] taps and an fp32 `dx`.
+ *
+ * The two backward forms accept any C >= 1 on slices of wider buffers.  A thread owns 4 channels, as in the fp32 kernels
+ * (one 8-byte load of 4 bf16; the data gradient stores 16 bytes), where every bf16 slice has an 8-byte-aligned base and a
+ * cstride and choff that are multiples of 4 elements (rtpose_prelu_bf16's rule) and the data gradient's dx a
+ * 16-byte-aligned base and a cstride and choff that are multiples of 4 floats; one channel otherwise.  (Units of 8
+ * channels, 16-byte loads, were measured for the data gradient and are slower at every depthwise shape of ShuffleNetV2;
+ * the weight gradient's 10 fp64 accumulators per channel leave no registers for them.)  A last unit with fewer than 4 live
+ * channels goes element by element.  The same bits in every form.  No scratch, no atomics: the same inputs give the same
+ * bits on every run.  Neighbouring channels and gaps are never written.
+ * Non-finite values: a NaN or an Inf of x / gy comes out where the fp32 kernel puts it.
+ * Every argument is checked on the host before any HIP call (RTPOSE_E_INVAL with a text), as the fp32 launchers check
+ * theirs: NULL pointers or layouts, C / N / H / W < 1, a stride other than 1 or 2, choff + C > cstride, a gap below 1
+ * where one is read, a layout smaller than its map, an odd base of a bf16 slice, a tensor above the launch limit, a
+ * workspace below the query's size, and memory that is not of the current device. */
+int rtpose_dwconv3x3_bf16_f32(const void* in, const rtpose_layout* lin, const float* w, const float* bias, float* out,
+                              const rtpose_layout* lout, int C, int N, int H, int W, int stride, void* stream);
+int rtpose_dwconv3x3_wgrad_bf16(const void* x, const rtpose_layout* lx, const void* gy, const rtpose_layout* lgy, float* dw,
+                                float* dbias, double* workspace, size_t workspace_doubles, int C, int N, int H, int W,
+                                int stride, void* stream);
+int rtpose_dwconv3x3_dgrad_bf16(const void* gy, const rtpose_layout* lgy, const float* w, float* dx, const rtpose_layout* ldx,
+                                int C, int N, int H, int W, int stride, void* stream);
+
 /* ---- 2b, continued.  Mixed-precision training: the weight gradient (+ bias gradient) of a stride-1 "same" conv,
  * k in {1, 3, 7}, from bf16 layout slices (csrc/conv_backward.hip; train.conv2d(compute_dtype='bf16')).  The forward
  * and the data gradient of such a step are rtpose_conv2d_bf16 (out_f32 = 1); this is the third kernel.  The reference has

@@ -269,6 +269,9 @@ _SIGS = {
     "rtpose_dwconv3x3_wgrad_slabs": (_i, [_i, _i, _i, _i, _i]),
     "rtpose_dwconv3x3_wgrad": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "rtpose_dwconv3x3_dgrad": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
+    "rtpose_dwconv3x3_bf16_f32": (_i, [_vp, _LP, _vp, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
+    "rtpose_dwconv3x3_wgrad_bf16": (_i, [_vp, _LP, _vp, _LP, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "rtpose_dwconv3x3_dgrad_bf16": (_i, [_vp, _LP, _vp, _vp, _LP, _i, _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),
     "rtpose_conv1x1_pair": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i, _i, _i, _i, _vp]),
     "rtpose_conv1x1_pair_bf16_fits": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _i]),

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "chan_slab.h"
 #include "pixel_walk.h"
 
 namespace rtpose {
@@ -338,9 +339,11 @@ __global__ void maxpool3x3s2_ceil_kernel(const T* __restrict__ src, Lay ls, T* _
 }
 
 // depthwise 3x3, pad 1 (the input layout's zero gaps), stride 1 or 2, + bias; w[9][C].
-template <class T>
+// O: the output's element type - T's, or float behind a bf16 input (the training forward of a layout-resident run, whose
+// BatchNorm reads the fp32 pre-activation: the accumulators are stored as they are, two 16-byte stores)
+template <class T, class O = T>
 __global__ void dwconv3x3_kernel(const T* __restrict__ in, Lay li, const float* __restrict__ w,
-                                 const float* __restrict__ bias, T* __restrict__ out, Lay lo, int C, int N, int Ho,
+                                 const float* __restrict__ bias, O* __restrict__ out, Lay lo, int C, int N, int Ho,
                                  int Wo, int stride) {
   typedef ChanVec<T> V;
   Walk q;
@@ -357,7 +360,14 @@ __global__ void dwconv3x3_kernel(const T* __restrict__ in, Lay li, const float* 
 #pragma unroll
       for (int e = 0; e < V::kLanes; ++e) acc.v[e] += v.v[e] * ww.v[e];
     }
-  acc.store(out + lay_off(lo, q) + q.c);
+  if constexpr (std::is_same<O, T>::value) {
+    acc.store(out + lay_off(lo, q) + q.c);
+  } else {
+    static_assert(V::kBf16 && std::is_same<O, float>::value, "bf16 in, fp32 out");
+    float* op = out + lay_off(lo, q) + q.c;
+    *reinterpret_cast<float4*>(op) = make_float4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+    *reinterpret_cast<float4*>(op + 4) = make_float4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]);
+  }
 }
 
 // depthwise 3x3, stride 1, fp32: FOUR consecutive output pixels of a row per thread.  The plain kernel
@@ -460,6 +470,36 @@ static int dwconv3x3(const char* who, const void* in_v, const rtpose_layout* lin
                      to_lay(lout), C, N, Ho, Wo, stride);
 }
 
+// rtpose_dwconv3x3_bf16_f32: the doors of rtpose_dwconv3x3_bf16, with every argument checked as the training launchers
+// check theirs (chan_slab.h)
+static int dwconv3x3_bf16_f32(const char* who, const void* in, const rtpose_layout* lin, const float* w, const float* bias,
+                              float* out, const rtpose_layout* lout, int C, int N, int H, int W, int stride, void* stream) {
+  if (stride != 1 && stride != 2) return fail(RTPOSE_E_INVAL, "%s: stride must be 1 or 2 (got %d)", who, stride);
+  long P;
+  if (int rc = check_shape(who, C, N, H, W, P)) return rc;
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  if (int rc = check_slice(who, "in", in, lin, C, H, W, 1)) return rc;
+  if (int rc = check_slice(who, "out", out, lout, C, Ho, Wo, 0)) return rc;
+  if (!w || !bias) return fail(RTPOSE_E_INVAL, "%s: NULL buffer (w or bias)", who);
+  if (C % 8) return fail(RTPOSE_E_INVAL, "%s: C must be a multiple of 8 (got %d)", who, C);
+  if (!slice_aligned(lin, 8) || reinterpret_cast<uintptr_t>(in) % 16 || !aligned16(*lout, out))
+    return fail(RTPOSE_E_INVAL, "%s: channel slices must be 16-byte aligned (in: base, cstride and choff multiples of 8 bf16 "
+                                "elements; out: of 4 floats)", who);
+  // (the kernel forms n * hs + y in an int)
+  if (rtpose_layout_pixels(lin, N, H, W) >= ((size_t)1 << 31) || rtpose_layout_pixels(lout, N, Ho, Wo) >= ((size_t)1 << 31))
+    return fail(RTPOSE_E_INVAL, "%s: tensor above the launch limit", who);
+
+  static thread_local CheckedPtr c_in, c_w, c_b, c_out;
+  const int dev = current_device();
+  int rc = c_in.check(in, dev, who, "in");
+  if (!rc) rc = c_w.check(w, dev, who, "w");
+  if (!rc) rc = c_b.check(bias, dev, who, "bias");
+  if (!rc) rc = c_out.check(out, dev, who, "out");
+  if (rc) return rc;
+  return launch_flat(dwconv3x3_kernel<unsigned short, float>, (size_t)N * Ho * Wo * (C / 8), stream,
+                     static_cast<const unsigned short*>(in), to_lay(lin), w, bias, out, to_lay(lout), C, N, Ho, Wo, stride);
+}
+
 }  // namespace rtpose
 
 using namespace rtpose;
@@ -545,6 +585,10 @@ int rtpose_dwconv3x3(const float* in, const rtpose_layout* lin, const float* w, 
 int rtpose_dwconv3x3_bf16(const void* in, const rtpose_layout* lin, const float* w, const float* bias, void* out,
                           const rtpose_layout* lout, int C, int N, int H, int W, int stride, void* stream) {
   return dwconv3x3<unsigned short>("dwconv3x3_bf16", in, lin, w, bias, out, lout, C, N, H, W, stride, stream);
+}
+int rtpose_dwconv3x3_bf16_f32(const void* in, const rtpose_layout* lin, const float* w, const float* bias, float* out,
+                              const rtpose_layout* lout, int C, int N, int H, int W, int stride, void* stream) {
+  return dwconv3x3_bf16_f32("dwconv3x3_bf16_f32", in, lin, w, bias, out, lout, C, N, H, W, stride, stream);
 }
 
 int rtpose_layout_copy_cmap(const float* src, const rtpose_layout* lsrc, float* dst, const rtpose_layout* ldst,

@@ -74,6 +74,14 @@ PyTorch keeps the graph and the optimizer; every convolution of it, forward and 
   writes relu(bn(.)) as bf16 straight into the gapped buffer the next conv reads and ``rtpose_bn_grad_bf16`` the bf16
   gradient the conv below reads.  No NCHW tensor and no fp32 BatchNorm output exists inside a run.  Opt-in.
 
+* Layout-resident branches (``unit_chain``; ``resident='branch'`` of ``forward_train`` and ``train_step``, shufflenet.Network
+  with ``compute_dtype='bf16'`` only): a run of conv -> BatchNorm (-> ReLU) units, the conv pointwise or depthwise 3x3, is one
+  autograd node.  Its pointwise launches are the per-conv bf16 path's (``out_f32 = 1``), its depthwise ones
+  ``rtpose_dwconv3x3_bf16_f32`` / ``_wgrad_bf16`` / ``_dgrad_bf16`` - bf16 activations, fp32 taps, fp32 outputs -; between them
+  ``rtpose_bn_apply_bf16`` writes bn(.) (+ ReLU) as bf16 straight into the gapped buffer the next op reads and
+  ``rtpose_bn_grad_bf16`` the bf16 gradient the op below reads.  ``dwconv3x3(compute_dtype='bf16')`` is the depthwise conv's
+  own bf16 node.  No NCHW tensor and no fp32 BatchNorm output exists inside a run.  Opt-in.
+
 On the default path the NCHW <-> layout conversion around every operation is known overhead.
 
 A non-finite activation reaches the loss: the entry points called here carry NaN and Inf through their sums and their
@@ -979,9 +987,45 @@ def _dw_taps(weight, cp):
     return taps, torch.zeros(cp, dtype=torch.float32, device=weight.device)
 
 
+def _dw_forward_into(bf16, xbuf, lx, taps, zero, cp, n, h, w, stride):
+    """rtpose_dwconv3x3 - `bf16`: rtpose_dwconv3x3_bf16_f32 on a bf16 buffer - of the first `cp` channels of a gapped layout
+    buffer into a new dense fp32 one: (buffer, layout)"""
+    name = "rtpose_dwconv3x3_bf16_f32" if bf16 else "rtpose_dwconv3x3"
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    ly = _capi.Layout.dense(cp, ho, wo)
+    ybuf = _buffer(ly, n, ho, wo, xbuf.device, False)
+    check(getattr(lib, name)(ptr(xbuf), C.byref(lx), ptr(taps), ptr(zero), ptr(ybuf), C.byref(ly), cp, n, h, w, stride,
+                             current_stream()), name)
+    return ybuf, ly
+
+
+def _dw_dgrad(bf16, gbuf, lg, taps, cp, n, h, w, stride):
+    """rtpose_dwconv3x3_dgrad - `bf16`: rtpose_dwconv3x3_dgrad_bf16 on a bf16 gradient - of `cp` channels into a new dense fp32
+    buffer of the conv's h x w input: (buffer, layout)"""
+    name = "rtpose_dwconv3x3_dgrad_bf16" if bf16 else "rtpose_dwconv3x3_dgrad"
+    ld = _capi.Layout.dense(cp, h, w)
+    dbuf = _buffer(ld, n, h, w, gbuf.device, False)
+    check(getattr(lib, name)(ptr(gbuf), C.byref(lg), ptr(taps), ptr(dbuf), C.byref(ld), cp, n, h, w, stride, current_stream()),
+          name)
+    return dbuf, ld
+
+
+def _dw_wgrad(bf16, xbuf, lx, gbuf, lg, like_weight, c, n, h, w, stride):
+    """rtpose_dwconv3x3_wgrad - `bf16`: rtpose_dwconv3x3_wgrad_bf16 on bf16 buffers - : dw shaped like `like_weight`, fp32"""
+    name = "rtpose_dwconv3x3_wgrad_bf16" if bf16 else "rtpose_dwconv3x3_wgrad"
+    dw = torch.empty_like(like_weight, memory_format=torch.contiguous_format)
+    doubles = lib.rtpose_dwconv3x3_wgrad_workspace_doubles(c, n, h, w, stride)
+    ws = torch.empty(doubles, dtype=torch.float64, device=gbuf.device)
+    check(getattr(lib, name)(ptr(xbuf), C.byref(lx), ptr(gbuf), C.byref(lg), ptr(dw), None, ptr(ws), doubles, c, n, h, w, stride,
+                             current_stream()), name)
+    return dw
+
+
 class _DwConv3x3(torch.autograd.Function):
+    """dwconv3x3's node.  With `bf16` the activations of all three kernels are bf16 (x and gy rounded as they enter, the
+    channels rounded up to 16); the taps, the outputs and the gradients are fp32 in both."""
     @staticmethod
-    def forward(ctx, x, weight, stride):
+    def forward(ctx, x, weight, stride, bf16):
         _require_device("train.dwconv3x3", x, weight)
         if stride not in (1, 2):
             raise _capi.RtposeError("train.dwconv3x3: stride must be 1 or 2; got %r" % (stride,))
@@ -993,14 +1037,12 @@ class _DwConv3x3(torch.autograd.Function):
         with torch.cuda.device(x.device):
             n, c, h, w = x.shape
             ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-            xbuf, lx = _to_layout(x.detach().contiguous(), 1)
+            xbuf, lx = _to_layout(x.detach().contiguous(), 1, bf16)
             taps, zero = _dw_taps(weight, lx.cstride)
-            ly = _capi.Layout.dense(lx.cstride, ho, wo)
-            ybuf = _buffer(ly, n, ho, wo, x.device, False)
-            check(lib.rtpose_dwconv3x3(ptr(xbuf), C.byref(lx), ptr(taps), ptr(zero), ptr(ybuf), C.byref(ly), lx.cstride, n, h, w,
-                                       stride, current_stream()), "rtpose_dwconv3x3")
+            ybuf, ly = _dw_forward_into(bf16, xbuf, lx, taps, zero, lx.cstride, n, h, w, stride)
             y = _from_layout(ybuf, ly, n, c, ho, wo)
         ctx.geom = (n, c, h, w, ho, wo, stride)
+        ctx.bf16 = bf16
         ctx.save_for_backward(weight)    # (for autograd's check that the filters were not modified in place since)
         ctx.xbuf, ctx.lx = (xbuf, lx) if ctx.needs_input_grad[1] else (None, None)
         ctx.taps = taps if ctx.needs_input_grad[0] else None
@@ -1014,31 +1056,30 @@ class _DwConv3x3(torch.autograd.Function):
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = dw = None
         with torch.cuda.device(gy.device):
-            stream = current_stream()
-            gbuf, lg = _to_layout(gy.detach().float().contiguous(), 1)
+            gbuf, lg = _to_layout(gy.detach().float().contiguous(), 1, ctx.bf16)
             if need_x:
-                ld = _capi.Layout.dense(lg.cstride, h, w)
-                dbuf = _buffer(ld, n, h, w, gy.device, False)
-                check(lib.rtpose_dwconv3x3_dgrad(ptr(gbuf), C.byref(lg), ptr(ctx.taps), ptr(dbuf), C.byref(ld), lg.cstride, n, h, w,
-                                                 stride, stream), "rtpose_dwconv3x3_dgrad")
+                dbuf, ld = _dw_dgrad(ctx.bf16, gbuf, lg, ctx.taps, lg.cstride, n, h, w, stride)
                 dx = _from_layout(dbuf, ld, n, c, h, w)
             if need_w:
-                dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-                doubles = lib.rtpose_dwconv3x3_wgrad_workspace_doubles(c, n, h, w, stride)
-                ws = torch.empty(doubles, dtype=torch.float64, device=gy.device)
-                check(lib.rtpose_dwconv3x3_wgrad(ptr(ctx.xbuf), C.byref(ctx.lx), ptr(gbuf), C.byref(lg), ptr(dw), None, ptr(ws),
-                                                 doubles, c, n, h, w, stride, stream), "rtpose_dwconv3x3_wgrad")
-        return dx, dw, None
+                dw = _dw_wgrad(ctx.bf16, ctx.xbuf, ctx.lx, gbuf, lg, weight, c, n, h, w, stride)
+        return dx, dw, None, None
 
 
-def dwconv3x3(x, weight, stride=1):
+def dwconv3x3(x, weight, stride=1, compute_dtype='fp32'):
     """``conv2d(x, weight, None, stride, 1, groups=C)`` of an ``nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False)``, stride 1
     or 2, with the library's kernels in both directions; NCHW fp32 device tensors, `weight` [C, 1, 3, 3].  Forward:
     ``rtpose_dwconv3x3`` on the channels rounded up to 8, with the taps permuted to its [9][C] packing by torch ops on the
     device on every call (9 C floats: nothing is cached, so nothing needs invalidating) and a zero bias.  Backward:
     ``rtpose_dwconv3x3_dgrad`` on the same taps and ``rtpose_dwconv3x3_wgrad`` on the kept layout copy of x, each only if its
-    gradient is needed."""
-    return _DwConv3x3.apply(x, weight, stride)
+    gradient is needed.
+    `compute_dtype`: 'fp32', the path above launch for launch, or 'bf16' for bf16 activations with fp32 taps and fp32
+    accumulation: x enters through ``rtpose_nchw_to_layout_bf16`` (round to nearest even, gap 1, channels rounded up to 16)
+    and is what is kept for the weight gradient, ``rtpose_dwconv3x3_bf16_f32`` writes a dense fp32 buffer that leaves as
+    NCHW fp32; gy enters through ``rtpose_nchw_to_layout_bf16`` (gap 1) and ``rtpose_dwconv3x3_dgrad_bf16`` /
+    ``rtpose_dwconv3x3_wgrad_bf16`` run, each only if its gradient is needed.  The two roundings are the only difference from
+    'fp32': parameters, outputs and gradients are fp32 either way (tests/dwconv_bf16_restate.py is the host emulation)."""
+    _check_compute_dtype("train.dwconv3x3", compute_dtype)
+    return _DwConv3x3.apply(x, weight, stride, compute_dtype == 'bf16')
 
 
 class _Conv3x3S2(torch.autograd.Function):
@@ -1402,6 +1443,273 @@ def preact_chain(x, layers, epoch=0, resync=False):
     return x
 
 
+# ---- a run of op -> BatchNorm -> (ReLU) units as one autograd node: a ShuffleNetV2 block's branch (bf16) -------------------------
+# runs that gave up residency because rtpose_conv2d_bf16 refused one of their forward convs
+unit_fallbacks = 0
+
+
+def reset_unit_fallbacks():
+    global unit_fallbacks
+    unit_fallbacks = 0
+
+
+class _UnitRefused(Exception):
+    """rtpose_conv2d_bf16 refused a forward conv of a run of units (before any launch of that conv)"""
+
+
+# the name _UnitChain launches its pointwise convs through, and nothing else does: replacing it plays a refusal of the node's
+# own launches and leaves alone the conv2d nodes the run falls back to (tests/test_train_branch_gpu.py)
+_unit_conv_into = _conv_launch
+
+
+def _unit_kind(m):
+    """'pw' for a pointwise nn.Conv2d (1x1, stride 1), 'dw' for a depthwise 3x3 (padding 1, stride 1 or 2, groups = channels,
+    no bias), None for anything else"""
+    if not isinstance(m, nn.Conv2d) or m.dilation != (1, 1) or m.padding_mode != 'zeros':
+        return None
+    if m.kernel_size == (1, 1) and m.stride == (1, 1) and m.padding == (0, 0) and m.groups == 1:
+        return 'pw'
+    if (m.kernel_size == (3, 3) and m.stride in ((1, 1), (2, 2)) and m.padding == (1, 1) and m.groups == m.in_channels
+            and m.out_channels == m.in_channels and m.bias is None):
+        return 'dw'
+    return None
+
+
+def _unit_out_size(m, h, w):
+    s = m.stride[0]
+    return (h - 1) // s + 1, (w - 1) // s + 1
+
+
+def _check_units(x, units):
+    who = "train.unit_chain"
+    if len(units) < 1:
+        raise _capi.RtposeError("%s: no units" % who)
+    for i, unit in enumerate(units):
+        if not isinstance(unit, tuple) or len(unit) != 3 or not isinstance(unit[0], nn.Module):
+            raise _capi.RtposeError("%s: units are (nn.Conv2d, nn.BatchNorm2d, relu) triples; got %r at %d"
+                                    % (who, type(unit).__name__, i))
+    _require_device(who, x, names=("x",))
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise _capi.RtposeError("%s takes an NCHW fp32 input; got %s %s" % (who, x.dtype, tuple(x.shape)))
+    n, c, h, w = x.shape
+    for i, (m, bn, _) in enumerate(units):
+        if _unit_kind(m) is None:
+            raise _capi.RtposeError("%s: unit %d: the op is a pointwise nn.Conv2d (1x1, stride 1) or a depthwise 3x3 (padding 1, "
+                                    "stride 1 or 2, groups = channels, no bias); got %r" % (who, i, m))
+        _require_device(who, m.weight, names=("a weight",))
+        if m.weight.dtype != torch.float32 or m.in_channels != c:
+            raise _capi.RtposeError("%s: unit %d: fp32 filters on the %d channels the unit before writes; got %r (%s)"
+                                    % (who, i, c, m, m.weight.dtype))
+        if m.bias is not None and (m.bias.dtype != torch.float32 or m.bias.device != m.weight.device):
+            raise _capi.RtposeError("%s: unit %d: the bias is None or an fp32 [%d] tensor beside the filters"
+                                    % (who, i, m.out_channels))
+        c = m.out_channels
+        h, w = _unit_out_size(m, h, w)
+        # (the BatchNorm's input has the op's n, c, h, w: a view of that shape stands for it)
+        _check_bn(x[:1, :1, :1, :1].expand(n, c, h, w), bn)
+        rm, rv = bn.running_mean, bn.running_var
+        if not (rm.is_contiguous() and rv.is_contiguous() and rm.dtype == rv.dtype == torch.float32):
+            raise _capi.RtposeError("%s: running_mean / running_var must be contiguous fp32 tensors" % who)
+
+
+class _UnitChain(torch.autograd.Function):
+    """unit_chain's node.  Inputs: x, (the conv modules, the BatchNorm modules, the ReLU flags, epoch, resync), then the
+    BatchNorm's weight and bias and the op's weight and bias (or None) of every unit."""
+    @staticmethod
+    def forward(ctx, x, meta, *params):
+        mods, bns, relus, epoch, resync = meta
+        gammas, betas, weights, biases = params[0::4], params[1::4], params[2::4], params[3::4]
+        L = len(mods)
+        kinds = [_unit_kind(m) for m in mods]
+        strides = [m.stride[0] for m in mods]
+        with torch.cuda.device(x.device):
+            stream = current_stream()
+            dev = x.device
+            n, _, h, w = x.shape
+            # what a refusal puts back: the kernels below update the running statistics, and the per-op run the node falls
+            # back to updates them again
+            stats = torch.cat([t for bn in bns for t in (bn.running_mean, bn.running_var)])
+            cur, lcur = _to_layout(x.detach().contiguous(), 1 if kinds[0] == 'dw' else 0, True)
+            xins, zs, saves, taps_of, sizes = [], [], [], [], []
+            y = None
+            for i in range(L):
+                wt = weights[i]
+                cout, c = wt.shape[0], lcur.cstride
+                if kinds[i] == 'dw':
+                    # (the first up8(C) channels of the buffer: the layout batch_norm gives the pre-activation)
+                    taps, zero = _dw_taps(wt, _up8(cout))
+                    z, lz = _dw_forward_into(True, cur, lcur, taps, zero, _up8(cout), n, h, w, strides[i])
+                else:
+                    taps = None
+                    wp, bp = _packed_for(wt, biases[i], 'fwd16', epoch, resync)
+                    lz = _capi.Layout.dense(_up8(cout), h, w)
+                    z = _buffer(lz, n, h, w, dev, False)
+                    if not _unit_conv_into(True, cur, lcur, wp, bp, c, cout, 1, False, n, h, w, z, lz, out_f32=1):
+                        for j, bn in enumerate(bns):
+                            cj = bn.num_features
+                            off = 2 * sum(b.num_features for b in bns[:j])
+                            bn.running_mean.copy_(stats[off:off + cj])
+                            bn.running_var.copy_(stats[off + cj:off + 2 * cj])
+                        raise _UnitRefused()
+                ho, wo = _unit_out_size(mods[i], h, w)
+                ws, doubles = _bn_workspace(cout, n, ho, wo, dev)
+                save = torch.empty(_capi.BN_SAVE_ROWS * cout, dtype=torch.float32, device=dev)
+                check(lib.rtpose_bn_stats(ptr(z), C.byref(lz), ptr(gammas[i].detach().contiguous()),
+                                          ptr(betas[i].detach().contiguous()), ptr(bns[i].running_mean),
+                                          ptr(bns[i].running_var), float(bns[i].momentum), float(bns[i].eps), ptr(save), ptr(ws),
+                                          doubles, cout, n, ho, wo, stream), "rtpose_bn_stats")
+                xins.append((cur, lcur)), zs.append((z, lz)), saves.append(save), taps_of.append(taps)
+                sizes.append((h, w, ho, wo))
+                relu = 1 if relus[i] else 0
+                if i + 1 < L:
+                    # bn(.) (+ ReLU) rounded straight into the buffer the next op reads: gapped for it, its pad channels zero
+                    la = _capi.Layout.padded(_up16(cout), ho, wo, 1 if kinds[i + 1] == 'dw' else 0)
+                    abuf = _buffer(la, n, ho, wo, dev, True, True)
+                    check(lib.rtpose_bn_apply_bf16(ptr(z), C.byref(lz), ptr(save), ptr(abuf), C.byref(la), relu, cout, n, ho, wo,
+                                                   stream), "rtpose_bn_apply_bf16")
+                    cur, lcur = abuf, la
+                else:
+                    ybuf = _buffer(lz, n, ho, wo, dev, False)
+                    check(lib.rtpose_bn_apply(ptr(z), C.byref(lz), ptr(save), ptr(ybuf), C.byref(lz), relu, cout, n, ho, wo,
+                                              stream), "rtpose_bn_apply")
+                    y = _from_layout(ybuf, lz, n, cout, ho, wo)
+                h, w = ho, wo
+            for bn in bns:
+                bn.num_batches_tracked.add_(1)
+        need = ctx.needs_input_grad
+        wants = [need[4 + 4 * i] or (biases[i] is not None and need[5 + 4 * i]) for i in range(L)]
+        wants_bn = [need[2 + 4 * i] or need[3 + 4 * i] for i in range(L)]
+        # the lowest unit whose backward anything needs: the walk stops there
+        low = 0 if need[0] else next((i for i in range(L) if wants[i] or wants_bn[i]), L)
+        ctx.n = n
+        ctx.meta = (kinds, strides, [bool(r) for r in relus], epoch, resync)
+        ctx.gammas, ctx.weights = gammas, weights
+        ctx.has_bias = [b is not None for b in biases]
+        ctx.low, ctx.wants = low, wants
+        ctx.save_for_backward(*(gammas + weights))   # (for autograd's check that none was modified in place since)
+        # per unit from `low` up: the fp32 pre-activation and the save rows its BatchNorm's backward reads, the bf16 input
+        # where a weight gradient reads it, the taps where a depthwise data gradient runs; nothing else
+        ctx.sizes = sizes
+        ctx.zs = [zs[i] if i >= low else None for i in range(L)]
+        ctx.saves = [saves[i] if i >= low else None for i in range(L)]
+        ctx.xins = [xins[i] if i >= low and wants[i] else None for i in range(L)]
+        ctx.taps = [taps_of[i] if (i > low or (i == low and need[0])) else None for i in range(L)]
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        kinds, strides, relus, epoch, resync = ctx.meta
+        ctx.saved_tensors
+        gammas, weights, low, wants = ctx.gammas, ctx.weights, ctx.low, ctx.wants
+        L = len(weights)
+        n = ctx.n
+        need = ctx.needs_input_grad
+        grads = [None] * (4 * L)
+        dx = None
+        if low >= L:
+            return (None, None) + tuple(grads)
+        with torch.cuda.device(gy.device):
+            dev = gy.device
+            stream = current_stream()
+            d, ld = _to_layout(gy.detach().float().contiguous(), 0)      # the fp32 gradient of the last BatchNorm's output
+            for i in range(L - 1, low - 1, -1):
+                wt = weights[i]
+                cout, cin = wt.shape[0], (wt.shape[0] if kinds[i] == 'dw' else wt.shape[1])
+                h, w, ho, wo = ctx.sizes[i]
+                need_d = i > low or need[0]          # the op's data gradient
+                need_g = need_d or wants[i]          # the bf16 gradient of the op's output
+                z, lz = ctx.zs[i]
+                ws, doubles = _bn_workspace(cout, n, ho, wo, dev)
+                dgam = torch.empty(cout, dtype=torch.float32, device=dev) if need[2 + 4 * i] else None
+                dbet = torch.empty(cout, dtype=torch.float32, device=dev) if need[3 + 4 * i] else None
+                g = lg = None
+                if need_g:
+                    # through the ReLU and the BatchNorm straight into the bf16 gradient the op's backward reads, gapped for it
+                    lg = _capi.Layout.padded(_up16(cout), ho, wo, 1 if kinds[i] == 'dw' else 0)
+                    g = _buffer(lg, n, ho, wo, dev, True, True)
+                check(lib.rtpose_bn_grad_bf16(ptr(z), C.byref(lz), ptr(d), C.byref(ld), ptr(ctx.saves[i]),
+                                              ptr(gammas[i].detach().contiguous()), 1 if relus[i] else 0, ptr(g),
+                                              C.byref(lg) if need_g else None, ptr(dgam), ptr(dbet), ptr(ws), doubles, cout, n,
+                                              ho, wo, stream), "rtpose_bn_grad_bf16")
+                grads[4 * i], grads[4 * i + 1] = dgam, dbet
+                if wants[i]:
+                    xin, lxin = ctx.xins[i]
+                    if kinds[i] == 'dw':
+                        grads[4 * i + 2] = _dw_wgrad(True, xin, lxin, g, lg, wt, cout, n, h, w, strides[i])
+                    else:
+                        need_b = ctx.has_bias[i] and need[5 + 4 * i]
+                        dw, db = _wgrad(True, xin, lxin, g, lg, wt, cin, cout, 1, n, h, w, need_b)
+                        grads[4 * i + 2] = dw if need[4 + 4 * i] else None
+                        grads[4 * i + 3] = db
+                if not need_d:
+                    break
+                # the data gradient into a dense fp32 buffer: the gy of the BatchNorm below
+                if kinds[i] == 'dw':
+                    d, ld = _dw_dgrad(True, g, lg, ctx.taps[i], _up8(cin), n, h, w, strides[i])
+                else:
+                    wp, bp = _packed_for(wt, None, 'bwd16', epoch, resync)
+                    ld = _capi.Layout.dense(_up8(cin), h, w)
+                    d = _buffer(ld, n, h, w, dev, False)
+                    if not _unit_conv_into(True, g, lg, wp, bp, lg.cstride, cin, 1, False, n, h, w, d, ld, out_f32=1):
+                        d, ld = _dgrad_fp32_fallback(g, lg, wt, n, h, w, epoch, resync)   # refused: this one conv in fp32
+                if i == 0:
+                    dx = _from_layout(d, ld, n, cin, h, w)
+        return (dx, None) + tuple(grads)
+
+
+def _unit_op(x, m, epoch, resync):
+    """the op of one unit through its own bf16 node"""
+    if _unit_kind(m) == 'dw':
+        return dwconv3x3(x, m.weight, m.stride[0], 'bf16')
+    return conv2d(x, m.weight, m.bias, False, epoch, resync, None, 'bf16')
+
+
+def unit_chain(x, units, epoch=0, resync=False):
+    """A run of L >= 1 units op -> BatchNorm (training mode) -> optional ReLU - a ShuffleNetV2 block's branch - as ONE
+    autograd node, bf16 operands.  `units`: (``nn.Conv2d``, ``nn.BatchNorm2d`` in training mode, relu) triples; the conv is a
+    pointwise one (1x1, stride 1, bias or none) or a depthwise 3x3 (padding 1, stride 1 or 2, groups = channels, no bias) on
+    the channels the unit before it writes; `x` NCHW fp32 on the device.  Returns the last unit's output, NCHW fp32.  The
+    BatchNorm checks are ``batch_norm``'s; `epoch` / `resync`: see ``conv2d``; the pointwise packings are the cached 'fwd16' /
+    'bwd16' ones, the depthwise taps are permuted on every call as ``dwconv3x3`` does.
+
+    Forward: x enters through one ``rtpose_nchw_to_layout_bf16``, gapped for the first op.  Per unit: the op writes a dense
+    fp32 pre-activation z - ``rtpose_conv2d_bf16(out_f32 = 1)`` or ``rtpose_dwconv3x3_bf16_f32`` -, ``rtpose_bn_stats`` runs on z
+    (the running statistics updated by the kernel, ``num_batches_tracked`` + 1, as ``batch_norm`` does) and
+    ``rtpose_bn_apply_bf16(relu)`` writes straight into the zero-initialised bf16 buffer the next op reads: gap 1 in front of a
+    depthwise conv, gap 0 in front of a pointwise one, the channels rounded up to 16.  The last unit runs ``rtpose_bn_apply``
+    (fp32) and leaves through one ``rtpose_layout_to_nchw``.  Kept per unit: the bf16 input where a weight gradient reads it,
+    the fp32 z and the ``save`` rows where the BatchNorm's backward runs; nothing else.
+    Backward (``once_differentiable``; any ``requires_grad`` subset of x, the filters and biases, the BatchNorm weights and
+    biases): gy enters once as an fp32 layout; per unit, top down, ``rtpose_bn_grad_bf16`` on the kept z writes the bf16
+    gradient the op's backward reads, gapped for it, and the BatchNorm's two parameter gradients; the op's weight gradient
+    is ``rtpose_conv2d_wgrad_bf16`` or ``rtpose_dwconv3x3_wgrad_bf16`` on the kept bf16 input, its data gradient
+    ``rtpose_conv2d_bf16(out_f32 = 1)`` on the 'bwd16' packing or ``rtpose_dwconv3x3_dgrad_bf16`` into a dense fp32 buffer,
+    the gy of the BatchNorm below.  The lowest op's data gradient leaves as NCHW fp32, only if x needs one.  The walk stops
+    at the lowest unit anything needs; a parameter gradient is computed only where it is required.
+
+    No rounding point moves against ``batch_norm(op(x, compute_dtype='bf16'), bn, relu)`` repeated L times, op being
+    ``conv2d`` or ``dwconv3x3``: the output, every gradient and the running statistics are equal to that composition's bit
+    for bit.
+
+    A forward conv ``rtpose_conv2d_bf16`` refuses (before launching) makes the run give up residency: the running statistics
+    the node has updated so far are put back, the run goes unit by unit through that composition - so every BatchNorm is
+    updated once - and ``unit_fallbacks`` counts it.  A refused data gradient runs that one conv in fp32 on the widened
+    gradient and is counted in ``bf16_fallbacks['dgrad']``."""
+    global unit_fallbacks
+    units = [tuple(unit) if isinstance(unit, (tuple, list)) else unit for unit in units]
+    _check_units(x, units)
+    epoch, resync = int(epoch), bool(resync)
+    meta = (tuple(m for m, _, _ in units), tuple(bn for _, bn, _ in units), tuple(bool(r) for _, _, r in units), epoch, resync)
+    try:
+        return _UnitChain.apply(x, meta, *[p for m, bn, _ in units for p in (bn.weight, bn.bias, m.weight, m.bias)])
+    except _UnitRefused:
+        unit_fallbacks += 1
+    for m, bn, relu in units:
+        x = batch_norm(_unit_op(x, m, epoch, resync), bn, relu=bool(relu))
+    return x
+
+
 def _check_same_conv(m):
     k = m.kernel_size[0]
     if m.kernel_size != (k, k) or m.stride != (1, 1) or m.padding != (k // 2, k // 2) or m.dilation != (1, 1) or m.groups != 1:
@@ -1634,12 +1942,14 @@ def shufflenet_block(blk, x, conv, bn, dw):
     return _channel_shuffle(x)
 
 
-def shufflenet_forward(model, x, conv, bn, dw, stem):
+def shufflenet_forward(model, x, conv, bn, dw, stem, block=None):
     """The reference's training-mode forward (lib/network/rtpose_shufflenetV2.py:56-63, :96-104, :144-148) over the module
     tree of a ``shufflenet.Network``, with the four operations as callables: ``conv(x, m)`` a pointwise ``nn.Conv2d`` m,
     ``bn(x, m, relu)`` an ``nn.BatchNorm2d`` m in training mode followed by a ReLU if `relu`, ``dw(x, m)`` a depthwise 3x3
     ``nn.Conv2d`` m of stride 1 or 2, ``stem(x, m)`` the 3x3 stride-2 ``stage1/conv``.  The split, ``torch.cat``, the channel
-    shuffle and ``MaxPool2d(3, 2, 0, ceil_mode=True)`` are torch's.  Returns ([PAF, HEAT], [PAF, HEAT])."""
+    shuffle and ``MaxPool2d(3, 2, 0, ceil_mode=True)`` are torch's.  `block`: None, or a callable ``block(m, x)`` that stands
+    for ``shufflenet_block(m, x, conv, bn, dw)`` of every block m and, for the conv -> BatchNorm -> ReLU ``nn.Sequential`` m in
+    front of the heads, for ``bn(conv(x, m[0]), m[1], True)``.  Returns ([PAF, HEAT], [PAF, HEAT])."""
     if not isinstance(model, ShuffleNetV2):
         raise TypeError("train.shufflenet_forward takes a shufflenet.Network; got %s" % type(model).__name__)
     if not model.training:
@@ -1652,20 +1962,36 @@ def shufflenet_forward(model, x, conv, bn, dw, stem):
     x = F.max_pool2d(x, pool.kernel_size, pool.stride, pool.padding, ceil_mode=pool.ceil_mode)
     for stage in (net[3], net[4], net[5]):
         for blk in stage:
-            x = shufflenet_block(blk, x, conv, bn, dw)
-    x = bn(conv(x, net[6][0]), net[6][1], True)
+            x = shufflenet_block(blk, x, conv, bn, dw) if block is None else block(blk, x)
+    x = bn(conv(x, net[6][0]), net[6][1], True) if block is None else block(net[6], x)
     paf = conv(x, model.paf)
     heat = conv(x, model.heatmap)
     return [paf, heat], [paf, heat]
 
 
-def _forward_train_shufflenet(model, x):
+def _forward_train_shufflenet(model, x, branch=False):
+    """`branch`: the conv branches of every block and the conv -> BatchNorm -> ReLU in front of the heads as ``unit_chain``
+    nodes, the two heads through ``conv2d(compute_dtype='bf16')``; ``data/bn``, the stem and its BatchNorm are the default's"""
     epoch, resync = _begin_bn_forward(model, "shufflenet.Network")
+    dt = 'bf16' if branch else 'fp32'
 
     def conv(t, m):
         if m.kernel_size != (1, 1) or m.stride != (1, 1) or m.padding != (0, 0) or m.dilation != (1, 1) or m.groups != 1:
             raise _capi.RtposeError("train: a pointwise conv of the ShuffleNetV2 tree is 1x1, stride 1; got %r" % (m,))
-        return conv2d(t, m.weight, m.bias, False, epoch, resync)
+        return conv2d(t, m.weight, m.bias, False, epoch, resync, None, dt)
+
+    def units(*seqs):
+        return [(seq[0], seq[1], len(seq) > 2) for seq in seqs]
+
+    def block(m, t):
+        if not hasattr(m, 'conv'):       # the conv -> BatchNorm -> ReLU in front of the heads
+            return unit_chain(t, units(m), epoch, resync)
+        if hasattr(m, 'conv0'):
+            t = torch.cat((unit_chain(t, units(*m.conv0), epoch, resync), unit_chain(t, units(*m.conv), epoch, resync)), 1)
+        else:
+            half = t.shape[1] // 2
+            t = torch.cat((t[:, :half], unit_chain(t[:, half:], units(*m.conv), epoch, resync)), 1)
+        return _channel_shuffle(t)
 
     def dw(t, m):
         s = m.stride[0]
@@ -1680,7 +2006,8 @@ def _forward_train_shufflenet(model, x):
             raise _capi.RtposeError("train: the ShuffleNetV2 stem is nn.Conv2d(3, 24, 3, 2, 1, bias=False); got %r" % (m,))
         return conv3x3_s2(t, m.weight, epoch, resync)
 
-    return shufflenet_forward(model, x, conv, lambda t, m, relu: batch_norm(t, m, relu=relu), dw, stem)
+    return shufflenet_forward(model, x, conv, lambda t, m, relu: batch_norm(t, m, relu=relu), dw, stem,
+                              block if branch else None)
 
 
 def _model_kind(model, who):
@@ -1728,7 +2055,8 @@ def _check_resident(who, resident):
     elif resident in (False, True):
         return False
     raise _capi.RtposeError("%s: resident is False, True or 'dense'; got %r ('bottleneck' is forward_train's and train_step's "
-                            "fourth value, for an hourglass.HourglassNet)" % (who, resident))
+                            "fourth value, for an hourglass.HourglassNet, and 'branch' their fifth, for a shufflenet.Network)"
+                            % (who, resident))
 
 
 def forward_train(model, x, compute_dtype='fp32', resident=False):
@@ -1742,8 +2070,14 @@ def forward_train(model, x, compute_dtype='fp32', resident=False):
     and for 'fp32'.  'bottleneck', for a ``HourglassNet`` in training mode with ``compute_dtype='bf16'`` only - the main
     branch of every Bottleneck is one ``preact_chain`` node, ``downsample``, ``fc``, the score heads and the hand-over convs
     run through ``conv2d(compute_dtype='bf16')``, ``bn1`` and the BatchNorm of ``fc`` through ``batch_norm``, the stem through
-    ``conv7x7_s2`` (fp32); refused for the other three and for 'fp32'.  Without it a ``HourglassNet`` takes no 'bf16'.  Any
-    other value is refused.  The default False is the per-conv path, launch for launch.
+    ``conv7x7_s2`` (fp32); refused for the other three and for 'fp32'.  Without it a ``HourglassNet`` takes no 'bf16'.
+    'branch', for a ``shufflenet.Network`` in training mode with ``compute_dtype='bf16'`` only - the three-unit ``conv`` branch
+    of every block, the two-unit ``conv0`` of a downsampling block and the conv -> BatchNorm -> ReLU in front of the heads are
+    one ``unit_chain`` node each, the two heads run through ``conv2d(compute_dtype='bf16')``, ``data/bn`` and the stem's
+    BatchNorm through ``batch_norm``, the stem through ``conv3x3_s2`` (fp32), and the split, ``torch.cat``, the channel shuffle
+    and the max-pool stay torch's; refused for the other three, for 'fp32', for a network in ``.eval()`` mode and for a CPU
+    tensor.  Without it a ``shufflenet.Network`` takes no 'bf16'.  Any other value is refused.  The default False is the
+    per-conv path, launch for launch.
     ``RtposeVGG`` (lib/network/rtpose_vgg.py:158-198): ((out6_1, out6_2), saved_for_loss[12]).
     ``OpenPose_Model`` (lib/network/openpose.py:86-109, :160-177):
     ([(paf[-2], heat[-2]), (paf[-1], heat[-1])], [paf_ret, heat_ret]).
@@ -1767,6 +2101,22 @@ def forward_train(model, x, compute_dtype='fp32', resident=False):
             raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there "
                                     "is deliberately no CPU fallback" % (x.device,))
         return _forward_train_hourglass(model, x, True)
+    if isinstance(resident, str) and resident == 'branch':
+        if kind != 'shufflenet':
+            raise _capi.RtposeError("train.forward_train: resident='branch' is for a shufflenet.Network only: unit_chain runs the "
+                                    "conv -> BatchNorm (-> ReLU) units of its blocks' branches, pointwise and depthwise, and a "
+                                    "%s has none" % type(model).__name__)
+        if compute_dtype != 'bf16':
+            raise _capi.RtposeError("train.forward_train: resident='branch' needs compute_dtype='bf16': unit_chain keeps bf16 "
+                                    "activations and gradients in the layouts, and an fp32 node is not built; got "
+                                    "compute_dtype=%r" % (compute_dtype,))
+        if not model.training:
+            raise _capi.RtposeError("train.forward_train: resident='branch' is the training-mode forward (batch statistics): "
+                                    "call .train() first; fine-tuning on frozen statistics (.eval()) is out of scope")
+        if not x.is_cuda:
+            raise _capi.RtposeError("train.forward_train runs only on an MI355X (HIP) device tensor; got a %s tensor - there "
+                                    "is deliberately no CPU fallback" % (x.device,))
+        return _forward_train_shufflenet(model, x, True)
     if compute_dtype != 'fp32' and kind in ('hourglass', 'shufflenet'):
         raise _capi.RtposeError("train.forward_train: compute_dtype=%r is for a network.RtposeVGG or an openpose.OpenPose_Model; "
                                 "the BatchNorm%s kernels a %s trains through are fp32 and take no compute dtype"
@@ -1818,7 +2168,8 @@ def train_step(model, optimizer, image, heat, paf, heat_mask=None, paf_mask=None
     RtposeVGG, ``encode.get_loss_openpose`` for an OpenPose_Model and, for a HourglassNet (train/train_SH.py:160-172),
     ``encode.get_loss_hourglass`` with the optional `heat_mask` / `paf_mask` (None: ones), for a shufflenet.Network
     (train/train_ShuffleNetV2.py:144-156) ``encode.get_loss_shufflenet`` with the same masks; the masks belong to those two
-    losses only.  `compute_dtype` / `resident`: see ``forward_train``; the optimizer steps the fp32 parameters either way."""
+    losses only.  `compute_dtype` / `resident` (False, True, 'dense', 'bottleneck' or 'branch'): see ``forward_train``; the
+    optimizer steps the fp32 parameters either way."""
     _check_compute_dtype("train.train_step", compute_dtype)
     kind = _model_kind(model, "train.train_step")
     if kind not in ('hourglass', 'shufflenet') and (heat_mask is not None or paf_mask is not None):
